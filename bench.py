@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- decode tokens/s of the fast-llama per-token hot path on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W [--pos P]      (N > 1: launched by torch.distributed.run, one process per GPU)
+  python bench.py --gpus N --steps K --warmup W [--pos P] [--full] [--dump-outputs DIR]   (N > 1: launched by torch.distributed.run, one process per GPU)
   python bench.py --config prefill512-int16                     (BASELINE config 5: the batched prompt path)
+
+A plain run sets up, warms up, times the K steps and prints the headline line; --full adds everything listed below.
+--dump-outputs DIR: after the timed steps, DIR/logits.npy (float32: the logits of the last timed step) and DIR/tokens.npy (float64: the
+ids of the K timed steps, the last one = argmax of those logits); with --config prefill<N>-..., DIR/tokens.npy holds the next token.
 
 One step = one greedy decode token of LLaMA2-7B int8 (synthetic weights, configs[2] of BASELINE.json) through the HIP path
 (fast-llama_amd/lib/libflm_gpu.so, C ABI include/flm_gpu.h).  All weights, the KV cache and the decode state are resident in HBM
@@ -16,7 +20,7 @@ replicas figure (N independent sequences, no data-path collective, "weak") is re
 run fails or decodes other ids than the reference on any rank, the line falls back to replicas and says so in `tp_note`.
 --parallel replicas measures the replicas only.
 
-Rank 0 prints ONE JSON line; besides the contract's keys it carries
+Rank 0 prints ONE JSON line; besides the contract's keys it carries, with --full,
   roofline       : dominant kernel (ffn13 GEMV) algorithmic bytes / its mean launch time measured live with HIP events on the ctx
                    stream, against the 8 TB/s HBM3E peak; traffic from the committed PMC summary under profiles/
   token_roofline : algorithmic bytes per token (weights + scales + norms + KV rows at the measured positions) x tokens/s vs 8 TB/s
@@ -24,6 +28,8 @@ Rank 0 prints ONE JSON line; besides the contract's keys it carries
   p50/p90        : per-token times of a second pass with one event per token
   cpu_baseline   : the reference's own CPU path (oracle/_ref/main, built from /root/reference by oracle/Makefile) timed on this
                    host's cores on a bounded sample (N = 1 only)
+and the long-context, 128-step and prefill operating points, BASELINE config 5 and (N > 1) the replicas figure.  N > 1 verifies every
+launch structure against the reference's ids whether or not --full is given: the headline is the fastest verified one.
 """
 from __future__ import annotations
 
@@ -270,10 +276,10 @@ def job_throughput(local_elapsed_s: float, steps: int, world: int, mode: str):
     return tokens / elapsed, elapsed
 
 
-def time_decode(ctx, cfg, args, prompt, barrier, gold):
+def time_decode(ctx, cfg, args, prompt, barrier, gold, verify=True):
     """prompt (untimed) -> greedy decode up to the start position (untimed; at least W steps, which also capture the
-    hipGraphs) -> EXACTLY K timed steps between barriers -> the ids for the parity field, and a second pass with an event
-    per token for the median.  Returns a dict of measurements."""
+    hipGraphs) -> EXACTLY K timed steps between barriers -> (--dump-outputs) what the last timed step computed; verify: the ids
+    for the parity field, and a second pass with an event per token for the median.  Returns a dict of measurements."""
     import torch
     # Every rank runs BOTH barriers whatever happens on it (a rank that raised before its barriers would leave the others in theirs while
     # it goes on to the caller's all-reduce: mismatched collectives, a hang instead of the fall-back to replicas); the error is re-raised
@@ -303,7 +309,13 @@ def time_decode(ctx, cfg, args, prompt, barrier, gold):
     barrier()
     if err is not None:
         raise err
-    ids += [int(x) for x in ctx.last_tokens(args.steps)]
+    timed_ids = [int(x) for x in ctx.last_tokens(args.steps)]
+    ids += timed_ids
+    res = {"wall_s": wall, "ms_dev": ms_dev, "pos": pos, "ids": ids}
+    if args.dump_outputs:     # (read before anything else runs on the context: the logits buffer still holds the last timed step's)
+        res["outputs"] = {"logits": ctx.debug_read("logits", 0, cfg.vocab_size), "tokens": np.asarray(timed_ids, dtype=np.float64)}
+    if not verify:
+        return res
     each = ctx.decode_timed_each(first, pos, args.steps)    # same tokens again (same cache rows), one event per token
     again = [int(x) for x in ctx.last_tokens(args.steps)]
     parity = {"against": None, "ids_checked": 0, "match": None, "replay_identical": again == ids[-args.steps:]}
@@ -313,8 +325,15 @@ def time_decode(ctx, cfg, args, prompt, barrier, gold):
         parity.update(against="greedy ids of the reference CPU path (oracle/_ref/libflref.so, ParallelTransformer::forward) on this model and prompt: "
                               f"{getattr(golden_ids, 'last', 'tests/golden')}; the same fixture's logits digests are checked bit for bit by tests/test_gpu_configs.py",
                       ids_checked=n, match=mism is None, first_mismatch=mism)
-    return {"wall_s": wall, "ms_dev": ms_dev, "pos": pos, "ids": ids, "parity": parity,
-            "p50_ms": float(np.median(each)), "p90_ms": float(np.percentile(each, 90)), "each_mean_ms": float(np.mean(each))}
+    res.update(parity=parity, p50_ms=float(np.median(each)), p90_ms=float(np.percentile(each, 90)), each_mean_ms=float(np.mean(each)))
+    return res
+
+
+def dump_outputs(path, outputs):
+    """--dump-outputs: one DIR/<name>.npy per array (float32 / float64, well under 64 MB)"""
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, f"{name}.npy"), a)
 
 
 def prefill_main(args):
@@ -343,6 +362,8 @@ def prefill_main(args):
     for _ in range(max(1, args.steps)):
         ctx.reset_kv(); ctx.sync(); torch.cuda.synchronize()
         t0 = time.perf_counter(); tok = ctx.forward_argmax(prompt, 0); times.append(time.perf_counter() - t0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"tokens": np.asarray([tok], dtype=np.float64)})
     dt = float(np.median(times))
     ctx.set_option("use_prefill", 0); ctx.reset_kv()
     tok_ref = ctx.forward_argmax(prompt, 0)                       # the same prompt, one token at a time through the decode kernels
@@ -384,7 +405,10 @@ def main():
     ap.add_argument("--prompt-len", type=int, default=9)
     ap.add_argument("--parallel", default="tp", choices=["replicas", "tp"],
                     help="N > 1: 'tp' (default) = ONE sequence, every matmul split by output rows over the GPUs (strong scaling, the headline value; "
-                         "the replicas figure is reported beside it); 'replicas' = one independent sequence per GPU only")
+                         "the replicas figure is reported beside it with --full); 'replicas' = one independent sequence per GPU only")
+    ap.add_argument("--full", action="store_true", help="besides the headline: parity against the reference's ids, p50 / p90, the long-context, 128-step and prefill "
+                                                        "operating points, per-kernel times and rooflines, BASELINE config 5, the replicas figure (N > 1) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (logits.npy float32, tokens.npy float64)")
     args = ap.parse_args()
     if args.config:
         return prefill_main(args)
@@ -424,7 +448,9 @@ def main():
     esz = 1 if qt == ff.QT_INT8 else 2
     cfg = synth.make_config(args.shape, qt)
     V = cfg.vocab_size
-    gold = golden_ids(cfg, qt, args.prompt_len)
+    full = args.full
+    verify = full or world > 1      # (N > 1: the headline is the fastest launch structure VERIFIED against the reference's ids)
+    gold = golden_ids(cfg, qt, args.prompt_len) if verify else None
 
     def prompt_for(seq):
         return np.array([1] + [int(x) for x in ((np.arange(1, args.prompt_len) + 131 * seq) * 7919) % V], dtype=np.int32)
@@ -460,7 +486,9 @@ def main():
         for kv in args.opt:
             ctx.set_option(kv.split("=")[0], int(kv.split("=")[1]))
         upload_synthetic(ctx, cfg)
-        m = time_decode(ctx, cfg, args, prompt_for(rank if mode == "replicas" else 0), barrier, gold if (mode == "single" or rank == 0) else None)
+        m = time_decode(ctx, cfg, args, prompt_for(rank if mode == "replicas" else 0), barrier, gold if (mode == "single" or rank == 0) else None, verify=verify)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, m["outputs"])
     tok_s, elapsed = job_throughput(m["wall_s"], args.steps, world, mode)
     pos = m["pos"]
     mid_pos = pos + args.steps // 2
@@ -469,7 +497,7 @@ def main():
     # a second operating point, outside the timed region of `value`: the same decode from position 512 ("also report at
     # pos ~ 512"): a 512-token prompt through the batched kernels, 4 untimed steps (graph capture), then K timed steps
     long_ctx = None
-    if mode == "single" and args.pos is None and rank == 0:
+    if full and mode == "single" and args.pos is None and rank == 0:
         try:
             lp = np.array([1] + [int(x) for x in (np.arange(1, 512) * 7919) % V], dtype=np.int32)
             lf = ctx.forward_argmax(lp, 0)
@@ -490,7 +518,7 @@ def main():
     # SURVEY.md 8d's decode protocol beside the driver's K timed steps (20 steps at positions 14..33 flatter the token by ~3 %: fewer cache rows): prompt = BOS + 8 tokens, 128 greedy
     # steps with one event per token, the first 8 discarded, mean and p50 over the other 120 (positions 17..136), with that span's own roofline fraction.  Outside the timed region of `value`.
     decode_128 = None
-    if mode == "single" and args.pos is None and rank == 0 and not args.no_decode128:
+    if full and mode == "single" and args.pos is None and rank == 0 and not args.no_decode128:
         try:
             p9 = prompt_for(0)
             ctx.reset_kv(); f9 = ctx.forward_argmax(p9, 0)
@@ -516,7 +544,7 @@ def main():
     # a third operating point, outside the timed region of `value`: BASELINE config 5's prompt path at this run's quant type -- a 512-token prompt through
     # the batched kernels (int8 GEMM tiles on the matrix cores, fp32-MFMA QK^T / PV), median of 3 forwards on a cleared cache
     prefill = None
-    if mode == "single" and args.pos is None and rank == 0:
+    if full and mode == "single" and args.pos is None and rank == 0:
         try:
             lp = np.array([1] + [int(x) for x in (np.arange(1, 512) * 7919) % V], dtype=np.int32)
             ctx.reset_kv(); ptok = ctx.forward_argmax(lp, 0)               # warm-up (group-major scale copies, first launches)
@@ -538,36 +566,38 @@ def main():
                                "the last layer's attention and FFN); peak = 3944 TOPS int8 MFMA (MI355X_MICROARCH.md) / 2; not part of `value`"}
         except Exception as e:  # noqa: BLE001
             prefill = {"error": str(e)}
-    # per-kernel times, live, HIP events on the ctx stream (eager launches, same kernels as the graph)
-    kt = ctx.kernel_times(mid_pos, iters=3)
-    # the dominant launch of the token: the fused FFN13 + FFN2 kernel where the token path runs it (single GPU), else FFN13
-    dom = next((k for k in ("token", "layers", "layer", "back", "ffn") if kt.get(k, (0.0, 0))[1] > 0), "ffn13")
-    dom_us, dom_cnt = kt[dom]
-    dom_bytes = ctx.kernel_bytes(dom, mid_pos)
-    achieved = dom_bytes / (dom_us * 1e-6) / 1e9 if dom_us > 0 else 0.0
-    try:
-        tpath = ctx.query("token_path")
-        token_path = {"resident": bool(ctx.query("resident")), "fell_back_after_timeout": bool(ctx.query("fallback")),
-                      "attn_wo_fused": bool(tpath & 1), "ffn_fused": bool(tpath & 2), "qkv_joins_at_long_contexts": bool(tpath & 4),
-                      "heads_split_at_long_contexts": bool(tpath & 64), "attention_to_ffn2_in_one_launch": bool(tpath & 128), "whole_layer_in_one_launch": bool(tpath & 256), "all_layers_in_one_launch": bool(tpath & 512) and kt.get("layers", (0.0, 0))[1] > 0,
-                      "whole_greedy_token_in_one_launch": bool(tpath & 1024) and kt.get("token", (0.0, 0))[1] > 0,
-                      "launches_per_token_short_context": (1 if (tpath & 1024 and kt.get("token", (0.0, 0))[1] > 0) else (1 if tpath & 512 and kt.get("layers", (0.0, 0))[1] > 0 else cfg.n_layers * (1 if tpath & 256 else 2 if tpath & 128 else 3)) + 3)}
-    except Exception as e:  # noqa: BLE001
-        token_path = {"error": str(e)}
-    try:
-        ao_active = ctx.query("ao_active")
-        token_path["wo_and_ffn2_consumed_in_arrival_order"] = ao_active == 3
-    except Exception:  # noqa: BLE001
-        ao_active = 0
+    kt = None
+    if full:
+        # per-kernel times, live, HIP events on the ctx stream (eager launches, same kernels as the graph)
+        kt = ctx.kernel_times(mid_pos, iters=3)
+        # the dominant launch of the token: the fused FFN13 + FFN2 kernel where the token path runs it (single GPU), else FFN13
+        dom = next((k for k in ("token", "layers", "layer", "back", "ffn") if kt.get(k, (0.0, 0))[1] > 0), "ffn13")
+        dom_us, dom_cnt = kt[dom]
+        dom_bytes = ctx.kernel_bytes(dom, mid_pos)
+        achieved = dom_bytes / (dom_us * 1e-6) / 1e9 if dom_us > 0 else 0.0
+        try:
+            tpath = ctx.query("token_path")
+            token_path = {"resident": bool(ctx.query("resident")), "fell_back_after_timeout": bool(ctx.query("fallback")),
+                          "attn_wo_fused": bool(tpath & 1), "ffn_fused": bool(tpath & 2), "qkv_joins_at_long_contexts": bool(tpath & 4),
+                          "heads_split_at_long_contexts": bool(tpath & 64), "attention_to_ffn2_in_one_launch": bool(tpath & 128), "whole_layer_in_one_launch": bool(tpath & 256), "all_layers_in_one_launch": bool(tpath & 512) and kt.get("layers", (0.0, 0))[1] > 0,
+                          "whole_greedy_token_in_one_launch": bool(tpath & 1024) and kt.get("token", (0.0, 0))[1] > 0,
+                          "launches_per_token_short_context": (1 if (tpath & 1024 and kt.get("token", (0.0, 0))[1] > 0) else (1 if tpath & 512 and kt.get("layers", (0.0, 0))[1] > 0 else cfg.n_layers * (1 if tpath & 256 else 2 if tpath & 128 else 3)) + 3)}
+        except Exception as e:  # noqa: BLE001
+            token_path = {"error": str(e)}
+        try:
+            ao_active = ctx.query("ao_active")
+            token_path["wo_and_ffn2_consumed_in_arrival_order"] = ao_active == 3
+        except Exception:  # noqa: BLE001
+            ao_active = 0
+        kernels = {k: {"us": round(v[0], 2), "per_token": v[1], "GBps": round(ctx.kernel_bytes(k, mid_pos) / (v[0] * 1e-6) / 1e9, 1) if v[0] > 0 else 0.0}
+                   for k, v in kt.items() if v[1] > 0}
     ctx_tp_info = getattr(ctx, "tp_info", None) or {}
-    kernels = {k: {"us": round(v[0], 2), "per_token": v[1], "GBps": round(ctx.kernel_bytes(k, mid_pos) / (v[0] * 1e-6) / 1e9, 1) if v[0] > 0 else 0.0}
-               for k, v in kt.items() if v[1] > 0}
     ctx.close()
 
     # BASELINE config 5 as stated (LLaMA2-7B int16 + a 512-token prompt), outside the timed region of `value`: a second context with the int16 checkpoint, the prompt
     # through the batched path, the next token checked against the reference's (tests/golden/model_7B_int16_L32.npz)
     config5 = None
-    if mode == "single" and args.pos is None and rank == 0 and args.shape == "7B" and qt == ff.QT_INT8 and not args.no_config5:
+    if full and mode == "single" and args.pos is None and rank == 0 and args.shape == "7B" and qt == ff.QT_INT8 and not args.no_config5:
         try:
             cfg16 = synth.make_config("7B", ff.QT_INT16)
             c16 = capi.Ctx(capi.desc_from_config(cfg16), device=device)
@@ -588,7 +618,7 @@ def main():
 
     # ---- N > 1: the replicas figure beside the tensor-parallel headline (one independent sequence per GPU, no collective) ----
     replicas = None
-    if mode == "tp":
+    if full and mode == "tp":
         try:
             rctx = capi.Ctx(capi.desc_from_config(cfg), device=device)
             upload_synthetic(rctx, cfg)
@@ -600,25 +630,25 @@ def main():
         except Exception as e:  # noqa: BLE001
             replicas = {"value": None, "note": f"failed: {e}"}
 
-    qn = 2 if qt == ff.QT_INT8 else 1
-    split_now = bool(token_path.get("heads_split_at_long_contexts")) and mid_pos + 1 >= 128      # (the launch's SPLIT instantiation: a head spread over hs / 32 workgroups)
-    # (round 5: k_layers<QT, XR2, SPLIT, R5>, R5 = 3 where the launch consumes Wo's / FFN2's activation in arrival order -- the instantiation this run launched, not just any in the library)
-    r5_now = 3 if (dom in ("layers", "token") and ao_active > 0) else 0
-    dom_regex = {"token": rf"k_layers<{qn}, \d+, {'true' if split_now else 'false'}, {r5_now}, true(?:, \w+)*>", "layers": rf"k_layers<{qn}, \d+, {'true' if split_now else 'false'}, {r5_now}, false(?:, \w+)*>", "layer": rf"k_attn_ffn<{qn}, \d+, true, false>", "back": rf"k_attn_ffn<{qn}, \d+, false, false>", "ffn": rf"k_ffn<{qn},"}.get(dom, rf"k_gemv<{qn}, 2, 2,")
-    if args.shape == "7B":
-        traffic, traffic_src, traffic_note = pmc_traffic(dom_regex, capi.LIB_PATH)
-    else:   # (the committed PMC summaries were collected on the 7B-shaped model: a launch of the same kernel on another shape moves other bytes)
-        traffic, traffic_src, traffic_note = None, None, "PMC summaries under profiles/ are of the LLaMA2-7B shape"
+    if full:
+        qn = 2 if qt == ff.QT_INT8 else 1
+        split_now = bool(token_path.get("heads_split_at_long_contexts")) and mid_pos + 1 >= 128      # (the launch's SPLIT instantiation: a head spread over hs / 32 workgroups)
+        # (round 5: k_layers<QT, XR2, SPLIT, R5>, R5 = 3 where the launch consumes Wo's / FFN2's activation in arrival order -- the instantiation this run launched, not just any in the library)
+        r5_now = 3 if (dom in ("layers", "token") and ao_active > 0) else 0
+        dom_regex = {"token": rf"k_layers<{qn}, \d+, {'true' if split_now else 'false'}, {r5_now}, true(?:, \w+)*>", "layers": rf"k_layers<{qn}, \d+, {'true' if split_now else 'false'}, {r5_now}, false(?:, \w+)*>", "layer": rf"k_attn_ffn<{qn}, \d+, true, false>", "back": rf"k_attn_ffn<{qn}, \d+, false, false>", "ffn": rf"k_ffn<{qn},"}.get(dom, rf"k_gemv<{qn}, 2, 2,")
+        if args.shape == "7B":
+            traffic, traffic_src, traffic_note = pmc_traffic(dom_regex, capi.LIB_PATH)
+        else:   # (the committed PMC summaries were collected on the 7B-shaped model: a launch of the same kernel on another shape moves other bytes)
+            traffic, traffic_src, traffic_note = None, None, "PMC summaries under profiles/ are of the LLaMA2-7B shape"
 
-    dom_name = {"token": f"k_layers<{args.quant}, TAIL> (the WHOLE greedy token in one launch: the embedding row read by the first layer, ALL {cfg.n_layers} decoder layers -- per layer QKV + RoPE, attention, "
-                         f"Wo + residual, FFN13 + SwiGLU, FFN2 + residual --, final norm + classifier, argmax + state advance; every edge a flag round)",
-                "layers": f"k_layers<{args.quant}> (ALL {cfg.n_layers} decoder layers of the token in one launch: per layer QKV + RoPE, attention, Wo + residual, FFN13 + SwiGLU, FFN2 + residual; "
-                          f"the edges between phases and between layers are flag rounds)",
-                "layer": f"k_attn_ffn<{args.quant}, QKV> (the whole decoder layer in one launch: QKV + RoPE, attention, Wo + residual, FFN13 + SwiGLU, FFN2 + residual)",
-                "back": f"k_attn_ffn<{args.quant}> (attention, Wo + residual, FFN13 + SwiGLU, FFN2 + residual in one launch)",
-                "ffn": f"k_ffn<{args.quant}> (ffn13 + SwiGLU and ffn2 + residual in one launch)"}.get(dom, f"k_gemv<{args.quant},rmsnorm+quantize,swiglu> (ffn13)")
+        dom_name = {"token": f"k_layers<{args.quant}, TAIL> (the WHOLE greedy token in one launch: the embedding row read by the first layer, ALL {cfg.n_layers} decoder layers -- per layer QKV + RoPE, attention, "
+                             f"Wo + residual, FFN13 + SwiGLU, FFN2 + residual --, final norm + classifier, argmax + state advance; every edge a flag round)",
+                    "layers": f"k_layers<{args.quant}> (ALL {cfg.n_layers} decoder layers of the token in one launch: per layer QKV + RoPE, attention, Wo + residual, FFN13 + SwiGLU, FFN2 + residual; "
+                              f"the edges between phases and between layers are flag rounds)",
+                    "layer": f"k_attn_ffn<{args.quant}, QKV> (the whole decoder layer in one launch: QKV + RoPE, attention, Wo + residual, FFN13 + SwiGLU, FFN2 + residual)",
+                    "back": f"k_attn_ffn<{args.quant}> (attention, Wo + residual, FFN13 + SwiGLU, FFN2 + residual in one launch)",
+                    "ffn": f"k_ffn<{args.quant}> (ffn13 + SwiGLU and ffn2 + residual in one launch)"}.get(dom, f"k_gemv<{args.quant},rmsnorm+quantize,swiglu> (ffn13)")
     if rank == 0:
-        tb = token_bytes(cfg, mid_pos, esz)
         line = {
             "metric": "decode tokens/s LLaMA2-7B int8" if args.shape == "7B" and qt == ff.QT_INT8 else f"decode tokens/s {args.shape} {args.quant}",
             "value": round(tok_s, 2), "unit": "tokens/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -630,26 +660,30 @@ def main():
                        "parallelism": {"single": "single-gpu", "tp": f"tp{world}: ONE sequence, every matmul split by output rows over {world} GPUs, activation slices exchanged by " + (getattr(ctx, "exchange", "") if mode == "tp" else ""),
                                        "replicas": f"{world} replicas: one independent sequence per GPU, no data-path collective"}[mode],
                        "device_ms_per_step": round(m["ms_dev"] / args.steps, 4), **({"options": args.opt} if args.opt else {})},
-            "p50_ms_per_step": round(m["p50_ms"], 4), "p90_ms_per_step": round(m["p90_ms"], 4),
-            "parity": m["parity"],
-            # per GPU: bytes each GPU streams per token it works on, at the rate it produces them
-            "token_roofline": {"bytes_per_token": int(tb / tp), "peak": HBM_PEAK_GBS, "unit": "GB/s per GPU", "pos": mid_pos,
-                               "achieved": round(tb / tp * (tok_s / (world / tp)) / 1e9, 1),
-                               "frac": round(tb / tp * (tok_s / (world / tp)) / 1e9 / HBM_PEAK_GBS, 4)},
-            "roofline": {"kernel": dom_name,
-                         "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src, "traffic_note": traffic_note,
-                         "bytes_per_launch": int(dom_bytes), "avg_launch_us": round(dom_us, 2), "launches_per_token": dom_cnt,
-                         **({"layers_per_launch": cfg.n_layers, "us_per_layer": round(dom_us / cfg.n_layers, 2)} if dom == "layers" else {}),
-                         **({"layers_per_launch": cfg.n_layers, "layers_alone_us": round(kt.get("layers", (0.0, 0))[0], 2), "us_per_layer": round(kt.get("layers", (0.0, 0))[0] / cfg.n_layers, 2),
-                             "note": "the whole greedy token is this one launch: bytes = the layers' + the classifier's + the embedding row; `layers_alone_us` = the same layers as a launch of their own (k_layers<.., TAIL = false>)"} if dom == "token" else {})},
-            "token_path": token_path,
-            "kernels": kernels,
-            "kernels_note": "us per launch, back-to-back launches of one class between one pair of HIP events; on a single GPU a greedy token runs `token` (k_layers<.., TAIL>: embedding row, all L decoder "
-                            "layers, classifier, argmax in ONE launch) where it is listed; else `layers` (k_layers: all L decoder layers in one launch): per token = embed + layers + cls + argmax; else `layer` (k_attn_ffn: one launch per layer; timed beside it); else attn_wo (k_attn_o) instead of attn + attn_o and ffn "
-                            "(k_ffn) instead of ffn13 + ffn2, and where qkv_attn_wo (k_qkv_attn_o: contexts from 128 positions on) is listed, that instead of qkv + attn_wo; the "
-                            "per-phase classes (qkv .. ffn2) are timed beside them for reference",
         }
+        if verify:
+            line.update({"p50_ms_per_step": round(m["p50_ms"], 4), "p90_ms_per_step": round(m["p90_ms"], 4), "parity": m["parity"]})
+        if full:
+            tb = token_bytes(cfg, mid_pos, esz)
+            line.update({
+                # per GPU: bytes each GPU streams per token it works on, at the rate it produces them
+                "token_roofline": {"bytes_per_token": int(tb / tp), "peak": HBM_PEAK_GBS, "unit": "GB/s per GPU", "pos": mid_pos,
+                                   "achieved": round(tb / tp * (tok_s / (world / tp)) / 1e9, 1),
+                                   "frac": round(tb / tp * (tok_s / (world / tp)) / 1e9 / HBM_PEAK_GBS, 4)},
+                "roofline": {"kernel": dom_name,
+                             "bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src, "traffic_note": traffic_note,
+                             "bytes_per_launch": int(dom_bytes), "avg_launch_us": round(dom_us, 2), "launches_per_token": dom_cnt,
+                             **({"layers_per_launch": cfg.n_layers, "us_per_layer": round(dom_us / cfg.n_layers, 2)} if dom == "layers" else {}),
+                             **({"layers_per_launch": cfg.n_layers, "layers_alone_us": round(kt.get("layers", (0.0, 0))[0], 2), "us_per_layer": round(kt.get("layers", (0.0, 0))[0] / cfg.n_layers, 2),
+                                 "note": "the whole greedy token is this one launch: bytes = the layers' + the classifier's + the embedding row; `layers_alone_us` = the same layers as a launch of their own (k_layers<.., TAIL = false>)"} if dom == "token" else {})},
+                "token_path": token_path,
+                "kernels": kernels,
+                "kernels_note": "us per launch, back-to-back launches of one class between one pair of HIP events; on a single GPU a greedy token runs `token` (k_layers<.., TAIL>: embedding row, all L decoder "
+                                "layers, classifier, argmax in ONE launch) where it is listed; else `layers` (k_layers: all L decoder layers in one launch): per token = embed + layers + cls + argmax; else `layer` (k_attn_ffn: one launch per layer; timed beside it); else attn_wo (k_attn_o) instead of attn + attn_o and ffn "
+                                "(k_ffn) instead of ffn13 + ffn2, and where qkv_attn_wo (k_qkv_attn_o: contexts from 128 positions on) is listed, that instead of qkv + attn_wo; the "
+                                "per-phase classes (qkv .. ffn2) are timed beside them for reference"
+            })
         if decode_128 is not None:
             line["decode_128"] = decode_128
         if long_ctx is not None:
@@ -663,8 +697,9 @@ def main():
         if mode == "tp" and ctx_tp_info:
             # (c) of the review's multi-GPU item: who ran, over what, and what an exchange costs (HIP events around the exchange launches / collectives of a timed token)
             info = dict(ctx_tp_info)
-            ar = kt.get("allreduce", (0.0, 0))
-            info["exchange_us"] = round(ar[0], 2); info["exchanges_per_token"] = ar[1]
+            if kt is not None:
+                ar = kt.get("allreduce", (0.0, 0))
+                info["exchange_us"] = round(ar[0], 2); info["exchanges_per_token"] = ar[1]
             info["scaling_measured"] = info["distinct_devices"] == world
             if tp_structures is not None:
                 best = pick_tp_structure(tp_structures)
@@ -674,7 +709,7 @@ def main():
             line["tp"] = info
         if tp_note:
             line["tp_note"] = tp_note
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(cfg)
             except Exception as e:  # noqa: BLE001

@@ -8,8 +8,14 @@ os.environ.setdefault("OMP_NUM_THREADS", str(max(1, min(8, os.cpu_count() or 1))
 os.environ.setdefault("OMP_WAIT_POLICY", "passive")
 # tests/test_gpu_tp.py runs up to 8 tensor-parallel ranks as 8 streams of ONE process on ONE GPU; their flag waits need one hardware
 # queue per stream (HIP's default is 4 per process: two streams sharing a queue would put a waiting kernel in front of the kernel
-# it waits for).  Read once, when the HIP runtime starts.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+# it waits for).  Read once, when the HIP runtime starts.  Raised, not defaulted: an environment that already sets a smaller value (4 is
+# common) would otherwise leave 4 or 8 ranks sharing 4 queues and their flag waits deadlock.
+try:
+    _queues = int(os.environ.get("GPU_MAX_HW_QUEUES", "0"))
+except ValueError:
+    _queues = 0
+if _queues < 16:
+    os.environ["GPU_MAX_HW_QUEUES"] = "16"
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

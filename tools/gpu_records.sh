@@ -2,16 +2,16 @@
 # round 6's records in one gpurun call: everything lands in gpurun_out/r06/ and is copied into profiles/ by hand
 O=gpurun_out/r06; mkdir -p $O
 (timeout 1500 python -m pytest tests -m gpu -q --durations=10 > $O/r06_gputests.log 2>&1; echo rc=$? >> $O/r06_gputests.log); grep -n "passed\|failed" $O/r06_gputests.log | tail -2
-python bench.py --steps 20 --warmup 5 > $O/r06_bench_n1_steps20.json 2> $O/bench20.err; cut -c1-120 $O/r06_bench_n1_steps20.json
-python bench.py > $O/r06_bench_n1.json 2> $O/bench128.err; cut -c1-120 $O/r06_bench_n1.json
+python bench.py --full --steps 20 --warmup 5 > $O/r06_bench_n1_steps20.json 2> $O/bench20.err; cut -c1-120 $O/r06_bench_n1_steps20.json
+python bench.py --full > $O/r06_bench_n1.json 2> $O/bench128.err; cut -c1-120 $O/r06_bench_n1.json
 bash tools/prof_bench.sh --steps 20 --warmup 5 > $O/prof_bench.txt 2>&1; cp gpurun_out/prof_bench/run_kernel_stats.csv $O/r06_bench_kernel_stats.csv; cp gpurun_out/prof_bench/bench.json $O/r06_bench_under_rocprof.json; head -8 $O/prof_bench.txt
 bash tools/pmc_bench.sh > $O/pmc_bench.txt 2>&1; cp gpurun_out/pmc/pmc_fetch_write_raw.json $O/r06_pmc_fetch_write_raw.json; tail -6 $O/pmc_bench.txt
-for n in 2 4; do FLM_BENCH_FORCE_DEVICE=0 GPU_MAX_HW_QUEUES=16 timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port 2960$n bench.py --gpus $n --steps 10 --warmup 3 --no-cpu-baseline 2> $O/tp$n.err | grep '^{"metric' > $O/r06_bench_tp${n}_one_gpu.json; cut -c1-120 $O/r06_bench_tp${n}_one_gpu.json; done
+for n in 2 4; do FLM_BENCH_FORCE_DEVICE=0 GPU_MAX_HW_QUEUES=16 timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port 2960$n bench.py --gpus $n --steps 10 --warmup 3 --full --no-cpu-baseline 2> $O/tp$n.err | grep '^{"metric' > $O/r06_bench_tp${n}_one_gpu.json; cut -c1-120 $O/r06_bench_tp${n}_one_gpu.json; done
 for w in 2 4 8; do GPU_MAX_HW_QUEUES=16 timeout 400 python tools/tp_onegpu.py $w 4 64 2>&1 | grep -v Warning; done > $O/r06_tp_onegpu.txt; cut -c1-170 $O/r06_tp_onegpu.txt
 (FLM_GPU_LIB=fast-llama_amd/lib/var/libflm_abl.so python tools/trace_back.py 4 14 "" 103; FLM_GPU_LIB=fast-llama_amd/lib/var/libflm_abl.so python tools/trace_back.py 4 14 "tuning=1,gr_edges=0" 103; FLM_GPU_LIB=fast-llama_amd/lib/var/libflm_abl.so python tools/trace_back.py 4 516 "" 103) > $O/r06_layer_timelines.txt 2>&1; grep -c "" $O/r06_layer_timelines.txt
-python bench.py --steps 20 --warmup 5 --quant int16 --no-cpu-baseline > $O/r06_bench_int16.json 2>/dev/null; cut -c1-120 $O/r06_bench_int16.json
-python bench.py --steps 20 --warmup 5 --shape 1.3B --no-cpu-baseline > $O/r06_bench_1p3B.json 2>/dev/null; cut -c1-120 $O/r06_bench_1p3B.json
-python bench.py --steps 20 --warmup 5 --pos 512 --no-cpu-baseline > $O/r06_bench_pos512.json 2>/dev/null; cut -c1-120 $O/r06_bench_pos512.json
+python bench.py --full --steps 20 --warmup 5 --quant int16 --no-cpu-baseline > $O/r06_bench_int16.json 2>/dev/null; cut -c1-120 $O/r06_bench_int16.json
+python bench.py --full --steps 20 --warmup 5 --shape 1.3B --no-cpu-baseline > $O/r06_bench_1p3B.json 2>/dev/null; cut -c1-120 $O/r06_bench_1p3B.json
+python bench.py --full --steps 20 --warmup 5 --pos 512 --no-cpu-baseline > $O/r06_bench_pos512.json 2>/dev/null; cut -c1-120 $O/r06_bench_pos512.json
 (timeout 900 python tools/soak32.py 1000 2; timeout 600 python tools/stress2.py 200; timeout 600 python tools/fuzz_shapes.py 30 7 0; timeout 600 python tools/fuzz_shapes.py 12 9 1) > $O/r06_fuzz_stress.txt 2>&1; tail -12 $O/r06_fuzz_stress.txt
 bash tools/pmc_prefill.sh > $O/pmc_prefill.txt 2>&1; tail -4 $O/pmc_prefill.txt
 python3 tools/pmc_agg.py gpurun_out/pmc/p1 gpurun_out/pmc/p2 gpurun_out/pmc/p3 > gpurun_out/pmc/prefill_counters.json 2>/dev/null
