@@ -28,7 +28,8 @@ SYMBOLS = (
 )
 
 
-TUNING_KEYS = ("wg_per_cu", "use_mfma", "tok_preq", "tok_nstq", "back_nst13", "back_nst13_head", "back_nst2", "back_pre13", "back_pre2", "back_ao2", "inject_wait_failure")   # csrc/flm_tuning.h
+# the experiment dials: the kOptDial rows of csrc/flm_tuning.h, in its order (tests/test_capi_host.py compares)
+TUNING_KEYS = ("wg_per_cu", "inject_wait_failure", "use_mfma", "tok_nstq", "tok_preq", "back_nst13", "back_nst13_head", "back_nst2", "back_pre13", "back_pre2", "back_ao2", "back_nwo", "attn_kpre")
 
 
 class FlmError(RuntimeError):

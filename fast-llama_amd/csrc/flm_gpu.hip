@@ -13,6 +13,30 @@ thread_local std::string g_last_error;
 int fail(flm_ctx* c, int code, const char* msg) { if (c) c->err = msg; g_last_error = msg; return code; }
 
 int prepare_all(flm_ctx* c);
+// graphs captured under a launch structure that no longer holds must not be replayed; with_args: k_layers' argument blocks are rebuilt as well
+static void drop_graphs(flm_ctx* c, bool with_args) {
+    for (auto& g : c->graphs) hipGraphExecDestroy(g.second);
+    c->graphs.clear();
+    if (with_args) c->la_valid[0] = c->la_valid[1] = false;
+}
+// device memory that lives as long as the context: recorded in c->owned, which flm_ctx_destroy frees (zero: cleared on the context's stream)
+template <class T> static hipError_t dev_alloc(flm_ctx* c, T** p, size_t bytes, bool zero = false) {
+    const hipError_t e = hipMalloc((void**)p, bytes); if (e != hipSuccess) return e;
+    c->owned.push_back(*p);
+    return zero ? hipMemsetAsync(*p, 0, bytes, c->stream) : hipSuccess;
+}
+static hipError_t clear_kv(flm_ctx* c) {
+    const size_t kvn = (size_t)c->d.n_layers * c->heads_local * c->kv_rows * c->hs;
+    const hipError_t ek = hipMemsetAsync(c->kcache, 0, kvn * 4, c->stream), ev = hipMemsetAsync(c->vcache, 0, kvn * 4, c->stream);
+    return ek != hipSuccess ? ek : ev;
+}
+// "An error in here is not the caller's": what flm_last_error said before a best-effort step (prepare_all, warm_up), put back when the step failed -- the error resurfaces
+// at the first forward
+struct SavedError {
+    flm_ctx* c; std::string err, gerr;
+    explicit SavedError(flm_ctx* c_) : c(c_), err(c_->err), gerr(g_last_error) {}
+    void restore() const { c->err = err; g_last_error = gerr; (void)hipGetLastError(); }
+};
 int esz_of(int qt) { return qt == FLM_QT_INT8 ? 1 : qt == FLM_QT_INT16 ? 2 : 4; }
 
 // balanced contiguous split (split_rows, transformer.cpp:264-287)
@@ -75,9 +99,9 @@ void build_rope_table(int hs, int max_seq, std::vector<float>& cs, std::vector<f
 
 int alloc_qmat(flm_ctx* c, QMat& m, int rows, int cols, int qt, bool with_st = false) {
     m.rows = rows; m.cols = cols;
-    HIPC(c, hipMalloc(&m.q, (size_t)rows * cols * esz_of(qt)));
-    HIPC(c, hipMalloc((void**)&m.s, (size_t)rows * (cols / kGroup) * sizeof(float)));
-    if (with_st) HIPC(c, hipMalloc((void**)&m.st, (size_t)rows * (cols / kGroup) * sizeof(float)));
+    HIPC(c, dev_alloc(c, &m.q, (size_t)rows * cols * esz_of(qt)));
+    HIPC(c, dev_alloc(c, &m.s, (size_t)rows * (cols / kGroup) * sizeof(float)));
+    if (with_st) HIPC(c, dev_alloc(c, &m.st, (size_t)rows * (cols / kGroup) * sizeof(float)));
     return FLM_OK;
 }
 
@@ -144,10 +168,10 @@ int xwg_check(flm_ctx* c) {
         c->attn_split = 0;
         return fail(c, FLM_ERR_COMM, "tensor parallel: a cross-workgroup wait on this rank timed out; the group's results are invalid and the context group cannot be used any more");
     }
-    if (!c->fb_active) { c->fb_saved[0] = c->fuse_attn_o; c->fb_saved[1] = c->fuse_ffn; c->fb_saved[2] = c->fuse_qkv; c->fb_saved[3] = c->fuse_back; c->fb_saved[4] = c->fuse_token; c->fb_saved[5] = c->attn_split; }
-    c->fuse_attn_o = 0; c->fuse_ffn = 0; c->fuse_qkv = 0; c->fuse_back = 0; c->fuse_token = 0; c->attn_split = 0; c->fell_back += 1; c->fb_active = true; c->fb_tokens = 0;
-    for (auto& g : c->graphs) hipGraphExecDestroy(g.second);
-    c->graphs.clear();
+    if (!c->fb_active) { c->fb_saved.clear(); for (const auto& o : kOptions) if (o.flags & kOptFallback) c->fb_saved.push_back(c->*o.member); }
+    for (const auto& o : kOptions) if (o.flags & kOptFallback) c->*o.member = 0;
+    c->fell_back += 1; c->fb_active = true; c->fb_tokens = 0;
+    drop_graphs(c, false);
     return FLM_RETRY;
 }
 
@@ -193,11 +217,10 @@ int maybe_recover(flm_ctx* c, int tokens) {
     if (c->fb_tokens < kFallbackProbation) return FLM_OK;
     c->fb_tokens = 0;
     if (run_census(c) != 1) return FLM_OK;                               // still crowded: another probation period
-    c->fuse_attn_o = c->fb_saved[0]; c->fuse_ffn = c->fb_saved[1]; c->fuse_qkv = c->fb_saved[2]; c->fuse_back = c->fb_saved[3]; c->fuse_token = c->fb_saved[4]; c->attn_split = c->fb_saved[5];
+    size_t i = 0;
+    for (const auto& o : kOptions) if (o.flags & kOptFallback) c->*o.member = c->fb_saved[i++];
     c->fb_active = false;
-    for (auto& g : c->graphs) hipGraphExecDestroy(g.second);
-    c->graphs.clear();
-    c->la_valid[0] = c->la_valid[1] = false;
+    drop_graphs(c, true);
     return prepare_all(c);
 }
 
@@ -297,24 +320,24 @@ int prepare_all(flm_ctx* c) {
 int alloc_run_bufs(flm_ctx* c) {
     const auto& d = c->d;
     c->prompt_cap = d.max_seq_len; c->out_cap = d.max_seq_len;
-    HIPC(c, hipMalloc((void**)&c->prompt_dev, sizeof(int) * c->prompt_cap));
-    HIPC(c, hipMalloc((void**)&c->out_tokens_dev, sizeof(int) * c->out_cap));
+    HIPC(c, dev_alloc(c, &c->prompt_dev, sizeof(int) * c->prompt_cap));
+    HIPC(c, dev_alloc(c, &c->out_tokens_dev, sizeof(int) * c->out_cap));
     c->bounce_bytes = (size_t)d.vocab_size * 4; if (c->bounce_bytes < sizeof(int) * (size_t)d.max_seq_len) c->bounce_bytes = sizeof(int) * (size_t)d.max_seq_len;
     HIPC(c, hipHostMalloc((void**)&c->bounce, c->bounce_bytes + 64, hipHostMallocDefault));          // (+ a line for the error word that rides along: d2h)
     // (tensor parallel: the full-width activations are regions of the exchange buffer, the rest is this rank's shard)
     const size_t cap = d.max_seq_len < 64 ? 64 : (size_t)d.max_seq_len, nmax = d.hidden_dim > d.dim ? d.hidden_dim : d.dim;
     if (!c->pf_in_xbuf) {
-        HIPC(c, hipMalloc((void**)&c->pf_x, cap * d.dim * 4));
-        HIPC(c, hipMalloc((void**)&c->pf_att, cap * d.dim * 4));
-        HIPC(c, hipMalloc((void**)&c->pf_hd, cap * d.hidden_dim * 4));
+        HIPC(c, dev_alloc(c, &c->pf_x, cap * d.dim * 4));
+        HIPC(c, dev_alloc(c, &c->pf_att, cap * d.dim * 4));
+        HIPC(c, dev_alloc(c, &c->pf_hd, cap * d.hidden_dim * 4));
     }
-    HIPC(c, hipMalloc((void**)&c->pf_qkv, cap * 3 * c->dim_local * 4));
-    HIPC(c, hipMalloc((void**)&c->pf_q, cap * c->dim_local * 4));
-    HIPC(c, hipMalloc((void**)&c->pf_gu, cap * 2 * c->hidden_local * 4));
-    HIPC(c, hipMalloc((void**)&c->pf_xs, 2 * cap * (nmax / kGroup) * 4 + 64));       // row-major [tokens][groups], then group-major [groups][tokens] (+ slack: the GEMM tiles read token pairs)
+    HIPC(c, dev_alloc(c, &c->pf_qkv, cap * 3 * c->dim_local * 4));
+    HIPC(c, dev_alloc(c, &c->pf_q, cap * c->dim_local * 4));
+    HIPC(c, dev_alloc(c, &c->pf_gu, cap * 2 * c->hidden_local * 4));
+    HIPC(c, dev_alloc(c, &c->pf_xs, 2 * cap * (nmax / kGroup) * 4 + 64));       // row-major [tokens][groups], then group-major [groups][tokens] (+ slack: the GEMM tiles read token pairs)
     c->pf_xst = c->pf_xs + cap * (nmax / kGroup);
-    HIPC(c, hipMalloc(&c->pf_xq, cap * nmax * c->esz));
-    if (c->hs % 32 == 0 && c->hs <= 128 && hipMalloc((void**)&c->pf_scores, (size_t)c->heads_local * cap * d.max_seq_len * 4) != hipSuccess) {
+    HIPC(c, dev_alloc(c, &c->pf_xq, cap * nmax * c->esz));
+    if (c->hs % 32 == 0 && c->hs <= 128 && dev_alloc(c, &c->pf_scores, (size_t)c->heads_local * cap * d.max_seq_len * 4) != hipSuccess) {
         c->pf_scores = nullptr; (void)hipGetLastError();        // (quadratic in max_seq_len: without it prompts take the kernels that compute their own scores)
     }
     c->pf_cap = (int)cap;
@@ -418,6 +441,22 @@ int feed(flm_ctx* c, const int32_t* tokens, int n, int pos, int final_advance) {
     return run_token(c, true, final_advance, pos + n);
 }
 
+// Every token entry point runs its work and then looks at the cross-workgroup error flag (xwg_check); if a hand-off
+// inside the fused attention + Wo launch timed out, the SAME work runs again on one kernel per phase: the cache rows
+// and logits of the failed attempt are simply overwritten, and the caller gets correct results and FLM_OK.
+// body: one attempt, up to the read-back of its results; commit: what only a verified attempt may change in the caller's state.
+template <class Body, class Commit>
+static int with_retry(flm_ctx* c, int tokens, Body body, Commit commit) {
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        int r = body(); if (r) return r;
+        r = xwg_check(c);
+        if (r == FLM_OK) { commit(); return maybe_recover(c, tokens); }
+        if (r != FLM_RETRY) return r;
+    }
+    return fail(c, FLM_ERR_HIP, "cross-workgroup wait timed out twice");
+}
+template <class Body> static int with_retry(flm_ctx* c, int tokens, Body body) { return with_retry(c, tokens, body, [] {}); }
+
 } // namespace fh
 
 // =============================================================================================
@@ -496,19 +535,18 @@ int flm_ctx_create(const flm_model_desc* desc, int device_id, int rank, int worl
         if (alloc_qmat(c, w.qkv, 3 * c->dim_local, d.dim, qt, true) || alloc_qmat(c, w.o, c->drow_count, d.dim, qt, true) ||
             alloc_qmat(c, w.w13, 2 * c->hidden_local, d.dim, qt, true) ||
             alloc_qmat(c, w.w2, c->drow_count, d.hidden_dim, qt, true)) return bail(FLM_ERR_OOM);
-        HIPB(hipMalloc((void**)&w.att_norm, d.dim * 4)); HIPB(hipMalloc((void**)&w.ffn_norm, d.dim * 4));
+        HIPB(dev_alloc(c, &w.att_norm, d.dim * 4)); HIPB(dev_alloc(c, &w.ffn_norm, d.dim * 4));
     }
     if (alloc_qmat(c, c->cls, c->plan.vocab_count > 0 ? c->plan.vocab_count : 1, d.dim, qt)) return bail(FLM_ERR_OOM);
     c->cls.rows = c->plan.vocab_count;
-    HIPB(hipMalloc((void**)&c->out_norm, d.dim * 4));
+    HIPB(dev_alloc(c, &c->out_norm, d.dim * 4));
 #ifndef FLM_KV_PAD
 #define FLM_KV_PAD 8
 #endif
     c->kv_rows = d.max_seq_len + FLM_KV_PAD;
     const size_t kvn = (size_t)L * c->heads_local * c->kv_rows * hs;
-    HIPB(hipMalloc((void**)&c->kcache, kvn * 4)); HIPB(hipMalloc((void**)&c->vcache, kvn * 4));
-    HIPB(hipMemsetAsync(c->kcache, 0, kvn * 4, c->stream)); HIPB(hipMemsetAsync(c->vcache, 0, kvn * 4, c->stream));
-    HIPB(hipMalloc((void**)&c->qbuf, c->dim_local * 4));
+    HIPB(dev_alloc(c, &c->kcache, kvn * 4, true)); HIPB(dev_alloc(c, &c->vcache, kvn * 4, true));
+    HIPB(dev_alloc(c, &c->qbuf, c->dim_local * 4));
     {   // the exchange buffer: att_out | x1 | hd | logits | flag lines [4 kinds][8 ranks] (full vectors on every rank under TP)
         auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
         const size_t o_att = 0, o_x1 = up(o_att + (size_t)d.dim * 4), o_hd = up(o_x1 + (size_t)d.dim * 4), o_lg = up(o_hd + (size_t)d.hidden_dim * 4);
@@ -525,35 +563,34 @@ int flm_ctx_create(const flm_model_desc* desc, int device_id, int rank, int worl
         hipError_t ae = hipErrorUnknown;
         if (world > 1) { ae = hipExtMallocWithFlags((void**)&c->xbuf, total, hipDeviceMallocFinegrained); c->xbuf_fine = ae == hipSuccess; }   // written by peer GPUs
         if (ae != hipSuccess) { (void)hipGetLastError(); HIPB(hipMalloc((void**)&c->xbuf, total)); }
+        c->owned.push_back(c->xbuf);
         c->xbuf_bytes = total; c->x_flags_off = o_fl; c->x_hflags_off = o_hf; c->x_tlines_off = world > 1 ? o_tl : 0; c->x_gran_off = world > 1 ? o_gr : 0;
         HIPB(hipMemsetAsync(c->xbuf, 0, total, c->stream));
         c->att_out = (float*)(c->xbuf + o_att); c->x1 = (float*)(c->xbuf + o_x1); c->hd = (float*)(c->xbuf + o_hd); c->logits = (float*)(c->xbuf + o_lg);
         c->peer[rank] = c->xbuf;
         if (world > 1) { c->pf_x = (float*)(c->xbuf + o_px); c->pf_att = (float*)(c->xbuf + o_pa); c->pf_hd = (float*)(c->xbuf + o_ph); c->pf_in_xbuf = true; }
-        HIPB(hipMalloc((void**)&c->xepoch, 64)); HIPB(hipMemsetAsync(c->xepoch, 0, 64, c->stream));
-        HIPB(hipMalloc((void**)&c->ffn_counter, 64)); HIPB(hipMemsetAsync(c->ffn_counter, 0, 64, c->stream));
+        HIPB(dev_alloc(c, &c->xepoch, 64, true));
+        HIPB(dev_alloc(c, &c->ffn_counter, 64, true));
     }
     if (world > 1) c->xg = (granule_t*)(c->xbuf + c->x_gran_off);                 // (cleared with the exchange buffer: tag 0, below every epoch)
-    else { const size_t gb = ((size_t)6 * c->d.dim + c->d.hidden_dim) * sizeof(granule_t);   /* x | x1 | att | hd | q | k | v */ HIPB(hipMalloc((void**)&c->xg, gb)); HIPB(hipMemsetAsync(c->xg, 0, gb, c->stream)); }
-    HIPB(hipMalloc((void**)&c->flag_lines, 1536 * 64)); HIPB(hipMalloc((void**)&c->xwg_err, 64));   // lines 0..255: k_attn_o's heads, 256..511: split heads' scores, 512..767: k_ffn, 768..1023: k_qkv_attn_o's QKV rows, 1024..1279: k_attn_ffn's x1 rows (k_embed clears all 1536)
-    HIPB(hipMemsetAsync(c->flag_lines, 0, 1536 * 64, c->stream)); HIPB(hipMemsetAsync(c->xwg_err, 0, 64, c->stream));
+    else { const size_t gb = ((size_t)6 * c->d.dim + c->d.hidden_dim) * sizeof(granule_t);   /* x | x1 | att | hd | q | k | v */ HIPB(dev_alloc(c, &c->xg, gb, true)); }
+    HIPB(dev_alloc(c, &c->flag_lines, 1536 * 64, true)); HIPB(dev_alloc(c, &c->xwg_err, 64, true));   // lines 0..255: k_attn_o's heads, 256..511: split heads' scores, 512..767: k_ffn, 768..1023: k_qkv_attn_o's QKV rows, 1024..1279: k_attn_ffn's x1 rows (k_embed clears all 1536)
     {   // the one-launch token (k_layers<.., TAIL>): [0] its epoch base, one flag line per classifier workgroup, their argmax slots
         const size_t tail_bytes = (16 + 256 * 16) * 4 + 256 * 2 * 4;
-        HIPB(hipMalloc((void**)&c->tail_mem, tail_bytes)); HIPB(hipMemsetAsync(c->tail_mem, 0, tail_bytes, c->stream));
+        HIPB(dev_alloc(c, &c->tail_mem, tail_bytes, true));
         const unsigned e0 = 4096u; HIPB(hipMemcpyAsync(c->tail_mem, &e0, 4, hipMemcpyHostToDevice, c->stream));
     }
-    HIPB(hipMalloc((void**)&c->eng_base, 64)); HIPB(hipMemsetAsync(c->eng_base, 0, 64, c->stream));   // the token's epoch base
+    HIPB(dev_alloc(c, &c->eng_base, 64, true));   // the token's epoch base
     for (int k = 0; k < 2; ++k) {   // k_layers' argument blocks, one set per head split (filled by layers_prepare; allocated here: nothing is allocated inside a forward)
-        HIPB(hipMalloc((void**)&c->la_dev[k], sizeof(LayerArgs) * (size_t)d.n_layers)); HIPB(hipMalloc((void**)&c->tail_dev[k], sizeof(TailArgs)));
+        HIPB(dev_alloc(c, &c->la_dev[k], sizeof(LayerArgs) * (size_t)d.n_layers)); HIPB(dev_alloc(c, &c->tail_dev[k], sizeof(TailArgs)));
     }
-    HIPB(hipMalloc(&c->att_q, (size_t)d.dim * c->esz)); HIPB(hipMalloc((void**)&c->att_qs, (size_t)(d.dim / kGroup) * 4));
-    HIPB(hipMalloc((void**)&c->att_sc, (size_t)c->heads_local * d.max_seq_len * 8)); HIPB(hipMemsetAsync(c->att_sc, 0, (size_t)c->heads_local * d.max_seq_len * 8, c->stream));   // (8 bytes per score: the parts of a split head exchange them as {score, tag} granules inside k_layers' granule launches, as floats elsewhere)
-    HIPB(hipMalloc((void**)&c->state, sizeof(DecodeState)));
-    HIPB(hipMemsetAsync(c->state, 0, sizeof(DecodeState), c->stream));
-    HIPB(hipMalloc((void**)&c->sparams, sizeof(SampleParams))); HIPB(hipMemsetAsync(c->sparams, 0, sizeof(SampleParams), c->stream));   // the device sampler's parameter block and sort buffers
-    HIPB(hipMalloc((void**)&c->sort_buf, (size_t)2 * d.vocab_size * sizeof(unsigned long long)));
+    HIPB(dev_alloc(c, &c->att_q, (size_t)d.dim * c->esz)); HIPB(dev_alloc(c, &c->att_qs, (size_t)(d.dim / kGroup) * 4));
+    HIPB(dev_alloc(c, &c->att_sc, (size_t)c->heads_local * d.max_seq_len * 8, true));   // (8 bytes per score: the parts of a split head exchange them as {score, tag} granules inside k_layers' granule launches, as floats elsewhere)
+    HIPB(dev_alloc(c, &c->state, sizeof(DecodeState), true));
+    HIPB(dev_alloc(c, &c->sparams, sizeof(SampleParams), true));   // the device sampler's parameter block and sort buffers
+    HIPB(dev_alloc(c, &c->sort_buf, (size_t)2 * d.vocab_size * sizeof(unsigned long long)));
     std::vector<float> cs, sn; build_rope_table(hs, d.max_seq_len, cs, sn);
-    HIPB(hipMalloc((void**)&c->rope_cos, cs.size() * 4)); HIPB(hipMalloc((void**)&c->rope_sin, sn.size() * 4));
+    HIPB(dev_alloc(c, &c->rope_cos, cs.size() * 4)); HIPB(dev_alloc(c, &c->rope_sin, sn.size() * 4));
     // (copies on the context's stream, never on the legacy stream: another context's thread may be capturing its token graph)
     HIPB(hipMemcpyAsync(c->rope_cos, cs.data(), cs.size() * 4, hipMemcpyHostToDevice, c->stream));
     HIPB(hipMemcpyAsync(c->rope_sin, sn.data(), sn.size() * 4, hipMemcpyHostToDevice, c->stream));
@@ -571,7 +608,9 @@ int flm_ctx_create(const flm_model_desc* desc, int device_id, int rank, int worl
             }
         }
         c->resident = run_census(c) == 1 ? 1 : 0;
-        if (!c->resident) { c->fuse_attn_o = 0; c->fuse_ffn = 0; c->fuse_qkv = 0; c->fuse_back = 0; c->attn_split = 0; }
+        // (the kOptResident rows; unlike a fallback, "fuse_token" keeps its value: on one GPU it selects nothing without "fuse_back", and whether a tensor-parallel group runs its
+        //  rank-spanning form is agreed at flm_p2p_import, from every rank's "resident")
+        if (!c->resident) for (const auto& o : kOptions) if (o.flags & kOptResident) c->*o.member = 0;
     }
 #undef HIPB
     *out = c;
@@ -582,16 +621,10 @@ void flm_ctx_destroy(flm_ctx* c) {
     if (!c) return;
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
-    for (auto& g : c->graphs) hipGraphExecDestroy(g.second);
-    auto fq = [](QMat& m) { if (m.q) hipFree(m.q); if (m.s) hipFree(m.s); if (m.st) hipFree(m.st); };
-    for (auto& l : c->layers) { fq(l.qkv); fq(l.o); fq(l.w13); fq(l.w2); if (l.att_norm) hipFree(l.att_norm); if (l.ffn_norm) hipFree(l.ffn_norm); }
-    fq(c->cls);
+    drop_graphs(c, false);
     for (int r = 0; r < c->world; ++r) if (c->peer_opened[r] && c->peer[r]) hipIpcCloseMemHandle(c->peer[r]);
-    void* ptrs[] = {c->emb, c->emb_s, c->out_norm, c->kcache, c->vcache, c->xbuf, c->xepoch, c->qbuf,
-                    c->rope_cos, c->rope_sin, c->state, c->prompt_dev, c->out_tokens_dev, c->sparams, c->sort_buf,
-                    c->world > 1 ? nullptr : (void*)c->xg, c->flag_lines, c->xwg_err, c->att_q, c->att_qs, c->att_sc, c->trace, c->eng_base, c->ffn_counter, c->la_dev[0], c->la_dev[1], c->tail_dev[0], c->tail_dev[1], c->tail_mem,
-                    c->pf_in_xbuf ? nullptr : c->pf_x, c->pf_qkv, c->pf_q, c->pf_in_xbuf ? nullptr : c->pf_att, c->pf_gu, c->pf_in_xbuf ? nullptr : c->pf_hd, c->pf_xs, c->pf_xq, c->pf_scores};
-    for (void* p : ptrs) if (p) hipFree(p);
+    for (void* p : c->owned) hipFree(p);
+    for (void* p : {c->emb, (void*)c->emb_s, (void*)c->trace}) if (p) hipFree(p);          // (re-allocated during the context's life: flm_upload_tensor, option "trace")
     if (c->bounce) hipHostFree(c->bounce);
     if (c->comm) ncclCommDestroy(c->comm);
     if (c->stream) hipStreamDestroy(c->stream);
@@ -605,23 +638,39 @@ void flm_ctx_destroy(flm_ctx* c) {
 // process share the pointer directly).  From then on activation slices travel by direct stores over xGMI plus one flag
 // round (k_xchg) instead of an RCCL all-gather, and the token is replayed from a hipGraph like the single-GPU one.
 namespace {
-struct P2pBlob { unsigned long long magic; int pid, device, rank, world; unsigned long long bytes; void* raw; hipIpcMemHandle_t h; int caps; /* bit 0: this rank can run the batched prompt path */ char pad[128 - 8 - 16 - 8 - 8 - sizeof(hipIpcMemHandle_t) - 4]; };
+struct P2pBlob { unsigned long long magic; int pid, device, rank, world; unsigned long long bytes; void* raw; hipIpcMemHandle_t h; int caps; /* pack(P2pCaps) */ char pad[128 - 8 - 16 - 8 - 8 - sizeof(hipIpcMemHandle_t) - 4]; };
 static_assert(sizeof(P2pBlob) == FLM_P2P_BLOB_BYTES, "blob size");
 constexpr unsigned long long kP2pMagic = 0x464C4D5032503031ull;   // "FLMP2P01"
+// What a rank can do and wants, as the blob's `caps` word carries it (the bits in pack's order; ranks that read it differently wait on flags nobody raises)
+struct P2pCaps {
+    bool prefill, resident, can_split, fold;            // bits 0-3: the batched prompt path is possible, one workgroup per CU resident (census), heads can be split over workgroups, "fold_xchg"
+    int tp_fuse_attn; bool tp_fuse_ffn, trust_fused;    // 4-5, 6, 7 ("tp_trust_fused")
+    int cu_parts, attn_split;                           // 8-11, 12-15
+    bool tp_layers; int cu_count; bool gr_edges;        // 16 "tp_fuse_layers" (and "fuse_token"), 17-26 the CUs this rank's launches are sized for, 27
+};
+constexpr int pack(const P2pCaps& x) {
+    return (x.prefill ? 1 : 0) | (x.resident ? 2 : 0) | (x.can_split ? 4 : 0) | (x.fold ? 8 : 0) | ((x.tp_fuse_attn & 3) << 4) | (x.tp_fuse_ffn ? 64 : 0) | (x.trust_fused ? 128 : 0)
+           | ((x.cu_parts & 15) << 8) | ((x.attn_split & 15) << 12) | (x.tp_layers ? 1 << 16 : 0) | ((x.cu_count & 1023) << 17) | (x.gr_edges ? 1 << 27 : 0);
+}
+constexpr P2pCaps unpack(int w) {
+    return {(w & 1) != 0, (w & 2) != 0, (w & 4) != 0, (w & 8) != 0, (w >> 4) & 3, (w & 64) != 0, (w & 128) != 0, (w >> 8) & 15, (w >> 12) & 15, (w & (1 << 16)) != 0, (w >> 17) & 1023, (w & (1 << 27)) != 0};
+}
+static_assert(pack(unpack(0x0FFFFFFF)) == 0x0FFFFFFF && pack(unpack(0x05A5A5A5)) == 0x05A5A5A5 && pack(unpack(0x0A5A5A5A)) == 0x0A5A5A5A, "caps: pack and unpack disagree");
 }
 #include <unistd.h>
 int flm_p2p_export(flm_ctx* c, void* blob128) {
     if (!c || !blob128) return FLM_ERR_INVALID;
     HIPC(c, hipSetDevice(c->device));
     P2pBlob b{}; b.magic = kP2pMagic; b.pid = (int)getpid(); b.device = c->device; b.rank = c->rank; b.world = c->world; b.bytes = c->xbuf_bytes; b.raw = c->xbuf;
-    // caps: bit 0 batched prompt path possible, 1 one workgroup per CU resident (census), 2 heads can be split over workgroups, 3 fold_xchg, 4-5 tp_fuse_attn, 6 tp_fuse_ffn,
-    //       7 tp_trust_fused, 8-11 cu_parts, 12-15 attn_split
     {
         const int Gfull = c->hs / kSplitDims;
-        const bool can = c->hs % kSplitDims == 0 && Gfull >= 2 && c->hs <= 128 && c->d.max_seq_len <= kSplitMaxSeq && c->heads_local * Gfull + 8 <= c->cu_count && c->heads_local * Gfull <= 256;
-        b.caps = (tp_prefill_capable(c) ? 1 : 0) | (c->resident ? 2 : 0) | (can ? 4 : 0) | (c->fold_xchg ? 8 : 0) | ((c->tp_fuse_attn < 0 ? 0 : c->tp_fuse_attn > 2 ? 2 : c->tp_fuse_attn) << 4) | (c->tp_fuse_ffn ? 64 : 0)
-               | (c->tp_trust_fused ? 128 : 0) | ((c->cu_parts & 15) << 8) | ((c->attn_split < 0 ? 0 : c->attn_split > 15 ? 15 : c->attn_split) << 12)
-               | (c->tp_fuse_layers && c->fuse_token ? 1 << 16 : 0) | ((c->cu_count & 1023) << 17) | (c->gr_edges ? 1 << 27 : 0);          // 16 tp_fuse_layers, 17-26 the CUs this rank's launches are sized for
+        P2pCaps x{};
+        x.prefill = tp_prefill_capable(c); x.resident = c->resident != 0; x.fold = c->fold_xchg != 0; x.tp_fuse_ffn = c->tp_fuse_ffn != 0; x.trust_fused = c->tp_trust_fused != 0;
+        x.can_split = c->hs % kSplitDims == 0 && Gfull >= 2 && c->hs <= 128 && c->d.max_seq_len <= kSplitMaxSeq && c->heads_local * Gfull + 8 <= c->cu_count && c->heads_local * Gfull <= 256;
+        x.tp_fuse_attn = c->tp_fuse_attn < 0 ? 0 : c->tp_fuse_attn > 2 ? 2 : c->tp_fuse_attn;
+        x.attn_split = c->attn_split < 0 ? 0 : c->attn_split > 15 ? 15 : c->attn_split;
+        x.cu_parts = c->cu_parts; x.cu_count = c->cu_count; x.tp_layers = c->tp_fuse_layers && c->fuse_token; x.gr_edges = c->gr_edges != 0;
+        b.caps = pack(x);
     }
     HIPC(c, hipIpcGetMemHandle(&b.h, c->xbuf));
     memcpy(blob128, &b, sizeof b);
@@ -637,26 +686,25 @@ int flm_p2p_import(flm_ctx* c, const void* blobs, int n) {
     for (int r = 0; r < n; ++r)
         if (b[r].magic != kP2pMagic || b[r].rank != r || b[r].world != c->world || b[r].bytes != c->xbuf_bytes) return fail(c, FLM_ERR_INVALID, "p2p_import: blobs are not those of this tensor-parallel group, in rank order");
     // (from here on the group's structure may change: graphs captured under the old one must not be replayed, whatever happens below)
-    for (auto& g : c->graphs) hipGraphExecDestroy(g.second);
-    c->graphs.clear();
-    c->la_valid[0] = c->la_valid[1] = false;
+    drop_graphs(c, true);
     c->tp_prefill = true;
-    for (int r = 0; r < n; ++r) if (!(b[r].caps & 1)) c->tp_prefill = false;
+    for (int r = 0; r < n; ++r) if (!unpack(b[r].caps).prefill) c->tp_prefill = false;
     c->ranks_on_device = 0;
     for (int r = 0; r < n; ++r) if (b[r].device == c->device) ++c->ranks_on_device;
     if (!tp_prefill_capable(c)) c->tp_prefill = false;
     {   // the group's launch structure: the weakest any rank can do, computed alike on every rank from the same blobs
-        bool fold = true, span = true, can = true, multi_dev = false, trust = true, tpl = true, ggr = true; int fa = 2, ff = 1, split = (b[0].caps >> 12) & 15;
+        bool fold = true, span = true, can = true, multi_dev = false, trust = true, tpl = true, ggr = true; int fa = 2, ff = 1;
+        const P2pCaps x0 = unpack(b[0].caps); int split = x0.attn_split;
         for (int r = 0; r < n; ++r) {
-            const int cp = (b[r].caps >> 8) & 15; int rod = 0;
+            const P2pCaps x = unpack(b[r].caps); int rod = 0;
             for (int q = 0; q < n; ++q) { if (b[q].device == b[r].device) ++rod; else multi_dev = true; }
-            const bool fold_r = (b[r].caps & 8) && cp >= rod, span_r = fold_r && ((b[r].caps & 2) || cp > 1);
-            fold = fold && fold_r; span = span && span_r; can = can && (b[r].caps & 4); trust = trust && (b[r].caps & 128);
-            const int fa_r = (b[r].caps >> 4) & 3; if (fa_r < fa) fa = fa_r;
-            if (!(b[r].caps & 64)) ff = 0;
-            if (!(b[r].caps & (1 << 27))) ggr = false;
-            if (((b[r].caps >> 12) & 15) != split) split = 0;                   // (ranks that disagree: nobody splits)
-            if (!(b[r].caps & (1 << 16)) || ((b[r].caps >> 17) & 1023) != ((b[0].caps >> 17) & 1023)) tpl = false;   // (the rank-spanning k_layers: every rank wants it, identical launch geometry)
+            const bool fold_r = x.fold && x.cu_parts >= rod, span_r = fold_r && (x.resident || x.cu_parts > 1);
+            fold = fold && fold_r; span = span && span_r; can = can && x.can_split; trust = trust && x.trust_fused;
+            if (x.tp_fuse_attn < fa) fa = x.tp_fuse_attn;
+            if (!x.tp_fuse_ffn) ff = 0;
+            if (!x.gr_edges) ggr = false;
+            if (x.attn_split != split) split = 0;                   // (ranks that disagree: nobody splits)
+            if (!x.tp_layers || x.cu_count != x0.cu_count) tpl = false;   // (the rank-spanning k_layers: every rank wants it, identical launch geometry)
         }
         // ranks on distinct devices: the folded exchanges and the rank-spanning launches rely on system-scope store / flag ordering over xGMI that was only ever
         // exercised between CU partitions of ONE GPU -> the k_xchg launches (a flag round behind a kernel boundary) unless every rank says "tp_trust_fused"
@@ -680,63 +728,32 @@ int flm_p2p_import(flm_ctx* c, const void* blobs, int n) {
         c->peer[r] = (char*)p; c->peer_opened[r] = true;
     }
     c->p2p = 1;
-    for (auto& g : c->graphs) hipGraphExecDestroy(g.second);
-    c->graphs.clear();
-    {   // the group's structure is known now: argument blocks and token graphs (captured, not launched -- nobody waits for a peer here); an error here resurfaces at the first forward
-        const std::string err0 = c->err, gerr0 = g_last_error;
-        if (prepare_all(c) != FLM_OK) { c->err = err0; g_last_error = gerr0; (void)hipGetLastError(); }
-    }
+    drop_graphs(c, false);
+    // the group's structure is known now: argument blocks and token graphs (captured, not launched -- nobody waits for a peer here); an error here resurfaces at the first forward
+    const SavedError saved(c);
+    if (prepare_all(c) != FLM_OK) saved.restore();
     return FLM_OK;
 }
 
 int flm_set_option(flm_ctx* c, const char* key, int value) {
     if (!c || !key) return FLM_ERR_INVALID;
-    std::string k(key);
-    if (c->world > 1 && c->p2p && (k == "use_mfma" || k == "use_pv_mfma" || k == "use_prefill_mq" || k == "use_qk_mfma"))
+    const std::string k(key);
+    const OptionRow* row = nullptr;
+    for (const auto& o : kOptions) if (k == o.key) row = &o;
+    const unsigned flags = row ? row->flags : 0;
+    if ((flags & kOptFrozen) && c->world > 1 && c->p2p)
         return fail(c, FLM_ERR_STATE, "set_option: which prompt kernels a tensor-parallel group runs is agreed at flm_p2p_import; set this option on every rank before importing (\"use_prefill\" may be switched later, on every rank alike)");
-    if (!c->resident && value != 0 && (k == "fuse_attn_o" || k == "fuse_ffn" || k == "fuse_qkv" || k == "fuse_back" || k == "attn_split"))
+    if ((flags & kOptResident) && !c->resident && value != 0)
         return fail(c, FLM_ERR_UNSUPPORTED, "set_option: this device does not keep one workgroup per CU resident (census at flm_ctx_create); the fused launches stay off");
-    for (const char* tk : kTuningKeys)
-        if (k == tk && !c->tuning) return fail(c, FLM_ERR_INVALID, "set_option: an experiment dial (csrc/flm_tuning.h), not part of the boundary: set option \"tuning\" 1 first");
+    if ((flags & kOptDial) && !c->tuning) return fail(c, FLM_ERR_INVALID, "set_option: an experiment dial (csrc/flm_tuning.h), not part of the boundary: set option \"tuning\" 1 first");
+    // the keys whose setter does more than store the value, then the table's rows.  "tuning" and "inject_wait_failure" change nothing a captured graph depends on
     if (k == "tuning") { c->tuning = value != 0; return FLM_OK; }
-    if (k == "wg_per_cu") { c->wg_per_cu = value > 0 ? value : 1; }
-    else if (k == "use_graph") c->use_graph = value;
-    else if (k == "graph_chunks") c->graph_chunks = value;
-    else if (k == "inject_wait_failure") {   // (tuning mode only: flm_tuning.h)
+    if (k == "inject_wait_failure") {
         if (value) { const int one = 1; HIPC(c, hipMemcpyAsync(c->xwg_err, &one, 4, hipMemcpyHostToDevice, c->stream)); HIPC(c, hipStreamSynchronize(c->stream)); }
         return FLM_OK;
     }
-    else if (k == "use_prefill") c->use_prefill = value;
-    else if (k == "use_mfma") c->use_mfma = value;
-    else if (k == "use_pv_mfma") c->use_pv_mfma = value;
-    else if (k == "fuse_attn_o") c->fuse_attn_o = value;
-    else if (k == "fuse_ffn") c->fuse_ffn = value;
-    else if (k == "fuse_qkv") c->fuse_qkv = value;
-    else if (k == "fuse_back") c->fuse_back = value;
-    else if (k == "fuse_layer") c->fuse_layer = value;
-    else if (k == "fuse_token") c->fuse_token = value;
-    else if (k == "fuse_tail") c->fuse_tail = value;
-    else if (k == "tok_nstq") c->tok_nstq = value;
-    else if (k == "tok_preq") c->tok_preq = value;
-    else if (k == "back_nst13") c->back_nst13 = value;
-    else if (k == "back_nst13_head") c->back_nst13_head = value;
-    else if (k == "back_nst2") c->back_nst2 = value;
-    else if (k == "back_pre13") c->back_pre13 = value;
-    else if (k == "back_pre2") c->back_pre2 = value;
-    else if (k == "back_ao") c->back_ao = value;
-    else if (k == "back_ao2") c->back_ao2 = value;
-    else if (k == "gr_edges") c->gr_edges = value;
-    else if (k == "back_nwo") c->back_nwo = value;
-    else if (k == "attn_kpre") c->attn_kpre = value;
-    else if (k == "use_prefill_mq") c->use_prefill_mq = value;
-    else if (k == "attn_split") c->attn_split = value;
-    else if (k == "fold_xchg") c->fold_xchg = value;
-    else if (k == "tp_fuse_attn") c->tp_fuse_attn = value;
-    else if (k == "tp_fuse_ffn") c->tp_fuse_ffn = value;
-    else if (k == "tp_fuse_layers") c->tp_fuse_layers = value;
+    if (k == "wg_per_cu") c->wg_per_cu = value > 0 ? value : 1;
     else if (k == "tp_fence") c->tp_fence = value < 0 ? -1 : value & 3;
-    else if (k == "tp_trust_fused") c->tp_trust_fused = value;
-    else if (k == "force_tp") c->force_tp = value;
     else if (k == "cu_parts") {
         // confine this context's stream to 1 / value of the device's CUs (part rank % value) and size its launches for them: how several tensor-parallel
         // ranks share ONE GPU without a waiting consumer launch taking the CUs its peers' producers need (tests; a real rank owns a device: value 1)
@@ -752,9 +769,10 @@ int flm_set_option(flm_ctx* c, const char* key, int value) {
         }
         HIPC(c, hipStreamDestroy(c->stream));
         c->stream = ns; c->cu_parts = value; c->cu_count = c->cu_total / value;
+        // (by hand, neither the kOptResident nor the kOptFallback rows: "attn_split" and "fuse_token" keep their values -- what a group of ranks on CU partitions splits and spans is
+        //  agreed at flm_p2p_import)
         if (value > 1) { c->fuse_attn_o = 0; c->fuse_ffn = 0; c->fuse_qkv = 0; c->fuse_back = 0; }
     }
-    else if (k == "use_qk_mfma") c->use_qk_mfma = value;
     else if (k == "use_p2p") {     // 0: exchange by RCCL all-gathers although the peers are mapped (needs the communicator); 1: back to peer-to-peer
         if (value) { for (int r = 0; r < c->world; ++r) if (!c->peer[r]) return fail(c, FLM_ERR_STATE, "use_p2p: flm_p2p_import has not mapped every peer"); }
         else if (c->world > 1 && !c->comm) return fail(c, FLM_ERR_STATE, "use_p2p 0: no RCCL communicator (comm_id was NULL at create)");
@@ -766,24 +784,49 @@ int flm_set_option(flm_ctx* c, const char* key, int value) {
         if (!c->trace) { HIPC(c, hipMalloc((void**)&c->trace, 131072 * 8)); }
         HIPC(c, hipMemset(c->trace, 0, 131072 * 8));
     }
+    else if (row) c->*row->member = value;
     else return fail(c, FLM_ERR_INVALID, "unknown option");
-    for (auto& g : c->graphs) hipGraphExecDestroy(g.second);
-    c->graphs.clear();
-    c->la_valid[0] = c->la_valid[1] = false;
+    drop_graphs(c, true);
     return FLM_OK;
 }
-
 
 int flm_query(flm_ctx* c, const char* key, int* value) {
     if (!c || !key || !value) return FLM_ERR_INVALID;
     const std::string k(key);
+    for (const auto& o : kOptions) if (o.member && k == o.key) { *value = c->*o.member; return FLM_OK; }
+    const bool tp = c->world > 1 && c->p2p, tpl = tp && c->grp_tpl;
+    // the granule hand-offs are what the one-launch token / the rank-spanning launch of head split i runs
+    auto gr = [&](int i) { return c->la_valid[i] && c->la_ok[i] && c->la_p[i].gr && (c->world > 1 ? tpl : c->tail_ok[i]); };
+    const int path = (c->fuse_attn_o ? 1 : 0) | (c->fuse_ffn ? 2 : 0) | (c->fuse_attn_o && c->fuse_qkv == 1 ? 4 : 0) | (c->fuse_attn_o && c->fuse_qkv >= 2 ? 8 : 0)
+                     | (c->fuse_back && c->fuse_attn_o && c->fuse_ffn ? (c->fuse_layer ? 128 + 256 + (c->fuse_token ? 512 + (c->fuse_tail && c->tail_ok[0] ? 1024 : 0) : 0) : 128) : 0);
+    // what the context derives from its options and its group: read-only
     const struct { const char* k; int v; } tab[] = {
-        {"tuning", c->tuning ? 1 : 0}, {"wg_per_cu", c->wg_per_cu}, {"use_graph", c->use_graph}, {"graph_chunks", c->graph_chunks}, {"use_prefill", c->use_prefill}, {"use_mfma", c->use_mfma}, {"use_pv_mfma", c->use_pv_mfma},
-        {"fuse_attn_o", c->fuse_attn_o}, {"fuse_ffn", c->fuse_ffn}, {"fuse_qkv", c->fuse_qkv}, {"fuse_back", c->fuse_back}, {"fuse_layer", c->fuse_layer}, {"fuse_token", c->fuse_token}, {"fuse_tail", c->fuse_tail}, {"tok_nstq", c->tok_nstq}, {"tok_preq", c->tok_preq}, {"back_nst13", c->back_nst13}, {"back_nst13_head", c->back_nst13_head}, {"back_nst2", c->back_nst2}, {"back_pre13", c->back_pre13}, {"back_pre2", c->back_pre2}, {"back_ao", c->back_ao}, {"back_ao2", c->back_ao2}, {"gr_edges", c->gr_edges}, {"back_nwo", c->back_nwo}, {"attn_kpre", c->attn_kpre}, {"kpre_active", c->la_valid[1] ? (int)c->la_p[1].kpre_off : -1}, {"nwo_active", c->la_valid[0] ? c->la_p[0].nw_o : -1}, {"preq_active", c->la_valid[0] ? c->la_p[0].preq : -1}, {"pre13_active", c->la_valid[0] ? c->la_p[0].pre13 : -1}, {"preq_active_split", c->la_valid[1] ? c->la_p[1].preq : -1}, {"pre13_active_split", c->la_valid[1] ? c->la_p[1].pre13 : -1},   /* the early register sets the last one-launch token ran with (plan_layer's by-launch values) */ {"gr_active", ((c->la_valid[0] && c->la_ok[0] && c->la_p[0].gr && (c->world > 1 ? (c->p2p && c->grp_tpl) : c->tail_ok[0])) ? 1 : 0) | ((c->la_valid[1] && c->la_ok[1] && c->la_p[1].gr && (c->world > 1 ? (c->p2p && c->grp_tpl) : c->tail_ok[1])) ? 2 : 0)},   /* the granule hand-offs are what the one-launch token / the rank-spanning launch runs: bit 0 one workgroup per head, bit 1 split heads */ {"use_prefill_mq", c->use_prefill_mq}, {"attn_split", c->attn_split},
-        {"use_qk_mfma", c->use_qk_mfma}, {"use_p2p", c->p2p}, {"fold_xchg", c->fold_xchg}, {"tp_fuse_attn", c->tp_fuse_attn}, {"tp_fuse_ffn", c->tp_fuse_ffn}, {"cu_parts", c->cu_parts}, {"fold_active", (c->world > 1 && c->p2p && c->grp_fold) ? 1 : 0}, {"span_active", (c->world > 1 && c->p2p && c->grp_span) ? 1 : 0}, {"tp_trust_fused", c->tp_trust_fused}, {"force_tp", c->force_tp},
-        {"tp_fuse_layers", c->tp_fuse_layers}, {"tp_fence", c->tp_fence}, {"tp_fence_active", c->tp_fence >= 0 ? c->tp_fence : (c->ranks_on_device == c->world ? 0 : 3)}, {"grp_gr", (c->world > 1 && c->grp_gr) ? 1 : 0}, {"grp_tp_fuse_layers", (c->world > 1 && c->p2p && c->grp_tpl) ? 1 : 0}, {"tp_layers_active", (c->world > 1 && c->p2p && c->grp_tpl && (c->la_valid[0] || c->la_valid[1])) ? (c->la_valid[0] && c->la_ok[0] ? 1 : 0) | (c->la_valid[1] && c->la_ok[1] ? 2 : 0) : -1},   /* the rank-spanning k_layers was planned: bit 0 one workgroup per head, bit 1 split heads */ {"grp_tp_fuse_attn", c->grp_tpfa}, {"grp_tp_fuse_ffn", c->grp_tpff}, {"grp_attn_split", c->grp_split}, {"resident", c->resident}, {"fallback", c->fell_back}, {"fallback_active", c->fb_active ? 1 : 0}, {"sampled_tokens", (int)c->sampled},
-        {"ao_active", c->la_ok[0] ? (c->la_p[0].ao_o ? 1 : 0) | (c->la_p[0].ao_2 ? 2 : 0) : -1},      // which hand-offs of the token's launch (short contexts) are consumed in arrival order; -1: that launch was not planned (yet)
-        {"token_path", (c->world == 1 ? ((c->fuse_attn_o ? 1 : 0) | (c->fuse_ffn ? 2 : 0) | (c->fuse_attn_o && c->fuse_qkv == 1 ? 4 : 0) | (c->fuse_attn_o && c->fuse_qkv >= 2 ? 8 : 0) | (c->fuse_back && c->fuse_attn_o && c->fuse_ffn ? (c->fuse_layer ? 128 + 256 + (c->fuse_token ? 512 + (c->fuse_tail && c->tail_ok[0] ? 1024 : 0) : 0) : 128) : 0)) : 0) | (c->attn_split ? 64 : 0)},
+        {"tuning", c->tuning ? 1 : 0},
+        {"kpre_active", c->la_valid[1] ? (int)c->la_p[1].kpre_off : -1},
+        {"nwo_active", c->la_valid[0] ? c->la_p[0].nw_o : -1},
+        // the early register sets the last one-launch token ran with (plan_layer's by-launch values)
+        {"preq_active", c->la_valid[0] ? c->la_p[0].preq : -1},
+        {"pre13_active", c->la_valid[0] ? c->la_p[0].pre13 : -1},
+        {"preq_active_split", c->la_valid[1] ? c->la_p[1].preq : -1},
+        {"pre13_active_split", c->la_valid[1] ? c->la_p[1].pre13 : -1},
+        {"gr_active", (gr(0) ? 1 : 0) | (gr(1) ? 2 : 0)},                         // bit 0 one workgroup per head, bit 1 split heads
+        {"fold_active", tp && c->grp_fold ? 1 : 0},
+        {"span_active", tp && c->grp_span ? 1 : 0},
+        {"tp_fence_active", c->tp_fence >= 0 ? c->tp_fence : (c->ranks_on_device == c->world ? 0 : 3)},
+        {"grp_gr", c->world > 1 && c->grp_gr ? 1 : 0},
+        {"grp_tp_fuse_layers", tpl ? 1 : 0},
+        // the rank-spanning k_layers was planned: bit 0 one workgroup per head, bit 1 split heads
+        {"tp_layers_active", tpl && (c->la_valid[0] || c->la_valid[1]) ? (c->la_valid[0] && c->la_ok[0] ? 1 : 0) | (c->la_valid[1] && c->la_ok[1] ? 2 : 0) : -1},
+        {"grp_tp_fuse_attn", c->grp_tpfa},
+        {"grp_tp_fuse_ffn", c->grp_tpff},
+        {"grp_attn_split", c->grp_split},
+        {"resident", c->resident},
+        {"fallback", c->fell_back},
+        {"fallback_active", c->fb_active ? 1 : 0},
+        {"sampled_tokens", (int)c->sampled},
+        // which hand-offs of the token's launch (short contexts) are consumed in arrival order; -1: that launch was not planned (yet)
+        {"ao_active", c->la_ok[0] ? (c->la_p[0].ao_o ? 1 : 0) | (c->la_p[0].ao_2 ? 2 : 0) : -1},
+        {"token_path", (c->world == 1 ? path : 0) | (c->attn_split ? 64 : 0)},
     };
     for (const auto& t : tab) if (k == t.k) { *value = t.v; return FLM_OK; }
     return fail(c, FLM_ERR_INVALID, "query: unknown key");
@@ -814,8 +857,7 @@ static int upload_tensor_impl(flm_ctx* c, int kind, int layer, int src_qt, const
         if (src_qt != FLM_QT_NONE) { HIPC(c, hipMalloc((void**)&c->emb_s, n / kGroup * 4)); HIPC(c, hipMemcpyAsync(c->emb_s, scales, n / kGroup * 4, hipMemcpyHostToDevice, c->stream)); }
         HIPC(c, hipStreamSynchronize(c->stream));
         c->emb_qt = src_qt; c->got_emb = true;
-        for (auto& g : c->graphs) hipGraphExecDestroy(g.second);
-        c->graphs.clear();
+        drop_graphs(c, false);                                               // (the argument blocks: above)
         return FLM_OK; }
     case FLM_T_OUTPUT_NORM: { int r = vec(c->out_norm, d.dim); if (!r) c->got_out_norm = true; return r; }
     case FLM_T_INPUT_NORM:  { int r = vec(c->layers[layer].att_norm, d.dim); if (!r) c->layers[layer].got |= 1u << 0; return r; }
@@ -854,7 +896,7 @@ static int upload_tensor_impl(flm_ctx* c, int kind, int layer, int src_qt, const
 static void warm_up(flm_ctx* c) {
     if (c->warmed || c->world != 1 || c->comm || !model_complete(c)) return;
     c->warmed = true;
-    const std::string err0 = c->err, gerr0 = g_last_error;
+    const SavedError saved(c);
     int32_t toks[kPrefillMin + 2] = {0};
     const int n = c->d.max_seq_len > kPrefillMin + 2 ? kPrefillMin + 2 : 1;
     bool ok = feed(c, toks, n, 0, 0) == FLM_OK && hipStreamSynchronize(c->stream) == hipSuccess;
@@ -870,18 +912,17 @@ static void warm_up(flm_ctx* c) {
     if (ok && sample_supported(c) && c->d.max_seq_len > kSplitFrom + 8 + kEach && attn_parts(c, kSplitFrom + 8) != attn_parts(c, 1))
         ok = set_state(c, kSplitFrom + 8, 0, 0) == FLM_OK && run_tokens(c, kSplitFrom + 8, kEach, 3) == FLM_OK && hipStreamSynchronize(c->stream) == hipSuccess;
     if (ok) (void)xwg_check(c);                                                // (a wait that gave up here puts the context on the per-phase kernels like any other)
-    const size_t kvn = (size_t)c->d.n_layers * c->heads_local * c->kv_rows * c->hs;     // the cache rows the dummy tokens wrote: cleared again
-    (void)hipMemsetAsync(c->kcache, 0, kvn * 4, c->stream); (void)hipMemsetAsync(c->vcache, 0, kvn * 4, c->stream);
+    (void)clear_kv(c);                                                          // the cache rows the dummy tokens wrote: cleared again
     (void)hipStreamSynchronize(c->stream);
-    (void)hipGetLastError(); c->err = err0; g_last_error = gerr0;               // (an error here is not the caller's: it resurfaces at the first forward)
+    saved.restore();                                                            // (whatever happened: an error here is not the caller's, it resurfaces at the first forward)
 }
 int flm_upload_tensor(flm_ctx* c, int kind, int layer, int src_qt, const void* values, const float* scales, int rows, int cols) {
     const int r = upload_tensor_impl(c, kind, layer, src_qt, values, scales, rows, cols);
     if (r == FLM_OK && model_complete(c)) {
         // the model's last tensor (or a replacement) has arrived: k_layers' argument blocks and the token graphs are built NOW, not inside the first forward
         // (transformer.cpp:110-130: no allocation during inference).  An error here is not the upload's: it resurfaces at the first forward.
-        const std::string err0 = c->err, gerr0 = g_last_error;
-        if (prepare_all(c) != FLM_OK) { c->err = err0; g_last_error = gerr0; (void)hipGetLastError(); }
+        const SavedError saved(c);
+        if (prepare_all(c) != FLM_OK) saved.restore();
         else warm_up(c);
     }
     return r;
@@ -899,8 +940,7 @@ int flm_prepare(flm_ctx* c) {
 int flm_reset_kv(flm_ctx* c) {
     if (!c) return FLM_ERR_INVALID;
     HIPC(c, hipSetDevice(c->device));
-    const size_t kvn = (size_t)c->d.n_layers * c->heads_local * c->kv_rows * c->hs;
-    HIPC(c, hipMemsetAsync(c->kcache, 0, kvn * 4, c->stream)); HIPC(c, hipMemsetAsync(c->vcache, 0, kvn * 4, c->stream));
+    HIPC(c, clear_kv(c));
     HIPC(c, hipStreamSynchronize(c->stream));
     return FLM_OK;
 }
@@ -972,29 +1012,22 @@ int flm_debug_read(flm_ctx* c, int what, int layer, float* out, size_t n) {
 
 int flm_sync(flm_ctx* c) { if (!c) return FLM_ERR_INVALID; HIPC(c, hipSetDevice(c->device)); HIPC(c, hipStreamSynchronize(c->stream)); return FLM_OK; }
 
-// Every entry point below runs its work and then looks at the cross-workgroup error flag (xwg_check); if a hand-off
-// inside the fused attention + Wo launch timed out, the SAME work runs again on one kernel per phase: the cache rows
-// and logits of the failed attempt are simply overwritten, and the caller gets correct results and FLM_OK.
 int flm_forward(flm_ctx* c, const int32_t* tokens, int n, int pos, float* logits_host) {
     if (!tokens || !logits_host) return FLM_ERR_INVALID;
     int r = check_ready(c, n, pos); if (r) return r;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        r = feed(c, tokens, n, pos, 0); if (r) return r;
-        r = d2h(c, logits_host, c->logits, (size_t)c->d.vocab_size * 4); if (r) return r;
-        r = xwg_check(c); if (r != FLM_RETRY) return r ? r : maybe_recover(c, n);
-    }
-    return fail(c, FLM_ERR_HIP, "cross-workgroup wait timed out twice");
+    return with_retry(c, n, [&] {
+        int r = feed(c, tokens, n, pos, 0); if (r) return r;
+        return d2h(c, logits_host, c->logits, (size_t)c->d.vocab_size * 4);
+    });
 }
 
 int flm_forward_argmax(flm_ctx* c, const int32_t* tokens, int n, int pos, int32_t* next_token) {
     if (!tokens || !next_token) return FLM_ERR_INVALID;
     int r = check_ready(c, n, pos); if (r) return r;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        r = feed(c, tokens, n, pos, 1); if (r) return r;
-        r = d2h(c, next_token, c->out_tokens_dev, 4); if (r) return r;
-        r = xwg_check(c); if (r != FLM_RETRY) return r ? r : maybe_recover(c, n);
-    }
-    return fail(c, FLM_ERR_HIP, "cross-workgroup wait timed out twice");
+    return with_retry(c, n, [&] {
+        int r = feed(c, tokens, n, pos, 1); if (r) return r;
+        return d2h(c, next_token, c->out_tokens_dev, 4);
+    });
 }
 
 static int decode_loop(flm_ctx* c, int32_t first_token, int pos, int n_steps, hipEvent_t e0, hipEvent_t e1, int advance = 1) {
@@ -1010,27 +1043,22 @@ static int decode_loop(flm_ctx* c, int32_t first_token, int pos, int n_steps, hi
 
 int flm_decode_greedy(flm_ctx* c, int32_t first_token, int pos, int n_steps, int32_t* out_tokens) {
     if (!out_tokens) return FLM_ERR_INVALID;
-    for (int attempt = 0; attempt < 2; ++attempt) {
+    return with_retry(c, n_steps, [&] {
         int r = decode_loop(c, first_token, pos, n_steps, nullptr, nullptr); if (r) return r;
-        r = d2h(c, out_tokens, c->out_tokens_dev, sizeof(int) * (size_t)n_steps); if (r) return r;
-        r = xwg_check(c); if (r != FLM_RETRY) return r ? r : maybe_recover(c, n_steps);
-    }
-    return fail(c, FLM_ERR_HIP, "cross-workgroup wait timed out twice");
+        return d2h(c, out_tokens, c->out_tokens_dev, sizeof(int) * (size_t)n_steps);
+    });
 }
 
 int flm_decode_timed(flm_ctx* c, int32_t first_token, int pos, int n_steps, float* ms) {
     if (!ms || !c) return FLM_ERR_INVALID;
     HIPC(c, hipSetDevice(c->device));
     EvPair ev; HIPC(c, hipEventCreate(&ev.e0)); HIPC(c, hipEventCreate(&ev.e1));
-    int r = FLM_OK;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        r = decode_loop(c, first_token, pos, n_steps, ev.e0, ev.e1);
-        if (!r) { hipError_t e = hipEventSynchronize(ev.e1); if (e == hipSuccess) e = hipEventElapsedTime(ms, ev.e0, ev.e1); if (e != hipSuccess) { c->err = hipGetErrorString(e); r = FLM_ERR_HIP; } }
-        if (!r) r = xwg_check(c);
-        if (r != FLM_RETRY) break;
-    }
-    if (r == FLM_OK) return maybe_recover(c, n_steps);
-    return r == FLM_RETRY ? fail(c, FLM_ERR_HIP, "cross-workgroup wait timed out twice") : r;
+    return with_retry(c, n_steps, [&]() -> int {
+        int r = decode_loop(c, first_token, pos, n_steps, ev.e0, ev.e1); if (r) return r;
+        hipError_t e = hipEventSynchronize(ev.e1); if (e == hipSuccess) e = hipEventElapsedTime(ms, ev.e0, ev.e1);
+        if (e != hipSuccess) { c->err = hipGetErrorString(e); return FLM_ERR_HIP; }
+        return FLM_OK;
+    });
 }
 
 // Sampler::sample on the device (flm_sample.h): the parameters and the caller's state go to the device block first, the sampled token graphs (captured at prepare,
@@ -1044,33 +1072,25 @@ int flm_forward_sample(flm_ctx* c, const int32_t* tokens, int n, int pos, float 
     if (!tokens || !next_token) return FLM_ERR_INVALID;
     int r = check_ready(c, n, pos); if (r) return r;
     r = sample_args_ok(c, temperature, topp, rng_state); if (r) return r;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        unsigned long long s = 0;
-        r = set_sample(c, temperature, topp, *rng_state); if (r) return r;
+    unsigned long long s = 0;
+    return with_retry(c, n, [&] {
+        int r = set_sample(c, temperature, topp, *rng_state); if (r) return r;
         r = feed(c, tokens, n, pos, 3); if (r) return r;
         r = d2h(c, &s, &c->sparams->rng, sizeof s); if (r) return r;
-        r = d2h(c, next_token, c->out_tokens_dev, 4); if (r) return r;
-        r = xwg_check(c);
-        if (r == FLM_OK) { *rng_state = s; c->sampled += 1; return maybe_recover(c, n); }
-        if (r != FLM_RETRY) return r;
-    }
-    return fail(c, FLM_ERR_HIP, "cross-workgroup wait timed out twice");
+        return d2h(c, next_token, c->out_tokens_dev, 4);
+    }, [&] { *rng_state = s; c->sampled += 1; });
 }
 int flm_decode_sample(flm_ctx* c, int32_t first_token, int pos, int n_steps, float temperature, float topp, uint64_t* rng_state, int32_t* out_tokens) {
     if (!c || !out_tokens) return FLM_ERR_INVALID;
     int r = sample_args_ok(c, temperature, topp, rng_state); if (r) return r;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        unsigned long long s = 0;
-        r = check_ready(c, n_steps, pos); if (r) return r;
+    unsigned long long s = 0;
+    return with_retry(c, n_steps, [&] {
+        int r = check_ready(c, n_steps, pos); if (r) return r;       // (in front of set_sample's launch: this entry point has selected no device yet)
         r = set_sample(c, temperature, topp, *rng_state); if (r) return r;
         r = decode_loop(c, first_token, pos, n_steps, nullptr, nullptr, 3); if (r) return r;
         r = d2h(c, &s, &c->sparams->rng, sizeof s); if (r) return r;
-        r = d2h(c, out_tokens, c->out_tokens_dev, sizeof(int) * (size_t)n_steps); if (r) return r;
-        r = xwg_check(c);
-        if (r == FLM_OK) { *rng_state = s; c->sampled += n_steps; return maybe_recover(c, n_steps); }
-        if (r != FLM_RETRY) return r;
-    }
-    return fail(c, FLM_ERR_HIP, "cross-workgroup wait timed out twice");
+        return d2h(c, out_tokens, c->out_tokens_dev, sizeof(int) * (size_t)n_steps);
+    }, [&] { *rng_state = s; c->sampled += n_steps; });
 }
 
 // the ids the last flm_decode_greedy / flm_decode_sample / flm_decode_timed* call generated (still in device memory): out[n]

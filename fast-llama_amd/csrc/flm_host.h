@@ -5,10 +5,10 @@
 //   flm_layerlaunch.hip  the whole-layer launch k_attn_ffn (flm_layer.h)
 //   flm_prompt.hip       the batched prompt path (GEMM tiles on the matrix cores, prompt attention)
 //   flm_ops.hip          the op-level exports of the parity tests (flm_op_*)
+//   flm_tuning.h         the option table: one row per flm_set_option / flm_query key (flm_gpu.hip walks it)
 #pragma once
 #include "flm_gpu.h"
 #include "flm_kernels.h"
-#include "flm_tuning.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -75,7 +75,7 @@ struct flm_ctx {
     bool warmed = false;                               // flm_gpu.hip warm_up: the runtime's lazily built launch resources were set up at load time
 
     // options
-    bool tuning = false;                               // option "tuning": the experiment dials (flm_tuning.h) may be set
+    bool tuning = false;                               // option "tuning": the experiment dials (the kOptDial rows of flm_tuning.h) may be set
     int wg_per_cu = 1; int use_graph = 1; int ablate = 0;
     int graph_chunks = 1;                              // option "graph_chunks": a greedy decode loop replays graphs of up to 16 tokens (0: one graph launch per token)
     int use_mfma = 1;                                  // option "use_mfma": int8 prefill GEMM tile shape on v_mfma_i32_32x32x32_i8: 1 by size, 2 (0) 64 x 64, 3 128 x 128
@@ -104,9 +104,9 @@ struct flm_ctx {
     unsigned* tail_mem = nullptr;                      // [0] the epoch base of the one-launch token's flag values, [16 ..) one flag line per classifier workgroup, then their argmax slots
     int fuse_layer = 1;                                // option "fuse_layer": ... with the QKV GEMV in front: the whole layer in one launch
     int back_nst13 = -1, back_nst13_head = -1, back_nst2 = 0, back_pre13 = 99 /* 99: by launch (plan_layer) */, back_pre2 = 16;   // options "back_*": k_attn_ffn's stash slots (-1: as many as the LDS holds) and early register set (flm_layer.h)
-    int attn_kpre = 1;                                 // tuning dial "attn_kpre": split heads' first two K tiles by LDS-DMA under the QKV phase (BackArgs::kpre_off)
-    int back_nwo = 0;                                  // tuning dial "back_nwo": waves that hold the arrival-order Wo's steps (0: ceil(steps / 2); 16: every wave, the stash issued by all)
-    int gr_edges = 1;                                  // tuning dial "gr_edges" (round 6): the one-launch token's x / x1 hand-offs as data-tagged granules (flm_gemv.h: granule_t; BackArgs::gr); 0: flag rounds
+    int attn_kpre = 1;                                 // option "attn_kpre" (a dial): split heads' first two K tiles by LDS-DMA under the QKV phase (BackArgs::kpre_off)
+    int back_nwo = 0;                                  // option "back_nwo" (a dial): waves that hold the arrival-order Wo's steps (0: ceil(steps / 2); 16: every wave, the stash issued by all)
+    int gr_edges = 1;                                  // option "gr_edges" (round 6; public: include/flm_gpu.h): the one-launch token's x / x1 hand-offs as data-tagged granules (flm_gemv.h: granule_t; BackArgs::gr); 0: flag rounds
     granule_t* xg = nullptr; size_t x_gran_off = 0;    // ... the granule vectors [x: dim][x1: dim][att: dim][hd: hidden] (tensor parallel: a region of the exchange buffer, at x_gran_off in every rank's)
     int back_ao = 3, back_ao2 = 2;                     // options "back_ao" (bit 0: Wo, bit 1: FFN2 consume their activation in arrival order, GemvCtx::run_ao) / "back_ao2" (what of W2 is requested in front of the first look)
     int fuse_qkv = 1;                                  // option "fuse_qkv": QKV in front of attention + Wo in the same launch (k_qkv_attn_o; single GPU): 0 never,
@@ -140,15 +140,17 @@ struct flm_ctx {
     unsigned* eng_base = nullptr;                      // the token's epoch base (device memory, advanced by k_embed): the tensor-parallel exchanges' flag values count from it
     int resident = 1;                                  // the census at create saw every workgroup of a cu_count-wide launch co-resident
     int fell_back = 0;                                 // how many times a cross-workgroup wait timed out and the context went to one kernel per phase ("fallback")
-    bool fb_active = false; int fb_tokens = 0; int fb_saved[6] = {0, 0, 0, 0, 0, 0};   // ... it is there now / tokens since / the launch structure it had (restored when the census passes again: maybe_recover)
+    bool fb_active = false; int fb_tokens = 0; std::vector<int> fb_saved;   // ... it is there now / tokens since / the launch structure it had (the kOptFallback rows of flm_tuning.h, in row order; restored when the census passes again: maybe_recover)
     int trace_class = -1; unsigned long long* trace = nullptr;   // FLM_ABLATE builds: GEMV timeline of one kernel class
     // the device sampler (flm_sample.h): per-call parameters written at the start of each flm_forward_sample / flm_decode_sample (the token graphs read them), the radix
     // sort's ping-pong buffers [2][vocab], and how many tokens this context sampled on the device ("sampled_tokens")
     flm::SampleParams* sparams = nullptr; unsigned long long* sort_buf = nullptr; long long sampled = 0;
     std::map<int, hipGraphExec_t> graphs;             // key = with_cls*4 + advance (3: sampled)
     std::vector<TimedLaunch>* timing = nullptr;
+    std::vector<void*> owned;                          // every device allocation that lives as long as the context (flm_gpu.hip dev_alloc); flm_ctx_destroy frees these
     std::string err;
 };
+#include "flm_tuning.h"                                           // (the option table: member pointers into flm_ctx)
 
 namespace fh {
 

@@ -195,7 +195,7 @@ int  flm_debug_read(flm_ctx* ctx, int what, int layer, float* out, size_t n);
  *   "tp_trust_fused" 1 = between DISTINCT devices too, run the folded exchanges / rank-spanning launches (default 0: the k_xchg launches; before flm_p2p_export)
  *   "cu_parts"       n = confine the context's stream to 1/n of the device's CUs (part rank % n): several ranks on ONE GPU (tests)
  *   "force_tp"       1 = a context created with an RCCL id and world == 1 takes the sharded token path (RCCL exchanges over a 1-rank communicator; tests)
- * Not part of the boundary: the experiment dials whose optimum was measured and fixed (stash slots, early register sets, tile shapes: csrc/flm_tuning.h) are refused
+ * Not part of the boundary: the experiment dials whose optimum was measured and fixed (stash slots, early register sets, tile shapes: the rows marked kOptDial in the option table, csrc/flm_tuning.h) are refused
  * until "tuning" 1 has been set; switches that skip work ("ablate", "trace") exist only in -DFLM_ABLATE=1 builds.  Unknown key: FLM_ERR_INVALID. */
 int  flm_set_option(flm_ctx* ctx, const char* key, int value);
 /* What the context actually runs (bench.py reports it; a caller can see that a fused launch was given up).  Keys: every flm_set_option key

@@ -45,3 +45,21 @@ def test_null_arguments_are_rejected_without_a_gpu():
     assert lib.flm_forward(None, None, 1, 0, None) != 0
     assert lib.flm_op_quantize(2, None, None, None, C.c_size_t(64), 64) != 0
     assert lib.flm_ctx_create(None, 0, 0, 1, None, None) != 0
+
+
+def test_option_table_agrees_with_the_binding_and_the_header():
+    """the option table (csrc/flm_tuning.h) is the one list of flm_set_option's keys: its dials are capi.TUNING_KEYS, and the option comment of include/flm_gpu.h
+    names no key the library does not know and every key that is not a dial"""
+    table = open(os.path.join(ROOT, "fast-llama_amd", "csrc", "flm_tuning.h")).read()
+    rows = re.findall(r'^\s*\{"(\w+)",\s*(?:&flm_ctx::\w+|nullptr),\s*([^}]*)\},', table, re.M)
+    keys = [k for k, _ in rows]
+    assert len(keys) == len(set(keys)) and len(keys) >= 30, keys
+    dials = tuple(k for k, flags in rows if "kOptDial" in flags)
+    assert dials == capi.TUNING_KEYS, set(dials) ^ set(capi.TUNING_KEYS)
+    hdr = open(os.path.join(ROOT, "include", "flm_gpu.h")).read()
+    comment = hdr[hdr.index("/* Structure switches"):hdr.index("flm_set_option(flm_ctx*")]
+    documented = set(re.findall(r'"(\w+)"', comment))
+    explicit = {"tuning", "wg_per_cu", "tp_fence", "inject_wait_failure", "cu_parts", "use_p2p", "ablate", "trace"}    # the setters written out in flm_set_option
+    assert documented <= set(keys) | explicit, documented - set(keys) - explicit
+    public = {k for k in keys if k not in dials}
+    assert public <= documented, public - documented
