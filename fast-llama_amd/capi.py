@@ -29,7 +29,7 @@ SYMBOLS = (
 
 
 # the experiment dials: the kOptDial rows of csrc/flm_tuning.h, in its order (tests/test_capi_host.py compares)
-TUNING_KEYS = ("wg_per_cu", "inject_wait_failure", "use_mfma", "tok_nstq", "tok_preq", "back_nst13", "back_nst13_head", "back_nst2", "back_pre13", "back_pre2", "back_ao2", "back_nwo", "attn_kpre")
+TUNING_KEYS = ("wg_per_cu", "inject_wait_failure", "age_epochs", "use_mfma", "tok_nstq", "tok_preq", "back_nst13", "back_nst13_head", "back_nst2", "back_pre13", "back_pre2", "back_ao2", "back_nwo", "attn_kpre")
 
 
 class FlmError(RuntimeError):
@@ -202,6 +202,21 @@ class Ctx:
         v = C.c_int(0)
         _check(lib().flm_query(self._h, key.encode(), C.byref(v)), self._h)
         return int(v.value)
+
+    def age_epochs(self, e):
+        """option "age_epochs": the device state of a context whose epoch counters stand at the 32-bit value `e` (csrc/flm_tuning.h)"""
+        e &= 0xFFFFFFFF
+        self.set_option("age_epochs", e - (1 << 32) if e >= 1 << 31 else e)
+
+    def epochs(self):
+        """the epoch counters as unsigned values: (the one-launch token's, the token's epoch base, k_xchg's logits exchanges)"""
+        return tuple(self.query(k) & 0xFFFFFFFF for k in ("epoch_tail", "epoch_eng", "epoch_xchg"))
+
+    def epoch_words(self, what, n):
+        """the never-cleared flag lines ("lines") / granule tags ("tags") that count from the epoch counters, as uint32 (flm_debug_read 11 / 12)"""
+        out = np.empty(n, dtype=np.float32)
+        _check(lib().flm_debug_read(self._h, {"lines": 11, "tags": 12}[what], 0, _p(out), C.c_size_t(n)), self._h)
+        return out.view(np.uint32)
 
     def debug_read(self, what, layer, n):
         names = {"x1": 0, "q": 1, "att_out": 2, "hd": 3, "kcache": 4, "vcache": 5, "logits": 6, "trace": 7, "trace_abs": 8, "back_trace": 10}

@@ -245,9 +245,9 @@ __device__ __forceinline__ void attn_head(const AttnArgs& a, const int h, char* 
                 if (!okq) qq = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rq, tid * 8, 0, kAuxCoherent));
                 if (!okk) { KA = __builtin_bit_cast(v4u32, __builtin_amdgcn_raw_buffer_load_b128(rk, kcol * 8, 0, kAuxCoherent)); KC = __builtin_bit_cast(v4u32, __builtin_amdgcn_raw_buffer_load_b128(rk, kcol * 8 + 16, 0, kAuxCoherent)); }
                 if (!okv) { VA = __builtin_bit_cast(v4u32, __builtin_amdgcn_raw_buffer_load_b128(rv, vcol * 8, 0, kAuxCoherent)); VC = __builtin_bit_cast(v4u32, __builtin_amdgcn_raw_buffer_load_b128(rv, vcol * 8 + 16, 0, kAuxCoherent)); }
-                if (!okq) { okq = qq.y == epoch_arg; qbits = qq.x; }
-                if (!okk) okk = KA.y == epoch_arg && KA.w == epoch_arg && KC.y == epoch_arg && KC.w == epoch_arg;
-                if (!okv) okv = VA.y == epoch_arg && VA.w == epoch_arg && VC.y == epoch_arg && VC.w == epoch_arg;
+                if (!okq) { okq = tag_is(qq.y, epoch_arg); qbits = qq.x; }
+                if (!okk) okk = tag_is(KA.y, epoch_arg) && tag_is(KA.w, epoch_arg) && tag_is(KC.y, epoch_arg) && tag_is(KC.w, epoch_arg);
+                if (!okv) okv = tag_is(VA.y, epoch_arg) && tag_is(VA.w, epoch_arg) && tag_is(VC.y, epoch_arg) && tag_is(VC.w, epoch_arg);
                 if (__all(okq && okk && okv) || gave_up) break;
                 if (__builtin_amdgcn_s_memrealtime() - t0 > 2000000ull) { __hip_atomic_store(a.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
             }
@@ -321,9 +321,9 @@ __device__ __forceinline__ void attn_head(const AttnArgs& a, const int h, char* 
             if (!okq) qq = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rq, tid * 8, 0, kAuxCoherent));
             if (!okk) { KA = __builtin_bit_cast(v4u32, __builtin_amdgcn_raw_buffer_load_b128(rk, kcol * 8, 0, kAuxCoherent)); KC = __builtin_bit_cast(v4u32, __builtin_amdgcn_raw_buffer_load_b128(rk, kcol * 8 + 16, 0, kAuxCoherent)); }
             if (!okv) { VA = __builtin_bit_cast(v4u32, __builtin_amdgcn_raw_buffer_load_b128(rv, vcol * 8, 0, kAuxCoherent)); VC = __builtin_bit_cast(v4u32, __builtin_amdgcn_raw_buffer_load_b128(rv, vcol * 8 + 16, 0, kAuxCoherent)); }
-            if (!okq) { okq = qq.y == epoch_arg; qbits = qq.x; }
-            if (!okk) okk = KA.y == epoch_arg && KA.w == epoch_arg && KC.y == epoch_arg && KC.w == epoch_arg;
-            if (!okv) okv = VA.y == epoch_arg && VA.w == epoch_arg && VC.y == epoch_arg && VC.w == epoch_arg;
+            if (!okq) { okq = tag_is(qq.y, epoch_arg); qbits = qq.x; }
+            if (!okk) okk = tag_is(KA.y, epoch_arg) && tag_is(KA.w, epoch_arg) && tag_is(KC.y, epoch_arg) && tag_is(KC.w, epoch_arg);
+            if (!okv) okv = tag_is(VA.y, epoch_arg) && tag_is(VA.w, epoch_arg) && tag_is(VC.y, epoch_arg) && tag_is(VC.w, epoch_arg);
             if (__all(okq && okk && okv) || gave_up) break;
             if (__builtin_amdgcn_s_memrealtime() - t0 > 2000000ull) { __hip_atomic_store(a.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
         }
@@ -483,7 +483,7 @@ __device__ __forceinline__ void attn_head(const AttnArgs& a, const int h, char* 
             const unsigned long long ts = __builtin_amdgcn_s_memrealtime();
             while (true) {
                 asm volatile("" ::: "memory");
-                if (!ok) { const unsigned long long gv = __hip_atomic_load(sg + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); ok = (unsigned)(gv >> 32) == xepoch; bits = (unsigned)gv; }
+                if (!ok) { const unsigned long long gv = __hip_atomic_load(sg + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); ok = tag_is((unsigned)(gv >> 32), xepoch); bits = (unsigned)gv; }
                 if (__all(ok) || gave_up) break;
                 if (__builtin_amdgcn_s_memrealtime() - ts > 2000000ull) { __hip_atomic_store(a.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
             }
@@ -504,7 +504,7 @@ __device__ __forceinline__ void attn_head(const AttnArgs& a, const int h, char* 
             const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
             while (true) {
                 const unsigned f = mine ? __hip_atomic_load(a.flag_sc + (h * G + tid) * 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : xepoch;
-                if (__all((int)(f - xepoch) >= 0)) break;
+                if (__all(flag_reached(f, xepoch))) break;
                 if (__builtin_amdgcn_s_memrealtime() - t0 > 2000000ull) { __hip_atomic_store(a.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
             }
         }
@@ -1294,7 +1294,7 @@ __global__ void __launch_bounds__(kGemvBlock, 4) k_attn_o(const AttnArgs aa, con
         while (true) {
             unsigned f = target;
             if (mine) f = tp.world ? __hip_atomic_load(flag + threadIdx.x * kFlagStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : __hip_atomic_load(flag + threadIdx.x * kFlagStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (__all((int)(f - target) >= 0)) break;
+            if (__all(flag_reached(f, target))) break;
             if (__builtin_amdgcn_s_memrealtime() - t0 > (tp.world ? 2000000000ull : 2000000ull)) { __hip_atomic_store(err, tp.world ? 2 : 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }   // (ranks start seconds apart)
             if (tp.world) __builtin_amdgcn_s_sleep(4);
         }
@@ -1384,7 +1384,7 @@ __global__ void __launch_bounds__(kGemvBlock, 4) k_qkv_attn_o(const GemvArgs aq,
         while (true) {
             unsigned f = htarget;
             if (mine) f = TP ? __hip_atomic_load(flag + threadIdx.x * kFlagStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : __hip_atomic_load(flag + threadIdx.x * kFlagStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (__all((int)(f - htarget) >= 0)) break;
+            if (__all(flag_reached(f, htarget))) break;
             if (__builtin_amdgcn_s_memrealtime() - t0 > (TP ? 2000000000ull : 2000000ull)) { __hip_atomic_store(err, TP ? 2 : 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
             if constexpr (TP) __builtin_amdgcn_s_sleep(4);
         }
@@ -1450,7 +1450,7 @@ __global__ void __launch_bounds__(kGemvBlock, 4) k_ffn(const GemvArgs a13, const
         while (true) {
             unsigned f = target;
             if (mine) f = TP ? __hip_atomic_load(flag + threadIdx.x * kFlagStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : __hip_atomic_load(flag + threadIdx.x * kFlagStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (__all((int)(f - target) >= 0)) break;
+            if (__all(flag_reached(f, target))) break;
             if (__builtin_amdgcn_s_memrealtime() - t0 > (TP ? 2000000000ull : 2000000ull)) { __hip_atomic_store(err, TP ? 2 : 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
             if constexpr (TP) __builtin_amdgcn_s_sleep(4);
         }

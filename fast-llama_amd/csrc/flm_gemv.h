@@ -323,7 +323,7 @@ __device__ __forceinline__ void gemv_preload(const GemvArgs& a, float4 (&xv)[XR 
 
 // ------------------------------------------------------------------------------------------
 // Data-tagged granules (round 6; cdna_hip_programming.md G16 form R2): the residual stream crosses workgroups INSIDE k_layers' one-launch token as 8-byte {value, tag}
-// granules -- ONE aligned write-through store per element, the tag = the flag value the hand-off's line would have carried (epoch base + layer + 1: never repeats).  The
+// granules -- ONE aligned write-through store per element, the tag = the flag value the hand-off's line would have carried (epoch base + layer + 1: repeats only after a whole lap of the epoch).  The
 // data is its own flag: the producer neither drains its stores nor raises a line, the consumer neither polls lines nor reads the vector behind them -- every thread re-reads
 // ITS four granules until their tags match (only the lanes whose granules are missing read again).  One round trip instead of drain + flag + look + read
 // (tools/ubench/allgather.hip).  A granule is written by one store and read by one 16-byte load of two whole granules: no ordering between stores is relied on.
@@ -1001,7 +1001,7 @@ struct GemvCtx {
         u32 spins = 0;
         while (pending) {
             const unsigned f = mine ? __hip_atomic_load(line, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : src.target;
-            const unsigned long long okm = __ballot((int)(f - src.target) >= 0);
+            const unsigned long long okm = __ballot(flag_reached(f, src.target));
             u32 now = 0;
 #pragma unroll
             for (u32 k = 0; k < 4; ++k) if (((okm >> (16 * k)) & 0xFFFFull) == 0xFFFFull) now |= 1u << k;
@@ -1060,7 +1060,7 @@ __device__ __forceinline__ void xchg_fold(const GemvArgs::XchgFold& x) {
         const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
         while (true) {
             const unsigned f = r < x.world ? __hip_atomic_load(x.local_flags + (x.slot * 8 + r) * 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : e;
-            if (__all((int)(f - e) >= 0)) break;
+            if (__all(flag_reached(f, e))) break;
             const bool aborted = __hip_atomic_load(x.local_flags + kXchgAbortLine * 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0;
             if (aborted || __builtin_amdgcn_s_memrealtime() - t0 > 2000000000ull) {                               // 20 s: ranks start seconds apart
                 __hip_atomic_store(x.err, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);

@@ -572,13 +572,13 @@ int flm_ctx_create(const flm_model_desc* desc, int device_id, int rank, int worl
         HIPB(dev_alloc(c, &c->xepoch, 64, true));
         HIPB(dev_alloc(c, &c->ffn_counter, 64, true));
     }
-    if (world > 1) c->xg = (granule_t*)(c->xbuf + c->x_gran_off);                 // (cleared with the exchange buffer: tag 0, below every epoch)
+    if (world > 1) c->xg = (granule_t*)(c->xbuf + c->x_gran_off);                 // (cleared with the exchange buffer: tag 0, which no target of a layer is)
     else { const size_t gb = ((size_t)6 * c->d.dim + c->d.hidden_dim) * sizeof(granule_t);   /* x | x1 | att | hd | q | k | v */ HIPB(dev_alloc(c, &c->xg, gb, true)); }
     HIPB(dev_alloc(c, &c->flag_lines, 1536 * 64, true)); HIPB(dev_alloc(c, &c->xwg_err, 64, true));   // lines 0..255: k_attn_o's heads, 256..511: split heads' scores, 512..767: k_ffn, 768..1023: k_qkv_attn_o's QKV rows, 1024..1279: k_attn_ffn's x1 rows (k_embed clears all 1536)
     {   // the one-launch token (k_layers<.., TAIL>): [0] its epoch base, one flag line per classifier workgroup, their argmax slots
         const size_t tail_bytes = (16 + 256 * 16) * 4 + 256 * 2 * 4;
         HIPB(dev_alloc(c, &c->tail_mem, tail_bytes, true));
-        const unsigned e0 = 4096u; HIPB(hipMemcpyAsync(c->tail_mem, &e0, 4, hipMemcpyHostToDevice, c->stream));
+        const unsigned e0 = kEpochFirst; HIPB(hipMemcpyAsync(c->tail_mem, &e0, 4, hipMemcpyHostToDevice, c->stream));
     }
     HIPB(dev_alloc(c, &c->eng_base, 64, true));   // the token's epoch base
     for (int k = 0; k < 2; ++k) {   // k_layers' argument blocks, one set per head split (filled by layers_prepare; allocated here: nothing is allocated inside a forward)
@@ -735,6 +735,50 @@ int flm_p2p_import(flm_ctx* c, const void* blobs, int n) {
     return FLM_OK;
 }
 
+// "age_epochs" (csrc/flm_tuning.h): the device state a real run would have left with the three epoch counters at E.  The counters; and every NEVER-CLEARED line or tag that
+// counts from one of them gets what the previous token would have left there (at most one token's stride below the new counter, never above what a real run holds): a line
+// left at its fresh 0 next to a counter of 0xFFFF_FF00 is a state no run can reach.  What k_embed clears every token (c->flag_lines) is left alone.
+__global__ void k_fill_words(unsigned* p, size_t n, unsigned stride, unsigned v) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i * stride] = v;
+}
+// the never-cleared regions of this context: lines (64 bytes apart) and granule tags (the high word of 8 bytes), by the counter their values count from
+struct EpochRegion { unsigned* first; size_t n; unsigned stride; int counter; /* 0 the one-launch token's epoch, 1 the token's epoch base, 2 k_xchg's per-kind counters */ bool tag; };
+static std::vector<EpochRegion> epoch_regions(flm_ctx* c) {
+    std::vector<EpochRegion> v;
+    const auto& d = c->d;
+    v.push_back({c->tail_mem + 16, 256, 16, 0, false});                                                        // the classifier workgroups' lines
+    if (c->world > 1) {
+        v.push_back({(unsigned*)(c->xbuf + c->x_flags_off), 4 * 8, 16, 2, false});                             // k_xchg's [kind][rank] lines
+        v.push_back({(unsigned*)(c->xbuf + c->x_flags_off) + 4 * 8 * 16, (size_t)(kXchgSlots - 4) * 8, 16, 1, false});   // the folded exchanges' [slot][rank] lines (not the abort line behind them)
+        v.push_back({(unsigned*)(c->xbuf + c->x_hflags_off), 256 + 8, 16, 1, false});                          // k_attn_o's / k_ffn's lines across ranks
+        v.push_back({(unsigned*)(c->xbuf + c->x_tlines_off), (size_t)(1 + 4 * c->world) * kTpLinesPerRank, 16, 1, false});   // the rank-spanning k_layers' lines
+        v.push_back({(unsigned*)(c->xbuf + c->x_gran_off) + 1, (size_t)3 * d.dim + d.hidden_dim, 2, 1, true});   // ... and its granule vectors
+    } else v.push_back({(unsigned*)c->xg + 1, (size_t)6 * d.dim + d.hidden_dim, 2, 0, true});                  // the one-launch token's granule vectors
+    v.push_back({(unsigned*)c->att_sc + 1, (size_t)c->heads_local * d.max_seq_len, 2, c->world > 1 ? 1 : 0, true});   // the split heads' score granules
+    return v;
+}
+static int age_epochs(flm_ctx* c, unsigned E) {
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    const unsigned Eb = E & ~(kEpochStride - 1u), L = (unsigned)c->d.n_layers;
+    const unsigned counters[8] = {E, Eb, E, E, E, E};                                      // tail_mem[0] | eng_base | xepoch[4]
+    // the lowest value the last token raised, per counter: the one-launch token moves its epoch on when it ends (the last token counted from E - (L + 2)), k_embed moves the
+    // token's epoch base on when a token starts (the last token counted from Eb itself), k_xchg's lines hold the counter's own value
+    const unsigned prev[3] = {E - (L + 2u) + 1u, Eb + 1u, E};
+    HIPC(c, hipMemcpyAsync(c->tail_mem, &counters[0], 4, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync(c->eng_base, &counters[1], 4, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipMemcpyAsync(c->xepoch, &counters[2], 16, hipMemcpyHostToDevice, c->stream));
+    HIPC(c, hipStreamSynchronize(c->stream));                                              // (counters goes out of scope)
+    for (const auto& r : epoch_regions(c)) {
+        const unsigned blocks = (unsigned)((r.n + 255) / 256);
+        // (the classifier lines hold the token's LAST value, its argmax round's: epoch - 1)
+        hipLaunchKernelGGL(k_fill_words, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, c->stream, r.first, r.n, r.stride, r.counter == 0 && !r.tag ? E - 1u : prev[r.counter]);
+        HIPC(c, hipGetLastError());
+    }
+    HIPC(c, hipStreamSynchronize(c->stream));
+    return FLM_OK;
+}
+
 int flm_set_option(flm_ctx* c, const char* key, int value) {
     if (!c || !key) return FLM_ERR_INVALID;
     const std::string k(key);
@@ -752,6 +796,7 @@ int flm_set_option(flm_ctx* c, const char* key, int value) {
         if (value) { const int one = 1; HIPC(c, hipMemcpyAsync(c->xwg_err, &one, 4, hipMemcpyHostToDevice, c->stream)); HIPC(c, hipStreamSynchronize(c->stream)); }
         return FLM_OK;
     }
+    if (k == "age_epochs") return age_epochs(c, (unsigned)value);
     if (k == "wg_per_cu") c->wg_per_cu = value > 0 ? value : 1;
     else if (k == "tp_fence") c->tp_fence = value < 0 ? -1 : value & 3;
     else if (k == "cu_parts") {
@@ -794,6 +839,15 @@ int flm_query(flm_ctx* c, const char* key, int* value) {
     if (!c || !key || !value) return FLM_ERR_INVALID;
     const std::string k(key);
     for (const auto& o : kOptions) if (o.member && k == o.key) { *value = c->*o.member; return FLM_OK; }
+    if (k == "epoch_tail" || k == "epoch_eng" || k == "epoch_xchg") {   // the epoch counters' current values (device memory; the bit pattern): the one-launch token's, the token's epoch base, k_xchg's logits exchanges
+        const unsigned* src = k == "epoch_tail" ? c->tail_mem : k == "epoch_eng" ? c->eng_base : c->xepoch + XK_LOGITS;
+        unsigned v = 0;
+        HIPC(c, hipSetDevice(c->device));
+        HIPC(c, hipMemcpyAsync(&v, src, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPC(c, hipStreamSynchronize(c->stream));
+        *value = (int)v;
+        return FLM_OK;
+    }
     const bool tp = c->world > 1 && c->p2p, tpl = tp && c->grp_tpl;
     // the granule hand-offs are what the one-launch token / the rank-spanning launch of head split i runs
     auto gr = [&](int i) { return c->la_valid[i] && c->la_ok[i] && c->la_p[i].gr && (c->world > 1 ? tpl : c->tail_ok[i]); };
@@ -945,7 +999,7 @@ int flm_reset_kv(flm_ctx* c) {
     return FLM_OK;
 }
 
-// debugging tap (tests): copy an internal device buffer to the host. what: 0 x1, 1 q, 2 att_out, 3 hd, 4 kcache(layer), 5 vcache(layer), 6 logits
+// debugging tap (tests): copy an internal device buffer to the host. what: 0 x1, 1 q, 2 att_out, 3 hd, 4 kcache(layer), 5 vcache(layer), 6 logits, 11 / 12 the epoch lines / tags
 int flm_debug_read(flm_ctx* c, int what, int layer, float* out, size_t n) {
     if (!c || !out) return FLM_ERR_INVALID;
     HIPC(c, hipSetDevice(c->device));
@@ -1001,6 +1055,17 @@ int flm_debug_read(flm_ctx* c, int what, int layer, float* out, size_t n) {
         // (words [4 * 4096, 5 * 4096): 100 MHz stamps again -- FFN13's run() --, relative to the same start)
         for (size_t i = nrt; i < n && i < 4 * 4096; ++i) { const size_t b = i - i % 16; out[i] = i % 16 == 15 ? (float)t[i] : ((t[i] && t[b]) ? (float)(long long)(t[i] - t[b]) : -1.f); }
         for (size_t i = 4 * 4096; i < n; ++i) out[i] = t[i] ? (float)((double)(long long)(t[i] - t0) * 0.01) : -1.f;
+        return FLM_OK; }
+    case 11: case 12: {   // the never-cleared flag lines (11) / granule tags (12) that count from the epoch counters ("age_epochs"), region by region in epoch_regions' order: raw 32-bit words
+        size_t at = 0;
+        for (const auto& r : epoch_regions(c)) {
+            if (r.tag != (what == 12) || at >= n) continue;
+            const size_t m = r.n < n - at ? r.n : n - at;
+            HIPC(c, hipMemcpy2DAsync(out + at, 4, r.first, (size_t)r.stride * 4, 4, m, hipMemcpyDeviceToHost, c->stream));
+            at += m;
+        }
+        HIPC(c, hipStreamSynchronize(c->stream));
+        if (at < n) return fail(c, FLM_ERR_INVALID, "debug_read: size");
         return FLM_OK; }
     default: return fail(c, FLM_ERR_INVALID, "debug_read: unknown buffer");
     }

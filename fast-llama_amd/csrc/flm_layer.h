@@ -52,7 +52,7 @@ struct BackArgs {
     unsigned long long* trace;  // FLM_ABLATE builds: [grid][16] s_memrealtime stamps (100 MHz, one clock for all XCDs; tools/trace_back.py)
     // round 6: the residual stream as data-tagged granules inside the one-launch token (flm_gemv.h: granule_t): xg_a = x behind FFN2 (the next layer's / the classifier's input),
     // xg_b = x1 behind Wo (FFN13's input), [dim] each.  gr = 1: the two strict all-to-all edges of a layer carry no flag round -- the consumers sweep the granules themselves.
-    // (TAIL launches only: their flag values count from an epoch and never repeat; the launch's first layer reads the embedding row, nothing else reads x.)
+    // (TAIL launches only: their flag values count from an epoch and repeat only after a lap of it -- every granule is rewritten every token; the launch's first layer reads the embedding row, nothing else reads x.)
     // Tensor parallel (k_layers<.., TP>): ALL four cross-rank vectors of a layer are granules in every rank's exchange buffer -- xg_att = the heads' fp32 output, xg_hd = FFN13's hd
     // too --, so the rank-spanning launch raises no line and needs no fence: a granule is ONE 8-byte store (over xGMI: one write), and nothing is inferred from the order of stores.
     // xg_hd also serves any launch whose FFN2 takes hd in its all-to-all form (R5 bit 1 clear: int16 7B).  gres_off: this rank's first row of the residual stream (0 on one GPU).
@@ -92,7 +92,7 @@ __device__ __forceinline__ void poll_wave(const unsigned* line, bool mine, unsig
     unsigned f = look();
     if (gave_up) return;
     while (true) {
-        if (__all((int)(f - target) >= 0)) break;
+        if (__all(flag_reached(f, target))) break;
         f = look();
         if (__builtin_amdgcn_s_memrealtime() - t0 > 2000000ull) { __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
     }
@@ -104,7 +104,7 @@ __device__ __forceinline__ void poll_wave(const unsigned* line, bool mine, unsig
         bool done = false;
 #pragma unroll
         for (int i = 0; i < FLM_POLL_DEPTH; ++i) {
-            if (__all((int)(f[i] - target) >= 0)) { done = true; break; }
+            if (__all(flag_reached(f[i], target))) { done = true; break; }
             f[i] = look();
             __builtin_amdgcn_s_sleep(FLM_POLL_GAP);
         }
@@ -125,7 +125,7 @@ __device__ __forceinline__ void poll_wave_tp(const unsigned* line, bool mine, un
     unsigned spins = 0;
     while (true) {
         const unsigned f = mine ? __hip_atomic_load(line, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : target;
-        if (__all((int)(f - target) >= 0)) break;
+        if (__all(flag_reached(f, target))) break;
         if ((++spins & 255u) == 0u) {
             const bool aborted = __hip_atomic_load(p.tp.peer[p.tp.rank] + p.tp.abort_off, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0 || __hip_atomic_load(p.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
             if (aborted || __builtin_amdgcn_s_memrealtime() - t0 > 2000000000ull) {
@@ -192,7 +192,7 @@ __device__ __forceinline__ void gemv_preload_granules(const GemvArgs& a, float4 
         }
         bool all = true;
 #pragma unroll
-        for (int i = 0; i < XR; ++i) { if (!ok[i]) ok[i] = A[i].y == tag && A[i].w == tag && C[i].y == tag && C[i].w == tag; all = all && ok[i]; }
+        for (int i = 0; i < XR; ++i) { if (!ok[i]) ok[i] = tag_is(A[i].y, tag) && tag_is(A[i].w, tag) && tag_is(C[i].y, tag) && tag_is(C[i].w, tag); all = all && ok[i]; }
         if (__all(all) || gave_up) break;
         if constexpr (!TP) {
             if (__builtin_amdgcn_s_memrealtime() - t0 > 2000000ull) { __hip_atomic_store(p.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
@@ -482,11 +482,12 @@ struct LayerArgs { GemvArgs aq, ao, a13, a2; AttnArgs aa; };
 // rows of the output matrix: transformer.cpp:154-160) is a phase behind the last layer's x flag round like the QKV phase of a layer (its first register sets and stash slots requested in
 // front of that round), and the greedy argmax (first maximum wins, sampler.cpp:36-47) + the decode state's advance close it: every classifier workgroup leaves the best of its own rows
 // in a slot and raises a line, workgroup 0 waits for all of them and picks.  Nobody clears the flag lines between tokens (k_embed did): every target of the launch counts from an epoch
-// base in device memory that the launch's last act moves on by L + 2 -- stale lines are always below.  fp32 embedding tables only (the host checks).
+// base in device memory that the launch's last act moves on by L + 2 (back to kEpochFirst at kEpochWrap) -- stale lines are always outside the window above the target
+// (flm_math.h flag_reached).  fp32 embedding tables only (the host checks).
 struct TailArgs {
     GemvArgs acls;              // the classifier GEMV (EPI_STORE into the logits)
     const float* emb; const int* tok_ptr; int dim, vocab;
-    unsigned* epoch;            // the launch's flag values count from *epoch (>= 4096: above anything k_embed-era launches leave in a line)
+    unsigned* epoch;            // the launch's flag values count from *epoch (in [kEpochFirst, kEpochWrap + L + 2): above anything k_embed-era launches leave in a line, kEpochWindow below 2^32)
     unsigned* flag_cls;         // one line per classifier workgroup
     float* slots;               // [gridc][2] { best logit, its row (as bits) } of a workgroup's rows
     int gridc;
@@ -543,7 +544,7 @@ __device__ __forceinline__ void tail_phase(const TailArgs& T, const BackArgs& p,
             DecodeState* st = T.st;
             if (T.out_tokens && st->step >= 0 && st->step < T.out_cap) T.out_tokens[st->step] = idx;
             st->tok = idx; st->pos += 1; st->step += 1;
-            *T.epoch = next_epoch;
+            *T.epoch = (FLM_WAIT_FORM == 0 && next_epoch >= kEpochWrap) ? kEpochFirst : next_epoch;     // (flm_math.h flag_reached: the epochs stay inside [kEpochFirst, kEpochWrap + L + 2))
         }
     }
 }

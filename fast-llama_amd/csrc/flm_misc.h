@@ -16,8 +16,10 @@ namespace flm {
 constexpr unsigned kEpochStride = 1024;      // the token's epoch base advances by this: exchanges (4 per layer + 2) per token must stay below it
 inline __global__ void k_embed(float* x, const void* emb, const float* emb_s, int emb_qt, int dim, const int* tok_ptr, unsigned* bar, unsigned* eng_base = nullptr, unsigned long long* ffn_counter = nullptr) {
     const int tok = *tok_ptr;
-    // a new token: the epoch base of the tensor-parallel exchanges' flag values moves on; wrap long before a value could become 0
-    if (eng_base && blockIdx.x == 0 && threadIdx.x == 0) { const unsigned b = *eng_base; *eng_base = b >= 0xFFF00000u ? 0u : b + kEpochStride; }
+    // a new token: the epoch base of the tensor-parallel exchanges' flag values moves on; back to 0 at kEpochWrap, so that no target comes within kEpochWindow of 2^32
+    // (flm_math.h flag_reached: the local lines cleared below must stay outside every target's window; the never-cleared cross-rank lines then hold values of the previous
+    //  lap, far above the new targets' windows)
+    if (eng_base && blockIdx.x == 0 && threadIdx.x == 0) { const unsigned b = *eng_base; *eng_base = b >= (FLM_WAIT_FORM == 0 ? kEpochWrap : 0xFFF00000u) ? 0u : b + kEpochStride; }
     // k_ffn<TP> finds a rank's last workgroup with (count + 1) % grid: a new token starts the count at 0, whatever grid earlier launches had (or a launch that gave up left behind)
     if (ffn_counter && blockIdx.x == 0 && threadIdx.x == 0) *ffn_counter = 0ull;
     if (bar && blockIdx.x == 0) {   // the flag lines (kFlagLines = 1536, 64 B apart) the workgroups of the token's fused launches wait on
@@ -97,7 +99,7 @@ inline __global__ void __launch_bounds__(64) k_xchg(const XchgArgs x) {
     const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
     while (true) {
         const unsigned f = r < x.world ? __hip_atomic_load(x.local_flags + (x.kind * 8 + r) * 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : e;
-        if (__all((int)(f - e) >= 0)) break;
+        if (__all(flag_reached(f, e))) break;
         // ranks start seconds apart (graph capture, module loading): be patient; but once ANY rank has given up, everybody leaves at once
         const bool aborted = __hip_atomic_load(x.local_flags + kXchgAbortLine * 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0;
         if (aborted || __builtin_amdgcn_s_memrealtime() - t0 > 2000000000ull) {                                   // 20 s of the 100 MHz clock

@@ -24,6 +24,12 @@
 //                      one kernel per phase and the context stays there for 64 tokens ("fallback" 1, "fallback_active" 1), then takes the census again and returns to the launch
 //                      structure it had (maybe_recover) -- the error path of a 20 ms time-out, exercised by tests/test_gpu_model.py without waiting for one.  An action, not a
 //                      value: no member, and flm_query does not know it
+//   "age_epochs"       value = the 32-bit pattern E: put the context's device state into what a real run would have left with its epoch counters at E -- the one-launch token's
+//                      epoch (TailArgs::epoch), the token's epoch base of the tensor-parallel hand-offs (rounded down to a multiple of the token's stride) and k_xchg's four exchange
+//                      counters --, every never-cleared flag line and granule tag that counts from one of them holding what the previous token would have left (flm_gpu.hip
+//                      age_epochs).  Days of decoding in one call: tests/test_gpu_longlived.py carries contexts across 2^31 and the counters' wrap with it.  Between two calls, and
+//                      under tensor parallelism on every rank alike before the next token.  An action like "inject_wait_failure"; flm_query reads the counters back as
+//                      "epoch_tail" / "epoch_eng" / "epoch_xchg"
 // Numbers behind the defaults: DESIGN.md section 7c / 7d, tools/back_bench.py.
 #pragma once
 namespace fh {
@@ -32,13 +38,14 @@ constexpr unsigned kOptResident = 2;   // a non-zero value needs one workgroup p
 constexpr unsigned kOptFrozen = 4;     // which prompt kernels a tensor-parallel group runs: refused once flm_p2p_import has agreed on them
 constexpr unsigned kOptFallback = 8;   // the launch structure that waits across workgroups: saved and zeroed when a wait gives up (xwg_check), restored by maybe_recover
 struct OptionRow { const char* key; int flm_ctx::* member; unsigned flags; };
-// Keys whose setter does more than store the value ("wg_per_cu", "tp_fence": clamped; "inject_wait_failure", "cu_parts", "use_p2p") have their row here -- flags, and the member
+// Keys whose setter does more than store the value ("wg_per_cu", "tp_fence": clamped; "inject_wait_failure", "age_epochs", "cu_parts", "use_p2p") have their row here -- flags, and the member
 // flm_query reports -- and their code in flm_set_option.  "tuning" (a bool) and FLM_ABLATE's "ablate" / "trace" (not queryable) are not rows.
 constexpr OptionRow kOptions[] = {
     {"wg_per_cu", &flm_ctx::wg_per_cu, kOptDial},
     {"use_graph", &flm_ctx::use_graph, 0},
     {"graph_chunks", &flm_ctx::graph_chunks, 0},
     {"inject_wait_failure", nullptr, kOptDial},
+    {"age_epochs", nullptr, kOptDial},
     {"use_prefill", &flm_ctx::use_prefill, 0},
     {"use_mfma", &flm_ctx::use_mfma, kOptDial | kOptFrozen},
     {"use_pv_mfma", &flm_ctx::use_pv_mfma, kOptFrozen},

@@ -157,7 +157,8 @@ int  flm_kernel_bytes(flm_ctx* ctx, int kclass, int pos, double* bytes);
 
 /* debugging tap for the parity tests: copy an internal fp32 device buffer to the host.
  * what: 0 residual x1[dim], 1 q[dim], 2 attention output[dim], 3 hd[hidden], 4 K cache of `layer`
- * [heads][max_seq][hs], 5 V cache of `layer`, 6 logits. */
+ * [heads][max_seq][hs], 5 V cache of `layer`, 6 logits; 11 / 12 the never-cleared flag lines / granule tags that
+ * count from the epoch counters, as raw 32-bit words (the long-lived-context tests). */
 int  flm_debug_read(flm_ctx* ctx, int what, int layer, float* out, size_t n);
 
 /* Structure switches: which launches a token runs.  None of them changes a result bit; the defaults are what was measured fastest.
@@ -210,7 +211,9 @@ int  flm_set_option(flm_ctx* ctx, const char* key, int value);
  *               (the whole layer in one launch), bit 9 all layers of the token in one launch (k_layers), bit 10 a greedy decode token is ONE launch (embedding row, layers,
  *               classifier, argmax in k_layers<.., TAIL>),
  *   "ao_active" which hand-offs of that launch are consumed in arrival order: bit 0 Wo, bit 1 FFN2 (-1: the launch has not been planned yet),
- *   "sampled_tokens" how many tokens this context sampled on the device (flm_forward_sample / flm_decode_sample).
+ *   "sampled_tokens" how many tokens this context sampled on the device (flm_forward_sample / flm_decode_sample),
+ *   "epoch_tail" / "epoch_eng" / "epoch_xchg" the epoch counters the cross-workgroup waits count from (device memory; the 32-bit pattern): the one-launch token's, the
+ *               tensor-parallel token's epoch base, k_xchg's logits exchanges (the long-lived-context tests).
  * Unknown key: FLM_ERR_INVALID. */
 int  flm_query(flm_ctx* ctx, const char* key, int* value);
 

@@ -489,11 +489,11 @@ def test_a_wait_that_gives_up_is_retried_on_one_kernel_per_phase(gpu):
 
 # every flm_set_option key with the initialiser of its flm_ctx member, and every read-only flm_query key: written out from the library's code as it stood before the option
 # table (csrc/flm_tuning.h) existed, NOT generated from the table -- the table is what this list checks
-OPTION_DEFAULTS = {"tuning": 0, "wg_per_cu": 1, "use_graph": 1, "graph_chunks": 1, "inject_wait_failure": None, "use_prefill": 1, "use_mfma": 1, "use_pv_mfma": 1, "use_qk_mfma": 1, "use_prefill_mq": 1,
+OPTION_DEFAULTS = {"tuning": 0, "wg_per_cu": 1, "use_graph": 1, "graph_chunks": 1, "inject_wait_failure": None, "age_epochs": None, "use_prefill": 1, "use_mfma": 1, "use_pv_mfma": 1, "use_qk_mfma": 1, "use_prefill_mq": 1,
                    "fuse_attn_o": 1, "fuse_ffn": 1, "fuse_qkv": 1, "fuse_back": 1, "fuse_layer": 1, "fuse_token": 1, "fuse_tail": 1, "tok_nstq": 4, "tok_preq": 99, "back_nst13": -1, "back_nst13_head": -1,
                    "back_nst2": 0, "back_pre13": 99, "back_pre2": 16, "back_ao": 3, "back_ao2": 2, "back_nwo": 0, "attn_kpre": 1, "gr_edges": 1, "attn_split": 1, "fold_xchg": 1, "tp_fuse_attn": 2,
                    "tp_fuse_ffn": 0, "tp_fuse_layers": 1, "tp_fence": -1, "tp_trust_fused": 0, "force_tp": 0, "cu_parts": 1, "use_p2p": 0}
-OPTION_DIALS = ("wg_per_cu", "use_mfma", "tok_preq", "tok_nstq", "back_nst13", "back_nst13_head", "back_nst2", "back_pre13", "back_pre2", "back_ao2", "attn_kpre", "back_nwo", "inject_wait_failure")
+OPTION_DIALS = ("wg_per_cu", "use_mfma", "tok_preq", "tok_nstq", "back_nst13", "back_nst13_head", "back_nst2", "back_pre13", "back_pre2", "back_ao2", "attn_kpre", "back_nwo", "inject_wait_failure", "age_epochs")
 DERIVED_QUERY_KEYS = ("kpre_active", "nwo_active", "preq_active", "pre13_active", "preq_active_split", "pre13_active_split", "gr_active", "fold_active", "span_active", "tp_fence_active", "grp_gr",
                       "grp_tp_fuse_layers", "tp_layers_active", "grp_tp_fuse_attn", "grp_tp_fuse_ffn", "grp_attn_split", "resident", "fallback", "fallback_active", "sampled_tokens", "ao_active", "token_path")
 
@@ -520,13 +520,13 @@ def test_option_and_query_surface(gpu):
         ctx.set_option("engine", 1)                            # round 3's engine left the library
     # the experiment dials (csrc/flm_tuning.h) are not part of the boundary: refused until "tuning" is set
     # the complete surface, on a fresh context: every option reads back its default and takes it again (a dial only behind "tuning"); the read-only keys answer;
-    # "inject_wait_failure" is an action and cannot be queried
-    assert len(OPTION_DEFAULTS) == 39 and set(OPTION_DIALS) < set(OPTION_DEFAULTS) and sorted(gpu.TUNING_KEYS) == sorted(OPTION_DIALS)
+    # "inject_wait_failure" and "age_epochs" are actions and cannot be queried
+    assert len(OPTION_DEFAULTS) == 40 and set(OPTION_DIALS) < set(OPTION_DEFAULTS) and sorted(gpu.TUNING_KEYS) == sorted(OPTION_DIALS)
     fresh = gpu.Ctx(gpu.desc_from_config(cfg))
     assert fresh.query("resident") == 1
     for key in DERIVED_QUERY_KEYS:
         fresh.query(key)
-    for key in ("inject_wait_failure", "ablate", "trace"):
+    for key in ("inject_wait_failure", "age_epochs", "ablate", "trace"):
         with pytest.raises(gpu.FlmError):
             fresh.query(key)
     for tuning in (0, 1):
@@ -548,7 +548,7 @@ def test_option_and_query_surface(gpu):
             ctx.set_option(key, 1, unlock=False)
     ctx.set_option("tuning", 1)
     for key in gpu.TUNING_KEYS:
-        if key != "inject_wait_failure":                       # (an action, not a value)
+        if key not in ("inject_wait_failure", "age_epochs"):   # (actions, not values)
             ctx.set_option(key, ctx.query(key), unlock=False)
     ctx.close()
     om = O.OracleModel(cfg, tensors)
