@@ -24,8 +24,11 @@ SYMBOLS = (
     "flm_kernel_times", "flm_kernel_bytes", "flm_set_option", "flm_query", "flm_debug_read",
     "flm_op_quantize", "flm_op_matmul_q", "flm_op_rmsnorm", "flm_op_swiglu", "flm_op_rope", "flm_op_softmax",
     "flm_op_attention", "flm_op_expf", "flm_op_math", "flm_op_square_sum", "flm_op_argmax", "flm_op_handoff_litmus", "flm_plan_shards",
-    "flm_forward_sample", "flm_decode_sample", "flm_op_sample",
+    "flm_forward_sample", "flm_decode_sample", "flm_op_sample", "flm_generate",
 )
+
+# flm_token_cb: int (*)(void* user, int index, int32_t token, int last); a non-zero return cancels
+TOKEN_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int32, C.c_int)
 
 
 # the experiment dials: the kOptDial rows of csrc/flm_tuning.h, in its order (tests/test_capi_host.py compares)
@@ -166,6 +169,29 @@ class Ctx:
         _check(lib().flm_decode_sample(self._h, int(first_token), int(pos), int(n_steps), C.c_float(temperature), C.c_float(topp), C.byref(st), _p(out)), self._h)
         return out, st.value
 
+    def generate(self, prompt, pos, max_tokens, temperature=0.0, topp=0.9, rng_state=0, stop_token=-1, on_token=None, want_ids=True):
+        """flm_generate -> (ids[n_out], the sampler state after the n_out draws).  on_token(index, token, last) is called per token while the device computes the next
+        ones; a truthy return cancels.  want_ids=False passes out_tokens = NULL (the ids then come through on_token only; the returned array is empty)."""
+        t = np.ascontiguousarray(prompt, dtype=np.int32)
+        out = np.empty(max(int(max_tokens), 1), dtype=np.int32) if want_ids else None
+        st = C.c_uint64(int(rng_state)); n_out = C.c_int(0)
+        raised = []
+
+        def tramp(_user, index, token, last):
+            try:
+                return 1 if on_token(int(index), int(token), bool(last)) else 0
+            except BaseException as e:      # (an exception must not unwind through the C frames: cancel, re-raise behind the call)
+                raised.append(e)
+                return 1
+        cb = TOKEN_CB(tramp) if on_token is not None else C.cast(None, TOKEN_CB)      # (kept alive by this frame for the duration of the call)
+        rc = lib().flm_generate(self._h, _p(t), len(t), int(pos), int(max_tokens), C.c_float(temperature), C.c_float(topp), C.byref(st),
+                                C.c_int32(int(stop_token)), cb, None, _p(out), C.byref(n_out))
+        del cb
+        if raised:
+            raise raised[0]
+        _check(rc, self._h)
+        return (out[:n_out.value].copy() if want_ids else np.empty(0, dtype=np.int32)), st.value
+
     def decode_timed(self, first_token, pos, n_steps) -> float:
         ms = C.c_float(0)
         _check(lib().flm_decode_timed(self._h, int(first_token), int(pos), int(n_steps), C.byref(ms)), self._h)
@@ -217,6 +243,13 @@ class Ctx:
         out = np.empty(n, dtype=np.float32)
         _check(lib().flm_debug_read(self._h, {"lines": 11, "tags": 12}[what], 0, _p(out), C.c_size_t(n)), self._h)
         return out.view(np.uint32)
+
+    def gen_ring(self, n):
+        """the first n granules of flm_generate's ring as the last call left them (flm_debug_read 13) -> (tokens, last bits, tags)"""
+        out = np.empty(2 * n, dtype=np.float32)
+        _check(lib().flm_debug_read(self._h, 13, 0, _p(out), C.c_size_t(2 * n)), self._h)
+        w = out.view(np.uint32).reshape(n, 2)
+        return (w[:, 0] & 0x7FFFFFFF).astype(np.int64), (w[:, 0] >> 31).astype(np.int64), w[:, 1].astype(np.int64)
 
     def debug_read(self, what, layer, n):
         names = {"x1": 0, "q": 1, "att_out": 2, "hd": 3, "kcache": 4, "vcache": 5, "logits": 6, "trace": 7, "trace_abs": 8, "back_trace": 10}

@@ -30,6 +30,7 @@ struct AttnArgs {
     const float* vcache;
     float* out;              // [heads*hs]
     const int* pos_ptr;
+    const int* halt;         // the decode state's latch (flm_math.h DecodeState::halt), read once at the launch's top; null: no state (op level, prompt kernels, tensor parallel)
     int hs, max_seq;
     int kv_rows;             // rows per head in the caches (0 = max_seq): the context pads the stride between two heads' rows -- at a power-of-two stride the heads' K / V streams share memory channels
     unsigned long long* trace;   // FLM_ABLATE builds: [head][8] s_memtime stamps
@@ -1241,6 +1242,7 @@ inline __global__ void __launch_bounds__(256) k_attn_pv_mfma(const AttnArgs a, i
 template <bool SPLIT>
 __global__ void __launch_bounds__(kAttnBlock) k_attn_decode(const AttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
+    if (halted(a.halt)) return;
     const int G = SPLIT ? a.G : 1;
     attn_head_any<false, SPLIT>(a, blockIdx.x / G, lds, *a.pos_ptr + 1, a.q, a.out, blockIdx.x % G, G);
 }
@@ -1265,6 +1267,7 @@ struct AoTp { unsigned* peer_flags[8]; const unsigned* base; unsigned add; int w
 template <int QT, int XR, bool PREQ, bool SPLIT = false>
 __global__ void __launch_bounds__(kGemvBlock, 4) k_attn_o(const AttnArgs aa, const GemvArgs a, const int n_heads, unsigned* flag, const unsigned target_, int* err, const AoTp tp) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
+    if (halted(a.halt)) return;
     auto stamp = [&](int k) { if (kAblate && a.trace && threadIdx.x == 0) a.trace[blockIdx.x * 8 + k] = __builtin_amdgcn_s_memtime(); };   // tools/trace_ao.py
     stamp(0);
     const unsigned target = tp.world ? *tp.base + tp.add : target_;
@@ -1326,6 +1329,7 @@ template <int QT, int XR, bool PREQ, bool SPLIT = false, bool TP = false>
 __global__ void __launch_bounds__(kGemvBlock, 4) k_qkv_attn_o(const GemvArgs aq, const AttnArgs aa, const GemvArgs a, const int gridq, const int n_heads, const int grido,
                                                               unsigned* flagq, unsigned* flag, const unsigned target, int* err, const AoTp tp) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
+    if constexpr (!TP) { if (halted(a.halt)) return; }
     auto nostamp = [](int) {};
     const unsigned htarget = TP ? *tp.base + tp.add : target;                   // the heads' lines (epoch values across ranks); flagq keeps `target`
     if constexpr (TP) { if (aq.xf.world) xchg_fold(aq.xf); }
@@ -1418,6 +1422,7 @@ struct FfnTp { unsigned* peer_flags[8]; const unsigned* base; unsigned add; int 
 template <int QT, int XR2, bool TP = false>
 __global__ void __launch_bounds__(kGemvBlock, 4) k_ffn(const GemvArgs a13, const GemvArgs a2, const int grid13, const int grid2, unsigned* flag, const unsigned target_, int* err, const FfnTp tp) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
+    if constexpr (!TP) { if (halted(a2.halt)) return; }
     auto nostamp = [](int) {};
     const unsigned target = TP ? *tp.base + tp.add : target_;
     if constexpr (TP) { if (a13.xf.world) xchg_fold(a13.xf); }                  // (every workgroup: the barrier inside is the workgroup's own)

@@ -29,6 +29,7 @@ struct GemvArgs {
     float* kcache; float* vcache;               // ROPE_KV: this layer's caches [heads][max_seq][hs]
     const float* rope_cos; const float* rope_sin; // [max_seq][hs/2]
     const int* pos_ptr;                         // device-resident position
+    const int* halt;                            // the decode state's latch (flm_math.h DecodeState::halt), read once at the launch's top; null: no state (op level, tensor parallel)
     int dim; int kv_dim; int max_seq; int hs;   // ROPE_KV geometry
     // tensor parallel, peer-to-peer: every result is also stored into the same place of every peer rank's buffer (mapped over
     // xGMI; system-scope stores), so that after the launch plus one flag round every rank holds the whole vector.
@@ -1078,6 +1079,7 @@ __device__ __forceinline__ void xchg_fold(const GemvArgs::XchgFold& x) {
 template <int QT, int PRO, int EPI, int XR, bool COH = false>
 __global__ void __launch_bounds__(kGemvBlock, 4) k_gemv(const GemvArgs a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
+    if (halted(a.halt)) return;
     unsigned long long rt0 = 0;
 #ifdef FLM_TRACE_WAVES
     auto stamp = [&](int k) { if (kAblate && a.trace && threadIdx.x == 0 && k == 0) a.trace[blockIdx.x * 8 + k] = __builtin_amdgcn_s_memtime(); };

@@ -324,6 +324,15 @@ int alloc_run_bufs(flm_ctx* c) {
     HIPC(c, dev_alloc(c, &c->out_tokens_dev, sizeof(int) * c->out_cap));
     c->bounce_bytes = (size_t)d.vocab_size * 4; if (c->bounce_bytes < sizeof(int) * (size_t)d.max_seq_len) c->bounce_bytes = sizeof(int) * (size_t)d.max_seq_len;
     HIPC(c, hipHostMalloc((void**)&c->bounce, c->bounce_bytes + 64, hipHostMallocDefault));          // (+ a line for the error word that rides along: d2h)
+    {   // flm_generate's granule ring (max_seq_len entries of 8 bytes) and, a line behind it, the cancel word: the device stores / loads them at system scope while the host polls / writes
+        c->gen_cap = d.max_seq_len;
+        const size_t ring_bytes = ((size_t)c->gen_cap * 8 + 63) & ~(size_t)63;
+        HIPC(c, hipHostMalloc((void**)&c->gen_host, ring_bytes + 64, hipHostMallocMapped | hipHostMallocCoherent));
+        memset(c->gen_host, 0, ring_bytes + 64);
+        void* dp = nullptr; HIPC(c, hipHostGetDevicePointer(&dp, c->gen_host, 0));
+        c->gen_ring_dev = (unsigned long long*)dp; c->gen_cancel_dev = (const int*)((char*)dp + ring_bytes);
+        c->gen_ids.assign((size_t)d.max_seq_len, 0);
+    }
     // (tensor parallel: the full-width activations are regions of the exchange buffer, the rest is this rank's shard)
     const size_t cap = d.max_seq_len < 64 ? 64 : (size_t)d.max_seq_len, nmax = d.hidden_dim > d.dim ? d.hidden_dim : d.dim;
     if (!c->pf_in_xbuf) {
@@ -346,9 +355,13 @@ int alloc_run_bufs(flm_ctx* c) {
 
 // decode state <- {pos, tok, step}: by value through a one-thread kernel (an async copy from a host stack frame would be
 // read after the frame is gone)
-__global__ void k_set_state(DecodeState* st, int pos, int tok, int step) { if (threadIdx.x == 0 && blockIdx.x == 0) { st->pos = pos; st->tok = tok; st->step = step; st->pad = 0; } }
+// (all of it: the latch open, and the generate words -- stop token -1, tag 0 for every entry point but flm_generate, which sets c->gen_* around its enqueue: they never halt)
+__global__ void k_set_state(DecodeState* st, const DecodeState v) { if (threadIdx.x == 0 && blockIdx.x == 0) *st = v; }
 int set_state(flm_ctx* c, int pos, int tok, int step) {
-    hipLaunchKernelGGL(k_set_state, dim3(1), dim3(64), 0, c->stream, c->state, pos, tok, step);
+    DecodeState v{};
+    v.pos = pos; v.tok = tok; v.step = step; v.halt = 0; v.stop_tok = c->gen_stop; v.gen_tag = c->gen_tag; v.max_tokens = c->gen_max;
+    v.ring_cap = c->gen_cap; v.ring = c->gen_ring_dev; v.cancel = c->gen_cancel_dev;
+    hipLaunchKernelGGL(k_set_state, dim3(1), dim3(64), 0, c->stream, c->state, v);
     HIPC(c, hipGetLastError());
     return FLM_OK;
 }
@@ -626,6 +639,7 @@ void flm_ctx_destroy(flm_ctx* c) {
     for (void* p : c->owned) hipFree(p);
     for (void* p : {c->emb, (void*)c->emb_s, (void*)c->trace}) if (p) hipFree(p);          // (re-allocated during the context's life: flm_upload_tensor, option "trace")
     if (c->bounce) hipHostFree(c->bounce);
+    if (c->gen_host) hipHostFree(c->gen_host);
     if (c->comm) ncclCommDestroy(c->comm);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
@@ -878,6 +892,8 @@ int flm_query(flm_ctx* c, const char* key, int* value) {
         {"fallback", c->fell_back},
         {"fallback_active", c->fb_active ? 1 : 0},
         {"sampled_tokens", (int)c->sampled},
+        {"gen_tokens", c->gen_tokens},
+        {"gen_streamed", c->gen_streamed},
         // which hand-offs of the token's launch (short contexts) are consumed in arrival order; -1: that launch was not planned (yet)
         {"ao_active", c->la_ok[0] ? (c->la_p[0].ao_o ? 1 : 0) | (c->la_p[0].ao_2 ? 2 : 0) : -1},
         {"token_path", (c->world == 1 ? path : 0) | (c->attn_split ? 64 : 0)},
@@ -999,7 +1015,7 @@ int flm_reset_kv(flm_ctx* c) {
     return FLM_OK;
 }
 
-// debugging tap (tests): copy an internal device buffer to the host. what: 0 x1, 1 q, 2 att_out, 3 hd, 4 kcache(layer), 5 vcache(layer), 6 logits, 11 / 12 the epoch lines / tags
+// debugging tap (tests): copy an internal device buffer to the host. what: 0 x1, 1 q, 2 att_out, 3 hd, 4 kcache(layer), 5 vcache(layer), 6 logits, 11 / 12 the epoch lines / tags, 13 flm_generate's ring
 int flm_debug_read(flm_ctx* c, int what, int layer, float* out, size_t n) {
     if (!c || !out) return FLM_ERR_INVALID;
     HIPC(c, hipSetDevice(c->device));
@@ -1066,6 +1082,11 @@ int flm_debug_read(flm_ctx* c, int what, int layer, float* out, size_t n) {
         }
         HIPC(c, hipStreamSynchronize(c->stream));
         if (at < n) return fail(c, FLM_ERR_INVALID, "debug_read: size");
+        return FLM_OK; }
+    case 13: {   // flm_generate's granule ring as the last call left it: raw 32-bit words, two per entry {token | last << 31, tag}
+        if (n > 2 * (size_t)c->gen_cap) return fail(c, FLM_ERR_INVALID, "debug_read: size");
+        HIPC(c, hipStreamSynchronize(c->stream));
+        memcpy(out, c->gen_host, n * 4);
         return FLM_OK; }
     default: return fail(c, FLM_ERR_INVALID, "debug_read: unknown buffer");
     }
@@ -1156,6 +1177,99 @@ int flm_decode_sample(flm_ctx* c, int32_t first_token, int pos, int n_steps, flo
         r = d2h(c, &s, &c->sparams->rng, sizeof s); if (r) return r;
         return d2h(c, out_tokens, c->out_tokens_dev, sizeof(int) * (size_t)n_steps);
     }, [&] { *rng_state = s; c->sampled += n_steps; });
+}
+
+// ParallelTransformer::generate (transformer.cpp:76-103) as one call: the prompt and ALL of max_tokens - 1 decode tokens go onto the stream at once (the graphs flm_decode_* replay:
+// nothing new is captured), the loop's two decisions are taken on the device by every token's last act (flm_math.h gen_last_act) -- stop on `stop_token`: the latch, behind which
+// the launches still queued return at their top; per-token callback: one granule per token into the page-locked ring, which this thread polls while the graphs replay.
+// Correctness does not depend on the host SEEING a granule before the stream drains: what the poll did not deliver is delivered behind the synchronise, from out_tokens_dev.
+namespace {
+struct GenWords {     // the decode state's generate words hold for the enqueue of one attempt only: every other entry point's set_state writes -1 / 0 / 0
+    flm_ctx* c;
+    GenWords(flm_ctx* c_, int stop, unsigned tag, int max_tokens) : c(c_) { c->gen_stop = stop; c->gen_tag = tag; c->gen_max = max_tokens; }
+    ~GenWords() { c->gen_stop = -1; c->gen_tag = 0; c->gen_max = 0; }
+};
+inline void cpu_relax() {
+#if defined(__x86_64__) || defined(__i386__)
+    __builtin_ia32_pause();
+#endif
+}
+}
+int flm_generate(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, int max_tokens, float temperature, float topp, uint64_t* rng_state,
+                 int32_t stop_token, flm_token_cb cb, void* user, int32_t* out_tokens, int* n_out) {
+    if (!c || !prompt || !n_out) return FLM_ERR_INVALID;
+    // (in front of everything else: a tensor-parallel rank must not touch a peer -- halting and cancelling across ranks is not built)
+    if (c->world > 1 || (c->comm && c->force_tp)) return fail(c, FLM_ERR_UNSUPPORTED, "generate: one GPU only (tensor-parallel callers keep the flm_decode_* loop)");
+    if (max_tokens < 1 || !(temperature >= 0.0f) || stop_token >= c->d.vocab_size) return fail(c, FLM_ERR_INVALID, "generate: max_tokens >= 1, temperature >= 0, stop_token < vocab_size (or -1)");
+    int r = check_ready(c, n_prompt, pos); if (r) return r;
+    if (pos + n_prompt + max_tokens - 1 > c->d.max_seq_len || max_tokens > c->out_cap || max_tokens > c->gen_cap) return fail(c, FLM_ERR_INVALID, "generate: pos + n_prompt + max_tokens - 1 exceeds max_seq_len");
+    const bool sampled = temperature != 0.0f;
+    if (sampled) { r = sample_args_ok(c, temperature, topp, rng_state); if (r) return r; }
+    const int advance = sampled ? 3 : 1;
+    volatile unsigned long long* ring = c->gen_host;
+    int* cancel_word = (int*)((char*)c->gen_host + (((size_t)c->gen_cap * 8 + 63) & ~(size_t)63));
+    int32_t* ids = c->gen_ids.data();
+    // across the attempts of a retried call: how many tokens went to the callback (never delivered twice), whether it cancelled, how many were seen while the stream was busy
+    int delivered = 0, streamed = 0, total = 0; bool cancelled = false;
+    unsigned long long s = 0;
+    auto deliver = [&](int index, int32_t token, int last) {
+        if (index < delivered) return;
+        delivered = index + 1;
+        if (cancelled || !cb) return;
+        if (cb(user, index, token, last) != 0) { cancelled = true; __atomic_store_n(cancel_word, 1, __ATOMIC_RELEASE); }
+    };
+    r = with_retry(c, n_prompt + max_tokens - 1, [&]() -> int {
+        // a tag per ATTEMPT: the granules a failed attempt left behind never carry the tag the next one polls for
+        c->gen_seq += 1; if (c->gen_seq == 0) c->gen_seq = 1;
+        const unsigned tag = c->gen_seq;
+        // (the stream is idle: every entry point returns behind a synchronise.)  A call whose callback cancelled in an attempt that is now re-run starts with the word CLEAR:
+        // the re-run must first reproduce the tokens the callback has already received -- the poll sets the word again once it has passed them, so *n_out never falls below
+        // what was delivered
+        __atomic_store_n(cancel_word, 0, __ATOMIC_RELEASE);
+        {
+            const GenWords words(c, stop_token < 0 ? -1 : stop_token, tag, max_tokens);
+            int r = FLM_OK;
+            if (sampled) r = set_sample(c, temperature, topp, *rng_state);
+            if (!r) r = feed(c, prompt, n_prompt, pos, advance);              // token 0: drawn from the prompt's last logits
+            if (!r && max_tokens > 1) r = run_tokens(c, pos + n_prompt, max_tokens - 1, advance);
+            if (r) { (void)hipStreamSynchronize(c->stream); return r; }
+        }
+        // poll: the granules in index order as they arrive, until the one marked last -- or until the stream has drained (looked at every kPollsPerQuery empty polls: the
+        // kernels' own waits are bounded, so the stream drains whatever happens, and the poll cannot spin for ever)
+        constexpr int kPollsPerQuery = 512, kTokensPerQuery = 16;
+        int next = 0, idle = 0, unconfirmed = 0; bool seen_last = false;
+        while (!seen_last && next < max_tokens) {
+            const unsigned long long g = __atomic_load_n(ring + next, __ATOMIC_ACQUIRE);
+            if ((unsigned)(g >> 32) == tag) {
+                const unsigned v = (unsigned)g;
+                if (next >= delivered) ++unconfirmed;
+                deliver(next, (int32_t)(v & 0x7fffffffu), (int)(v >> 31));
+                seen_last = (v >> 31) != 0; ++next; idle = 0;
+                if (cancelled && next >= delivered) __atomic_store_n(cancel_word, 1, __ATOMIC_RELEASE);      // (a re-run: behind the tokens the callback already has)
+                // "gen_streamed": one look at the stream per kTokensPerQuery tokens (and behind the last one), not per token -- a stream still busy NOW was busy when the
+                // tokens since the previous look were handed out
+                if ((seen_last || next % kTokensPerQuery == 0) && unconfirmed) { if (hipStreamQuery(c->stream) == hipErrorNotReady) streamed += unconfirmed; unconfirmed = 0; }
+                continue;
+            }
+            if (++idle % kPollsPerQuery == 0 && hipStreamQuery(c->stream) != hipErrorNotReady) break;
+            cpu_relax();
+        }
+        (void)hipGetLastError();                                                    // (hipErrorNotReady is not an error of the call)
+        HIPC(c, hipStreamSynchronize(c->stream));
+        // behind the synchronise: how many tokens were drawn (the state's step counter: a halting token counts, nothing behind it ran), their ids, the sampler's state
+        DecodeState stt{};
+        int r = d2h(c, &stt, c->state, sizeof stt); if (r) return r;
+        if (sampled) { r = d2h(c, &s, &c->sparams->rng, sizeof s); if (r) return r; }
+        total = stt.step < 1 ? 1 : stt.step > max_tokens ? max_tokens : stt.step;
+        return d2h(c, ids, c->out_tokens_dev, sizeof(int) * (size_t)total);     // (the error word rides along: xwg_check looks at it next)
+    }, [&] {
+        for (int i = delivered; i < total; ++i) deliver(i, ids[i], i + 1 == total ? 1 : 0);
+        if (out_tokens) memcpy(out_tokens, ids, sizeof(int32_t) * (size_t)total);
+        *n_out = total;
+        if (sampled) { *rng_state = s; c->sampled += total; }
+        c->gen_tokens = total; c->gen_streamed = streamed;
+    });
+    return r;
 }
 
 // the ids the last flm_decode_greedy / flm_decode_sample / flm_decode_timed* call generated (still in device memory): out[n]

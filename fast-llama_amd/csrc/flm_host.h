@@ -145,6 +145,12 @@ struct flm_ctx {
     // the device sampler (flm_sample.h): per-call parameters written at the start of each flm_forward_sample / flm_decode_sample (the token graphs read them), the radix
     // sort's ping-pong buffers [2][vocab], and how many tokens this context sampled on the device ("sampled_tokens")
     flm::SampleParams* sparams = nullptr; unsigned long long* sort_buf = nullptr; long long sampled = 0;
+    // flm_generate (flm_gpu.hip): the granule ring [max_seq_len] and the cancel word -- page-locked, mapped, host-coherent memory allocated at create (gen_host; the device's view of it:
+    // gen_ring_dev / gen_cancel_dev) --, what set_state writes into the decode state's generate words (gen_stop .. gen_max: -1 / 0 / 0 outside a flm_generate call), the
+    // per-attempt sequence number the granules are tagged with, a pageable staging buffer for the ids, and the last call's figures ("gen_tokens" / "gen_streamed")
+    unsigned long long* gen_host = nullptr; unsigned long long* gen_ring_dev = nullptr; const int* gen_cancel_dev = nullptr; int gen_cap = 0;
+    int gen_stop = -1; unsigned gen_tag = 0; int gen_max = 0; unsigned gen_seq = 0;
+    std::vector<int32_t> gen_ids; int gen_tokens = 0, gen_streamed = 0;
     std::map<int, hipGraphExec_t> graphs;             // key = with_cls*4 + advance (3: sampled)
     std::vector<TimedLaunch>* timing = nullptr;
     std::vector<void*> owned;                          // every device allocation that lives as long as the context (flm_gpu.hip dev_alloc); flm_ctx_destroy frees these
@@ -248,6 +254,8 @@ int run_token(flm_ctx* c, bool with_cls, int advance, int T);
 // the device sampler's LDS fits one workgroup (vocab up to ~36 K); beyond it the sampled entry points refuse (FLM_ERR_UNSUPPORTED) and a caller samples on the host
 inline bool sample_supported(const flm_ctx* c) { return c->d.vocab_size >= 2 && sample_lds_bytes(c->d.vocab_size) <= kLdsMax; }
 int set_state(flm_ctx* c, int pos, int tok, int step);
+// the decode state's latch as the single-GPU token launches receive it (flm_math.h DecodeState::halt); the tensor-parallel launch forms get none and run unconditionally
+inline const int* halt_ptr(const flm_ctx* c) { return (c->world > 1 || (c->comm != nullptr && c->force_tp)) ? nullptr : &c->state->halt; }
 int check_ready(flm_ctx* c, int n, int pos);
 constexpr int kPrefillMin = 4;
 int prefill_batched_qt(flm_ctx* c, int B, int pos);      // (flm_prompt.hip; by the model's quant type)

@@ -35,6 +35,7 @@ struct BackArgs {
     unsigned* flag_x2;          // k_layers: FFN2 workgroups' lines (the residual stream x for the next layer's QKV)
     int nstq, preq;             // k_layers: stash slots / early waves of [Wq; Wk; Wv] requested in front of the x poll
     unsigned target; int* err;
+    const int* halt;            // the decode state's latch (flm_math.h DecodeState::halt), read once at the launch's top; null: tensor parallel
     unsigned st_base;           // LDS byte offset of the stash slots (above every phase's own layout)
     int nst13;                  // stash slots of [W1; W3] a Wo workgroup fills under the attention
     int nst13_head;             // ... a head workgroup fills when its head is done
@@ -469,6 +470,7 @@ __device__ __forceinline__ void layer_body(const GemvArgs& aq, const AttnArgs& a
 template <int QT, int XR2, bool QKV = false, bool SPLIT = false>
 __global__ void __launch_bounds__(kGemvBlock, 4) k_attn_ffn(const GemvArgs aq, const AttnArgs aa, const GemvArgs ao, const GemvArgs a13, const GemvArgs a2, const BackArgs p) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
+    if (halted(p.halt)) return;
     layer_body<QT, XR2, QKV, SPLIT, false>(aq, aa, ao, a13, a2, p, lds, p.target, false, false, true);
 }
 
@@ -543,7 +545,9 @@ __device__ __forceinline__ void tail_phase(const TailArgs& T, const BackArgs& p,
             if (idx == 0x7fffffff) idx = 0;                                     // all -inf / NaN: the reference returns index 0
             DecodeState* st = T.st;
             if (T.out_tokens && st->step >= 0 && st->step < T.out_cap) T.out_tokens[st->step] = idx;
-            st->tok = idx; st->pos += 1; st->step += 1;
+            const bool halt = gen_last_act(st, st->step, idx, p.err);         // (the token's last act: flm_math.h)
+            if (!halt) { st->tok = idx; st->pos += 1; }
+            st->step += 1;
             *T.epoch = (FLM_WAIT_FORM == 0 && next_epoch >= kEpochWrap) ? kEpochFirst : next_epoch;     // (flm_math.h flag_reached: the epochs stay inside [kEpochFirst, kEpochWrap + L + 2))
         }
     }
@@ -554,6 +558,7 @@ template <int QT, int XR2, bool SPLIT, int R5 = 0, bool TAIL = false, bool TP = 
 __global__ void __launch_bounds__(kGemvBlock, 4) k_layers(const LayerArgs* __restrict__ LA, const BackArgs p, const int l0, const int l1, const TailArgs* __restrict__ TA = nullptr) {
     static_assert(!TP || (R5 == 0 && !TAIL), "the rank-spanning launch carries the all-to-all hand-offs, the classifier is a launch of its own");
     extern __shared__ __attribute__((aligned(16))) char lds[];
+    if constexpr (!TP) { if (halted(p.halt)) return; }                             // (a scalar load and a scalar branch in front of everything else; the rank-spanning form gets nothing)
     // (the argument blocks through the CONSTANT address space: uniform scalar loads at the point of use, like kernel arguments -- through a generic pointer they would sit in vector registers)
     typedef const LayerArgs __attribute__((address_space(4))) CLayerArgs;
     CLayerArgs* LAc = (CLayerArgs*)(unsigned long long)LA;

@@ -60,7 +60,7 @@ int plan_layer(flm_ctx* c, int l, bool with_qkv, int G, LayerArgs& A, BackArgs& 
     p.n_heads = parts; p.grido = Po.grid; p.grid13 = P13.grid; p.grid2 = P2.grid;
     p.flag_h = c->flag_lines; p.flag_hd = c->flag_lines + 512 * 16; p.flag_x = c->flag_lines + 1024 * 16;
     p.gridq = with_qkv ? Pq.grid : 0; p.flag_q = c->flag_lines + 768 * 16;
-    p.target = (unsigned)(l + 1); p.err = c->xwg_err;
+    p.target = (unsigned)(l + 1); p.err = c->xwg_err; p.halt = tpl ? nullptr : halt_ptr(c);
     p.st_base = (unsigned)own; p.nst13 = slots(c->back_nst13); p.nst13_head = slots(c->back_nst13_head); p.nst2 = slots(c->back_nst2); p.pre13 = c->back_pre13 == 99 ? 16 : c->back_pre13 < 0 ? 0 : c->back_pre13 > 16 ? 16 : c->back_pre13; p.pre2 = c->back_pre2 < 0 ? 0 : c->back_pre2 > 16 ? 16 : c->back_pre2;
     {   // arrival-order hand-offs (GemvCtx::run_ao): one pass per workgroup, every step resident, a column block with <= 16 producers (PRO_QUANT: <= 256 elements)
         auto steps = [&](const GemvArgs& a, const GemvPlan& P, int rows) { const int RB = 64 >> P.cb_shift, RBP = P.Rm / RB, nbc = (a.n * esz / 16) >> P.cb_shift; return (rows + P.Rm - 1) / P.Rm <= P.grid ? ((RBP + kStepBlk - 1) / kStepBlk) * nbc : 1 << 30; };

@@ -52,7 +52,46 @@ constexpr int kWavesPerBlock = kGemvBlock / kWave;
 constexpr int kGroup = 64;            // quantization group (QUANT_GROUP_SIZE, the only value the reference uses)
 
 // the device-resident decode state: a token is replayed from a hipGraph without host round trips
-struct DecodeState { int pos; int tok; int step; int pad; };
+// (k_set_state writes every word at the start of each entry point.)  The words behind `step` belong to flm_generate, the loop that stops on the device:
+//   halt       the latch: the token just drawn was the stop token, or the host cancelled.  INVARIANT: it is WRITTEN only by a token's last act (gen_last_act below: one thread of
+//              tail_phase / k_argmax_advance / k_sample_advance) and READ only at the very top of a launch (halted()), and a kernel boundary lies between the two -- the last act
+//              closes its launch -- so every workgroup of a persistent launch takes the same branch.  A halted launch touches nothing: no flag line, no epoch, no K / V row,
+//              no logits, no sampler state, no ring entry -- the context is that of one that decoded exactly the fed tokens
+//   stop_tok   -1: none (every entry point but flm_generate: they never halt);  gen_tag: the call's sequence number, 0: not a flm_generate call (nothing is published, the
+//              cancel word is not looked at);  max_tokens: the call's token budget (the granule of its last token is marked)
+//   ring       [ring_cap] 8-byte granules {token | last << 31, gen_tag} in page-locked host-coherent memory: ONE aligned system-scope store per token, the data is its own flag
+//              (DESIGN.md sections 5c / 7e) -- a stale entry of an earlier call never carries the current tag;  cancel: one word of the same memory, written by the host.  The
+//              cancel word has exactly ONE reader per token, the last act's thread: no other workgroup may look at host memory
+struct DecodeState { int pos; int tok; int step; int halt; int stop_tok; unsigned gen_tag; int max_tokens; int ring_cap; unsigned long long* ring; const int* cancel; };
+// the latch at a launch's top: a uniform scalar load through the constant address space (as k_layers reads its argument blocks), a scalar branch.  halt == nullptr: the caller
+// passes no state (the op-level exports, the tensor-parallel launch forms) and runs unconditionally.
+// RELIES ON: the word is NOT immutable, as constant-address-space memory is otherwise taken to be -- a vector store of the previous launch's last act (or of k_set_state) wrote
+// it.  What makes the scalar load see that store is the dispatch boundary the invariant above puts between the two: the runtime's release at the end of a kernel writes the
+// store back, its acquire at the start of the next one invalidates the scalar cache (between the nodes of a replayed graph too) -- the same boundary `pos` and `tok` have
+// always crossed.  Inside ONE launch the word must never be read after it was written; nothing does (tests/test_gpu_generate.py: the cache rows behind a stop stay zero)
+__device__ __forceinline__ bool halted(const int* halt) {
+    typedef const int __attribute__((address_space(4))) CInt;
+    return halt != nullptr && *(CInt*)(unsigned long long)halt != 0;
+}
+// A token's last act, by the ONE thread that has just written out_tokens[step]: publish the token's granule (flm_generate calls only), set the latch; returns it -- a halting
+// token does not move tok / pos on: the stop token is not fed.  err: the cross-workgroup waits' error word; once a wait of the call has given up its tokens are not published
+// (the host re-runs the call and delivers them from the sound attempt).  Why a token computed on garbage cannot be published: garbage exists only behind a wait that gave up,
+// the wave that gives up stores the error word (poll_wave) BEFORE it leaves the wait and produces anything from what it failed to wait for, and whatever it produces reaches this
+// thread only through the later hand-offs of the token (flag rounds / granules / a kernel boundary), each of them an agent-scope store -> load chain behind that error store:
+// when the garbage can have influenced `tok`, the relaxed agent-scope load below already sees the word set.  A token published before any wait gave up was computed soundly
+__device__ __forceinline__ bool gen_last_act(DecodeState* st, const int step, const int tok, const int* err) {
+    bool halt = tok == st->stop_tok;
+    const unsigned tag = st->gen_tag;
+    if (tag != 0u) {
+        halt = halt || __hip_atomic_load(st->cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0;
+        const bool last = halt || step + 1 >= st->max_tokens;
+        const bool sound = err == nullptr || __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0;
+        if (sound && step >= 0 && step < st->ring_cap)
+            __hip_atomic_store(st->ring + step, ((unsigned long long)tag << 32) | (unsigned long long)((unsigned)tok | (last ? 0x80000000u : 0u)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    st->halt = halt ? 1 : 0;
+    return halt;
+}
 
 // ------------------------------------------------------------------------------------------
 // Every cross-workgroup / cross-rank wait compares a flag line's value f with a target that counts from an epoch in device memory (TailArgs::epoch, the token's epoch base

@@ -14,7 +14,8 @@ namespace flm {
 // ------------------------------------------------------------------------------------------
 // x1 = embedding[token] (copy or dequantize; transformer.cpp:115-122)
 constexpr unsigned kEpochStride = 1024;      // the token's epoch base advances by this: exchanges (4 per layer + 2) per token must stay below it
-inline __global__ void k_embed(float* x, const void* emb, const float* emb_s, int emb_qt, int dim, const int* tok_ptr, unsigned* bar, unsigned* eng_base = nullptr, unsigned long long* ffn_counter = nullptr) {
+inline __global__ void k_embed(float* x, const void* emb, const float* emb_s, int emb_qt, int dim, const int* tok_ptr, unsigned* bar, unsigned* eng_base = nullptr, unsigned long long* ffn_counter = nullptr, const int* halt = nullptr) {
+    if (halted(halt)) return;                                    // (flm_math.h DecodeState::halt: in front of the epoch base, the counter and the lines)
     const int tok = *tok_ptr;
     // a new token: the epoch base of the tensor-parallel exchanges' flag values moves on; back to 0 at kEpochWrap, so that no target comes within kEpochWindow of 2^32
     // (flm_math.h flag_reached: the local lines cleared below must stay outside every target's window; the never-cleared cross-rank lines then hold values of the previous
@@ -41,7 +42,8 @@ inline __global__ void k_embed(float* x, const void* emb, const float* emb_s, in
 
 // sample_argmax (src/transformer/sampler.cpp:36-47): first maximum wins.  One workgroup.
 // Also advances the device-resident decode state: tok <- argmax, pos <- pos+1, out[step++] <- argmax.
-inline __global__ void __launch_bounds__(1024) k_argmax_advance(const float* logits, int n, DecodeState* st, int* out_tokens, int advance, int out_cap) {
+inline __global__ void __launch_bounds__(1024) k_argmax_advance(const float* logits, int n, DecodeState* st, int* out_tokens, int advance, int out_cap, const int* err = nullptr) {
+    if (halted(&st->halt)) return;
     __shared__ float bv[16]; __shared__ int bi[16];
     float best = -INFINITY; int idx = 0x7fffffff;
     // ascending index order within a thread and strict '>' keep the FIRST maximum
@@ -71,7 +73,8 @@ inline __global__ void __launch_bounds__(1024) k_argmax_advance(const float* log
         for (int w = 1; w < (int)(blockDim.x >> 6); ++w) if (bv[w] > best || (bv[w] == best && bi[w] < idx)) { best = bv[w]; idx = bi[w]; }
         if (idx == 0x7fffffff) idx = 0;      // all -inf / NaN: reference returns index 0
         if (out_tokens && st->step >= 0 && st->step < out_cap) out_tokens[st->step] = idx;      // (out_cap: the buffer's size; a caller that forgot to reset `step` must not write past it)
-        if (advance) { st->tok = idx; st->pos += 1; }
+        const bool halt = gen_last_act(st, st->step, idx, err);                                 // (the token's last act: flm_math.h)
+        if (advance && !halt) { st->tok = idx; st->pos += 1; }
         st->step += 1;
     }
 }

@@ -32,6 +32,7 @@ struct SampleArgs {
     SampleParams* sp;                     // in: temperature, top-p, state; out: the state after the draw
     DecodeState* st; int* out_tokens; int out_cap; int advance;
     unsigned long long* sort_buf;         // [2][n]: the radix sort's ping-pong buffers
+    const int* err;                       // the cross-workgroup waits' error word (gen_last_act; may be null)
 };
 
 // xorshift* (sampler.cpp random_u32 / random_f32): the coin of one draw
@@ -105,6 +106,7 @@ __device__ __forceinline__ void wave_excl_scan256(const int* in, int* out) {
 // One workgroup of 1024 threads, sample_lds_bytes(n) of dynamic LDS, n >= 2.  Writes out_tokens[step], advances the state like k_argmax_advance, and the sampler state.
 inline __global__ void __launch_bounds__(kSampleBlock) k_sample_advance(const SampleArgs a) {
     extern __shared__ float4 sample_lds4[];
+    if (halted(&a.st->halt)) return;       // (flm_math.h DecodeState::halt: the sampler state stays at the last drawn token's)
     float* strip = reinterpret_cast<float*>(sample_lds4);
     const int n = a.n, B = sample_lane_elems(n), LS = B + 4;
     int* cnt = reinterpret_cast<int*>(strip + 64 * LS);
@@ -248,7 +250,8 @@ inline __global__ void __launch_bounds__(kSampleBlock) k_sample_advance(const Sa
     if (t == 0) {
         DecodeState* st = a.st;
         if (a.out_tokens && st->step >= 0 && st->step < a.out_cap) a.out_tokens[st->step] = tok;
-        if (a.advance) { st->tok = tok; st->pos += 1; }
+        const bool halt = gen_last_act(st, st->step, tok, a.err);                               // (the token's last act: flm_math.h)
+        if (a.advance && !halt) { st->tok = tok; st->pos += 1; }
         st->step += 1;
         a.sp->rng = rng;
     }

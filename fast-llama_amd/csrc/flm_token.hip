@@ -44,7 +44,7 @@ GemvPlan gemv_plan(int n, int esz, int rows, bool two, bool pairs, bool norm, in
 GemvArgs args_qkv(flm_ctx* c, int l) {
     const auto& d = c->d; LayerW& w = c->layers[l];
     const size_t kv_layer = (size_t)c->heads_local * c->kv_rows * c->hs;
-    GemvArgs a{}; a.ablate = c->ablate;
+    GemvArgs a{}; a.ablate = c->ablate; a.halt = halt_ptr(c);
     a.W = w.qkv.q; a.sW = w.qkv.s; a.n = d.dim; a.items = w.qkv.rows / 2;
     a.x = c->x1; a.norm_w = w.att_norm;
     a.out = c->qbuf; a.kcache = c->kcache + (size_t)l * kv_layer; a.vcache = c->vcache + (size_t)l * kv_layer;
@@ -69,7 +69,7 @@ int attn_parts(const flm_ctx* c, int T) {
 AttnArgs args_attn(flm_ctx* c, int l, int G) {
     const auto& d = c->d;
     const size_t kv_layer = (size_t)c->heads_local * c->kv_rows * c->hs;
-    AttnArgs a{};
+    AttnArgs a{}; a.halt = halt_ptr(c);
     a.q = c->qbuf; a.kcache = c->kcache + (size_t)l * kv_layer; a.vcache = c->vcache + (size_t)l * kv_layer;
     a.out = c->att_out + (size_t)c->plan.head_begin * c->hs; a.pos_ptr = &c->state->pos; a.hs = c->hs; a.max_seq = d.max_seq_len; a.kv_rows = c->kv_rows;
     a.G = G; a.sc_global = c->att_sc; a.flag_sc = c->flag_lines + 256 * 16; a.epoch = (unsigned)(l + 1); a.err = c->xwg_err;
@@ -78,7 +78,7 @@ AttnArgs args_attn(flm_ctx* c, int l, int G) {
 }
 GemvArgs args_o(flm_ctx* c, int l) {
     LayerW& w = c->layers[l];
-    GemvArgs a{}; a.ablate = c->ablate;
+    GemvArgs a{}; a.ablate = c->ablate; a.halt = halt_ptr(c);
     a.W = w.o.q; a.sW = w.o.s; a.n = c->d.dim; a.items = c->drow_count;
     a.x = c->att_out; a.out = c->x1 + c->drow_begin;
     set_peers(c, a, a.out);
@@ -86,7 +86,7 @@ GemvArgs args_o(flm_ctx* c, int l) {
 }
 GemvArgs args_ffn13(flm_ctx* c, int l) {
     LayerW& w = c->layers[l];
-    GemvArgs a{}; a.ablate = c->ablate;
+    GemvArgs a{}; a.ablate = c->ablate; a.halt = halt_ptr(c);
     a.W = w.w13.q; a.sW = w.w13.s; a.n = c->d.dim; a.items = c->hidden_local;
     a.x = c->x1; a.norm_w = w.ffn_norm; a.out = c->hd + c->plan.hidden_begin;
     set_peers(c, a, a.out);
@@ -94,14 +94,14 @@ GemvArgs args_ffn13(flm_ctx* c, int l) {
 }
 GemvArgs args_ffn2(flm_ctx* c, int l) {
     LayerW& w = c->layers[l];
-    GemvArgs a{}; a.ablate = c->ablate;
+    GemvArgs a{}; a.ablate = c->ablate; a.halt = halt_ptr(c);
     a.W = w.w2.q; a.sW = w.w2.s; a.n = c->d.hidden_dim; a.items = c->drow_count;
     a.x = c->hd; a.out = c->x1 + c->drow_begin;
     set_peers(c, a, a.out);
     return a;
 }
 GemvArgs args_cls(flm_ctx* c) {
-    GemvArgs a{}; a.ablate = c->ablate;
+    GemvArgs a{}; a.ablate = c->ablate; a.halt = halt_ptr(c);
     a.W = c->cls.q; a.sW = c->cls.s; a.n = c->d.dim; a.items = c->cls.rows;
     a.x = c->x1; a.norm_w = c->out_norm; a.out = c->logits + (c->world > 1 ? (size_t)c->rank * c->vocab_slot : 0);
     set_peers(c, a, a.out);
@@ -281,7 +281,7 @@ int enqueue_token(flm_ctx* c, hipStream_t st, bool with_cls, int advance, int G)
     }
     {
         Tick t(c, st, KC_EMBED);
-        hipLaunchKernelGGL(k_embed, dim3((d.dim + 255) / 256), dim3(256), 0, st, c->x1, (const void*)c->emb, (const float*)c->emb_s, c->emb_qt, d.dim, (const int*)&c->state->tok, c->flag_lines, c->eng_base, c->ffn_counter);
+        hipLaunchKernelGGL(k_embed, dim3((d.dim + 255) / 256), dim3(256), 0, st, c->x1, (const void*)c->emb, (const float*)c->emb_s, c->emb_qt, d.dim, (const int*)&c->state->tok, c->flag_lines, c->eng_base, c->ffn_counter, halt_ptr(c));
         HIPC(c, hipGetLastError());
     }
     const int wgs = gemv_grid(c->cu_count, c->wg_per_cu, 0, 0);
@@ -376,12 +376,12 @@ layers_done:
             if (!sample_supported(c)) return fail(c, FLM_ERR_UNSUPPORTED, "device sampler: vocabulary too large for one workgroup's LDS");
             Tick t(c, st, KC_ARGMAX);
             SampleArgs sa{};
-            sa.logits = c->logits; sa.n = d.vocab_size; sa.sp = c->sparams; sa.st = c->state; sa.out_tokens = c->out_tokens_dev; sa.out_cap = c->out_cap; sa.advance = 1; sa.sort_buf = c->sort_buf;
+            sa.logits = c->logits; sa.n = d.vocab_size; sa.sp = c->sparams; sa.st = c->state; sa.out_tokens = c->out_tokens_dev; sa.out_cap = c->out_cap; sa.advance = 1; sa.sort_buf = c->sort_buf; sa.err = c->xwg_err;
             hipLaunchKernelGGL(k_sample_advance, dim3(1), dim3(kSampleBlock), sample_lds_bytes(d.vocab_size), st, sa);
             HIPC(c, hipGetLastError());
         } else if (advance != 0) {
             Tick t(c, st, KC_ARGMAX);
-            hipLaunchKernelGGL(k_argmax_advance, dim3(1), dim3(1024), 0, st, (const float*)c->logits, d.vocab_size, c->state, c->out_tokens_dev, 1, c->out_cap);
+            hipLaunchKernelGGL(k_argmax_advance, dim3(1), dim3(1024), 0, st, (const float*)c->logits, d.vocab_size, c->state, c->out_tokens_dev, 1, c->out_cap, (const int*)c->xwg_err);
             HIPC(c, hipGetLastError());
         }
     } else if (advance == 2) {
@@ -424,7 +424,7 @@ int flm_kernel_times(flm_ctx* c, int pos, int iters, float* avg_us, int32_t* cou
     const hipEvent_t e0 = ev.e0, e1 = ev.e1;
     auto launch = [&](int kc, int l) -> int {
         switch (kc) {
-        case KC_EMBED:  hipLaunchKernelGGL(k_embed, dim3((d.dim + 255) / 256), dim3(256), 0, st, c->x1, (const void*)c->emb, (const float*)c->emb_s, c->emb_qt, d.dim, (const int*)&c->state->tok, c->flag_lines, c->eng_base, c->ffn_counter); return FLM_OK;
+        case KC_EMBED:  hipLaunchKernelGGL(k_embed, dim3((d.dim + 255) / 256), dim3(256), 0, st, c->x1, (const void*)c->emb, (const float*)c->emb_s, c->emb_qt, d.dim, (const int*)&c->state->tok, c->flag_lines, c->eng_base, c->ffn_counter, halt_ptr(c)); return FLM_OK;
         case KC_QKV:    return launch_gemv<PRO_RMSNORM_QUANT, EPI_ROPE_KV>(c, st, qt, args_qkv(c, l), wgs);
         case KC_ATTN:   { const int G = attn_parts(c, pos + 1);
                           if (G > 1) hipLaunchKernelGGL(k_attn_decode<true>, dim3(c->heads_local * G), dim3(kAttnBlock), attn_lds_bytes(d.max_seq_len, c->hs, true), st, args_attn(c, l, G));

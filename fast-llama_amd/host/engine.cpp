@@ -182,6 +182,22 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
         for (int r = 1; r < world; ++r) if (ids[r] != ids[0] || st[r] != st[0]) { _err = "tensor parallel: the ranks sampled different tokens"; fprintf(stderr, "%s\n", _err.c_str()); return false; }
         return true;
     };
+    if (world == 1) {
+        // one device: the whole loop is ONE call (flm_generate): the prompt and every decode token go onto the stream at once, the device stops on token 0 itself and hands
+        // each token over as it appears -- text streams per token as the reference's does, nothing is computed past the stop.  The loop's count: one token from the prompt,
+        // then one per position up to max_tokens (the arithmetic above).  The host-sampler loop below stays for vocabularies the device sampler refuses.
+        struct Sink { decltype(emit)* fn; int n_in; } sink{&emit, n_in};
+        const flm_token_cb on_token = [](void* user, int index, int32_t token, int /*last*/) -> int {
+            Sink* s = (Sink*)user;
+            return (*s->fn)(token, index == 0 ? 0 : s->n_in + index - 1, index == 0 ? s->n_in : 1) ? 0 : 1;      // (emit's false: cancel)
+        };
+        uint64_t st = _sampler.state();
+        int n_out = 0;
+        const int rc = flm_generate(_ctxs[0], input.data(), n_in, 0, (max_new_tokens > 0 ? max_new_tokens : 0) + 1, temperature, topp, &st, 0, on_token, &sink, nullptr, &n_out);
+        if (rc == FLM_OK) { if (!greedy) _sampler.set_state(st); return true; }
+        if (rc != FLM_ERR_UNSUPPORTED) return false;
+        dev_sample = false;
+    }
     while (next != 0 && i < max_tokens) {
         if (dev_sample && (int)cur.size() == 1) {
             // the device-resident sampled loop, in chunks like the greedy one; the host's Sampler keeps the authoritative state

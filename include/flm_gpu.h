@@ -13,7 +13,7 @@
  * Ownership: the caller owns every host pointer (copied during the call); the ctx owns all device
  * memory, ALL of it allocated at flm_ctx_create / flm_upload_tensor time (prompt, output-id and batched-prefill buffers are
  * sized by max_seq_len; the launches' argument blocks and every token graph the entry points replay are built when the model's
- * last tensor arrives, at flm_p2p_import, or by flm_prepare) -- nothing is allocated inside flm_forward* / flm_decode_* (the
+ * last tensor arrives, at flm_p2p_import, or by flm_prepare) -- nothing is allocated inside flm_forward* / flm_decode_* / flm_generate (the
  * reference's zero-allocation contract, transformer.cpp:110-130; tests/test_gpu_configs.py brackets the first calls with
  * hipMemGetInfo and a hipMalloc interposer).  Exceptions, both off the steady path: after flm_set_option the graphs are
  * re-instantiated by the next call (or by flm_prepare), and so they are when a context returns from a fallback.
@@ -116,7 +116,8 @@ int  flm_forward_argmax(flm_ctx* ctx, const int32_t* tokens, int n, int pos, int
 /* Device-resident greedy loop == the body of ParallelTransformer::generate (transformer.cpp:92-101)
  * at temperature 0: feeds `first_token` at `pos`, then n_steps-1 further argmax tokens, no host
  * round trip between tokens.  out_tokens[n_steps] receives every sampled token.  Does not stop
- * on token 0 (the caller truncates). */
+ * on token 0: all n_steps tokens are computed (a caller that wants the reference's loop -- stop on a token, per-token
+ * callback -- calls flm_generate below; truncating this call's output is the other way). */
 int  flm_decode_greedy(flm_ctx* ctx, int32_t first_token, int pos, int n_steps, int32_t* out_tokens);
 /* Same loop, nothing copied back; *ms = device time of the n_steps tokens measured with HIP events
  * on the ctx's stream (bench.py's timed region; call flm_sync afterwards is not needed). */
@@ -129,8 +130,33 @@ int  flm_decode_timed_each(flm_ctx* ctx, int32_t first_token, int pos, int n_ste
  * of each call: changing them re-captures no graph and allocates nothing.  A call that retries behind a timed-out cross-workgroup wait restarts from the
  * caller's state.  FLM_ERR_UNSUPPORTED where the vocabulary does not fit one workgroup's LDS (above ~36 K entries): sample on the host there. */
 int  flm_forward_sample(flm_ctx* ctx, const int32_t* tokens, int n, int pos, float temperature, float topp, uint64_t* rng_state, int32_t* next_token);
-/* the device-resident loop of flm_decode_greedy with the argmax replaced by the sampler: out_tokens[n_steps], one draw per token; no stop on token 0 */
+/* the device-resident loop of flm_decode_greedy with the argmax replaced by the sampler: out_tokens[n_steps], one draw per token; no stop on token 0
+ * (flm_generate stops on the device) */
 int  flm_decode_sample(flm_ctx* ctx, int32_t first_token, int pos, int n_steps, float temperature, float topp, uint64_t* rng_state, int32_t* out_tokens);
+/* ParallelTransformer::generate (transformer.cpp:76-103) as one call: forward, sample, call back per token, stop on a token -- the whole loop on the device's stream.
+ * The prompt enters at `pos` exactly as in flm_forward* (more than 5 tokens: the batched path).  Token `index` 0 is drawn from the prompt's last logits, every further one from
+ * the previous token fed at the next position: the argmax when temperature == 0 (rng_state may be NULL then), otherwise the device sampler with flm_decode_sample's state contract.
+ * The loop ends after max_tokens tokens, at the first token equal to stop_token (-1: none; the reference's loop: 0), or one or more tokens behind a callback's non-zero return
+ * (cancel: how far the device runs ahead of the callback is not bounded here).  The stop token is delivered and counted, with last = 1; it is NOT fed: it gets no K/V row and
+ * draws nothing further.  *n_out = tokens delivered, out_tokens[0 .. *n_out) = their ids, *rng_state = the state after exactly *n_out draws; afterwards the KV cache holds
+ * pos + n_prompt + *n_out - 1 rows and the caller may continue from there with any entry point.  cb (may be NULL) is called on the calling thread, in index order, as the tokens
+ * appear -- while the device is still computing the next ones --, `last` set on the final token only; after it has returned non-zero it is not called again (the tokens the device
+ * had drawn by then are still counted in *n_out and written to out_tokens).
+ * How: every token's last act on the device (the argmax / sampler thread that advances the decode state) publishes {token | last << 31, call tag} as ONE aligned 8-byte store into
+ * a ring in page-locked host-coherent memory and sets a latch when the token is the stop token or the host's cancel word is set; every launch of a token looks at the latch first
+ * and returns if it is set, so the launches still queued behind a stop touch nothing.  The prompt and all max_tokens - 1 decode tokens are enqueued at once (the token graphs of
+ * flm_decode_*: nothing new is captured) with no host synchronisation between them; the host polls the ring, then synchronises and delivers whatever it has not seen yet.
+ * Nothing is allocated in the call (the ring, max_seq_len entries, and the cancel word exist since flm_ctx_create).  A call that retries behind a timed-out cross-workgroup wait
+ * restarts from the caller's state, produces the same ids, and does not deliver again what the first attempt delivered (a cancel raised in the first attempt takes effect in the
+ * re-run only behind the tokens the callback has already received: *n_out never falls below them).
+ * FLM_ERR_INVALID if pos + n_prompt + max_tokens - 1 > max_seq_len (nothing is launched); FLM_ERR_UNSUPPORTED for temperature > 0 where flm_decode_sample refuses, and for
+ * world > 1 (before anything is launched: halting and cancelling across ranks is not built). */
+typedef int (*flm_token_cb)(void* user, int index, int32_t token, int last);   /* non-zero return: cancel */
+int  flm_generate(flm_ctx* ctx, const int32_t* prompt, int n_prompt, int pos, int max_tokens,
+                  float temperature, float topp, uint64_t* rng_state /* NULL allowed iff temperature == 0 */,
+                  int32_t stop_token /* -1: none; the reference's loop: 0 */,
+                  flm_token_cb cb /* may be NULL */, void* user,
+                  int32_t* out_tokens /* [max_tokens], may be NULL */, int* n_out);
 /* the ids generated by the last flm_decode_greedy / flm_decode_sample / flm_decode_timed* call: out[n] (n <= its n_steps) */
 int  flm_last_tokens(flm_ctx* ctx, int n, int32_t* out);
 int  flm_reset_kv(flm_ctx* ctx);
@@ -158,7 +184,8 @@ int  flm_kernel_bytes(flm_ctx* ctx, int kclass, int pos, double* bytes);
 /* debugging tap for the parity tests: copy an internal fp32 device buffer to the host.
  * what: 0 residual x1[dim], 1 q[dim], 2 attention output[dim], 3 hd[hidden], 4 K cache of `layer`
  * [heads][max_seq][hs], 5 V cache of `layer`, 6 logits; 11 / 12 the never-cleared flag lines / granule tags that
- * count from the epoch counters, as raw 32-bit words (the long-lived-context tests). */
+ * count from the epoch counters, as raw 32-bit words (the long-lived-context tests); 13 flm_generate's granule ring as the last call left it, two raw 32-bit
+ * words per entry: {token | last << 31, the call's tag}. */
 int  flm_debug_read(flm_ctx* ctx, int what, int layer, float* out, size_t n);
 
 /* Structure switches: which launches a token runs.  None of them changes a result bit; the defaults are what was measured fastest.
@@ -211,7 +238,8 @@ int  flm_set_option(flm_ctx* ctx, const char* key, int value);
  *               (the whole layer in one launch), bit 9 all layers of the token in one launch (k_layers), bit 10 a greedy decode token is ONE launch (embedding row, layers,
  *               classifier, argmax in k_layers<.., TAIL>),
  *   "ao_active" which hand-offs of that launch are consumed in arrival order: bit 0 Wo, bit 1 FFN2 (-1: the launch has not been planned yet),
- *   "sampled_tokens" how many tokens this context sampled on the device (flm_forward_sample / flm_decode_sample),
+ *   "sampled_tokens" how many tokens this context sampled on the device (flm_forward_sample / flm_decode_sample / flm_generate at temperature > 0),
+ *   "gen_tokens" / "gen_streamed" the last flm_generate call: tokens delivered / how many of them were delivered while hipStreamQuery still said the stream was busy,
  *   "epoch_tail" / "epoch_eng" / "epoch_xchg" the epoch counters the cross-workgroup waits count from (device memory; the 32-bit pattern): the one-launch token's, the
  *               tensor-parallel token's epoch base, k_xchg's logits exchanges (the long-lived-context tests).
  * Unknown key: FLM_ERR_INVALID. */
