@@ -24,8 +24,11 @@ SYMBOLS = (
     "flm_kernel_times", "flm_kernel_bytes", "flm_set_option", "flm_query", "flm_debug_read",
     "flm_op_quantize", "flm_op_matmul_q", "flm_op_rmsnorm", "flm_op_swiglu", "flm_op_rope", "flm_op_softmax",
     "flm_op_attention", "flm_op_expf", "flm_op_math", "flm_op_square_sum", "flm_op_argmax", "flm_op_handoff_litmus", "flm_plan_shards",
-    "flm_forward_sample", "flm_decode_sample", "flm_op_sample", "flm_generate",
+    "flm_forward_sample", "flm_decode_sample", "flm_op_sample", "flm_generate", "flm_score_tokens", "flm_op_score_rows",
 )
+
+# flm_score (include/flm_gpu.h): one row of flm_score_tokens / flm_op_score_rows
+SCORE_DTYPE = np.dtype([("argmax", np.int32), ("target_logit", np.float32), ("max_logit", np.float32), ("sum", np.float32), ("prob", np.float32)])
 
 # flm_token_cb: int (*)(void* user, int index, int32_t token, int last); a non-zero return cancels
 TOKEN_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int32, C.c_int)
@@ -192,6 +195,18 @@ class Ctx:
         _check(rc, self._h)
         return (out[:n_out.value].copy() if want_ids else np.empty(0, dtype=np.int32)), st.value
 
+    def score(self, tokens, pos, targets=None, want_logits=False):
+        """flm_score_tokens -> a structured array (SCORE_DTYPE) with one row per position; with want_logits also the [n][vocab] logits.  targets None: the next token of
+        the sequence, none for the last row; an entry of -1: none."""
+        t = np.ascontiguousarray(tokens, dtype=np.int32)
+        tg = None if targets is None else np.ascontiguousarray(targets, dtype=np.int32)
+        if tg is not None and tg.size != t.size:
+            raise ValueError("score: one target per token")
+        out = np.zeros(len(t), dtype=SCORE_DTYPE)
+        lg = np.empty((len(t), self.desc.vocab_size), dtype=np.float32) if want_logits else None
+        _check(lib().flm_score_tokens(self._h, _p(t), len(t), int(pos), _p(tg), _p(out), _p(lg)), self._h)
+        return (out, lg) if want_logits else out
+
     def decode_timed(self, first_token, pos, n_steps) -> float:
         ms = C.c_float(0)
         _check(lib().flm_decode_timed(self._h, int(first_token), int(pos), int(n_steps), C.byref(ms)), self._h)
@@ -299,6 +314,33 @@ def op_sample(logits, temperature, topp, rng_state):
     out = C.c_int32(-1); st = C.c_uint64(int(rng_state))
     _check(lib().flm_op_sample(_p(a), int(a.size), C.c_float(temperature), C.c_float(topp), C.byref(st), C.byref(out)))
     return out.value, st.value
+
+
+def op_score_rows(logits, targets=None):
+    """k_score_rows on logits[rows][n] -> SCORE_DTYPE[rows]; targets[rows] (-1 / None: no target)"""
+    a = np.ascontiguousarray(logits, dtype=np.float32)
+    a = a.reshape(1, -1) if a.ndim == 1 else a
+    tg = None if targets is None else np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
+    if tg is not None and tg.size != a.shape[0]:
+        raise ValueError("op_score_rows: one target per row")
+    out = np.zeros(a.shape[0], dtype=SCORE_DTYPE)
+    _check(lib().flm_op_score_rows(_p(a), int(a.shape[0]), int(a.shape[1]), _p(tg), _p(out)))
+    return out
+
+
+def nll(scores, targets=None):
+    """per-position natural-log loss in float64 from flm_score rows, -((target_logit - max_logit) - log(sum)) -- the UNCLIPPED log-probability, finite where the sampler's
+    clipped prob is 0 --, and its mean over the rows that have a target.  targets: what was passed to score (rows with -1 have none); None: every row but the last has one.
+    -> (loss[n] with NaN where a row has no target, mean)"""
+    s = np.asarray(scores)
+    valid = np.ones(s.shape[0], dtype=bool)
+    if targets is None:
+        valid[-1:] = False
+    else:
+        valid = np.asarray(targets).reshape(-1) >= 0
+    loss = np.full(s.shape[0], np.nan, dtype=np.float64)
+    loss[valid] = -((s["target_logit"][valid].astype(np.float64) - s["max_logit"][valid].astype(np.float64)) - np.log(s["sum"][valid].astype(np.float64)))
+    return loss, (float(loss[valid].mean()) if valid.any() else float("nan"))
 
 
 def op_handoff_litmus(rounds):

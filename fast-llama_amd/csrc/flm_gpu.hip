@@ -322,7 +322,9 @@ int alloc_run_bufs(flm_ctx* c) {
     c->prompt_cap = d.max_seq_len; c->out_cap = d.max_seq_len;
     HIPC(c, dev_alloc(c, &c->prompt_dev, sizeof(int) * c->prompt_cap));
     HIPC(c, dev_alloc(c, &c->out_tokens_dev, sizeof(int) * c->out_cap));
-    c->bounce_bytes = (size_t)d.vocab_size * 4; if (c->bounce_bytes < sizeof(int) * (size_t)d.max_seq_len) c->bounce_bytes = sizeof(int) * (size_t)d.max_seq_len;
+    HIPC(c, dev_alloc(c, &c->score_tgt, sizeof(int) * (size_t)d.max_seq_len));           // flm_score_tokens: a target and a flm_score per position
+    HIPC(c, dev_alloc(c, &c->score_dev, sizeof(ScoreRow) * (size_t)d.max_seq_len));
+    c->bounce_bytes = (size_t)d.vocab_size * 4; if (c->bounce_bytes < sizeof(ScoreRow) * (size_t)d.max_seq_len) c->bounce_bytes = sizeof(ScoreRow) * (size_t)d.max_seq_len;   // (a row of logits | max_seq_len ids | max_seq_len flm_score: each one trip)
     HIPC(c, hipHostMalloc((void**)&c->bounce, c->bounce_bytes + 64, hipHostMallocDefault));          // (+ a line for the error word that rides along: d2h)
     {   // flm_generate's granule ring (max_seq_len entries of 8 bytes) and, a line behind it, the cancel word: the device stores / loads them at system scope while the host polls / writes
         c->gen_cap = d.max_seq_len;
@@ -550,7 +552,7 @@ int flm_ctx_create(const flm_model_desc* desc, int device_id, int rank, int worl
             alloc_qmat(c, w.w2, c->drow_count, d.hidden_dim, qt, true)) return bail(FLM_ERR_OOM);
         HIPB(dev_alloc(c, &w.att_norm, d.dim * 4)); HIPB(dev_alloc(c, &w.ffn_norm, d.dim * 4));
     }
-    if (alloc_qmat(c, c->cls, c->plan.vocab_count > 0 ? c->plan.vocab_count : 1, d.dim, qt)) return bail(FLM_ERR_OOM);
+    if (alloc_qmat(c, c->cls, c->plan.vocab_count > 0 ? c->plan.vocab_count : 1, d.dim, qt, true)) return bail(FLM_ERR_OOM);   // (cls.st: flm_score_tokens' classifier runs on the GEMM tiles)
     c->cls.rows = c->plan.vocab_count;
     HIPB(dev_alloc(c, &c->out_norm, d.dim * 4));
 #ifndef FLM_KV_PAD
@@ -903,7 +905,7 @@ int flm_query(flm_ctx* c, const char* key, int* value) {
 }
 
 static int upload_tensor_impl(flm_ctx* c, int kind, int layer, int src_qt, const void* values, const float* scales, int rows, int cols) {
-    if (c) { c->st_ready = false; c->la_valid[0] = c->la_valid[1] = false; }       // (the device-resident argument blocks of k_layers hold pointers into the tensors -- the embedding table's is re-allocated below -- and depend on their types)
+    if (c) { c->st_ready = false; c->cls_st_ready = false; c->la_valid[0] = c->la_valid[1] = false; }       // (the device-resident argument blocks of k_layers hold pointers into the tensors -- the embedding table's is re-allocated below -- and depend on their types)
     if (!c || !values) return FLM_ERR_INVALID;
     HIPC(c, hipSetDevice(c->device));
     const auto& d = c->d;
@@ -960,6 +962,15 @@ static int upload_tensor_impl(flm_ctx* c, int kind, int layer, int src_qt, const
     default: return fail(c, FLM_ERR_INVALID, "unknown tensor kind");
     }
 }
+// flm_score_tokens: where a chunk of rows' logits is staged -- the prefill scores (free once the last layer's attention is done) or, a row at a time, the logits vector --
+// and how many rows a chunk has (option "score_rows" caps it; a negative value takes the logits vector although the scores exist: how the tests reach that staging on small shapes)
+static float* score_stage(const flm_ctx* c, int* chunk) {
+    const size_t row_bytes = (size_t)c->d.vocab_size * 4;
+    const size_t sc_rows = c->pf_scores && c->score_rows >= 0 ? ((size_t)c->heads_local * c->pf_cap * c->d.max_seq_len * 4) / row_bytes : 0;
+    *chunk = sc_rows >= 1 ? (int)(sc_rows < (size_t)c->pf_cap ? sc_rows : (size_t)c->pf_cap) : 1;
+    if (c->score_rows > 0 && c->score_rows < *chunk) *chunk = c->score_rows;
+    return sc_rows >= 1 ? c->pf_scores : c->logits;
+}
 // Once per context, when its model is complete (single GPU: a tensor-parallel rank must not wait for peers at load time): one short prompt through the batched kernels and one token
 // with logits, on dummy ids, so that whatever the HIP runtime sets up lazily at a first launch -- queue-side pools that grow with the number of launches in flight: 2 MiB of device
 // memory at the first prompt of a process (tools/alloc_diag.py) -- is set up at LOAD time and not inside the caller's first flm_forward.  The cache rows it wrote are cleared again.
@@ -970,6 +981,11 @@ static void warm_up(flm_ctx* c) {
     int32_t toks[kPrefillMin + 2] = {0};
     const int n = c->d.max_seq_len > kPrefillMin + 2 ? kPrefillMin + 2 : 1;
     bool ok = feed(c, toks, n, 0, 0) == FLM_OK && hipStreamSynchronize(c->stream) == hipSuccess;
+    // ... and flm_score_tokens' launches: the batch with its last layer completed, the classifier tiles and the statistics kernel (whatever targets the memory holds: the kernel checks them)
+    if (ok && n > 1 && sample_supported(c)) {
+        int chunk = 1; float* const stage = score_stage(c, &chunk);
+        ok = prefill_batched_qt(c, n - 1, 0, true) == FLM_OK && score_classify(c, 0, chunk < n - 1 ? chunk : n - 1, stage) == FLM_OK && hipStreamSynchronize(c->stream) == hipSuccess;
+    }
     // ... and every graph a greedy loop replays, once: chunks of 16, 8, 4, 2 tokens and the single token, for one workgroup per head and (from kSplitFrom positions on) for split
     // heads -- whatever a graph's FIRST launch costs (seen once: ~2 ms inside a timed region of 20 tokens) is paid here
     const int kEach = 2 * kChunk - 1;
@@ -1270,6 +1286,50 @@ int flm_generate(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, int m
         c->gen_tokens = total; c->gen_streamed = streamed;
     });
     return r;
+}
+
+// Score a sequence: every position's logits in one batched pass, reduced on the device to a flm_score per row (flm_score.h).  The call is flm_forward's work plus the rows
+// flm_forward drops: the batch of the first n - 1 tokens runs with its LAST layer completed (prefill_batched, all_layers), its final residual rows go through the output norm
+// and the classifier on the GEMM tiles in chunks that fit the staging (score_classify), and the last token runs through the decode kernels exactly as in flm_forward -- so the
+// cache rows, c->logits and the decode state are literally what flm_forward leaves.  Fewer than kPrefillMin + 1 tokens (the batches the layer kernels have never run at) and
+// "use_prefill" 0: token by token, every token with its classifier.
+static_assert(sizeof(flm_score) == sizeof(ScoreRow) && sizeof(flm_score) == 20, "flm_score is k_score_rows' ScoreRow");
+int flm_score_tokens(flm_ctx* c, const int32_t* tokens, int n, int pos, const int32_t* targets, flm_score* out, float* logits_all) {
+    if (!c || !tokens || !out) return fail(c, FLM_ERR_INVALID, "score: null argument");
+    if (c->world > 1 || (c->comm && c->force_tp)) return fail(c, FLM_ERR_UNSUPPORTED, "score: one GPU only (tensor-parallel scoring is not built)");
+    int r = check_ready(c, n, pos); if (r) return r;
+    const int V = c->d.vocab_size;
+    if (!sample_supported(c)) return fail(c, FLM_ERR_UNSUPPORTED, "score: the vocabulary does not fit one workgroup's LDS (the device sampler's bound)");
+    for (int i = 0; i < n; ++i) {
+        if (tokens[i] < 0 || tokens[i] >= V) return fail(c, FLM_ERR_INVALID, "token id out of range");
+        if (targets && (targets[i] < -1 || targets[i] >= V)) return fail(c, FLM_ERR_INVALID, "score: target outside [0, vocab) and not -1");
+    }
+    const size_t row_bytes = (size_t)V * 4;
+    int chunk = 1; float* const stage = score_stage(c, &chunk);
+    return with_retry(c, n, [&]() -> int {
+        int r = h2d(c, c->prompt_dev, tokens, sizeof(int) * (size_t)n); if (r) return r;
+        HIPC(c, hipStreamSynchronize(c->stream));                                    // (the ids have left the bounce buffer)
+        int32_t* tg = c->gen_ids.data();                                             // (pageable staging of max_seq_len ids, there since create)
+        for (int i = 0; i < n; ++i) tg[i] = targets ? targets[i] : (i + 1 < n ? tokens[i + 1] : -1);
+        r = h2d(c, c->score_tgt, tg, sizeof(int) * (size_t)n); if (r) return r;
+        const bool batched = c->use_prefill && n - 1 >= kPrefillMin;
+        const int nb = batched ? n - 1 : 0;                                          // rows of the batch; the rest go through the decode kernels
+        if (batched) {
+            r = prefill_batched_qt(c, nb, pos, true); if (r) return r;
+            for (int r0 = 0; r0 < nb; r0 += chunk) {
+                const int m = nb - r0 < chunk ? nb - r0 : chunk;
+                r = score_classify(c, r0, m, stage); if (r) return r;
+                if (logits_all) for (int i = 0; i < m; ++i) { r = d2h(c, logits_all + (size_t)(r0 + i) * V, stage + (size_t)i * V, row_bytes); if (r) return r; }
+            }
+        }
+        for (int i = nb; i < n; ++i) {
+            r = set_state(c, pos + i, tokens[i], 0); if (r) return r;
+            r = run_token(c, true, 0, pos + i + 1); if (r) return r;
+            r = launch_score_rows(c, c->stream, c->logits, 0, V, c->score_tgt + i, c->score_dev + i, 1); if (r) return r;
+            if (logits_all) { r = d2h(c, logits_all + (size_t)i * V, c->logits, row_bytes); if (r) return r; }
+        }
+        return d2h(c, out, c->score_dev, sizeof(flm_score) * (size_t)n);       // (the error word rides along: xwg_check looks at it next)
+    });
 }
 
 // the ids the last flm_decode_greedy / flm_decode_sample / flm_decode_timed* call generated (still in device memory): out[n]

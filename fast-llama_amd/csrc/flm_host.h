@@ -151,6 +151,10 @@ struct flm_ctx {
     unsigned long long* gen_host = nullptr; unsigned long long* gen_ring_dev = nullptr; const int* gen_cancel_dev = nullptr; int gen_cap = 0;
     int gen_stop = -1; unsigned gen_tag = 0; int gen_max = 0; unsigned gen_seq = 0;
     std::vector<int32_t> gen_ids; int gen_tokens = 0, gen_streamed = 0;
+    // flm_score_tokens (flm_gpu.hip; the classifier stage: flm_prompt.hip): the rows' targets and statistics in device memory [max_seq_len] (allocated at create), and the
+    // classifier's scales group-major (cls.st) for the GEMM tiles, transposed once per set of weights
+    int* score_tgt = nullptr; flm::ScoreRow* score_dev = nullptr; bool cls_st_ready = false;
+    int score_rows = 0;                                // option "score_rows": rows per classifier chunk of flm_score_tokens (0: as many as the staging holds; < 0: one row at a time through c->logits)
     std::map<int, hipGraphExec_t> graphs;             // key = with_cls*4 + advance (3: sampled)
     std::vector<TimedLaunch>* timing = nullptr;
     std::vector<void*> owned;                          // every device allocation that lives as long as the context (flm_gpu.hip dev_alloc); flm_ctx_destroy frees these
@@ -258,7 +262,12 @@ int set_state(flm_ctx* c, int pos, int tok, int step);
 inline const int* halt_ptr(const flm_ctx* c) { return (c->world > 1 || (c->comm != nullptr && c->force_tp)) ? nullptr : &c->state->halt; }
 int check_ready(flm_ctx* c, int n, int pos);
 constexpr int kPrefillMin = 4;
-int prefill_batched_qt(flm_ctx* c, int B, int pos);      // (flm_prompt.hip; by the model's quant type)
+int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers = false);      // (flm_prompt.hip; by the model's quant type.  all_layers: the last layer is completed too -- flm_score_tokens needs every row's final residual)
+// flm_score_tokens' classifier stage (flm_prompt.hip): rows [row0, row0 + m) of the batch's final residual (pf_x) -> output norm, quantize, the classifier GEMM tiles into
+// `stage` [m][vocab], k_score_rows into score_dev[row0 ..]
+int score_classify(flm_ctx* c, int row0, int m, float* stage);
+// k_score_rows on `rows` rows of n logits, ld floats apart (c may be null: flm_op_score_rows)
+int launch_score_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, int n, const int* targets, flm::ScoreRow* out, int rows);
 int launch_gemm_store(flm_ctx* c, hipStream_t st, int qt, const GemmArgs& g, int use_mfma);   // (flm_prompt.hip: one GEMM tile launch, plain store epilogue: flm_op_matmul_q)
 void build_rope_table(int hs, int max_seq, std::vector<float>& cs, std::vector<float>& sn);  // (flm_gpu.hip)
 

@@ -153,6 +153,22 @@ int flm_op_sample(const float* logits, int n, float temperature, float topp, uin
     return FLM_OK;
 }
 
+/* k_score_rows -- the statistics kernel of flm_score_tokens -- on caller-supplied rows of logits */
+int flm_op_score_rows(const float* logits, int rows, int n, const int32_t* targets, flm_score* out) {
+    if (!logits || !out || rows < 1 || n < 2) return FLM_ERR_INVALID;
+    if (sample_lds_bytes(n) > kLdsMax) return FLM_ERR_UNSUPPORTED;
+    if (targets) for (int i = 0; i < rows; ++i) if (targets[i] < -1 || targets[i] >= n) return FLM_ERR_INVALID;
+    static_assert(sizeof(flm_score) == sizeof(ScoreRow), "flm_score is k_score_rows' ScoreRow");
+    DevBuf dl, dt, dout;
+    if (dl.alloc((size_t)rows * n * 4) || dt.alloc((size_t)rows * 4) || dout.alloc((size_t)rows * sizeof(ScoreRow))) return FLM_ERR_OOM;
+    OPC(hipMemcpy(dl.p, logits, (size_t)rows * n * 4, hipMemcpyHostToDevice));
+    if (targets) OPC(hipMemcpy(dt.p, targets, (size_t)rows * 4, hipMemcpyHostToDevice));
+    int r = launch_score_rows(nullptr, 0, dl.as<float>(), n, n, targets ? dt.as<int>() : nullptr, dout.as<ScoreRow>(), rows); if (r) return r;
+    OPC(hipDeviceSynchronize());
+    OPC(hipMemcpy(out, dout.p, (size_t)rows * sizeof(ScoreRow), hipMemcpyDeviceToHost));
+    return FLM_OK;
+}
+
 int flm_op_swiglu(float* xo, const float* xr, size_t n) {
     if (!xo || !xr || n == 0) return FLM_ERR_INVALID;
     DevBuf a, b; if (a.alloc(n * 4) || b.alloc(n * 4)) return FLM_ERR_OOM;

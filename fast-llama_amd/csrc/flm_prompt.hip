@@ -65,8 +65,9 @@ int launch_gemm(flm_ctx* c, hipStream_t st, const GemmArgs& g, int use_mfma) {
     return FLM_OK;
 }
 
+// all_layers (flm_score_tokens): the last layer runs to its end as well -- pf_x then holds every row's final residual, the classifier's input
 template <int QT>
-int prefill_batched(flm_ctx* c, int B, int pos) {
+int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers) {
     const auto& d = c->d;
     const int L = d.n_layers, dim = d.dim, hid = d.hidden_dim, hs = c->hs;
     hipStream_t st = c->stream;
@@ -107,7 +108,7 @@ int prefill_batched(flm_ctx* c, int B, int pos) {
                                (const float*)c->rope_cos, (const float*)c->rope_sin, dimL, hs, c->kv_rows, pos);
             HIPC(c, hipGetLastError());
         }
-        if (l == L - 1) break;                            // the batch only has to fill the cache: nothing downstream of the last layer's K/V is needed
+        if (l == L - 1 && !all_layers) break;             // the batch only has to fill the cache: nothing downstream of the last layer's K/V is needed
         // attention of every query over the cache rows 0 .. its own position   (execute_attn :441-449): the local heads' columns of att
         AttnArgs aa{}; aa.q = c->pf_q; aa.kcache = c->kcache + (size_t)l * kv_layer; aa.vcache = c->vcache + (size_t)l * kv_layer;
         aa.out = c->pf_att + col_a; aa.pos_ptr = &c->state->pos; aa.hs = hs; aa.max_seq = d.max_seq_len; aa.kv_rows = c->kv_rows;
@@ -176,8 +177,49 @@ int prefill_batched(flm_ctx* c, int B, int pos) {
 int launch_gemm_store(flm_ctx* c, hipStream_t st, int qt, const GemmArgs& g, int use_mfma) {
     return qt == FLM_QT_INT8 ? launch_gemm<QT_INT8, EPI_STORE>(c, st, g, use_mfma) : launch_gemm<QT_INT16, EPI_STORE>(c, st, g, use_mfma);
 }
-int prefill_batched_qt(flm_ctx* c, int B, int pos) {
-    return c->d.quant_type == FLM_QT_INT8 ? prefill_batched<QT_INT8>(c, B, pos) : prefill_batched<QT_INT16>(c, B, pos);
+int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers) {
+    return c->d.quant_type == FLM_QT_INT8 ? prefill_batched<QT_INT8>(c, B, pos, all_layers) : prefill_batched<QT_INT16>(c, B, pos, all_layers);
+}
+
+// ---------------------------------------------------------------------------------------------
+// flm_score_tokens: the classifier for a chunk of the batch's rows.  The row prologue is the decode classifier's (rmsnorm with the output norm's weight, quantize), the tiles
+// are the prompt path's with the plain store epilogue -- every (row, vocabulary entry) is the chain the token path's classifier GEMV runs -- and k_score_rows reads the staged
+// logits.  The chunk is launched as a batch of its own (m rows): the group-major activation scales (pf_xst) are laid out by the launch's row count.
+// ---------------------------------------------------------------------------------------------
+int launch_score_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, int n, const int* targets, ScoreRow* out, int rows) {
+    {   // a vocabulary's strip can take most of the LDS: raise the kernel's dynamic-LDS limit, once per device
+        static std::mutex mu; static bool done[64] = {false};
+        int dev = 0; HIPC(c, hipGetDevice(&dev));
+        std::lock_guard<std::mutex> lk(mu);
+        if (dev >= 0 && dev < 64 && !done[dev]) {
+            HIPC(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_score_rows), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
+            done[dev] = true;
+        }
+    }
+    const ScoreArgs a{logits, ld, n, targets, out};
+    hipLaunchKernelGGL(k_score_rows, dim3(rows), dim3(kSampleBlock), score_lds_bytes(n), st, a);
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
+template <int QT>
+static int score_classify_t(flm_ctx* c, int row0, int m, float* stage) {
+    const int dim = c->d.dim, V = c->d.vocab_size;
+    hipStream_t st = c->stream;
+    if (!c->cls_st_ready) {   // once per set of weights, like the layers' copies (no allocation: cls.st came with the matrix)
+        const size_t n = (size_t)c->cls.rows * (c->cls.cols / kGroup);
+        hipLaunchKernelGGL(k_transpose_scales, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float*)c->cls.s, c->cls.st, c->cls.rows, c->cls.cols / kGroup);
+        HIPC(c, hipGetLastError());
+        c->cls_st_ready = true;
+    }
+    // logits = Wcls quantize(rmsnorm(x1))   (transformer.cpp:154-160)
+    RowsArgs ra{c->pf_x + (size_t)row0 * dim, c->out_norm, c->pf_xq, c->pf_xs, dim, c->pf_xst};
+    int r = launch_rows<QT, PRO_RMSNORM_QUANT>(c, st, ra, m); if (r) return r;
+    GemmArgs g{c->cls.q, c->cls.s, c->pf_xq, c->pf_xs, stage, V, dim, V, m, c->pf_xst, c->cls.st};
+    r = launch_gemm<QT, EPI_STORE>(c, st, g, c->use_mfma); if (r) return r;
+    return launch_score_rows(c, st, stage, V, V, c->score_tgt + row0, c->score_dev + row0, m);
+}
+int score_classify(flm_ctx* c, int row0, int m, float* stage) {
+    return c->d.quant_type == FLM_QT_INT8 ? score_classify_t<QT_INT8>(c, row0, m, stage) : score_classify_t<QT_INT16>(c, row0, m, stage);
 }
 
 } // namespace fh

@@ -1,6 +1,7 @@
 #include "engine.h"
 #include <algorithm>
 
+#include <math.h>
 #include <stdio.h>
 #include <string.h>
 
@@ -151,6 +152,29 @@ void print_vector(const char* title, const std::vector<int>& vec) {       // uti
     std::cout << title << "[";
     for (size_t i = 0; i < vec.size(); ++i) { if (i) std::cout << ", "; std::cout << std::setw(dw) << vec[i]; }
     std::cout << "]" << std::endl;
+}
+
+bool GpuTransformer::score(const char* prompt) {
+    const std::vector<int> input = encode(prompt);
+    if (input.empty()) { fprintf(stderr, "Empty input for score()\n"); return false; }
+    if (_ctxs.size() != 1) { _err = "score: one device only"; return false; }
+    printf("Input prompt:%s\n", prompt);
+    print_vector("Input tokens:", input);
+    const int n = (int)input.size();
+    std::vector<flm_score> sc(n);
+    const auto t0 = std::chrono::high_resolution_clock::now();
+    const int rc = flm_score_tokens(_ctxs[0], input.data(), n, 0, nullptr, sc.data(), nullptr);
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::high_resolution_clock::now() - t0).count();
+    if (rc != FLM_OK) { _err = std::string("score: ") + flm_last_error(_ctxs[0]); return false; }
+    // the unclipped log-probability from the row's exact ingredients, in double: (target_logit - max_logit) - log(sum); the last row has no target
+    double loss = 0.0;
+    for (int i = 0; i < n; ++i) {
+        printf("score:%4d\ttoken:%6d\targmax:%6d\tprob:%.9g\n", i, input[i], (int)sc[i].argmax, (double)sc[i].prob);
+        if (i + 1 < n) loss -= ((double)sc[i].target_logit - (double)sc[i].max_logit) - log((double)sc[i].sum);
+    }
+    const double mean = n > 1 ? loss / (n - 1) : 0.0;
+    printf("score_tokens:%3d\tmean_loss:%.6f\tperplexity:%.4f\tscore_latancy:%5.2fms\n", n, mean, exp(mean), ms);
+    return true;
 }
 
 bool GpuTransformer::generate(const char* prompt, const std::function<bool(const char*, int, int, bool)>& cb,

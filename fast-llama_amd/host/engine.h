@@ -30,6 +30,9 @@ public:
     std::string decode(const std::vector<int>& tokens) const { return _tok.decode(tokens); }
     // generate(prompt, cb(text, n_input, n_output, ended), max_new_tokens, temperature, topp): transformer.cpp:54-103
     bool generate(const char* prompt, const std::function<bool(const char*, int, int, bool)>& cb, int max_new_tokens, float temperature, float topp);
+    // --mode score (this build only): the prompt's tokens through flm_score_tokens in one call; one line per position (index, token id, argmax id, the probability of the
+    // next token), then a summary line (token count, mean natural-log loss, perplexity, ms)
+    bool score(const char* prompt);
     int get_quant_type() const { return _cfg.quant_type; }
     const std::string& error() const { return _err; }
     // more than one device: which launch structure of the sharded token load() settled on (calibrate_structure), for --detail

@@ -1,7 +1,8 @@
 // main.cpp -- drop-in for the reference CLI (src/main.cpp): the same flags, the same prompt/output/summary
 // lines, the per-token transformer running on an MI355X through include/flm_gpu.h.
 //   ./main -c model.flm -q int8 -i "prompt" [-n 512] [-t 1.0] [-p 0.9] [-j N] [--mode gen|chat|bm] [--rounds R]
-// Extra flags of this build: --device <hip ordinal>; --devices a,b,... = the reference's parallel width (-j, main.cpp:30,78) on GPUs: one
+// Extra of this build: --mode score = no generation: the prompt's tokens are scored in one batched pass (flm_score_tokens) -- per position the greedy id and the probability of
+// the next token, then token count, mean loss, perplexity and ms; --device <hip ordinal>; --devices a,b,... = the reference's parallel width (-j, main.cpp:30,78) on GPUs: one
 // sequence sharded over the named devices (split_rows, transformer.cpp:264-287), one host thread per device.
 #include <stdio.h>
 #include <stdlib.h>
@@ -20,7 +21,7 @@
 using namespace flmhost;
 
 namespace {
-enum class Mode { GEN, CHAT, TEST };
+enum class Mode { GEN, CHAT, TEST, SCORE };
 struct Args {
     std::string ckpt, tknr, encode_str, decode_str;
     FileType ft = FileType::UNKNOWN;
@@ -39,7 +40,7 @@ void usage(const char* bin) {
     fprintf(stderr, "   --checkpoint,-c   <string>    the file path of the model checkpoint\n");
     fprintf(stderr, "   --tokenizer,-z    <string>    the file path of the tokenizer\n");
     fprintf(stderr, "   --file-type,-f    <string>    flm | gguf | llama2c\n");
-    fprintf(stderr, "   --mode            <string>    gen | chat | benchmark(bm)\n");
+    fprintf(stderr, "   --mode            <string>    gen | chat | benchmark(bm) | score (this build only: per-token probabilities and the perplexity of the prompt)\n");
     fprintf(stderr, "   --prompt,-i       <string>    the input prompt text\n");
     fprintf(stderr, "   --max-tokens,-n   <integer>   the maximum number of generated tokens\n");
     fprintf(stderr, "   --temperature,-t  <float>     the value for temperature sampling, [0, 1]\n");
@@ -92,7 +93,7 @@ const Flag kFlags[] = {
     {"-t", "--temperature",    true,  [](Args& a, const char* v) { a.temp = (float)atof(v); }},
     {nullptr, "--seed",        true,  [](Args& a, const char* v) { a.seed = atoi(v); }},
     {nullptr, "--rounds",      true,  [](Args& a, const char* v) { a.rounds = atoi(v); }},
-    {"-m", "--mode",           true,  [](Args& a, const char* v) { pick<Mode>(v, {{"gen", Mode::GEN}, {"generate", Mode::GEN}, {"chat", Mode::CHAT}, {"benchmark", Mode::TEST}, {"bm", Mode::TEST}}, a.mode); }},
+    {"-m", "--mode",           true,  [](Args& a, const char* v) { pick<Mode>(v, {{"gen", Mode::GEN}, {"generate", Mode::GEN}, {"chat", Mode::CHAT}, {"benchmark", Mode::TEST}, {"bm", Mode::TEST}, {"score", Mode::SCORE}}, a.mode); }},
     {nullptr, "--device",      true,  [](Args& a, const char* v) { a.device = atoi(v); }},                                  // (this build only)
     {nullptr, "--devices",     true,  [](Args& a, const char* v) { if (!parse_devices(v, a.devices)) a.bad_devices = v; }},   // (this build only)
 };
@@ -148,6 +149,11 @@ int main(int argc, const char** argv) {
     if (!tf.load(args.ckpt, args.tknr, args.ft, args.qtype, args.devices)) { fprintf(stderr, "Failed to load model\n%s\n", tf.error().c_str()); return 1; }
     args.qtype = tf.get_quant_type();
     if (args.detail) fprintf(stderr, "Model loaded\n\n");
+
+    if (args.mode == Mode::SCORE) {      // (its own lines: the reference has no such mode, and the summary line below stays the reference's)
+        if (!tf.score(args.prompt)) { fprintf(stderr, "%s\n", tf.error().c_str()); return 1; }
+        return 0;
+    }
 
     double sum_prompt_tok = 1e-10, sum_output_tok = 1e-10, sum_prompt_ms = 1e-10, sum_output_ms = 1e-10;
     for (int r = 0; r < args.rounds; ++r) {

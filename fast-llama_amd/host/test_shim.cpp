@@ -1,5 +1,7 @@
 // test_shim.cpp -- C entry points over the host-side classes so that tests/ can drive them through ctypes
 // (no GPU needed).  Built as lib/libflm_host.so next to the CLI; the CLI itself does not use it.
+#include <math.h>
+#include <stdint.h>
 #include <string.h>
 
 #include <string>
@@ -71,6 +73,23 @@ int fh_sample_state(int vocab, unsigned long long* state, const float* logits, f
     const int tok = s.sample(l.data(), temperature, topp);
     *state = s.state();
     return tok;
+}
+// flm_score (include/flm_gpu.h) of one row of logits, in plain C++: sample_argmax (sampler.cpp:36-47) and the sampler's clipped softmax (tf_operators.cpp:188-209) at
+// temperature 1, read at `target` (-1: none) -- libm expf, a sequential fp32 sum in index order, prob = e_target * (float)(1.0 / sum).  out5: {argmax, target_logit,
+// max_logit, sum, prob} as 32-bit words (the struct's layout).  The expected value of the device's k_score_rows.
+void fh_score_row(const float* x, int n, int target, void* out5) {
+    int arg = 0; float mx = x[0];
+    for (int i = 1; i < n; ++i) if (x[i] > mx) { mx = x[i]; arg = i; }
+    float sum = 0.0f, et = 0.0f;
+    for (int i = 0; i < n; ++i) {
+        const float d = x[i] - mx;
+        const float e = d < -15 ? 0.0f : expf(d);
+        if (!(d < -15)) sum += e;
+        if (i == target) et = e;
+    }
+    struct { int32_t argmax; float target_logit, max_logit, sum, prob; } r{arg, 0.0f, mx, sum, 0.0f};
+    if (target >= 0 && target < n) { r.target_logit = x[target]; r.prob = et * (float)(1. / sum); }
+    memcpy(out5, &r, sizeof r);
 }
 void fh_quantize(const float* x, size_t n, int qtype, void* q, float* scales) { quantize_groups(x, n, qtype, q, scales); }
 

@@ -157,6 +157,29 @@ int  flm_generate(flm_ctx* ctx, const int32_t* prompt, int n_prompt, int pos, in
                   int32_t stop_token /* -1: none; the reference's loop: 0 */,
                   flm_token_cb cb /* may be NULL */, void* user,
                   int32_t* out_tokens /* [max_tokens], may be NULL */, int* n_out);
+/* Score a sequence in ONE batched pass: per position the greedy id and the probability the model gives a target token -- what perplexity and draft-and-verify schemes need,
+ * without one flm_forward call and 4 * vocab bytes of logits per token.  Row i describes the logits after feeding tokens[0..i] at positions pos .. pos + i: exactly the logits
+ * flm_forward(tokens, i + 1, pos) returns, bit for bit (logits_all[i][vocab] receives them when it is not NULL).
+ *   argmax                 sample_argmax (sampler.cpp:36-47): the first maximum wins
+ *   max_logit, sum, prob   the reference sampler's softmax (tf_operators.cpp:188-209) at temperature 1 on that row, read at the row's target: d = x - max; e = d < -15 ? 0 : expf(d);
+ *                          sum = the sequential fp32 chain of the e in index order; prob = e_target * (float)(1.0 / sum)
+ *   target_logit           the target's raw fp32 logit
+ * so that the UNCLIPPED log-probability is (target_logit - max_logit) - log(sum), evaluated by the caller in double from bit-exact ingredients (a clipped target has prob 0 and
+ * a finite loss).  targets[n]: the index read in row i, -1 = none; NULL: tokens[i + 1], none for the last row.  A row without a target has target_logit = prob = 0.
+ * Afterwards the KV cache holds rows pos .. pos + n - 1 and the decode state is what flm_forward with the same arguments leaves: the caller may continue from pos + n with any
+ * entry point, or rewind by passing a smaller pos.
+ * How: the first n - 1 tokens run through the batched prompt kernels with the last layer completed, their final rows through the output norm and the classifier on the GEMM tiles
+ * in chunks of as many rows as the staging holds (the prefill scores' memory, free by then; without it one row at a time through the logits vector; option "score_rows" caps the
+ * chunk), one 1024-thread workgroup per row reduces a chunk's logits to its flm_score; the last token runs through the decode kernels as in flm_forward.  n < 5 (and
+ * "use_prefill" 0): token by token, each with its classifier.  Nothing is allocated in the call (the classifier's group-major scales, the targets and the results' device
+ * memory exist since flm_ctx_create); the n structs come back in one trip through the bounce buffer, logits_all row by row.
+ * Errors, with nothing launched: FLM_ERR_INVALID for n < 1, pos + n > max_seq_len, a token or a target outside [0, vocab) other than a target of -1, out == NULL;
+ * FLM_ERR_UNSUPPORTED for world > 1 and where the vocabulary does not fit the statistics kernel's LDS strip (flm_forward_sample's bound, ~36 K entries); FLM_ERR_STATE before the
+ * model is complete.  Not built: tensor-parallel scoring, temperatures other than 1. */
+typedef struct flm_score { int32_t argmax; float target_logit, max_logit, sum, prob; } flm_score;
+int  flm_score_tokens(flm_ctx* ctx, const int32_t* tokens, int n, int pos,
+                      const int32_t* targets /* [n], NULL: tokens[i + 1], none for the last */,
+                      flm_score* out /* [n] */, float* logits_all /* [n][vocab], may be NULL */);
 /* the ids generated by the last flm_decode_greedy / flm_decode_sample / flm_decode_timed* call: out[n] (n <= its n_steps) */
 int  flm_last_tokens(flm_ctx* ctx, int n, int32_t* out);
 int  flm_reset_kv(flm_ctx* ctx);
@@ -202,6 +225,7 @@ int  flm_debug_read(flm_ctx* ctx, int what, int layer, float* out, size_t n);
  *                    for the producers of its own steps' column blocks only)
  *   "attn_split"     0 = one workgroup per head at every context length (default 1: hs / 32 workgroups per head from 128 positions on; n >= 2: always n)
  *   "use_prefill"    0 = prompts token by token (default 1: batched; under tensor parallelism once the peers are mapped with flm_p2p_import)
+ *   "score_rows"     n = flm_score_tokens runs its classifier on chunks of at most n rows (default 0: as many rows as the staging holds; < 0: one row at a time through the logits vector, the staging of a context without prefill scores)
  *   "use_prefill_mq" 0 = batched attention with one query per workgroup (default 1: eight)
  *   "use_qk_mfma" / "use_pv_mfma"  0 = prefill scores / softmax x V on VALU chains (default 1: v_mfma_f32_16x16x4_f32, the same bits)
  * Tensor parallel (set on every rank alike, before flm_p2p_export where noted):
@@ -263,6 +287,8 @@ int  flm_op_argmax(const float* logits, int n, int32_t* idx);
 /* Sampler::sample (sampler.cpp:113-137) through k_sample_advance, the kernel of flm_forward_sample / flm_decode_sample: logits[n] are not modified;
  * *rng_state in / out as there.  n >= 2. */
 int  flm_op_sample(const float* logits, int n, float temperature, float topp, uint64_t* rng_state, int32_t* out);
+/* flm_score_tokens' statistics kernel (k_score_rows) on caller-supplied logits[rows][n]: out[rows]; targets[rows] as there (NULL: none).  2 <= n, n within the LDS bound. */
+int  flm_op_score_rows(const float* logits, int rows, int n, const int32_t* targets, flm_score* out);
 /* simd::swiglu(xo,xr,n) (x86_simd.cpp:1766-1770) */
 int  flm_op_swiglu(float* xo, const float* xr, size_t n);
 /* rope_v2 (tf_operators.cpp:352-402): one head row of n_dims at position pos */
