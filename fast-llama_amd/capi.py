@@ -25,6 +25,7 @@ SYMBOLS = (
     "flm_op_quantize", "flm_op_matmul_q", "flm_op_rmsnorm", "flm_op_swiglu", "flm_op_rope", "flm_op_softmax",
     "flm_op_attention", "flm_op_expf", "flm_op_math", "flm_op_square_sum", "flm_op_argmax", "flm_op_handoff_litmus", "flm_plan_shards",
     "flm_forward_sample", "flm_decode_sample", "flm_op_sample", "flm_generate", "flm_score_tokens", "flm_op_score_rows",
+    "flm_verify_greedy", "flm_generate_lookup", "flm_op_matmul_skinny", "flm_op_spec_draft",
 )
 
 # flm_score (include/flm_gpu.h): one row of flm_score_tokens / flm_op_score_rows
@@ -207,6 +208,35 @@ class Ctx:
         _check(lib().flm_score_tokens(self._h, _p(t), len(t), int(pos), _p(tg), _p(out), _p(lg)), self._h)
         return (out, lg) if want_logits else out
 
+    def verify_greedy(self, first_token, drafts, pos) -> np.ndarray:
+        """flm_verify_greedy -> the m + 1 ids the decode loop started with first_token at pos produces, m = the drafts that were right (len(drafts) = k, 4..15)"""
+        d = np.ascontiguousarray(drafts, dtype=np.int32)
+        out = np.empty(len(d) + 1, dtype=np.int32); n_out = C.c_int(0)
+        _check(lib().flm_verify_greedy(self._h, int(first_token), _p(d), len(d), int(pos), _p(out), C.byref(n_out)), self._h)
+        return out[:n_out.value].copy()
+
+    def generate_lookup(self, prompt, pos, max_tokens, stop_token=-1, draft_len=7, ngram_max=3, on_token=None, want_ids=True) -> np.ndarray:
+        """flm_generate_lookup -> ids[n_out]: flm_generate at temperature 0 through draft-and-verify steps.  on_token(index, token, last) as in generate."""
+        t = np.ascontiguousarray(prompt, dtype=np.int32)
+        out = np.empty(max(int(max_tokens), 1), dtype=np.int32) if want_ids else None
+        n_out = C.c_int(0)
+        raised = []
+
+        def tramp(_user, index, token, last):
+            try:
+                return 1 if on_token(int(index), int(token), bool(last)) else 0
+            except BaseException as e:      # (an exception must not unwind through the C frames: cancel, re-raise behind the call)
+                raised.append(e)
+                return 1
+        cb = TOKEN_CB(tramp) if on_token is not None else C.cast(None, TOKEN_CB)
+        rc = lib().flm_generate_lookup(self._h, _p(t), len(t), int(pos), int(max_tokens), C.c_int32(int(stop_token)), int(draft_len), int(ngram_max),
+                                       cb, None, _p(out), C.byref(n_out))
+        del cb
+        if raised:
+            raise raised[0]
+        _check(rc, self._h)
+        return out[:n_out.value].copy() if want_ids else np.empty(0, dtype=np.int32)
+
     def decode_timed(self, first_token, pos, n_steps) -> float:
         ms = C.c_float(0)
         _check(lib().flm_decode_timed(self._h, int(first_token), int(pos), int(n_steps), C.byref(ms)), self._h)
@@ -299,6 +329,38 @@ def op_matmul_q(qt, W, sW, X, sX, gs=64):
     out = np.empty((w, m), dtype=np.float32)
     _check(lib().flm_op_matmul_q(qt, _p(out), _p(W), _p(sW), _p(X), _p(sX), m, n, w, gs))
     return out
+
+
+def op_matmul_skinny(W, sW, X, sX, gs=64):
+    """flm_op_matmul_skinny: the verify pass's int8 GEMM (k_gemm_q8_skinny), 1 <= X.shape[0] <= 16 -> out[w][m]"""
+    W = np.ascontiguousarray(W, dtype=np.int8); X = np.ascontiguousarray(X, dtype=np.int8)
+    sW = np.ascontiguousarray(sW, dtype=np.float32); sX = np.ascontiguousarray(sX, dtype=np.float32)
+    m, n = W.shape; w = X.shape[0]
+    out = np.empty((w, m), dtype=np.float32)
+    _check(lib().flm_op_matmul_skinny(QT_INT8, _p(out), _p(W), _p(sW), _p(X), _p(sX), m, n, w, gs))
+    return out
+
+
+def op_spec_draft(history, k, ngram_max) -> np.ndarray:
+    """k_spec_draft, the device's prompt-lookup drafter, on a history -> d[k]"""
+    h = np.ascontiguousarray(history, dtype=np.int32)
+    d = np.empty(int(k), dtype=np.int32)
+    _check(lib().flm_op_spec_draft(_p(h), len(h), int(k), int(ngram_max), _p(d)))
+    return d
+
+
+_host = None
+
+
+def spec_draft_host(history, k, ngram_max) -> np.ndarray:
+    """the drafter's host restatement (host/spec_draft.h through lib/libflm_host.so: fh_spec_draft); needs no GPU"""
+    global _host
+    if _host is None:
+        _host = C.CDLL(os.path.join(_HERE, "lib", "libflm_host.so"))
+    h = np.ascontiguousarray(history, dtype=np.int32)
+    d = np.empty(int(k), dtype=np.int32)
+    _host.fh_spec_draft(_p(h), len(h), int(k), int(ngram_max), _p(d))
+    return d
 
 
 def op_argmax(logits) -> int:

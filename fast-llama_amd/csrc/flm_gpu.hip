@@ -324,6 +324,9 @@ int alloc_run_bufs(flm_ctx* c) {
     HIPC(c, dev_alloc(c, &c->out_tokens_dev, sizeof(int) * c->out_cap));
     HIPC(c, dev_alloc(c, &c->score_tgt, sizeof(int) * (size_t)d.max_seq_len));           // flm_score_tokens: a target and a flm_score per position
     HIPC(c, dev_alloc(c, &c->score_dev, sizeof(ScoreRow) * (size_t)d.max_seq_len));
+    HIPC(c, dev_alloc(c, &c->spec_hist, sizeof(int) * ((size_t)d.max_seq_len + 32), true));   // flm_generate_lookup: the call's token history; a verify batch's row maxima and result block
+    HIPC(c, dev_alloc(c, &c->spec_arg, sizeof(int) * 16, true));
+    HIPC(c, dev_alloc(c, &c->spec_out, sizeof(SpecOut), true));
     c->bounce_bytes = (size_t)d.vocab_size * 4; if (c->bounce_bytes < sizeof(ScoreRow) * (size_t)d.max_seq_len) c->bounce_bytes = sizeof(ScoreRow) * (size_t)d.max_seq_len;   // (a row of logits | max_seq_len ids | max_seq_len flm_score: each one trip)
     HIPC(c, hipHostMalloc((void**)&c->bounce, c->bounce_bytes + 64, hipHostMallocDefault));          // (+ a line for the error word that rides along: d2h)
     {   // flm_generate's granule ring (max_seq_len entries of 8 bytes) and, a line behind it, the cancel word: the device stores / loads them at system scope while the host polls / writes
@@ -839,6 +842,7 @@ int flm_set_option(flm_ctx* c, const char* key, int value) {
         else if (c->world > 1 && !c->comm) return fail(c, FLM_ERR_STATE, "use_p2p 0: no RCCL communicator (comm_id was NULL at create)");
         c->p2p = value ? 1 : 0;
     }
+    else if (k == "spec_gemm") { c->spec_gemm = value ? 1 : 0; return FLM_OK; }      // (read per call by the new entry points only: no captured graph depends on it)
     else if (kAblate && k == "ablate") c->ablate = value;              // FLM_ABLATE builds only: a product library cannot skip work
     else if (kAblate && k == "trace") {   // value = kernel class to trace (KC_*), -1 off
         c->trace_class = value;
@@ -896,6 +900,8 @@ int flm_query(flm_ctx* c, const char* key, int* value) {
         {"sampled_tokens", (int)c->sampled},
         {"gen_tokens", c->gen_tokens},
         {"gen_streamed", c->gen_streamed},
+        {"spec_steps", c->spec_steps},
+        {"spec_accepted", c->spec_accepted},
         // which hand-offs of the token's launch (short contexts) are consumed in arrival order; -1: that launch was not planned (yet)
         {"ao_active", c->la_ok[0] ? (c->la_p[0].ao_o ? 1 : 0) | (c->la_p[0].ao_2 ? 2 : 0) : -1},
         {"token_path", (c->world == 1 ? path : 0) | (c->attn_split ? 64 : 0)},
@@ -970,6 +976,25 @@ static float* score_stage(const flm_ctx* c, int* chunk) {
     *chunk = sc_rows >= 1 ? (int)(sc_rows < (size_t)c->pf_cap ? sc_rows : (size_t)c->pf_cap) : 1;
     if (c->score_rows > 0 && c->score_rows < *chunk) *chunk = c->score_rows;
     return sc_rows >= 1 ? c->pf_scores : c->logits;
+}
+// One verify pass at `pos` over the batch prompt_dev[0 .. k] (draft: written by the drafter from the history spec_hist[0 .. n_hist) first): all layers, the classifier in
+// chunks, the rows' first maxima, the accept step.  Enqueues only; the result block spec_out is read by the caller.
+static int spec_step(flm_ctx* c, int pos, int k, int ngram_max, int n_hist, int stop, int room, bool draft) {
+    const int B = k + 1;
+    if (draft) {
+        hipLaunchKernelGGL(k_spec_draft, dim3(1), dim3(kSampleBlock), 0, c->stream, (const int*)c->spec_hist, n_hist, k, ngram_max, c->prompt_dev);
+        HIPC(c, hipGetLastError());
+    }
+    const bool skinny = c->spec_gemm != 0;
+    int r = prefill_batched_qt(c, B, pos, true, skinny); if (r) return r;
+    int chunk = 1; float* const stage = score_stage(c, &chunk);
+    for (int r0 = 0; r0 < B; r0 += chunk) {
+        const int m = B - r0 < chunk ? B - r0 : chunk;
+        r = spec_classify(c, r0, m, stage, skinny, c->spec_arg); if (r) return r;
+    }
+    hipLaunchKernelGGL(k_spec_accept, dim3(1), dim3(64), 0, c->stream, c->spec_out, (const int*)c->spec_arg, (const int*)c->prompt_dev, k, draft ? c->spec_hist : (int*)nullptr, n_hist, stop, room);
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
 }
 // Once per context, when its model is complete (single GPU: a tensor-parallel rank must not wait for peers at load time): one short prompt through the batched kernels and one token
 // with logits, on dummy ids, so that whatever the HIP runtime sets up lazily at a first launch -- queue-side pools that grow with the number of launches in flight: 2 MiB of device
@@ -1330,6 +1355,88 @@ int flm_score_tokens(flm_ctx* c, const int32_t* tokens, int n, int pos, const in
         }
         return d2h(c, out, c->score_dev, sizeof(flm_score) * (size_t)n);       // (the error word rides along: xwg_check looks at it next)
     });
+}
+
+// Greedy draft-and-verify (include/flm_gpu.h).  flm_verify_greedy: first_token and the k drafts as ONE batch of k + 1 rows through the batched kernels with the last layer
+// completed; row i's first maximum a[i] is the id the token path draws behind first_token, a[0 .. i) -- as long as the drafts were those ids, so the accept step keeps
+// a[0 .. m], m = the first i with a[i] != drafts[i].  Everything up to the m + 1 ids' trip back is on the stream; nothing is allocated.
+int flm_verify_greedy(flm_ctx* c, int32_t first_token, const int32_t* drafts, int k, int pos, int32_t* out_tokens, int* n_out) {
+    if (!c || !drafts || !out_tokens || !n_out) return fail(c, FLM_ERR_INVALID, "verify: null argument");
+    if (c->world > 1 || (c->comm && c->force_tp)) return fail(c, FLM_ERR_UNSUPPORTED, "verify: one GPU only");
+    if (k < 4 || k > 15) return fail(c, FLM_ERR_INVALID, "verify: 4 <= k <= 15 drafts");
+    int r = check_ready(c, k + 1, pos); if (r) return r;
+    const int V = c->d.vocab_size;
+    if (first_token < 0 || first_token >= V) return fail(c, FLM_ERR_INVALID, "token id out of range");
+    for (int i = 0; i < k; ++i) if (drafts[i] < 0 || drafts[i] >= V) return fail(c, FLM_ERR_INVALID, "verify: draft outside [0, vocab)");
+    SpecOut so{};
+    return with_retry(c, k + 1, [&]() -> int {
+        int32_t* b = c->gen_ids.data();                                               // (pageable staging of max_seq_len ids, there since create)
+        b[0] = first_token; for (int i = 0; i < k; ++i) b[1 + i] = drafts[i];
+        int r = h2d(c, c->prompt_dev, b, sizeof(int) * (size_t)(k + 1)); if (r) return r;
+        r = spec_step(c, pos, k, 0, 0, -1, k + 1, false); if (r) return r;
+        return d2h(c, &so, c->spec_out, sizeof so);                                   // (the error word rides along: xwg_check looks at it next)
+    }, [&] {
+        memcpy(out_tokens, so.ids, sizeof(int32_t) * (size_t)so.n_emit);
+        *n_out = so.n_emit;
+    });
+}
+
+// flm_generate at temperature 0 with several ids per pass over the weights: the prompt enters as in flm_forward_argmax; then every step drafts draft_len tokens ON THE DEVICE from
+// the call's history (k_spec_draft), verifies them in one batch of draft_len + 1 rows and accepts the longest prefix the model would have produced itself (k_spec_accept: cut at the
+// stop token and at max_tokens, appended to the history).  The batched kernels take the position as a launch argument, so the host reads the step's result block -- m and the ids,
+// one trip -- before it enqueues the next step: ONE synchronisation per step.  Where a batch would run past max_seq_len, or fewer than 2 ids are still wanted, the step is an
+// ordinary one-launch greedy token.  Every step is re-runnable (its inputs are the history below n_hist and launch arguments), which is what the retry wrapper needs.
+int flm_generate_lookup(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, int max_tokens, int32_t stop_token, int draft_len, int ngram_max,
+                        flm_token_cb cb, void* user, int32_t* out_tokens, int* n_out) {
+    if (!c || !prompt || !n_out) return FLM_ERR_INVALID;
+    if (c->world > 1 || (c->comm && c->force_tp)) return fail(c, FLM_ERR_UNSUPPORTED, "generate_lookup: one GPU only");
+    if (max_tokens < 1 || stop_token >= c->d.vocab_size || draft_len < 4 || draft_len > 15 || ngram_max < 1 || ngram_max > 8)
+        return fail(c, FLM_ERR_INVALID, "generate_lookup: max_tokens >= 1, stop_token < vocab_size (or -1), 4 <= draft_len <= 15, 1 <= ngram_max <= 8");
+    int r = check_ready(c, n_prompt, pos); if (r) return r;
+    if (pos + n_prompt + max_tokens - 1 > c->d.max_seq_len || max_tokens > c->out_cap) return fail(c, FLM_ERR_INVALID, "generate_lookup: pos + n_prompt + max_tokens - 1 exceeds max_seq_len");
+    for (int i = 0; i < n_prompt; ++i) if (prompt[i] < 0 || prompt[i] >= c->d.vocab_size) return fail(c, FLM_ERR_INVALID, "token id out of range");
+    const int stop = stop_token < 0 ? -1 : stop_token;
+    int total = 0, steps = 0, accepted = 0; bool done = false, cancelled = false;
+    int32_t last_tok = 0;
+    SpecOut so{};
+    auto deliver = [&]() {                       // the step's ids, in index order, on this thread
+        for (int i = 0; i < so.n_emit; ++i) {
+            const int index = total + i;
+            const bool last = i + 1 == so.n_emit && (so.stopped || index + 1 == max_tokens);
+            if (out_tokens) out_tokens[index] = so.ids[i];
+            if (cb && !cancelled && cb(user, index, so.ids[i], last ? 1 : 0) != 0) cancelled = true;
+        }
+        total += so.n_emit; last_tok = so.ids[so.n_emit - 1];
+        done = so.stopped || total >= max_tokens || cancelled;
+    };
+    // token 0: the prompt, exactly as flm_forward_argmax feeds it; the history starts as the prompt and that id
+    r = with_retry(c, n_prompt, [&]() -> int {
+        int r = feed(c, prompt, n_prompt, pos, 1); if (r) return r;
+        hipLaunchKernelGGL(k_spec_begin, dim3(1), dim3(256), 0, c->stream, c->spec_hist, (const int*)c->prompt_dev, n_prompt, (const int*)c->out_tokens_dev, c->spec_out, stop);
+        HIPC(c, hipGetLastError());
+        return d2h(c, &so, c->spec_out, sizeof so);
+    }, deliver);
+    if (r) return r;
+    while (!done) {
+        const int at = pos + n_prompt + total - 1, room = max_tokens - total, n_hist = n_prompt + total;       // the last id is fed at `at`
+        const bool batch = room >= 2 && at + draft_len + 1 <= c->d.max_seq_len;
+        r = with_retry(c, batch ? draft_len + 1 : 1, [&]() -> int {
+            int r;
+            if (batch) r = spec_step(c, at, draft_len, ngram_max, n_hist, stop, room, true);
+            else {
+                r = set_state(c, at, last_tok, 0); if (r) return r;
+                r = run_token(c, true, 1, at + 1); if (r) return r;
+                hipLaunchKernelGGL(k_spec_accept, dim3(1), dim3(64), 0, c->stream, c->spec_out, (const int*)c->out_tokens_dev, (const int*)c->prompt_dev, 0, c->spec_hist, n_hist, stop, room);
+                r = hipGetLastError() == hipSuccess ? FLM_OK : fail(c, FLM_ERR_HIP, "generate_lookup: launch failed");
+            }
+            if (r) return r;
+            return d2h(c, &so, c->spec_out, sizeof so);
+        }, [&] { if (batch) { steps += 1; accepted += so.n_emit - 1; } deliver(); });
+        if (r) return r;
+    }
+    *n_out = total;
+    c->spec_steps = steps; c->spec_accepted = accepted;
+    return FLM_OK;
 }
 
 // the ids the last flm_decode_greedy / flm_decode_sample / flm_decode_timed* call generated (still in device memory): out[n]

@@ -154,6 +154,11 @@ struct flm_ctx {
     // flm_score_tokens (flm_gpu.hip; the classifier stage: flm_prompt.hip): the rows' targets and statistics in device memory [max_seq_len] (allocated at create), and the
     // classifier's scales group-major (cls.st) for the GEMM tiles, transposed once per set of weights
     int* score_tgt = nullptr; flm::ScoreRow* score_dev = nullptr; bool cls_st_ready = false;
+    // flm_verify_greedy / flm_generate_lookup (flm_gpu.hip; kernels: flm_spec.h): the call's token history [max_seq_len + 32], the batch rows' first maxima [16] and the step's
+    // result block, device memory since create; which GEMM the verify pass runs; the last call's figures ("spec_steps" / "spec_accepted")
+    int* spec_hist = nullptr; int* spec_arg = nullptr; flm::SpecOut* spec_out = nullptr;
+    int spec_gemm = 0;                                 // option "spec_gemm": 1 = the verify pass's int8 GEMMs through k_gemm_q8_skinny (B <= 16), 0 (default until both forms have been timed: DESIGN.md section 5e) = the 64 x 64 tiles; the new entry points only
+    int spec_steps = 0, spec_accepted = 0;
     int score_rows = 0;                                // option "score_rows": rows per classifier chunk of flm_score_tokens (0: as many as the staging holds; < 0: one row at a time through c->logits)
     std::map<int, hipGraphExec_t> graphs;             // key = with_cls*4 + advance (3: sampled)
     std::vector<TimedLaunch>* timing = nullptr;
@@ -262,10 +267,13 @@ int set_state(flm_ctx* c, int pos, int tok, int step);
 inline const int* halt_ptr(const flm_ctx* c) { return (c->world > 1 || (c->comm != nullptr && c->force_tp)) ? nullptr : &c->state->halt; }
 int check_ready(flm_ctx* c, int n, int pos);
 constexpr int kPrefillMin = 4;
-int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers = false);      // (flm_prompt.hip; by the model's quant type.  all_layers: the last layer is completed too -- flm_score_tokens needs every row's final residual)
+int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers = false, bool skinny = false);      // (flm_prompt.hip; by the model's quant type.  all_layers: the last layer is completed too -- flm_score_tokens needs every row's final residual; skinny: int8 and B <= 16: every GEMM through k_gemm_q8_skinny -- the verify pass under "spec_gemm" 1)
 // flm_score_tokens' classifier stage (flm_prompt.hip): rows [row0, row0 + m) of the batch's final residual (pf_x) -> output norm, quantize, the classifier GEMM tiles into
 // `stage` [m][vocab], k_score_rows into score_dev[row0 ..]
 int score_classify(flm_ctx* c, int row0, int m, float* stage);
+// the verify pass's classifier stage (flm_prompt.hip): score_classify's prologue and GEMM (skinny: k_gemm_q8_skinny), then k_argmax_rows into argmax_out[row0 ..]
+int spec_classify(flm_ctx* c, int row0, int m, float* stage, bool skinny, int* argmax_out);
+int launch_gemm_skinny_store(flm_ctx* c, hipStream_t st, const GemmArgs& g, int force_nb = 0);   // (flm_prompt.hip: k_gemm_q8_skinny, plain store epilogue: flm_op_matmul_skinny; c may be null; force_nb 1 / 2: that many 16-row fragments per wave, 0: by size)
 // k_score_rows on `rows` rows of n logits, ld floats apart (c may be null: flm_op_score_rows)
 int launch_score_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, int n, const int* targets, flm::ScoreRow* out, int rows);
 int launch_gemm_store(flm_ctx* c, hipStream_t st, int qt, const GemmArgs& g, int use_mfma);   // (flm_prompt.hip: one GEMM tile launch, plain store epilogue: flm_op_matmul_q)

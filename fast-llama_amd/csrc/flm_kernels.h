@@ -42,13 +42,15 @@
 //   k_embed, k_argmax_advance, k_xchg (tensor-parallel exchange)
 //   k_sample_advance      (flm_sample.h) Sampler::sample on the device -- temperature, clipped softmax, xorshift coin, multinomial / top-p -- bit for bit: the sampled token's
 //                         last launch in place of k_argmax_advance (flm_forward_sample / flm_decode_sample, the per-phase tail: k_embed + k_layers + k_gemv(cls) + k_sample_advance)
+//   k_gemm_q8_skinny      (flm_prefill.h) the int8 GEMM for <= 16 tokens on v_mfma_i32_16x16x64_i8, weights straight from global memory: the verify pass of draft-and-verify
+//   k_spec_draft, k_argmax_rows, k_spec_accept  (flm_spec.h) the prompt-lookup drafter, the per-row first-maximum argmax and the accept step of flm_verify_greedy / flm_generate_lookup
 //   k_score_rows          (flm_score.h) per row of a block of logits: first-maximum argmax, the clipped softmax's max / exact sequential sum, the target's logit and probability
 //                         (flm_score_tokens behind the batched prompt path's classifier GEMM; flm_op_score_rows)
 // plus small op-level kernels that expose the same __device__ functions to the parity tests.
 // (Round 3's weight-streaming engine -- loader / consumer waves around an LDS ring -- was measured slower than these launches and left the library in round 4:
 //  tools/experiments/engine/, numbers in profiles/r03_engine_timelines.txt.)
 //
-// The code lives in: flm_math.h (exact scalar / wave building blocks), flm_gemv.h, flm_attn.h, flm_layer.h, flm_prefill.h, flm_misc.h, flm_sample.h, flm_score.h.
+// The code lives in: flm_math.h (exact scalar / wave building blocks), flm_gemv.h, flm_attn.h, flm_layer.h, flm_prefill.h, flm_misc.h, flm_sample.h, flm_score.h, flm_spec.h.
 #pragma once
 #include "flm_math.h"
 #include "flm_gemv.h"
@@ -58,3 +60,4 @@
 #include "flm_misc.h"
 #include "flm_sample.h"
 #include "flm_score.h"
+#include "flm_spec.h"

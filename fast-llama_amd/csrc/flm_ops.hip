@@ -118,6 +118,44 @@ int flm_op_matmul_q(int qt, float* out, const void* W, const float* sW, const vo
     return FLM_OK;
 }
 
+/* quant::matmul for 1 <= w <= 16 batch rows through k_gemm_q8_skinny, the verify pass's int8 GEMM (plain store epilogue): out[w][m] */
+int flm_op_matmul_skinny(int qt, float* out, const void* W, const float* sW, const void* X, const float* sX, int m, int n, int w, int gs) {
+    if (!out || !W || !sW || !X || !sX || m < 1 || n < 1 || w < 1 || w > kSkinnyTokens || gs != kGroup || n % kGroup) return FLM_ERR_INVALID;
+    if (qt != FLM_QT_INT8) return FLM_ERR_UNSUPPORTED;
+    const size_t sn = n / kGroup;
+    DevBuf dW, dsW, dX, dsX, dsWT, dO;
+    if (dW.alloc((size_t)m * n) || dsW.alloc((size_t)m * sn * 4) || dX.alloc((size_t)w * n) || dsX.alloc((size_t)w * sn * 4) || dsWT.alloc((size_t)m * sn * 4) || dO.alloc((size_t)w * m * 4)) return FLM_ERR_OOM;
+    {   // the weight scales once more, group-major (k_transpose_scales on the model path)
+        std::vector<float> tw((size_t)m * sn);
+        for (int r = 0; r < m; ++r) for (size_t g = 0; g < sn; ++g) tw[g * m + r] = sW[(size_t)r * sn + g];
+        OPC(hipMemcpy(dsWT.p, tw.data(), tw.size() * 4, hipMemcpyHostToDevice));
+    }
+    OPC(hipMemcpy(dW.p, W, (size_t)m * n, hipMemcpyHostToDevice)); OPC(hipMemcpy(dsW.p, sW, (size_t)m * sn * 4, hipMemcpyHostToDevice));
+    OPC(hipMemcpy(dX.p, X, (size_t)w * n, hipMemcpyHostToDevice)); OPC(hipMemcpy(dsX.p, sX, (size_t)w * sn * 4, hipMemcpyHostToDevice));
+    OPC(hipMemset(dO.p, 0xff, (size_t)w * m * 4));                                      // (an output nobody stored reads as NaN)
+    GemmArgs g{dW.p, dsW.as<float>(), dX.p, dsX.as<float>(), dO.as<float>(), m, n, m, w, nullptr, dsWT.as<float>()};
+    const char* nb = getenv("FLM_OP_SKINNY_NB");                  // tests: 1 / 2 = fragments per wave (by size otherwise: two only from 8192 rows on)
+    int r = launch_gemm_skinny_store(nullptr, 0, g, nb ? atoi(nb) : 0); if (r) return r;
+    OPC(hipDeviceSynchronize());
+    OPC(hipMemcpy(out, dO.p, (size_t)w * m * 4, hipMemcpyDeviceToHost));
+    return FLM_OK;
+}
+
+/* k_spec_draft -- the prompt-lookup drafter of flm_generate_lookup -- on a caller-supplied history h[n]: d[k] */
+int flm_op_spec_draft(const int32_t* h, int n, int k, int ngram_max, int32_t* d) {
+    if (!h || !d || n < 1 || n >= (1 << 24) || k < 1 || k > 15 || ngram_max < 1 || ngram_max > 8) return FLM_ERR_INVALID;
+    DevBuf dh, db;
+    if (dh.alloc((size_t)n * 4) || db.alloc(16 * 4)) return FLM_ERR_OOM;
+    OPC(hipMemcpy(dh.p, h, (size_t)n * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_spec_draft, dim3(1), dim3(kSampleBlock), 0, 0, (const int*)dh.as<int>(), n, k, ngram_max, db.as<int>());
+    OPC(hipGetLastError()); OPC(hipDeviceSynchronize());
+    int32_t b[16];
+    OPC(hipMemcpy(b, db.p, 16 * 4, hipMemcpyDeviceToHost));
+    if (b[0] != h[n - 1]) return FLM_ERR_HIP;                                           // (row 0 of the batch is the history's last token)
+    memcpy(d, b + 1, (size_t)k * 4);
+    return FLM_OK;
+}
+
 /* sample_argmax (sampler.cpp:36-47) as k_argmax_advance evaluates it: first maximum wins */
 int flm_op_argmax(const float* logits, int n, int32_t* idx) {
     if (!logits || !idx || n < 1) return FLM_ERR_INVALID;

@@ -447,6 +447,141 @@ __global__ void __launch_bounds__(256, 3) k_gemm_q16_mfma(const GemmArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// The skinny int8 GEMM: B <= 16 tokens (the verify pass of flm_verify_greedy / flm_generate_lookup, flm_op_matmul_skinny).  At 5 .. 16 rows three quarters or more of
+// every 64-token tile above is padding, the LDS staging that bounds the tiles buys nothing (a weight byte is used once) and Wo has 64 tiles for 256 CUs.  Here:
+//   * v_mfma_i32_16x16x64_i8: ONE instruction = 16 tokens x 16 weight rows x one quant group of 64 -- the group's 256 int32 dots, exact.  Tokens are the A operand, weight
+//     rows the B operand (as in the tiles): C/D col = lane & 15 = the weight row, row = 4 (lane >> 4) + reg = the token, so a lane owns ONE weight row and four tokens.
+//     A and B use the same byte -> k assignment (lane quarter q takes bytes 16 q .. 16 q + 15 of the group), and integer sums are order-free.
+//   * weights go from global memory straight into the operand registers: a lane's 16 bytes are contiguous in its row, the four lanes of a row cover the group's 64
+//     bytes.  Nothing is staged in LDS; D groups (8, or 6 with two fragments) are in flight per wave in a register ring, every weight byte is read once per pass.
+//   * per output the SAME fp32 chain step as k_gemm_q8_mfma: v_cvt, sw * sx, fma, groups ascending -- the bits are the tiles' (and the token path's).
+//   * a workgroup is ONE wave and owns 16 rows (NB = 1: Wo and W2 of the 7B shape = 256 workgroups, one per CU) or 32 (NB = 2, where that still gives every CU a
+//     workgroup: QKV, the classifier; the two fragments share the activation operand) -- SwiGLU: the same 16 rows of W1 and W3, gate and up meet in one lane.
+//   * the <= 16 quantized activation rows are read through L2 (buffer loads; token columns >= B read as zero and are never stored); their scales sit in LDS,
+//     [groups][16], zero for idle columns and for the ring's groups past the end: fma(0 * 0, float(0), acc) = acc (acc is never -0).
+// int16 models keep the hi / lo-plane tiles (k_gemm_q16_mfma) in the verify pass: correct, not fast.
+// ------------------------------------------------------------------------------------------
+template <int EPI, int NB>
+__device__ __forceinline__ void skinny_epilogue(const GemmArgs& a, const float (&acc)[NB][4], const int rbase, const int lane) {
+    const int q = lane >> 4;
+    if constexpr (EPI == EPI_ROPE_KV) {
+        // a fragment's 16 rows lie inside one of q / k / v (dim is a multiple of 32) and a RoPE pair (rows 2i, 2i + 1) in neighbouring lanes
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            const int row = rbase + j * 16, which = row / a.dim, within = row - which * a.dim, hh = within / a.hs, dd = within - hh * a.hs;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int b = 4 * q + i, pos = a.pos0 + b;
+                const float mine = acc[j][i], other = __shfl_xor(mine, 1, 64);
+                if (row >= a.rows || b >= a.B) continue;
+                float v = mine;
+                if (which < 2) {
+                    const float c = a.rope_cos[(size_t)pos * (a.hs / 2) + dd / 2], sn_ = a.rope_sin[(size_t)pos * (a.hs / 2) + dd / 2];
+                    float o0, o1;
+                    rope_pair((lane & 1) ? other : mine, (lane & 1) ? mine : other, c, sn_, o0, o1);
+                    v = (lane & 1) ? o1 : o0;
+                }
+                if (which == 0) a.qout[(size_t)b * a.dim + within] = v;
+                else (which == 1 ? a.kcache : a.vcache)[((size_t)hh * a.max_seq + pos) * a.hs + dd] = v;
+            }
+        }
+    } else if constexpr (EPI == EPI_SWIGLU) {
+        if (rbase < a.rows) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int b = 4 * q + i;
+                if (b < a.B) st_result_tp(a.out, (size_t)b * a.ldo + rbase, swiglu_elem(acc[0][i], acc[NB - 1][i]), a.out_peer, a.n_peer);   // o1.swiglu(o3) transformer.cpp:481
+            }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            const int row = rbase + j * 16;
+            if (row >= a.rows) continue;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int b = 4 * q + i;
+                if (b >= a.B) continue;
+                const size_t idx = (size_t)b * a.ldo + row;
+                if constexpr (EPI == EPI_RESIDUAL) a.out[idx] = __fadd_rn(a.out[idx], acc[j][i]);
+                else a.out[idx] = acc[j][i];
+            }
+        }
+    }
+}
+constexpr int kSkinnyTokens = 16;
+__host__ __device__ constexpr int skinny_depth(int nb) { return nb == 1 ? 8 : 6; }                       // groups in flight per wave
+__host__ __device__ inline int skinny_groups_padded(int sn, int nb) { const int d = skinny_depth(nb); return (sn + d - 1) / d * d + d; }
+__host__ __device__ inline size_t skinny_lds_bytes(int n, int nb) { return (size_t)skinny_groups_padded(n / kGroup, nb) * kSkinnyTokens * 4; }
+// grid: ceil(rows / (16 NB)) workgroups of 64 threads (SWIGLU: ceil(rows / 16), NB = 2); skinny_lds_bytes(n, NB) of dynamic LDS; B <= 16; single GPU (no peers)
+template <int EPI, int NB>
+__global__ void __launch_bounds__(64) k_gemm_q8_skinny(const GemmArgs a) {
+    constexpr bool TWO = EPI == EPI_SWIGLU;
+    static_assert(!TWO || NB == 2, "gate and up are the two B fragments of the wave");
+    constexpr int D = skinny_depth(NB);
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    float* const sxl = reinterpret_cast<float*>(lds);                       // [groups, padded][16 tokens]
+    const int lane = threadIdx.x, l15 = lane & 15, q = lane >> 4;
+    const int sn = a.n / kGroup, snp = skinny_groups_padded(sn, NB);
+    const int r0 = blockIdx.x * (TWO ? 16 : 16 * NB);
+    for (int i = lane; i < snp * kSkinnyTokens; i += 64) { const int g = i >> 4, b = i & 15; sxl[i] = (g < sn && b < a.B) ? a.Xs[(size_t)b * sn + g] : 0.0f; }
+    __syncthreads();
+    const unsigned rowbytes = (unsigned)a.n;
+    constexpr unsigned kOOB = 0x80000000u;
+    const unsigned s_rows = (TWO ? 2u : 1u) * (unsigned)a.rows;
+    const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.W), 0, (int)(s_rows * rowbytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rX = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.Xq), 0, (int)((unsigned)a.B * rowbytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rS = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.sWT), 0, (int)(s_rows * (unsigned)sn * 4), 0x00020000);
+    // fragment j: rows r0 + 16 j .. (SWIGLU: rows r0 .. of W1 (j = 0) and of W3 (j = 1)); rows past the matrix and groups past the end read as zero
+    unsigned woff[NB], soff[NB];
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+        const int row = r0 + (TWO ? 0 : 16 * j) + l15;
+        const unsigned wrow = (unsigned)(TWO ? j * a.rows + row : row);
+        woff[j] = row < a.rows ? wrow * rowbytes + (unsigned)q * 16 : kOOB;
+        soff[j] = row < a.rows ? wrow * 4 : kOOB;
+    }
+    const unsigned xoff = l15 < a.B ? (unsigned)l15 * rowbytes + (unsigned)q * 16 : kOOB;
+    const unsigned sstep = s_rows * 4;
+    v4u wr[D][NB], xr[D]; unsigned sr[D][NB];
+    auto fetch = [&](const int slot, const int g) {                       // group g -> ring slot `slot`
+        const bool in = g < sn;
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            wr[slot][j] = __builtin_amdgcn_raw_buffer_load_b128(rW, (int)(in && woff[j] != kOOB ? woff[j] + (unsigned)g * kGroup : kOOB), 0, 0);
+            sr[slot][j] = __builtin_amdgcn_raw_buffer_load_b32(rS, (int)(in && soff[j] != kOOB ? soff[j] + (unsigned)g * sstep : kOOB), 0, 0);
+        }
+        xr[slot] = __builtin_amdgcn_raw_buffer_load_b128(rX, (int)(in && xoff != kOOB ? xoff + (unsigned)g * kGroup : kOOB), 0, 0);
+    };
+    float acc[NB][4];
+#pragma unroll
+    for (int j = 0; j < NB; ++j)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[j][i] = 0.f;
+#pragma unroll
+    for (int k = 0; k < D; ++k) fetch(k, k);
+    for (int g0 = 0; g0 < sn; g0 += D) {
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            const int g = g0 + k;                                           // (g >= sn in the last round: zero operands, zero scales)
+            const float4 sx = *reinterpret_cast<const float4*>(sxl + g * kSkinnyTokens + 4 * q);
+#pragma unroll
+            for (int j = 0; j < NB; ++j) {
+                const v4i z = {0, 0, 0, 0};
+                const v4i d = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(v4i, xr[k]), __builtin_bit_cast(v4i, wr[k][j]), z, 0, 0, 0);
+                const float sw = __uint_as_float(sr[k][j]);
+                acc[j][0] = __fmaf_rn(__fmul_rn(sw, sx.x), (float)d[0], acc[j][0]);   // quant_operators.cpp:274
+                acc[j][1] = __fmaf_rn(__fmul_rn(sw, sx.y), (float)d[1], acc[j][1]);
+                acc[j][2] = __fmaf_rn(__fmul_rn(sw, sx.z), (float)d[2], acc[j][2]);
+                acc[j][3] = __fmaf_rn(__fmul_rn(sw, sx.w), (float)d[3], acc[j][3]);
+            }
+            fetch(k, g + D);
+        }
+    }
+    skinny_epilogue<EPI, NB>(a, acc, r0 + l15, lane);
+}
+
 // qkv[b] = [q ; k ; v] (dim each) of token b at position pos0 + b: RoPE on q and k (rope_v2 pairs), q -> qout[b], k / v -> cache rows
 inline __global__ void k_rope_kv_rows(const float* qkv, float* qout, float* kcache, float* vcache, const float* rope_cos, const float* rope_sin,
                                int dim, int hs, int max_seq, int pos0) {

@@ -65,9 +65,30 @@ int launch_gemm(flm_ctx* c, hipStream_t st, const GemmArgs& g, int use_mfma) {
     return FLM_OK;
 }
 
+// The skinny int8 GEMM of the verify pass (flm_prefill.h k_gemm_q8_skinny): B <= 16 tokens, one wave per workgroup.  Two fragments (32 rows) per wave where that still
+// gives every CU a workgroup, else one (16 rows: Wo and W2 of the 7B shape = 256 workgroups); SwiGLU: the same 16 rows of W1 and W3.
+template <int EPI>
+int launch_gemm_skinny(flm_ctx* c, hipStream_t st, const GemmArgs& g, int force_nb = 0) {
+    if (g.B < 1 || g.B > kSkinnyTokens || g.n_peer) return fail(c, FLM_ERR_INVALID, "skinny gemm: 1 .. 16 tokens, one GPU");
+    if ((double)g.rows * g.n * (EPI == EPI_SWIGLU ? 2 : 1) >= 2147483648.0 || skinny_lds_bytes(g.n, 1) > 64 * 1024) return fail(c, FLM_ERR_UNSUPPORTED, "skinny gemm: matrix of 2 GiB or more, or rows longer than 65536");
+    const int cus = c ? c->cu_count : 256;
+    if constexpr (EPI == EPI_SWIGLU) hipLaunchKernelGGL((k_gemm_q8_skinny<EPI_SWIGLU, 2>), dim3((g.rows + 15) / 16), dim3(64), skinny_lds_bytes(g.n, 2), st, g);
+    else if (force_nb == 2 || (force_nb == 0 && (g.rows + 31) / 32 >= cus)) hipLaunchKernelGGL((k_gemm_q8_skinny<EPI, 2>), dim3((g.rows + 31) / 32), dim3(64), skinny_lds_bytes(g.n, 2), st, g);
+    else hipLaunchKernelGGL((k_gemm_q8_skinny<EPI, 1>), dim3((g.rows + 15) / 16), dim3(64), skinny_lds_bytes(g.n, 1), st, g);
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
+// one GEMM of the batched path: the tiles, or -- int8, `skinny` (the verify pass under "spec_gemm" 1) -- the skinny kernel
+template <int QT, int EPI>
+int launch_gemm_any(flm_ctx* c, hipStream_t st, const GemmArgs& g, int use_mfma, bool skinny) {
+    if constexpr (QT == QT_INT8) { if (skinny) return launch_gemm_skinny<EPI>(c, st, g); }
+    return launch_gemm<QT, EPI>(c, st, g, use_mfma);
+}
+
 // all_layers (flm_score_tokens): the last layer runs to its end as well -- pf_x then holds every row's final residual, the classifier's input
 template <int QT>
-int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers) {
+int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req = false) {
+    const bool skinny = skinny_req && QT == QT_INT8 && B <= kSkinnyTokens && c->world == 1;      // (the verify pass; int16: the tiles)
     const auto& d = c->d;
     const int L = d.n_layers, dim = d.dim, hid = d.hidden_dim, hs = c->hs;
     hipStream_t st = c->stream;
@@ -97,13 +118,13 @@ int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers) {
         RowsArgs ra{c->pf_x, w.att_norm, c->pf_xq, c->pf_xs, dim, c->pf_xst};
         r = launch_rows<QT, PRO_RMSNORM_QUANT>(c, st, ra, B, tp); if (r) return r;
         GemmArgs g{w.qkv.q, w.qkv.s, c->pf_xq, c->pf_xs, c->pf_qkv, 3 * dimL, dim, 3 * dimL, B, c->pf_xst, w.qkv.st};
-        if ((QT == QT_INT16 || c->use_mfma) && dimL % 32 == 0 && hs % 2 == 0) {      // (int16: always the matrix-core tiles -- round 5: with the same epilogues as the int8 tiles)
+        if ((QT == QT_INT16 || c->use_mfma || skinny) && dimL % 32 == 0 && hs % 2 == 0) {      // (int16: always the matrix-core tiles -- round 5: with the same epilogues as the int8 tiles)
             // RoPE and the cache rows as the epilogue of the matrix-core tiles: no [tokens][3 dim] round trip, no k_rope_kv_rows
             g.qout = c->pf_q; g.kcache = c->kcache + (size_t)l * kv_layer; g.vcache = c->vcache + (size_t)l * kv_layer;
             g.rope_cos = c->rope_cos; g.rope_sin = c->rope_sin; g.dim = dimL; g.hs = hs; g.max_seq = c->kv_rows /* (the stride between two heads' cache rows) */; g.pos0 = pos;
-            r = launch_gemm<QT, EPI_ROPE_KV>(c, st, g, c->use_mfma); if (r) return r;
+            r = launch_gemm_any<QT, EPI_ROPE_KV>(c, st, g, c->use_mfma, skinny); if (r) return r;
         } else {
-            r = launch_gemm<QT, EPI_STORE>(c, st, g, c->use_mfma); if (r) return r;
+            r = launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, skinny); if (r) return r;
             hipLaunchKernelGGL(k_rope_kv_rows, dim3(B), dim3(256), 0, st, (const float*)c->pf_qkv, c->pf_q, c->kcache + (size_t)l * kv_layer, c->vcache + (size_t)l * kv_layer,
                                (const float*)c->rope_cos, (const float*)c->rope_sin, dimL, hs, c->kv_rows, pos);
             HIPC(c, hipGetLastError());
@@ -145,16 +166,16 @@ int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers) {
         r = launch_rows<QT, PRO_QUANT>(c, st, rq, B, tp); if (r) return r;
         GemmArgs go{w.o.q, w.o.s, c->pf_xq, c->pf_xs, c->pf_x + col_o, dim, dim, rows_o, B, c->pf_xst, w.o.st};
         peers(go, go.out);
-        r = launch_gemm<QT, EPI_RESIDUAL>(c, st, go, c->use_mfma); if (r) return r;
+        r = launch_gemm_any<QT, EPI_RESIDUAL>(c, st, go, c->use_mfma, skinny); if (r) return r;
         if (tp) { r = exchange(c, st, XK_X1, nullptr, nullptr, 0); if (r) return r; }
         // hd = swiglu(W1 qx, W3 qx) with qx = quantize(rmsnorm(x1))   (transformer.cpp:144-147, 468-483): this rank's slice of hd
         RowsArgs rf{c->pf_x, w.ffn_norm, c->pf_xq, c->pf_xs, dim, c->pf_xst};
         r = launch_rows<QT, PRO_RMSNORM_QUANT>(c, st, rf, B, tp); if (r) return r;
-        if (QT == QT_INT16 || (c->use_mfma && (tp || c->use_mfma == 3 || (c->use_mfma == 1 && ((hidL + 63) / 64) * ((B + 127) / 128) >= 256)))) {
+        if (QT == QT_INT16 || skinny || (c->use_mfma && (tp || c->use_mfma == 3 || (c->use_mfma == 1 && ((hidL + 63) / 64) * ((B + 127) / 128) >= 256)))) {
             // 128 x 128 tiles of 64 gate + 64 up rows: the GEMM's epilogue is the SwiGLU
             GemmArgs g13{w.w13.q, w.w13.s, c->pf_xq, c->pf_xs, c->pf_hd + col_h, hid, dim, hidL, B, c->pf_xst, w.w13.st};
             peers(g13, g13.out);
-            r = launch_gemm<QT, EPI_SWIGLU>(c, st, g13, c->use_mfma); if (r) return r;
+            r = launch_gemm_any<QT, EPI_SWIGLU>(c, st, g13, c->use_mfma, skinny); if (r) return r;
         } else {
             GemmArgs g13{w.w13.q, w.w13.s, c->pf_xq, c->pf_xs, c->pf_gu, 2 * hidL, dim, 2 * hidL, B, c->pf_xst, w.w13.st};
             r = launch_gemm<QT, EPI_STORE>(c, st, g13, c->use_mfma); if (r) return r;
@@ -168,7 +189,7 @@ int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers) {
         r = launch_rows<QT, PRO_QUANT>(c, st, rh, B, tp); if (r) return r;
         GemmArgs g2{w.w2.q, w.w2.s, c->pf_xq, c->pf_xs, c->pf_x + col_o, dim, hid, rows_o, B, c->pf_xst, w.w2.st};
         peers(g2, g2.out);
-        r = launch_gemm<QT, EPI_RESIDUAL>(c, st, g2, c->use_mfma); if (r) return r;
+        r = launch_gemm_any<QT, EPI_RESIDUAL>(c, st, g2, c->use_mfma, skinny); if (r) return r;
         if (tp) { r = exchange(c, st, XK_X1, nullptr, nullptr, 0); if (r) return r; }
     }
     return FLM_OK;
@@ -177,9 +198,10 @@ int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers) {
 int launch_gemm_store(flm_ctx* c, hipStream_t st, int qt, const GemmArgs& g, int use_mfma) {
     return qt == FLM_QT_INT8 ? launch_gemm<QT_INT8, EPI_STORE>(c, st, g, use_mfma) : launch_gemm<QT_INT16, EPI_STORE>(c, st, g, use_mfma);
 }
-int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers) {
-    return c->d.quant_type == FLM_QT_INT8 ? prefill_batched<QT_INT8>(c, B, pos, all_layers) : prefill_batched<QT_INT16>(c, B, pos, all_layers);
+int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers, bool skinny) {
+    return c->d.quant_type == FLM_QT_INT8 ? prefill_batched<QT_INT8>(c, B, pos, all_layers, skinny) : prefill_batched<QT_INT16>(c, B, pos, all_layers, skinny);
 }
+int launch_gemm_skinny_store(flm_ctx* c, hipStream_t st, const GemmArgs& g, int force_nb) { return launch_gemm_skinny<EPI_STORE>(c, st, g, force_nb); }
 
 // ---------------------------------------------------------------------------------------------
 // flm_score_tokens: the classifier for a chunk of the batch's rows.  The row prologue is the decode classifier's (rmsnorm with the output norm's weight, quantize), the tiles
@@ -202,7 +224,7 @@ int launch_score_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, i
     return FLM_OK;
 }
 template <int QT>
-static int score_classify_t(flm_ctx* c, int row0, int m, float* stage) {
+static int score_classify_t(flm_ctx* c, int row0, int m, float* stage, bool skinny, int* argmax_out) {
     const int dim = c->d.dim, V = c->d.vocab_size;
     hipStream_t st = c->stream;
     if (!c->cls_st_ready) {   // once per set of weights, like the layers' copies (no allocation: cls.st came with the matrix)
@@ -215,11 +237,20 @@ static int score_classify_t(flm_ctx* c, int row0, int m, float* stage) {
     RowsArgs ra{c->pf_x + (size_t)row0 * dim, c->out_norm, c->pf_xq, c->pf_xs, dim, c->pf_xst};
     int r = launch_rows<QT, PRO_RMSNORM_QUANT>(c, st, ra, m); if (r) return r;
     GemmArgs g{c->cls.q, c->cls.s, c->pf_xq, c->pf_xs, stage, V, dim, V, m, c->pf_xst, c->cls.st};
-    r = launch_gemm<QT, EPI_STORE>(c, st, g, c->use_mfma); if (r) return r;
+    r = launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, skinny && m <= kSkinnyTokens); if (r) return r;
+    if (argmax_out) {   // the verify pass: the rows' first maxima only (no softmax, no sum chain, no LDS strip: any vocabulary)
+        hipLaunchKernelGGL(k_argmax_rows, dim3(m), dim3(kSampleBlock), 0, st, (const float*)stage, V, V, argmax_out + row0);
+        HIPC(c, hipGetLastError());
+        return FLM_OK;
+    }
     return launch_score_rows(c, st, stage, V, V, c->score_tgt + row0, c->score_dev + row0, m);
 }
 int score_classify(flm_ctx* c, int row0, int m, float* stage) {
-    return c->d.quant_type == FLM_QT_INT8 ? score_classify_t<QT_INT8>(c, row0, m, stage) : score_classify_t<QT_INT16>(c, row0, m, stage);
+    return c->d.quant_type == FLM_QT_INT8 ? score_classify_t<QT_INT8>(c, row0, m, stage, false, nullptr) : score_classify_t<QT_INT16>(c, row0, m, stage, false, nullptr);
+}
+// the verify pass's classifier stage: the same chunk through the same prologue and GEMM (skinny: k_gemm_q8_skinny, int8), then k_argmax_rows into argmax_out[row0 ..]
+int spec_classify(flm_ctx* c, int row0, int m, float* stage, bool skinny, int* argmax_out) {
+    return c->d.quant_type == FLM_QT_INT8 ? score_classify_t<QT_INT8>(c, row0, m, stage, skinny, argmax_out) : score_classify_t<QT_INT16>(c, row0, m, stage, false, argmax_out);
 }
 
 } // namespace fh

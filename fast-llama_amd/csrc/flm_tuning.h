@@ -48,6 +48,7 @@ constexpr OptionRow kOptions[] = {
     {"age_epochs", nullptr, kOptDial},
     {"use_prefill", &flm_ctx::use_prefill, 0},
     {"score_rows", &flm_ctx::score_rows, 0},
+    {"spec_gemm", &flm_ctx::spec_gemm, 0},
     {"use_mfma", &flm_ctx::use_mfma, kOptDial | kOptFrozen},
     {"use_pv_mfma", &flm_ctx::use_pv_mfma, kOptFrozen},
     {"use_qk_mfma", &flm_ctx::use_qk_mfma, kOptFrozen},

@@ -217,7 +217,14 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
         };
         uint64_t st = _sampler.state();
         int n_out = 0;
-        const int rc = flm_generate(_ctxs[0], input.data(), n_in, 0, (max_new_tokens > 0 ? max_new_tokens : 0) + 1, temperature, topp, &st, 0, on_token, &sink, nullptr, &n_out);
+        int rc;
+        if (greedy && _lookup_k > 0) {      // --lookup: the same loop through draft-and-verify steps (the same ids and callbacks)
+            rc = flm_generate_lookup(_ctxs[0], input.data(), n_in, 0, (max_new_tokens > 0 ? max_new_tokens : 0) + 1, 0, _lookup_k, _lookup_g, on_token, &sink, nullptr, &n_out);
+            int v = 0;
+            if (rc == FLM_OK && flm_query(_ctxs[0], "spec_steps", &v) == FLM_OK) _lookup_steps += v;
+            if (rc == FLM_OK && flm_query(_ctxs[0], "spec_accepted", &v) == FLM_OK) _lookup_accepted += v;
+        } else
+        rc = flm_generate(_ctxs[0], input.data(), n_in, 0, (max_new_tokens > 0 ? max_new_tokens : 0) + 1, temperature, topp, &st, 0, on_token, &sink, nullptr, &n_out);
         if (rc == FLM_OK) { if (!greedy) _sampler.set_state(st); return true; }
         if (rc != FLM_ERR_UNSUPPORTED) return false;
         dev_sample = false;

@@ -33,6 +33,11 @@ public:
     // --mode score (this build only): the prompt's tokens through flm_score_tokens in one call; one line per position (index, token id, argmax id, the probability of the
     // next token), then a summary line (token count, mean natural-log loss, perplexity, ms)
     bool score(const char* prompt);
+    // --lookup K[,G] (this build only): temperature-0 generation on one device runs through flm_generate_lookup (draft-and-verify with the prompt-lookup drafter: the same ids,
+    // several per pass over the weights); lookup_steps / lookup_accepted: verify passes run / drafted ids accepted, summed over the generate calls
+    void set_lookup(int draft_len, int ngram_max) { _lookup_k = draft_len; _lookup_g = ngram_max; }
+    int lookup_steps() const { return _lookup_steps; }
+    int lookup_accepted() const { return _lookup_accepted; }
     int get_quant_type() const { return _cfg.quant_type; }
     const std::string& error() const { return _err; }
     // more than one device: which launch structure of the sharded token load() settled on (calibrate_structure), for --detail
@@ -52,6 +57,7 @@ private:
     // run f(rank) on every rank at once (the ranks wait for each other's slices inside the launches); first non-zero status wins
     int on_all(const std::function<int(int)>& f);
     std::string _err;
+    int _lookup_k = 0, _lookup_g = 3, _lookup_steps = 0, _lookup_accepted = 0;
 };
 
 } // namespace flmhost

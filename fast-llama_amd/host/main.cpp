@@ -31,6 +31,8 @@ struct Args {
     bool use_numa = false, detail = false, debug = false;
     std::vector<int> devices;
     const char* bad_devices = nullptr;      // a --devices argument that did not parse
+    int lookup_k = 0, lookup_g = 3;         // --lookup K[,G]: draft length (4..15; 0 = off) and longest n-gram (1..8) of the prompt-lookup drafter
+    const char* bad_lookup = nullptr;
     Mode mode = Mode::GEN;
 };
 const char* Y = "\x1b[33m"; const char* G = "\x1b[32m"; const char* E = "\x1b[0m";
@@ -49,6 +51,7 @@ void usage(const char* bin) {
     fprintf(stderr, "   --threads,-j      <number>    accepted for compatibility (the GPU build has no worker threads)\n");
     fprintf(stderr, "   --device          <number>    HIP device ordinal (this build only)\n");
     fprintf(stderr, "   --devices         <a,b,...>   shard ONE sequence over these HIP devices, 1 to 8 of them (this build only)\n");
+    fprintf(stderr, "   --lookup          <K[,G]>     with -t 0 on one device: draft K (4..15) tokens per step by prompt lookup (n-grams up to G, 1..8, default 3) and verify them in one pass; the same text (this build only)\n");
     fprintf(stderr, "   --encode,-e       <string>    encode the input string into tokens\n");
     fprintf(stderr, "   --decode,-d       <string>    decode the input tokens to text\n");
     fprintf(stderr, "   --help,-h                     print this message\n");
@@ -96,6 +99,11 @@ const Flag kFlags[] = {
     {"-m", "--mode",           true,  [](Args& a, const char* v) { pick<Mode>(v, {{"gen", Mode::GEN}, {"generate", Mode::GEN}, {"chat", Mode::CHAT}, {"benchmark", Mode::TEST}, {"bm", Mode::TEST}, {"score", Mode::SCORE}}, a.mode); }},
     {nullptr, "--device",      true,  [](Args& a, const char* v) { a.device = atoi(v); }},                                  // (this build only)
     {nullptr, "--devices",     true,  [](Args& a, const char* v) { if (!parse_devices(v, a.devices)) a.bad_devices = v; }},   // (this build only)
+    {nullptr, "--lookup",      true,  [](Args& a, const char* v) {                                                            // (this build only)
+        char* e; const long k = strtol(v, &e, 10); long g = 3;
+        bool ok = e != v && k >= 4 && k <= 15;
+        if (ok && *e == ',') { const char* s = e + 1; g = strtol(s, &e, 10); ok = e != s && g >= 1 && g <= 8; }
+        if (ok && *e == 0) { a.lookup_k = (int)k; a.lookup_g = (int)g; } else a.bad_lookup = v; }},
 };
 }
 void parse(Args& a, int argc, const char** argv) {
@@ -110,6 +118,7 @@ void parse(Args& a, int argc, const char** argv) {
         hit->apply(a, v);
         if (a.bad_devices) { fprintf(stderr, "Invalid --devices list:\x1b[31m%s\x1b[0m (expected 1 to 8 HIP device ordinals, e.g. 0,1,2,3)\n", a.bad_devices); usage(argv[0]); exit(-1); }
     }
+    if (a.bad_lookup) { fprintf(stderr, "Invalid --lookup:\x1b[31m%s\x1b[0m (expected K or K,G with 4 <= K <= 15 and 1 <= G <= 8)\n", a.bad_lookup); usage(argv[0]); exit(-1); }
     if (a.rounds < 1) a.rounds = a.mode == Mode::TEST ? 16 : 1;
 }
 
@@ -145,7 +154,12 @@ int main(int argc, const char** argv) {
     if (args.devices.empty()) args.devices.push_back(args.device);
     // ranks sharing a GPU wait for each other inside their launches: each needs a hardware queue of its own (HIP's default is 4 per process)
     if (args.devices.size() > 1) setenv("GPU_MAX_HW_QUEUES", "16", 0);
+    if (args.lookup_k && (args.devices.size() > 1 || args.temp != 0.0f)) {
+        fprintf(stderr, "warning: --lookup applies to -t 0 on one device only; ignored\n");
+        args.lookup_k = 0;
+    }
     GpuTransformer tf(args.detail || args.debug);
+    if (args.lookup_k) tf.set_lookup(args.lookup_k, args.lookup_g);
     if (!tf.load(args.ckpt, args.tknr, args.ft, args.qtype, args.devices)) { fprintf(stderr, "Failed to load model\n%s\n", tf.error().c_str()); return 1; }
     args.qtype = tf.get_quant_type();
     if (args.detail) fprintf(stderr, "Model loaded\n\n");
@@ -178,8 +192,10 @@ int main(int argc, const char** argv) {
     const char* qn = args.qtype == 2 ? "int8" : args.qtype == 1 ? "int16" : args.qtype == 3 ? "int4" : "None";
     // the reference's summary line (main.cpp:136-145); simd_size reports the wavefront width here
     printf("num_threads:%s%2d%s\tquant:%s%s%s\tuse_numa:%s%d%s\tsimd_size:%d\tprompt_size:%3d\toutput_size:%3d\ttotal_latancy:%5.0fms\t"
-           "prompt_token_latancy:%s%4.2f%sms\toutput_token_latancy:%s%4.2f%sms\tprompt_speed:%s%5.1f%stps\toutput_speed:%s%5.1f%stps\n",
+           "prompt_token_latancy:%s%4.2f%sms\toutput_token_latancy:%s%4.2f%sms\tprompt_speed:%s%5.1f%stps\toutput_speed:%s%5.1f%stps",
            Y, args.num_threads, E, G, qn, E, G, (int)args.use_numa, E, 64, (int)pt, (int)ot, pm + om,
            Y, first_lat, E, Y, later_lat, E, G, 1000. / first_lat, E, G, 1000. / later_lat, E);
+    if (args.lookup_k) printf("\tlookup:%d,%d\taccepted/steps:%s%d/%d%s", args.lookup_k, args.lookup_g, G, tf.lookup_accepted(), tf.lookup_steps(), E);   // (--lookup only: without it the line is the reference's)
+    printf("\n");
     return 0;
 }

@@ -8,6 +8,7 @@
 
 #include "model_file.h"
 #include "sampler.h"
+#include "spec_draft.h"
 #include "tokenizer.h"
 
 using namespace flmhost;
@@ -91,6 +92,8 @@ void fh_score_row(const float* x, int n, int target, void* out5) {
     if (target >= 0 && target < n) { r.target_logit = x[target]; r.prob = et * (float)(1. / sum); }
     memcpy(out5, &r, sizeof r);
 }
+// the prompt-lookup drafter of flm_generate_lookup (spec_draft.h): h[n] -> d[k]; the expected value of the device's k_spec_draft
+void fh_spec_draft(const int32_t* h, int n, int k, int ngram_max, int32_t* d) { spec_draft(h, n, k, ngram_max, d); }
 void fh_quantize(const float* x, size_t n, int qtype, void* q, float* scales) { quantize_groups(x, n, qtype, q, scales); }
 
 }

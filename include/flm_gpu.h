@@ -180,6 +180,35 @@ typedef struct flm_score { int32_t argmax; float target_logit, max_logit, sum, p
 int  flm_score_tokens(flm_ctx* ctx, const int32_t* tokens, int n, int pos,
                       const int32_t* targets /* [n], NULL: tokens[i + 1], none for the last */,
                       flm_score* out /* [n] */, float* logits_all /* [n][vocab], may be NULL */);
+/* Greedy draft-and-verify: several ids per pass over the weights, the ids of flm_decode_greedy element for element.
+ * flm_verify_greedy is the primitive, for callers with a drafter of their own: first_token and drafts[0 .. k) run as ONE batch of k + 1 rows at positions pos .. pos + k through
+ * the batched prompt kernels (every row, the last layer and the classifier included: no token goes through the decode kernels); a[i] = the first maximum of row i's logits
+ * (sample_argmax); on the device m = the first i with a[i] != drafts[i] (k if there is none).  *n_out = m + 1 and out_tokens[0 .. m] = a[0 .. m]: exactly what the decode loop
+ * started with first_token at pos returns for m + 1 steps -- a batched row's logits are flm_forward's bit for bit and the argmax is pinned, so this is equality, not a tolerance.
+ * Afterwards the K/V rows pos .. pos + m are valid and are the token path's bits; the rows behind them are stale (every entry point writes a row before it reads it); the caller
+ * continues at pos + m + 1 with token out_tokens[m], through any entry point.  4 <= k <= 15 (batches of 5 .. 16 rows).  Errors, with nothing launched: FLM_ERR_INVALID for k
+ * outside 4 .. 15, pos + k + 1 > max_seq_len, ids outside [0, vocab); FLM_ERR_UNSUPPORTED for world > 1; FLM_ERR_STATE before the model is complete.  No vocabulary bound (an
+ * argmax needs no LDS strip).  Nothing is allocated in the call; the m + 1 ids come back in one trip.
+ * The weight pass: option "spec_gemm" 1 = int8 models run every GEMM of the batch through the skinny kernel (v_mfma_i32_16x16x64_i8, 16 tokens x 16 rows x one quant group per
+ * instruction, weights from global memory straight into the operand registers, one wave per 16 or 32 rows so that every matrix of the 7B shape fills 256 CUs); 0 = the 64 x 64
+ * tiles of the prompt path.  int16 models always run the hi / lo-plane tiles here: correct, not fast. */
+int  flm_verify_greedy(flm_ctx* ctx, int32_t first_token, const int32_t* drafts, int k, int pos,
+                       int32_t* out_tokens /* [k + 1] */, int* n_out);
+/* The loop on top of it, with a built-in prompt-lookup drafter: flm_generate's contract at temperature 0 for *n_out, out_tokens and cb (the stop token is delivered and counted
+ * with last = 1 and not fed; the loop ends after max_tokens or behind a callback's non-zero return; cb runs on the calling thread in index order, for all accepted ids of a step).
+ * The prompt enters exactly as in flm_forward_argmax.  A step = draft -> a batch of draft_len + 1 rows -> row argmax -> accept, all on the device:
+ *   drafter   over the call's history h[0 .. n) (the prompt and every accepted id, in device memory): for g = min(ngram_max, n - 1) down to 1 the LARGEST j with j + g <= n - 1 and
+ *             h[j .. j + g) == h[n - g .. n); the first g with a match wins, period p = n - g - j; d[i] = h[n - p + i] for i < p, else d[i - p]; no match: d[i] = h[n - 1].
+ *             The choice is a maximum over the matching positions, independent of the order in which waves finish
+ *   accept    the verified run is cut behind the first stop token and at max_tokens, appended to the history, and left with m where the host reads both in one trip
+ * The batched kernels take the position as a launch argument, so the host learns m before it enqueues the next step: ONE host synchronisation per step (a device-resident or
+ * graph-captured loop is not built).  Where pos + draft_len + 1 would pass max_seq_len, or fewer than 2 ids are still wanted, the step is an ordinary one-launch greedy token; the
+ * ids are the same.  FLM_ERR_INVALID if pos + n_prompt + max_tokens - 1 > max_seq_len, draft_len outside 4 .. 15 or ngram_max outside 1 .. 8; FLM_ERR_UNSUPPORTED for world > 1.
+ * Temperature > 0 is not built.  flm_query: "spec_steps" / "spec_accepted" = the last call's verify passes / drafted ids accepted in them. */
+int  flm_generate_lookup(flm_ctx* ctx, const int32_t* prompt, int n_prompt, int pos, int max_tokens,
+                         int32_t stop_token /* -1: none */, int draft_len /* 4..15 */, int ngram_max /* 1..8 */,
+                         flm_token_cb cb /* may be NULL */, void* user,
+                         int32_t* out_tokens /* [max_tokens], may be NULL */, int* n_out);
 /* the ids generated by the last flm_decode_greedy / flm_decode_sample / flm_decode_timed* call: out[n] (n <= its n_steps) */
 int  flm_last_tokens(flm_ctx* ctx, int n, int32_t* out);
 int  flm_reset_kv(flm_ctx* ctx);
@@ -226,6 +255,8 @@ int  flm_debug_read(flm_ctx* ctx, int what, int layer, float* out, size_t n);
  *   "attn_split"     0 = one workgroup per head at every context length (default 1: hs / 32 workgroups per head from 128 positions on; n >= 2: always n)
  *   "use_prefill"    0 = prompts token by token (default 1: batched; under tensor parallelism once the peers are mapped with flm_p2p_import)
  *   "score_rows"     n = flm_score_tokens runs its classifier on chunks of at most n rows (default 0: as many rows as the staging holds; < 0: one row at a time through the logits vector, the staging of a context without prefill scores)
+ *   "spec_gemm"      1 = flm_verify_greedy / flm_generate_lookup run the verify batch's int8 GEMMs on the skinny kernel for <= 16 rows (default 0: the prompt path's 64 x 64
+ *                    tiles, until both forms have been timed on the device: DESIGN.md section 5e); the same bits; no other entry point looks at it
  *   "use_prefill_mq" 0 = batched attention with one query per workgroup (default 1: eight)
  *   "use_qk_mfma" / "use_pv_mfma"  0 = prefill scores / softmax x V on VALU chains (default 1: v_mfma_f32_16x16x4_f32, the same bits)
  * Tensor parallel (set on every rank alike, before flm_p2p_export where noted):
@@ -263,6 +294,7 @@ int  flm_set_option(flm_ctx* ctx, const char* key, int value);
  *               classifier, argmax in k_layers<.., TAIL>),
  *   "ao_active" which hand-offs of that launch are consumed in arrival order: bit 0 Wo, bit 1 FFN2 (-1: the launch has not been planned yet),
  *   "sampled_tokens" how many tokens this context sampled on the device (flm_forward_sample / flm_decode_sample / flm_generate at temperature > 0),
+ *   "spec_steps" / "spec_accepted" the last flm_generate_lookup call: verify passes run / drafted ids accepted in them,
  *   "gen_tokens" / "gen_streamed" the last flm_generate call: tokens delivered / how many of them were delivered while hipStreamQuery still said the stream was busy,
  *   "epoch_tail" / "epoch_eng" / "epoch_xchg" the epoch counters the cross-workgroup waits count from (device memory; the 32-bit pattern): the one-launch token's, the
  *               tensor-parallel token's epoch base, k_xchg's logits exchanges (the long-lived-context tests).
@@ -277,6 +309,12 @@ int  flm_op_quantize(int qt, void* qx, float* qs, const float* x, size_t n, int 
  * kernel); w >= 16: the tile kernels of the batched prompt path (int8 and int16 on the int8 matrix cores; FLM_OP_GEMM=1|2|3: the tile shape) */
 int  flm_op_matmul_q(int qt, float* out, const void* mat1, const float* scales1,
                      const void* mat2, const float* scales2, int m, int n, int w, int gs);
+/* the same product for 1 <= w <= 16 batch rows through the skinny int8 kernel of the verify pass (k_gemm_q8_skinny); FLM_QT_INT8 only
+ * (FLM_OP_SKINNY_NB=1|2: 16-row fragments per wave; by size otherwise) */
+int  flm_op_matmul_skinny(int qt, float* out, const void* mat1, const float* scales1,
+                          const void* mat2, const float* scales2, int m, int n, int w, int gs);
+/* the prompt-lookup drafter of flm_generate_lookup (k_spec_draft) on a caller-supplied history h[n]: d[k], 1 <= k <= 15, 1 <= ngram_max <= 8 */
+int  flm_op_spec_draft(const int32_t* h, int n, int k, int ngram_max, int32_t* d);
 /* simd::rmsnorm(o,x,w,n) (x86_simd.cpp:1754-1764) */
 int  flm_op_rmsnorm(float* o, const float* x, const float* w, size_t n);
 /* simd::square_sum (x86_simd.cpp:942-960), n % 16 == 0, n <= 16384: out6 = { total from the speculative wave evaluation the
