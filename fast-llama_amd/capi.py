@@ -26,6 +26,7 @@ SYMBOLS = (
     "flm_op_attention", "flm_op_expf", "flm_op_math", "flm_op_square_sum", "flm_op_argmax", "flm_op_handoff_litmus", "flm_plan_shards",
     "flm_forward_sample", "flm_decode_sample", "flm_op_sample", "flm_generate", "flm_score_tokens", "flm_op_score_rows",
     "flm_verify_greedy", "flm_generate_lookup", "flm_op_matmul_skinny", "flm_op_spec_draft",
+    "flm_verify_sample", "flm_generate_lookup_sample", "flm_op_sample_rows",
 )
 
 # flm_score (include/flm_gpu.h): one row of flm_score_tokens / flm_op_score_rows
@@ -237,6 +238,39 @@ class Ctx:
         _check(rc, self._h)
         return out[:n_out.value].copy() if want_ids else np.empty(0, dtype=np.int32)
 
+    def verify_sample(self, first_token, drafts, pos, temperature, topp, rng_state):
+        """flm_verify_sample -> (the m + 1 ids the sampled decode loop started with first_token at pos and rng_state draws, m = the drafts that were right; the state after
+        those m + 1 draws).  rng_state None: a NULL pointer (allowed at temperature 0)."""
+        d = np.ascontiguousarray(drafts, dtype=np.int32)
+        out = np.empty(len(d) + 1, dtype=np.int32); n_out = C.c_int(0)
+        st = None if rng_state is None else C.c_uint64(int(rng_state))
+        _check(lib().flm_verify_sample(self._h, int(first_token), _p(d), len(d), int(pos), C.c_float(temperature), C.c_float(topp),
+                                       C.byref(st) if st is not None else None, _p(out), C.byref(n_out)), self._h)
+        return out[:n_out.value].copy(), (st.value if st is not None else None)
+
+    def generate_lookup_sample(self, prompt, pos, max_tokens, temperature=1.0, topp=0.9, rng_state=0, stop_token=-1, draft_len=7, ngram_max=3, on_token=None, want_ids=True):
+        """flm_generate_lookup_sample -> (ids[n_out], the sampler state after the n_out draws): flm_generate at any temperature through draft-and-verify steps.
+        on_token(index, token, last) as in generate."""
+        t = np.ascontiguousarray(prompt, dtype=np.int32)
+        out = np.empty(max(int(max_tokens), 1), dtype=np.int32) if want_ids else None
+        st = C.c_uint64(int(rng_state)); n_out = C.c_int(0)
+        raised = []
+
+        def tramp(_user, index, token, last):
+            try:
+                return 1 if on_token(int(index), int(token), bool(last)) else 0
+            except BaseException as e:      # (an exception must not unwind through the C frames: cancel, re-raise behind the call)
+                raised.append(e)
+                return 1
+        cb = TOKEN_CB(tramp) if on_token is not None else C.cast(None, TOKEN_CB)
+        rc = lib().flm_generate_lookup_sample(self._h, _p(t), len(t), int(pos), int(max_tokens), C.c_float(temperature), C.c_float(topp), C.byref(st),
+                                              C.c_int32(int(stop_token)), int(draft_len), int(ngram_max), cb, None, _p(out), C.byref(n_out))
+        del cb
+        if raised:
+            raise raised[0]
+        _check(rc, self._h)
+        return (out[:n_out.value].copy() if want_ids else np.empty(0, dtype=np.int32)), st.value
+
     def decode_timed(self, first_token, pos, n_steps) -> float:
         ms = C.c_float(0)
         _check(lib().flm_decode_timed(self._h, int(first_token), int(pos), int(n_steps), C.byref(ms)), self._h)
@@ -376,6 +410,15 @@ def op_sample(logits, temperature, topp, rng_state):
     out = C.c_int32(-1); st = C.c_uint64(int(rng_state))
     _check(lib().flm_op_sample(_p(a), int(a.size), C.c_float(temperature), C.c_float(topp), C.byref(st), C.byref(out)))
     return out.value, st.value
+
+
+def op_sample_rows(logits, n, temperature, topp, rng_state):
+    """k_sample_rows on logits[rows][ld], the first n entries of each row -> (ids[rows], the sampler state after `rows` draws): row i with the (i + 1)-th coin"""
+    a = np.ascontiguousarray(logits, dtype=np.float32)
+    a = a.reshape(1, -1) if a.ndim == 1 else a
+    out = np.full(a.shape[0], -1, dtype=np.int32); st = C.c_uint64(int(rng_state))
+    _check(lib().flm_op_sample_rows(_p(a), int(a.shape[0]), int(a.shape[1]), int(n), C.c_float(temperature), C.c_float(topp), C.byref(st), _p(out)))
+    return out, st.value
 
 
 def op_score_rows(logits, targets=None):

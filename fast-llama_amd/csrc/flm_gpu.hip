@@ -327,6 +327,7 @@ int alloc_run_bufs(flm_ctx* c) {
     HIPC(c, dev_alloc(c, &c->spec_hist, sizeof(int) * ((size_t)d.max_seq_len + 32), true));   // flm_generate_lookup: the call's token history; a verify batch's row maxima and result block
     HIPC(c, dev_alloc(c, &c->spec_arg, sizeof(int) * 16, true));
     HIPC(c, dev_alloc(c, &c->spec_out, sizeof(SpecOut), true));
+    HIPC(c, dev_alloc(c, &c->spec_out_s, sizeof(SpecOutSample), true));
     c->bounce_bytes = (size_t)d.vocab_size * 4; if (c->bounce_bytes < sizeof(ScoreRow) * (size_t)d.max_seq_len) c->bounce_bytes = sizeof(ScoreRow) * (size_t)d.max_seq_len;   // (a row of logits | max_seq_len ids | max_seq_len flm_score: each one trip)
     HIPC(c, hipHostMalloc((void**)&c->bounce, c->bounce_bytes + 64, hipHostMallocDefault));          // (+ a line for the error word that rides along: d2h)
     {   // flm_generate's granule ring (max_seq_len entries of 8 bytes) and, a line behind it, the cancel word: the device stores / loads them at system scope while the host polls / writes
@@ -606,7 +607,7 @@ int flm_ctx_create(const flm_model_desc* desc, int device_id, int rank, int worl
     HIPB(dev_alloc(c, &c->att_sc, (size_t)c->heads_local * d.max_seq_len * 8, true));   // (8 bytes per score: the parts of a split head exchange them as {score, tag} granules inside k_layers' granule launches, as floats elsewhere)
     HIPB(dev_alloc(c, &c->state, sizeof(DecodeState), true));
     HIPB(dev_alloc(c, &c->sparams, sizeof(SampleParams), true));   // the device sampler's parameter block and sort buffers
-    HIPB(dev_alloc(c, &c->sort_buf, (size_t)2 * d.vocab_size * sizeof(unsigned long long)));
+    if (sample_supported(c)) HIPB(dev_alloc(c, &c->sort_buf, (size_t)kSpecRows * 2 * d.vocab_size * sizeof(unsigned long long)));   // ([16][2][vocab]: a slice per row of a sampled verify batch)
     std::vector<float> cs, sn; build_rope_table(hs, d.max_seq_len, cs, sn);
     HIPB(dev_alloc(c, &c->rope_cos, cs.size() * 4)); HIPB(dev_alloc(c, &c->rope_sin, sn.size() * 4));
     // (copies on the context's stream, never on the legacy stream: another context's thread may be capturing its token graph)
@@ -979,7 +980,9 @@ static float* score_stage(const flm_ctx* c, int* chunk) {
 }
 // One verify pass at `pos` over the batch prompt_dev[0 .. k] (draft: written by the drafter from the history spec_hist[0 .. n_hist) first): all layers, the classifier in
 // chunks, the rows' first maxima, the accept step.  Enqueues only; the result block spec_out is read by the caller.
-static int spec_step(flm_ctx* c, int pos, int k, int ngram_max, int n_hist, int stop, int room, bool draft) {
+// draw given (the sampled entry points): the rows are drawn by k_sample_rows with the coins of draw->base (temperature 0: first maxima, as above), and the accept step is
+// k_spec_accept_sample into spec_out_s, which also leaves the state after the step's draws.  Without it: the launches of the greedy entry points, unchanged.
+static int spec_step(flm_ctx* c, int pos, int k, int ngram_max, int n_hist, int stop, int room, bool draft, const SpecDraw* draw = nullptr) {
     const int B = k + 1;
     if (draft) {
         hipLaunchKernelGGL(k_spec_draft, dim3(1), dim3(kSampleBlock), 0, c->stream, (const int*)c->spec_hist, n_hist, k, ngram_max, c->prompt_dev);
@@ -990,9 +993,10 @@ static int spec_step(flm_ctx* c, int pos, int k, int ngram_max, int n_hist, int 
     int chunk = 1; float* const stage = score_stage(c, &chunk);
     for (int r0 = 0; r0 < B; r0 += chunk) {
         const int m = B - r0 < chunk ? B - r0 : chunk;
-        r = spec_classify(c, r0, m, stage, skinny, c->spec_arg); if (r) return r;
+        r = spec_classify(c, r0, m, stage, skinny, c->spec_arg, draw); if (r) return r;
     }
-    hipLaunchKernelGGL(k_spec_accept, dim3(1), dim3(64), 0, c->stream, c->spec_out, (const int*)c->spec_arg, (const int*)c->prompt_dev, k, draft ? c->spec_hist : (int*)nullptr, n_hist, stop, room);
+    if (draw) hipLaunchKernelGGL(k_spec_accept_sample, dim3(1), dim3(64), 0, c->stream, c->spec_out_s, (const int*)c->spec_arg, (const int*)c->prompt_dev, k, draft ? c->spec_hist : (int*)nullptr, n_hist, stop, room, draw->base, draw->temperature != 0.0f ? 1 : 0);
+    else hipLaunchKernelGGL(k_spec_accept, dim3(1), dim3(64), 0, c->stream, c->spec_out, (const int*)c->spec_arg, (const int*)c->prompt_dev, k, draft ? c->spec_hist : (int*)nullptr, n_hist, stop, room);
     HIPC(c, hipGetLastError());
     return FLM_OK;
 }
@@ -1435,6 +1439,104 @@ int flm_generate_lookup(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos
         if (r) return r;
     }
     *n_out = total;
+    c->spec_steps = steps; c->spec_accepted = accepted;
+    return FLM_OK;
+}
+
+// Sampled draft-and-verify (include/flm_gpu.h).  The sampler is a function of (logits, the coin), the coin of the sampled decode loop's i-th token is the i-th draw of its
+// xorshift state, and a batched row's logits are flm_forward's bits: so row i of a verify batch, drawn with the (i + 1)-th coin of the step's state (k_sample_rows: the draw
+// k_sample_advance makes, one function), is the id the loop draws behind rows 0 .. i - 1 -- as long as the drafts were those ids.  The accept step cuts at the first draft that
+// differs and leaves the state after as many draws as ids it delivers (k_spec_accept_sample); the coins drawn for the rows behind the cut are simply not counted.  Equality with
+// flm_decode_sample, not rejection sampling.  Temperature 0: the greedy form's kernels (first maxima, no coin, the state untouched).
+int flm_verify_sample(flm_ctx* c, int32_t first_token, const int32_t* drafts, int k, int pos, float temperature, float topp, uint64_t* rng_state, int32_t* out_tokens, int* n_out) {
+    if (!c || !drafts || !out_tokens || !n_out) return fail(c, FLM_ERR_INVALID, "verify: null argument");
+    if (c->world > 1 || (c->comm && c->force_tp)) return fail(c, FLM_ERR_UNSUPPORTED, "verify: one GPU only");
+    if (k < 4 || k > 15) return fail(c, FLM_ERR_INVALID, "verify: 4 <= k <= 15 drafts");
+    if (!(temperature >= 0.0f) || topp != topp) return fail(c, FLM_ERR_INVALID, "verify: temperature must be >= 0, top-p a number");
+    int r = check_ready(c, k + 1, pos); if (r) return r;
+    const int V = c->d.vocab_size;
+    if (first_token < 0 || first_token >= V) return fail(c, FLM_ERR_INVALID, "token id out of range");
+    for (int i = 0; i < k; ++i) if (drafts[i] < 0 || drafts[i] >= V) return fail(c, FLM_ERR_INVALID, "verify: draft outside [0, vocab)");
+    const bool sampled = temperature != 0.0f;
+    if (sampled) { r = sample_args_ok(c, temperature, topp, rng_state); if (r) return r; }
+    SpecOutSample so{};
+    return with_retry(c, k + 1, [&]() -> int {
+        int32_t* b = c->gen_ids.data();                                               // (pageable staging of max_seq_len ids, there since create)
+        b[0] = first_token; for (int i = 0; i < k; ++i) b[1 + i] = drafts[i];
+        int r = h2d(c, c->prompt_dev, b, sizeof(int) * (size_t)(k + 1)); if (r) return r;
+        const SpecDraw draw{temperature, topp, sampled ? (unsigned long long)*rng_state : 0ull};
+        r = spec_step(c, pos, k, 0, 0, -1, k + 1, false, &draw); if (r) return r;
+        return d2h(c, &so, c->spec_out_s, sizeof so);                                 // (the ids and the state in one trip; the error word rides along)
+    }, [&] {
+        memcpy(out_tokens, so.o.ids, sizeof(int32_t) * (size_t)so.o.n_emit);
+        *n_out = so.o.n_emit;
+        if (sampled) { *rng_state = so.rng; c->sampled += so.o.n_emit; }
+    });
+}
+
+// flm_generate_lookup at any temperature: the same loop, the same drafter, the same history; token 0 is drawn from the prompt's last logits with the first coin (the sampled token
+// graph, as in flm_forward_sample), every step draws its rows with the coins of the state the HOST holds at the step's start -- a launch argument, like n_hist and room, so a
+// re-run step draws the same coins -- and brings back the state after the draws it delivered, in the block that carries the ids.  A single-token step is the sampled token graph
+// (k_sample_advance reads the device parameter block, written from the host's state first) and the accept kernel with K = 0.
+int flm_generate_lookup_sample(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, int max_tokens, float temperature, float topp, uint64_t* rng_state,
+                               int32_t stop_token, int draft_len, int ngram_max, flm_token_cb cb, void* user, int32_t* out_tokens, int* n_out) {
+    if (!c || !prompt || !n_out) return FLM_ERR_INVALID;
+    if (c->world > 1 || (c->comm && c->force_tp)) return fail(c, FLM_ERR_UNSUPPORTED, "generate_lookup: one GPU only");
+    if (max_tokens < 1 || !(temperature >= 0.0f) || topp != topp || stop_token >= c->d.vocab_size || draft_len < 4 || draft_len > 15 || ngram_max < 1 || ngram_max > 8)
+        return fail(c, FLM_ERR_INVALID, "generate_lookup: max_tokens >= 1, temperature >= 0, stop_token < vocab_size (or -1), 4 <= draft_len <= 15, 1 <= ngram_max <= 8");
+    int r = check_ready(c, n_prompt, pos); if (r) return r;
+    if (pos + n_prompt + max_tokens - 1 > c->d.max_seq_len || max_tokens > c->out_cap) return fail(c, FLM_ERR_INVALID, "generate_lookup: pos + n_prompt + max_tokens - 1 exceeds max_seq_len");
+    for (int i = 0; i < n_prompt; ++i) if (prompt[i] < 0 || prompt[i] >= c->d.vocab_size) return fail(c, FLM_ERR_INVALID, "token id out of range");
+    const bool sampled = temperature != 0.0f;
+    if (sampled) { r = sample_args_ok(c, temperature, topp, rng_state); if (r) return r; }
+    const int stop = stop_token < 0 ? -1 : stop_token, advance = sampled ? 3 : 1;
+    int total = 0, steps = 0, accepted = 0; bool done = false, cancelled = false;
+    int32_t last_tok = 0;
+    unsigned long long state = sampled ? (unsigned long long)*rng_state : 0ull;      // the sampler's state behind the ids delivered so far
+    SpecOutSample so{};
+    auto deliver = [&]() {                       // the step's ids, in index order, on this thread; the state moves with them
+        for (int i = 0; i < so.o.n_emit; ++i) {
+            const int index = total + i;
+            const bool last = i + 1 == so.o.n_emit && (so.o.stopped || index + 1 == max_tokens);
+            if (out_tokens) out_tokens[index] = so.o.ids[i];
+            if (cb && !cancelled && cb(user, index, so.o.ids[i], last ? 1 : 0) != 0) cancelled = true;
+        }
+        total += so.o.n_emit; last_tok = so.o.ids[so.o.n_emit - 1]; state = so.rng;
+        done = so.o.stopped || total >= max_tokens || cancelled;
+    };
+    // one token through the token graph and the accept kernel with K = 0: the id from the decode state's first output slot, cut / appended / counted like a verified run of one
+    auto accept_one = [&](int n_hist, int room) -> int {
+        hipLaunchKernelGGL(k_spec_accept_sample, dim3(1), dim3(64), 0, c->stream, c->spec_out_s, (const int*)c->out_tokens_dev, (const int*)c->prompt_dev, 0, c->spec_hist, n_hist, stop, room, state, sampled ? 1 : 0);
+        if (hipGetLastError() != hipSuccess) return fail(c, FLM_ERR_HIP, "generate_lookup: launch failed");
+        return d2h(c, &so, c->spec_out_s, sizeof so);
+    };
+    // token 0: the prompt, exactly as flm_forward_sample (flm_forward_argmax) feeds it; the history starts as the prompt and that id
+    r = with_retry(c, n_prompt, [&]() -> int {
+        int r = sampled ? set_sample(c, temperature, topp, state) : FLM_OK; if (r) return r;
+        r = feed(c, prompt, n_prompt, pos, advance); if (r) return r;
+        hipLaunchKernelGGL(k_spec_begin, dim3(1), dim3(256), 0, c->stream, c->spec_hist, (const int*)c->prompt_dev, n_prompt, (const int*)c->out_tokens_dev, &c->spec_out_s->o, stop);
+        HIPC(c, hipGetLastError());
+        return accept_one(n_prompt, max_tokens);
+    }, deliver);
+    if (r) return r;
+    while (!done) {
+        const int at = pos + n_prompt + total - 1, room = max_tokens - total, n_hist = n_prompt + total;       // the last id is fed at `at`
+        const bool batch = room >= 2 && at + draft_len + 1 <= c->d.max_seq_len;
+        r = with_retry(c, batch ? draft_len + 1 : 1, [&]() -> int {
+            if (batch) {
+                const SpecDraw draw{temperature, topp, state};
+                int r = spec_step(c, at, draft_len, ngram_max, n_hist, stop, room, true, &draw); if (r) return r;
+                return d2h(c, &so, c->spec_out_s, sizeof so);
+            }
+            int r = sampled ? set_sample(c, temperature, topp, state) : FLM_OK; if (r) return r;
+            r = set_state(c, at, last_tok, 0); if (r) return r;
+            r = run_token(c, true, advance, at + 1); if (r) return r;
+            return accept_one(n_hist, room);
+        }, [&] { if (batch) { steps += 1; accepted += so.o.n_emit - 1; } deliver(); });
+        if (r) return r;
+    }
+    *n_out = total;
+    if (sampled) { *rng_state = state; c->sampled += total; }
     c->spec_steps = steps; c->spec_accepted = accepted;
     return FLM_OK;
 }

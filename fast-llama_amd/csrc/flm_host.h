@@ -143,7 +143,8 @@ struct flm_ctx {
     bool fb_active = false; int fb_tokens = 0; std::vector<int> fb_saved;   // ... it is there now / tokens since / the launch structure it had (the kOptFallback rows of flm_tuning.h, in row order; restored when the census passes again: maybe_recover)
     int trace_class = -1; unsigned long long* trace = nullptr;   // FLM_ABLATE builds: GEMV timeline of one kernel class
     // the device sampler (flm_sample.h): per-call parameters written at the start of each flm_forward_sample / flm_decode_sample (the token graphs read them), the radix
-    // sort's ping-pong buffers [2][vocab], and how many tokens this context sampled on the device ("sampled_tokens")
+    // sort's ping-pong buffers [16][2][vocab] (one [2][vocab] slice per row of a sampled verify batch; the token path sorts in slice 0; null where the vocabulary is beyond
+    // the sampler: sample_supported), and how many tokens this context sampled on the device ("sampled_tokens")
     flm::SampleParams* sparams = nullptr; unsigned long long* sort_buf = nullptr; long long sampled = 0;
     // flm_generate (flm_gpu.hip): the granule ring [max_seq_len] and the cancel word -- page-locked, mapped, host-coherent memory allocated at create (gen_host; the device's view of it:
     // gen_ring_dev / gen_cancel_dev) --, what set_state writes into the decode state's generate words (gen_stop .. gen_max: -1 / 0 / 0 outside a flm_generate call), the
@@ -157,6 +158,7 @@ struct flm_ctx {
     // flm_verify_greedy / flm_generate_lookup (flm_gpu.hip; kernels: flm_spec.h): the call's token history [max_seq_len + 32], the batch rows' first maxima [16] and the step's
     // result block, device memory since create; which GEMM the verify pass runs; the last call's figures ("spec_steps" / "spec_accepted")
     int* spec_hist = nullptr; int* spec_arg = nullptr; flm::SpecOut* spec_out = nullptr;
+    flm::SpecOutSample* spec_out_s = nullptr;          // flm_verify_sample / flm_generate_lookup_sample: their step's result block (the ids and the sampler's state behind them, one trip)
     int spec_gemm = 0;                                 // option "spec_gemm": 1 = the verify pass's int8 GEMMs through k_gemm_q8_skinny (B <= 16), 0 (default until both forms have been timed: DESIGN.md section 5e) = the 64 x 64 tiles; the new entry points only
     int spec_steps = 0, spec_accepted = 0;
     int score_rows = 0;                                // option "score_rows": rows per classifier chunk of flm_score_tokens (0: as many as the staging holds; < 0: one row at a time through c->logits)
@@ -272,7 +274,12 @@ int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers = false, bool
 // `stage` [m][vocab], k_score_rows into score_dev[row0 ..]
 int score_classify(flm_ctx* c, int row0, int m, float* stage);
 // the verify pass's classifier stage (flm_prompt.hip): score_classify's prologue and GEMM (skinny: k_gemm_q8_skinny), then k_argmax_rows into argmax_out[row0 ..]
-int spec_classify(flm_ctx* c, int row0, int m, float* stage, bool skinny, int* argmax_out);
+// (draw: the sampled verify pass -- temperature, top-p and the step's xorshift state: k_sample_rows draws row row0 + i with that state's (row0 + i + 1)-th coin; null or temperature 0: k_argmax_rows)
+struct SpecDraw { float temperature, topp; unsigned long long base; };
+int spec_classify(flm_ctx* c, int row0, int m, float* stage, bool skinny, int* argmax_out, const SpecDraw* draw = nullptr);
+// k_sample_rows on `rows` <= 16 rows of n logits, ld floats apart, batch rows row0 ..; sort_buf [rows][2][n] (flm_prompt.hip; c may be null: flm_op_sample_rows)
+int launch_sample_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, int n, int row0, int rows, float temperature, float topp, unsigned long long base,
+                       unsigned long long* sort_buf, int* out);
 int launch_gemm_skinny_store(flm_ctx* c, hipStream_t st, const GemmArgs& g, int force_nb = 0);   // (flm_prompt.hip: k_gemm_q8_skinny, plain store epilogue: flm_op_matmul_skinny; c may be null; force_nb 1 / 2: that many 16-row fragments per wave, 0: by size)
 // k_score_rows on `rows` rows of n logits, ld floats apart (c may be null: flm_op_score_rows)
 int launch_score_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, int n, const int* targets, flm::ScoreRow* out, int rows);

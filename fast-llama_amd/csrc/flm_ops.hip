@@ -191,6 +191,21 @@ int flm_op_sample(const float* logits, int n, float temperature, float topp, uin
     return FLM_OK;
 }
 
+/* k_sample_rows -- the sampler over the rows of a sampled verify batch -- on caller-supplied logits[rows][ld]: row i drawn with the (i + 1)-th coin of *rng_state */
+int flm_op_sample_rows(const float* logits, int rows, int ld, int n, float temperature, float topp, uint64_t* rng_state, int32_t* out) {
+    if (!logits || !rng_state || !out || rows < 1 || rows > kSpecRows || n < 2 || ld < n || !(temperature >= 0.0f) || topp != topp) return FLM_ERR_INVALID;
+    if (sample_lds_bytes(n) > kLdsMax) return FLM_ERR_UNSUPPORTED;
+    DevBuf dl, dout, dsort;
+    if (dl.alloc((size_t)rows * ld * 4) || dout.alloc((size_t)kSpecRows * 4) || dsort.alloc((size_t)rows * 2 * n * 8)) return FLM_ERR_OOM;
+    OPC(hipMemcpy(dl.p, logits, (size_t)rows * ld * 4, hipMemcpyHostToDevice));
+    OPC(hipMemset(dout.p, 0xff, (size_t)kSpecRows * 4));
+    int r = launch_sample_rows(nullptr, 0, dl.as<float>(), ld, n, 0, rows, temperature, topp, (unsigned long long)*rng_state, dsort.as<unsigned long long>(), dout.as<int>()); if (r) return r;
+    OPC(hipDeviceSynchronize());
+    OPC(hipMemcpy(out, dout.p, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    if (temperature != 0.0f) { unsigned long long s = *rng_state; for (int i = 0; i < rows; ++i) s = sample_step(s); *rng_state = s; }   // (one coin per row: the state after `rows` draws)
+    return FLM_OK;
+}
+
 /* k_score_rows -- the statistics kernel of flm_score_tokens -- on caller-supplied rows of logits */
 int flm_op_score_rows(const float* logits, int rows, int n, const int32_t* targets, flm_score* out) {
     if (!logits || !out || rows < 1 || n < 2) return FLM_ERR_INVALID;

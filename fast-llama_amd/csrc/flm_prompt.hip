@@ -223,8 +223,25 @@ int launch_score_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, i
     HIPC(c, hipGetLastError());
     return FLM_OK;
 }
+// k_sample_rows on `rows` rows of n logits, ld floats apart: batch rows row0 .. row0 + rows - 1 of a step whose state is `base` (flm_sample.h)
+int launch_sample_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, int n, int row0, int rows, float temperature, float topp, unsigned long long base,
+                       unsigned long long* sort_buf, int* out) {
+    {   // the strip of a large vocabulary: the dynamic-LDS limit, once per device (flm_ctx_create raises it for the contexts' devices)
+        static std::mutex mu; static bool done[64] = {false};
+        int dev = 0; HIPC(c, hipGetDevice(&dev));
+        std::lock_guard<std::mutex> lk(mu);
+        if (dev >= 0 && dev < 64 && !done[dev]) {
+            HIPC(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sample_rows), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
+            done[dev] = true;
+        }
+    }
+    if (rows < 1 || row0 < 0 || row0 + rows > kSpecRows) return fail(c, FLM_ERR_INVALID, "sample_rows: rows outside a batch of 16");
+    hipLaunchKernelGGL(k_sample_rows, dim3(rows), dim3(kSampleBlock), sample_lds_bytes(n), st, logits, ld, n, row0, temperature, topp, base, sort_buf, out);
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
 template <int QT>
-static int score_classify_t(flm_ctx* c, int row0, int m, float* stage, bool skinny, int* argmax_out) {
+static int score_classify_t(flm_ctx* c, int row0, int m, float* stage, bool skinny, int* argmax_out, const SpecDraw* draw = nullptr) {
     const int dim = c->d.dim, V = c->d.vocab_size;
     hipStream_t st = c->stream;
     if (!c->cls_st_ready) {   // once per set of weights, like the layers' copies (no allocation: cls.st came with the matrix)
@@ -238,6 +255,8 @@ static int score_classify_t(flm_ctx* c, int row0, int m, float* stage, bool skin
     int r = launch_rows<QT, PRO_RMSNORM_QUANT>(c, st, ra, m); if (r) return r;
     GemmArgs g{c->cls.q, c->cls.s, c->pf_xq, c->pf_xs, stage, V, dim, V, m, c->pf_xst, c->cls.st};
     r = launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, skinny && m <= kSkinnyTokens); if (r) return r;
+    if (argmax_out && draw && draw->temperature != 0.0f)      // the sampled verify pass: row row0 + i drawn with the (row0 + i + 1)-th coin of the step's state
+        return launch_sample_rows(c, st, stage, V, V, row0, m, draw->temperature, draw->topp, draw->base, c->sort_buf, argmax_out);
     if (argmax_out) {   // the verify pass: the rows' first maxima only (no softmax, no sum chain, no LDS strip: any vocabulary)
         hipLaunchKernelGGL(k_argmax_rows, dim3(m), dim3(kSampleBlock), 0, st, (const float*)stage, V, V, argmax_out + row0);
         HIPC(c, hipGetLastError());
@@ -249,8 +268,9 @@ int score_classify(flm_ctx* c, int row0, int m, float* stage) {
     return c->d.quant_type == FLM_QT_INT8 ? score_classify_t<QT_INT8>(c, row0, m, stage, false, nullptr) : score_classify_t<QT_INT16>(c, row0, m, stage, false, nullptr);
 }
 // the verify pass's classifier stage: the same chunk through the same prologue and GEMM (skinny: k_gemm_q8_skinny, int8), then k_argmax_rows into argmax_out[row0 ..]
-int spec_classify(flm_ctx* c, int row0, int m, float* stage, bool skinny, int* argmax_out) {
-    return c->d.quant_type == FLM_QT_INT8 ? score_classify_t<QT_INT8>(c, row0, m, stage, skinny, argmax_out) : score_classify_t<QT_INT16>(c, row0, m, stage, false, argmax_out);
+// (draw given and its temperature > 0: k_sample_rows in place of k_argmax_rows)
+int spec_classify(flm_ctx* c, int row0, int m, float* stage, bool skinny, int* argmax_out, const SpecDraw* draw) {
+    return c->d.quant_type == FLM_QT_INT8 ? score_classify_t<QT_INT8>(c, row0, m, stage, skinny, argmax_out, draw) : score_classify_t<QT_INT16>(c, row0, m, stage, false, argmax_out, draw);
 }
 
 } // namespace fh

@@ -11,6 +11,8 @@
 // the strip); digits that are equal in every candidate are skipped.
 // Coin == 0 (the CLI's seed 0 keeps the state at 0 for ever): multinomial returns the first index with p > 0, top-p the lowest index among the maximal probabilities;
 // both still need the exact sum (p = e * (1 / sum) can tie where the logits differ), neither needs the sort or a cumulative chain.
+// k_sample_rows is the same draw (sample_draw, the one function both kernels call) over the rows of a verify batch, row i with the (i + 1)-th coin of the step's state:
+// what the sampled decode loop draws at its i-th token (flm_spec.h).
 #pragma once
 #include "flm_math.h"
 #include "flm_gemv.h"
@@ -36,8 +38,9 @@ struct SampleArgs {
 };
 
 // xorshift* (sampler.cpp random_u32 / random_f32): the coin of one draw
+__host__ __device__ __forceinline__ unsigned long long sample_step(unsigned long long s) { s ^= s >> 12; s ^= s << 25; s ^= s >> 27; return s; }
 __device__ __forceinline__ float sample_coin(unsigned long long& s) {
-    s ^= s >> 12; s ^= s << 25; s ^= s >> 27;
+    s = sample_step(s);
     const unsigned r = (unsigned)((s * 0x2545F4914F6CDD1Dull) >> 32);
     return __fdiv_rn((float)(r >> 8), 16777216.0f);
 }
@@ -103,30 +106,27 @@ __device__ __forceinline__ void wave_excl_scan256(const int* in, int* out) {
     out[4 * lane] = e; out[4 * lane + 1] = e + a0; out[4 * lane + 2] = e + a0 + a1; out[4 * lane + 3] = e + a0 + a1 + a2;
 }
 
-// One workgroup of 1024 threads, sample_lds_bytes(n) of dynamic LDS, n >= 2.  Writes out_tokens[step], advances the state like k_argmax_advance, and the sampler state.
-inline __global__ void __launch_bounds__(kSampleBlock) k_sample_advance(const SampleArgs a) {
-    extern __shared__ float4 sample_lds4[];
-    if (halted(&a.st->halt)) return;       // (flm_math.h DecodeState::halt: the sampler state stays at the last drawn token's)
-    float* strip = reinterpret_cast<float*>(sample_lds4);
-    const int n = a.n, B = sample_lane_elems(n), LS = B + 4;
+// ONE draw of Sampler::sample by one workgroup of 1024 threads: the token for `logits[0 .. n)` at (temp, topp), n >= 2, with the coin drawn from `rng` (advanced by that one
+// draw; untouched at temp == 0).  strip: sample_lds_bytes(n) of LDS; sort_buf: [2][n] of the workgroup's own.  Every thread returns the token.  Both sampler kernels are this
+// function: k_sample_advance (the token path: one row, then the decode state's advance) and k_sample_rows (a verify batch: one workgroup per row).
+__device__ __forceinline__ int sample_draw(const float* logits, int n, float temp, float topp, unsigned long long& rng, unsigned long long* sort_buf, float* strip) {
+    const int B = sample_lane_elems(n), LS = B + 4;
     int* cnt = reinterpret_cast<int*>(strip + 64 * LS);
     int* dbase = cnt + kSampleWaves * 256;
     int* hist = dbase + 256;
     int* misc = hist + 4 * 256;            // [0..31] reductions, [32] result, [33] sum / n0, [36..39] "digit d is the same in every candidate"
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const float temp = a.sp->temperature, topp = a.sp->topp;
-    unsigned long long rng = a.sp->rng;
     auto spos = [&](int i) { const int L = i / B; return L * LS + (i - L * B); };       // element i's place in the strip
     int tok;
     if (temp == 0.0f) {
         // sample_argmax: first maximum wins, the state is not touched
-        tok = block_first_max([&](int i) { return a.logits[i]; }, n, 0, misc);
+        tok = block_first_max([&](int i) { return logits[i]; }, n, 0, misc);
     } else {
         // logits[q] /= temperature; the max of the divided values
         float mx = -INFINITY;
         for (int i = t; i < 64 * B; i += kSampleBlock) {
             float x = 0.f;
-            if (i < n) { x = __fdiv_rn(a.logits[i], temp); mx = fmaxf(mx, x); }
+            if (i < n) { x = __fdiv_rn(logits[i], temp); mx = fmaxf(mx, x); }
             strip[spos(i)] = x;
         }
         mx = wave_max(mx);
@@ -196,8 +196,8 @@ inline __global__ void __launch_bounds__(kSampleBlock) k_sample_advance(const Sa
                     if (misc[36 + d] && (any || d < 3 || src >= 0)) continue;          // (a digit equal in every candidate orders nothing; one pass runs in any case)
                     if (w == 0) wave_excl_scan256(hist + d * 256, dbase);
                     const int dstb = src < 0 ? 0 : src ^ 1;
-                    const unsigned long long* sb = a.sort_buf + (size_t)(src < 0 ? 0 : src) * n;
-                    unsigned long long* db = a.sort_buf + (size_t)dstb * n;
+                    const unsigned long long* sb = sort_buf + (size_t)(src < 0 ? 0 : src) * n;
+                    unsigned long long* db = sort_buf + (size_t)dstb * n;
                     const int N = src < 0 ? n : n0;
 #pragma unroll 1
                     for (int b0 = 0; b0 < N; b0 += kSampleBlock) {
@@ -225,7 +225,7 @@ inline __global__ void __launch_bounds__(kSampleBlock) k_sample_advance(const Sa
                     }
                     src = dstb;
                 }
-                const unsigned long long* sorted = a.sort_buf + (size_t)src * n;
+                const unsigned long long* sorted = sort_buf + (size_t)src * n;
                 // the sorted probabilities as a strip of their own; cum = the chain up to the first element where cum > topp (last), r = coin * cum,
                 // then the first element up to last with r < cdf -- the same chain again
                 const int B2 = sample_lane_elems(n0), LS2 = B2 + 4;
@@ -247,7 +247,16 @@ inline __global__ void __launch_bounds__(kSampleBlock) k_sample_advance(const Sa
             }
         }
     }
-    if (t == 0) {
+    return tok;
+}
+
+// One workgroup of 1024 threads, sample_lds_bytes(n) of dynamic LDS, n >= 2.  Writes out_tokens[step], advances the state like k_argmax_advance, and the sampler state.
+inline __global__ void __launch_bounds__(kSampleBlock) k_sample_advance(const SampleArgs a) {
+    extern __shared__ float4 sample_lds4[];
+    if (halted(&a.st->halt)) return;       // (flm_math.h DecodeState::halt: the sampler state stays at the last drawn token's)
+    unsigned long long rng = a.sp->rng;
+    const int tok = sample_draw(a.logits, a.n, a.sp->temperature, a.sp->topp, rng, a.sort_buf, reinterpret_cast<float*>(sample_lds4));
+    if (threadIdx.x == 0) {
         DecodeState* st = a.st;
         if (a.out_tokens && st->step >= 0 && st->step < a.out_cap) a.out_tokens[st->step] = tok;
         const bool halt = gen_last_act(st, st->step, tok, a.err);                               // (the token's last act: flm_math.h)
@@ -255,6 +264,21 @@ inline __global__ void __launch_bounds__(kSampleBlock) k_sample_advance(const Sa
         st->step += 1;
         a.sp->rng = rng;
     }
+}
+
+// The same draw over the rows of a verify batch's classifier chunk: one workgroup per row, grid = the chunk's rows, sample_lds_bytes(n) of dynamic LDS.  Row r of the
+// chunk (logits + r * ld) is batch row row0 + r: its coin is the (row0 + r + 1)-th draw from `base`, the state at the step's start -- every workgroup steps the state
+// there itself (row0 + r < kSpecRows steps), so no row waits for another.  Row r sorts in its own [2][n] slice of sort_buf.  Writes out[row0 + r] and nothing else.
+// temp == 0: the first maximum, no coin.
+constexpr int kSpecRows = 16;
+inline __global__ void __launch_bounds__(kSampleBlock) k_sample_rows(const float* __restrict__ logits, int ld, int n, int row0, float temp, float topp,
+                                                                     unsigned long long base, unsigned long long* sort_buf, int* __restrict__ out) {
+    extern __shared__ float4 sample_lds4[];
+    const int r = blockIdx.x, row = row0 + r;
+    unsigned long long rng = base;
+    for (int i = 0; i < row && i < kSpecRows; ++i) rng = sample_step(rng);
+    const int tok = sample_draw(logits + (size_t)r * ld, n, temp, topp, rng, sort_buf + (size_t)r * 2 * n, reinterpret_cast<float*>(sample_lds4));
+    if (threadIdx.x == 0) out[row] = tok;
 }
 
 } // namespace flm

@@ -217,14 +217,25 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
         };
         uint64_t st = _sampler.state();
         int n_out = 0;
-        int rc;
-        if (greedy && _lookup_k > 0) {      // --lookup: the same loop through draft-and-verify steps (the same ids and callbacks)
-            rc = flm_generate_lookup(_ctxs[0], input.data(), n_in, 0, (max_new_tokens > 0 ? max_new_tokens : 0) + 1, 0, _lookup_k, _lookup_g, on_token, &sink, nullptr, &n_out);
+        const int want = (max_new_tokens > 0 ? max_new_tokens : 0) + 1;
+        int rc = FLM_ERR_UNSUPPORTED;
+        bool whole = true;                  // the plain loop (flm_generate) still has to run
+        auto count = [&] {
             int v = 0;
             if (rc == FLM_OK && flm_query(_ctxs[0], "spec_steps", &v) == FLM_OK) _lookup_steps += v;
             if (rc == FLM_OK && flm_query(_ctxs[0], "spec_accepted", &v) == FLM_OK) _lookup_accepted += v;
-        } else
-        rc = flm_generate(_ctxs[0], input.data(), n_in, 0, (max_new_tokens > 0 ? max_new_tokens : 0) + 1, temperature, topp, &st, 0, on_token, &sink, nullptr, &n_out);
+        };
+        if (_draft_k > 0) {                 // --draft: the same loop through draft-and-verify steps at the run's temperature; refused (nothing was launched): the run without the flag
+            rc = greedy ? flm_generate_lookup(_ctxs[0], input.data(), n_in, 0, want, 0, _draft_k, _draft_g, on_token, &sink, nullptr, &n_out)
+                        : flm_generate_lookup_sample(_ctxs[0], input.data(), n_in, 0, want, temperature, topp, &st, 0, _draft_k, _draft_g, on_token, &sink, nullptr, &n_out);
+            count();
+            whole = rc == FLM_ERR_UNSUPPORTED;
+        } else if (greedy && _lookup_k > 0) {      // --lookup: the same loop through draft-and-verify steps (the same ids and callbacks)
+            rc = flm_generate_lookup(_ctxs[0], input.data(), n_in, 0, want, 0, _lookup_k, _lookup_g, on_token, &sink, nullptr, &n_out);
+            count();
+            whole = false;
+        }
+        if (whole) rc = flm_generate(_ctxs[0], input.data(), n_in, 0, want, temperature, topp, &st, 0, on_token, &sink, nullptr, &n_out);
         if (rc == FLM_OK) { if (!greedy) _sampler.set_state(st); return true; }
         if (rc != FLM_ERR_UNSUPPORTED) return false;
         dev_sample = false;

@@ -36,6 +36,9 @@ public:
     // --lookup K[,G] (this build only): temperature-0 generation on one device runs through flm_generate_lookup (draft-and-verify with the prompt-lookup drafter: the same ids,
     // several per pass over the weights); lookup_steps / lookup_accepted: verify passes run / drafted ids accepted, summed over the generate calls
     void set_lookup(int draft_len, int ngram_max) { _lookup_k = draft_len; _lookup_g = ngram_max; }
+    // --draft K[,G] (this build only): the same at whatever temperature the run has: at 0 flm_generate_lookup, otherwise flm_generate_lookup_sample with the Sampler's state (written
+    // back afterwards) -- the same ids as the sampled loop's; where the library refuses (FLM_ERR_UNSUPPORTED) the run is what it is without the flag.  Counted in lookup_steps / _accepted
+    void set_draft(int draft_len, int ngram_max) { _draft_k = draft_len; _draft_g = ngram_max; }
     int lookup_steps() const { return _lookup_steps; }
     int lookup_accepted() const { return _lookup_accepted; }
     int get_quant_type() const { return _cfg.quant_type; }
@@ -58,6 +61,7 @@ private:
     int on_all(const std::function<int(int)>& f);
     std::string _err;
     int _lookup_k = 0, _lookup_g = 3, _lookup_steps = 0, _lookup_accepted = 0;
+    int _draft_k = 0, _draft_g = 3;
 };
 
 } // namespace flmhost

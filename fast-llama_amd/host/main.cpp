@@ -33,6 +33,8 @@ struct Args {
     const char* bad_devices = nullptr;      // a --devices argument that did not parse
     int lookup_k = 0, lookup_g = 3;         // --lookup K[,G]: draft length (4..15; 0 = off) and longest n-gram (1..8) of the prompt-lookup drafter
     const char* bad_lookup = nullptr;
+    int draft_k = 0, draft_g = 3;           // --draft K[,G]: the same drafter and ranges at whatever temperature the run has (-t 0: flm_generate_lookup, else flm_generate_lookup_sample)
+    const char* bad_draft = nullptr;
     Mode mode = Mode::GEN;
 };
 const char* Y = "\x1b[33m"; const char* G = "\x1b[32m"; const char* E = "\x1b[0m";
@@ -52,6 +54,7 @@ void usage(const char* bin) {
     fprintf(stderr, "   --device          <number>    HIP device ordinal (this build only)\n");
     fprintf(stderr, "   --devices         <a,b,...>   shard ONE sequence over these HIP devices, 1 to 8 of them (this build only)\n");
     fprintf(stderr, "   --lookup          <K[,G]>     with -t 0 on one device: draft K (4..15) tokens per step by prompt lookup (n-grams up to G, 1..8, default 3) and verify them in one pass; the same text (this build only)\n");
+    fprintf(stderr, "   --draft           <K[,G]>     on one device, at any temperature: draft K (4..15) tokens per step by prompt lookup (n-grams up to G, 1..8, default 3) and verify them in one pass, sampled rows drawn with the sampler's own coins; the same text (this build only)\n");
     fprintf(stderr, "   --encode,-e       <string>    encode the input string into tokens\n");
     fprintf(stderr, "   --decode,-d       <string>    decode the input tokens to text\n");
     fprintf(stderr, "   --help,-h                     print this message\n");
@@ -69,6 +72,14 @@ bool parse_devices(const char* v, std::vector<int>& out) {      // a comma-separ
         if (ok) { out.push_back((int)d); v = *e ? e + 1 : e; }
     }
     return ok;
+}
+bool parse_draft(const char* v, int& k_out, int& g_out) {       // K or K,G with 4 <= K <= 15 and 1 <= G <= 8 (default 3), nothing else
+    char* e; const long k = strtol(v, &e, 10); long g = 3;
+    bool ok = e != v && k >= 4 && k <= 15;
+    if (ok && *e == ',') { const char* s = e + 1; g = strtol(s, &e, 10); ok = e != s && g >= 1 && g <= 8; }
+    if (!ok || *e != 0) return false;
+    k_out = (int)k; g_out = (int)g;
+    return true;
 }
 template <class E> bool pick(const char* v, std::initializer_list<std::pair<const char*, E>> names, E& out) {     // case-insensitive keyword -> enum; unknown words leave `out` alone (as the reference does)
     for (const auto& n : names) if (!strcasecmp(v, n.first)) { out = n.second; return true; }
@@ -104,6 +115,7 @@ const Flag kFlags[] = {
         bool ok = e != v && k >= 4 && k <= 15;
         if (ok && *e == ',') { const char* s = e + 1; g = strtol(s, &e, 10); ok = e != s && g >= 1 && g <= 8; }
         if (ok && *e == 0) { a.lookup_k = (int)k; a.lookup_g = (int)g; } else a.bad_lookup = v; }},
+    {nullptr, "--draft",       true,  [](Args& a, const char* v) { if (!parse_draft(v, a.draft_k, a.draft_g)) a.bad_draft = v; }},                 // (this build only)
 };
 }
 void parse(Args& a, int argc, const char** argv) {
@@ -119,6 +131,7 @@ void parse(Args& a, int argc, const char** argv) {
         if (a.bad_devices) { fprintf(stderr, "Invalid --devices list:\x1b[31m%s\x1b[0m (expected 1 to 8 HIP device ordinals, e.g. 0,1,2,3)\n", a.bad_devices); usage(argv[0]); exit(-1); }
     }
     if (a.bad_lookup) { fprintf(stderr, "Invalid --lookup:\x1b[31m%s\x1b[0m (expected K or K,G with 4 <= K <= 15 and 1 <= G <= 8)\n", a.bad_lookup); usage(argv[0]); exit(-1); }
+    if (a.bad_draft) { fprintf(stderr, "Invalid --draft:\x1b[31m%s\x1b[0m (expected K or K,G with 4 <= K <= 15 and 1 <= G <= 8)\n", a.bad_draft); usage(argv[0]); exit(-1); }
     if (a.rounds < 1) a.rounds = a.mode == Mode::TEST ? 16 : 1;
 }
 
@@ -158,8 +171,13 @@ int main(int argc, const char** argv) {
         fprintf(stderr, "warning: --lookup applies to -t 0 on one device only; ignored\n");
         args.lookup_k = 0;
     }
+    if (args.draft_k && args.devices.size() > 1) {
+        fprintf(stderr, "warning: --draft applies to one device only; ignored\n");
+        args.draft_k = 0;
+    }
     GpuTransformer tf(args.detail || args.debug);
     if (args.lookup_k) tf.set_lookup(args.lookup_k, args.lookup_g);
+    if (args.draft_k) tf.set_draft(args.draft_k, args.draft_g);
     if (!tf.load(args.ckpt, args.tknr, args.ft, args.qtype, args.devices)) { fprintf(stderr, "Failed to load model\n%s\n", tf.error().c_str()); return 1; }
     args.qtype = tf.get_quant_type();
     if (args.detail) fprintf(stderr, "Model loaded\n\n");
@@ -196,6 +214,7 @@ int main(int argc, const char** argv) {
            Y, args.num_threads, E, G, qn, E, G, (int)args.use_numa, E, 64, (int)pt, (int)ot, pm + om,
            Y, first_lat, E, Y, later_lat, E, G, 1000. / first_lat, E, G, 1000. / later_lat, E);
     if (args.lookup_k) printf("\tlookup:%d,%d\taccepted/steps:%s%d/%d%s", args.lookup_k, args.lookup_g, G, tf.lookup_accepted(), tf.lookup_steps(), E);   // (--lookup only: without it the line is the reference's)
+    if (args.draft_k) printf("\tdraft:%d,%d\taccepted/steps:%s%d/%d%s", args.draft_k, args.draft_g, G, tf.lookup_accepted(), tf.lookup_steps(), E);      // (--draft only)
     printf("\n");
     return 0;
 }

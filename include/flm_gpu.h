@@ -204,11 +204,37 @@ int  flm_verify_greedy(flm_ctx* ctx, int32_t first_token, const int32_t* drafts,
  * The batched kernels take the position as a launch argument, so the host learns m before it enqueues the next step: ONE host synchronisation per step (a device-resident or
  * graph-captured loop is not built).  Where pos + draft_len + 1 would pass max_seq_len, or fewer than 2 ids are still wanted, the step is an ordinary one-launch greedy token; the
  * ids are the same.  FLM_ERR_INVALID if pos + n_prompt + max_tokens - 1 > max_seq_len, draft_len outside 4 .. 15 or ngram_max outside 1 .. 8; FLM_ERR_UNSUPPORTED for world > 1.
- * Temperature > 0 is not built.  flm_query: "spec_steps" / "spec_accepted" = the last call's verify passes / drafted ids accepted in them. */
+ * Temperature > 0: flm_generate_lookup_sample below.  flm_query: "spec_steps" / "spec_accepted" = the last call's verify passes / drafted ids accepted in them. */
 int  flm_generate_lookup(flm_ctx* ctx, const int32_t* prompt, int n_prompt, int pos, int max_tokens,
                          int32_t stop_token /* -1: none */, int draft_len /* 4..15 */, int ngram_max /* 1..8 */,
                          flm_token_cb cb /* may be NULL */, void* user,
                          int32_t* out_tokens /* [max_tokens], may be NULL */, int* n_out);
+/* Sampled draft-and-verify: the ids of flm_decode_sample element for element, several per pass over the weights.  The sampler is a function of a row's logits and one coin, and
+ * token i of a sampled decode loop is drawn with the i-th coin of its xorshift state; so row i of a verify batch is drawn with the (i + 1)-th coin of the step's state
+ * (k_sample_rows: one 1024-thread workgroup per row, every row the draw flm_forward_sample makes -- the IEEE division by the temperature, the clipped expf, the sequential sum
+ * chain, multinomial or top-p behind the stable radix sort; the two kernels share that code), and the batch is cut at the first draw that differs from its draft.  This is
+ * equality, not rejection sampling: no id is re-drawn and no tolerance is involved; a call consumes exactly as many coins as it returns ids.
+ * flm_verify_sample is flm_verify_greedy's contract with the row argmax replaced by the row draw: s[i] = row i drawn with the (i + 1)-th coin of *rng_state, m = the first i with
+ * s[i] != drafts[i] (k if none), out_tokens[0 .. m] = s[0 .. m], *n_out = m + 1, *rng_state = the state after m + 1 draws -- what flm_decode_sample(first_token, pos, m + 1,
+ * temperature, topp, the same state) returns and leaves; the K/V rows pos .. pos + m are the token path's bits.  temperature == 0: flm_verify_greedy's result, the state
+ * untouched (rng_state may be NULL; no vocabulary bound).  Errors as in flm_verify_greedy, and FLM_ERR_INVALID for a NULL rng_state at temperature != 0, a negative or NaN
+ * temperature, a NaN top-p; FLM_ERR_UNSUPPORTED at temperature != 0 where flm_decode_sample refuses (the vocabulary bound).  Nothing is launched on any error; nothing is
+ * allocated in the call (the rows sort in slices of a [16][2][vocab] buffer that exists since flm_ctx_create); the ids and the state come back in one trip. */
+int  flm_verify_sample(flm_ctx* ctx, int32_t first_token, const int32_t* drafts, int k, int pos,
+                       float temperature, float topp, uint64_t* rng_state /* NULL allowed iff temperature == 0 */,
+                       int32_t* out_tokens /* [k + 1] */, int* n_out);
+/* flm_generate's contract at ANY temperature through draft-and-verify steps with flm_generate_lookup's drafter: the same ids, *n_out, callbacks and final state as flm_generate
+ * with the same arguments (a callback's cancel ends the call behind the step that delivered it; *rng_state is then the state after *n_out draws all the same).  Token 0 is drawn
+ * from the prompt's last logits with the first coin, as flm_forward_sample does it; every step is draft -> the batch -> the rows' draws -> accept, and the accept step leaves, next
+ * to m and the ids, the state after exactly as many draws as ids it delivers (a run cut by the stop token or max_tokens counts only the ids in front of the cut).  The step's
+ * state is a launch argument from the host, so a step that is re-run (the retry path) draws the same coins and delivers nothing twice.  Where fewer than 2 ids are still wanted,
+ * or the batch would pass max_seq_len, the step is one ordinary sampled token.  *rng_state on return: the state after *n_out draws (untouched at temperature 0, where the call is
+ * flm_generate_lookup).  Errors as in flm_generate_lookup and flm_generate; one GPU only.  "spec_steps" / "spec_accepted" as there; the ids count in "sampled_tokens". */
+int  flm_generate_lookup_sample(flm_ctx* ctx, const int32_t* prompt, int n_prompt, int pos, int max_tokens,
+                                float temperature, float topp, uint64_t* rng_state /* NULL allowed iff temperature == 0 */,
+                                int32_t stop_token /* -1: none */, int draft_len /* 4..15 */, int ngram_max /* 1..8 */,
+                                flm_token_cb cb /* may be NULL */, void* user,
+                                int32_t* out_tokens /* [max_tokens], may be NULL */, int* n_out);
 /* the ids generated by the last flm_decode_greedy / flm_decode_sample / flm_decode_timed* call: out[n] (n <= its n_steps) */
 int  flm_last_tokens(flm_ctx* ctx, int n, int32_t* out);
 int  flm_reset_kv(flm_ctx* ctx);
@@ -255,7 +281,7 @@ int  flm_debug_read(flm_ctx* ctx, int what, int layer, float* out, size_t n);
  *   "attn_split"     0 = one workgroup per head at every context length (default 1: hs / 32 workgroups per head from 128 positions on; n >= 2: always n)
  *   "use_prefill"    0 = prompts token by token (default 1: batched; under tensor parallelism once the peers are mapped with flm_p2p_import)
  *   "score_rows"     n = flm_score_tokens runs its classifier on chunks of at most n rows (default 0: as many rows as the staging holds; < 0: one row at a time through the logits vector, the staging of a context without prefill scores)
- *   "spec_gemm"      1 = flm_verify_greedy / flm_generate_lookup run the verify batch's int8 GEMMs on the skinny kernel for <= 16 rows (default 0: the prompt path's 64 x 64
+ *   "spec_gemm"      1 = flm_verify_greedy / flm_generate_lookup and their sampled forms run the verify batch's int8 GEMMs on the skinny kernel for <= 16 rows (default 0: the prompt path's 64 x 64
  *                    tiles, until both forms have been timed on the device: DESIGN.md section 5e); the same bits; no other entry point looks at it
  *   "use_prefill_mq" 0 = batched attention with one query per workgroup (default 1: eight)
  *   "use_qk_mfma" / "use_pv_mfma"  0 = prefill scores / softmax x V on VALU chains (default 1: v_mfma_f32_16x16x4_f32, the same bits)
@@ -293,8 +319,8 @@ int  flm_set_option(flm_ctx* ctx, const char* key, int value);
  *               (the whole layer in one launch), bit 9 all layers of the token in one launch (k_layers), bit 10 a greedy decode token is ONE launch (embedding row, layers,
  *               classifier, argmax in k_layers<.., TAIL>),
  *   "ao_active" which hand-offs of that launch are consumed in arrival order: bit 0 Wo, bit 1 FFN2 (-1: the launch has not been planned yet),
- *   "sampled_tokens" how many tokens this context sampled on the device (flm_forward_sample / flm_decode_sample / flm_generate at temperature > 0),
- *   "spec_steps" / "spec_accepted" the last flm_generate_lookup call: verify passes run / drafted ids accepted in them,
+ *   "sampled_tokens" how many tokens this context sampled on the device (flm_forward_sample / flm_decode_sample / flm_generate / flm_verify_sample / flm_generate_lookup_sample at temperature > 0),
+ *   "spec_steps" / "spec_accepted" the last flm_generate_lookup / flm_generate_lookup_sample call: verify passes run / drafted ids accepted in them,
  *   "gen_tokens" / "gen_streamed" the last flm_generate call: tokens delivered / how many of them were delivered while hipStreamQuery still said the stream was busy,
  *   "epoch_tail" / "epoch_eng" / "epoch_xchg" the epoch counters the cross-workgroup waits count from (device memory; the 32-bit pattern): the one-launch token's, the
  *               tensor-parallel token's epoch base, k_xchg's logits exchanges (the long-lived-context tests).
@@ -325,6 +351,9 @@ int  flm_op_argmax(const float* logits, int n, int32_t* idx);
 /* Sampler::sample (sampler.cpp:113-137) through k_sample_advance, the kernel of flm_forward_sample / flm_decode_sample: logits[n] are not modified;
  * *rng_state in / out as there.  n >= 2. */
 int  flm_op_sample(const float* logits, int n, float temperature, float topp, uint64_t* rng_state, int32_t* out);
+/* the sampler of flm_verify_sample (k_sample_rows) on caller-supplied logits[rows][ld], n entries per row, 1 <= rows <= 16, ld >= n >= 2: out[i] = row i drawn with the
+ * (i + 1)-th coin of *rng_state, i.e. what `rows` successive flm_op_sample calls on the rows return; *rng_state out: the state after `rows` draws (temperature 0: untouched) */
+int  flm_op_sample_rows(const float* logits, int rows, int ld, int n, float temperature, float topp, uint64_t* rng_state, int32_t* out);
 /* flm_score_tokens' statistics kernel (k_score_rows) on caller-supplied logits[rows][n]: out[rows]; targets[rows] as there (NULL: none).  2 <= n, n within the LDS bound. */
 int  flm_op_score_rows(const float* logits, int rows, int n, const int32_t* targets, flm_score* out);
 /* simd::swiglu(xo,xr,n) (x86_simd.cpp:1766-1770) */

@@ -4,7 +4,14 @@
        t_B alone, median of `reps` calls, for "spec_gemm" 1 (the skinny kernel) and 0 (the 64 x 64 tiles; measured twice, in front of and behind the skinny runs: the spread
        is printed beside it); t_B / t_1 is the break-even number of ids per step
    (c) flm_generate_lookup on a prompt that repeats a block of its own continuation: tokens/s, accepted / steps
-Exits non-zero unless the ids of (a), (b) and (c) agree.  Prints one JSON line.  python tools/spec_bench.py [N] [reps] [layers]"""
+With --temperature T (> 0) and --topp P the same three for the SAMPLED path, state 1234, after the greedy ones and in the same JSON line under "sampled":
+   (a') flm_decode_sample: t_1 sampled, beside the greedy t_1 (the difference is k_sample_advance against the argmax tail)
+   (b') flm_verify_sample fed flm_decode_sample's ids as drafts, B = 5, 8, 16, with the "spec_gemm" form (c) chose; beside it flm_verify_greedy's pass at the same B in the
+        same run (the difference is k_sample_rows over B rows against k_argmax_rows)
+   (c') flm_generate_lookup_sample on the same kind of prompt, at state 1234 and at state 0 (the CLI's default seed: every coin 0): tokens/s, accepted / steps
+Exits non-zero unless the ids of (a), (b) and (c) agree -- and, sampled, unless ids and final states agree with flm_generate.  Prints one JSON line.
+python tools/spec_bench.py [--temperature T] [--topp P] [N] [reps] [layers]"""
+import argparse
 import json
 import os
 import sys
@@ -15,11 +22,17 @@ import numpy as np
 import __graft_entry__ as g; g.load_package()
 from fast_llama_amd import capi, synth, flmfile as ff
 
-N = int(sys.argv[1]) if len(sys.argv) > 1 else 128
-reps = int(sys.argv[2]) if len(sys.argv) > 2 else 9
+ap = argparse.ArgumentParser()
+ap.add_argument("--temperature", "-t", type=float, default=0.0)
+ap.add_argument("--topp", "-p", type=float, default=0.9)
+ap.add_argument("N", nargs="?", type=int, default=128)
+ap.add_argument("reps", nargs="?", type=int, default=9)
+ap.add_argument("layers", nargs="?", type=int, default=None)
+opt = ap.parse_args()
+N, reps = opt.N, opt.reps
 cfg = synth.make_config("7B", ff.QT_INT8)
-if len(sys.argv) > 3:
-    cfg.n_layers = int(sys.argv[3])
+if opt.layers is not None:
+    cfg.n_layers = opt.layers
 ctx = capi.Ctx(capi.desc_from_config(cfg, max_seq_len=1024))
 ctx.upload_all(synth.make_tensors(cfg, seed=7, share_layers=True))
 seed = np.concatenate([[1], np.random.default_rng(1).integers(0, cfg.vocab_size, 15)]).astype(np.int32)
@@ -61,6 +74,53 @@ t0 = time.perf_counter(); got = ctx.generate_lookup(prompt, 0, N, draft_len=7, n
 ok = ok and np.array_equal(got, ref)
 res.update({"lookup_tok_s": round(N / dt_c, 1), "lookup_steps": ctx.query("spec_steps"), "lookup_accepted": ctx.query("spec_accepted"),
             "lookup_gemm": ctx.query("spec_gemm"), "ids_agree": bool(ok), "fallback": ctx.query("fallback")})
+
+# the sampled path
+if opt.temperature > 0:
+    T, P, S0 = opt.temperature, opt.topp, 1234
+    gemm = ctx.query("spec_gemm")
+    sm = {"temperature": T, "topp": P, "gemm": gemm}
+    ctx.reset_kv()
+    sfirst, s1 = ctx.forward_sample(seed, 0, T, P, S0)
+    ctx.decode_sample(sfirst, len(seed), 8, T, P, s1)        # warm
+    t0 = time.perf_counter(); sids, s_end = ctx.decode_sample(sfirst, len(seed), N, T, P, s1); dt = time.perf_counter() - t0
+    sm.update({"decode_tok_s": round(N / dt, 1), "t1_ms": round(dt * 1e3 / N, 4), "t1_minus_greedy_t1_ms": round(dt * 1e3 / N - t1_ms, 4)})
+
+    def spass_ms(k, sampled):
+        global ok
+        ts = []
+        for _ in range(reps + 1):
+            t0 = time.perf_counter()
+            if sampled:
+                got, s = ctx.verify_sample(sfirst, sids[:k], len(seed), T, P, s1)
+            else:
+                got = ctx.verify_greedy(first, ids[:k], len(seed))
+            ts.append((time.perf_counter() - t0) * 1e3)
+            if sampled:
+                want, sw = ctx.decode_sample(sfirst, len(seed), k + 1, T, P, s1)
+                ok = ok and np.array_equal(got, want) and s == sw
+        return float(np.median(ts[1:]))
+    for k in (4, 7, 15):
+        sa = spass_ms(k, True); gr = spass_ms(k, False)
+        sm[f"B{k + 1}"] = {"sample_ms": round(sa, 3), "greedy_ms": round(gr, 3), "sample_minus_greedy_ms": round(sa - gr, 3), "sample_over_t1": round(sa / sm["t1_ms"], 2)}
+    for S in (S0, 0):
+        ctx.reset_kv()
+        sref, s_ref = ctx.generate(seed, 0, 32, T, P, S)
+        sblock = np.concatenate([seed, sref]).astype(np.int32)
+        sprompt = np.concatenate([sblock, sblock]).astype(np.int32)
+        ctx.reset_kv()
+        t0 = time.perf_counter(); want, sw = ctx.generate(sprompt, 0, N, T, P, S); dt_g = time.perf_counter() - t0
+        ctx.reset_kv()
+        ctx.generate_lookup_sample(sprompt, 0, 8, T, P, S, draft_len=7)            # warm
+        ctx.reset_kv()
+        t0 = time.perf_counter(); got, sg = ctx.generate_lookup_sample(sprompt, 0, N, T, P, S, draft_len=7, ngram_max=3); dt_l = time.perf_counter() - t0
+        agree = bool(np.array_equal(got, want) and sg == sw)
+        ok = ok and agree
+        sm[f"state{S}"] = {"generate_tok_s": round(N / dt_g, 1), "lookup_tok_s": round(N / dt_l, 1), "lookup_steps": ctx.query("spec_steps"), "lookup_accepted": ctx.query("spec_accepted"),
+                           "ids_and_state_agree": agree}
+    sm["fallback"] = ctx.query("fallback")
+    res["sampled"] = sm
+    res["ids_agree"] = bool(ok)
 print(json.dumps(res), flush=True)
 ctx.close()
 sys.exit(0 if ok else 1)
