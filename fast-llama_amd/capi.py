@@ -7,6 +7,7 @@ FlmError is raised.
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import os
 
 import numpy as np
@@ -27,6 +28,7 @@ SYMBOLS = (
     "flm_forward_sample", "flm_decode_sample", "flm_op_sample", "flm_generate", "flm_score_tokens", "flm_op_score_rows",
     "flm_verify_greedy", "flm_generate_lookup", "flm_op_matmul_skinny", "flm_op_spec_draft",
     "flm_verify_sample", "flm_generate_lookup_sample", "flm_op_sample_rows",
+    "flm_generate_ex", "flm_forward_sample_ex", "flm_op_shape_logits",
 )
 
 # flm_score (include/flm_gpu.h): one row of flm_score_tokens / flm_op_score_rows
@@ -38,6 +40,43 @@ TOKEN_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int32, C.c_int)
 
 # the experiment dials: the kOptDial rows of csrc/flm_tuning.h, in its order (tests/test_capi_host.py compares)
 TUNING_KEYS = ("wg_per_cu", "inject_wait_failure", "age_epochs", "use_mfma", "tok_nstq", "tok_preq", "back_nst13", "back_nst13_head", "back_nst2", "back_pre13", "back_pre2", "back_ao2", "back_nwo", "attn_kpre")
+
+
+PENALTY_WINDOW_MAX, BIAS_MAX = 1024, 256      # FLM_PENALTY_WINDOW_MAX, FLM_BIAS_MAX
+
+
+class SamplingStruct(C.Structure):
+    """flm_sampling (include/flm_gpu.h)"""
+    _fields_ = [("temperature", C.c_float), ("topp", C.c_float), ("top_k", C.c_int32), ("min_p", C.c_float), ("repeat_penalty", C.c_float),
+                ("frequency_penalty", C.c_float), ("presence_penalty", C.c_float), ("penalty_last_n", C.c_int32), ("n_bias", C.c_int32),
+                ("bias_ids", C.c_void_p), ("bias_values", C.c_void_p)]
+
+
+@dataclasses.dataclass
+class Sampling:
+    """the sampling controls of flm_generate_ex / flm_forward_sample_ex / flm_op_shape_logits; the defaults are the neutral values.  bias: {id: value} or (ids, values)"""
+    temperature: float = 0.0
+    topp: float = 0.9
+    top_k: int = 0
+    min_p: float = 0.0
+    repeat_penalty: float = 1.0
+    frequency_penalty: float = 0.0
+    presence_penalty: float = 0.0
+    penalty_last_n: int = 0
+    bias: object = None
+
+    def bias_arrays(self):
+        if self.bias is None:
+            return np.empty(0, dtype=np.int32), np.empty(0, dtype=np.float32)
+        ids, vals = (list(self.bias.keys()), list(self.bias.values())) if isinstance(self.bias, dict) else self.bias
+        return np.ascontiguousarray(ids, dtype=np.int32), np.ascontiguousarray(vals, dtype=np.float32)
+
+    def struct(self):
+        """-> (flm_sampling, the arrays it points into: keep them alive for the call)"""
+        ids, vals = self.bias_arrays()
+        st = SamplingStruct(self.temperature, self.topp, int(self.top_k), self.min_p, self.repeat_penalty, self.frequency_penalty, self.presence_penalty,
+                            int(self.penalty_last_n), int(ids.size), _p(ids) if ids.size else None, _p(vals) if ids.size else None)
+        return st, (ids, vals)
 
 
 class FlmError(RuntimeError):
@@ -196,6 +235,39 @@ class Ctx:
             raise raised[0]
         _check(rc, self._h)
         return (out[:n_out.value].copy() if want_ids else np.empty(0, dtype=np.int32)), st.value
+
+    def generate_ex(self, prompt, pos, max_tokens, sampling, rng_state=0, stop_token=-1, on_token=None, want_ids=True):
+        """flm_generate_ex: generate() with the sampling controls of a Sampling -> (ids[n_out], the sampler state after the n_out draws)"""
+        t = np.ascontiguousarray(prompt, dtype=np.int32)
+        out = np.empty(max(int(max_tokens), 1), dtype=np.int32) if want_ids else None
+        st = C.c_uint64(int(rng_state)); n_out = C.c_int(0)
+        sp, keep = sampling.struct()
+        raised = []
+
+        def tramp(_user, index, token, last):
+            try:
+                return 1 if on_token(int(index), int(token), bool(last)) else 0
+            except BaseException as e:      # (an exception must not unwind through the C frames: cancel, re-raise behind the call)
+                raised.append(e)
+                return 1
+        cb = TOKEN_CB(tramp) if on_token is not None else C.cast(None, TOKEN_CB)
+        rc = lib().flm_generate_ex(self._h, _p(t), len(t), int(pos), int(max_tokens), C.byref(sp), C.byref(st),
+                                   C.c_int32(int(stop_token)), cb, None, _p(out), C.byref(n_out))
+        del cb, keep
+        if raised:
+            raise raised[0]
+        _check(rc, self._h)
+        return (out[:n_out.value].copy() if want_ids else np.empty(0, dtype=np.int32)), st.value
+
+    def forward_sample_ex(self, tokens, pos, sampling, window=(), rng_state=0):
+        """flm_forward_sample_ex -> (next token, the sampler state after the draw); window: the ids the penalties look at, used as given"""
+        t = np.ascontiguousarray(tokens, dtype=np.int32)
+        w = np.ascontiguousarray(window, dtype=np.int32)
+        nxt = C.c_int32(-1); st = C.c_uint64(int(rng_state))
+        sp, keep = sampling.struct()
+        _check(lib().flm_forward_sample_ex(self._h, _p(t), len(t), int(pos), C.byref(sp), _p(w) if w.size else None, int(w.size), C.byref(st), C.byref(nxt)), self._h)
+        del keep
+        return nxt.value, st.value
 
     def score(self, tokens, pos, targets=None, want_logits=False):
         """flm_score_tokens -> a structured array (SCORE_DTYPE) with one row per position; with want_logits also the [n][vocab] logits.  targets None: the next token of
@@ -410,6 +482,31 @@ def op_sample(logits, temperature, topp, rng_state):
     out = C.c_int32(-1); st = C.c_uint64(int(rng_state))
     _check(lib().flm_op_sample(_p(a), int(a.size), C.c_float(temperature), C.c_float(topp), C.byref(st), C.byref(out)))
     return out.value, st.value
+
+
+def op_shape_logits(logits, sampling, window=()) -> np.ndarray:
+    """k_shape_logits, the shaping stage of flm_generate_ex, on one row of logits -> the shaped row"""
+    a = np.ascontiguousarray(logits, dtype=np.float32)
+    w = np.ascontiguousarray(window, dtype=np.int32)
+    out = np.empty_like(a)
+    sp, keep = sampling.struct()
+    _check(lib().flm_op_shape_logits(_p(a), int(a.size), C.byref(sp), _p(w) if w.size else None, int(w.size), _p(out)))
+    del keep
+    return out
+
+
+def shape_host(logits, sampling, window=()) -> np.ndarray:
+    """the shaping stage's host restatement (host/sampler.cpp shape_logits through lib/libflm_host.so: fh_shape); needs no GPU"""
+    global _host
+    if _host is None:
+        _host = C.CDLL(os.path.join(_HERE, "lib", "libflm_host.so"))
+    a = np.ascontiguousarray(logits, dtype=np.float32)
+    w = np.ascontiguousarray(window, dtype=np.int32)
+    ids, vals = sampling.bias_arrays()
+    out = np.empty_like(a)
+    _host.fh_shape(_p(a), int(a.size), C.c_float(sampling.temperature), int(sampling.top_k), C.c_float(sampling.min_p), C.c_float(sampling.repeat_penalty),
+                   C.c_float(sampling.frequency_penalty), C.c_float(sampling.presence_penalty), int(ids.size), _p(ids), _p(vals), _p(w), int(w.size), _p(out))
+    return out
 
 
 def op_sample_rows(logits, n, temperature, topp, rng_state):

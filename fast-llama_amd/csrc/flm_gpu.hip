@@ -234,7 +234,7 @@ static bool chunks_in_use(const flm_ctx* c) { return c->use_graph && !c->timing 
 // the cached graph of `n` token sequences (n >= 2: greedy tokens, a chunk; n == 1: one token by (classifier, advance)) for G workgroups per head: captured and instantiated on first use --
 // flm_prepare (and the end of the upload) asks for every graph the entry points replay, so that this happens THERE and not inside a forward
 static int token_graph(flm_ctx* c, bool with_cls, int advance, int G, int n, hipGraphExec_t* out) {
-    const int key = (with_cls ? 4 : 0) + advance + 8 * G + 4096 * (n >= 2 ? n : 0);
+    const int key = (with_cls ? 4 : 0) + (advance == kAdvShaped ? 3 + (1 << 27) : advance) + 8 * G + 4096 * (n >= 2 ? n : 0);   // (the shaped form: the sampled form's key + bit 27)
     auto it = c->graphs.find(key);
     if (it == c->graphs.end()) {
         hipGraph_t g = nullptr; hipGraphExec_t ge = nullptr;
@@ -311,6 +311,11 @@ int prepare_all(flm_ctx* c) {
             if ((r = token_graph(c, true, 3, G, 1, &ge))) return r;
             if (chunks_in_use(c)) for (int n = 2; n <= kChunk; n *= 2) if ((r = token_graph(c, true, 3, G, n, &ge))) return r;
         }
+        // ... and the shaped token's (flm_generate_ex: classifier, k_shape_logits, the sampler on the shaped row; its controls live in device memory too); one GPU only
+        if (c->world == 1 && !(c->comm && c->force_tp)) {
+            if ((r = token_graph(c, true, kAdvShaped, G, 1, &ge))) return r;
+            if (chunks_in_use(c)) for (int n = 2; n <= kChunk; n *= 2) if ((r = token_graph(c, true, kAdvShaped, G, n, &ge))) return r;
+        }
     }
     return FLM_OK;
 }
@@ -330,6 +335,7 @@ int alloc_run_bufs(flm_ctx* c) {
     HIPC(c, dev_alloc(c, &c->spec_out_s, sizeof(SpecOutSample), true));
     c->bounce_bytes = (size_t)d.vocab_size * 4; if (c->bounce_bytes < sizeof(ScoreRow) * (size_t)d.max_seq_len) c->bounce_bytes = sizeof(ScoreRow) * (size_t)d.max_seq_len;   // (a row of logits | max_seq_len ids | max_seq_len flm_score: each one trip)
     HIPC(c, hipHostMalloc((void**)&c->bounce, c->bounce_bytes + 64, hipHostMallocDefault));          // (+ a line for the error word that rides along: d2h)
+    HIPC(c, hipHostMalloc((void**)&c->shape_stage, sizeof(ShapeParams), hipHostMallocDefault));   // (the shaper's parameter block on its way to the device: set_shape)
     {   // flm_generate's granule ring (max_seq_len entries of 8 bytes) and, a line behind it, the cancel word: the device stores / loads them at system scope while the host polls / writes
         c->gen_cap = d.max_seq_len;
         const size_t ring_bytes = ((size_t)c->gen_cap * 8 + 63) & ~(size_t)63;
@@ -380,6 +386,55 @@ static int set_sample(flm_ctx* c, float temperature, float topp, unsigned long l
     HIPC(c, hipGetLastError());
     return FLM_OK;
 }
+// the shaper's parameter block for this call: through a page-locked staging copy of its own (allocated at create), moved by a kernel on the context's stream like every
+// other upload -- not through the bounce buffer, which carries the prompt in the same call, so no synchronise is needed.  The stream is idle when an entry point starts
+// (every entry point, and every attempt of a retried call, returns behind a synchronise): the previous call's copy has left the staging block
+static int copy_words(flm_ctx* c, const void* src, void* dst, size_t bytes, bool with_err);
+static int set_shape(flm_ctx* c, const ShapeParams& sp) {
+    static_assert(sizeof(ShapeParams) % 4 == 0, "whole words");
+    if (hipStreamQuery(c->stream) != hipSuccess) { (void)hipGetLastError(); HIPC(c, hipStreamSynchronize(c->stream)); }   // (never taken today; an entry point that one day returns without a synchronise must not race the copy below)
+    memcpy(c->shape_stage, &sp, sizeof sp);
+    return copy_words(c, c->shape_stage, c->shape_p, sizeof sp, false);
+}
+const char* shape_fill(const flm_sampling* sp, int vocab, const int32_t* window, int n_window, bool follow, ShapeParams* out, bool* active) {
+    if (!sp) return "sampling: null struct";
+    if (!(sp->temperature >= 0.0f) || sp->topp != sp->topp) return "sampling: temperature must be >= 0, top-p a number";
+    if (sp->top_k < 0) return "sampling: top_k < 0";
+    if (!(sp->min_p >= 0.0f && sp->min_p < 1.0f)) return "sampling: min_p outside [0, 1)";
+    if (!(sp->repeat_penalty > 0.0f) || isinf(sp->repeat_penalty)) return "sampling: repeat_penalty must be a positive number";
+    if (sp->frequency_penalty != sp->frequency_penalty || sp->presence_penalty != sp->presence_penalty) return "sampling: a penalty is NaN";
+    if (sp->penalty_last_n < 0 || sp->penalty_last_n > FLM_PENALTY_WINDOW_MAX) return "sampling: penalty_last_n outside [0, FLM_PENALTY_WINDOW_MAX]";
+    if (n_window < 0 || n_window > FLM_PENALTY_WINDOW_MAX || (n_window > 0 && !window)) return "sampling: n_window outside [0, FLM_PENALTY_WINDOW_MAX]";
+    if (sp->n_bias < 0 || sp->n_bias > FLM_BIAS_MAX || (sp->n_bias > 0 && (!sp->bias_ids || !sp->bias_values))) return "sampling: n_bias outside [0, FLM_BIAS_MAX]";
+    for (int i = 0; i < sp->n_bias; ++i) {
+        const int id = sp->bias_ids[i]; const float b = sp->bias_values[i];
+        if (id < 0 || id >= vocab) return "sampling: bias id outside [0, vocab)";
+        if (b != b || b == INFINITY) return "sampling: a bias is NaN or +inf";
+        for (int k = 0; k < i; ++k) if (sp->bias_ids[k] == id) return "sampling: a bias id is listed twice";
+    }
+    for (int i = 0; i < n_window; ++i) if (window[i] < 0 || window[i] >= vocab) return "sampling: window id outside [0, vocab)";
+    static_assert(kShapeWindowMax == FLM_PENALTY_WINDOW_MAX && kShapeBiasMax == FLM_BIAS_MAX, "flm_shape.h mirrors the header's limits");
+    ShapeParams& o = *out;
+    memset(&o, 0, sizeof o);
+    const bool pen = sp->repeat_penalty != 1.0f || sp->frequency_penalty != 0.0f || sp->presence_penalty != 0.0f;
+    o.temperature = sp->temperature;
+    o.minp_on = sp->min_p > 0.0f && sp->temperature != 0.0f ? 1 : 0;
+    if (o.minp_on) { volatile float mp = sp->min_p; o.lt = logf(mp); }        // (glibc's logf, at run time: the one logarithm of the definition)
+    o.top_k = sp->top_k > 0 && sp->top_k < vocab ? sp->top_k : 0;
+    o.repeat = sp->repeat_penalty; o.freq = sp->frequency_penalty; o.pres = sp->presence_penalty;
+    o.follow = follow ? 1 : 0;
+    o.last_n = follow && pen ? sp->penalty_last_n : 0;
+    // follow: the tail of the prompt that can still be inside the window at the first token
+    int nh = pen ? n_window : 0;
+    if (follow && nh > o.last_n) { window += nh - o.last_n; nh = o.last_n; }
+    o.n_head = nh;
+    for (int i = 0; i < nh; ++i) o.head[i] = window[i];
+    o.n_bias = sp->n_bias;
+    for (int i = 0; i < sp->n_bias; ++i) { o.bias_ids[i] = sp->bias_ids[i]; o.bias_vals[i] = sp->bias_values[i]; }
+    const bool pen_on = pen && (follow ? o.last_n > 0 : nh > 0);
+    *active = o.n_bias > 0 || pen_on || o.top_k > 0 || o.minp_on;
+    return nullptr;
+}
 
 int check_ready(flm_ctx* c, int n, int pos) {
     if (!c) return FLM_ERR_INVALID;
@@ -404,7 +459,7 @@ __global__ void k_copy_words(const unsigned* __restrict__ src, unsigned* __restr
     for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) dst[i] = src[i];
     if (word_src && blockIdx.x == 0 && threadIdx.x == 0) *word_dst = *word_src;
 }
-static int copy_words(flm_ctx* c, const void* src, void* dst, size_t bytes, bool with_err = false) {
+static int copy_words(flm_ctx* c, const void* src, void* dst, size_t bytes, bool with_err) {
     const unsigned n = (unsigned)(bytes / 4);                                       // (ids, logits: whole words)
     const unsigned blocks = n < 256 * 64 ? (n + 255) / 256 : 64;
     hipLaunchKernelGGL(k_copy_words, dim3(blocks ? blocks : 1), dim3(256), 0, c->stream, (const unsigned*)src, (unsigned*)dst, n,
@@ -428,7 +483,7 @@ int h2d(flm_ctx* c, void* dst_dev, const void* src, size_t bytes) {
         const size_t nb = bytes - o < c->bounce_bytes ? bytes - o : c->bounce_bytes;
         if (o) HIPC(c, hipStreamSynchronize(c->stream));                          // (the previous piece has left the buffer)
         memcpy(c->bounce, (const char*)src + o, nb);
-        int r = copy_words(c, c->bounce, (char*)dst_dev + o, nb); if (r) return r;
+        int r = copy_words(c, c->bounce, (char*)dst_dev + o, nb, false); if (r) return r;
     }
     return FLM_OK;
 }
@@ -607,6 +662,8 @@ int flm_ctx_create(const flm_model_desc* desc, int device_id, int rank, int worl
     HIPB(dev_alloc(c, &c->att_sc, (size_t)c->heads_local * d.max_seq_len * 8, true));   // (8 bytes per score: the parts of a split head exchange them as {score, tag} granules inside k_layers' granule launches, as floats elsewhere)
     HIPB(dev_alloc(c, &c->state, sizeof(DecodeState), true));
     HIPB(dev_alloc(c, &c->sparams, sizeof(SampleParams), true));   // the device sampler's parameter block and sort buffers
+    HIPB(dev_alloc(c, &c->shape_p, sizeof(ShapeParams), true));    // the logit shaper's parameter block and the shaped row (flm_shape.h)
+    HIPB(dev_alloc(c, &c->shape_row, (size_t)d.vocab_size * sizeof(float), true));
     if (sample_supported(c)) HIPB(dev_alloc(c, &c->sort_buf, (size_t)kSpecRows * 2 * d.vocab_size * sizeof(unsigned long long)));   // ([16][2][vocab]: a slice per row of a sampled verify batch)
     std::vector<float> cs, sn; build_rope_table(hs, d.max_seq_len, cs, sn);
     HIPB(dev_alloc(c, &c->rope_cos, cs.size() * 4)); HIPB(dev_alloc(c, &c->rope_sin, sn.size() * 4));
@@ -646,6 +703,7 @@ void flm_ctx_destroy(flm_ctx* c) {
     for (void* p : {c->emb, (void*)c->emb_s, (void*)c->trace}) if (p) hipFree(p);          // (re-allocated during the context's life: flm_upload_tensor, option "trace")
     if (c->bounce) hipHostFree(c->bounce);
     if (c->gen_host) hipHostFree(c->gen_host);
+    if (c->shape_stage) hipHostFree(c->shape_stage);
     if (c->comm) ncclCommDestroy(c->comm);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
@@ -899,6 +957,7 @@ int flm_query(flm_ctx* c, const char* key, int* value) {
         {"fallback", c->fell_back},
         {"fallback_active", c->fb_active ? 1 : 0},
         {"sampled_tokens", (int)c->sampled},
+        {"shaped_tokens", (int)c->shaped},
         {"gen_tokens", c->gen_tokens},
         {"gen_streamed", c->gen_streamed},
         {"spec_steps", c->spec_steps},
@@ -1026,6 +1085,13 @@ static void warm_up(flm_ctx* c) {
         ok = set_sample(c, 1.0f, 0.9f, 0ull) == FLM_OK && set_state(c, n, 0, 0) == FLM_OK && run_tokens(c, n, kEach, 3) == FLM_OK && hipStreamSynchronize(c->stream) == hipSuccess;
     if (ok && sample_supported(c) && c->d.max_seq_len > kSplitFrom + 8 + kEach && attn_parts(c, kSplitFrom + 8) != attn_parts(c, 1))
         ok = set_state(c, kSplitFrom + 8, 0, 0) == FLM_OK && run_tokens(c, kSplitFrom + 8, kEach, 3) == FLM_OK && hipStreamSynchronize(c->stream) == hipSuccess;
+    // ... and the shaped token's graphs, every control neutral (the shaper copies the row)
+    if (ok && c->d.vocab_size >= 2 && c->d.max_seq_len > n + kEach) {
+        ShapeParams np{}; np.repeat = 1.0f; np.follow = 1;
+        ok = set_shape(c, np) == FLM_OK && set_sample(c, sample_supported(c) ? 1.0f : 0.0f, 0.9f, 0ull) == FLM_OK && set_state(c, n, 0, 0) == FLM_OK && run_tokens(c, n, kEach, kAdvShaped) == FLM_OK && hipStreamSynchronize(c->stream) == hipSuccess;
+        if (ok && c->d.max_seq_len > kSplitFrom + 8 + kEach && attn_parts(c, kSplitFrom + 8) != attn_parts(c, 1))
+            ok = set_state(c, kSplitFrom + 8, 0, 0) == FLM_OK && run_tokens(c, kSplitFrom + 8, kEach, kAdvShaped) == FLM_OK && hipStreamSynchronize(c->stream) == hipSuccess;
+    }
     if (ok) (void)xwg_check(c);                                                // (a wait that gave up here puts the context on the per-phase kernels like any other)
     (void)clear_kv(c);                                                          // the cache rows the dummy tokens wrote: cleared again
     (void)hipStreamSynchronize(c->stream);
@@ -1240,8 +1306,9 @@ inline void cpu_relax() {
 #endif
 }
 }
-int flm_generate(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, int max_tokens, float temperature, float topp, uint64_t* rng_state,
-                 int32_t stop_token, flm_token_cb cb, void* user, int32_t* out_tokens, int* n_out) {
+// shape: null = flm_generate; else flm_generate_ex with a control set: the block goes to the device first and every token takes the shaped form
+static int generate_impl(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, int max_tokens, float temperature, float topp, uint64_t* rng_state,
+                         int32_t stop_token, flm_token_cb cb, void* user, int32_t* out_tokens, int* n_out, const ShapeParams* shape) {
     if (!c || !prompt || !n_out) return FLM_ERR_INVALID;
     // (in front of everything else: a tensor-parallel rank must not touch a peer -- halting and cancelling across ranks is not built)
     if (c->world > 1 || (c->comm && c->force_tp)) return fail(c, FLM_ERR_UNSUPPORTED, "generate: one GPU only (tensor-parallel callers keep the flm_decode_* loop)");
@@ -1250,7 +1317,7 @@ int flm_generate(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, int m
     if (pos + n_prompt + max_tokens - 1 > c->d.max_seq_len || max_tokens > c->out_cap || max_tokens > c->gen_cap) return fail(c, FLM_ERR_INVALID, "generate: pos + n_prompt + max_tokens - 1 exceeds max_seq_len");
     const bool sampled = temperature != 0.0f;
     if (sampled) { r = sample_args_ok(c, temperature, topp, rng_state); if (r) return r; }
-    const int advance = sampled ? 3 : 1;
+    const int advance = shape ? kAdvShaped : sampled ? 3 : 1;
     volatile unsigned long long* ring = c->gen_host;
     int* cancel_word = (int*)((char*)c->gen_host + (((size_t)c->gen_cap * 8 + 63) & ~(size_t)63));
     int32_t* ids = c->gen_ids.data();
@@ -1274,7 +1341,8 @@ int flm_generate(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, int m
         {
             const GenWords words(c, stop_token < 0 ? -1 : stop_token, tag, max_tokens);
             int r = FLM_OK;
-            if (sampled) r = set_sample(c, temperature, topp, *rng_state);
+            if (shape) r = set_shape(c, *shape);
+            if (!r && (sampled || shape)) r = set_sample(c, temperature, topp, sampled ? *rng_state : 0ull);
             if (!r) r = feed(c, prompt, n_prompt, pos, advance);              // token 0: drawn from the prompt's last logits
             if (!r && max_tokens > 1) r = run_tokens(c, pos + n_prompt, max_tokens - 1, advance);
             if (r) { (void)hipStreamSynchronize(c->stream); return r; }
@@ -1312,9 +1380,49 @@ int flm_generate(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, int m
         if (out_tokens) memcpy(out_tokens, ids, sizeof(int32_t) * (size_t)total);
         *n_out = total;
         if (sampled) { *rng_state = s; c->sampled += total; }
+        if (shape) c->shaped += total;
         c->gen_tokens = total; c->gen_streamed = streamed;
     });
     return r;
+}
+int flm_generate(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, int max_tokens, float temperature, float topp, uint64_t* rng_state,
+                 int32_t stop_token, flm_token_cb cb, void* user, int32_t* out_tokens, int* n_out) {
+    return generate_impl(c, prompt, n_prompt, pos, max_tokens, temperature, topp, rng_state, stop_token, cb, user, out_tokens, n_out, nullptr);
+}
+// flm_generate with the sampling controls (include/flm_gpu.h; the stage: flm_shape.h).  Every control neutral: flm_generate itself.  Otherwise the same call with the shaped
+// token form: the controls, the bias pairs and the prompt's last penalty_last_n ids go to the device block first; the kernel assembles each token's window from that tail and
+// the ids drawn so far (out_tokens_dev at the state's step), so a retried attempt rebuilds the same windows from the same ids.
+int flm_generate_ex(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, int max_tokens, const flm_sampling* sampling, uint64_t* rng_state,
+                    int32_t stop_token, flm_token_cb cb, void* user, int32_t* out_tokens, int* n_out) {
+    if (!c || !prompt || !n_out) return FLM_ERR_INVALID;
+    if (n_prompt < 1 || n_prompt > c->d.max_seq_len) return fail(c, FLM_ERR_INVALID, "tokens/pos outside [0, max_seq_len]");
+    for (int i = 0; i < n_prompt; ++i) if (prompt[i] < 0 || prompt[i] >= c->d.vocab_size) return fail(c, FLM_ERR_INVALID, "token id out of range");
+    ShapeParams sp; bool active = false;
+    const int tail = n_prompt < FLM_PENALTY_WINDOW_MAX ? n_prompt : FLM_PENALTY_WINDOW_MAX;
+    if (const char* why = shape_fill(sampling, c->d.vocab_size, prompt + (n_prompt - tail), tail, true, &sp, &active)) return fail(c, FLM_ERR_INVALID, why);
+    if (sampling->temperature != 0.0f && !rng_state) return fail(c, FLM_ERR_INVALID, "sample: rng_state must be given at temperature != 0");
+    return generate_impl(c, prompt, n_prompt, pos, max_tokens, sampling->temperature, sampling->topp, rng_state, stop_token, cb, user, out_tokens, n_out, active ? &sp : nullptr);
+}
+// flm_forward_sample with the controls and the caller's window (used as given).  Every control neutral: flm_forward_sample / flm_forward_argmax.
+int flm_forward_sample_ex(flm_ctx* c, const int32_t* tokens, int n, int pos, const flm_sampling* sampling, const int32_t* window, int n_window, uint64_t* rng_state, int32_t* next_token) {
+    if (!c || !tokens || !next_token) return FLM_ERR_INVALID;
+    ShapeParams sp; bool active = false;
+    if (const char* why = shape_fill(sampling, c->d.vocab_size, window, n_window, false, &sp, &active)) return fail(c, FLM_ERR_INVALID, why);
+    const float temperature = sampling->temperature, topp = sampling->topp;
+    const bool sampled = temperature != 0.0f;
+    if (sampled && !rng_state) return fail(c, FLM_ERR_INVALID, "sample: rng_state must be given at temperature != 0");
+    if (!active) return sampled ? flm_forward_sample(c, tokens, n, pos, temperature, topp, rng_state, next_token) : flm_forward_argmax(c, tokens, n, pos, next_token);
+    if (c->world > 1 || (c->comm && c->force_tp)) return fail(c, FLM_ERR_UNSUPPORTED, "shaped token: one GPU only");
+    int r = check_ready(c, n, pos); if (r) return r;
+    if (sampled) { r = sample_args_ok(c, temperature, topp, rng_state); if (r) return r; }
+    unsigned long long s = 0;
+    return with_retry(c, n, [&] {
+        int r = set_shape(c, sp); if (r) return r;
+        r = set_sample(c, temperature, topp, sampled ? *rng_state : 0ull); if (r) return r;
+        r = feed(c, tokens, n, pos, kAdvShaped); if (r) return r;
+        if (sampled) { r = d2h(c, &s, &c->sparams->rng, sizeof s); if (r) return r; }
+        return d2h(c, next_token, c->out_tokens_dev, 4);
+    }, [&] { if (sampled) { *rng_state = s; c->sampled += 1; } c->shaped += 1; });
 }
 
 // Score a sequence: every position's logits in one batched pass, reduced on the device to a flm_score per row (flm_score.h).  The call is flm_forward's work plus the rows

@@ -146,6 +146,10 @@ struct flm_ctx {
     // sort's ping-pong buffers [16][2][vocab] (one [2][vocab] slice per row of a sampled verify batch; the token path sorts in slice 0; null where the vocabulary is beyond
     // the sampler: sample_supported), and how many tokens this context sampled on the device ("sampled_tokens")
     flm::SampleParams* sparams = nullptr; unsigned long long* sort_buf = nullptr; long long sampled = 0;
+    // the logit shaper (flm_shape.h): its per-call parameter block (controls, bias pairs, the prompt's tail for the penalty window: written at the start of each flm_generate_ex /
+    // flm_forward_sample_ex), the shaped row [vocab] the sampler reads in the shaped token form, and how many tokens this context drew through that form ("shaped_tokens")
+    flm::ShapeParams* shape_p = nullptr; float* shape_row = nullptr; long long shaped = 0;
+    flm::ShapeParams* shape_stage = nullptr;           // ... the block's own page-locked staging copy (the bounce buffer carries the prompt in the same call)
     // flm_generate (flm_gpu.hip): the granule ring [max_seq_len] and the cancel word -- page-locked, mapped, host-coherent memory allocated at create (gen_host; the device's view of it:
     // gen_ring_dev / gen_cancel_dev) --, what set_state writes into the decode state's generate words (gen_stop .. gen_max: -1 / 0 / 0 outside a flm_generate call), the
     // per-attempt sequence number the granules are tagged with, a pageable staging buffer for the ids, and the last call's figures ("gen_tokens" / "gen_streamed")
@@ -162,7 +166,7 @@ struct flm_ctx {
     int spec_gemm = 0;                                 // option "spec_gemm": 1 = the verify pass's int8 GEMMs through k_gemm_q8_skinny (B <= 16), 0 (default until both forms have been timed: DESIGN.md section 5e) = the 64 x 64 tiles; the new entry points only
     int spec_steps = 0, spec_accepted = 0;
     int score_rows = 0;                                // option "score_rows": rows per classifier chunk of flm_score_tokens (0: as many as the staging holds; < 0: one row at a time through c->logits)
-    std::map<int, hipGraphExec_t> graphs;             // key = with_cls*4 + advance (3: sampled)
+    std::map<int, hipGraphExec_t> graphs;             // key = with_cls*4 + advance (3: sampled; the shaped form: 3 + bit 27)
     std::vector<TimedLaunch>* timing = nullptr;
     std::vector<void*> owned;                          // every device allocation that lives as long as the context (flm_gpu.hip dev_alloc); flm_ctx_destroy frees these
     std::string err;
@@ -260,7 +264,11 @@ int launch_layers(flm_ctx* c, hipStream_t st, int l0, int l1, int G, bool tail =
 // one activation exchange between the tensor-parallel ranks (flm_token.hip)
 enum XKind { XK_ATT = 0, XK_X1 = 1, XK_HD = 2, XK_LOGITS = 3 };
 int exchange(flm_ctx* c, hipStream_t st, int kind, float* full, float* mine, int count);
+constexpr int kAdvShaped = 4;                         // enqueue_token's advance: classifier, k_shape_logits, then the sampler (the argmax where the vocabulary is beyond the sampler) on the shaped row
 int enqueue_token(flm_ctx* c, hipStream_t st, bool with_cls, int advance, int G);
+// flm_sampling -> the shaper's parameter block (flm_gpu.hip): validates everything include/flm_gpu.h lists (null on success, else what is wrong); window[n_window] becomes the
+// block's head; *active: some control is not neutral.  follow: flm_generate_ex's sliding window (penalty_last_n), else the window as given
+const char* shape_fill(const flm_sampling* sp, int vocab, const int32_t* window, int n_window, bool follow, flm::ShapeParams* out, bool* active);
 int run_token(flm_ctx* c, bool with_cls, int advance, int T);
 // the device sampler's LDS fits one workgroup (vocab up to ~36 K); beyond it the sampled entry points refuse (FLM_ERR_UNSUPPORTED) and a caller samples on the host
 inline bool sample_supported(const flm_ctx* c) { return c->d.vocab_size >= 2 && sample_lds_bytes(c->d.vocab_size) <= kLdsMax; }

@@ -61,5 +61,6 @@
 #include "flm_prefill.h"
 #include "flm_misc.h"
 #include "flm_sample.h"
+#include "flm_shape.h"
 #include "flm_score.h"
 #include "flm_spec.h"

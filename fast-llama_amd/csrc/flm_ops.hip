@@ -206,6 +206,23 @@ int flm_op_sample_rows(const float* logits, int rows, int ld, int n, float tempe
     return FLM_OK;
 }
 
+/* k_shape_logits -- the shaping stage of the shaped token form (flm_shape.h) -- on caller-supplied logits and window */
+int flm_op_shape_logits(const float* logits, int n, const flm_sampling* sampling, const int32_t* window, int n_window, float* out) {
+    if (!logits || !out || n < 2) return FLM_ERR_INVALID;
+    ShapeParams sp; bool active = false;
+    if (const char* why = shape_fill(sampling, n, window, n_window, false, &sp, &active)) { g_last_error = why; return FLM_ERR_INVALID; }
+    DevBuf dl, dout, dp;
+    if (dl.alloc((size_t)n * 4) || dout.alloc((size_t)n * 4) || dp.alloc(sizeof sp)) return FLM_ERR_OOM;
+    OPC(hipMemcpy(dl.p, logits, (size_t)n * 4, hipMemcpyHostToDevice));
+    OPC(hipMemcpy(dp.p, &sp, sizeof sp, hipMemcpyHostToDevice));
+    ShapeArgs a{};
+    a.logits = dl.as<float>(); a.out = dout.as<float>(); a.n = n; a.p = dp.as<ShapeParams>();
+    hipLaunchKernelGGL(k_shape_logits, dim3(1), dim3(kSampleBlock), 0, 0, a);
+    OPC(hipGetLastError()); OPC(hipDeviceSynchronize());
+    OPC(hipMemcpy(out, dout.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return FLM_OK;
+}
+
 /* k_score_rows -- the statistics kernel of flm_score_tokens -- on caller-supplied rows of logits */
 int flm_op_score_rows(const float* logits, int rows, int n, const int32_t* targets, flm_score* out) {
     if (!logits || !out || rows < 1 || n < 2) return FLM_ERR_INVALID;

@@ -1,0 +1,180 @@
+// flm_shape.h -- the logit-shaping stage of the "shaped" token form: classifier -> k_shape_logits -> k_sample_advance.  One 1024-thread workgroup turns the raw logits row L
+// into the shaped row S (a row of its own, vocab floats, allocated at flm_ctx_create) that the UNCHANGED sampler (flm_sample.h sample_draw) then reads.  No reference
+// counterpart: the reference samples with temperature and top-p only.  The definition (restated sequentially in host/sampler.cpp shape_logits, which this
+// kernel equals bit for bit), all arithmetic fp32 round-to-nearest without contraction:
+//   1 bias       S = L; S[id] += b for each of n_bias distinct ids (b finite or -inf)
+//   2 penalties  for every DISTINCT id t of the window W[0 .. w), c = its occurrences: x = S[t]; repeat_penalty != 1: x = x > 0 ? x / rp : x * rp; frequency or presence
+//                != 0: x = x - ((float)c * fp + pp); S[t] = x.  Window entry j belongs to thread j; the thread of an id's FIRST occurrence counts and writes: no order dependence
+//   3 top-k      0 < k < n: keep the k entries first in (larger value, then lower index), -0.0 == +0.0; the rest -> -inf.  A radix select over an order-preserving 32-bit key
+//                (-0.0 canonicalised): four 8-bit passes, most significant digit first, each an integer LDS histogram of the entries that match the prefix so far; they leave the
+//                threshold key and `need`, how many threshold-equal entries to admit; those are the `need` lowest indices, found by an index-ordered count (ballot + per-wave
+//                bases, as the radix sort of flm_sample.h ranks its elements).  Integer atomics only; nothing depends on the order in which waves run
+//   4 min-p      min_p > 0 and temperature != 0: y = S[i] / temperature over the entries that are not -inf, mx = max y, S[i] = -inf where y - mx < lt; lt = logf(min_p) comes
+//                from the HOST (glibc) as a parameter: no logarithm is evaluated here
+// A stage whose control is neutral writes nothing, so with every control neutral S is L bit for bit.  The rows stay in global memory (L2-resident: a few passes over 4 * n
+// bytes), so there is no vocabulary bound; LDS holds the window (<= 1024 ids), four 256-bin histograms and a few scan words.
+// The window at generated step s (ShapeParams::follow): the last min(last_n, n_head + s) ids of head[0 .. n_head) -- the tail of the call's prompt, uploaded at the start of
+// the call -- followed by out_tokens[0 .. s), the ids this call has drawn so far (s = DecodeState::step); follow == 0: head[0 .. n_head) as given (flm_forward_sample_ex).
+// Part of flm_kernels.h; include that header.
+#pragma once
+#include "flm_math.h"
+#include "flm_sample.h"
+#pragma clang fp contract(off)
+
+namespace flm {
+
+constexpr int kShapeWindowMax = 1024;      // == FLM_PENALTY_WINDOW_MAX
+constexpr int kShapeBiasMax = 256;         // == FLM_BIAS_MAX
+// the per-call parameter block in device memory (written at the start of each call; the shaped token graphs read it)
+struct ShapeParams {
+    float temperature;                     // min-p's divisor (the sampler's own copy lives in SampleParams)
+    float lt; int minp_on;                 // logf(min_p) from the host; min_p > 0
+    int top_k;
+    float repeat; float freq; float pres;
+    int last_n;                            // follow: penalty_last_n
+    int n_head; int follow;
+    int n_bias;
+    int pad_;
+    int bias_ids[kShapeBiasMax]; float bias_vals[kShapeBiasMax];
+    int head[kShapeWindowMax];
+};
+struct ShapeArgs {
+    const float* logits; float* out; int n;
+    const ShapeParams* p;
+    const DecodeState* st;                 // the latch and, under follow, the step; null: flm_op_shape_logits
+    const int* out_tokens; int out_cap;
+};
+
+// larger float <-> larger key; -0.0 and +0.0 share a key
+__device__ __forceinline__ unsigned shape_key(float x) {
+    unsigned u = __float_as_uint(x);
+    if (u == 0x80000000u) u = 0u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+inline __global__ void __launch_bounds__(kSampleBlock) k_shape_logits(const ShapeArgs a) {
+    __shared__ int win[kShapeWindowMax];
+    __shared__ int hist[4 * 256];
+    __shared__ int misc[64];               // [0..15] per-wave words, [16] digit, [17] rem, [18] equal-count, [20..35] per-wave floats
+    if (a.st != nullptr && halted(&a.st->halt)) return;
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6, n = a.n;
+    const ShapeParams* p = a.p;
+    const float* L = a.logits; float* S = a.out;
+    // 1: the copy, then the biases (distinct ids: one writer per entry)
+    for (int i = t; i < n; i += kSampleBlock) S[i] = L[i];
+    __syncthreads();
+    const int nb = min(p->n_bias, kShapeBiasMax);
+    if (t < nb) { const int id = p->bias_ids[t]; if ((unsigned)id < (unsigned)n) S[id] = __fadd_rn(S[id], p->bias_vals[t]); }
+    // 2: the window into LDS, then one thread per entry
+    int w = min(max(p->n_head, 0), kShapeWindowMax);
+    int skip = 0, nh = w;
+    if (p->follow) {
+        const int s = a.st ? min(max(a.st->step, 0), a.out_cap) : 0;
+        const int total = nh + s;
+        w = min(min(max(p->last_n, 0), kShapeWindowMax), total);
+        skip = total - w;
+    }
+    const float rp = p->repeat, fp = p->freq, pp = p->pres;
+    const bool rep_on = rp != 1.0f, fpp_on = fp != 0.0f || pp != 0.0f;
+    if (w > 0 && (rep_on || fpp_on)) {
+        if (t < w) { const int g = skip + t; win[t] = g < nh ? p->head[g] : a.out_tokens[g - nh]; }
+        __syncthreads();
+        if (t < w) {
+            const int id = win[t];
+            int c = 0; bool first = true;
+            for (int k = 0; k < w; ++k) { const bool same = win[k] == id; c += same ? 1 : 0; first = first && !(same && k < t); }
+            if (first && (unsigned)id < (unsigned)n) {
+                float x = S[id];
+                if (rep_on) x = x > 0.0f ? __fdiv_rn(x, rp) : __fmul_rn(x, rp);
+                if (fpp_on) x = __fsub_rn(x, __fadd_rn(__fmul_rn((float)c, fp), pp));
+                S[id] = x;
+            }
+        }
+    }
+    __syncthreads();
+    // 3: top-k
+    const int K = p->top_k;
+    if (K > 0 && K < n) {
+        for (int k = t; k < 4 * 256; k += kSampleBlock) hist[k] = 0;
+        if (t == 0) misc[17] = K;
+        __syncthreads();
+        unsigned prefix = 0u;              // the digits chosen so far, in the key's top bits
+#pragma unroll 1
+        for (int d = 0; d < 4; ++d) {
+            const int shift = 24 - 8 * d;
+            int* h = hist + d * 256;
+#pragma unroll 1
+            for (int b0 = 0; b0 < n; b0 += kSampleBlock) {
+                const int i = b0 + t;
+                bool valid = i < n;
+                unsigned key = 0u;
+                if (valid) { key = shape_key(S[i]); valid = d == 0 || (key >> (shift + 8)) == (prefix >> (shift + 8)); }
+                const unsigned dig = (key >> shift) & 255u;
+                // the lanes of this wave with the same digit add once, through their lowest lane
+                unsigned long long m = __ballot(valid);
+#pragma unroll
+                for (int bb = 0; bb < 8; ++bb) { const unsigned long long bm = __ballot((dig >> bb) & 1u); m &= ((dig >> bb) & 1u) ? bm : ~bm; }
+                if (valid && (m & ((1ull << lane) - 1ull)) == 0ull) atomicAdd(&h[dig], __popcll(m));
+            }
+            __syncthreads();
+            if (wv == 0) {
+                // the digit at which the count from the top reaches rem: lane l holds bins 4l .. 4l + 3
+                const int rem = misc[17];
+                const int a0 = h[4 * lane], a1 = h[4 * lane + 1], a2 = h[4 * lane + 2], a3 = h[4 * lane + 3];
+                const int s = a0 + a1 + a2 + a3;
+                int suf = s;
+                for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_down(suf, o, kWave); if (lane + o < 64) suf += u; }
+                int above = suf - s;       // entries in the bins of higher lanes
+                const int bins[4] = {a3, a2, a1, a0};
+                int fd = -1, frem = 0, feq = 0;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    if (fd < 0 && above < rem && above + bins[q] >= rem) { fd = 4 * lane + 3 - q; frem = rem - above; feq = bins[q]; }
+                    above += bins[q];
+                }
+                if (fd >= 0) { misc[16] = fd; misc[17] = frem; misc[18] = feq; }
+            }
+            __syncthreads();
+            prefix |= (unsigned)misc[16] << shift;
+        }
+        const unsigned T = prefix;
+        const int need = misc[17], eqc = misc[18];
+        if (need >= eqc) {
+            // every threshold-equal entry is admitted (no tie at the cut): one pass
+            for (int i = t; i < n; i += kSampleBlock) if (shape_key(S[i]) < T) S[i] = -INFINITY;
+        } else {
+            int base = 0;                  // threshold-equal entries in front of this block of 1024 indices
+#pragma unroll 1
+            for (int b0 = 0; b0 < n; b0 += kSampleBlock) {
+                const int i = b0 + t;
+                const unsigned key = i < n ? shape_key(S[i]) : 0u;
+                const bool eq = i < n && key == T;
+                const unsigned long long m = __ballot(eq);
+                if (lane == 0) misc[wv] = __popcll(m);
+                __syncthreads();
+                int before = base, all = 0;
+                for (int k = 0; k < kSampleWaves; ++k) { const int c = misc[k]; before += k < wv ? c : 0; all += c; }
+                const int rank = before + __popcll(m & ((1ull << lane) - 1ull));
+                if (i < n && (key < T || (eq && rank >= need))) S[i] = -INFINITY;
+                base += all;
+                __syncthreads();
+            }
+        }
+        __syncthreads();
+    }
+    // 4: min-p
+    const float temp = p->temperature;
+    if (p->minp_on && temp != 0.0f) {
+        float mx = -INFINITY;
+        for (int i = t; i < n; i += kSampleBlock) { const float x = S[i]; if (x != -INFINITY) mx = fmaxf(mx, __fdiv_rn(x, temp)); }
+        mx = wave_max(mx);
+        if (lane == 0) misc[20 + wv] = __float_as_int(mx);
+        __syncthreads();
+        mx = __int_as_float(misc[20]);
+        for (int k = 1; k < kSampleWaves; ++k) mx = fmaxf(mx, __int_as_float(misc[20 + k]));
+        const float lt = p->lt;
+        for (int i = t; i < n; i += kSampleBlock) { const float x = S[i]; if (x != -INFINITY && __fsub_rn(__fdiv_rn(x, temp), mx) < lt) S[i] = -INFINITY; }
+    }
+}
+
+} // namespace flm

@@ -38,7 +38,7 @@ GemvPlan gemv_plan(int n, int esz, int rows, bool two, bool pairs, bool norm, in
 // One token: ParallelTransformer::forward at bs == 1 (transformer.cpp:105-161).
 // Position and token are read from c->state on the device.
 //   with_cls  : run the final norm + classifier (+ argmax)
-//   advance   : 1 = greedy (tok <- argmax, pos++), 0 = leave state (caller copies logits), 2 = prompt feed, 3 = sampled (tok <- k_sample_advance, pos++)
+//   advance   : 1 = greedy (tok <- argmax, pos++), 0 = leave state (caller copies logits), 2 = prompt feed, 3 = sampled (tok <- k_sample_advance, pos++), 4 = shaped (k_shape_logits in front of the sampler, which reads the shaped row)
 // ---------------------------------------------------------------------------------------------
 // argument blocks of the five GEMVs and the attention of layer l (shared by the per-phase launches and k_token)
 GemvArgs args_qkv(flm_ctx* c, int l) {
@@ -372,7 +372,22 @@ layers_done:
             r = launch_gemv<PRO_RMSNORM_QUANT, EPI_STORE>(c, st, qt, folded(traced(args_cls(c), KC_CLS, 0), L - 1, 3), wgs, coh); if (r) return r;
         }
         if (tp) { r = exchange(c, st, XK_LOGITS, c->logits, c->logits + (size_t)c->rank * c->vocab_slot, c->vocab_slot); if (r) return r; }
-        if (advance == 3) {   // a sampled token: every rank samples the same all-gathered logits with the same state and draws the same token
+        if (advance == kAdvShaped) {   // a shaped token: the shaper writes the shaped row, the sampler (unchanged) draws from it
+            if (tp) return fail(c, FLM_ERR_UNSUPPORTED, "shaped token: one GPU only");
+            ShapeArgs ha{};
+            ha.logits = c->logits; ha.out = c->shape_row; ha.n = d.vocab_size; ha.p = c->shape_p; ha.st = c->state; ha.out_tokens = c->out_tokens_dev; ha.out_cap = c->out_cap;
+            hipLaunchKernelGGL(k_shape_logits, dim3(1), dim3(kSampleBlock), 0, st, ha);
+            HIPC(c, hipGetLastError());
+            Tick t(c, st, KC_ARGMAX);
+            if (sample_supported(c)) {
+                SampleArgs sa{};
+                sa.logits = c->shape_row; sa.n = d.vocab_size; sa.sp = c->sparams; sa.st = c->state; sa.out_tokens = c->out_tokens_dev; sa.out_cap = c->out_cap; sa.advance = 1; sa.sort_buf = c->sort_buf; sa.err = c->xwg_err;
+                hipLaunchKernelGGL(k_sample_advance, dim3(1), dim3(kSampleBlock), sample_lds_bytes(d.vocab_size), st, sa);
+            } else {          // (the entry points admit temperature 0 only here: the first maximum of the shaped row)
+                hipLaunchKernelGGL(k_argmax_advance, dim3(1), dim3(1024), 0, st, (const float*)c->shape_row, d.vocab_size, c->state, c->out_tokens_dev, 1, c->out_cap, (const int*)c->xwg_err);
+            }
+            HIPC(c, hipGetLastError());
+        } else if (advance == 3) {   // a sampled token: every rank samples the same all-gathered logits with the same state and draws the same token
             if (!sample_supported(c)) return fail(c, FLM_ERR_UNSUPPORTED, "device sampler: vocabulary too large for one workgroup's LDS");
             Tick t(c, st, KC_ARGMAX);
             SampleArgs sa{};

@@ -181,6 +181,13 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
                               int max_new_tokens, float temperature, float topp) {
     const std::vector<int> input = encode(prompt);
     if (input.empty()) { fprintf(stderr, "Empty input for generate()\n"); return false; }
+    if (_shape_set) {       // the bias ids against THIS model's vocabulary, here and not only in the C ABI: the host loop below hands them to shape_logits directly
+        for (size_t i = 0; i < _bias_ids.size(); ++i) {
+            bool bad = _bias_ids[i] < 0 || _bias_ids[i] >= _cfg.vocab_size;
+            for (size_t k = 0; k < i && !bad; ++k) bad = _bias_ids[k] == _bias_ids[i];
+            if (bad) { _err = "--logit-bias: an id outside [0, vocab) or listed twice"; return false; }
+        }
+    }
     printf("Input prompt:%s\n", prompt);
     print_vector("Input tokens:", input);
     const int n_in = (int)input.size();
@@ -225,7 +232,15 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
             if (rc == FLM_OK && flm_query(_ctxs[0], "spec_steps", &v) == FLM_OK) _lookup_steps += v;
             if (rc == FLM_OK && flm_query(_ctxs[0], "spec_accepted", &v) == FLM_OK) _lookup_accepted += v;
         };
-        if (_draft_k > 0) {                 // --draft: the same loop through draft-and-verify steps at the run's temperature; refused (nothing was launched): the run without the flag
+        if (_shape_set) {                   // the sampling controls: the same loop with the shaping stage on the device (flm_generate_ex); refused: the host loop below shapes
+            flm_sampling sp{};
+            sp.temperature = temperature; sp.topp = topp; sp.top_k = _shape.top_k; sp.min_p = _shape.min_p; sp.repeat_penalty = _shape.repeat_penalty;
+            sp.frequency_penalty = _shape.frequency_penalty; sp.presence_penalty = _shape.presence_penalty; sp.penalty_last_n = _shape_last_n;
+            sp.n_bias = _shape.n_bias; sp.bias_ids = _shape.bias_ids; sp.bias_values = _shape.bias_values;
+            rc = flm_generate_ex(_ctxs[0], input.data(), n_in, 0, want, &sp, &st, 0, on_token, &sink, nullptr, &n_out);
+            if (rc == FLM_ERR_INVALID) { _err = flm_last_error(_ctxs[0]); fprintf(stderr, "%s\n", _err.c_str()); }
+            whole = false;
+        } else if (_draft_k > 0) {          // --draft: the same loop through draft-and-verify steps at the run's temperature; refused (nothing was launched): the run without the flag
             rc = greedy ? flm_generate_lookup(_ctxs[0], input.data(), n_in, 0, want, 0, _draft_k, _draft_g, on_token, &sink, nullptr, &n_out)
                         : flm_generate_lookup_sample(_ctxs[0], input.data(), n_in, 0, want, temperature, topp, &st, 0, _draft_k, _draft_g, on_token, &sink, nullptr, &n_out);
             count();
@@ -240,6 +255,13 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
         if (rc != FLM_ERR_UNSUPPORTED) return false;
         dev_sample = false;
     }
+    // the sampling controls where the loop is the host's: the logits come back, shape_logits runs over the window (the last penalty_last_n ids of the prompt and what was
+    // generated since), then the host sampler -- what flm_generate_ex computes on the device
+    const bool shaped = _shape_set;
+    std::vector<int32_t> history;
+    if (shaped) history.assign(input.begin(), input.end());
+    std::vector<float> shaped_row(shaped ? _cfg.vocab_size : 0);
+    if (shaped) dev_sample = false;
     while (next != 0 && i < max_tokens) {
         if (dev_sample && (int)cur.size() == 1) {
             // the device-resident sampled loop, in chunks like the greedy one; the host's Sampler keeps the authoritative state
@@ -260,7 +282,7 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
             if (stop) break;
             continue;
         }
-        if (greedy && (int)cur.size() == 1) {
+        if (greedy && !shaped && (int)cur.size() == 1) {
             // temperature 0: run a chunk of tokens in the device-resident greedy loop (no per-token host round trip)
             int chunk = max_tokens - i; if (chunk > 8) chunk = 8;
             std::vector<int32_t> out(chunk);
@@ -278,7 +300,7 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
             continue;
         }
         int rc;
-        if (greedy) {
+        if (greedy && !shaped) {
             std::vector<int32_t> ts(_ctxs.size(), 0);
             rc = on_all([&](int r) { return flm_forward_argmax(_ctxs[r], cur.data(), (int)cur.size(), i, &ts[r]); }); next = ts[0];
         } else if (dev_sample) {
@@ -292,7 +314,12 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
             std::vector<std::vector<float>> lgs(_ctxs.size());
             for (size_t r = 1; r < lgs.size(); ++r) lgs[r].resize(_cfg.vocab_size);
             rc = on_all([&](int r) { return flm_forward(_ctxs[r], cur.data(), (int)cur.size(), i, r == 0 ? logits.data() : lgs[r].data()); });
-            if (rc == FLM_OK) next = _sampler.sample(logits.data(), temperature, topp);
+            if (rc == FLM_OK && shaped) {
+                const int w = (int)history.size() < _shape_last_n ? (int)history.size() : _shape_last_n;
+                shape_logits(logits.data(), _cfg.vocab_size, temperature, _shape, history.data() + (history.size() - w), w, shaped_row.data());
+                next = _sampler.sample(shaped_row.data(), temperature, topp);
+                history.push_back(next);
+            } else if (rc == FLM_OK) next = _sampler.sample(logits.data(), temperature, topp);
         }
         if (rc != FLM_OK) return false;
         if (!emit(next, i, (int)cur.size())) break;

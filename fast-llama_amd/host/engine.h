@@ -39,6 +39,15 @@ public:
     // --draft K[,G] (this build only): the same at whatever temperature the run has: at 0 flm_generate_lookup, otherwise flm_generate_lookup_sample with the Sampler's state (written
     // back afterwards) -- the same ids as the sampled loop's; where the library refuses (FLM_ERR_UNSUPPORTED) the run is what it is without the flag.  Counted in lookup_steps / _accepted
     void set_draft(int draft_len, int ngram_max) { _draft_k = draft_len; _draft_g = ngram_max; }
+    // --top-k / --min-p / --repeat-penalty / --repeat-last-n / --presence-penalty / --frequency-penalty / --logit-bias (this build only): the sampling controls of flm_sampling.
+    // One device: the whole loop is flm_generate_ex (the shaping stage on the device); where the engine samples on the host (a vocabulary beyond the device sampler, several
+    // devices) it calls shape_logits in front of the host sampler: the same ids.  --lookup / --draft are ignored then (spec decoding does not take the controls).
+    // Not called: nothing changes.
+    void set_sampling(const ShapeControls& c, int penalty_last_n, const std::vector<int32_t>& bias_ids, const std::vector<float>& bias_values) {
+        _shape = c; _shape_last_n = penalty_last_n; _bias_ids = bias_ids; _bias_values = bias_values;
+        _shape.n_bias = (int)_bias_ids.size(); _shape.bias_ids = _bias_ids.data(); _shape.bias_values = _bias_values.data();
+        _shape_set = true;
+    }
     int lookup_steps() const { return _lookup_steps; }
     int lookup_accepted() const { return _lookup_accepted; }
     int get_quant_type() const { return _cfg.quant_type; }
@@ -62,6 +71,7 @@ private:
     std::string _err;
     int _lookup_k = 0, _lookup_g = 3, _lookup_steps = 0, _lookup_accepted = 0;
     int _draft_k = 0, _draft_g = 3;
+    bool _shape_set = false; ShapeControls _shape; int _shape_last_n = 0; std::vector<int32_t> _bias_ids; std::vector<float> _bias_values;
 };
 
 } // namespace flmhost

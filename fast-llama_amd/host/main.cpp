@@ -4,6 +4,7 @@
 // Extra of this build: --mode score = no generation: the prompt's tokens are scored in one batched pass (flm_score_tokens) -- per position the greedy id and the probability of
 // the next token, then token count, mean loss, perplexity and ms; --device <hip ordinal>; --devices a,b,... = the reference's parallel width (-j, main.cpp:30,78) on GPUs: one
 // sequence sharded over the named devices (split_rows, transformer.cpp:264-287), one host thread per device.
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -35,6 +36,9 @@ struct Args {
     const char* bad_lookup = nullptr;
     int draft_k = 0, draft_g = 3;           // --draft K[,G]: the same drafter and ranges at whatever temperature the run has (-t 0: flm_generate_lookup, else flm_generate_lookup_sample)
     const char* bad_draft = nullptr;
+    // the sampling controls (flm_sampling): any of these flags switches the shaping stage on
+    bool shape_set = false; ShapeControls shape; int repeat_last_n = 64;
+    std::vector<int32_t> bias_ids; std::vector<float> bias_values; const char* bad_sampling = nullptr;
     Mode mode = Mode::GEN;
 };
 const char* Y = "\x1b[33m"; const char* G = "\x1b[32m"; const char* E = "\x1b[0m";
@@ -55,6 +59,13 @@ void usage(const char* bin) {
     fprintf(stderr, "   --devices         <a,b,...>   shard ONE sequence over these HIP devices, 1 to 8 of them (this build only)\n");
     fprintf(stderr, "   --lookup          <K[,G]>     with -t 0 on one device: draft K (4..15) tokens per step by prompt lookup (n-grams up to G, 1..8, default 3) and verify them in one pass; the same text (this build only)\n");
     fprintf(stderr, "   --draft           <K[,G]>     on one device, at any temperature: draft K (4..15) tokens per step by prompt lookup (n-grams up to G, 1..8, default 3) and verify them in one pass, sampled rows drawn with the sampler's own coins; the same text (this build only)\n");
+    fprintf(stderr, "   --top-k           <integer>   keep the K most likely tokens, 0 = off (this build only)\n");
+    fprintf(stderr, "   --min-p           <float>     drop tokens whose probability is below this fraction of the most likely one's, [0, 1), 0 = off (this build only)\n");
+    fprintf(stderr, "   --repeat-penalty  <float>     penalise the tokens of the last --repeat-last-n ids, > 0, 1 = off (this build only)\n");
+    fprintf(stderr, "   --repeat-last-n   <integer>   the penalties' window, 0 .. 1024, default 64 (this build only)\n");
+    fprintf(stderr, "   --presence-penalty  <float>   subtracted once from every token of the window, 0 = off (this build only)\n");
+    fprintf(stderr, "   --frequency-penalty <float>   subtracted per occurrence in the window, 0 = off (this build only)\n");
+    fprintf(stderr, "   --logit-bias      <id=val[,id=val...]>  added to these tokens' logits; -inf bans a token; at most 256 pairs (this build only)\n");
     fprintf(stderr, "   --encode,-e       <string>    encode the input string into tokens\n");
     fprintf(stderr, "   --decode,-d       <string>    decode the input tokens to text\n");
     fprintf(stderr, "   --help,-h                     print this message\n");
@@ -80,6 +91,20 @@ bool parse_draft(const char* v, int& k_out, int& g_out) {       // K or K,G with
     if (!ok || *e != 0) return false;
     k_out = (int)k; g_out = (int)g;
     return true;
+}
+bool parse_float(const char* v, float& out) { char* e; const float f = strtof(v, &e); if (e == v || *e != 0) return false; out = f; return true; }
+bool parse_bias(const char* v, std::vector<int32_t>& ids, std::vector<float>& vals) {       // id=val[,id=val...], val a float or -inf, at most 256 pairs
+    ids.clear(); vals.clear();
+    bool ok = *v != 0;
+    while (ok && *v) {
+        char* e; const long id = strtol(v, &e, 10);
+        ok = e != v && id >= 0 && *e == '=' && ids.size() < 256;
+        if (!ok) break;
+        const char* s = e + 1; const float b = strtof(s, &e);
+        ok = e != s && (*e == 0 || (*e == ',' && e[1] != 0)) && b == b && b != INFINITY;
+        if (ok) { ids.push_back((int32_t)id); vals.push_back(b); v = *e ? e + 1 : e; }
+    }
+    return ok;
 }
 template <class E> bool pick(const char* v, std::initializer_list<std::pair<const char*, E>> names, E& out) {     // case-insensitive keyword -> enum; unknown words leave `out` alone (as the reference does)
     for (const auto& n : names) if (!strcasecmp(v, n.first)) { out = n.second; return true; }
@@ -116,6 +141,13 @@ const Flag kFlags[] = {
         if (ok && *e == ',') { const char* s = e + 1; g = strtol(s, &e, 10); ok = e != s && g >= 1 && g <= 8; }
         if (ok && *e == 0) { a.lookup_k = (int)k; a.lookup_g = (int)g; } else a.bad_lookup = v; }},
     {nullptr, "--draft",       true,  [](Args& a, const char* v) { if (!parse_draft(v, a.draft_k, a.draft_g)) a.bad_draft = v; }},                 // (this build only)
+    {nullptr, "--top-k",             true, [](Args& a, const char* v) { char* e; const long k = strtol(v, &e, 10); a.shape_set = true; if (e == v || *e || k < 0 || k > 0x7fffffff) a.bad_sampling = v; else a.shape.top_k = (int)k; }},   // (this build only)
+    {nullptr, "--min-p",             true, [](Args& a, const char* v) { a.shape_set = true; if (!parse_float(v, a.shape.min_p) || !(a.shape.min_p >= 0.f && a.shape.min_p < 1.f)) a.bad_sampling = v; }},                              // (this build only)
+    {nullptr, "--repeat-penalty",    true, [](Args& a, const char* v) { a.shape_set = true; if (!parse_float(v, a.shape.repeat_penalty) || !(a.shape.repeat_penalty > 0.f) || a.shape.repeat_penalty == INFINITY) a.bad_sampling = v; }},   // (this build only)
+    {nullptr, "--repeat-last-n",     true, [](Args& a, const char* v) { char* e; const long k = strtol(v, &e, 10); a.shape_set = true; if (e == v || *e || k < 0 || k > 1024) a.bad_sampling = v; else a.repeat_last_n = (int)k; }},         // (this build only)
+    {nullptr, "--presence-penalty",  true, [](Args& a, const char* v) { a.shape_set = true; if (!parse_float(v, a.shape.presence_penalty) || a.shape.presence_penalty != a.shape.presence_penalty) a.bad_sampling = v; }},               // (this build only)
+    {nullptr, "--frequency-penalty", true, [](Args& a, const char* v) { a.shape_set = true; if (!parse_float(v, a.shape.frequency_penalty) || a.shape.frequency_penalty != a.shape.frequency_penalty) a.bad_sampling = v; }},            // (this build only)
+    {nullptr, "--logit-bias",        true, [](Args& a, const char* v) { a.shape_set = true; if (!parse_bias(v, a.bias_ids, a.bias_values)) a.bad_sampling = v; }},                                                                      // (this build only)
 };
 }
 void parse(Args& a, int argc, const char** argv) {
@@ -132,6 +164,7 @@ void parse(Args& a, int argc, const char** argv) {
     }
     if (a.bad_lookup) { fprintf(stderr, "Invalid --lookup:\x1b[31m%s\x1b[0m (expected K or K,G with 4 <= K <= 15 and 1 <= G <= 8)\n", a.bad_lookup); usage(argv[0]); exit(-1); }
     if (a.bad_draft) { fprintf(stderr, "Invalid --draft:\x1b[31m%s\x1b[0m (expected K or K,G with 4 <= K <= 15 and 1 <= G <= 8)\n", a.bad_draft); usage(argv[0]); exit(-1); }
+    if (a.bad_sampling) { fprintf(stderr, "Invalid sampling control:\x1b[31m%s\x1b[0m (--top-k >= 0, --min-p in [0, 1), --repeat-penalty > 0, --repeat-last-n 0..1024, --logit-bias id=val[,id=val...] with at most 256 pairs)\n", a.bad_sampling); usage(argv[0]); exit(-1); }
     if (a.rounds < 1) a.rounds = a.mode == Mode::TEST ? 16 : 1;
 }
 
@@ -175,7 +208,12 @@ int main(int argc, const char** argv) {
         fprintf(stderr, "warning: --draft applies to one device only; ignored\n");
         args.draft_k = 0;
     }
+    if (args.shape_set && (args.lookup_k || args.draft_k)) {
+        fprintf(stderr, "warning: --lookup / --draft do not take the sampling controls; ignored\n");
+        args.lookup_k = args.draft_k = 0;
+    }
     GpuTransformer tf(args.detail || args.debug);
+    if (args.shape_set) tf.set_sampling(args.shape, args.repeat_last_n, args.bias_ids, args.bias_values);
     if (args.lookup_k) tf.set_lookup(args.lookup_k, args.lookup_g);
     if (args.draft_k) tf.set_draft(args.draft_k, args.draft_g);
     if (!tf.load(args.ckpt, args.tknr, args.ft, args.qtype, args.devices)) { fprintf(stderr, "Failed to load model\n%s\n", tf.error().c_str()); return 1; }

@@ -3,6 +3,9 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include <algorithm>
+#include <numeric>
+
 namespace flmhost {
 
 float Sampler::coin() {
@@ -51,6 +54,40 @@ int Sampler::sample(float* logits, float temperature, float topp) {
     float cdf = 0.f;
     for (int i = 0; i <= last; ++i) { cdf += _idx[i].prob; if (r < cdf) return _idx[i].index; }
     return _idx[last].index;
+}
+
+void shape_logits(const float* L, int n, float temperature, const ShapeControls& c, const int32_t* window, int n_window, float* S) {
+    for (int i = 0; i < n; ++i) S[i] = L[i];
+    // 1: bias
+    for (int i = 0; i < c.n_bias; ++i) S[c.bias_ids[i]] = S[c.bias_ids[i]] + c.bias_values[i];
+    // 2: penalties, once per distinct id of the window
+    const bool rep = c.repeat_penalty != 1.0f, fpp = c.frequency_penalty != 0.0f || c.presence_penalty != 0.0f;
+    if (n_window > 0 && (rep || fpp)) {
+        for (int j = 0; j < n_window; ++j) {
+            const int t = window[j];
+            int count = 0; bool first = true;
+            for (int k = 0; k < n_window; ++k) if (window[k] == t) { ++count; if (k < j) first = false; }
+            if (!first) continue;
+            float x = S[t];
+            if (rep) x = x > 0.0f ? x / c.repeat_penalty : x * c.repeat_penalty;
+            if (fpp) x = x - ((float)count * c.frequency_penalty + c.presence_penalty);
+            S[t] = x;
+        }
+    }
+    // 3: top-k
+    if (c.top_k > 0 && c.top_k < n) {
+        std::vector<int> idx(n);
+        std::iota(idx.begin(), idx.end(), 0);
+        std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return S[a] > S[b]; });
+        for (int r = c.top_k; r < n; ++r) S[idx[r]] = -INFINITY;
+    }
+    // 4: min-p
+    if (c.min_p > 0.0f && temperature != 0.0f) {
+        const float lt = logf(c.min_p);
+        float mx = -INFINITY;
+        for (int i = 0; i < n; ++i) if (S[i] != -INFINITY) { const float y = S[i] / temperature; if (y > mx) mx = y; }
+        for (int i = 0; i < n; ++i) if (S[i] != -INFINITY) { const float y = S[i] / temperature; if (y - mx < lt) S[i] = -INFINITY; }
+    }
 }
 
 } // namespace flmhost

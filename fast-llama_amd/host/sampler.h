@@ -23,4 +23,15 @@ private:
     std::vector<PI> _idx;
 };
 
+// The logit-shaping stage in front of Sampler::sample (include/flm_gpu.h, flm_sampling): a plain sequential restatement of its definition -- bias, penalties over the
+// DISTINCT ids of the window, top-k (larger value first, equal values by lower index), min-p in the logit domain with glibc's logf -- that the device's k_shape_logits
+// (csrc/flm_shape.h) equals bit for bit.  S[n] <- the shaped L[n]; a stage whose control is neutral writes nothing.  The arguments are taken as valid: the C ABI checks them, and so does GpuTransformer::generate before its host loop calls this.
+struct ShapeControls {
+    int top_k = 0; float min_p = 0.f;
+    float repeat_penalty = 1.f, frequency_penalty = 0.f, presence_penalty = 0.f;
+    int n_bias = 0; const int32_t* bias_ids = nullptr; const float* bias_values = nullptr;
+    bool neutral() const { return top_k <= 0 && min_p <= 0.f && repeat_penalty == 1.f && frequency_penalty == 0.f && presence_penalty == 0.f && n_bias == 0; }
+};
+void shape_logits(const float* L, int n, float temperature, const ShapeControls& c, const int32_t* window, int n_window, float* S);
+
 } // namespace flmhost

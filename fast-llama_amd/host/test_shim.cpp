@@ -75,6 +75,14 @@ int fh_sample_state(int vocab, unsigned long long* state, const float* logits, f
     *state = s.state();
     return tok;
 }
+// the logit-shaping stage (sampler.h shape_logits) on one row: out[n]; the expected value of the device's k_shape_logits
+void fh_shape(const float* logits, int n, float temperature, int top_k, float min_p, float repeat_penalty, float frequency_penalty, float presence_penalty,
+              int n_bias, const int32_t* bias_ids, const float* bias_values, const int32_t* window, int n_window, float* out) {
+    ShapeControls c;
+    c.top_k = top_k; c.min_p = min_p; c.repeat_penalty = repeat_penalty; c.frequency_penalty = frequency_penalty; c.presence_penalty = presence_penalty;
+    c.n_bias = n_bias; c.bias_ids = bias_ids; c.bias_values = bias_values;
+    shape_logits(logits, n, temperature, c, window, n_window, out);
+}
 // flm_score (include/flm_gpu.h) of one row of logits, in plain C++: sample_argmax (sampler.cpp:36-47) and the sampler's clipped softmax (tf_operators.cpp:188-209) at
 // temperature 1, read at `target` (-1: none) -- libm expf, a sequential fp32 sum in index order, prob = e_target * (float)(1.0 / sum).  out5: {argmax, target_logit,
 // max_logit, sum, prob} as 32-bit words (the struct's layout).  The expected value of the device's k_score_rows.

@@ -235,6 +235,47 @@ int  flm_generate_lookup_sample(flm_ctx* ctx, const int32_t* prompt, int n_promp
                                 int32_t stop_token /* -1: none */, int draft_len /* 4..15 */, int ngram_max /* 1..8 */,
                                 flm_token_cb cb /* may be NULL */, void* user,
                                 int32_t* out_tokens /* [max_tokens], may be NULL */, int* n_out);
+/* Sampling controls on the device: top-k, min-p, repetition / frequency / presence penalties over a window of recent ids, and a logit bias (-inf: a ban).  No reference
+ * counterpart (the reference samples with temperature and top-p only).  A shaping stage (k_shape_logits, csrc/flm_shape.h: one 1024-thread workgroup, no vocabulary bound) runs
+ * between the classifier and the sampler above, which is not changed and reads the shaped row S instead of the raw row L.  The definition, all of it fp32 round-to-nearest:
+ *   1 bias       S = L; S[id] = S[id] + b for each of the n_bias pairs (ids distinct; b finite or -inf)
+ *   2 penalties  window W[0 .. w), w > 0: for every DISTINCT id t of W with c occurrences (each id once): x = S[t]; repeat_penalty != 1: x = x > 0 ? x / repeat_penalty
+ *                : x * repeat_penalty; frequency_penalty or presence_penalty != 0: x = x - ((float)c * frequency_penalty + presence_penalty); S[t] = x
+ *   3 top-k      0 < top_k < n: the top_k entries first in "larger value, equal values by lower index" (float comparison: -0.0 ties +0.0) stay, all others become -inf
+ *   4 min-p      min_p > 0 and temperature != 0: y[i] = S[i] / temperature over the entries that are not -inf, mx = max y; S[i] = -inf where y[i] - mx < logf(min_p) (the
+ *                logarithm is taken once on the host, glibc's): the entries whose probability is below min_p times the largest one
+ *   5 the sampler  on S with (temperature, topp), unchanged -- its top-p cutoff keeps using the full n; temperature 0: the first maximum of S
+ * A stage whose control is neutral (n_bias 0; repeat_penalty 1; frequency_penalty = presence_penalty = 0, or an empty window; top_k 0 or >= n; min_p 0) writes nothing: with
+ * every control neutral S is L bit for bit and the _ex entry points run the launches of their plain forms.  The host restatement is host/sampler.cpp shape_logits; the device
+ * equals it bit for bit, so ids under controls are a host loop's ids (flm_forward, shape_logits, Sampler::sample) element for element.  NaN logits are outside the contract.
+ * The controls live in a device block written at the start of each call (like the sampler's parameters): no graph is re-captured, nothing is allocated.
+ * Spec decoding (the flm_verify_ and flm_generate_lookup families) does not take the controls: each row of a verify batch would need a window of its own.  Not built. */
+#define FLM_PENALTY_WINDOW_MAX 1024
+#define FLM_BIAS_MAX 256
+typedef struct flm_sampling {
+    float temperature, topp;          /* as flm_generate */
+    int32_t top_k;                    /* 0: off */
+    float min_p;                      /* 0: off */
+    float repeat_penalty;             /* 1: off */
+    float frequency_penalty, presence_penalty;   /* 0: off */
+    int32_t penalty_last_n;           /* 0 .. FLM_PENALTY_WINDOW_MAX; 0: penalties off */
+    int32_t n_bias;                   /* 0 .. FLM_BIAS_MAX */
+    const int32_t* bias_ids; const float* bias_values;
+} flm_sampling;
+/* flm_generate with the controls: its contract in every other respect (the stop token, cancel, streaming, *n_out, *rng_state after exactly *n_out draws, the KV rows,
+ * FLM_ERR_UNSUPPORTED for world > 1; a retried call re-runs from the caller's state and delivers nothing twice).  The penalty window at generated token s is the last
+ * min(penalty_last_n, n_prompt + s) ids of THIS call's prompt followed by the ids this call has drawn so far, assembled on the device; ids that were in the KV cache before the
+ * call (pos > 0) are not part of it.  A token is classifier -> k_shape_logits -> the sampler, replayed as a graph built at flm_prepare next to the sampled one; at temperature 0
+ * with a control set the same form runs (the sampler's own first-maximum branch), not the one-launch greedy token.  Vocabulary: the shaper has no bound; at temperature != 0 the
+ * sampler's FLM_ERR_UNSUPPORTED above ~36 K entries stays; at temperature 0 there is none.  rng_state may be NULL iff temperature == 0.
+ * FLM_ERR_INVALID, with nothing launched: a NULL struct, top_k < 0, min_p outside [0, 1) or NaN, repeat_penalty <= 0 or NaN, a NaN frequency or presence penalty,
+ * penalty_last_n / n_window / n_bias out of range, a bias id outside [0, vocab) or listed twice, a bias that is NaN or +inf, a window id outside [0, vocab). */
+int  flm_generate_ex(flm_ctx* ctx, const int32_t* prompt, int n_prompt, int pos, int max_tokens, const flm_sampling* sampling,
+                     uint64_t* rng_state, int32_t stop_token, flm_token_cb cb, void* user, int32_t* out_tokens, int* n_out);
+/* flm_forward_sample with the controls, for callers with a loop of their own: the window is the caller's, window[0 .. n_window), 0 <= n_window <= FLM_PENALTY_WINDOW_MAX, used
+ * as given (penalty_last_n is only range-checked here; n_window == 0: penalties off).  One GPU only when a control is set. */
+int  flm_forward_sample_ex(flm_ctx* ctx, const int32_t* tokens, int n, int pos, const flm_sampling* sampling,
+                           const int32_t* window, int n_window, uint64_t* rng_state, int32_t* next_token);
 /* the ids generated by the last flm_decode_greedy / flm_decode_sample / flm_decode_timed* call: out[n] (n <= its n_steps) */
 int  flm_last_tokens(flm_ctx* ctx, int n, int32_t* out);
 int  flm_reset_kv(flm_ctx* ctx);
@@ -320,6 +361,7 @@ int  flm_set_option(flm_ctx* ctx, const char* key, int value);
  *               classifier, argmax in k_layers<.., TAIL>),
  *   "ao_active" which hand-offs of that launch are consumed in arrival order: bit 0 Wo, bit 1 FFN2 (-1: the launch has not been planned yet),
  *   "sampled_tokens" how many tokens this context sampled on the device (flm_forward_sample / flm_decode_sample / flm_generate / flm_verify_sample / flm_generate_lookup_sample at temperature > 0),
+ *   "shaped_tokens" how many tokens this context drew through the shaped token form (flm_generate_ex / flm_forward_sample_ex with a control set),
  *   "spec_steps" / "spec_accepted" the last flm_generate_lookup / flm_generate_lookup_sample call: verify passes run / drafted ids accepted in them,
  *   "gen_tokens" / "gen_streamed" the last flm_generate call: tokens delivered / how many of them were delivered while hipStreamQuery still said the stream was busy,
  *   "epoch_tail" / "epoch_eng" / "epoch_xchg" the epoch counters the cross-workgroup waits count from (device memory; the 32-bit pattern): the one-launch token's, the
@@ -354,6 +396,9 @@ int  flm_op_sample(const float* logits, int n, float temperature, float topp, ui
 /* the sampler of flm_verify_sample (k_sample_rows) on caller-supplied logits[rows][ld], n entries per row, 1 <= rows <= 16, ld >= n >= 2: out[i] = row i drawn with the
  * (i + 1)-th coin of *rng_state, i.e. what `rows` successive flm_op_sample calls on the rows return; *rng_state out: the state after `rows` draws (temperature 0: untouched) */
 int  flm_op_sample_rows(const float* logits, int rows, int ld, int n, float temperature, float topp, uint64_t* rng_state, int32_t* out);
+/* the shaping stage of flm_generate_ex (k_shape_logits) on caller-supplied logits[n], n >= 2, and window[n_window] used as given: out[n] = the shaped row (steps 1 - 4 of the
+ * definition at flm_sampling; sampling->temperature is min-p's divisor, topp is not used).  No bound on n.  Errors as there. */
+int  flm_op_shape_logits(const float* logits, int n, const flm_sampling* sampling, const int32_t* window, int n_window, float* out);
 /* flm_score_tokens' statistics kernel (k_score_rows) on caller-supplied logits[rows][n]: out[rows]; targets[rows] as there (NULL: none).  2 <= n, n within the LDS bound. */
 int  flm_op_score_rows(const float* logits, int rows, int n, const int32_t* targets, flm_score* out);
 /* simd::swiglu(xo,xr,n) (x86_simd.cpp:1766-1770) */

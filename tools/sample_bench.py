@@ -5,7 +5,11 @@ weights, 32 layers by default).  Prints one JSON line:
     K tokens after a 9-token prompt, median of R runs, all measured in the same process;
   * the old loop: flm_forward of one token + host Sampler (host/sampler.cpp) per token, same model, same parameters;
   * with --ops: op_sample (k_sample_advance) wall time per call on peaked / medium / flat 32 000-entry logits (the kernel's own time: run under
-    rocprofv3 --kernel-trace --stats)."""
+    rocprofv3 --kernel-trace --stats);
+  * with --shape (and nothing else): the shaped loop against the unshaped one on the same context -- tokens/s of flm_generate at -t 1 -p 0.9, seed 1234 (the sampled loop as
+    it was before the shaping stage existed: the same launches), of flm_generate_ex with a control that changes nothing (a bias of +0: the stage's launch on top of the same
+    sampler work) and with a full set of controls (top-k 40, min-p 0.05, repeat penalty 1.1 over 64 ids, a bias and a ban: the sampler then sorts fewer candidates), the
+    runs alternating; the stage's own duration: k_shape_logits in a rocprofv3 --kernel-trace --stats run of this command."""
 import argparse
 import importlib.util
 import json
@@ -40,8 +44,40 @@ def main():
     ap.add_argument("--host-steps", type=int, default=32)
     ap.add_argument("--ops", action="store_true", help="also time op_sample on peaked / medium / flat logits")
     ap.add_argument("--ops-only", action="store_true")
+    ap.add_argument("--shape", action="store_true", help="time the shaped loop (flm_generate_ex) against the unshaped one (flm_generate) on the same context, nothing else")
     args = ap.parse_args()
     out = {}
+    if args.shape:
+        cfg = synth.make_config("7B", ff.QT_INT8)
+        cfg.n_layers = args.layers
+        ctx = capi.Ctx(capi.desc_from_config(cfg), device=0)
+        _bench_module().upload_synthetic(ctx, cfg)
+        prompt = np.array([1] + [int(x) for x in (np.arange(1, 9) * 7919) % cfg.vocab_size], np.int32)
+        K = args.steps
+        noop = capi.Sampling(temperature=1.0, topp=0.9, bias={11: 0.0})
+        full = capi.Sampling(temperature=1.0, topp=0.9, top_k=40, min_p=0.05, repeat_penalty=1.1, penalty_last_n=64, bias={3: 1.0, 7: -np.inf})
+        runs = {"unshaped": lambda: ctx.generate(prompt, 0, K, temperature=1.0, topp=0.9, rng_state=1234),
+                "shaped_noop": lambda: ctx.generate_ex(prompt, 0, K, noop, rng_state=1234),
+                "shaped_full": lambda: ctx.generate_ex(prompt, 0, K, full, rng_state=1234)}
+        ts = {k: [] for k in runs}
+        ids = {}
+        for rep in range(args.reps + 1):
+            for name, fn in runs.items():                # alternating: the three forms see the same machine
+                ctx.sync(); t0 = time.perf_counter(); ids[name] = fn()[0]; dt = time.perf_counter() - t0
+                if rep:
+                    ts[name].append(dt)
+        assert list(ids["unshaped"]) == list(ids["shaped_noop"]) and len(ids["shaped_full"]) == K
+        for name in runs:
+            med = float(np.median(ts[name]))
+            out[f"{name}_tok_s"] = round(K / med, 1)
+            out[f"{name}_ms_per_call"] = round(med * 1e3, 2)
+            out[f"{name}_spread_ms"] = round((max(ts[name]) - min(ts[name])) * 1e3, 2)
+        out["shaped_noop_extra_us_per_token"] = round((np.median(ts["shaped_noop"]) - np.median(ts["unshaped"])) / K * 1e6, 1)
+        out["shaped_full_extra_us_per_token"] = round((np.median(ts["shaped_full"]) - np.median(ts["unshaped"])) / K * 1e6, 1)
+        out["tokens_per_call"] = K; out["prompt_tokens"] = len(prompt); out["shaped_tokens"] = ctx.query("shaped_tokens")
+        ctx.close()
+        print(json.dumps(out), flush=True)
+        return
     if not args.ops_only:
         cfg = synth.make_config("7B", ff.QT_INT8)
         cfg.n_layers = args.layers
