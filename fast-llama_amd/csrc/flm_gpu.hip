@@ -229,18 +229,18 @@ int maybe_recover(flm_ctx* c, int tokens) {
 // n greedy tokens whose attention spreads a head over the same number of workgroups, as ONE cached graph of n token sequences (a chunk): between two graph launches the
 // device idles ~10 us, between two nodes of a graph ~1.5 -- with the token one launch long that gap is the largest item left outside it.  Chunks of 16, 8, 4, 2 tokens, then single ones.
 constexpr int kChunk = 16;
-static bool graphs_in_use(const flm_ctx* c) { return c->use_graph && !c->timing && !((c->world > 1 || (c->comm && c->force_tp)) && !c->p2p); }   // (RCCL collectives stay eager)
-static bool chunks_in_use(const flm_ctx* c) { return c->use_graph && !c->timing && c->world == 1 && !(c->comm && c->force_tp) && c->graph_chunks; }
-// the cached graph of `n` token sequences (n >= 2: greedy tokens, a chunk; n == 1: one token by (classifier, advance)) for G workgroups per head: captured and instantiated on first use --
+static bool graphs_in_use(const flm_ctx* c) { return c->use_graph && !c->timing && !(sharded(c) && !c->p2p); }   // (RCCL collectives stay eager)
+static bool chunks_in_use(const flm_ctx* c) { return c->use_graph && !c->timing && !sharded(c) && c->graph_chunks; }
+// the cached graph of `n` token sequences (n >= 2: a chunk of a decode loop; n == 1: one token) of (classifier, form) for G workgroups per head: captured and instantiated on first use --
 // flm_prepare (and the end of the upload) asks for every graph the entry points replay, so that this happens THERE and not inside a forward
-static int token_graph(flm_ctx* c, bool with_cls, int advance, int G, int n, hipGraphExec_t* out) {
-    const int key = (with_cls ? 4 : 0) + (advance == kAdvShaped ? 3 + (1 << 27) : advance) + 8 * G + 4096 * (n >= 2 ? n : 0);   // (the shaped form: the sampled form's key + bit 27)
+static int token_graph(flm_ctx* c, bool with_cls, TokenForm form, int G, int n, hipGraphExec_t* out) {
+    const GraphKey key(with_cls, form, G, n);
     auto it = c->graphs.find(key);
     if (it == c->graphs.end()) {
         hipGraph_t g = nullptr; hipGraphExec_t ge = nullptr;
         HIPC(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
         int r = FLM_OK;
-        for (int i = 0; i < n && !r; ++i) r = enqueue_token(c, c->stream, with_cls, advance, G);
+        for (int i = 0; i < n && !r; ++i) r = enqueue_token(c, c->stream, with_cls, form, G);
         hipError_t e = hipStreamEndCapture(c->stream, &g);
         if (r) { if (g) hipGraphDestroy(g); return r; }
         HIPC(c, e);
@@ -257,16 +257,16 @@ static int prepare_layers(flm_ctx* c, int G) {
     int r = layers_prepare(c, G); if (!r) r = layers_prepare(c, attn_parts(c, 1)); if (!r) r = layers_prepare(c, attn_parts(c, c->d.max_seq_len));
     return r;
 }
-static int run_chunk(flm_ctx* c, int T, int n, int advance) {
+static int run_chunk(flm_ctx* c, int T, int n, TokenForm form) {
     const int G = attn_parts(c, T);
     int r = prepare_layers(c, G); if (r) return r;
     hipGraphExec_t ge = nullptr;
-    r = token_graph(c, true, advance, G, n, &ge); if (r) return r;
+    r = token_graph(c, true, form, G, n, &ge); if (r) return r;
     HIPC(c, hipGraphLaunch(ge, c->stream));
     return FLM_OK;
 }
-// greedy (advance 1) or sampled (advance 3) tokens at positions pos .. pos + n - 1 (the attention of token i covers pos + i + 1 positions)
-static int run_tokens(flm_ctx* c, int pos, int n, int advance) {
+// greedy, sampled or shaped tokens at positions pos .. pos + n - 1 (the attention of token i covers pos + i + 1 positions)
+static int run_tokens(flm_ctx* c, int pos, int n, TokenForm form) {
     const bool chunks = chunks_in_use(c);
     int i = 0;
     while (i < n) {
@@ -275,47 +275,48 @@ static int run_tokens(flm_ctx* c, int pos, int n, int advance) {
         if (chunks) while (run < kChunk && i + run < n && attn_parts(c, T + run) == G) ++run;
         int m = 1; while (2 * m <= run) m *= 2;                       // the largest power of two of them: graphs of 16, 8, 4, 2 tokens (a handful of cached graphs), then single ones
         int r;
-        if (m >= 2) r = run_chunk(c, T, m, advance); else r = run_token(c, true, advance, T);
+        if (m >= 2) r = run_chunk(c, T, m, form); else r = run_token(c, true, form, T);
         if (r) return r;
         i += m;
     }
     return FLM_OK;
 }
-int run_greedy_tokens(flm_ctx* c, int pos, int n) { return run_tokens(c, pos, n, 1); }
-int run_token(flm_ctx* c, bool with_cls, int advance, int T) {
+int run_token(flm_ctx* c, bool with_cls, TokenForm form, int T) {
     const int G = attn_parts(c, T);
     int r = prepare_layers(c, G); if (r) return r;
-    if (!graphs_in_use(c)) return enqueue_token(c, c->stream, with_cls, advance, G);
+    if (!graphs_in_use(c)) return enqueue_token(c, c->stream, with_cls, form, G);
     hipGraphExec_t ge = nullptr;
-    r = token_graph(c, with_cls, advance, G, 1, &ge); if (r) return r;
+    r = token_graph(c, with_cls, form, G, 1, &ge); if (r) return r;
     HIPC(c, hipGraphLaunch(ge, c->stream));
     return FLM_OK;
 }
-// Everything the token entry points use beyond the buffers of flm_ctx_create: k_layers' argument blocks (both head splits) and every graph flm_forward* / flm_decode_* replay --
-// single tokens by (classifier, advance) and the greedy chunks of 2 .. 16 tokens, for one workgroup per head and for split heads.  Captures and instantiates, launches nothing
-// (a tensor-parallel rank must not wait for peers here).  Called when the last tensor of a model arrives, at the end of flm_p2p_import, and by flm_prepare.
+// the token forms a context's decode loops replay (single tokens and chunks): greedy always, sampled where the sampler supports the vocabulary, shaped on one GPU.  Their
+// parameters live in device memory (set_sample / set_shape), so no call re-captures or allocates
+static int loop_forms(const flm_ctx* c, TokenForm out[3]) {
+    int n = 0;
+    out[n++] = TokenForm::Greedy;
+    if (sample_supported(c)) out[n++] = TokenForm::Sampled;
+    if (!sharded(c)) out[n++] = TokenForm::Shaped;
+    return n;
+}
+// Everything the token entry points use beyond the buffers of flm_ctx_create: k_layers' argument blocks (both head splits) and every graph flm_forward* / flm_decode_* / flm_generate*
+// replay -- the two single tokens that leave the state to the caller (with logits; a prompt token) and, per loop form, the single token and the chunks of 2 .. 16 tokens --, for one
+// workgroup per head and for split heads.  Captures and instantiates, launches nothing (a tensor-parallel rank must not wait for peers here).  Called when the last tensor of a model
+// arrives, at the end of flm_p2p_import, and by flm_prepare.
 int prepare_all(flm_ctx* c) {
     if (!model_complete(c)) return FLM_OK;
-    if ((c->world > 1 || (c->comm && c->force_tp)) && !c->p2p && !c->comm) return FLM_OK;      // (a tensor-parallel rank that has not met its peers yet: flm_p2p_import prepares)
+    if (sharded(c) && !c->p2p && !c->comm) return FLM_OK;      // (a tensor-parallel rank that has not met its peers yet: flm_p2p_import prepares)
     const int G1 = attn_parts(c, 1), G2 = attn_parts(c, c->d.max_seq_len);
     int r = prepare_layers(c, G1); if (r) return r;
     if (!graphs_in_use(c)) return FLM_OK;
+    TokenForm forms[3]; const int n_forms = loop_forms(c, forms);
     const int Gs[2] = {G1, G2};
     for (int i = 0; i < (G2 != G1 ? 2 : 1); ++i) {
         const int G = Gs[i];
         hipGraphExec_t ge = nullptr;
-        if ((r = token_graph(c, true, 0, G, 1, &ge)) || (r = token_graph(c, true, 1, G, 1, &ge)) || (r = token_graph(c, false, 2, G, 1, &ge))) return r;
-        if (chunks_in_use(c)) for (int n = 2; n <= kChunk; n *= 2) if ((r = token_graph(c, true, 1, G, n, &ge))) return r;
-        // the sampled token's graphs next to the greedy ones: its parameters live in device memory (set_sample), so no call re-captures or allocates
-        if (sample_supported(c)) {
-            if ((r = token_graph(c, true, 3, G, 1, &ge))) return r;
-            if (chunks_in_use(c)) for (int n = 2; n <= kChunk; n *= 2) if ((r = token_graph(c, true, 3, G, n, &ge))) return r;
-        }
-        // ... and the shaped token's (flm_generate_ex: classifier, k_shape_logits, the sampler on the shaped row; its controls live in device memory too); one GPU only
-        if (c->world == 1 && !(c->comm && c->force_tp)) {
-            if ((r = token_graph(c, true, kAdvShaped, G, 1, &ge))) return r;
-            if (chunks_in_use(c)) for (int n = 2; n <= kChunk; n *= 2) if ((r = token_graph(c, true, kAdvShaped, G, n, &ge))) return r;
-        }
+        if ((r = token_graph(c, true, TokenForm::Logits, G, 1, &ge)) || (r = token_graph(c, false, TokenForm::Prompt, G, 1, &ge))) return r;
+        for (int f = 0; f < n_forms; ++f)
+            for (int n = 1; n <= (chunks_in_use(c) ? kChunk : 1); n *= 2) if ((r = token_graph(c, true, forms[f], G, n, &ge))) return r;
     }
     return FLM_OK;
 }
@@ -331,8 +332,7 @@ int alloc_run_bufs(flm_ctx* c) {
     HIPC(c, dev_alloc(c, &c->score_dev, sizeof(ScoreRow) * (size_t)d.max_seq_len));
     HIPC(c, dev_alloc(c, &c->spec_hist, sizeof(int) * ((size_t)d.max_seq_len + 32), true));   // flm_generate_lookup: the call's token history; a verify batch's row maxima and result block
     HIPC(c, dev_alloc(c, &c->spec_arg, sizeof(int) * 16, true));
-    HIPC(c, dev_alloc(c, &c->spec_out, sizeof(SpecOut), true));
-    HIPC(c, dev_alloc(c, &c->spec_out_s, sizeof(SpecOutSample), true));
+    HIPC(c, dev_alloc(c, &c->spec_res, sizeof(SpecOut), true));
     c->bounce_bytes = (size_t)d.vocab_size * 4; if (c->bounce_bytes < sizeof(ScoreRow) * (size_t)d.max_seq_len) c->bounce_bytes = sizeof(ScoreRow) * (size_t)d.max_seq_len;   // (a row of logits | max_seq_len ids | max_seq_len flm_score: each one trip)
     HIPC(c, hipHostMalloc((void**)&c->bounce, c->bounce_bytes + 64, hipHostMallocDefault));          // (+ a line for the error word that rides along: d2h)
     HIPC(c, hipHostMalloc((void**)&c->shape_stage, sizeof(ShapeParams), hipHostMallocDefault));   // (the shaper's parameter block on its way to the device: set_shape)
@@ -487,12 +487,22 @@ int h2d(flm_ctx* c, void* dst_dev, const void* src, size_t bytes) {
     }
     return FLM_OK;
 }
+int Draw::arm(flm_ctx* c) const {
+    int r = shape ? set_shape(c, *shape) : FLM_OK;
+    if (!r && form != TokenForm::Greedy) r = set_sample(c, temperature, topp, coins() ? (unsigned long long)*rng_state : 0ull);
+    return r;
+}
+int Draw::fetch(flm_ctx* c) { return coins() ? d2h(c, &after, &c->sparams->rng, sizeof after) : FLM_OK; }
+void Draw::commit(flm_ctx* c, int n) const {
+    if (coins()) { *rng_state = after; c->sampled += n; }
+    if (shape) c->shaped += n;
+}
 // feed tokens[0..n) sequentially (row i of the reference's batched prefill depends only on rows
 // <= i through the KV cache, so token-by-token evaluation performs the same per-row arithmetic).
-int feed(flm_ctx* c, const int32_t* tokens, int n, int pos, int final_advance) {
+int feed(flm_ctx* c, const int32_t* tokens, int n, int pos, TokenForm last) {
     int r;
     if (n > c->prompt_cap) return fail(c, FLM_ERR_INVALID, "more tokens than max_seq_len");
-    for (int i = 0; i < n; ++i) if (tokens[i] < 0 || tokens[i] >= c->d.vocab_size) return fail(c, FLM_ERR_INVALID, "token id out of range");
+    if (!ids_in_vocab(c, tokens, n)) return fail(c, FLM_ERR_INVALID, "token id out of range");
     { const int rc = h2d(c, c->prompt_dev, tokens, sizeof(int) * (size_t)n); if (rc) return rc; }     // (prompt_cap <= the bounce buffer: one piece; the stream orders it in front of the kernels, nothing touches the buffer before the call's read-back)
     // batched: single GPU always; tensor parallel over the peer-to-peer exchange with the matrix-core kernels (the kernels that store their
     // column slices into the peers' buffers)
@@ -502,17 +512,17 @@ int feed(flm_ctx* c, const int32_t* tokens, int n, int pos, int final_advance) {
         r = prefill_batched_qt(c, n - 1, pos);
         if (r) return r;
         r = set_state(c, pos + n - 1, tokens[n - 1], 0); if (r) return r;
-        return run_token(c, true, final_advance, pos + n);
+        return run_token(c, true, last, pos + n);
     }
     r = set_state(c, pos, tokens[0], 0); if (r) return r;
-    for (int i = 0; i + 1 < n; ++i) { r = run_token(c, false, 2, pos + i + 1); if (r) return r; }
+    for (int i = 0; i + 1 < n; ++i) { r = run_token(c, false, TokenForm::Prompt, pos + i + 1); if (r) return r; }
     // last token: classifier; state.step is reset so out_tokens[0] receives the argmax
     if (n > 1) {
         // step was used as the prompt cursor; zero it for the argmax slot
         hipLaunchKernelGGL(k_set_step, dim3(1), dim3(64), 0, c->stream, c->state, 0);
         HIPC(c, hipGetLastError());
     }
-    return run_token(c, true, final_advance, pos + n);
+    return run_token(c, true, last, pos + n);
 }
 
 // Every token entry point runs its work and then looks at the cross-workgroup error flag (xwg_check); if a hand-off
@@ -1038,10 +1048,9 @@ static float* score_stage(const flm_ctx* c, int* chunk) {
     return sc_rows >= 1 ? c->pf_scores : c->logits;
 }
 // One verify pass at `pos` over the batch prompt_dev[0 .. k] (draft: written by the drafter from the history spec_hist[0 .. n_hist) first): all layers, the classifier in
-// chunks, the rows' first maxima, the accept step.  Enqueues only; the result block spec_out is read by the caller.
-// draw given (the sampled entry points): the rows are drawn by k_sample_rows with the coins of draw->base (temperature 0: first maxima, as above), and the accept step is
-// k_spec_accept_sample into spec_out_s, which also leaves the state after the step's draws.  Without it: the launches of the greedy entry points, unchanged.
-static int spec_step(flm_ctx* c, int pos, int k, int ngram_max, int n_hist, int stop, int room, bool draft, const SpecDraw* draw = nullptr) {
+// chunks, the rows' ids -- drawn by k_sample_rows with the coins of draw.base, at temperature 0 their first maxima --, the accept step, which also leaves the state after
+// the step's draws.  Enqueues only; the result block spec_res is read by the caller.
+static int spec_step(flm_ctx* c, int pos, int k, int ngram_max, int n_hist, int stop, int room, bool draft, const SpecDraw& draw) {
     const int B = k + 1;
     if (draft) {
         hipLaunchKernelGGL(k_spec_draft, dim3(1), dim3(kSampleBlock), 0, c->stream, (const int*)c->spec_hist, n_hist, k, ngram_max, c->prompt_dev);
@@ -1054,8 +1063,7 @@ static int spec_step(flm_ctx* c, int pos, int k, int ngram_max, int n_hist, int 
         const int m = B - r0 < chunk ? B - r0 : chunk;
         r = spec_classify(c, r0, m, stage, skinny, c->spec_arg, draw); if (r) return r;
     }
-    if (draw) hipLaunchKernelGGL(k_spec_accept_sample, dim3(1), dim3(64), 0, c->stream, c->spec_out_s, (const int*)c->spec_arg, (const int*)c->prompt_dev, k, draft ? c->spec_hist : (int*)nullptr, n_hist, stop, room, draw->base, draw->temperature != 0.0f ? 1 : 0);
-    else hipLaunchKernelGGL(k_spec_accept, dim3(1), dim3(64), 0, c->stream, c->spec_out, (const int*)c->spec_arg, (const int*)c->prompt_dev, k, draft ? c->spec_hist : (int*)nullptr, n_hist, stop, room);
+    hipLaunchKernelGGL(k_spec_accept_sample, dim3(1), dim3(64), 0, c->stream, c->spec_res, (const int*)c->spec_arg, (const int*)c->prompt_dev, k, draft ? c->spec_hist : (int*)nullptr, n_hist, stop, room, draw.base, draw.temperature != 0.0f ? 1 : 0);
     HIPC(c, hipGetLastError());
     return FLM_OK;
 }
@@ -1068,29 +1076,26 @@ static void warm_up(flm_ctx* c) {
     const SavedError saved(c);
     int32_t toks[kPrefillMin + 2] = {0};
     const int n = c->d.max_seq_len > kPrefillMin + 2 ? kPrefillMin + 2 : 1;
-    bool ok = feed(c, toks, n, 0, 0) == FLM_OK && hipStreamSynchronize(c->stream) == hipSuccess;
+    bool ok = feed(c, toks, n, 0, TokenForm::Logits) == FLM_OK && hipStreamSynchronize(c->stream) == hipSuccess;
     // ... and flm_score_tokens' launches: the batch with its last layer completed, the classifier tiles and the statistics kernel (whatever targets the memory holds: the kernel checks them)
     if (ok && n > 1 && sample_supported(c)) {
         int chunk = 1; float* const stage = score_stage(c, &chunk);
         ok = prefill_batched_qt(c, n - 1, 0, true) == FLM_OK && score_classify(c, 0, chunk < n - 1 ? chunk : n - 1, stage) == FLM_OK && hipStreamSynchronize(c->stream) == hipSuccess;
     }
-    // ... and every graph a greedy loop replays, once: chunks of 16, 8, 4, 2 tokens and the single token, for one workgroup per head and (from kSplitFrom positions on) for split
-    // heads -- whatever a graph's FIRST launch costs (seen once: ~2 ms inside a timed region of 20 tokens) is paid here
-    const int kEach = 2 * kChunk - 1;
-    if (ok && c->d.max_seq_len > n + kEach) ok = set_state(c, n, 0, 0) == FLM_OK && run_greedy_tokens(c, n, kEach) == FLM_OK && hipStreamSynchronize(c->stream) == hipSuccess;
-    if (ok && c->d.max_seq_len > kSplitFrom + 8 + kEach && attn_parts(c, kSplitFrom + 8) != attn_parts(c, 1))
-        ok = set_state(c, kSplitFrom + 8, 0, 0) == FLM_OK && run_greedy_tokens(c, kSplitFrom + 8, kEach) == FLM_OK && hipStreamSynchronize(c->stream) == hipSuccess;
-    // ... and the sampled token's graphs (the CLI's defaults: temperature 1, top-p 0.9, state 0)
-    if (ok && sample_supported(c) && c->d.max_seq_len > n + kEach)
-        ok = set_sample(c, 1.0f, 0.9f, 0ull) == FLM_OK && set_state(c, n, 0, 0) == FLM_OK && run_tokens(c, n, kEach, 3) == FLM_OK && hipStreamSynchronize(c->stream) == hipSuccess;
-    if (ok && sample_supported(c) && c->d.max_seq_len > kSplitFrom + 8 + kEach && attn_parts(c, kSplitFrom + 8) != attn_parts(c, 1))
-        ok = set_state(c, kSplitFrom + 8, 0, 0) == FLM_OK && run_tokens(c, kSplitFrom + 8, kEach, 3) == FLM_OK && hipStreamSynchronize(c->stream) == hipSuccess;
-    // ... and the shaped token's graphs, every control neutral (the shaper copies the row)
-    if (ok && c->d.vocab_size >= 2 && c->d.max_seq_len > n + kEach) {
-        ShapeParams np{}; np.repeat = 1.0f; np.follow = 1;
-        ok = set_shape(c, np) == FLM_OK && set_sample(c, sample_supported(c) ? 1.0f : 0.0f, 0.9f, 0ull) == FLM_OK && set_state(c, n, 0, 0) == FLM_OK && run_tokens(c, n, kEach, kAdvShaped) == FLM_OK && hipStreamSynchronize(c->stream) == hipSuccess;
-        if (ok && c->d.max_seq_len > kSplitFrom + 8 + kEach && attn_parts(c, kSplitFrom + 8) != attn_parts(c, 1))
-            ok = set_state(c, kSplitFrom + 8, 0, 0) == FLM_OK && run_tokens(c, kSplitFrom + 8, kEach, kAdvShaped) == FLM_OK && hipStreamSynchronize(c->stream) == hipSuccess;
+    // ... and every graph a decode loop replays, once, per loop form (sampled: the CLI's defaults, temperature 1, top-p 0.9, state 0; shaped: every control neutral, the
+    // shaper copies the row): chunks of 16, 8, 4, 2 tokens and the single token, for one workgroup per head and (from kSplitFrom positions on) for split heads -- whatever a
+    // graph's FIRST launch costs (seen once: ~2 ms inside a timed region of 20 tokens) is paid here
+    const int kEach = 2 * kChunk - 1, split_at = kSplitFrom + 8;
+    const bool split = c->d.max_seq_len > split_at + kEach && attn_parts(c, split_at) != attn_parts(c, 1);
+    ShapeParams neutral{}; neutral.repeat = 1.0f; neutral.follow = 1;
+    uint64_t zero = 0;
+    TokenForm forms[3]; const int n_forms = loop_forms(c, forms);
+    for (int f = 0; f < n_forms && ok && c->d.max_seq_len > n + kEach; ++f) {
+        const bool shaped = forms[f] == TokenForm::Shaped;
+        if (shaped && c->d.vocab_size < 2) continue;
+        const Draw dr = shaped ? Draw(sample_supported(c) ? 1.0f : 0.0f, 0.9f, &zero, &neutral) : Draw(forms[f], 1.0f, 0.9f, &zero);
+        ok = dr.arm(c) == FLM_OK && set_state(c, n, 0, 0) == FLM_OK && run_tokens(c, n, kEach, dr.form) == FLM_OK && hipStreamSynchronize(c->stream) == hipSuccess;
+        if (ok && split) ok = set_state(c, split_at, 0, 0) == FLM_OK && run_tokens(c, split_at, kEach, dr.form) == FLM_OK && hipStreamSynchronize(c->stream) == hipSuccess;
     }
     if (ok) (void)xwg_check(c);                                                // (a wait that gave up here puts the context on the per-phase kernels like any other)
     (void)clear_kv(c);                                                          // the cache rows the dummy tokens wrote: cleared again
@@ -1213,7 +1218,7 @@ int flm_forward(flm_ctx* c, const int32_t* tokens, int n, int pos, float* logits
     if (!tokens || !logits_host) return FLM_ERR_INVALID;
     int r = check_ready(c, n, pos); if (r) return r;
     return with_retry(c, n, [&] {
-        int r = feed(c, tokens, n, pos, 0); if (r) return r;
+        int r = feed(c, tokens, n, pos, TokenForm::Logits); if (r) return r;
         return d2h(c, logits_host, c->logits, (size_t)c->d.vocab_size * 4);
     });
 }
@@ -1222,18 +1227,18 @@ int flm_forward_argmax(flm_ctx* c, const int32_t* tokens, int n, int pos, int32_
     if (!tokens || !next_token) return FLM_ERR_INVALID;
     int r = check_ready(c, n, pos); if (r) return r;
     return with_retry(c, n, [&] {
-        int r = feed(c, tokens, n, pos, 1); if (r) return r;
+        int r = feed(c, tokens, n, pos, TokenForm::Greedy); if (r) return r;
         return d2h(c, next_token, c->out_tokens_dev, 4);
     });
 }
 
-static int decode_loop(flm_ctx* c, int32_t first_token, int pos, int n_steps, hipEvent_t e0, hipEvent_t e1, int advance = 1) {
+static int decode_loop(flm_ctx* c, int32_t first_token, int pos, int n_steps, hipEvent_t e0, hipEvent_t e1, TokenForm form = TokenForm::Greedy) {
     int r = check_ready(c, n_steps, pos); if (r) return r;
-    if (first_token < 0 || first_token >= c->d.vocab_size) return fail(c, FLM_ERR_INVALID, "token id out of range");
+    if (!ids_in_vocab(c, &first_token, 1)) return fail(c, FLM_ERR_INVALID, "token id out of range");
     if (n_steps > c->out_cap) return fail(c, FLM_ERR_INVALID, "more steps than max_seq_len");
     r = set_state(c, pos, first_token, 0); if (r) return r;
     if (e0) HIPC(c, hipEventRecord(e0, c->stream));
-    r = run_tokens(c, pos, n_steps, advance); if (r) return r;
+    r = run_tokens(c, pos, n_steps, form); if (r) return r;
     if (e1) HIPC(c, hipEventRecord(e1, c->stream));
     return FLM_OK;
 }
@@ -1265,29 +1270,32 @@ static int sample_args_ok(flm_ctx* c, float temperature, float topp, const uint6
     if (!sample_supported(c)) return fail(c, FLM_ERR_UNSUPPORTED, "device sampler: vocabulary too large for one workgroup's LDS (sample on the host)");
     return FLM_OK;
 }
+// one token drawn behind tokens[0 .. n): flm_forward_sample and, with the shaper's block, flm_forward_sample_ex
+static int forward_draw(flm_ctx* c, const int32_t* tokens, int n, int pos, Draw dr, int32_t* next_token) {
+    int r = check_ready(c, n, pos); if (r) return r;
+    if (dr.coins()) { r = sample_args_ok(c, dr.temperature, dr.topp, dr.rng_state); if (r) return r; }
+    return with_retry(c, n, [&] {
+        int r = dr.arm(c); if (r) return r;
+        r = feed(c, tokens, n, pos, dr.form); if (r) return r;
+        r = dr.fetch(c); if (r) return r;
+        return d2h(c, next_token, c->out_tokens_dev, 4);
+    }, [&] { dr.commit(c, 1); });
+}
 int flm_forward_sample(flm_ctx* c, const int32_t* tokens, int n, int pos, float temperature, float topp, uint64_t* rng_state, int32_t* next_token) {
     if (!tokens || !next_token) return FLM_ERR_INVALID;
-    int r = check_ready(c, n, pos); if (r) return r;
-    r = sample_args_ok(c, temperature, topp, rng_state); if (r) return r;
-    unsigned long long s = 0;
-    return with_retry(c, n, [&] {
-        int r = set_sample(c, temperature, topp, *rng_state); if (r) return r;
-        r = feed(c, tokens, n, pos, 3); if (r) return r;
-        r = d2h(c, &s, &c->sparams->rng, sizeof s); if (r) return r;
-        return d2h(c, next_token, c->out_tokens_dev, 4);
-    }, [&] { *rng_state = s; c->sampled += 1; });
+    return forward_draw(c, tokens, n, pos, Draw(TokenForm::Sampled, temperature, topp, rng_state), next_token);
 }
 int flm_decode_sample(flm_ctx* c, int32_t first_token, int pos, int n_steps, float temperature, float topp, uint64_t* rng_state, int32_t* out_tokens) {
     if (!c || !out_tokens) return FLM_ERR_INVALID;
     int r = sample_args_ok(c, temperature, topp, rng_state); if (r) return r;
-    unsigned long long s = 0;
+    Draw dr(TokenForm::Sampled, temperature, topp, rng_state);
     return with_retry(c, n_steps, [&] {
         int r = check_ready(c, n_steps, pos); if (r) return r;       // (in front of set_sample's launch: this entry point has selected no device yet)
-        r = set_sample(c, temperature, topp, *rng_state); if (r) return r;
-        r = decode_loop(c, first_token, pos, n_steps, nullptr, nullptr, 3); if (r) return r;
-        r = d2h(c, &s, &c->sparams->rng, sizeof s); if (r) return r;
+        r = dr.arm(c); if (r) return r;
+        r = decode_loop(c, first_token, pos, n_steps, nullptr, nullptr, dr.form); if (r) return r;
+        r = dr.fetch(c); if (r) return r;
         return d2h(c, out_tokens, c->out_tokens_dev, sizeof(int) * (size_t)n_steps);
-    }, [&] { *rng_state = s; c->sampled += n_steps; });
+    }, [&] { dr.commit(c, n_steps); });
 }
 
 // ParallelTransformer::generate (transformer.cpp:76-103) as one call: the prompt and ALL of max_tokens - 1 decode tokens go onto the stream at once (the graphs flm_decode_* replay:
@@ -1311,19 +1319,17 @@ static int generate_impl(flm_ctx* c, const int32_t* prompt, int n_prompt, int po
                          int32_t stop_token, flm_token_cb cb, void* user, int32_t* out_tokens, int* n_out, const ShapeParams* shape) {
     if (!c || !prompt || !n_out) return FLM_ERR_INVALID;
     // (in front of everything else: a tensor-parallel rank must not touch a peer -- halting and cancelling across ranks is not built)
-    if (c->world > 1 || (c->comm && c->force_tp)) return fail(c, FLM_ERR_UNSUPPORTED, "generate: one GPU only (tensor-parallel callers keep the flm_decode_* loop)");
+    if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "generate: one GPU only (tensor-parallel callers keep the flm_decode_* loop)");
     if (max_tokens < 1 || !(temperature >= 0.0f) || stop_token >= c->d.vocab_size) return fail(c, FLM_ERR_INVALID, "generate: max_tokens >= 1, temperature >= 0, stop_token < vocab_size (or -1)");
     int r = check_ready(c, n_prompt, pos); if (r) return r;
     if (pos + n_prompt + max_tokens - 1 > c->d.max_seq_len || max_tokens > c->out_cap || max_tokens > c->gen_cap) return fail(c, FLM_ERR_INVALID, "generate: pos + n_prompt + max_tokens - 1 exceeds max_seq_len");
-    const bool sampled = temperature != 0.0f;
-    if (sampled) { r = sample_args_ok(c, temperature, topp, rng_state); if (r) return r; }
-    const int advance = shape ? kAdvShaped : sampled ? 3 : 1;
+    Draw dr(temperature, topp, rng_state, shape);
+    if (dr.coins()) { r = sample_args_ok(c, temperature, topp, rng_state); if (r) return r; }
     volatile unsigned long long* ring = c->gen_host;
     int* cancel_word = (int*)((char*)c->gen_host + (((size_t)c->gen_cap * 8 + 63) & ~(size_t)63));
     int32_t* ids = c->gen_ids.data();
     // across the attempts of a retried call: how many tokens went to the callback (never delivered twice), whether it cancelled, how many were seen while the stream was busy
     int delivered = 0, streamed = 0, total = 0; bool cancelled = false;
-    unsigned long long s = 0;
     auto deliver = [&](int index, int32_t token, int last) {
         if (index < delivered) return;
         delivered = index + 1;
@@ -1340,11 +1346,9 @@ static int generate_impl(flm_ctx* c, const int32_t* prompt, int n_prompt, int po
         __atomic_store_n(cancel_word, 0, __ATOMIC_RELEASE);
         {
             const GenWords words(c, stop_token < 0 ? -1 : stop_token, tag, max_tokens);
-            int r = FLM_OK;
-            if (shape) r = set_shape(c, *shape);
-            if (!r && (sampled || shape)) r = set_sample(c, temperature, topp, sampled ? *rng_state : 0ull);
-            if (!r) r = feed(c, prompt, n_prompt, pos, advance);              // token 0: drawn from the prompt's last logits
-            if (!r && max_tokens > 1) r = run_tokens(c, pos + n_prompt, max_tokens - 1, advance);
+            int r = dr.arm(c);
+            if (!r) r = feed(c, prompt, n_prompt, pos, dr.form);              // token 0: drawn from the prompt's last logits
+            if (!r && max_tokens > 1) r = run_tokens(c, pos + n_prompt, max_tokens - 1, dr.form);
             if (r) { (void)hipStreamSynchronize(c->stream); return r; }
         }
         // poll: the granules in index order as they arrive, until the one marked last -- or until the stream has drained (looked at every kPollsPerQuery empty polls: the
@@ -1372,15 +1376,14 @@ static int generate_impl(flm_ctx* c, const int32_t* prompt, int n_prompt, int po
         // behind the synchronise: how many tokens were drawn (the state's step counter: a halting token counts, nothing behind it ran), their ids, the sampler's state
         DecodeState stt{};
         int r = d2h(c, &stt, c->state, sizeof stt); if (r) return r;
-        if (sampled) { r = d2h(c, &s, &c->sparams->rng, sizeof s); if (r) return r; }
+        r = dr.fetch(c); if (r) return r;
         total = stt.step < 1 ? 1 : stt.step > max_tokens ? max_tokens : stt.step;
         return d2h(c, ids, c->out_tokens_dev, sizeof(int) * (size_t)total);     // (the error word rides along: xwg_check looks at it next)
     }, [&] {
         for (int i = delivered; i < total; ++i) deliver(i, ids[i], i + 1 == total ? 1 : 0);
         if (out_tokens) memcpy(out_tokens, ids, sizeof(int32_t) * (size_t)total);
         *n_out = total;
-        if (sampled) { *rng_state = s; c->sampled += total; }
-        if (shape) c->shaped += total;
+        dr.commit(c, total);
         c->gen_tokens = total; c->gen_streamed = streamed;
     });
     return r;
@@ -1396,7 +1399,7 @@ int flm_generate_ex(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, in
                     int32_t stop_token, flm_token_cb cb, void* user, int32_t* out_tokens, int* n_out) {
     if (!c || !prompt || !n_out) return FLM_ERR_INVALID;
     if (n_prompt < 1 || n_prompt > c->d.max_seq_len) return fail(c, FLM_ERR_INVALID, "tokens/pos outside [0, max_seq_len]");
-    for (int i = 0; i < n_prompt; ++i) if (prompt[i] < 0 || prompt[i] >= c->d.vocab_size) return fail(c, FLM_ERR_INVALID, "token id out of range");
+    if (!ids_in_vocab(c, prompt, n_prompt)) return fail(c, FLM_ERR_INVALID, "token id out of range");
     ShapeParams sp; bool active = false;
     const int tail = n_prompt < FLM_PENALTY_WINDOW_MAX ? n_prompt : FLM_PENALTY_WINDOW_MAX;
     if (const char* why = shape_fill(sampling, c->d.vocab_size, prompt + (n_prompt - tail), tail, true, &sp, &active)) return fail(c, FLM_ERR_INVALID, why);
@@ -1412,17 +1415,8 @@ int flm_forward_sample_ex(flm_ctx* c, const int32_t* tokens, int n, int pos, con
     const bool sampled = temperature != 0.0f;
     if (sampled && !rng_state) return fail(c, FLM_ERR_INVALID, "sample: rng_state must be given at temperature != 0");
     if (!active) return sampled ? flm_forward_sample(c, tokens, n, pos, temperature, topp, rng_state, next_token) : flm_forward_argmax(c, tokens, n, pos, next_token);
-    if (c->world > 1 || (c->comm && c->force_tp)) return fail(c, FLM_ERR_UNSUPPORTED, "shaped token: one GPU only");
-    int r = check_ready(c, n, pos); if (r) return r;
-    if (sampled) { r = sample_args_ok(c, temperature, topp, rng_state); if (r) return r; }
-    unsigned long long s = 0;
-    return with_retry(c, n, [&] {
-        int r = set_shape(c, sp); if (r) return r;
-        r = set_sample(c, temperature, topp, sampled ? *rng_state : 0ull); if (r) return r;
-        r = feed(c, tokens, n, pos, kAdvShaped); if (r) return r;
-        if (sampled) { r = d2h(c, &s, &c->sparams->rng, sizeof s); if (r) return r; }
-        return d2h(c, next_token, c->out_tokens_dev, 4);
-    }, [&] { if (sampled) { *rng_state = s; c->sampled += 1; } c->shaped += 1; });
+    if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "shaped token: one GPU only");
+    return forward_draw(c, tokens, n, pos, Draw(temperature, topp, rng_state, &sp), next_token);
 }
 
 // Score a sequence: every position's logits in one batched pass, reduced on the device to a flm_score per row (flm_score.h).  The call is flm_forward's work plus the rows
@@ -1433,14 +1427,12 @@ int flm_forward_sample_ex(flm_ctx* c, const int32_t* tokens, int n, int pos, con
 static_assert(sizeof(flm_score) == sizeof(ScoreRow) && sizeof(flm_score) == 20, "flm_score is k_score_rows' ScoreRow");
 int flm_score_tokens(flm_ctx* c, const int32_t* tokens, int n, int pos, const int32_t* targets, flm_score* out, float* logits_all) {
     if (!c || !tokens || !out) return fail(c, FLM_ERR_INVALID, "score: null argument");
-    if (c->world > 1 || (c->comm && c->force_tp)) return fail(c, FLM_ERR_UNSUPPORTED, "score: one GPU only (tensor-parallel scoring is not built)");
+    if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "score: one GPU only (tensor-parallel scoring is not built)");
     int r = check_ready(c, n, pos); if (r) return r;
     const int V = c->d.vocab_size;
     if (!sample_supported(c)) return fail(c, FLM_ERR_UNSUPPORTED, "score: the vocabulary does not fit one workgroup's LDS (the device sampler's bound)");
-    for (int i = 0; i < n; ++i) {
-        if (tokens[i] < 0 || tokens[i] >= V) return fail(c, FLM_ERR_INVALID, "token id out of range");
-        if (targets && (targets[i] < -1 || targets[i] >= V)) return fail(c, FLM_ERR_INVALID, "score: target outside [0, vocab) and not -1");
-    }
+    if (!ids_in_vocab(c, tokens, n)) return fail(c, FLM_ERR_INVALID, "token id out of range");
+    for (int i = 0; targets && i < n; ++i) if (targets[i] < -1 || targets[i] >= V) return fail(c, FLM_ERR_INVALID, "score: target outside [0, vocab) and not -1");
     const size_t row_bytes = (size_t)V * 4;
     int chunk = 1; float* const stage = score_stage(c, &chunk);
     return with_retry(c, n, [&]() -> int {
@@ -1461,7 +1453,7 @@ int flm_score_tokens(flm_ctx* c, const int32_t* tokens, int n, int pos, const in
         }
         for (int i = nb; i < n; ++i) {
             r = set_state(c, pos + i, tokens[i], 0); if (r) return r;
-            r = run_token(c, true, 0, pos + i + 1); if (r) return r;
+            r = run_token(c, true, TokenForm::Logits, pos + i + 1); if (r) return r;
             r = launch_score_rows(c, c->stream, c->logits, 0, V, c->score_tgt + i, c->score_dev + i, 1); if (r) return r;
             if (logits_all) { r = d2h(c, logits_all + (size_t)i * V, c->logits, row_bytes); if (r) return r; }
         }
@@ -1469,64 +1461,85 @@ int flm_score_tokens(flm_ctx* c, const int32_t* tokens, int n, int pos, const in
     });
 }
 
-// Greedy draft-and-verify (include/flm_gpu.h).  flm_verify_greedy: first_token and the k drafts as ONE batch of k + 1 rows through the batched kernels with the last layer
-// completed; row i's first maximum a[i] is the id the token path draws behind first_token, a[0 .. i) -- as long as the drafts were those ids, so the accept step keeps
-// a[0 .. m], m = the first i with a[i] != drafts[i].  Everything up to the m + 1 ids' trip back is on the stream; nothing is allocated.
-int flm_verify_greedy(flm_ctx* c, int32_t first_token, const int32_t* drafts, int k, int pos, int32_t* out_tokens, int* n_out) {
+// Draft-and-verify (include/flm_gpu.h), greedy and sampled in one implementation.  A verify pass: first_token and the k drafts as ONE batch of k + 1 rows through the batched
+// kernels with the last layer completed; row i's id a[i] is the id the token path draws behind first_token, a[0 .. i) -- as long as the drafts were those ids, so the accept
+// step keeps a[0 .. m], m = the first i with a[i] != drafts[i].  Temperature 0: a[i] is the row's first maximum; no coin, the state untouched (rng_state may be null, the
+// vocabulary is not bound by the sampler).  Otherwise: the sampler is a function of (logits, the coin), the coin of the sampled decode loop's i-th token is the i-th draw of
+// its xorshift state, and a batched row's logits are flm_forward's bits: row i drawn with the (i + 1)-th coin of the step's state (k_sample_rows: the draw k_sample_advance
+// makes, one function) is the id the loop draws; the accept step leaves the state after as many draws as ids it delivers, the coins drawn for the rows behind the cut are
+// simply not counted.  Equality with flm_decode_sample, not rejection sampling.  Everything up to the result block's trip back is on the stream; nothing is allocated.
+static int verify_impl(flm_ctx* c, int32_t first_token, const int32_t* drafts, int k, int pos, float temperature, float topp, uint64_t* rng_state, int32_t* out_tokens, int* n_out) {
     if (!c || !drafts || !out_tokens || !n_out) return fail(c, FLM_ERR_INVALID, "verify: null argument");
-    if (c->world > 1 || (c->comm && c->force_tp)) return fail(c, FLM_ERR_UNSUPPORTED, "verify: one GPU only");
+    if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "verify: one GPU only");
     if (k < 4 || k > 15) return fail(c, FLM_ERR_INVALID, "verify: 4 <= k <= 15 drafts");
+    if (!(temperature >= 0.0f) || topp != topp) return fail(c, FLM_ERR_INVALID, "verify: temperature must be >= 0, top-p a number");
     int r = check_ready(c, k + 1, pos); if (r) return r;
-    const int V = c->d.vocab_size;
-    if (first_token < 0 || first_token >= V) return fail(c, FLM_ERR_INVALID, "token id out of range");
-    for (int i = 0; i < k; ++i) if (drafts[i] < 0 || drafts[i] >= V) return fail(c, FLM_ERR_INVALID, "verify: draft outside [0, vocab)");
+    if (!ids_in_vocab(c, &first_token, 1)) return fail(c, FLM_ERR_INVALID, "token id out of range");
+    if (!ids_in_vocab(c, drafts, k)) return fail(c, FLM_ERR_INVALID, "verify: draft outside [0, vocab)");
+    const bool sampled = temperature != 0.0f;
+    if (sampled) { r = sample_args_ok(c, temperature, topp, rng_state); if (r) return r; }
     SpecOut so{};
     return with_retry(c, k + 1, [&]() -> int {
         int32_t* b = c->gen_ids.data();                                               // (pageable staging of max_seq_len ids, there since create)
         b[0] = first_token; for (int i = 0; i < k; ++i) b[1 + i] = drafts[i];
         int r = h2d(c, c->prompt_dev, b, sizeof(int) * (size_t)(k + 1)); if (r) return r;
-        r = spec_step(c, pos, k, 0, 0, -1, k + 1, false); if (r) return r;
-        return d2h(c, &so, c->spec_out, sizeof so);                                   // (the error word rides along: xwg_check looks at it next)
+        r = spec_step(c, pos, k, 0, 0, -1, k + 1, false, SpecDraw{temperature, topp, sampled ? (unsigned long long)*rng_state : 0ull}); if (r) return r;
+        return d2h(c, &so, c->spec_res, sizeof so);                                   // (the ids and the state in one trip; the error word rides along: xwg_check looks at it next)
     }, [&] {
         memcpy(out_tokens, so.ids, sizeof(int32_t) * (size_t)so.n_emit);
         *n_out = so.n_emit;
+        if (sampled) { *rng_state = so.rng; c->sampled += so.n_emit; }
     });
 }
+int flm_verify_greedy(flm_ctx* c, int32_t first_token, const int32_t* drafts, int k, int pos, int32_t* out_tokens, int* n_out) {
+    return verify_impl(c, first_token, drafts, k, pos, 0.0f, 0.0f, nullptr, out_tokens, n_out);
+}
+int flm_verify_sample(flm_ctx* c, int32_t first_token, const int32_t* drafts, int k, int pos, float temperature, float topp, uint64_t* rng_state, int32_t* out_tokens, int* n_out) {
+    return verify_impl(c, first_token, drafts, k, pos, temperature, topp, rng_state, out_tokens, n_out);
+}
 
-// flm_generate at temperature 0 with several ids per pass over the weights: the prompt enters as in flm_forward_argmax; then every step drafts draft_len tokens ON THE DEVICE from
-// the call's history (k_spec_draft), verifies them in one batch of draft_len + 1 rows and accepts the longest prefix the model would have produced itself (k_spec_accept: cut at the
-// stop token and at max_tokens, appended to the history).  The batched kernels take the position as a launch argument, so the host reads the step's result block -- m and the ids,
-// one trip -- before it enqueues the next step: ONE synchronisation per step.  Where a batch would run past max_seq_len, or fewer than 2 ids are still wanted, the step is an
-// ordinary one-launch greedy token.  Every step is re-runnable (its inputs are the history below n_hist and launch arguments), which is what the retry wrapper needs.
-int flm_generate_lookup(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, int max_tokens, int32_t stop_token, int draft_len, int ngram_max,
-                        flm_token_cb cb, void* user, int32_t* out_tokens, int* n_out) {
+// flm_generate with several ids per pass over the weights: the prompt enters as in flm_forward_argmax / flm_forward_sample (token 0 is drawn from its last logits, with the
+// first coin); then every step drafts draft_len tokens ON THE DEVICE from the call's history (k_spec_draft), verifies them in one batch of draft_len + 1 rows and accepts the
+// longest prefix the model would have produced itself (k_spec_accept_sample: cut at the stop token and at max_tokens, appended to the history).  The batched kernels take the
+// position as a launch argument, so the host reads the step's result block -- m, the ids and the state after the draws it delivers, one trip -- before it enqueues the next
+// step: ONE synchronisation per step.  Where a batch would run past max_seq_len, or fewer than 2 ids are still wanted, the step is an ordinary one-launch greedy token or the
+// sampled token graph (k_sample_advance reads the device parameter block, written from the host's state first) and the accept kernel with K = 0.  Every step is re-runnable:
+// its inputs are the history below n_hist and launch arguments -- n_hist, room and the state the HOST holds at the step's start, so a re-run step draws the same coins --,
+// which is what the retry wrapper needs.  The caller's state is written once, at the end.
+static int generate_lookup_impl(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, int max_tokens, float temperature, float topp, uint64_t* rng_state,
+                                int32_t stop_token, int draft_len, int ngram_max, flm_token_cb cb, void* user, int32_t* out_tokens, int* n_out) {
     if (!c || !prompt || !n_out) return FLM_ERR_INVALID;
-    if (c->world > 1 || (c->comm && c->force_tp)) return fail(c, FLM_ERR_UNSUPPORTED, "generate_lookup: one GPU only");
-    if (max_tokens < 1 || stop_token >= c->d.vocab_size || draft_len < 4 || draft_len > 15 || ngram_max < 1 || ngram_max > 8)
-        return fail(c, FLM_ERR_INVALID, "generate_lookup: max_tokens >= 1, stop_token < vocab_size (or -1), 4 <= draft_len <= 15, 1 <= ngram_max <= 8");
+    if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "generate_lookup: one GPU only");
+    if (max_tokens < 1 || !(temperature >= 0.0f) || topp != topp || stop_token >= c->d.vocab_size || draft_len < 4 || draft_len > 15 || ngram_max < 1 || ngram_max > 8)
+        return fail(c, FLM_ERR_INVALID, "generate_lookup: max_tokens >= 1, temperature >= 0, stop_token < vocab_size (or -1), 4 <= draft_len <= 15, 1 <= ngram_max <= 8");
     int r = check_ready(c, n_prompt, pos); if (r) return r;
     if (pos + n_prompt + max_tokens - 1 > c->d.max_seq_len || max_tokens > c->out_cap) return fail(c, FLM_ERR_INVALID, "generate_lookup: pos + n_prompt + max_tokens - 1 exceeds max_seq_len");
-    for (int i = 0; i < n_prompt; ++i) if (prompt[i] < 0 || prompt[i] >= c->d.vocab_size) return fail(c, FLM_ERR_INVALID, "token id out of range");
+    if (!ids_in_vocab(c, prompt, n_prompt)) return fail(c, FLM_ERR_INVALID, "token id out of range");
+    const bool sampled = temperature != 0.0f;
+    if (sampled) { r = sample_args_ok(c, temperature, topp, rng_state); if (r) return r; }
     const int stop = stop_token < 0 ? -1 : stop_token;
     int total = 0, steps = 0, accepted = 0; bool done = false, cancelled = false;
     int32_t last_tok = 0;
+    uint64_t state = sampled ? *rng_state : 0;                       // the sampler's state behind the ids delivered so far
+    const Draw dr(temperature, topp, &state);                        // (arms a token graph from THAT state)
     SpecOut so{};
-    auto deliver = [&]() {                       // the step's ids, in index order, on this thread
+    auto deliver = [&]() {                       // the step's ids, in index order, on this thread; the state moves with them
         for (int i = 0; i < so.n_emit; ++i) {
             const int index = total + i;
             const bool last = i + 1 == so.n_emit && (so.stopped || index + 1 == max_tokens);
             if (out_tokens) out_tokens[index] = so.ids[i];
             if (cb && !cancelled && cb(user, index, so.ids[i], last ? 1 : 0) != 0) cancelled = true;
         }
-        total += so.n_emit; last_tok = so.ids[so.n_emit - 1];
+        total += so.n_emit; last_tok = so.ids[so.n_emit - 1]; state = so.rng;
         done = so.stopped || total >= max_tokens || cancelled;
     };
-    // token 0: the prompt, exactly as flm_forward_argmax feeds it; the history starts as the prompt and that id
+    // token 0: the prompt, exactly as flm_forward_argmax / flm_forward_sample feeds it; the history starts as the prompt and that id
     r = with_retry(c, n_prompt, [&]() -> int {
-        int r = feed(c, prompt, n_prompt, pos, 1); if (r) return r;
-        hipLaunchKernelGGL(k_spec_begin, dim3(1), dim3(256), 0, c->stream, c->spec_hist, (const int*)c->prompt_dev, n_prompt, (const int*)c->out_tokens_dev, c->spec_out, stop);
+        int r = dr.arm(c); if (r) return r;
+        r = feed(c, prompt, n_prompt, pos, dr.form); if (r) return r;
+        hipLaunchKernelGGL(k_spec_begin, dim3(1), dim3(256), 0, c->stream, c->spec_hist, (const int*)c->prompt_dev, n_prompt, (const int*)c->out_tokens_dev, c->spec_res, stop, (unsigned long long)state, sampled ? 1 : 0);
         HIPC(c, hipGetLastError());
-        return d2h(c, &so, c->spec_out, sizeof so);
+        return d2h(c, &so, c->spec_res, sizeof so);
     }, deliver);
     if (r) return r;
     while (!done) {
@@ -1534,119 +1547,31 @@ int flm_generate_lookup(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos
         const bool batch = room >= 2 && at + draft_len + 1 <= c->d.max_seq_len;
         r = with_retry(c, batch ? draft_len + 1 : 1, [&]() -> int {
             int r;
-            if (batch) r = spec_step(c, at, draft_len, ngram_max, n_hist, stop, room, true);
-            else {
+            if (batch) r = spec_step(c, at, draft_len, ngram_max, n_hist, stop, room, true, SpecDraw{temperature, topp, (unsigned long long)state});
+            else {      // one token through the token graph and the accept kernel with K = 0: the id from the decode state's first output slot, cut / appended / counted like a verified run of one
+                r = dr.arm(c); if (r) return r;
                 r = set_state(c, at, last_tok, 0); if (r) return r;
-                r = run_token(c, true, 1, at + 1); if (r) return r;
-                hipLaunchKernelGGL(k_spec_accept, dim3(1), dim3(64), 0, c->stream, c->spec_out, (const int*)c->out_tokens_dev, (const int*)c->prompt_dev, 0, c->spec_hist, n_hist, stop, room);
+                r = run_token(c, true, dr.form, at + 1); if (r) return r;
+                hipLaunchKernelGGL(k_spec_accept_sample, dim3(1), dim3(64), 0, c->stream, c->spec_res, (const int*)c->out_tokens_dev, (const int*)c->prompt_dev, 0, c->spec_hist, n_hist, stop, room, (unsigned long long)state, sampled ? 1 : 0);
                 r = hipGetLastError() == hipSuccess ? FLM_OK : fail(c, FLM_ERR_HIP, "generate_lookup: launch failed");
             }
             if (r) return r;
-            return d2h(c, &so, c->spec_out, sizeof so);
+            return d2h(c, &so, c->spec_res, sizeof so);
         }, [&] { if (batch) { steps += 1; accepted += so.n_emit - 1; } deliver(); });
-        if (r) return r;
-    }
-    *n_out = total;
-    c->spec_steps = steps; c->spec_accepted = accepted;
-    return FLM_OK;
-}
-
-// Sampled draft-and-verify (include/flm_gpu.h).  The sampler is a function of (logits, the coin), the coin of the sampled decode loop's i-th token is the i-th draw of its
-// xorshift state, and a batched row's logits are flm_forward's bits: so row i of a verify batch, drawn with the (i + 1)-th coin of the step's state (k_sample_rows: the draw
-// k_sample_advance makes, one function), is the id the loop draws behind rows 0 .. i - 1 -- as long as the drafts were those ids.  The accept step cuts at the first draft that
-// differs and leaves the state after as many draws as ids it delivers (k_spec_accept_sample); the coins drawn for the rows behind the cut are simply not counted.  Equality with
-// flm_decode_sample, not rejection sampling.  Temperature 0: the greedy form's kernels (first maxima, no coin, the state untouched).
-int flm_verify_sample(flm_ctx* c, int32_t first_token, const int32_t* drafts, int k, int pos, float temperature, float topp, uint64_t* rng_state, int32_t* out_tokens, int* n_out) {
-    if (!c || !drafts || !out_tokens || !n_out) return fail(c, FLM_ERR_INVALID, "verify: null argument");
-    if (c->world > 1 || (c->comm && c->force_tp)) return fail(c, FLM_ERR_UNSUPPORTED, "verify: one GPU only");
-    if (k < 4 || k > 15) return fail(c, FLM_ERR_INVALID, "verify: 4 <= k <= 15 drafts");
-    if (!(temperature >= 0.0f) || topp != topp) return fail(c, FLM_ERR_INVALID, "verify: temperature must be >= 0, top-p a number");
-    int r = check_ready(c, k + 1, pos); if (r) return r;
-    const int V = c->d.vocab_size;
-    if (first_token < 0 || first_token >= V) return fail(c, FLM_ERR_INVALID, "token id out of range");
-    for (int i = 0; i < k; ++i) if (drafts[i] < 0 || drafts[i] >= V) return fail(c, FLM_ERR_INVALID, "verify: draft outside [0, vocab)");
-    const bool sampled = temperature != 0.0f;
-    if (sampled) { r = sample_args_ok(c, temperature, topp, rng_state); if (r) return r; }
-    SpecOutSample so{};
-    return with_retry(c, k + 1, [&]() -> int {
-        int32_t* b = c->gen_ids.data();                                               // (pageable staging of max_seq_len ids, there since create)
-        b[0] = first_token; for (int i = 0; i < k; ++i) b[1 + i] = drafts[i];
-        int r = h2d(c, c->prompt_dev, b, sizeof(int) * (size_t)(k + 1)); if (r) return r;
-        const SpecDraw draw{temperature, topp, sampled ? (unsigned long long)*rng_state : 0ull};
-        r = spec_step(c, pos, k, 0, 0, -1, k + 1, false, &draw); if (r) return r;
-        return d2h(c, &so, c->spec_out_s, sizeof so);                                 // (the ids and the state in one trip; the error word rides along)
-    }, [&] {
-        memcpy(out_tokens, so.o.ids, sizeof(int32_t) * (size_t)so.o.n_emit);
-        *n_out = so.o.n_emit;
-        if (sampled) { *rng_state = so.rng; c->sampled += so.o.n_emit; }
-    });
-}
-
-// flm_generate_lookup at any temperature: the same loop, the same drafter, the same history; token 0 is drawn from the prompt's last logits with the first coin (the sampled token
-// graph, as in flm_forward_sample), every step draws its rows with the coins of the state the HOST holds at the step's start -- a launch argument, like n_hist and room, so a
-// re-run step draws the same coins -- and brings back the state after the draws it delivered, in the block that carries the ids.  A single-token step is the sampled token graph
-// (k_sample_advance reads the device parameter block, written from the host's state first) and the accept kernel with K = 0.
-int flm_generate_lookup_sample(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, int max_tokens, float temperature, float topp, uint64_t* rng_state,
-                               int32_t stop_token, int draft_len, int ngram_max, flm_token_cb cb, void* user, int32_t* out_tokens, int* n_out) {
-    if (!c || !prompt || !n_out) return FLM_ERR_INVALID;
-    if (c->world > 1 || (c->comm && c->force_tp)) return fail(c, FLM_ERR_UNSUPPORTED, "generate_lookup: one GPU only");
-    if (max_tokens < 1 || !(temperature >= 0.0f) || topp != topp || stop_token >= c->d.vocab_size || draft_len < 4 || draft_len > 15 || ngram_max < 1 || ngram_max > 8)
-        return fail(c, FLM_ERR_INVALID, "generate_lookup: max_tokens >= 1, temperature >= 0, stop_token < vocab_size (or -1), 4 <= draft_len <= 15, 1 <= ngram_max <= 8");
-    int r = check_ready(c, n_prompt, pos); if (r) return r;
-    if (pos + n_prompt + max_tokens - 1 > c->d.max_seq_len || max_tokens > c->out_cap) return fail(c, FLM_ERR_INVALID, "generate_lookup: pos + n_prompt + max_tokens - 1 exceeds max_seq_len");
-    for (int i = 0; i < n_prompt; ++i) if (prompt[i] < 0 || prompt[i] >= c->d.vocab_size) return fail(c, FLM_ERR_INVALID, "token id out of range");
-    const bool sampled = temperature != 0.0f;
-    if (sampled) { r = sample_args_ok(c, temperature, topp, rng_state); if (r) return r; }
-    const int stop = stop_token < 0 ? -1 : stop_token, advance = sampled ? 3 : 1;
-    int total = 0, steps = 0, accepted = 0; bool done = false, cancelled = false;
-    int32_t last_tok = 0;
-    unsigned long long state = sampled ? (unsigned long long)*rng_state : 0ull;      // the sampler's state behind the ids delivered so far
-    SpecOutSample so{};
-    auto deliver = [&]() {                       // the step's ids, in index order, on this thread; the state moves with them
-        for (int i = 0; i < so.o.n_emit; ++i) {
-            const int index = total + i;
-            const bool last = i + 1 == so.o.n_emit && (so.o.stopped || index + 1 == max_tokens);
-            if (out_tokens) out_tokens[index] = so.o.ids[i];
-            if (cb && !cancelled && cb(user, index, so.o.ids[i], last ? 1 : 0) != 0) cancelled = true;
-        }
-        total += so.o.n_emit; last_tok = so.o.ids[so.o.n_emit - 1]; state = so.rng;
-        done = so.o.stopped || total >= max_tokens || cancelled;
-    };
-    // one token through the token graph and the accept kernel with K = 0: the id from the decode state's first output slot, cut / appended / counted like a verified run of one
-    auto accept_one = [&](int n_hist, int room) -> int {
-        hipLaunchKernelGGL(k_spec_accept_sample, dim3(1), dim3(64), 0, c->stream, c->spec_out_s, (const int*)c->out_tokens_dev, (const int*)c->prompt_dev, 0, c->spec_hist, n_hist, stop, room, state, sampled ? 1 : 0);
-        if (hipGetLastError() != hipSuccess) return fail(c, FLM_ERR_HIP, "generate_lookup: launch failed");
-        return d2h(c, &so, c->spec_out_s, sizeof so);
-    };
-    // token 0: the prompt, exactly as flm_forward_sample (flm_forward_argmax) feeds it; the history starts as the prompt and that id
-    r = with_retry(c, n_prompt, [&]() -> int {
-        int r = sampled ? set_sample(c, temperature, topp, state) : FLM_OK; if (r) return r;
-        r = feed(c, prompt, n_prompt, pos, advance); if (r) return r;
-        hipLaunchKernelGGL(k_spec_begin, dim3(1), dim3(256), 0, c->stream, c->spec_hist, (const int*)c->prompt_dev, n_prompt, (const int*)c->out_tokens_dev, &c->spec_out_s->o, stop);
-        HIPC(c, hipGetLastError());
-        return accept_one(n_prompt, max_tokens);
-    }, deliver);
-    if (r) return r;
-    while (!done) {
-        const int at = pos + n_prompt + total - 1, room = max_tokens - total, n_hist = n_prompt + total;       // the last id is fed at `at`
-        const bool batch = room >= 2 && at + draft_len + 1 <= c->d.max_seq_len;
-        r = with_retry(c, batch ? draft_len + 1 : 1, [&]() -> int {
-            if (batch) {
-                const SpecDraw draw{temperature, topp, state};
-                int r = spec_step(c, at, draft_len, ngram_max, n_hist, stop, room, true, &draw); if (r) return r;
-                return d2h(c, &so, c->spec_out_s, sizeof so);
-            }
-            int r = sampled ? set_sample(c, temperature, topp, state) : FLM_OK; if (r) return r;
-            r = set_state(c, at, last_tok, 0); if (r) return r;
-            r = run_token(c, true, advance, at + 1); if (r) return r;
-            return accept_one(n_hist, room);
-        }, [&] { if (batch) { steps += 1; accepted += so.o.n_emit - 1; } deliver(); });
         if (r) return r;
     }
     *n_out = total;
     if (sampled) { *rng_state = state; c->sampled += total; }
     c->spec_steps = steps; c->spec_accepted = accepted;
     return FLM_OK;
+}
+int flm_generate_lookup(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, int max_tokens, int32_t stop_token, int draft_len, int ngram_max,
+                        flm_token_cb cb, void* user, int32_t* out_tokens, int* n_out) {
+    return generate_lookup_impl(c, prompt, n_prompt, pos, max_tokens, 0.0f, 0.0f, nullptr, stop_token, draft_len, ngram_max, cb, user, out_tokens, n_out);
+}
+int flm_generate_lookup_sample(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, int max_tokens, float temperature, float topp, uint64_t* rng_state,
+                               int32_t stop_token, int draft_len, int ngram_max, flm_token_cb cb, void* user, int32_t* out_tokens, int* n_out) {
+    return generate_lookup_impl(c, prompt, n_prompt, pos, max_tokens, temperature, topp, rng_state, stop_token, draft_len, ngram_max, cb, user, out_tokens, n_out);
 }
 
 // the ids the last flm_decode_greedy / flm_decode_sample / flm_decode_timed* call generated (still in device memory): out[n]
@@ -1667,7 +1592,7 @@ int flm_decode_timed_each(flm_ctx* c, int32_t first_token, int pos, int n_steps,
     for (auto& x : ev.e) HIPC(c, hipEventCreate(&x));
     r = set_state(c, pos, first_token, 0); if (r) return r;
     HIPC(c, hipEventRecord(ev.e[0], c->stream));
-    for (int i = 0; i < n_steps; ++i) { r = run_token(c, true, 1, pos + i + 1); if (r) return r; HIPC(c, hipEventRecord(ev.e[i + 1], c->stream)); }
+    for (int i = 0; i < n_steps; ++i) { r = run_token(c, true, TokenForm::Greedy, pos + i + 1); if (r) return r; HIPC(c, hipEventRecord(ev.e[i + 1], c->stream)); }
     HIPC(c, hipEventSynchronize(ev.e[n_steps]));
     for (int i = 0; i < n_steps; ++i) HIPC(c, hipEventElapsedTime(&ms_each[i], ev.e[i], ev.e[i + 1]));
     r = xwg_check(c);

@@ -1,6 +1,6 @@
 // flm_host.h -- what the translation units of libflm_gpu.so share on the HOST side: the context, the launch planning of the GEMV and the entry points of one
 // translation unit that another one calls.
-//   flm_gpu.hip          context, upload, options, p2p bootstrap, the model-level C ABI (forward / decode / debug taps), run_token
+//   flm_gpu.hip          context, upload, options, p2p bootstrap, the model-level C ABI (forward / decode / generate / score / draft-and-verify / debug taps), run_token
 //   flm_token.hip        the per-token launch sequence (enqueue_token), the per-phase and fused decode launches, per-kernel timing (flm_kernel_times / _bytes)
 //   flm_layerlaunch.hip  the whole-layer launch k_attn_ffn (flm_layer.h)
 //   flm_prompt.hip       the batched prompt path (GEMM tiles on the matrix cores, prompt attention)
@@ -21,6 +21,7 @@
 #include <map>
 #include <string>
 #include <mutex>
+#include <tuple>
 #include <vector>
 
 namespace fh {
@@ -40,6 +41,15 @@ struct TimedLaunch { int kclass; hipEvent_t e0, e1; };
 // owners that release on every exit path (the error macros return from the middle of a function)
 struct DevMem { void* p = nullptr; ~DevMem() { if (p) hipFree(p); } };
 struct EvPair { hipEvent_t e0 = nullptr, e1 = nullptr; ~EvPair() { if (e0) hipEventDestroy(e0); if (e1) hipEventDestroy(e1); } };
+// What a token does behind its layers (enqueue_token):
+//   Logits   the classifier's logits stay for the caller, the decode state is left alone
+//   Greedy   tok <- the first maximum (k_argmax_advance, or the one-launch token), pos++
+//   Prompt   a prompt token in front of the last one: no classifier, the state moves on to the next prompt id
+//   Sampled  tok <- k_sample_advance on the logits, pos++
+//   Shaped   k_shape_logits, then the sampler (the argmax where the vocabulary is beyond the sampler) on the shaped row, pos++
+enum class TokenForm { Logits, Greedy, Prompt, Sampled, Shaped };
+// a cached token graph: n token sequences (with_cls, form) for G workgroups per head
+using GraphKey = std::tuple<bool, TokenForm, int, int>;
 
 
 } // namespace fh
@@ -159,14 +169,14 @@ struct flm_ctx {
     // flm_score_tokens (flm_gpu.hip; the classifier stage: flm_prompt.hip): the rows' targets and statistics in device memory [max_seq_len] (allocated at create), and the
     // classifier's scales group-major (cls.st) for the GEMM tiles, transposed once per set of weights
     int* score_tgt = nullptr; flm::ScoreRow* score_dev = nullptr; bool cls_st_ready = false;
-    // flm_verify_greedy / flm_generate_lookup (flm_gpu.hip; kernels: flm_spec.h): the call's token history [max_seq_len + 32], the batch rows' first maxima [16] and the step's
-    // result block, device memory since create; which GEMM the verify pass runs; the last call's figures ("spec_steps" / "spec_accepted")
-    int* spec_hist = nullptr; int* spec_arg = nullptr; flm::SpecOut* spec_out = nullptr;
-    flm::SpecOutSample* spec_out_s = nullptr;          // flm_verify_sample / flm_generate_lookup_sample: their step's result block (the ids and the sampler's state behind them, one trip)
+    // draft-and-verify, greedy and sampled (flm_gpu.hip verify_impl / generate_lookup_impl; kernels: flm_spec.h): the call's token history [max_seq_len + 32], the batch rows'
+    // ids [16] (first maxima or draws) and the step's result block (the accepted ids and the sampler's state behind them, one trip), device memory since create; which GEMM
+    // the verify pass runs; the last call's figures ("spec_steps" / "spec_accepted")
+    int* spec_hist = nullptr; int* spec_arg = nullptr; flm::SpecOut* spec_res = nullptr;
     int spec_gemm = 0;                                 // option "spec_gemm": 1 = the verify pass's int8 GEMMs through k_gemm_q8_skinny (B <= 16), 0 (default until both forms have been timed: DESIGN.md section 5e) = the 64 x 64 tiles; the new entry points only
     int spec_steps = 0, spec_accepted = 0;
     int score_rows = 0;                                // option "score_rows": rows per classifier chunk of flm_score_tokens (0: as many as the staging holds; < 0: one row at a time through c->logits)
-    std::map<int, hipGraphExec_t> graphs;             // key = with_cls*4 + advance (3: sampled; the shaped form: 3 + bit 27)
+    std::map<GraphKey, hipGraphExec_t> graphs;        // the token graphs captured so far (flm_gpu.hip token_graph)
     std::vector<TimedLaunch>* timing = nullptr;
     std::vector<void*> owned;                          // every device allocation that lives as long as the context (flm_gpu.hip dev_alloc); flm_ctx_destroy frees these
     std::string err;
@@ -264,17 +274,35 @@ int launch_layers(flm_ctx* c, hipStream_t st, int l0, int l1, int G, bool tail =
 // one activation exchange between the tensor-parallel ranks (flm_token.hip)
 enum XKind { XK_ATT = 0, XK_X1 = 1, XK_HD = 2, XK_LOGITS = 3 };
 int exchange(flm_ctx* c, hipStream_t st, int kind, float* full, float* mine, int count);
-constexpr int kAdvShaped = 4;                         // enqueue_token's advance: classifier, k_shape_logits, then the sampler (the argmax where the vocabulary is beyond the sampler) on the shaped row
-int enqueue_token(flm_ctx* c, hipStream_t st, bool with_cls, int advance, int G);
+int enqueue_token(flm_ctx* c, hipStream_t st, bool with_cls, TokenForm form, int G);
 // flm_sampling -> the shaper's parameter block (flm_gpu.hip): validates everything include/flm_gpu.h lists (null on success, else what is wrong); window[n_window] becomes the
 // block's head; *active: some control is not neutral.  follow: flm_generate_ex's sliding window (penalty_last_n), else the window as given
 const char* shape_fill(const flm_sampling* sp, int vocab, const int32_t* window, int n_window, bool follow, flm::ShapeParams* out, bool* active);
-int run_token(flm_ctx* c, bool with_cls, int advance, int T);
+int run_token(flm_ctx* c, bool with_cls, TokenForm form, int T);
 // the device sampler's LDS fits one workgroup (vocab up to ~36 K); beyond it the sampled entry points refuse (FLM_ERR_UNSUPPORTED) and a caller samples on the host
 inline bool sample_supported(const flm_ctx* c) { return c->d.vocab_size >= 2 && sample_lds_bytes(c->d.vocab_size) <= kLdsMax; }
 int set_state(flm_ctx* c, int pos, int tok, int step);
 // the decode state's latch as the single-GPU token launches receive it (flm_math.h DecodeState::halt); the tensor-parallel launch forms get none and run unconditionally
-inline const int* halt_ptr(const flm_ctx* c) { return (c->world > 1 || (c->comm != nullptr && c->force_tp)) ? nullptr : &c->state->halt; }
+// this context runs the sharded (tensor-parallel) token path; a 1-rank communicator takes it only on request ("force_tp")
+inline bool sharded(const flm_ctx* c) { return c->world > 1 || (c->comm != nullptr && c->force_tp); }
+inline const int* halt_ptr(const flm_ctx* c) { return sharded(c) ? nullptr : &c->state->halt; }
+// ids[0 .. n) lie in [0, vocab)
+inline bool ids_in_vocab(const flm_ctx* c, const int32_t* ids, int n) {
+    for (int i = 0; i < n; ++i) if (ids[i] < 0 || ids[i] >= c->d.vocab_size) return false;
+    return true;
+}
+// How a call's tokens are drawn: the token form, the sampler's parameters, the caller's xorshift state and, for the shaped form, the shaper's parameter block (flm_gpu.hip)
+struct Draw {
+    TokenForm form; float temperature, topp; uint64_t* rng_state; const flm::ShapeParams* shape;
+    unsigned long long after = 0;                                 // the state an attempt left on the device (fetch); the caller's changes only behind a verified attempt (commit)
+    // Greedy / Sampled by temperature, Shaped where a block is given
+    Draw(float t, float p, uint64_t* st, const flm::ShapeParams* sh = nullptr) : form(sh ? TokenForm::Shaped : t != 0.0f ? TokenForm::Sampled : TokenForm::Greedy), temperature(t), topp(p), rng_state(st), shape(sh) {}
+    Draw(TokenForm f, float t, float p, uint64_t* st) : form(f), temperature(t), topp(p), rng_state(st), shape(nullptr) {}
+    bool coins() const { return form == TokenForm::Sampled || (form == TokenForm::Shaped && temperature != 0.0f); }   // the caller's state is read and moved on
+    int arm(flm_ctx* c) const;             // an attempt's start: the shaper's block, then the sampler's parameters FROM THE CALLER'S STATE -- a retried attempt draws nothing twice
+    int fetch(flm_ctx* c);                 // an attempt's end: the state behind its draws comes back
+    void commit(flm_ctx* c, int n) const;  // a verified attempt of n tokens: the caller's state, "sampled_tokens" / "shaped_tokens"
+};
 int check_ready(flm_ctx* c, int n, int pos);
 constexpr int kPrefillMin = 4;
 int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers = false, bool skinny = false);      // (flm_prompt.hip; by the model's quant type.  all_layers: the last layer is completed too -- flm_score_tokens needs every row's final residual; skinny: int8 and B <= 16: every GEMM through k_gemm_q8_skinny -- the verify pass under "spec_gemm" 1)
@@ -282,9 +310,9 @@ int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers = false, bool
 // `stage` [m][vocab], k_score_rows into score_dev[row0 ..]
 int score_classify(flm_ctx* c, int row0, int m, float* stage);
 // the verify pass's classifier stage (flm_prompt.hip): score_classify's prologue and GEMM (skinny: k_gemm_q8_skinny), then k_argmax_rows into argmax_out[row0 ..]
-// (draw: the sampled verify pass -- temperature, top-p and the step's xorshift state: k_sample_rows draws row row0 + i with that state's (row0 + i + 1)-th coin; null or temperature 0: k_argmax_rows)
+// (draw: temperature, top-p and the step's xorshift state: k_sample_rows draws row row0 + i with that state's (row0 + i + 1)-th coin; temperature 0: k_argmax_rows)
 struct SpecDraw { float temperature, topp; unsigned long long base; };
-int spec_classify(flm_ctx* c, int row0, int m, float* stage, bool skinny, int* argmax_out, const SpecDraw* draw = nullptr);
+int spec_classify(flm_ctx* c, int row0, int m, float* stage, bool skinny, int* argmax_out, const SpecDraw& draw);
 // k_sample_rows on `rows` <= 16 rows of n logits, ld floats apart, batch rows row0 ..; sort_buf [rows][2][n] (flm_prompt.hip; c may be null: flm_op_sample_rows)
 int launch_sample_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, int n, int row0, int rows, float temperature, float topp, unsigned long long base,
                        unsigned long long* sort_buf, int* out);

@@ -43,9 +43,10 @@
 //   k_sample_advance      (flm_sample.h) Sampler::sample on the device -- temperature, clipped softmax, xorshift coin, multinomial / top-p -- bit for bit: the sampled token's
 //                         last launch in place of k_argmax_advance (flm_forward_sample / flm_decode_sample, the per-phase tail: k_embed + k_layers + k_gemv(cls) + k_sample_advance)
 //   k_sample_rows         (flm_sample.h) the same draw (sample_draw, one __device__ function for both) over the rows of a verify batch, row i with the (i + 1)-th coin of the step's
-//                         state; k_spec_accept_sample (flm_spec.h) leaves the state after the delivered ids' draws: flm_verify_sample / flm_generate_lookup_sample
+//                         state: flm_verify_sample / flm_generate_lookup_sample
 //   k_gemm_q8_skinny      (flm_prefill.h) the int8 GEMM for <= 16 tokens on v_mfma_i32_16x16x64_i8, weights straight from global memory: the verify pass of draft-and-verify
-//   k_spec_draft, k_argmax_rows, k_spec_accept  (flm_spec.h) the prompt-lookup drafter, the per-row first-maximum argmax and the accept step of flm_verify_greedy / flm_generate_lookup
+//   k_spec_draft, k_argmax_rows, k_spec_begin, k_spec_accept_sample  (flm_spec.h) draft-and-verify, greedy and sampled: the prompt-lookup drafter, the per-row first-maximum argmax
+//                         (temperature 0), the history's start and the accept step, which leaves the accepted ids and the sampler's state after their draws in one block
 //   k_score_rows          (flm_score.h) per row of a block of logits: first-maximum argmax, the clipped softmax's max / exact sequential sum, the target's logit and probability
 //                         (flm_score_tokens behind the batched prompt path's classifier GEMM; flm_op_score_rows)
 // plus small op-level kernels that expose the same __device__ functions to the parity tests.

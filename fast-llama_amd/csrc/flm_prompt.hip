@@ -269,8 +269,8 @@ int score_classify(flm_ctx* c, int row0, int m, float* stage) {
 }
 // the verify pass's classifier stage: the same chunk through the same prologue and GEMM (skinny: k_gemm_q8_skinny, int8), then k_argmax_rows into argmax_out[row0 ..]
 // (draw given and its temperature > 0: k_sample_rows in place of k_argmax_rows)
-int spec_classify(flm_ctx* c, int row0, int m, float* stage, bool skinny, int* argmax_out, const SpecDraw* draw) {
-    return c->d.quant_type == FLM_QT_INT8 ? score_classify_t<QT_INT8>(c, row0, m, stage, skinny, argmax_out, draw) : score_classify_t<QT_INT16>(c, row0, m, stage, false, argmax_out, draw);
+int spec_classify(flm_ctx* c, int row0, int m, float* stage, bool skinny, int* argmax_out, const SpecDraw& draw) {
+    return c->d.quant_type == FLM_QT_INT8 ? score_classify_t<QT_INT8>(c, row0, m, stage, skinny, argmax_out, &draw) : score_classify_t<QT_INT16>(c, row0, m, stage, false, argmax_out, &draw);
 }
 
 } // namespace fh

@@ -1,20 +1,23 @@
-// flm_spec.h -- draft-and-verify (flm_verify_greedy / flm_generate_lookup and their sampled forms): the prompt-lookup drafter, the per-row argmax of a batch's logits and the accept
-// step.  Part of flm_kernels.h; include that header.  The weight pass of a verify batch is the prompt path's (flm_prefill.h: the tiles, or k_gemm_q8_skinny).
+// flm_spec.h -- draft-and-verify (flm_verify_greedy / flm_generate_lookup and their sampled forms, one implementation: flm_gpu.hip verify_impl / generate_lookup_impl): the
+// prompt-lookup drafter, the per-row argmax of a batch's logits and the accept step.  Part of flm_kernels.h; include that header.  The weight pass of a verify batch is the
+// prompt path's (flm_prefill.h: the tiles, or k_gemm_q8_skinny).
 //
-// A step: k_spec_draft writes the batch's tokens {h[n - 1], d[0 .. K)}; the batched layer kernels and the classifier produce K + 1 rows of logits; k_argmax_rows
-// reduces row i to a[i], the first maximum (sample_argmax, sampler.cpp:36-47: block_first_max, what k_argmax_advance computes); k_spec_accept keeps a[0 .. m] where m is
-// the first i with a[i] != d[i] -- a[i] is the id the token path would draw behind a[0 .. i), because row i saw exactly those tokens.
-//
-// The sampled form (flm_verify_sample / flm_generate_lookup_sample): k_sample_rows (flm_sample.h) in place of k_argmax_rows -- row i drawn with the (i + 1)-th coin of the
-// step's xorshift state, i.e. Sampler::sample as the sampled decode loop calls it for its i-th token -- and k_spec_accept_sample, which also leaves the state after as many
-// draws as the step delivers ids.  The ids are flm_decode_sample's element for element; nothing is rejected or re-drawn.
+// A step: k_spec_draft writes the batch's tokens {h[n - 1], d[0 .. K)}; the batched layer kernels and the classifier produce K + 1 rows of logits; row i is reduced to
+// a[i]; k_spec_accept_sample keeps a[0 .. m] where m is the first i with a[i] != d[i] -- a[i] is the id the token path would draw behind a[0 .. i), because row i saw
+// exactly those tokens -- and leaves the sampler's state after as many draws as the step delivers ids.
+//   temperature 0: a[i] = the row's first maximum (k_argmax_rows: sample_argmax, sampler.cpp:36-47: block_first_max, what k_argmax_advance computes); no coin, the state
+//                  passes through untouched;
+//   otherwise:     k_sample_rows (flm_sample.h) draws row i with the (i + 1)-th coin of the step's xorshift state, i.e. Sampler::sample as the sampled decode loop calls
+//                  it for its i-th token.  The ids are flm_decode_sample's element for element; nothing is rejected or re-drawn.
 #pragma once
 #include "flm_sample.h"
 
 namespace flm {
 
-// what a step leaves for the host, read back in ONE trip: the accepted run ids[0 .. n_emit)
-struct SpecOut { int m; int n_emit; int stopped; int pad; int ids[16]; };
+// what a step leaves for the host, read back in ONE trip: the accepted run ids[0 .. n_emit) and the sampler's state after exactly n_emit draws -- one per id the step
+// delivers, so the next step's row 0 draws with the coin the sampled decode loop uses for that token.  (Not m + 1 draws: `room` and the stop token can cut the run
+// shorter; the rows behind the cut drew coins the loop never does.)  Temperature 0: the state the step started from.
+struct SpecOut { int m; int n_emit; int stopped; int pad; int ids[16]; unsigned long long rng; };
 
 // The prompt-lookup drafter over the token history h[0 .. n), n >= 1 (host restatement: host/spec_draft.h, pinned by tests/test_spec_host.py):
 //   for g = min(ngram_max, n - 1) down to 1: the LARGEST j with j + g <= n - 1 and h[j .. j + g) == h[n - g .. n); the first g with a match wins, period p = n - g - j;
@@ -56,37 +59,31 @@ inline __global__ void __launch_bounds__(kSampleBlock) k_argmax_rows(const float
 
 // The accept step (one thread): m = the first i < K with a[i] != batch[1 + i] (K if none); the run a[0 .. m] is cut to `room` ids (what the call may still deliver)
 // and behind the first `stop` id (-1: none), stored into out->ids and, where hist is given, appended at hist[n_hist ..).  K = 0: one id from a single-token launch.
-// n_hist and room come from the host (it learns m every step), so a step that is re-run stores the same words again.
-__device__ __forceinline__ int spec_accept(SpecOut* out, const int* __restrict__ a, const int* __restrict__ batch, int K, int* hist, int n_hist, int stop, int room) {
+// out->rng = base after n_emit steps of the xorshift state when `draws`, else base.  n_hist, room and base (the state at the step's start) come from the host (it learns m
+// every step), so a step that is re-run stores the same words again.
+inline __global__ void k_spec_accept_sample(SpecOut* out, const int* __restrict__ a, const int* __restrict__ batch, int K, int* hist, int n_hist, int stop, int room,
+                                            unsigned long long base, int draws) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
     int m = 0;
     while (m < K && a[m] == batch[1 + m]) ++m;
     int n = m + 1 < room ? m + 1 : room, stopped = 0;
     for (int i = 0; i < n; ++i) if (a[i] == stop) { n = i + 1; stopped = 1; break; }
     for (int i = 0; i < n; ++i) { const int id = a[i]; out->ids[i] = id; if (hist) hist[n_hist + i] = id; }
     out->m = m; out->n_emit = n; out->stopped = stopped; out->pad = 0;
-    return n;
-}
-inline __global__ void k_spec_accept(SpecOut* out, const int* __restrict__ a, const int* __restrict__ batch, int K, int* hist, int n_hist, int stop, int room) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    (void)spec_accept(out, a, batch, K, hist, n_hist, stop, room);
-}
-// The sampled step's result block: SpecOut, and behind it the sampler's state after exactly n_emit draws -- one per id the step delivers, so the next step's row 0 draws
-// with the coin the sampled decode loop uses for that token.  (Not m + 1 draws: `room` and the stop token can cut the run shorter; the rows behind the cut drew coins the
-// loop never does.)  base: the state at the step's start, a launch argument like n_hist and room -- a step that is re-run stores the same words again.
-// draws = 0 (temperature 0: the rows are first maxima, no coin): rng = base.
-struct SpecOutSample { SpecOut o; unsigned long long rng; };
-inline __global__ void k_spec_accept_sample(SpecOutSample* out, const int* __restrict__ a, const int* __restrict__ batch, int K, int* hist, int n_hist, int stop, int room,
-                                            unsigned long long base, int draws) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const int n = spec_accept(&out->o, a, batch, K, hist, n_hist, stop, room);
     unsigned long long s = base;
     if (draws) for (int i = 0; i < n; ++i) s = sample_step(s);
     out->rng = s;
 }
-// flm_generate_lookup's start: the history = the prompt and the id drawn from its last logits (tok0[0], the decode state's first output slot)
-inline __global__ void k_spec_begin(int* __restrict__ hist, const int* __restrict__ prompt, int n_prompt, const int* __restrict__ tok0, SpecOut* out, int stop) {
+// flm_generate_lookup's start: the history = the prompt and the id drawn from its last logits (tok0[0], the decode state's first output slot); the whole result block of
+// that one id (the state after its one draw)
+inline __global__ void k_spec_begin(int* __restrict__ hist, const int* __restrict__ prompt, int n_prompt, const int* __restrict__ tok0, SpecOut* out, int stop,
+                                    unsigned long long base, int draws) {
     for (int i = threadIdx.x; i < n_prompt; i += blockDim.x) hist[i] = prompt[i];
-    if (threadIdx.x == 0) { const int id = tok0[0]; hist[n_prompt] = id; out->ids[0] = id; out->m = 0; out->n_emit = 1; out->stopped = id == stop ? 1 : 0; out->pad = 0; }
+    if (threadIdx.x == 0) {
+        const int id = tok0[0];
+        hist[n_prompt] = id; out->ids[0] = id; out->m = 0; out->n_emit = 1; out->stopped = id == stop ? 1 : 0; out->pad = 0;
+        out->rng = draws ? sample_step(base) : base;
+    }
 }
 
 } // namespace flm

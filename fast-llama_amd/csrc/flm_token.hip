@@ -38,7 +38,7 @@ GemvPlan gemv_plan(int n, int esz, int rows, bool two, bool pairs, bool norm, in
 // One token: ParallelTransformer::forward at bs == 1 (transformer.cpp:105-161).
 // Position and token are read from c->state on the device.
 //   with_cls  : run the final norm + classifier (+ argmax)
-//   advance   : 1 = greedy (tok <- argmax, pos++), 0 = leave state (caller copies logits), 2 = prompt feed, 3 = sampled (tok <- k_sample_advance, pos++), 4 = shaped (k_shape_logits in front of the sampler, which reads the shaped row)
+//   form      : what happens behind the layers (flm_host.h TokenForm)
 // ---------------------------------------------------------------------------------------------
 // argument blocks of the five GEMVs and the attention of layer l (shared by the per-phase launches and k_token)
 GemvArgs args_qkv(flm_ctx* c, int l) {
@@ -270,11 +270,11 @@ int exchange(flm_ctx* c, hipStream_t st, int kind, float* full, float* mine, int
     return FLM_OK;
 }
 
-int enqueue_token(flm_ctx* c, hipStream_t st, bool with_cls, int advance, int G) {
+int enqueue_token(flm_ctx* c, hipStream_t st, bool with_cls, TokenForm form, int G) {
     const auto& d = c->d;
     const int qt = d.quant_type, hs = c->hs, L = d.n_layers;
-    const bool tp = c->world > 1 || (c->comm != nullptr && c->force_tp), coh = tp && c->p2p;   // (a 1-rank communicator takes the sharded path only on request: "force_tp")
-    if (!tp && with_cls && advance == 1 && c->fuse_tail && c->fuse_token && c->fuse_layer && c->fuse_back && c->fuse_attn_o && c->fuse_ffn && !c->timing && (c->trace_class < 0 || c->trace_class == 103)) {   // (trace builds, class 103: the stamps of the one-launch token's second layer)
+    const bool tp = sharded(c), coh = tp && c->p2p;
+    if (!tp && with_cls && form == TokenForm::Greedy && c->fuse_tail && c->fuse_token && c->fuse_layer && c->fuse_back && c->fuse_attn_o && c->fuse_ffn && !c->timing && (c->trace_class < 0 || c->trace_class == 103)) {   // (trace builds, class 103: the stamps of the one-launch token's second layer)
         // a greedy decode token as ONE launch: embedding row, all layers, classifier, argmax + state advance (k_layers<.., TAIL>)
         const int r = launch_layers(c, st, 0, L, G, true);
         if (r != FLM_ERR_UNSUPPORTED) return r;
@@ -372,7 +372,7 @@ layers_done:
             r = launch_gemv<PRO_RMSNORM_QUANT, EPI_STORE>(c, st, qt, folded(traced(args_cls(c), KC_CLS, 0), L - 1, 3), wgs, coh); if (r) return r;
         }
         if (tp) { r = exchange(c, st, XK_LOGITS, c->logits, c->logits + (size_t)c->rank * c->vocab_slot, c->vocab_slot); if (r) return r; }
-        if (advance == kAdvShaped) {   // a shaped token: the shaper writes the shaped row, the sampler (unchanged) draws from it
+        if (form == TokenForm::Shaped) {   // a shaped token: the shaper writes the shaped row, the sampler (unchanged) draws from it
             if (tp) return fail(c, FLM_ERR_UNSUPPORTED, "shaped token: one GPU only");
             ShapeArgs ha{};
             ha.logits = c->logits; ha.out = c->shape_row; ha.n = d.vocab_size; ha.p = c->shape_p; ha.st = c->state; ha.out_tokens = c->out_tokens_dev; ha.out_cap = c->out_cap;
@@ -387,19 +387,19 @@ layers_done:
                 hipLaunchKernelGGL(k_argmax_advance, dim3(1), dim3(1024), 0, st, (const float*)c->shape_row, d.vocab_size, c->state, c->out_tokens_dev, 1, c->out_cap, (const int*)c->xwg_err);
             }
             HIPC(c, hipGetLastError());
-        } else if (advance == 3) {   // a sampled token: every rank samples the same all-gathered logits with the same state and draws the same token
+        } else if (form == TokenForm::Sampled) {   // a sampled token: every rank samples the same all-gathered logits with the same state and draws the same token
             if (!sample_supported(c)) return fail(c, FLM_ERR_UNSUPPORTED, "device sampler: vocabulary too large for one workgroup's LDS");
             Tick t(c, st, KC_ARGMAX);
             SampleArgs sa{};
             sa.logits = c->logits; sa.n = d.vocab_size; sa.sp = c->sparams; sa.st = c->state; sa.out_tokens = c->out_tokens_dev; sa.out_cap = c->out_cap; sa.advance = 1; sa.sort_buf = c->sort_buf; sa.err = c->xwg_err;
             hipLaunchKernelGGL(k_sample_advance, dim3(1), dim3(kSampleBlock), sample_lds_bytes(d.vocab_size), st, sa);
             HIPC(c, hipGetLastError());
-        } else if (advance != 0) {
+        } else if (form != TokenForm::Logits) {
             Tick t(c, st, KC_ARGMAX);
             hipLaunchKernelGGL(k_argmax_advance, dim3(1), dim3(1024), 0, st, (const float*)c->logits, d.vocab_size, c->state, c->out_tokens_dev, 1, c->out_cap, (const int*)c->xwg_err);
             HIPC(c, hipGetLastError());
         }
-    } else if (advance == 2) {
+    } else if (form == TokenForm::Prompt) {
         hipLaunchKernelGGL(k_advance_prompt, dim3(1), dim3(64), 0, st, c->state, (const int*)c->prompt_dev);
         HIPC(c, hipGetLastError());
     }
@@ -418,7 +418,7 @@ int flm_kernel_times(flm_ctx* c, int pos, int iters, float* avg_us, int32_t* cou
         for (int it = 0; it < iters + 1; ++it) {
             r = set_state(c, pos, 1 % c->d.vocab_size, 0); if (r) return r;
             std::vector<TimedLaunch> tl; c->timing = &tl;
-            r = enqueue_token(c, c->stream, true, 1, attn_parts(c, pos + 1));
+            r = enqueue_token(c, c->stream, true, TokenForm::Greedy, attn_parts(c, pos + 1));
             c->timing = nullptr;
             hipStreamSynchronize(c->stream);
             for (auto& t : tl) {

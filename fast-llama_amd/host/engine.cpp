@@ -240,15 +240,13 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
             rc = flm_generate_ex(_ctxs[0], input.data(), n_in, 0, want, &sp, &st, 0, on_token, &sink, nullptr, &n_out);
             if (rc == FLM_ERR_INVALID) { _err = flm_last_error(_ctxs[0]); fprintf(stderr, "%s\n", _err.c_str()); }
             whole = false;
-        } else if (_draft_k > 0) {          // --draft: the same loop through draft-and-verify steps at the run's temperature; refused (nothing was launched): the run without the flag
-            rc = greedy ? flm_generate_lookup(_ctxs[0], input.data(), n_in, 0, want, 0, _draft_k, _draft_g, on_token, &sink, nullptr, &n_out)
-                        : flm_generate_lookup_sample(_ctxs[0], input.data(), n_in, 0, want, temperature, topp, &st, 0, _draft_k, _draft_g, on_token, &sink, nullptr, &n_out);
+        } else if (_draft_k > 0 || (greedy && _lookup_k > 0)) {
+            // --draft: the same loop through draft-and-verify steps at the run's temperature; refused (nothing was launched): the run without the flag.
+            // --lookup: the same at temperature 0 only (the same ids and callbacks)
+            const bool draft = _draft_k > 0;
+            rc = flm_generate_lookup_sample(_ctxs[0], input.data(), n_in, 0, want, temperature, topp, &st, 0, draft ? _draft_k : _lookup_k, draft ? _draft_g : _lookup_g, on_token, &sink, nullptr, &n_out);
             count();
-            whole = rc == FLM_ERR_UNSUPPORTED;
-        } else if (greedy && _lookup_k > 0) {      // --lookup: the same loop through draft-and-verify steps (the same ids and callbacks)
-            rc = flm_generate_lookup(_ctxs[0], input.data(), n_in, 0, want, 0, _lookup_k, _lookup_g, on_token, &sink, nullptr, &n_out);
-            count();
-            whole = false;
+            whole = draft && rc == FLM_ERR_UNSUPPORTED;
         }
         if (whole) rc = flm_generate(_ctxs[0], input.data(), n_in, 0, want, temperature, topp, &st, 0, on_token, &sink, nullptr, &n_out);
         if (rc == FLM_OK) { if (!greedy) _sampler.set_state(st); return true; }

@@ -288,6 +288,27 @@ def test_generate_lookup_other_models(gpu, name, gemm):
 
 
 # ---- the contract around the calls -------------------------------------------------------------------------------------------------------------------------------
+def test_a_retried_greedy_lookup_call_delivers_once_per_token(gpu):
+    """after a timed-out cross-workgroup wait (injected: "inject_wait_failure") the step re-runs from the history and counters the host held at its start: the same ids as
+    an undisturbed call and as flm_generate, every index delivered once.  The call ends at max_seq_len, so it includes single-token steps."""
+    cfg, tensors = _model("tiny-int8")
+    prompt, _ = _looping_prompt(gpu)
+    pos, N = MAX_SEQ - len(prompt) - 12 + 1, 12
+    ref = _ctx(gpu, cfg, tensors)
+    ctx = _ctx(gpu, cfg, tensors)
+    a_seen, a_cb = _record(); b_seen, b_cb = _record()
+    want = ref.generate_lookup(prompt, pos, N, draft_len=7, on_token=a_cb)
+    assert ref.query("spec_steps") < N - 1
+    ref.reset_kv()
+    assert np.array_equal(want, ref.generate(prompt, pos, N)[0])
+    ctx.set_option("inject_wait_failure", 1)
+    got = ctx.generate_lookup(prompt, pos, N, draft_len=7, on_token=b_cb)
+    assert np.array_equal(got, want) and len(got) == N
+    assert b_seen == a_seen and [i for i, _, _ in b_seen] == list(range(N))
+    assert ctx.query("fallback") == 1 and ref.query("fallback") == 0
+    ref.close(); ctx.close()
+
+
 def test_nothing_is_allocated_inside_the_new_calls(gpu):
     """the first flm_verify_greedy and flm_generate_lookup of a fresh context, bracketed with hipMemGetInfo: free memory unchanged"""
     hip = ctypes.CDLL("libamdhip64.so")

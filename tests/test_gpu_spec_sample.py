@@ -149,6 +149,20 @@ def test_verify_sample_other_parameters_and_temperature_zero(gpu):
         ctx.reset_kv()
         got, s = ctx.verify_sample(1, drafts, 0, 0.0, 0.9, None)
         assert np.array_equal(got, want) and s is None
+    # ... and flm_generate_lookup_sample is flm_generate_lookup: ids, step counters and callbacks; the state untouched, no token counted as sampled
+    prompt, _ = _looping_prompt(gpu)
+    sampled_before = ctx.query("sampled_tokens")
+    for K in (4, 15):
+        a_seen, a_cb = _record(); b_seen, b_cb = _record()
+        ctx.reset_kv()
+        want = ctx.generate_lookup(prompt, 0, 60, draft_len=K, on_token=a_cb)
+        want_steps = (ctx.query("spec_steps"), ctx.query("spec_accepted"))
+        ctx.reset_kv()
+        got, s = ctx.generate_lookup_sample(prompt, 0, 60, 0.0, 0.9, 3, draft_len=K, on_token=b_cb)
+        assert np.array_equal(got, want) and len(got) == 60 and s == 3, K
+        assert (ctx.query("spec_steps"), ctx.query("spec_accepted")) == want_steps and want_steps[1] > 0, K
+        assert a_seen == b_seen and len(b_seen) == 60, K
+    assert ctx.query("sampled_tokens") == sampled_before
     ctx.close()
 
 
@@ -274,7 +288,7 @@ def test_a_retried_sampled_lookup_call_draws_once_per_token(gpu):
     cfg, tensors = _model("tiny-int8")
     prompt, _ = _looping_prompt(gpu)
     pos, N = MAX_SEQ - len(prompt) - 12 + 1, 12
-    for t, p, s0 in ((1.0, 0.9, 1234), (1.0, 0.9, 0)):
+    for t, p, s0 in ((1.0, 0.9, 1234), (1.0, 0.9, 0), (0.0, 0.9, 3)):
         ref = _ctx(gpu, cfg, tensors)
         ctx = _ctx(gpu, cfg, tensors)
         a_seen, a_cb = _record(); b_seen, b_cb = _record()
