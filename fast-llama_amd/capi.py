@@ -29,6 +29,7 @@ SYMBOLS = (
     "flm_verify_greedy", "flm_generate_lookup", "flm_op_matmul_skinny", "flm_op_spec_draft",
     "flm_verify_sample", "flm_generate_lookup_sample", "flm_op_sample_rows",
     "flm_generate_ex", "flm_forward_sample_ex", "flm_op_shape_logits",
+    "flm_verify_sample_ex", "flm_generate_lookup_ex", "flm_op_shape_rows",
 )
 
 # flm_score (include/flm_gpu.h): one row of flm_score_tokens / flm_op_score_rows
@@ -343,6 +344,43 @@ class Ctx:
         _check(rc, self._h)
         return (out[:n_out.value].copy() if want_ids else np.empty(0, dtype=np.int32)), st.value
 
+    def verify_sample_ex(self, first_token, drafts, pos, sampling, window=(), rng_state=0):
+        """flm_verify_sample_ex -> (the m + 1 ids a flm_forward_sample_ex loop started with first_token at pos draws when it slides `window` over them, m = the drafts that
+        were right; the state after those draws).  rng_state None: a NULL pointer (allowed at temperature 0)."""
+        d = np.ascontiguousarray(drafts, dtype=np.int32)
+        w = np.ascontiguousarray(window, dtype=np.int32)
+        out = np.empty(len(d) + 1, dtype=np.int32); n_out = C.c_int(0)
+        st = None if rng_state is None else C.c_uint64(int(rng_state))
+        sp, keep = sampling.struct()
+        _check(lib().flm_verify_sample_ex(self._h, int(first_token), _p(d), len(d), int(pos), C.byref(sp), _p(w) if w.size else None, int(w.size),
+                                          C.byref(st) if st is not None else None, _p(out), C.byref(n_out)), self._h)
+        del keep
+        return out[:n_out.value].copy(), (st.value if st is not None else None)
+
+    def generate_lookup_ex(self, prompt, pos, max_tokens, sampling, rng_state=0, stop_token=-1, draft_len=7, ngram_max=3, on_token=None, want_ids=True):
+        """flm_generate_lookup_ex -> (ids[n_out], the sampler state after the n_out draws): flm_generate_ex through draft-and-verify steps.
+        on_token(index, token, last) as in generate."""
+        t = np.ascontiguousarray(prompt, dtype=np.int32)
+        out = np.empty(max(int(max_tokens), 1), dtype=np.int32) if want_ids else None
+        st = C.c_uint64(int(rng_state)); n_out = C.c_int(0)
+        sp, keep = sampling.struct()
+        raised = []
+
+        def tramp(_user, index, token, last):
+            try:
+                return 1 if on_token(int(index), int(token), bool(last)) else 0
+            except BaseException as e:      # (an exception must not unwind through the C frames: cancel, re-raise behind the call)
+                raised.append(e)
+                return 1
+        cb = TOKEN_CB(tramp) if on_token is not None else C.cast(None, TOKEN_CB)
+        rc = lib().flm_generate_lookup_ex(self._h, _p(t), len(t), int(pos), int(max_tokens), C.byref(sp), C.byref(st), C.c_int32(int(stop_token)),
+                                          int(draft_len), int(ngram_max), cb, None, _p(out), C.byref(n_out))
+        del cb, keep
+        if raised:
+            raise raised[0]
+        _check(rc, self._h)
+        return (out[:n_out.value].copy() if want_ids else np.empty(0, dtype=np.int32)), st.value
+
     def decode_timed(self, first_token, pos, n_steps) -> float:
         ms = C.c_float(0)
         _check(lib().flm_decode_timed(self._h, int(first_token), int(pos), int(n_steps), C.byref(ms)), self._h)
@@ -491,6 +529,35 @@ def op_shape_logits(logits, sampling, window=()) -> np.ndarray:
     out = np.empty_like(a)
     sp, keep = sampling.struct()
     _check(lib().flm_op_shape_logits(_p(a), int(a.size), C.byref(sp), _p(w) if w.size else None, int(w.size), _p(out)))
+    del keep
+    return out
+
+
+def row_windows(window, drafts, last_n):
+    """the windows of a verify batch's rows: row r looks at the last min(last_n, len(window) + r) ids of window ++ drafts[0 .. r), r = 0 .. len(drafts) (pure Python; with
+    shape_host the host restatement of k_shape_rows)"""
+    base = [int(x) for x in window]
+    d = [int(x) for x in drafts]
+    out = []
+    for r in range(len(d) + 1):
+        h = base + d[:r]
+        w = min(int(last_n), len(h))
+        out.append(np.array(h[len(h) - w:] if w > 0 else [], dtype=np.int32))
+    return out
+
+
+def op_shape_rows(logits, n, sampling, window=(), drafts=()) -> np.ndarray:
+    """k_shape_rows, the shaper of a verify batch under the controls, on logits[rows][ld], the first n entries of each row -> the shaped rows [rows][n]; row r over the last
+    min(penalty_last_n, len(window) + r) ids of window ++ drafts[0 .. r) (drafts: rows - 1 ids)"""
+    a = np.ascontiguousarray(logits, dtype=np.float32)
+    a = a.reshape(1, -1) if a.ndim == 1 else a
+    w = np.ascontiguousarray(window, dtype=np.int32)
+    d = np.ascontiguousarray(drafts, dtype=np.int32)
+    if d.size != a.shape[0] - 1:
+        raise ValueError("op_shape_rows: rows - 1 drafts")
+    out = np.empty((a.shape[0], int(n)), dtype=np.float32)
+    sp, keep = sampling.struct()
+    _check(lib().flm_op_shape_rows(_p(a), int(a.shape[0]), int(a.shape[1]), int(n), C.byref(sp), _p(w) if w.size else None, int(w.size), _p(d) if d.size else None, _p(out)))
     del keep
     return out
 

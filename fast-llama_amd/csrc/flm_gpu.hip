@@ -1468,7 +1468,11 @@ int flm_score_tokens(flm_ctx* c, const int32_t* tokens, int n, int pos, const in
 // its xorshift state, and a batched row's logits are flm_forward's bits: row i drawn with the (i + 1)-th coin of the step's state (k_sample_rows: the draw k_sample_advance
 // makes, one function) is the id the loop draws; the accept step leaves the state after as many draws as ids it delivers, the coins drawn for the rows behind the cut are
 // simply not counted.  Equality with flm_decode_sample, not rejection sampling.  Everything up to the result block's trip back is on the stream; nothing is allocated.
-static int verify_impl(flm_ctx* c, int32_t first_token, const int32_t* drafts, int k, int pos, float temperature, float topp, uint64_t* rng_state, int32_t* out_tokens, int* n_out) {
+// shape (flm_verify_sample_ex with a control set): the shaper's block -- the controls, the caller's window as its head, penalty_last_n -- goes to the device in front of the
+// batch, and k_shape_rows shapes every row over its own window (the head ++ the drafts in front of the row) before it is drawn.  The shaped row is a function of (raw row,
+// window, controls) and the draw one of (shaped row, coin): row i is flm_forward_sample_ex's id behind first_token, a[0 .. i) for a caller who slides that window.
+static int verify_impl(flm_ctx* c, int32_t first_token, const int32_t* drafts, int k, int pos, float temperature, float topp, uint64_t* rng_state, int32_t* out_tokens, int* n_out,
+                       const ShapeParams* shape = nullptr) {
     if (!c || !drafts || !out_tokens || !n_out) return fail(c, FLM_ERR_INVALID, "verify: null argument");
     if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "verify: one GPU only");
     if (k < 4 || k > 15) return fail(c, FLM_ERR_INVALID, "verify: 4 <= k <= 15 drafts");
@@ -1482,13 +1486,17 @@ static int verify_impl(flm_ctx* c, int32_t first_token, const int32_t* drafts, i
     return with_retry(c, k + 1, [&]() -> int {
         int32_t* b = c->gen_ids.data();                                               // (pageable staging of max_seq_len ids, there since create)
         b[0] = first_token; for (int i = 0; i < k; ++i) b[1 + i] = drafts[i];
-        int r = h2d(c, c->prompt_dev, b, sizeof(int) * (size_t)(k + 1)); if (r) return r;
-        r = spec_step(c, pos, k, 0, 0, -1, k + 1, false, SpecDraw{temperature, topp, sampled ? (unsigned long long)*rng_state : 0ull}); if (r) return r;
+        int r = shape ? set_shape(c, *shape) : FLM_OK; if (r) return r;
+        r = h2d(c, c->prompt_dev, b, sizeof(int) * (size_t)(k + 1)); if (r) return r;
+        SpecDraw sd{temperature, topp, sampled ? (unsigned long long)*rng_state : 0ull};
+        if (shape) { sd.shape = c->shape_p; sd.win = c->shape_p->head; sd.n_win = shape->n_head; }
+        r = spec_step(c, pos, k, 0, 0, -1, k + 1, false, sd); if (r) return r;
         return d2h(c, &so, c->spec_res, sizeof so);                                   // (the ids and the state in one trip; the error word rides along: xwg_check looks at it next)
     }, [&] {
         memcpy(out_tokens, so.ids, sizeof(int32_t) * (size_t)so.n_emit);
         *n_out = so.n_emit;
         if (sampled) { *rng_state = so.rng; c->sampled += so.n_emit; }
+        if (shape) c->shaped += so.n_emit;
     });
 }
 int flm_verify_greedy(flm_ctx* c, int32_t first_token, const int32_t* drafts, int k, int pos, int32_t* out_tokens, int* n_out) {
@@ -1496,6 +1504,21 @@ int flm_verify_greedy(flm_ctx* c, int32_t first_token, const int32_t* drafts, in
 }
 int flm_verify_sample(flm_ctx* c, int32_t first_token, const int32_t* drafts, int k, int pos, float temperature, float topp, uint64_t* rng_state, int32_t* out_tokens, int* n_out) {
     return verify_impl(c, first_token, drafts, k, pos, temperature, topp, rng_state, out_tokens, n_out);
+}
+// flm_verify_sample with the controls: row r shaped over the last min(penalty_last_n, n_window + r) ids of window ++ drafts[0 .. r).  Every control neutral: flm_verify_sample.
+int flm_verify_sample_ex(flm_ctx* c, int32_t first_token, const int32_t* drafts, int k, int pos, const flm_sampling* sampling, const int32_t* window, int n_window,
+                         uint64_t* rng_state, int32_t* out_tokens, int* n_out) {
+    if (!c || !drafts || !out_tokens || !n_out) return fail(c, FLM_ERR_INVALID, "verify: null argument");
+    if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "verify: one GPU only");
+    ShapeParams sp; bool active = false;
+    if (const char* why = shape_fill(sampling, c->d.vocab_size, window, n_window, false, &sp, &active)) return fail(c, FLM_ERR_INVALID, why);
+    if (n_window > sampling->penalty_last_n) return fail(c, FLM_ERR_INVALID, "verify: n_window > penalty_last_n (row 0 takes the window as given)");
+    if (sampling->temperature != 0.0f && !rng_state) return fail(c, FLM_ERR_INVALID, "sample: rng_state must be given at temperature != 0");
+    // the rows' windows slide at penalty_last_n (the token form ignores it without follow); the drafts bring the penalties to life behind row 0 even where the caller's
+    // window is empty
+    const bool pen = sampling->repeat_penalty != 1.0f || sampling->frequency_penalty != 0.0f || sampling->presence_penalty != 0.0f;
+    if (pen && sampling->penalty_last_n > 0) { sp.last_n = sampling->penalty_last_n; active = true; }
+    return verify_impl(c, first_token, drafts, k, pos, sampling->temperature, sampling->topp, rng_state, out_tokens, n_out, active ? &sp : nullptr);
 }
 
 // flm_generate with several ids per pass over the weights: the prompt enters as in flm_forward_argmax / flm_forward_sample (token 0 is drawn from its last logits, with the
@@ -1506,8 +1529,13 @@ int flm_verify_sample(flm_ctx* c, int32_t first_token, const int32_t* drafts, in
 // sampled token graph (k_sample_advance reads the device parameter block, written from the host's state first) and the accept kernel with K = 0.  Every step is re-runnable:
 // its inputs are the history below n_hist and launch arguments -- n_hist, room and the state the HOST holds at the step's start, so a re-run step draws the same coins --,
 // which is what the retry wrapper needs.  The caller's state is written once, at the end.
+// shape (flm_generate_lookup_ex with a control set; the block filled as flm_generate_ex fills it: follow, the prompt's tail as its head): token 0 is the shaped token form
+// behind the prompt; a batch step's rows are shaped by k_shape_rows over the call's history in device memory (spec_hist[0 .. n_hist) ++ the drafts in front of the row, the
+// window flm_generate_ex has at that token); a single-token step runs the shaped token graph with its window written into the block from the ids the host holds (follow 0:
+// set_state has reset the step counter the follow form counts by).  Every step's inputs stay the history below n_hist, launch arguments and the block.
 static int generate_lookup_impl(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, int max_tokens, float temperature, float topp, uint64_t* rng_state,
-                                int32_t stop_token, int draft_len, int ngram_max, flm_token_cb cb, void* user, int32_t* out_tokens, int* n_out) {
+                                int32_t stop_token, int draft_len, int ngram_max, flm_token_cb cb, void* user, int32_t* out_tokens, int* n_out,
+                                const ShapeParams* shape = nullptr) {
     if (!c || !prompt || !n_out) return FLM_ERR_INVALID;
     if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "generate_lookup: one GPU only");
     if (max_tokens < 1 || !(temperature >= 0.0f) || topp != topp || stop_token >= c->d.vocab_size || draft_len < 4 || draft_len > 15 || ngram_max < 1 || ngram_max > 8)
@@ -1521,13 +1549,15 @@ static int generate_lookup_impl(flm_ctx* c, const int32_t* prompt, int n_prompt,
     int total = 0, steps = 0, accepted = 0; bool done = false, cancelled = false;
     int32_t last_tok = 0;
     uint64_t state = sampled ? *rng_state : 0;                       // the sampler's state behind the ids delivered so far
-    const Draw dr(temperature, topp, &state);                        // (arms a token graph from THAT state)
+    const Draw dr(temperature, topp, &state, shape);                 // (arms a token graph from THAT state)
+    int32_t* const drawn = c->gen_ids.data();                        // shaped: the ids delivered so far, for the single-token steps' windows (pageable, max_seq_len ids, there since create)
     SpecOut so{};
     auto deliver = [&]() {                       // the step's ids, in index order, on this thread; the state moves with them
         for (int i = 0; i < so.n_emit; ++i) {
             const int index = total + i;
             const bool last = i + 1 == so.n_emit && (so.stopped || index + 1 == max_tokens);
             if (out_tokens) out_tokens[index] = so.ids[i];
+            if (shape) drawn[index] = so.ids[i];
             if (cb && !cancelled && cb(user, index, so.ids[i], last ? 1 : 0) != 0) cancelled = true;
         }
         total += so.n_emit; last_tok = so.ids[so.n_emit - 1]; state = so.rng;
@@ -1547,9 +1577,21 @@ static int generate_lookup_impl(flm_ctx* c, const int32_t* prompt, int n_prompt,
         const bool batch = room >= 2 && at + draft_len + 1 <= c->d.max_seq_len;
         r = with_retry(c, batch ? draft_len + 1 : 1, [&]() -> int {
             int r;
-            if (batch) r = spec_step(c, at, draft_len, ngram_max, n_hist, stop, room, true, SpecDraw{temperature, topp, (unsigned long long)state});
+            if (batch) {
+                SpecDraw sd{temperature, topp, (unsigned long long)state};
+                if (shape) { sd.shape = c->shape_p; sd.win = c->spec_hist; sd.n_win = n_hist; }      // (the block: as token 0's attempt left it)
+                r = spec_step(c, at, draft_len, ngram_max, n_hist, stop, room, true, sd);
+            }
             else {      // one token through the token graph and the accept kernel with K = 0: the id from the decode state's first output slot, cut / appended / counted like a verified run of one
-                r = dr.arm(c); if (r) return r;
+                if (shape) {   // its window, as given: the last min(last_n, n_hist) ids of prompt ++ drawn[0 .. total)
+                    ShapeParams one = *shape;
+                    const int w = one.last_n < n_hist ? one.last_n : n_hist;
+                    for (int j = 0; j < w; ++j) { const int g = n_hist - w + j; one.head[j] = g < n_prompt ? prompt[g] : drawn[g - n_prompt]; }
+                    one.n_head = w; one.follow = 0;
+                    r = Draw(temperature, topp, &state, &one).arm(c);
+                }
+                else r = dr.arm(c);
+                if (r) return r;
                 r = set_state(c, at, last_tok, 0); if (r) return r;
                 r = run_token(c, true, dr.form, at + 1); if (r) return r;
                 hipLaunchKernelGGL(k_spec_accept_sample, dim3(1), dim3(64), 0, c->stream, c->spec_res, (const int*)c->out_tokens_dev, (const int*)c->prompt_dev, 0, c->spec_hist, n_hist, stop, room, (unsigned long long)state, sampled ? 1 : 0);
@@ -1562,6 +1604,7 @@ static int generate_lookup_impl(flm_ctx* c, const int32_t* prompt, int n_prompt,
     }
     *n_out = total;
     if (sampled) { *rng_state = state; c->sampled += total; }
+    if (shape) c->shaped += total;
     c->spec_steps = steps; c->spec_accepted = accepted;
     return FLM_OK;
 }
@@ -1572,6 +1615,20 @@ int flm_generate_lookup(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos
 int flm_generate_lookup_sample(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, int max_tokens, float temperature, float topp, uint64_t* rng_state,
                                int32_t stop_token, int draft_len, int ngram_max, flm_token_cb cb, void* user, int32_t* out_tokens, int* n_out) {
     return generate_lookup_impl(c, prompt, n_prompt, pos, max_tokens, temperature, topp, rng_state, stop_token, draft_len, ngram_max, cb, user, out_tokens, n_out);
+}
+// flm_generate_ex's ids through draft-and-verify steps.  Every control neutral: flm_generate_lookup_sample.
+int flm_generate_lookup_ex(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, int max_tokens, const flm_sampling* sampling, uint64_t* rng_state, int32_t stop_token,
+                           int draft_len, int ngram_max, flm_token_cb cb, void* user, int32_t* out_tokens, int* n_out) {
+    if (!c || !prompt || !n_out) return FLM_ERR_INVALID;
+    if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "generate_lookup: one GPU only");
+    if (n_prompt < 1 || n_prompt > c->d.max_seq_len) return fail(c, FLM_ERR_INVALID, "tokens/pos outside [0, max_seq_len]");
+    if (!ids_in_vocab(c, prompt, n_prompt)) return fail(c, FLM_ERR_INVALID, "token id out of range");
+    ShapeParams sp; bool active = false;
+    const int tail = n_prompt < FLM_PENALTY_WINDOW_MAX ? n_prompt : FLM_PENALTY_WINDOW_MAX;
+    if (const char* why = shape_fill(sampling, c->d.vocab_size, prompt + (n_prompt - tail), tail, true, &sp, &active)) return fail(c, FLM_ERR_INVALID, why);
+    if (sampling->temperature != 0.0f && !rng_state) return fail(c, FLM_ERR_INVALID, "sample: rng_state must be given at temperature != 0");
+    return generate_lookup_impl(c, prompt, n_prompt, pos, max_tokens, sampling->temperature, sampling->topp, rng_state, stop_token, draft_len, ngram_max, cb, user, out_tokens, n_out,
+                                active ? &sp : nullptr);
 }
 
 // the ids the last flm_decode_greedy / flm_decode_sample / flm_decode_timed* call generated (still in device memory): out[n]

@@ -169,7 +169,7 @@ struct flm_ctx {
     // flm_score_tokens (flm_gpu.hip; the classifier stage: flm_prompt.hip): the rows' targets and statistics in device memory [max_seq_len] (allocated at create), and the
     // classifier's scales group-major (cls.st) for the GEMM tiles, transposed once per set of weights
     int* score_tgt = nullptr; flm::ScoreRow* score_dev = nullptr; bool cls_st_ready = false;
-    // draft-and-verify, greedy and sampled (flm_gpu.hip verify_impl / generate_lookup_impl; kernels: flm_spec.h): the call's token history [max_seq_len + 32], the batch rows'
+    // draft-and-verify, greedy, sampled and under the controls (flm_gpu.hip verify_impl / generate_lookup_impl; kernels: flm_spec.h, flm_shape.h k_shape_rows): the call's token history [max_seq_len + 32], the batch rows'
     // ids [16] (first maxima or draws) and the step's result block (the accepted ids and the sampler's state behind them, one trip), device memory since create; which GEMM
     // the verify pass runs; the last call's figures ("spec_steps" / "spec_accepted")
     int* spec_hist = nullptr; int* spec_arg = nullptr; flm::SpecOut* spec_res = nullptr;
@@ -311,7 +311,12 @@ int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers = false, bool
 int score_classify(flm_ctx* c, int row0, int m, float* stage);
 // the verify pass's classifier stage (flm_prompt.hip): score_classify's prologue and GEMM (skinny: k_gemm_q8_skinny), then k_argmax_rows into argmax_out[row0 ..]
 // (draw: temperature, top-p and the step's xorshift state: k_sample_rows draws row row0 + i with that state's (row0 + i + 1)-th coin; temperature 0: k_argmax_rows)
-struct SpecDraw { float temperature, topp; unsigned long long base; };
+// shape (the device block) given: k_shape_rows shapes the chunk's rows in place in front of the draw, row i over the last min(last_n, n_win + i) ids of
+// win[0 .. n_win) ++ the batch's drafts in front of it (prompt_dev + 1); null: no shape kernel runs
+struct SpecDraw { float temperature, topp; unsigned long long base; const flm::ShapeParams* shape = nullptr; const int* win = nullptr; int n_win = 0; };
+// k_shape_rows on `rows` rows (batch rows row0 ..) of n logits, ld floats apart -> out, ld_out apart (out == logits: in place); c may be null: flm_op_shape_rows
+int launch_shape_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, float* out, int ld_out, int n, int row0, int rows, const flm::ShapeParams* p,
+                      const int* win, int n_win, const int* drafts);
 int spec_classify(flm_ctx* c, int row0, int m, float* stage, bool skinny, int* argmax_out, const SpecDraw& draw);
 // k_sample_rows on `rows` <= 16 rows of n logits, ld floats apart, batch rows row0 ..; sort_buf [rows][2][n] (flm_prompt.hip; c may be null: flm_op_sample_rows)
 int launch_sample_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, int n, int row0, int rows, float temperature, float topp, unsigned long long base,

@@ -223,6 +223,28 @@ int flm_op_shape_logits(const float* logits, int n, const flm_sampling* sampling
     return FLM_OK;
 }
 
+/* k_shape_rows -- the shaper over the rows of a verify batch under the controls (flm_shape.h) -- on caller-supplied rows, window and drafts */
+int flm_op_shape_rows(const float* logits, int rows, int ld, int n, const flm_sampling* sampling, const int32_t* window, int n_window, const int32_t* drafts, float* out) {
+    if (!logits || !out || rows < 1 || rows > kSpecRows || n < 2 || ld < n || (rows > 1 && !drafts)) return FLM_ERR_INVALID;
+    ShapeParams sp; bool active = false;
+    if (const char* why = shape_fill(sampling, n, window, n_window, false, &sp, &active)) { g_last_error = why; return FLM_ERR_INVALID; }
+    for (int i = 0; i + 1 < rows; ++i) if (drafts[i] < 0 || drafts[i] >= n) { g_last_error = "shape_rows: draft outside [0, n)"; return FLM_ERR_INVALID; }
+    const bool pen = sampling->repeat_penalty != 1.0f || sampling->frequency_penalty != 0.0f || sampling->presence_penalty != 0.0f;
+    sp.last_n = pen ? sampling->penalty_last_n : 0;
+    int32_t d[kSpecRows] = {0};
+    for (int i = 0; i + 1 < rows; ++i) d[i] = drafts[i];
+    DevBuf dl, dout, dp, dd;
+    if (dl.alloc((size_t)rows * ld * 4) || dout.alloc((size_t)rows * n * 4) || dp.alloc(sizeof sp) || dd.alloc(sizeof d)) return FLM_ERR_OOM;
+    OPC(hipMemcpy(dl.p, logits, (size_t)rows * ld * 4, hipMemcpyHostToDevice));
+    OPC(hipMemcpy(dp.p, &sp, sizeof sp, hipMemcpyHostToDevice));
+    OPC(hipMemcpy(dd.p, d, sizeof d, hipMemcpyHostToDevice));
+    const ShapeParams* p = dp.as<ShapeParams>();
+    int r = launch_shape_rows(nullptr, 0, dl.as<float>(), ld, dout.as<float>(), n, n, 0, rows, p, p->head, sp.n_head, dd.as<int>()); if (r) return r;
+    OPC(hipDeviceSynchronize());
+    OPC(hipMemcpy(out, dout.p, (size_t)rows * n * 4, hipMemcpyDeviceToHost));
+    return FLM_OK;
+}
+
 /* k_score_rows -- the statistics kernel of flm_score_tokens -- on caller-supplied rows of logits */
 int flm_op_score_rows(const float* logits, int rows, int n, const int32_t* targets, flm_score* out) {
     if (!logits || !out || rows < 1 || n < 2) return FLM_ERR_INVALID;

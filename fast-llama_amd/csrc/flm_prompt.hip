@@ -240,6 +240,14 @@ int launch_sample_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, 
     HIPC(c, hipGetLastError());
     return FLM_OK;
 }
+int launch_shape_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, float* out, int ld_out, int n, int row0, int rows, const ShapeParams* p,
+                      const int* win, int n_win, const int* drafts) {
+    if (rows < 1 || row0 < 0 || row0 + rows > kSpecRows) return fail(c, FLM_ERR_INVALID, "shape_rows: rows outside a batch of 16");
+    const ShapeRowsArgs a{logits, ld, out, ld_out, n, row0, p, win, n_win, drafts};
+    hipLaunchKernelGGL(k_shape_rows, dim3(rows), dim3(kSampleBlock), 0, st, a);
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
 template <int QT>
 static int score_classify_t(flm_ctx* c, int row0, int m, float* stage, bool skinny, int* argmax_out, const SpecDraw* draw = nullptr) {
     const int dim = c->d.dim, V = c->d.vocab_size;
@@ -255,6 +263,9 @@ static int score_classify_t(flm_ctx* c, int row0, int m, float* stage, bool skin
     int r = launch_rows<QT, PRO_RMSNORM_QUANT>(c, st, ra, m); if (r) return r;
     GemmArgs g{c->cls.q, c->cls.s, c->pf_xq, c->pf_xs, stage, V, dim, V, m, c->pf_xst, c->cls.st};
     r = launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, skinny && m <= kSkinnyTokens); if (r) return r;
+    if (argmax_out && draw && draw->shape) {                  // a control is set: the chunk's rows shaped in place, each over its own window, in front of the draw
+        r = launch_shape_rows(c, st, stage, V, stage, V, V, row0, m, draw->shape, draw->win, draw->n_win, c->prompt_dev + 1); if (r) return r;
+    }
     if (argmax_out && draw && draw->temperature != 0.0f)      // the sampled verify pass: row row0 + i drawn with the (row0 + i + 1)-th coin of the step's state
         return launch_sample_rows(c, st, stage, V, V, row0, m, draw->temperature, draw->topp, draw->base, c->sort_buf, argmax_out);
     if (argmax_out) {   // the verify pass: the rows' first maxima only (no softmax, no sum chain, no LDS strip: any vocabulary)

@@ -1,4 +1,6 @@
-// flm_shape.h -- the logit-shaping stage of the "shaped" token form: classifier -> k_shape_logits -> k_sample_advance.  One 1024-thread workgroup turns the raw logits row L
+// flm_shape.h -- the logit-shaping stage of the "shaped" token form: classifier -> k_shape_logits -> k_sample_advance, and of a verify batch under the sampling controls:
+// classifier GEMM -> k_shape_rows -> k_sample_rows / k_argmax_rows (one workgroup per row, each row over a window of its own, in place).  Both kernels are shape_row behind
+// their own window arithmetic.  One 1024-thread workgroup turns the raw logits row L
 // into the shaped row S (a row of its own, vocab floats, allocated at flm_ctx_create) that the UNCHANGED sampler (flm_sample.h sample_draw) then reads.  No reference
 // counterpart: the reference samples with temperature and top-p only.  The definition (restated sequentially in host/sampler.cpp shape_logits, which this
 // kernel equals bit for bit), all arithmetic fp32 round-to-nearest without contraction:
@@ -52,32 +54,34 @@ __device__ __forceinline__ unsigned shape_key(float x) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-inline __global__ void __launch_bounds__(kSampleBlock) k_shape_logits(const ShapeArgs a) {
-    __shared__ int win[kShapeWindowMax];
-    __shared__ int hist[4 * 256];
-    __shared__ int misc[64];               // [0..15] per-wave words, [16] digit, [17] rem, [18] equal-count, [20..35] per-wave floats
-    if (a.st != nullptr && halted(&a.st->halt)) return;
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6, n = a.n;
-    const ShapeParams* p = a.p;
-    const float* L = a.logits; float* S = a.out;
+// the LDS of one row's shaping: the window (<= 1024 ids), four 256-bin histograms, the scan words
+struct ShapeLds {
+    int win[kShapeWindowMax];
+    int hist[4 * 256];
+    int misc[64];                          // [0..15] per-wave words, [16] digit, [17] rem, [18] equal-count, [20..35] per-wave floats
+};
+// The window of one row: entry j = element skip + j of a[0 .. na) followed by b[..], j < w; both kernels below describe their window this way (k_shape_logits: the block's
+// head and the ids drawn so far; k_shape_rows: the base window and the batch's drafts in front of the row)
+struct ShapeWindow { const int* a; int na; const int* b; int skip; int w; };
+
+// Steps 1 - 4 of the definition on ONE row, by one 1024-thread workgroup: L[0 .. n) -> S[0 .. n) (S == L: shaped in place, the copy is skipped).  THE definition: k_shape_logits
+// (the shaped token form) and k_shape_rows (the rows of a verify batch) are both this function behind their own window arithmetic
+__device__ __forceinline__ void shape_row(const float* L, float* S, const int n, const ShapeParams* p, const ShapeWindow wd, ShapeLds& lds) {
+    int* const win = lds.win; int* const hist = lds.hist; int* const misc = lds.misc;
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
     // 1: the copy, then the biases (distinct ids: one writer per entry)
-    for (int i = t; i < n; i += kSampleBlock) S[i] = L[i];
-    __syncthreads();
+    if (S != L) {
+        for (int i = t; i < n; i += kSampleBlock) S[i] = L[i];
+        __syncthreads();
+    }
     const int nb = min(p->n_bias, kShapeBiasMax);
     if (t < nb) { const int id = p->bias_ids[t]; if ((unsigned)id < (unsigned)n) S[id] = __fadd_rn(S[id], p->bias_vals[t]); }
     // 2: the window into LDS, then one thread per entry
-    int w = min(max(p->n_head, 0), kShapeWindowMax);
-    int skip = 0, nh = w;
-    if (p->follow) {
-        const int s = a.st ? min(max(a.st->step, 0), a.out_cap) : 0;
-        const int total = nh + s;
-        w = min(min(max(p->last_n, 0), kShapeWindowMax), total);
-        skip = total - w;
-    }
+    const int w = wd.w;
     const float rp = p->repeat, fp = p->freq, pp = p->pres;
     const bool rep_on = rp != 1.0f, fpp_on = fp != 0.0f || pp != 0.0f;
     if (w > 0 && (rep_on || fpp_on)) {
-        if (t < w) { const int g = skip + t; win[t] = g < nh ? p->head[g] : a.out_tokens[g - nh]; }
+        if (t < w) { const int g = wd.skip + t; win[t] = g < wd.na ? wd.a[g] : wd.b[g - wd.na]; }
         __syncthreads();
         if (t < w) {
             const int id = win[t];
@@ -175,6 +179,43 @@ inline __global__ void __launch_bounds__(kSampleBlock) k_shape_logits(const Shap
         const float lt = p->lt;
         for (int i = t; i < n; i += kSampleBlock) { const float x = S[i]; if (x != -INFINITY && __fsub_rn(__fdiv_rn(x, temp), mx) < lt) S[i] = -INFINITY; }
     }
+}
+
+inline __global__ void __launch_bounds__(kSampleBlock) k_shape_logits(const ShapeArgs a) {
+    __shared__ ShapeLds lds;
+    if (a.st != nullptr && halted(&a.st->halt)) return;
+    const ShapeParams* p = a.p;
+    int w = min(max(p->n_head, 0), kShapeWindowMax);
+    int skip = 0;
+    const int nh = w;
+    if (p->follow) {
+        const int s = a.st ? min(max(a.st->step, 0), a.out_cap) : 0;
+        const int total = nh + s;
+        w = min(min(max(p->last_n, 0), kShapeWindowMax), total);
+        skip = total - w;
+    }
+    shape_row(a.logits, a.out, a.n, p, ShapeWindow{p->head, nh, a.out_tokens, skip, w}, lds);
+}
+
+// The shaper over the rows of a verify batch's classifier chunk: one 1024-thread workgroup per row, grid = the chunk's rows (<= 16); block r shapes batch row row0 + r (the
+// convention of k_sample_rows).  The window of batch row i is the one the shaped token loop has when it draws that token PROVIDED the drafts in front of the row were the
+// loop's ids -- the only case in which the accept step keeps the row: the last w = min(last_n, n_base + i) ids of base[0 .. n_base) ++ drafts[0 .. i), last_n the block's.
+// w <= 1024 whatever n_base is.  No latch: a verify batch has none.  out == logits: in place (the verify pass: its staged rows are never returned)
+struct ShapeRowsArgs {
+    const float* logits; int ld;           // the chunk's rows, ld floats apart
+    float* out; int ld_out;
+    int n; int row0;
+    const ShapeParams* p;                  // the controls, the bias pairs, last_n
+    const int* base; int n_base;           // flm_verify_sample_ex: the caller's window (the block's head); flm_generate_lookup_ex: the call's history
+    const int* drafts;                     // the batch's drafts d[0 .. 15): row i looks at d[0 .. i)
+};
+inline __global__ void __launch_bounds__(kSampleBlock) k_shape_rows(const ShapeRowsArgs a) {
+    __shared__ ShapeLds lds;
+    const int r = blockIdx.x, row = a.row0 + r;
+    const int nbase = max(a.n_base, 0);
+    const int total = nbase + row;
+    const int w = min(min(max(a.p->last_n, 0), kShapeWindowMax), total);
+    shape_row(a.logits + (size_t)r * a.ld, a.out + (size_t)r * a.ld_out, a.n, a.p, ShapeWindow{a.base, nbase, a.drafts, total - w, w}, lds);
 }
 
 } // namespace flm

@@ -237,7 +237,14 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
             sp.temperature = temperature; sp.topp = topp; sp.top_k = _shape.top_k; sp.min_p = _shape.min_p; sp.repeat_penalty = _shape.repeat_penalty;
             sp.frequency_penalty = _shape.frequency_penalty; sp.presence_penalty = _shape.presence_penalty; sp.penalty_last_n = _shape_last_n;
             sp.n_bias = _shape.n_bias; sp.bias_ids = _shape.bias_ids; sp.bias_values = _shape.bias_values;
-            rc = flm_generate_ex(_ctxs[0], input.data(), n_in, 0, want, &sp, &st, 0, on_token, &sink, nullptr, &n_out);
+            // with --draft (any temperature) / --lookup (temperature 0): the same ids through draft-and-verify steps whose rows are shaped each over its own window
+            // (flm_generate_lookup_ex); refused as unsupported (nothing was launched): the token loop
+            if (_draft_k > 0 || (greedy && _lookup_k > 0)) {
+                const bool draft = _draft_k > 0;
+                rc = flm_generate_lookup_ex(_ctxs[0], input.data(), n_in, 0, want, &sp, &st, 0, draft ? _draft_k : _lookup_k, draft ? _draft_g : _lookup_g, on_token, &sink, nullptr, &n_out);
+                count();
+            }
+            if (rc == FLM_ERR_UNSUPPORTED) rc = flm_generate_ex(_ctxs[0], input.data(), n_in, 0, want, &sp, &st, 0, on_token, &sink, nullptr, &n_out);
             if (rc == FLM_ERR_INVALID) { _err = flm_last_error(_ctxs[0]); fprintf(stderr, "%s\n", _err.c_str()); }
             whole = false;
         } else if (_draft_k > 0 || (greedy && _lookup_k > 0)) {

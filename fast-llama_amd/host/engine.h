@@ -41,7 +41,7 @@ public:
     void set_draft(int draft_len, int ngram_max) { _draft_k = draft_len; _draft_g = ngram_max; }
     // --top-k / --min-p / --repeat-penalty / --repeat-last-n / --presence-penalty / --frequency-penalty / --logit-bias (this build only): the sampling controls of flm_sampling.
     // One device: the whole loop is flm_generate_ex (the shaping stage on the device); where the engine samples on the host (a vocabulary beyond the device sampler, several
-    // devices) it calls shape_logits in front of the host sampler: the same ids.  --lookup / --draft are ignored then (spec decoding does not take the controls).
+    // devices) it calls shape_logits in front of the host sampler: the same ids.  --lookup / --draft: flm_generate_lookup_ex, the same ids through draft-and-verify steps.
     // Not called: nothing changes.
     void set_sampling(const ShapeControls& c, int penalty_last_n, const std::vector<int32_t>& bias_ids, const std::vector<float>& bias_values) {
         _shape = c; _shape_last_n = penalty_last_n; _bias_ids = bias_ids; _bias_values = bias_values;

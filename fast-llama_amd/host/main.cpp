@@ -208,10 +208,6 @@ int main(int argc, const char** argv) {
         fprintf(stderr, "warning: --draft applies to one device only; ignored\n");
         args.draft_k = 0;
     }
-    if (args.shape_set && (args.lookup_k || args.draft_k)) {
-        fprintf(stderr, "warning: --lookup / --draft do not take the sampling controls; ignored\n");
-        args.lookup_k = args.draft_k = 0;
-    }
     GpuTransformer tf(args.detail || args.debug);
     if (args.shape_set) tf.set_sampling(args.shape, args.repeat_last_n, args.bias_ids, args.bias_values);
     if (args.lookup_k) tf.set_lookup(args.lookup_k, args.lookup_g);

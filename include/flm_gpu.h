@@ -249,7 +249,7 @@ int  flm_generate_lookup_sample(flm_ctx* ctx, const int32_t* prompt, int n_promp
  * every control neutral S is L bit for bit and the _ex entry points run the launches of their plain forms.  The host restatement is host/sampler.cpp shape_logits; the device
  * equals it bit for bit, so ids under controls are a host loop's ids (flm_forward, shape_logits, Sampler::sample) element for element.  NaN logits are outside the contract.
  * The controls live in a device block written at the start of each call (like the sampler's parameters): no graph is re-captured, nothing is allocated.
- * Spec decoding (the flm_verify_ and flm_generate_lookup families) does not take the controls: each row of a verify batch would need a window of its own.  Not built. */
+ * Spec decoding takes the controls through flm_verify_sample_ex / flm_generate_lookup_ex below: every row of a verify batch is shaped over a window of its own. */
 #define FLM_PENALTY_WINDOW_MAX 1024
 #define FLM_BIAS_MAX 256
 typedef struct flm_sampling {
@@ -276,6 +276,30 @@ int  flm_generate_ex(flm_ctx* ctx, const int32_t* prompt, int n_prompt, int pos,
  * as given (penalty_last_n is only range-checked here; n_window == 0: penalties off).  One GPU only when a control is set. */
 int  flm_forward_sample_ex(flm_ctx* ctx, const int32_t* tokens, int n, int pos, const flm_sampling* sampling,
                            const int32_t* window, int n_window, uint64_t* rng_state, int32_t* next_token);
+/* Draft-and-verify under the controls.  In a flm_generate_ex loop the window of generated token s is the last min(penalty_last_n, n_prompt + s) ids of prompt ++ drawn[0 .. s).
+ * Row r of a verify batch fed with {last id, d[0 .. k)} matters only if d[0 .. r) were the ids drawn for rows 0 .. r - 1 -- exactly when the accept step keeps row r -- and then
+ * the loop's window for that token is the last min(penalty_last_n, n_hist + r) ids of hist[0 .. n_hist) ++ d[0 .. r): both parts are in device memory before the batch runs.
+ * The shaped row is a function of (raw row, window, controls) and the draw a function of (shaped row, coin r + 1), so shaping row r with that window (k_shape_rows,
+ * csrc/flm_shape.h: one 1024-thread workgroup per row, the definition above through the same device function as k_shape_logits, in place in the classifier's staging, no
+ * vocabulary bound) and drawing it with the verify pass's row sampler (the row argmax at temperature 0) gives the id the shaped token loop draws.  Rows behind the first
+ * mismatch used windows the loop never sees; they are discarded anyway.  Equality, not rejection sampling.
+ * flm_verify_sample_ex: flm_verify_sample's contract with row r shaped over the last min(penalty_last_n, n_window + r) ids of window ++ drafts[0 .. r); n_window <=
+ * penalty_last_n is required (row 0 then uses the window exactly as given; penalty_last_n == 0: penalties off).  The ids, *n_out, the state and the K/V rows pos .. pos + m are
+ * those of *n_out successive flm_forward_sample_ex calls by a caller who keeps that sliding window.
+ * flm_generate_lookup_ex: flm_generate_ex's contract (ids, *n_out, callbacks, stop, cancel as in flm_generate_lookup_sample, the final state, the K/V rows) through
+ * draft-and-verify steps: token 0 is the shaped token behind the prompt, a batch step's base window is the call's history, a single-token step (fewer than 2 ids wanted, or
+ * the batch would pass max_seq_len) is the shaped token with its window written from the ids the host holds.
+ * Both: every control neutral = the launches of flm_verify_sample / flm_generate_lookup_sample (no shape kernel); FLM_ERR_INVALID as in flm_generate_ex /
+ * flm_forward_sample_ex and in the plain forms (nothing launched); FLM_ERR_UNSUPPORTED for world > 1 and, at temperature != 0, above the sampler's vocabulary bound (none at
+ * temperature 0); nothing is allocated in a call; a re-run step delivers nothing twice.  The ids delivered with a control set count in "shaped_tokens". */
+int  flm_verify_sample_ex(flm_ctx* ctx, int32_t first_token, const int32_t* drafts, int k, int pos,
+                          const flm_sampling* sampling, const int32_t* window, int n_window,
+                          uint64_t* rng_state /* NULL allowed iff temperature == 0 */, int32_t* out_tokens /* [k + 1] */, int* n_out);
+int  flm_generate_lookup_ex(flm_ctx* ctx, const int32_t* prompt, int n_prompt, int pos, int max_tokens,
+                            const flm_sampling* sampling, uint64_t* rng_state /* NULL allowed iff temperature == 0 */,
+                            int32_t stop_token /* -1: none */, int draft_len /* 4..15 */, int ngram_max /* 1..8 */,
+                            flm_token_cb cb /* may be NULL */, void* user,
+                            int32_t* out_tokens /* [max_tokens], may be NULL */, int* n_out);
 /* the ids generated by the last flm_decode_greedy / flm_decode_sample / flm_decode_timed* call: out[n] (n <= its n_steps) */
 int  flm_last_tokens(flm_ctx* ctx, int n, int32_t* out);
 int  flm_reset_kv(flm_ctx* ctx);
@@ -361,7 +385,7 @@ int  flm_set_option(flm_ctx* ctx, const char* key, int value);
  *               classifier, argmax in k_layers<.., TAIL>),
  *   "ao_active" which hand-offs of that launch are consumed in arrival order: bit 0 Wo, bit 1 FFN2 (-1: the launch has not been planned yet),
  *   "sampled_tokens" how many tokens this context sampled on the device (flm_forward_sample / flm_decode_sample / flm_generate / flm_verify_sample / flm_generate_lookup_sample at temperature > 0),
- *   "shaped_tokens" how many tokens this context drew through the shaped token form (flm_generate_ex / flm_forward_sample_ex with a control set),
+ *   "shaped_tokens" how many tokens this context drew under the controls (flm_generate_ex / flm_forward_sample_ex / flm_verify_sample_ex / flm_generate_lookup_ex with a control set),
  *   "spec_steps" / "spec_accepted" the last flm_generate_lookup / flm_generate_lookup_sample call: verify passes run / drafted ids accepted in them,
  *   "gen_tokens" / "gen_streamed" the last flm_generate call: tokens delivered / how many of them were delivered while hipStreamQuery still said the stream was busy,
  *   "epoch_tail" / "epoch_eng" / "epoch_xchg" the epoch counters the cross-workgroup waits count from (device memory; the 32-bit pattern): the one-launch token's, the
@@ -399,6 +423,11 @@ int  flm_op_sample_rows(const float* logits, int rows, int ld, int n, float temp
 /* the shaping stage of flm_generate_ex (k_shape_logits) on caller-supplied logits[n], n >= 2, and window[n_window] used as given: out[n] = the shaped row (steps 1 - 4 of the
  * definition at flm_sampling; sampling->temperature is min-p's divisor, topp is not used).  No bound on n.  Errors as there. */
 int  flm_op_shape_logits(const float* logits, int n, const flm_sampling* sampling, const int32_t* window, int n_window, float* out);
+/* the shaper of flm_verify_sample_ex (k_shape_rows) on caller-supplied logits[rows][ld], n entries per row, 1 <= rows <= 16, ld >= n >= 2: out[r][0 .. n) = row r shaped over
+ * the last min(penalty_last_n, n_window + r) ids of window ++ drafts[0 .. r) -- flm_op_shape_logits on row r with that window.  drafts: rows - 1 ids in [0, n) (may be NULL
+ * for rows == 1).  No bound on n.  Errors as there. */
+int  flm_op_shape_rows(const float* logits, int rows, int ld, int n, const flm_sampling* sampling, const int32_t* window, int n_window,
+                       const int32_t* drafts /* [rows - 1] */, float* out /* [rows][n] */);
 /* flm_score_tokens' statistics kernel (k_score_rows) on caller-supplied logits[rows][n]: out[rows]; targets[rows] as there (NULL: none).  2 <= n, n within the LDS bound. */
 int  flm_op_score_rows(const float* logits, int rows, int n, const int32_t* targets, flm_score* out);
 /* simd::swiglu(xo,xr,n) (x86_simd.cpp:1766-1770) */

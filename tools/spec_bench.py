@@ -9,8 +9,14 @@ With --temperature T (> 0) and --topp P the same three for the SAMPLED path, sta
    (b') flm_verify_sample fed flm_decode_sample's ids as drafts, B = 5, 8, 16, with the "spec_gemm" form (c) chose; beside it flm_verify_greedy's pass at the same B in the
         same run (the difference is k_sample_rows over B rows against k_argmax_rows)
    (c') flm_generate_lookup_sample on the same kind of prompt, at state 1234 and at state 0 (the CLI's default seed: every coin 0): tokens/s, accepted / steps
-Exits non-zero unless the ids of (a), (b) and (c) agree -- and, sampled, unless ids and final states agree with flm_generate.  Prints one JSON line.
-python tools/spec_bench.py [--temperature T] [--topp P] [N] [reps] [layers]"""
+With --shape the same for the path under the sampling controls (the controls of tests/test_gpu_shape.py: CONTROLS), at --temperature (default 1.0 there), state 1234, in the
+same JSON line under "shaped":
+   (b") flm_verify_sample_ex fed flm_generate_ex's ids as drafts, B = 5, 8, 16; beside it the unshaped flm_verify_sample pass at the same B in the same run (the
+        difference is the parameter block's upload and k_shape_rows over B rows)
+   (c") flm_generate_lookup_ex on a prompt that repeats a block of its own shaped continuation: tokens/s, accepted / steps, beside flm_generate_ex's tokens/s
+Exits non-zero unless the ids of (a), (b) and (c) agree -- and, sampled, unless ids and final states agree with flm_generate; shaped, with flm_generate_ex.  Prints one
+JSON line.
+python tools/spec_bench.py [--temperature T] [--topp P] [--shape] [N] [reps] [layers]"""
 import argparse
 import json
 import os
@@ -25,6 +31,7 @@ from fast_llama_amd import capi, synth, flmfile as ff
 ap = argparse.ArgumentParser()
 ap.add_argument("--temperature", "-t", type=float, default=0.0)
 ap.add_argument("--topp", "-p", type=float, default=0.9)
+ap.add_argument("--shape", action="store_true")
 ap.add_argument("N", nargs="?", type=int, default=128)
 ap.add_argument("reps", nargs="?", type=int, default=9)
 ap.add_argument("layers", nargs="?", type=int, default=None)
@@ -120,6 +127,58 @@ if opt.temperature > 0:
                            "ids_and_state_agree": agree}
     sm["fallback"] = ctx.query("fallback")
     res["sampled"] = sm
+    res["ids_agree"] = bool(ok)
+# the path under the sampling controls
+if opt.shape:
+    T, P, S0 = (opt.temperature if opt.temperature > 0 else 1.0), opt.topp, 1234
+    controls = dict(top_k=5, min_p=0.05, repeat_penalty=1.3, penalty_last_n=8, bias={3: 2.0, 7: -np.inf})     # tests/test_gpu_shape.py: CONTROLS
+    sc = capi.Sampling(temperature=T, topp=P, **controls)
+    sh = {"temperature": T, "topp": P, "gemm": ctx.query("spec_gemm")}
+    ctx.reset_kv()
+    gids, _ = ctx.generate_ex(seed, 0, 17, sc, rng_state=S0)          # token 0 behind the seed prompt, then the 16 ids a verify pass at len(seed) must return
+    window = np.concatenate([seed, gids[:1]])[-controls["penalty_last_n"]:]
+    ctx.reset_kv()
+    ufirst, u1 = ctx.forward_sample(seed, 0, T, P, S0)
+    uids, _ = ctx.decode_sample(ufirst, len(seed), 16, T, P, u1)
+
+    def xpass_ms(k, shaped):
+        global ok
+        ts = []
+        for _ in range(reps + 1):
+            t0 = time.perf_counter()
+            if shaped:
+                got, _ = ctx.verify_sample_ex(int(gids[0]), gids[1:k + 1], len(seed), sc, window, advance(S0, 1))
+            else:
+                got, _ = ctx.verify_sample(ufirst, uids[:k], len(seed), T, P, u1)
+            ts.append((time.perf_counter() - t0) * 1e3)
+            ok = ok and np.array_equal(got, gids[1:k + 2] if shaped else uids[:k + 1])
+        return float(np.median(ts[1:]))
+
+    def advance(s, n):
+        for _ in range(n):
+            s ^= s >> 12; s ^= (s << 25) & ((1 << 64) - 1); s ^= s >> 27
+        return s
+    for k in (4, 7, 15):
+        a = xpass_ms(k, True); b = xpass_ms(k, False)
+        sh[f"B{k + 1}"] = {"shaped_ms": round(a, 3), "unshaped_ms": round(b, 3), "shaped_minus_unshaped_ms": round(a - b, 3)}
+    ctx.reset_kv()
+    xref, _ = ctx.generate_ex(seed, 0, 32, sc, rng_state=S0)
+    xblock = np.concatenate([seed, xref]).astype(np.int32)
+    xprompt = np.concatenate([xblock, xblock]).astype(np.int32)
+    ctx.reset_kv()
+    t0 = time.perf_counter(); want, sw = ctx.generate_ex(xprompt, 0, N, sc, rng_state=S0); dt_g = time.perf_counter() - t0
+    ctx.reset_kv()
+    ctx.generate_lookup_ex(xprompt, 0, 8, sc, rng_state=S0, draft_len=7)          # warm
+    ctx.reset_kv()
+    t0 = time.perf_counter(); got, sg = ctx.generate_lookup_ex(xprompt, 0, N, sc, rng_state=S0, draft_len=7, ngram_max=3); dt_l = time.perf_counter() - t0
+    agree = bool(np.array_equal(got, want) and sg == sw)
+    ok = ok and agree
+    sh.update({"generate_ex_tok_s": round(N / dt_g, 1), "lookup_ex_tok_s": round(N / dt_l, 1), "lookup_steps": ctx.query("spec_steps"), "lookup_accepted": ctx.query("spec_accepted"),
+               "ids_and_state_agree": agree, "fallback": ctx.query("fallback")})
+    for k in (4, 7, 15):
+        print(f"t_{k + 1}: shaped {sh[f'B{k + 1}']['shaped_ms']} ms, unshaped {sh[f'B{k + 1}']['unshaped_ms']} ms")
+    print(f"flm_generate_lookup_ex: {sh['lookup_ex_tok_s']} tokens/s, accepted / steps {sh['lookup_accepted']} / {sh['lookup_steps']} (flm_generate_ex: {sh['generate_ex_tok_s']} tokens/s)")
+    res["shaped"] = sh
     res["ids_agree"] = bool(ok)
 print(json.dumps(res), flush=True)
 ctx.close()
