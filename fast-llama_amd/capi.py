@@ -30,6 +30,7 @@ SYMBOLS = (
     "flm_verify_sample", "flm_generate_lookup_sample", "flm_op_sample_rows",
     "flm_generate_ex", "flm_forward_sample_ex", "flm_op_shape_logits",
     "flm_verify_sample_ex", "flm_generate_lookup_ex", "flm_op_shape_rows",
+    "flm_dfa_validate", "flm_constraint_set", "flm_constraint_arm", "flm_op_constrain_rows",
 )
 
 # flm_score (include/flm_gpu.h): one row of flm_score_tokens / flm_op_score_rows
@@ -82,6 +83,116 @@ class Sampling:
 
 class FlmError(RuntimeError):
     pass
+
+
+DFA_STATES_MAX, DFA_EDGES_MAX = 65536, 1 << 24      # FLM_DFA_STATES_MAX, FLM_DFA_EDGES_MAX
+
+
+class DfaStruct(C.Structure):
+    """flm_dfa (include/flm_gpu.h)"""
+    _fields_ = [("n_states", C.c_int32), ("n_edges", C.c_int32), ("row_ptr", C.c_void_p), ("edge_token", C.c_void_p), ("edge_next", C.c_void_p)]
+
+
+class Dfa:
+    """A token-level deterministic automaton in CSR form (flm_dfa): the edges of state q are [row_ptr[q], row_ptr[q + 1]), their tokens strictly ascending.  Holds the three
+    int32 arrays as given -- validation is flm_dfa_validate's (dfa_validate below)."""
+
+    def __init__(self, row_ptr, edge_token, edge_next):
+        self.row_ptr = np.ascontiguousarray(row_ptr, dtype=np.int32)
+        self.edge_token = np.ascontiguousarray(edge_token, dtype=np.int32)
+        self.edge_next = np.ascontiguousarray(edge_next, dtype=np.int32)
+
+    @property
+    def n_states(self):
+        return int(self.row_ptr.size) - 1
+
+    @property
+    def n_edges(self):
+        return int(self.edge_token.size)
+
+    def struct(self):
+        """-> flm_dfa pointing into this object's arrays (keep the object alive for the call)"""
+        return DfaStruct(self.n_states, self.n_edges, _p(self.row_ptr), _p(self.edge_token), _p(self.edge_next))
+
+    def edges(self, q):
+        """-> (tokens, next states) of state q"""
+        a, b = int(self.row_ptr[q]), int(self.row_ptr[q + 1])
+        return self.edge_token[a:b], self.edge_next[a:b]
+
+    @classmethod
+    def from_edges(cls, n_states, triples):
+        """(state, token, next) triples in any order -> Dfa, sorted by (state, token)"""
+        tr = sorted((int(q), int(t), int(n)) for q, t, n in triples)
+        row = np.zeros(int(n_states) + 1, dtype=np.int64)
+        for q, _, _ in tr:
+            if not 0 <= q < n_states:
+                raise ValueError(f"dfa: state {q} outside [0, {n_states})")
+            row[q + 1] += 1
+        return cls(np.cumsum(row), [t for _, t, _ in tr], [n for _, _, n in tr])
+
+    def save(self, path):
+        """the text format: a header line `flm-dfa 1 <n_states>`, then one `state token next` line per edge"""
+        with open(path, "w") as f:
+            f.write(f"flm-dfa 1 {self.n_states}\n")
+            for q in range(self.n_states):
+                for t, n in zip(*self.edges(q)):
+                    f.write(f"{q} {int(t)} {int(n)}\n")
+
+    @classmethod
+    def load(cls, path):
+        """reads what save writes; the edge lines may come in any order (sorted here)"""
+        with open(path) as f:
+            head = f.readline().split()
+            if len(head) != 3 or head[0] != "flm-dfa" or head[1] != "1":
+                raise ValueError(f"{path}: not a `flm-dfa 1 <n_states>` file")
+            n_states = int(head[2])
+            triples = []
+            for line in f:
+                w = line.split()
+                if not w:
+                    continue
+                if len(w) != 3:
+                    raise ValueError(f"{path}: expected `state token next`, got {line!r}")
+                triples.append((int(w[0]), int(w[1]), int(w[2])))
+        return cls.from_edges(n_states, triples)
+
+    @classmethod
+    def from_choices(cls, pieces, choices, end_id):
+        """"answer with one of these strings": pieces[id] = the text token id decodes to (empty / None: never allowed), choices = the strings, end_id = the token that
+        ends the answer.  States are the nodes of the character trie of `choices` (state 0 = the root) plus one final state (the last); there is an edge u -> v on every
+        piece that walks from u to v inside the trie; a node that completes a choice has an edge on end_id to the final state, which loops on end_id."""
+        children, done = [{}], [False]
+        for ch in choices:
+            if not ch:
+                raise ValueError("from_choices: an empty choice")
+            u = 0
+            for x in ch:
+                if x not in children[u]:
+                    children[u][x] = len(children); children.append({}); done.append(False)
+                u = children[u][x]
+            done[u] = True
+        final = len(children)
+        triples = [(final, int(end_id), final)]
+        for u in range(final):
+            if done[u]:
+                triples.append((u, int(end_id), final))
+            for tid, piece in enumerate(pieces):
+                if not piece or tid == int(end_id):
+                    continue
+                v = u
+                for x in piece:
+                    v = children[v].get(x)
+                    if v is None:
+                        break
+                if v is not None:
+                    triples.append((u, tid, v))
+        return cls.from_edges(final + 1, triples)
+
+
+def dfa_validate(dfa: Dfa, vocab: int):
+    """flm_dfa_validate: raises FlmError naming the rule that failed"""
+    st = dfa.struct()
+    _check(lib().flm_dfa_validate(C.byref(st), int(vocab)))
 
 
 class ModelDesc(C.Structure):
@@ -269,6 +380,18 @@ class Ctx:
         _check(lib().flm_forward_sample_ex(self._h, _p(t), len(t), int(pos), C.byref(sp), _p(w) if w.size else None, int(w.size), C.byref(st), C.byref(nxt)), self._h)
         del keep
         return nxt.value, st.value
+
+    def constraint_set(self, dfa):
+        """flm_constraint_set: install or replace the automaton (None: remove it); the context is disarmed afterwards"""
+        if dfa is None:
+            _check(lib().flm_constraint_set(self._h, None), self._h)
+            return
+        st = dfa.struct()
+        _check(lib().flm_constraint_set(self._h, C.byref(st)), self._h)
+
+    def constraint_arm(self, state):
+        """flm_constraint_arm: the state the _ex entry points mask in from now on (-1: disarm); query("constraint_state") reads it back"""
+        _check(lib().flm_constraint_arm(self._h, C.c_int32(int(state))), self._h)
 
     def score(self, tokens, pos, targets=None, want_logits=False):
         """flm_score_tokens -> a structured array (SCORE_DTYPE) with one row per position; with want_logits also the [n][vocab] logits.  targets None: the next token of
@@ -560,6 +683,45 @@ def op_shape_rows(logits, n, sampling, window=(), drafts=()) -> np.ndarray:
     _check(lib().flm_op_shape_rows(_p(a), int(a.shape[0]), int(a.shape[1]), int(n), C.byref(sp), _p(w) if w.size else None, int(w.size), _p(d) if d.size else None, _p(out)))
     del keep
     return out
+
+
+def op_constrain_rows(logits, n, sampling, dfa, state, window=(), drafts=()):
+    """k_shape_rows with the constraint's step 0 on logits[rows][ld] -> (the shaped rows [rows][n], states[rows]): row r masked in delta folded over drafts[0 .. r) from `state`"""
+    a = np.ascontiguousarray(logits, dtype=np.float32)
+    a = a.reshape(1, -1) if a.ndim == 1 else a
+    w = np.ascontiguousarray(window, dtype=np.int32)
+    d = np.ascontiguousarray(drafts, dtype=np.int32)
+    if d.size != a.shape[0] - 1:
+        raise ValueError("op_constrain_rows: rows - 1 drafts")
+    out = np.empty((a.shape[0], int(n)), dtype=np.float32)
+    states = np.full(a.shape[0], -2, dtype=np.int32)
+    sp, keep = sampling.struct()
+    st = dfa.struct()
+    _check(lib().flm_op_constrain_rows(_p(a), int(a.shape[0]), int(a.shape[1]), int(n), C.byref(sp), _p(w) if w.size else None, int(w.size), _p(d) if d.size else None,
+                                       C.byref(st), C.c_int32(int(state)), _p(out), _p(states)))
+    del keep
+    return out, states
+
+
+def _host_lib():
+    global _host
+    if _host is None:
+        _host = C.CDLL(os.path.join(_HERE, "lib", "libflm_host.so"))
+    return _host
+
+
+def constrain_host(logits, tokens) -> np.ndarray:
+    """step 0's host restatement (host/sampler.cpp constrain_logits through lib/libflm_host.so: fh_constrain): -inf wherever the index is not in `tokens` (ascending); no GPU"""
+    a = np.ascontiguousarray(logits, dtype=np.float32)
+    t = np.ascontiguousarray(tokens, dtype=np.int32)
+    out = np.empty_like(a)
+    _host_lib().fh_constrain(_p(a), int(a.size), _p(t), int(t.size), _p(out))
+    return out
+
+
+def dfa_next_host(dfa: Dfa, q, t) -> int:
+    """delta(q, t) through the host restatement (host/sampler.cpp dfa_next: fh_dfa_next); no GPU"""
+    return int(_host_lib().fh_dfa_next(_p(dfa.row_ptr), _p(dfa.edge_token), _p(dfa.edge_next), int(q), int(t)))
 
 
 def shape_host(logits, sampling, window=()) -> np.ndarray:

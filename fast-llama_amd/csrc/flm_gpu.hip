@@ -5,6 +5,7 @@
 // is here one stream of 5*L+3 kernel launches whose position/token operands live in device memory, so
 // the whole token can be replayed from a hipGraph with no host round trip.
 #include "flm_host.h"
+#include <algorithm>
 
 namespace fh {
 
@@ -396,6 +397,48 @@ static int set_shape(flm_ctx* c, const ShapeParams& sp) {
     memcpy(c->shape_stage, &sp, sizeof sp);
     return copy_words(c, c->shape_stage, c->shape_p, sizeof sp, false);
 }
+// the constraint's block, by value like the decode state: {the arrays, n_states, q, applied = 0}.  One tiny launch on the context's stream: no allocation, no graph touched
+__global__ void k_set_dfa(DfaBlock* blk, const DfaBlock v) { if (threadIdx.x == 0 && blockIdx.x == 0) *blk = v; }
+static int set_dfa(flm_ctx* c, int q) {
+    DfaBlock v{};
+    const int ns = (int)c->dfa_row.size() - 1;
+    if (c->dfa_dev && ns > 0) { v.row_ptr = c->dfa_dev; v.edge_token = c->dfa_dev + (ns + 1); v.edge_next = v.edge_token + c->dfa_tok.size(); v.n_states = ns; }
+    v.q = v.n_states > 0 ? q : -1; v.applied = 0;
+    hipLaunchKernelGGL(k_set_dfa, dim3(1), dim3(64), 0, c->stream, c->dfa_blk, v);
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
+// delta(q, t): the edge_next of t's edge in q, or q itself when t has no edge there -- reachable only through the multinomial branch's last-index fallback of Sampler::sample
+// (`return _n - 1`), which can name a masked id; folded over the ids a call delivered
+int dfa_fold(const flm_ctx* c, int q, const int32_t* ids, int n) {
+    for (int i = 0; i < n; ++i) {
+        const int32_t* b = c->dfa_tok.data() + c->dfa_row[q]; const int32_t* e = c->dfa_tok.data() + c->dfa_row[q + 1];
+        const int32_t* it = std::lower_bound(b, e, ids[i]);
+        if (it != e && *it == ids[i]) q = c->dfa_nxt[it - c->dfa_tok.data()];
+    }
+    return q;
+}
+const char* dfa_check(const flm_dfa* a, int vocab) {
+    if (!a) return "dfa: null struct";
+    if (vocab < 1) return "dfa: vocab < 1";
+    if (a->n_states < 1 || a->n_states > FLM_DFA_STATES_MAX) return "dfa: n_states outside [1, FLM_DFA_STATES_MAX]";
+    if (a->n_edges < 1 || a->n_edges > FLM_DFA_EDGES_MAX) return "dfa: n_edges outside [1, FLM_DFA_EDGES_MAX]";
+    if (!a->row_ptr || !a->edge_token || !a->edge_next) return "dfa: null array";
+    if (a->row_ptr[0] != 0 || a->row_ptr[a->n_states] != a->n_edges) return "dfa: row_ptr must start at 0 and end at n_edges";
+    for (int q = 0; q < a->n_states; ++q) {
+        if (a->row_ptr[q + 1] < a->row_ptr[q] || a->row_ptr[q + 1] > a->n_edges) return "dfa: row_ptr is not non-decreasing within [0, n_edges]";
+    }
+    for (int q = 0; q < a->n_states; ++q) if (a->row_ptr[q + 1] == a->row_ptr[q]) return "dfa: a state has no edge";
+    for (int q = 0; q < a->n_states; ++q) {
+        for (int e = a->row_ptr[q]; e < a->row_ptr[q + 1]; ++e) {
+            if (a->edge_token[e] < 0 || a->edge_token[e] >= vocab) return "dfa: edge token outside [0, vocab)";
+            if (a->edge_next[e] < 0 || a->edge_next[e] >= a->n_states) return "dfa: edge_next outside [0, n_states)";
+            if (e > a->row_ptr[q] && a->edge_token[e] == a->edge_token[e - 1]) return "dfa: a token is listed twice in a state";
+            if (e > a->row_ptr[q] && a->edge_token[e] < a->edge_token[e - 1]) return "dfa: tokens must be strictly ascending inside a state";
+        }
+    }
+    return nullptr;
+}
 const char* shape_fill(const flm_sampling* sp, int vocab, const int32_t* window, int n_window, bool follow, ShapeParams* out, bool* active) {
     if (!sp) return "sampling: null struct";
     if (!(sp->temperature >= 0.0f) || sp->topp != sp->topp) return "sampling: temperature must be >= 0, top-p a number";
@@ -489,6 +532,7 @@ int h2d(flm_ctx* c, void* dst_dev, const void* src, size_t bytes) {
 }
 int Draw::arm(flm_ctx* c) const {
     int r = shape ? set_shape(c, *shape) : FLM_OK;
+    if (!r && cstate >= 0) r = set_dfa(c, cstate);
     if (!r && form != TokenForm::Greedy) r = set_sample(c, temperature, topp, coins() ? (unsigned long long)*rng_state : 0ull);
     return r;
 }
@@ -674,6 +718,12 @@ int flm_ctx_create(const flm_model_desc* desc, int device_id, int rank, int worl
     HIPB(dev_alloc(c, &c->sparams, sizeof(SampleParams), true));   // the device sampler's parameter block and sort buffers
     HIPB(dev_alloc(c, &c->shape_p, sizeof(ShapeParams), true));    // the logit shaper's parameter block and the shaped row (flm_shape.h)
     HIPB(dev_alloc(c, &c->shape_row, (size_t)d.vocab_size * sizeof(float), true));
+    {   // the constraint's block (flm_shape.h DfaBlock): no automaton, disarmed
+        HIPB(dev_alloc(c, &c->dfa_blk, sizeof(DfaBlock), true));
+        DfaBlock none{}; none.q = -1;
+        HIPB(hipMemcpyAsync(c->dfa_blk, &none, sizeof none, hipMemcpyHostToDevice, c->stream));
+        HIPB(hipStreamSynchronize(c->stream));                                // (`none` goes out of scope)
+    }
     if (sample_supported(c)) HIPB(dev_alloc(c, &c->sort_buf, (size_t)kSpecRows * 2 * d.vocab_size * sizeof(unsigned long long)));   // ([16][2][vocab]: a slice per row of a sampled verify batch)
     std::vector<float> cs, sn; build_rope_table(hs, d.max_seq_len, cs, sn);
     HIPB(dev_alloc(c, &c->rope_cos, cs.size() * 4)); HIPB(dev_alloc(c, &c->rope_sin, sn.size() * 4));
@@ -710,7 +760,7 @@ void flm_ctx_destroy(flm_ctx* c) {
     drop_graphs(c, false);
     for (int r = 0; r < c->world; ++r) if (c->peer_opened[r] && c->peer[r]) hipIpcCloseMemHandle(c->peer[r]);
     for (void* p : c->owned) hipFree(p);
-    for (void* p : {c->emb, (void*)c->emb_s, (void*)c->trace}) if (p) hipFree(p);          // (re-allocated during the context's life: flm_upload_tensor, option "trace")
+    for (void* p : {c->emb, (void*)c->emb_s, (void*)c->trace, (void*)c->dfa_dev}) if (p) hipFree(p);          // (re-allocated during the context's life: flm_upload_tensor, option "trace", flm_constraint_set)
     if (c->bounce) hipHostFree(c->bounce);
     if (c->gen_host) hipHostFree(c->gen_host);
     if (c->shape_stage) hipHostFree(c->shape_stage);
@@ -968,6 +1018,7 @@ int flm_query(flm_ctx* c, const char* key, int* value) {
         {"fallback_active", c->fb_active ? 1 : 0},
         {"sampled_tokens", (int)c->sampled},
         {"shaped_tokens", (int)c->shaped},
+        {"constraint_state", c->dfa_state},
         {"gen_tokens", c->gen_tokens},
         {"gen_streamed", c->gen_streamed},
         {"spec_steps", c->spec_steps},
@@ -1279,7 +1330,7 @@ static int forward_draw(flm_ctx* c, const int32_t* tokens, int n, int pos, Draw 
         r = feed(c, tokens, n, pos, dr.form); if (r) return r;
         r = dr.fetch(c); if (r) return r;
         return d2h(c, next_token, c->out_tokens_dev, 4);
-    }, [&] { dr.commit(c, 1); });
+    }, [&] { dr.commit(c, 1); if (dr.cstate >= 0) c->dfa_state = dfa_fold(c, dr.cstate, next_token, 1); });
 }
 int flm_forward_sample(flm_ctx* c, const int32_t* tokens, int n, int pos, float temperature, float topp, uint64_t* rng_state, int32_t* next_token) {
     if (!tokens || !next_token) return FLM_ERR_INVALID;
@@ -1316,14 +1367,14 @@ inline void cpu_relax() {
 }
 // shape: null = flm_generate; else flm_generate_ex with a control set: the block goes to the device first and every token takes the shaped form
 static int generate_impl(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, int max_tokens, float temperature, float topp, uint64_t* rng_state,
-                         int32_t stop_token, flm_token_cb cb, void* user, int32_t* out_tokens, int* n_out, const ShapeParams* shape) {
+                         int32_t stop_token, flm_token_cb cb, void* user, int32_t* out_tokens, int* n_out, const ShapeParams* shape, int cq = -1) {
     if (!c || !prompt || !n_out) return FLM_ERR_INVALID;
     // (in front of everything else: a tensor-parallel rank must not touch a peer -- halting and cancelling across ranks is not built)
     if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "generate: one GPU only (tensor-parallel callers keep the flm_decode_* loop)");
     if (max_tokens < 1 || !(temperature >= 0.0f) || stop_token >= c->d.vocab_size) return fail(c, FLM_ERR_INVALID, "generate: max_tokens >= 1, temperature >= 0, stop_token < vocab_size (or -1)");
     int r = check_ready(c, n_prompt, pos); if (r) return r;
     if (pos + n_prompt + max_tokens - 1 > c->d.max_seq_len || max_tokens > c->out_cap || max_tokens > c->gen_cap) return fail(c, FLM_ERR_INVALID, "generate: pos + n_prompt + max_tokens - 1 exceeds max_seq_len");
-    Draw dr(temperature, topp, rng_state, shape);
+    Draw dr(temperature, topp, rng_state, shape, cq);
     if (dr.coins()) { r = sample_args_ok(c, temperature, topp, rng_state); if (r) return r; }
     volatile unsigned long long* ring = c->gen_host;
     int* cancel_word = (int*)((char*)c->gen_host + (((size_t)c->gen_cap * 8 + 63) & ~(size_t)63));
@@ -1384,6 +1435,7 @@ static int generate_impl(flm_ctx* c, const int32_t* prompt, int n_prompt, int po
         if (out_tokens) memcpy(out_tokens, ids, sizeof(int32_t) * (size_t)total);
         *n_out = total;
         dr.commit(c, total);
+        if (dr.cstate >= 0) c->dfa_state = dfa_fold(c, dr.cstate, ids, total);      // (the stop token, when delivered, included)
         c->gen_tokens = total; c->gen_streamed = streamed;
     });
     return r;
@@ -1404,7 +1456,8 @@ int flm_generate_ex(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, in
     const int tail = n_prompt < FLM_PENALTY_WINDOW_MAX ? n_prompt : FLM_PENALTY_WINDOW_MAX;
     if (const char* why = shape_fill(sampling, c->d.vocab_size, prompt + (n_prompt - tail), tail, true, &sp, &active)) return fail(c, FLM_ERR_INVALID, why);
     if (sampling->temperature != 0.0f && !rng_state) return fail(c, FLM_ERR_INVALID, "sample: rng_state must be given at temperature != 0");
-    return generate_impl(c, prompt, n_prompt, pos, max_tokens, sampling->temperature, sampling->topp, rng_state, stop_token, cb, user, out_tokens, n_out, active ? &sp : nullptr);
+    const int cq = sharded(c) ? -1 : c->dfa_state;                    // an armed constraint counts as a control that is set: the shaped form runs, masking only
+    return generate_impl(c, prompt, n_prompt, pos, max_tokens, sampling->temperature, sampling->topp, rng_state, stop_token, cb, user, out_tokens, n_out, active || cq >= 0 ? &sp : nullptr, cq);
 }
 // flm_forward_sample with the controls and the caller's window (used as given).  Every control neutral: flm_forward_sample / flm_forward_argmax.
 int flm_forward_sample_ex(flm_ctx* c, const int32_t* tokens, int n, int pos, const flm_sampling* sampling, const int32_t* window, int n_window, uint64_t* rng_state, int32_t* next_token) {
@@ -1414,9 +1467,10 @@ int flm_forward_sample_ex(flm_ctx* c, const int32_t* tokens, int n, int pos, con
     const float temperature = sampling->temperature, topp = sampling->topp;
     const bool sampled = temperature != 0.0f;
     if (sampled && !rng_state) return fail(c, FLM_ERR_INVALID, "sample: rng_state must be given at temperature != 0");
-    if (!active) return sampled ? flm_forward_sample(c, tokens, n, pos, temperature, topp, rng_state, next_token) : flm_forward_argmax(c, tokens, n, pos, next_token);
+    const int cq = sharded(c) ? -1 : c->dfa_state;
+    if (!active && cq < 0) return sampled ? flm_forward_sample(c, tokens, n, pos, temperature, topp, rng_state, next_token) : flm_forward_argmax(c, tokens, n, pos, next_token);
     if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "shaped token: one GPU only");
-    return forward_draw(c, tokens, n, pos, Draw(temperature, topp, rng_state, &sp), next_token);
+    return forward_draw(c, tokens, n, pos, Draw(temperature, topp, rng_state, &sp, cq), next_token);
 }
 
 // Score a sequence: every position's logits in one batched pass, reduced on the device to a flm_score per row (flm_score.h).  The call is flm_forward's work plus the rows
@@ -1472,7 +1526,7 @@ int flm_score_tokens(flm_ctx* c, const int32_t* tokens, int n, int pos, const in
 // batch, and k_shape_rows shapes every row over its own window (the head ++ the drafts in front of the row) before it is drawn.  The shaped row is a function of (raw row,
 // window, controls) and the draw one of (shaped row, coin): row i is flm_forward_sample_ex's id behind first_token, a[0 .. i) for a caller who slides that window.
 static int verify_impl(flm_ctx* c, int32_t first_token, const int32_t* drafts, int k, int pos, float temperature, float topp, uint64_t* rng_state, int32_t* out_tokens, int* n_out,
-                       const ShapeParams* shape = nullptr) {
+                       const ShapeParams* shape = nullptr, int cq = -1) {
     if (!c || !drafts || !out_tokens || !n_out) return fail(c, FLM_ERR_INVALID, "verify: null argument");
     if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "verify: one GPU only");
     if (k < 4 || k > 15) return fail(c, FLM_ERR_INVALID, "verify: 4 <= k <= 15 drafts");
@@ -1489,7 +1543,7 @@ static int verify_impl(flm_ctx* c, int32_t first_token, const int32_t* drafts, i
         int r = shape ? set_shape(c, *shape) : FLM_OK; if (r) return r;
         r = h2d(c, c->prompt_dev, b, sizeof(int) * (size_t)(k + 1)); if (r) return r;
         SpecDraw sd{temperature, topp, sampled ? (unsigned long long)*rng_state : 0ull};
-        if (shape) { sd.shape = c->shape_p; sd.win = c->shape_p->head; sd.n_win = shape->n_head; }
+        if (shape) { sd.shape = c->shape_p; sd.win = c->shape_p->head; sd.n_win = shape->n_head; sd.cstate = cq; }
         r = spec_step(c, pos, k, 0, 0, -1, k + 1, false, sd); if (r) return r;
         return d2h(c, &so, c->spec_res, sizeof so);                                   // (the ids and the state in one trip; the error word rides along: xwg_check looks at it next)
     }, [&] {
@@ -1497,6 +1551,7 @@ static int verify_impl(flm_ctx* c, int32_t first_token, const int32_t* drafts, i
         *n_out = so.n_emit;
         if (sampled) { *rng_state = so.rng; c->sampled += so.n_emit; }
         if (shape) c->shaped += so.n_emit;
+        if (shape && cq >= 0) c->dfa_state = dfa_fold(c, cq, so.ids, so.n_emit);
     });
 }
 int flm_verify_greedy(flm_ctx* c, int32_t first_token, const int32_t* drafts, int k, int pos, int32_t* out_tokens, int* n_out) {
@@ -1518,7 +1573,8 @@ int flm_verify_sample_ex(flm_ctx* c, int32_t first_token, const int32_t* drafts,
     // window is empty
     const bool pen = sampling->repeat_penalty != 1.0f || sampling->frequency_penalty != 0.0f || sampling->presence_penalty != 0.0f;
     if (pen && sampling->penalty_last_n > 0) { sp.last_n = sampling->penalty_last_n; active = true; }
-    return verify_impl(c, first_token, drafts, k, pos, sampling->temperature, sampling->topp, rng_state, out_tokens, n_out, active ? &sp : nullptr);
+    const int cq = c->dfa_state;
+    return verify_impl(c, first_token, drafts, k, pos, sampling->temperature, sampling->topp, rng_state, out_tokens, n_out, active || cq >= 0 ? &sp : nullptr, cq);
 }
 
 // flm_generate with several ids per pass over the weights: the prompt enters as in flm_forward_argmax / flm_forward_sample (token 0 is drawn from its last logits, with the
@@ -1535,7 +1591,7 @@ int flm_verify_sample_ex(flm_ctx* c, int32_t first_token, const int32_t* drafts,
 // set_state has reset the step counter the follow form counts by).  Every step's inputs stay the history below n_hist, launch arguments and the block.
 static int generate_lookup_impl(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, int max_tokens, float temperature, float topp, uint64_t* rng_state,
                                 int32_t stop_token, int draft_len, int ngram_max, flm_token_cb cb, void* user, int32_t* out_tokens, int* n_out,
-                                const ShapeParams* shape = nullptr) {
+                                const ShapeParams* shape = nullptr, int cq = -1) {
     if (!c || !prompt || !n_out) return FLM_ERR_INVALID;
     if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "generate_lookup: one GPU only");
     if (max_tokens < 1 || !(temperature >= 0.0f) || topp != topp || stop_token >= c->d.vocab_size || draft_len < 4 || draft_len > 15 || ngram_max < 1 || ngram_max > 8)
@@ -1549,7 +1605,8 @@ static int generate_lookup_impl(flm_ctx* c, const int32_t* prompt, int n_prompt,
     int total = 0, steps = 0, accepted = 0; bool done = false, cancelled = false;
     int32_t last_tok = 0;
     uint64_t state = sampled ? *rng_state : 0;                       // the sampler's state behind the ids delivered so far
-    const Draw dr(temperature, topp, &state, shape);                 // (arms a token graph from THAT state)
+    const Draw dr(temperature, topp, &state, shape, cq);             // (arms a token graph from THAT state)
+    int cst = shape ? cq : -1;                                       // the constraint's state behind the ids delivered so far: the host folds every step's ids into it and passes the result on
     int32_t* const drawn = c->gen_ids.data();                        // shaped: the ids delivered so far, for the single-token steps' windows (pageable, max_seq_len ids, there since create)
     SpecOut so{};
     auto deliver = [&]() {                       // the step's ids, in index order, on this thread; the state moves with them
@@ -1560,6 +1617,7 @@ static int generate_lookup_impl(flm_ctx* c, const int32_t* prompt, int n_prompt,
             if (shape) drawn[index] = so.ids[i];
             if (cb && !cancelled && cb(user, index, so.ids[i], last ? 1 : 0) != 0) cancelled = true;
         }
+        if (cst >= 0) cst = dfa_fold(c, cst, so.ids, so.n_emit);
         total += so.n_emit; last_tok = so.ids[so.n_emit - 1]; state = so.rng;
         done = so.stopped || total >= max_tokens || cancelled;
     };
@@ -1579,7 +1637,7 @@ static int generate_lookup_impl(flm_ctx* c, const int32_t* prompt, int n_prompt,
             int r;
             if (batch) {
                 SpecDraw sd{temperature, topp, (unsigned long long)state};
-                if (shape) { sd.shape = c->shape_p; sd.win = c->spec_hist; sd.n_win = n_hist; }      // (the block: as token 0's attempt left it)
+                if (shape) { sd.shape = c->shape_p; sd.win = c->spec_hist; sd.n_win = n_hist; sd.cstate = cst; }      // (the block: as token 0's attempt left it)
                 r = spec_step(c, at, draft_len, ngram_max, n_hist, stop, room, true, sd);
             }
             else {      // one token through the token graph and the accept kernel with K = 0: the id from the decode state's first output slot, cut / appended / counted like a verified run of one
@@ -1588,7 +1646,7 @@ static int generate_lookup_impl(flm_ctx* c, const int32_t* prompt, int n_prompt,
                     const int w = one.last_n < n_hist ? one.last_n : n_hist;
                     for (int j = 0; j < w; ++j) { const int g = n_hist - w + j; one.head[j] = g < n_prompt ? prompt[g] : drawn[g - n_prompt]; }
                     one.n_head = w; one.follow = 0;
-                    r = Draw(temperature, topp, &state, &one).arm(c);
+                    r = Draw(temperature, topp, &state, &one, cst).arm(c);       // (and the constraint's block: {the folded state, 0})
                 }
                 else r = dr.arm(c);
                 if (r) return r;
@@ -1605,6 +1663,7 @@ static int generate_lookup_impl(flm_ctx* c, const int32_t* prompt, int n_prompt,
     *n_out = total;
     if (sampled) { *rng_state = state; c->sampled += total; }
     if (shape) c->shaped += total;
+    if (cst >= 0) c->dfa_state = cst;
     c->spec_steps = steps; c->spec_accepted = accepted;
     return FLM_OK;
 }
@@ -1627,8 +1686,51 @@ int flm_generate_lookup_ex(flm_ctx* c, const int32_t* prompt, int n_prompt, int 
     const int tail = n_prompt < FLM_PENALTY_WINDOW_MAX ? n_prompt : FLM_PENALTY_WINDOW_MAX;
     if (const char* why = shape_fill(sampling, c->d.vocab_size, prompt + (n_prompt - tail), tail, true, &sp, &active)) return fail(c, FLM_ERR_INVALID, why);
     if (sampling->temperature != 0.0f && !rng_state) return fail(c, FLM_ERR_INVALID, "sample: rng_state must be given at temperature != 0");
+    const int cq = c->dfa_state;
     return generate_lookup_impl(c, prompt, n_prompt, pos, max_tokens, sampling->temperature, sampling->topp, rng_state, stop_token, draft_len, ngram_max, cb, user, out_tokens, n_out,
-                                active ? &sp : nullptr);
+                                active || cq >= 0 ? &sp : nullptr, cq);
+}
+
+// Constrained decoding (include/flm_gpu.h): the automaton lives in ONE device allocation made here, off the steady path; the shaped token graphs reach it through the block
+// allocated at create, whose contents the launches below rewrite -- nothing is re-captured.
+int flm_dfa_validate(const flm_dfa* dfa, int vocab) {
+    if (const char* why = dfa_check(dfa, vocab)) { g_last_error = why; return FLM_ERR_INVALID; }
+    return FLM_OK;
+}
+int flm_constraint_set(flm_ctx* c, const flm_dfa* dfa) {
+    if (!c) return FLM_ERR_INVALID;
+    if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "constraint: one GPU only");
+    if (!model_complete(c)) return fail(c, FLM_ERR_STATE, "constraint_set before all tensors were uploaded");
+    if (dfa) if (const char* why = dfa_check(dfa, c->d.vocab_size)) return fail(c, FLM_ERR_INVALID, why);
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    int* fresh = nullptr;
+    if (dfa) {
+        const size_t ns = (size_t)dfa->n_states, ne = (size_t)dfa->n_edges, words = ns + 1 + 2 * ne;
+        if (hipMalloc((void**)&fresh, words * 4) != hipSuccess) { (void)hipGetLastError(); return fail(c, FLM_ERR_OOM, "constraint_set: out of device memory"); }
+        hipError_t e = hipMemcpyAsync(fresh, dfa->row_ptr, (ns + 1) * 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(fresh + ns + 1, dfa->edge_token, ne * 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(fresh + ns + 1 + ne, dfa->edge_next, ne * 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) { hipFree(fresh); HIPC(c, e); }
+        c->dfa_row.assign(dfa->row_ptr, dfa->row_ptr + ns + 1); c->dfa_tok.assign(dfa->edge_token, dfa->edge_token + ne); c->dfa_nxt.assign(dfa->edge_next, dfa->edge_next + ne);
+    } else { c->dfa_row.clear(); c->dfa_tok.clear(); c->dfa_nxt.clear(); }
+    int* const old = c->dfa_dev;
+    c->dfa_dev = fresh; c->dfa_state = -1;
+    int r = set_dfa(c, -1); if (r) return r;                                  // the block: the new arrays, disarmed
+    HIPC(c, hipStreamSynchronize(c->stream));
+    if (old) HIPC(c, hipFree(old));                                           // (behind the block's rewrite: no launch can still name the old arrays)
+    return FLM_OK;
+}
+int flm_constraint_arm(flm_ctx* c, int32_t state) {
+    if (!c) return FLM_ERR_INVALID;
+    const int ns = (int)c->dfa_row.size() - 1;
+    if (state != -1 && (ns < 1 || state < 0 || state >= ns)) return fail(c, FLM_ERR_INVALID, ns < 1 ? "constraint_arm: no automaton installed" : "constraint_arm: state outside [0, n_states)");
+    if (state == -1 && ns < 1) { c->dfa_state = -1; return FLM_OK; }
+    HIPC(c, hipSetDevice(c->device));
+    int r = set_dfa(c, state); if (r) return r;
+    c->dfa_state = state;
+    return FLM_OK;
 }
 
 // the ids the last flm_decode_greedy / flm_decode_sample / flm_decode_timed* call generated (still in device memory): out[n]

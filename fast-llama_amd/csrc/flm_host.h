@@ -160,6 +160,11 @@ struct flm_ctx {
     // flm_forward_sample_ex), the shaped row [vocab] the sampler reads in the shaped token form, and how many tokens this context drew through that form ("shaped_tokens")
     flm::ShapeParams* shape_p = nullptr; float* shape_row = nullptr; long long shaped = 0;
     flm::ShapeParams* shape_stage = nullptr;           // ... the block's own page-locked staging copy (the bounce buffer carries the prompt in the same call)
+    // constrained decoding (include/flm_gpu.h flm_constraint_set / _arm; the mask: flm_shape.h step 0): the device block the shaped token graphs reach the automaton
+    // through (allocated at create; only its contents change), the automaton's three arrays in ONE device allocation made by flm_constraint_set, the host copy the state is
+    // folded over after every call, and the armed state (-1: disarmed; "constraint_state")
+    flm::DfaBlock* dfa_blk = nullptr; int* dfa_dev = nullptr;
+    std::vector<int32_t> dfa_row, dfa_tok, dfa_nxt; int dfa_state = -1;
     // flm_generate (flm_gpu.hip): the granule ring [max_seq_len] and the cancel word -- page-locked, mapped, host-coherent memory allocated at create (gen_host; the device's view of it:
     // gen_ring_dev / gen_cancel_dev) --, what set_state writes into the decode state's generate words (gen_stop .. gen_max: -1 / 0 / 0 outside a flm_generate call), the
     // per-attempt sequence number the granules are tagged with, a pageable staging buffer for the ids, and the last call's figures ("gen_tokens" / "gen_streamed")
@@ -294,12 +299,13 @@ inline bool ids_in_vocab(const flm_ctx* c, const int32_t* ids, int n) {
 // How a call's tokens are drawn: the token form, the sampler's parameters, the caller's xorshift state and, for the shaped form, the shaper's parameter block (flm_gpu.hip)
 struct Draw {
     TokenForm form; float temperature, topp; uint64_t* rng_state; const flm::ShapeParams* shape;
+    int cstate = -1;                                              // the constraint's state at the call's first token (-1: none; only with a block: an armed constraint counts as a control)
     unsigned long long after = 0;                                 // the state an attempt left on the device (fetch); the caller's changes only behind a verified attempt (commit)
     // Greedy / Sampled by temperature, Shaped where a block is given
-    Draw(float t, float p, uint64_t* st, const flm::ShapeParams* sh = nullptr) : form(sh ? TokenForm::Shaped : t != 0.0f ? TokenForm::Sampled : TokenForm::Greedy), temperature(t), topp(p), rng_state(st), shape(sh) {}
+    Draw(float t, float p, uint64_t* st, const flm::ShapeParams* sh = nullptr, int cq = -1) : form(sh ? TokenForm::Shaped : t != 0.0f ? TokenForm::Sampled : TokenForm::Greedy), temperature(t), topp(p), rng_state(st), shape(sh), cstate(sh ? cq : -1) {}
     Draw(TokenForm f, float t, float p, uint64_t* st) : form(f), temperature(t), topp(p), rng_state(st), shape(nullptr) {}
     bool coins() const { return form == TokenForm::Sampled || (form == TokenForm::Shaped && temperature != 0.0f); }   // the caller's state is read and moved on
-    int arm(flm_ctx* c) const;             // an attempt's start: the shaper's block, then the sampler's parameters FROM THE CALLER'S STATE -- a retried attempt draws nothing twice
+    int arm(flm_ctx* c) const;             // an attempt's start: the shaper's block, the constraint's {state, 0}, then the sampler's parameters FROM THE CALLER'S STATE -- a retried attempt draws nothing twice
     int fetch(flm_ctx* c);                 // an attempt's end: the state behind its draws comes back
     void commit(flm_ctx* c, int n) const;  // a verified attempt of n tokens: the caller's state, "sampled_tokens" / "shaped_tokens"
 };
@@ -313,10 +319,14 @@ int score_classify(flm_ctx* c, int row0, int m, float* stage);
 // (draw: temperature, top-p and the step's xorshift state: k_sample_rows draws row row0 + i with that state's (row0 + i + 1)-th coin; temperature 0: k_argmax_rows)
 // shape (the device block) given: k_shape_rows shapes the chunk's rows in place in front of the draw, row i over the last min(last_n, n_win + i) ids of
 // win[0 .. n_win) ++ the batch's drafts in front of it (prompt_dev + 1); null: no shape kernel runs
-struct SpecDraw { float temperature, topp; unsigned long long base; const flm::ShapeParams* shape = nullptr; const int* win = nullptr; int n_win = 0; };
+struct SpecDraw { float temperature, topp; unsigned long long base; const flm::ShapeParams* shape = nullptr; const int* win = nullptr; int n_win = 0; int cstate = -1 /* the batch's base constraint state; -1: none */; };
 // k_shape_rows on `rows` rows (batch rows row0 ..) of n logits, ld floats apart -> out, ld_out apart (out == logits: in place); c may be null: flm_op_shape_rows
 int launch_shape_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, float* out, int ld_out, int n, int row0, int rows, const flm::ShapeParams* p,
-                      const int* win, int n_win, const int* drafts);
+                      const int* win, int n_win, const int* drafts, const flm::DfaBlock* dfa = nullptr, int cstate = -1, int* states_out = nullptr);
+// delta folded over ids[0 .. n) from state q on the context's host copy of the automaton (flm_gpu.hip; q in [0, n_states))
+int dfa_fold(const flm_ctx* c, int q, const int32_t* ids, int n);
+// the rules of flm_dfa_validate (flm_gpu.hip): null, or which one failed
+const char* dfa_check(const flm_dfa* dfa, int vocab);
 int spec_classify(flm_ctx* c, int row0, int m, float* stage, bool skinny, int* argmax_out, const SpecDraw& draw);
 // k_sample_rows on `rows` <= 16 rows of n logits, ld floats apart, batch rows row0 ..; sort_buf [rows][2][n] (flm_prompt.hip; c may be null: flm_op_sample_rows)
 int launch_sample_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, int n, int row0, int rows, float temperature, float topp, unsigned long long base,

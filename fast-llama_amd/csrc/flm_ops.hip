@@ -245,6 +245,41 @@ int flm_op_shape_rows(const float* logits, int rows, int ld, int n, const flm_sa
     return FLM_OK;
 }
 
+/* k_shape_rows with the constraint's step 0 in front -- the shaper of a verify batch on an armed context -- on caller-supplied rows, window, drafts and automaton */
+int flm_op_constrain_rows(const float* logits, int rows, int ld, int n, const flm_sampling* sampling, const int32_t* window, int n_window, const int32_t* drafts,
+                          const flm_dfa* dfa, int32_t state, float* out, int32_t* states_out) {
+    if (!logits || !out || !states_out || rows < 1 || rows > kSpecRows || n < 2 || ld < n || (rows > 1 && !drafts)) return FLM_ERR_INVALID;
+    ShapeParams sp; bool active = false;
+    if (const char* why = shape_fill(sampling, n, window, n_window, false, &sp, &active)) { g_last_error = why; return FLM_ERR_INVALID; }
+    if (const char* why = dfa_check(dfa, n)) { g_last_error = why; return FLM_ERR_INVALID; }
+    if (state < 0 || state >= dfa->n_states) { g_last_error = "constrain_rows: state outside [0, n_states)"; return FLM_ERR_INVALID; }
+    for (int i = 0; i + 1 < rows; ++i) if (drafts[i] < 0 || drafts[i] >= n) { g_last_error = "constrain_rows: draft outside [0, n)"; return FLM_ERR_INVALID; }
+    const bool pen = sampling->repeat_penalty != 1.0f || sampling->frequency_penalty != 0.0f || sampling->presence_penalty != 0.0f;
+    sp.last_n = pen ? sampling->penalty_last_n : 0;
+    int32_t d[kSpecRows] = {0};
+    for (int i = 0; i + 1 < rows; ++i) d[i] = drafts[i];
+    const size_t ns = (size_t)dfa->n_states, ne = (size_t)dfa->n_edges;
+    DevBuf dl, dout, dp, dd, da, db, ds;
+    if (dl.alloc((size_t)rows * ld * 4) || dout.alloc((size_t)rows * n * 4) || dp.alloc(sizeof sp) || dd.alloc(sizeof d) || da.alloc((ns + 1 + 2 * ne) * 4) ||
+        db.alloc(sizeof(DfaBlock)) || ds.alloc((size_t)kSpecRows * 4)) return FLM_ERR_OOM;
+    OPC(hipMemcpy(dl.p, logits, (size_t)rows * ld * 4, hipMemcpyHostToDevice));
+    OPC(hipMemcpy(dp.p, &sp, sizeof sp, hipMemcpyHostToDevice));
+    OPC(hipMemcpy(dd.p, d, sizeof d, hipMemcpyHostToDevice));
+    int* arr = da.as<int>();
+    OPC(hipMemcpy(arr, dfa->row_ptr, (ns + 1) * 4, hipMemcpyHostToDevice));
+    OPC(hipMemcpy(arr + ns + 1, dfa->edge_token, ne * 4, hipMemcpyHostToDevice));
+    OPC(hipMemcpy(arr + ns + 1 + ne, dfa->edge_next, ne * 4, hipMemcpyHostToDevice));
+    DfaBlock blk{}; blk.row_ptr = arr; blk.edge_token = arr + ns + 1; blk.edge_next = arr + ns + 1 + ne; blk.n_states = dfa->n_states; blk.q = -1;
+    OPC(hipMemcpy(db.p, &blk, sizeof blk, hipMemcpyHostToDevice));
+    OPC(hipMemset(ds.p, 0xff, (size_t)kSpecRows * 4));
+    const ShapeParams* p = dp.as<ShapeParams>();
+    int r = launch_shape_rows(nullptr, 0, dl.as<float>(), ld, dout.as<float>(), n, n, 0, rows, p, p->head, sp.n_head, dd.as<int>(), db.as<DfaBlock>(), state, ds.as<int>()); if (r) return r;
+    OPC(hipDeviceSynchronize());
+    OPC(hipMemcpy(out, dout.p, (size_t)rows * n * 4, hipMemcpyDeviceToHost));
+    OPC(hipMemcpy(states_out, ds.p, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    return FLM_OK;
+}
+
 /* k_score_rows -- the statistics kernel of flm_score_tokens -- on caller-supplied rows of logits */
 int flm_op_score_rows(const float* logits, int rows, int n, const int32_t* targets, flm_score* out) {
     if (!logits || !out || rows < 1 || n < 2) return FLM_ERR_INVALID;

@@ -241,9 +241,9 @@ int launch_sample_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, 
     return FLM_OK;
 }
 int launch_shape_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, float* out, int ld_out, int n, int row0, int rows, const ShapeParams* p,
-                      const int* win, int n_win, const int* drafts) {
+                      const int* win, int n_win, const int* drafts, const DfaBlock* dfa, int cstate, int* states_out) {
     if (rows < 1 || row0 < 0 || row0 + rows > kSpecRows) return fail(c, FLM_ERR_INVALID, "shape_rows: rows outside a batch of 16");
-    const ShapeRowsArgs a{logits, ld, out, ld_out, n, row0, p, win, n_win, drafts};
+    const ShapeRowsArgs a{logits, ld, out, ld_out, n, row0, p, win, n_win, drafts, dfa, dfa ? cstate : -1, states_out};
     hipLaunchKernelGGL(k_shape_rows, dim3(rows), dim3(kSampleBlock), 0, st, a);
     HIPC(c, hipGetLastError());
     return FLM_OK;
@@ -264,7 +264,7 @@ static int score_classify_t(flm_ctx* c, int row0, int m, float* stage, bool skin
     GemmArgs g{c->cls.q, c->cls.s, c->pf_xq, c->pf_xs, stage, V, dim, V, m, c->pf_xst, c->cls.st};
     r = launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, skinny && m <= kSkinnyTokens); if (r) return r;
     if (argmax_out && draw && draw->shape) {                  // a control is set: the chunk's rows shaped in place, each over its own window, in front of the draw
-        r = launch_shape_rows(c, st, stage, V, stage, V, V, row0, m, draw->shape, draw->win, draw->n_win, c->prompt_dev + 1); if (r) return r;
+        r = launch_shape_rows(c, st, stage, V, stage, V, V, row0, m, draw->shape, draw->win, draw->n_win, c->prompt_dev + 1, c->dfa_blk, draw->cstate); if (r) return r;
     }
     if (argmax_out && draw && draw->temperature != 0.0f)      // the sampled verify pass: row row0 + i drawn with the (row0 + i + 1)-th coin of the step's state
         return launch_sample_rows(c, st, stage, V, V, row0, m, draw->temperature, draw->topp, draw->base, c->sort_buf, argmax_out);

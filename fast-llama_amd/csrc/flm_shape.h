@@ -4,6 +4,9 @@
 // into the shaped row S (a row of its own, vocab floats, allocated at flm_ctx_create) that the UNCHANGED sampler (flm_sample.h sample_draw) then reads.  No reference
 // counterpart: the reference samples with temperature and top-p only.  The definition (restated sequentially in host/sampler.cpp shape_logits, which this
 // kernel equals bit for bit), all arithmetic fp32 round-to-nearest without contraction:
+//   0 constraint a context armed with a token-level DFA at state q (the host restatement: host/sampler.cpp constrain_logits): S = L; S[i] = -inf for
+//                every i without an edge in q.  The state's sorted edge list is scattered, 32768 indices at a time, into a bit map in the `hist` area (free until top-k) with
+//                integer LDS atomics; one pass clears what has no bit.  A masked entry stays -inf under steps 1 - 4 (-inf + b = -inf for every allowed bias)
 //   1 bias       S = L; S[id] += b for each of n_bias distinct ids (b finite or -inf)
 //   2 penalties  for every DISTINCT id t of the window W[0 .. w), c = its occurrences: x = S[t]; repeat_penalty != 1: x = x > 0 ? x / rp : x * rp; frequency or presence
 //                != 0: x = x - ((float)c * fp + pp); S[t] = x.  Window entry j belongs to thread j; the thread of an id's FIRST occurrence counts and writes: no order dependence
@@ -40,11 +43,28 @@ struct ShapeParams {
     int bias_ids[kShapeBiasMax]; float bias_vals[kShapeBiasMax];
     int head[kShapeWindowMax];
 };
+// The constraint's device block (allocated at flm_ctx_create; flm_constraint_set / flm_constraint_arm / Draw::arm rewrite its contents, so the token graphs captured at
+// flm_prepare with its ADDRESS as their argument follow an automaton that arrives or changes later).  CSR: the edges of state s are [row_ptr[s], row_ptr[s + 1]), their tokens
+// strictly ascending (flm_dfa_validate).  q: the state of the token at generated step `applied` (-1: disarmed); k_shape_logits moves the pair on
+struct DfaBlock {
+    const int* row_ptr; const int* edge_token; const int* edge_next;
+    int n_states;
+    int q, applied;
+    int pad_;
+};
+// delta(q, t): the edge_next of t's edge in q (binary search in the sorted list), q itself where t has no edge there.  q in [0, n_states)
+__device__ __forceinline__ int dfa_step(const DfaBlock* d, const int ns, const int q, const int t) {
+    int lo = d->row_ptr[q], hi = d->row_ptr[q + 1];
+    while (lo < hi) { const int mid = lo + ((hi - lo) >> 1); if (d->edge_token[mid] < t) lo = mid + 1; else hi = mid; }
+    if (lo < d->row_ptr[q + 1] && d->edge_token[lo] == t) return min(max(d->edge_next[lo], 0), ns - 1);
+    return q;
+}
 struct ShapeArgs {
     const float* logits; float* out; int n;
     const ShapeParams* p;
     const DecodeState* st;                 // the latch and, under follow, the step; null: flm_op_shape_logits
     const int* out_tokens; int out_cap;
+    DfaBlock* dfa;                         // the constraint's block (q < 0: none); null: flm_op_shape_logits
 };
 
 // larger float <-> larger key; -0.0 and +0.0 share a key
@@ -58,21 +78,42 @@ __device__ __forceinline__ unsigned shape_key(float x) {
 struct ShapeLds {
     int win[kShapeWindowMax];
     int hist[4 * 256];
-    int misc[64];                          // [0..15] per-wave words, [16] digit, [17] rem, [18] equal-count, [20..35] per-wave floats
+    int misc[64];                          // [0..15] per-wave words, [16] digit, [17] rem, [18] equal-count, [20..35] per-wave floats, [40] the constraint's state
 };
+constexpr int kMaskChunk = 4 * 256 * 32;   // indices one bit map in ShapeLds::hist covers
+// one state's edge list (step 0's allowed ids); ne < 0: no constraint
+struct ShapeMask { const int* tok; int ne; };
 // The window of one row: entry j = element skip + j of a[0 .. na) followed by b[..], j < w; both kernels below describe their window this way (k_shape_logits: the block's
 // head and the ids drawn so far; k_shape_rows: the base window and the batch's drafts in front of the row)
 struct ShapeWindow { const int* a; int na; const int* b; int skip; int w; };
 
-// Steps 1 - 4 of the definition on ONE row, by one 1024-thread workgroup: L[0 .. n) -> S[0 .. n) (S == L: shaped in place, the copy is skipped).  THE definition: k_shape_logits
-// (the shaped token form) and k_shape_rows (the rows of a verify batch) are both this function behind their own window arithmetic
-__device__ __forceinline__ void shape_row(const float* L, float* S, const int n, const ShapeParams* p, const ShapeWindow wd, ShapeLds& lds) {
+// Steps 0 - 4 of the definition on ONE row, by one 1024-thread workgroup: L[0 .. n) -> S[0 .. n) (S == L: shaped in place, the copy is skipped).  THE definition: k_shape_logits
+// (the shaped token form) and k_shape_rows (the rows of a verify batch) are both this function behind their own window and state arithmetic
+__device__ __forceinline__ void shape_row(const float* L, float* S, const int n, const ShapeParams* p, const ShapeWindow wd, const ShapeMask mk, ShapeLds& lds) {
     int* const win = lds.win; int* const hist = lds.hist; int* const misc = lds.misc;
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
     // 1: the copy, then the biases (distinct ids: one writer per entry)
     if (S != L) {
         for (int i = t; i < n; i += kSampleBlock) S[i] = L[i];
         __syncthreads();
+    }
+    // 0: the constraint.  Per chunk of 32768 indices: clear the bit map, the threads stride over the edge list and set the bits of the tokens inside the chunk, one pass
+    // writes -inf where the bit is clear.  Any list length, any n; the order in which waves run changes nothing (OR is commutative)
+    if (mk.ne >= 0) {
+        unsigned* const bitmap = (unsigned*)hist;
+#pragma unroll 1
+        for (int c0 = 0; c0 < n; c0 += kMaskChunk) {
+            bitmap[t] = 0u;                // (4 * 256 words, kSampleBlock threads)
+            __syncthreads();
+            for (int e = t; e < mk.ne; e += kSampleBlock) {
+                const unsigned o = (unsigned)(mk.tok[e] - c0);
+                if (o < (unsigned)kMaskChunk) atomicOr(&bitmap[o >> 5], 1u << (o & 31u));
+            }
+            __syncthreads();
+            const int c1 = min(n, c0 + kMaskChunk);
+            for (int i = c0 + t; i < c1; i += kSampleBlock) { const unsigned o = (unsigned)(i - c0); if (!((bitmap[o >> 5] >> (o & 31u)) & 1u)) S[i] = -INFINITY; }
+            __syncthreads();
+        }
     }
     const int nb = min(p->n_bias, kShapeBiasMax);
     if (t < nb) { const int id = p->bias_ids[t]; if ((unsigned)id < (unsigned)n) S[id] = __fadd_rn(S[id], p->bias_vals[t]); }
@@ -194,7 +235,28 @@ inline __global__ void __launch_bounds__(kSampleBlock) k_shape_logits(const Shap
         w = min(min(max(p->last_n, 0), kShapeWindowMax), total);
         skip = total - w;
     }
-    shape_row(a.logits, a.out, a.n, p, ShapeWindow{p->head, nh, a.out_tokens, skip, w}, lds);
+    // the constraint: thread 0 moves {q, applied} on over the ids drawn since (out_tokens[applied .. s): normally one), stores the pair and hands q to the workgroup.  A
+    // retried attempt starts from the pair Draw::arm wrote, {the armed state, 0}, and rebuilds the same states from the ids it draws again
+    ShapeMask mk{nullptr, -1};
+    if (a.dfa != nullptr) {
+        static_assert(kSampleBlock == 4 * 256, "one bit-map word per thread");
+        if (threadIdx.x == 0) {
+            DfaBlock* d = a.dfa;
+            const int ns = d->n_states;
+            int q = d->q;
+            if (q >= 0 && ns > 0) {
+                q = min(q, ns - 1);
+                const int s = (p->follow && a.st) ? min(max(a.st->step, 0), a.out_cap) : 0;
+                for (int j = min(max(d->applied, 0), s); j < s; ++j) q = dfa_step(d, ns, q, a.out_tokens[j]);
+                d->q = q; d->applied = s;
+            } else q = -1;
+            lds.misc[40] = q;
+        }
+        __syncthreads();
+        const int q = lds.misc[40];
+        if (q >= 0) { const int e0 = a.dfa->row_ptr[q]; mk.tok = a.dfa->edge_token + e0; mk.ne = a.dfa->row_ptr[q + 1] - e0; }
+    }
+    shape_row(a.logits, a.out, a.n, p, ShapeWindow{p->head, nh, a.out_tokens, skip, w}, mk, lds);
 }
 
 // The shaper over the rows of a verify batch's classifier chunk: one 1024-thread workgroup per row, grid = the chunk's rows (<= 16); block r shapes batch row row0 + r (the
@@ -208,6 +270,9 @@ struct ShapeRowsArgs {
     const ShapeParams* p;                  // the controls, the bias pairs, last_n
     const int* base; int n_base;           // flm_verify_sample_ex: the caller's window (the block's head); flm_generate_lookup_ex: the call's history
     const int* drafts;                     // the batch's drafts d[0 .. 15): row i looks at d[0 .. i)
+    // the constraint: the batch's base state as a launch argument (-1: none), like n_base and the coin state; row i is masked in delta folded over d[0 .. i) from it -- the
+    // loop's state for that token exactly when the accept step keeps the row (the windows' argument).  states_out (may be null; flm_op_constrain_rows): [16], row i's state
+    const DfaBlock* dfa; int state; int* states_out;
 };
 inline __global__ void __launch_bounds__(kSampleBlock) k_shape_rows(const ShapeRowsArgs a) {
     __shared__ ShapeLds lds;
@@ -215,7 +280,23 @@ inline __global__ void __launch_bounds__(kSampleBlock) k_shape_rows(const ShapeR
     const int nbase = max(a.n_base, 0);
     const int total = nbase + row;
     const int w = min(min(max(a.p->last_n, 0), kShapeWindowMax), total);
-    shape_row(a.logits + (size_t)r * a.ld, a.out + (size_t)r * a.ld_out, a.n, a.p, ShapeWindow{a.base, nbase, a.drafts, total - w, w}, lds);
+    ShapeMask mk{nullptr, -1};
+    if (a.dfa != nullptr && a.state >= 0) {
+        if (threadIdx.x == 0) {            // at most 15 searches: cheaper than a dependency between the rows, as with the xorshift steps
+            const int ns = a.dfa->n_states;
+            int q = -1;
+            if (ns > 0) {
+                q = min(a.state, ns - 1);
+                for (int j = 0; j < row; ++j) q = dfa_step(a.dfa, ns, q, a.drafts[j]);
+                if (a.states_out) a.states_out[row] = q;
+            }
+            lds.misc[40] = q;
+        }
+        __syncthreads();
+        const int q = lds.misc[40];
+        if (q >= 0) { const int e0 = a.dfa->row_ptr[q]; mk.tok = a.dfa->edge_token + e0; mk.ne = a.dfa->row_ptr[q + 1] - e0; }
+    }
+    shape_row(a.logits + (size_t)r * a.ld, a.out + (size_t)r * a.ld_out, a.n, a.p, ShapeWindow{a.base, nbase, a.drafts, total - w, w}, mk, lds);
 }
 
 } // namespace flm

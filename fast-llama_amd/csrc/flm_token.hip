@@ -375,7 +375,7 @@ layers_done:
         if (form == TokenForm::Shaped) {   // a shaped token: the shaper writes the shaped row, the sampler (unchanged) draws from it
             if (tp) return fail(c, FLM_ERR_UNSUPPORTED, "shaped token: one GPU only");
             ShapeArgs ha{};
-            ha.logits = c->logits; ha.out = c->shape_row; ha.n = d.vocab_size; ha.p = c->shape_p; ha.st = c->state; ha.out_tokens = c->out_tokens_dev; ha.out_cap = c->out_cap;
+            ha.logits = c->logits; ha.out = c->shape_row; ha.n = d.vocab_size; ha.p = c->shape_p; ha.st = c->state; ha.out_tokens = c->out_tokens_dev; ha.out_cap = c->out_cap; ha.dfa = c->dfa_blk;
             hipLaunchKernelGGL(k_shape_logits, dim3(1), dim3(kSampleBlock), 0, st, ha);
             HIPC(c, hipGetLastError());
             Tick t(c, st, KC_ARGMAX);

@@ -188,6 +188,12 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
             if (bad) { _err = "--logit-bias: an id outside [0, vocab) or listed twice"; return false; }
         }
     }
+    flm_dfa dfa{};
+    if (_dfa_set) {         // against THIS model's vocabulary, here and not only in flm_constraint_set: the host loop below walks the arrays directly
+        dfa.n_states = (int32_t)_dfa_row.size() - 1; dfa.n_edges = (int32_t)_dfa_tok.size();
+        dfa.row_ptr = _dfa_row.data(); dfa.edge_token = _dfa_tok.data(); dfa.edge_next = _dfa_nxt.data();
+        if (flm_dfa_validate(&dfa, _cfg.vocab_size) != FLM_OK) { _err = std::string("--constraint: ") + flm_last_error(nullptr); return false; }
+    }
     printf("Input prompt:%s\n", prompt);
     print_vector("Input tokens:", input);
     const int n_in = (int)input.size();
@@ -232,7 +238,15 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
             if (rc == FLM_OK && flm_query(_ctxs[0], "spec_steps", &v) == FLM_OK) _lookup_steps += v;
             if (rc == FLM_OK && flm_query(_ctxs[0], "spec_accepted", &v) == FLM_OK) _lookup_accepted += v;
         };
-        if (_shape_set) {                   // the sampling controls: the same loop with the shaping stage on the device (flm_generate_ex); refused: the host loop below shapes
+        bool armed = false;                 // --constraint: installed once, armed at state 0 before every run; refused (nothing was launched): the host loop below masks
+        if (_dfa_set) {
+            int cr = _dfa_installed ? FLM_OK : flm_constraint_set(_ctxs[0], &dfa);
+            if (cr == FLM_OK) { _dfa_installed = true; cr = flm_constraint_arm(_ctxs[0], 0); }
+            if (cr != FLM_OK && cr != FLM_ERR_UNSUPPORTED) { _err = std::string("--constraint: ") + flm_last_error(_ctxs[0]); fprintf(stderr, "%s\n", _err.c_str()); return false; }
+            armed = cr == FLM_OK;
+        }
+        const bool dev_ok = !_dfa_set || armed;
+        if (dev_ok && (_shape_set || armed)) {          // the sampling controls / the constraint: the same loop with the shaping stage on the device (flm_generate_ex; no control flag: neutral controls, masking only); refused: the host loop below shapes
             flm_sampling sp{};
             sp.temperature = temperature; sp.topp = topp; sp.top_k = _shape.top_k; sp.min_p = _shape.min_p; sp.repeat_penalty = _shape.repeat_penalty;
             sp.frequency_penalty = _shape.frequency_penalty; sp.presence_penalty = _shape.presence_penalty; sp.penalty_last_n = _shape_last_n;
@@ -247,7 +261,7 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
             if (rc == FLM_ERR_UNSUPPORTED) rc = flm_generate_ex(_ctxs[0], input.data(), n_in, 0, want, &sp, &st, 0, on_token, &sink, nullptr, &n_out);
             if (rc == FLM_ERR_INVALID) { _err = flm_last_error(_ctxs[0]); fprintf(stderr, "%s\n", _err.c_str()); }
             whole = false;
-        } else if (_draft_k > 0 || (greedy && _lookup_k > 0)) {
+        } else if (dev_ok && (_draft_k > 0 || (greedy && _lookup_k > 0))) {
             // --draft: the same loop through draft-and-verify steps at the run's temperature; refused (nothing was launched): the run without the flag.
             // --lookup: the same at temperature 0 only (the same ids and callbacks)
             const bool draft = _draft_k > 0;
@@ -255,6 +269,7 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
             count();
             whole = draft && rc == FLM_ERR_UNSUPPORTED;
         }
+        if (!dev_ok) { whole = false; rc = FLM_ERR_UNSUPPORTED; }
         if (whole) rc = flm_generate(_ctxs[0], input.data(), n_in, 0, want, temperature, topp, &st, 0, on_token, &sink, nullptr, &n_out);
         if (rc == FLM_OK) { if (!greedy) _sampler.set_state(st); return true; }
         if (rc != FLM_ERR_UNSUPPORTED) return false;
@@ -262,7 +277,8 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
     }
     // the sampling controls where the loop is the host's: the logits come back, shape_logits runs over the window (the last penalty_last_n ids of the prompt and what was
     // generated since), then the host sampler -- what flm_generate_ex computes on the device
-    const bool shaped = _shape_set;
+    const bool shaped = _shape_set || _dfa_set;
+    int q = 0;                              // --constraint on the host: the automaton's state, from 0
     std::vector<int32_t> history;
     if (shaped) history.assign(input.begin(), input.end());
     std::vector<float> shaped_row(shaped ? _cfg.vocab_size : 0);
@@ -321,8 +337,10 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
             rc = on_all([&](int r) { return flm_forward(_ctxs[r], cur.data(), (int)cur.size(), i, r == 0 ? logits.data() : lgs[r].data()); });
             if (rc == FLM_OK && shaped) {
                 const int w = (int)history.size() < _shape_last_n ? (int)history.size() : _shape_last_n;
+                if (_dfa_set) constrain_logits(logits.data(), _cfg.vocab_size, _dfa_tok.data() + _dfa_row[q], _dfa_row[q + 1] - _dfa_row[q], logits.data());      // step 0, in place
                 shape_logits(logits.data(), _cfg.vocab_size, temperature, _shape, history.data() + (history.size() - w), w, shaped_row.data());
                 next = _sampler.sample(shaped_row.data(), temperature, topp);
+                if (_dfa_set) q = dfa_next(_dfa_row.data(), _dfa_tok.data(), _dfa_nxt.data(), q, next);
                 history.push_back(next);
             } else if (rc == FLM_OK) next = _sampler.sample(logits.data(), temperature, topp);
         }

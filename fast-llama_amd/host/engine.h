@@ -48,6 +48,12 @@ public:
         _shape.n_bias = (int)_bias_ids.size(); _shape.bias_ids = _bias_ids.data(); _shape.bias_values = _bias_values.data();
         _shape_set = true;
     }
+    // --constraint FILE (this build only): a token-level DFA (flm_dfa; the text format of capi.Dfa.save) masks every generated token's logits.  One device: installed with
+    // flm_constraint_set, armed at state 0 before every generate; the run is flm_generate_ex / flm_generate_lookup_ex (neutral controls where no control flag was given).
+    // Where the engine samples on the host (the library refuses, several devices) it calls constrain_logits and dfa_next itself: the same ids.
+    void set_constraint(std::vector<int32_t> row_ptr, std::vector<int32_t> edge_token, std::vector<int32_t> edge_next) {
+        _dfa_row = std::move(row_ptr); _dfa_tok = std::move(edge_token); _dfa_nxt = std::move(edge_next); _dfa_set = true; _dfa_installed = false;
+    }
     int lookup_steps() const { return _lookup_steps; }
     int lookup_accepted() const { return _lookup_accepted; }
     int get_quant_type() const { return _cfg.quant_type; }
@@ -71,6 +77,7 @@ private:
     std::string _err;
     int _lookup_k = 0, _lookup_g = 3, _lookup_steps = 0, _lookup_accepted = 0;
     int _draft_k = 0, _draft_g = 3;
+    bool _dfa_set = false, _dfa_installed = false; std::vector<int32_t> _dfa_row, _dfa_tok, _dfa_nxt;
     bool _shape_set = false; ShapeControls _shape; int _shape_last_n = 0; std::vector<int32_t> _bias_ids; std::vector<float> _bias_values;
 };
 

@@ -10,6 +10,7 @@
 #include <string.h>
 #include <strings.h>
 
+#include <algorithm>
 #include <chrono>
 #include <initializer_list>
 #include <iostream>
@@ -39,6 +40,8 @@ struct Args {
     // the sampling controls (flm_sampling): any of these flags switches the shaping stage on
     bool shape_set = false; ShapeControls shape; int repeat_last_n = 64;
     std::vector<int32_t> bias_ids; std::vector<float> bias_values; const char* bad_sampling = nullptr;
+    const char* constraint = nullptr;       // --constraint FILE: a token-level DFA in the `flm-dfa 1 <n_states>` text format
+    std::vector<int32_t> dfa_row, dfa_tok, dfa_nxt;
     Mode mode = Mode::GEN;
 };
 const char* Y = "\x1b[33m"; const char* G = "\x1b[32m"; const char* E = "\x1b[0m";
@@ -66,6 +69,7 @@ void usage(const char* bin) {
     fprintf(stderr, "   --presence-penalty  <float>   subtracted once from every token of the window, 0 = off (this build only)\n");
     fprintf(stderr, "   --frequency-penalty <float>   subtracted per occurrence in the window, 0 = off (this build only)\n");
     fprintf(stderr, "   --logit-bias      <id=val[,id=val...]>  added to these tokens' logits; -inf bans a token; at most 256 pairs (this build only)\n");
+    fprintf(stderr, "   --constraint      <file>      mask every generated token with a token-level DFA, armed at state 0: a `flm-dfa 1 <n_states>` line, then `state token next` per line (this build only)\n");
     fprintf(stderr, "   --encode,-e       <string>    encode the input string into tokens\n");
     fprintf(stderr, "   --decode,-d       <string>    decode the input tokens to text\n");
     fprintf(stderr, "   --help,-h                     print this message\n");
@@ -147,6 +151,7 @@ const Flag kFlags[] = {
     {nullptr, "--repeat-last-n",     true, [](Args& a, const char* v) { char* e; const long k = strtol(v, &e, 10); a.shape_set = true; if (e == v || *e || k < 0 || k > 1024) a.bad_sampling = v; else a.repeat_last_n = (int)k; }},         // (this build only)
     {nullptr, "--presence-penalty",  true, [](Args& a, const char* v) { a.shape_set = true; if (!parse_float(v, a.shape.presence_penalty) || a.shape.presence_penalty != a.shape.presence_penalty) a.bad_sampling = v; }},               // (this build only)
     {nullptr, "--frequency-penalty", true, [](Args& a, const char* v) { a.shape_set = true; if (!parse_float(v, a.shape.frequency_penalty) || a.shape.frequency_penalty != a.shape.frequency_penalty) a.bad_sampling = v; }},            // (this build only)
+    {nullptr, "--constraint",        true, [](Args& a, const char* v) { a.constraint = v; }},                                                                                                                                      // (this build only)
     {nullptr, "--logit-bias",        true, [](Args& a, const char* v) { a.shape_set = true; if (!parse_bias(v, a.bias_ids, a.bias_values)) a.bad_sampling = v; }},                                                                      // (this build only)
 };
 }
@@ -166,6 +171,34 @@ void parse(Args& a, int argc, const char** argv) {
     if (a.bad_draft) { fprintf(stderr, "Invalid --draft:\x1b[31m%s\x1b[0m (expected K or K,G with 4 <= K <= 15 and 1 <= G <= 8)\n", a.bad_draft); usage(argv[0]); exit(-1); }
     if (a.bad_sampling) { fprintf(stderr, "Invalid sampling control:\x1b[31m%s\x1b[0m (--top-k >= 0, --min-p in [0, 1), --repeat-penalty > 0, --repeat-last-n 0..1024, --logit-bias id=val[,id=val...] with at most 256 pairs)\n", a.bad_sampling); usage(argv[0]); exit(-1); }
     if (a.rounds < 1) a.rounds = a.mode == Mode::TEST ? 16 : 1;
+}
+
+// --constraint FILE -> CSR arrays sorted by (state, token); false with `why` set for anything that is not the format or breaks a rule of flm_dfa_validate that needs no
+// vocabulary (the token bound is checked against the model's once it is loaded)
+bool load_constraint(const char* path, Args& a, std::string& why) {
+    FILE* f = fopen(path, "r");
+    if (!f) { why = "cannot open the file"; return false; }
+    char tag[16] = {0}; int ver = 0, ns = 0;
+    struct Edge { long q, t, n; };
+    std::vector<Edge> edges;
+    bool ok = fscanf(f, "%15s %d %d", tag, &ver, &ns) == 3 && !strcmp(tag, "flm-dfa") && ver == 1 && ns >= 1 && ns <= FLM_DFA_STATES_MAX;
+    if (!ok) why = "the first line must be `flm-dfa 1 <n_states>` with 1 <= n_states <= 65536";
+    while (ok) {
+        Edge e; const int got = fscanf(f, "%ld %ld %ld", &e.q, &e.t, &e.n);
+        if (got == EOF) break;
+        ok = got == 3 && e.q >= 0 && e.q < ns && e.t >= 0 && e.t <= 0x7ffffffe && e.n >= 0 && e.n < ns && edges.size() < (size_t)FLM_DFA_EDGES_MAX;
+        if (!ok) why = "every further line must be `state token next` with both states in [0, n_states) and token >= 0";
+        else edges.push_back(e);
+    }
+    fclose(f);
+    if (!ok) return false;
+    std::sort(edges.begin(), edges.end(), [](const Edge& x, const Edge& y) { return x.q != y.q ? x.q < y.q : x.t < y.t; });
+    a.dfa_row.assign(ns + 1, 0);
+    for (const Edge& e : edges) { a.dfa_row[e.q + 1] += 1; a.dfa_tok.push_back((int32_t)e.t); a.dfa_nxt.push_back((int32_t)e.n); }
+    for (int q = 0; q < ns; ++q) a.dfa_row[q + 1] += a.dfa_row[q];
+    flm_dfa d{ns, (int32_t)edges.size(), a.dfa_row.data(), a.dfa_tok.data(), a.dfa_nxt.data()};
+    if (flm_dfa_validate(&d, 0x7fffffff) != FLM_OK) { why = flm_last_error(nullptr); return false; }
+    return true;
 }
 
 int64_t now_us() { return std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::high_resolution_clock::now().time_since_epoch()).count(); }
@@ -208,7 +241,12 @@ int main(int argc, const char** argv) {
         fprintf(stderr, "warning: --draft applies to one device only; ignored\n");
         args.draft_k = 0;
     }
+    if (args.constraint) {                  // a malformed file is a usage error, before any model is loaded
+        std::string why;
+        if (!load_constraint(args.constraint, args, why)) { fprintf(stderr, "Invalid --constraint file:\x1b[31m%s\x1b[0m (%s)\n", args.constraint, why.c_str()); usage(argv[0]); return -1; }
+    }
     GpuTransformer tf(args.detail || args.debug);
+    if (args.constraint) tf.set_constraint(args.dfa_row, args.dfa_tok, args.dfa_nxt);
     if (args.shape_set) tf.set_sampling(args.shape, args.repeat_last_n, args.bias_ids, args.bias_values);
     if (args.lookup_k) tf.set_lookup(args.lookup_k, args.lookup_g);
     if (args.draft_k) tf.set_draft(args.draft_k, args.draft_g);

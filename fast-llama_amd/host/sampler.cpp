@@ -90,4 +90,17 @@ void shape_logits(const float* L, int n, float temperature, const ShapeControls&
     }
 }
 
+void constrain_logits(const float* L, int n, const int32_t* tokens, int count, float* S) {
+    int e = 0;
+    for (int i = 0; i < n; ++i) {
+        while (e < count && tokens[e] < i) ++e;
+        S[i] = (e < count && tokens[e] == i) ? L[i] : -INFINITY;
+    }
+}
+
+int dfa_next(const int32_t* row_ptr, const int32_t* edge_token, const int32_t* edge_next, int q, int t) {
+    for (int e = row_ptr[q]; e < row_ptr[q + 1]; ++e) if (edge_token[e] == t) return edge_next[e];
+    return q;
+}
+
 } // namespace flmhost

@@ -34,4 +34,12 @@ struct ShapeControls {
 };
 void shape_logits(const float* L, int n, float temperature, const ShapeControls& c, const int32_t* window, int n_window, float* S);
 
+// Constrained decoding (include/flm_gpu.h, flm_dfa): step 0 of the shaping definition and the automaton's transition, restated sequentially; the device's mask
+// (csrc/flm_shape.h) equals constrain_logits bit for bit.
+// S[n] <- L[n] with -inf at every index that is not one of tokens[0 .. count) (the edge list of the armed state: ascending ids in [0, n)).  S may be L
+void constrain_logits(const float* L, int n, const int32_t* tokens, int count, float* S);
+// delta(q, t) over a CSR automaton: the edge_next of t's edge in state q, or q itself when t has no edge there (reachable only through Sampler::sample's last-index
+// fallback, `return _n - 1` in its multinomial branch, which can name a masked id)
+int dfa_next(const int32_t* row_ptr, const int32_t* edge_token, const int32_t* edge_next, int q, int t);
+
 } // namespace flmhost

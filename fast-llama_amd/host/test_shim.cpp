@@ -83,6 +83,10 @@ void fh_shape(const float* logits, int n, float temperature, int top_k, float mi
     c.n_bias = n_bias; c.bias_ids = bias_ids; c.bias_values = bias_values;
     shape_logits(logits, n, temperature, c, window, n_window, out);
 }
+// step 0 of the shaping definition (sampler.h constrain_logits) on one row: out[n]; the expected value of the device's mask
+void fh_constrain(const float* logits, int n, const int32_t* tokens, int count, float* out) { constrain_logits(logits, n, tokens, count, out); }
+// the automaton's transition (sampler.h dfa_next)
+int fh_dfa_next(const int32_t* row_ptr, const int32_t* edge_token, const int32_t* edge_next, int q, int t) { return dfa_next(row_ptr, edge_token, edge_next, q, t); }
 // flm_score (include/flm_gpu.h) of one row of logits, in plain C++: sample_argmax (sampler.cpp:36-47) and the sampler's clipped softmax (tf_operators.cpp:188-209) at
 // temperature 1, read at `target` (-1: none) -- libm expf, a sequential fp32 sum in index order, prob = e_target * (float)(1.0 / sum).  out5: {argmax, target_logit,
 // max_logit, sum, prob} as 32-bit words (the struct's layout).  The expected value of the device's k_score_rows.

@@ -300,6 +300,40 @@ int  flm_generate_lookup_ex(flm_ctx* ctx, const int32_t* prompt, int n_prompt, i
                             int32_t stop_token /* -1: none */, int draft_len /* 4..15 */, int ngram_max /* 1..8 */,
                             flm_token_cb cb /* may be NULL */, void* user,
                             int32_t* out_tokens /* [max_tokens], may be NULL */, int* n_out);
+/* Constrained decoding: a token-level deterministic automaton masks the logits in front of the controls -- what "one of these strings", a JSON shape or a regular expression
+ * reduce to.  No reference counterpart.  The automaton is CSR: the edges of state q are [row_ptr[q], row_ptr[q + 1]).
+ *   delta(q, t)  the edge_next of t's edge in state q, or q ITSELF when t has no edge there.  The no-edge case is reachable only through the multinomial branch's last-index
+ *                fallback of Sampler::sample (sampler.cpp `return _n - 1`: the coin lies beyond the accumulated probabilities), which can name a masked id.
+ *   step 0       with the context armed at state q the shaping definition at flm_sampling gains a step in front of the bias: S = L; S[i] = -inf for every i without an edge
+ *                in q.  A masked entry stays -inf under steps 1 - 4 (-inf + b = -inf for every allowed bias), so step 0 followed by those steps is the whole definition; the
+ *                host restatement is host/sampler.cpp constrain_logits followed by shape_logits.  Every state has an edge: the mask alone never bans a whole row.
+ * flm_dfa_validate (pure host arithmetic, like flm_plan_shards): FLM_OK, or FLM_ERR_INVALID with flm_last_error(NULL) naming the rule -- n_states in [1, FLM_DFA_STATES_MAX] and
+ * n_edges in [1, FLM_DFA_EDGES_MAX]; row_ptr[0] = 0, non-decreasing, row_ptr[n_states] = n_edges; tokens strictly ascending inside a state and in [0, vocab); edge_next in
+ * [0, n_states); every state has at least one edge.
+ * flm_constraint_set installs or replaces the automaton (NULL: removes it): validated against the model's vocabulary, copied to device memory allocated HERE, off the steady
+ * path like flm_upload_tensor (the previous automaton's memory is released), with a host copy kept; afterwards the constraint is disarmed.  FLM_ERR_UNSUPPORTED on a sharded
+ * context, FLM_ERR_STATE before the model is complete.  No graph is re-captured: the shaped token graphs reach the automaton through a device block that exists since
+ * flm_ctx_create and whose contents are rewritten.
+ * flm_constraint_arm sets the state (-1: disarms); FLM_ERR_INVALID for a state outside [0, n_states) or with no automaton installed.  Allocates nothing, re-captures nothing.
+ * flm_query "constraint_state" reads the state (-1: disarmed).  (Not an option: flm_set_option drops the graphs.)
+ * While armed, the four _ex entry points apply it -- flm_generate_ex, flm_forward_sample_ex, flm_verify_sample_ex, flm_generate_lookup_ex -- and an armed constraint counts as
+ * a control that is set: with every flm_sampling control neutral the shaped form still runs, masking only, and the delivered ids count in "shaped_tokens".  After a call that
+ * delivers ids t[0 .. n) the state is delta folded over them from the state the context was armed at, the stop token included when delivered (the host folds its own copy of
+ * the automaton over the ids it delivered: nothing extra is read back).  Row r of a verify batch is masked in delta folded over drafts[0 .. r): the loop's state for that token
+ * exactly when the accept step keeps the row.  A retried call restarts from the state it was armed at and delivers nothing twice; on any error nothing is launched and the
+ * state does not move.  Every other rule of the _ex forms stays.  The PLAIN entry points (flm_forward*, flm_decode_*, flm_generate, flm_verify_greedy / _sample,
+ * flm_generate_lookup / _sample, flm_score_tokens) ignore the constraint and leave its state alone. */
+#define FLM_DFA_STATES_MAX 65536
+#define FLM_DFA_EDGES_MAX  (1 << 24)
+typedef struct flm_dfa {            /* CSR: the edges of state q are [row_ptr[q], row_ptr[q + 1]) */
+    int32_t n_states, n_edges;
+    const int32_t* row_ptr;         /* [n_states + 1], row_ptr[0] = 0, non-decreasing, row_ptr[n_states] = n_edges */
+    const int32_t* edge_token;      /* [n_edges], STRICTLY ascending inside a state, in [0, vocab) */
+    const int32_t* edge_next;       /* [n_edges], in [0, n_states) */
+} flm_dfa;
+int  flm_dfa_validate(const flm_dfa* dfa, int vocab);
+int  flm_constraint_set(flm_ctx* ctx, const flm_dfa* dfa);
+int  flm_constraint_arm(flm_ctx* ctx, int32_t state);
 /* the ids generated by the last flm_decode_greedy / flm_decode_sample / flm_decode_timed* call: out[n] (n <= its n_steps) */
 int  flm_last_tokens(flm_ctx* ctx, int n, int32_t* out);
 int  flm_reset_kv(flm_ctx* ctx);
@@ -385,7 +419,8 @@ int  flm_set_option(flm_ctx* ctx, const char* key, int value);
  *               classifier, argmax in k_layers<.., TAIL>),
  *   "ao_active" which hand-offs of that launch are consumed in arrival order: bit 0 Wo, bit 1 FFN2 (-1: the launch has not been planned yet),
  *   "sampled_tokens" how many tokens this context sampled on the device (flm_forward_sample / flm_decode_sample / flm_generate / flm_verify_sample / flm_generate_lookup_sample at temperature > 0),
- *   "shaped_tokens" how many tokens this context drew under the controls (flm_generate_ex / flm_forward_sample_ex / flm_verify_sample_ex / flm_generate_lookup_ex with a control set),
+ *   "shaped_tokens" how many tokens this context drew under the controls (flm_generate_ex / flm_forward_sample_ex / flm_verify_sample_ex / flm_generate_lookup_ex with a control set or a constraint armed),
+   "constraint_state" the automaton state the context is armed at (flm_constraint_arm; moved on by every _ex call over the ids it delivers), -1: disarmed,
  *   "spec_steps" / "spec_accepted" the last flm_generate_lookup / flm_generate_lookup_sample call: verify passes run / drafted ids accepted in them,
  *   "gen_tokens" / "gen_streamed" the last flm_generate call: tokens delivered / how many of them were delivered while hipStreamQuery still said the stream was busy,
  *   "epoch_tail" / "epoch_eng" / "epoch_xchg" the epoch counters the cross-workgroup waits count from (device memory; the 32-bit pattern): the one-launch token's, the
@@ -428,6 +463,10 @@ int  flm_op_shape_logits(const float* logits, int n, const flm_sampling* samplin
  * for rows == 1).  No bound on n.  Errors as there. */
 int  flm_op_shape_rows(const float* logits, int rows, int ld, int n, const flm_sampling* sampling, const int32_t* window, int n_window,
                        const int32_t* drafts /* [rows - 1] */, float* out /* [rows][n] */);
+/* flm_op_shape_rows with the automaton added (k_shape_rows with its step 0): row r is masked in delta folded over drafts[0 .. r) from `state`, then shaped as there;
+ * states_out[r] receives that state.  dfa is validated against n; state in [0, n_states).  Drafts without an edge leave the state where it is. */
+int  flm_op_constrain_rows(const float* logits, int rows, int ld, int n, const flm_sampling* sampling, const int32_t* window, int n_window,
+                           const int32_t* drafts /* [rows - 1] */, const flm_dfa* dfa, int32_t state, float* out /* [rows][n] */, int32_t* states_out /* [rows] */);
 /* flm_score_tokens' statistics kernel (k_score_rows) on caller-supplied logits[rows][n]: out[rows]; targets[rows] as there (NULL: none).  2 <= n, n within the LDS bound. */
 int  flm_op_score_rows(const float* logits, int rows, int n, const int32_t* targets, flm_score* out);
 /* simd::swiglu(xo,xr,n) (x86_simd.cpp:1766-1770) */

@@ -9,7 +9,9 @@ weights, 32 layers by default).  Prints one JSON line:
   * with --shape (and nothing else): the shaped loop against the unshaped one on the same context -- tokens/s of flm_generate at -t 1 -p 0.9, seed 1234 (the sampled loop as
     it was before the shaping stage existed: the same launches), of flm_generate_ex with a control that changes nothing (a bias of +0: the stage's launch on top of the same
     sampler work) and with a full set of controls (top-k 40, min-p 0.05, repeat penalty 1.1 over 64 ids, a bias and a ban: the sampler then sorts fewer candidates), the
-    runs alternating; the stage's own duration: k_shape_logits in a rocprofv3 --kernel-trace --stats run of this command."""
+    runs alternating; the stage's own duration: k_shape_logits in a rocprofv3 --kernel-trace --stats run of this command;
+  * with --constraint (and nothing else): the shaped token with and without an armed automaton, in the same run -- flm_generate_ex with a bias of +0 (the stage's launch,
+    no mask) against the same call armed with a Dfa.from_choices automaton whose every state on the way allows half the vocabulary (the even ids), alternating."""
 import argparse
 import importlib.util
 import json
@@ -45,8 +47,45 @@ def main():
     ap.add_argument("--ops", action="store_true", help="also time op_sample on peaked / medium / flat logits")
     ap.add_argument("--ops-only", action="store_true")
     ap.add_argument("--shape", action="store_true", help="time the shaped loop (flm_generate_ex) against the unshaped one (flm_generate) on the same context, nothing else")
+    ap.add_argument("--constraint", action="store_true", help="time the shaped token with and without an armed automaton (half the vocabulary allowed), nothing else")
     args = ap.parse_args()
     out = {}
+    if args.constraint:
+        cfg = synth.make_config("7B", ff.QT_INT8)
+        cfg.n_layers = args.layers
+        ctx = capi.Ctx(capi.desc_from_config(cfg), device=0)
+        _bench_module().upload_synthetic(ctx, cfg)
+        V, K = cfg.vocab_size, args.steps
+        prompt = np.array([1] + [int(x) for x in (np.arange(1, 9) * 7919) % V], np.int32)
+        # one choice of K + 1 characters, every even id spells one character: states 0 .. K allow the V / 2 even ids each
+        dfa = capi.Dfa.from_choices(["a" if i % 2 == 0 and i != 2 else "" for i in range(V)], ["a" * (K + 1)], end_id=2)
+        ctx.constraint_set(dfa)
+        noop = capi.Sampling(temperature=1.0, topp=0.9, bias={11: 0.0})
+
+        def armed():
+            ctx.constraint_arm(0)
+            r = ctx.generate_ex(prompt, 0, K, noop, rng_state=1234)
+            ctx.constraint_arm(-1)
+            return r
+        runs = {"shaped_unmasked": lambda: ctx.generate_ex(prompt, 0, K, noop, rng_state=1234), "shaped_masked": armed}
+        ts = {k: [] for k in runs}
+        ids = {}
+        for rep in range(args.reps + 1):
+            for name, fn in runs.items():                # alternating: both forms see the same machine
+                ctx.sync(); t0 = time.perf_counter(); ids[name] = fn()[0]; dt = time.perf_counter() - t0
+                if rep:
+                    ts[name].append(dt)
+        assert len(ids["shaped_masked"]) == K and all(int(x) % 2 == 0 for x in ids["shaped_masked"])
+        for name in runs:
+            med = float(np.median(ts[name]))
+            out[f"{name}_tok_s"] = round(K / med, 1)
+            out[f"{name}_ms_per_call"] = round(med * 1e3, 2)
+            out[f"{name}_spread_ms"] = round((max(ts[name]) - min(ts[name])) * 1e3, 2)
+        out["mask_extra_us_per_token"] = round((np.median(ts["shaped_masked"]) - np.median(ts["shaped_unmasked"])) / K * 1e6, 1)
+        out["tokens_per_call"] = K; out["allowed_ids_per_state"] = int(dfa.edges(0)[0].size); out["dfa_edges"] = dfa.n_edges
+        ctx.close()
+        print(json.dumps(out), flush=True)
+        return
     if args.shape:
         cfg = synth.make_config("7B", ff.QT_INT8)
         cfg.n_layers = args.layers
