@@ -31,10 +31,17 @@ SYMBOLS = (
     "flm_generate_ex", "flm_forward_sample_ex", "flm_op_shape_logits",
     "flm_verify_sample_ex", "flm_generate_lookup_ex", "flm_op_shape_rows",
     "flm_dfa_validate", "flm_constraint_set", "flm_constraint_arm", "flm_op_constrain_rows",
+    "flm_logprobs_arm", "flm_last_logprobs", "flm_op_logprob_rows", "flm_logprob_stage_time",
 )
 
 # flm_score (include/flm_gpu.h): one row of flm_score_tokens / flm_op_score_rows
 SCORE_DTYPE = np.dtype([("argmax", np.int32), ("target_logit", np.float32), ("max_logit", np.float32), ("sum", np.float32), ("prob", np.float32)])
+
+# flm_logprob (include/flm_gpu.h): the record of one delivered token, 192 bytes
+LOGPROBS_MAX = 20                                  # FLM_LOGPROBS_MAX
+LOGPROB_SOURCES = {"raw": 0, "shaped": 1}          # FLM_LOGPROBS_RAW, FLM_LOGPROBS_SHAPED
+LOGPROB_DTYPE = np.dtype([("token", np.int32), ("logit", np.float32), ("max_logit", np.float32), ("sum", np.float32), ("n_top", np.int32),
+                          ("top_id", np.int32, (LOGPROBS_MAX,)), ("top_logit", np.float32, (LOGPROBS_MAX,)), ("pad_", np.int32, (3,))])
 
 # flm_token_cb: int (*)(void* user, int index, int32_t token, int last); a non-zero return cancels
 TOKEN_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int32, C.c_int)
@@ -366,6 +373,7 @@ class Ctx:
         rc = lib().flm_generate_ex(self._h, _p(t), len(t), int(pos), int(max_tokens), C.byref(sp), C.byref(st),
                                    C.c_int32(int(stop_token)), cb, None, _p(out), C.byref(n_out))
         del cb, keep
+        self._ex_n_out = int(n_out.value) if rc == 0 else 1
         if raised:
             raise raised[0]
         _check(rc, self._h)
@@ -377,6 +385,7 @@ class Ctx:
         w = np.ascontiguousarray(window, dtype=np.int32)
         nxt = C.c_int32(-1); st = C.c_uint64(int(rng_state))
         sp, keep = sampling.struct()
+        self._ex_n_out = 1
         _check(lib().flm_forward_sample_ex(self._h, _p(t), len(t), int(pos), C.byref(sp), _p(w) if w.size else None, int(w.size), C.byref(st), C.byref(nxt)), self._h)
         del keep
         return nxt.value, st.value
@@ -392,6 +401,31 @@ class Ctx:
     def constraint_arm(self, state):
         """flm_constraint_arm: the state the _ex entry points mask in from now on (-1: disarm); query("constraint_state") reads it back"""
         _check(lib().flm_constraint_arm(self._h, C.c_int32(int(state))), self._h)
+
+    def logprobs_arm(self, top_n, source="raw"):
+        """flm_logprobs_arm: from now on the _ex entry points leave one record per delivered id (top_n alternatives, 0 .. 20; -1: off) from the classifier's row ("raw") or
+        the row the sampler reads ("shaped"); query("logprobs_top_n") reads the setting back"""
+        _check(lib().flm_logprobs_arm(self._h, int(top_n), int(LOGPROB_SOURCES.get(source, source))), self._h)
+
+    def last_logprobs(self, first=0, n=None):
+        """flm_last_logprobs -> LOGPROB_DTYPE[n]: records [first, first + n) of the last _ex call; n None: all of them from `first` on (the *n_out this wrapper saw)"""
+        if n is None:
+            n = max(getattr(self, "_ex_n_out", 1) - int(first), 1)      # (no _ex call through this wrapper yet: one record is asked for and the library says why not)
+        out = np.zeros(int(n), dtype=LOGPROB_DTYPE)
+        _check(lib().flm_last_logprobs(self._h, int(first), int(n), _p(out)), self._h)
+        return out
+
+    def logprob_stage_time(self, iters=50) -> float:
+        """flm_logprob_stage_time: the mean duration in microseconds of one launch of the token form's stage, on what the last armed call left"""
+        us = C.c_float(0)
+        _check(lib().flm_logprob_stage_time(self._h, int(iters), C.byref(us)), self._h)
+        return us.value
+
+    def logprob_records_raw(self, n):
+        """the first n record slots as the device holds them, the ones behind the last call's *n_out included (flm_debug_read 14) -> LOGPROB_DTYPE[n]"""
+        out = np.empty(48 * int(n), dtype=np.float32)
+        _check(lib().flm_debug_read(self._h, 14, 0, _p(out), C.c_size_t(out.size)), self._h)
+        return out.view(LOGPROB_DTYPE)
 
     def score(self, tokens, pos, targets=None, want_logits=False):
         """flm_score_tokens -> a structured array (SCORE_DTYPE) with one row per position; with want_logits also the [n][vocab] logits.  targets None: the next token of
@@ -478,6 +512,7 @@ class Ctx:
         _check(lib().flm_verify_sample_ex(self._h, int(first_token), _p(d), len(d), int(pos), C.byref(sp), _p(w) if w.size else None, int(w.size),
                                           C.byref(st) if st is not None else None, _p(out), C.byref(n_out)), self._h)
         del keep
+        self._ex_n_out = int(n_out.value)
         return out[:n_out.value].copy(), (st.value if st is not None else None)
 
     def generate_lookup_ex(self, prompt, pos, max_tokens, sampling, rng_state=0, stop_token=-1, draft_len=7, ngram_max=3, on_token=None, want_ids=True):
@@ -499,6 +534,7 @@ class Ctx:
         rc = lib().flm_generate_lookup_ex(self._h, _p(t), len(t), int(pos), int(max_tokens), C.byref(sp), C.byref(st), C.c_int32(int(stop_token)),
                                           int(draft_len), int(ngram_max), cb, None, _p(out), C.byref(n_out))
         del cb, keep
+        self._ex_n_out = int(n_out.value) if rc == 0 else 1
         if raised:
             raise raised[0]
         _check(rc, self._h)
@@ -757,6 +793,40 @@ def op_score_rows(logits, targets=None):
     out = np.zeros(a.shape[0], dtype=SCORE_DTYPE)
     _check(lib().flm_op_score_rows(_p(a), int(a.shape[0]), int(a.shape[1]), _p(tg), _p(out)))
     return out
+
+
+def op_logprob_rows(logits, n, chosen, top_n):
+    """k_logprob_rows on logits[rows][ld], the first n entries of each row -> LOGPROB_DTYPE[rows]: row r's record with drawn id chosen[r]"""
+    a = np.ascontiguousarray(logits, dtype=np.float32)
+    a = a.reshape(1, -1) if a.ndim == 1 else a
+    ch = np.ascontiguousarray(chosen, dtype=np.int32).reshape(-1)
+    if ch.size != a.shape[0]:
+        raise ValueError("op_logprob_rows: one drawn id per row")
+    out = np.zeros(a.shape[0], dtype=LOGPROB_DTYPE)
+    _check(lib().flm_op_logprob_rows(_p(a), int(a.shape[0]), int(a.shape[1]), int(n), _p(ch), int(top_n), _p(out)))
+    return out
+
+
+def logprob_host(logits, chosen, top_n):
+    """the record's host restatement (host/sampler.cpp logprob_row through lib/libflm_host.so: fh_logprob_row) on one row -> LOGPROB_DTYPE[1]; needs no GPU"""
+    a = np.ascontiguousarray(logits, dtype=np.float32).reshape(-1)
+    out = np.zeros(1, dtype=LOGPROB_DTYPE)
+    _host_lib().fh_logprob_row(_p(a), int(a.size), int(chosen), int(top_n), _p(out))
+    return out
+
+
+def logprob_values(rec):
+    """float64 log-probabilities from flm_logprob records, (logit - max_logit) - log(sum) evaluated in double from the bit-exact ingredients
+    -> (logprob[rows], top_logprob[rows][20]); -inf where the logit is -inf, NaN in the top slots at and beyond n_top"""
+    r = np.atleast_1d(np.asarray(rec))
+    mx = r["max_logit"].astype(np.float64); ls = np.log(r["sum"].astype(np.float64))
+    with np.errstate(invalid="ignore"):
+        lp = (r["logit"].astype(np.float64) - mx) - ls
+        top = (r["top_logit"].astype(np.float64) - mx[:, None]) - ls[:, None]
+    lp[np.isneginf(r["logit"])] = -np.inf
+    top[np.isneginf(r["top_logit"])] = -np.inf
+    top[np.arange(LOGPROBS_MAX)[None, :] >= r["n_top"][:, None]] = np.nan
+    return lp, top
 
 
 def nll(scores, targets=None):

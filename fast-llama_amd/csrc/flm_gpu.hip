@@ -293,11 +293,13 @@ int run_token(flm_ctx* c, bool with_cls, TokenForm form, int T) {
 }
 // the token forms a context's decode loops replay (single tokens and chunks): greedy always, sampled where the sampler supports the vocabulary, shaped on one GPU.  Their
 // parameters live in device memory (set_sample / set_shape), so no call re-captures or allocates
-static int loop_forms(const flm_ctx* c, TokenForm out[3]) {
+constexpr int kLoopForms = 4;
+static int loop_forms(const flm_ctx* c, TokenForm out[kLoopForms]) {
     int n = 0;
     out[n++] = TokenForm::Greedy;
     if (sample_supported(c)) out[n++] = TokenForm::Sampled;
     if (!sharded(c)) out[n++] = TokenForm::Shaped;
+    if (logprobs_supported(c)) out[n++] = TokenForm::ShapedLp;        // (the armed form, next to the shaped graphs: flm_logprobs_arm captures nothing)
     return n;
 }
 // Everything the token entry points use beyond the buffers of flm_ctx_create: k_layers' argument blocks (both head splits) and every graph flm_forward* / flm_decode_* / flm_generate*
@@ -310,7 +312,7 @@ int prepare_all(flm_ctx* c) {
     const int G1 = attn_parts(c, 1), G2 = attn_parts(c, c->d.max_seq_len);
     int r = prepare_layers(c, G1); if (r) return r;
     if (!graphs_in_use(c)) return FLM_OK;
-    TokenForm forms[3]; const int n_forms = loop_forms(c, forms);
+    TokenForm forms[kLoopForms]; const int n_forms = loop_forms(c, forms);
     const int Gs[2] = {G1, G2};
     for (int i = 0; i < (G2 != G1 ? 2 : 1); ++i) {
         const int G = Gs[i];
@@ -405,6 +407,14 @@ static int set_dfa(flm_ctx* c, int q) {
     if (c->dfa_dev && ns > 0) { v.row_ptr = c->dfa_dev; v.edge_token = c->dfa_dev + (ns + 1); v.edge_next = v.edge_token + c->dfa_tok.size(); v.n_states = ns; }
     v.q = v.n_states > 0 ? q : -1; v.applied = 0;
     hipLaunchKernelGGL(k_set_dfa, dim3(1), dim3(64), 0, c->stream, c->dfa_blk, v);
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
+// the log-probability stage's block, by value like the decode state: {top_n (-1: off), source, the record index of step 0}.  One tiny launch: no allocation, no graph touched
+__global__ void k_set_lp(LogprobBlock* blk, const LogprobBlock v) { if (threadIdx.x == 0 && blockIdx.x == 0) *blk = v; }
+static int set_lp(flm_ctx* c, int base) {
+    LogprobBlock v{}; v.top_n = c->lp_top_n; v.source = c->lp_source; v.base = base;
+    hipLaunchKernelGGL(k_set_lp, dim3(1), dim3(64), 0, c->stream, c->lp_blk, v);
     HIPC(c, hipGetLastError());
     return FLM_OK;
 }
@@ -533,6 +543,7 @@ int h2d(flm_ctx* c, void* dst_dev, const void* src, size_t bytes) {
 int Draw::arm(flm_ctx* c) const {
     int r = shape ? set_shape(c, *shape) : FLM_OK;
     if (!r && cstate >= 0) r = set_dfa(c, cstate);
+    if (!r && lp_base >= 0) r = set_lp(c, lp_base);
     if (!r && form != TokenForm::Greedy) r = set_sample(c, temperature, topp, coins() ? (unsigned long long)*rng_state : 0ull);
     return r;
 }
@@ -584,6 +595,8 @@ static int with_retry(flm_ctx* c, int tokens, Body body, Commit commit) {
     return fail(c, FLM_ERR_HIP, "cross-workgroup wait timed out twice");
 }
 template <class Body> static int with_retry(flm_ctx* c, int tokens, Body body) { return with_retry(c, tokens, body, [] {}); }
+// the context is armed for per-token log-probabilities (flm_logprobs_arm refuses where logprobs_supported is false; "force_tp" may have been set since)
+static bool lp_armed(const flm_ctx* c) { return c->lp_top_n >= 0 && logprobs_supported(c) && c->lp_rec != nullptr; }
 
 } // namespace fh
 
@@ -724,6 +737,15 @@ int flm_ctx_create(const flm_model_desc* desc, int device_id, int rank, int worl
         HIPB(hipMemcpyAsync(c->dfa_blk, &none, sizeof none, hipMemcpyHostToDevice, c->stream));
         HIPB(hipStreamSynchronize(c->stream));                                // (`none` goes out of scope)
     }
+    if (logprobs_supported(c)) {   // per-token log-probabilities (flm_logprob.h): the block (disarmed), the records and their tags, a verify batch's side rows
+        HIPB(dev_alloc(c, &c->lp_blk, sizeof(LogprobBlock), true));
+        LogprobBlock off{}; off.top_n = -1;
+        HIPB(hipMemcpyAsync(c->lp_blk, &off, sizeof off, hipMemcpyHostToDevice, c->stream));
+        HIPB(hipStreamSynchronize(c->stream));                                // (`off` goes out of scope)
+        HIPB(dev_alloc(c, &c->lp_rec, sizeof(LogprobRec) * (size_t)d.max_seq_len, true));
+        HIPB(dev_alloc(c, &c->lp_tags, sizeof(unsigned) * (size_t)d.max_seq_len, true));
+        HIPB(dev_alloc(c, &c->lp_side, (size_t)kSpecRows * d.vocab_size * sizeof(float)));
+    }
     if (sample_supported(c)) HIPB(dev_alloc(c, &c->sort_buf, (size_t)kSpecRows * 2 * d.vocab_size * sizeof(unsigned long long)));   // ([16][2][vocab]: a slice per row of a sampled verify batch)
     std::vector<float> cs, sn; build_rope_table(hs, d.max_seq_len, cs, sn);
     HIPB(dev_alloc(c, &c->rope_cos, cs.size() * 4)); HIPB(dev_alloc(c, &c->rope_sin, sn.size() * 4));
@@ -740,6 +762,7 @@ int flm_ctx_create(const flm_model_desc* desc, int device_id, int rank, int worl
             if (device_id >= 0 && device_id < 64 && !attr_done[device_id]) {
                 HIPB(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_census), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
                 HIPB(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sample_advance), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
+                HIPB(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_logprob_token), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
                 attr_done[device_id] = true;
             }
         }
@@ -1019,6 +1042,7 @@ int flm_query(flm_ctx* c, const char* key, int* value) {
         {"sampled_tokens", (int)c->sampled},
         {"shaped_tokens", (int)c->shaped},
         {"constraint_state", c->dfa_state},
+        {"logprobs_top_n", c->lp_top_n},
         {"gen_tokens", c->gen_tokens},
         {"gen_streamed", c->gen_streamed},
         {"spec_steps", c->spec_steps},
@@ -1140,10 +1164,13 @@ static void warm_up(flm_ctx* c) {
     const bool split = c->d.max_seq_len > split_at + kEach && attn_parts(c, split_at) != attn_parts(c, 1);
     ShapeParams neutral{}; neutral.repeat = 1.0f; neutral.follow = 1;
     uint64_t zero = 0;
-    TokenForm forms[3]; const int n_forms = loop_forms(c, forms);
+    TokenForm forms[kLoopForms]; const int n_forms = loop_forms(c, forms);
     for (int f = 0; f < n_forms && ok && c->d.max_seq_len > n + kEach; ++f) {
-        const bool shaped = forms[f] == TokenForm::Shaped;
+        const bool shaped = shaped_form(forms[f]);
         if (shaped && c->d.vocab_size < 2) continue;
+        // (the armed form is captured at prepare_all like the others but not replayed here: a context that is never armed runs at load time exactly the launches it ran
+        //  before that form existed; the first armed call pays its graphs' first launch)
+        if (forms[f] == TokenForm::ShapedLp) continue;
         const Draw dr = shaped ? Draw(sample_supported(c) ? 1.0f : 0.0f, 0.9f, &zero, &neutral) : Draw(forms[f], 1.0f, 0.9f, &zero);
         ok = dr.arm(c) == FLM_OK && set_state(c, n, 0, 0) == FLM_OK && run_tokens(c, n, kEach, dr.form) == FLM_OK && hipStreamSynchronize(c->stream) == hipSuccess;
         if (ok && split) ok = set_state(c, split_at, 0, 0) == FLM_OK && run_tokens(c, split_at, kEach, dr.form) == FLM_OK && hipStreamSynchronize(c->stream) == hipSuccess;
@@ -1182,7 +1209,7 @@ int flm_reset_kv(flm_ctx* c) {
     return FLM_OK;
 }
 
-// debugging tap (tests): copy an internal device buffer to the host. what: 0 x1, 1 q, 2 att_out, 3 hd, 4 kcache(layer), 5 vcache(layer), 6 logits, 11 / 12 the epoch lines / tags, 13 flm_generate's ring
+// debugging tap (tests): copy an internal device buffer to the host. what: 0 x1, 1 q, 2 att_out, 3 hd, 4 kcache(layer), 5 vcache(layer), 6 logits, 11 / 12 the epoch lines / tags, 13 flm_generate's ring, 14 the log-probability records
 int flm_debug_read(flm_ctx* c, int what, int layer, float* out, size_t n) {
     if (!c || !out) return FLM_ERR_INVALID;
     HIPC(c, hipSetDevice(c->device));
@@ -1255,6 +1282,9 @@ int flm_debug_read(flm_ctx* c, int what, int layer, float* out, size_t n) {
         HIPC(c, hipStreamSynchronize(c->stream));
         memcpy(out, c->gen_host, n * 4);
         return FLM_OK; }
+    case 14: {   // the log-probability records as the device holds them, the slots behind the last call's *n_out included: raw 32-bit words, 48 per record
+        if (!c->lp_rec || n > (size_t)kLogprobWords * c->d.max_seq_len) return fail(c, FLM_ERR_INVALID, "debug_read: size");
+        return d2h(c, out, c->lp_rec, n * 4); }
     default: return fail(c, FLM_ERR_INVALID, "debug_read: unknown buffer");
     }
     if (n > cap || layer < 0 || layer >= c->d.n_layers) return fail(c, FLM_ERR_INVALID, "debug_read: size/layer");
@@ -1330,7 +1360,7 @@ static int forward_draw(flm_ctx* c, const int32_t* tokens, int n, int pos, Draw 
         r = feed(c, tokens, n, pos, dr.form); if (r) return r;
         r = dr.fetch(c); if (r) return r;
         return d2h(c, next_token, c->out_tokens_dev, 4);
-    }, [&] { dr.commit(c, 1); if (dr.cstate >= 0) c->dfa_state = dfa_fold(c, dr.cstate, next_token, 1); });
+    }, [&] { dr.commit(c, 1); if (dr.cstate >= 0) c->dfa_state = dfa_fold(c, dr.cstate, next_token, 1); if (dr.lp_base >= 0) c->lp_count = 1; });
 }
 int flm_forward_sample(flm_ctx* c, const int32_t* tokens, int n, int pos, float temperature, float topp, uint64_t* rng_state, int32_t* next_token) {
     if (!tokens || !next_token) return FLM_ERR_INVALID;
@@ -1367,14 +1397,14 @@ inline void cpu_relax() {
 }
 // shape: null = flm_generate; else flm_generate_ex with a control set: the block goes to the device first and every token takes the shaped form
 static int generate_impl(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, int max_tokens, float temperature, float topp, uint64_t* rng_state,
-                         int32_t stop_token, flm_token_cb cb, void* user, int32_t* out_tokens, int* n_out, const ShapeParams* shape, int cq = -1) {
+                         int32_t stop_token, flm_token_cb cb, void* user, int32_t* out_tokens, int* n_out, const ShapeParams* shape, int cq = -1, bool lp = false) {
     if (!c || !prompt || !n_out) return FLM_ERR_INVALID;
     // (in front of everything else: a tensor-parallel rank must not touch a peer -- halting and cancelling across ranks is not built)
     if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "generate: one GPU only (tensor-parallel callers keep the flm_decode_* loop)");
     if (max_tokens < 1 || !(temperature >= 0.0f) || stop_token >= c->d.vocab_size) return fail(c, FLM_ERR_INVALID, "generate: max_tokens >= 1, temperature >= 0, stop_token < vocab_size (or -1)");
     int r = check_ready(c, n_prompt, pos); if (r) return r;
     if (pos + n_prompt + max_tokens - 1 > c->d.max_seq_len || max_tokens > c->out_cap || max_tokens > c->gen_cap) return fail(c, FLM_ERR_INVALID, "generate: pos + n_prompt + max_tokens - 1 exceeds max_seq_len");
-    Draw dr(temperature, topp, rng_state, shape, cq);
+    Draw dr(temperature, topp, rng_state, shape, cq, lp ? 0 : -1);       // (armed: record i is out_tokens[i]'s)
     if (dr.coins()) { r = sample_args_ok(c, temperature, topp, rng_state); if (r) return r; }
     volatile unsigned long long* ring = c->gen_host;
     int* cancel_word = (int*)((char*)c->gen_host + (((size_t)c->gen_cap * 8 + 63) & ~(size_t)63));
@@ -1437,6 +1467,7 @@ static int generate_impl(flm_ctx* c, const int32_t* prompt, int n_prompt, int po
         dr.commit(c, total);
         if (dr.cstate >= 0) c->dfa_state = dfa_fold(c, dr.cstate, ids, total);      // (the stop token, when delivered, included)
         c->gen_tokens = total; c->gen_streamed = streamed;
+        if (dr.lp_base >= 0) c->lp_count = total;
     });
     return r;
 }
@@ -1450,6 +1481,7 @@ int flm_generate(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, int m
 int flm_generate_ex(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, int max_tokens, const flm_sampling* sampling, uint64_t* rng_state,
                     int32_t stop_token, flm_token_cb cb, void* user, int32_t* out_tokens, int* n_out) {
     if (!c || !prompt || !n_out) return FLM_ERR_INVALID;
+    c->lp_count = -1;                                                 // (flm_last_logprobs: until this call has delivered armed)
     if (n_prompt < 1 || n_prompt > c->d.max_seq_len) return fail(c, FLM_ERR_INVALID, "tokens/pos outside [0, max_seq_len]");
     if (!ids_in_vocab(c, prompt, n_prompt)) return fail(c, FLM_ERR_INVALID, "token id out of range");
     ShapeParams sp; bool active = false;
@@ -1457,20 +1489,23 @@ int flm_generate_ex(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, in
     if (const char* why = shape_fill(sampling, c->d.vocab_size, prompt + (n_prompt - tail), tail, true, &sp, &active)) return fail(c, FLM_ERR_INVALID, why);
     if (sampling->temperature != 0.0f && !rng_state) return fail(c, FLM_ERR_INVALID, "sample: rng_state must be given at temperature != 0");
     const int cq = sharded(c) ? -1 : c->dfa_state;                    // an armed constraint counts as a control that is set: the shaped form runs, masking only
-    return generate_impl(c, prompt, n_prompt, pos, max_tokens, sampling->temperature, sampling->topp, rng_state, stop_token, cb, user, out_tokens, n_out, active || cq >= 0 ? &sp : nullptr, cq);
+    const bool lp = lp_armed(c);                                      // ... and so does a context armed for log-probabilities: the shaped form with the record stage behind its sampler
+    return generate_impl(c, prompt, n_prompt, pos, max_tokens, sampling->temperature, sampling->topp, rng_state, stop_token, cb, user, out_tokens, n_out, active || cq >= 0 || lp ? &sp : nullptr, cq, lp);
 }
 // flm_forward_sample with the controls and the caller's window (used as given).  Every control neutral: flm_forward_sample / flm_forward_argmax.
 int flm_forward_sample_ex(flm_ctx* c, const int32_t* tokens, int n, int pos, const flm_sampling* sampling, const int32_t* window, int n_window, uint64_t* rng_state, int32_t* next_token) {
     if (!c || !tokens || !next_token) return FLM_ERR_INVALID;
+    c->lp_count = -1;
     ShapeParams sp; bool active = false;
     if (const char* why = shape_fill(sampling, c->d.vocab_size, window, n_window, false, &sp, &active)) return fail(c, FLM_ERR_INVALID, why);
     const float temperature = sampling->temperature, topp = sampling->topp;
     const bool sampled = temperature != 0.0f;
     if (sampled && !rng_state) return fail(c, FLM_ERR_INVALID, "sample: rng_state must be given at temperature != 0");
     const int cq = sharded(c) ? -1 : c->dfa_state;
-    if (!active && cq < 0) return sampled ? flm_forward_sample(c, tokens, n, pos, temperature, topp, rng_state, next_token) : flm_forward_argmax(c, tokens, n, pos, next_token);
+    const bool lp = lp_armed(c);
+    if (!active && cq < 0 && !lp) return sampled ? flm_forward_sample(c, tokens, n, pos, temperature, topp, rng_state, next_token) : flm_forward_argmax(c, tokens, n, pos, next_token);
     if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "shaped token: one GPU only");
-    return forward_draw(c, tokens, n, pos, Draw(temperature, topp, rng_state, &sp, cq), next_token);
+    return forward_draw(c, tokens, n, pos, Draw(temperature, topp, rng_state, &sp, cq, lp ? 0 : -1), next_token);
 }
 
 // Score a sequence: every position's logits in one batched pass, reduced on the device to a flm_score per row (flm_score.h).  The call is flm_forward's work plus the rows
@@ -1526,7 +1561,7 @@ int flm_score_tokens(flm_ctx* c, const int32_t* tokens, int n, int pos, const in
 // batch, and k_shape_rows shapes every row over its own window (the head ++ the drafts in front of the row) before it is drawn.  The shaped row is a function of (raw row,
 // window, controls) and the draw one of (shaped row, coin): row i is flm_forward_sample_ex's id behind first_token, a[0 .. i) for a caller who slides that window.
 static int verify_impl(flm_ctx* c, int32_t first_token, const int32_t* drafts, int k, int pos, float temperature, float topp, uint64_t* rng_state, int32_t* out_tokens, int* n_out,
-                       const ShapeParams* shape = nullptr, int cq = -1) {
+                       const ShapeParams* shape = nullptr, int cq = -1, bool lp = false) {
     if (!c || !drafts || !out_tokens || !n_out) return fail(c, FLM_ERR_INVALID, "verify: null argument");
     if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "verify: one GPU only");
     if (k < 4 || k > 15) return fail(c, FLM_ERR_INVALID, "verify: 4 <= k <= 15 drafts");
@@ -1544,6 +1579,7 @@ static int verify_impl(flm_ctx* c, int32_t first_token, const int32_t* drafts, i
         r = h2d(c, c->prompt_dev, b, sizeof(int) * (size_t)(k + 1)); if (r) return r;
         SpecDraw sd{temperature, topp, sampled ? (unsigned long long)*rng_state : 0ull};
         if (shape) { sd.shape = c->shape_p; sd.win = c->shape_p->head; sd.n_win = shape->n_head; sd.cstate = cq; }
+        if (lp) { sd.lp_top_n = c->lp_top_n; sd.lp_source = c->lp_source; sd.lp_base = 0; }      // (row r's record is out_tokens[r]'s)
         r = spec_step(c, pos, k, 0, 0, -1, k + 1, false, sd); if (r) return r;
         return d2h(c, &so, c->spec_res, sizeof so);                                   // (the ids and the state in one trip; the error word rides along: xwg_check looks at it next)
     }, [&] {
@@ -1552,6 +1588,7 @@ static int verify_impl(flm_ctx* c, int32_t first_token, const int32_t* drafts, i
         if (sampled) { *rng_state = so.rng; c->sampled += so.n_emit; }
         if (shape) c->shaped += so.n_emit;
         if (shape && cq >= 0) c->dfa_state = dfa_fold(c, cq, so.ids, so.n_emit);
+        if (lp) c->lp_count = so.n_emit;
     });
 }
 int flm_verify_greedy(flm_ctx* c, int32_t first_token, const int32_t* drafts, int k, int pos, int32_t* out_tokens, int* n_out) {
@@ -1564,6 +1601,7 @@ int flm_verify_sample(flm_ctx* c, int32_t first_token, const int32_t* drafts, in
 int flm_verify_sample_ex(flm_ctx* c, int32_t first_token, const int32_t* drafts, int k, int pos, const flm_sampling* sampling, const int32_t* window, int n_window,
                          uint64_t* rng_state, int32_t* out_tokens, int* n_out) {
     if (!c || !drafts || !out_tokens || !n_out) return fail(c, FLM_ERR_INVALID, "verify: null argument");
+    c->lp_count = -1;
     if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "verify: one GPU only");
     ShapeParams sp; bool active = false;
     if (const char* why = shape_fill(sampling, c->d.vocab_size, window, n_window, false, &sp, &active)) return fail(c, FLM_ERR_INVALID, why);
@@ -1574,7 +1612,8 @@ int flm_verify_sample_ex(flm_ctx* c, int32_t first_token, const int32_t* drafts,
     const bool pen = sampling->repeat_penalty != 1.0f || sampling->frequency_penalty != 0.0f || sampling->presence_penalty != 0.0f;
     if (pen && sampling->penalty_last_n > 0) { sp.last_n = sampling->penalty_last_n; active = true; }
     const int cq = c->dfa_state;
-    return verify_impl(c, first_token, drafts, k, pos, sampling->temperature, sampling->topp, rng_state, out_tokens, n_out, active || cq >= 0 ? &sp : nullptr, cq);
+    const bool lp = lp_armed(c);
+    return verify_impl(c, first_token, drafts, k, pos, sampling->temperature, sampling->topp, rng_state, out_tokens, n_out, active || cq >= 0 || lp ? &sp : nullptr, cq, lp);
 }
 
 // flm_generate with several ids per pass over the weights: the prompt enters as in flm_forward_argmax / flm_forward_sample (token 0 is drawn from its last logits, with the
@@ -1591,7 +1630,7 @@ int flm_verify_sample_ex(flm_ctx* c, int32_t first_token, const int32_t* drafts,
 // set_state has reset the step counter the follow form counts by).  Every step's inputs stay the history below n_hist, launch arguments and the block.
 static int generate_lookup_impl(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, int max_tokens, float temperature, float topp, uint64_t* rng_state,
                                 int32_t stop_token, int draft_len, int ngram_max, flm_token_cb cb, void* user, int32_t* out_tokens, int* n_out,
-                                const ShapeParams* shape = nullptr, int cq = -1) {
+                                const ShapeParams* shape = nullptr, int cq = -1, bool lp = false) {
     if (!c || !prompt || !n_out) return FLM_ERR_INVALID;
     if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "generate_lookup: one GPU only");
     if (max_tokens < 1 || !(temperature >= 0.0f) || topp != topp || stop_token >= c->d.vocab_size || draft_len < 4 || draft_len > 15 || ngram_max < 1 || ngram_max > 8)
@@ -1605,7 +1644,7 @@ static int generate_lookup_impl(flm_ctx* c, const int32_t* prompt, int n_prompt,
     int total = 0, steps = 0, accepted = 0; bool done = false, cancelled = false;
     int32_t last_tok = 0;
     uint64_t state = sampled ? *rng_state : 0;                       // the sampler's state behind the ids delivered so far
-    const Draw dr(temperature, topp, &state, shape, cq);             // (arms a token graph from THAT state)
+    const Draw dr(temperature, topp, &state, shape, cq, lp ? 0 : -1);   // (arms a token graph from THAT state; armed for log-probabilities: token 0's record is record 0)
     int cst = shape ? cq : -1;                                       // the constraint's state behind the ids delivered so far: the host folds every step's ids into it and passes the result on
     int32_t* const drawn = c->gen_ids.data();                        // shaped: the ids delivered so far, for the single-token steps' windows (pageable, max_seq_len ids, there since create)
     SpecOut so{};
@@ -1638,6 +1677,7 @@ static int generate_lookup_impl(flm_ctx* c, const int32_t* prompt, int n_prompt,
             if (batch) {
                 SpecDraw sd{temperature, topp, (unsigned long long)state};
                 if (shape) { sd.shape = c->shape_p; sd.win = c->spec_hist; sd.n_win = n_hist; sd.cstate = cst; }      // (the block: as token 0's attempt left it)
+                if (lp) { sd.lp_top_n = c->lp_top_n; sd.lp_source = c->lp_source; sd.lp_base = total; }               // (records land behind the ids delivered so far)
                 r = spec_step(c, at, draft_len, ngram_max, n_hist, stop, room, true, sd);
             }
             else {      // one token through the token graph and the accept kernel with K = 0: the id from the decode state's first output slot, cut / appended / counted like a verified run of one
@@ -1646,7 +1686,7 @@ static int generate_lookup_impl(flm_ctx* c, const int32_t* prompt, int n_prompt,
                     const int w = one.last_n < n_hist ? one.last_n : n_hist;
                     for (int j = 0; j < w; ++j) { const int g = n_hist - w + j; one.head[j] = g < n_prompt ? prompt[g] : drawn[g - n_prompt]; }
                     one.n_head = w; one.follow = 0;
-                    r = Draw(temperature, topp, &state, &one, cst).arm(c);       // (and the constraint's block: {the folded state, 0})
+                    r = Draw(temperature, topp, &state, &one, cst, lp ? total : -1).arm(c);       // (and the constraint's block: {the folded state, 0}; the record stage's: step 0 is record `total`)
                 }
                 else r = dr.arm(c);
                 if (r) return r;
@@ -1664,6 +1704,7 @@ static int generate_lookup_impl(flm_ctx* c, const int32_t* prompt, int n_prompt,
     if (sampled) { *rng_state = state; c->sampled += total; }
     if (shape) c->shaped += total;
     if (cst >= 0) c->dfa_state = cst;
+    if (lp) c->lp_count = total;
     c->spec_steps = steps; c->spec_accepted = accepted;
     return FLM_OK;
 }
@@ -1679,6 +1720,7 @@ int flm_generate_lookup_sample(flm_ctx* c, const int32_t* prompt, int n_prompt, 
 int flm_generate_lookup_ex(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, int max_tokens, const flm_sampling* sampling, uint64_t* rng_state, int32_t stop_token,
                            int draft_len, int ngram_max, flm_token_cb cb, void* user, int32_t* out_tokens, int* n_out) {
     if (!c || !prompt || !n_out) return FLM_ERR_INVALID;
+    c->lp_count = -1;
     if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "generate_lookup: one GPU only");
     if (n_prompt < 1 || n_prompt > c->d.max_seq_len) return fail(c, FLM_ERR_INVALID, "tokens/pos outside [0, max_seq_len]");
     if (!ids_in_vocab(c, prompt, n_prompt)) return fail(c, FLM_ERR_INVALID, "token id out of range");
@@ -1687,8 +1729,9 @@ int flm_generate_lookup_ex(flm_ctx* c, const int32_t* prompt, int n_prompt, int 
     if (const char* why = shape_fill(sampling, c->d.vocab_size, prompt + (n_prompt - tail), tail, true, &sp, &active)) return fail(c, FLM_ERR_INVALID, why);
     if (sampling->temperature != 0.0f && !rng_state) return fail(c, FLM_ERR_INVALID, "sample: rng_state must be given at temperature != 0");
     const int cq = c->dfa_state;
+    const bool lp = lp_armed(c);
     return generate_lookup_impl(c, prompt, n_prompt, pos, max_tokens, sampling->temperature, sampling->topp, rng_state, stop_token, draft_len, ngram_max, cb, user, out_tokens, n_out,
-                                active || cq >= 0 ? &sp : nullptr, cq);
+                                active || cq >= 0 || lp ? &sp : nullptr, cq, lp);
 }
 
 // Constrained decoding (include/flm_gpu.h): the automaton lives in ONE device allocation made here, off the steady path; the shaped token graphs reach it through the block
@@ -1731,6 +1774,47 @@ int flm_constraint_arm(flm_ctx* c, int32_t state) {
     int r = set_dfa(c, state); if (r) return r;
     c->dfa_state = state;
     return FLM_OK;
+}
+
+// Per-token log-probabilities (include/flm_gpu.h; the stage: flm_logprob.h).  A context setting like flm_constraint_arm: the block, the records and the armed token graphs
+// exist since flm_ctx_create / flm_prepare, so arming rewrites the block's contents and nothing else
+static_assert(sizeof(flm_logprob) == sizeof(LogprobRec) && sizeof(flm_logprob) == 192 && FLM_LOGPROBS_MAX == kLogprobsMax, "flm_logprob is the stage's LogprobRec");
+int flm_logprobs_arm(flm_ctx* c, int top_n, int source) {
+    if (!c) return FLM_ERR_INVALID;
+    if (top_n < -1 || top_n > FLM_LOGPROBS_MAX || (source != FLM_LOGPROBS_RAW && source != FLM_LOGPROBS_SHAPED)) return fail(c, FLM_ERR_INVALID, "logprobs_arm: top_n outside [-1, FLM_LOGPROBS_MAX] or source not 0 / 1");
+    if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "logprobs: one GPU only");
+    if (!sample_supported(c) || !c->lp_rec) return fail(c, FLM_ERR_UNSUPPORTED, "logprobs: the vocabulary does not fit one workgroup's LDS (the device sampler's bound)");
+    if (!model_complete(c)) return fail(c, FLM_ERR_STATE, "logprobs_arm before all tensors were uploaded");
+    HIPC(c, hipSetDevice(c->device));
+    const int old_n = c->lp_top_n, old_s = c->lp_source;
+    c->lp_top_n = top_n; c->lp_source = source;
+    const int r = set_lp(c, 0);
+    if (r) { c->lp_top_n = old_n; c->lp_source = old_s; }
+    return r;
+}
+// the stage's own duration: `iters` launches of k_logprob_token back to back between ONE pair of events on the context's stream (flm_kernel_times' way: launch duration +
+// the dependent-dispatch gap), on the rows and the decode state the last armed call left -- every launch rewrites that call's last record with the same bytes
+int flm_logprob_stage_time(flm_ctx* c, int iters, float* avg_us) {
+    if (!c || !avg_us || iters < 1) return FLM_ERR_INVALID;
+    if (!lp_armed(c) || c->lp_count < 1) return fail(c, FLM_ERR_STATE, "logprob_stage_time: behind an armed _ex call that delivered ids");
+    HIPC(c, hipSetDevice(c->device));
+    EvPair ev; HIPC(c, hipEventCreate(&ev.e0)); HIPC(c, hipEventCreate(&ev.e1));
+    int r = launch_logprob_token(c, c->stream); if (r) return r;      // (one launch outside the events: the first one's set-up)
+    HIPC(c, hipEventRecord(ev.e0, c->stream));
+    for (int i = 0; i < iters && !r; ++i) r = launch_logprob_token(c, c->stream);
+    if (r) return r;
+    HIPC(c, hipEventRecord(ev.e1, c->stream));
+    HIPC(c, hipEventSynchronize(ev.e1));
+    float ms = 0.0f; HIPC(c, hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    *avg_us = ms * 1000.0f / (float)iters;
+    return FLM_OK;
+}
+int flm_last_logprobs(flm_ctx* c, int first, int n, flm_logprob* out) {
+    if (!c || !out) return FLM_ERR_INVALID;
+    if (c->lp_count < 0 || !c->lp_rec) return fail(c, FLM_ERR_STATE, "last_logprobs: the last _ex call ran disarmed or failed, or there was none");
+    if (first < 0 || n < 1 || first > c->lp_count - n) return fail(c, FLM_ERR_INVALID, "last_logprobs: first + n passes the call's n_out");
+    HIPC(c, hipSetDevice(c->device));
+    return d2h(c, out, c->lp_rec + first, sizeof(flm_logprob) * (size_t)n);      // (through the bounce buffer, in pieces of its size: the one place records cross the bus)
 }
 
 // the ids the last flm_decode_greedy / flm_decode_sample / flm_decode_timed* call generated (still in device memory): out[n]

@@ -47,7 +47,10 @@ struct EvPair { hipEvent_t e0 = nullptr, e1 = nullptr; ~EvPair() { if (e0) hipEv
 //   Prompt   a prompt token in front of the last one: no classifier, the state moves on to the next prompt id
 //   Sampled  tok <- k_sample_advance on the logits, pos++
 //   Shaped   k_shape_logits, then the sampler (the argmax where the vocabulary is beyond the sampler) on the shaped row, pos++
-enum class TokenForm { Logits, Greedy, Prompt, Sampled, Shaped };
+//   ShapedLp Shaped with k_logprob_token behind the sampler (flm_logprob.h): what the _ex entry points replay while the context is armed with flm_logprobs_arm.  A form of
+//            its own, so that the Shaped graphs stay node for node what they were and arming captures nothing
+enum class TokenForm { Logits, Greedy, Prompt, Sampled, Shaped, ShapedLp };
+inline bool shaped_form(TokenForm f) { return f == TokenForm::Shaped || f == TokenForm::ShapedLp; }
 // a cached token graph: n token sequences (with_cls, form) for G workgroups per head
 using GraphKey = std::tuple<bool, TokenForm, int, int>;
 
@@ -180,6 +183,12 @@ struct flm_ctx {
     int* spec_hist = nullptr; int* spec_arg = nullptr; flm::SpecOut* spec_res = nullptr;
     int spec_gemm = 0;                                 // option "spec_gemm": 1 = the verify pass's int8 GEMMs through k_gemm_q8_skinny (B <= 16), 0 (default until both forms have been timed: DESIGN.md section 5e) = the 64 x 64 tiles; the new entry points only
     int spec_steps = 0, spec_accepted = 0;
+    // per-token log-probabilities (include/flm_gpu.h flm_logprobs_arm; the stage: flm_logprob.h): the armed setting (top_n -1: off; "logprobs_top_n") and its device block,
+    // the records [max_seq_len] with their attempt tags, and the side rows [16][vocab] a verify batch is shaped into when the raw rows must survive -- all device memory
+    // since create (null where the context is sharded or the vocabulary is beyond the sampler: arming refuses there).  lp_count: the records the last _ex call left
+    // (-1: it ran disarmed, failed, or there was none)
+    int lp_top_n = -1, lp_source = 0, lp_count = -1;
+    flm::LogprobBlock* lp_blk = nullptr; flm::LogprobRec* lp_rec = nullptr; unsigned* lp_tags = nullptr; float* lp_side = nullptr;
     int score_rows = 0;                                // option "score_rows": rows per classifier chunk of flm_score_tokens (0: as many as the staging holds; < 0: one row at a time through c->logits)
     std::map<GraphKey, hipGraphExec_t> graphs;        // the token graphs captured so far (flm_gpu.hip token_graph)
     std::vector<TimedLaunch>* timing = nullptr;
@@ -280,6 +289,7 @@ int launch_layers(flm_ctx* c, hipStream_t st, int l0, int l1, int G, bool tail =
 enum XKind { XK_ATT = 0, XK_X1 = 1, XK_HD = 2, XK_LOGITS = 3 };
 int exchange(flm_ctx* c, hipStream_t st, int kind, float* full, float* mine, int count);
 int enqueue_token(flm_ctx* c, hipStream_t st, bool with_cls, TokenForm form, int G);
+int launch_logprob_token(flm_ctx* c, hipStream_t st);                  // (flm_token.hip: the armed form's last launch)
 // flm_sampling -> the shaper's parameter block (flm_gpu.hip): validates everything include/flm_gpu.h lists (null on success, else what is wrong); window[n_window] becomes the
 // block's head; *active: some control is not neutral.  follow: flm_generate_ex's sliding window (penalty_last_n), else the window as given
 const char* shape_fill(const flm_sampling* sp, int vocab, const int32_t* window, int n_window, bool follow, flm::ShapeParams* out, bool* active);
@@ -290,6 +300,8 @@ int set_state(flm_ctx* c, int pos, int tok, int step);
 // the decode state's latch as the single-GPU token launches receive it (flm_math.h DecodeState::halt); the tensor-parallel launch forms get none and run unconditionally
 // this context runs the sharded (tensor-parallel) token path; a 1-rank communicator takes it only on request ("force_tp")
 inline bool sharded(const flm_ctx* c) { return c->world > 1 || (c->comm != nullptr && c->force_tp); }
+// per-token log-probabilities can be armed: one GPU, the vocabulary within the sampler's LDS strip (the sum chain's bound; flm_score_tokens has the same)
+inline bool logprobs_supported(const flm_ctx* c) { return !sharded(c) && sample_supported(c); }
 inline const int* halt_ptr(const flm_ctx* c) { return sharded(c) ? nullptr : &c->state->halt; }
 // ids[0 .. n) lie in [0, vocab)
 inline bool ids_in_vocab(const flm_ctx* c, const int32_t* ids, int n) {
@@ -300,11 +312,12 @@ inline bool ids_in_vocab(const flm_ctx* c, const int32_t* ids, int n) {
 struct Draw {
     TokenForm form; float temperature, topp; uint64_t* rng_state; const flm::ShapeParams* shape;
     int cstate = -1;                                              // the constraint's state at the call's first token (-1: none; only with a block: an armed constraint counts as a control)
+    int lp_base = -1;                                             // the context is armed for log-probabilities: the record index of the token at step 0 (-1: not armed); the form is then ShapedLp
     unsigned long long after = 0;                                 // the state an attempt left on the device (fetch); the caller's changes only behind a verified attempt (commit)
     // Greedy / Sampled by temperature, Shaped where a block is given
-    Draw(float t, float p, uint64_t* st, const flm::ShapeParams* sh = nullptr, int cq = -1) : form(sh ? TokenForm::Shaped : t != 0.0f ? TokenForm::Sampled : TokenForm::Greedy), temperature(t), topp(p), rng_state(st), shape(sh), cstate(sh ? cq : -1) {}
+    Draw(float t, float p, uint64_t* st, const flm::ShapeParams* sh = nullptr, int cq = -1, int lp = -1) : form(sh ? (lp >= 0 ? TokenForm::ShapedLp : TokenForm::Shaped) : t != 0.0f ? TokenForm::Sampled : TokenForm::Greedy), temperature(t), topp(p), rng_state(st), shape(sh), cstate(sh ? cq : -1), lp_base(sh ? lp : -1) {}
     Draw(TokenForm f, float t, float p, uint64_t* st) : form(f), temperature(t), topp(p), rng_state(st), shape(nullptr) {}
-    bool coins() const { return form == TokenForm::Sampled || (form == TokenForm::Shaped && temperature != 0.0f); }   // the caller's state is read and moved on
+    bool coins() const { return form == TokenForm::Sampled || (shaped_form(form) && temperature != 0.0f); }   // the caller's state is read and moved on
     int arm(flm_ctx* c) const;             // an attempt's start: the shaper's block, the constraint's {state, 0}, then the sampler's parameters FROM THE CALLER'S STATE -- a retried attempt draws nothing twice
     int fetch(flm_ctx* c);                 // an attempt's end: the state behind its draws comes back
     void commit(flm_ctx* c, int n) const;  // a verified attempt of n tokens: the caller's state, "sampled_tokens" / "shaped_tokens"
@@ -319,7 +332,8 @@ int score_classify(flm_ctx* c, int row0, int m, float* stage);
 // (draw: temperature, top-p and the step's xorshift state: k_sample_rows draws row row0 + i with that state's (row0 + i + 1)-th coin; temperature 0: k_argmax_rows)
 // shape (the device block) given: k_shape_rows shapes the chunk's rows in place in front of the draw, row i over the last min(last_n, n_win + i) ids of
 // win[0 .. n_win) ++ the batch's drafts in front of it (prompt_dev + 1); null: no shape kernel runs
-struct SpecDraw { float temperature, topp; unsigned long long base; const flm::ShapeParams* shape = nullptr; const int* win = nullptr; int n_win = 0; int cstate = -1 /* the batch's base constraint state; -1: none */; };
+struct SpecDraw { float temperature, topp; unsigned long long base; const flm::ShapeParams* shape = nullptr; const int* win = nullptr; int n_win = 0; int cstate = -1 /* the batch's base constraint state; -1: none */;
+                  int lp_top_n = -1 /* the context is armed: k_logprob_rows behind the rows' draws, records from lp_base on; -1: not */, lp_source = 0, lp_base = 0; };
 // k_shape_rows on `rows` rows (batch rows row0 ..) of n logits, ld floats apart -> out, ld_out apart (out == logits: in place); c may be null: flm_op_shape_rows
 int launch_shape_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, float* out, int ld_out, int n, int row0, int rows, const flm::ShapeParams* p,
                       const int* win, int n_win, const int* drafts, const flm::DfaBlock* dfa = nullptr, int cstate = -1, int* states_out = nullptr);
@@ -328,6 +342,9 @@ int dfa_fold(const flm_ctx* c, int q, const int32_t* ids, int n);
 // the rules of flm_dfa_validate (flm_gpu.hip): null, or which one failed
 const char* dfa_check(const flm_dfa* dfa, int vocab);
 int spec_classify(flm_ctx* c, int row0, int m, float* stage, bool skinny, int* argmax_out, const SpecDraw& draw);
+// k_logprob_rows on `rows` <= 16 rows of n logits, ld floats apart, batch rows row0 ..: chosen[row0 + r] the row's drawn id, its record rec[rec_base + row0 + r]
+// (flm_prompt.hip; c may be null: flm_op_logprob_rows)
+int launch_logprob_rows(flm_ctx* c, hipStream_t st, const float* rows_dev, int ld, int n, int row0, int rows, const int* chosen, int top_n, flm::LogprobRec* rec, int rec_base, int rec_cap);
 // k_sample_rows on `rows` <= 16 rows of n logits, ld floats apart, batch rows row0 ..; sort_buf [rows][2][n] (flm_prompt.hip; c may be null: flm_op_sample_rows)
 int launch_sample_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, int n, int row0, int rows, float temperature, float topp, unsigned long long base,
                        unsigned long long* sort_buf, int* out);

@@ -49,11 +49,13 @@
 //                         (temperature 0), the history's start and the accept step, which leaves the accepted ids and the sampler's state after their draws in one block
 //   k_score_rows          (flm_score.h) per row of a block of logits: first-maximum argmax, the clipped softmax's max / exact sequential sum, the target's logit and probability
 //                         (flm_score_tokens behind the batched prompt path's classifier GEMM; flm_op_score_rows)
+//   k_logprob_token, k_logprob_rows  (flm_logprob.h) the record of one drawn token -- its logit, the clipped softmax's max / exact sum, the first top_n entries of the row -- behind
+//                         the shaped token form's sampler / behind a verify batch's row draws, while the context is armed (flm_logprobs_arm; flm_op_logprob_rows)
 // plus small op-level kernels that expose the same __device__ functions to the parity tests.
 // (Round 3's weight-streaming engine -- loader / consumer waves around an LDS ring -- was measured slower than these launches and left the library in round 4:
 //  tools/experiments/engine/, numbers in profiles/r03_engine_timelines.txt.)
 //
-// The code lives in: flm_math.h (exact scalar / wave building blocks), flm_gemv.h, flm_attn.h, flm_layer.h, flm_prefill.h, flm_misc.h, flm_sample.h, flm_score.h, flm_spec.h.
+// The code lives in: flm_math.h (exact scalar / wave building blocks), flm_gemv.h, flm_attn.h, flm_layer.h, flm_prefill.h, flm_misc.h, flm_sample.h, flm_score.h, flm_logprob.h, flm_spec.h.
 #pragma once
 #include "flm_math.h"
 #include "flm_gemv.h"
@@ -64,4 +66,5 @@
 #include "flm_sample.h"
 #include "flm_shape.h"
 #include "flm_score.h"
+#include "flm_logprob.h"
 #include "flm_spec.h"

@@ -296,6 +296,22 @@ int flm_op_score_rows(const float* logits, int rows, int n, const int32_t* targe
     return FLM_OK;
 }
 
+/* k_logprob_rows -- the record stage of an armed context's verify batch (flm_logprob.h) -- on caller-supplied rows of logits and drawn ids */
+int flm_op_logprob_rows(const float* logits, int rows, int ld, int n, const int32_t* chosen, int top_n, flm_logprob* out) {
+    if (!logits || !chosen || !out || rows < 1 || rows > kSpecRows || n < 2 || ld < n || top_n < 0 || top_n > FLM_LOGPROBS_MAX) return FLM_ERR_INVALID;
+    if (sample_lds_bytes(n) > kLdsMax) return FLM_ERR_UNSUPPORTED;
+    for (int i = 0; i < rows; ++i) if (chosen[i] < 0 || chosen[i] >= n) return FLM_ERR_INVALID;
+    static_assert(sizeof(flm_logprob) == sizeof(LogprobRec), "flm_logprob is k_logprob_rows' LogprobRec");
+    DevBuf dl, dc, dout;
+    if (dl.alloc((size_t)rows * ld * 4) || dc.alloc((size_t)kSpecRows * 4) || dout.alloc((size_t)rows * sizeof(LogprobRec))) return FLM_ERR_OOM;
+    OPC(hipMemcpy(dl.p, logits, (size_t)rows * ld * 4, hipMemcpyHostToDevice));
+    OPC(hipMemcpy(dc.p, chosen, (size_t)rows * 4, hipMemcpyHostToDevice));
+    int r = launch_logprob_rows(nullptr, 0, dl.as<float>(), ld, n, 0, rows, dc.as<int>(), top_n, dout.as<LogprobRec>(), 0, rows); if (r) return r;
+    OPC(hipDeviceSynchronize());
+    OPC(hipMemcpy(out, dout.p, (size_t)rows * sizeof(LogprobRec), hipMemcpyDeviceToHost));
+    return FLM_OK;
+}
+
 int flm_op_swiglu(float* xo, const float* xr, size_t n) {
     if (!xo || !xr || n == 0) return FLM_ERR_INVALID;
     DevBuf a, b; if (a.alloc(n * 4) || b.alloc(n * 4)) return FLM_ERR_OOM;

@@ -248,6 +248,23 @@ int launch_shape_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, f
     HIPC(c, hipGetLastError());
     return FLM_OK;
 }
+int launch_logprob_rows(flm_ctx* c, hipStream_t st, const float* rows_dev, int ld, int n, int row0, int rows, const int* chosen, int top_n, LogprobRec* rec, int rec_base, int rec_cap) {
+    {   // the strip of a large vocabulary: the dynamic-LDS limit, once per device
+        static std::mutex mu; static bool done[64] = {false};
+        int dev = 0; HIPC(c, hipGetDevice(&dev));
+        std::lock_guard<std::mutex> lk(mu);
+        if (dev >= 0 && dev < 64 && !done[dev]) {
+            HIPC(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_logprob_rows), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
+            done[dev] = true;
+        }
+    }
+    if (rows < 1 || row0 < 0 || row0 + rows > kSpecRows || top_n < 0 || top_n > kLogprobsMax || !rec) return fail(c, FLM_ERR_INVALID, "logprob_rows: rows outside a batch of 16, or top_n outside [0, 20]");
+    if (n < 2 || sample_lds_bytes(n) > kLdsMax) return fail(c, FLM_ERR_UNSUPPORTED, "logprob_rows: the row does not fit one workgroup's LDS strip");
+    const LogprobRowsArgs a{rows_dev, ld, n, row0, chosen, top_n, rec, rec_base, rec_cap};
+    hipLaunchKernelGGL(k_logprob_rows, dim3(rows), dim3(kSampleBlock), logprob_lds_bytes(n), st, a);
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
 template <int QT>
 static int score_classify_t(flm_ctx* c, int row0, int m, float* stage, bool skinny, int* argmax_out, const SpecDraw* draw = nullptr) {
     const int dim = c->d.dim, V = c->d.vocab_size;
@@ -263,14 +280,23 @@ static int score_classify_t(flm_ctx* c, int row0, int m, float* stage, bool skin
     int r = launch_rows<QT, PRO_RMSNORM_QUANT>(c, st, ra, m); if (r) return r;
     GemmArgs g{c->cls.q, c->cls.s, c->pf_xq, c->pf_xs, stage, V, dim, V, m, c->pf_xst, c->cls.st};
     r = launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, skinny && m <= kSkinnyTokens); if (r) return r;
-    if (argmax_out && draw && draw->shape) {                  // a control is set: the chunk's rows shaped in place, each over its own window, in front of the draw
-        r = launch_shape_rows(c, st, stage, V, stage, V, V, row0, m, draw->shape, draw->win, draw->n_win, c->prompt_dev + 1, c->dfa_blk, draw->cstate); if (r) return r;
-    }
-    if (argmax_out && draw && draw->temperature != 0.0f)      // the sampled verify pass: row row0 + i drawn with the (row0 + i + 1)-th coin of the step's state
-        return launch_sample_rows(c, st, stage, V, V, row0, m, draw->temperature, draw->topp, draw->base, c->sort_buf, argmax_out);
-    if (argmax_out) {   // the verify pass: the rows' first maxima only (no softmax, no sum chain, no LDS strip: any vocabulary)
-        hipLaunchKernelGGL(k_argmax_rows, dim3(m), dim3(kSampleBlock), 0, st, (const float*)stage, V, V, argmax_out + row0);
-        HIPC(c, hipGetLastError());
+    if (argmax_out) {
+        const bool lp = draw && draw->lp_top_n >= 0;          // the context is armed for log-probabilities: a record per row behind the draws (flm_logprob.h)
+        float* rows = stage;                                  // what the draw reads
+        if (draw && draw->shape) {                            // a control is set: the chunk's rows shaped, each over its own window, in front of the draw -- in place, or into
+            if (lp && draw->lp_source == 0) {                 // the side rows where the records want the RAW rows (shape_row copies when S != L); m <= 16: a batch's rows
+                if (m > kSpecRows || !c->lp_side) return fail(c, FLM_ERR_INVALID, "logprobs: a verify chunk of more than 16 rows");
+                rows = c->lp_side;
+            }
+            r = launch_shape_rows(c, st, stage, V, rows, V, V, row0, m, draw->shape, draw->win, draw->n_win, c->prompt_dev + 1, c->dfa_blk, draw->cstate); if (r) return r;
+        }
+        if (draw && draw->temperature != 0.0f) {              // the sampled verify pass: row row0 + i drawn with the (row0 + i + 1)-th coin of the step's state
+            r = launch_sample_rows(c, st, rows, V, V, row0, m, draw->temperature, draw->topp, draw->base, c->sort_buf, argmax_out); if (r) return r;
+        } else {   // the verify pass: the rows' first maxima only (no softmax, no sum chain, no LDS strip: any vocabulary)
+            hipLaunchKernelGGL(k_argmax_rows, dim3(m), dim3(kSampleBlock), 0, st, (const float*)rows, V, V, argmax_out + row0);
+            HIPC(c, hipGetLastError());
+        }
+        if (lp) return launch_logprob_rows(c, st, draw->lp_source ? rows : stage, V, V, row0, m, argmax_out, draw->lp_top_n, c->lp_rec, draw->lp_base, c->d.max_seq_len);
         return FLM_OK;
     }
     return launch_score_rows(c, st, stage, V, V, c->score_tgt + row0, c->score_dev + row0, m);

@@ -87,6 +87,59 @@ struct ShapeMask { const int* tok; int ne; };
 // head and the ids drawn so far; k_shape_rows: the base window and the batch's drafts in front of the row)
 struct ShapeWindow { const int* a; int na; const int* b; int skip; int w; };
 
+// The radix select of step 3 (and of flm_logprob.h's top-N) by one 1024-thread workgroup: the key that is K-th in descending order among keyf(i), i < n (0 < K <= n) -- four
+// 8-bit passes, most significant digit first, each an integer LDS histogram of the entries that match the prefix so far.  Returns that threshold key; *need: how many
+// threshold-equal entries belong to the first K, *eqc: how many there are (need <= eqc).  hist: 4 * 256 words, misc: 64 words ([16] digit, [17] rem, [18] equal-count: read
+// by every thread on return, so a caller writes them only behind a barrier of its own).  Integer atomics only; nothing depends on the order in which waves run
+template <class KF>
+__device__ __forceinline__ unsigned radix_select(KF keyf, const int n, const int K, int* const hist, int* const misc, int* need, int* eqc) {
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    for (int k = t; k < 4 * 256; k += kSampleBlock) hist[k] = 0;
+    if (t == 0) misc[17] = K;
+    __syncthreads();
+    unsigned prefix = 0u;              // the digits chosen so far, in the key's top bits
+#pragma unroll 1
+    for (int d = 0; d < 4; ++d) {
+        const int shift = 24 - 8 * d;
+        int* h = hist + d * 256;
+#pragma unroll 1
+        for (int b0 = 0; b0 < n; b0 += kSampleBlock) {
+            const int i = b0 + t;
+            bool valid = i < n;
+            unsigned key = 0u;
+            if (valid) { key = keyf(i); valid = d == 0 || (key >> (shift + 8)) == (prefix >> (shift + 8)); }
+            const unsigned dig = (key >> shift) & 255u;
+            // the lanes of this wave with the same digit add once, through their lowest lane
+            unsigned long long m = __ballot(valid);
+#pragma unroll
+            for (int bb = 0; bb < 8; ++bb) { const unsigned long long bm = __ballot((dig >> bb) & 1u); m &= ((dig >> bb) & 1u) ? bm : ~bm; }
+            if (valid && (m & ((1ull << lane) - 1ull)) == 0ull) atomicAdd(&h[dig], __popcll(m));
+        }
+        __syncthreads();
+        if (wv == 0) {
+            // the digit at which the count from the top reaches rem: lane l holds bins 4l .. 4l + 3
+            const int rem = misc[17];
+            const int a0 = h[4 * lane], a1 = h[4 * lane + 1], a2 = h[4 * lane + 2], a3 = h[4 * lane + 3];
+            const int s = a0 + a1 + a2 + a3;
+            int suf = s;
+            for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_down(suf, o, kWave); if (lane + o < 64) suf += u; }
+            int above = suf - s;       // entries in the bins of higher lanes
+            const int bins[4] = {a3, a2, a1, a0};
+            int fd = -1, frem = 0, feq = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                if (fd < 0 && above < rem && above + bins[q] >= rem) { fd = 4 * lane + 3 - q; frem = rem - above; feq = bins[q]; }
+                above += bins[q];
+            }
+            if (fd >= 0) { misc[16] = fd; misc[17] = frem; misc[18] = feq; }
+        }
+        __syncthreads();
+        prefix |= (unsigned)misc[16] << shift;
+    }
+    *need = misc[17]; *eqc = misc[18];
+    return prefix;
+}
+
 // Steps 0 - 4 of the definition on ONE row, by one 1024-thread workgroup: L[0 .. n) -> S[0 .. n) (S == L: shaped in place, the copy is skipped).  THE definition: k_shape_logits
 // (the shaped token form) and k_shape_rows (the rows of a verify batch) are both this function behind their own window and state arithmetic
 __device__ __forceinline__ void shape_row(const float* L, float* S, const int n, const ShapeParams* p, const ShapeWindow wd, const ShapeMask mk, ShapeLds& lds) {
@@ -140,50 +193,8 @@ __device__ __forceinline__ void shape_row(const float* L, float* S, const int n,
     // 3: top-k
     const int K = p->top_k;
     if (K > 0 && K < n) {
-        for (int k = t; k < 4 * 256; k += kSampleBlock) hist[k] = 0;
-        if (t == 0) misc[17] = K;
-        __syncthreads();
-        unsigned prefix = 0u;              // the digits chosen so far, in the key's top bits
-#pragma unroll 1
-        for (int d = 0; d < 4; ++d) {
-            const int shift = 24 - 8 * d;
-            int* h = hist + d * 256;
-#pragma unroll 1
-            for (int b0 = 0; b0 < n; b0 += kSampleBlock) {
-                const int i = b0 + t;
-                bool valid = i < n;
-                unsigned key = 0u;
-                if (valid) { key = shape_key(S[i]); valid = d == 0 || (key >> (shift + 8)) == (prefix >> (shift + 8)); }
-                const unsigned dig = (key >> shift) & 255u;
-                // the lanes of this wave with the same digit add once, through their lowest lane
-                unsigned long long m = __ballot(valid);
-#pragma unroll
-                for (int bb = 0; bb < 8; ++bb) { const unsigned long long bm = __ballot((dig >> bb) & 1u); m &= ((dig >> bb) & 1u) ? bm : ~bm; }
-                if (valid && (m & ((1ull << lane) - 1ull)) == 0ull) atomicAdd(&h[dig], __popcll(m));
-            }
-            __syncthreads();
-            if (wv == 0) {
-                // the digit at which the count from the top reaches rem: lane l holds bins 4l .. 4l + 3
-                const int rem = misc[17];
-                const int a0 = h[4 * lane], a1 = h[4 * lane + 1], a2 = h[4 * lane + 2], a3 = h[4 * lane + 3];
-                const int s = a0 + a1 + a2 + a3;
-                int suf = s;
-                for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_down(suf, o, kWave); if (lane + o < 64) suf += u; }
-                int above = suf - s;       // entries in the bins of higher lanes
-                const int bins[4] = {a3, a2, a1, a0};
-                int fd = -1, frem = 0, feq = 0;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    if (fd < 0 && above < rem && above + bins[q] >= rem) { fd = 4 * lane + 3 - q; frem = rem - above; feq = bins[q]; }
-                    above += bins[q];
-                }
-                if (fd >= 0) { misc[16] = fd; misc[17] = frem; misc[18] = feq; }
-            }
-            __syncthreads();
-            prefix |= (unsigned)misc[16] << shift;
-        }
-        const unsigned T = prefix;
-        const int need = misc[17], eqc = misc[18];
+        int need, eqc;
+        const unsigned T = radix_select([&](int i) { return shape_key(S[i]); }, n, K, hist, misc, &need, &eqc);
         if (need >= eqc) {
             // every threshold-equal entry is admitted (no tie at the cut): one pass
             for (int i = t; i < n; i += kSampleBlock) if (shape_key(S[i]) < T) S[i] = -INFINITY;

@@ -270,6 +270,16 @@ int exchange(flm_ctx* c, hipStream_t st, int kind, float* full, float* mine, int
     return FLM_OK;
 }
 
+// k_logprob_token behind the shaped form's sampler: the record of the token that launch drew, from the raw or the shaped row by the context's device block
+int launch_logprob_token(flm_ctx* c, hipStream_t st) {
+    if (!logprobs_supported(c) || !c->lp_rec) return fail(c, FLM_ERR_UNSUPPORTED, "logprobs: one GPU, a vocabulary within the sampler's LDS bound");
+    LogprobArgs la{};
+    la.raw = c->logits; la.shaped = c->shape_row; la.n = c->d.vocab_size; la.blk = c->lp_blk; la.st = c->state; la.out_tokens = c->out_tokens_dev; la.out_cap = c->out_cap;
+    la.rec = c->lp_rec; la.tags = c->lp_tags; la.rec_cap = c->d.max_seq_len;
+    hipLaunchKernelGGL(k_logprob_token, dim3(1), dim3(kSampleBlock), logprob_lds_bytes(c->d.vocab_size), st, la);
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
 int enqueue_token(flm_ctx* c, hipStream_t st, bool with_cls, TokenForm form, int G) {
     const auto& d = c->d;
     const int qt = d.quant_type, hs = c->hs, L = d.n_layers;
@@ -372,21 +382,24 @@ layers_done:
             r = launch_gemv<PRO_RMSNORM_QUANT, EPI_STORE>(c, st, qt, folded(traced(args_cls(c), KC_CLS, 0), L - 1, 3), wgs, coh); if (r) return r;
         }
         if (tp) { r = exchange(c, st, XK_LOGITS, c->logits, c->logits + (size_t)c->rank * c->vocab_slot, c->vocab_slot); if (r) return r; }
-        if (form == TokenForm::Shaped) {   // a shaped token: the shaper writes the shaped row, the sampler (unchanged) draws from it
+        if (shaped_form(form)) {   // a shaped token: the shaper writes the shaped row, the sampler (unchanged) draws from it
             if (tp) return fail(c, FLM_ERR_UNSUPPORTED, "shaped token: one GPU only");
             ShapeArgs ha{};
             ha.logits = c->logits; ha.out = c->shape_row; ha.n = d.vocab_size; ha.p = c->shape_p; ha.st = c->state; ha.out_tokens = c->out_tokens_dev; ha.out_cap = c->out_cap; ha.dfa = c->dfa_blk;
             hipLaunchKernelGGL(k_shape_logits, dim3(1), dim3(kSampleBlock), 0, st, ha);
             HIPC(c, hipGetLastError());
-            Tick t(c, st, KC_ARGMAX);
-            if (sample_supported(c)) {
-                SampleArgs sa{};
-                sa.logits = c->shape_row; sa.n = d.vocab_size; sa.sp = c->sparams; sa.st = c->state; sa.out_tokens = c->out_tokens_dev; sa.out_cap = c->out_cap; sa.advance = 1; sa.sort_buf = c->sort_buf; sa.err = c->xwg_err;
-                hipLaunchKernelGGL(k_sample_advance, dim3(1), dim3(kSampleBlock), sample_lds_bytes(d.vocab_size), st, sa);
-            } else {          // (the entry points admit temperature 0 only here: the first maximum of the shaped row)
-                hipLaunchKernelGGL(k_argmax_advance, dim3(1), dim3(1024), 0, st, (const float*)c->shape_row, d.vocab_size, c->state, c->out_tokens_dev, 1, c->out_cap, (const int*)c->xwg_err);
+            {
+                Tick t(c, st, KC_ARGMAX);
+                if (sample_supported(c)) {
+                    SampleArgs sa{};
+                    sa.logits = c->shape_row; sa.n = d.vocab_size; sa.sp = c->sparams; sa.st = c->state; sa.out_tokens = c->out_tokens_dev; sa.out_cap = c->out_cap; sa.advance = 1; sa.sort_buf = c->sort_buf; sa.err = c->xwg_err;
+                    hipLaunchKernelGGL(k_sample_advance, dim3(1), dim3(kSampleBlock), sample_lds_bytes(d.vocab_size), st, sa);
+                } else {          // (the entry points admit temperature 0 only here: the first maximum of the shaped row)
+                    hipLaunchKernelGGL(k_argmax_advance, dim3(1), dim3(1024), 0, st, (const float*)c->shape_row, d.vocab_size, c->state, c->out_tokens_dev, 1, c->out_cap, (const int*)c->xwg_err);
+                }
+                HIPC(c, hipGetLastError());
             }
-            HIPC(c, hipGetLastError());
+            if (form == TokenForm::ShapedLp) { r = launch_logprob_token(c, st); if (r) return r; }   // an armed context: the drawn token's record (flm_logprob.h)
         } else if (form == TokenForm::Sampled) {   // a sampled token: every rank samples the same all-gathered logits with the same state and draws the same token
             if (!sample_supported(c)) return fail(c, FLM_ERR_UNSUPPORTED, "device sampler: vocabulary too large for one workgroup's LDS");
             Tick t(c, st, KC_ARGMAX);

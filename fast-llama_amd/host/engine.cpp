@@ -201,6 +201,8 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
     if (max_new_tokens > _cfg.max_seq_len - n_in) max_new_tokens = _cfg.max_seq_len - n_in;
     const int max_tokens = n_in + max_new_tokens;
 
+    _lp.clear();
+    if (_lp_top_n >= 0 && _ctxs.size() != 1) { _err = "--logprobs: one device only"; fprintf(stderr, "%s\n", _err.c_str()); return false; }
     int prev = -1;
     auto emit = [&](int tok, int index, int n_cur) {
         const std::string piece = _tok.decode(tok, prev);
@@ -246,7 +248,11 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
             armed = cr == FLM_OK;
         }
         const bool dev_ok = !_dfa_set || armed;
-        if (dev_ok && (_shape_set || armed)) {          // the sampling controls / the constraint: the same loop with the shaping stage on the device (flm_generate_ex; no control flag: neutral controls, masking only); refused: the host loop below shapes
+        const bool lp = _lp_top_n >= 0;     // --logprobs: armed before every run; the records exist on the device path only, so a refusal is an error, not a host loop
+        if (lp && (!dev_ok || flm_logprobs_arm(_ctxs[0], _lp_top_n, _lp_shaped ? FLM_LOGPROBS_SHAPED : FLM_LOGPROBS_RAW) != FLM_OK)) {
+            _err = std::string("--logprobs: ") + (dev_ok ? flm_last_error(_ctxs[0]) : "the constraint could not be armed on the device"); fprintf(stderr, "%s\n", _err.c_str()); return false;
+        }
+        if (dev_ok && (_shape_set || armed || lp)) {          // the sampling controls / the constraint: the same loop with the shaping stage on the device (flm_generate_ex; no control flag: neutral controls, masking only); refused: the host loop below shapes
             flm_sampling sp{};
             sp.temperature = temperature; sp.topp = topp; sp.top_k = _shape.top_k; sp.min_p = _shape.min_p; sp.repeat_penalty = _shape.repeat_penalty;
             sp.frequency_penalty = _shape.frequency_penalty; sp.presence_penalty = _shape.presence_penalty; sp.penalty_last_n = _shape_last_n;
@@ -260,6 +266,11 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
             }
             if (rc == FLM_ERR_UNSUPPORTED) rc = flm_generate_ex(_ctxs[0], input.data(), n_in, 0, want, &sp, &st, 0, on_token, &sink, nullptr, &n_out);
             if (rc == FLM_ERR_INVALID) { _err = flm_last_error(_ctxs[0]); fprintf(stderr, "%s\n", _err.c_str()); }
+            if (lp && rc != FLM_OK) { if (_err.empty()) _err = std::string("--logprobs: ") + flm_last_error(_ctxs[0]); return false; }
+            if (lp && n_out > 0) {
+                _lp.resize((size_t)n_out);
+                if (flm_last_logprobs(_ctxs[0], 0, n_out, _lp.data()) != FLM_OK) { _err = std::string("--logprobs: ") + flm_last_error(_ctxs[0]); _lp.clear(); return false; }
+            }
             whole = false;
         } else if (dev_ok && (_draft_k > 0 || (greedy && _lookup_k > 0))) {
             // --draft: the same loop through draft-and-verify steps at the run's temperature; refused (nothing was launched): the run without the flag.

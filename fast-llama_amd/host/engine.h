@@ -54,6 +54,10 @@ public:
     void set_constraint(std::vector<int32_t> row_ptr, std::vector<int32_t> edge_token, std::vector<int32_t> edge_next) {
         _dfa_row = std::move(row_ptr); _dfa_tok = std::move(edge_token); _dfa_nxt = std::move(edge_next); _dfa_set = true; _dfa_installed = false;
     }
+    // --logprobs N[,shaped] (this build only): the context is armed with flm_logprobs_arm before every generate on one device, the run takes the _ex path as an armed
+    // constraint does, and the records of the last generate are kept for the caller: one flm_logprob per delivered token
+    void set_logprobs(int top_n, bool shaped) { _lp_top_n = top_n; _lp_shaped = shaped; }
+    const std::vector<flm_logprob>& logprobs() const { return _lp; }
     int lookup_steps() const { return _lookup_steps; }
     int lookup_accepted() const { return _lookup_accepted; }
     int get_quant_type() const { return _cfg.quant_type; }
@@ -77,6 +81,7 @@ private:
     std::string _err;
     int _lookup_k = 0, _lookup_g = 3, _lookup_steps = 0, _lookup_accepted = 0;
     int _draft_k = 0, _draft_g = 3;
+    int _lp_top_n = -1; bool _lp_shaped = false; std::vector<flm_logprob> _lp;
     bool _dfa_set = false, _dfa_installed = false; std::vector<int32_t> _dfa_row, _dfa_tok, _dfa_nxt;
     bool _shape_set = false; ShapeControls _shape; int _shape_last_n = 0; std::vector<int32_t> _bias_ids; std::vector<float> _bias_values;
 };

@@ -40,6 +40,7 @@ struct Args {
     // the sampling controls (flm_sampling): any of these flags switches the shaping stage on
     bool shape_set = false; ShapeControls shape; int repeat_last_n = 64;
     std::vector<int32_t> bias_ids; std::vector<float> bias_values; const char* bad_sampling = nullptr;
+    int logprobs_n = -1; bool logprobs_shaped = false; const char* bad_logprobs = nullptr;   // --logprobs N[,shaped]: top-N alternatives per generated token (0..20; -1 = off), from the raw or the shaped row
     const char* constraint = nullptr;       // --constraint FILE: a token-level DFA in the `flm-dfa 1 <n_states>` text format
     std::vector<int32_t> dfa_row, dfa_tok, dfa_nxt;
     Mode mode = Mode::GEN;
@@ -70,6 +71,7 @@ void usage(const char* bin) {
     fprintf(stderr, "   --frequency-penalty <float>   subtracted per occurrence in the window, 0 = off (this build only)\n");
     fprintf(stderr, "   --logit-bias      <id=val[,id=val...]>  added to these tokens' logits; -inf bans a token; at most 256 pairs (this build only)\n");
     fprintf(stderr, "   --constraint      <file>      mask every generated token with a token-level DFA, armed at state 0: a `flm-dfa 1 <n_states>` line, then `state token next` per line (this build only)\n");
+    fprintf(stderr, "   --logprobs        <N[,shaped]>  on one device: after the text, one line per generated token `index id logprob | id:logprob ...` with the N (0..20) most likely alternatives, from the model's own distribution or (shaped) the row the sampler read (this build only)\n");
     fprintf(stderr, "   --encode,-e       <string>    encode the input string into tokens\n");
     fprintf(stderr, "   --decode,-d       <string>    decode the input tokens to text\n");
     fprintf(stderr, "   --help,-h                     print this message\n");
@@ -94,6 +96,12 @@ bool parse_draft(const char* v, int& k_out, int& g_out) {       // K or K,G with
     if (ok && *e == ',') { const char* s = e + 1; g = strtol(s, &e, 10); ok = e != s && g >= 1 && g <= 8; }
     if (!ok || *e != 0) return false;
     k_out = (int)k; g_out = (int)g;
+    return true;
+}
+bool parse_logprobs(const char* v, int& n_out, bool& shaped_out) {   // N or N,shaped with 0 <= N <= 20, nothing else
+    char* e; const long n = strtol(v, &e, 10);
+    if (e == v || n < 0 || n > FLM_LOGPROBS_MAX || (*e != 0 && strcmp(e, ",shaped") != 0)) return false;
+    n_out = (int)n; shaped_out = *e != 0;
     return true;
 }
 bool parse_float(const char* v, float& out) { char* e; const float f = strtof(v, &e); if (e == v || *e != 0) return false; out = f; return true; }
@@ -151,6 +159,7 @@ const Flag kFlags[] = {
     {nullptr, "--repeat-last-n",     true, [](Args& a, const char* v) { char* e; const long k = strtol(v, &e, 10); a.shape_set = true; if (e == v || *e || k < 0 || k > 1024) a.bad_sampling = v; else a.repeat_last_n = (int)k; }},         // (this build only)
     {nullptr, "--presence-penalty",  true, [](Args& a, const char* v) { a.shape_set = true; if (!parse_float(v, a.shape.presence_penalty) || a.shape.presence_penalty != a.shape.presence_penalty) a.bad_sampling = v; }},               // (this build only)
     {nullptr, "--frequency-penalty", true, [](Args& a, const char* v) { a.shape_set = true; if (!parse_float(v, a.shape.frequency_penalty) || a.shape.frequency_penalty != a.shape.frequency_penalty) a.bad_sampling = v; }},            // (this build only)
+    {nullptr, "--logprobs",          true, [](Args& a, const char* v) { if (!parse_logprobs(v, a.logprobs_n, a.logprobs_shaped)) a.bad_logprobs = v; }},                                                                          // (this build only)
     {nullptr, "--constraint",        true, [](Args& a, const char* v) { a.constraint = v; }},                                                                                                                                      // (this build only)
     {nullptr, "--logit-bias",        true, [](Args& a, const char* v) { a.shape_set = true; if (!parse_bias(v, a.bias_ids, a.bias_values)) a.bad_sampling = v; }},                                                                      // (this build only)
 };
@@ -170,6 +179,7 @@ void parse(Args& a, int argc, const char** argv) {
     if (a.bad_lookup) { fprintf(stderr, "Invalid --lookup:\x1b[31m%s\x1b[0m (expected K or K,G with 4 <= K <= 15 and 1 <= G <= 8)\n", a.bad_lookup); usage(argv[0]); exit(-1); }
     if (a.bad_draft) { fprintf(stderr, "Invalid --draft:\x1b[31m%s\x1b[0m (expected K or K,G with 4 <= K <= 15 and 1 <= G <= 8)\n", a.bad_draft); usage(argv[0]); exit(-1); }
     if (a.bad_sampling) { fprintf(stderr, "Invalid sampling control:\x1b[31m%s\x1b[0m (--top-k >= 0, --min-p in [0, 1), --repeat-penalty > 0, --repeat-last-n 0..1024, --logit-bias id=val[,id=val...] with at most 256 pairs)\n", a.bad_sampling); usage(argv[0]); exit(-1); }
+    if (a.bad_logprobs) { fprintf(stderr, "Invalid --logprobs:\x1b[31m%s\x1b[0m (expected N or N,shaped with 0 <= N <= 20)\n", a.bad_logprobs); usage(argv[0]); exit(-1); }
     if (a.rounds < 1) a.rounds = a.mode == Mode::TEST ? 16 : 1;
 }
 
@@ -241,6 +251,10 @@ int main(int argc, const char** argv) {
         fprintf(stderr, "warning: --draft applies to one device only; ignored\n");
         args.draft_k = 0;
     }
+    if (args.logprobs_n >= 0 && args.devices.size() > 1) {      // (refused, not ignored: the lines are what the caller asked for)
+        fprintf(stderr, "--logprobs applies to one device only: it cannot be combined with --devices of more than one\n");
+        return -1;
+    }
     if (args.constraint) {                  // a malformed file is a usage error, before any model is loaded
         std::string why;
         if (!load_constraint(args.constraint, args, why)) { fprintf(stderr, "Invalid --constraint file:\x1b[31m%s\x1b[0m (%s)\n", args.constraint, why.c_str()); usage(argv[0]); return -1; }
@@ -248,6 +262,7 @@ int main(int argc, const char** argv) {
     GpuTransformer tf(args.detail || args.debug);
     if (args.constraint) tf.set_constraint(args.dfa_row, args.dfa_tok, args.dfa_nxt);
     if (args.shape_set) tf.set_sampling(args.shape, args.repeat_last_n, args.bias_ids, args.bias_values);
+    if (args.logprobs_n >= 0) tf.set_logprobs(args.logprobs_n, args.logprobs_shaped);
     if (args.lookup_k) tf.set_lookup(args.lookup_k, args.lookup_g);
     if (args.draft_k) tf.set_draft(args.draft_k, args.draft_g);
     if (!tf.load(args.ckpt, args.tknr, args.ft, args.qtype, args.devices)) { fprintf(stderr, "Failed to load model\n%s\n", tf.error().c_str()); return 1; }
@@ -274,6 +289,14 @@ int main(int argc, const char** argv) {
         if (!tf.generate(args.prompt, cb, args.max_tokens, args.temp, args.topp) && !tf.error().empty()) { fprintf(stderr, "%s\n", tf.error().c_str()); return 1; }
         const int64_t total_us = now_us() - t0;
         if (args.mode != Mode::TEST) printf("%s\n\n", E);
+        if (args.mode != Mode::TEST && args.logprobs_n >= 0) {      // --logprobs: index id logprob | id:logprob ...; the log-probability in double from the record's exact ingredients
+            const auto& lp = tf.logprobs();
+            for (size_t i = 0; i < lp.size(); ++i) {
+                printf("%zu %d %.9g |", i, (int)lp[i].token, ((double)lp[i].logit - (double)lp[i].max_logit) - log((double)lp[i].sum));
+                for (int j = 0; j < lp[i].n_top; ++j) printf(" %d:%.9g", (int)lp[i].top_id[j], ((double)lp[i].top_logit[j] - (double)lp[i].max_logit) - log((double)lp[i].sum));
+                printf("\n");
+            }
+        }
         sum_prompt_tok += prompt_tokens; sum_output_tok += output_tokens;
         sum_prompt_ms += first_us / 1000.; sum_output_ms += (total_us - first_us) / 1000.;
     }

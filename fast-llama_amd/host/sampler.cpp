@@ -103,4 +103,32 @@ int dfa_next(const int32_t* row_ptr, const int32_t* edge_token, const int32_t* e
     return q;
 }
 
+void logprob_row(const float* R, int n, int chosen, int top_n, LogprobRecord* out) {
+    LogprobRecord r{};
+    // flm_score's statistics at temperature 1: the first maximum, the clipped exponentials (libm expf), their sequential sum in index order
+    float mx = R[0];
+    for (int i = 1; i < n; ++i) if (R[i] > mx) mx = R[i];
+    float sum = 0.0f;
+    for (int i = 0; i < n; ++i) {
+        const float d = R[i] - mx;
+        if (!(d < -15)) sum += expf(d);
+    }
+    r.token = chosen; r.logit = R[chosen]; r.max_logit = mx; r.sum = sum;
+    // the first n_top indices in "larger value, equal values by lower index" (float comparison: -0.0 ties +0.0; -inf takes part): a stable selection -- the indices arrive in
+    // ascending order, and one enters the list only in front of strictly smaller values
+    const int K = std::min(std::min(std::max(top_n, 0), kLogprobsMax), n);
+    int m = 0;
+    for (int i = 0; i < n && K > 0; ++i) {
+        const float x = R[i];
+        if (m == K && !(x > R[r.top_id[K - 1]])) continue;
+        int j = m < K ? m : K - 1;                      // the slot that opens: the list's end, or its last entry falls out
+        while (j > 0 && x > R[r.top_id[j - 1]]) { r.top_id[j] = r.top_id[j - 1]; --j; }
+        r.top_id[j] = i;
+        if (m < K) ++m;
+    }
+    r.n_top = K;
+    for (int j = 0; j < K; ++j) r.top_logit[j] = R[r.top_id[j]];
+    *out = r;
+}
+
 } // namespace flmhost

@@ -42,4 +42,11 @@ void constrain_logits(const float* L, int n, const int32_t* tokens, int count, f
 // fallback, `return _n - 1` in its multinomial branch, which can name a masked id)
 int dfa_next(const int32_t* row_ptr, const int32_t* edge_token, const int32_t* edge_next, int q, int t);
 
+// The record of one drawn token (include/flm_gpu.h, flm_logprob): a plain sequential restatement of its definition that the device's logprob_row (csrc/flm_logprob.h)
+// equals element for element.  R[n], n >= 2, chosen in [0, n), top_n in [0, kLogprobsMax]; the struct is flm_logprob's layout, 192 bytes
+constexpr int kLogprobsMax = 20;
+struct LogprobRecord { int32_t token; float logit, max_logit, sum; int32_t n_top; int32_t top_id[kLogprobsMax]; float top_logit[kLogprobsMax]; int32_t pad_[3]; };
+static_assert(sizeof(LogprobRecord) == 192, "flm_logprob is 192 bytes");
+void logprob_row(const float* R, int n, int chosen, int top_n, LogprobRecord* out);
+
 } // namespace flmhost

@@ -2,9 +2,12 @@
 // (no GPU needed).  Built as lib/libflm_host.so next to the CLI; the CLI itself does not use it.
 #include <math.h>
 #include <stdint.h>
+#include <stddef.h>
 #include <string.h>
 
 #include <string>
+
+#include "flm_gpu.h"
 
 #include "model_file.h"
 #include "sampler.h"
@@ -103,6 +106,17 @@ void fh_score_row(const float* x, int n, int target, void* out5) {
     struct { int32_t argmax; float target_logit, max_logit, sum, prob; } r{arg, 0.0f, mx, sum, 0.0f};
     if (target >= 0 && target < n) { r.target_logit = x[target]; r.prob = et * (float)(1. / sum); }
     memcpy(out5, &r, sizeof r);
+}
+// flm_logprob (include/flm_gpu.h) of one row with drawn id `chosen` (sampler.h logprob_row): out = the 192-byte struct; the expected value of the device's k_logprob_rows
+void fh_logprob_row(const float* x, int n, int chosen, int top_n, void* out) {
+    LogprobRecord r; logprob_row(x, n, chosen, top_n, &r);
+    memcpy(out, &r, sizeof r);
+}
+// the C struct's layout as the compiler sees it (include/flm_gpu.h): {sizeof, offsets of token, logit, max_logit, sum, n_top, top_id, top_logit, pad_}
+void fh_logprob_layout(int* out9) {
+    const int v[9] = {(int)sizeof(flm_logprob), (int)offsetof(flm_logprob, token), (int)offsetof(flm_logprob, logit), (int)offsetof(flm_logprob, max_logit), (int)offsetof(flm_logprob, sum),
+                      (int)offsetof(flm_logprob, n_top), (int)offsetof(flm_logprob, top_id), (int)offsetof(flm_logprob, top_logit), (int)offsetof(flm_logprob, pad_)};
+    memcpy(out9, v, sizeof v);
 }
 // the prompt-lookup drafter of flm_generate_lookup (spec_draft.h): h[n] -> d[k]; the expected value of the device's k_spec_draft
 void fh_spec_draft(const int32_t* h, int n, int k, int ngram_max, int32_t* d) { spec_draft(h, n, k, ngram_max, d); }

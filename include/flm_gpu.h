@@ -334,6 +334,45 @@ typedef struct flm_dfa {            /* CSR: the edges of state q are [row_ptr[q]
 int  flm_dfa_validate(const flm_dfa* dfa, int vocab);
 int  flm_constraint_set(flm_ctx* ctx, const flm_dfa* dfa);
 int  flm_constraint_arm(flm_ctx* ctx, int32_t state);
+/* Per-token log-probabilities and top-N alternatives from the device loop: how sure the model was of each id it delivered, and what the alternatives were (OpenAI-style
+ * logprobs / top_logprobs, llama.cpp's n_probs).  No reference counterpart.  One small stage (k_logprob_token / k_logprob_rows, csrc/flm_logprob.h: one 1024-thread workgroup
+ * per row) runs behind the draw, on the row that is still in device memory.  The record of ONE token drawn from a row R[0 .. n) with drawn id t, top_n in 0 .. FLM_LOGPROBS_MAX:
+ *   token, logit     t and R[t].  R[t] may be -inf: the multinomial branch's last-index fallback can name a masked id (see delta at flm_dfa)
+ *   max_logit, sum   exactly flm_score's fields on R at temperature 1: max_logit = the first maximum's value; e_i = (R[i] - max) < -15 ? 0 : expf(R[i] - max); sum = the
+ *                    sequential fp32 chain of the e_i in index order
+ *   n_top, top_id, top_logit   n_top = min(top_n, n); top_id[0 .. n_top) = the first n_top indices in the order "larger value, equal values by lower index, -0.0 ties +0.0"
+ *                    (step 3's order at flm_sampling), listed in that order; -inf entries take part, so a row with fewer than n_top finite entries lists its -inf entries by
+ *                    index; top_logit[j] = R[top_id[j]]; the entries at and beyond n_top are 0
+ * No logarithm is taken on the device: the caller evaluates (logit - max_logit) - log(sum) in double from bit-exact ingredients, flm_score's rule.  Rows with a NaN, or whose
+ * maximum is -inf, are outside the contract.  The host restatement is host/sampler.cpp logprob_row; the device equals it element for element.
+ * source selects R: FLM_LOGPROBS_RAW = the classifier's row L, the model's own distribution; FLM_LOGPROBS_SHAPED = the row S the sampler reads, after steps 0 - 4 (mask, bias,
+ * penalties, top-k, min-p).  Both are evaluated at temperature 1.  NOT built: dividing by the sampler's temperature, top-p renormalisation, records through the streaming
+ * callback (flm_token_cb is unchanged), tensor-parallel contexts, vocabularies beyond the sampler's bound, prompt tokens (that is flm_score_tokens).
+ * flm_logprobs_arm is a context setting like flm_constraint_arm (top_n -1: off).  It allocates nothing and re-captures nothing: top_n and source live in a device block that
+ * exists since flm_ctx_create (its contents are rewritten), like the record buffer of max_seq_len records, and the armed token graphs are built at flm_prepare next to the
+ * shaped ones.  flm_query "logprobs_top_n" reads the setting (-1: off).  (Not an option: flm_set_option drops the graphs.)  FLM_ERR_INVALID for top_n outside -1 .. 20 or a
+ * source other than 0 / 1; FLM_ERR_UNSUPPORTED on a sharded context and where the vocabulary is beyond the device sampler's LDS strip (the sum chain's bound, as in
+ * flm_score_tokens); FLM_ERR_STATE before the model is complete.
+ * While armed, the four _ex entry points -- flm_generate_ex, flm_forward_sample_ex, flm_verify_sample_ex, flm_generate_lookup_ex -- write one record per delivered id, record i
+ * for out_tokens[i] (flm_forward_sample_ex: one record per call).  An armed context counts as a control that is set: with every flm_sampling control neutral the shaped form
+ * still runs, the ids count in "shaped_tokens", and S is L bit for bit.  Arming changes no result: the ids, *n_out, *rng_state, the callbacks, the K/V rows and
+ * "constraint_state" equal the disarmed call's.  A stop token that is delivered has its record; the launches queued behind it write nothing.  Under source = raw with a control
+ * or a constraint set, a verify batch is shaped into side rows ([16][vocab], there since flm_ctx_create) so that the raw rows survive.  A retried call rewrites its records.
+ * The plain entry points ignore the setting.  On any error nothing is launched.
+ * flm_last_logprobs copies records [first, first + n) of the last _ex call to the host, through the bounce buffer (in pieces if need be): the only place records cross the
+ * bus -- an armed _ex call itself reads back nothing extra.  FLM_ERR_INVALID if first + n passes that call's *n_out (or n < 1); FLM_ERR_STATE if the last _ex call ran
+ * disarmed or failed, or there was none. */
+#define FLM_LOGPROBS_MAX 20
+#define FLM_LOGPROBS_RAW 0
+#define FLM_LOGPROBS_SHAPED 1
+typedef struct flm_logprob { int32_t token; float logit, max_logit, sum; int32_t n_top;
+                             int32_t top_id[FLM_LOGPROBS_MAX]; float top_logit[FLM_LOGPROBS_MAX]; int32_t pad_[3]; } flm_logprob; /* 192 bytes */
+int  flm_logprobs_arm(flm_ctx* ctx, int top_n /* -1: off; 0 .. FLM_LOGPROBS_MAX */, int source);
+int  flm_last_logprobs(flm_ctx* ctx, int first, int n, flm_logprob* out /* [n] */);
+/* measurement tap (tools/sample_bench.py --logprobs), in the manner of flm_kernel_times: the mean duration in microseconds of ONE launch of the token form's stage, `iters`
+ * launches enqueued back to back between one pair of HIP events, on the rows and the decode state the last armed _ex call left (each launch rewrites that call's last record
+ * with the same bytes).  FLM_ERR_STATE unless the context is armed and its last _ex call delivered ids. */
+int  flm_logprob_stage_time(flm_ctx* ctx, int iters, float* avg_us);
 /* the ids generated by the last flm_decode_greedy / flm_decode_sample / flm_decode_timed* call: out[n] (n <= its n_steps) */
 int  flm_last_tokens(flm_ctx* ctx, int n, int32_t* out);
 int  flm_reset_kv(flm_ctx* ctx);
@@ -362,7 +401,8 @@ int  flm_kernel_bytes(flm_ctx* ctx, int kclass, int pos, double* bytes);
  * what: 0 residual x1[dim], 1 q[dim], 2 attention output[dim], 3 hd[hidden], 4 K cache of `layer`
  * [heads][max_seq][hs], 5 V cache of `layer`, 6 logits; 11 / 12 the never-cleared flag lines / granule tags that
  * count from the epoch counters, as raw 32-bit words (the long-lived-context tests); 13 flm_generate's granule ring as the last call left it, two raw 32-bit
- * words per entry: {token | last << 31, the call's tag}. */
+ * words per entry: {token | last << 31, the call's tag}; 14 the per-token log-probability records as the device holds them (the slots behind the last call's *n_out
+ * included), 48 raw 32-bit words per record. */
 int  flm_debug_read(flm_ctx* ctx, int what, int layer, float* out, size_t n);
 
 /* Structure switches: which launches a token runs.  None of them changes a result bit; the defaults are what was measured fastest.
@@ -421,6 +461,7 @@ int  flm_set_option(flm_ctx* ctx, const char* key, int value);
  *   "sampled_tokens" how many tokens this context sampled on the device (flm_forward_sample / flm_decode_sample / flm_generate / flm_verify_sample / flm_generate_lookup_sample at temperature > 0),
  *   "shaped_tokens" how many tokens this context drew under the controls (flm_generate_ex / flm_forward_sample_ex / flm_verify_sample_ex / flm_generate_lookup_ex with a control set or a constraint armed),
    "constraint_state" the automaton state the context is armed at (flm_constraint_arm; moved on by every _ex call over the ids it delivers), -1: disarmed,
+ *   "logprobs_top_n" the top_n the context is armed with for per-token log-probabilities (flm_logprobs_arm), -1: off,
  *   "spec_steps" / "spec_accepted" the last flm_generate_lookup / flm_generate_lookup_sample call: verify passes run / drafted ids accepted in them,
  *   "gen_tokens" / "gen_streamed" the last flm_generate call: tokens delivered / how many of them were delivered while hipStreamQuery still said the stream was busy,
  *   "epoch_tail" / "epoch_eng" / "epoch_xchg" the epoch counters the cross-workgroup waits count from (device memory; the 32-bit pattern): the one-launch token's, the
@@ -469,6 +510,9 @@ int  flm_op_constrain_rows(const float* logits, int rows, int ld, int n, const f
                            const int32_t* drafts /* [rows - 1] */, const flm_dfa* dfa, int32_t state, float* out /* [rows][n] */, int32_t* states_out /* [rows] */);
 /* flm_score_tokens' statistics kernel (k_score_rows) on caller-supplied logits[rows][n]: out[rows]; targets[rows] as there (NULL: none).  2 <= n, n within the LDS bound. */
 int  flm_op_score_rows(const float* logits, int rows, int n, const int32_t* targets, flm_score* out);
+/* the record stage of flm_logprobs_arm (k_logprob_rows) on caller-supplied logits[rows][ld], n entries per row, 1 <= rows <= 16, ld >= n >= 2, n within the LDS bound:
+ * out[r] = the flm_logprob of row r with drawn id chosen[r] in [0, n) and top_n in [0, FLM_LOGPROBS_MAX]. */
+int  flm_op_logprob_rows(const float* logits, int rows, int ld, int n, const int32_t* chosen /* [rows] */, int top_n, flm_logprob* out /* [rows] */);
 /* simd::swiglu(xo,xr,n) (x86_simd.cpp:1766-1770) */
 int  flm_op_swiglu(float* xo, const float* xr, size_t n);
 /* rope_v2 (tf_operators.cpp:352-402): one head row of n_dims at position pos */

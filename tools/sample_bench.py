@@ -11,7 +11,11 @@ weights, 32 layers by default).  Prints one JSON line:
     sampler work) and with a full set of controls (top-k 40, min-p 0.05, repeat penalty 1.1 over 64 ids, a bias and a ban: the sampler then sorts fewer candidates), the
     runs alternating; the stage's own duration: k_shape_logits in a rocprofv3 --kernel-trace --stats run of this command;
   * with --constraint (and nothing else): the shaped token with and without an armed automaton, in the same run -- flm_generate_ex with a bias of +0 (the stage's launch,
-    no mask) against the same call armed with a Dfa.from_choices automaton whose every state on the way allows half the vocabulary (the even ids), alternating."""
+    no mask) against the same call armed with a Dfa.from_choices automaton whose every state on the way allows half the vocabulary (the even ids), alternating;
+  * with --logprobs (and nothing else): flm_generate_ex with a bias of +0 (the shaped form) disarmed, and armed with flm_logprobs_arm at top_n 0, 5 and 20 from the raw and
+    from the shaped row, alternating; the stage's own duration per launch from HIP events (flm_logprob_stage_time) and the sampler launch it follows (flm_kernel_times'
+    class "argmax" on the sampled form is the greedy argmax: the sampled launch's own figure is op_sample's, --ops).  On a library without the feature (the parent commit
+    through FLM_GPU_LIB) only the disarmed figure is measured: the same command gives the pair that shows the disarmed path did not move."""
 import argparse
 import importlib.util
 import json
@@ -48,8 +52,58 @@ def main():
     ap.add_argument("--ops-only", action="store_true")
     ap.add_argument("--shape", action="store_true", help="time the shaped loop (flm_generate_ex) against the unshaped one (flm_generate) on the same context, nothing else")
     ap.add_argument("--constraint", action="store_true", help="time the shaped token with and without an armed automaton (half the vocabulary allowed), nothing else")
+    ap.add_argument("--logprobs", action="store_true", help="time the shaped token disarmed and armed for per-token log-probabilities (top_n 0 / 5 / 20, raw / shaped), nothing else")
     args = ap.parse_args()
     out = {}
+    if args.logprobs:
+        cfg = synth.make_config("7B", ff.QT_INT8)
+        cfg.n_layers = args.layers
+        ctx = capi.Ctx(capi.desc_from_config(cfg), device=0)
+        _bench_module().upload_synthetic(ctx, cfg)
+        V, K = cfg.vocab_size, args.steps
+        prompt = np.array([1] + [int(x) for x in (np.arange(1, 9) * 7919) % V], np.int32)
+        noop = capi.Sampling(temperature=1.0, topp=0.9, bias={11: 0.0})
+        have = hasattr(capi.lib(), "flm_logprobs_arm")
+
+        def armed(top_n, source):
+            def run():
+                ctx.logprobs_arm(top_n, source)
+                r = ctx.generate_ex(prompt, 0, K, noop, rng_state=1234)
+                ctx.logprobs_arm(-1)
+                return r
+            return run
+        runs = {"disarmed": lambda: ctx.generate_ex(prompt, 0, K, noop, rng_state=1234)}
+        if have:
+            for source in ("raw", "shaped"):
+                for top_n in (0, 5, 20):
+                    runs[f"armed_{source}_top{top_n}"] = armed(top_n, source)
+        ts = {k: [] for k in runs}
+        ids = {}
+        for rep in range(args.reps + 1):
+            for name, fn in runs.items():                # alternating: every form sees the same machine
+                ctx.sync(); t0 = time.perf_counter(); ids[name] = fn()[0]; dt = time.perf_counter() - t0
+                if rep:
+                    ts[name].append(dt)
+        assert all(list(v) == list(ids["disarmed"]) for v in ids.values())      # arming changes no id
+        base = float(np.median(ts["disarmed"]))
+        for name in runs:
+            med = float(np.median(ts[name]))
+            out[f"{name}_tok_s"] = round(K / med, 1)
+            out[f"{name}_spread_ms"] = round((max(ts[name]) - min(ts[name])) * 1e3, 2)
+            if name != "disarmed":
+                out[f"{name}_extra_us_per_token"] = round((med - base) / K * 1e6, 1)
+                out[f"{name}_share_of_token"] = round((med - base) / base, 4)
+        if have:
+            for source in ("raw", "shaped"):
+                for top_n in (0, 5, 20):
+                    ctx.logprobs_arm(top_n, source)
+                    ctx.generate_ex(prompt, 0, K, noop, rng_state=1234)
+                    out[f"stage_{source}_top{top_n}_us"] = round(ctx.logprob_stage_time(50), 2)
+            ctx.logprobs_arm(-1)
+        out["tokens_per_call"] = K; out["prompt_tokens"] = len(prompt); out["layers"] = args.layers; out["feature_present"] = bool(have)
+        ctx.close()
+        print(json.dumps(out), flush=True)
+        return
     if args.constraint:
         cfg = synth.make_config("7B", ff.QT_INT8)
         cfg.n_layers = args.layers
