@@ -332,35 +332,13 @@ class Ctx:
         _check(lib().flm_decode_sample(self._h, int(first_token), int(pos), int(n_steps), C.c_float(temperature), C.c_float(topp), C.byref(st), _p(out)), self._h)
         return out, st.value
 
-    def generate(self, prompt, pos, max_tokens, temperature=0.0, topp=0.9, rng_state=0, stop_token=-1, on_token=None, want_ids=True):
-        """flm_generate -> (ids[n_out], the sampler state after the n_out draws).  on_token(index, token, last) is called per token while the device computes the next
-        ones; a truthy return cancels.  want_ids=False passes out_tokens = NULL (the ids then come through on_token only; the returned array is empty)."""
-        t = np.ascontiguousarray(prompt, dtype=np.int32)
+    def _stream(self, call, max_tokens, on_token, want_ids, rng_state=0, sampling=None):
+        """what the five generate* wrappers share: out_tokens / n_out / the sampler state, the trampoline around on_token (kept alive, like the Sampling's arrays, for the
+        duration of the call), the call itself -- call(sp, st, cb, out, n_out), sp the flm_sampling of `sampling` or None --, a callback's exception re-raised behind it, and
+        for the _ex forms (sampling given) the *n_out last_logprobs() asks for (1 where the call failed) -> (ids[n_out], the sampler state after the n_out draws)"""
         out = np.empty(max(int(max_tokens), 1), dtype=np.int32) if want_ids else None
         st = C.c_uint64(int(rng_state)); n_out = C.c_int(0)
-        raised = []
-
-        def tramp(_user, index, token, last):
-            try:
-                return 1 if on_token(int(index), int(token), bool(last)) else 0
-            except BaseException as e:      # (an exception must not unwind through the C frames: cancel, re-raise behind the call)
-                raised.append(e)
-                return 1
-        cb = TOKEN_CB(tramp) if on_token is not None else C.cast(None, TOKEN_CB)      # (kept alive by this frame for the duration of the call)
-        rc = lib().flm_generate(self._h, _p(t), len(t), int(pos), int(max_tokens), C.c_float(temperature), C.c_float(topp), C.byref(st),
-                                C.c_int32(int(stop_token)), cb, None, _p(out), C.byref(n_out))
-        del cb
-        if raised:
-            raise raised[0]
-        _check(rc, self._h)
-        return (out[:n_out.value].copy() if want_ids else np.empty(0, dtype=np.int32)), st.value
-
-    def generate_ex(self, prompt, pos, max_tokens, sampling, rng_state=0, stop_token=-1, on_token=None, want_ids=True):
-        """flm_generate_ex: generate() with the sampling controls of a Sampling -> (ids[n_out], the sampler state after the n_out draws)"""
-        t = np.ascontiguousarray(prompt, dtype=np.int32)
-        out = np.empty(max(int(max_tokens), 1), dtype=np.int32) if want_ids else None
-        st = C.c_uint64(int(rng_state)); n_out = C.c_int(0)
-        sp, keep = sampling.struct()
+        sp, keep = sampling.struct() if sampling is not None else (None, None)
         raised = []
 
         def tramp(_user, index, token, last):
@@ -370,14 +348,29 @@ class Ctx:
                 raised.append(e)
                 return 1
         cb = TOKEN_CB(tramp) if on_token is not None else C.cast(None, TOKEN_CB)
-        rc = lib().flm_generate_ex(self._h, _p(t), len(t), int(pos), int(max_tokens), C.byref(sp), C.byref(st),
-                                   C.c_int32(int(stop_token)), cb, None, _p(out), C.byref(n_out))
+        rc = call(C.byref(sp) if sp is not None else None, C.byref(st), cb, _p(out), C.byref(n_out))
         del cb, keep
-        self._ex_n_out = int(n_out.value) if rc == 0 else 1
+        if sampling is not None:
+            self._ex_n_out = int(n_out.value) if rc == 0 else 1
         if raised:
             raise raised[0]
         _check(rc, self._h)
         return (out[:n_out.value].copy() if want_ids else np.empty(0, dtype=np.int32)), st.value
+
+    def generate(self, prompt, pos, max_tokens, temperature=0.0, topp=0.9, rng_state=0, stop_token=-1, on_token=None, want_ids=True):
+        """flm_generate -> (ids[n_out], the sampler state after the n_out draws).  on_token(index, token, last) is called per token while the device computes the next
+        ones; a truthy return cancels.  want_ids=False passes out_tokens = NULL (the ids then come through on_token only; the returned array is empty)."""
+        t = np.ascontiguousarray(prompt, dtype=np.int32)
+        return self._stream(lambda sp, st, cb, out, n_out: lib().flm_generate(
+            self._h, _p(t), len(t), int(pos), int(max_tokens), C.c_float(temperature), C.c_float(topp), st, C.c_int32(int(stop_token)), cb, None, out, n_out),
+            max_tokens, on_token, want_ids, rng_state)
+
+    def generate_ex(self, prompt, pos, max_tokens, sampling, rng_state=0, stop_token=-1, on_token=None, want_ids=True):
+        """flm_generate_ex: generate() with the sampling controls of a Sampling -> (ids[n_out], the sampler state after the n_out draws)"""
+        t = np.ascontiguousarray(prompt, dtype=np.int32)
+        return self._stream(lambda sp, st, cb, out, n_out: lib().flm_generate_ex(
+            self._h, _p(t), len(t), int(pos), int(max_tokens), sp, st, C.c_int32(int(stop_token)), cb, None, out, n_out),
+            max_tokens, on_token, want_ids, rng_state, sampling)
 
     def forward_sample_ex(self, tokens, pos, sampling, window=(), rng_state=0):
         """flm_forward_sample_ex -> (next token, the sampler state after the draw); window: the ids the penalties look at, used as given"""
@@ -449,24 +442,9 @@ class Ctx:
     def generate_lookup(self, prompt, pos, max_tokens, stop_token=-1, draft_len=7, ngram_max=3, on_token=None, want_ids=True) -> np.ndarray:
         """flm_generate_lookup -> ids[n_out]: flm_generate at temperature 0 through draft-and-verify steps.  on_token(index, token, last) as in generate."""
         t = np.ascontiguousarray(prompt, dtype=np.int32)
-        out = np.empty(max(int(max_tokens), 1), dtype=np.int32) if want_ids else None
-        n_out = C.c_int(0)
-        raised = []
-
-        def tramp(_user, index, token, last):
-            try:
-                return 1 if on_token(int(index), int(token), bool(last)) else 0
-            except BaseException as e:      # (an exception must not unwind through the C frames: cancel, re-raise behind the call)
-                raised.append(e)
-                return 1
-        cb = TOKEN_CB(tramp) if on_token is not None else C.cast(None, TOKEN_CB)
-        rc = lib().flm_generate_lookup(self._h, _p(t), len(t), int(pos), int(max_tokens), C.c_int32(int(stop_token)), int(draft_len), int(ngram_max),
-                                       cb, None, _p(out), C.byref(n_out))
-        del cb
-        if raised:
-            raise raised[0]
-        _check(rc, self._h)
-        return out[:n_out.value].copy() if want_ids else np.empty(0, dtype=np.int32)
+        return self._stream(lambda sp, st, cb, out, n_out: lib().flm_generate_lookup(
+            self._h, _p(t), len(t), int(pos), int(max_tokens), C.c_int32(int(stop_token)), int(draft_len), int(ngram_max), cb, None, out, n_out),
+            max_tokens, on_token, want_ids)[0]
 
     def verify_sample(self, first_token, drafts, pos, temperature, topp, rng_state):
         """flm_verify_sample -> (the m + 1 ids the sampled decode loop started with first_token at pos and rng_state draws, m = the drafts that were right; the state after
@@ -482,24 +460,9 @@ class Ctx:
         """flm_generate_lookup_sample -> (ids[n_out], the sampler state after the n_out draws): flm_generate at any temperature through draft-and-verify steps.
         on_token(index, token, last) as in generate."""
         t = np.ascontiguousarray(prompt, dtype=np.int32)
-        out = np.empty(max(int(max_tokens), 1), dtype=np.int32) if want_ids else None
-        st = C.c_uint64(int(rng_state)); n_out = C.c_int(0)
-        raised = []
-
-        def tramp(_user, index, token, last):
-            try:
-                return 1 if on_token(int(index), int(token), bool(last)) else 0
-            except BaseException as e:      # (an exception must not unwind through the C frames: cancel, re-raise behind the call)
-                raised.append(e)
-                return 1
-        cb = TOKEN_CB(tramp) if on_token is not None else C.cast(None, TOKEN_CB)
-        rc = lib().flm_generate_lookup_sample(self._h, _p(t), len(t), int(pos), int(max_tokens), C.c_float(temperature), C.c_float(topp), C.byref(st),
-                                              C.c_int32(int(stop_token)), int(draft_len), int(ngram_max), cb, None, _p(out), C.byref(n_out))
-        del cb
-        if raised:
-            raise raised[0]
-        _check(rc, self._h)
-        return (out[:n_out.value].copy() if want_ids else np.empty(0, dtype=np.int32)), st.value
+        return self._stream(lambda sp, st, cb, out, n_out: lib().flm_generate_lookup_sample(
+            self._h, _p(t), len(t), int(pos), int(max_tokens), C.c_float(temperature), C.c_float(topp), st, C.c_int32(int(stop_token)), int(draft_len), int(ngram_max),
+            cb, None, out, n_out), max_tokens, on_token, want_ids, rng_state)
 
     def verify_sample_ex(self, first_token, drafts, pos, sampling, window=(), rng_state=0):
         """flm_verify_sample_ex -> (the m + 1 ids a flm_forward_sample_ex loop started with first_token at pos draws when it slides `window` over them, m = the drafts that
@@ -519,26 +482,9 @@ class Ctx:
         """flm_generate_lookup_ex -> (ids[n_out], the sampler state after the n_out draws): flm_generate_ex through draft-and-verify steps.
         on_token(index, token, last) as in generate."""
         t = np.ascontiguousarray(prompt, dtype=np.int32)
-        out = np.empty(max(int(max_tokens), 1), dtype=np.int32) if want_ids else None
-        st = C.c_uint64(int(rng_state)); n_out = C.c_int(0)
-        sp, keep = sampling.struct()
-        raised = []
-
-        def tramp(_user, index, token, last):
-            try:
-                return 1 if on_token(int(index), int(token), bool(last)) else 0
-            except BaseException as e:      # (an exception must not unwind through the C frames: cancel, re-raise behind the call)
-                raised.append(e)
-                return 1
-        cb = TOKEN_CB(tramp) if on_token is not None else C.cast(None, TOKEN_CB)
-        rc = lib().flm_generate_lookup_ex(self._h, _p(t), len(t), int(pos), int(max_tokens), C.byref(sp), C.byref(st), C.c_int32(int(stop_token)),
-                                          int(draft_len), int(ngram_max), cb, None, _p(out), C.byref(n_out))
-        del cb, keep
-        self._ex_n_out = int(n_out.value) if rc == 0 else 1
-        if raised:
-            raise raised[0]
-        _check(rc, self._h)
-        return (out[:n_out.value].copy() if want_ids else np.empty(0, dtype=np.int32)), st.value
+        return self._stream(lambda sp, st, cb, out, n_out: lib().flm_generate_lookup_ex(
+            self._h, _p(t), len(t), int(pos), int(max_tokens), sp, st, C.c_int32(int(stop_token)), int(draft_len), int(ngram_max), cb, None, out, n_out),
+            max_tokens, on_token, want_ids, rng_state, sampling)
 
     def decode_timed(self, first_token, pos, n_steps) -> float:
         ms = C.c_float(0)

@@ -1,6 +1,9 @@
 // flm_host.h -- what the translation units of libflm_gpu.so share on the HOST side: the context, the launch planning of the GEMV and the entry points of one
 // translation unit that another one calls.
-//   flm_gpu.hip          context, upload, options, p2p bootstrap, the model-level C ABI (forward / decode / generate / score / draft-and-verify / debug taps), run_token
+//   flm_gpu.hip          the context and everything that outlives a call: create / destroy, upload, residency and fallback, the p2p bootstrap, options and queries, epoch
+//                        ageing, the debug taps, the graph cache (run_token / run_tokens / prepare_all), warm_up, flm_prepare
+//   flm_calls.hip        what a call does: check_ready, feed, the retry wrapper, the by-value block setters, d2h / h2d, the draw plan (Draw) and the model-level entry
+//                        points (forward / decode / generate / score / draft-and-verify / constraint / log-probabilities)
 //   flm_token.hip        the per-token launch sequence (enqueue_token), the per-phase and fused decode launches, per-kernel timing (flm_kernel_times / _bytes)
 //   flm_layerlaunch.hip  the whole-layer launch k_attn_ffn (flm_layer.h)
 //   flm_prompt.hip       the batched prompt path (GEMM tiles on the matrix cores, prompt attention)
@@ -168,16 +171,16 @@ struct flm_ctx {
     // folded over after every call, and the armed state (-1: disarmed; "constraint_state")
     flm::DfaBlock* dfa_blk = nullptr; int* dfa_dev = nullptr;
     std::vector<int32_t> dfa_row, dfa_tok, dfa_nxt; int dfa_state = -1;
-    // flm_generate (flm_gpu.hip): the granule ring [max_seq_len] and the cancel word -- page-locked, mapped, host-coherent memory allocated at create (gen_host; the device's view of it:
+    // flm_generate (flm_calls.hip): the granule ring [max_seq_len] and the cancel word -- page-locked, mapped, host-coherent memory allocated at create (gen_host; the device's view of it:
     // gen_ring_dev / gen_cancel_dev) --, what set_state writes into the decode state's generate words (gen_stop .. gen_max: -1 / 0 / 0 outside a flm_generate call), the
     // per-attempt sequence number the granules are tagged with, a pageable staging buffer for the ids, and the last call's figures ("gen_tokens" / "gen_streamed")
     unsigned long long* gen_host = nullptr; unsigned long long* gen_ring_dev = nullptr; const int* gen_cancel_dev = nullptr; int gen_cap = 0;
     int gen_stop = -1; unsigned gen_tag = 0; int gen_max = 0; unsigned gen_seq = 0;
     std::vector<int32_t> gen_ids; int gen_tokens = 0, gen_streamed = 0;
-    // flm_score_tokens (flm_gpu.hip; the classifier stage: flm_prompt.hip): the rows' targets and statistics in device memory [max_seq_len] (allocated at create), and the
+    // flm_score_tokens (flm_calls.hip; the classifier stage: flm_prompt.hip): the rows' targets and statistics in device memory [max_seq_len] (allocated at create), and the
     // classifier's scales group-major (cls.st) for the GEMM tiles, transposed once per set of weights
     int* score_tgt = nullptr; flm::ScoreRow* score_dev = nullptr; bool cls_st_ready = false;
-    // draft-and-verify, greedy, sampled and under the controls (flm_gpu.hip verify_impl / generate_lookup_impl; kernels: flm_spec.h, flm_shape.h k_shape_rows): the call's token history [max_seq_len + 32], the batch rows'
+    // draft-and-verify, greedy, sampled and under the controls (flm_calls.hip verify_impl / generate_lookup_impl; kernels: flm_spec.h, flm_shape.h k_shape_rows): the call's token history [max_seq_len + 32], the batch rows'
     // ids [16] (first maxima or draws) and the step's result block (the accepted ids and the sampler's state behind them, one trip), device memory since create; which GEMM
     // the verify pass runs; the last call's figures ("spec_steps" / "spec_accepted")
     int* spec_hist = nullptr; int* spec_arg = nullptr; flm::SpecOut* spec_res = nullptr;
@@ -290,7 +293,7 @@ enum XKind { XK_ATT = 0, XK_X1 = 1, XK_HD = 2, XK_LOGITS = 3 };
 int exchange(flm_ctx* c, hipStream_t st, int kind, float* full, float* mine, int count);
 int enqueue_token(flm_ctx* c, hipStream_t st, bool with_cls, TokenForm form, int G);
 int launch_logprob_token(flm_ctx* c, hipStream_t st);                  // (flm_token.hip: the armed form's last launch)
-// flm_sampling -> the shaper's parameter block (flm_gpu.hip): validates everything include/flm_gpu.h lists (null on success, else what is wrong); window[n_window] becomes the
+// flm_sampling -> the shaper's parameter block (flm_calls.hip): validates everything include/flm_gpu.h lists (null on success, else what is wrong); window[n_window] becomes the
 // block's head; *active: some control is not neutral.  follow: flm_generate_ex's sliding window (penalty_last_n), else the window as given
 const char* shape_fill(const flm_sampling* sp, int vocab, const int32_t* window, int n_window, bool follow, flm::ShapeParams* out, bool* active);
 int run_token(flm_ctx* c, bool with_cls, TokenForm form, int T);
@@ -308,21 +311,46 @@ inline bool ids_in_vocab(const flm_ctx* c, const int32_t* ids, int n) {
     for (int i = 0; i < n; ++i) if (ids[i] < 0 || ids[i] >= c->d.vocab_size) return false;
     return true;
 }
-// How a call's tokens are drawn: the token form, the sampler's parameters, the caller's xorshift state and, for the shaped form, the shaper's parameter block (flm_gpu.hip)
+struct SpecDraw;
+// How a call draws its tokens, resolved ONCE at the entry point (flm_calls.hip: the plain entry points construct it, the _ex ones go through draw_resolve) and the only
+// thing an implementation receives about drawing.  An implementation asks for the form, arms its attempts and commits; which of a control, an armed constraint or a context
+// armed for log-probabilities made the form shaped it cannot tell and need not know.
 struct Draw {
-    TokenForm form; float temperature, topp; uint64_t* rng_state; const flm::ShapeParams* shape;
-    int cstate = -1;                                              // the constraint's state at the call's first token (-1: none; only with a block: an armed constraint counts as a control)
-    int lp_base = -1;                                             // the context is armed for log-probabilities: the record index of the token at step 0 (-1: not armed); the form is then ShapedLp
-    unsigned long long after = 0;                                 // the state an attempt left on the device (fetch); the caller's changes only behind a verified attempt (commit)
-    // Greedy / Sampled by temperature, Shaped where a block is given
-    Draw(float t, float p, uint64_t* st, const flm::ShapeParams* sh = nullptr, int cq = -1, int lp = -1) : form(sh ? (lp >= 0 ? TokenForm::ShapedLp : TokenForm::Shaped) : t != 0.0f ? TokenForm::Sampled : TokenForm::Greedy), temperature(t), topp(p), rng_state(st), shape(sh), cstate(sh ? cq : -1), lp_base(sh ? lp : -1) {}
-    Draw(TokenForm f, float t, float p, uint64_t* st) : form(f), temperature(t), topp(p), rng_state(st), shape(nullptr) {}
-    bool coins() const { return form == TokenForm::Sampled || (shaped_form(form) && temperature != 0.0f); }   // the caller's state is read and moved on
-    int arm(flm_ctx* c) const;             // an attempt's start: the shaper's block, the constraint's {state, 0}, then the sampler's parameters FROM THE CALLER'S STATE -- a retried attempt draws nothing twice
-    int fetch(flm_ctx* c);                 // an attempt's end: the state behind its draws comes back
-    void commit(flm_ctx* c, int n) const;  // a verified attempt of n tokens: the caller's state, "sampled_tokens" / "shaped_tokens"
+    float temperature, topp; uint64_t* rng_state;
+    TokenForm form;                                               // Greedy / Sampled by temperature (sampler: Sampled whatever the temperature -- flm_forward_sample / flm_decode_sample); shape_by: Shaped / ShapedLp
+    flm::ShapeParams block;                                       // the shaper's parameter block (shaped forms only)
+    int cstate = -1;                                              // the constraint's state at the call's first token (-1: none; only with the block: an armed constraint counts as a control)
+    bool lp = false;                                              // the context is armed for log-probabilities: the form is ShapedLp, record i is the call's i-th id's
+    Draw(float t = 0.0f, float p = 0.0f, uint64_t* st = nullptr, bool sampler = false) { plain(t, p, st, sampler); }
+    void plain(float t, float p, uint64_t* st, bool sampler = false) { temperature = t; topp = p; rng_state = st; form = t != 0.0f || sampler ? TokenForm::Sampled : TokenForm::Greedy; }
+    void shape_by(int cq, bool armed) { form = armed ? TokenForm::ShapedLp : TokenForm::Shaped; cstate = cq; lp = armed; }   // `block` is filled: the shaped form runs
+    bool shaped() const { return shaped_form(form); }
+    bool coins() const { return form == TokenForm::Sampled || (shaped() && temperature != 0.0f); }   // the caller's state is read and moved on
+    // an attempt's start: the shaper's block, the constraint's {state, 0}, the record stage's base, then the sampler's parameters FROM THE CALLER'S STATE -- a retried attempt draws nothing twice
+    int arm(flm_ctx* c) const { return arm_with(c, block, coins() ? (unsigned long long)*rng_state : 0ull, cstate, 0); }       // (rng_state may be null where no coin is drawn)
+    // a later single-token step of a call that holds its running copies on the host (generate_lookup_impl): the sampler's state, the constraint's state and the record base
+    // as they stand behind the n_hist = n_prompt + n_drawn ids so far; the block's head is the window as given, the last min(last_n, n_hist) ids of prompt ++ drawn
+    int arm_step(flm_ctx* c, unsigned long long rng, int q, int rec_base, const int32_t* prompt, int n_prompt, const int32_t* drawn, int n_drawn) const;
+    int arm_block(flm_ctx* c) const;       // a verify batch's attempt: the block alone (the rows' draws take everything else as launch arguments: batch)
+    // the batch form of this plan for one verify step: what varies per step is the xorshift state its rows' coins count from, the window in device memory
+    // (win[0 .. n_win) ++ the drafts in front of a row; win null: the block's own head, as the last arm_block left it), the constraint's state at row 0 and the record index of row 0
+    SpecDraw batch(const flm_ctx* c, unsigned long long base, const int* win, int n_win, int q, int rec_base) const;
+    int fetch(flm_ctx* c, unsigned long long* after) const;       // an attempt's end: the state behind its draws comes back
+    // a verified attempt that delivered ids[0 .. n) and left the sampler's state `after`: the ONE place that writes the caller's state, "sampled_tokens" / "shaped_tokens",
+    // "constraint_state" (folded over the ids; q_after: the caller folded step by step) and the count of records flm_last_logprobs hands out
+    void commit(flm_ctx* c, const int32_t* ids, int n, unsigned long long after) const;
+    void commit(flm_ctx* c, int n, unsigned long long after, int q_after) const;
+private:
+    int arm_with(flm_ctx* c, const flm::ShapeParams& blk, unsigned long long rng, int q, int rec_base) const;
 };
 int check_ready(flm_ctx* c, int n, int pos);
+// what flm_calls.hip calls of flm_gpu.hip (the context's state and the graph cache), then what flm_gpu.hip calls of a call's plumbing (warm_up, flm_debug_read)
+bool model_complete(const flm_ctx* c);
+int run_tokens(flm_ctx* c, int pos, int n, TokenForm form);
+int maybe_recover(flm_ctx* c, int tokens);
+int feed(flm_ctx* c, const int32_t* tokens, int n, int pos, TokenForm last);
+int d2h(flm_ctx* c, void* dst, const void* src_dev, size_t bytes);
+float* score_stage(const flm_ctx* c, int* chunk);
 constexpr int kPrefillMin = 4;
 int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers = false, bool skinny = false);      // (flm_prompt.hip; by the model's quant type.  all_layers: the last layer is completed too -- flm_score_tokens needs every row's final residual; skinny: int8 and B <= 16: every GEMM through k_gemm_q8_skinny -- the verify pass under "spec_gemm" 1)
 // flm_score_tokens' classifier stage (flm_prompt.hip): rows [row0, row0 + m) of the batch's final residual (pf_x) -> output norm, quantize, the classifier GEMM tiles into
@@ -331,15 +359,15 @@ int score_classify(flm_ctx* c, int row0, int m, float* stage);
 // the verify pass's classifier stage (flm_prompt.hip): score_classify's prologue and GEMM (skinny: k_gemm_q8_skinny), then k_argmax_rows into argmax_out[row0 ..]
 // (draw: temperature, top-p and the step's xorshift state: k_sample_rows draws row row0 + i with that state's (row0 + i + 1)-th coin; temperature 0: k_argmax_rows)
 // shape (the device block) given: k_shape_rows shapes the chunk's rows in place in front of the draw, row i over the last min(last_n, n_win + i) ids of
-// win[0 .. n_win) ++ the batch's drafts in front of it (prompt_dev + 1); null: no shape kernel runs
+// win[0 .. n_win) ++ the batch's drafts in front of it (prompt_dev + 1); null: no shape kernel runs.  Filled by Draw::batch and by nobody else
 struct SpecDraw { float temperature, topp; unsigned long long base; const flm::ShapeParams* shape = nullptr; const int* win = nullptr; int n_win = 0; int cstate = -1 /* the batch's base constraint state; -1: none */;
                   int lp_top_n = -1 /* the context is armed: k_logprob_rows behind the rows' draws, records from lp_base on; -1: not */, lp_source = 0, lp_base = 0; };
 // k_shape_rows on `rows` rows (batch rows row0 ..) of n logits, ld floats apart -> out, ld_out apart (out == logits: in place); c may be null: flm_op_shape_rows
 int launch_shape_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, float* out, int ld_out, int n, int row0, int rows, const flm::ShapeParams* p,
                       const int* win, int n_win, const int* drafts, const flm::DfaBlock* dfa = nullptr, int cstate = -1, int* states_out = nullptr);
-// delta folded over ids[0 .. n) from state q on the context's host copy of the automaton (flm_gpu.hip; q in [0, n_states))
+// delta folded over ids[0 .. n) from state q on the context's host copy of the automaton (flm_calls.hip; q in [0, n_states))
 int dfa_fold(const flm_ctx* c, int q, const int32_t* ids, int n);
-// the rules of flm_dfa_validate (flm_gpu.hip): null, or which one failed
+// the rules of flm_dfa_validate (flm_calls.hip): null, or which one failed
 const char* dfa_check(const flm_dfa* dfa, int vocab);
 int spec_classify(flm_ctx* c, int row0, int m, float* stage, bool skinny, int* argmax_out, const SpecDraw& draw);
 // k_logprob_rows on `rows` <= 16 rows of n logits, ld floats apart, batch rows row0 ..: chosen[row0 + r] the row's drawn id, its record rec[rec_base + row0 + r]
