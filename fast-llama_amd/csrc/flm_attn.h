@@ -219,15 +219,35 @@ __device__ __forceinline__ void attn_head(const AttnArgs& a, const int h, char* 
             for (int u = 0; u < DV; ++u) request(rV, u, nt, prowv, goffv, ringV[u], Told);
         }
     }
+    // GRIN: q and this token's K / V row as granules (tag epoch_arg) from the QKV phase of this launch: every thread re-reads ITS pieces until their tags match -- q element tid,
+    // the four granules from column kcol of the K row (none: kcol < 0) and, if own_v, from column vcol of the V row.  No line round, no read behind it.
+    struct Swept { unsigned qbits; v4f kp, vp; };
+    auto sweep = [&](const int kcol, const int vcol, const bool own_v) -> Swept {
+        const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned long long*>(a.qg) + (size_t)h * hs, 0, hs * 8, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned long long*>(a.kg) + (size_t)h * hs, 0, hs * 8, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned long long*>(a.vg) + (size_t)h * hs, 0, hs * 8, 0x00020000);
+        unsigned qbits = 0; v4u32 KA = {0u, 0u, 0u, 0u}, KC = KA, VA = KA, VC = KA;
+        bool okq = tid >= hs, okk = kcol < 0, okv = !own_v;
+        const int gave_up = __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+        while (true) {
+            asm volatile("" ::: "memory");
+            uint2 qq = make_uint2(0u, 0u);
+            if (!okq) qq = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rq, tid * 8, 0, kAuxCoherent));
+            if (!okk) granules4_load(rk, kcol * 8, KA, KC);
+            if (!okv) granules4_load(rv, vcol * 8, VA, VC);
+            if (!okq) { okq = tag_is(qq.y, epoch_arg); qbits = qq.x; }
+            if (!okk) okk = granules4_tagged(KA, KC, epoch_arg);
+            if (!okv) okv = granules4_tagged(VA, VC, epoch_arg);
+            if (__all(okq && okk && okv) || gave_up) break;
+            if (give_up_local(t0, a.err)) break;
+        }
+        return Swept{qbits, granules4_values(KA, KC), granules4_values(VA, VC)};
+    };
     constexpr bool swept = PRE && !SPLIT && GRIN;                  // (GRIN: k_layers' one-launch token, one workgroup per head)
     if constexpr (swept) {
         {
-            // q and this token's K / V row as granules (tag epoch_arg) from the QKV phase of this launch: every thread re-reads ITS pieces until their tags match -- q element
-            // tid, and at most one 16-byte piece of the K tile and of the V tile that hold row T - 1 (T <= 2 tiles: everything was requested above).  No line round, no read behind it.
-            typedef unsigned v4u32 __attribute__((ext_vector_type(4)));
-            const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned long long*>(a.qg) + (size_t)h * hs, 0, hs * 8, 0x00020000);
-            const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned long long*>(a.kg) + (size_t)h * hs, 0, hs * 8, 0x00020000);
-            const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned long long*>(a.vg) + (size_t)h * hs, 0, hs * 8, 0x00020000);
+            // at most one 16-byte piece of the K tile and of the V tile that hold row T - 1 (T <= 2 tiles: everything was requested above)
             int kcol = -1, vcol = -1;                                   // first column of the thread's piece of row T - 1 (none: -1)
 #pragma unroll
             for (int u = 0; u < D; ++u)
@@ -236,26 +256,10 @@ __device__ __forceinline__ void attn_head(const AttnArgs& a, const int h, char* 
                     if (sb + u < se && (sb + u) * kAttnTile + prow[j] == T - 1) kcol = (goff[j] >> 2) % hs;
                     if (u < DV && u < nt && u * kAttnTile + prowv[j] == T - 1) vcol = (goffv[j] >> 2) % hs;
                 }
-            unsigned qbits = 0; v4u32 KA = {0u, 0u, 0u, 0u}, KC = KA, VA = KA, VC = KA;
-            bool okq = tid >= hs, okk = kcol < 0, okv = vcol < 0;
-            const int gave_up = __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-            while (true) {
-                asm volatile("" ::: "memory");
-                uint2 qq = make_uint2(0u, 0u);
-                if (!okq) qq = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rq, tid * 8, 0, kAuxCoherent));
-                if (!okk) { KA = __builtin_bit_cast(v4u32, __builtin_amdgcn_raw_buffer_load_b128(rk, kcol * 8, 0, kAuxCoherent)); KC = __builtin_bit_cast(v4u32, __builtin_amdgcn_raw_buffer_load_b128(rk, kcol * 8 + 16, 0, kAuxCoherent)); }
-                if (!okv) { VA = __builtin_bit_cast(v4u32, __builtin_amdgcn_raw_buffer_load_b128(rv, vcol * 8, 0, kAuxCoherent)); VC = __builtin_bit_cast(v4u32, __builtin_amdgcn_raw_buffer_load_b128(rv, vcol * 8 + 16, 0, kAuxCoherent)); }
-                if (!okq) { okq = tag_is(qq.y, epoch_arg); qbits = qq.x; }
-                if (!okk) okk = tag_is(KA.y, epoch_arg) && tag_is(KA.w, epoch_arg) && tag_is(KC.y, epoch_arg) && tag_is(KC.w, epoch_arg);
-                if (!okv) okv = tag_is(VA.y, epoch_arg) && tag_is(VA.w, epoch_arg) && tag_is(VC.y, epoch_arg) && tag_is(VC.w, epoch_arg);
-                if (__all(okq && okk && okv) || gave_up) break;
-                if (__builtin_amdgcn_s_memrealtime() - t0 > 2000000ull) { __hip_atomic_store(a.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
-            }
+            const Swept w = sweep(kcol, vcol, vcol >= 0);
             stamp(7);
-            qv[0] = tid < hs ? __uint_as_float(qbits) : 0.f;
-            const v4f kp = {__uint_as_float(KA.x), __uint_as_float(KA.z), __uint_as_float(KC.x), __uint_as_float(KC.z)};
-            const v4f vp = {__uint_as_float(VA.x), __uint_as_float(VA.z), __uint_as_float(VC.x), __uint_as_float(VC.z)};
+            qv[0] = tid < hs ? __uint_as_float(w.qbits) : 0.f;
+            const v4f kp = w.kp, vp = w.vp;
 #pragma unroll
             for (int u = 0; u < D; ++u)
 #pragma unroll
@@ -302,39 +306,19 @@ __device__ __forceinline__ void attn_head(const AttnArgs& a, const int h, char* 
         // the split head's part: q element tid, the one 16-byte piece of this token's K row if it lies in one of the part's tiles, and the piece of this token's V row in the part's
         // 32 dimensions (8 threads own them) -- as granules (tag epoch_arg) from the QKV phase of this launch, every thread re-reading ITS pieces until their tags match
         static_assert(!swept_s || FLM_SPLIT_V_LATE, "the V slice is requested behind the sweep");
-        typedef unsigned v4u32 __attribute__((ext_vector_type(4)));
-        const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned long long*>(a.qg) + (size_t)h * hs, 0, hs * 8, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned long long*>(a.kg) + (size_t)h * hs, 0, hs * 8, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned long long*>(a.vg) + (size_t)h * hs, 0, hs * 8, 0x00020000);
         int kcol = -1;
 #pragma unroll
         for (int j = 0; j < NF; ++j)
             if (tlast >= sb && tlast < se && tlast * kAttnTile + prow[j] == T - 1) kcol = (goff[j] >> 2) % hs;
         const bool vown = (((T - 1) & (kSplitMaxSeq / 2 - 1)) >> 2) == (tid >> 3);     // rows 4 (tid / 8) + (j % 4) + 512 (j / 4) of the slice are this thread's
         const int vcol = d0 + (tid & 7) * 4;
-        unsigned qbits = 0; v4u32 KA = {0u, 0u, 0u, 0u}, KC = KA, VA = KA, VC = KA;
-        bool okq = tid >= hs, okk = kcol < 0, okv = !vown;
-        const int gave_up = __hip_atomic_load(a.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-        while (true) {
-            asm volatile("" ::: "memory");
-            uint2 qq = make_uint2(0u, 0u);
-            if (!okq) qq = __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(rq, tid * 8, 0, kAuxCoherent));
-            if (!okk) { KA = __builtin_bit_cast(v4u32, __builtin_amdgcn_raw_buffer_load_b128(rk, kcol * 8, 0, kAuxCoherent)); KC = __builtin_bit_cast(v4u32, __builtin_amdgcn_raw_buffer_load_b128(rk, kcol * 8 + 16, 0, kAuxCoherent)); }
-            if (!okv) { VA = __builtin_bit_cast(v4u32, __builtin_amdgcn_raw_buffer_load_b128(rv, vcol * 8, 0, kAuxCoherent)); VC = __builtin_bit_cast(v4u32, __builtin_amdgcn_raw_buffer_load_b128(rv, vcol * 8 + 16, 0, kAuxCoherent)); }
-            if (!okq) { okq = tag_is(qq.y, epoch_arg); qbits = qq.x; }
-            if (!okk) okk = tag_is(KA.y, epoch_arg) && tag_is(KA.w, epoch_arg) && tag_is(KC.y, epoch_arg) && tag_is(KC.w, epoch_arg);
-            if (!okv) okv = tag_is(VA.y, epoch_arg) && tag_is(VA.w, epoch_arg) && tag_is(VC.y, epoch_arg) && tag_is(VC.w, epoch_arg);
-            if (__all(okq && okk && okv) || gave_up) break;
-            if (__builtin_amdgcn_s_memrealtime() - t0 > 2000000ull) { __hip_atomic_store(a.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
-        }
+        const Swept w = sweep(kcol, vcol, vown);
         // every wave: what it requested before the sweep has landed -- the pre-landed tiles' DMA among it (the QKV phase of the granule form ends without a drain; the first
         // step's barrier follows) -- loads return in order, so this waits for nothing a sweeping wave has not already seen
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         stamp(7);
-        qv[0] = tid < hs ? __uint_as_float(qbits) : 0.f;
-        knew = v4f{__uint_as_float(KA.x), __uint_as_float(KA.z), __uint_as_float(KC.x), __uint_as_float(KC.z)};
-        vnew = v4f{__uint_as_float(VA.x), __uint_as_float(VA.z), __uint_as_float(VC.x), __uint_as_float(VC.z)};
+        qv[0] = tid < hs ? __uint_as_float(w.qbits) : 0.f;
+        knew = w.kp; vnew = w.vp;
         // (this token's K piece goes into its tile IN LDS: into a pre-landed tile now, into a ring tile when it is parked -- whichever tile of the part it is)
         if (kpre != nullptr) {
 #pragma unroll
@@ -486,7 +470,7 @@ __device__ __forceinline__ void attn_head(const AttnArgs& a, const int h, char* 
                 asm volatile("" ::: "memory");
                 if (!ok) { const unsigned long long gv = __hip_atomic_load(sg + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); ok = tag_is((unsigned)(gv >> 32), xepoch); bits = (unsigned)gv; }
                 if (__all(ok) || gave_up) break;
-                if (__builtin_amdgcn_s_memrealtime() - ts > 2000000ull) { __hip_atomic_store(a.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
+                if (give_up_local(ts, a.err)) break;
             }
             if (t < T) {
                 const float sv = mine ? sc[t] : __uint_as_float(bits);
@@ -499,16 +483,8 @@ __device__ __forceinline__ void attn_head(const AttnArgs& a, const int h, char* 
         // exchange: my scores are in memory -> raise my line; wait for the other parts' lines; fetch their scores
         wait_stores_done();
         __syncthreads();
-        if (tid == 0) __hip_atomic_store(a.flag_sc + (h * G + g) * 16, xepoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (tid < 64) {
-            const bool mine = tid < G;
-            const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-            while (true) {
-                const unsigned f = mine ? __hip_atomic_load(a.flag_sc + (h * G + tid) * 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : xepoch;
-                if (__all(flag_reached(f, xepoch))) break;
-                if (__builtin_amdgcn_s_memrealtime() - t0 > 2000000ull) { __hip_atomic_store(a.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
-            }
-        }
+        if (tid == 0) __hip_atomic_store(a.flag_sc + (h * G + g) * kFlagStride, xepoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid < 64) poll_wave(a.flag_sc + (h * G + tid) * kFlagStride, tid < G, xepoch, a.err);
         __syncthreads();
         lmax = -INFINITY;
         for (int t = tid; t < T; t += kAttnBlock) {
@@ -1257,7 +1233,6 @@ __global__ void __launch_bounds__(kAttnBlock) k_attn_decode(const AttnArgs a) {
 // grid_barrier: a shared counter cost 2.7 us from the last head's bump to the last poll's success), then the activation
 // is read with coherent loads.  All workgroups are resident (grid <= CUs, one 1024-thread workgroup per CU); a poll that
 // never succeeds gives up after ~20 ms and raises *err.  The flag lines are zero when the token starts (k_embed).
-constexpr int kFlagStride = 16;      // dwords
 // k_attn_o under tensor parallelism (peer to peer): this rank's head parts are lines [line0, line0 + its parts) of n_lines; a head part raises its line in EVERY
 // rank's array (system-scope store behind a release fence: its slice of att has gone to every rank's buffer before), the Wo workgroups wait for all n_lines
 // lines of the local array and acquire.  The value is the token's epoch base (device memory, advanced by k_embed) + add: the lines are never cleared.
@@ -1293,15 +1268,10 @@ __global__ void __launch_bounds__(kGemvBlock, 4) k_attn_o(const AttnArgs aa, con
     const int n_poll = tp.world ? tp.n_lines : n_heads;
     if ((int)(threadIdx.x & ~63u) < n_poll) {                               // the waves that own at least one head's flag: lane i polls head i's line
         const bool mine = (int)threadIdx.x < n_poll;
-        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-        while (true) {
-            unsigned f = target;
-            if (mine) f = tp.world ? __hip_atomic_load(flag + threadIdx.x * kFlagStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : __hip_atomic_load(flag + threadIdx.x * kFlagStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (__all(flag_reached(f, target))) break;
-            if (__builtin_amdgcn_s_memrealtime() - t0 > (tp.world ? 2000000000ull : 2000000ull)) { __hip_atomic_store(err, tp.world ? 2 : 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }   // (ranks start seconds apart)
-            if (tp.world) __builtin_amdgcn_s_sleep(4);
-        }
-        if (tp.world) __atomic_thread_fence(__ATOMIC_ACQUIRE);
+        if (tp.world) {
+            poll_wave<__HIP_MEMORY_SCOPE_SYSTEM, true, 4>(flag + threadIdx.x * kFlagStride, mine, target, err);   // (ranks start seconds apart)
+            __atomic_thread_fence(__ATOMIC_ACQUIRE);
+        } else poll_wave(flag + threadIdx.x * kFlagStride, mine, target, err);
     }
     __syncthreads();
     stamp(2);
@@ -1347,23 +1317,8 @@ __global__ void __launch_bounds__(kGemvBlock, 4) k_qkv_attn_o(const GemvArgs aq,
     if ((int)blockIdx.x < n_heads) {                                            // n_heads counts head PARTS: heads * G
         const int G = SPLIT ? aa.G : 1, h = blockIdx.x / G;
         if (threadIdx.x < 256) {
-            // lane i: does workgroup i reduce a row of this head's q, k or v?  (pass p = rows [p Rm, (p + 1) Rm) of [Wq; Wk; Wv], workgroup p mod gridq)
-            bool need = false;
-            if ((int)threadIdx.x < gridq) {
-                const unsigned Rm = aq.rows_per_pass, hs = aa.hs, nq = gridq;
-#pragma unroll
-                for (int m = 0; m < 3; ++m) {
-                    const unsigned r0 = (m == 0 ? 0u : m == 1 ? (unsigned)aq.dim : (unsigned)(aq.dim + aq.kv_dim)) + h * hs;
-                    const unsigned pa = r0 / Rm, pb = (r0 + hs - 1) / Rm;
-                    need |= (threadIdx.x + nq - pa % nq) % nq <= pb - pa;
-                }
-            }
-            const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-            while (true) {
-                const unsigned f = need ? __hip_atomic_load(flagq + threadIdx.x * kFlagStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : target;
-                if (__all(f >= target)) break;
-                if (__builtin_amdgcn_s_memrealtime() - t0 > 2000000ull) { __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
-            }
+            const bool need = qkv_line_needed(threadIdx.x, (unsigned)gridq, (unsigned)aq.rows_per_pass, (unsigned)aa.hs, (unsigned)h, (unsigned)aq.dim, (unsigned)aq.kv_dim);
+            poll_wave(flagq + threadIdx.x * kFlagStride, need, target, err);
         }
         __syncthreads();
         attn_head_any<true, SPLIT>(aa, h, lds, *aa.pos_ptr + 1, aa.q, aa.out, blockIdx.x % G, G);
@@ -1384,15 +1339,10 @@ __global__ void __launch_bounds__(kGemvBlock, 4) k_qkv_attn_o(const GemvArgs aq,
     const int n_poll = TP ? tp.n_lines : n_heads;
     if ((int)(threadIdx.x & ~63u) < n_poll) {                               // the waves that own at least one head's flag: lane i polls head i's line
         const bool mine = (int)threadIdx.x < n_poll;
-        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-        while (true) {
-            unsigned f = htarget;
-            if (mine) f = TP ? __hip_atomic_load(flag + threadIdx.x * kFlagStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : __hip_atomic_load(flag + threadIdx.x * kFlagStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (__all(flag_reached(f, htarget))) break;
-            if (__builtin_amdgcn_s_memrealtime() - t0 > (TP ? 2000000000ull : 2000000ull)) { __hip_atomic_store(err, TP ? 2 : 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
-            if constexpr (TP) __builtin_amdgcn_s_sleep(4);
-        }
-        if constexpr (TP) __atomic_thread_fence(__ATOMIC_ACQUIRE);
+        if constexpr (TP) {
+            poll_wave<__HIP_MEMORY_SCOPE_SYSTEM, true, 4>(flag + threadIdx.x * kFlagStride, mine, htarget, err);
+            __atomic_thread_fence(__ATOMIC_ACQUIRE);
+        } else poll_wave(flag + threadIdx.x * kFlagStride, mine, htarget, err);
     }
     __syncthreads();
     float4 xv[XR > 0 ? XR : 1], nv[XR > 0 ? XR : 1];
@@ -1451,15 +1401,10 @@ __global__ void __launch_bounds__(kGemvBlock, 4) k_ffn(const GemvArgs a13, const
     g2.issue(kAblate ? a2.ablate : 0, 1);                                       // ONE set now (64 KiB per CU: taken by the memory pipeline before the flags come in); hd
     if (threadIdx.x < 256) {                                                    // requested behind two sets would wait for 128 KiB per CU to drain (measured: no gain at all)
         const bool mine = (int)threadIdx.x < (TP ? tp.world : (int)gridDim.x);
-        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-        while (true) {
-            unsigned f = target;
-            if (mine) f = TP ? __hip_atomic_load(flag + threadIdx.x * kFlagStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : __hip_atomic_load(flag + threadIdx.x * kFlagStride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (__all(flag_reached(f, target))) break;
-            if (__builtin_amdgcn_s_memrealtime() - t0 > (TP ? 2000000000ull : 2000000ull)) { __hip_atomic_store(err, TP ? 2 : 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
-            if constexpr (TP) __builtin_amdgcn_s_sleep(4);
-        }
-        if constexpr (TP) __atomic_thread_fence(__ATOMIC_ACQUIRE);
+        if constexpr (TP) {
+            poll_wave<__HIP_MEMORY_SCOPE_SYSTEM, true, 4>(flag + threadIdx.x * kFlagStride, mine, target, err);
+            __atomic_thread_fence(__ATOMIC_ACQUIRE);
+        } else poll_wave(flag + threadIdx.x * kFlagStride, mine, target, err);
     }
     __syncthreads();
     float4 xv2[XR2 > 0 ? XR2 : 1], nv2[XR2 > 0 ? XR2 : 1];

@@ -2,6 +2,7 @@
 // Part of flm_kernels.h (hand-written gfx950 / CDNA4 kernels of the fast-llama per-token hot path); include that header.
 #pragma once
 #include "flm_math.h"
+#include "flm_wait.h"
 // (bit-exactness hygiene: see flm_math.h -- no implicit FMA contraction in any of these headers)
 #pragma clang fp contract(off)
 
@@ -993,7 +994,7 @@ struct GemvCtx {
         const u32 e0 = kc * EPB, e1 = e0 + EPB < n ? e0 + EPB : n;
         const u32 p0 = udiv(e0, src.rows, inv_rows), p1 = udiv(e1 - 1, src.rows, inv_rows), pj = p0 + (lane & 15);
         const bool mine = ks < NS && pj <= p1;
-        const unsigned* line = src.flags + (pj % src.grid) * 16 /* kFlagStride */;
+        const unsigned* line = src.flags + (pj % src.grid) * kFlagStride;
         u32 pending = 0;
 #pragma unroll
         for (u32 k = 0; k < 4; ++k) if (wave < nw && wave + nw * k < NS) pending |= 1u << k;
@@ -1010,8 +1011,7 @@ struct GemvCtx {
             if (!now) {
                 // 20 ms: the host re-runs the call on one kernel per phase.  (And when ANOTHER wait of the launch has already given up, do not spend this one's 20 ms as well:
                 // a look at *err every 64 empty looks.)
-                const bool late = __builtin_amdgcn_s_memrealtime() - t0 > 2000000ull;
-                if (late) __hip_atomic_store(src.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                const bool late = give_up_local(t0, src.err);
                 if (late || ((++spins & 63u) == 0u && __hip_atomic_load(src.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0)) now = pending;
             }
             AoBlock b[4];
@@ -1048,28 +1048,16 @@ struct GemvCtx {
 // its system-scope stores into every peer's buffer are done), so workgroup 0 tells every peer "my slice of exchange e is in your memory" (release fence,
 // one flag line per (slot, rank)); every workgroup then waits until all ranks' lines in the LOCAL buffer have reached e and acquires.  e comes from the
 // token's epoch base in device memory (the same on every rank: all ranks run the same tokens), so a captured graph replays correctly.
-constexpr int kXchgSlots = 8;                  // flag slots: 0..3 k_xchg's kinds (att, x1, hd, logits), 4..6 the folded exchanges (att, x1, hd)
-constexpr int kXchgAbortLine = kXchgSlots * 8; // flag line behind the [slot][8 ranks] lines: non-zero = some rank gave up, nobody waits any more
+// (flag slots and the abort line: kXchgSlots, kXchgAbortLine in flm_wait.h; 20 s of patience: ranks start seconds apart)
 __device__ __forceinline__ void xchg_fold(const GemvArgs::XchgFold& x) {
     const unsigned e = *x.base + x.add;
     const int r = threadIdx.x;
     if (threadIdx.x < 64) {
         if (blockIdx.x == 0) {
             __atomic_thread_fence(__ATOMIC_RELEASE);
-            if (r < x.world) __hip_atomic_store(x.peer_flags[r] + (x.slot * 8 + x.rank) * 16, e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            if (r < x.world) __hip_atomic_store(x.peer_flags[r] + (x.slot * 8 + x.rank) * kFlagStride, e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
-        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-        while (true) {
-            const unsigned f = r < x.world ? __hip_atomic_load(x.local_flags + (x.slot * 8 + r) * 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : e;
-            if (__all(flag_reached(f, e))) break;
-            const bool aborted = __hip_atomic_load(x.local_flags + kXchgAbortLine * 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0;
-            if (aborted || __builtin_amdgcn_s_memrealtime() - t0 > 2000000000ull) {                               // 20 s: ranks start seconds apart
-                __hip_atomic_store(x.err, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                if (r < x.world) __hip_atomic_store(x.peer_flags[r] + kXchgAbortLine * 16, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                break;
-            }
-            __builtin_amdgcn_s_sleep(4);
-        }
+        poll_wave<__HIP_MEMORY_SCOPE_SYSTEM, true, 4>(x.local_flags + (x.slot * 8 + r) * kFlagStride, r < x.world, e, x.err, XchgAbortLine<GemvArgs::XchgFold>{x, r});
         __atomic_thread_fence(__ATOMIC_ACQUIRE);
     }
     __syncthreads();

@@ -180,6 +180,7 @@ int xwg_check(flm_ctx* c) {
 // Census: the fused launches (k_attn_o, k_ffn, k_qkv_attn_o, k_attn_ffn, split heads) wait for each other's flags, so every workgroup of a
 // cu_count-wide launch of 1024-thread workgroups with most of the CU's LDS must be RESIDENT at once.  The occupancy API cannot see a masked or
 // partitioned device (MI355X_MICROARCH.md: verify with a census kernel): every workgroup checks in and waits (bounded) until all have.
+constexpr unsigned long long kCensusTicks = 200000ull;       // 2 ms of the 100 MHz clock: a resident workgroup checks in within microseconds
 __global__ void __launch_bounds__(1024) k_census(unsigned* counter, unsigned n, int* ok) {
     extern __shared__ char census_lds[];
     if (threadIdx.x == 0) {
@@ -187,7 +188,7 @@ __global__ void __launch_bounds__(1024) k_census(unsigned* counter, unsigned n, 
         __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
         bool all = false;
-        while (!all && __builtin_amdgcn_s_memrealtime() - t0 < 200000ull) {                       // 2 ms of the 100 MHz clock
+        while (!all && __builtin_amdgcn_s_memrealtime() - t0 < kCensusTicks) {
             all = __hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= n;
             if (!all) __builtin_amdgcn_s_sleep(8);
         }

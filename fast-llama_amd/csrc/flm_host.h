@@ -8,6 +8,7 @@
 //   flm_layerlaunch.hip  the whole-layer launch k_attn_ffn (flm_layer.h)
 //   flm_prompt.hip       the batched prompt path (GEMM tiles on the matrix cores, prompt attention)
 //   flm_ops.hip          the op-level exports of the parity tests (flm_op_*)
+//   flm_wait.h           (device side, part of flm_kernels.h) every cross-workgroup / cross-rank wait of the fused launches: flag polls, granule pieces, when a wait gives up
 //   flm_tuning.h         the option table: one row per flm_set_option / flm_query key (flm_gpu.hip walks it)
 #pragma once
 #include "flm_gpu.h"

@@ -75,97 +75,13 @@ struct BackArgs {
     } tp;
 };
 
-// One wave's look at its lines until all have reached `target`.  A look is a round trip to memory (the lines are written and read across XCDs); with one look in flight a
-// raised line is noticed half a round trip late on average.  FLM_POLL_DEPTH > 1 keeps that many looks in flight, FLM_POLL_GAP apart -- measured (tools/variants.sh): depth 3
-// takes 0.2 .. 0.3 us off a short-context layer and ADDS 1.6 us to a long-context one (the split heads' loads queue behind three times the polling traffic): depth 1 stays.
-#ifndef FLM_POLL_DEPTH
-#define FLM_POLL_DEPTH 1
-#endif
-#ifndef FLM_POLL_GAP
-#define FLM_POLL_GAP 6            // s_sleep units (64 cycles) between two looks
-#endif
-__device__ __forceinline__ void poll_wave(const unsigned* line, bool mine, unsigned target, int* err) {
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    auto look = [&]() -> unsigned { return mine ? __hip_atomic_load(line, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : target; };
-#if FLM_POLL_DEPTH <= 1
-    // (a wait of this launch has already given up: the host re-runs the call anyway; do not spend another 20 ms here -- the look at *err flies beside the first look at the lines)
-    const int gave_up = __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    unsigned f = look();
-    if (gave_up) return;
-    while (true) {
-        if (__all(flag_reached(f, target))) break;
-        f = look();
-        if (__builtin_amdgcn_s_memrealtime() - t0 > 2000000ull) { __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
-    }
-#else
-    unsigned f[FLM_POLL_DEPTH];
-#pragma unroll
-    for (int i = 0; i < FLM_POLL_DEPTH; ++i) { f[i] = look(); if (i + 1 < FLM_POLL_DEPTH) __builtin_amdgcn_s_sleep(FLM_POLL_GAP); }
-    while (true) {
-        bool done = false;
-#pragma unroll
-        for (int i = 0; i < FLM_POLL_DEPTH; ++i) {
-            if (__all(flag_reached(f[i], target))) { done = true; break; }
-            f[i] = look();
-            __builtin_amdgcn_s_sleep(FLM_POLL_GAP);
-        }
-        if (done) break;
-        if (__builtin_amdgcn_s_memrealtime() - t0 > 2000000ull) { __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
-    }
-#endif
-}
-// lane i (of the first 256 threads) polls line i of `n` lines until all have reached `target`
-__device__ __forceinline__ void poll_lines(const unsigned* flag, int n, unsigned target, int* err) {
-    if ((int)(threadIdx.x & ~63u) < n) poll_wave(flag + threadIdx.x * kFlagStride, (int)threadIdx.x < n, target, err);
-}
-// ---- the same across tensor-parallel ranks (layer_body<.., TP>): the lines are written by peer GPUs (system-scope stores into this rank's region), so the looks are
-// system-scope loads; ranks start seconds apart (module loading, graph capture), so a wait is patient (20 s) -- but once ANY rank has given up (the abort line) everybody leaves.
-// *err = 2: a group error (FLM_ERR_COMM; nothing is re-run on one rank alone).
-__device__ __forceinline__ void poll_wave_tp(const unsigned* line, bool mine, unsigned target, const BackArgs& p) {
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    unsigned spins = 0;
-    while (true) {
-        const unsigned f = mine ? __hip_atomic_load(line, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : target;
-        if (__all(flag_reached(f, target))) break;
-        if ((++spins & 255u) == 0u) {
-            const bool aborted = __hip_atomic_load(p.tp.peer[p.tp.rank] + p.tp.abort_off, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0 || __hip_atomic_load(p.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-            if (aborted || __builtin_amdgcn_s_memrealtime() - t0 > 2000000000ull) {
-                __hip_atomic_store(p.err, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                for (int r = 0; r < p.tp.world; ++r) __hip_atomic_store(p.tp.peer[r] + p.tp.abort_off, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                break;
-            }
-        }
-    }
-}
-// every thread takes the lines tid, tid + 1024, ... of `n` (<= 8 ranks x 256 workgroups); the caller's barrier follows
-template <bool TP>
-__device__ __forceinline__ void poll_lines_t(const unsigned* flag, int n, unsigned target, const BackArgs& p) {
-    if constexpr (!TP) poll_lines(flag, n, target, p.err);
-    else {
-        for (int b = 0; b < n; b += kGemvBlock) {
-            const int i = b + (int)threadIdx.x;
-            if ((i & ~63) < n) poll_wave_tp(flag + (size_t)i * kFlagStride, i < n, target, p);
-        }
-        if (p.tp.fence & 2) __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    }
-}
-// a producer workgroup's line goes up (its stores have completed: wait_stores_done + barrier in front): one local store, or one store into every rank's array
-template <bool TP>
-__device__ __forceinline__ void raise_line(const BackArgs& p, unsigned* local, unsigned off, unsigned line, unsigned target) {
-    if constexpr (!TP) { if (threadIdx.x == 0) __hip_atomic_store(local + line * kFlagStride, target, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    else if (threadIdx.x == 0) {
-        if (p.tp.fence & 1) __atomic_thread_fence(__ATOMIC_RELEASE);
-        for (int r = 0; r < p.tp.world; ++r) __hip_atomic_store(p.tp.peer[r] + off + line * kFlagStride, target, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-}
+// (the flag rounds -- poll_wave, poll_lines, poll_lines_t, raise_line -- and the give-up policy of every wait: flm_wait.h)
 
 // gemv_preload on a granule vector (flm_gemv.h: granule_t): xv[i] = elements 4 tid + 4096 i .. + 3 once their tags are `tag` (every thread re-reads ITS granules until they
 // match; only the lanes whose granules are missing read again); wv[i] = the norm weights (PRO_RMSNORM_QUANT).  XR rounds cover the vector (the host checks).  A wait of ~20 ms
 // raises *err (the host re-runs the call on one kernel per phase); TP: patient (20 s: ranks start seconds apart), leaves when any rank has given up (the abort line), *err = 2.
 template <int PRO, int XR, bool TP>
 __device__ __forceinline__ void gemv_preload_granules(const GemvArgs& a, float4 (&xv)[XR], float4 (&wv)[XR], const granule_t* g, const unsigned tag, const BackArgs& p) {
-    typedef float v4f __attribute__((ext_vector_type(4)));
-    typedef unsigned v4u32 __attribute__((ext_vector_type(4)));
     const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc(const_cast<granule_t*>(g), 0, a.n * 8, 0x00020000);
     const int gave_up = __hip_atomic_load(p.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if constexpr (PRO == PRO_RMSNORM_QUANT) {
@@ -185,29 +101,17 @@ __device__ __forceinline__ void gemv_preload_granules(const GemvArgs& a, float4 
         asm volatile("" ::: "memory");                                         // (the loads are re-issued every pass)
 #pragma unroll
         for (int i = 0; i < XR; ++i) {
-            if (!ok[i]) {
-                const int off = (int)((threadIdx.x * 4 + i * kGemvBlock * 4) * 8);
-                A[i] = __builtin_bit_cast(v4u32, __builtin_amdgcn_raw_buffer_load_b128(rg, off, 0, kAuxCoherent));
-                C[i] = __builtin_bit_cast(v4u32, __builtin_amdgcn_raw_buffer_load_b128(rg, off + 16, 0, kAuxCoherent));
-            }
+            if (!ok[i]) granules4_load(rg, (int)((threadIdx.x * 4 + i * kGemvBlock * 4) * 8), A[i], C[i]);
         }
         bool all = true;
 #pragma unroll
-        for (int i = 0; i < XR; ++i) { if (!ok[i]) ok[i] = tag_is(A[i].y, tag) && tag_is(A[i].w, tag) && tag_is(C[i].y, tag) && tag_is(C[i].w, tag); all = all && ok[i]; }
+        for (int i = 0; i < XR; ++i) { if (!ok[i]) ok[i] = granules4_tagged(A[i], C[i], tag); all = all && ok[i]; }
         if (__all(all) || gave_up) break;
-        if constexpr (!TP) {
-            if (__builtin_amdgcn_s_memrealtime() - t0 > 2000000ull) { __hip_atomic_store(p.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); break; }
-        } else if ((++spins & 255u) == 0u) {
-            const bool aborted = __hip_atomic_load(p.tp.peer[p.tp.rank] + p.tp.abort_off, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0 || __hip_atomic_load(p.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-            if (aborted || __builtin_amdgcn_s_memrealtime() - t0 > 2000000000ull) {
-                __hip_atomic_store(p.err, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                for (int r = 0; r < p.tp.world; ++r) __hip_atomic_store(p.tp.peer[r] + p.tp.abort_off, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                break;
-            }
-        }
+        if constexpr (!TP) { if (give_up_local(t0, p.err)) break; }
+        else if ((++spins & (TpAbortLine<BackArgs>::kEvery - 1)) == 0u) { if (give_up_ranks(t0, p.err, TpAbortLine<BackArgs>{p})) break; }
     }
 #pragma unroll
-    for (int i = 0; i < XR; ++i) xv[i] = make_float4(__uint_as_float(A[i].x), __uint_as_float(A[i].z), __uint_as_float(C[i].x), __uint_as_float(C[i].z));
+    for (int i = 0; i < XR; ++i) { const v4f v = granules4_values(A[i], C[i]); xv[i] = make_float4(v.x, v.y, v.z, v.w); }
 }
 
 #ifndef FLM_BACK_LATE
@@ -295,17 +199,7 @@ __device__ __forceinline__ void layer_body(const GemvArgs& aq, const AttnArgs& a
         // the lines of the workgroups that reduced this head's rows of q, k and v: polled INSIDE the head (attn_head<.., PRE>), behind its requests for the earlier tokens' cache rows
         auto qwait = [&]() {
             if (threadIdx.x < 256) {
-                // lane i: does workgroup i reduce a row of this head's q, k or v?  (pass p = rows [p Rm, (p + 1) Rm) of [Wq; Wk; Wv], workgroup p mod gridq)
-                bool need = false;
-                if ((int)threadIdx.x < p.gridq) {
-                    const unsigned Rm = aq.rows_per_pass, hs = aa.hs, nq = p.gridq, h = hh;
-#pragma unroll
-                    for (int m = 0; m < 3; ++m) {
-                        const unsigned r0 = (m == 0 ? 0u : m == 1 ? (unsigned)aq.dim : (unsigned)(aq.dim + aq.kv_dim)) + h * hs;
-                        const unsigned pa = r0 / Rm, pb = (r0 + hs - 1) / Rm;
-                        need |= (threadIdx.x + nq - pa % nq) % nq <= pb - pa;
-                    }
-                }
+                const bool need = qkv_line_needed(threadIdx.x, (unsigned)p.gridq, (unsigned)aq.rows_per_pass, (unsigned)aa.hs, (unsigned)hh, (unsigned)aq.dim, (unsigned)aq.kv_dim);
                 poll_wave(p.flag_q + threadIdx.x * kFlagStride, need, target, p.err);
             }
             __syncthreads();
@@ -485,7 +379,7 @@ struct LayerArgs { GemvArgs aq, ao, a13, a2; AttnArgs aa; };
 // front of that round), and the greedy argmax (first maximum wins, sampler.cpp:36-47) + the decode state's advance close it: every classifier workgroup leaves the best of its own rows
 // in a slot and raises a line, workgroup 0 waits for all of them and picks.  Nobody clears the flag lines between tokens (k_embed did): every target of the launch counts from an epoch
 // base in device memory that the launch's last act moves on by L + 2 (back to kEpochFirst at kEpochWrap) -- stale lines are always outside the window above the target
-// (flm_math.h flag_reached).  fp32 embedding tables only (the host checks).
+// (flm_wait.h flag_reached).  fp32 embedding tables only (the host checks).
 struct TailArgs {
     GemvArgs acls;              // the classifier GEMV (EPI_STORE into the logits)
     const float* emb; const int* tok_ptr; int dim, vocab;
@@ -548,7 +442,7 @@ __device__ __forceinline__ void tail_phase(const TailArgs& T, const BackArgs& p,
             const bool halt = gen_last_act(st, st->step, idx, p.err);         // (the token's last act: flm_math.h)
             if (!halt) { st->tok = idx; st->pos += 1; }
             st->step += 1;
-            *T.epoch = (FLM_WAIT_FORM == 0 && next_epoch >= kEpochWrap) ? kEpochFirst : next_epoch;     // (flm_math.h flag_reached: the epochs stay inside [kEpochFirst, kEpochWrap + L + 2))
+            *T.epoch = (FLM_WAIT_FORM == 0 && next_epoch >= kEpochWrap) ? kEpochFirst : next_epoch;     // (flm_wait.h flag_reached: the epochs stay inside [kEpochFirst, kEpochWrap + L + 2))
         }
     }
 }

@@ -75,10 +75,9 @@ __device__ __forceinline__ bool halted(const int* halt) {
 }
 // A token's last act, by the ONE thread that has just written out_tokens[step]: publish the token's granule (flm_generate calls only), set the latch; returns it -- a halting
 // token does not move tok / pos on: the stop token is not fed.  err: the cross-workgroup waits' error word; once a wait of the call has given up its tokens are not published
-// (the host re-runs the call and delivers them from the sound attempt).  Why a token computed on garbage cannot be published: garbage exists only behind a wait that gave up,
-// the wave that gives up stores the error word (poll_wave) BEFORE it leaves the wait and produces anything from what it failed to wait for, and whatever it produces reaches this
-// thread only through the later hand-offs of the token (flag rounds / granules / a kernel boundary), each of them an agent-scope store -> load chain behind that error store:
-// when the garbage can have influenced `tok`, the relaxed agent-scope load below already sees the word set.  A token published before any wait gave up was computed soundly
+// (the host re-runs the call and delivers them from the sound attempt).  A token computed on garbage cannot be published: the wave that gives up a wait stores the error word
+// BEFORE it leaves the wait (flm_wait.h: the give-up policy and why that suffices), so when garbage can have influenced `tok`, the relaxed agent-scope load below already sees
+// the word set.  A token published before any wait gave up was computed soundly
 __device__ __forceinline__ bool gen_last_act(DecodeState* st, const int step, const int tok, const int* err) {
     bool halt = tok == st->stop_tok;
     const unsigned tag = st->gen_tag;
@@ -91,40 +90,6 @@ __device__ __forceinline__ bool gen_last_act(DecodeState* st, const int step, co
     }
     st->halt = halt ? 1 : 0;
     return halt;
-}
-
-// ------------------------------------------------------------------------------------------
-// Every cross-workgroup / cross-rank wait compares a flag line's value f with a target that counts from an epoch in device memory (TailArgs::epoch, the token's epoch base
-// advanced by k_embed, k_xchg's per-kind counters) or, in the k_embed-era launches, with layer + 1 against lines k_embed cleared.  A line has reached its target when
-// f - target (mod 2^32) lies in [0, kEpochWindow): values a producer of the SAME launch may already have moved on to lie a few hundred above the target at most, and everything
-// stale -- the previous token's value (just below), a line k_embed cleared (0) or a k_embed-era launch left at layer + 1, a value from the counter's previous lap -- lies
-// outside the window as long as the epochs stay inside [kEpochFirst, kEpochWrap + a token's stride): targets keep kEpochWindow away from both ends of the 32-bit range, and
-// the counters go back to their first value at kEpochWrap (tail_phase, k_embed).  The signed form this replaces, (int)(f - target) >= 0, let a cleared line pass every target
-// above 2^31 (tests/test_gpu_longlived.py ages a context there).  Granule tags compare by equality: a tag repeats after a whole lap of its counter, and every granule is
-// rewritten every token.
-// FLM_WAIT_FORM (experiment builds: the teeth of tests/test_gpu_longlived.py): 1 = the signed difference again, 2 = plain f >= target and tag >= target.
-// ------------------------------------------------------------------------------------------
-#ifndef FLM_WAIT_FORM
-#define FLM_WAIT_FORM 0
-#endif
-constexpr unsigned kEpochWindow = 1u << 20;
-constexpr unsigned kEpochFirst = 4096u;          // the one-launch token's first epoch: above anything a k_embed-era launch leaves in a line (layer + 1)
-constexpr unsigned kEpochWrap = 0xFFE00000u;     // a counter that reaches this goes back to its first value: no target comes within kEpochWindow of 2^32
-__device__ __forceinline__ bool flag_reached(const unsigned f, const unsigned target) {
-#if FLM_WAIT_FORM == 1
-    return (int)(f - target) >= 0;
-#elif FLM_WAIT_FORM == 2
-    return f >= target;
-#else
-    return f - target < kEpochWindow;
-#endif
-}
-__device__ __forceinline__ bool tag_is(const unsigned t, const unsigned tag) {
-#if FLM_WAIT_FORM == 2
-    return t >= tag;
-#else
-    return t == tag;
-#endif
 }
 
 enum { QT_INT16 = 1, QT_INT8 = 2 };

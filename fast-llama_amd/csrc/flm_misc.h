@@ -18,7 +18,7 @@ inline __global__ void k_embed(float* x, const void* emb, const float* emb_s, in
     if (halted(halt)) return;                                    // (flm_math.h DecodeState::halt: in front of the epoch base, the counter and the lines)
     const int tok = *tok_ptr;
     // a new token: the epoch base of the tensor-parallel exchanges' flag values moves on; back to 0 at kEpochWrap, so that no target comes within kEpochWindow of 2^32
-    // (flm_math.h flag_reached: the local lines cleared below must stay outside every target's window; the never-cleared cross-rank lines then hold values of the previous
+    // (flm_wait.h flag_reached: the local lines cleared below must stay outside every target's window; the never-cleared cross-rank lines then hold values of the previous
     //  lap, far above the new targets' windows)
     if (eng_base && blockIdx.x == 0 && threadIdx.x == 0) { const unsigned b = *eng_base; *eng_base = b >= (FLM_WAIT_FORM == 0 ? kEpochWrap : 0xFFF00000u) ? 0u : b + kEpochStride; }
     // k_ffn<TP> finds a rank's last workgroup with (count + 1) % grid: a new token starts the count at 0, whatever grid earlier launches had (or a launch that gave up left behind)
@@ -98,20 +98,9 @@ inline __global__ void __launch_bounds__(64) k_xchg(const XchgArgs x) {
     // release: the slices this rank's producing kernel stored into the peers' buffers (system-scope stores, completed by the kernel boundary in front of
     // this launch) are ordered before the flag for ANY observer -- on one device that cannot fail, across xGMI links it is what the flag promises
     __atomic_thread_fence(__ATOMIC_RELEASE);
-    if (r < x.world) __hip_atomic_store(x.peer_flags[r] + (x.kind * 8 + x.rank) * 16, e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    while (true) {
-        const unsigned f = r < x.world ? __hip_atomic_load(x.local_flags + (x.kind * 8 + r) * 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : e;
-        if (__all(flag_reached(f, e))) break;
-        // ranks start seconds apart (graph capture, module loading): be patient; but once ANY rank has given up, everybody leaves at once
-        const bool aborted = __hip_atomic_load(x.local_flags + kXchgAbortLine * 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0;
-        if (aborted || __builtin_amdgcn_s_memrealtime() - t0 > 2000000000ull) {                                   // 20 s of the 100 MHz clock
-            __hip_atomic_store(x.err, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            if (r < x.world) __hip_atomic_store(x.peer_flags[r] + kXchgAbortLine * 16, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            break;
-        }
-        __builtin_amdgcn_s_sleep(8);
-    }
+    if (r < x.world) __hip_atomic_store(x.peer_flags[r] + (x.kind * 8 + x.rank) * kFlagStride, e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    // ranks start seconds apart (graph capture, module loading): be patient; but once ANY rank has given up, everybody leaves at once
+    poll_wave<__HIP_MEMORY_SCOPE_SYSTEM, true, 8>(x.local_flags + (x.kind * 8 + r) * kFlagStride, r < x.world, e, x.err, XchgAbortLine<XchgArgs>{x, r});
     // acquire: nothing this rank reads after the wait (the consumers' system-coherent loads in the next launch) is served from before the peers' flags
     __atomic_thread_fence(__ATOMIC_ACQUIRE);
     if (r == 0) *x.epoch = e;

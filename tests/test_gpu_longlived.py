@@ -7,7 +7,7 @@ a real run would have left with its counters at a given value -- shown faithful 
 48-token greedy decode (inside a 16-token graph replay), then through a single-token forward (k_embed clears the local lines to 0), more greedy tokens, a batched prompt chunk
 and sampled tokens, an injected wait failure with its 64-token probation and the return to the one-launch token -- ids, sampler state and logits against the CPU oracle, bit for
 bit, and "fallback" counting exactly the injected episode.  Edges: 2^31 (where a signed difference changes sign against a cleared line) and kEpochWrap = 0xFFE0_0000, where
-the one-launch token's epoch goes back to 4096 and the token's epoch base to 0 (flm_math.h flag_reached); k_xchg's counters run through 2^32.
+the one-launch token's epoch goes back to 4096 and the token's epoch base to 0 (flm_wait.h flag_reached); k_xchg's counters run through 2^32.
 
 Part B -- call-order fuzz: the seeded scripts of tests/callscript.py (rewinds, decode directly after flm_reset_kv, prompt chunks behind decoded tokens, graph-chunk edges behind
 one another, structure switches between calls, injected wait failures, flm_kernel_times and the documented recovery) on one context against one oracle."""

@@ -2,6 +2,7 @@
 ids; the kernels are built to be BIT-IDENTICAL to the reference CPU path, so these tests assert exact
 equality of every logit against the CPU oracle (itself bit-exact with the reference,
 tests/test_oracle_vs_reference.py) and against the committed golden logits produced by the reference."""
+import functools
 import os
 
 import numpy as np
@@ -484,6 +485,42 @@ def test_a_wait_that_gives_up_is_retried_on_one_kernel_per_phase(gpu):
     assert ctx.forward_argmax(prompt, 0) == first
     assert list(ctx.decode_greedy(first, len(prompt), 10)) == want_ids
     assert bits_equal(ctx.debug_read("logits", 0, cfg.vocab_size), last)
+    ctx.close()
+
+
+@functools.lru_cache(maxsize=None)
+def _gave_up_reference(n_prompt):
+    """the model of the test above and the oracle's first id, 8 greedy ids and the logits behind the 4th, computed once per prompt length"""
+    cfg = synth.make_config("7B", ff.QT_INT8); cfg.n_layers = 2
+    tensors = synth.make_tensors(cfg, seed=59)
+    om = O.OracleModel(cfg, tensors)
+    prompt = _prompt(cfg.vocab_size, n_prompt)
+    first = int(np.argmax(om.forward(prompt, 0)))
+    want_ids, cur, pos, logits4 = [], first, len(prompt), None
+    for i in range(8):
+        lg = om.forward(np.array([cur], np.int32), pos); cur = int(np.argmax(lg)); want_ids.append(cur); pos += 1
+        if i == 3: logits4 = lg
+    return cfg, tensors, prompt, first, want_ids, logits4
+
+
+@pytest.mark.parametrize("n_prompt,opts", [(5, {}), (5, {"fuse_token": 0}), (5, {"fuse_layer": 0}), (5, {"fuse_back": 0}), (5, {"fuse_qkv": 2}), (5, {"tuning": 1, "gr_edges": 0}),
+                                           (130, {})],      # (130: split heads, the smallest position this file runs them at)
+                         ids=lambda v: str(v) if isinstance(v, int) else ("-".join(f"{k}{x}" for k, x in v.items()) or "default"))
+def test_a_wait_that_gives_up_runs_through_every_launch_form(gpu, n_prompt, opts):
+    """once a wait of a launch has given up, every later wait of the launch looks at the error word and runs through (flm_wait.h) -- in every launch form: the one-launch token on
+    granules and on flag rounds, one launch per layer, the layer's back half, attention + Wo and FFN13 + FFN2 with and without QKV in front, split heads.  The flag is raised by
+    hand in front of the decode; ids and the last logits are the oracle's bit for bit, the episode is counted, and the fallen-back context goes on with the oracle's ids."""
+    cfg, tensors, prompt, first, want_ids, logits4 = _gave_up_reference(n_prompt)
+    ctx = gpu.Ctx(gpu.desc_from_config(cfg)); ctx.upload_all(tensors)
+    for k, v in opts.items():
+        ctx.set_option(k, v)
+    if n_prompt >= 128: assert ctx.query("token_path") & 64                    # (heads split over workgroups from 128 positions on)
+    assert ctx.forward_argmax(prompt, 0) == first
+    ctx.set_option("inject_wait_failure", 1)
+    assert list(ctx.decode_greedy(first, len(prompt), 4)) == want_ids[:4]
+    assert bits_equal(ctx.debug_read("logits", 0, cfg.vocab_size), logits4)
+    assert ctx.query("fallback") == 1
+    assert list(ctx.decode_greedy(want_ids[3], len(prompt) + 4, 4)) == want_ids[4:]
     ctx.close()
 
 
