@@ -32,6 +32,7 @@ SYMBOLS = (
     "flm_verify_sample_ex", "flm_generate_lookup_ex", "flm_op_shape_rows",
     "flm_dfa_validate", "flm_constraint_set", "flm_constraint_arm", "flm_op_constrain_rows",
     "flm_logprobs_arm", "flm_last_logprobs", "flm_op_logprob_rows", "flm_logprob_stage_time",
+    "flm_stop_validate", "flm_stop_match", "flm_stop_set", "flm_op_stop_match",
 )
 
 # flm_score (include/flm_gpu.h): one row of flm_score_tokens / flm_op_score_rows
@@ -194,6 +195,66 @@ class Dfa:
                 if v is not None:
                     triples.append((u, tid, v))
         return cls.from_edges(final + 1, triples)
+
+
+STOP_IDS_MAX, STOP_SEQS_MAX, STOP_SEQ_LEN_MAX = 64, 16, 32      # FLM_STOP_IDS_MAX, FLM_STOP_SEQS_MAX, FLM_STOP_SEQ_LEN_MAX
+STOP_LENGTH, STOP_TOKEN, STOP_ID, STOP_SEQ, STOP_CANCEL = 0, 1, 2, 3, 4      # FLM_STOP_LENGTH .. FLM_STOP_CANCEL
+STOP_REASONS = ("length", "stop_token", "stop_id", "stop_seq", "cancel")
+
+
+class StopRulesStruct(C.Structure):
+    """flm_stop_rules (include/flm_gpu.h)"""
+    _fields_ = [("n_ids", C.c_int32), ("ids", C.c_void_p), ("n_seqs", C.c_int32), ("seq_ptr", C.c_void_p), ("seq_tokens", C.c_void_p)]
+
+
+class StopRules:
+    """A set of stop ids and stop sequences (flm_stop_rules): ids = the ids that end a call, seqs = sequences of ids that end it at their last id.  Holds the arrays as
+    given -- validation is flm_stop_validate's (validate below).  raw=(ids, seq_ptr, seq_tokens) takes the three arrays as they are (the tests build broken ones)."""
+
+    def __init__(self, ids=(), seqs=(), raw=None):
+        if raw is not None:
+            self.ids, self.seq_ptr, self.seq_tokens = (np.ascontiguousarray(a, dtype=np.int32) for a in raw)
+            return
+        seqs = [[int(t) for t in s] for s in seqs]
+        self.ids = np.ascontiguousarray(list(ids), dtype=np.int32)
+        self.seq_ptr = np.ascontiguousarray(np.concatenate(([0], np.cumsum([len(s) for s in seqs]))), dtype=np.int32)
+        self.seq_tokens = np.ascontiguousarray([t for s in seqs for t in s], dtype=np.int32)
+
+    @property
+    def n_seqs(self):
+        return max(int(self.seq_ptr.size) - 1, 0)
+
+    @property
+    def seqs(self):
+        return [[int(t) for t in self.seq_tokens[self.seq_ptr[s]:self.seq_ptr[s + 1]]] for s in range(self.n_seqs)]
+
+    def struct(self, n_ids=None, n_seqs=None):
+        """-> flm_stop_rules pointing into this object's arrays (keep the object alive for the call); n_ids / n_seqs override the counts"""
+        return StopRulesStruct(int(self.ids.size) if n_ids is None else int(n_ids), _p(self.ids), self.n_seqs if n_seqs is None else int(n_seqs),
+                               _p(self.seq_ptr), _p(self.seq_tokens))
+
+    def validate(self, vocab):
+        """flm_stop_validate: raises FlmError naming the rule that is broken"""
+        st = self.struct()
+        _check(lib().flm_stop_validate(C.byref(st), int(vocab)))
+
+
+def stop_match_host(rules, ids, stop_token=-1):
+    """flm_stop_match, the host restatement of the stop rules (host/stop_rules.h; no GPU): -> (the first index of ids that fires or len(ids), kind, rule); rules may be None"""
+    t = np.ascontiguousarray(ids, dtype=np.int32)
+    st = rules.struct() if rules is not None else None
+    kind, rule = C.c_int(-1), C.c_int(-1)
+    first = lib().flm_stop_match(C.byref(st) if st is not None else None, C.c_int32(int(stop_token)), _p(t), int(t.size), C.byref(kind), C.byref(rule))
+    return int(first), int(kind.value), int(rule.value)
+
+
+def op_stop_match(rules, ids, stop_token=-1):
+    """flm_op_stop_match: the device's matcher (csrc/flm_stop.h, what the shaped token form runs) on ids -> (first, kind, rule) as stop_match_host"""
+    t = np.ascontiguousarray(ids, dtype=np.int32)
+    st = rules.struct()
+    first, kind, rule = C.c_int(-1), C.c_int(-1), C.c_int(-1)
+    _check(lib().flm_op_stop_match(C.byref(st), C.c_int32(int(stop_token)), _p(t), int(t.size), C.byref(first), C.byref(kind), C.byref(rule)))
+    return int(first.value), int(kind.value), int(rule.value)
 
 
 def dfa_validate(dfa: Dfa, vocab: int):
@@ -394,6 +455,18 @@ class Ctx:
     def constraint_arm(self, state):
         """flm_constraint_arm: the state the _ex entry points mask in from now on (-1: disarm); query("constraint_state") reads it back"""
         _check(lib().flm_constraint_arm(self._h, C.c_int32(int(state))), self._h)
+
+    def stop_set(self, rules):
+        """flm_stop_set: install or replace the stop rules flm_generate_ex / flm_generate_lookup_ex end on (None: remove them); query("stop_rules") reads back whether any are installed"""
+        if rules is None:
+            _check(lib().flm_stop_set(self._h, None), self._h)
+            return
+        st = rules.struct()
+        _check(lib().flm_stop_set(self._h, C.byref(st)), self._h)
+
+    def stop_reason(self):
+        """why the last generate-family call ended -> (STOP_LENGTH | STOP_TOKEN | STOP_ID | STOP_SEQ | STOP_CANCEL, the id's position / the sequence's index)"""
+        return self.query("stop_reason"), self.query("stop_rule")
 
     def logprobs_arm(self, top_n, source="raw"):
         """flm_logprobs_arm: from now on the _ex entry points leave one record per delivered id (top_n alternatives, 0 .. 20; -1: off) from the classifier's row ("raw") or

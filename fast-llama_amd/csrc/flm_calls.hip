@@ -2,6 +2,7 @@
 // copies, the draw plan of flm_host.h) and the entry points themselves (include/flm_gpu.h: forward / decode / generate / score / draft-and-verify, the constraint, the
 // log-probabilities).  What outlives a call -- the context, its memory, options, graphs and preparation -- is flm_gpu.hip.
 #include "flm_host.h"
+#include "../host/stop_rules.h"
 #include <algorithm>
 
 namespace fh {
@@ -12,7 +13,7 @@ namespace fh {
 __global__ void k_set_state(DecodeState* st, const DecodeState v) { if (threadIdx.x == 0 && blockIdx.x == 0) *st = v; }
 int set_state(flm_ctx* c, int pos, int tok, int step) {
     DecodeState v{};
-    v.pos = pos; v.tok = tok; v.step = step; v.halt = 0; v.stop_tok = c->gen_stop; v.gen_tag = c->gen_tag; v.max_tokens = c->gen_max;
+    v.pos = pos; v.tok = tok; v.step = step; v.halt = 0; v.stop_tok = c->gen_stop; v.gen_tag = c->gen_tag; v.max_tokens = c->gen_max; v.stop_rules = c->gen_rules;
     v.ring_cap = c->gen_cap; v.ring = c->gen_ring_dev; v.cancel = c->gen_cancel_dev;
     hipLaunchKernelGGL(k_set_state, dim3(1), dim3(64), 0, c->stream, c->state, v);
     HIPC(c, hipGetLastError());
@@ -254,8 +255,9 @@ static bool lp_armed(const flm_ctx* c) { return c->lp_top_n >= 0 && logprobs_sup
 // only), and so does a context armed for log-probabilities (the shaped form with the record stage behind its sampler).  own(block, active): what one entry point checks or
 // changes between the block's validation and that decision (null, or what is wrong)
 struct NoOwn { const char* operator()(ShapeParams&, bool&) const { return nullptr; } };
+// honour_rules (flm_generate_ex / flm_generate_lookup_ex): installed stop rules count as a control that is set too -- the matcher lives in the shaped form's last launch
 template <class Own = NoOwn>
-static int draw_resolve(flm_ctx* c, const flm_sampling* sampling, const int32_t* window, int n_window, bool follow, uint64_t* rng_state, Draw& dr, Own own = Own()) {
+static int draw_resolve(flm_ctx* c, const flm_sampling* sampling, const int32_t* window, int n_window, bool follow, uint64_t* rng_state, Draw& dr, Own own = Own(), bool honour_rules = false) {
     bool active = false;
     const char* why = shape_fill(sampling, c->d.vocab_size, window, n_window, follow, &dr.block, &active);
     if (!why) why = own(dr.block, active);
@@ -264,7 +266,8 @@ static int draw_resolve(flm_ctx* c, const flm_sampling* sampling, const int32_t*
     dr.plain(sampling->temperature, sampling->topp, rng_state);
     const int cq = sharded(c) ? -1 : c->dfa_state;
     const bool lp = lp_armed(c);
-    if (active || cq >= 0 || lp) dr.shape_by(cq, lp);
+    const bool rules = honour_rules && !sharded(c) && stop_installed(c);
+    if (active || cq >= 0 || lp || rules) { dr.shape_by(cq, lp); dr.rules = rules; }
     return FLM_OK;
 }
 // flm_score_tokens: where a chunk of rows' logits is staged -- the prefill scores (free once the last layer's attention is done) or, a row at a time, the logits vector --
@@ -276,10 +279,24 @@ float* score_stage(const flm_ctx* c, int* chunk) {
     if (c->score_rows > 0 && c->score_rows < *chunk) *chunk = c->score_rows;
     return sc_rows >= 1 ? c->pf_scores : c->logits;
 }
+// the host's view of the installed rules (pointers into the context's copy), and why a generate-family call that delivered ids[0 .. n) of max_tokens ended: the host
+// restatement at the last delivered index; no rule fires there: fewer ids than asked for = behind a cancel, else length ("stop_reason" / "stop_rule")
+static flm_stop_rules stop_view(const flm_ctx* c) {
+    const StopBlock& b = c->stop_host;
+    return flm_stop_rules{b.n_ids, b.ids, b.n_seqs, b.seq_ptr, b.seq_tok};
+}
+static void stop_note(flm_ctx* c, bool with_rules, int32_t stop_token, const int32_t* ids, int n, int max_tokens) {
+    const flm_stop_rules v = stop_view(c);
+    int kind = FLM_STOP_LENGTH, rule = 0;
+    if (n < 1 || !flmhost::stop_fires_at(with_rules ? &v : nullptr, stop_token, ids, n - 1, &kind, &rule)) { kind = n < max_tokens ? FLM_STOP_CANCEL : FLM_STOP_LENGTH; rule = 0; }
+    c->stop_reason = kind; c->stop_rule = rule;
+}
 // One verify pass at `pos` over the batch prompt_dev[0 .. k] (draft: written by the drafter from the history spec_hist[0 .. n_hist) first): all layers, the classifier in
 // chunks, the rows' ids -- drawn by k_sample_rows with the coins of draw.base, at temperature 0 their first maxima --, the accept step, which also leaves the state after
 // the step's draws.  Enqueues only; the result block spec_res is read by the caller.
-static int spec_step(flm_ctx* c, int pos, int k, int ngram_max, int n_hist, int stop, int room, bool draft, const SpecDraw& draw) {
+// rules (the loop under installed stop rules; null otherwise): the accept step also cuts the run behind the first index a rule fires at (k_spec_accept_rules), evaluated
+// against spec_hist[n_prompt .. n_hist) ++ the run
+static int spec_step(flm_ctx* c, int pos, int k, int ngram_max, int n_hist, int stop, int room, bool draft, const SpecDraw& draw, const StopBlock* rules = nullptr, int n_prompt = 0) {
     const int B = k + 1;
     if (draft) {
         hipLaunchKernelGGL(k_spec_draft, dim3(1), dim3(kSampleBlock), 0, c->stream, (const int*)c->spec_hist, n_hist, k, ngram_max, c->prompt_dev);
@@ -292,7 +309,8 @@ static int spec_step(flm_ctx* c, int pos, int k, int ngram_max, int n_hist, int 
         const int m = B - r0 < chunk ? B - r0 : chunk;
         r = spec_classify(c, r0, m, stage, skinny, c->spec_arg, draw); if (r) return r;
     }
-    hipLaunchKernelGGL(k_spec_accept_sample, dim3(1), dim3(64), 0, c->stream, c->spec_res, (const int*)c->spec_arg, (const int*)c->prompt_dev, k, draft ? c->spec_hist : (int*)nullptr, n_hist, stop, room, draw.base, draw.temperature != 0.0f ? 1 : 0);
+    if (rules && draft) hipLaunchKernelGGL(k_spec_accept_rules, dim3(1), dim3(kSampleBlock), 0, c->stream, c->spec_res, (const int*)c->spec_arg, (const int*)c->prompt_dev, k, c->spec_hist, n_prompt, n_hist, stop, room, draw.base, draw.temperature != 0.0f ? 1 : 0, rules);
+    else hipLaunchKernelGGL(k_spec_accept_sample, dim3(1), dim3(64), 0, c->stream, c->spec_res, (const int*)c->spec_arg, (const int*)c->prompt_dev, k, draft ? c->spec_hist : (int*)nullptr, n_hist, stop, room, draw.base, draw.temperature != 0.0f ? 1 : 0);
     HIPC(c, hipGetLastError());
     return FLM_OK;
 }
@@ -394,8 +412,8 @@ int flm_decode_sample(flm_ctx* c, int32_t first_token, int pos, int n_steps, flo
 namespace {
 struct GenWords {     // the decode state's generate words hold for the enqueue of one attempt only: every other entry point's set_state writes -1 / 0 / 0
     flm_ctx* c;
-    GenWords(flm_ctx* c_, int stop, unsigned tag, int max_tokens) : c(c_) { c->gen_stop = stop; c->gen_tag = tag; c->gen_max = max_tokens; }
-    ~GenWords() { c->gen_stop = -1; c->gen_tag = 0; c->gen_max = 0; }
+    GenWords(flm_ctx* c_, int stop, unsigned tag, int max_tokens, bool rules) : c(c_) { c->gen_stop = stop; c->gen_tag = tag; c->gen_max = max_tokens; c->gen_rules = rules ? 1 : 0; }
+    ~GenWords() { c->gen_stop = -1; c->gen_tag = 0; c->gen_max = 0; c->gen_rules = 0; }
 };
 inline void cpu_relax() {
 #if defined(__x86_64__) || defined(__i386__)
@@ -434,7 +452,7 @@ static int generate_impl(flm_ctx* c, const int32_t* prompt, int n_prompt, int po
         // what was delivered
         __atomic_store_n(cancel_word, 0, __ATOMIC_RELEASE);
         {
-            const GenWords words(c, stop_token < 0 ? -1 : stop_token, tag, max_tokens);
+            const GenWords words(c, stop_token < 0 ? -1 : stop_token, tag, max_tokens, dr.rules);       // (dr.rules: the plan is flm_generate_ex's and rules are installed)
             int r = dr.arm(c);
             if (!r) r = feed(c, prompt, n_prompt, pos, dr.form);              // token 0: drawn from the prompt's last logits
             if (!r && max_tokens > 1) r = run_tokens(c, pos + n_prompt, max_tokens - 1, dr.form);
@@ -474,6 +492,7 @@ static int generate_impl(flm_ctx* c, const int32_t* prompt, int n_prompt, int po
         *n_out = total;
         dr.commit(c, ids, total, after);                                  // (the stop token, when delivered, included; armed: record i is out_tokens[i]'s)
         c->gen_tokens = total; c->gen_streamed = streamed;
+        stop_note(c, dr.rules, stop_token, ids, total, max_tokens);
     });
     return r;
 }
@@ -492,7 +511,7 @@ int flm_generate_ex(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, in
     if (!ids_in_vocab(c, prompt, n_prompt)) return fail(c, FLM_ERR_INVALID, "token id out of range");
     const int tail = n_prompt < FLM_PENALTY_WINDOW_MAX ? n_prompt : FLM_PENALTY_WINDOW_MAX;
     Draw dr;
-    if (int r = draw_resolve(c, sampling, prompt + (n_prompt - tail), tail, true, rng_state, dr)) return r;
+    if (int r = draw_resolve(c, sampling, prompt + (n_prompt - tail), tail, true, rng_state, dr, NoOwn(), true)) return r;
     return generate_impl(c, prompt, n_prompt, pos, max_tokens, dr, stop_token, cb, user, out_tokens, n_out);
 }
 // flm_forward_sample with the controls and the caller's window (used as given).  Every control neutral: flm_forward_sample / flm_forward_argmax.
@@ -637,14 +656,15 @@ static int generate_lookup_impl(flm_ctx* c, const int32_t* prompt, int n_prompt,
     // delivered so far (the host folds every step's ids into it and passes the result on; armed for log-probabilities, record i is the call's i-th id's: the base is `total`)
     uint64_t state = sampled ? *dr.rng_state : 0;
     int cst = dr.cstate;
-    int32_t* const drawn = c->gen_ids.data();                        // shaped: the ids delivered so far, for the single-token steps' windows (pageable, max_seq_len ids, there since create)
+    int32_t* const drawn = c->gen_ids.data();                        // shaped: the ids delivered so far, for the single-token steps' windows and the finish reason (pageable, max_seq_len ids, there since create)
+    const StopBlock* const rules = dr.rules ? c->stop_blk : nullptr;  // installed stop rules (flm_generate_lookup_ex): token 0 and every accept step evaluate them on the device
     SpecOut so{};
     auto deliver = [&]() {                       // the step's ids, in index order, on this thread; the state moves with them
         for (int i = 0; i < so.n_emit; ++i) {
             const int index = total + i;
             const bool last = i + 1 == so.n_emit && (so.stopped || index + 1 == max_tokens);
             if (out_tokens) out_tokens[index] = so.ids[i];
-            if (dr.shaped()) drawn[index] = so.ids[i];
+            drawn[index] = so.ids[i];
             if (cb && !cancelled && cb(user, index, so.ids[i], last ? 1 : 0) != 0) cancelled = true;
         }
         if (cst >= 0) cst = dfa_fold(c, cst, so.ids, so.n_emit);
@@ -655,7 +675,7 @@ static int generate_lookup_impl(flm_ctx* c, const int32_t* prompt, int n_prompt,
     r = with_retry(c, n_prompt, [&]() -> int {
         int r = dr.arm(c); if (r) return r;
         r = feed(c, prompt, n_prompt, pos, dr.form); if (r) return r;
-        hipLaunchKernelGGL(k_spec_begin, dim3(1), dim3(256), 0, c->stream, c->spec_hist, (const int*)c->prompt_dev, n_prompt, (const int*)c->out_tokens_dev, c->spec_res, stop, (unsigned long long)state, sampled ? 1 : 0);
+        hipLaunchKernelGGL(k_spec_begin, dim3(1), dim3(rules ? kSampleBlock : 256), 0, c->stream, c->spec_hist, (const int*)c->prompt_dev, n_prompt, (const int*)c->out_tokens_dev, c->spec_res, stop, (unsigned long long)state, sampled ? 1 : 0, rules);
         HIPC(c, hipGetLastError());
         return d2h(c, &so, c->spec_res, sizeof so);
     }, deliver);
@@ -666,7 +686,7 @@ static int generate_lookup_impl(flm_ctx* c, const int32_t* prompt, int n_prompt,
         r = with_retry(c, batch ? draft_len + 1 : 1, [&]() -> int {
             int r;
             if (batch) {       // (the block: as token 0's attempt left it; the rows' windows: the history; records land behind the ids delivered so far)
-                r = spec_step(c, at, draft_len, ngram_max, n_hist, stop, room, true, dr.batch(c, state, c->spec_hist, n_hist, cst, total));
+                r = spec_step(c, at, draft_len, ngram_max, n_hist, stop, room, true, dr.batch(c, state, c->spec_hist, n_hist, cst, total), rules, n_prompt);
             }
             else {      // one token through the token graph and the accept kernel with K = 0: the id from the decode state's first output slot, cut / appended / counted like a verified run of one
                 // (its window, as given: the last min(last_n, n_hist) ids of prompt ++ drawn[0 .. total); the constraint's block: {the folded state, 0}; the record stage's: step 0 is record `total`)
@@ -674,7 +694,8 @@ static int generate_lookup_impl(flm_ctx* c, const int32_t* prompt, int n_prompt,
                 if (r) return r;
                 r = set_state(c, at, last_tok, 0); if (r) return r;
                 r = run_token(c, true, dr.form, at + 1); if (r) return r;
-                hipLaunchKernelGGL(k_spec_accept_sample, dim3(1), dim3(64), 0, c->stream, c->spec_res, (const int*)c->out_tokens_dev, (const int*)c->prompt_dev, 0, c->spec_hist, n_hist, stop, room, (unsigned long long)state, sampled ? 1 : 0);
+                if (rules) hipLaunchKernelGGL(k_spec_accept_rules, dim3(1), dim3(kSampleBlock), 0, c->stream, c->spec_res, (const int*)c->out_tokens_dev, (const int*)c->prompt_dev, 0, c->spec_hist, n_prompt, n_hist, stop, room, (unsigned long long)state, sampled ? 1 : 0, rules);
+                else hipLaunchKernelGGL(k_spec_accept_sample, dim3(1), dim3(64), 0, c->stream, c->spec_res, (const int*)c->out_tokens_dev, (const int*)c->prompt_dev, 0, c->spec_hist, n_hist, stop, room, (unsigned long long)state, sampled ? 1 : 0);
                 r = hipGetLastError() == hipSuccess ? FLM_OK : fail(c, FLM_ERR_HIP, "generate_lookup: launch failed");
             }
             if (r) return r;
@@ -685,6 +706,7 @@ static int generate_lookup_impl(flm_ctx* c, const int32_t* prompt, int n_prompt,
     *n_out = total;
     dr.commit(c, total, state, cst);
     c->spec_steps = steps; c->spec_accepted = accepted;
+    stop_note(c, dr.rules, stop_token, drawn, total, max_tokens);
     return FLM_OK;
 }
 int flm_generate_lookup(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, int max_tokens, int32_t stop_token, int draft_len, int ngram_max,
@@ -705,7 +727,7 @@ int flm_generate_lookup_ex(flm_ctx* c, const int32_t* prompt, int n_prompt, int 
     if (!ids_in_vocab(c, prompt, n_prompt)) return fail(c, FLM_ERR_INVALID, "token id out of range");
     const int tail = n_prompt < FLM_PENALTY_WINDOW_MAX ? n_prompt : FLM_PENALTY_WINDOW_MAX;
     Draw dr;
-    if (int r = draw_resolve(c, sampling, prompt + (n_prompt - tail), tail, true, rng_state, dr)) return r;
+    if (int r = draw_resolve(c, sampling, prompt + (n_prompt - tail), tail, true, rng_state, dr, NoOwn(), true)) return r;
     return generate_lookup_impl(c, prompt, n_prompt, pos, max_tokens, dr, stop_token, draft_len, ngram_max, cb, user, out_tokens, n_out);
 }
 
@@ -749,6 +771,43 @@ int flm_constraint_arm(flm_ctx* c, int32_t state) {
     int r = set_dfa(c, state); if (r) return r;
     c->dfa_state = state;
     return FLM_OK;
+}
+
+// Stop rules (include/flm_gpu.h; the matcher: flm_stop.h; the host restatement: host/stop_rules.h).  The block exists since flm_ctx_create: installing rules rewrites its
+// contents through the bounce buffer (one small copy kernel on the context's stream) -- no allocation, no graph touched
+int flm_stop_validate(const flm_stop_rules* r, int vocab) {
+    if (const char* why = flmhost::stop_check(r, vocab)) { g_last_error = why; return FLM_ERR_INVALID; }
+    return FLM_OK;
+}
+int flm_stop_match(const flm_stop_rules* r, int32_t stop_token, const int32_t* ids, int n, int* kind, int* rule) {
+    int k = FLM_STOP_LENGTH, ru = 0;
+    const int first = ids && n > 0 ? flmhost::stop_match(r, stop_token, ids, n, &k, &ru) : (n > 0 ? n : 0);
+    if (kind) *kind = k;
+    if (rule) *rule = ru;
+    return first;
+}
+int flm_stop_set(flm_ctx* c, const flm_stop_rules* r) {
+    if (!c) return FLM_ERR_INVALID;
+    if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "stop rules: one GPU only");
+    if (!model_complete(c)) return fail(c, FLM_ERR_STATE, "stop_set before all tensors were uploaded");
+    if (!sample_supported(c)) return fail(c, FLM_ERR_UNSUPPORTED, "stop rules: the vocabulary does not fit one workgroup's LDS (the device sampler's bound)");
+    if (r) if (const char* why = flmhost::stop_check(r, c->d.vocab_size)) return fail(c, FLM_ERR_INVALID, why);
+    static_assert(kStopIdsMax == FLM_STOP_IDS_MAX && kStopSeqsMax == FLM_STOP_SEQS_MAX && kStopSeqLenMax == FLM_STOP_SEQ_LEN_MAX, "flm_stop.h mirrors the header's limits");
+    static_assert(sizeof(StopBlock) % 4 == 0, "whole words");
+    StopBlock b{};
+    if (r) {
+        b.n_ids = r->n_ids; b.n_seqs = r->n_seqs; b.n_tok = r->n_seqs > 0 ? r->seq_ptr[r->n_seqs] : 0;
+        for (int i = 0; i < r->n_ids; ++i) b.ids[i] = r->ids[i];
+        for (int s = 0; s <= r->n_seqs && r->n_seqs > 0; ++s) b.seq_ptr[s] = r->seq_ptr[s];
+        for (int k = 0; k < b.n_tok; ++k) b.seq_tok[k] = r->seq_tokens[k];
+    }
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    // (a HIP error between the pieces of the copy would leave the device block half rewritten: the host copy, which alone decides whether a call looks at the block, then says "none")
+    int rc = h2d(c, c->stop_blk, &b, sizeof b);
+    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, FLM_ERR_HIP, "stop_set: the copy of the rule block failed");   // (`b` has left the bounce buffer; the next call's first launch sees the block)
+    c->stop_host = rc ? StopBlock{} : b;
+    return rc;
 }
 
 // Per-token log-probabilities (include/flm_gpu.h; the stage: flm_logprob.h).  A context setting like flm_constraint_arm: the block, the records and the armed token graphs

@@ -514,6 +514,7 @@ int flm_ctx_create(const flm_model_desc* desc, int device_id, int rank, int worl
         HIPB(hipMemcpyAsync(c->dfa_blk, &none, sizeof none, hipMemcpyHostToDevice, c->stream));
         HIPB(hipStreamSynchronize(c->stream));                                // (`none` goes out of scope)
     }
+    HIPB(dev_alloc(c, &c->stop_blk, sizeof(StopBlock), true));     // the stop rules' block (flm_stop.h), zeroed: no rules
     if (logprobs_supported(c)) {   // per-token log-probabilities (flm_logprob.h): the block (disarmed), the records and their tags, a verify batch's side rows
         HIPB(dev_alloc(c, &c->lp_blk, sizeof(LogprobBlock), true));
         LogprobBlock off{}; off.top_n = -1;
@@ -820,6 +821,9 @@ int flm_query(flm_ctx* c, const char* key, int* value) {
         {"shaped_tokens", (int)c->shaped},
         {"constraint_state", c->dfa_state},
         {"logprobs_top_n", c->lp_top_n},
+        {"stop_rules", stop_installed(c) ? 1 : 0},
+        {"stop_reason", c->stop_reason},
+        {"stop_rule", c->stop_rule},
         {"gen_tokens", c->gen_tokens},
         {"gen_streamed", c->gen_streamed},
         {"spec_steps", c->spec_steps},

@@ -177,6 +177,7 @@ struct flm_ctx {
     // per-attempt sequence number the granules are tagged with, a pageable staging buffer for the ids, and the last call's figures ("gen_tokens" / "gen_streamed")
     unsigned long long* gen_host = nullptr; unsigned long long* gen_ring_dev = nullptr; const int* gen_cancel_dev = nullptr; int gen_cap = 0;
     int gen_stop = -1; unsigned gen_tag = 0; int gen_max = 0; unsigned gen_seq = 0;
+    int gen_rules = 0;                                 // ... and DecodeState::stop_rules: 1 while flm_generate_ex enqueues an attempt under installed stop rules, else 0
     std::vector<int32_t> gen_ids; int gen_tokens = 0, gen_streamed = 0;
     // flm_score_tokens (flm_calls.hip; the classifier stage: flm_prompt.hip): the rows' targets and statistics in device memory [max_seq_len] (allocated at create), and the
     // classifier's scales group-major (cls.st) for the GEMM tiles, transposed once per set of weights
@@ -193,6 +194,10 @@ struct flm_ctx {
     // (-1: it ran disarmed, failed, or there was none)
     int lp_top_n = -1, lp_source = 0, lp_count = -1;
     flm::LogprobBlock* lp_blk = nullptr; flm::LogprobRec* lp_rec = nullptr; unsigned* lp_tags = nullptr; float* lp_side = nullptr;
+    // stop rules (include/flm_gpu.h flm_stop_set; the matcher: flm_stop.h): the rule block in device memory since create (the shaped token graphs hold the pointer; only its
+    // contents change), the host copy the finish reason is computed from (n_ids = n_seqs = 0: none installed; "stop_rules"), and why the last generate-family call ended
+    // ("stop_reason" / "stop_rule")
+    flm::StopBlock* stop_blk = nullptr; flm::StopBlock stop_host{}; int stop_reason = 0, stop_rule = 0;
     int score_rows = 0;                                // option "score_rows": rows per classifier chunk of flm_score_tokens (0: as many as the staging holds; < 0: one row at a time through c->logits)
     std::map<GraphKey, hipGraphExec_t> graphs;        // the token graphs captured so far (flm_gpu.hip token_graph)
     std::vector<TimedLaunch>* timing = nullptr;
@@ -322,6 +327,7 @@ struct Draw {
     flm::ShapeParams block;                                       // the shaper's parameter block (shaped forms only)
     int cstate = -1;                                              // the constraint's state at the call's first token (-1: none; only with the block: an armed constraint counts as a control)
     bool lp = false;                                              // the context is armed for log-probabilities: the form is ShapedLp, record i is the call's i-th id's
+    bool rules = false;                                           // stop rules are installed and this entry point honours them (flm_generate_ex / flm_generate_lookup_ex; only with the block)
     Draw(float t = 0.0f, float p = 0.0f, uint64_t* st = nullptr, bool sampler = false) { plain(t, p, st, sampler); }
     void plain(float t, float p, uint64_t* st, bool sampler = false) { temperature = t; topp = p; rng_state = st; form = t != 0.0f || sampler ? TokenForm::Sampled : TokenForm::Greedy; }
     void shape_by(int cq, bool armed) { form = armed ? TokenForm::ShapedLp : TokenForm::Shaped; cstate = cq; lp = armed; }   // `block` is filled: the shaped form runs
@@ -366,6 +372,8 @@ struct SpecDraw { float temperature, topp; unsigned long long base; const flm::S
 // k_shape_rows on `rows` rows (batch rows row0 ..) of n logits, ld floats apart -> out, ld_out apart (out == logits: in place); c may be null: flm_op_shape_rows
 int launch_shape_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, float* out, int ld_out, int n, int row0, int rows, const flm::ShapeParams* p,
                       const int* win, int n_win, const int* drafts, const flm::DfaBlock* dfa = nullptr, int cstate = -1, int* states_out = nullptr);
+// stop rules are installed (flm_stop_set refuses where the shaped form could not honour them)
+inline bool stop_installed(const flm_ctx* c) { return c->stop_blk != nullptr && (c->stop_host.n_ids | c->stop_host.n_seqs) != 0; }
 // delta folded over ids[0 .. n) from state q on the context's host copy of the automaton (flm_calls.hip; q in [0, n_states))
 int dfa_fold(const flm_ctx* c, int q, const int32_t* ids, int n);
 // the rules of flm_dfa_validate (flm_calls.hip): null, or which one failed

@@ -51,11 +51,13 @@
 //                         (flm_score_tokens behind the batched prompt path's classifier GEMM; flm_op_score_rows)
 //   k_logprob_token, k_logprob_rows  (flm_logprob.h) the record of one drawn token -- its logit, the clipped softmax's max / exact sum, the first top_n entries of the row -- behind
 //                         the shaped token form's sampler / behind a verify batch's row draws, while the context is armed (flm_logprobs_arm; flm_op_logprob_rows)
+//   stop_match, k_op_stop_match, k_spec_accept_rules  (flm_stop.h, flm_spec.h) the stop rules of flm_stop_set: one workgroup-parallel matcher in front of
+//                         the shaped token form's last act (k_sample_advance), in the accept step of draft-and-verify, and behind flm_op_stop_match
 // plus small op-level kernels that expose the same __device__ functions to the parity tests.
 // (Round 3's weight-streaming engine -- loader / consumer waves around an LDS ring -- was measured slower than these launches and left the library in round 4:
 //  tools/experiments/engine/, numbers in profiles/r03_engine_timelines.txt.)
 //
-// The code lives in: flm_math.h (exact scalar / wave building blocks), flm_wait.h (every cross-workgroup wait: flag polls, granule pieces, the give-up policy), flm_gemv.h, flm_attn.h, flm_layer.h, flm_prefill.h, flm_misc.h, flm_sample.h, flm_score.h, flm_logprob.h, flm_spec.h.
+// The code lives in: flm_math.h (exact scalar / wave building blocks), flm_wait.h (every cross-workgroup wait: flag polls, granule pieces, the give-up policy), flm_gemv.h, flm_attn.h, flm_layer.h, flm_prefill.h, flm_misc.h, flm_sample.h, flm_score.h, flm_logprob.h, flm_spec.h, flm_stop.h.
 #pragma once
 #include "flm_math.h"
 #include "flm_wait.h"
@@ -64,6 +66,7 @@
 #include "flm_layer.h"
 #include "flm_prefill.h"
 #include "flm_misc.h"
+#include "flm_stop.h"
 #include "flm_sample.h"
 #include "flm_shape.h"
 #include "flm_score.h"

@@ -62,7 +62,9 @@ constexpr int kGroup = 64;            // quantization group (QUANT_GROUP_SIZE, t
 //   ring       [ring_cap] 8-byte granules {token | last << 31, gen_tag} in page-locked host-coherent memory: ONE aligned system-scope store per token, the data is its own flag
 //              (DESIGN.md sections 5c / 7e) -- a stale entry of an earlier call never carries the current tag;  cancel: one word of the same memory, written by the host.  The
 //              cancel word has exactly ONE reader per token, the last act's thread: no other workgroup may look at host memory
-struct DecodeState { int pos; int tok; int step; int halt; int stop_tok; unsigned gen_tag; int max_tokens; int ring_cap; unsigned long long* ring; const int* cancel; };
+//   stop_rules 1: this call honours the installed stop rules in the token form (flm_generate_ex under rules: the state's step is the call's index and out_tokens holds the
+//              call's ids); 0 for every other entry point, whatever form it replays -- the shaped form's matcher (flm_sample.h) looks at this word and nothing else
+struct DecodeState { int pos; int tok; int step; int halt; int stop_tok; unsigned gen_tag; int max_tokens; int ring_cap; unsigned long long* ring; const int* cancel; int stop_rules; };
 // the latch at a launch's top: a uniform scalar load through the constant address space (as k_layers reads its argument blocks), a scalar branch.  halt == nullptr: the caller
 // passes no state (the op-level exports, the tensor-parallel launch forms) and runs unconditionally.
 // RELIES ON: the word is NOT immutable, as constant-address-space memory is otherwise taken to be -- a vector store of the previous launch's last act (or of k_set_state) wrote
@@ -77,9 +79,10 @@ __device__ __forceinline__ bool halted(const int* halt) {
 // token does not move tok / pos on: the stop token is not fed.  err: the cross-workgroup waits' error word; once a wait of the call has given up its tokens are not published
 // (the host re-runs the call and delivers them from the sound attempt).  A token computed on garbage cannot be published: the wave that gives up a wait stores the error word
 // BEFORE it leaves the wait (flm_wait.h: the give-up policy and why that suffices), so when garbage can have influenced `tok`, the relaxed agent-scope load below already sees
-// the word set.  A token published before any wait gave up was computed soundly
-__device__ __forceinline__ bool gen_last_act(DecodeState* st, const int step, const int tok, const int* err) {
-    bool halt = tok == st->stop_tok;
+// the word set.  A token published before any wait gave up was computed soundly.  fired: a stop rule fires at this token (flm_stop.h, evaluated by the workgroup in front of
+// this call; the shaped token forms only): the token halts exactly as the stop token does
+__device__ __forceinline__ bool gen_last_act(DecodeState* st, const int step, const int tok, const int* err, const bool fired = false) {
+    bool halt = tok == st->stop_tok || fired;
     const unsigned tag = st->gen_tag;
     if (tag != 0u) {
         halt = halt || __hip_atomic_load(st->cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0;

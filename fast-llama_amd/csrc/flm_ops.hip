@@ -156,6 +156,28 @@ int flm_op_spec_draft(const int32_t* h, int n, int k, int ngram_max, int32_t* d)
     return FLM_OK;
 }
 
+/* the stop rules' matcher (flm_stop.h stop_match, the function the shaped token form runs in front of its last act) on caller-supplied ids: the first index that fires */
+int flm_op_stop_match(const flm_stop_rules* r, int32_t stop_token, const int32_t* ids, int n, int* first, int* kind, int* rule) {
+    if (!r || !ids || !first || !kind || !rule || n < 1 || n > (1 << 20)) return FLM_ERR_INVALID;
+    for (int i = 0; i < n; ++i) if (ids[i] < 0) return FLM_ERR_INVALID;
+    if (int rc = flm_stop_validate(r, 0x7fffffff)) return rc;                         // (the op has no model: any non-negative id is inside its vocabulary)
+    StopBlock b{};
+    b.n_ids = r->n_ids; b.n_seqs = r->n_seqs; b.n_tok = r->n_seqs > 0 ? r->seq_ptr[r->n_seqs] : 0;
+    for (int i = 0; i < r->n_ids; ++i) b.ids[i] = r->ids[i];
+    for (int s = 0; s <= r->n_seqs && r->n_seqs > 0; ++s) b.seq_ptr[s] = r->seq_ptr[s];
+    for (int k = 0; k < b.n_tok; ++k) b.seq_tok[k] = r->seq_tokens[k];
+    DevBuf db, di, dr;
+    if (db.alloc(sizeof b) || di.alloc((size_t)n * 4) || dr.alloc(4 * 4)) return FLM_ERR_OOM;
+    OPC(hipMemcpy(db.p, &b, sizeof b, hipMemcpyHostToDevice));
+    OPC(hipMemcpy(di.p, ids, (size_t)n * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_op_stop_match, dim3(1), dim3(1024), 0, 0, (const StopBlock*)db.as<StopBlock>(), (const int*)di.as<int>(), n, stop_token < 0 ? -1 : stop_token, dr.as<int>());
+    OPC(hipGetLastError()); OPC(hipDeviceSynchronize());
+    int res[3];
+    OPC(hipMemcpy(res, dr.p, sizeof res, hipMemcpyDeviceToHost));
+    *first = res[0]; *kind = res[1]; *rule = res[2];
+    return FLM_OK;
+}
+
 /* sample_argmax (sampler.cpp:36-47) as k_argmax_advance evaluates it: first maximum wins */
 int flm_op_argmax(const float* logits, int n, int32_t* idx) {
     if (!logits || !idx || n < 1) return FLM_ERR_INVALID;

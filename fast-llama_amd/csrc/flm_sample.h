@@ -16,6 +16,7 @@
 #pragma once
 #include "flm_math.h"
 #include "flm_gemv.h"
+#include "flm_stop.h"
 #pragma clang fp contract(off)
 
 namespace flm {
@@ -35,6 +36,7 @@ struct SampleArgs {
     DecodeState* st; int* out_tokens; int out_cap; int advance;
     unsigned long long* sort_buf;         // [2][n]: the radix sort's ping-pong buffers
     const int* err;                       // the cross-workgroup waits' error word (gen_last_act; may be null)
+    const StopBlock* stop;                // the stop rules' block (flm_stop.h; the shaped token forms pass it, every other launch null): looked at where DecodeState::stop_rules is set
 };
 
 // xorshift* (sampler.cpp random_u32 / random_f32): the coin of one draw
@@ -114,7 +116,7 @@ __device__ __forceinline__ int sample_draw(const float* logits, int n, float tem
     int* cnt = reinterpret_cast<int*>(strip + 64 * LS);
     int* dbase = cnt + kSampleWaves * 256;
     int* hist = dbase + 256;
-    int* misc = hist + 4 * 256;            // [0..31] reductions, [32] result, [33] sum / n0, [36..39] "digit d is the same in every candidate"
+    int* misc = hist + 4 * 256;            // [0..31] reductions, [32] result, [33] sum / n0, [36..39] "digit d is the same in every candidate"; [40..55] are k_sample_advance's (sample_misc)
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     auto spos = [&](int i) { const int L = i / B; return L * LS + (i - L * B); };       // element i's place in the strip
     int tok;
@@ -250,16 +252,33 @@ __device__ __forceinline__ int sample_draw(const float* logits, int n, float tem
     return tok;
 }
 
+// the 64 words at the end of sample_draw's LDS (its `misc`): sample_draw uses [0..39]; [40..55] hold the stop matcher's mismatch words (kStopLdsWords) in k_sample_advance,
+// so the kernel's LDS does not grow and the sampler's vocabulary bound stays where it is
+__device__ __forceinline__ unsigned* sample_misc(float* strip, int n) {
+    return reinterpret_cast<unsigned*>(strip + 64 * (sample_lane_elems(n) + 4)) + kSampleWaves * 256 + 256 + 4 * 256;
+}
+static_assert(40 + kStopLdsWords <= 64, "the stop matcher's words fit behind sample_draw's");
+
 // One workgroup of 1024 threads, sample_lds_bytes(n) of dynamic LDS, n >= 2.  Writes out_tokens[step], advances the state like k_argmax_advance, and the sampler state.
+// a.stop given, not empty, and the call one that honours rules in the token form (DecodeState::stop_rules, set by flm_generate_ex alone): the stop rules are
+// matched against out_tokens[0 .. step) ++ tok by the whole workgroup (flm_stop.h) in front of the last act, which then halts as on the stop token.  The ids of THIS
+// attempt lie in out_tokens from index 0 on (a retried attempt rewrites them before it reads them), and every read stays below out_cap.
 inline __global__ void __launch_bounds__(kSampleBlock) k_sample_advance(const SampleArgs a) {
     extern __shared__ float4 sample_lds4[];
     if (halted(&a.st->halt)) return;       // (flm_math.h DecodeState::halt: the sampler state stays at the last drawn token's)
     unsigned long long rng = a.sp->rng;
     const int tok = sample_draw(a.logits, a.n, a.sp->temperature, a.sp->topp, rng, a.sort_buf, reinterpret_cast<float*>(sample_lds4));
+    bool fired = false;
+    if (stop_armed(a.stop) && a.out_tokens != nullptr && a.st->stop_rules != 0) {       // (uniform: every thread takes the same branch)
+        const int step = a.st->step;                                                   // (written behind the matcher's barrier only: by thread 0, below)
+        const int* const ot = a.out_tokens; const int cap = a.out_cap;
+        if (step >= 0 && step < cap)
+            fired = stop_match(a.stop, tok, [&](int j) { return j < cap ? ot[j] : -1; }, step, sample_misc(reinterpret_cast<float*>(sample_lds4), a.n) + 40).kind != 0;
+    }
     if (threadIdx.x == 0) {
         DecodeState* st = a.st;
         if (a.out_tokens && st->step >= 0 && st->step < a.out_cap) a.out_tokens[st->step] = tok;
-        const bool halt = gen_last_act(st, st->step, tok, a.err);                               // (the token's last act: flm_math.h)
+        const bool halt = gen_last_act(st, st->step, tok, a.err, fired);                        // (the token's last act: flm_math.h)
         if (a.advance && !halt) { st->tok = tok; st->pos += 1; }
         st->step += 1;
         a.sp->rng = rng;

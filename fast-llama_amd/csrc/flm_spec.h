@@ -74,14 +74,52 @@ inline __global__ void k_spec_accept_sample(SpecOut* out, const int* __restrict_
     if (draws) for (int i = 0; i < n; ++i) s = sample_step(s);
     out->rng = s;
 }
-// flm_generate_lookup's start: the history = the prompt and the id drawn from its last logits (tok0[0], the decode state's first output slot); the whole result block of
-// that one id (the state after its one draw)
-inline __global__ void k_spec_begin(int* __restrict__ hist, const int* __restrict__ prompt, int n_prompt, const int* __restrict__ tok0, SpecOut* out, int stop,
-                                    unsigned long long base, int draws) {
-    for (int i = threadIdx.x; i < n_prompt; i += blockDim.x) hist[i] = prompt[i];
+// The accept step under stop rules (flm_stop_set; flm_generate_lookup_ex): the same words as k_spec_accept_sample, with the run also cut behind the first index at which a
+// rule fires.  The ids this call has delivered are hist[n_prompt .. n_hist); the run a[0 .. n) follows them, so the matcher's t[j] is hist[n_prompt + j] below n_gen =
+// n_hist - n_prompt and a[j - n_gen] from there on -- ids in front of n_prompt are never read.  One workgroup of 1024 threads: thread 0 finds m and the cut at `room` as
+// before, the workgroup evaluates stop_match (flm_stop.h) at the run's n indices -- the mismatch words alternate between two sets, one barrier per index --, thread 0 keeps
+// the first index that fires or holds the stop token and stores the block.  hist must be given (the loop's call; flm_verify_sample_ex ignores the rules)
+inline __global__ void __launch_bounds__(kSampleBlock) k_spec_accept_rules(SpecOut* out, const int* __restrict__ a, const int* __restrict__ batch, int K, int* hist, int n_prompt,
+                                                                           int n_hist, int stop, int room, unsigned long long base, int draws, const StopBlock* rules) {
+    __shared__ unsigned lds[2][kStopLdsWords];
+    __shared__ int run[2];
     if (threadIdx.x == 0) {
-        const int id = tok0[0];
-        hist[n_prompt] = id; out->ids[0] = id; out->m = 0; out->n_emit = 1; out->stopped = id == stop ? 1 : 0; out->pad = 0;
+        int m = 0;
+        while (m < K && a[m] == batch[1 + m]) ++m;
+        run[0] = m; run[1] = m + 1 < room ? m + 1 : room;
+    }
+    __syncthreads();
+    const int m = run[0], n_gen = n_hist - n_prompt;
+    int n = run[1], stopped = 0;
+    const bool armed = stop_armed(rules);
+    const int* const h = hist + n_prompt;
+    int cut = n;
+    for (int i = 0; i < n; ++i) {
+        const int id = a[i];
+        bool ends = id == stop;
+        if (armed) ends = stop_match(rules, id, [&](int j) { return j < n_gen ? h[j] : a[j - n_gen]; }, n_gen + i, lds[i & 1]).kind != 0 || ends;
+        if (ends && cut == n && !stopped) { cut = i + 1; stopped = 1; }       // (valid in wave 0; thread 0 stores)
+    }
+    if (threadIdx.x != 0) return;
+    n = cut;
+    for (int i = 0; i < n; ++i) { const int id = a[i]; out->ids[i] = id; hist[n_hist + i] = id; }
+    out->m = m; out->n_emit = n; out->stopped = stopped; out->pad = 0;
+    unsigned long long s = base;
+    if (draws) for (int i = 0; i < n; ++i) s = sample_step(s);
+    out->rng = s;
+}
+// flm_generate_lookup's start: the history = the prompt and the id drawn from its last logits (tok0[0], the decode state's first output slot); the whole result block of
+// that one id (the state after its one draw).  rules (may be null; then launched with any block size): index 0 of the call stops on a listed id or a sequence of length 1
+// too -- launched with 1024 threads, the matcher's workgroup
+inline __global__ void __launch_bounds__(kSampleBlock) k_spec_begin(int* __restrict__ hist, const int* __restrict__ prompt, int n_prompt, const int* __restrict__ tok0,
+                                                                    SpecOut* out, int stop, unsigned long long base, int draws, const StopBlock* rules = nullptr) {
+    __shared__ unsigned lds[kStopLdsWords];
+    for (int i = threadIdx.x; i < n_prompt; i += blockDim.x) hist[i] = prompt[i];
+    const int id = tok0[0];
+    bool fired = false;
+    if (stop_armed(rules)) fired = stop_match(rules, id, [](int) { return -1; }, 0, lds).kind != 0;
+    if (threadIdx.x == 0) {
+        hist[n_prompt] = id; out->ids[0] = id; out->m = 0; out->n_emit = 1; out->stopped = id == stop || fired ? 1 : 0; out->pad = 0;
         out->rng = draws ? sample_step(base) : base;
     }
 }

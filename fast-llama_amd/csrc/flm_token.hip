@@ -393,6 +393,7 @@ layers_done:
                 if (sample_supported(c)) {
                     SampleArgs sa{};
                     sa.logits = c->shape_row; sa.n = d.vocab_size; sa.sp = c->sparams; sa.st = c->state; sa.out_tokens = c->out_tokens_dev; sa.out_cap = c->out_cap; sa.advance = 1; sa.sort_buf = c->sort_buf; sa.err = c->xwg_err;
+                    sa.stop = c->stop_blk;                                             // (the stop rules: the shaped forms only, flm_stop.h)
                     hipLaunchKernelGGL(k_sample_advance, dim3(1), dim3(kSampleBlock), sample_lds_bytes(d.vocab_size), st, sa);
                 } else {          // (the entry points admit temperature 0 only here: the first maximum of the shaped row)
                     hipLaunchKernelGGL(k_argmax_advance, dim3(1), dim3(1024), 0, st, (const float*)c->shape_row, d.vocab_size, c->state, c->out_tokens_dev, 1, c->out_cap, (const int*)c->xwg_err);

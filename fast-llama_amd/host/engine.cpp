@@ -202,6 +202,17 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
     const int max_tokens = n_in + max_new_tokens;
 
     _lp.clear();
+    _stop_reason = -1; _stop_rule = 0;
+    if (_stop_set && _ctxs.size() != 1) { _err = "--stop-ids / --stop-seq / --stop: one device only"; fprintf(stderr, "%s\n", _err.c_str()); return false; }
+    if (_stop_set && !_stop_installed) {        // the rules, once: the ids, the sequences, then every --stop string's one tokenisation (no BOS); checked against THIS model's vocabulary by flm_stop_set
+        std::vector<int32_t> ptr{0}, toks;
+        auto add = [&](const std::vector<int32_t>& q) { toks.insert(toks.end(), q.begin(), q.end()); ptr.push_back((int32_t)toks.size()); };
+        for (const auto& q : _stop_seqs) add(q);
+        for (const auto& str : _stop_strs) { const std::vector<int> e = _tok.encode(str, false); add(std::vector<int32_t>(e.begin(), e.end())); }
+        flm_stop_rules sr{(int32_t)_stop_ids.size(), _stop_ids.data(), (int32_t)ptr.size() - 1, ptr.data(), toks.data()};
+        if (flm_stop_set(_ctxs[0], &sr) != FLM_OK) { _err = std::string("stop rules: ") + flm_last_error(_ctxs[0]); fprintf(stderr, "%s\n", _err.c_str()); return false; }
+        _stop_installed = true;
+    }
     if (_lp_top_n >= 0 && _ctxs.size() != 1) { _err = "--logprobs: one device only"; fprintf(stderr, "%s\n", _err.c_str()); return false; }
     int prev = -1;
     auto emit = [&](int tok, int index, int n_cur) {
@@ -252,7 +263,8 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
         if (lp && (!dev_ok || flm_logprobs_arm(_ctxs[0], _lp_top_n, _lp_shaped ? FLM_LOGPROBS_SHAPED : FLM_LOGPROBS_RAW) != FLM_OK)) {
             _err = std::string("--logprobs: ") + (dev_ok ? flm_last_error(_ctxs[0]) : "the constraint could not be armed on the device"); fprintf(stderr, "%s\n", _err.c_str()); return false;
         }
-        if (dev_ok && (_shape_set || armed || lp)) {          // the sampling controls / the constraint: the same loop with the shaping stage on the device (flm_generate_ex; no control flag: neutral controls, masking only); refused: the host loop below shapes
+        if (_stop_set && !dev_ok) { _err = "--stop-ids / --stop-seq / --stop need the device loop, and --constraint could not be installed there (the library refused the automaton): drop one of the two"; fprintf(stderr, "%s\n", _err.c_str()); return false; }
+        if (dev_ok && (_shape_set || armed || lp || _stop_set)) {          // the sampling controls / the constraint: the same loop with the shaping stage on the device (flm_generate_ex; no control flag: neutral controls, masking only); refused: the host loop below shapes
             flm_sampling sp{};
             sp.temperature = temperature; sp.topp = topp; sp.top_k = _shape.top_k; sp.min_p = _shape.min_p; sp.repeat_penalty = _shape.repeat_penalty;
             sp.frequency_penalty = _shape.frequency_penalty; sp.presence_penalty = _shape.presence_penalty; sp.penalty_last_n = _shape_last_n;
@@ -266,6 +278,7 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
             }
             if (rc == FLM_ERR_UNSUPPORTED) rc = flm_generate_ex(_ctxs[0], input.data(), n_in, 0, want, &sp, &st, 0, on_token, &sink, nullptr, &n_out);
             if (rc == FLM_ERR_INVALID) { _err = flm_last_error(_ctxs[0]); fprintf(stderr, "%s\n", _err.c_str()); }
+            if (_stop_set && rc != FLM_OK) { if (_err.empty()) _err = std::string("stop rules: ") + flm_last_error(_ctxs[0]); return false; }      // (the rules live on the device path only)
             if (lp && rc != FLM_OK) { if (_err.empty()) _err = std::string("--logprobs: ") + flm_last_error(_ctxs[0]); return false; }
             if (lp && n_out > 0) {
                 _lp.resize((size_t)n_out);
@@ -282,7 +295,11 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
         }
         if (!dev_ok) { whole = false; rc = FLM_ERR_UNSUPPORTED; }
         if (whole) rc = flm_generate(_ctxs[0], input.data(), n_in, 0, want, temperature, topp, &st, 0, on_token, &sink, nullptr, &n_out);
-        if (rc == FLM_OK) { if (!greedy) _sampler.set_state(st); return true; }
+        if (rc == FLM_OK) {
+            if (!greedy) _sampler.set_state(st);
+            if (flm_query(_ctxs[0], "stop_reason", &_stop_reason) != FLM_OK || flm_query(_ctxs[0], "stop_rule", &_stop_rule) != FLM_OK) _stop_reason = -1;
+            return true;
+        }
         if (rc != FLM_ERR_UNSUPPORTED) return false;
         dev_sample = false;
     }

@@ -58,6 +58,16 @@ public:
     // constraint does, and the records of the last generate are kept for the caller: one flm_logprob per delivered token
     void set_logprobs(int top_n, bool shaped) { _lp_top_n = top_n; _lp_shaped = shaped; }
     const std::vector<flm_logprob>& logprobs() const { return _lp; }
+    // --stop-ids / --stop-seq / --stop (this build only, one device): stop rules next to the loop's own stop on token 0 (flm_stop_rules).  ids: the stop ids; seqs: id
+    // sequences; strs: strings, each tokenised ONCE by this tokenizer without BOS when the model is loaded and matched token by token on that one tokenisation (text that
+    // tokenises differently in context does not match).  Installed with flm_stop_set before the first generate; the run is flm_generate_ex / flm_generate_lookup_ex
+    // (neutral controls where no control flag was given): the device ends the call at the first index flm_stop_match names.  Refused by the library: an error
+    void set_stop(std::vector<int32_t> ids, std::vector<std::vector<int32_t>> seqs, std::vector<std::string> strs) {
+        _stop_ids = std::move(ids); _stop_seqs = std::move(seqs); _stop_strs = std::move(strs); _stop_set = true; _stop_installed = false;
+    }
+    // why the last generate on one device ended: FLM_STOP_LENGTH .. FLM_STOP_CANCEL and the rule (flm_query "stop_reason" / "stop_rule"); -1 where no call ran
+    int stop_reason() const { return _stop_reason; }
+    int stop_rule() const { return _stop_rule; }
     int lookup_steps() const { return _lookup_steps; }
     int lookup_accepted() const { return _lookup_accepted; }
     int get_quant_type() const { return _cfg.quant_type; }
@@ -82,6 +92,8 @@ private:
     int _lookup_k = 0, _lookup_g = 3, _lookup_steps = 0, _lookup_accepted = 0;
     int _draft_k = 0, _draft_g = 3;
     int _lp_top_n = -1; bool _lp_shaped = false; std::vector<flm_logprob> _lp;
+    bool _stop_set = false, _stop_installed = false; std::vector<int32_t> _stop_ids; std::vector<std::vector<int32_t>> _stop_seqs; std::vector<std::string> _stop_strs;
+    int _stop_reason = -1, _stop_rule = 0;
     bool _dfa_set = false, _dfa_installed = false; std::vector<int32_t> _dfa_row, _dfa_tok, _dfa_nxt;
     bool _shape_set = false; ShapeControls _shape; int _shape_last_n = 0; std::vector<int32_t> _bias_ids; std::vector<float> _bias_values;
 };

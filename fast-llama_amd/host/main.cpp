@@ -3,7 +3,8 @@
 //   ./main -c model.flm -q int8 -i "prompt" [-n 512] [-t 1.0] [-p 0.9] [-j N] [--mode gen|chat|bm] [--rounds R]
 // Extra of this build: --mode score = no generation: the prompt's tokens are scored in one batched pass (flm_score_tokens) -- per position the greedy id and the probability of
 // the next token, then token count, mean loss, perplexity and ms; --device <hip ordinal>; --devices a,b,... = the reference's parallel width (-j, main.cpp:30,78) on GPUs: one
-// sequence sharded over the named devices (split_rows, transformer.cpp:264-287), one host thread per device.
+// sequence sharded over the named devices (split_rows, transformer.cpp:264-287), one host thread per device; --stop-ids / --stop-seq / --stop = stop rules next to the loop's
+// stop on token 0 (flm_stop_rules; one device), with a `finish_reason:` line behind the output (also printed by --mode test).
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -41,9 +42,12 @@ struct Args {
     bool shape_set = false; ShapeControls shape; int repeat_last_n = 64;
     std::vector<int32_t> bias_ids; std::vector<float> bias_values; const char* bad_sampling = nullptr;
     int logprobs_n = -1; bool logprobs_shaped = false; const char* bad_logprobs = nullptr;   // --logprobs N[,shaped]: top-N alternatives per generated token (0..20; -1 = off), from the raw or the shaped row
+    // --stop-ids a,b,... / --stop-seq a,b,... (repeatable) / --stop STR (repeatable): stop rules next to the loop's own stop on token 0
+    std::vector<int32_t> stop_ids; std::vector<std::vector<int32_t>> stop_seqs; std::vector<std::string> stop_strs; const char* bad_stop = nullptr;
     const char* constraint = nullptr;       // --constraint FILE: a token-level DFA in the `flm-dfa 1 <n_states>` text format
     std::vector<int32_t> dfa_row, dfa_tok, dfa_nxt;
     Mode mode = Mode::GEN;
+    bool mode_test = false;                 // --mode test: the benchmark mode under the spelling that also prints the finish reason (benchmark / bm print what they always did)
 };
 const char* Y = "\x1b[33m"; const char* G = "\x1b[32m"; const char* E = "\x1b[0m";
 
@@ -52,7 +56,7 @@ void usage(const char* bin) {
     fprintf(stderr, "   --checkpoint,-c   <string>    the file path of the model checkpoint\n");
     fprintf(stderr, "   --tokenizer,-z    <string>    the file path of the tokenizer\n");
     fprintf(stderr, "   --file-type,-f    <string>    flm | gguf | llama2c\n");
-    fprintf(stderr, "   --mode            <string>    gen | chat | benchmark(bm) | score (this build only: per-token probabilities and the perplexity of the prompt)\n");
+    fprintf(stderr, "   --mode            <string>    gen | chat | benchmark(bm) | score (this build only: per-token probabilities and the perplexity of the prompt) | test (this build only: benchmark, with a `finish_reason:<why>\\trule:<n>` line per round)\n");
     fprintf(stderr, "   --prompt,-i       <string>    the input prompt text\n");
     fprintf(stderr, "   --max-tokens,-n   <integer>   the maximum number of generated tokens\n");
     fprintf(stderr, "   --temperature,-t  <float>     the value for temperature sampling, [0, 1]\n");
@@ -72,6 +76,10 @@ void usage(const char* bin) {
     fprintf(stderr, "   --logit-bias      <id=val[,id=val...]>  added to these tokens' logits; -inf bans a token; at most 256 pairs (this build only)\n");
     fprintf(stderr, "   --constraint      <file>      mask every generated token with a token-level DFA, armed at state 0: a `flm-dfa 1 <n_states>` line, then `state token next` per line (this build only)\n");
     fprintf(stderr, "   --logprobs        <N[,shaped]>  on one device: after the text, one line per generated token `index id logprob | id:logprob ...` with the N (0..20) most likely alternatives, from the model's own distribution or (shaped) the row the sampler read (this build only)\n");
+    fprintf(stderr, "   --stop-ids        <a,b,...>   on one device: end the output at the first of these token ids too (delivered, like token 0), at most 64 distinct ids (this build only)\n");
+    fprintf(stderr, "   --stop-seq        <a,b,...>   on one device: end the output behind this sequence of 1..32 token ids; repeatable, at most 16 sequences with --stop (this build only)\n");
+    fprintf(stderr, "   --stop            <string>    the same for a string, tokenised once without BOS: a token-level match on that one tokenisation; repeatable; a string of more than 32 tokens is reported once the model (its tokenizer) is loaded (this build only)\n");
+    fprintf(stderr, "                                 with any of the three a line `finish_reason:<length|stop_token|stop_id|stop_seq|cancel>\\trule:<n>` follows the output\n");
     fprintf(stderr, "   --encode,-e       <string>    encode the input string into tokens\n");
     fprintf(stderr, "   --decode,-d       <string>    decode the input tokens to text\n");
     fprintf(stderr, "   --help,-h                     print this message\n");
@@ -103,6 +111,16 @@ bool parse_logprobs(const char* v, int& n_out, bool& shaped_out) {   // N or N,s
     if (e == v || n < 0 || n > FLM_LOGPROBS_MAX || (*e != 0 && strcmp(e, ",shaped") != 0)) return false;
     n_out = (int)n; shaped_out = *e != 0;
     return true;
+}
+bool parse_ids(const char* v, size_t max_n, std::vector<int32_t>& out) {      // a comma-separated list of 1 to max_n non-negative ids, nothing else
+    out.clear();
+    bool ok = *v != 0;
+    while (ok && *v) {
+        char* e; const long d = strtol(v, &e, 10);
+        ok = e != v && *v >= '0' && *v <= '9' && d >= 0 && d <= 0x7ffffffe && (*e == 0 || (*e == ',' && e[1] != 0)) && out.size() < max_n;
+        if (ok) { out.push_back((int32_t)d); v = *e ? e + 1 : e; }
+    }
+    return ok;
 }
 bool parse_float(const char* v, float& out) { char* e; const float f = strtof(v, &e); if (e == v || *e != 0) return false; out = f; return true; }
 bool parse_bias(const char* v, std::vector<int32_t>& ids, std::vector<float>& vals) {       // id=val[,id=val...], val a float or -inf, at most 256 pairs
@@ -144,7 +162,7 @@ const Flag kFlags[] = {
     {"-t", "--temperature",    true,  [](Args& a, const char* v) { a.temp = (float)atof(v); }},
     {nullptr, "--seed",        true,  [](Args& a, const char* v) { a.seed = atoi(v); }},
     {nullptr, "--rounds",      true,  [](Args& a, const char* v) { a.rounds = atoi(v); }},
-    {"-m", "--mode",           true,  [](Args& a, const char* v) { pick<Mode>(v, {{"gen", Mode::GEN}, {"generate", Mode::GEN}, {"chat", Mode::CHAT}, {"benchmark", Mode::TEST}, {"bm", Mode::TEST}, {"score", Mode::SCORE}}, a.mode); }},
+    {"-m", "--mode",           true,  [](Args& a, const char* v) { pick<Mode>(v, {{"gen", Mode::GEN}, {"generate", Mode::GEN}, {"chat", Mode::CHAT}, {"benchmark", Mode::TEST}, {"bm", Mode::TEST}, {"test", Mode::TEST}, {"score", Mode::SCORE}}, a.mode); a.mode_test = !strcasecmp(v, "test"); }},
     {nullptr, "--device",      true,  [](Args& a, const char* v) { a.device = atoi(v); }},                                  // (this build only)
     {nullptr, "--devices",     true,  [](Args& a, const char* v) { if (!parse_devices(v, a.devices)) a.bad_devices = v; }},   // (this build only)
     {nullptr, "--lookup",      true,  [](Args& a, const char* v) {                                                            // (this build only)
@@ -160,6 +178,13 @@ const Flag kFlags[] = {
     {nullptr, "--presence-penalty",  true, [](Args& a, const char* v) { a.shape_set = true; if (!parse_float(v, a.shape.presence_penalty) || a.shape.presence_penalty != a.shape.presence_penalty) a.bad_sampling = v; }},               // (this build only)
     {nullptr, "--frequency-penalty", true, [](Args& a, const char* v) { a.shape_set = true; if (!parse_float(v, a.shape.frequency_penalty) || a.shape.frequency_penalty != a.shape.frequency_penalty) a.bad_sampling = v; }},            // (this build only)
     {nullptr, "--logprobs",          true, [](Args& a, const char* v) { if (!parse_logprobs(v, a.logprobs_n, a.logprobs_shaped)) a.bad_logprobs = v; }},                                                                          // (this build only)
+    {nullptr, "--stop-ids",          true, [](Args& a, const char* v) {                                                                                                                                                             // (this build only)
+        std::vector<int32_t> ids; bool ok = parse_ids(v, FLM_STOP_IDS_MAX, ids);
+        for (size_t i = 0; ok && i < ids.size(); ++i) for (size_t k = 0; k < i; ++k) ok = ok && ids[k] != ids[i];
+        for (size_t i = 0; ok && i < ids.size(); ++i) ok = std::find(a.stop_ids.begin(), a.stop_ids.end(), ids[i]) == a.stop_ids.end();
+        if (ok && a.stop_ids.size() + ids.size() <= (size_t)FLM_STOP_IDS_MAX) a.stop_ids.insert(a.stop_ids.end(), ids.begin(), ids.end()); else a.bad_stop = v; }},
+    {nullptr, "--stop-seq",          true, [](Args& a, const char* v) { std::vector<int32_t> q; if (parse_ids(v, FLM_STOP_SEQ_LEN_MAX, q)) a.stop_seqs.push_back(q); else a.bad_stop = v; }},                                       // (this build only)
+    {nullptr, "--stop",              true, [](Args& a, const char* v) { if (*v) a.stop_strs.push_back(v); else a.bad_stop = "--stop with an empty string"; }},                                                                    // (this build only)
     {nullptr, "--constraint",        true, [](Args& a, const char* v) { a.constraint = v; }},                                                                                                                                      // (this build only)
     {nullptr, "--logit-bias",        true, [](Args& a, const char* v) { a.shape_set = true; if (!parse_bias(v, a.bias_ids, a.bias_values)) a.bad_sampling = v; }},                                                                      // (this build only)
 };
@@ -180,6 +205,8 @@ void parse(Args& a, int argc, const char** argv) {
     if (a.bad_draft) { fprintf(stderr, "Invalid --draft:\x1b[31m%s\x1b[0m (expected K or K,G with 4 <= K <= 15 and 1 <= G <= 8)\n", a.bad_draft); usage(argv[0]); exit(-1); }
     if (a.bad_sampling) { fprintf(stderr, "Invalid sampling control:\x1b[31m%s\x1b[0m (--top-k >= 0, --min-p in [0, 1), --repeat-penalty > 0, --repeat-last-n 0..1024, --logit-bias id=val[,id=val...] with at most 256 pairs)\n", a.bad_sampling); usage(argv[0]); exit(-1); }
     if (a.bad_logprobs) { fprintf(stderr, "Invalid --logprobs:\x1b[31m%s\x1b[0m (expected N or N,shaped with 0 <= N <= 20)\n", a.bad_logprobs); usage(argv[0]); exit(-1); }
+    if (!a.bad_stop && a.stop_seqs.size() + a.stop_strs.size() > (size_t)FLM_STOP_SEQS_MAX) a.bad_stop = "more than 16 --stop-seq / --stop";
+    if (a.bad_stop) { fprintf(stderr, "Invalid stop rule:\x1b[31m%s\x1b[0m (--stop-ids a,b,... with at most 64 distinct ids >= 0; --stop-seq a,b,... with 1 to 32 ids >= 0; --stop a non-empty string; at most 16 sequences and strings)\n", a.bad_stop); usage(argv[0]); exit(-1); }
     if (a.rounds < 1) a.rounds = a.mode == Mode::TEST ? 16 : 1;
 }
 
@@ -255,6 +282,11 @@ int main(int argc, const char** argv) {
         fprintf(stderr, "--logprobs applies to one device only: it cannot be combined with --devices of more than one\n");
         return -1;
     }
+    const bool stop_set = !args.stop_ids.empty() || !args.stop_seqs.empty() || !args.stop_strs.empty();
+    if (stop_set && args.devices.size() > 1) {                  // (refused, not ignored: where the output ends is what the caller asked for)
+        fprintf(stderr, "--stop-ids / --stop-seq / --stop apply to one device only: they cannot be combined with --devices of more than one\n");
+        return -1;
+    }
     if (args.constraint) {                  // a malformed file is a usage error, before any model is loaded
         std::string why;
         if (!load_constraint(args.constraint, args, why)) { fprintf(stderr, "Invalid --constraint file:\x1b[31m%s\x1b[0m (%s)\n", args.constraint, why.c_str()); usage(argv[0]); return -1; }
@@ -263,6 +295,7 @@ int main(int argc, const char** argv) {
     if (args.constraint) tf.set_constraint(args.dfa_row, args.dfa_tok, args.dfa_nxt);
     if (args.shape_set) tf.set_sampling(args.shape, args.repeat_last_n, args.bias_ids, args.bias_values);
     if (args.logprobs_n >= 0) tf.set_logprobs(args.logprobs_n, args.logprobs_shaped);
+    if (stop_set) tf.set_stop(args.stop_ids, args.stop_seqs, args.stop_strs);
     if (args.lookup_k) tf.set_lookup(args.lookup_k, args.lookup_g);
     if (args.draft_k) tf.set_draft(args.draft_k, args.draft_g);
     if (!tf.load(args.ckpt, args.tknr, args.ft, args.qtype, args.devices)) { fprintf(stderr, "Failed to load model\n%s\n", tf.error().c_str()); return 1; }
@@ -296,6 +329,10 @@ int main(int argc, const char** argv) {
                 for (int j = 0; j < lp[i].n_top; ++j) printf(" %d:%.9g", (int)lp[i].top_id[j], ((double)lp[i].top_logit[j] - (double)lp[i].max_logit) - log((double)lp[i].sum));
                 printf("\n");
             }
+        }
+        if ((args.mode_test || stop_set) && tf.stop_reason() >= 0) {      // the finish reason (flm_query "stop_reason" / "stop_rule"): --mode test, and wherever stop rules were given
+            static const char* const kReason[] = {"length", "stop_token", "stop_id", "stop_seq", "cancel"};
+            printf("finish_reason:%s\trule:%d\toutput_size:%d\n", kReason[tf.stop_reason() > 4 ? 0 : tf.stop_reason()], tf.stop_rule(), output_tokens);
         }
         sum_prompt_tok += prompt_tokens; sum_output_tok += output_tokens;
         sum_prompt_ms += first_us / 1000.; sum_output_ms += (total_us - first_us) / 1000.;

@@ -373,6 +373,55 @@ int  flm_last_logprobs(flm_ctx* ctx, int first, int n, flm_logprob* out /* [n] *
  * launches enqueued back to back between one pair of HIP events, on the rows and the decode state the last armed _ex call left (each launch rewrites that call's last record
  * with the same bytes).  FLM_ERR_STATE unless the context is armed and its last _ex call delivered ids. */
 int  flm_logprob_stage_time(flm_ctx* ctx, int iters, float* avg_us);
+/* Stop rules on the device: a set of stop ids and up to 16 short stop sequences, next to the entry point's one stop token -- several end ids (a vocabulary's eos, a chat
+ * model's end-of-turn id) and the `stop` strings of the serving APIs, token level.  No reference counterpart (its loop ends on token 0 only).  The decision is taken on the
+ * device in the token's last act, so a call that ends on a rule is as exact about where it ends as one that ends on the stop token; a callback's cancel is not (it lands one
+ * or more tokens behind).
+ *   when a rule fires   take t[0 .. n), the ids THIS call has delivered (the prompt and the ids of earlier calls take no part).  Index i fires when
+ *                 kind 1  t[i] == stop_token, the entry point's own argument;
+ *                 kind 2  t[i] is one of ids; rule = its lowest position in ids;
+ *                 kind 3  some sequence s of length L <= i + 1 has t[i - L + 1 .. i] == seq_s; rule = the lowest such s.
+ *               Several at one index: preferred in that order.  The call ends at the first firing index (and at max_tokens, and behind a cancel, as before).
+ *   the final id  is treated exactly as the stop token: delivered and counted with last = 1, NOT fed -- no K/V row, no further draw.  The earlier ids of a fired sequence
+ *               were ordinary tokens and have their rows: the cache holds pos + n_prompt + *n_out - 1 rows, *rng_state is the state after exactly *n_out draws,
+ *               "constraint_state" is folded over the delivered ids, there is one log-probability record per delivered id.
+ * flm_stop_validate (pure host arithmetic, like flm_dfa_validate): FLM_OK, or FLM_ERR_INVALID with flm_last_error(NULL) naming the rule -- n_ids in [0, FLM_STOP_IDS_MAX],
+ * n_seqs in [0, FLM_STOP_SEQS_MAX]; ids distinct and in [0, vocab); seq_ptr[0] = 0, not decreasing, every length in [1, FLM_STOP_SEQ_LEN_MAX]; sequence tokens in [0, vocab).
+ * flm_stop_match (pure host arithmetic; r may be NULL, stop_token -1: none; the rules are taken as valid): the first index of ids[0 .. n) that fires, with its *kind and
+ * *rule, or n with *kind = FLM_STOP_LENGTH.  The host restatement of the definition (host/stop_rules.h: a direct suffix comparison per index), which the device equals index
+ * for index.
+ * flm_stop_set installs or replaces the rules (NULL, or a set with no id and no sequence: removes them), validated against the model's vocabulary.  A context setting like
+ * flm_constraint_set, but it allocates nothing and re-captures nothing: the rule block has a fixed size (at most 64 + 17 + 512 words and its counts), exists in device memory
+ * since flm_ctx_create, and the shaped token graphs reach it through a pointer captured at flm_prepare; only its contents are rewritten, and a host copy is kept.
+ * FLM_ERR_UNSUPPORTED on a sharded context and where the vocabulary is beyond the device sampler's LDS strip (the shaped form ends in the plain argmax there, which takes no
+ * rules); FLM_ERR_STATE before the model is complete; FLM_ERR_INVALID as flm_stop_validate reports it.  On an error nothing is launched and the installed rules stay.
+ * Where the rules apply: in flm_generate_ex and flm_generate_lookup_ex ONLY.  An installed non-empty rule set counts as a control that is set: with every flm_sampling control
+ * neutral the shaped form still runs and the ids count in "shaped_tokens".  In a draft-and-verify step the accept step cuts the verified run behind the first firing index,
+ * evaluated against the ids the call has delivered followed by the run.  The PLAIN entry points ignore the rules, and so do flm_forward_sample_ex and flm_verify_sample_ex:
+ * their callers hold the ids and call flm_stop_match themselves.
+ * flm_query: "stop_rules" = 1 when rules are installed; "stop_reason" / "stop_rule" describe the last generate-family call (flm_generate, flm_generate_ex, flm_generate_lookup
+ * and its _sample / _ex forms): the host runs flm_stop_match's rule at the last delivered index -- a rule fires there: its kind and rule; otherwise *n_out < max_tokens: cancel;
+ * otherwise length (nothing extra is read back, as for "constraint_state").  The plain forms report reasons 0, 1 and 4.
+ * flm_op_stop_match (op level): flm_stop_match's result through the device function the token form runs (csrc/flm_stop.h), on caller-supplied ids: *first, *kind, *rule.
+ * NOT built: text-level matching across tokenisations, withholding the ids of a partially matched sequence from the callback, min_tokens, tensor-parallel contexts, rules in
+ * the plain entry points or in the one-launch greedy token. */
+#define FLM_STOP_IDS_MAX     64
+#define FLM_STOP_SEQS_MAX    16
+#define FLM_STOP_SEQ_LEN_MAX 32
+typedef struct flm_stop_rules {
+    int32_t n_ids;  const int32_t* ids;            /* distinct, in [0, vocab) */
+    int32_t n_seqs; const int32_t* seq_ptr;        /* [n_seqs + 1], seq_ptr[0] = 0; sequence s = seq_tokens[seq_ptr[s] .. seq_ptr[s + 1]), length 1 .. FLM_STOP_SEQ_LEN_MAX */
+    const int32_t* seq_tokens;                     /* ids in [0, vocab) */
+} flm_stop_rules;
+#define FLM_STOP_LENGTH 0   /* max_tokens reached */
+#define FLM_STOP_TOKEN  1   /* the entry point's stop_token */
+#define FLM_STOP_ID     2   /* one of the rules' ids */
+#define FLM_STOP_SEQ    3   /* one of the rules' sequences */
+#define FLM_STOP_CANCEL 4   /* behind a callback's non-zero return */
+int  flm_stop_validate(const flm_stop_rules* r, int vocab);
+int  flm_stop_match(const flm_stop_rules* r /* may be NULL */, int32_t stop_token, const int32_t* ids, int n, int* kind, int* rule);
+int  flm_stop_set(flm_ctx* ctx, const flm_stop_rules* r /* NULL: remove */);
+int  flm_op_stop_match(const flm_stop_rules* r, int32_t stop_token, const int32_t* ids, int n, int* first, int* kind, int* rule);
 /* the ids generated by the last flm_decode_greedy / flm_decode_sample / flm_decode_timed* call: out[n] (n <= its n_steps) */
 int  flm_last_tokens(flm_ctx* ctx, int n, int32_t* out);
 int  flm_reset_kv(flm_ctx* ctx);
@@ -462,6 +511,8 @@ int  flm_set_option(flm_ctx* ctx, const char* key, int value);
  *   "shaped_tokens" how many tokens this context drew under the controls (flm_generate_ex / flm_forward_sample_ex / flm_verify_sample_ex / flm_generate_lookup_ex with a control set or a constraint armed),
    "constraint_state" the automaton state the context is armed at (flm_constraint_arm; moved on by every _ex call over the ids it delivers), -1: disarmed,
  *   "logprobs_top_n" the top_n the context is armed with for per-token log-probabilities (flm_logprobs_arm), -1: off,
+ *   "stop_rules" 1 = stop rules are installed (flm_stop_set), "stop_reason" / "stop_rule" why the last generate-family call ended (FLM_STOP_LENGTH .. FLM_STOP_CANCEL) and, for
+ *               an id or a sequence, which one,
  *   "spec_steps" / "spec_accepted" the last flm_generate_lookup / flm_generate_lookup_sample call: verify passes run / drafted ids accepted in them,
  *   "gen_tokens" / "gen_streamed" the last flm_generate call: tokens delivered / how many of them were delivered while hipStreamQuery still said the stream was busy,
  *   "epoch_tail" / "epoch_eng" / "epoch_xchg" the epoch counters the cross-workgroup waits count from (device memory; the 32-bit pattern): the one-launch token's, the

@@ -15,7 +15,10 @@ weights, 32 layers by default).  Prints one JSON line:
   * with --logprobs (and nothing else): flm_generate_ex with a bias of +0 (the shaped form) disarmed, and armed with flm_logprobs_arm at top_n 0, 5 and 20 from the raw and
     from the shaped row, alternating; the stage's own duration per launch from HIP events (flm_logprob_stage_time) and the sampler launch it follows (flm_kernel_times'
     class "argmax" on the sampled form is the greedy argmax: the sampled launch's own figure is op_sample's, --ops).  On a library without the feature (the parent commit
-    through FLM_GPU_LIB) only the disarmed figure is measured: the same command gives the pair that shows the disarmed path did not move."""
+    through FLM_GPU_LIB) only the disarmed figure is measured: the same command gives the pair that shows the disarmed path did not move;
+  * with --stop (and nothing else): the shaped token (flm_generate_ex with a bias of +0) with no stop rules installed and with the largest rule set installed -- 64 ids
+    and 16 sequences of 32 ids, none of which ever fires --, alternating, every run's own figure listed (`runs_ms`) so that two commands' spreads can be compared.  On a
+    library without the feature (the parent commit through FLM_GPU_LIB) only the rule-free figure is measured: (i) the parent, (ii) this commit without rules, (iii) with."""
 import argparse
 import importlib.util
 import json
@@ -53,8 +56,47 @@ def main():
     ap.add_argument("--shape", action="store_true", help="time the shaped loop (flm_generate_ex) against the unshaped one (flm_generate) on the same context, nothing else")
     ap.add_argument("--constraint", action="store_true", help="time the shaped token with and without an armed automaton (half the vocabulary allowed), nothing else")
     ap.add_argument("--logprobs", action="store_true", help="time the shaped token disarmed and armed for per-token log-probabilities (top_n 0 / 5 / 20, raw / shaped), nothing else")
+    ap.add_argument("--stop", action="store_true", help="time the shaped token with no stop rules and with the largest rule set (64 ids, 16 sequences of 32) that never fires, nothing else")
     args = ap.parse_args()
     out = {}
+    if args.stop:
+        cfg = synth.make_config("7B", ff.QT_INT8)
+        cfg.n_layers = args.layers
+        ctx = capi.Ctx(capi.desc_from_config(cfg), device=0)
+        _bench_module().upload_synthetic(ctx, cfg)
+        V, K = cfg.vocab_size, args.steps
+        prompt = np.array([1] + [int(x) for x in (np.arange(1, 9) * 7919) % V], np.int32)
+        noop = capi.Sampling(temperature=1.0, topp=0.9, bias={11: 0.0})
+        have = hasattr(capi.lib(), "flm_stop_set")
+        plain = [int(x) for x in ctx.generate_ex(prompt, 0, K, noop, rng_state=1234)[0]]
+        runs = {"no_rules": lambda: ctx.generate_ex(prompt, 0, K, noop, rng_state=1234)}
+        if have:
+            never = [t for t in range(V - 1, 0, -1) if t not in plain][:65]      # 64 ids that do not occur, and one more that every sequence ends in
+            big = capi.StopRules(never[:64], [[plain[(s + j) % K] for j in range(31)] + [never[64]] for s in range(16)])
+
+            def with_rules():
+                ctx.stop_set(big)
+                r = ctx.generate_ex(prompt, 0, K, noop, rng_state=1234)
+                ctx.stop_set(None)
+                return r
+            runs["largest_rules"] = with_rules
+        ts = {k: [] for k in runs}
+        for rep_i in range(args.reps + 1):
+            for name, fn in runs.items():                # alternating: both forms see the same machine
+                ctx.sync(); t0 = time.perf_counter(); ids = fn()[0]; dt = time.perf_counter() - t0
+                assert [int(x) for x in ids] == plain        # rules that never fire change no id
+                if rep_i:
+                    ts[name].append(dt)
+        for name in runs:
+            med = float(np.median(ts[name]))
+            out[f"{name}_us_per_token"] = round(med / K * 1e6, 2)
+            out[f"{name}_runs_ms"] = [round(x * 1e3, 3) for x in ts[name]]
+        if have:
+            out["rules_extra_us_per_token"] = round((np.median(ts["largest_rules"]) - np.median(ts["no_rules"])) / K * 1e6, 2)
+        out["tokens_per_call"] = K; out["prompt_tokens"] = len(prompt); out["layers"] = args.layers; out["feature_present"] = bool(have)
+        ctx.close()
+        print(json.dumps(out), flush=True)
+        return
     if args.logprobs:
         cfg = synth.make_config("7B", ff.QT_INT8)
         cfg.n_layers = args.layers

@@ -14,9 +14,12 @@ same JSON line under "shaped":
    (b") flm_verify_sample_ex fed flm_generate_ex's ids as drafts, B = 5, 8, 16; beside it the unshaped flm_verify_sample pass at the same B in the same run (the
         difference is the parameter block's upload and k_shape_rows over B rows)
    (c") flm_generate_lookup_ex on a prompt that repeats a block of its own shaped continuation: tokens/s, accepted / steps, beside flm_generate_ex's tokens/s
+With --stop (behind (a), nothing else): the accept step with and without stop rules -- flm_generate_lookup_ex at temperature 1, state 1234, a bias of +0, on a prompt that
+repeats a block of its own continuation, with no rules installed (k_spec_accept_sample, one thread) and with the largest rule set that never fires (64 ids, 16 sequences of
+32: k_spec_accept_rules, the workgroup matcher over every id of the run), alternating; the difference per verify step in microseconds, under "stop".
 Exits non-zero unless the ids of (a), (b) and (c) agree -- and, sampled, unless ids and final states agree with flm_generate; shaped, with flm_generate_ex.  Prints one
 JSON line.
-python tools/spec_bench.py [--temperature T] [--topp P] [--shape] [N] [reps] [layers]"""
+python tools/spec_bench.py [--temperature T] [--topp P] [--shape] [--stop] [N] [reps] [layers]"""
 import argparse
 import json
 import os
@@ -32,6 +35,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--temperature", "-t", type=float, default=0.0)
 ap.add_argument("--topp", "-p", type=float, default=0.9)
 ap.add_argument("--shape", action="store_true")
+ap.add_argument("--stop", action="store_true")
 ap.add_argument("N", nargs="?", type=int, default=128)
 ap.add_argument("reps", nargs="?", type=int, default=9)
 ap.add_argument("layers", nargs="?", type=int, default=None)
@@ -51,6 +55,37 @@ ctx.decode_greedy(first, len(seed), 8)                    # warm
 t0 = time.perf_counter(); ids = ctx.decode_greedy(first, len(seed), N); dt_a = time.perf_counter() - t0
 t1_ms = dt_a * 1e3 / N
 res = {"layers": cfg.n_layers, "N": N, "decode_tok_s": round(N / dt_a, 1), "t1_ms": round(t1_ms, 4)}
+
+if opt.stop:
+    noop = capi.Sampling(temperature=1.0, topp=0.9, bias={11: 0.0})
+    ctx.reset_kv()
+    xref, _ = ctx.generate_ex(seed, 0, 32, noop, rng_state=1234)
+    xblock = np.concatenate([seed, xref]).astype(np.int32)
+    xprompt = np.concatenate([xblock, xblock]).astype(np.int32)
+    ctx.reset_kv()
+    want, sw = ctx.generate_ex(xprompt, 0, N, noop, rng_state=1234)
+    seen = set(int(x) for x in want)
+    never = [t for t in range(cfg.vocab_size - 1, 0, -1) if t not in seen][:65]
+    big = capi.StopRules(never[:64], [[int(want[(q + j) % N]) for j in range(31)] + [never[64]] for q in range(16)])
+    ts = {"no_rules": [], "largest_rules": []}
+    steps = {}
+    for r in range(reps + 1):
+        for name in ts:                                   # alternating: both forms see the same machine
+            ctx.stop_set(big if name == "largest_rules" else None)
+            ctx.reset_kv()
+            t0 = time.perf_counter(); got, sg = ctx.generate_lookup_ex(xprompt, 0, N, noop, rng_state=1234, draft_len=7, ngram_max=3); dt = time.perf_counter() - t0
+            ok = ok and np.array_equal(got, want) and sg == sw
+            steps[name] = ctx.query("spec_steps")
+            if r:
+                ts[name].append(dt)
+    ctx.stop_set(None)
+    med = {k: float(np.median(v)) for k, v in ts.items()}
+    res["stop"] = {"lookup_ex_ms": {k: round(v * 1e3, 3) for k, v in med.items()}, "runs_ms": {k: [round(x * 1e3, 3) for x in v] for k, v in ts.items()}, "steps": steps,
+                   "rules_extra_us_per_step": round((med["largest_rules"] - med["no_rules"]) / max(steps["largest_rules"], 1) * 1e6, 2),
+                   "accepted": ctx.query("spec_accepted"), "ids_and_state_agree": bool(ok), "fallback": ctx.query("fallback")}
+    print(json.dumps(res), flush=True)
+    ctx.close()
+    sys.exit(0 if ok else 1)
 
 # (b) one verify pass with every draft right
 def pass_ms(k, gemm):
