@@ -33,6 +33,7 @@ SYMBOLS = (
     "flm_dfa_validate", "flm_constraint_set", "flm_constraint_arm", "flm_op_constrain_rows",
     "flm_logprobs_arm", "flm_last_logprobs", "flm_op_logprob_rows", "flm_logprob_stage_time",
     "flm_stop_validate", "flm_stop_match", "flm_stop_set", "flm_op_stop_match",
+    "flm_draft_set", "flm_generate_draft",
 )
 
 # flm_score (include/flm_gpu.h): one row of flm_score_tokens / flm_op_score_rows
@@ -558,6 +559,23 @@ class Ctx:
         return self._stream(lambda sp, st, cb, out, n_out: lib().flm_generate_lookup_ex(
             self._h, _p(t), len(t), int(pos), int(max_tokens), sp, st, C.c_int32(int(stop_token)), int(draft_len), int(ngram_max), cb, None, out, n_out),
             max_tokens, on_token, want_ids, rng_state, sampling)
+
+    def draft_set(self, draft):
+        """flm_draft_set: pair this (target) context with the draft context `draft` for generate_draft (None: detach).  The target does not own the draft: detach before
+        closing either"""
+        _check(lib().flm_draft_set(self._h, draft._h if draft is not None else None), self._h)
+        self._draft = draft      # (kept alive while attached)
+
+    def generate_draft(self, prompt, pos, max_tokens, sampling, rng_state=0, stop_token=-1, draft_len=7, on_token=None, want_ids=True):
+        """flm_generate_draft -> (ids[n_out], the sampler state after the n_out draws): flm_generate_ex through draft-and-verify steps drafted by the attached draft
+        context.  sampling None: a NULL struct (every control neutral, temperature 0).  on_token(index, token, last) as in generate."""
+        t = np.ascontiguousarray(prompt, dtype=np.int32)
+        ids, st = self._stream(lambda sp, st, cb, out, n_out: lib().flm_generate_draft(
+            self._h, _p(t), len(t), int(pos), int(max_tokens), sp, st, C.c_int32(int(stop_token)), int(draft_len), cb, None, out, n_out),
+            max_tokens, on_token, want_ids, rng_state, sampling)
+        if sampling is None:
+            self._ex_n_out = max(len(ids), 1)
+        return ids, st
 
     def decode_timed(self, first_token, pos, n_steps) -> float:
         ms = C.c_float(0)

@@ -291,14 +291,67 @@ static void stop_note(flm_ctx* c, bool with_rules, int32_t stop_token, const int
     if (n < 1 || !flmhost::stop_fires_at(with_rules ? &v : nullptr, stop_token, ids, n - 1, &kind, &rule)) { kind = n < max_tokens ? FLM_STOP_CANCEL : FLM_STOP_LENGTH; rule = 0; }
     c->stop_reason = kind; c->stop_rule = rule;
 }
+// The model-based drafter (flm_generate_draft): how the target context c and its draft d share the device.  The one-launch token spins on co-resident workgroups, so a
+// launch of one context must never be resident next to a launch of the other (two resident grids: timed-out waits).  The two streams are therefore JOINED around
+// everything the draft enqueues: draft_open -- event [0], recorded on the target's stream, waited for on the draft's: the draft starts behind whatever the target has
+// queued --, the draft's work, draft_close -- event [1], recorded on the draft's stream, waited for on the target's: the target's batch starts behind the draft.  Target ->
+// the NEXT step's draft needs no event: the host reads the step's result block (a synchronise of the target's stream) before it enqueues anything more.
+static int draft_open(flm_ctx* c, flm_ctx* d) {
+    HIPC(c, hipEventRecord(c->draft_ev[0], c->stream));
+    HIPC(c, hipStreamWaitEvent(d->stream, c->draft_ev[0], 0));
+    return FLM_OK;
+}
+static int draft_close(flm_ctx* c, flm_ctx* d) {
+    HIPC(c, hipEventRecord(c->draft_ev[1], d->stream));
+    HIPC(c, hipStreamWaitEvent(c->stream, c->draft_ev[1], 0));
+    return FLM_OK;
+}
+// where the draft's error word lands on the host: the second word of the target's bounce line (d2h puts the target's own into the first), read behind the same synchronise
+static int* draft_err_word(const flm_ctx* c) { return (int*)(c->bounce + c->bounce_bytes + 4); }
+// ... carried there by a copy on the TARGET's stream behind draft_close (the attempts whose batch does not run k_spec_take_drafts, which carries it itself)
+static int draft_err_along(flm_ctx* c, const flm_ctx* d) {
+    hipLaunchKernelGGL(k_copy_words, dim3(1), dim3(64), 0, c->stream, (const unsigned*)d->xwg_err, (unsigned*)draft_err_word(c), 1u, (const unsigned*)nullptr, (unsigned*)nullptr);
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
+// an error of a call made on the draft's behalf is the target's call's error
+static int draft_rc(flm_ctx* c, const flm_ctx* d, int r) { if (r) { c->err = "draft: " + d->err; g_last_error = c->err; } return r; }
+// with_retry for an attempt that ran work of BOTH contexts: a wait that gave up in either re-runs the whole attempt (each context falls back and recovers by its own
+// policy: xwg_check / maybe_recover, untouched); d_tokens: what the draft computed in it.  d null: with_retry
+template <class Body, class Commit>
+static int with_retry_pair(flm_ctx* c, flm_ctx* d, int tokens, int d_tokens, Body body, Commit commit) {
+    if (!d) return with_retry(c, tokens, body, commit);
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        int r = body();
+        if (r) { (void)hipStreamSynchronize(d->stream); (void)hipStreamSynchronize(c->stream); return r; }
+        d->err_word = *(volatile int*)draft_err_word(c); d->err_word_fresh = true;        // (behind the body's read-back, like the target's own)
+        const int rd = xwg_check(d), rc = xwg_check(c);
+        if (rd != FLM_OK && rd != FLM_RETRY) return draft_rc(c, d, rd);
+        if (rc != FLM_OK && rc != FLM_RETRY) return rc;
+        if (rd == FLM_OK && rc == FLM_OK) {
+            commit();
+            r = maybe_recover(c, tokens);
+            return r ? r : draft_rc(c, d, maybe_recover(d, d_tokens));
+        }
+    }
+    return fail(c, FLM_ERR_HIP, "cross-workgroup wait timed out twice");
+}
+
 // One verify pass at `pos` over the batch prompt_dev[0 .. k] (draft: written by the drafter from the history spec_hist[0 .. n_hist) first): all layers, the classifier in
 // chunks, the rows' ids -- drawn by k_sample_rows with the coins of draw.base, at temperature 0 their first maxima --, the accept step, which also leaves the state after
 // the step's draws.  Enqueues only; the result block spec_res is read by the caller.
 // rules (the loop under installed stop rules; null otherwise): the accept step also cuts the run behind the first index a rule fires at (k_spec_accept_rules), evaluated
 // against spec_hist[n_prompt .. n_hist) ++ the run
-static int spec_step(flm_ctx* c, int pos, int k, int ngram_max, int n_hist, int stop, int room, bool draft, const SpecDraw& draw, const StopBlock* rules = nullptr, int n_prompt = 0) {
+// drafter (flm_generate_draft; null otherwise): the batch's drafts are the k ids that context's token loop left in its out_tokens_dev (k_spec_take_drafts, behind the wait
+// on its event: draft_close) instead of the prompt-lookup drafter's; its error word rides along
+static int spec_step(flm_ctx* c, int pos, int k, int ngram_max, int n_hist, int stop, int room, bool draft, const SpecDraw& draw, const StopBlock* rules = nullptr, int n_prompt = 0, const flm_ctx* drafter = nullptr) {
     const int B = k + 1;
-    if (draft) {
+    if (draft && drafter) {
+        hipLaunchKernelGGL(k_spec_take_drafts, dim3(1), dim3(kWave), 0, c->stream, (const int*)c->spec_hist, n_hist, (const int*)drafter->out_tokens_dev, k, c->d.vocab_size, c->prompt_dev,
+                           (const int*)drafter->xwg_err, draft_err_word(c));
+        HIPC(c, hipGetLastError());
+    }
+    else if (draft) {
         hipLaunchKernelGGL(k_spec_draft, dim3(1), dim3(kSampleBlock), 0, c->stream, (const int*)c->spec_hist, n_hist, k, ngram_max, c->prompt_dev);
         HIPC(c, hipGetLastError());
     }
@@ -638,8 +691,18 @@ int flm_verify_sample_ex(flm_ctx* c, int32_t first_token, const int32_t* drafts,
 // behind the prompt; a batch step's rows are shaped by k_shape_rows over the call's history in device memory (spec_hist[0 .. n_hist) ++ the drafts in front of the row, the
 // window flm_generate_ex has at that token); a single-token step runs the shaped token graph with its window written into the block from the ids the host holds (follow 0:
 // set_state has reset the step counter the follow form counts by).  Every step's inputs stay the history below n_hist, launch arguments and the block.
+// The drafter is a parameter: d null = the prompt-lookup drafter above (the six lookup exports: what they enqueue is unchanged); d given (flm_generate_draft, ngram_max
+// unused) = the paired draft context.  Then token 0's attempt also feeds the prompt to the draft (its own draw discarded), and a batch step drafts with the draft's
+// device-resident token loop: joined in front of the target's batch (draft_open / draft_close), first what the draft lacks -- only ever the last draft of a step that
+// accepted them all, which was never fed: one token, its output discarded --, then set_state {last id, at} and draft_len tokens, greedy at temperature 0, else the plain
+// sampled form with the draft's sampler block written with the STEP's base state and the call's temperature / top-p: draft i is drawn with the (i + 1)-th coin, the coin
+// k_sample_rows uses for row i of the batch -- where the two models agree on a row they draw the same id.  The controls, the constraint, the stop rules and the
+// log-probability stage act on the target's rows only.  k_spec_take_drafts turns the draft's out_tokens_dev into the batch; no id goes through the host, and a step keeps
+// its ONE synchronisation.  How many rows the draft has (d_rows) is host-held like n_hist, room and the state, so a re-run step -- after a wait that gave up in EITHER
+// context: with_retry_pair -- enqueues the same work.  Single-token steps run on the target alone; what the draft lacks at the end is fed once before the call returns, so
+// both caches hold pos + n_prompt + *n_out - 1 rows of the same sequence.
 static int generate_lookup_impl(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, int max_tokens, const Draw& dr,
-                                int32_t stop_token, int draft_len, int ngram_max, flm_token_cb cb, void* user, int32_t* out_tokens, int* n_out) {
+                                int32_t stop_token, int draft_len, int ngram_max, flm_token_cb cb, void* user, int32_t* out_tokens, int* n_out, flm_ctx* d = nullptr) {
     if (!c || !prompt || !n_out) return FLM_ERR_INVALID;
     if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "generate_lookup: one GPU only");
     if (max_tokens < 1 || !(dr.temperature >= 0.0f) || dr.topp != dr.topp || stop_token >= c->d.vocab_size || draft_len < 4 || draft_len > 15 || ngram_max < 1 || ngram_max > 8)
@@ -647,8 +710,15 @@ static int generate_lookup_impl(flm_ctx* c, const int32_t* prompt, int n_prompt,
     int r = check_ready(c, n_prompt, pos); if (r) return r;
     if (pos + n_prompt + max_tokens - 1 > c->d.max_seq_len || max_tokens > c->out_cap) return fail(c, FLM_ERR_INVALID, "generate_lookup: pos + n_prompt + max_tokens - 1 exceeds max_seq_len");
     if (!ids_in_vocab(c, prompt, n_prompt)) return fail(c, FLM_ERR_INVALID, "token id out of range");
+    if (d) {
+        if (!model_complete(d)) return fail(c, FLM_ERR_STATE, "generate_draft: the draft model is not complete");
+        if (pos + n_prompt + max_tokens - 1 > d->d.max_seq_len) return fail(c, FLM_ERR_INVALID, "generate_draft: pos + n_prompt + max_tokens - 1 exceeds the draft's max_seq_len");
+        d->err_word_fresh = false;
+    }
     const bool sampled = dr.coins();
     if (sampled) { r = sample_args_ok(c, dr.temperature, dr.topp, dr.rng_state); if (r) return r; }
+    const TokenForm d_form = dr.temperature != 0.0f ? TokenForm::Sampled : TokenForm::Greedy;      // the draft's plain form
+    int d_rows = pos, d_tokens = 0;                                  // draft: the cache rows it holds of this sequence / tokens it computed in this call
     const int stop = stop_token < 0 ? -1 : stop_token;
     int total = 0, steps = 0, accepted = 0; bool done = false, cancelled = false;
     int32_t last_tok = 0;
@@ -672,21 +742,36 @@ static int generate_lookup_impl(flm_ctx* c, const int32_t* prompt, int n_prompt,
         done = so.stopped || total >= max_tokens || cancelled;
     };
     // token 0: the prompt, exactly as flm_forward_argmax / flm_forward_sample feeds it; the history starts as the prompt and that id
-    r = with_retry(c, n_prompt, [&]() -> int {
+    r = with_retry_pair(c, d, n_prompt, n_prompt, [&]() -> int {
         int r = dr.arm(c); if (r) return r;
+        if (d) {       // the draft feeds the same prompt at the same position, in front of the target (the streams joined: draft_open); its own draw is discarded
+            r = draft_open(c, d); if (r) return r;
+            r = draft_rc(c, d, feed(d, prompt, n_prompt, pos, TokenForm::Greedy)); if (r) return r;
+            r = draft_close(c, d); if (r) return r;
+        }
         r = feed(c, prompt, n_prompt, pos, dr.form); if (r) return r;
         hipLaunchKernelGGL(k_spec_begin, dim3(1), dim3(rules ? kSampleBlock : 256), 0, c->stream, c->spec_hist, (const int*)c->prompt_dev, n_prompt, (const int*)c->out_tokens_dev, c->spec_res, stop, (unsigned long long)state, sampled ? 1 : 0, rules);
         HIPC(c, hipGetLastError());
+        if (d) { r = draft_err_along(c, d); if (r) return r; }
         return d2h(c, &so, c->spec_res, sizeof so);
-    }, deliver);
+    }, [&] { if (d) { d_rows = pos + n_prompt; d_tokens += n_prompt; } deliver(); });
     if (r) return r;
     while (!done) {
         const int at = pos + n_prompt + total - 1, room = max_tokens - total, n_hist = n_prompt + total;       // the last id is fed at `at`
-        const bool batch = room >= 2 && at + draft_len + 1 <= c->d.max_seq_len;
-        r = with_retry(c, batch ? draft_len + 1 : 1, [&]() -> int {
+        const bool batch = room >= 2 && at + draft_len + 1 <= c->d.max_seq_len && (!d || at + draft_len <= d->d.max_seq_len);
+        const int d_lacks = d && batch ? at - d_rows : 0;                // rows the draft has to feed in front of its drafts (the ids the host holds: drawn)
+        r = with_retry_pair(c, batch ? d : nullptr, batch ? draft_len + 1 : 1, d_lacks + draft_len, [&]() -> int {
             int r;
+            if (batch && d) {       // the draft's side of the step, joined in front of the target's batch; nothing of it is copied back
+                r = draft_open(c, d); if (r) return r;
+                if (d_lacks > 0) { r = draft_rc(c, d, feed(d, drawn + (d_rows - pos - n_prompt), d_lacks, d_rows, TokenForm::Greedy)); if (r) return r; }
+                if (sampled) { r = draft_rc(c, d, set_sample(d, dr.temperature, dr.topp, (unsigned long long)state)); if (r) return r; }
+                r = draft_rc(c, d, set_state(d, at, last_tok, 0)); if (r) return r;
+                r = draft_rc(c, d, run_tokens(d, at, draft_len, d_form)); if (r) return r;
+                r = draft_close(c, d); if (r) return r;
+            }
             if (batch) {       // (the block: as token 0's attempt left it; the rows' windows: the history; records land behind the ids delivered so far)
-                r = spec_step(c, at, draft_len, ngram_max, n_hist, stop, room, true, dr.batch(c, state, c->spec_hist, n_hist, cst, total), rules, n_prompt);
+                r = spec_step(c, at, draft_len, ngram_max, n_hist, stop, room, true, dr.batch(c, state, c->spec_hist, n_hist, cst, total), rules, n_prompt, d);
             }
             else {      // one token through the token graph and the accept kernel with K = 0: the id from the decode state's first output slot, cut / appended / counted like a verified run of one
                 // (its window, as given: the last min(last_n, n_hist) ids of prompt ++ drawn[0 .. total); the constraint's block: {the folded state, 0}; the record stage's: step 0 is record `total`)
@@ -700,8 +785,23 @@ static int generate_lookup_impl(flm_ctx* c, const int32_t* prompt, int n_prompt,
             }
             if (r) return r;
             return d2h(c, &so, c->spec_res, sizeof so);
-        }, [&] { if (batch) { steps += 1; accepted += so.n_emit - 1; } deliver(); });
+        }, [&] {
+            if (batch) { steps += 1; accepted += so.n_emit - 1; }
+            // (the draft fed the last id and its first draft_len - 1 drafts: of the rows behind `at` as many are this sequence's as ids were delivered, draft_len at the most)
+            if (batch && d) { d_rows = at + (so.n_emit < draft_len ? so.n_emit : draft_len); d_tokens += d_lacks + draft_len; }
+            deliver();
+        });
         if (r) return r;
+    }
+    if (d) {       // the draft is caught up before the call returns: what it lacks of pos + n_prompt + total - 1 rows, fed once (the target's stream is idle behind the last read-back)
+        const int need = pos + n_prompt + total - 1, n = need - d_rows;
+        if (n > 0) {
+            r = with_retry(d, n, [&]() -> int { return feed(d, drawn + (d_rows - pos - n_prompt), n, d_rows, TokenForm::Greedy); });
+            if (r) return draft_rc(c, d, r);
+            d_tokens += n;
+        }
+        HIPC(c, hipStreamSynchronize(d->stream));
+        c->draft_tokens = d_tokens;
     }
     *n_out = total;
     dr.commit(c, total, state, cst);
@@ -729,6 +829,22 @@ int flm_generate_lookup_ex(flm_ctx* c, const int32_t* prompt, int n_prompt, int 
     Draw dr;
     if (int r = draw_resolve(c, sampling, prompt + (n_prompt - tail), tail, true, rng_state, dr, NoOwn(), true)) return r;
     return generate_lookup_impl(c, prompt, n_prompt, pos, max_tokens, dr, stop_token, draft_len, ngram_max, cb, user, out_tokens, n_out);
+}
+// flm_generate_lookup_ex with the paired draft context (flm_draft_set) as the drafter: the same loop, the same plan.  sampling null: every control neutral at temperature 0.
+int flm_generate_draft(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, int max_tokens, const flm_sampling* sampling, uint64_t* rng_state, int32_t stop_token,
+                       int draft_len, flm_token_cb cb, void* user, int32_t* out_tokens, int* n_out) {
+    if (!c || !prompt || !n_out) return FLM_ERR_INVALID;
+    c->lp_count = -1;
+    if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "generate_draft: one GPU only");
+    flm_ctx* const d = c->draft;
+    if (!d) return fail(c, FLM_ERR_STATE, "generate_draft: no draft context attached (flm_draft_set)");
+    if (n_prompt < 1 || n_prompt > c->d.max_seq_len) return fail(c, FLM_ERR_INVALID, "tokens/pos outside [0, max_seq_len]");
+    if (!ids_in_vocab(c, prompt, n_prompt)) return fail(c, FLM_ERR_INVALID, "token id out of range");
+    const int tail = n_prompt < FLM_PENALTY_WINDOW_MAX ? n_prompt : FLM_PENALTY_WINDOW_MAX;
+    flm_sampling neutral{}; neutral.repeat_penalty = 1.0f;
+    Draw dr;
+    if (int r = draw_resolve(c, sampling ? sampling : &neutral, prompt + (n_prompt - tail), tail, true, rng_state, dr, NoOwn(), true)) return r;
+    return generate_lookup_impl(c, prompt, n_prompt, pos, max_tokens, dr, stop_token, draft_len, 1, cb, user, out_tokens, n_out, d);
 }
 
 // Constrained decoding (include/flm_gpu.h): the automaton lives in ONE device allocation made here, off the steady path; the shaped token graphs reach it through the block

@@ -559,6 +559,7 @@ void flm_ctx_destroy(flm_ctx* c) {
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
     drop_graphs(c, false);
+    for (hipEvent_t& e : c->draft_ev) if (e) { hipEventDestroy(e); e = nullptr; }       // (a pairing the caller did not detach: the events are this context's, the draft is not)
     for (int r = 0; r < c->world; ++r) if (c->peer_opened[r] && c->peer[r]) hipIpcCloseMemHandle(c->peer[r]);
     for (void* p : c->owned) hipFree(p);
     for (void* p : {c->emb, (void*)c->emb_s, (void*)c->trace, (void*)c->dfa_dev}) if (p) hipFree(p);          // (re-allocated during the context's life: flm_upload_tensor, option "trace", flm_constraint_set)
@@ -568,6 +569,31 @@ void flm_ctx_destroy(flm_ctx* c) {
     if (c->comm) ncclCommDestroy(c->comm);
     if (c->stream) hipStreamDestroy(c->stream);
     delete c;
+}
+
+// Pair a target context with a draft context for flm_generate_draft (include/flm_gpu.h).  Everything the pairing needs beyond what both contexts hold since
+// flm_ctx_create is made HERE -- the two events that order the two streams --, so the call itself allocates nothing.  The draft's error word reaches the host through the
+// second word of the target's bounce line (there since create); the hand-off kernel reads the draft's ids where its token loop leaves them.  No graph of either context
+// depends on the pairing: attaching, re-attaching and detaching capture nothing.  The target does not own the draft: the caller detaches before destroying either.
+int flm_draft_set(flm_ctx* c, flm_ctx* draft) {
+    if (!c) return FLM_ERR_INVALID;
+    if (draft) {
+        if (draft == c) return fail(c, FLM_ERR_INVALID, "draft_set: a context cannot draft for itself");
+        if (sharded(c) || sharded(draft)) return fail(c, FLM_ERR_UNSUPPORTED, "draft_set: one GPU only (both contexts)");
+        if (draft->device != c->device) return fail(c, FLM_ERR_UNSUPPORTED, "draft_set: the draft lives on another device");
+        if (draft->d.vocab_size != c->d.vocab_size) return fail(c, FLM_ERR_INVALID, "draft_set: the two vocabularies differ in size");
+        if (!model_complete(c) || !model_complete(draft)) return fail(c, FLM_ERR_STATE, "draft_set before all tensors of both models were uploaded");
+    }
+    HIPC(c, hipSetDevice(c->device));
+    HIPC(c, hipStreamSynchronize(c->stream));
+    if (draft) {
+        HIPC(c, hipStreamSynchronize(draft->stream));
+        for (hipEvent_t& e : c->draft_ev) if (!e) HIPC(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    } else {
+        for (hipEvent_t& e : c->draft_ev) if (e) { HIPC(c, hipEventDestroy(e)); e = nullptr; }
+    }
+    c->draft = draft;
+    return FLM_OK;
 }
 
 // ---- tensor parallel, peer-to-peer bootstrap ---------------------------------------------------
@@ -828,6 +854,7 @@ int flm_query(flm_ctx* c, const char* key, int* value) {
         {"gen_streamed", c->gen_streamed},
         {"spec_steps", c->spec_steps},
         {"spec_accepted", c->spec_accepted},
+        {"draft_tokens", c->draft_tokens},
         // which hand-offs of the token's launch (short contexts) are consumed in arrival order; -1: that launch was not planned (yet)
         {"ao_active", c->la_ok[0] ? (c->la_p[0].ao_o ? 1 : 0) | (c->la_p[0].ao_2 ? 2 : 0) : -1},
         {"token_path", (c->world == 1 ? path : 0) | (c->attn_split ? 64 : 0)},

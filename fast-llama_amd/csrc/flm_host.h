@@ -188,6 +188,11 @@ struct flm_ctx {
     int* spec_hist = nullptr; int* spec_arg = nullptr; flm::SpecOut* spec_res = nullptr;
     int spec_gemm = 0;                                 // option "spec_gemm": 1 = the verify pass's int8 GEMMs through k_gemm_q8_skinny (B <= 16), 0 (default until both forms have been timed: DESIGN.md section 5e) = the 64 x 64 tiles; the new entry points only
     int spec_steps = 0, spec_accepted = 0;
+    // the model-based drafter (include/flm_gpu.h flm_draft_set / flm_generate_draft; flm_calls.hip generate_lookup_impl): the paired draft context (not owned; null: none),
+    // the two events that order its stream and this one -- [0] recorded here, waited for there, in front of everything the draft enqueues; [1] recorded there, waited for
+    // here, behind it -- created by flm_draft_set, and how many tokens the draft computed in the last call ("draft_tokens").  The draft's error word travels to the second
+    // word of this context's bounce line (bounce + bounce_bytes + 4), next to its own
+    flm_ctx* draft = nullptr; hipEvent_t draft_ev[2] = {nullptr, nullptr}; int draft_tokens = 0;
     // per-token log-probabilities (include/flm_gpu.h flm_logprobs_arm; the stage: flm_logprob.h): the armed setting (top_n -1: off; "logprobs_top_n") and its device block,
     // the records [max_seq_len] with their attempt tags, and the side rows [16][vocab] a verify batch is shaped into when the raw rows must survive -- all device memory
     // since create (null where the context is sharded or the vocabulary is beyond the sampler: arming refuses there).  lp_count: the records the last _ex call left

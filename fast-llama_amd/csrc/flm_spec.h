@@ -9,6 +9,7 @@
 //                  passes through untouched;
 //   otherwise:     k_sample_rows (flm_sample.h) draws row i with the (i + 1)-th coin of the step's xorshift state, i.e. Sampler::sample as the sampled decode loop calls
 //                  it for its i-th token.  The ids are flm_decode_sample's element for element; nothing is rejected or re-drawn.
+// With a draft MODEL as the drafter (flm_generate_draft) k_spec_take_drafts takes k_spec_draft's place: the batch's drafts are the ids a second context's token loop drew.
 #pragma once
 #include "flm_sample.h"
 
@@ -47,6 +48,20 @@ inline __global__ void __launch_bounds__(kSampleBlock) k_spec_draft(const int* _
         if (best) { const int e = (int)(best & 0xffffffu), p = n - e; v = h[e + t % p]; }
         batch[1 + t] = v;
     }
+}
+
+// The model-based drafter's hand-off (flm_generate_draft): the K ids a DRAFT context's device-resident token loop left in its out_tokens_dev become the verify batch of the
+// target, in the layout k_spec_draft leaves -- batch[0] = h[n - 1], batch[1 + i] = draft_out[i], i < K -- so everything behind it is the lookup loop's.  Runs on the
+// target's stream behind a wait on the draft's event; no draft id travels to the host.  An id outside [0, vocab) (impossible with a sound draft of the same vocabulary) is
+// replaced by h[n - 1]: a re-run step never indexes the embedding out of range, and a wrong draft costs acceptance, never an id.  err_src -> err_dst: the draft context's
+// "a cross-workgroup wait gave up" word rides along to the target's page-locked line, where the host finds it behind the step's ONE read-back.  One wave.
+inline __global__ void __launch_bounds__(kWave) k_spec_take_drafts(const int* __restrict__ h, int n, const int* __restrict__ draft_out, int K, int vocab, int* __restrict__ batch,
+                                                                   const int* __restrict__ err_src, int* __restrict__ err_dst) {
+    const int t = threadIdx.x;
+    if (blockIdx.x != 0) return;
+    const int last = h[n - 1];
+    if (t == 0) { batch[0] = last; if (err_src) *err_dst = *err_src; }
+    if (t < K) { const int d = draft_out[t]; batch[1 + t] = d >= 0 && d < vocab ? d : last; }
 }
 
 // a[r] = the first maximum of row r of logits[rows][ld], n entries: one workgroup of 1024 threads per row

@@ -13,7 +13,27 @@
 
 namespace flmhost {
 
-GpuTransformer::~GpuTransformer() { for (flm_ctx* c : _ctxs) if (c) flm_ctx_destroy(c); }
+GpuTransformer::~GpuTransformer() {
+    if (_draft_ctx) { if (!_ctxs.empty() && _ctxs[0]) flm_draft_set(_ctxs[0], nullptr); flm_ctx_destroy(_draft_ctx); }      // (detached first: the target does not own it)
+    for (flm_ctx* c : _ctxs) if (c) flm_ctx_destroy(c);
+}
+
+// --draft-model: a second model on the target's device, in a context of its own, paired with the target (flm_draft_set checks the vocabulary)
+bool GpuTransformer::load_draft(const std::string& ckpt, const std::string& tknr, FileType ft, int qtype, int device) {
+    if (_ctxs.size() != 1 || !_ctxs[0]) { _err = "--draft-model: one device only, and the model is loaded first"; return false; }
+    ModelFile mf;
+    if (!load_model_file(ckpt, tknr, ft, false, _debug, mf, _err)) { _err = "--draft-model: " + _err; return false; }
+    Config cfg = mf.cfg;
+    if (cfg.quant_type == 0) cfg.quant_type = qtype;           // the file's quant type wins over -q, as for the model itself
+    flm_model_desc d{};
+    d.dim = cfg.dim; d.hidden_dim = cfg.hidden_dim; d.n_layers = cfg.n_layers; d.n_heads = cfg.n_heads; d.n_kv_heads = cfg.n_kv_heads;
+    d.vocab_size = cfg.vocab_size; d.max_seq_len = _cfg.max_seq_len; d.quant_type = cfg.quant_type; d.quant_group_size = cfg.quant_group_size;
+    if (flm_ctx_create(&d, device, 0, 1, nullptr, &_draft_ctx) != FLM_OK) { _err = std::string("--draft-model: GPU context: ") + flm_last_error(nullptr); _draft_ctx = nullptr; return false; }
+    for (const HostTensor& t : mf.tensors)
+        if (flm_upload_tensor(_draft_ctx, t.kind, t.layer, t.qtype, t.values, t.scales, t.rows, t.cols) != FLM_OK) { _err = std::string("--draft-model: upload: ") + flm_last_error(_draft_ctx); return false; }
+    if (flm_draft_set(_ctxs[0], _draft_ctx) != FLM_OK) { _err = std::string("--draft-model: ") + flm_last_error(_ctxs[0]); flm_ctx_destroy(_draft_ctx); _draft_ctx = nullptr; return false; }
+    return true;
+}
 
 int GpuTransformer::on_all(const std::function<int(int)>& f) {
     const int n = (int)_ctxs.size();
@@ -271,7 +291,11 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
             sp.n_bias = _shape.n_bias; sp.bias_ids = _shape.bias_ids; sp.bias_values = _shape.bias_values;
             // with --draft (any temperature) / --lookup (temperature 0): the same ids through draft-and-verify steps whose rows are shaped each over its own window
             // (flm_generate_lookup_ex); refused as unsupported (nothing was launched): the token loop
-            if (_draft_k > 0 || (greedy && _lookup_k > 0)) {
+            if (_draft_ctx) {       // --draft-model: the same ids with the draft model as the drafter (flm_generate_draft), at any temperature
+                rc = flm_generate_draft(_ctxs[0], input.data(), n_in, 0, want, &sp, &st, 0, _draft_k > 0 ? _draft_k : 7, on_token, &sink, nullptr, &n_out);
+                count();
+            }
+            else if (_draft_k > 0 || (greedy && _lookup_k > 0)) {
                 const bool draft = _draft_k > 0;
                 rc = flm_generate_lookup_ex(_ctxs[0], input.data(), n_in, 0, want, &sp, &st, 0, draft ? _draft_k : _lookup_k, draft ? _draft_g : _lookup_g, on_token, &sink, nullptr, &n_out);
                 count();
@@ -285,6 +309,13 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
                 if (flm_last_logprobs(_ctxs[0], 0, n_out, _lp.data()) != FLM_OK) { _err = std::string("--logprobs: ") + flm_last_error(_ctxs[0]); _lp.clear(); return false; }
             }
             whole = false;
+        } else if (dev_ok && _draft_ctx) {
+            // --draft-model: the plain loop's ids through draft-and-verify steps drafted by the draft model; refused as unsupported (nothing was launched): the run without the flag
+            flm_sampling sp{};
+            sp.temperature = temperature; sp.topp = topp; sp.repeat_penalty = 1.0f;
+            rc = flm_generate_draft(_ctxs[0], input.data(), n_in, 0, want, &sp, &st, 0, _draft_k > 0 ? _draft_k : 7, on_token, &sink, nullptr, &n_out);
+            count();
+            whole = rc == FLM_ERR_UNSUPPORTED;
         } else if (dev_ok && (_draft_k > 0 || (greedy && _lookup_k > 0))) {
             // --draft: the same loop through draft-and-verify steps at the run's temperature; refused (nothing was launched): the run without the flag.
             // --lookup: the same at temperature 0 only (the same ids and callbacks)

@@ -39,6 +39,11 @@ public:
     // --draft K[,G] (this build only): the same at whatever temperature the run has: at 0 flm_generate_lookup, otherwise flm_generate_lookup_sample with the Sampler's state (written
     // back afterwards) -- the same ids as the sampled loop's; where the library refuses (FLM_ERR_UNSUPPORTED) the run is what it is without the flag.  Counted in lookup_steps / _accepted
     void set_draft(int draft_len, int ngram_max) { _draft_k = draft_len; _draft_g = ngram_max; }
+    // --draft-model FILE (this build only; one device, after load): a second, small model of the same vocabulary on the same device (the quantisation: the file's own or -q),
+    // paired with the model through flm_draft_set.  Generation then runs through flm_generate_draft -- draft-and-verify with that model as the drafter, draft length --draft K
+    // (7 without the flag), at any temperature and under every control flag: the same ids and text as the run without the flag; where the library refuses the call as
+    // unsupported the run is what it is without the flag.  Counted in lookup_steps / _accepted.  A missing or malformed file, another vocabulary size: false, error() says why
+    bool load_draft(const std::string& ckpt, const std::string& tknr, FileType ft, int qtype, int device);
     // --top-k / --min-p / --repeat-penalty / --repeat-last-n / --presence-penalty / --frequency-penalty / --logit-bias (this build only): the sampling controls of flm_sampling.
     // One device: the whole loop is flm_generate_ex (the shaping stage on the device); where the engine samples on the host (a vocabulary beyond the device sampler, several
     // devices) it calls shape_logits in front of the host sampler: the same ids.  --lookup / --draft: flm_generate_lookup_ex, the same ids through draft-and-verify steps.
@@ -91,6 +96,7 @@ private:
     std::string _err;
     int _lookup_k = 0, _lookup_g = 3, _lookup_steps = 0, _lookup_accepted = 0;
     int _draft_k = 0, _draft_g = 3;
+    flm_ctx* _draft_ctx = nullptr;                  // --draft-model: the draft model's context (owned here; the target context only refers to it)
     int _lp_top_n = -1; bool _lp_shaped = false; std::vector<flm_logprob> _lp;
     bool _stop_set = false, _stop_installed = false; std::vector<int32_t> _stop_ids; std::vector<std::vector<int32_t>> _stop_seqs; std::vector<std::string> _stop_strs;
     int _stop_reason = -1, _stop_rule = 0;

@@ -4,7 +4,8 @@
 // Extra of this build: --mode score = no generation: the prompt's tokens are scored in one batched pass (flm_score_tokens) -- per position the greedy id and the probability of
 // the next token, then token count, mean loss, perplexity and ms; --device <hip ordinal>; --devices a,b,... = the reference's parallel width (-j, main.cpp:30,78) on GPUs: one
 // sequence sharded over the named devices (split_rows, transformer.cpp:264-287), one host thread per device; --stop-ids / --stop-seq / --stop = stop rules next to the loop's
-// stop on token 0 (flm_stop_rules; one device), with a `finish_reason:` line behind the output (also printed by --mode test).
+// stop on token 0 (flm_stop_rules; one device), with a `finish_reason:` line behind the output (also printed by --mode test); --draft-model FILE = a second, small model of
+// the same vocabulary drafts for the loop (flm_generate_draft; one device): the same text, several tokens per pass over the weights where the two models agree.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -38,6 +39,7 @@ struct Args {
     const char* bad_lookup = nullptr;
     int draft_k = 0, draft_g = 3;           // --draft K[,G]: the same drafter and ranges at whatever temperature the run has (-t 0: flm_generate_lookup, else flm_generate_lookup_sample)
     const char* bad_draft = nullptr;
+    std::string draft_model;                // --draft-model FILE: a small model of the same vocabulary drafts instead of the prompt lookup (flm_generate_draft; K of --draft, 7 without it)
     // the sampling controls (flm_sampling): any of these flags switches the shaping stage on
     bool shape_set = false; ShapeControls shape; int repeat_last_n = 64;
     std::vector<int32_t> bias_ids; std::vector<float> bias_values; const char* bad_sampling = nullptr;
@@ -67,6 +69,7 @@ void usage(const char* bin) {
     fprintf(stderr, "   --devices         <a,b,...>   shard ONE sequence over these HIP devices, 1 to 8 of them (this build only)\n");
     fprintf(stderr, "   --lookup          <K[,G]>     with -t 0 on one device: draft K (4..15) tokens per step by prompt lookup (n-grams up to G, 1..8, default 3) and verify them in one pass; the same text (this build only)\n");
     fprintf(stderr, "   --draft           <K[,G]>     on one device, at any temperature: draft K (4..15) tokens per step by prompt lookup (n-grams up to G, 1..8, default 3) and verify them in one pass, sampled rows drawn with the sampler's own coins; the same text (this build only)\n");
+    fprintf(stderr, "   --draft-model     <file>      on one device, at any temperature: a second, small model of the same vocabulary (quantisation: the file's own or -q) drafts the K tokens of --draft (default 7) instead of the prompt lookup; the same text (this build only)\n");
     fprintf(stderr, "   --top-k           <integer>   keep the K most likely tokens, 0 = off (this build only)\n");
     fprintf(stderr, "   --min-p           <float>     drop tokens whose probability is below this fraction of the most likely one's, [0, 1), 0 = off (this build only)\n");
     fprintf(stderr, "   --repeat-penalty  <float>     penalise the tokens of the last --repeat-last-n ids, > 0, 1 = off (this build only)\n");
@@ -171,6 +174,7 @@ const Flag kFlags[] = {
         if (ok && *e == ',') { const char* s = e + 1; g = strtol(s, &e, 10); ok = e != s && g >= 1 && g <= 8; }
         if (ok && *e == 0) { a.lookup_k = (int)k; a.lookup_g = (int)g; } else a.bad_lookup = v; }},
     {nullptr, "--draft",       true,  [](Args& a, const char* v) { if (!parse_draft(v, a.draft_k, a.draft_g)) a.bad_draft = v; }},                 // (this build only)
+    {nullptr, "--draft-model", true,  [](Args& a, const char* v) { a.draft_model = v; }},                                                                                          // (this build only)
     {nullptr, "--top-k",             true, [](Args& a, const char* v) { char* e; const long k = strtol(v, &e, 10); a.shape_set = true; if (e == v || *e || k < 0 || k > 0x7fffffff) a.bad_sampling = v; else a.shape.top_k = (int)k; }},   // (this build only)
     {nullptr, "--min-p",             true, [](Args& a, const char* v) { a.shape_set = true; if (!parse_float(v, a.shape.min_p) || !(a.shape.min_p >= 0.f && a.shape.min_p < 1.f)) a.bad_sampling = v; }},                              // (this build only)
     {nullptr, "--repeat-penalty",    true, [](Args& a, const char* v) { a.shape_set = true; if (!parse_float(v, a.shape.repeat_penalty) || !(a.shape.repeat_penalty > 0.f) || a.shape.repeat_penalty == INFINITY) a.bad_sampling = v; }},   // (this build only)
@@ -278,6 +282,10 @@ int main(int argc, const char** argv) {
         fprintf(stderr, "warning: --draft applies to one device only; ignored\n");
         args.draft_k = 0;
     }
+    if (!args.draft_model.empty() && args.devices.size() > 1) {
+        fprintf(stderr, "warning: --draft-model applies to one device only; ignored\n");
+        args.draft_model.clear();
+    }
     if (args.logprobs_n >= 0 && args.devices.size() > 1) {      // (refused, not ignored: the lines are what the caller asked for)
         fprintf(stderr, "--logprobs applies to one device only: it cannot be combined with --devices of more than one\n");
         return -1;
@@ -291,6 +299,11 @@ int main(int argc, const char** argv) {
         std::string why;
         if (!load_constraint(args.constraint, args, why)) { fprintf(stderr, "Invalid --constraint file:\x1b[31m%s\x1b[0m (%s)\n", args.constraint, why.c_str()); usage(argv[0]); return -1; }
     }
+    if (!args.draft_model.empty()) {        // a file that cannot be read is a usage error, before any model is loaded
+        FILE* f = fopen(args.draft_model.c_str(), "rb");
+        if (!f) { fprintf(stderr, "Invalid --draft-model file:\x1b[31m%s\x1b[0m (cannot open the file)\n", args.draft_model.c_str()); usage(argv[0]); return -1; }
+        fclose(f);
+    }
     GpuTransformer tf(args.detail || args.debug);
     if (args.constraint) tf.set_constraint(args.dfa_row, args.dfa_tok, args.dfa_nxt);
     if (args.shape_set) tf.set_sampling(args.shape, args.repeat_last_n, args.bias_ids, args.bias_values);
@@ -299,6 +312,7 @@ int main(int argc, const char** argv) {
     if (args.lookup_k) tf.set_lookup(args.lookup_k, args.lookup_g);
     if (args.draft_k) tf.set_draft(args.draft_k, args.draft_g);
     if (!tf.load(args.ckpt, args.tknr, args.ft, args.qtype, args.devices)) { fprintf(stderr, "Failed to load model\n%s\n", tf.error().c_str()); return 1; }
+    if (!args.draft_model.empty() && !tf.load_draft(args.draft_model, args.tknr, args.ft, args.qtype, args.devices[0])) { fprintf(stderr, "Failed to load the draft model\n%s\n", tf.error().c_str()); return 1; }
     args.qtype = tf.get_quant_type();
     if (args.detail) fprintf(stderr, "Model loaded\n\n");
 
@@ -346,7 +360,8 @@ int main(int argc, const char** argv) {
            Y, args.num_threads, E, G, qn, E, G, (int)args.use_numa, E, 64, (int)pt, (int)ot, pm + om,
            Y, first_lat, E, Y, later_lat, E, G, 1000. / first_lat, E, G, 1000. / later_lat, E);
     if (args.lookup_k) printf("\tlookup:%d,%d\taccepted/steps:%s%d/%d%s", args.lookup_k, args.lookup_g, G, tf.lookup_accepted(), tf.lookup_steps(), E);   // (--lookup only: without it the line is the reference's)
-    if (args.draft_k) printf("\tdraft:%d,%d\taccepted/steps:%s%d/%d%s", args.draft_k, args.draft_g, G, tf.lookup_accepted(), tf.lookup_steps(), E);      // (--draft only)
+    if (!args.draft_model.empty()) printf("\tdraft_model:%d\taccepted/steps:%s%d/%d%s", args.draft_k ? args.draft_k : 7, G, tf.lookup_accepted(), tf.lookup_steps(), E);   // (--draft-model only)
+    else if (args.draft_k) printf("\tdraft:%d,%d\taccepted/steps:%s%d/%d%s", args.draft_k, args.draft_g, G, tf.lookup_accepted(), tf.lookup_steps(), E);      // (--draft only)
     printf("\n");
     return 0;
 }

@@ -300,6 +300,40 @@ int  flm_generate_lookup_ex(flm_ctx* ctx, const int32_t* prompt, int n_prompt, i
                             int32_t stop_token /* -1: none */, int draft_len /* 4..15 */, int ngram_max /* 1..8 */,
                             flm_token_cb cb /* may be NULL */, void* user,
                             int32_t* out_tokens /* [max_tokens], may be NULL */, int* n_out);
+/* Draft-and-verify with a small DRAFT MODEL of the same vocabulary as the drafter, instead of the prompt lookup: the drafter every engine pairs a big model with, and the
+ * one that pays on text that does not repeat its history.  The verify contract is equality with the plain loop, not rejection sampling, so the ids cannot depend on the
+ * drafter: a bad draft model costs acceptance, never an id.
+ * flm_draft_set pairs a target context with a draft context (NULL: detach).  FLM_ERR_INVALID when draft == ctx or the vocabulary sizes differ; FLM_ERR_UNSUPPORTED when
+ * either context has world > 1 or the two sit on different devices; FLM_ERR_STATE before both models are complete.  Everything the pairing needs is created here (the two
+ * events that order the two contexts' streams; the hand-off reads the draft's ids where its decode loop leaves them and brings its error word along in the target's own
+ * page-locked line), so the generate call below allocates nothing; no graph of either context is re-captured by attaching, re-attaching or detaching.  The target does NOT
+ * own the draft: the caller detaches before destroying either context.  Every other entry point of both contexts behaves as it does unpaired; the caller must not run
+ * calls on the draft context from another thread while the generate call below runs on the target.
+ * flm_generate_draft is flm_generate_lookup_ex's signature without ngram_max, and its contract: ids, *n_out, *rng_state, the callback sequence, the target's K/V rows,
+ * "constraint_state", the log-probability records and "stop_reason" / "stop_rule" equal flm_generate_ex's with the same arguments, element for element.  sampling may be NULL
+ * (every control neutral at temperature 0) or neutral: the plain forms; temperature 0 needs no rng_state.  4 <= draft_len <= 15.  FLM_ERR_STATE when no draft is attached; argument
+ * errors as in flm_generate_lookup_ex, and FLM_ERR_INVALID when pos + n_prompt + max_tokens - 1 passes the DRAFT's max_seq_len; nothing is launched on an error.
+ *   token 0   the target's prompt feed as there; the draft feeds the same prompt at the same pos, its own draw discarded
+ *   a step    the draft context runs its device-resident token loop for draft_len tokens from {the last id, its position}: greedy at temperature 0, else its plain sampled
+ *             form with the step's base state and the call's temperature / top-p -- draft i is drawn with the (i + 1)-th coin, the coin the verify batch uses for row i
+ *             (common random numbers: where the two models agree on a row they draw the same id).  The controls, the constraint, the stop rules and the log-probabilities act
+ *             on the target's rows only; the draft drafts from its raw logits.  k_spec_take_drafts (csrc/flm_spec.h), on the target's stream behind the draft's event, makes
+ *             the draft's ids the batch (an id outside [0, vocab) is replaced by the last id); everything behind it is the lookup loop's.  No draft id travels to the host:
+ *             a step still has ONE host synchronisation.  The two contexts' launches never overlap on the device (the one-launch token waits on co-resident workgroups).
+ *   catch-up  after a step that accepted every draft the draft context lacks one row (the last draft was never fed): it feeds that token at the head of its next step.
+ *             Single-token steps (fewer than 2 ids wanted, or the batch would pass either max_seq_len) run on the target alone; the draft feeds what it lacks once, before
+ *             the call returns.
+ *   re-run    a step's inputs stay host-held (the history's length, the room, the state, the draft's row count): a timed-out wait in EITHER context re-runs the whole step,
+ *             nothing is delivered twice; each context falls back and recovers by its own policy.
+ * Precondition: both caches hold rows for the same pos tokens.  Postcondition: both hold pos + n_prompt + *n_out - 1 rows of the same sequence (the draft is caught up before
+ * the call returns), so a following call at that position, on either entry point, is valid.  Beyond that the draft's decode state and sampler block are unspecified.
+ * flm_query: "spec_steps" / "spec_accepted" as for the lookup loop, "draft_tokens" = tokens the draft context computed in the last call. */
+int  flm_draft_set(flm_ctx* ctx, flm_ctx* draft /* NULL: detach */);
+int  flm_generate_draft(flm_ctx* ctx, const int32_t* prompt, int n_prompt, int pos, int max_tokens,
+                        const flm_sampling* sampling /* may be NULL */, uint64_t* rng_state /* NULL allowed iff temperature == 0 */,
+                        int32_t stop_token /* -1: none */, int draft_len /* 4..15 */,
+                        flm_token_cb cb /* may be NULL */, void* user,
+                        int32_t* out_tokens /* [max_tokens], may be NULL */, int* n_out);
 /* Constrained decoding: a token-level deterministic automaton masks the logits in front of the controls -- what "one of these strings", a JSON shape or a regular expression
  * reduce to.  No reference counterpart.  The automaton is CSR: the edges of state q are [row_ptr[q], row_ptr[q + 1]).
  *   delta(q, t)  the edge_next of t's edge in state q, or q ITSELF when t has no edge there.  The no-edge case is reachable only through the multinomial branch's last-index
@@ -514,6 +548,7 @@ int  flm_set_option(flm_ctx* ctx, const char* key, int value);
  *   "stop_rules" 1 = stop rules are installed (flm_stop_set), "stop_reason" / "stop_rule" why the last generate-family call ended (FLM_STOP_LENGTH .. FLM_STOP_CANCEL) and, for
  *               an id or a sequence, which one,
  *   "spec_steps" / "spec_accepted" the last flm_generate_lookup / flm_generate_lookup_sample call: verify passes run / drafted ids accepted in them,
+ *   "draft_tokens" the last flm_generate_draft call: tokens the draft context computed (its prompt feed, its drafts, its catch-up feeds),
  *   "gen_tokens" / "gen_streamed" the last flm_generate call: tokens delivered / how many of them were delivered while hipStreamQuery still said the stream was busy,
  *   "epoch_tail" / "epoch_eng" / "epoch_xchg" the epoch counters the cross-workgroup waits count from (device memory; the 32-bit pattern): the one-launch token's, the
  *               tensor-parallel token's epoch base, k_xchg's logits exchanges (the long-lived-context tests).

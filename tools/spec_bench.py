@@ -17,9 +17,13 @@ same JSON line under "shaped":
 With --stop (behind (a), nothing else): the accept step with and without stop rules -- flm_generate_lookup_ex at temperature 1, state 1234, a bias of +0, on a prompt that
 repeats a block of its own continuation, with no rules installed (k_spec_accept_sample, one thread) and with the largest rule set that never fires (64 ids, 16 sequences of
 32: k_spec_accept_rules, the workgroup matcher over every id of the run), alternating; the difference per verify step in microseconds, under "stop".
+With --draft-model SHAPE (behind (a), nothing else; SHAPE a synthetic shape of the target's vocabulary such as 110M, or `self` = the target's own tensors in a second
+context: every draft accepted, the upper bound; --target SHAPE picks the target, default 7B): draft-and-verify with a draft MODEL as the drafter (flm_generate_draft), in
+one run on one box: t_1 of the target, the draft's time per token, the target's verify pass t_B for B = 5, 8, 16, and the loop's tokens/s with accepted / steps beside
+flm_generate_ex on the target alone in the same process -- at temperature 0 and, with --temperature T, sampled at state 1234; under "draft_model".
 Exits non-zero unless the ids of (a), (b) and (c) agree -- and, sampled, unless ids and final states agree with flm_generate; shaped, with flm_generate_ex.  Prints one
 JSON line.
-python tools/spec_bench.py [--temperature T] [--topp P] [--shape] [--stop] [N] [reps] [layers]"""
+python tools/spec_bench.py [--temperature T] [--topp P] [--shape] [--stop] [--target SHAPE] [--draft-model SHAPE|self] [N] [reps] [layers]"""
 import argparse
 import json
 import os
@@ -36,16 +40,19 @@ ap.add_argument("--temperature", "-t", type=float, default=0.0)
 ap.add_argument("--topp", "-p", type=float, default=0.9)
 ap.add_argument("--shape", action="store_true")
 ap.add_argument("--stop", action="store_true")
+ap.add_argument("--target", default="7B")
+ap.add_argument("--draft-model", dest="draft_model", default=None)
 ap.add_argument("N", nargs="?", type=int, default=128)
 ap.add_argument("reps", nargs="?", type=int, default=9)
 ap.add_argument("layers", nargs="?", type=int, default=None)
 opt = ap.parse_args()
 N, reps = opt.N, opt.reps
-cfg = synth.make_config("7B", ff.QT_INT8)
+cfg = synth.make_config(opt.target, ff.QT_INT8)
 if opt.layers is not None:
     cfg.n_layers = opt.layers
 ctx = capi.Ctx(capi.desc_from_config(cfg, max_seq_len=1024))
-ctx.upload_all(synth.make_tensors(cfg, seed=7, share_layers=True))
+tensors = synth.make_tensors(cfg, seed=7, share_layers=True)
+ctx.upload_all(tensors)
 seed = np.concatenate([[1], np.random.default_rng(1).integers(0, cfg.vocab_size, 15)]).astype(np.int32)
 ok = True
 
@@ -85,6 +92,50 @@ if opt.stop:
                    "accepted": ctx.query("spec_accepted"), "ids_and_state_agree": bool(ok), "fallback": ctx.query("fallback")}
     print(json.dumps(res), flush=True)
     ctx.close()
+    sys.exit(0 if ok else 1)
+
+if opt.draft_model:
+    same = opt.draft_model == "self"
+    dcfg = cfg if same else synth.make_config(opt.draft_model, ff.QT_INT8)
+    draft = capi.Ctx(capi.desc_from_config(dcfg, max_seq_len=1024))
+    draft.upload_all(tensors if same else synth.make_tensors(dcfg, seed=8, share_layers=True))
+    dm = {"target": opt.target, "draft": opt.draft_model, "draft_layers": dcfg.n_layers, "t1_ms": round(t1_ms, 4)}
+    # the draft's time per token: its own decode loop behind the same prompt
+    dfirst = draft.forward_argmax(seed, 0)
+    draft.decode_greedy(dfirst, len(seed), 8)                 # warm
+    t0 = time.perf_counter(); draft.decode_greedy(dfirst, len(seed), N); dm["draft_t1_ms"] = round((time.perf_counter() - t0) * 1e3 / N, 4)
+    # the target's verify pass with every draft right, B = 5, 8, 16
+    for k in (4, 7, 15):
+        ts = []
+        for _ in range(reps + 1):
+            t0 = time.perf_counter(); got = ctx.verify_greedy(first, ids[:k], len(seed)); ts.append((time.perf_counter() - t0) * 1e3)
+            ok = ok and np.array_equal(got, ids[:k + 1])
+        dm[f"t{k + 1}_ms"] = round(float(np.median(ts[1:])), 3)
+    ctx.draft_set(draft)
+    settings = [("greedy", capi.Sampling(temperature=0.0), 0)] + ([("sampled", capi.Sampling(temperature=opt.temperature, topp=opt.topp), 1234)] if opt.temperature > 0 else [])
+    for name, sp, S in settings:
+        for K in (4, 7, 15):
+            ctx.reset_kv(); draft.reset_kv()
+            ctx.generate_ex(seed, 0, 8, sp, rng_state=S)          # warm
+            ctx.reset_kv()
+            t0 = time.perf_counter(); want, sw = ctx.generate_ex(seed, 0, N, sp, rng_state=S); dt_g = time.perf_counter() - t0
+            ctx.reset_kv()
+            ctx.generate_draft(seed, 0, 8, sp, rng_state=S, draft_len=K)          # warm
+            ctx.reset_kv(); draft.reset_kv()
+            t0 = time.perf_counter(); got, sg = ctx.generate_draft(seed, 0, N, sp, rng_state=S, draft_len=K); dt_d = time.perf_counter() - t0
+            agree = bool(np.array_equal(got, want) and sg == sw)
+            ok = ok and agree
+            dm[f"{name}_K{K}"] = {"generate_ex_tok_s": round(N / dt_g, 1), "generate_draft_tok_s": round(N / dt_d, 1), "steps": ctx.query("spec_steps"), "accepted": ctx.query("spec_accepted"),
+                                  "draft_tokens": ctx.query("draft_tokens"), "ids_and_state_agree": agree}
+            print(f"{name} K = {K}: flm_generate_draft {dm[f'{name}_K{K}']['generate_draft_tok_s']} tokens/s, accepted / steps {ctx.query('spec_accepted')} / {ctx.query('spec_steps')} "
+                  f"(flm_generate_ex on the target alone: {dm[f'{name}_K{K}']['generate_ex_tok_s']} tokens/s)")
+    print(f"t_1 target {dm['t1_ms']} ms, draft {dm['draft_t1_ms']} ms per token; t_5 {dm['t5_ms']} ms, t_8 {dm['t8_ms']} ms, t_16 {dm['t16_ms']} ms")
+    dm["fallback"] = [ctx.query("fallback"), draft.query("fallback")]
+    res["draft_model"] = dm
+    res["ids_agree"] = bool(ok)
+    print(json.dumps(res), flush=True)
+    ctx.draft_set(None)
+    draft.close(); ctx.close()
     sys.exit(0 if ok else 1)
 
 # (b) one verify pass with every draft right
