@@ -34,6 +34,7 @@ SYMBOLS = (
     "flm_logprobs_arm", "flm_last_logprobs", "flm_op_logprob_rows", "flm_logprob_stage_time",
     "flm_stop_validate", "flm_stop_match", "flm_stop_set", "flm_op_stop_match",
     "flm_draft_set", "flm_generate_draft",
+    "flm_entropy_validate", "flm_entropy_set", "flm_entropy_mu", "flm_op_logf", "flm_op_entropy_rows",
 )
 
 # flm_score (include/flm_gpu.h): one row of flm_score_tokens / flm_op_score_rows
@@ -92,6 +93,29 @@ class Sampling:
 
 class FlmError(RuntimeError):
     pass
+
+
+class EntropyStruct(C.Structure):
+    """flm_entropy (include/flm_gpu.h)"""
+    _fields_ = [("typical_p", C.c_float), ("mirostat", C.c_int32), ("tau", C.c_float), ("eta", C.c_float), ("mu", C.c_float)]
+
+
+@dataclasses.dataclass
+class Entropy:
+    """the entropy-driven samplers of flm_entropy_set: locally typical sampling (0 < typical_p < 1) or Mirostat v2 (mirostat = 2, target entropy tau, learning rate eta,
+    starting state mu; None: 2 * tau).  The defaults are off"""
+    typical_p: float = 0.0
+    mirostat: int = 0
+    tau: float = 5.0
+    eta: float = 0.1
+    mu: object = None
+
+    def struct(self):
+        return EntropyStruct(self.typical_p, int(self.mirostat), self.tau, self.eta, 2.0 * self.tau if self.mu is None else self.mu)
+
+    @property
+    def mode(self):
+        return 2 if self.mirostat == 2 else 1 if 0.0 < self.typical_p < 1.0 else 0
 
 
 DFA_STATES_MAX, DFA_EDGES_MAX = 65536, 1 << 24      # FLM_DFA_STATES_MAX, FLM_DFA_EDGES_MAX
@@ -469,6 +493,21 @@ class Ctx:
         """why the last generate-family call ended -> (STOP_LENGTH | STOP_TOKEN | STOP_ID | STOP_SEQ | STOP_CANCEL, the id's position / the sequence's index)"""
         return self.query("stop_reason"), self.query("stop_rule")
 
+    def entropy_set(self, entropy):
+        """flm_entropy_set: from now on flm_generate_ex / flm_forward_sample_ex (typical: the draft-and-verify _ex entry points too) apply the stage (None: off);
+        query("entropy") reads the mode back"""
+        if entropy is None:
+            _check(lib().flm_entropy_set(self._h, None), self._h)
+            return
+        st = entropy.struct()
+        _check(lib().flm_entropy_set(self._h, C.byref(st)), self._h)
+
+    def entropy_mu(self) -> float:
+        """flm_entropy_mu: Mirostat's state behind the ids delivered so far (np.float32)"""
+        mu = C.c_float(0)
+        _check(lib().flm_entropy_mu(self._h, C.byref(mu)), self._h)
+        return np.float32(mu.value)
+
     def logprobs_arm(self, top_n, source="raw"):
         """flm_logprobs_arm: from now on the _ex entry points leave one record per delivered id (top_n alternatives, 0 .. 20; -1: off) from the classifier's row ("raw") or
         the row the sampler reads ("shaped"); query("logprobs_top_n") reads the setting back"""
@@ -809,6 +848,58 @@ def shape_host(logits, sampling, window=()) -> np.ndarray:
     _host.fh_shape(_p(a), int(a.size), C.c_float(sampling.temperature), int(sampling.top_k), C.c_float(sampling.min_p), C.c_float(sampling.repeat_penalty),
                    C.c_float(sampling.frequency_penalty), C.c_float(sampling.presence_penalty), int(ids.size), _p(ids), _p(vals), _p(w), int(w.size), _p(out))
     return out
+
+
+def entropy_validate(entropy):
+    """flm_entropy_validate (pure host arithmetic): raises FlmError naming the rule that failed"""
+    st = entropy.struct()
+    _check(lib().flm_entropy_validate(C.byref(st)))
+
+
+def op_logf(x) -> np.ndarray:
+    """flm_logf as the device evaluates it, over positive normal floats"""
+    a = np.array(x, dtype=np.float32, copy=True).reshape(-1)
+    _check(lib().flm_op_logf(_p(a), C.c_size_t(a.size)))
+    return a
+
+
+def logf_host(x) -> np.ndarray:
+    """flm_logf as the host compiles it (csrc/flm_logf.h through lib/libflm_host.so: fh_logf); needs no GPU"""
+    a = np.array(x, dtype=np.float32, copy=True).reshape(-1)
+    _host_lib().fh_logf(_p(a), C.c_size_t(a.size))
+    return a
+
+
+def entropy_host(logits, temperature, entropy, mu=None, chosen=None):
+    """the entropy-driven stages' host restatement (host/sampler.cpp entropy_logits / mirostat_update through lib/libflm_host.so) on one row; needs no GPU.
+    -> the masked row; with chosen (Mirostat): (the masked row, obs, the updated mu) as np.float32.  mu None: entropy's starting state"""
+    a = np.ascontiguousarray(logits, dtype=np.float32).reshape(-1)
+    st = entropy.struct()
+    m = st.mu if mu is None else mu
+    out = np.empty_like(a)
+    h = _host_lib()
+    h.fh_entropy(_p(a), int(a.size), C.c_float(temperature), C.c_float(st.typical_p), int(st.mirostat), C.c_float(m), _p(out))
+    if chosen is None:
+        return out
+    h.fh_mirostat_update.restype = C.c_float
+    obs = C.c_float(0)
+    m2 = h.fh_mirostat_update(_p(out), int(a.size), C.c_float(temperature), int(chosen), C.c_float(st.tau), C.c_float(st.eta), C.c_float(m), C.byref(obs))
+    return out, np.float32(obs.value), np.float32(m2)
+
+
+def op_entropy_rows(logits, n, temperature, entropy, mu=None, chosen=None):
+    """k_entropy_rows on logits[rows][ld], the first n entries of each row -> the masked rows [rows][n]; Mirostat: mu[rows] the rows' states, and with chosen[rows]
+    -> (the masked rows, obs[rows], the updated mu[rows])"""
+    a = np.ascontiguousarray(logits, dtype=np.float32)
+    a = a.reshape(1, -1) if a.ndim == 1 else a
+    rows = int(a.shape[0])
+    st = entropy.struct()
+    m = None if mu is None else np.ascontiguousarray(np.broadcast_to(np.asarray(mu, dtype=np.float32), (rows,)))
+    ch = None if chosen is None else np.ascontiguousarray(chosen, dtype=np.int32).reshape(-1)
+    out = np.empty((rows, int(n)), dtype=np.float32)
+    obs = np.zeros(rows, dtype=np.float32); mu2 = np.zeros(rows, dtype=np.float32)
+    _check(lib().flm_op_entropy_rows(_p(a), rows, int(a.shape[1]), int(n), C.c_float(temperature), C.byref(st), _p(m), _p(ch), _p(out), _p(obs), _p(mu2)))
+    return out if chosen is None else (out, obs, mu2)
 
 
 def op_sample_rows(logits, n, temperature, topp, rng_state):

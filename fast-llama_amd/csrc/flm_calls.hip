@@ -57,6 +57,24 @@ static int set_lp(flm_ctx* c, int base) {
     HIPC(c, hipGetLastError());
     return FLM_OK;
 }
+// the entropy-driven samplers' block, by value like the decode state, from the host's copy: the parameters and Mirostat's mu behind the ids delivered so far -- written
+// at the start of every attempt, so a retried attempt updates nothing twice.  One tiny launch: no allocation, no graph touched
+__global__ void k_set_entropy(EntropyBlock* blk, const EntropyBlock v) { if (threadIdx.x == 0 && blockIdx.x == 0) *blk = v; }
+static int set_entropy(flm_ctx* c) {
+    EntropyBlock v{}; v.typical_p = c->ent.typical_p; v.mirostat = c->ent.mirostat; v.tau = c->ent.tau; v.eta = c->ent.eta; v.mu = c->ent.mu;
+    hipLaunchKernelGGL(k_set_entropy, dim3(1), dim3(64), 0, c->stream, c->ent_blk, v);
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
+// the rules of flm_entropy_validate: null, or which one failed
+static const char* entropy_check(const flm_entropy* e) {
+    if (!e) return "entropy: null struct";
+    if (e->typical_p != e->typical_p) return "entropy: typical_p is NaN";
+    if (e->mirostat != 0 && e->mirostat != 2) return "entropy: mirostat must be 0 or 2";
+    if (e->mirostat == 2 && !(isfinite(e->tau) && isfinite(e->eta) && isfinite(e->mu))) return "entropy: tau, eta and mu must be finite";
+    if (e->mirostat == 2 && typical_on(e->typical_p)) return "entropy: typical_p and mirostat are both set";
+    return nullptr;
+}
 // delta(q, t): the edge_next of t's edge in q, or q itself when t has no edge there -- reachable only through the multinomial branch's last-index fallback of Sampler::sample
 // (`return _n - 1`), which can name a masked id; folded over the ids a call delivered
 int dfa_fold(const flm_ctx* c, int q, const int32_t* ids, int n) {
@@ -179,6 +197,7 @@ int Draw::arm_with(flm_ctx* c, const ShapeParams& blk, unsigned long long rng, i
     int r = shaped() ? set_shape(c, blk) : FLM_OK;
     if (!r && q >= 0) r = set_dfa(c, q);
     if (!r && lp) r = set_lp(c, rec_base);
+    if (!r && ent) r = set_entropy(c);
     if (!r && form != TokenForm::Greedy) r = set_sample(c, temperature, topp, coins() ? rng : 0ull);
     return r;
 }
@@ -195,15 +214,20 @@ SpecDraw Draw::batch(const flm_ctx* c, unsigned long long base, const int* win, 
     SpecDraw sd{temperature, topp, base};
     if (shaped()) { sd.shape = c->shape_p; sd.win = win ? win : c->shape_p->head; sd.n_win = win ? n_win : block.n_head; sd.cstate = q; }
     if (lp) { sd.lp_top_n = c->lp_top_n; sd.lp_source = c->lp_source; sd.lp_base = rec_base; }
+    sd.typical_p = typical_p;
     return sd;
 }
-int Draw::fetch(flm_ctx* c, unsigned long long* after) const { return coins() ? d2h(c, after, &c->sparams->rng, sizeof *after) : FLM_OK; }
+int Draw::fetch(flm_ctx* c, unsigned long long* after) const {
+    if (mu_moves()) { const int r = d2h(c, &c->ent_mu_fetched, &c->ent_blk->mu, sizeof(float)); if (r) return r; }
+    return coins() ? d2h(c, after, &c->sparams->rng, sizeof *after) : FLM_OK;
+}
 void Draw::commit(flm_ctx* c, const int32_t* ids, int n, unsigned long long after) const { commit(c, n, after, cstate >= 0 ? dfa_fold(c, cstate, ids, n) : -1); }
 void Draw::commit(flm_ctx* c, int n, unsigned long long after, int q_after) const {
     if (coins()) { *rng_state = after; c->sampled += n; }
     if (shaped()) c->shaped += n;
     if (q_after >= 0) c->dfa_state = q_after;
     if (lp) c->lp_count = n;
+    if (mu_moves()) c->ent.mu = c->ent_mu_fetched;
 }
 // feed tokens[0..n) sequentially (row i of the reference's batched prefill depends only on rows
 // <= i through the KV cache, so token-by-token evaluation performs the same per-row arithmetic).
@@ -255,9 +279,10 @@ static bool lp_armed(const flm_ctx* c) { return c->lp_top_n >= 0 && logprobs_sup
 // only), and so does a context armed for log-probabilities (the shaped form with the record stage behind its sampler).  own(block, active): what one entry point checks or
 // changes between the block's validation and that decision (null, or what is wrong)
 struct NoOwn { const char* operator()(ShapeParams&, bool&) const { return nullptr; } };
-// honour_rules (flm_generate_ex / flm_generate_lookup_ex): installed stop rules count as a control that is set too -- the matcher lives in the shaped form's last launch
+// honour_rules (flm_generate_ex / flm_generate_lookup_ex): installed stop rules count as a control that is set too -- the matcher lives in the shaped form's last launch.
+// flm_entropy_set counts as one as well (the ShapedEnt form); batch (the draft-and-verify entry points): Mirostat is refused -- row r's mu depends on the draws in front of it
 template <class Own = NoOwn>
-static int draw_resolve(flm_ctx* c, const flm_sampling* sampling, const int32_t* window, int n_window, bool follow, uint64_t* rng_state, Draw& dr, Own own = Own(), bool honour_rules = false) {
+static int draw_resolve(flm_ctx* c, const flm_sampling* sampling, const int32_t* window, int n_window, bool follow, uint64_t* rng_state, Draw& dr, Own own = Own(), bool honour_rules = false, bool batch = false) {
     bool active = false;
     const char* why = shape_fill(sampling, c->d.vocab_size, window, n_window, follow, &dr.block, &active);
     if (!why) why = own(dr.block, active);
@@ -267,7 +292,10 @@ static int draw_resolve(flm_ctx* c, const flm_sampling* sampling, const int32_t*
     const int cq = sharded(c) ? -1 : c->dfa_state;
     const bool lp = lp_armed(c);
     const bool rules = honour_rules && !sharded(c) && stop_installed(c);
-    if (active || cq >= 0 || lp || rules) { dr.shape_by(cq, lp); dr.rules = rules; }
+    const int ent = entropy_supported(c) ? c->ent_mode : 0;
+    if (ent && lp) return fail(c, FLM_ERR_UNSUPPORTED, "entropy: not built on a context armed for log-probabilities");
+    if (ent == 2 && batch) return fail(c, FLM_ERR_UNSUPPORTED, "entropy: Mirostat is not built through the draft-and-verify entry points");
+    if (active || cq >= 0 || lp || rules || ent) { dr.shape_by(cq, lp, ent, c->ent.typical_p); dr.rules = rules; }
     return FLM_OK;
 }
 // flm_score_tokens: where a chunk of rows' logits is staged -- the prefill scores (free once the last layer's attention is done) or, a row at a time, the logits vector --
@@ -674,7 +702,7 @@ int flm_verify_sample_ex(flm_ctx* c, int32_t first_token, const int32_t* drafts,
         const bool pen = sampling->repeat_penalty != 1.0f || sampling->frequency_penalty != 0.0f || sampling->presence_penalty != 0.0f;
         if (pen && sampling->penalty_last_n > 0) { sp.last_n = sampling->penalty_last_n; active = true; }
         return nullptr;
-    });
+    }, false, true);
     if (r) return r;
     return verify_impl(c, first_token, drafts, k, pos, dr, out_tokens, n_out);
 }
@@ -827,7 +855,7 @@ int flm_generate_lookup_ex(flm_ctx* c, const int32_t* prompt, int n_prompt, int 
     if (!ids_in_vocab(c, prompt, n_prompt)) return fail(c, FLM_ERR_INVALID, "token id out of range");
     const int tail = n_prompt < FLM_PENALTY_WINDOW_MAX ? n_prompt : FLM_PENALTY_WINDOW_MAX;
     Draw dr;
-    if (int r = draw_resolve(c, sampling, prompt + (n_prompt - tail), tail, true, rng_state, dr, NoOwn(), true)) return r;
+    if (int r = draw_resolve(c, sampling, prompt + (n_prompt - tail), tail, true, rng_state, dr, NoOwn(), true, true)) return r;
     return generate_lookup_impl(c, prompt, n_prompt, pos, max_tokens, dr, stop_token, draft_len, ngram_max, cb, user, out_tokens, n_out);
 }
 // flm_generate_lookup_ex with the paired draft context (flm_draft_set) as the drafter: the same loop, the same plan.  sampling null: every control neutral at temperature 0.
@@ -843,7 +871,7 @@ int flm_generate_draft(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos,
     const int tail = n_prompt < FLM_PENALTY_WINDOW_MAX ? n_prompt : FLM_PENALTY_WINDOW_MAX;
     flm_sampling neutral{}; neutral.repeat_penalty = 1.0f;
     Draw dr;
-    if (int r = draw_resolve(c, sampling ? sampling : &neutral, prompt + (n_prompt - tail), tail, true, rng_state, dr, NoOwn(), true)) return r;
+    if (int r = draw_resolve(c, sampling ? sampling : &neutral, prompt + (n_prompt - tail), tail, true, rng_state, dr, NoOwn(), true, true)) return r;
     return generate_lookup_impl(c, prompt, n_prompt, pos, max_tokens, dr, stop_token, draft_len, 1, cb, user, out_tokens, n_out, d);
 }
 
@@ -924,6 +952,31 @@ int flm_stop_set(flm_ctx* c, const flm_stop_rules* r) {
     if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, FLM_ERR_HIP, "stop_set: the copy of the rule block failed");   // (`b` has left the bounce buffer; the next call's first launch sees the block)
     c->stop_host = rc ? StopBlock{} : b;
     return rc;
+}
+
+// The entropy-driven samplers (include/flm_gpu.h; the stages: flm_entropy.h; the host restatement: host/sampler.cpp entropy_logits).  A context setting like
+// flm_logprobs_arm: the block and the entropy token graphs exist since flm_ctx_create / flm_prepare, so the setting changes the host copy and nothing else -- the block is
+// rewritten from it at the start of every attempt (Draw::arm)
+int flm_entropy_validate(const flm_entropy* e) {
+    if (const char* why = entropy_check(e)) { g_last_error = why; return FLM_ERR_INVALID; }
+    return FLM_OK;
+}
+int flm_entropy_set(flm_ctx* c, const flm_entropy* e) {
+    if (!c) return FLM_ERR_INVALID;
+    if (e) if (const char* why = entropy_check(e)) return fail(c, FLM_ERR_INVALID, why);
+    if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "entropy: one GPU only");
+    if (!sample_supported(c) || !c->ent_blk) return fail(c, FLM_ERR_UNSUPPORTED, "entropy: the vocabulary does not fit one workgroup's LDS (the device sampler's bound)");
+    if (!model_complete(c)) return fail(c, FLM_ERR_STATE, "entropy_set before all tensors were uploaded");
+    const int mode = !e ? 0 : e->mirostat == 2 ? 2 : typical_on(e->typical_p) ? 1 : 0;
+    c->ent = mode ? *e : flm_entropy{};
+    c->ent_mode = mode;
+    return FLM_OK;
+}
+int flm_entropy_mu(flm_ctx* c, float* mu) {
+    if (!c || !mu) return FLM_ERR_INVALID;
+    if (c->ent_mode != 2) return fail(c, FLM_ERR_STATE, "entropy_mu: Mirostat is not set");
+    *mu = c->ent.mu;
+    return FLM_OK;
 }
 
 // Per-token log-probabilities (include/flm_gpu.h; the stage: flm_logprob.h).  A context setting like flm_constraint_arm: the block, the records and the armed token graphs

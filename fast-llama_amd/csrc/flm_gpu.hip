@@ -294,13 +294,14 @@ int run_token(flm_ctx* c, bool with_cls, TokenForm form, int T) {
 }
 // the token forms a context's decode loops replay (single tokens and chunks): greedy always, sampled where the sampler supports the vocabulary, shaped on one GPU.  Their
 // parameters live in device memory (set_sample / set_shape), so no call re-captures or allocates
-constexpr int kLoopForms = 4;
+constexpr int kLoopForms = 5;
 static int loop_forms(const flm_ctx* c, TokenForm out[kLoopForms]) {
     int n = 0;
     out[n++] = TokenForm::Greedy;
     if (sample_supported(c)) out[n++] = TokenForm::Sampled;
     if (!sharded(c)) out[n++] = TokenForm::Shaped;
     if (logprobs_supported(c)) out[n++] = TokenForm::ShapedLp;        // (the armed form, next to the shaped graphs: flm_logprobs_arm captures nothing)
+    if (entropy_supported(c)) out[n++] = TokenForm::ShapedEnt;        // (the entropy form, likewise: flm_entropy_set captures nothing)
     return n;
 }
 // Everything the token entry points use beyond the buffers of flm_ctx_create: k_layers' argument blocks (both head splits) and every graph flm_forward* / flm_decode_* / flm_generate*
@@ -523,6 +524,7 @@ int flm_ctx_create(const flm_model_desc* desc, int device_id, int rank, int worl
         HIPB(dev_alloc(c, &c->lp_rec, sizeof(LogprobRec) * (size_t)d.max_seq_len, true));
         HIPB(dev_alloc(c, &c->lp_tags, sizeof(unsigned) * (size_t)d.max_seq_len, true));
         HIPB(dev_alloc(c, &c->lp_side, (size_t)kSpecRows * d.vocab_size * sizeof(float)));
+        HIPB(dev_alloc(c, &c->ent_blk, sizeof(EntropyBlock), true));   // the entropy-driven samplers' block (flm_entropy.h), zeroed: both stages off
     }
     if (sample_supported(c)) HIPB(dev_alloc(c, &c->sort_buf, (size_t)kSpecRows * 2 * d.vocab_size * sizeof(unsigned long long)));   // ([16][2][vocab]: a slice per row of a sampled verify batch)
     std::vector<float> cs, sn; build_rope_table(hs, d.max_seq_len, cs, sn);
@@ -541,6 +543,7 @@ int flm_ctx_create(const flm_model_desc* desc, int device_id, int rank, int worl
                 HIPB(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_census), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
                 HIPB(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sample_advance), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
                 HIPB(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_logprob_token), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
+                HIPB(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_entropy_advance), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
                 attr_done[device_id] = true;
             }
         }
@@ -847,6 +850,7 @@ int flm_query(flm_ctx* c, const char* key, int* value) {
         {"shaped_tokens", (int)c->shaped},
         {"constraint_state", c->dfa_state},
         {"logprobs_top_n", c->lp_top_n},
+        {"entropy", c->ent_mode},
         {"stop_rules", stop_installed(c) ? 1 : 0},
         {"stop_reason", c->stop_reason},
         {"stop_rule", c->stop_rule},
@@ -949,7 +953,7 @@ static void warm_up(flm_ctx* c) {
         if (shaped && c->d.vocab_size < 2) continue;
         // (the armed form is captured at prepare_all like the others but not replayed here: a context that is never armed runs at load time exactly the launches it ran
         //  before that form existed; the first armed call pays its graphs' first launch)
-        if (forms[f] == TokenForm::ShapedLp) continue;
+        if (forms[f] == TokenForm::ShapedLp || forms[f] == TokenForm::ShapedEnt) continue;
         Draw dr(forms[f] == TokenForm::Sampled || (shaped && sample_supported(c)) ? 1.0f : 0.0f, 0.9f, &zero);
         if (shaped) { dr.block = neutral; dr.shape_by(-1, false); }
         ok = dr.arm(c) == FLM_OK && set_state(c, n, 0, 0) == FLM_OK && run_tokens(c, n, kEach, dr.form) == FLM_OK && hipStreamSynchronize(c->stream) == hipSuccess;

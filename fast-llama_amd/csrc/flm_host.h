@@ -53,8 +53,10 @@ struct EvPair { hipEvent_t e0 = nullptr, e1 = nullptr; ~EvPair() { if (e0) hipEv
 //   Shaped   k_shape_logits, then the sampler (the argmax where the vocabulary is beyond the sampler) on the shaped row, pos++
 //   ShapedLp Shaped with k_logprob_token behind the sampler (flm_logprob.h): what the _ex entry points replay while the context is armed with flm_logprobs_arm.  A form of
 //            its own, so that the Shaped graphs stay node for node what they were and arming captures nothing
-enum class TokenForm { Logits, Greedy, Prompt, Sampled, Shaped, ShapedLp };
-inline bool shaped_form(TokenForm f) { return f == TokenForm::Shaped || f == TokenForm::ShapedLp; }
+//   ShapedEnt the shaped form with k_entropy_advance as its last launch (flm_entropy.h: stage 5 / 6, the unchanged draw, Mirostat's update, the token's tail): what
+//            flm_generate_ex / flm_forward_sample_ex replay while flm_entropy_set is on.  A form of its own for the same reason
+enum class TokenForm { Logits, Greedy, Prompt, Sampled, Shaped, ShapedLp, ShapedEnt };
+inline bool shaped_form(TokenForm f) { return f == TokenForm::Shaped || f == TokenForm::ShapedLp || f == TokenForm::ShapedEnt; }
 // a cached token graph: n token sequences (with_cls, form) for G workgroups per head
 using GraphKey = std::tuple<bool, TokenForm, int, int>;
 
@@ -203,6 +205,11 @@ struct flm_ctx {
     // contents change), the host copy the finish reason is computed from (n_ids = n_seqs = 0: none installed; "stop_rules"), and why the last generate-family call ended
     // ("stop_reason" / "stop_rule")
     flm::StopBlock* stop_blk = nullptr; flm::StopBlock stop_host{}; int stop_reason = 0, stop_rule = 0;
+    // the entropy-driven samplers (include/flm_gpu.h flm_entropy_set; the stages: flm_entropy.h): the setting's device block since create (null where the context is sharded
+    // or the vocabulary is beyond the sampler: the setting refuses there; the entropy token graphs hold the pointer, Draw::arm rewrites its contents from `ent` at the start
+    // of every attempt), the host copy -- ent.mu is Mirostat's state behind the ids delivered so far, moved by Draw::commit alone --, the mode (0 off, 1 typical, 2 Mirostat;
+    // "entropy") and the state the last attempt's read-back brought along (Draw::fetch; committed only when the attempt is verified)
+    flm::EntropyBlock* ent_blk = nullptr; flm_entropy ent{}; int ent_mode = 0; float ent_mu_fetched = 0.0f;
     int score_rows = 0;                                // option "score_rows": rows per classifier chunk of flm_score_tokens (0: as many as the staging holds; < 0: one row at a time through c->logits)
     std::map<GraphKey, hipGraphExec_t> graphs;        // the token graphs captured so far (flm_gpu.hip token_graph)
     std::vector<TimedLaunch>* timing = nullptr;
@@ -316,6 +323,8 @@ int set_state(flm_ctx* c, int pos, int tok, int step);
 inline bool sharded(const flm_ctx* c) { return c->world > 1 || (c->comm != nullptr && c->force_tp); }
 // per-token log-probabilities can be armed: one GPU, the vocabulary within the sampler's LDS strip (the sum chain's bound; flm_score_tokens has the same)
 inline bool logprobs_supported(const flm_ctx* c) { return !sharded(c) && sample_supported(c); }
+// the entropy-driven samplers can be set: the same bound (the stage runs on the sampler's strip), and the block exists
+inline bool entropy_supported(const flm_ctx* c) { return !sharded(c) && sample_supported(c) && c->ent_blk != nullptr; }
 inline const int* halt_ptr(const flm_ctx* c) { return sharded(c) ? nullptr : &c->state->halt; }
 // ids[0 .. n) lie in [0, vocab)
 inline bool ids_in_vocab(const flm_ctx* c, const int32_t* ids, int n) {
@@ -333,9 +342,13 @@ struct Draw {
     int cstate = -1;                                              // the constraint's state at the call's first token (-1: none; only with the block: an armed constraint counts as a control)
     bool lp = false;                                              // the context is armed for log-probabilities: the form is ShapedLp, record i is the call's i-th id's
     bool rules = false;                                           // stop rules are installed and this entry point honours them (flm_generate_ex / flm_generate_lookup_ex; only with the block)
+    int ent = 0; float typical_p = 0.0f;                          // flm_entropy_set is on (1 typical, 2 Mirostat): the form is ShapedEnt; a verify batch's rows get stage 5 (typical only)
     Draw(float t = 0.0f, float p = 0.0f, uint64_t* st = nullptr, bool sampler = false) { plain(t, p, st, sampler); }
     void plain(float t, float p, uint64_t* st, bool sampler = false) { temperature = t; topp = p; rng_state = st; form = t != 0.0f || sampler ? TokenForm::Sampled : TokenForm::Greedy; }
-    void shape_by(int cq, bool armed) { form = armed ? TokenForm::ShapedLp : TokenForm::Shaped; cstate = cq; lp = armed; }   // `block` is filled: the shaped form runs
+    void shape_by(int cq, bool armed, int entropy = 0, float tp = 0.0f) {                                                   // `block` is filled: the shaped form runs
+        form = entropy ? TokenForm::ShapedEnt : armed ? TokenForm::ShapedLp : TokenForm::Shaped; cstate = cq; lp = armed; ent = entropy; typical_p = entropy == 1 ? tp : 0.0f;
+    }
+    bool mu_moves() const { return ent == 2 && temperature != 0.0f; }   // Mirostat's state is read back and committed
     bool shaped() const { return shaped_form(form); }
     bool coins() const { return form == TokenForm::Sampled || (shaped() && temperature != 0.0f); }   // the caller's state is read and moved on
     // an attempt's start: the shaper's block, the constraint's {state, 0}, the record stage's base, then the sampler's parameters FROM THE CALLER'S STATE -- a retried attempt draws nothing twice
@@ -347,9 +360,9 @@ struct Draw {
     // the batch form of this plan for one verify step: what varies per step is the xorshift state its rows' coins count from, the window in device memory
     // (win[0 .. n_win) ++ the drafts in front of a row; win null: the block's own head, as the last arm_block left it), the constraint's state at row 0 and the record index of row 0
     SpecDraw batch(const flm_ctx* c, unsigned long long base, const int* win, int n_win, int q, int rec_base) const;
-    int fetch(flm_ctx* c, unsigned long long* after) const;       // an attempt's end: the state behind its draws comes back
+    int fetch(flm_ctx* c, unsigned long long* after) const;       // an attempt's end: the state behind its draws comes back (and Mirostat's, into flm_ctx::ent_mu_fetched)
     // a verified attempt that delivered ids[0 .. n) and left the sampler's state `after`: the ONE place that writes the caller's state, "sampled_tokens" / "shaped_tokens",
-    // "constraint_state" (folded over the ids; q_after: the caller folded step by step) and the count of records flm_last_logprobs hands out
+    // "constraint_state" (folded over the ids; q_after: the caller folded step by step), the count of records flm_last_logprobs hands out and Mirostat's mu
     void commit(flm_ctx* c, const int32_t* ids, int n, unsigned long long after) const;
     void commit(flm_ctx* c, int n, unsigned long long after, int q_after) const;
 private:
@@ -373,6 +386,7 @@ int score_classify(flm_ctx* c, int row0, int m, float* stage);
 // shape (the device block) given: k_shape_rows shapes the chunk's rows in place in front of the draw, row i over the last min(last_n, n_win + i) ids of
 // win[0 .. n_win) ++ the batch's drafts in front of it (prompt_dev + 1); null: no shape kernel runs.  Filled by Draw::batch and by nobody else
 struct SpecDraw { float temperature, topp; unsigned long long base; const flm::ShapeParams* shape = nullptr; const int* win = nullptr; int n_win = 0; int cstate = -1 /* the batch's base constraint state; -1: none */;
+                  float typical_p = 0.0f /* flm_entropy_set, typical: k_entropy_rows between the shaper and the rows' draws; otherwise 0 */;
                   int lp_top_n = -1 /* the context is armed: k_logprob_rows behind the rows' draws, records from lp_base on; -1: not */, lp_source = 0, lp_base = 0; };
 // k_shape_rows on `rows` rows (batch rows row0 ..) of n logits, ld floats apart -> out, ld_out apart (out == logits: in place); c may be null: flm_op_shape_rows
 int launch_shape_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, float* out, int ld_out, int n, int row0, int rows, const flm::ShapeParams* p,
@@ -387,6 +401,8 @@ int spec_classify(flm_ctx* c, int row0, int m, float* stage, bool skinny, int* a
 // k_logprob_rows on `rows` <= 16 rows of n logits, ld floats apart, batch rows row0 ..: chosen[row0 + r] the row's drawn id, its record rec[rec_base + row0 + r]
 // (flm_prompt.hip; c may be null: flm_op_logprob_rows)
 int launch_logprob_rows(flm_ctx* c, hipStream_t st, const float* rows_dev, int ld, int n, int row0, int rows, const int* chosen, int top_n, flm::LogprobRec* rec, int rec_base, int rec_cap);
+// k_entropy_rows on `rows` <= 16 rows of n logits, ld floats apart, in place; sort_buf [rows][2][n] (flm_prompt.hip; c may be null: flm_op_entropy_rows)
+int launch_entropy_rows(flm_ctx* c, hipStream_t st, const flm::EntropyRowsArgs& a, int rows);
 // k_sample_rows on `rows` <= 16 rows of n logits, ld floats apart, batch rows row0 ..; sort_buf [rows][2][n] (flm_prompt.hip; c may be null: flm_op_sample_rows)
 int launch_sample_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, int n, int row0, int rows, float temperature, float topp, unsigned long long base,
                        unsigned long long* sort_buf, int* out);

@@ -57,7 +57,7 @@
 // (Round 3's weight-streaming engine -- loader / consumer waves around an LDS ring -- was measured slower than these launches and left the library in round 4:
 //  tools/experiments/engine/, numbers in profiles/r03_engine_timelines.txt.)
 //
-// The code lives in: flm_math.h (exact scalar / wave building blocks), flm_wait.h (every cross-workgroup wait: flag polls, granule pieces, the give-up policy), flm_gemv.h, flm_attn.h, flm_layer.h, flm_prefill.h, flm_misc.h, flm_sample.h, flm_score.h, flm_logprob.h, flm_spec.h, flm_stop.h.
+// The code lives in: flm_math.h (exact scalar / wave building blocks), flm_wait.h (every cross-workgroup wait: flag polls, granule pieces, the give-up policy), flm_gemv.h, flm_attn.h, flm_layer.h, flm_prefill.h, flm_misc.h, flm_sample.h, flm_score.h, flm_logprob.h, flm_spec.h, flm_stop.h, flm_entropy.h (with flm_logf.h, the logarithm the host compiles too).
 #pragma once
 #include "flm_math.h"
 #include "flm_wait.h"
@@ -69,6 +69,7 @@
 #include "flm_stop.h"
 #include "flm_sample.h"
 #include "flm_shape.h"
+#include "flm_entropy.h"
 #include "flm_score.h"
 #include "flm_logprob.h"
 #include "flm_spec.h"

@@ -334,6 +334,44 @@ int flm_op_logprob_rows(const float* logits, int rows, int ld, int n, const int3
     return FLM_OK;
 }
 
+/* flm_logf as the device evaluates it (csrc/flm_logf.h: the header the host compiles too) */
+int flm_op_logf(float* x, size_t n) {
+    if (!x || n == 0) return FLM_ERR_INVALID;
+    DevBuf d; if (d.alloc(n * 4)) return FLM_ERR_OOM;
+    OPC(hipMemcpy(d.p, x, n * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_op_logf, dim3(256), dim3(256), 0, 0, d.as<float>(), n);
+    OPC(hipGetLastError()); OPC(hipDeviceSynchronize());
+    OPC(hipMemcpy(x, d.p, n * 4, hipMemcpyDeviceToHost));
+    return FLM_OK;
+}
+
+/* k_entropy_rows -- stage 5 / 6 of flm_entropy_set over the rows of a verify batch (flm_entropy.h) -- on caller-supplied rows, with Mirostat's update for given ids */
+int flm_op_entropy_rows(const float* logits, int rows, int ld, int n, float temperature, const flm_entropy* e, const float* mu, const int32_t* chosen,
+                        float* out, float* obs_out, float* mu_out) {
+    if (!logits || !out || !e || rows < 1 || rows > kSpecRows || n < 2 || ld < n || !(temperature >= 0.0f)) return FLM_ERR_INVALID;
+    if (int r = flm_entropy_validate(e)) return r;
+    if (e->mirostat == 2 && !mu) { g_last_error = "entropy_rows: Mirostat needs a mu per row"; return FLM_ERR_INVALID; }
+    if (chosen) for (int i = 0; i < rows; ++i) if (chosen[i] < 0 || chosen[i] >= n) { g_last_error = "entropy_rows: chosen id outside [0, n)"; return FLM_ERR_INVALID; }
+    if (sample_lds_bytes(n) > kLdsMax) return FLM_ERR_UNSUPPORTED;
+    DevBuf dl, dm, dc, dobs, dmu, dsort;
+    if (dl.alloc((size_t)rows * ld * 4) || dm.alloc((size_t)kSpecRows * 4) || dc.alloc((size_t)kSpecRows * 4) || dobs.alloc((size_t)kSpecRows * 4) || dmu.alloc((size_t)kSpecRows * 4) ||
+        dsort.alloc((size_t)rows * 2 * n * sizeof(unsigned long long))) return FLM_ERR_OOM;
+    OPC(hipMemcpy(dl.p, logits, (size_t)rows * ld * 4, hipMemcpyHostToDevice));
+    if (mu) OPC(hipMemcpy(dm.p, mu, (size_t)rows * 4, hipMemcpyHostToDevice));
+    if (chosen) OPC(hipMemcpy(dc.p, chosen, (size_t)rows * 4, hipMemcpyHostToDevice));
+    OPC(hipMemset(dobs.p, 0, (size_t)kSpecRows * 4)); OPC(hipMemset(dmu.p, 0, (size_t)kSpecRows * 4));
+    EntropyRowsArgs a{};
+    a.rows = dl.as<float>(); a.ld = ld; a.n = n; a.temp = temperature; a.typical_p = e->typical_p; a.mirostat = e->mirostat; a.tau = e->tau; a.eta = e->eta;
+    a.mu = mu ? dm.as<float>() : nullptr; a.sort_buf = dsort.as<unsigned long long>();
+    a.chosen = chosen ? dc.as<int>() : nullptr; a.obs_out = dobs.as<float>(); a.mu_out = dmu.as<float>();
+    int r = launch_entropy_rows(nullptr, 0, a, rows); if (r) return r;
+    OPC(hipDeviceSynchronize());
+    for (int i = 0; i < rows; ++i) OPC(hipMemcpy(out + (size_t)i * n, dl.as<float>() + (size_t)i * ld, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (obs_out) OPC(hipMemcpy(obs_out, dobs.p, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    if (mu_out) OPC(hipMemcpy(mu_out, dmu.p, (size_t)rows * 4, hipMemcpyDeviceToHost));
+    return FLM_OK;
+}
+
 int flm_op_swiglu(float* xo, const float* xr, size_t n) {
     if (!xo || !xr || n == 0) return FLM_ERR_INVALID;
     DevBuf a, b; if (a.alloc(n * 4) || b.alloc(n * 4)) return FLM_ERR_OOM;

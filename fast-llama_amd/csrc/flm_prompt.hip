@@ -240,6 +240,22 @@ int launch_sample_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, 
     HIPC(c, hipGetLastError());
     return FLM_OK;
 }
+int launch_entropy_rows(flm_ctx* c, hipStream_t st, const EntropyRowsArgs& a, int rows) {
+    {   // the strip of a large vocabulary: the dynamic-LDS limit, once per device
+        static std::mutex mu; static bool done[64] = {false};
+        int dev = 0; HIPC(c, hipGetDevice(&dev));
+        std::lock_guard<std::mutex> lk(mu);
+        if (dev >= 0 && dev < 64 && !done[dev]) {
+            HIPC(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_entropy_rows), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
+            done[dev] = true;
+        }
+    }
+    if (rows < 1 || rows > kSpecRows) return fail(c, FLM_ERR_INVALID, "entropy_rows: rows outside a batch of 16");
+    if (a.n < 2 || a.ld < a.n || sample_lds_bytes(a.n) > kLdsMax) return fail(c, FLM_ERR_UNSUPPORTED, "entropy_rows: the row does not fit one workgroup's LDS strip");
+    hipLaunchKernelGGL(k_entropy_rows, dim3(rows), dim3(kSampleBlock), sample_lds_bytes(a.n), st, a);
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
 int launch_shape_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, float* out, int ld_out, int n, int row0, int rows, const ShapeParams* p,
                       const int* win, int n_win, const int* drafts, const DfaBlock* dfa, int cstate, int* states_out) {
     if (rows < 1 || row0 < 0 || row0 + rows > kSpecRows) return fail(c, FLM_ERR_INVALID, "shape_rows: rows outside a batch of 16");
@@ -289,6 +305,10 @@ static int score_classify_t(flm_ctx* c, int row0, int m, float* stage, bool skin
                 rows = c->lp_side;
             }
             r = launch_shape_rows(c, st, stage, V, rows, V, V, row0, m, draw->shape, draw->win, draw->n_win, c->prompt_dev + 1, c->dfa_blk, draw->cstate); if (r) return r;
+        }
+        if (draw && draw->temperature != 0.0f && typical_on(draw->typical_p)) {   // flm_entropy_set, typical: stage 5 on every row, in place (a function of the row alone)
+            EntropyRowsArgs ea{}; ea.rows = rows; ea.ld = V; ea.n = V; ea.temp = draw->temperature; ea.typical_p = draw->typical_p; ea.sort_buf = c->sort_buf;
+            r = launch_entropy_rows(c, st, ea, m); if (r) return r;
         }
         if (draw && draw->temperature != 0.0f) {              // the sampled verify pass: row row0 + i drawn with the (row0 + i + 1)-th coin of the step's state
             r = launch_sample_rows(c, st, rows, V, V, row0, m, draw->temperature, draw->topp, draw->base, c->sort_buf, argmax_out); if (r) return r;

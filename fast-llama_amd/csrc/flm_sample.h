@@ -108,6 +108,79 @@ __device__ __forceinline__ void wave_excl_scan256(const int* in, int* out) {
     out[4 * lane] = e; out[4 * lane + 1] = e + a0; out[4 * lane + 2] = e + a0 + a1; out[4 * lane + 3] = e + a0 + a1 + a2;
 }
 
+// The stable LSD radix sort of sample_draw's candidates (and of flm_entropy.h's), by one 1024-thread workgroup, in two steps.  cand(i, key): index i < n is a candidate, and
+// its 32-bit key; the order is ascending key, equal keys by ascending index.  hist: 4 * 256 words, misc: sample_draw's ([33] the count, [36..39] "digit d is the same in every
+// candidate").
+// sort_count: the candidates' digit histograms and their number (returned to every thread)
+template <class CF>
+__device__ __forceinline__ int sort_count(CF cand, const int n, int* const hist, int* const misc) {
+    const int t = threadIdx.x, lane = t & 63;
+    for (int k = t; k < 4 * 256; k += kSampleBlock) hist[k] = 0;
+    if (t < 8) misc[32 + t] = 0;
+    __syncthreads();
+    int mine = 0;
+    for (int i = t; i < n; i += kSampleBlock) {
+        unsigned key;
+        if (cand(i, key)) {
+            ++mine;
+#pragma unroll
+            for (int d = 0; d < 4; ++d) atomicAdd(&hist[d * 256 + ((key >> (8 * d)) & 255u)], 1);
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, kWave);
+    if (lane == 0) atomicAdd(&misc[33], mine);
+    __syncthreads();
+    const int n0 = misc[33];
+    for (int k = t; k < 4 * 256; k += kSampleBlock) if (n0 > 0 && hist[k] == n0) misc[36 + (k >> 8)] = 1;
+    __syncthreads();
+    return n0;
+}
+// sort_run (behind sort_count, n0 > 0): the passes, index order in -- ties keep ascending index.  The first pass reads the candidates through cand (and filters), the others
+// a half of sort_buf [2][n].  Returns the sorted entries {key << 32 | index} [n0]: one of the halves
+template <class CF>
+__device__ __forceinline__ const unsigned long long* sort_run(CF cand, const int n, const int n0, unsigned long long* sort_buf, int* const cnt, int* const dbase, int* const hist, int* const misc) {
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    bool any = false;
+#pragma unroll 1
+    for (int d = 0; d < 4; ++d) any = any || !misc[36 + d];
+    int src = -1;                                                 // -1: the strip; 0 / 1: sort_buf half
+#pragma unroll 1
+    for (int d = 0; d < 4; ++d) {
+        if (misc[36 + d] && (any || d < 3 || src >= 0)) continue;          // (a digit equal in every candidate orders nothing; one pass runs in any case)
+        if (w == 0) wave_excl_scan256(hist + d * 256, dbase);
+        const int dstb = src < 0 ? 0 : src ^ 1;
+        const unsigned long long* sb = sort_buf + (size_t)(src < 0 ? 0 : src) * n;
+        unsigned long long* db = sort_buf + (size_t)dstb * n;
+        const int N = src < 0 ? n : n0;
+#pragma unroll 1
+        for (int b0 = 0; b0 < N; b0 += kSampleBlock) {
+            const int i = b0 + t;
+            bool valid = i < N;
+            unsigned long long e = 0ull;
+            if (src < 0) {
+                unsigned key = 0u;
+                valid = valid && cand(i, key);
+                e = ((unsigned long long)key << 32) | (unsigned)i;
+            } else if (valid) e = sb[i];
+            const unsigned dig = (unsigned)(e >> (32 + 8 * d)) & 255u;
+            for (int k = t; k < kSampleWaves * 256; k += kSampleBlock) cnt[k] = 0;
+            unsigned long long m = __ballot(valid);
+#pragma unroll
+            for (int bb = 0; bb < 8; ++bb) { const unsigned long long bm = __ballot((dig >> bb) & 1u); m &= ((dig >> bb) & 1u) ? bm : ~bm; }
+            const int rank = __popcll(m & ((1ull << lane) - 1ull));
+            __syncthreads();
+            if (valid && rank == 0) cnt[w * 256 + dig] = __popcll(m);
+            __syncthreads();
+            if (t < 256) { int run = dbase[t]; for (int k = 0; k < kSampleWaves; ++k) { const int c = cnt[k * 256 + t]; cnt[k * 256 + t] = run; run += c; } dbase[t] = run; }
+            __syncthreads();
+            if (valid) db[cnt[w * 256 + dig] + rank] = e;
+            __syncthreads();
+        }
+        src = dstb;
+    }
+    return sort_buf + (size_t)src * n;
+}
+
 // ONE draw of Sampler::sample by one workgroup of 1024 threads: the token for `logits[0 .. n)` at (temp, topp), n >= 2, with the coin drawn from `rng` (advanced by that one
 // draw; untouched at temp == 0).  strip: sample_lds_bytes(n) of LDS; sort_buf: [2][n] of the workgroup's own.  Every thread returns the token.  Both sampler kernels are this
 // function: k_sample_advance (the token path: one row, then the decode state's advance) and k_sample_rows (a verify batch: one workgroup per row).
@@ -161,27 +234,10 @@ __device__ __forceinline__ int sample_draw(const float* logits, int n, float tem
         } else {
             const float cutoff = __fdiv_rn(__fsub_rn(1.0f, topp), (float)(n - 1));
             int n0 = 0;
+            // the candidates and their keys: inverted probability bits -- ascending key = descending probability
+            auto cand = [&](int i, unsigned& key) { const float p = strip[spos(i)]; key = ~__float_as_uint(p); return p >= cutoff; };
             if (coin != 0.0f) {
-                // the candidates' digit histograms (the keys: inverted probability bits -- ascending key = descending probability), their count
-                for (int k = t; k < 4 * 256; k += kSampleBlock) hist[k] = 0;
-                if (t < 8) misc[32 + t] = 0;
-                __syncthreads();
-                int mine = 0;
-                for (int i = t; i < n; i += kSampleBlock) {
-                    const float p = strip[spos(i)];
-                    if (p >= cutoff) {
-                        const unsigned key = ~__float_as_uint(p);
-                        ++mine;
-#pragma unroll
-                        for (int d = 0; d < 4; ++d) atomicAdd(&hist[d * 256 + ((key >> (8 * d)) & 255u)], 1);
-                    }
-                }
-                for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, kWave);
-                if (lane == 0) atomicAdd(&misc[33], mine);
-                __syncthreads();
-                n0 = misc[33];
-                for (int k = t; k < 4 * 256; k += kSampleBlock) if (n0 > 0 && hist[k] == n0) misc[36 + (k >> 8)] = 1;
-                __syncthreads();
+                n0 = sort_count(cand, n, hist, misc);
             }
             if (coin == 0.0f || n0 == 0) {
                 // coin 0: r = 0 * cum = 0 < cdf at the first sorted element -- the lowest index among the maximal probabilities.  (n0 == 0, reachable only for
@@ -189,45 +245,7 @@ __device__ __forceinline__ int sample_draw(const float* logits, int n, float tem
                 tok = block_first_max([&](int i) { return strip[spos(i)]; }, n, 0, misc);
             } else {
                 // stable LSD radix sort of the candidates, index order in: ties keep ascending index.  The first pass reads the strip (and filters), the others a buffer.
-                bool any = false;
-#pragma unroll 1
-                for (int d = 0; d < 4; ++d) any = any || !misc[36 + d];
-                int src = -1;                                                 // -1: the strip; 0 / 1: sort_buf half
-#pragma unroll 1
-                for (int d = 0; d < 4; ++d) {
-                    if (misc[36 + d] && (any || d < 3 || src >= 0)) continue;          // (a digit equal in every candidate orders nothing; one pass runs in any case)
-                    if (w == 0) wave_excl_scan256(hist + d * 256, dbase);
-                    const int dstb = src < 0 ? 0 : src ^ 1;
-                    const unsigned long long* sb = sort_buf + (size_t)(src < 0 ? 0 : src) * n;
-                    unsigned long long* db = sort_buf + (size_t)dstb * n;
-                    const int N = src < 0 ? n : n0;
-#pragma unroll 1
-                    for (int b0 = 0; b0 < N; b0 += kSampleBlock) {
-                        const int i = b0 + t;
-                        bool valid = i < N;
-                        unsigned long long e = 0ull;
-                        if (src < 0) {
-                            const float p = valid ? strip[spos(i)] : 0.0f;
-                            valid = valid && p >= cutoff;
-                            e = ((unsigned long long)(~__float_as_uint(p)) << 32) | (unsigned)i;
-                        } else if (valid) e = sb[i];
-                        const unsigned dig = (unsigned)(e >> (32 + 8 * d)) & 255u;
-                        for (int k = t; k < kSampleWaves * 256; k += kSampleBlock) cnt[k] = 0;
-                        unsigned long long m = __ballot(valid);
-#pragma unroll
-                        for (int bb = 0; bb < 8; ++bb) { const unsigned long long bm = __ballot((dig >> bb) & 1u); m &= ((dig >> bb) & 1u) ? bm : ~bm; }
-                        const int rank = __popcll(m & ((1ull << lane) - 1ull));
-                        __syncthreads();
-                        if (valid && rank == 0) cnt[w * 256 + dig] = __popcll(m);
-                        __syncthreads();
-                        if (t < 256) { int run = dbase[t]; for (int k = 0; k < kSampleWaves; ++k) { const int c = cnt[k * 256 + t]; cnt[k * 256 + t] = run; run += c; } dbase[t] = run; }
-                        __syncthreads();
-                        if (valid) db[cnt[w * 256 + dig] + rank] = e;
-                        __syncthreads();
-                    }
-                    src = dstb;
-                }
-                const unsigned long long* sorted = sort_buf + (size_t)src * n;
+                const unsigned long long* sorted = sort_run(cand, n, n0, sort_buf, cnt, dbase, hist, misc);
                 // the sorted probabilities as a strip of their own; cum = the chain up to the first element where cum > topp (last), r = coin * cum,
                 // then the first element up to last with r < cdf -- the same chain again
                 const int B2 = sample_lane_elems(n0), LS2 = B2 + 4;
@@ -259,21 +277,18 @@ __device__ __forceinline__ unsigned* sample_misc(float* strip, int n) {
 }
 static_assert(40 + kStopLdsWords <= 64, "the stop matcher's words fit behind sample_draw's");
 
-// One workgroup of 1024 threads, sample_lds_bytes(n) of dynamic LDS, n >= 2.  Writes out_tokens[step], advances the state like k_argmax_advance, and the sampler state.
+// The tail of a sampled token, by the whole workgroup behind the draw of `tok` (k_sample_advance, and flm_entropy.h's k_entropy_advance): the stop rules, out_tokens[step],
+// the token's last act, the decode state's advance, the sampler state's write-back.
 // a.stop given, not empty, and the call one that honours rules in the token form (DecodeState::stop_rules, set by flm_generate_ex alone): the stop rules are
 // matched against out_tokens[0 .. step) ++ tok by the whole workgroup (flm_stop.h) in front of the last act, which then halts as on the stop token.  The ids of THIS
 // attempt lie in out_tokens from index 0 on (a retried attempt rewrites them before it reads them), and every read stays below out_cap.
-inline __global__ void __launch_bounds__(kSampleBlock) k_sample_advance(const SampleArgs a) {
-    extern __shared__ float4 sample_lds4[];
-    if (halted(&a.st->halt)) return;       // (flm_math.h DecodeState::halt: the sampler state stays at the last drawn token's)
-    unsigned long long rng = a.sp->rng;
-    const int tok = sample_draw(a.logits, a.n, a.sp->temperature, a.sp->topp, rng, a.sort_buf, reinterpret_cast<float*>(sample_lds4));
+__device__ __forceinline__ void sample_finish(const SampleArgs& a, const int tok, const unsigned long long rng, float* const strip) {
     bool fired = false;
     if (stop_armed(a.stop) && a.out_tokens != nullptr && a.st->stop_rules != 0) {       // (uniform: every thread takes the same branch)
         const int step = a.st->step;                                                   // (written behind the matcher's barrier only: by thread 0, below)
         const int* const ot = a.out_tokens; const int cap = a.out_cap;
         if (step >= 0 && step < cap)
-            fired = stop_match(a.stop, tok, [&](int j) { return j < cap ? ot[j] : -1; }, step, sample_misc(reinterpret_cast<float*>(sample_lds4), a.n) + 40).kind != 0;
+            fired = stop_match(a.stop, tok, [&](int j) { return j < cap ? ot[j] : -1; }, step, sample_misc(strip, a.n) + 40).kind != 0;
     }
     if (threadIdx.x == 0) {
         DecodeState* st = a.st;
@@ -283,6 +298,15 @@ inline __global__ void __launch_bounds__(kSampleBlock) k_sample_advance(const Sa
         st->step += 1;
         a.sp->rng = rng;
     }
+}
+// One workgroup of 1024 threads, sample_lds_bytes(n) of dynamic LDS, n >= 2.  Writes out_tokens[step], advances the state like k_argmax_advance, and the sampler state
+// (sample_finish).
+inline __global__ void __launch_bounds__(kSampleBlock) k_sample_advance(const SampleArgs a) {
+    extern __shared__ float4 sample_lds4[];
+    if (halted(&a.st->halt)) return;       // (flm_math.h DecodeState::halt: the sampler state stays at the last drawn token's)
+    unsigned long long rng = a.sp->rng;
+    const int tok = sample_draw(a.logits, a.n, a.sp->temperature, a.sp->topp, rng, a.sort_buf, reinterpret_cast<float*>(sample_lds4));
+    sample_finish(a, tok, rng, reinterpret_cast<float*>(sample_lds4));
 }
 
 // The same draw over the rows of a verify batch's classifier chunk: one workgroup per row, grid = the chunk's rows, sample_lds_bytes(n) of dynamic LDS.  Row r of the

@@ -394,8 +394,14 @@ layers_done:
                     SampleArgs sa{};
                     sa.logits = c->shape_row; sa.n = d.vocab_size; sa.sp = c->sparams; sa.st = c->state; sa.out_tokens = c->out_tokens_dev; sa.out_cap = c->out_cap; sa.advance = 1; sa.sort_buf = c->sort_buf; sa.err = c->xwg_err;
                     sa.stop = c->stop_blk;                                             // (the stop rules: the shaped forms only, flm_stop.h)
-                    hipLaunchKernelGGL(k_sample_advance, dim3(1), dim3(kSampleBlock), sample_lds_bytes(d.vocab_size), st, sa);
+                    if (form == TokenForm::ShapedEnt) {                                // flm_entropy_set: the stage, the draw, mu's update and the tail in one launch (flm_entropy.h)
+                        if (!c->ent_blk) return fail(c, FLM_ERR_UNSUPPORTED, "entropy token: no device block");
+                        hipLaunchKernelGGL(k_entropy_advance, dim3(1), dim3(kSampleBlock), sample_lds_bytes(d.vocab_size), st, EntropyArgs{sa, c->ent_blk});
+                    } else {
+                        hipLaunchKernelGGL(k_sample_advance, dim3(1), dim3(kSampleBlock), sample_lds_bytes(d.vocab_size), st, sa);
+                    }
                 } else {          // (the entry points admit temperature 0 only here: the first maximum of the shaped row)
+                    if (form == TokenForm::ShapedEnt) return fail(c, FLM_ERR_UNSUPPORTED, "entropy token: vocabulary too large for one workgroup's LDS");
                     hipLaunchKernelGGL(k_argmax_advance, dim3(1), dim3(1024), 0, st, (const float*)c->shape_row, d.vocab_size, c->state, c->out_tokens_dev, 1, c->out_cap, (const int*)c->xwg_err);
                 }
                 HIPC(c, hipGetLastError());

@@ -234,6 +234,7 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
         _stop_installed = true;
     }
     if (_lp_top_n >= 0 && _ctxs.size() != 1) { _err = "--logprobs: one device only"; fprintf(stderr, "%s\n", _err.c_str()); return false; }
+    if (_lp_top_n >= 0 && _ent_set) { _err = "--logprobs cannot be combined with --typical / --mirostat (not built)"; fprintf(stderr, "%s\n", _err.c_str()); return false; }
     int prev = -1;
     auto emit = [&](int tok, int index, int n_cur) {
         const std::string piece = _tok.decode(tok, prev);
@@ -283,8 +284,16 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
         if (lp && (!dev_ok || flm_logprobs_arm(_ctxs[0], _lp_top_n, _lp_shaped ? FLM_LOGPROBS_SHAPED : FLM_LOGPROBS_RAW) != FLM_OK)) {
             _err = std::string("--logprobs: ") + (dev_ok ? flm_last_error(_ctxs[0]) : "the constraint could not be armed on the device"); fprintf(stderr, "%s\n", _err.c_str()); return false;
         }
+        bool ent_dev = false;               // --typical / --mirostat: set before every run (Mirostat's state starts over); refused as unsupported: the host loop below runs the stages
+        if (_ent_set && dev_ok) {
+            const int er = flm_entropy_set(_ctxs[0], &_ent);
+            if (er != FLM_OK && er != FLM_ERR_UNSUPPORTED) { _err = std::string("--typical / --mirostat: ") + flm_last_error(_ctxs[0]); fprintf(stderr, "%s\n", _err.c_str()); return false; }
+            ent_dev = er == FLM_OK;
+        }
+        if (_stop_set && _ent_set && !ent_dev) { _err = "--stop-ids / --stop-seq / --stop need the device loop, and --typical / --mirostat could not be set there (the library refused: a vocabulary beyond the device sampler): drop one of the two"; fprintf(stderr, "%s\n", _err.c_str()); return false; }
         if (_stop_set && !dev_ok) { _err = "--stop-ids / --stop-seq / --stop need the device loop, and --constraint could not be installed there (the library refused the automaton): drop one of the two"; fprintf(stderr, "%s\n", _err.c_str()); return false; }
-        if (dev_ok && (_shape_set || armed || lp || _stop_set)) {          // the sampling controls / the constraint: the same loop with the shaping stage on the device (flm_generate_ex; no control flag: neutral controls, masking only); refused: the host loop below shapes
+        if (_ent_set && !ent_dev) { whole = false; rc = FLM_ERR_UNSUPPORTED; }
+        else if (dev_ok && (_shape_set || armed || lp || _stop_set || ent_dev)) {          // the sampling controls / the constraint: the same loop with the shaping stage on the device (flm_generate_ex; no control flag: neutral controls, masking only); refused: the host loop below shapes
             flm_sampling sp{};
             sp.temperature = temperature; sp.topp = topp; sp.top_k = _shape.top_k; sp.min_p = _shape.min_p; sp.repeat_penalty = _shape.repeat_penalty;
             sp.frequency_penalty = _shape.frequency_penalty; sp.presence_penalty = _shape.presence_penalty; sp.penalty_last_n = _shape_last_n;
@@ -324,7 +333,7 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
             count();
             whole = draft && rc == FLM_ERR_UNSUPPORTED;
         }
-        if (!dev_ok) { whole = false; rc = FLM_ERR_UNSUPPORTED; }
+        if (!dev_ok || (_ent_set && !ent_dev)) { whole = false; rc = FLM_ERR_UNSUPPORTED; }
         if (whole) rc = flm_generate(_ctxs[0], input.data(), n_in, 0, want, temperature, topp, &st, 0, on_token, &sink, nullptr, &n_out);
         if (rc == FLM_OK) {
             if (!greedy) _sampler.set_state(st);
@@ -336,7 +345,8 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
     }
     // the sampling controls where the loop is the host's: the logits come back, shape_logits runs over the window (the last penalty_last_n ids of the prompt and what was
     // generated since), then the host sampler -- what flm_generate_ex computes on the device
-    const bool shaped = _shape_set || _dfa_set;
+    const bool shaped = _shape_set || _dfa_set || _ent_set;
+    float mu = _ent.mu;                     // --mirostat on the host: the running state, from its start
     int q = 0;                              // --constraint on the host: the automaton's state, from 0
     std::vector<int32_t> history;
     if (shaped) history.assign(input.begin(), input.end());
@@ -398,7 +408,12 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
                 const int w = (int)history.size() < _shape_last_n ? (int)history.size() : _shape_last_n;
                 if (_dfa_set) constrain_logits(logits.data(), _cfg.vocab_size, _dfa_tok.data() + _dfa_row[q], _dfa_row[q + 1] - _dfa_row[q], logits.data());      // step 0, in place
                 shape_logits(logits.data(), _cfg.vocab_size, temperature, _shape, history.data() + (history.size() - w), w, shaped_row.data());
-                next = _sampler.sample(shaped_row.data(), temperature, topp);
+                const bool miro = _ent_set && _ent.mirostat == 2 && temperature != 0.0f;
+                if (_ent_set) entropy_logits(shaped_row.data(), _cfg.vocab_size, temperature, _ent.typical_p, _ent.mirostat, mu, shaped_row.data());      // stages 5 / 6, in place
+                std::vector<float> masked;
+                if (miro) masked = shaped_row;          // (the sampler overwrites its row: the update reads the masked logits)
+                next = _sampler.sample(shaped_row.data(), temperature, miro ? 1.0f : topp);
+                if (miro) mu = mirostat_update(masked.data(), _cfg.vocab_size, temperature, next, _ent.tau, _ent.eta, mu, nullptr);
                 if (_dfa_set) q = dfa_next(_dfa_row.data(), _dfa_tok.data(), _dfa_nxt.data(), q, next);
                 history.push_back(next);
             } else if (rc == FLM_OK) next = _sampler.sample(logits.data(), temperature, topp);

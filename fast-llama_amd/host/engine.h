@@ -62,6 +62,9 @@ public:
     // --logprobs N[,shaped] (this build only): the context is armed with flm_logprobs_arm before every generate on one device, the run takes the _ex path as an armed
     // constraint does, and the records of the last generate are kept for the caller: one flm_logprob per delivered token
     void set_logprobs(int top_n, bool shaped) { _lp_top_n = top_n; _lp_shaped = shaped; }
+    // --typical / --mirostat: flm_entropy_set before every generate (Mirostat's state starts at e.mu each time); the run is flm_generate_ex (with --draft / --lookup and
+    // typical: flm_generate_lookup_ex); where the loop is the host's, entropy_logits / mirostat_update behind shape_logits: the same ids.  Not together with --logprobs
+    void set_entropy(const flm_entropy& e) { _ent = e; _ent_set = e.mirostat == 2 || (e.typical_p > 0.0f && e.typical_p < 1.0f); }
     const std::vector<flm_logprob>& logprobs() const { return _lp; }
     // --stop-ids / --stop-seq / --stop (this build only, one device): stop rules next to the loop's own stop on token 0 (flm_stop_rules).  ids: the stop ids; seqs: id
     // sequences; strs: strings, each tokenised ONCE by this tokenizer without BOS when the model is loaded and matched token by token on that one tokenisation (text that
@@ -101,6 +104,7 @@ private:
     bool _stop_set = false, _stop_installed = false; std::vector<int32_t> _stop_ids; std::vector<std::vector<int32_t>> _stop_seqs; std::vector<std::string> _stop_strs;
     int _stop_reason = -1, _stop_rule = 0;
     bool _dfa_set = false, _dfa_installed = false; std::vector<int32_t> _dfa_row, _dfa_tok, _dfa_nxt;
+    bool _ent_set = false; flm_entropy _ent{};
     bool _shape_set = false; ShapeControls _shape; int _shape_last_n = 0; std::vector<int32_t> _bias_ids; std::vector<float> _bias_values;
 };
 

@@ -17,6 +17,7 @@
 #include <initializer_list>
 #include <iostream>
 #include <string>
+#include <cmath>
 #include <utility>
 #include <vector>
 
@@ -43,6 +44,8 @@ struct Args {
     // the sampling controls (flm_sampling): any of these flags switches the shaping stage on
     bool shape_set = false; ShapeControls shape; int repeat_last_n = 64;
     std::vector<int32_t> bias_ids; std::vector<float> bias_values; const char* bad_sampling = nullptr;
+    // --typical P / --mirostat 2 [--mirostat-ent TAU] [--mirostat-lr ETA]: the entropy-driven samplers (flm_entropy); mu starts at 2 TAU
+    bool ent_set = false; float typical = 0.0f; int mirostat = 0; float miro_tau = 5.0f, miro_eta = 0.1f;
     int logprobs_n = -1; bool logprobs_shaped = false; const char* bad_logprobs = nullptr;   // --logprobs N[,shaped]: top-N alternatives per generated token (0..20; -1 = off), from the raw or the shaped row
     // --stop-ids a,b,... / --stop-seq a,b,... (repeatable) / --stop STR (repeatable): stop rules next to the loop's own stop on token 0
     std::vector<int32_t> stop_ids; std::vector<std::vector<int32_t>> stop_seqs; std::vector<std::string> stop_strs; const char* bad_stop = nullptr;
@@ -77,6 +80,10 @@ void usage(const char* bin) {
     fprintf(stderr, "   --presence-penalty  <float>   subtracted once from every token of the window, 0 = off (this build only)\n");
     fprintf(stderr, "   --frequency-penalty <float>   subtracted per occurrence in the window, 0 = off (this build only)\n");
     fprintf(stderr, "   --logit-bias      <id=val[,id=val...]>  added to these tokens' logits; -inf bans a token; at most 256 pairs (this build only)\n");
+    fprintf(stderr, "   --typical         <float>     locally typical sampling: keep the tokens whose surprise is closest to the distribution's entropy, up to this probability mass, (0, 1), 1 = off (this build only)\n");
+    fprintf(stderr, "   --mirostat        <0|2>       2: Mirostat v2 -- keep the tokens whose surprise (bits) is at most a running state that follows --mirostat-ent; top-p is ignored; 0 = off (this build only)\n");
+    fprintf(stderr, "   --mirostat-ent    <float>     Mirostat's target entropy tau, default 5; the state starts at 2 tau (this build only)\n");
+    fprintf(stderr, "   --mirostat-lr     <float>     Mirostat's learning rate eta, default 0.1 (this build only)\n");
     fprintf(stderr, "   --constraint      <file>      mask every generated token with a token-level DFA, armed at state 0: a `flm-dfa 1 <n_states>` line, then `state token next` per line (this build only)\n");
     fprintf(stderr, "   --logprobs        <N[,shaped]>  on one device: after the text, one line per generated token `index id logprob | id:logprob ...` with the N (0..20) most likely alternatives, from the model's own distribution or (shaped) the row the sampler read (this build only)\n");
     fprintf(stderr, "   --stop-ids        <a,b,...>   on one device: end the output at the first of these token ids too (delivered, like token 0), at most 64 distinct ids (this build only)\n");
@@ -181,6 +188,10 @@ const Flag kFlags[] = {
     {nullptr, "--repeat-last-n",     true, [](Args& a, const char* v) { char* e; const long k = strtol(v, &e, 10); a.shape_set = true; if (e == v || *e || k < 0 || k > 1024) a.bad_sampling = v; else a.repeat_last_n = (int)k; }},         // (this build only)
     {nullptr, "--presence-penalty",  true, [](Args& a, const char* v) { a.shape_set = true; if (!parse_float(v, a.shape.presence_penalty) || a.shape.presence_penalty != a.shape.presence_penalty) a.bad_sampling = v; }},               // (this build only)
     {nullptr, "--frequency-penalty", true, [](Args& a, const char* v) { a.shape_set = true; if (!parse_float(v, a.shape.frequency_penalty) || a.shape.frequency_penalty != a.shape.frequency_penalty) a.bad_sampling = v; }},            // (this build only)
+    {nullptr, "--typical",           true, [](Args& a, const char* v) { a.ent_set = true; if (!parse_float(v, a.typical) || a.typical != a.typical) a.bad_sampling = v; }},                                                          // (this build only)
+    {nullptr, "--mirostat",          true, [](Args& a, const char* v) { char* e; const long k = strtol(v, &e, 10); a.ent_set = true; if (e == v || *e || (k != 0 && k != 2)) a.bad_sampling = v; else a.mirostat = (int)k; }},          // (this build only)
+    {nullptr, "--mirostat-ent",      true, [](Args& a, const char* v) { a.ent_set = true; if (!parse_float(v, a.miro_tau) || !std::isfinite(a.miro_tau)) a.bad_sampling = v; }},                                                     // (this build only)
+    {nullptr, "--mirostat-lr",       true, [](Args& a, const char* v) { a.ent_set = true; if (!parse_float(v, a.miro_eta) || !std::isfinite(a.miro_eta)) a.bad_sampling = v; }},                                                     // (this build only)
     {nullptr, "--logprobs",          true, [](Args& a, const char* v) { if (!parse_logprobs(v, a.logprobs_n, a.logprobs_shaped)) a.bad_logprobs = v; }},                                                                          // (this build only)
     {nullptr, "--stop-ids",          true, [](Args& a, const char* v) {                                                                                                                                                             // (this build only)
         std::vector<int32_t> ids; bool ok = parse_ids(v, FLM_STOP_IDS_MAX, ids);
@@ -207,7 +218,8 @@ void parse(Args& a, int argc, const char** argv) {
     }
     if (a.bad_lookup) { fprintf(stderr, "Invalid --lookup:\x1b[31m%s\x1b[0m (expected K or K,G with 4 <= K <= 15 and 1 <= G <= 8)\n", a.bad_lookup); usage(argv[0]); exit(-1); }
     if (a.bad_draft) { fprintf(stderr, "Invalid --draft:\x1b[31m%s\x1b[0m (expected K or K,G with 4 <= K <= 15 and 1 <= G <= 8)\n", a.bad_draft); usage(argv[0]); exit(-1); }
-    if (a.bad_sampling) { fprintf(stderr, "Invalid sampling control:\x1b[31m%s\x1b[0m (--top-k >= 0, --min-p in [0, 1), --repeat-penalty > 0, --repeat-last-n 0..1024, --logit-bias id=val[,id=val...] with at most 256 pairs)\n", a.bad_sampling); usage(argv[0]); exit(-1); }
+    if (!a.bad_sampling && a.mirostat == 2 && a.typical > 0.0f && a.typical < 1.0f) a.bad_sampling = "--typical together with --mirostat 2";
+    if (a.bad_sampling) { fprintf(stderr, "Invalid sampling control:\x1b[31m%s\x1b[0m (--top-k >= 0, --min-p in [0, 1), --repeat-penalty > 0, --repeat-last-n 0..1024, --logit-bias id=val[,id=val...] with at most 256 pairs, --typical a number, --mirostat 0 or 2 with finite --mirostat-ent / --mirostat-lr, never --typical in (0, 1) together with --mirostat 2)\n", a.bad_sampling); usage(argv[0]); exit(-1); }
     if (a.bad_logprobs) { fprintf(stderr, "Invalid --logprobs:\x1b[31m%s\x1b[0m (expected N or N,shaped with 0 <= N <= 20)\n", a.bad_logprobs); usage(argv[0]); exit(-1); }
     if (!a.bad_stop && a.stop_seqs.size() + a.stop_strs.size() > (size_t)FLM_STOP_SEQS_MAX) a.bad_stop = "more than 16 --stop-seq / --stop";
     if (a.bad_stop) { fprintf(stderr, "Invalid stop rule:\x1b[31m%s\x1b[0m (--stop-ids a,b,... with at most 64 distinct ids >= 0; --stop-seq a,b,... with 1 to 32 ids >= 0; --stop a non-empty string; at most 16 sequences and strings)\n", a.bad_stop); usage(argv[0]); exit(-1); }
@@ -307,6 +319,7 @@ int main(int argc, const char** argv) {
     GpuTransformer tf(args.detail || args.debug);
     if (args.constraint) tf.set_constraint(args.dfa_row, args.dfa_tok, args.dfa_nxt);
     if (args.shape_set) tf.set_sampling(args.shape, args.repeat_last_n, args.bias_ids, args.bias_values);
+    if (args.ent_set) tf.set_entropy(flm_entropy{args.typical, args.mirostat, args.miro_tau, args.miro_eta, 2.0f * args.miro_tau});
     if (args.logprobs_n >= 0) tf.set_logprobs(args.logprobs_n, args.logprobs_shaped);
     if (stop_set) tf.set_stop(args.stop_ids, args.stop_seqs, args.stop_strs);
     if (args.lookup_k) tf.set_lookup(args.lookup_k, args.lookup_g);

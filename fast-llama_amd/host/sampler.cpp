@@ -1,4 +1,5 @@
 #include "sampler.h"
+#include "../csrc/flm_logf.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -129,6 +130,66 @@ void logprob_row(const float* R, int n, int chosen, int top_n, LogprobRecord* ou
     r.n_top = K;
     for (int j = 0; j < K; ++j) r.top_logit[j] = R[r.top_id[j]];
     *out = r;
+}
+
+namespace {
+// the statistics of a row at temperature T: d[n], e[n]; returns the sequential sum
+struct RowStats { std::vector<float> d, e; float sum = 0.f; int first_max = 0; };
+void row_stats(const float* R, int n, float T, RowStats& s) {
+    s.d.resize(n); s.e.resize(n);
+    for (int i = 0; i < n; ++i) s.d[i] = R[i] / T;
+    float mx = s.d[0]; s.first_max = 0;
+    for (int i = 1; i < n; ++i) if (s.d[i] > mx) { mx = s.d[i]; s.first_max = i; }
+    float sum = 0.f;
+    for (int i = 0; i < n; ++i) {
+        const float d = s.d[i] - mx;
+        s.d[i] = d;
+        s.e[i] = d < -15 ? 0.f : expf(d);
+        sum += s.e[i];
+    }
+    s.sum = sum;
+}
+}
+
+int entropy_logits(const float* R, int n, float T, float typical_p, int mirostat, float mu, float* S) {
+    if (S != R) for (int i = 0; i < n; ++i) S[i] = R[i];
+    const bool typ = typical_p > 0.0f && typical_p < 1.0f, miro = mirostat == 2;
+    if (T == 0.0f || !(typ || miro)) return 0;
+    RowStats st; row_stats(R, n, T, st);
+    const float ls = flm_logf(st.sum);
+    int dropped = 0;
+    if (miro) {
+        for (int i = 0; i < n; ++i) {
+            if (st.e[i] == 0.f || i == st.first_max) continue;
+            const float a = ls - st.d[i];
+            if (!(a * 1.44269504f <= mu)) { S[i] = -INFINITY; ++dropped; }
+        }
+        return dropped;
+    }
+    const float inv = (float)(1. / st.sum);
+    std::vector<float> p(n), key(n);
+    float H = 0.f;
+    for (int i = 0; i < n; ++i) {
+        p[i] = st.e[i] * inv;
+        const float h = st.e[i] == 0.f ? 0.f : p[i] * (ls - st.d[i]);
+        H += h;
+    }
+    std::vector<int> idx;
+    for (int i = 0; i < n; ++i) if (st.e[i] != 0.f) { key[i] = fabsf((ls - st.d[i]) - H); idx.push_back(i); }
+    std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return key[a] < key[b]; });
+    float c = 0.f; size_t last = idx.size();
+    for (size_t j = 0; j < idx.size(); ++j) { c += p[idx[j]]; if (c > typical_p) { last = j; break; } }
+    for (size_t j = last + 1; j < idx.size(); ++j) { S[idx[j]] = -INFINITY; ++dropped; }
+    return dropped;
+}
+
+float mirostat_update(const float* S, int n, float T, int t, float tau, float eta, float mu, float* obs_out) {
+    RowStats st; row_stats(S, n, T, st);
+    const float obs = (flm_logf(st.sum) - st.d[t]) * 1.44269504f;
+    if (obs_out) *obs_out = obs;
+    const float err = obs - tau;
+    const float step = eta * err;
+    return mu - step;
 }
 
 } // namespace flmhost

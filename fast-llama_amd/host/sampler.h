@@ -49,4 +49,17 @@ struct LogprobRecord { int32_t token; float logit, max_logit, sum; int32_t n_top
 static_assert(sizeof(LogprobRecord) == 192, "flm_logprob is 192 bytes");
 void logprob_row(const float* R, int n, int chosen, int top_n, LogprobRecord* out);
 
+// The entropy-driven stages behind the shaping stage (include/flm_gpu.h, flm_entropy): a plain sequential restatement of their definition that the
+// device's entropy_row (csrc/flm_entropy.h) equals bit for bit.  R[n] is the row the sampler is about to read, S[n] <- R with -inf at every live entry the stage drops
+// (S may be R).  Statistics: y = R / T, d = y - max y, e = d < -15 ? 0 : expf(d), sum and H sequential in index order, p = e * (float)(1. / sum), surprise a = flm_logf(sum) - d
+// (csrc/flm_logf.h).  Dead entries (e == 0) are never candidates and stay as they are.
+//   typical_p in (0, 1): stage 5 -- the live entries ordered by |a - H| ascending (equal keys by index), kept up to and including the first at which the running sum of p
+//                        passes typical_p
+//   mirostat == 2:       stage 6 -- a live entry stays iff a * 1.44269504f <= mu; the first maximum always stays
+// T == 0, or neither set: S = R.  Returns how many live entries were dropped.  The arguments are taken as valid (never both stages): the C ABI checks them
+int entropy_logits(const float* R, int n, float temperature, float typical_p, int mirostat, float mu, float* S);
+// Mirostat's state behind the draw of id t from the MASKED row S (at topp = 1): obs = (flm_logf(sum') - d[t]) * 1.44269504f with sum' the sequential sum over the masked
+// row, then mu - eta * (obs - tau) in three operations.  *obs_out (may be null): obs
+float mirostat_update(const float* S, int n, float temperature, int t, float tau, float eta, float mu, float* obs_out);
+
 } // namespace flmhost

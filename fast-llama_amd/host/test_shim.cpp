@@ -13,6 +13,7 @@
 #include "sampler.h"
 #include "spec_draft.h"
 #include "tokenizer.h"
+#include "../csrc/flm_logf.h"
 
 using namespace flmhost;
 
@@ -117,6 +118,16 @@ void fh_logprob_layout(int* out9) {
     const int v[9] = {(int)sizeof(flm_logprob), (int)offsetof(flm_logprob, token), (int)offsetof(flm_logprob, logit), (int)offsetof(flm_logprob, max_logit), (int)offsetof(flm_logprob, sum),
                       (int)offsetof(flm_logprob, n_top), (int)offsetof(flm_logprob, top_id), (int)offsetof(flm_logprob, top_logit), (int)offsetof(flm_logprob, pad_)};
     memcpy(out9, v, sizeof v);
+}
+// flm_logf (csrc/flm_logf.h) as the host compiles it: x[n] in place; the expected value of the device's flm_op_logf
+void fh_logf(float* x, size_t n) { for (size_t i = 0; i < n; ++i) x[i] = flm_logf(x[i]); }
+// the entropy-driven stages (sampler.h entropy_logits) on one row: out[n], returns how many live entries were dropped; the expected value of the device's entropy_row
+int fh_entropy(const float* logits, int n, float temperature, float typical_p, int mirostat, float mu, float* out) {
+    return entropy_logits(logits, n, temperature, typical_p, mirostat, mu, out);
+}
+// Mirostat's update behind the draw of id t from the masked row (sampler.h mirostat_update): returns the new mu, *obs the observed surprise
+float fh_mirostat_update(const float* masked, int n, float temperature, int t, float tau, float eta, float mu, float* obs) {
+    return mirostat_update(masked, n, temperature, t, tau, eta, mu, obs);
 }
 // the prompt-lookup drafter of flm_generate_lookup (spec_draft.h): h[n] -> d[k]; the expected value of the device's k_spec_draft
 void fh_spec_draft(const int32_t* h, int n, int k, int ngram_max, int32_t* d) { spec_draft(h, n, k, ngram_max, d); }

@@ -407,6 +407,38 @@ int  flm_last_logprobs(flm_ctx* ctx, int first, int n, flm_logprob* out /* [n] *
  * launches enqueued back to back between one pair of HIP events, on the rows and the decode state the last armed _ex call left (each launch rewrites that call's last record
  * with the same bytes).  FLM_ERR_STATE unless the context is armed and its last _ex call delivered ids. */
 int  flm_logprob_stage_time(flm_ctx* ctx, int iters, float* avg_us);
+/* The entropy-driven samplers: locally typical sampling (llama-family `--typical P`) and Mirostat v2 (`--mirostat 2`, target entropy tau, learning rate eta, running state
+ * mu).  No reference counterpart.  Two more stages, 5 and 6, behind steps 0 - 4 of flm_sampling, on the row R the sampler is about to read (the shaped row S; with every plain
+ * control neutral: the classifier's row).  They act at temperature != 0 only: at temperature 0 both are neutral and mu does not move.  All arithmetic fp32 round-to-nearest
+ * without contraction; the logarithm is flm_logf -- csrc/flm_logf.h: a fixed sequence of IEEE double operations, one function for host and device; within 1 ulp of libm.
+ *   statistics   y = R / T, mx = max y, d = y - mx, e = d < -15 ? 0 : expf(d) (the sampler's clip), sum = the sequential fp32 chain of e in index order,
+ *                p = e * (float)(1.0 / sum), ls = flm_logf of sum, surprise a = ls - d (nats).  Entries with e == 0 are DEAD: never candidates, left untouched
+ *   5 typical    0 < typical_p < 1: H = the sequential chain in index order of h = p * a (dead: 0); key = fabsf(a - H); the live entries ordered by key ascending, equal
+ *                keys by ascending index; c = c + p along that order from 0: the kept set ends with the first entry at which c > typical_p (included; none: all stay);
+ *                every other live entry becomes -inf
+ *   6 mirostat   mirostat == 2: a live entry stays iff a * 1.44269504f <= mu; the first maximum always stays; the others become -inf.  The unchanged sampler then draws id
+ *                t at the call's temperature with topp = 1.0 (multinomial: flm_sampling's topp is ignored).  sum' = the sequential chain over the masked row,
+ *                obs = (flm_logf of sum' - d[t]) * 1.44269504f, then in three operations mu = mu - eta * (obs - tau)
+ * The host restatement is host/sampler.cpp entropy_logits / mirostat_update; the device (csrc/flm_entropy.h) equals it bit for bit.
+ * flm_entropy_validate (pure host arithmetic): FLM_OK, or FLM_ERR_INVALID with flm_last_error(NULL) naming the rule -- typical_p a number, mirostat 0 or 2, tau, eta and mu
+ * finite where mirostat is set, never both stages.
+ * flm_entropy_set is a context setting like flm_logprobs_arm (NULL, or a struct with both stages off: off).  It allocates nothing and re-captures nothing: the parameters
+ * and mu live in a device block that exists since flm_ctx_create, rewritten from the host's copy at the start of every attempt (a retried attempt updates nothing twice), and
+ * the token form -- classifier, k_shape_logits, k_entropy_advance (the stage, the unchanged draw, mu's update, the token's last act: one launch) -- has its graphs built at
+ * flm_prepare next to the shaped ones.  FLM_ERR_UNSUPPORTED on a sharded context and where the vocabulary is beyond the device sampler's LDS strip; FLM_ERR_STATE before
+ * the model is complete.  flm_query "entropy": 0 off, 1 typical, 2 Mirostat.
+ * While set, flm_generate_ex and flm_forward_sample_ex apply the stages; the setting counts as a control that is set (the ids count in "shaped_tokens").  With only
+ * typical_p set, flm_verify_sample_ex, flm_generate_lookup_ex and flm_generate_draft apply stage 5 to every row of a verify batch (k_entropy_rows between the shaper and the
+ * rows' draws): the stage is a function of the row alone, so the ids are flm_generate_ex's.  flm_entropy_mu: the state behind exactly the ids delivered so far, the halting
+ * id's update included (moved by nothing but a verified attempt's commit).  The plain entry points ignore the setting.
+ * NOT built (FLM_ERR_UNSUPPORTED, nothing launched): Mirostat through the draft-and-verify entry points (row r's mu depends on the draws in front of it); this setting on
+ * a context armed for log-probabilities; Mirostat v1; tensor-parallel contexts. */
+typedef struct flm_entropy { float typical_p;      /* <= 0 or >= 1: off */
+                             int32_t mirostat;     /* 0: off, 2: v2 */
+                             float tau, eta, mu;   /* mu: the starting state (callers usually pass 2 * tau) */ } flm_entropy;
+int  flm_entropy_validate(const flm_entropy* e);
+int  flm_entropy_set(flm_ctx* ctx, const flm_entropy* e /* NULL: off */);
+int  flm_entropy_mu(flm_ctx* ctx, float* mu);
 /* Stop rules on the device: a set of stop ids and up to 16 short stop sequences, next to the entry point's one stop token -- several end ids (a vocabulary's eos, a chat
  * model's end-of-turn id) and the `stop` strings of the serving APIs, token level.  No reference counterpart (its loop ends on token 0 only).  The decision is taken on the
  * device in the token's last act, so a call that ends on a rule is as exact about where it ends as one that ends on the stop token; a callback's cancel is not (it lands one
@@ -544,6 +576,7 @@ int  flm_set_option(flm_ctx* ctx, const char* key, int value);
  *   "sampled_tokens" how many tokens this context sampled on the device (flm_forward_sample / flm_decode_sample / flm_generate / flm_verify_sample / flm_generate_lookup_sample at temperature > 0),
  *   "shaped_tokens" how many tokens this context drew under the controls (flm_generate_ex / flm_forward_sample_ex / flm_verify_sample_ex / flm_generate_lookup_ex with a control set or a constraint armed),
    "constraint_state" the automaton state the context is armed at (flm_constraint_arm; moved on by every _ex call over the ids it delivers), -1: disarmed,
+ *   "entropy" the entropy-driven sampler the context is set to (flm_entropy_set): 0 off, 1 locally typical, 2 Mirostat v2,
  *   "logprobs_top_n" the top_n the context is armed with for per-token log-probabilities (flm_logprobs_arm), -1: off,
  *   "stop_rules" 1 = stop rules are installed (flm_stop_set), "stop_reason" / "stop_rule" why the last generate-family call ended (FLM_STOP_LENGTH .. FLM_STOP_CANCEL) and, for
  *               an id or a sequence, which one,
@@ -599,6 +632,13 @@ int  flm_op_score_rows(const float* logits, int rows, int n, const int32_t* targ
 /* the record stage of flm_logprobs_arm (k_logprob_rows) on caller-supplied logits[rows][ld], n entries per row, 1 <= rows <= 16, ld >= n >= 2, n within the LDS bound:
  * out[r] = the flm_logprob of row r with drawn id chosen[r] in [0, n) and top_n in [0, FLM_LOGPROBS_MAX]. */
 int  flm_op_logprob_rows(const float* logits, int rows, int ld, int n, const int32_t* chosen /* [rows] */, int top_n, flm_logprob* out /* [rows] */);
+/* csrc/flm_logf.h's flm_logf as the device evaluates it, in place over n positive normal floats: the tests pin it to the host's compilation of the same header */
+int  flm_op_logf(float* x, size_t n);
+/* the entropy-driven stages of flm_entropy_set (k_entropy_rows) on caller-supplied logits[rows][ld], n entries per row, 1 <= rows <= 16, ld >= n >= 2, n within the LDS
+ * bound: out[r][0 .. n) = row r after stage 5 (e->typical_p) or stage 6 at mu[r] (e->mirostat == 2; mu: [rows], e->mu is not used), at `temperature`.  chosen given
+ * ([rows], ids in [0, n); Mirostat only): obs_out[r] / mu_out[r] = the observed surprise of chosen[r] on the masked row and the updated state (e->tau, e->eta). */
+int  flm_op_entropy_rows(const float* logits, int rows, int ld, int n, float temperature, const flm_entropy* e, const float* mu /* [rows] or NULL */,
+                         const int32_t* chosen /* [rows] or NULL */, float* out /* [rows][n] */, float* obs_out /* [rows] or NULL */, float* mu_out /* [rows] or NULL */);
 /* simd::swiglu(xo,xr,n) (x86_simd.cpp:1766-1770) */
 int  flm_op_swiglu(float* xo, const float* xr, size_t n);
 /* rope_v2 (tf_operators.cpp:352-402): one head row of n_dims at position pos */

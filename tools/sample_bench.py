@@ -18,7 +18,11 @@ weights, 32 layers by default).  Prints one JSON line:
     through FLM_GPU_LIB) only the disarmed figure is measured: the same command gives the pair that shows the disarmed path did not move;
   * with --stop (and nothing else): the shaped token (flm_generate_ex with a bias of +0) with no stop rules installed and with the largest rule set installed -- 64 ids
     and 16 sequences of 32 ids, none of which ever fires --, alternating, every run's own figure listed (`runs_ms`) so that two commands' spreads can be compared.  On a
-    library without the feature (the parent commit through FLM_GPU_LIB) only the rule-free figure is measured: (i) the parent, (ii) this commit without rules, (iii) with."""
+    library without the feature (the parent commit through FLM_GPU_LIB) only the rule-free figure is measured: (i) the parent, (ii) this commit without rules, (iii) with;
+  * with --entropy (and nothing else): the entropy-driven samplers in one process -- tokens/s of flm_generate_ex with top-k 40 alone (the shaped form: the baseline), with
+    flm_entropy_set at typical_p 0.5 and at Mirostat v2 (tau 5, eta 0.1) on top of the same top-k, the runs alternating, and of the host loop a caller needs without the
+    feature (flm_forward's logits over the bus, fh_shape, fh_entropy, fh_sample_state, fh_mirostat_update per token); the same with every control neutral (the stages on the
+    classifier's whole row: 32 000 live candidates)."""
 import argparse
 import importlib.util
 import json
@@ -57,8 +61,55 @@ def main():
     ap.add_argument("--constraint", action="store_true", help="time the shaped token with and without an armed automaton (half the vocabulary allowed), nothing else")
     ap.add_argument("--logprobs", action="store_true", help="time the shaped token disarmed and armed for per-token log-probabilities (top_n 0 / 5 / 20, raw / shaped), nothing else")
     ap.add_argument("--stop", action="store_true", help="time the shaped token with no stop rules and with the largest rule set (64 ids, 16 sequences of 32) that never fires, nothing else")
+    ap.add_argument("--entropy", action="store_true", help="time flm_generate_ex with top-k alone, with typical sampling and with Mirostat v2 set, and the host loop, nothing else")
     args = ap.parse_args()
     out = {}
+    if args.entropy:
+        from entropy_util import host_loop
+        cfg = synth.make_config("7B", ff.QT_INT8)
+        cfg.n_layers = args.layers
+        ctx = capi.Ctx(capi.desc_from_config(cfg), device=0)
+        _bench_module().upload_synthetic(ctx, cfg)
+        V, K = cfg.vocab_size, args.steps
+        prompt = np.array([1] + [int(x) for x in (np.arange(1, 9) * 7919) % V], np.int32)
+        topk = capi.Sampling(temperature=1.0, topp=0.9, top_k=40)
+        noop = capi.Sampling(temperature=1.0, topp=0.9, bias={11: 0.0})
+        typ, miro = capi.Entropy(typical_p=0.5), capi.Entropy(mirostat=2, tau=5.0, eta=0.1)
+
+        def under(ent, s):
+            def run():
+                ctx.entropy_set(ent)
+                r = ctx.generate_ex(prompt, 0, K, s, rng_state=1234)
+                ctx.entropy_set(None)
+                return r
+            return run
+        runs = {"topk": under(None, topk), "topk_typical": under(typ, topk), "topk_mirostat": under(miro, topk),
+                "noop": under(None, noop), "typical": under(typ, noop), "mirostat": under(miro, noop)}
+        ts = {k: [] for k in runs}
+        for rep in range(args.reps + 1):
+            for name, fn in runs.items():                # alternating: every form sees the same machine
+                ctx.sync(); t0 = time.perf_counter(); ids = fn()[0]; dt = time.perf_counter() - t0
+                assert len(ids) == K
+                if rep:
+                    ts[name].append(dt)
+        for name in runs:
+            med = float(np.median(ts[name]))
+            out[f"{name}_tok_s"] = round(K / med, 1)
+            out[f"{name}_spread_ms"] = round((max(ts[name]) - min(ts[name])) * 1e3, 2)
+        for name, base in (("topk_typical", "topk"), ("topk_mirostat", "topk"), ("typical", "noop"), ("mirostat", "noop")):
+            out[f"{name}_extra_us_per_token"] = round((np.median(ts[name]) - np.median(ts[base])) / K * 1e6, 1)
+        H = host_lib()
+        for name, ent in (("typical", typ), ("mirostat", miro)):
+            hs = []
+            for _ in range(2):
+                ctx.sync(); t0 = time.perf_counter()
+                host_loop(ctx, H, prompt, args.host_steps, topk, ent, 1234)
+                hs.append(time.perf_counter() - t0)
+            out[f"host_loop_topk_{name}_tok_s"] = round(args.host_steps / float(np.median(hs)), 1)
+        out["tokens_per_call"] = K; out["prompt_tokens"] = len(prompt); out["layers"] = args.layers
+        ctx.close()
+        print(json.dumps(out), flush=True)
+        return
     if args.stop:
         cfg = synth.make_config("7B", ff.QT_INT8)
         cfg.n_layers = args.layers
