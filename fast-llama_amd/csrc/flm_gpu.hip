@@ -820,8 +820,10 @@ int flm_query(flm_ctx* c, const char* key, int* value) {
     const bool tp = c->world > 1 && c->p2p, tpl = tp && c->grp_tpl;
     // the granule hand-offs are what the one-launch token / the rank-spanning launch of head split i runs
     auto gr = [&](int i) { return c->la_valid[i] && c->la_ok[i] && c->la_p[i].gr && (c->world > 1 ? tpl : c->tail_ok[i]); };
-    const int path = (c->fuse_attn_o ? 1 : 0) | (c->fuse_ffn ? 2 : 0) | (c->fuse_attn_o && c->fuse_qkv == 1 ? 4 : 0) | (c->fuse_attn_o && c->fuse_qkv >= 2 ? 8 : 0)
-                     | (c->fuse_back && c->fuse_attn_o && c->fuse_ffn ? (c->fuse_layer ? 128 + 256 + (c->fuse_token ? 512 + (c->fuse_tail && c->tail_ok[0] ? 1024 : 0) : 0) : 128) : 0);
+    // the forms the options allow (flm_host.h TokenPlan), one bit each; the one-launch token where its argument block was planned too
+    const TokenPlan P = token_plan(c, 1);
+    const int path = (P.opt[LF_ATTN_O] ? 1 : 0) | (P.opt[LF_FFN] ? 2 : 0) | (P.qkv == 1 ? 4 : 0) | (P.qkv >= 2 ? 8 : 0) | (P.opt[LF_BACK] ? 128 : 0) | (P.opt[LF_LAYER] ? 256 : 0)
+                     | (P.opt[LF_LAYERS] ? 512 : 0) | (P.opt[LF_TOKEN] && c->tail_ok[0] ? 1024 : 0);
     // what the context derives from its options and its group: read-only
     const struct { const char* k; int v; } tab[] = {
         {"tuning", c->tuning ? 1 : 0},

@@ -4,8 +4,11 @@
 //                        ageing, the debug taps, the graph cache (run_token / run_tokens / prepare_all), warm_up, flm_prepare
 //   flm_calls.hip        what a call does: check_ready, feed, the retry wrapper, the by-value block setters, d2h / h2d, the draw plan (Draw) and the model-level entry
 //                        points (forward / decode / generate / score / draft-and-verify / constraint / log-probabilities)
-//   flm_token.hip        the per-token launch sequence (enqueue_token), the per-phase and fused decode launches, per-kernel timing (flm_kernel_times / _bytes)
-//   flm_layerlaunch.hip  the whole-layer launch k_attn_ffn (flm_layer.h)
+//   flm_token.hip        the per-token launch sequence (enqueue_token: the launch forms it tries come from TokenPlan below), the per-phase and fused decode launches, each
+//                        launched in one place, per-kernel timing (flm_kernel_times / _bytes)
+//   flm_layerlaunch.hip  the whole-layer launch k_attn_ffn (flm_layer.h) and the layer's argument blocks (plan_layer)
+//   flm_layers.hip       all layers of a token / the whole greedy token in one launch (k_layers); flm_layers_tp.hip: its rank-spanning form
+//   flm_launch.h         from a run-time choice to one instantiation of a kernel template: the variant lists' dispatch() / for_each_variant()
 //   flm_prompt.hip       the batched prompt path (GEMM tiles on the matrix cores, prompt attention)
 //   flm_ops.hip          the op-level exports of the parity tests (flm_op_*)
 //   flm_wait.h           (device side, part of flm_kernels.h) every cross-workgroup / cross-rank wait of the fused launches: flag polls, granule pieces, when a wait gives up
@@ -13,6 +16,7 @@
 #pragma once
 #include "flm_gpu.h"
 #include "flm_kernels.h"
+#include "flm_launch.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -235,21 +239,26 @@ void split_even(int total, int parts, int idx, int* begin, int* count);
 struct GemvPlan { int Rm, cb_shift, grid, nbuf; size_t lds; };
 GemvPlan gemv_plan(int n, int esz, int rows, bool two, bool pairs, bool norm, int wgs);
 // fill the pass geometry of one GEMV into its argument block; returns the LDS bytes and grid it needs
-template <int QT, int PRO, int EPI>
-int plan_gemv(flm_ctx* c, GemvArgs& a, int wgs, GemvPlan& P) {
-    constexpr bool TWO = EPI == EPI_SWIGLU, PAIRS = EPI == EPI_ROPE_KV;
+inline int plan_gemv(flm_ctx* c, GemvArgs& a, int esz, int pro, int epi, int wgs, GemvPlan& P) {
+    const bool TWO = epi == EPI_SWIGLU, PAIRS = epi == EPI_ROPE_KV;
     const int rows = a.items * (PAIRS ? 2 : 1);
-    if ((double)rows * a.n * QTraits<QT>::kEsz * (TWO ? 2 : 1) >= 2147483648.0) return fail(c, FLM_ERR_UNSUPPORTED, "gemv: matrix of 2 GiB or more");
-    P = gemv_plan(a.n, QTraits<QT>::kEsz, rows, TWO, PAIRS, PRO == PRO_RMSNORM_QUANT, wgs);     // (the chain staging area only where an rmsnorm prologue runs)
+    if ((double)rows * a.n * esz * (TWO ? 2 : 1) >= 2147483648.0) return fail(c, FLM_ERR_UNSUPPORTED, "gemv: matrix of 2 GiB or more");
+    P = gemv_plan(a.n, esz, rows, TWO, PAIRS, pro == PRO_RMSNORM_QUANT, wgs);     // (the chain staging area only where an rmsnorm prologue runs)
     if (P.lds > kLdsMax) return fail(c, FLM_ERR_UNSUPPORTED, "gemv: activation vector does not fit LDS");
     a.rows_per_pass = P.Rm; a.cb_shift = P.cb_shift; a.nbuf = P.nbuf;
     return FLM_OK;
 }
+template <int QT, int PRO, int EPI>
+int plan_gemv(flm_ctx* c, GemvArgs& a, int wgs, GemvPlan& P) { return plan_gemv(c, a, QTraits<QT>::kEsz, PRO, EPI, wgs, P); }
+// rounds of the activation sweep: every thread of a workgroup takes four elements of the n per round
+inline int gemv_rounds(int n) { return (n + kGemvBlock * 4 - 1) / (kGemvBlock * 4); }
+// the kernels' rounds template argument (XR / XR2) for a sweep of 1 .. 3 rounds: 1 | 3
+inline int rounds_class(int rounds) { return rounds <= 1 ? 1 : 3; }
 template <int QT, int PRO, int EPI, bool COH>
 int launch_gemv_xr(flm_ctx* c, hipStream_t st, GemvArgs a, int wgs) {
     GemvPlan P;
     int r = plan_gemv<QT, PRO, EPI>(c, a, wgs, P); if (r) return r;
-    const int rounds = (a.n + kGemvBlock * 4 - 1) / (kGemvBlock * 4);
+    const int rounds = gemv_rounds(a.n);
     if (PRO == PRO_NONE)   hipLaunchKernelGGL((k_gemv<QT, PRO, EPI, 0, COH>), dim3(P.grid), dim3(kGemvBlock), P.lds, st, a);
     else if (rounds <= 1)  hipLaunchKernelGGL((k_gemv<QT, PRO, EPI, 1, COH>), dim3(P.grid), dim3(kGemvBlock), P.lds, st, a);
     else if (rounds <= 3)  hipLaunchKernelGGL((k_gemv<QT, PRO, EPI, 3, COH>), dim3(P.grid), dim3(kGemvBlock), P.lds, st, a);
@@ -301,6 +310,8 @@ GemvArgs args_ffn13(flm_ctx* c, int l);
 GemvArgs args_ffn2(flm_ctx* c, int l);
 GemvArgs args_cls(flm_ctx* c);
 void set_fold(flm_ctx* c, GemvArgs& a, int l, int kind);
+// the argument blocks, the launch geometry and the stash sizes of layer l for k_attn_ffn / k_layers, by quant type (flm_layerlaunch.hip plan_layer: see there for `tail`)
+int plan_layer_qt(flm_ctx* c, int qt, int l, bool with_qkv, int G, LayerArgs& A, BackArgs& p, int& grid, int& r2, TailArgs* tail);
 // the whole decoder layer (with_qkv) / attention .. FFN2 of layer l in one launch (flm_layerlaunch.hip); FLM_ERR_UNSUPPORTED when the shape does not allow it
 int launch_layer(flm_ctx* c, hipStream_t st, int qt, int l, bool with_qkv, int G = 1);
 // all layers of a token in one launch (flm_layers.hip): the argument blocks are built outside any capture
@@ -326,6 +337,66 @@ inline bool logprobs_supported(const flm_ctx* c) { return !sharded(c) && sample_
 // the entropy-driven samplers can be set: the same bound (the stage runs on the sampler's strip), and the block exists
 inline bool entropy_supported(const flm_ctx* c) { return !sharded(c) && sample_supported(c) && c->ent_blk != nullptr; }
 inline const int* halt_ptr(const flm_ctx* c) { return sharded(c) ? nullptr : &c->state->halt; }
+
+// The token's launch plan: which launch forms a token of this context may take, decided in ONE place.  enqueue_token tries the forms that run() in its order of
+// preference (a form answers FLM_ERR_UNSUPPORTED where the shape does not allow it: the next one is tried), flm_kernel_times times the forms the options allow and
+// flm_query("token_path") reports them.  DESIGN.md section 5: the table of forms.
+// In enqueue_token's order of preference: the whole greedy token (k_layers<.., TAIL>), all layers (k_layers), ... in one launch per rank that spans the ranks (k_layers<.., TP>),
+// the whole layer (k_attn_ffn<.., QKV>), QKV + attention + Wo (k_qkv_attn_o), attention + Wo + FFN13 + FFN2 (k_attn_ffn), attention + Wo (k_attn_o), FFN13 + FFN2 (k_ffn)
+enum Launch { LF_TOKEN = 0, LF_LAYERS, LF_LAYERS_TP, LF_LAYER, LF_QKV_ATTN_O, LF_BACK, LF_ATTN_O, LF_FFN, kLaunchForms };
+// What instrumentation takes away.  Timing (flm_kernel_times across ranks: one event pair per phase) leaves no fused form.  A trace (FLM_ABLATE builds, option "trace")
+// stamps the timeline of ONE kernel class: the form that class belongs to still runs, every other one steps aside.  -1: the form runs under no trace
+constexpr int trace_admits(Launch f) { return f == LF_TOKEN || f == LF_LAYERS ? 103 : f == LF_LAYER || f == LF_BACK ? 102 : f == LF_ATTN_O ? 101 : -1; }
+// "fuse_token": the all-layers forms are wanted (token_plan; layers_prepare / launch_layers and plan_layer build for them on this alone: their checks are the shape's)
+inline bool wants_layers(const flm_ctx* c) { return c->fuse_token != 0; }
+struct TokenPlan {
+    bool opt[kLaunchForms];                        // what the OPTIONS allow on one GPU, whatever this context is: each form its own option and the forms it is made of (flm_kernel_times, "token_path")
+    int qkv;                                       // "fuse_qkv" where attention + Wo is fused at all: 0 never in front of it, 1 with split heads, >= 2 always
+    bool tp, coh, fold, span; int tpfa, tpff;      // sharded; peers store into the activations; flag rounds folded into the consuming launches; launches span the ranks, as agreed for "tp_fuse_attn" / "tp_fuse_ffn"
+    bool use[kLaunchForms];                        // what THIS CONTEXT's token may try (enqueue_token, through runs()): one GPU: opt; sharded: none but the rank-spanning forms the group agreed on
+    bool timing; int trace_class;
+    bool runs(Launch f) const { return use[f] && !timing && (trace_class < 0 || trace_class == trace_admits(f)); }
+};
+inline TokenPlan token_plan(const flm_ctx* c, int G) {   // G: workgroups per head (attn_parts)
+    TokenPlan P{};
+    bool* o = P.opt;
+    o[LF_ATTN_O] = c->fuse_attn_o != 0;
+    o[LF_FFN] = c->fuse_ffn != 0;
+    P.qkv = o[LF_ATTN_O] ? c->fuse_qkv : 0;
+    o[LF_QKV_ATTN_O] = P.qkv >= 2 || (P.qkv && G > 1);
+    o[LF_BACK] = c->fuse_back && o[LF_ATTN_O] && o[LF_FFN];
+    o[LF_LAYER] = c->fuse_layer && o[LF_BACK];
+    o[LF_LAYERS] = wants_layers(c) && o[LF_LAYER];
+    o[LF_TOKEN] = c->fuse_tail && o[LF_LAYERS];
+    o[LF_LAYERS_TP] = wants_layers(c);
+    P.tp = sharded(c); P.coh = P.tp && c->p2p;
+    P.fold = P.tp && c->p2p && c->world > 1 && c->grp_fold;          // (agreed by the group at flm_p2p_import)
+    P.span = P.fold && c->grp_span;                                   // (they wait across workgroups of one launch too: only where the census found one workgroup per CU resident)
+    P.tpfa = P.span ? c->grp_tpfa : 0; P.tpff = P.span ? c->grp_tpff : 0;
+    for (int f = 0; f < kLaunchForms; ++f) P.use[f] = !P.tp && o[f];
+    P.use[LF_LAYERS_TP] = P.span && c->grp_tpl && o[LF_LAYERS_TP];
+    P.use[LF_QKV_ATTN_O] |= P.tpfa >= 2; P.use[LF_ATTN_O] |= P.tpfa != 0; P.use[LF_FFN] |= P.tpff != 0;
+    P.timing = c->timing != nullptr; P.trace_class = c->trace_class;
+    return P;
+}
+
+// the quant types and rounds classes the fused kernels' variant lists are made of (flm_launch.h)
+using VQuant = Variants<Variant<QT_INT8>, Variant<QT_INT16>>;
+using VRounds = Variants<Variant<1>, Variant<3>>;
+inline int quant_variant(int qt) { return qt == FLM_QT_INT8 ? QT_INT8 : QT_INT16; }
+// a launch that stashes weights takes the CU's whole LDS: raise the dynamic-LDS limit of EVERY instantiation in the list the launch dispatches over, once per device
+// (kernel_of: a list entry -> the kernel's address; the launch goes through the same function)
+template <class List, class KernelOf> int raise_lds_limit(flm_ctx* c, KernelOf kernel_of) {
+    static std::mutex mu; static bool done[64] = {false};
+    std::lock_guard<std::mutex> lk(mu);
+    if (c->device >= 0 && c->device < 64 && !done[c->device]) {
+        std::vector<const void*> fns;
+        for_each_variant(List{}, [&](auto v) { fns.push_back((const void*)kernel_of(v)); });
+        for (const void* f : fns) HIPC(c, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
+        done[c->device] = true;
+    }
+    return FLM_OK;
+}
 // ids[0 .. n) lie in [0, vocab)
 inline bool ids_in_vocab(const flm_ctx* c, const int32_t* ids, int n) {
     for (int i = 0; i < n; ++i) if (ids[i] < 0 || ids[i] >= c->d.vocab_size) return false;

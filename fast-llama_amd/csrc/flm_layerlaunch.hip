@@ -3,7 +3,6 @@
 
 namespace fh {
 
-// attention + Wo + FFN13 + FFN2 of layer l in one launch (k_attn_ffn, flm_layer.h); returns FLM_ERR_UNSUPPORTED when the shape does not allow it
 // the argument blocks, the launch geometry and the stash sizes of layer l (the same for every layer but for the pointers): shared by k_attn_ffn's launch and k_layers' (flm_layers.hip)
 template <int QT>
 int plan_layer(flm_ctx* c, int l, bool with_qkv, int G, LayerArgs& A, BackArgs& p, int& grid, int& r2, TailArgs* tail) {     // tail (k_layers' one-launch token): in: non-null = wanted; out: tail->gridc > 0 = possible, filled
@@ -20,13 +19,13 @@ int plan_layer(flm_ctx* c, int l, bool with_qkv, int G, LayerArgs& A, BackArgs& 
     int r = plan_gemv<QT, PRO_QUANT, EPI_RESIDUAL>(c, ao, wgs_o, Po); if (r) return r;
     if (with_qkv) {
         r = plan_gemv<QT, PRO_RMSNORM_QUANT, EPI_ROPE_KV>(c, aq, all, Pq); if (r) return r;
-        if ((aq.n + kGemvBlock * 4 - 1) / (kGemvBlock * 4) > 1) return FLM_ERR_UNSUPPORTED;
+        if (gemv_rounds(aq.n) > 1) return FLM_ERR_UNSUPPORTED;
     }
     r = plan_gemv<QT, PRO_RMSNORM_QUANT, EPI_SWIGLU>(c, a13, all, P13); if (r) return r;
     r = plan_gemv<QT, PRO_QUANT, EPI_RESIDUAL>(c, a2, all, P2); if (r) return r;
-    const int r13 = (a13.n + kGemvBlock * 4 - 1) / (kGemvBlock * 4); r2 = (a2.n + kGemvBlock * 4 - 1) / (kGemvBlock * 4);
-    if (r13 > 1 || r2 > 3) return FLM_ERR_UNSUPPORTED;
-    if ((G > 1 || tpl) && (ao.n + kGemvBlock * 4 - 1) / (kGemvBlock * 4) > 1) return FLM_ERR_UNSUPPORTED;     // (the Wo workgroups quantize the heads' fp32 output themselves: one round)
+    r2 = gemv_rounds(a2.n);
+    if (gemv_rounds(a13.n) > 1 || r2 > 3) return FLM_ERR_UNSUPPORTED;
+    if ((G > 1 || tpl) && gemv_rounds(ao.n) > 1) return FLM_ERR_UNSUPPORTED;     // (the Wo workgroups quantize the heads' fp32 output themselves: one round)
     // a workgroup with a single pass needs one strip buffer: the LDS above the phases' own layouts is the stash
     auto one_pass = [&](GemvArgs& a, GemvPlan& P, bool two, bool norm, int rows_per_item = 1) {
         const int rows = a.items * rows_per_item, npass = (rows + P.Rm - 1) / P.Rm;
@@ -34,7 +33,7 @@ int plan_layer(flm_ctx* c, int l, bool with_qkv, int G, LayerArgs& A, BackArgs& 
     };
     one_pass(ao, Po, false, false); one_pass(a13, P13, true, true); one_pass(a2, P2, false, false);
     size_t own = Po.lds; if (P13.lds > own) own = P13.lds; if (P2.lds > own) own = P2.lds;
-    if (with_qkv) { one_pass(aq, Pq, false, true, 2); if (Pq.lds > kLdsMax) return FLM_ERR_UNSUPPORTED; if (c->fuse_token && Pq.lds > own) own = Pq.lds; }   // (k_layers stashes [Wq; Wk; Wv] too: above its layout as well)
+    if (with_qkv) { one_pass(aq, Pq, false, true, 2); if (Pq.lds > kLdsMax) return FLM_ERR_UNSUPPORTED; if (wants_layers(c) && Pq.lds > own) own = Pq.lds; }   // (k_layers stashes [Wq; Wk; Wv] too: above its layout as well)
     // the one-launch token runs the classifier as a phase of the same launch: its layout must fit below the stash as well
     GemvArgs acls{}; GemvPlan Pc{}; bool tail_fits = false;
     if (tail) {
@@ -42,9 +41,9 @@ int plan_layer(flm_ctx* c, int l, bool with_qkv, int G, LayerArgs& A, BackArgs& 
         // (round 6: the one-launch token IS the granule form of the hand-offs -- flm_layer.h GRM --: one sweep round per thread for dim, and its one-workgroup-per-head instantiation
         //  takes q and the new K / V row as granules with the head's <= 2 tiles requested at once: long contexts must be able to split.  "gr_edges" 0: the four-launch token on flag rounds)
         const bool gr_tail = c->gr_edges && c->xg && d.dim <= 4 * kGemvBlock && d.dim % 4 == 0 && d.hidden_dim % 4 == 0 && (d.max_seq_len <= kSplitFrom || attn_parts(c, d.max_seq_len) > 1);
-        if (gr_tail && c->fuse_tail && with_qkv && c->fuse_token && c->world == 1 && !tpl && c->got_emb && c->emb_qt == 0 && c->got_cls) {
+        if (gr_tail && c->fuse_tail && with_qkv && wants_layers(c) && c->world == 1 && !tpl && c->got_emb && c->emb_qt == 0 && c->got_cls) {
             acls = args_cls(c);
-            if (plan_gemv<QT, PRO_RMSNORM_QUANT, EPI_STORE>(c, acls, all, Pc) == FLM_OK && (acls.n + kGemvBlock * 4 - 1) / (kGemvBlock * 4) <= 1 && Pc.grid <= 256 && Pc.lds + 8 * (kStepBlk * 1024 + 256) <= kLdsMax) {
+            if (plan_gemv<QT, PRO_RMSNORM_QUANT, EPI_STORE>(c, acls, all, Pc) == FLM_OK && gemv_rounds(acls.n) <= 1 && Pc.grid <= 256 && Pc.lds + 8 * (kStepBlk * 1024 + 256) <= kLdsMax) {
                 tail_fits = true; if (Pc.lds > own) own = Pc.lds;
             }
         }
@@ -133,43 +132,21 @@ int plan_layer(flm_ctx* c, int l, bool with_qkv, int G, LayerArgs& A, BackArgs& 
     }
     return FLM_OK;
 }
-template int plan_layer<QT_INT8>(flm_ctx*, int, bool, int, LayerArgs&, BackArgs&, int&, int&, TailArgs*);
-template int plan_layer<QT_INT16>(flm_ctx*, int, bool, int, LayerArgs&, BackArgs&, int&, int&, TailArgs*);
-
-// attention + Wo + FFN13 + FFN2 of layer l (with_qkv: the whole layer) in one launch (k_attn_ffn, flm_layer.h); returns FLM_ERR_UNSUPPORTED when the shape does not allow it
-template <int QT>
-int launch_attn_ffn(flm_ctx* c, hipStream_t st, int l, bool with_qkv, int G) {
-    LayerArgs A; BackArgs p; int grid = 0, r2 = 0;
-    int r = plan_layer<QT>(c, l, with_qkv, G, A, p, grid, r2, nullptr); if (r) return r;
-    const GemvArgs &aq = A.aq, &ao = A.ao, &a13 = A.a13, &a2 = A.a2; const AttnArgs& aa = A.aa;
-    {   // the stash takes the rest of the CU's 160 KiB: raise the kernels' dynamic-LDS limit, once per device
-        static std::mutex mu; static bool done[64] = {false};
-        std::lock_guard<std::mutex> lk(mu);
-        if (c->device >= 0 && c->device < 64 && !done[c->device]) {
-            const void* fns[] = {(const void*)&k_attn_ffn<QT_INT8, 1, false>, (const void*)&k_attn_ffn<QT_INT8, 3, false>, (const void*)&k_attn_ffn<QT_INT16, 1, false>, (const void*)&k_attn_ffn<QT_INT16, 3, false>,
-                                 (const void*)&k_attn_ffn<QT_INT8, 1, true>, (const void*)&k_attn_ffn<QT_INT8, 3, true>, (const void*)&k_attn_ffn<QT_INT16, 1, true>, (const void*)&k_attn_ffn<QT_INT16, 3, true>,
-                                 (const void*)&k_attn_ffn<QT_INT8, 1, true, true>, (const void*)&k_attn_ffn<QT_INT8, 3, true, true>, (const void*)&k_attn_ffn<QT_INT16, 1, true, true>, (const void*)&k_attn_ffn<QT_INT16, 3, true, true>};
-            for (const void* f : fns) HIPC(c, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
-            done[c->device] = true;
-        }
-    }
-    const dim3 g3(grid), b3(kGemvBlock);
-    if (G > 1) {
-        if (r2 <= 1) hipLaunchKernelGGL((k_attn_ffn<QT, 1, true, true>), g3, b3, kLdsMax, st, aq, aa, ao, a13, a2, p);
-        else         hipLaunchKernelGGL((k_attn_ffn<QT, 3, true, true>), g3, b3, kLdsMax, st, aq, aa, ao, a13, a2, p);
-    }
-    else if (with_qkv) {
-        if (r2 <= 1) hipLaunchKernelGGL((k_attn_ffn<QT, 1, true>), g3, b3, kLdsMax, st, aq, aa, ao, a13, a2, p);
-        else         hipLaunchKernelGGL((k_attn_ffn<QT, 3, true>), g3, b3, kLdsMax, st, aq, aa, ao, a13, a2, p);
-    }
-    else if (r2 <= 1) hipLaunchKernelGGL((k_attn_ffn<QT, 1, false>), g3, b3, kLdsMax, st, aq, aa, ao, a13, a2, p);
-    else              hipLaunchKernelGGL((k_attn_ffn<QT, 3, false>), g3, b3, kLdsMax, st, aq, aa, ao, a13, a2, p);
-    HIPC(c, hipGetLastError());
-    return FLM_OK;
+int plan_layer_qt(flm_ctx* c, int qt, int l, bool with_qkv, int G, LayerArgs& A, BackArgs& p, int& grid, int& r2, TailArgs* tail) {
+    return qt == FLM_QT_INT8 ? plan_layer<QT_INT8>(c, l, with_qkv, G, A, p, grid, r2, tail) : plan_layer<QT_INT16>(c, l, with_qkv, G, A, p, grid, r2, tail);
 }
 
+// attention + Wo + FFN13 + FFN2 of layer l (with_qkv: the whole layer) in one launch (k_attn_ffn, flm_layer.h); returns FLM_ERR_UNSUPPORTED when the shape does not allow it
+using VAttnFfn = cross_t<VQuant, cross_t<VRounds, Variants<Variant<0, 0>, Variant<1, 0>, Variant<1, 1>>>>;     // [QT][XR2][QKV, SPLIT]: split heads only in the whole-layer form
 int launch_layer(flm_ctx* c, hipStream_t st, int qt, int l, bool with_qkv, int G) {
-    return qt == FLM_QT_INT8 ? launch_attn_ffn<QT_INT8>(c, st, l, with_qkv, G) : launch_attn_ffn<QT_INT16>(c, st, l, with_qkv, G);
+    LayerArgs A; BackArgs p; int grid = 0, r2 = 0;
+    int r = plan_layer_qt(c, qt, l, with_qkv, G, A, p, grid, r2, nullptr); if (r) return r;
+    auto kernel_of = [](auto v) { using V = decltype(v); return &k_attn_ffn<V::v[0], V::v[1], V::v[2] != 0, V::v[3] != 0>; };
+    r = raise_lds_limit<VAttnFfn>(c, kernel_of); if (r) return r;       // (the stash takes the rest of the CU's 160 KiB)
+    const int want[] = {quant_variant(qt), rounds_class(r2), G > 1 || with_qkv, G > 1};
+    if (!dispatch(VAttnFfn{}, want, [&](auto v) { hipLaunchKernelGGL(kernel_of(v), dim3(grid), dim3(kGemvBlock), kLdsMax, st, A.aq, A.aa, A.ao, A.a13, A.a2, p); })) return FLM_ERR_UNSUPPORTED;
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
 }
 
 } // namespace fh

@@ -5,13 +5,12 @@
 
 namespace fh {
 
-template <int QT> int plan_layer(flm_ctx* c, int l, bool with_qkv, int G, LayerArgs& A, BackArgs& p, int& grid, int& r2, TailArgs* tail);     // flm_layerlaunch.hip
 int launch_layers_tp(flm_ctx* c, hipStream_t st, const LayerArgs* LA, const BackArgs& p, int grid, int r2, int l0, int l1, int G);           // flm_layers_tp.hip
 
 // the layers' argument blocks in device memory, per number of workgroups a head is spread over (G = 1 | hs / 32): built outside any stream capture, valid until an option changes
 int layers_prepare(flm_ctx* c, int G) {
     const int key = G > 1 ? 1 : 0;
-    if (!c->fuse_token || (c->world != 1 && !(c->p2p && c->grp_tpl))) return FLM_OK;            // (tensor parallel: the rank-spanning form, where the group agreed on it)
+    if (!wants_layers(c) || (c->world != 1 && !(c->p2p && c->grp_tpl))) return FLM_OK;            // (tensor parallel: the rank-spanning form, where the group agreed on it)
     if (c->la_valid[key]) return FLM_OK;
     const int L = c->d.n_layers, qt = c->d.quant_type;
     std::vector<LayerArgs> host((size_t)L);
@@ -20,7 +19,7 @@ int layers_prepare(flm_ctx* c, int G) {
     TailArgs tail{};
     for (int l = 0; l < L; ++l) {
         BackArgs p; int grid = 0, r2 = 0;
-        const int r = qt == FLM_QT_INT8 ? plan_layer<QT_INT8>(c, l, true, G, host[l], p, grid, r2, &tail) : plan_layer<QT_INT16>(c, l, true, G, host[l], p, grid, r2, &tail);
+        const int r = plan_layer_qt(c, qt, l, true, G, host[l], p, grid, r2, &tail);
         if (r == FLM_ERR_UNSUPPORTED) { c->la_valid[key] = true; c->err = err0; g_last_error = gerr0; return FLM_OK; }      // (this shape runs one launch per layer, or per phase: a probe, not a failure -- flm_last_error keeps what it said)
         if (r) return r;
         c->la_p[key] = p; c->la_grid[key] = grid; c->la_r2[key] = r2;
@@ -36,44 +35,25 @@ int layers_prepare(flm_ctx* c, int G) {
     return FLM_OK;
 }
 
+// the instantiations of k_layers on one GPU: [QT][XR2][SPLIT][R5 = 0 | 3 (both arrival-order hand-offs)][TAIL]
+using VLayers = cross_t<VQuant, cross_t<VRounds, cross_t<Variants<Variant<0>, Variant<1>>, cross_t<Variants<Variant<0>, Variant<3>>, Variants<Variant<0>, Variant<1>>>>>>;
 // layers [l0, l1) of the token in one launch; FLM_ERR_UNSUPPORTED: not prepared / not possible for this shape
 int launch_layers(flm_ctx* c, hipStream_t st, int l0, int l1, int G, bool tail) {
     const int key = G > 1 ? 1 : 0;
-    if (!c->fuse_token || !c->la_valid[key] || !c->la_ok[key] || l1 <= l0) return FLM_ERR_UNSUPPORTED;
+    if (!wants_layers(c) || !c->la_valid[key] || !c->la_ok[key] || l1 <= l0) return FLM_ERR_UNSUPPORTED;
     if (tail && (!c->tail_ok[key] || l0 != 0 || l1 != c->d.n_layers)) return FLM_ERR_UNSUPPORTED;
     if (c->world > 1) {
         if (tail || !c->p2p || !c->grp_tpl || !c->la_p[key].tp.world) return FLM_ERR_UNSUPPORTED;
         return launch_layers_tp(c, st, (const LayerArgs*)c->la_dev[key], c->la_p[key], c->la_grid[key], c->la_r2[key], l0, l1, G);
     }
-    {
-        static std::mutex mu; static bool done[64] = {false};
-        std::lock_guard<std::mutex> lk(mu);
-        if (c->device >= 0 && c->device < 64 && !done[c->device]) {
-            const void* fns[] = {(const void*)&k_layers<QT_INT8, 1, false>, (const void*)&k_layers<QT_INT8, 3, false>, (const void*)&k_layers<QT_INT16, 1, false>, (const void*)&k_layers<QT_INT16, 3, false>,
-                                 (const void*)&k_layers<QT_INT8, 1, true>, (const void*)&k_layers<QT_INT8, 3, true>, (const void*)&k_layers<QT_INT16, 1, true>, (const void*)&k_layers<QT_INT16, 3, true>,
-                                 (const void*)&k_layers<QT_INT8, 1, false, 3>, (const void*)&k_layers<QT_INT8, 3, false, 3>, (const void*)&k_layers<QT_INT16, 1, false, 3>, (const void*)&k_layers<QT_INT16, 3, false, 3>,
-                                 (const void*)&k_layers<QT_INT8, 1, true, 3>, (const void*)&k_layers<QT_INT8, 3, true, 3>, (const void*)&k_layers<QT_INT16, 1, true, 3>, (const void*)&k_layers<QT_INT16, 3, true, 3>,
-                                 (const void*)&k_layers<QT_INT8, 1, false, 3, true>, (const void*)&k_layers<QT_INT8, 3, false, 3, true>, (const void*)&k_layers<QT_INT16, 1, false, 3, true>, (const void*)&k_layers<QT_INT16, 3, false, 3, true>,
-                                 (const void*)&k_layers<QT_INT8, 1, true, 3, true>, (const void*)&k_layers<QT_INT8, 3, true, 3, true>, (const void*)&k_layers<QT_INT16, 1, true, 3, true>, (const void*)&k_layers<QT_INT16, 3, true, 3, true>,
-                                 (const void*)&k_layers<QT_INT8, 1, false, 0, true>, (const void*)&k_layers<QT_INT8, 3, false, 0, true>, (const void*)&k_layers<QT_INT16, 1, false, 0, true>, (const void*)&k_layers<QT_INT16, 3, false, 0, true>,
-                                 (const void*)&k_layers<QT_INT8, 1, true, 0, true>, (const void*)&k_layers<QT_INT8, 3, true, 0, true>, (const void*)&k_layers<QT_INT16, 1, true, 0, true>, (const void*)&k_layers<QT_INT16, 3, true, 0, true>};
-            for (const void* f : fns) HIPC(c, hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
-            done[c->device] = true;
-        }
-    }
-    const dim3 g3(c->la_grid[key]), b3(kGemvBlock);
-    const LayerArgs* LA = (const LayerArgs*)c->la_dev[key];
+    auto kernel_of = [](auto v) { using V = decltype(v); return &k_layers<V::v[0], V::v[1], V::v[2] != 0, V::v[3], V::v[4] != 0>; };
+    int r = raise_lds_limit<VLayers>(c, kernel_of); if (r) return r;
     BackArgs p = c->la_p[key];
     if (!tail) { p.gr = 0; if (c->back_pre13 == 99) p.pre13 = 16; if (c->tok_preq == 99) p.preq = 16; }                                                                // (granule tags count from the tail launch's epoch: flm_layer.h BackArgs::gr)
-    const bool i8 = c->d.quant_type == FLM_QT_INT8, one = c->la_r2[key] <= 1;
-    const TailArgs* TA = (const TailArgs*)c->tail_dev[key];
-#define FLM_LAUNCH_LAYERS(QT, XR2, SP) do { if (tail && p.r5) hipLaunchKernelGGL((k_layers<QT, XR2, SP, 3, true>), g3, b3, kLdsMax, st, LA, p, l0, l1, TA); \
-                                            else if (tail) hipLaunchKernelGGL((k_layers<QT, XR2, SP, 0, true>), g3, b3, kLdsMax, st, LA, p, l0, l1, TA); \
-                                            else if (p.r5) hipLaunchKernelGGL((k_layers<QT, XR2, SP, 3>), g3, b3, kLdsMax, st, LA, p, l0, l1, (const TailArgs*)nullptr); \
-                                            else hipLaunchKernelGGL((k_layers<QT, XR2, SP, 0>), g3, b3, kLdsMax, st, LA, p, l0, l1, (const TailArgs*)nullptr); } while (0)
-    if (G > 1) { if (i8) { if (one) FLM_LAUNCH_LAYERS(QT_INT8, 1, true); else FLM_LAUNCH_LAYERS(QT_INT8, 3, true); } else { if (one) FLM_LAUNCH_LAYERS(QT_INT16, 1, true); else FLM_LAUNCH_LAYERS(QT_INT16, 3, true); } }
-    else       { if (i8) { if (one) FLM_LAUNCH_LAYERS(QT_INT8, 1, false); else FLM_LAUNCH_LAYERS(QT_INT8, 3, false); } else { if (one) FLM_LAUNCH_LAYERS(QT_INT16, 1, false); else FLM_LAUNCH_LAYERS(QT_INT16, 3, false); } }
-#undef FLM_LAUNCH_LAYERS
+    const LayerArgs* LA = (const LayerArgs*)c->la_dev[key];
+    const TailArgs* TA = tail ? (const TailArgs*)c->tail_dev[key] : nullptr;
+    const int want[] = {quant_variant(c->d.quant_type), rounds_class(c->la_r2[key]), G > 1, p.r5 ? 3 : 0, tail};
+    if (!dispatch(VLayers{}, want, [&](auto v) { hipLaunchKernelGGL(kernel_of(v), dim3(c->la_grid[key]), dim3(kGemvBlock), kLdsMax, st, LA, p, l0, l1, TA); })) return FLM_ERR_UNSUPPORTED;
     HIPC(c, hipGetLastError());
     return FLM_OK;
 }

@@ -119,138 +119,113 @@ void set_fold(flm_ctx* c, GemvArgs& a, int l, int kind) {
     a.xf.rank = c->rank; a.xf.world = c->world; a.xf.slot = 4 + (kind == 3 ? 1 : kind); a.xf.err = c->xwg_err;      // kinds: 0 att, 1 x1 behind Wo, 2 hd, 3 x1 behind FFN2 (the x1 slot again)
 }
 
-// attention + Wo GEMV of layer l in one launch (k_attn_o); returns FLM_ERR_UNSUPPORTED when the shape does not allow it
-template <int QT>
-int launch_attn_o(flm_ctx* c, hipStream_t st, int l, int G) {
-    const auto& d = c->d;
-    const int parts = c->heads_local * G, wgs = c->cu_count - parts;
-    if (wgs < 1 || parts > 256) return FLM_ERR_UNSUPPORTED;
-    GemvArgs a = args_o(c, l);
-    if (kAblate && c->trace_class == 101 && l == 0) a.trace = c->trace;     // tools/trace_ao.py
-    GemvPlan P;
-    int r = plan_gemv<QT, PRO_QUANT, EPI_RESIDUAL>(c, a, wgs, P); if (r) return r;
-    const int rounds = (a.n + kGemvBlock * 4 - 1) / (kGemvBlock * 4);
-    if (rounds > 3) return FLM_ERR_UNSUPPORTED;
-    size_t lds = attn_lds_bytes(d.max_seq_len, c->hs, G > 1); if (P.lds > lds) lds = P.lds;
-    AttnArgs aa = args_attn(c, l, G);
-    unsigned* flag = c->flag_lines;                              // one 64-byte line per head part, value = layer + 1; k_embed clears them at the start of the token
-    const dim3 grid(parts + P.grid), block(kGemvBlock);
-    AoTp tp{};
-    if (c->world > 1) {
-        // across ranks: every rank's head parts raise their lines in every rank's array (in the exchange buffer); the Wo workgroups read the full att vector
-        // from this rank's exchange region (the heads' stores went to every rank) with coherent loads and quantize it themselves
-        if (d.n_heads * G > 256) return FLM_ERR_UNSUPPORTED;
-        tp.world = c->world; tp.line0 = c->plan.head_begin * G; tp.n_lines = d.n_heads * G; tp.base = c->eng_base; tp.add = (unsigned)(4 * l + 1);
-        for (int r = 0; r < c->world; ++r) tp.peer_flags[r] = (unsigned*)(c->peer[r] + c->x_hflags_off);
-        flag = (unsigned*)(c->xbuf + c->x_hflags_off);
-        if (G > 1) {
-            if (rounds <= 1) hipLaunchKernelGGL((k_attn_o<QT, 1, false, true>), grid, block, lds, st, aa, a, parts, flag, 0u, c->xwg_err, tp);
-            else             hipLaunchKernelGGL((k_attn_o<QT, 3, false, true>), grid, block, lds, st, aa, a, parts, flag, 0u, c->xwg_err, tp);
-        }
-        else if (rounds <= 1) hipLaunchKernelGGL((k_attn_o<QT, 1, false>), grid, block, lds, st, aa, a, parts, flag, 0u, c->xwg_err, tp);
-        else                  hipLaunchKernelGGL((k_attn_o<QT, 3, false>), grid, block, lds, st, aa, a, parts, flag, 0u, c->xwg_err, tp);
-        HIPC(c, hipGetLastError());
-        return FLM_OK;
-    }
-    if (c->hs % kGroup == 0 && G == 1) {
-        // a head's output is whole quant groups: the head workgroups quantize it themselves (A3 on the 64 values a wave
-        // holds), the GEMV workgroups fetch 1 (2) bytes per element and skip the quantize prologue
-        aa.oq = c->att_q; aa.os = c->att_qs; aa.oqt = QT;
-        a.xq = c->att_q; a.xs = c->att_qs;
-        hipLaunchKernelGGL((k_attn_o<QT, 0, true>), grid, block, lds, st, aa, a, parts, flag, (unsigned)(l + 1), c->xwg_err, tp);
-    }
-    else if (G > 1) {
-        if (rounds <= 1) hipLaunchKernelGGL((k_attn_o<QT, 1, false, true>), grid, block, lds, st, aa, a, parts, flag, (unsigned)(l + 1), c->xwg_err, tp);
-        else             hipLaunchKernelGGL((k_attn_o<QT, 3, false, true>), grid, block, lds, st, aa, a, parts, flag, (unsigned)(l + 1), c->xwg_err, tp);
-    }
-    else if (rounds <= 1) hipLaunchKernelGGL((k_attn_o<QT, 1, false>), grid, block, lds, st, aa, a, parts, flag, (unsigned)(l + 1), c->xwg_err, tp);
-    else                  hipLaunchKernelGGL((k_attn_o<QT, 3, false>), grid, block, lds, st, aa, a, parts, flag, (unsigned)(l + 1), c->xwg_err, tp);
-    HIPC(c, hipGetLastError());
-    return FLM_OK;
-}
+// the instantiations of k_attn_o / k_qkv_attn_o: [QT] x [XR, PREQ, SPLIT (, TP)] -- PREQ has no sweep and one workgroup per head, a launch across ranks no PREQ
+using VAttnO = cross_t<VQuant, Variants<Variant<0, 1, 0>, Variant<1, 0, 0>, Variant<3, 0, 0>, Variant<1, 0, 1>, Variant<3, 0, 1>>>;
+using VQkvAttnO = cross_t<VQuant, Variants<Variant<0, 1, 0, 0>, Variant<1, 0, 0, 0>, Variant<3, 0, 0, 0>, Variant<1, 0, 1, 0>, Variant<3, 0, 1, 0>,
+                                           Variant<1, 0, 0, 1>, Variant<3, 0, 0, 1>, Variant<1, 0, 1, 1>, Variant<3, 0, 1, 1>>>;
+using VFfn = cross_t<VQuant, cross_t<VRounds, Variants<Variant<0>, Variant<1>>>>;                                                          // [QT][XR2][TP]
 
-// QKV + attention + Wo GEMV of layer l in one launch (k_qkv_attn_o); returns FLM_ERR_UNSUPPORTED when the shape does not allow it
-template <int QT>
-int launch_qkv_attn_o(flm_ctx* c, hipStream_t st, int l, int G) {
+// attention + Wo GEMV of layer l in one launch (k_attn_o), with_qkv: with the QKV GEMV in front (k_qkv_attn_o); returns FLM_ERR_UNSUPPORTED when the shape does not allow it
+static int launch_attn_o(flm_ctx* c, hipStream_t st, int qt, int l, int G, bool with_qkv) {
     const auto& d = c->d;
-    const int parts = c->heads_local * G, all = c->cu_count < 256 ? c->cu_count : 256, wgs = all - parts;
+    const int qv = quant_variant(qt), parts = c->heads_local * G, all = with_qkv && c->cu_count > 256 ? 256 : c->cu_count, wgs = all - parts;
     if (wgs < 1 || parts > 256) return FLM_ERR_UNSUPPORTED;
-    GemvArgs aq = args_qkv(c, l), a = args_o(c, l);
-    GemvPlan Pq, P;
-    int r = plan_gemv<QT, PRO_RMSNORM_QUANT, EPI_ROPE_KV>(c, aq, all, Pq); if (r) return r;
-    r = plan_gemv<QT, PRO_QUANT, EPI_RESIDUAL>(c, a, wgs, P); if (r) return r;
-    const int rq = (aq.n + kGemvBlock * 4 - 1) / (kGemvBlock * 4), rounds = (a.n + kGemvBlock * 4 - 1) / (kGemvBlock * 4);
-    if (rq > 1 || rounds > 3) return FLM_ERR_UNSUPPORTED;
+    GemvArgs aq = with_qkv ? args_qkv(c, l) : GemvArgs{}, a = args_o(c, l);          // (without the QKV phase: aq unused, Pq stays zero -- neutral in the LDS and grid maxima below)
+    if (!with_qkv && kAblate && c->trace_class == 101 && l == 0) a.trace = c->trace;     // tools/trace_ao.py
+    GemvPlan Pq{}, P;
+    int r = with_qkv ? plan_gemv(c, aq, c->esz, PRO_RMSNORM_QUANT, EPI_ROPE_KV, all, Pq) : FLM_OK; if (r) return r;
+    r = plan_gemv(c, a, c->esz, PRO_QUANT, EPI_RESIDUAL, wgs, P); if (r) return r;
+    const int rounds = gemv_rounds(a.n);
+    if ((with_qkv && gemv_rounds(aq.n) > 1) || rounds > 3) return FLM_ERR_UNSUPPORTED;
     size_t lds = attn_lds_bytes(d.max_seq_len, c->hs, G > 1); if (P.lds > lds) lds = P.lds; if (Pq.lds > lds) lds = Pq.lds;
     AttnArgs aa = args_attn(c, l, G);
-    unsigned* flag = c->flag_lines;                              // heads' lines (as k_attn_o)
+    unsigned* flag = c->flag_lines;                              // one 64-byte line per head part, value = layer + 1; k_embed clears them at the start of the token
     unsigned* flagq = c->flag_lines + 768 * 16;                  // the QKV workgroups' lines; value = layer + 1, cleared by k_embed
-    const int gridx = parts + P.grid > Pq.grid ? parts + P.grid : Pq.grid;
-    const dim3 grid(gridx), block(kGemvBlock);
-    const unsigned tgt = (unsigned)(l + 1);
+    unsigned target = (unsigned)(l + 1);
+    const dim3 grid(parts + P.grid > Pq.grid ? parts + P.grid : Pq.grid), block(kGemvBlock);
     AoTp tp{};
+    bool preq = false;
     if (c->world > 1) {
-        // across ranks (see launch_attn_o); the QKV phase consumes the x1 exchange behind the previous layer's FFN2 (kind 3 of layer l - 1; layer 0 reads the embedding)
+        // across ranks: every rank's head parts raise their lines in every rank's array (in the exchange buffer, counting from the token's epoch base); the Wo workgroups read
+        // the full att vector from this rank's exchange region (the heads' stores went to every rank) with coherent loads and quantize it themselves.  The QKV phase consumes
+        // the x1 exchange behind the previous layer's FFN2 (kind 3 of layer l - 1; layer 0 reads the embedding)
         if (d.n_heads * G > 256) return FLM_ERR_UNSUPPORTED;
-        if (l > 0) set_fold(c, aq, l - 1, 3);
+        if (with_qkv && l > 0) set_fold(c, aq, l - 1, 3);
         tp.world = c->world; tp.line0 = c->plan.head_begin * G; tp.n_lines = d.n_heads * G; tp.base = c->eng_base; tp.add = (unsigned)(4 * l + 1);
         for (int r = 0; r < c->world; ++r) tp.peer_flags[r] = (unsigned*)(c->peer[r] + c->x_hflags_off);
-        flag = (unsigned*)(c->xbuf + c->x_hflags_off);
-        if (G > 1) {
-            if (rounds <= 1) hipLaunchKernelGGL((k_qkv_attn_o<QT, 1, false, true, true>), grid, block, lds, st, aq, aa, a, Pq.grid, parts, P.grid, flagq, flag, tgt, c->xwg_err, tp);
-            else             hipLaunchKernelGGL((k_qkv_attn_o<QT, 3, false, true, true>), grid, block, lds, st, aq, aa, a, Pq.grid, parts, P.grid, flagq, flag, tgt, c->xwg_err, tp);
-        }
-        else if (rounds <= 1) hipLaunchKernelGGL((k_qkv_attn_o<QT, 1, false, false, true>), grid, block, lds, st, aq, aa, a, Pq.grid, parts, P.grid, flagq, flag, tgt, c->xwg_err, tp);
-        else                  hipLaunchKernelGGL((k_qkv_attn_o<QT, 3, false, false, true>), grid, block, lds, st, aq, aa, a, Pq.grid, parts, P.grid, flagq, flag, tgt, c->xwg_err, tp);
-        HIPC(c, hipGetLastError());
-        return FLM_OK;
+        flag = (unsigned*)(c->xbuf + c->x_hflags_off); if (!with_qkv) target = 0u;
+    } else if (c->hs % kGroup == 0 && G == 1) {
+        // a head's output is whole quant groups: the head workgroups quantize it themselves (A3 on the 64 values a wave
+        // holds), the GEMV workgroups fetch 1 (2) bytes per element and skip the quantize prologue
+        preq = true; aa.oq = c->att_q; aa.os = c->att_qs; aa.oqt = qv; a.xq = c->att_q; a.xs = c->att_qs;
     }
-    if (c->hs % kGroup == 0 && G == 1) {
-        aa.oq = c->att_q; aa.os = c->att_qs; aa.oqt = QT;
-        a.xq = c->att_q; a.xs = c->att_qs;
-        hipLaunchKernelGGL((k_qkv_attn_o<QT, 0, true>), grid, block, lds, st, aq, aa, a, Pq.grid, parts, P.grid, flagq, flag, tgt, c->xwg_err, tp);
-    }
-    else if (G > 1) {
-        if (rounds <= 1) hipLaunchKernelGGL((k_qkv_attn_o<QT, 1, false, true>), grid, block, lds, st, aq, aa, a, Pq.grid, parts, P.grid, flagq, flag, tgt, c->xwg_err, tp);
-        else             hipLaunchKernelGGL((k_qkv_attn_o<QT, 3, false, true>), grid, block, lds, st, aq, aa, a, Pq.grid, parts, P.grid, flagq, flag, tgt, c->xwg_err, tp);
-    }
-    else if (rounds <= 1) hipLaunchKernelGGL((k_qkv_attn_o<QT, 1, false>), grid, block, lds, st, aq, aa, a, Pq.grid, parts, P.grid, flagq, flag, tgt, c->xwg_err, tp);
-    else                  hipLaunchKernelGGL((k_qkv_attn_o<QT, 3, false>), grid, block, lds, st, aq, aa, a, Pq.grid, parts, P.grid, flagq, flag, tgt, c->xwg_err, tp);
+    const int want[] = {qv, preq ? 0 : rounds_class(rounds), preq, G > 1, c->world > 1};
+    const int want_o[] = {want[0], want[1], want[2], want[3]};
+    const bool found = with_qkv
+        ? dispatch(VQkvAttnO{}, want, [&](auto v) { using V = decltype(v);
+              hipLaunchKernelGGL((k_qkv_attn_o<V::v[0], V::v[1], V::v[2] != 0, V::v[3] != 0, V::v[4] != 0>), grid, block, lds, st, aq, aa, a, Pq.grid, parts, P.grid, flagq, flag, target, c->xwg_err, tp); })
+        : dispatch(VAttnO{}, want_o, [&](auto v) { using V = decltype(v);
+              hipLaunchKernelGGL((k_attn_o<V::v[0], V::v[1], V::v[2] != 0, V::v[3] != 0>), grid, block, lds, st, aa, a, parts, flag, target, c->xwg_err, tp); });
+    if (!found) return FLM_ERR_UNSUPPORTED;
     HIPC(c, hipGetLastError());
     return FLM_OK;
 }
 
 // FFN13 + FFN2 of layer l in one launch (k_ffn); returns FLM_ERR_UNSUPPORTED when the shape does not allow it
-template <int QT>
-int launch_ffn(flm_ctx* c, hipStream_t st, int l) {
+static int launch_ffn(flm_ctx* c, hipStream_t st, int qt, int l) {
     GemvArgs a13 = args_ffn13(c, l), a2 = args_ffn2(c, l);
-    const int wgs = c->cu_count < 256 ? c->cu_count : 256;       // every workgroup resident, one flag line each
+    const int qv = quant_variant(qt), wgs = c->cu_count < 256 ? c->cu_count : 256;       // every workgroup resident, one flag line each
     GemvPlan P13, P2;
-    int r = plan_gemv<QT, PRO_RMSNORM_QUANT, EPI_SWIGLU>(c, a13, wgs, P13); if (r) return r;
-    r = plan_gemv<QT, PRO_QUANT, EPI_RESIDUAL>(c, a2, wgs, P2); if (r) return r;
-    const int r13 = (a13.n + kGemvBlock * 4 - 1) / (kGemvBlock * 4), r2 = (a2.n + kGemvBlock * 4 - 1) / (kGemvBlock * 4);
-    if (r13 > 1 || r2 > 3) return FLM_ERR_UNSUPPORTED;
+    int r = plan_gemv(c, a13, c->esz, PRO_RMSNORM_QUANT, EPI_SWIGLU, wgs, P13); if (r) return r;
+    r = plan_gemv(c, a2, c->esz, PRO_QUANT, EPI_RESIDUAL, wgs, P2); if (r) return r;
+    const int r2 = gemv_rounds(a2.n);
+    if (gemv_rounds(a13.n) > 1 || r2 > 3) return FLM_ERR_UNSUPPORTED;
     const size_t lds = P13.lds > P2.lds ? P13.lds : P2.lds;
     const int grid = P13.grid > P2.grid ? P13.grid : P2.grid;
     unsigned* flag = c->flag_lines + 512 * 16;                    // value = layer + 1; k_embed clears the lines at the start of the token
+    unsigned target = (unsigned)(l + 1);
     FfnTp tp{};
     if (c->world > 1) {
         // across ranks: FFN13 consumes the x1 exchange behind the Wo launch (folded flag round, kind 1); one line per RANK for hd (in the exchange buffer, behind the head lines)
         set_fold(c, a13, l, 1);
         tp.world = c->world; tp.rank = c->rank; tp.base = c->eng_base; tp.add = (unsigned)(4 * l + 3); tp.counter = c->ffn_counter;
         for (int r = 0; r < c->world; ++r) tp.peer_flags[r] = (unsigned*)(c->peer[r] + c->x_hflags_off) + 256 * 16;
-        flag = (unsigned*)(c->xbuf + c->x_hflags_off) + 256 * 16;
-        if (r2 <= 1) hipLaunchKernelGGL((k_ffn<QT, 1, true>), dim3(grid), dim3(kGemvBlock), lds, st, a13, a2, P13.grid, P2.grid, flag, 0u, c->xwg_err, tp);
-        else         hipLaunchKernelGGL((k_ffn<QT, 3, true>), dim3(grid), dim3(kGemvBlock), lds, st, a13, a2, P13.grid, P2.grid, flag, 0u, c->xwg_err, tp);
-        HIPC(c, hipGetLastError());
-        return FLM_OK;
+        flag = (unsigned*)(c->xbuf + c->x_hflags_off) + 256 * 16; target = 0u;
     }
-    if (r2 <= 1) hipLaunchKernelGGL((k_ffn<QT, 1>), dim3(grid), dim3(kGemvBlock), lds, st, a13, a2, P13.grid, P2.grid, flag, (unsigned)(l + 1), c->xwg_err, tp);
-    else         hipLaunchKernelGGL((k_ffn<QT, 3>), dim3(grid), dim3(kGemvBlock), lds, st, a13, a2, P13.grid, P2.grid, flag, (unsigned)(l + 1), c->xwg_err, tp);
+    const int want[] = {qv, rounds_class(r2), c->world > 1};
+    if (!dispatch(VFfn{}, want, [&](auto v) { using V = decltype(v);
+            hipLaunchKernelGGL((k_ffn<V::v[0], V::v[1], V::v[2] != 0>), dim3(grid), dim3(kGemvBlock), lds, st, a13, a2, P13.grid, P2.grid, flag, target, c->xwg_err, tp); }))
+        return FLM_ERR_UNSUPPORTED;
     HIPC(c, hipGetLastError());
     return FLM_OK;
 }
 
+// the launches a token and flm_kernel_times share, each written once
+static int launch_embed(flm_ctx* c, hipStream_t st) {
+    const int dim = c->d.dim;
+    hipLaunchKernelGGL(k_embed, dim3((dim + 255) / 256), dim3(256), 0, st, c->x1, (const void*)c->emb, (const float*)c->emb_s, c->emb_qt, dim, (const int*)&c->state->tok, c->flag_lines, c->eng_base, c->ffn_counter, halt_ptr(c));
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
+// ATTN task (execute_attn :441-449): local heads write their slice of the full att_out vector (on every rank, peer to peer); G > 1: a head spread over G workgroups
+static int launch_attn_decode(flm_ctx* c, hipStream_t st, int l, int G, bool trace) {
+    AttnArgs aa = args_attn(c, l, G); if (trace) aa.trace = c->trace;
+    hipLaunchKernelGGL(G > 1 ? k_attn_decode<true> : k_attn_decode<false>, dim3(c->heads_local * (G > 1 ? G : 1)), dim3(kAttnBlock), attn_lds_bytes(c->d.max_seq_len, c->hs, G > 1), st, aa);
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
+// the sampler's argument block on `row` (the logits, or the shaped row)
+static SampleArgs args_sample(flm_ctx* c, const float* row) {
+    SampleArgs sa{};
+    sa.logits = row; sa.n = c->d.vocab_size; sa.sp = c->sparams; sa.st = c->state; sa.out_tokens = c->out_tokens_dev; sa.out_cap = c->out_cap; sa.advance = 1; sa.sort_buf = c->sort_buf; sa.err = c->xwg_err;
+    return sa;
+}
+// tok <- the first maximum of `row`, pos++, the id recorded in the call's output ids
+static int launch_argmax_advance(flm_ctx* c, hipStream_t st, const float* row) {
+    hipLaunchKernelGGL(k_argmax_advance, dim3(1), dim3(1024), 0, st, row, c->d.vocab_size, c->state, c->out_tokens_dev, 1, c->out_cap, (const int*)c->xwg_err);
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
 
 // one activation exchange between the tensor-parallel ranks (the reference's threads share the vector in memory instead):
 // peer-to-peer (the producer already stored its slice everywhere: flag round only) or an RCCL all-gather
@@ -280,38 +255,67 @@ int launch_logprob_token(flm_ctx* c, hipStream_t st) {
     HIPC(c, hipGetLastError());
     return FLM_OK;
 }
+// what a token does behind its classifier (flm_host.h TokenForm): the shaper, the draw (sampler, entropy stage or first maximum) and the record, by form
+static int enqueue_draw(flm_ctx* c, hipStream_t st, TokenForm form, bool tp) {
+    const auto& d = c->d;
+    if (form == TokenForm::Logits) return FLM_OK;
+    const bool shaped = shaped_form(form);
+    const float* row = c->logits;
+    if (shaped) {   // a shaped token: the shaper writes the shaped row, the sampler (unchanged) draws from it
+        if (tp) return fail(c, FLM_ERR_UNSUPPORTED, "shaped token: one GPU only");
+        ShapeArgs ha{};
+        ha.logits = c->logits; ha.out = c->shape_row; ha.n = d.vocab_size; ha.p = c->shape_p; ha.st = c->state; ha.out_tokens = c->out_tokens_dev; ha.out_cap = c->out_cap; ha.dfa = c->dfa_blk;
+        hipLaunchKernelGGL(k_shape_logits, dim3(1), dim3(kSampleBlock), 0, st, ha);
+        HIPC(c, hipGetLastError());
+        row = c->shape_row;
+    }
+    // a sampled token: every rank samples the same all-gathered logits with the same state and draws the same token
+    if (form == TokenForm::Sampled && !sample_supported(c)) return fail(c, FLM_ERR_UNSUPPORTED, "device sampler: vocabulary too large for one workgroup's LDS");
+    {
+        Tick t(c, st, KC_ARGMAX);
+        if ((shaped || form == TokenForm::Sampled) && sample_supported(c)) {
+            SampleArgs sa = args_sample(c, row);
+            if (shaped) sa.stop = c->stop_blk;                                 // (the stop rules: the shaped forms only, flm_stop.h)
+            if (form == TokenForm::ShapedEnt) {                                // flm_entropy_set: the stage, the draw, mu's update and the tail in one launch (flm_entropy.h)
+                if (!c->ent_blk) return fail(c, FLM_ERR_UNSUPPORTED, "entropy token: no device block");
+                hipLaunchKernelGGL(k_entropy_advance, dim3(1), dim3(kSampleBlock), sample_lds_bytes(d.vocab_size), st, EntropyArgs{sa, c->ent_blk});
+            } else {
+                hipLaunchKernelGGL(k_sample_advance, dim3(1), dim3(kSampleBlock), sample_lds_bytes(d.vocab_size), st, sa);
+            }
+            HIPC(c, hipGetLastError());
+        } else {          // greedy; a shaped token whose vocabulary is beyond the sampler (the entry points admit temperature 0 only there): the first maximum of the row
+            if (form == TokenForm::ShapedEnt) return fail(c, FLM_ERR_UNSUPPORTED, "entropy token: vocabulary too large for one workgroup's LDS");
+            const int r = launch_argmax_advance(c, st, row); if (r) return r;
+        }
+    }
+    if (form == TokenForm::ShapedLp) return launch_logprob_token(c, st);   // an armed context: the drawn token's record (flm_logprob.h)
+    return FLM_OK;
+}
+
 int enqueue_token(flm_ctx* c, hipStream_t st, bool with_cls, TokenForm form, int G) {
     const auto& d = c->d;
     const int qt = d.quant_type, hs = c->hs, L = d.n_layers;
-    const bool tp = sharded(c), coh = tp && c->p2p;
-    if (!tp && with_cls && form == TokenForm::Greedy && c->fuse_tail && c->fuse_token && c->fuse_layer && c->fuse_back && c->fuse_attn_o && c->fuse_ffn && !c->timing && (c->trace_class < 0 || c->trace_class == 103)) {   // (trace builds, class 103: the stamps of the one-launch token's second layer)
+    const TokenPlan P = token_plan(c, G);
+    const bool tp = P.tp, coh = P.coh, fold = P.fold;
+    if (with_cls && form == TokenForm::Greedy && P.runs(LF_TOKEN)) {   // (trace builds, class 103: the stamps of the one-launch token's second layer)
         // a greedy decode token as ONE launch: embedding row, all layers, classifier, argmax + state advance (k_layers<.., TAIL>)
         const int r = launch_layers(c, st, 0, L, G, true);
         if (r != FLM_ERR_UNSUPPORTED) return r;
     }
-    {
-        Tick t(c, st, KC_EMBED);
-        hipLaunchKernelGGL(k_embed, dim3((d.dim + 255) / 256), dim3(256), 0, st, c->x1, (const void*)c->emb, (const float*)c->emb_s, c->emb_qt, d.dim, (const int*)&c->state->tok, c->flag_lines, c->eng_base, c->ffn_counter, halt_ptr(c));
-        HIPC(c, hipGetLastError());
-    }
+    int r;
+    { Tick t(c, st, KC_EMBED); r = launch_embed(c, st); if (r) return r; }
     const int wgs = gemv_grid(c->cu_count, c->wg_per_cu, 0, 0);
     auto traced = [&](GemvArgs a, int kc, int l) { if (kAblate && c->trace_class == kc && l == 0) a.trace = c->trace; return a; };
-    int r;
     // tensor parallel, peer to peer: the flag rounds of the att / x1 / hd exchanges happen inside the launches that consume them (xchg_fold), not in
     // launches of their own; what stays a k_xchg is the logits' exchange and, for a token without classifier, the last x1 exchange (the next token's
     // k_embed rewrites x1: every peer's stores into it must have landed first)
     // (ranks sharing a device need a CU partition each -- "cu_parts" -- or a consumer that fills the device while it polls keeps its peers' producers out)
-    const bool fold = tp && c->p2p && c->world > 1 && c->grp_fold;          // (agreed by the group at flm_p2p_import)
     auto folded = [&](GemvArgs a, int l, int kind) { if (fold && l >= 0) set_fold(c, a, l, kind); return a; };
-    // launches that span the ranks wait across workgroups of one launch too: only where the census found one workgroup per CU resident (a CU partition
-    // made for the tests is sized for it: launches are cut to the partition)
-    const bool span = fold && c->grp_span;
-    const int tpfa = span ? c->grp_tpfa : 0, tpff = span ? c->grp_tpff : 0;
-    if (!tp && c->fuse_token && c->fuse_layer && c->fuse_back && c->fuse_attn_o && c->fuse_ffn && !c->timing && (c->trace_class < 0 || c->trace_class == 103)) {   // all layers in one launch
+    if (P.runs(LF_LAYERS)) {   // all layers in one launch
         r = launch_layers(c, st, 0, L, G);
         if (r == FLM_OK) goto layers_done; else if (r != FLM_ERR_UNSUPPORTED) return r;
     }
-    if (span && c->grp_tpl && c->fuse_token && !c->timing && c->trace_class < 0) {   // tensor parallel: all layers in one launch that spans the ranks (k_layers<.., TP>)
+    if (P.runs(LF_LAYERS_TP)) {   // tensor parallel: all layers in one launch that spans the ranks (k_layers<.., TP>)
         r = launch_layers(c, st, 0, L, G);
         if (r == FLM_OK) {
             // (a token without classifier: the next token's k_embed rewrites x1 -- every peer's stores of the last layer's rows into it must have landed first; with one, the
@@ -322,34 +326,27 @@ int enqueue_token(flm_ctx* c, hipStream_t st, bool with_cls, TokenForm form, int
     }
     for (int l = 0; l < L; ++l) {
         bool fused = false;
-        const bool back_ok = !tp && c->fuse_back && c->fuse_attn_o && c->fuse_ffn && !c->timing && (c->trace_class < 0 || c->trace_class == 102);
-        if (back_ok && c->fuse_layer) {   // the whole layer in one launch
+        if (P.runs(LF_LAYER)) {   // the whole layer in one launch
             r = launch_layer(c, st, qt, l, true, G);
             if (r == FLM_OK) continue; else if (r != FLM_ERR_UNSUPPORTED) return r;
         }
-        if (((!tp && c->fuse_attn_o && (c->fuse_qkv >= 2 || (c->fuse_qkv && G > 1))) || (span && tpfa >= 2)) && !c->timing && c->trace_class < 0) {   // QKV + attention + ATTN_O in one launch (tensor parallel: "tp_fuse_attn" 2)
-            r = qt == FLM_QT_INT8 ? launch_qkv_attn_o<QT_INT8>(c, st, l, G) : launch_qkv_attn_o<QT_INT16>(c, st, l, G);
+        if (P.runs(LF_QKV_ATTN_O)) {   // QKV + attention + ATTN_O in one launch (tensor parallel: "tp_fuse_attn" 2)
+            r = launch_attn_o(c, st, qt, l, G, true);
             if (r == FLM_OK) fused = true; else if (r != FLM_ERR_UNSUPPORTED) return r;
         }
         if (!fused) {   // QKV task + RoPE + KV append (transformer.cpp:132-135, execute_qkv :386-395, execute_attn :431-439): this rank's heads
             Tick t(c, st, KC_QKV);
             r = launch_gemv<PRO_RMSNORM_QUANT, EPI_ROPE_KV>(c, st, qt, folded(traced(args_qkv(c, l), KC_QKV, l), l - 1, 3), wgs, coh); if (r) return r;
         }
-        if (!fused && back_ok && G == 1) {   // attention + ATTN_O + FFN13 + FFN2 in one launch
+        if (!fused && P.runs(LF_BACK) && G == 1) {   // attention + ATTN_O + FFN13 + FFN2 in one launch
             r = launch_layer(c, st, qt, l, false);
             if (r == FLM_OK) continue; else if (r != FLM_ERR_UNSUPPORTED) return r;
         }
-        if (!fused && ((!tp && c->fuse_attn_o) || (span && tpfa)) && !c->timing && (c->trace_class < 0 || c->trace_class == 101)) {   // attention + ATTN_O in one launch (tensor parallel: across the ranks)
-            r = qt == FLM_QT_INT8 ? launch_attn_o<QT_INT8>(c, st, l, G) : launch_attn_o<QT_INT16>(c, st, l, G);
+        if (!fused && P.runs(LF_ATTN_O)) {   // attention + ATTN_O in one launch (tensor parallel: across the ranks)
+            r = launch_attn_o(c, st, qt, l, G, false);
             if (r == FLM_OK) fused = true; else if (r != FLM_ERR_UNSUPPORTED) return r;
         }
-        if (!fused) {   // ATTN task (execute_attn :441-449): local heads write their slice of the full att_out vector (on every rank, peer to peer)
-            Tick t(c, st, KC_ATTN);
-            AttnArgs aa = args_attn(c, l, G); if (kAblate && c->trace_class == KC_ATTN && l == 0) aa.trace = c->trace;
-            if (G > 1) hipLaunchKernelGGL(k_attn_decode<true>, dim3(c->heads_local * G), dim3(kAttnBlock), attn_lds_bytes(d.max_seq_len, hs, true), st, aa);
-            else       hipLaunchKernelGGL(k_attn_decode<false>, dim3(c->heads_local), dim3(kAttnBlock), attn_lds_bytes(d.max_seq_len, hs, false), st, aa);
-            HIPC(c, hipGetLastError());
-        }
+        if (!fused) { Tick t(c, st, KC_ATTN); r = launch_attn_decode(c, st, l, G, kAblate && c->trace_class == KC_ATTN && l == 0); if (r) return r; }
         // every rank needs all heads' outputs: the reference's threads share x2 in memory (transformer.cpp:451-454)
         if (tp && !fold) { r = exchange(c, st, XK_ATT, c->att_out, c->att_out + (size_t)c->plan.head_begin * hs, c->dim_local); if (r) return r; }
         if (!fused) {   // ATTN_O task + residual (transformer.cpp:138-139, execute_attn_o :457-466): this rank's rows of Wo
@@ -357,8 +354,8 @@ int enqueue_token(flm_ctx* c, hipStream_t st, bool with_cls, TokenForm form, int
             r = launch_gemv<PRO_QUANT, EPI_RESIDUAL>(c, st, qt, folded(traced(args_o(c, l), KC_ATTN_O, l), l, 0), wgs, coh); if (r) return r;
         }
         if (tp && !fold) { r = exchange(c, st, XK_X1, c->x1, c->x1 + c->drow_begin, c->drow_count); if (r) return r; }
-        if (((!tp && c->fuse_ffn) || (span && tpff)) && !c->timing && c->trace_class < 0) {   // FFN13 + FFN2 in one launch (tensor parallel: across the ranks)
-            r = qt == FLM_QT_INT8 ? launch_ffn<QT_INT8>(c, st, l) : launch_ffn<QT_INT16>(c, st, l);
+        if (P.runs(LF_FFN)) {   // FFN13 + FFN2 in one launch (tensor parallel: across the ranks)
+            r = launch_ffn(c, st, qt, l);
             if (r == FLM_OK) {
                 if (tp && l == L - 1 && !with_cls) { r = exchange(c, st, XK_X1, c->x1, c->x1 + c->drow_begin, c->drow_count); if (r) return r; }   // (see below)
                 continue;
@@ -382,43 +379,7 @@ layers_done:
             r = launch_gemv<PRO_RMSNORM_QUANT, EPI_STORE>(c, st, qt, folded(traced(args_cls(c), KC_CLS, 0), L - 1, 3), wgs, coh); if (r) return r;
         }
         if (tp) { r = exchange(c, st, XK_LOGITS, c->logits, c->logits + (size_t)c->rank * c->vocab_slot, c->vocab_slot); if (r) return r; }
-        if (shaped_form(form)) {   // a shaped token: the shaper writes the shaped row, the sampler (unchanged) draws from it
-            if (tp) return fail(c, FLM_ERR_UNSUPPORTED, "shaped token: one GPU only");
-            ShapeArgs ha{};
-            ha.logits = c->logits; ha.out = c->shape_row; ha.n = d.vocab_size; ha.p = c->shape_p; ha.st = c->state; ha.out_tokens = c->out_tokens_dev; ha.out_cap = c->out_cap; ha.dfa = c->dfa_blk;
-            hipLaunchKernelGGL(k_shape_logits, dim3(1), dim3(kSampleBlock), 0, st, ha);
-            HIPC(c, hipGetLastError());
-            {
-                Tick t(c, st, KC_ARGMAX);
-                if (sample_supported(c)) {
-                    SampleArgs sa{};
-                    sa.logits = c->shape_row; sa.n = d.vocab_size; sa.sp = c->sparams; sa.st = c->state; sa.out_tokens = c->out_tokens_dev; sa.out_cap = c->out_cap; sa.advance = 1; sa.sort_buf = c->sort_buf; sa.err = c->xwg_err;
-                    sa.stop = c->stop_blk;                                             // (the stop rules: the shaped forms only, flm_stop.h)
-                    if (form == TokenForm::ShapedEnt) {                                // flm_entropy_set: the stage, the draw, mu's update and the tail in one launch (flm_entropy.h)
-                        if (!c->ent_blk) return fail(c, FLM_ERR_UNSUPPORTED, "entropy token: no device block");
-                        hipLaunchKernelGGL(k_entropy_advance, dim3(1), dim3(kSampleBlock), sample_lds_bytes(d.vocab_size), st, EntropyArgs{sa, c->ent_blk});
-                    } else {
-                        hipLaunchKernelGGL(k_sample_advance, dim3(1), dim3(kSampleBlock), sample_lds_bytes(d.vocab_size), st, sa);
-                    }
-                } else {          // (the entry points admit temperature 0 only here: the first maximum of the shaped row)
-                    if (form == TokenForm::ShapedEnt) return fail(c, FLM_ERR_UNSUPPORTED, "entropy token: vocabulary too large for one workgroup's LDS");
-                    hipLaunchKernelGGL(k_argmax_advance, dim3(1), dim3(1024), 0, st, (const float*)c->shape_row, d.vocab_size, c->state, c->out_tokens_dev, 1, c->out_cap, (const int*)c->xwg_err);
-                }
-                HIPC(c, hipGetLastError());
-            }
-            if (form == TokenForm::ShapedLp) { r = launch_logprob_token(c, st); if (r) return r; }   // an armed context: the drawn token's record (flm_logprob.h)
-        } else if (form == TokenForm::Sampled) {   // a sampled token: every rank samples the same all-gathered logits with the same state and draws the same token
-            if (!sample_supported(c)) return fail(c, FLM_ERR_UNSUPPORTED, "device sampler: vocabulary too large for one workgroup's LDS");
-            Tick t(c, st, KC_ARGMAX);
-            SampleArgs sa{};
-            sa.logits = c->logits; sa.n = d.vocab_size; sa.sp = c->sparams; sa.st = c->state; sa.out_tokens = c->out_tokens_dev; sa.out_cap = c->out_cap; sa.advance = 1; sa.sort_buf = c->sort_buf; sa.err = c->xwg_err;
-            hipLaunchKernelGGL(k_sample_advance, dim3(1), dim3(kSampleBlock), sample_lds_bytes(d.vocab_size), st, sa);
-            HIPC(c, hipGetLastError());
-        } else if (form != TokenForm::Logits) {
-            Tick t(c, st, KC_ARGMAX);
-            hipLaunchKernelGGL(k_argmax_advance, dim3(1), dim3(1024), 0, st, (const float*)c->logits, d.vocab_size, c->state, c->out_tokens_dev, 1, c->out_cap, (const int*)c->xwg_err);
-            HIPC(c, hipGetLastError());
-        }
+        return enqueue_draw(c, st, form, tp);
     } else if (form == TokenForm::Prompt) {
         hipLaunchKernelGGL(k_advance_prompt, dim3(1), dim3(64), 0, st, c->state, (const int*)c->prompt_dev);
         HIPC(c, hipGetLastError());
@@ -457,43 +418,30 @@ int flm_kernel_times(flm_ctx* c, int pos, int iters, float* avg_us, int32_t* cou
     r = set_state(c, pos, 1 % d.vocab_size, 0); if (r) return r;
     EvPair ev; HIPC(c, hipEventCreate(&ev.e0)); HIPC(c, hipEventCreate(&ev.e1));
     const hipEvent_t e0 = ev.e0, e1 = ev.e1;
+    const int G = attn_parts(c, pos + 1);
+    const TokenPlan P = token_plan(c, G);             // (the half the options decide: a form is timed wherever they allow it and the shape supports it, whatever the token would prefer)
     auto launch = [&](int kc, int l) -> int {
         switch (kc) {
-        case KC_EMBED:  hipLaunchKernelGGL(k_embed, dim3((d.dim + 255) / 256), dim3(256), 0, st, c->x1, (const void*)c->emb, (const float*)c->emb_s, c->emb_qt, d.dim, (const int*)&c->state->tok, c->flag_lines, c->eng_base, c->ffn_counter, halt_ptr(c)); return FLM_OK;
+        case KC_EMBED:  return launch_embed(c, st);
         case KC_QKV:    return launch_gemv<PRO_RMSNORM_QUANT, EPI_ROPE_KV>(c, st, qt, args_qkv(c, l), wgs);
-        case KC_ATTN:   { const int G = attn_parts(c, pos + 1);
-                          if (G > 1) hipLaunchKernelGGL(k_attn_decode<true>, dim3(c->heads_local * G), dim3(kAttnBlock), attn_lds_bytes(d.max_seq_len, c->hs, true), st, args_attn(c, l, G));
-                          else       hipLaunchKernelGGL(k_attn_decode<false>, dim3(c->heads_local), dim3(kAttnBlock), attn_lds_bytes(d.max_seq_len, c->hs, false), st, args_attn(c, l, 1));
-                          return FLM_OK; }
+        case KC_ATTN:   return launch_attn_decode(c, st, l, G, false);
         case KC_ATTN_O: return launch_gemv<PRO_QUANT, EPI_RESIDUAL>(c, st, qt, args_o(c, l), wgs);
         case KC_FFN13:  return launch_gemv<PRO_RMSNORM_QUANT, EPI_SWIGLU>(c, st, qt, args_ffn13(c, l), wgs);
         case KC_FFN2:   return launch_gemv<PRO_QUANT, EPI_RESIDUAL>(c, st, qt, args_ffn2(c, l), wgs);
         case KC_CLS:    return launch_gemv<PRO_RMSNORM_QUANT, EPI_STORE>(c, st, qt, args_cls(c), wgs);
         case KC_ARGMAX: hipLaunchKernelGGL(k_argmax_advance, dim3(1), dim3(1024), 0, st, (const float*)c->logits, d.vocab_size, c->state, (int*)nullptr, 0, 0); return FLM_OK;   // (no id is recorded: the step counter runs on)
         // the fused launches the token path uses on a single GPU (FLM_ERR_UNSUPPORTED: this shape / option setting runs the phases separately)
-        case KC_ATTN_WO: if (!c->fuse_attn_o || c->world > 1) return FLM_ERR_UNSUPPORTED;      // (across ranks the launch waits for its peers' heads: not timed in isolation)
-                         return qt == FLM_QT_INT8 ? launch_attn_o<QT_INT8>(c, st, l, attn_parts(c, pos + 1)) : launch_attn_o<QT_INT16>(c, st, l, attn_parts(c, pos + 1));
-        case KC_FFN:     if (!c->fuse_ffn || c->world > 1) return FLM_ERR_UNSUPPORTED;
-                         return qt == FLM_QT_INT8 ? launch_ffn<QT_INT8>(c, st, l) : launch_ffn<QT_INT16>(c, st, l);
-        case KC_QKV_ATTN_WO: { const int G = attn_parts(c, pos + 1);
-                         if (c->world > 1) return FLM_ERR_UNSUPPORTED;
-                         if (!c->fuse_attn_o || !(c->fuse_qkv >= 2 || (c->fuse_qkv && G > 1))) return FLM_ERR_UNSUPPORTED;
-                         return qt == FLM_QT_INT8 ? launch_qkv_attn_o<QT_INT8>(c, st, l, G) : launch_qkv_attn_o<QT_INT16>(c, st, l, G); }
-        case KC_LAYER: case KC_BACK: {
-                         if (c->world > 1 || !c->fuse_back || !c->fuse_attn_o || !c->fuse_ffn || (kc == KC_BACK && attn_parts(c, pos + 1) != 1) || (kc == KC_LAYER) != (c->fuse_layer != 0)) return FLM_ERR_UNSUPPORTED;
-                         return launch_layer(c, st, qt, l, kc == KC_LAYER, attn_parts(c, pos + 1)); }
-        case KC_LAYERS: {   // ONE launch for the L layers (enqueued for l == 0)
-                         if (c->world > 1 || !c->fuse_token || !c->fuse_layer || !c->fuse_back || !c->fuse_attn_o || !c->fuse_ffn) return FLM_ERR_UNSUPPORTED;
+        case KC_ATTN_WO:     return P.opt[LF_ATTN_O] ? launch_attn_o(c, st, qt, l, G, false) : FLM_ERR_UNSUPPORTED;
+        case KC_FFN:         return P.opt[LF_FFN] ? launch_ffn(c, st, qt, l) : FLM_ERR_UNSUPPORTED;
+        case KC_QKV_ATTN_WO: return P.opt[LF_QKV_ATTN_O] ? launch_attn_o(c, st, qt, l, G, true) : FLM_ERR_UNSUPPORTED;
+        case KC_LAYER:       return P.opt[LF_LAYER] ? launch_layer(c, st, qt, l, true, G) : FLM_ERR_UNSUPPORTED;
+        case KC_BACK:        return P.opt[LF_BACK] && !P.opt[LF_LAYER] && G == 1 ? launch_layer(c, st, qt, l, false, G) : FLM_ERR_UNSUPPORTED;    // (timed only where the token takes it: "fuse_layer" 0, one workgroup per head)
+        case KC_LAYERS: case KC_TOKEN: {   // ONE launch for the L layers / for the whole greedy token: embedding row, the L layers, classifier, argmax + state advance (enqueued for l == 0;
+                         // the token moves the state on: put back first)
+                         if (!P.opt[kc == KC_TOKEN ? LF_TOKEN : LF_LAYERS]) return FLM_ERR_UNSUPPORTED;
                          if (l != 0) return FLM_OK;
-                         const int G = attn_parts(c, pos + 1);
                          const int rr = layers_prepare(c, G); if (rr) return rr;
-                         return launch_layers(c, st, 0, L, G); }
-        case KC_TOKEN: {    // ONE launch for the whole greedy token: embedding row, the L layers, classifier, argmax + state advance (enqueued for l == 0; it moves the state on: put back first)
-                         if (c->world > 1 || !c->fuse_tail || !c->fuse_token || !c->fuse_layer || !c->fuse_back || !c->fuse_attn_o || !c->fuse_ffn) return FLM_ERR_UNSUPPORTED;
-                         if (l != 0) return FLM_OK;
-                         const int G = attn_parts(c, pos + 1);
-                         const int rr = layers_prepare(c, G); if (rr) return rr;
-                         return launch_layers(c, st, 0, L, G, true); }
+                         return launch_layers(c, st, 0, L, G, kc == KC_TOKEN); }
         default: return FLM_OK;
         }
     };
@@ -527,21 +475,28 @@ int flm_kernel_bytes(flm_ctx* c, int kclass, int pos, double* bytes) {
     if (!c || !bytes) return FLM_ERR_INVALID;
     const auto& d = c->d; const double e = c->esz, sb = 4.0 / kGroup;
     auto mat = [&](double rows, double cols) { return rows * cols * (e + sb); };
+    // the five phases of a layer (every term an integer multiple of 1/16 far below 2^53: the sums are exact in any grouping)
+    const double qkv = mat(3.0 * c->dim_local, d.dim) + d.dim * 4.0;               // + rmsnorm weight
+    const double attn = 2.0 * c->heads_local * c->hs * 4.0 * (pos + 1);            // fp32 K and V rows
+    const double wo = mat(c->drow_count, d.dim);
+    const double ffn13 = 2.0 * mat(c->hidden_local, d.dim) + d.dim * 4.0;
+    const double ffn2 = mat(c->drow_count, d.hidden_dim);
+    const double layer = qkv + attn + wo + ffn13 + ffn2, cls = mat(c->cls.rows, d.dim) + d.dim * 4.0;
     switch (kclass) {
     case KC_EMBED:  *bytes = d.dim * 4.0; break;
-    case KC_QKV:    *bytes = mat(3.0 * c->dim_local, d.dim) + d.dim * 4.0; break;               // + rmsnorm weight
-    case KC_ATTN:   *bytes = 2.0 * c->heads_local * c->hs * 4.0 * (pos + 1); break;             // fp32 K and V rows
-    case KC_ATTN_O: *bytes = mat(c->drow_count, d.dim); break;
-    case KC_FFN13:  *bytes = 2.0 * mat(c->hidden_local, d.dim) + d.dim * 4.0; break;
-    case KC_FFN2:   *bytes = mat(c->drow_count, d.hidden_dim); break;
-    case KC_ATTN_WO: *bytes = 2.0 * c->heads_local * c->hs * 4.0 * (pos + 1) + mat(c->drow_count, d.dim); break;
-    case KC_FFN:    *bytes = 2.0 * mat(c->hidden_local, d.dim) + d.dim * 4.0 + mat(c->drow_count, d.hidden_dim); break;
-    case KC_QKV_ATTN_WO: *bytes = mat(3.0 * c->dim_local, d.dim) + d.dim * 4.0 + 2.0 * c->heads_local * c->hs * 4.0 * (pos + 1) + mat(c->drow_count, d.dim); break;
-    case KC_CLS:    *bytes = mat(c->cls.rows, d.dim) + d.dim * 4.0; break;
-    case KC_BACK:   *bytes = 2.0 * c->heads_local * c->hs * 4.0 * (pos + 1) + mat(c->drow_count, d.dim) + 2.0 * mat(c->hidden_local, d.dim) + d.dim * 4.0 + mat(c->drow_count, d.hidden_dim); break;
-    case KC_LAYER:  *bytes = mat(3.0 * c->dim_local, d.dim) + d.dim * 4.0 + 2.0 * c->heads_local * c->hs * 4.0 * (pos + 1) + mat(c->drow_count, d.dim) + 2.0 * mat(c->hidden_local, d.dim) + d.dim * 4.0 + mat(c->drow_count, d.hidden_dim); break;
-    case KC_LAYERS: *bytes = (double)d.n_layers * (mat(3.0 * c->dim_local, d.dim) + d.dim * 4.0 + 2.0 * c->heads_local * c->hs * 4.0 * (pos + 1) + mat(c->drow_count, d.dim) + 2.0 * mat(c->hidden_local, d.dim) + d.dim * 4.0 + mat(c->drow_count, d.hidden_dim)); break;
-    case KC_TOKEN:  { double lb = 0, cb = 0; flm_kernel_bytes(c, KC_LAYERS, pos, &lb); flm_kernel_bytes(c, KC_CLS, pos, &cb); *bytes = lb + cb + d.dim * 4.0; break; }   // the layers + the classifier + the embedding row
+    case KC_QKV:    *bytes = qkv; break;
+    case KC_ATTN:   *bytes = attn; break;
+    case KC_ATTN_O: *bytes = wo; break;
+    case KC_FFN13:  *bytes = ffn13; break;
+    case KC_FFN2:   *bytes = ffn2; break;
+    case KC_ATTN_WO: *bytes = attn + wo; break;
+    case KC_FFN:    *bytes = ffn13 + ffn2; break;
+    case KC_QKV_ATTN_WO: *bytes = qkv + attn + wo; break;
+    case KC_CLS:    *bytes = cls; break;
+    case KC_BACK:   *bytes = attn + wo + ffn13 + ffn2; break;
+    case KC_LAYER:  *bytes = layer; break;
+    case KC_LAYERS: *bytes = (double)d.n_layers * layer; break;
+    case KC_TOKEN:  *bytes = (double)d.n_layers * layer + cls + d.dim * 4.0; break;   // the layers + the classifier + the embedding row
     default:        *bytes = 0; break;
     }
     return FLM_OK;
