@@ -35,6 +35,7 @@ SYMBOLS = (
     "flm_stop_validate", "flm_stop_match", "flm_stop_set", "flm_op_stop_match",
     "flm_draft_set", "flm_generate_draft",
     "flm_entropy_validate", "flm_entropy_set", "flm_entropy_mu", "flm_op_logf", "flm_op_entropy_rows",
+    "flm_fan_layout_for", "flm_generate_n", "flm_fan_keep", "flm_op_attention_fan",
 )
 
 # flm_score (include/flm_gpu.h): one row of flm_score_tokens / flm_op_score_rows
@@ -45,6 +46,16 @@ LOGPROBS_MAX = 20                                  # FLM_LOGPROBS_MAX
 LOGPROB_SOURCES = {"raw": 0, "shaped": 1}          # FLM_LOGPROBS_RAW, FLM_LOGPROBS_SHAPED
 LOGPROB_DTYPE = np.dtype([("token", np.int32), ("logit", np.float32), ("max_logit", np.float32), ("sum", np.float32), ("n_top", np.int32),
                           ("top_id", np.int32, (LOGPROBS_MAX,)), ("top_logit", np.float32, (LOGPROBS_MAX,)), ("pad_", np.int32, (3,))])
+
+# flm_fan_cb: int (*)(void* user, int seq, int index, int32_t token, int last); a non-zero return cancels the whole call
+FAN_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int32, C.c_int)
+FAN_MAX = 16                                       # FLM_FAN_MAX
+
+
+class FanLayout(C.Structure):
+    """flm_fan_layout (include/flm_gpu.h)"""
+    _fields_ = [("shared_rows", C.c_int32), ("tail_rows", C.c_int32), ("n", C.c_int32), ("base", C.c_int32 * FAN_MAX)]
+
 
 # flm_token_cb: int (*)(void* user, int index, int32_t token, int last); a non-zero return cancels
 TOKEN_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int32, C.c_int)
@@ -599,6 +610,48 @@ class Ctx:
             self._h, _p(t), len(t), int(pos), int(max_tokens), sp, st, C.c_int32(int(stop_token)), int(draft_len), int(ngram_max), cb, None, out, n_out),
             max_tokens, on_token, want_ids, rng_state, sampling)
 
+    def generate_n(self, prompt, pos, max_tokens, states=None, n=None, temperature=0.0, topp=0.9, stop_token=-1, on_token=None):
+        """flm_generate_n: n completions of one prompt, one batch per pass over the weights -> (a list of n id arrays, the n sampler states after each sequence's draws).
+        states: the n sequences' sampler states (n = len(states)); None with n given: a NULL pointer (temperature 0 only; the returned states are None).
+        on_token(seq, index, token, last) is called per delivered id; a truthy return cancels the whole call."""
+        if states is None:
+            if n is None:
+                raise ValueError("generate_n: give the sequences' states, or n at temperature 0")
+            if temperature != 0:
+                raise ValueError("generate_n: states must be given at temperature != 0")
+        else:
+            if n is not None and int(n) != len(states):
+                raise ValueError("generate_n: n differs from len(states)")
+            n = len(states)
+        n = int(n)
+        if not 2 <= n <= FAN_MAX:
+            raise ValueError(f"generate_n: n = {n} outside 2 .. {FAN_MAX}")
+        if int(max_tokens) < 1:
+            raise ValueError("generate_n: max_tokens < 1")
+        t = np.ascontiguousarray(prompt, dtype=np.int32)
+        st = None if states is None else np.array([int(x) for x in states], dtype=np.uint64)
+        out = np.full((n, int(max_tokens)), -1, dtype=np.int32); n_out = np.zeros(n, dtype=np.int32)
+        raised = []
+
+        def tramp(_user, seq, index, token, last):
+            try:
+                return 1 if on_token(int(seq), int(index), int(token), bool(last)) else 0
+            except BaseException as e:      # (an exception must not unwind through the C frames: cancel, re-raise behind the call)
+                raised.append(e)
+                return 1
+        cb = FAN_CB(tramp) if on_token is not None else C.cast(None, FAN_CB)
+        rc = lib().flm_generate_n(self._h, _p(t), len(t), int(pos), int(max_tokens), n, C.c_float(temperature), C.c_float(topp), _p(st),
+                                  C.c_int32(int(stop_token)), cb, None, _p(out), _p(n_out))
+        del cb
+        if raised:
+            raise raised[0]
+        _check(rc, self._h)
+        return [out[j, :n_out[j]].copy() for j in range(n)], (None if st is None else [int(x) for x in st])
+
+    def fan_keep(self, seq):
+        """flm_fan_keep: move sequence `seq`'s tail of the last generate_n behind the shared rows; any entry point continues from pos + n_prompt + n_out[seq] - 1"""
+        _check(lib().flm_fan_keep(self._h, int(seq)), self._h)
+
     def draft_set(self, draft):
         """flm_draft_set: pair this (target) context with the draft context `draft` for generate_draft (None: detach).  The target does not own the draft: detach before
         closing either"""
@@ -1023,6 +1076,26 @@ def op_math(fn, x, y=None):
     b = None if y is None else np.ascontiguousarray(y, dtype=np.float32).reshape(-1)
     _check(lib().flm_op_math(int(fn), _p(a), _p(b), C.c_size_t(a.size)))
     return a
+
+
+def fan_layout(pos, n_prompt, max_tokens, n, max_seq_len) -> FanLayout:
+    """flm_fan_layout_for (pure host arithmetic): the rows flm_generate_n uses, or FlmError where the call would refuse"""
+    out = FanLayout()
+    _check(lib().flm_fan_layout_for(int(pos), int(n_prompt), int(max_tokens), int(n), int(max_seq_len), C.byref(out)))
+    return out
+
+
+def op_attention_fan(kc, vc, q, k, v, n_heads, hs, max_seq, S, t, base):
+    """one flm_generate_n step's attention: q, k, v [n, n_heads*hs] at logical position S + t; row j's k / v go to cache row base[j] + t.  kc, vc [n_heads, max_seq, hs]
+    are updated in place; returns out [n, n_heads*hs]."""
+    for a in (kc, vc):
+        assert a.dtype == np.float32 and a.flags.c_contiguous
+    b = np.ascontiguousarray(base, dtype=np.int32); n = len(b)
+    q = np.ascontiguousarray(q, dtype=np.float32); k = np.ascontiguousarray(k, dtype=np.float32); v = np.ascontiguousarray(v, dtype=np.float32)
+    assert q.shape == k.shape == v.shape == (n, n_heads * hs)
+    out = np.empty((n, n_heads * hs), dtype=np.float32)
+    _check(lib().flm_op_attention_fan(_p(out), _p(kc), _p(vc), _p(q), _p(k), _p(v), n_heads, hs, max_seq, n, int(S), int(t), _p(b)))
+    return out
 
 
 def op_attention(kc, vc, q, k, v, n_heads, hs, max_seq, pos):

@@ -149,6 +149,7 @@ const char* shape_fill(const flm_sampling* sp, int vocab, const int32_t* window,
 int check_ready(flm_ctx* c, int n, int pos) {
     if (!c) return FLM_ERR_INVALID;
     c->err_word_fresh = false;                                                  // (an error word a previous call's read-back brought along says nothing about this call)
+    c->fan_valid = false;                                                       // (every entry point that writes the cache comes through here: flm_fan_keep's tails are gone)
     if (!model_complete(c)) return fail(c, FLM_ERR_STATE, "forward before all tensors were uploaded");
     if (n < 1 || pos < 0 || pos + n > c->d.max_seq_len) return fail(c, FLM_ERR_INVALID, "tokens/pos outside [0, max_seq_len]");
     HIPC(c, hipSetDevice(c->device));
@@ -873,6 +874,109 @@ int flm_generate_draft(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos,
     Draw dr;
     if (int r = draw_resolve(c, sampling ? sampling : &neutral, prompt + (n_prompt - tail), tail, true, rng_state, dr, NoOwn(), true, true)) return r;
     return generate_lookup_impl(c, prompt, n_prompt, pos, max_tokens, dr, stop_token, draft_len, 1, cb, user, out_tokens, n_out, d);
+}
+
+// Parallel sampling (include/flm_gpu.h; kernels: flm_fan.h; the batch pass: flm_prompt.hip prefill_batched with a FanDesc).  The layout is pure host arithmetic and the one
+// place the capacity condition is written
+int flm_fan_layout_for(int pos, int n_prompt, int max_tokens, int n, int max_seq_len, flm_fan_layout* out) {
+    if (!out) return FLM_ERR_INVALID;
+    const char* why = nullptr;
+    if (n < 2 || n > FLM_FAN_MAX) why = "fan: n outside 2 .. FLM_FAN_MAX";
+    else if (pos < 0 || n_prompt < 1 || max_tokens < 1 || max_seq_len < 1) why = "fan: pos >= 0, n_prompt >= 1, max_tokens >= 1";
+    else if ((long long)pos + n_prompt + (long long)n * (max_tokens - 1) > max_seq_len) why = "fan: pos + n_prompt + n * (max_tokens - 1) exceeds max_seq_len";
+    if (why) { g_last_error = why; return FLM_ERR_INVALID; }
+    flm_fan_layout l{};
+    l.shared_rows = pos + n_prompt; l.tail_rows = max_tokens - 1; l.n = n;
+    for (int j = 0; j < n; ++j) l.base[j] = l.shared_rows + j * l.tail_rows;
+    *out = l;
+    return FLM_OK;
+}
+// The loop follows generate_lookup_impl's pattern: the prompt through feed (its last token leaves the logits), token 0 of every sequence drawn from that one row, then one
+// step per token with ONE synchronisation (the result block).  The host holds every sequence's last id, state and the live mask; a step starts by writing them into its
+// launches (k_fan_load, the by-value FanIn of the draw and accept kernels) and its kernels write nothing a re-run reads, which is what the retry wrapper needs.  Rows that
+// finished stay in the batch -- they feed their last id again into their own tail rows -- and their outputs are dropped.
+int flm_generate_n(flm_ctx* c, const int32_t* prompt, int n_prompt, int pos, int max_tokens, int n, float temperature, float topp, uint64_t* rng_states,
+                   int32_t stop_token, flm_fan_cb cb, void* user, int32_t* out_tokens, int* n_out) {
+    if (!c || !prompt || !out_tokens || !n_out) return FLM_ERR_INVALID;
+    if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "generate_n: one GPU only");
+    flm_fan_layout lay{};
+    if (flm_fan_layout_for(pos, n_prompt, max_tokens, n, c->d.max_seq_len, &lay)) { c->err = g_last_error; return FLM_ERR_INVALID; }
+    if (!(temperature >= 0.0f) || topp != topp || stop_token >= c->d.vocab_size || (temperature != 0.0f && !rng_states))
+        return fail(c, FLM_ERR_INVALID, "generate_n: temperature >= 0, top-p a number, stop_token < vocab_size (or -1), rng_states given at temperature != 0");
+    if (!ids_in_vocab(c, prompt, n_prompt)) return fail(c, FLM_ERR_INVALID, "token id out of range");
+    if (temperature != 0.0f && !sample_supported(c)) return fail(c, FLM_ERR_UNSUPPORTED, "device sampler: vocabulary too large for one workgroup's LDS (sample on the host)");
+    if (c->hs > 128 || fan_lds_bytes(1, c->d.max_seq_len, c->hs) > kLdsMax) return fail(c, FLM_ERR_UNSUPPORTED, "generate_n: head sizes up to 128 (the multi-query attention's bound)");
+    int r = check_ready(c, n_prompt, pos); if (r) return r;
+    const bool draws = temperature != 0.0f;
+    const int stop = stop_token < 0 ? -1 : stop_token, S = lay.shared_rows;
+    FanIn in{}; in.live = (1u << n) - 1u;
+    for (int j = 0; j < n; ++j) in.rng[j] = draws ? (unsigned long long)rng_states[j] : 0ull;
+    int count[FLM_FAN_MAX] = {0};
+    FanOut fo{};
+    bool cancelled = false;
+    auto accept = [&]() -> int {      // the step's last launch and its one trip back (the error word rides along: xwg_check looks at it next)
+        hipLaunchKernelGGL(k_fan_accept, dim3(1), dim3(64), 0, c->stream, c->fan_res, (const int*)c->fan_drawn, (const unsigned long long*)c->fan_after, in, n, stop);
+        HIPC(c, hipGetLastError());
+        return d2h(c, &fo, c->fan_res, sizeof fo);
+    };
+    auto deliver = [&](int index) {   // a verified step's ids, in sequence order, on this thread; the host's copies move with them
+        for (int j = 0; j < n; ++j) {
+            if (!((in.live >> j) & 1u)) continue;
+            const int32_t id = fo.ids[j];
+            const bool last = !((fo.live >> j) & 1u) || index + 1 == max_tokens;
+            out_tokens[(size_t)j * max_tokens + index] = id; count[j] = index + 1;
+            in.ids[j] = id; in.rng[j] = fo.rng[j];
+            if (cb && !cancelled && cb(user, j, index, id, last ? 1 : 0) != 0) cancelled = true;
+        }
+        in.live = fo.live;
+    };
+    // token 0: the prompt exactly as flm_forward feeds it; every sequence draws from the one row of logits with its own first coin
+    r = with_retry(c, n_prompt, [&]() -> int {
+        int r = feed(c, prompt, n_prompt, pos, TokenForm::Logits); if (r) return r;
+        r = launch_sample_fan(c, c->stream, c->logits, 0, c->d.vocab_size, 0, n, temperature, topp, in, c->sort_buf, c->fan_drawn, c->fan_after); if (r) return r;
+        return accept();
+    }, [&] { deliver(0); });
+    if (r) return r;
+    const bool skinny = c->spec_gemm != 0;
+    int chunk = 1; float* const stage = score_stage(c, &chunk);
+    for (int index = 1; index < max_tokens && in.live && !cancelled; ++index) {
+        FanDesc f{}; f.S = S; f.t = index - 1; f.n = n;
+        for (int j = 0; j < n; ++j) f.base[j] = lay.base[j];
+        r = with_retry(c, n, [&]() -> int {
+            hipLaunchKernelGGL(k_fan_load, dim3(1), dim3(64), 0, c->stream, in, n, c->prompt_dev);
+            HIPC(c, hipGetLastError());
+            int r = prefill_batched_qt(c, n, S + f.t, true, skinny, &f); if (r) return r;
+            for (int r0 = 0; r0 < n; r0 += chunk) {
+                const int m = n - r0 < chunk ? n - r0 : chunk;
+                r = fan_classify(c, r0, m, stage, skinny, temperature, topp, in); if (r) return r;
+            }
+            return accept();
+        }, [&] { deliver(index); });
+        if (r) return r;
+    }
+    long long total = 0;
+    for (int j = 0; j < n; ++j) { n_out[j] = count[j]; total += count[j]; if (draws) rng_states[j] = in.rng[j]; }
+    if (draws) c->sampled += total;
+    // "stop_reason" over the whole call: cancel; else length where any sequence ran to max_tokens; else every sequence ended on the stop token
+    bool any_full = false; for (int j = 0; j < n; ++j) any_full = any_full || count[j] == max_tokens;
+    c->stop_reason = cancelled ? FLM_STOP_CANCEL : any_full ? FLM_STOP_LENGTH : FLM_STOP_TOKEN; c->stop_rule = 0;
+    c->fan_lay = lay; for (int j = 0; j < FLM_FAN_MAX; ++j) c->fan_count[j] = j < n ? count[j] : 0;
+    c->fan_valid = true;
+    return FLM_OK;
+}
+int flm_fan_keep(flm_ctx* c, int seq) {
+    if (!c) return FLM_ERR_INVALID;
+    if (!c->fan_valid) return fail(c, FLM_ERR_INVALID, "fan_keep: no flm_generate_n precedes, or the cache was written since");
+    if (seq < 0 || seq >= c->fan_lay.n) return fail(c, FLM_ERR_INVALID, "fan_keep: seq outside [0, n)");
+    HIPC(c, hipSetDevice(c->device));
+    const int rows = c->fan_count[seq] - 1;
+    c->fan_valid = false;                                             // (the move overwrites tail 0's rows: once)
+    if (seq > 0 && rows > 0) {
+        hipLaunchKernelGGL(k_fan_keep, dim3(c->d.n_layers * c->heads_local), dim3(256), 0, c->stream, c->kcache, c->vcache, c->kv_rows, c->hs, c->fan_lay.base[seq], c->fan_lay.shared_rows, rows);
+        HIPC(c, hipGetLastError());
+        HIPC(c, hipStreamSynchronize(c->stream));
+    }
+    return FLM_OK;
 }
 
 // Constrained decoding (include/flm_gpu.h): the automaton lives in ONE device allocation made here, off the steady path; the shaped token graphs reach it through the block

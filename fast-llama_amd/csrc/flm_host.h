@@ -9,7 +9,7 @@
 //   flm_layerlaunch.hip  the whole-layer launch k_attn_ffn (flm_layer.h) and the layer's argument blocks (plan_layer)
 //   flm_layers.hip       all layers of a token / the whole greedy token in one launch (k_layers); flm_layers_tp.hip: its rank-spanning form
 //   flm_launch.h         from a run-time choice to one instantiation of a kernel template: the variant lists' dispatch() / for_each_variant()
-//   flm_prompt.hip       the batched prompt path (GEMM tiles on the matrix cores, prompt attention)
+//   flm_prompt.hip       the batched prompt path (GEMM tiles on the matrix cores, prompt attention; with a FanDesc: one step of flm_generate_n)
 //   flm_ops.hip          the op-level exports of the parity tests (flm_op_*)
 //   flm_wait.h           (device side, part of flm_kernels.h) every cross-workgroup / cross-rank wait of the fused launches: flag polls, granule pieces, when a wait gives up
 //   flm_tuning.h         the option table: one row per flm_set_option / flm_query key (flm_gpu.hip walks it)
@@ -214,6 +214,11 @@ struct flm_ctx {
     // of every attempt), the host copy -- ent.mu is Mirostat's state behind the ids delivered so far, moved by Draw::commit alone --, the mode (0 off, 1 typical, 2 Mirostat;
     // "entropy") and the state the last attempt's read-back brought along (Draw::fetch; committed only when the attempt is verified)
     flm::EntropyBlock* ent_blk = nullptr; flm_entropy ent{}; int ent_mode = 0; float ent_mu_fetched = 0.0f;
+    // parallel sampling (include/flm_gpu.h flm_generate_n / flm_fan_keep; flm_calls.hip; kernels: flm_fan.h): a step's drawn ids [16] and the states behind the draws [16],
+    // its result block (one trip per step) -- device memory since create --, and what flm_fan_keep needs of the last call: its layout and every sequence's count
+    // (fan_valid: until the next call that writes the cache)
+    int* fan_drawn = nullptr; unsigned long long* fan_after = nullptr; flm::FanOut* fan_res = nullptr;
+    flm_fan_layout fan_lay{}; int fan_count[FLM_FAN_MAX] = {0}; bool fan_valid = false;
     int score_rows = 0;                                // option "score_rows": rows per classifier chunk of flm_score_tokens (0: as many as the staging holds; < 0: one row at a time through c->logits)
     std::map<GraphKey, hipGraphExec_t> graphs;        // the token graphs captured so far (flm_gpu.hip token_graph)
     std::vector<TimedLaunch>* timing = nullptr;
@@ -448,7 +453,14 @@ int feed(flm_ctx* c, const int32_t* tokens, int n, int pos, TokenForm last);
 int d2h(flm_ctx* c, void* dst, const void* src_dev, size_t bytes);
 float* score_stage(const flm_ctx* c, int* chunk);
 constexpr int kPrefillMin = 4;
-int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers = false, bool skinny = false);      // (flm_prompt.hip; by the model's quant type.  all_layers: the last layer is completed too -- flm_score_tokens needs every row's final residual; skinny: int8 and B <= 16: every GEMM through k_gemm_q8_skinny -- the verify pass under "spec_gemm" 1)
+int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers = false, bool skinny = false, const flm::FanDesc* fan = nullptr);      // (flm_prompt.hip; by the model's quant type.  all_layers: the last layer is completed too -- flm_score_tokens needs every row's final residual; skinny: int8 and B <= 16: every GEMM through k_gemm_q8_skinny -- the verify pass under "spec_gemm" 1; fan: the rows are a fan step's -- flm_generate_n)
+// a fan step's pieces (flm_prompt.hip; kernels: flm_fan.h).  fan_classify: rows [row0, row0 + m) through score_classify's prologue and GEMM into `stage`, then k_sample_fan
+// into fan_drawn / fan_after, row j with in.rng[j].  The launchers take c == null from the op-level mirror (flm_op_attention_fan)
+int fan_classify(flm_ctx* c, int row0, int m, float* stage, bool skinny, float temperature, float topp, const flm::FanIn& in);
+int launch_sample_fan(flm_ctx* c, hipStream_t st, const float* logits, int ld, int n, int row0, int rows, float temperature, float topp, const flm::FanIn& in,
+                      unsigned long long* sort_buf, int* drawn, unsigned long long* after);
+int launch_attn_fan(flm_ctx* c, hipStream_t st, const flm::AttnArgs& aa, const flm::FanDesc& f, int heads, int row_stride);
+int launch_rope_kv_fan(flm_ctx* c, hipStream_t st, const float* qkv, float* qout, float* kcache, float* vcache, const float* rope_cos, const float* rope_sin, int dim, int hs, int kv_rows, const flm::FanDesc& f);
 // flm_score_tokens' classifier stage (flm_prompt.hip): rows [row0, row0 + m) of the batch's final residual (pf_x) -> output norm, quantize, the classifier GEMM tiles into
 // `stage` [m][vocab], k_score_rows into score_dev[row0 ..]
 int score_classify(flm_ctx* c, int row0, int m, float* stage);

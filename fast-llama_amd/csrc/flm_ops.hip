@@ -438,6 +438,34 @@ int flm_op_attention(float* out, float* kc, float* vc, const float* q, const flo
     return FLM_OK;
 }
 
+// one flm_generate_n step's RoPE / cache rows / attention on caller-supplied caches: the launches prefill_batched makes with a FanDesc (flm_prompt.hip)
+int flm_op_attention_fan(float* out, float* kc, float* vc, const float* q, const float* k, const float* v,
+                         int n_heads, int hs, int max_seq, int n, int S, int t, const int32_t* base) {
+    if (!out || !kc || !vc || !q || !k || !v || !base || n_heads < 1 || hs < 32 || hs > 128 || hs % 8 || n < 2 || n > FLM_FAN_MAX || S < 1 || t < 0 || max_seq < 1 || S + t + 1 > max_seq) return FLM_ERR_INVALID;
+    FanDesc f{}; f.S = S; f.t = t; f.n = n;
+    for (int j = 0; j < n; ++j) { if (base[j] < 0 || base[j] + t >= max_seq) return FLM_ERR_INVALID; f.base[j] = base[j]; }
+    const int dim = n_heads * hs, pos = S + t;
+    const size_t nd = (size_t)n * dim, nc = (size_t)n_heads * max_seq * hs, h2 = hs / 2;
+    std::vector<float> cs, sn; build_rope_table(hs, pos + 1, cs, sn);
+    std::vector<float> qkv(3 * nd);
+    for (int j = 0; j < n; ++j) {
+        memcpy(&qkv[(size_t)j * 3 * dim], q + (size_t)j * dim, (size_t)dim * 4); memcpy(&qkv[(size_t)j * 3 * dim + dim], k + (size_t)j * dim, (size_t)dim * 4);
+        memcpy(&qkv[(size_t)j * 3 * dim + 2 * dim], v + (size_t)j * dim, (size_t)dim * 4);
+    }
+    DevBuf dqkv, dq, dkc, dvc, dout, dc, dsn;
+    if (dqkv.alloc(3 * nd * 4) || dq.alloc(nd * 4) || dkc.alloc(nc * 4) || dvc.alloc(nc * 4) || dout.alloc(nd * 4) || dc.alloc((pos + 1) * h2 * 4) || dsn.alloc((pos + 1) * h2 * 4)) return FLM_ERR_OOM;
+    OPC(hipMemcpy(dqkv.p, qkv.data(), 3 * nd * 4, hipMemcpyHostToDevice));
+    OPC(hipMemcpy(dkc.p, kc, nc * 4, hipMemcpyHostToDevice)); OPC(hipMemcpy(dvc.p, vc, nc * 4, hipMemcpyHostToDevice));
+    OPC(hipMemcpy(dc.p, cs.data(), (pos + 1) * h2 * 4, hipMemcpyHostToDevice)); OPC(hipMemcpy(dsn.p, sn.data(), (pos + 1) * h2 * 4, hipMemcpyHostToDevice));
+    int r = launch_rope_kv_fan(nullptr, 0, dqkv.as<float>(), dq.as<float>(), dkc.as<float>(), dvc.as<float>(), dc.as<float>(), dsn.as<float>(), dim, hs, max_seq, f); if (r) return r;
+    AttnArgs a{}; a.q = dq.as<float>(); a.kcache = dkc.as<float>(); a.vcache = dvc.as<float>(); a.out = dout.as<float>(); a.hs = hs; a.max_seq = max_seq;
+    r = launch_attn_fan(nullptr, 0, a, f, n_heads, dim); if (r) return r;
+    OPC(hipDeviceSynchronize());
+    OPC(hipMemcpy(out, dout.p, nd * 4, hipMemcpyDeviceToHost));
+    OPC(hipMemcpy(kc, dkc.p, nc * 4, hipMemcpyDeviceToHost)); OPC(hipMemcpy(vc, dvc.p, nc * 4, hipMemcpyDeviceToHost));
+    return FLM_OK;
+}
+
 /* elementary functions exactly as the kernels evaluate them (tests pin them against the host's IEEE results) */
 int flm_op_math(int fn, float* x, const float* y, size_t n) {
     if (!x || n == 0 || fn < 0 || fn > 5 || (fn >= 2 && !y)) return FLM_ERR_INVALID;

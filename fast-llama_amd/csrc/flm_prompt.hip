@@ -85,9 +85,36 @@ int launch_gemm_any(flm_ctx* c, hipStream_t st, const GemmArgs& g, int use_mfma,
     return launch_gemm<QT, EPI>(c, st, g, use_mfma);
 }
 
+// k_attn_fan on the n rows of a fan step (flm_fan.h): queries per workgroup by what the LDS allows; c may be null (flm_op_attention_fan)
+int launch_attn_fan(flm_ctx* c, hipStream_t st, const AttnArgs& aa, const FanDesc& f, int heads, int row_stride) {
+    {   // a group's score rows and tiles can take most of the LDS: raise the kernel's dynamic-LDS limit, once per device
+        static std::mutex mu; static bool done[64] = {false};
+        int dev = 0; HIPC(c, hipGetDevice(&dev));
+        std::lock_guard<std::mutex> lk(mu);
+        if (dev >= 0 && dev < 64 && !done[dev]) {
+            HIPC(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_fan), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
+            done[dev] = true;
+        }
+    }
+    if (aa.hs > 128 || aa.hs % 8 || f.n < 1 || f.n > kFanMax || f.S < 1 || f.t < 0 || f.S + f.t + 1 > aa.max_seq) return fail(c, FLM_ERR_INVALID, "attn_fan: head size <= 128, 1 .. 16 rows, S + t + 1 <= max_seq_len");
+    for (int j = 0; j < f.n; ++j) if (f.base[j] < 0 || f.base[j] + f.t >= aa.max_seq) return fail(c, FLM_ERR_INVALID, "attn_fan: a tail row outside the cache");
+    const int G = fan_group(aa.max_seq, aa.hs, kLdsMax);
+    if (fan_lds_bytes(G, aa.max_seq, aa.hs) > kLdsMax) return fail(c, FLM_ERR_UNSUPPORTED, "attn_fan: one query's scores do not fit the LDS");
+    hipLaunchKernelGGL(k_attn_fan, dim3(heads, (f.n + G - 1) / G), dim3(kAttnBlock), fan_lds_bytes(G, aa.max_seq, aa.hs), st, aa, f, row_stride, G);
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
+int launch_rope_kv_fan(flm_ctx* c, hipStream_t st, const float* qkv, float* qout, float* kcache, float* vcache, const float* rope_cos, const float* rope_sin, int dim, int hs, int kv_rows, const FanDesc& f) {
+    hipLaunchKernelGGL(k_rope_kv_fan, dim3(f.n), dim3(256), 0, st, qkv, qout, kcache, vcache, rope_cos, rope_sin, dim, hs, kv_rows, f);
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
+
 // all_layers (flm_score_tokens): the last layer runs to its end as well -- pf_x then holds every row's final residual, the classifier's input
+// fan (flm_generate_n; null: every launch is the one made without it): the B rows are the sequences of a fan step (flm_fan.h) -- `pos` is their one LOGICAL position, the
+// QKV GEMM takes the plain-store route with k_rope_kv_fan behind it, the attention is k_attn_fan; everything else is a row's own and stays what it is
 template <int QT>
-int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req = false) {
+int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req = false, const FanDesc* fan = nullptr) {
     const bool skinny = skinny_req && QT == QT_INT8 && B <= kSkinnyTokens && c->world == 1;      // (the verify pass; int16: the tiles)
     const auto& d = c->d;
     const int L = d.n_layers, dim = d.dim, hid = d.hidden_dim, hs = c->hs;
@@ -118,7 +145,11 @@ int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req
         RowsArgs ra{c->pf_x, w.att_norm, c->pf_xq, c->pf_xs, dim, c->pf_xst};
         r = launch_rows<QT, PRO_RMSNORM_QUANT>(c, st, ra, B, tp); if (r) return r;
         GemmArgs g{w.qkv.q, w.qkv.s, c->pf_xq, c->pf_xs, c->pf_qkv, 3 * dimL, dim, 3 * dimL, B, c->pf_xst, w.qkv.st};
-        if ((QT == QT_INT16 || c->use_mfma || skinny) && dimL % 32 == 0 && hs % 2 == 0) {      // (int16: always the matrix-core tiles -- round 5: with the same epilogues as the int8 tiles)
+        if (fan) {
+            r = launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, skinny); if (r) return r;
+            r = launch_rope_kv_fan(c, st, c->pf_qkv, c->pf_q, c->kcache + (size_t)l * kv_layer, c->vcache + (size_t)l * kv_layer, c->rope_cos, c->rope_sin, dimL, hs, c->kv_rows, *fan); if (r) return r;
+        }
+        else if ((QT == QT_INT16 || c->use_mfma || skinny) && dimL % 32 == 0 && hs % 2 == 0) {      // (int16: always the matrix-core tiles -- round 5: with the same epilogues as the int8 tiles)
             // RoPE and the cache rows as the epilogue of the matrix-core tiles: no [tokens][3 dim] round trip, no k_rope_kv_rows
             g.qout = c->pf_q; g.kcache = c->kcache + (size_t)l * kv_layer; g.vcache = c->vcache + (size_t)l * kv_layer;
             g.rope_cos = c->rope_cos; g.rope_sin = c->rope_sin; g.dim = dimL; g.hs = hs; g.max_seq = c->kv_rows /* (the stride between two heads' cache rows) */; g.pos0 = pos;
@@ -138,7 +169,8 @@ int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req
         // one query per workgroup needs 4 bytes per position and always fits (flm_ctx_create checked max_seq_len against it)
         const bool mq_fits = attn_mq_lds_bytes(d.max_seq_len, hs) <= kLdsMax;
         const bool pv_mfma = c->use_pv_mfma && (hs & 1) == 0;
-        if (hs <= 128 && c->use_prefill_mq && c->use_qk_mfma && c->pf_scores && (pv_mfma || mq_fits)) {
+        if (fan) { r = launch_attn_fan(c, st, aa, *fan, c->heads_local, dim); if (r) return r; }
+        else if (hs <= 128 && c->use_prefill_mq && c->use_qk_mfma && c->pf_scores && (pv_mfma || mq_fits)) {
             // scores on the matrix cores (fp32 MFMA = the reference's chains, bit for bit), then softmax + weighted sum per tile of queries
             aa.sc_global = c->pf_scores;
             const dim3 gq(c->heads_local, (B + kQkQ - 1) / kQkQ);
@@ -198,8 +230,9 @@ int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req
 int launch_gemm_store(flm_ctx* c, hipStream_t st, int qt, const GemmArgs& g, int use_mfma) {
     return qt == FLM_QT_INT8 ? launch_gemm<QT_INT8, EPI_STORE>(c, st, g, use_mfma) : launch_gemm<QT_INT16, EPI_STORE>(c, st, g, use_mfma);
 }
-int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers, bool skinny) {
-    return c->d.quant_type == FLM_QT_INT8 ? prefill_batched<QT_INT8>(c, B, pos, all_layers, skinny) : prefill_batched<QT_INT16>(c, B, pos, all_layers, skinny);
+int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers, bool skinny, const FanDesc* fan) {
+    if (fan && (c->world != 1 || fan->n != B || pos != fan->S + fan->t)) return fail(c, FLM_ERR_INVALID, "prefill: a fan step is one GPU's batch of fan.n rows at S + t");
+    return c->d.quant_type == FLM_QT_INT8 ? prefill_batched<QT_INT8>(c, B, pos, all_layers, skinny, fan) : prefill_batched<QT_INT16>(c, B, pos, all_layers, skinny, fan);
 }
 int launch_gemm_skinny_store(flm_ctx* c, hipStream_t st, const GemmArgs& g, int force_nb) { return launch_gemm_skinny<EPI_STORE>(c, st, g, force_nb); }
 
@@ -281,8 +314,9 @@ int launch_logprob_rows(flm_ctx* c, hipStream_t st, const float* rows_dev, int l
     HIPC(c, hipGetLastError());
     return FLM_OK;
 }
+// the classifier on rows [row0, row0 + m) of the batch's final residual: `stage` [m][vocab] receives their logits
 template <int QT>
-static int score_classify_t(flm_ctx* c, int row0, int m, float* stage, bool skinny, int* argmax_out, const SpecDraw* draw = nullptr) {
+static int classify_rows_t(flm_ctx* c, int row0, int m, float* stage, bool skinny) {
     const int dim = c->d.dim, V = c->d.vocab_size;
     hipStream_t st = c->stream;
     if (!c->cls_st_ready) {   // once per set of weights, like the layers' copies (no allocation: cls.st came with the matrix)
@@ -295,7 +329,13 @@ static int score_classify_t(flm_ctx* c, int row0, int m, float* stage, bool skin
     RowsArgs ra{c->pf_x + (size_t)row0 * dim, c->out_norm, c->pf_xq, c->pf_xs, dim, c->pf_xst};
     int r = launch_rows<QT, PRO_RMSNORM_QUANT>(c, st, ra, m); if (r) return r;
     GemmArgs g{c->cls.q, c->cls.s, c->pf_xq, c->pf_xs, stage, V, dim, V, m, c->pf_xst, c->cls.st};
-    r = launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, skinny && m <= kSkinnyTokens); if (r) return r;
+    return launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, skinny && m <= kSkinnyTokens);
+}
+template <int QT>
+static int score_classify_t(flm_ctx* c, int row0, int m, float* stage, bool skinny, int* argmax_out, const SpecDraw* draw = nullptr) {
+    const int V = c->d.vocab_size;
+    hipStream_t st = c->stream;
+    int r = classify_rows_t<QT>(c, row0, m, stage, skinny); if (r) return r;
     if (argmax_out) {
         const bool lp = draw && draw->lp_top_n >= 0;          // the context is armed for log-probabilities: a record per row behind the draws (flm_logprob.h)
         float* rows = stage;                                  // what the draw reads
@@ -323,6 +363,30 @@ static int score_classify_t(flm_ctx* c, int row0, int m, float* stage, bool skin
 }
 int score_classify(flm_ctx* c, int row0, int m, float* stage) {
     return c->d.quant_type == FLM_QT_INT8 ? score_classify_t<QT_INT8>(c, row0, m, stage, false, nullptr) : score_classify_t<QT_INT16>(c, row0, m, stage, false, nullptr);
+}
+// k_sample_fan on `rows` rows of n logits, ld floats apart (0: all from one row), batch rows row0 ..; sort_buf [16][2][n] (c may be null)
+int launch_sample_fan(flm_ctx* c, hipStream_t st, const float* logits, int ld, int n, int row0, int rows, float temperature, float topp, const FanIn& in,
+                      unsigned long long* sort_buf, int* drawn, unsigned long long* after) {
+    {   // the strip of a large vocabulary: the dynamic-LDS limit, once per device
+        static std::mutex mu; static bool done[64] = {false};
+        int dev = 0; HIPC(c, hipGetDevice(&dev));
+        std::lock_guard<std::mutex> lk(mu);
+        if (dev >= 0 && dev < 64 && !done[dev]) {
+            HIPC(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sample_fan), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
+            done[dev] = true;
+        }
+    }
+    if (rows < 1 || row0 < 0 || row0 + rows > kFanMax) return fail(c, FLM_ERR_INVALID, "sample_fan: rows outside a batch of 16");
+    if (temperature != 0.0f && (n < 2 || sample_lds_bytes(n) > kLdsMax || !sort_buf)) return fail(c, FLM_ERR_UNSUPPORTED, "sample_fan: the row does not fit one workgroup's LDS strip");
+    hipLaunchKernelGGL(k_sample_fan, dim3(rows), dim3(kSampleBlock), temperature != 0.0f ? sample_lds_bytes(n) : 2 * kSampleWaves * sizeof(int), st, logits, ld, n, row0, temperature, topp, in, sort_buf, drawn, after);
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
+// a fan step's classifier stage: the chunk through score_classify's prologue and GEMM, then k_sample_fan -- every row with its own state
+int fan_classify(flm_ctx* c, int row0, int m, float* stage, bool skinny, float temperature, float topp, const FanIn& in) {
+    const int V = c->d.vocab_size;
+    int r = c->d.quant_type == FLM_QT_INT8 ? classify_rows_t<QT_INT8>(c, row0, m, stage, skinny) : classify_rows_t<QT_INT16>(c, row0, m, stage, false); if (r) return r;
+    return launch_sample_fan(c, c->stream, stage, V, V, row0, m, temperature, topp, in, c->sort_buf, c->fan_drawn, c->fan_after);
 }
 // the verify pass's classifier stage: the same chunk through the same prologue and GEMM (skinny: k_gemm_q8_skinny, int8), then k_argmax_rows into argmax_out[row0 ..]
 // (draw given and its temperature > 0: k_sample_rows in place of k_argmax_rows)

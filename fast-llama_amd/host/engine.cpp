@@ -197,6 +197,34 @@ bool GpuTransformer::score(const char* prompt) {
     return true;
 }
 
+bool GpuTransformer::generate_samples(const char* prompt, int n, uint64_t seed, int max_new_tokens, float temperature, float topp, std::vector<std::string>& texts) {
+    texts.clear();
+    if (_ctxs.size() != 1) { _err = "--samples: one device only"; return false; }
+    if (n < 1 || n > FLM_FAN_MAX) { _err = "--samples: 1 to 16 samples"; return false; }
+    const std::vector<int> input = encode(prompt);
+    if (input.empty()) { fprintf(stderr, "Empty input for generate()\n"); return false; }
+    printf("Input prompt:%s\n", prompt);
+    print_vector("Input tokens:", input);
+    const int n_in = (int)input.size();
+    if (n_in >= _cfg.max_seq_len) { fprintf(stderr, "Input is too long for generate()\n"); return false; }
+    if (max_new_tokens < 0) max_new_tokens = 0;
+    if (max_new_tokens > (_cfg.max_seq_len - n_in) / n) max_new_tokens = (_cfg.max_seq_len - n_in) / n;      // (the n tails share what the prompt leaves: flm_fan_layout_for)
+    const int want = max_new_tokens + 1;
+    std::vector<int32_t> ids((size_t)n * want);
+    std::vector<int> n_out(n, 0);
+    std::vector<uint64_t> st(n);
+    for (int j = 0; j < n; ++j) st[j] = seed + (uint64_t)j;
+    const int rc = n == 1 ? flm_generate(_ctxs[0], input.data(), n_in, 0, want, temperature, topp, st.data(), 0, nullptr, nullptr, ids.data(), n_out.data())
+                          : flm_generate_n(_ctxs[0], input.data(), n_in, 0, want, n, temperature, topp, st.data(), 0, nullptr, nullptr, ids.data(), n_out.data());
+    if (rc != FLM_OK) { _err = std::string("--samples: ") + flm_last_error(_ctxs[0]); return false; }
+    texts.resize(n);
+    for (int j = 0; j < n; ++j) {
+        int prev = -1;
+        for (int i = 0; i < n_out[j]; ++i) { const int tok = ids[(size_t)j * want + i]; texts[j] += _tok.decode(tok, prev); prev = tok; }
+    }
+    return true;
+}
+
 bool GpuTransformer::generate(const char* prompt, const std::function<bool(const char*, int, int, bool)>& cb,
                               int max_new_tokens, float temperature, float topp) {
     const std::vector<int> input = encode(prompt);

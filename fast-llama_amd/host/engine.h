@@ -30,6 +30,10 @@ public:
     std::string decode(const std::vector<int>& tokens) const { return _tok.decode(tokens); }
     // generate(prompt, cb(text, n_input, n_output, ended), max_new_tokens, temperature, topp): transformer.cpp:54-103
     bool generate(const char* prompt, const std::function<bool(const char*, int, int, bool)>& cb, int max_new_tokens, float temperature, float topp);
+    // --samples N (this build only; one device, none of the other extras): N completions of the prompt, all N drawn per pass over the weights (flm_generate_n; N == 1:
+    // flm_generate).  Sample j's sampler state is seed + j -- here --seed counts, where the plain run keeps the reference's state 0 --, every sample stops on token 0 by
+    // itself and max_new_tokens is cut to what the N tails leave room for.  texts[j]: sample j's pieces as generate() would have streamed them
+    bool generate_samples(const char* prompt, int n, uint64_t seed, int max_new_tokens, float temperature, float topp, std::vector<std::string>& texts);
     // --mode score (this build only): the prompt's tokens through flm_score_tokens in one call; one line per position (index, token id, argmax id, the probability of the
     // next token), then a summary line (token count, mean natural-log loss, perplexity, ms)
     bool score(const char* prompt);

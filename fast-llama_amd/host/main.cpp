@@ -5,7 +5,8 @@
 // the next token, then token count, mean loss, perplexity and ms; --device <hip ordinal>; --devices a,b,... = the reference's parallel width (-j, main.cpp:30,78) on GPUs: one
 // sequence sharded over the named devices (split_rows, transformer.cpp:264-287), one host thread per device; --stop-ids / --stop-seq / --stop = stop rules next to the loop's
 // stop on token 0 (flm_stop_rules; one device), with a `finish_reason:` line behind the output (also printed by --mode test); --draft-model FILE = a second, small model of
-// the same vocabulary drafts for the loop (flm_generate_draft; one device): the same text, several tokens per pass over the weights where the two models agree.
+// the same vocabulary drafts for the loop (flm_generate_draft; one device): the same text, several tokens per pass over the weights where the two models agree;
+// --samples N = N completions of the prompt, all N drawn per pass over the weights (flm_generate_n; one device), sample j with the sampler state --seed + j.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -36,6 +37,7 @@ struct Args {
     bool use_numa = false, detail = false, debug = false;
     std::vector<int> devices;
     const char* bad_devices = nullptr;      // a --devices argument that did not parse
+    int samples = 0; const char* bad_samples = nullptr;      // --samples N: 1..16 completions of the prompt (0 = off)
     int lookup_k = 0, lookup_g = 3;         // --lookup K[,G]: draft length (4..15; 0 = off) and longest n-gram (1..8) of the prompt-lookup drafter
     const char* bad_lookup = nullptr;
     int draft_k = 0, draft_g = 3;           // --draft K[,G]: the same drafter and ranges at whatever temperature the run has (-t 0: flm_generate_lookup, else flm_generate_lookup_sample)
@@ -73,6 +75,7 @@ void usage(const char* bin) {
     fprintf(stderr, "   --lookup          <K[,G]>     with -t 0 on one device: draft K (4..15) tokens per step by prompt lookup (n-grams up to G, 1..8, default 3) and verify them in one pass; the same text (this build only)\n");
     fprintf(stderr, "   --draft           <K[,G]>     on one device, at any temperature: draft K (4..15) tokens per step by prompt lookup (n-grams up to G, 1..8, default 3) and verify them in one pass, sampled rows drawn with the sampler's own coins; the same text (this build only)\n");
     fprintf(stderr, "   --draft-model     <file>      on one device, at any temperature: a second, small model of the same vocabulary (quantisation: the file's own or -q) drafts the K tokens of --draft (default 7) instead of the prompt lookup; the same text (this build only)\n");
+    fprintf(stderr, "   --samples         <N>         on one device: N (1..16) completions of the prompt, all N drawn per pass over the weights, printed one after another, each behind a line `--- sample j ---`; sample j's sampler state is --seed + j (here --seed counts); not with the other extras of this build (this build only)\n");
     fprintf(stderr, "   --top-k           <integer>   keep the K most likely tokens, 0 = off (this build only)\n");
     fprintf(stderr, "   --min-p           <float>     drop tokens whose probability is below this fraction of the most likely one's, [0, 1), 0 = off (this build only)\n");
     fprintf(stderr, "   --repeat-penalty  <float>     penalise the tokens of the last --repeat-last-n ids, > 0, 1 = off (this build only)\n");
@@ -181,6 +184,7 @@ const Flag kFlags[] = {
         if (ok && *e == ',') { const char* s = e + 1; g = strtol(s, &e, 10); ok = e != s && g >= 1 && g <= 8; }
         if (ok && *e == 0) { a.lookup_k = (int)k; a.lookup_g = (int)g; } else a.bad_lookup = v; }},
     {nullptr, "--draft",       true,  [](Args& a, const char* v) { if (!parse_draft(v, a.draft_k, a.draft_g)) a.bad_draft = v; }},                 // (this build only)
+    {nullptr, "--samples",     true,  [](Args& a, const char* v) { char* e; const long k = strtol(v, &e, 10); if (e == v || *e || k < 1 || k > FLM_FAN_MAX) a.bad_samples = v; else a.samples = (int)k; }},   // (this build only)
     {nullptr, "--draft-model", true,  [](Args& a, const char* v) { a.draft_model = v; }},                                                                                          // (this build only)
     {nullptr, "--top-k",             true, [](Args& a, const char* v) { char* e; const long k = strtol(v, &e, 10); a.shape_set = true; if (e == v || *e || k < 0 || k > 0x7fffffff) a.bad_sampling = v; else a.shape.top_k = (int)k; }},   // (this build only)
     {nullptr, "--min-p",             true, [](Args& a, const char* v) { a.shape_set = true; if (!parse_float(v, a.shape.min_p) || !(a.shape.min_p >= 0.f && a.shape.min_p < 1.f)) a.bad_sampling = v; }},                              // (this build only)
@@ -217,6 +221,7 @@ void parse(Args& a, int argc, const char** argv) {
         if (a.bad_devices) { fprintf(stderr, "Invalid --devices list:\x1b[31m%s\x1b[0m (expected 1 to 8 HIP device ordinals, e.g. 0,1,2,3)\n", a.bad_devices); usage(argv[0]); exit(-1); }
     }
     if (a.bad_lookup) { fprintf(stderr, "Invalid --lookup:\x1b[31m%s\x1b[0m (expected K or K,G with 4 <= K <= 15 and 1 <= G <= 8)\n", a.bad_lookup); usage(argv[0]); exit(-1); }
+    if (a.bad_samples) { fprintf(stderr, "Invalid --samples:\x1b[31m%s\x1b[0m (expected a number of completions, 1 to 16)\n", a.bad_samples); usage(argv[0]); exit(-1); }
     if (a.bad_draft) { fprintf(stderr, "Invalid --draft:\x1b[31m%s\x1b[0m (expected K or K,G with 4 <= K <= 15 and 1 <= G <= 8)\n", a.bad_draft); usage(argv[0]); exit(-1); }
     if (!a.bad_sampling && a.mirostat == 2 && a.typical > 0.0f && a.typical < 1.0f) a.bad_sampling = "--typical together with --mirostat 2";
     if (a.bad_sampling) { fprintf(stderr, "Invalid sampling control:\x1b[31m%s\x1b[0m (--top-k >= 0, --min-p in [0, 1), --repeat-penalty > 0, --repeat-last-n 0..1024, --logit-bias id=val[,id=val...] with at most 256 pairs, --typical a number, --mirostat 0 or 2 with finite --mirostat-ent / --mirostat-lr, never --typical in (0, 1) together with --mirostat 2)\n", a.bad_sampling); usage(argv[0]); exit(-1); }
@@ -303,6 +308,11 @@ int main(int argc, const char** argv) {
         return -1;
     }
     const bool stop_set = !args.stop_ids.empty() || !args.stop_seqs.empty() || !args.stop_strs.empty();
+    if (args.samples && (args.devices.size() > 1 || args.lookup_k || args.draft_k || !args.draft_model.empty() || args.shape_set || args.ent_set || args.logprobs_n >= 0 || stop_set ||
+                         args.constraint || args.mode != Mode::GEN)) {      // (refused, not ignored: flm_generate_n is the plain loop's contract, n times)
+        fprintf(stderr, "--samples applies to --mode gen on one device, without --lookup / --draft / --draft-model, the sampling controls, --typical / --mirostat, --logprobs, the stop rules and --constraint\n");
+        return -1;
+    }
     if (stop_set && args.devices.size() > 1) {                  // (refused, not ignored: where the output ends is what the caller asked for)
         fprintf(stderr, "--stop-ids / --stop-seq / --stop apply to one device only: they cannot be combined with --devices of more than one\n");
         return -1;
@@ -331,6 +341,14 @@ int main(int argc, const char** argv) {
 
     if (args.mode == Mode::SCORE) {      // (its own lines: the reference has no such mode, and the summary line below stays the reference's)
         if (!tf.score(args.prompt)) { fprintf(stderr, "%s\n", tf.error().c_str()); return 1; }
+        return 0;
+    }
+
+    if (args.samples) {      // (its own lines: the completions one after another; no summary line -- tools/fan_bench.py times this path)
+        std::vector<std::string> texts;
+        if (!tf.generate_samples(args.prompt, args.samples, (uint64_t)(int64_t)args.seed, args.max_tokens, args.temp, args.topp, texts)) { fprintf(stderr, "%s\n", tf.error().c_str()); return 1; }
+        printf("prompt: %s%s%s\n", Y, args.prompt, E);
+        for (size_t j = 0; j < texts.size(); ++j) printf("--- sample %zu ---\n%s\n", j, texts[j].c_str());
         return 0;
     }
 

@@ -334,6 +334,43 @@ int  flm_generate_draft(flm_ctx* ctx, const int32_t* prompt, int n_prompt, int p
                         int32_t stop_token /* -1: none */, int draft_len /* 4..15 */,
                         flm_token_cb cb /* may be NULL */, void* user,
                         int32_t* out_tokens /* [max_tokens], may be NULL */, int* n_out);
+/* Parallel sampling: n completions of ONE prompt, all n drawn per pass over the weights -- what the API parameter n / best_of, self-consistency voting and reranking ask
+ * for, without n sequential flm_generate calls.  One context, one cache, one shared prompt; no reference counterpart (the reference generates one sequence).
+ * Contract, for every j < n: out_tokens[j * max_tokens + 0 .. n_out[j]), n_out[j] and rng_states[j] afterwards are exactly what
+ *     flm_generate(ctx, prompt, n_prompt, pos, max_tokens, temperature, topp, &rng_states[j], stop_token, ...)
+ * delivers on a context whose cache holds the same pos rows: the ids element for element, the states as 64-bit integers.  The stop token is delivered, counted and not fed;
+ * a finished sequence's state stays at the state after its last delivered draw; the others go on.  temperature == 0 is allowed: every row is the greedy run, rng_states may be
+ * NULL and no state is touched.  Like plain flm_generate the call IGNORES installed stop rules, the constraint, armed log-probabilities and flm_entropy_set.
+ *   layout    S = pos + n_prompt cache rows are shared by all sequences.  Sequence j's fed tokens (at most max_tokens - 1 of them) live in the physical rows base[j] + i,
+ *             base[j] = S + j * (max_tokens - 1); token i of a tail is at LOGICAL position S + i -- for RoPE and for the attention's order -- whatever its physical row.  The
+ *             call needs S + n * (max_tokens - 1) <= max_seq_len and no cache memory of its own.  flm_fan_layout_for computes and checks this without a device (pure host
+ *             arithmetic, like flm_plan_shards); the entry point uses the same function.
+ *   a step    the prompt enters as in flm_generate (flm_forward's rows); token 0 of every sequence is drawn from the one row of logits it leaves, each with its own first
+ *             coin.  Then one step per token: the n last ids run as ONE batch of n rows through the batched kernels (the verify pass's: every row's logits are flm_forward's
+ *             bits), the attention of row j over the shared rows followed by tail j in the logical order (k_attn_fan, csrc/flm_fan.h: a workgroup brings a shared K / V tile to
+ *             LDS once for up to 8 rows), row j drawn by the unchanged sampler with state j.  ONE host synchronisation per step (the result block: ids, live mask, states);
+ *             finished sequences stay in the batch, their outputs dropped.  A step's inputs are launch arguments from what the host holds, so a step that retries behind a
+ *             timed-out cross-workgroup wait (the prompt's token launches can have one) enqueues the same work.
+ *   cb        the flm_fan_cb receives (user, seq, index, token, last): called on the calling thread, per step in sequence order; `last` on a sequence's final token.  A non-zero return
+ *             cancels the WHOLE call: the callback is not called again, the ids of the step in flight are still counted (n_out covers what was delivered).
+ *   after     rows [0, S) are untouched: the prompt's rows bit-equal what flm_forward leaves; rows behind S are unspecified.  flm_fan_keep(ctx, j), valid until the next call
+ *             that writes the cache (and once), moves tail j to rows [S, S + n_out[j] - 1) with one copy kernel over all layers and heads (source and destination cannot
+ *             overlap for j > 0; j = 0 is in place): the cache is then bit for bit what sequence j's own flm_generate would have left, and any entry point continues from
+ *             pos + n_prompt + n_out[j] - 1.
+ * Errors, with nothing launched and the cache untouched: FLM_ERR_INVALID for n outside 2 .. FLM_FAN_MAX, S + n * (max_tokens - 1) > max_seq_len, max_tokens < 1, a NULL prompt /
+ * out_tokens / n_out, a NULL rng_states at temperature != 0, ids outside [0, vocab), stop_token >= vocab; for flm_fan_keep without a preceding flm_generate_n or with seq outside
+ * [0, n).  FLM_ERR_UNSUPPORTED for world > 1, for temperature > 0 where flm_decode_sample refuses (the vocabulary bound), and for head sizes above 128 (the multi-query attention's
+ * bound).  flm_query "stop_reason" describes the WHOLE call: cancel; else length where any sequence ran to max_tokens; else the stop token ("stop_rule" 0).
+ * Nothing is allocated in the call: the drawn ids, the states and the result block (a few hundred bytes) exist since flm_ctx_create. */
+#define FLM_FAN_MAX 16
+typedef struct flm_fan_layout { int32_t shared_rows, tail_rows, n; int32_t base[FLM_FAN_MAX]; } flm_fan_layout;
+int  flm_fan_layout_for(int pos, int n_prompt, int max_tokens, int n, int max_seq_len, flm_fan_layout* out);
+typedef int (*flm_fan_cb)(void* user, int seq, int index, int32_t token, int last);   /* non-zero return: cancel the whole call */
+int  flm_generate_n(flm_ctx* ctx, const int32_t* prompt, int n_prompt, int pos, int max_tokens, int n,
+                    float temperature, float topp, uint64_t* rng_states /* [n]; NULL allowed iff temperature == 0 */,
+                    int32_t stop_token /* -1: none */, flm_fan_cb cb /* may be NULL */, void* user,
+                    int32_t* out_tokens /* [n][max_tokens] */, int* n_out /* [n] */);
+int  flm_fan_keep(flm_ctx* ctx, int seq);
 /* Constrained decoding: a token-level deterministic automaton masks the logits in front of the controls -- what "one of these strings", a JSON shape or a regular expression
  * reduce to.  No reference counterpart.  The automaton is CSR: the edges of state q are [row_ptr[q], row_ptr[q + 1]).
  *   delta(q, t)  the edge_next of t's edge in state q, or q ITSELF when t has no edge there.  The no-edge case is reachable only through the multinomial branch's last-index
@@ -650,6 +687,11 @@ int  flm_op_softmax(float* x, int n);
  * out [n_heads*hs]. */
 int  flm_op_attention(float* out, float* kc, float* vc, const float* q, const float* k, const float* v,
                       int n_heads, int hs, int max_seq, int pos);
+/* the same task for the n rows of one flm_generate_n step (k_rope_kv_fan + k_attn_fan, csrc/flm_fan.h): q, k, v are [n][n_heads*hs], all at logical position S + t; row j's
+ * k / v go to cache row base[j] + t and its query attends rows 0 .. S - 1 followed by base[j] .. base[j] + t.  kc, vc as above (updated); out [n][n_heads*hs].
+ * 2 <= n <= FLM_FAN_MAX, hs <= 128, S >= 1, S + t + 1 <= max_seq and every base[j] + t < max_seq (FLM_ERR_INVALID otherwise). */
+int  flm_op_attention_fan(float* out, float* kc, float* vc, const float* q, const float* k, const float* v,
+                          int n_heads, int hs, int max_seq, int n, int S, int t, const int32_t* base);
 /* libm expf as the device evaluates it (the reference calls glibc expf in softmax_sisd and swiglu);
  * in place over n floats.  Lets the tests pin the device routine against glibc bit for bit. */
 int  flm_op_expf(float* x, size_t n);
