@@ -36,6 +36,7 @@ SYMBOLS = (
     "flm_draft_set", "flm_generate_draft",
     "flm_entropy_validate", "flm_entropy_set", "flm_entropy_mu", "flm_op_logf", "flm_op_entropy_rows",
     "flm_fan_layout_for", "flm_generate_n", "flm_fan_keep", "flm_op_attention_fan",
+    "flm_batch_layout_for", "flm_batch_open", "flm_batch_join", "flm_batch_step", "flm_batch_state", "flm_batch_close", "flm_generate_batch", "flm_op_attention_slots",
 )
 
 # flm_score (include/flm_gpu.h): one row of flm_score_tokens / flm_op_score_rows
@@ -55,6 +56,47 @@ FAN_MAX = 16                                       # FLM_FAN_MAX
 class FanLayout(C.Structure):
     """flm_fan_layout (include/flm_gpu.h)"""
     _fields_ = [("shared_rows", C.c_int32), ("tail_rows", C.c_int32), ("n", C.c_int32), ("base", C.c_int32 * FAN_MAX)]
+
+
+BATCH_MAX = 16                                     # FLM_BATCH_MAX
+
+
+class BatchLayout(C.Structure):
+    """flm_batch_layout (include/flm_gpu.h)"""
+    _fields_ = [("n_slots", C.c_int32), ("base", C.c_int32 * BATCH_MAX), ("rows", C.c_int32 * BATCH_MAX)]
+
+
+class BatchReqStruct(C.Structure):
+    """flm_batch_req (include/flm_gpu.h)"""
+    _fields_ = [("prompt", C.c_void_p), ("n_prompt", C.c_int32), ("max_tokens", C.c_int32), ("temperature", C.c_float), ("topp", C.c_float),
+                ("rng_state", C.c_uint64), ("stop_token", C.c_int32)]
+
+
+class BatchOutStruct(C.Structure):
+    """flm_batch_out (include/flm_gpu.h)"""
+    _fields_ = [("ids", C.c_int32 * BATCH_MAX), ("live", C.c_uint32), ("finished", C.c_uint32)]
+
+
+@dataclasses.dataclass
+class BatchReq:
+    """one request of batch_join / generate_batch: what flm_generate takes for one sequence on a fresh context"""
+    prompt: object
+    max_tokens: int
+    temperature: float = 0.0
+    topp: float = 0.9
+    rng_state: int = 0
+    stop_token: int = -1
+
+    def struct(self):
+        """-> (flm_batch_req, the array it points into: keep it alive for the call)"""
+        t = np.ascontiguousarray(self.prompt, dtype=np.int32).reshape(-1)
+        if int(self.max_tokens) < 1:
+            raise ValueError("batch request: max_tokens < 1")
+        if t.size < 1:
+            raise ValueError("batch request: an empty prompt")
+        if not 0 <= int(self.rng_state) < 1 << 64:
+            raise ValueError("batch request: rng_state outside 64 bits")
+        return BatchReqStruct(_p(t), int(t.size), int(self.max_tokens), float(self.temperature), float(self.topp), int(self.rng_state), int(self.stop_token)), t
 
 
 # flm_token_cb: int (*)(void* user, int index, int32_t token, int last); a non-zero return cancels
@@ -652,6 +694,62 @@ class Ctx:
         """flm_fan_keep: move sequence `seq`'s tail of the last generate_n behind the shared rows; any entry point continues from pos + n_prompt + n_out[seq] - 1"""
         _check(lib().flm_fan_keep(self._h, int(seq)), self._h)
 
+    def batch_open(self, layout):
+        """flm_batch_open: divide the cache into the layout's slots (batch_layout) and empty them all; launches nothing"""
+        _check(lib().flm_batch_open(self._h, C.byref(layout)), self._h)
+
+    def batch_join(self, slot, req):
+        """flm_batch_join: the request's prompt enters the empty slot `slot` -> (token 0, whether the slot is live behind it)"""
+        st, keep = req.struct()
+        first = C.c_int32(-1); live = C.c_int(0)
+        _check(lib().flm_batch_join(self._h, int(slot), C.byref(st), C.byref(first), C.byref(live)), self._h)
+        del keep
+        return int(first.value), bool(live.value)
+
+    def batch_step(self):
+        """flm_batch_step: one pass over the weights for all live slots -> (ids[BATCH_MAX] by slot, -1 where a slot delivered nothing; the live mask behind the step; the
+        mask of the slots whose last id is in it)"""
+        out = BatchOutStruct()
+        _check(lib().flm_batch_step(self._h, C.byref(out)), self._h)
+        return np.array(out.ids[:], dtype=np.int32), int(out.live), int(out.finished)
+
+    def batch_state(self, slot):
+        """flm_batch_state -> (the sampler state behind the slot's delivered ids, their count, FLM_STOP_TOKEN (1) / FLM_STOP_LENGTH (0); 0 while the slot runs)"""
+        st = C.c_uint64(0); n = C.c_int(0); why = C.c_int(0)
+        _check(lib().flm_batch_state(self._h, int(slot), C.byref(st), C.byref(n), C.byref(why)), self._h)
+        return int(st.value), int(n.value), int(why.value)
+
+    def batch_close(self, keep_slot=-1):
+        """flm_batch_close: end the batch; keep_slot >= 0: that slot's rows move to [0, len) and any entry point continues its conversation from pos = len"""
+        _check(lib().flm_batch_close(self._h, int(keep_slot)), self._h)
+
+    def generate_batch(self, reqs, on_token=None):
+        """flm_generate_batch: the requests (BatchReq, 1 .. BATCH_MAX of them) served together, one batch per pass over the weights -> (a list of id arrays, the sampler
+        states after each request's draws).  on_token(seq, index, token, last) is called per delivered id; a truthy return ends the call behind that step."""
+        reqs = list(reqs)
+        n = len(reqs)
+        if not 1 <= n <= BATCH_MAX:
+            raise ValueError(f"generate_batch: {n} requests outside 1 .. {BATCH_MAX}")
+        pairs = [r.struct() for r in reqs]
+        arr = (BatchReqStruct * n)(*[p[0] for p in pairs])
+        stride = max(int(r.max_tokens) for r in reqs)
+        out = np.full((n, stride), -1, dtype=np.int32); n_out = np.zeros(n, dtype=np.int32); st = np.zeros(n, dtype=np.uint64)
+        raised = []
+
+        def tramp(_user, seq, index, token, last):
+            try:
+                return 1 if on_token(int(seq), int(index), int(token), bool(last)) else 0
+            except BaseException as e:      # (an exception must not unwind through the C frames: cancel, re-raise behind the call)
+                raised.append(e)
+                return 1
+        cb = FAN_CB(tramp) if on_token is not None else C.cast(None, FAN_CB)
+        rc = lib().flm_generate_batch(self._h, arr, n, cb, None, _p(out), stride, _p(n_out), _p(st))
+        del cb, pairs
+        if raised:
+            raise raised[0]
+        _check(rc, self._h)
+        return [out[j, :n_out[j]].copy() for j in range(n)], [int(x) for x in st]
+
     def draft_set(self, draft):
         """flm_draft_set: pair this (target) context with the draft context `draft` for generate_draft (None: detach).  The target does not own the draft: detach before
         closing either"""
@@ -1082,6 +1180,28 @@ def fan_layout(pos, n_prompt, max_tokens, n, max_seq_len) -> FanLayout:
     """flm_fan_layout_for (pure host arithmetic): the rows flm_generate_n uses, or FlmError where the call would refuse"""
     out = FanLayout()
     _check(lib().flm_fan_layout_for(int(pos), int(n_prompt), int(max_tokens), int(n), int(max_seq_len), C.byref(out)))
+    return out
+
+
+def batch_layout(rows, max_seq_len) -> BatchLayout:
+    """flm_batch_layout_for (pure host arithmetic): slot s owns the cache rows [base[s], base[s] + rows[s]), or FlmError where the layout is refused"""
+    r = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
+    out = BatchLayout()
+    _check(lib().flm_batch_layout_for(int(r.size), _p(r), int(max_seq_len), C.byref(out)))
+    return out
+
+
+def op_attention_slots(kc, vc, q, k, v, n_heads, hs, max_seq, base, pos):
+    """one flm_batch_step's attention: q, k, v [n, n_heads*hs]; row r at logical position pos[r] of the slot that starts at cache row base[r]: its k / v go to cache row
+    base[r] + pos[r].  kc, vc [n_heads, max_seq, hs] are updated in place; returns out [n, n_heads*hs]."""
+    for a in (kc, vc):
+        assert a.dtype == np.float32 and a.flags.c_contiguous
+    b = np.ascontiguousarray(base, dtype=np.int32); ps = np.ascontiguousarray(pos, dtype=np.int32); n = len(b)
+    assert len(ps) == n
+    q = np.ascontiguousarray(q, dtype=np.float32); k = np.ascontiguousarray(k, dtype=np.float32); v = np.ascontiguousarray(v, dtype=np.float32)
+    assert q.shape == k.shape == v.shape == (n, n_heads * hs)
+    out = np.empty((n, n_heads * hs), dtype=np.float32)
+    _check(lib().flm_op_attention_slots(_p(out), _p(kc), _p(vc), _p(q), _p(k), _p(v), n_heads, hs, max_seq, n, _p(b), _p(ps)))
     return out
 
 

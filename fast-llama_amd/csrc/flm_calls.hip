@@ -150,6 +150,7 @@ int check_ready(flm_ctx* c, int n, int pos) {
     if (!c) return FLM_ERR_INVALID;
     c->err_word_fresh = false;                                                  // (an error word a previous call's read-back brought along says nothing about this call)
     c->fan_valid = false;                                                       // (every entry point that writes the cache comes through here: flm_fan_keep's tails are gone)
+    c->batch_open = false;                                                      // (... and so are an open batch's slots: flm_batch_join / _step / _close(keep) answer FLM_ERR_STATE)
     if (!model_complete(c)) return fail(c, FLM_ERR_STATE, "forward before all tensors were uploaded");
     if (n < 1 || pos < 0 || pos + n > c->d.max_seq_len) return fail(c, FLM_ERR_INVALID, "tokens/pos outside [0, max_seq_len]");
     HIPC(c, hipSetDevice(c->device));
@@ -977,6 +978,200 @@ int flm_fan_keep(flm_ctx* c, int seq) {
         HIPC(c, hipStreamSynchronize(c->stream));
     }
     return FLM_OK;
+}
+
+// Cache slots (include/flm_gpu.h; kernels: flm_batch.h; the batch pass: flm_prompt.hip prefill_batched with a row origin / a SlotDesc).  The layout is pure host arithmetic
+// and the one place the capacity condition is written
+int flm_batch_layout_for(int n_slots, const int32_t* rows, int max_seq_len, flm_batch_layout* out) {
+    if (!out || !rows) return FLM_ERR_INVALID;
+    const char* why = nullptr;
+    long long sum = 0;
+    if (n_slots < 1 || n_slots > FLM_BATCH_MAX) why = "batch: n_slots outside 1 .. FLM_BATCH_MAX";
+    else {
+        for (int s = 0; s < n_slots && !why; ++s) { if (rows[s] < 1) why = "batch: a slot of fewer than 1 row"; sum += rows[s]; }
+        if (!why && sum > max_seq_len) why = "batch: the slots' rows exceed max_seq_len";
+    }
+    if (why) { g_last_error = why; return FLM_ERR_INVALID; }
+    flm_batch_layout l{};
+    l.n_slots = n_slots;
+    for (int s = 0, b = 0; s < n_slots; ++s) { l.base[s] = b; l.rows[s] = rows[s]; b += rows[s]; }
+    *out = l;
+    return FLM_OK;
+}
+// what every batch entry point behind open starts with: check_ready's work WITHOUT ending the batch
+static int batch_ready(flm_ctx* c, const char* who) {
+    if (!c) return FLM_ERR_INVALID;
+    if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "batch: one GPU only");
+    if (!c->batch_open) { c->err = std::string(who) + ": no open batch (flm_batch_open), or the cache was written since"; g_last_error = c->err; return FLM_ERR_STATE; }
+    c->err_word_fresh = false;
+    HIPC(c, hipSetDevice(c->device));
+    return FLM_OK;
+}
+int flm_batch_open(flm_ctx* c, const flm_batch_layout* layout) {
+    if (!c || !layout) return FLM_ERR_INVALID;
+    if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "batch: one GPU only");
+    if (!model_complete(c)) return fail(c, FLM_ERR_STATE, "batch_open before all tensors were uploaded");
+    if (attn_lds_bytes(c->d.max_seq_len, c->hs) > kLdsMax) return fail(c, FLM_ERR_UNSUPPORTED, "batch: the one-query attention's LDS does not fit at this head size and max_seq_len");
+    flm_batch_layout lay{};
+    if (layout->n_slots < 1 || layout->n_slots > FLM_BATCH_MAX) return fail(c, FLM_ERR_INVALID, "batch: n_slots outside 1 .. FLM_BATCH_MAX");
+    if (flm_batch_layout_for(layout->n_slots, layout->rows, c->d.max_seq_len, &lay)) { c->err = g_last_error; return FLM_ERR_INVALID; }
+    for (int s = 0; s < lay.n_slots; ++s) if (layout->base[s] != lay.base[s]) return fail(c, FLM_ERR_INVALID, "batch: the layout is not flm_batch_layout_for's (base is the prefix sum of rows)");
+    c->fan_valid = false;
+    c->batch_lay = lay;
+    for (auto& s : c->batch_slot) s = flm_ctx::BatchSlot{};
+    c->batch_open = true;
+    return FLM_OK;
+}
+// the result block's trip back behind the accept step (the error word rides along: xwg_check looks at it next)
+static int batch_accept(flm_ctx* c, const SlotIn& in, const SlotDesc& f, SlotOut* so) {
+    hipLaunchKernelGGL(k_batch_accept, dim3(1), dim3(64), 0, c->stream, c->batch_res, (const int*)c->fan_drawn, (const unsigned long long*)c->fan_after, in, f);
+    HIPC(c, hipGetLastError());
+    return d2h(c, so, c->batch_res, sizeof *so);
+}
+// a verified draw of slot s: the host's copy of the slot moves behind it
+static void batch_take(flm_ctx* c, int s, const SlotOut& so) {
+    flm_ctx::BatchSlot& b = c->batch_slot[s];
+    b.last = so.ids[s]; b.rng = so.rng[s]; b.n_out += 1;
+    if (b.temp != 0.0f) c->sampled += 1;
+    if ((so.finished >> s) & 1u) { b.live = false; b.reason = (b.stop >= 0 && b.last == b.stop) ? FLM_STOP_TOKEN : FLM_STOP_LENGTH; }
+}
+int flm_batch_join(flm_ctx* c, int slot, const flm_batch_req* q, int32_t* first_token, int* live) {
+    if (!c || !q || !first_token || !live) return FLM_ERR_INVALID;
+    int r = batch_ready(c, "batch_join"); if (r) return r;
+    const flm_batch_layout& lay = c->batch_lay;
+    if (slot < 0 || slot >= lay.n_slots) return fail(c, FLM_ERR_INVALID, "batch_join: slot outside the layout");
+    flm_ctx::BatchSlot& b = c->batch_slot[slot];
+    if (b.live) return fail(c, FLM_ERR_INVALID, "batch_join: the slot's sequence is still running");
+    if (!q->prompt || q->n_prompt < 1 || q->max_tokens < 1 || (long long)q->n_prompt + q->max_tokens - 1 > lay.rows[slot] || q->n_prompt > c->pf_cap || q->n_prompt > c->prompt_cap)
+        return fail(c, FLM_ERR_INVALID, "batch_join: n_prompt >= 1, max_tokens >= 1, n_prompt + max_tokens - 1 <= the slot's rows");
+    if (!(q->temperature >= 0.0f) || q->topp != q->topp || q->stop_token >= c->d.vocab_size)
+        return fail(c, FLM_ERR_INVALID, "batch_join: temperature >= 0, top-p a number, stop_token < vocab_size (or -1)");
+    if (!ids_in_vocab(c, q->prompt, q->n_prompt)) return fail(c, FLM_ERR_INVALID, "token id out of range");
+    if (q->temperature != 0.0f && !sample_supported(c)) return fail(c, FLM_ERR_UNSUPPORTED, "device sampler: vocabulary too large for one workgroup's LDS (sample on the host)");
+    const int n = q->n_prompt, stop = q->stop_token < 0 ? -1 : q->stop_token;
+    // the draw's one row: row 0 of a SlotIn / SlotDesc of its own
+    SlotIn in{}; in.rng[0] = (unsigned long long)q->rng_state; in.temp[0] = q->temperature; in.topp[0] = q->topp; in.stop[0] = stop; in.left[0] = q->max_tokens;
+    for (int s = 0; s < lay.n_slots; ++s) if (c->batch_slot[s].live) in.live |= 1u << s;
+    in.live |= 1u << slot;
+    SlotDesc f{}; f.n = 1; f.slot[0] = slot; f.base[0] = lay.base[slot]; f.pos[0] = n - 1; f.rows[0] = lay.rows[slot];
+    const bool skinny = c->spec_gemm != 0 && n <= kSkinnyTokens;
+    int chunk = 1; float* const stage = score_stage(c, &chunk);
+    SlotOut so{};
+    return with_retry(c, n, [&]() -> int {
+        int r = h2d(c, c->prompt_dev, q->prompt, sizeof(int) * (size_t)n); if (r) return r;
+        r = prefill_batched_qt(c, n, 0, true, skinny, nullptr, lay.base[slot], nullptr); if (r) return r;
+        r = batch_classify(c, n - 1, 0, 1, stage, skinny, in); if (r) return r;          // (only the prompt's last row goes through the classifier and the draw)
+        return batch_accept(c, in, f, &so);
+    }, [&] {
+        b = flm_ctx::BatchSlot{};
+        b.used = true; b.live = true; b.pos = n; b.max_tokens = q->max_tokens; b.stop = stop; b.temp = q->temperature; b.topp = q->topp;
+        batch_take(c, slot, so);
+        *first_token = b.last; *live = b.live ? 1 : 0;
+    });
+}
+int flm_batch_step(flm_ctx* c, flm_batch_out* out) {
+    if (!c || !out) return FLM_ERR_INVALID;
+    int r = batch_ready(c, "batch_step"); if (r) return r;
+    const flm_batch_layout& lay = c->batch_lay;
+    SlotIn in{}; SlotDesc f{};
+    for (int s = 0; s < lay.n_slots; ++s) {
+        const flm_ctx::BatchSlot& b = c->batch_slot[s];
+        if (!b.live) continue;
+        const int i = f.n++;
+        f.slot[i] = s; f.base[i] = lay.base[s]; f.pos[i] = b.pos; f.rows[i] = lay.rows[s];
+        in.ids[i] = b.last; in.rng[i] = b.rng; in.temp[i] = b.temp; in.topp[i] = b.topp; in.stop[i] = b.stop; in.left[i] = b.max_tokens - b.n_out;
+        in.live |= 1u << s;
+    }
+    for (int s = 0; s < FLM_BATCH_MAX; ++s) out->ids[s] = -1;
+    out->live = 0; out->finished = 0;
+    if (!f.n) return FLM_OK;
+    const int B = f.n;
+    const bool skinny = c->spec_gemm != 0;
+    int chunk = 1; float* const stage = score_stage(c, &chunk);
+    SlotOut so{};
+    return with_retry(c, B, [&]() -> int {
+        hipLaunchKernelGGL(k_slots_load, dim3(1), dim3(64), 0, c->stream, in, B, c->prompt_dev);
+        HIPC(c, hipGetLastError());
+        int r = prefill_batched_qt(c, B, 0, true, skinny, nullptr, 0, &f); if (r) return r;
+        for (int r0 = 0; r0 < B; r0 += chunk) {
+            const int m = B - r0 < chunk ? B - r0 : chunk;
+            r = batch_classify(c, r0, r0, m, stage, skinny, in); if (r) return r;
+        }
+        return batch_accept(c, in, f, &so);
+    }, [&] {
+        for (int i = 0; i < B; ++i) { c->batch_slot[f.slot[i]].pos += 1; batch_take(c, f.slot[i], so); }     // (the fed id's row is in the cache; the drawn one is the next to feed)
+        for (int s = 0; s < FLM_BATCH_MAX; ++s) out->ids[s] = so.ids[s];
+        out->live = so.live; out->finished = so.finished;
+    });
+}
+int flm_batch_state(flm_ctx* c, int slot, uint64_t* rng_state, int* n_out, int* stop_reason) {
+    if (!c) return FLM_ERR_INVALID;
+    if (!c->batch_open) return fail(c, FLM_ERR_STATE, "batch_state: no open batch (flm_batch_open), or the cache was written since");
+    if (slot < 0 || slot >= c->batch_lay.n_slots) return fail(c, FLM_ERR_INVALID, "batch_state: slot outside the layout");
+    const flm_ctx::BatchSlot& b = c->batch_slot[slot];
+    if (rng_state) *rng_state = (uint64_t)b.rng;
+    if (n_out) *n_out = b.n_out;
+    if (stop_reason) *stop_reason = b.live ? 0 : b.reason;
+    return FLM_OK;
+}
+int flm_batch_close(flm_ctx* c, int keep_slot) {
+    if (!c) return FLM_ERR_INVALID;
+    if (keep_slot < 0) { c->batch_open = false; return FLM_OK; }
+    int r = batch_ready(c, "batch_close"); if (r) return r;
+    if (keep_slot >= c->batch_lay.n_slots || !c->batch_slot[keep_slot].used) return fail(c, FLM_ERR_INVALID, "batch_close: keep_slot outside the layout, or a slot that never held a sequence");
+    const int base = c->batch_lay.base[keep_slot], len = c->batch_slot[keep_slot].pos;      // (pos: the rows the sequence has in the cache = n_prompt + n_out - 1)
+    c->batch_open = false;
+    // rows [base, base + len) -> [0, len).  base < len: source and destination overlap -- chunks of at most `base` rows, ascending, each launch's ranges disjoint (a chunk's
+    // destination was the source of the chunks in front of it, which the stream has finished)
+    for (int off = 0; base > 0 && off < len; off += base) {
+        const int count = len - off < base ? len - off : base;
+        hipLaunchKernelGGL(k_fan_keep, dim3(c->d.n_layers * c->heads_local), dim3(256), 0, c->stream, c->kcache, c->vcache, c->kv_rows, c->hs, base + off, off, count);
+        HIPC(c, hipGetLastError());
+    }
+    HIPC(c, hipStreamSynchronize(c->stream));
+    return FLM_OK;
+}
+int flm_generate_batch(flm_ctx* c, const flm_batch_req* reqs, int n, flm_fan_cb cb, void* user, int32_t* out_tokens, int stride, int* n_out, uint64_t* rng_out) {
+    if (!c || !reqs || !out_tokens || !n_out) return FLM_ERR_INVALID;
+    if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "generate_batch: one GPU only");
+    if (n < 1 || n > FLM_BATCH_MAX) return fail(c, FLM_ERR_INVALID, "generate_batch: n outside 1 .. FLM_BATCH_MAX");
+    int32_t rows[FLM_BATCH_MAX];
+    for (int j = 0; j < n; ++j) {
+        if (reqs[j].n_prompt < 1 || reqs[j].max_tokens < 1 || reqs[j].max_tokens > stride || (long long)reqs[j].n_prompt + reqs[j].max_tokens - 1 > c->d.max_seq_len)
+            return fail(c, FLM_ERR_INVALID, "generate_batch: n_prompt >= 1, 1 <= max_tokens <= stride, n_prompt + max_tokens - 1 <= max_seq_len");
+        rows[j] = reqs[j].n_prompt + reqs[j].max_tokens - 1;
+    }
+    flm_batch_layout lay{};
+    if (flm_batch_layout_for(n, rows, c->d.max_seq_len, &lay)) { c->err = g_last_error; return FLM_ERR_INVALID; }
+    int r = flm_batch_open(c, &lay); if (r) return r;
+    bool cancelled = false;
+    unsigned live_mask = 0;
+    for (int j = 0; j < n; ++j) n_out[j] = 0;
+    for (int j = 0; j < n && !cancelled; ++j) {
+        int32_t id = -1; int live = 0;
+        r = flm_batch_join(c, j, &reqs[j], &id, &live); if (r) { c->batch_open = false; return r; }
+        out_tokens[(size_t)j * stride] = id; n_out[j] = 1;
+        if (live) live_mask |= 1u << j;
+        if (cb && cb(user, j, 0, id, live ? 0 : 1) != 0) cancelled = true;
+    }
+    while (live_mask && !cancelled) {
+        flm_batch_out bo{};
+        r = flm_batch_step(c, &bo); if (r) { c->batch_open = false; return r; }
+        for (int j = 0; j < n; ++j) {
+            if (bo.ids[j] < 0) continue;
+            const int index = n_out[j];
+            out_tokens[(size_t)j * stride + index] = bo.ids[j]; n_out[j] = index + 1;
+            if (cb && !cancelled && cb(user, j, index, bo.ids[j], (bo.finished >> j) & 1u ? 1 : 0) != 0) cancelled = true;
+        }
+        live_mask = bo.live;
+    }
+    bool any_full = false;
+    for (int j = 0; j < n; ++j) {
+        if (rng_out) rng_out[j] = (uint64_t)c->batch_slot[j].rng;
+        any_full = any_full || (c->batch_slot[j].used && n_out[j] == reqs[j].max_tokens);
+    }
+    c->stop_reason = cancelled ? FLM_STOP_CANCEL : any_full ? FLM_STOP_LENGTH : FLM_STOP_TOKEN; c->stop_rule = 0;
+    return flm_batch_close(c, -1);
 }
 
 // Constrained decoding (include/flm_gpu.h): the automaton lives in ONE device allocation made here, off the steady path; the shaped token graphs reach it through the block

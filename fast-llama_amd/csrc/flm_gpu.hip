@@ -341,6 +341,8 @@ int alloc_run_bufs(flm_ctx* c) {
     HIPC(c, dev_alloc(c, &c->fan_drawn, sizeof(int) * kFanMax, true));                      // flm_generate_n: a step's drawn ids, the states behind the draws, its result block
     HIPC(c, dev_alloc(c, &c->fan_after, sizeof(unsigned long long) * kFanMax, true));
     HIPC(c, dev_alloc(c, &c->fan_res, sizeof(FanOut), true));
+    HIPC(c, dev_alloc(c, &c->batch_res, sizeof(SlotOut), true));                            // flm_batch_join / flm_batch_step: the result block
+    HIPC(c, dev_alloc(c, &c->batch_views, sizeof(AttnArgs) * kBatchMax, true));            // ... and k_attn_slots' views
     c->bounce_bytes = (size_t)d.vocab_size * 4; if (c->bounce_bytes < sizeof(ScoreRow) * (size_t)d.max_seq_len) c->bounce_bytes = sizeof(ScoreRow) * (size_t)d.max_seq_len;   // (a row of logits | max_seq_len ids | max_seq_len flm_score: each one trip)
     HIPC(c, hipHostMalloc((void**)&c->bounce, c->bounce_bytes + 64, hipHostMallocDefault));          // (+ a line for the error word that rides along: d2h)
     HIPC(c, hipHostMalloc((void**)&c->shape_stage, sizeof(ShapeParams), hipHostMallocDefault));   // (the shaper's parameter block on its way to the device: set_shape)
@@ -993,7 +995,7 @@ int flm_prepare(flm_ctx* c) {
 int flm_reset_kv(flm_ctx* c) {
     if (!c) return FLM_ERR_INVALID;
     HIPC(c, hipSetDevice(c->device));
-    c->fan_valid = false;
+    c->fan_valid = false; c->batch_open = false;
     HIPC(c, clear_kv(c));
     HIPC(c, hipStreamSynchronize(c->stream));
     return FLM_OK;

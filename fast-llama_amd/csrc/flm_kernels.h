@@ -55,11 +55,13 @@
 //                         the shaped token form's last act (k_sample_advance), in the accept step of draft-and-verify, and behind flm_op_stop_match
 //   k_attn_fan, k_rope_kv_fan, k_sample_fan, k_fan_accept, k_fan_keep  (flm_fan.h) parallel sampling (flm_generate_n): n completions of one prompt as ONE batch per weight
 //                         pass -- every row attends the shared prompt rows followed by its own tail, and is drawn with its own sampler state
+//   k_rope_kv_slots, k_attn_slots, k_sample_slots, k_batch_accept  (flm_batch.h) cache slots (flm_batch_*): up to 16 independent sequences as ONE batch per weight pass --
+//                         every row at its own position in its own region of the one cache, drawn with its own sampler parameters and state
 // plus small op-level kernels that expose the same __device__ functions to the parity tests.
 // (Round 3's weight-streaming engine -- loader / consumer waves around an LDS ring -- was measured slower than these launches and left the library in round 4:
 //  tools/experiments/engine/, numbers in profiles/r03_engine_timelines.txt.)
 //
-// The code lives in: flm_math.h (exact scalar / wave building blocks), flm_wait.h (every cross-workgroup wait: flag polls, granule pieces, the give-up policy), flm_gemv.h, flm_attn.h, flm_layer.h, flm_prefill.h, flm_misc.h, flm_sample.h, flm_score.h, flm_logprob.h, flm_spec.h, flm_stop.h, flm_fan.h, flm_entropy.h (with flm_logf.h, the logarithm the host compiles too).
+// The code lives in: flm_math.h (exact scalar / wave building blocks), flm_wait.h (every cross-workgroup wait: flag polls, granule pieces, the give-up policy), flm_gemv.h, flm_attn.h, flm_layer.h, flm_prefill.h, flm_misc.h, flm_sample.h, flm_score.h, flm_logprob.h, flm_spec.h, flm_stop.h, flm_fan.h, flm_batch.h, flm_entropy.h (with flm_logf.h, the logarithm the host compiles too).
 #pragma once
 #include "flm_math.h"
 #include "flm_wait.h"
@@ -76,3 +78,4 @@
 #include "flm_logprob.h"
 #include "flm_spec.h"
 #include "flm_fan.h"
+#include "flm_batch.h"

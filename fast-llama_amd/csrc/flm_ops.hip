@@ -466,6 +466,40 @@ int flm_op_attention_fan(float* out, float* kc, float* vc, const float* q, const
     return FLM_OK;
 }
 
+// one flm_batch_step's RoPE / cache rows / attention on caller-supplied caches: the launches prefill_batched makes with a SlotDesc (flm_prompt.hip)
+int flm_op_attention_slots(float* out, float* kc, float* vc, const float* q, const float* k, const float* v,
+                           int n_heads, int hs, int max_seq, int n, const int32_t* base, const int32_t* pos) {
+    if (!out || !kc || !vc || !q || !k || !v || !base || !pos || n_heads < 1 || hs < 32 || hs > 256 || hs % 8 || n < 1 || n > FLM_BATCH_MAX || max_seq < 1) return FLM_ERR_INVALID;
+    SlotDesc f{}; f.n = n;
+    int top = 0;
+    for (int r = 0; r < n; ++r) {
+        if (base[r] < 0 || pos[r] < 0 || (long long)base[r] + pos[r] >= max_seq) return FLM_ERR_INVALID;
+        f.slot[r] = r; f.base[r] = base[r]; f.pos[r] = pos[r]; f.rows[r] = max_seq - base[r];
+        top = pos[r] > top ? pos[r] : top;
+    }
+    const int dim = n_heads * hs;
+    const size_t nd = (size_t)n * dim, nc = (size_t)n_heads * max_seq * hs, h2 = hs / 2;
+    std::vector<float> cs, sn; build_rope_table(hs, top + 1, cs, sn);
+    std::vector<float> qkv(3 * nd);
+    for (int j = 0; j < n; ++j) {
+        memcpy(&qkv[(size_t)j * 3 * dim], q + (size_t)j * dim, (size_t)dim * 4); memcpy(&qkv[(size_t)j * 3 * dim + dim], k + (size_t)j * dim, (size_t)dim * 4);
+        memcpy(&qkv[(size_t)j * 3 * dim + 2 * dim], v + (size_t)j * dim, (size_t)dim * 4);
+    }
+    DevBuf dqkv, dq, dkc, dvc, dout, dc, dsn, dviews;
+    if (dqkv.alloc(3 * nd * 4) || dq.alloc(nd * 4) || dkc.alloc(nc * 4) || dvc.alloc(nc * 4) || dout.alloc(nd * 4) || dc.alloc((top + 1) * h2 * 4) || dsn.alloc((top + 1) * h2 * 4) ||
+        dviews.alloc(sizeof(AttnArgs) * kBatchMax)) return FLM_ERR_OOM;
+    OPC(hipMemcpy(dqkv.p, qkv.data(), 3 * nd * 4, hipMemcpyHostToDevice));
+    OPC(hipMemcpy(dkc.p, kc, nc * 4, hipMemcpyHostToDevice)); OPC(hipMemcpy(dvc.p, vc, nc * 4, hipMemcpyHostToDevice));
+    OPC(hipMemcpy(dc.p, cs.data(), (top + 1) * h2 * 4, hipMemcpyHostToDevice)); OPC(hipMemcpy(dsn.p, sn.data(), (top + 1) * h2 * 4, hipMemcpyHostToDevice));
+    int r = launch_rope_kv_slots(nullptr, 0, dqkv.as<float>(), dq.as<float>(), dkc.as<float>(), dvc.as<float>(), dc.as<float>(), dsn.as<float>(), dim, hs, max_seq, f); if (r) return r;
+    AttnArgs a{}; a.q = dq.as<float>(); a.kcache = dkc.as<float>(); a.vcache = dvc.as<float>(); a.out = dout.as<float>(); a.hs = hs; a.max_seq = max_seq;
+    r = launch_attn_slots(nullptr, 0, a, f, n_heads, dim, dviews.as<AttnArgs>()); if (r) return r;
+    OPC(hipDeviceSynchronize());
+    OPC(hipMemcpy(out, dout.p, nd * 4, hipMemcpyDeviceToHost));
+    OPC(hipMemcpy(kc, dkc.p, nc * 4, hipMemcpyDeviceToHost)); OPC(hipMemcpy(vc, dvc.p, nc * 4, hipMemcpyDeviceToHost));
+    return FLM_OK;
+}
+
 /* elementary functions exactly as the kernels evaluate them (tests pin them against the host's IEEE results) */
 int flm_op_math(int fn, float* x, const float* y, size_t n) {
     if (!x || n == 0 || fn < 0 || fn > 5 || (fn >= 2 && !y)) return FLM_ERR_INVALID;

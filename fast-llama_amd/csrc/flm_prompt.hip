@@ -110,11 +110,45 @@ int launch_rope_kv_fan(flm_ctx* c, hipStream_t st, const float* qkv, float* qout
     return FLM_OK;
 }
 
+// k_slot_views + k_attn_slots on the n live rows of a batch step (flm_batch.h): one workgroup per (head, row), the LDS of the largest slot; views: device memory for 16
+// AttnArgs; c may be null (flm_op_attention_slots)
+int launch_attn_slots(flm_ctx* c, hipStream_t st, const AttnArgs& aa, const SlotDesc& f, int heads, int row_stride, AttnArgs* views) {
+    {   // a long slot's score row can take more than the default limit: raise the kernel's dynamic-LDS limit, once per device
+        static std::mutex mu; static bool done[64] = {false};
+        int dev = 0; HIPC(c, hipGetDevice(&dev));
+        std::lock_guard<std::mutex> lk(mu);
+        if (dev >= 0 && dev < 64 && !done[dev]) {
+            HIPC(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_slots), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
+            done[dev] = true;
+        }
+    }
+    if (aa.hs > 256 || aa.hs % 8 || f.n < 1 || f.n > kBatchMax || aa.n_peer || !views) return fail(c, FLM_ERR_INVALID, "attn_slots: head size <= 256, 1 .. 16 rows, one GPU");
+    int largest = 0;
+    for (int r = 0; r < f.n; ++r) {
+        if (f.base[r] < 0 || f.rows[r] < 1 || f.base[r] + f.rows[r] > aa.max_seq || f.pos[r] < 0 || f.pos[r] >= f.rows[r]) return fail(c, FLM_ERR_INVALID, "attn_slots: a row outside its slot, or a slot outside the cache");
+        largest = f.rows[r] > largest ? f.rows[r] : largest;
+    }
+    if (attn_lds_bytes(largest, aa.hs) > kLdsMax) return fail(c, FLM_ERR_UNSUPPORTED, "attn_slots: one query's scores do not fit the LDS");
+    hipLaunchKernelGGL(k_slot_views, dim3(1), dim3(64), 0, st, aa, f, views);
+    HIPC(c, hipGetLastError());
+    hipLaunchKernelGGL(k_attn_slots, dim3(heads, f.n), dim3(kAttnBlock), attn_lds_bytes(largest, aa.hs), st, (const AttnArgs*)views, f, row_stride);
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
+int launch_rope_kv_slots(flm_ctx* c, hipStream_t st, const float* qkv, float* qout, float* kcache, float* vcache, const float* rope_cos, const float* rope_sin, int dim, int hs, int kv_rows, const SlotDesc& f) {
+    hipLaunchKernelGGL(k_rope_kv_slots, dim3(f.n), dim3(256), 0, st, qkv, qout, kcache, vcache, rope_cos, rope_sin, dim, hs, kv_rows, f);
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
+
 // all_layers (flm_score_tokens): the last layer runs to its end as well -- pf_x then holds every row's final residual, the classifier's input
 // fan (flm_generate_n; null: every launch is the one made without it): the B rows are the sequences of a fan step (flm_fan.h) -- `pos` is their one LOGICAL position, the
 // QKV GEMM takes the plain-store route with k_rope_kv_fan behind it, the attention is k_attn_fan; everything else is a row's own and stays what it is
+// row0 (flm_batch_join; 0: every launch is the one made without it): the batch is a prompt entering the cache slot whose region starts at physical row row0 -- the layer's
+// cache pointers move by row0 rows for every kernel that writes or reads them, the attention's bound shrinks to what lies behind row0; `pos` stays the LOGICAL position
+// slots (a flm_batch_step; null: as above): the B rows are the live slots' last ids, each at its own position in its own region -- the fan's route with k_rope_kv_slots and k_attn_slots
 template <int QT>
-int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req = false, const FanDesc* fan = nullptr) {
+int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req = false, const FanDesc* fan = nullptr, int row0 = 0, const SlotDesc* slots = nullptr) {
     const bool skinny = skinny_req && QT == QT_INT8 && B <= kSkinnyTokens && c->world == 1;      // (the verify pass; int16: the tiles)
     const auto& d = c->d;
     const int L = d.n_layers, dim = d.dim, hid = d.hidden_dim, hs = c->hs;
@@ -141,35 +175,42 @@ int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req
     HIPC(c, hipGetLastError());
     for (int l = 0; l < L; ++l) {
         LayerW& w = c->layers[l];
+        float* const kc = c->kcache + (size_t)l * kv_layer + (size_t)row0 * hs;    // (row0: the slot's origin; the stride between two heads' rows stays kv_rows)
+        float* const vc = c->vcache + (size_t)l * kv_layer + (size_t)row0 * hs;
         // x2 = rmsnorm(x1); qx = quantize(x2); q,k,v = W x; RoPE; cache rows   (transformer.cpp:132-135, 386-395, 431-439)
         RowsArgs ra{c->pf_x, w.att_norm, c->pf_xq, c->pf_xs, dim, c->pf_xst};
         r = launch_rows<QT, PRO_RMSNORM_QUANT>(c, st, ra, B, tp); if (r) return r;
         GemmArgs g{w.qkv.q, w.qkv.s, c->pf_xq, c->pf_xs, c->pf_qkv, 3 * dimL, dim, 3 * dimL, B, c->pf_xst, w.qkv.st};
         if (fan) {
             r = launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, skinny); if (r) return r;
-            r = launch_rope_kv_fan(c, st, c->pf_qkv, c->pf_q, c->kcache + (size_t)l * kv_layer, c->vcache + (size_t)l * kv_layer, c->rope_cos, c->rope_sin, dimL, hs, c->kv_rows, *fan); if (r) return r;
+            r = launch_rope_kv_fan(c, st, c->pf_qkv, c->pf_q, kc, vc, c->rope_cos, c->rope_sin, dimL, hs, c->kv_rows, *fan); if (r) return r;
+        }
+        else if (slots) {
+            r = launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, skinny); if (r) return r;
+            r = launch_rope_kv_slots(c, st, c->pf_qkv, c->pf_q, kc, vc, c->rope_cos, c->rope_sin, dimL, hs, c->kv_rows, *slots); if (r) return r;
         }
         else if ((QT == QT_INT16 || c->use_mfma || skinny) && dimL % 32 == 0 && hs % 2 == 0) {      // (int16: always the matrix-core tiles -- round 5: with the same epilogues as the int8 tiles)
             // RoPE and the cache rows as the epilogue of the matrix-core tiles: no [tokens][3 dim] round trip, no k_rope_kv_rows
-            g.qout = c->pf_q; g.kcache = c->kcache + (size_t)l * kv_layer; g.vcache = c->vcache + (size_t)l * kv_layer;
+            g.qout = c->pf_q; g.kcache = kc; g.vcache = vc;
             g.rope_cos = c->rope_cos; g.rope_sin = c->rope_sin; g.dim = dimL; g.hs = hs; g.max_seq = c->kv_rows /* (the stride between two heads' cache rows) */; g.pos0 = pos;
             r = launch_gemm_any<QT, EPI_ROPE_KV>(c, st, g, c->use_mfma, skinny); if (r) return r;
         } else {
             r = launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, skinny); if (r) return r;
-            hipLaunchKernelGGL(k_rope_kv_rows, dim3(B), dim3(256), 0, st, (const float*)c->pf_qkv, c->pf_q, c->kcache + (size_t)l * kv_layer, c->vcache + (size_t)l * kv_layer,
+            hipLaunchKernelGGL(k_rope_kv_rows, dim3(B), dim3(256), 0, st, (const float*)c->pf_qkv, c->pf_q, kc, vc,
                                (const float*)c->rope_cos, (const float*)c->rope_sin, dimL, hs, c->kv_rows, pos);
             HIPC(c, hipGetLastError());
         }
         if (l == L - 1 && !all_layers) break;             // the batch only has to fill the cache: nothing downstream of the last layer's K/V is needed
         // attention of every query over the cache rows 0 .. its own position   (execute_attn :441-449): the local heads' columns of att
-        AttnArgs aa{}; aa.q = c->pf_q; aa.kcache = c->kcache + (size_t)l * kv_layer; aa.vcache = c->vcache + (size_t)l * kv_layer;
-        aa.out = c->pf_att + col_a; aa.pos_ptr = &c->state->pos; aa.hs = hs; aa.max_seq = d.max_seq_len; aa.kv_rows = c->kv_rows;
+        AttnArgs aa{}; aa.q = c->pf_q; aa.kcache = kc; aa.vcache = vc;
+        aa.out = c->pf_att + col_a; aa.pos_ptr = &c->state->pos; aa.hs = hs; aa.max_seq = d.max_seq_len - row0; aa.kv_rows = c->kv_rows;
         if (tp) { const size_t off = (char*)aa.out - c->xbuf; for (int r2 = 0; r2 < c->world; ++r2) if (r2 != c->rank) aa.out_peer[aa.n_peer++] = (float*)(c->peer[r2] + off); }
         // which kernels: the exps of a tile of queries (weighted sum on the matrix cores) or the scores of 8 queries (VALU) must fit the LDS;
         // one query per workgroup needs 4 bytes per position and always fits (flm_ctx_create checked max_seq_len against it)
         const bool mq_fits = attn_mq_lds_bytes(d.max_seq_len, hs) <= kLdsMax;
         const bool pv_mfma = c->use_pv_mfma && (hs & 1) == 0;
         if (fan) { r = launch_attn_fan(c, st, aa, *fan, c->heads_local, dim); if (r) return r; }
+        else if (slots) { r = launch_attn_slots(c, st, aa, *slots, c->heads_local, dim, c->batch_views); if (r) return r; }
         else if (hs <= 128 && c->use_prefill_mq && c->use_qk_mfma && c->pf_scores && (pv_mfma || mq_fits)) {
             // scores on the matrix cores (fp32 MFMA = the reference's chains, bit for bit), then softmax + weighted sum per tile of queries
             aa.sc_global = c->pf_scores;
@@ -230,9 +271,14 @@ int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req
 int launch_gemm_store(flm_ctx* c, hipStream_t st, int qt, const GemmArgs& g, int use_mfma) {
     return qt == FLM_QT_INT8 ? launch_gemm<QT_INT8, EPI_STORE>(c, st, g, use_mfma) : launch_gemm<QT_INT16, EPI_STORE>(c, st, g, use_mfma);
 }
-int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers, bool skinny, const FanDesc* fan) {
+int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers, bool skinny, const FanDesc* fan, int row0, const SlotDesc* slots) {
     if (fan && (c->world != 1 || fan->n != B || pos != fan->S + fan->t)) return fail(c, FLM_ERR_INVALID, "prefill: a fan step is one GPU's batch of fan.n rows at S + t");
-    return c->d.quant_type == FLM_QT_INT8 ? prefill_batched<QT_INT8>(c, B, pos, all_layers, skinny, fan) : prefill_batched<QT_INT16>(c, B, pos, all_layers, skinny, fan);
+    if ((row0 || slots) && (c->world != 1 || fan || row0 < 0 || (slots && (row0 || slots->n != B)) || row0 + pos + (slots ? 0 : B) > c->d.max_seq_len))
+        return fail(c, FLM_ERR_INVALID, "prefill: a slot's batch is one GPU's, inside the cache, and not a fan step");
+    for (int r = 0; slots && r < slots->n; ++r)      // (in front of the first launch: k_rope_kv_slots writes the rows' cache rows)
+        if (slots->n > kBatchMax || slots->base[r] < 0 || slots->rows[r] < 1 || slots->pos[r] < 0 || slots->pos[r] >= slots->rows[r] || (long long)slots->base[r] + slots->rows[r] > c->d.max_seq_len)
+            return fail(c, FLM_ERR_INVALID, "prefill: a batch row outside its slot, or a slot outside the cache");
+    return c->d.quant_type == FLM_QT_INT8 ? prefill_batched<QT_INT8>(c, B, pos, all_layers, skinny, fan, row0, slots) : prefill_batched<QT_INT16>(c, B, pos, all_layers, skinny, fan, row0, slots);
 }
 int launch_gemm_skinny_store(flm_ctx* c, hipStream_t st, const GemmArgs& g, int force_nb) { return launch_gemm_skinny<EPI_STORE>(c, st, g, force_nb); }
 
@@ -387,6 +433,32 @@ int fan_classify(flm_ctx* c, int row0, int m, float* stage, bool skinny, float t
     const int V = c->d.vocab_size;
     int r = c->d.quant_type == FLM_QT_INT8 ? classify_rows_t<QT_INT8>(c, row0, m, stage, skinny) : classify_rows_t<QT_INT16>(c, row0, m, stage, false); if (r) return r;
     return launch_sample_fan(c, c->stream, stage, V, V, row0, m, temperature, topp, in, c->sort_buf, c->fan_drawn, c->fan_after);
+}
+// k_sample_slots on `rows` rows of n logits, ld floats apart, batch rows row0 ..; sort_buf [16][2][n] (needed where a row of the chunk is sampled)
+int launch_sample_slots(flm_ctx* c, hipStream_t st, const float* logits, int ld, int n, int row0, int rows, const SlotIn& in, unsigned long long* sort_buf, int* drawn, unsigned long long* after) {
+    {   // the strip of a large vocabulary: the dynamic-LDS limit, once per device
+        static std::mutex mu; static bool done[64] = {false};
+        int dev = 0; HIPC(c, hipGetDevice(&dev));
+        std::lock_guard<std::mutex> lk(mu);
+        if (dev >= 0 && dev < 64 && !done[dev]) {
+            HIPC(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sample_slots), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
+            done[dev] = true;
+        }
+    }
+    if (rows < 1 || row0 < 0 || row0 + rows > kBatchMax) return fail(c, FLM_ERR_INVALID, "sample_slots: rows outside a batch of 16");
+    bool sampled = false;
+    for (int r = row0; r < row0 + rows; ++r) sampled = sampled || in.temp[r] != 0.0f;
+    if (sampled && (n < 2 || sample_lds_bytes(n) > kLdsMax || !sort_buf)) return fail(c, FLM_ERR_UNSUPPORTED, "sample_slots: the row does not fit one workgroup's LDS strip");
+    hipLaunchKernelGGL(k_sample_slots, dim3(rows), dim3(kSampleBlock), sampled ? sample_lds_bytes(n) : 2 * kSampleWaves * sizeof(int), st, logits, ld, n, row0, in, sort_buf, drawn, after);
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
+// a batch step's classifier stage, or a join's (src_row0: the batch row the chunk starts at; row0: the SlotIn row its first draw belongs to): the chunk through
+// score_classify's prologue and GEMM, then k_sample_slots -- every row with its own parameters and state
+int batch_classify(flm_ctx* c, int src_row0, int row0, int m, float* stage, bool skinny, const SlotIn& in) {
+    const int V = c->d.vocab_size;
+    int r = c->d.quant_type == FLM_QT_INT8 ? classify_rows_t<QT_INT8>(c, src_row0, m, stage, skinny) : classify_rows_t<QT_INT16>(c, src_row0, m, stage, false); if (r) return r;
+    return launch_sample_slots(c, c->stream, stage, V, V, row0, m, in, c->sort_buf, c->fan_drawn, c->fan_after);
 }
 // the verify pass's classifier stage: the same chunk through the same prologue and GEMM (skinny: k_gemm_q8_skinny, int8), then k_argmax_rows into argmax_out[row0 ..]
 // (draw given and its temperature > 0: k_sample_rows in place of k_argmax_rows)

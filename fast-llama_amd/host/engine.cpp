@@ -225,6 +225,41 @@ bool GpuTransformer::generate_samples(const char* prompt, int n, uint64_t seed, 
     return true;
 }
 
+bool GpuTransformer::generate_prompts(const std::vector<std::string>& prompts, uint64_t seed, int max_new_tokens, float temperature, float topp, std::vector<std::string>& texts) {
+    texts.clear();
+    const int n = (int)prompts.size();
+    if (_ctxs.size() != 1) { _err = "--prompts: one device only"; return false; }
+    if (n < 1 || n > FLM_BATCH_MAX) { _err = "--prompts: 1 to 16 prompts"; return false; }
+    if (max_new_tokens < 0) max_new_tokens = 0;
+    const int share = _cfg.max_seq_len / n;                  // (every prompt gets an equal share of the cache's rows: flm_batch_layout_for)
+    std::vector<std::vector<int>> inputs(n);
+    std::vector<flm_batch_req> reqs(n);
+    int want = 1;
+    for (int j = 0; j < n; ++j) {
+        inputs[j] = encode(prompts[j].c_str());
+        if (inputs[j].empty()) { fprintf(stderr, "Empty input for generate()\n"); return false; }
+        printf("Input prompt:%s\n", prompts[j].c_str());
+        print_vector("Input tokens:", inputs[j]);
+        const int n_in = (int)inputs[j].size();
+        if (n_in >= share) { fprintf(stderr, "Input is too long for generate()\n"); return false; }
+        const int room = share - n_in;
+        flm_batch_req& q = reqs[j];
+        q.prompt = inputs[j].data(); q.n_prompt = n_in; q.max_tokens = (max_new_tokens < room ? max_new_tokens : room) + 1;
+        q.temperature = temperature; q.topp = topp; q.rng_state = seed + (uint64_t)j; q.stop_token = 0;
+        want = q.max_tokens > want ? q.max_tokens : want;
+    }
+    std::vector<int32_t> ids((size_t)n * want);
+    std::vector<int> n_out(n, 0);
+    const int rc = flm_generate_batch(_ctxs[0], reqs.data(), n, nullptr, nullptr, ids.data(), want, n_out.data(), nullptr);
+    if (rc != FLM_OK) { _err = std::string("--prompts: ") + flm_last_error(_ctxs[0]); return false; }
+    texts.resize(n);
+    for (int j = 0; j < n; ++j) {
+        int prev = -1;
+        for (int i = 0; i < n_out[j]; ++i) { const int tok = ids[(size_t)j * want + i]; texts[j] += _tok.decode(tok, prev); prev = tok; }
+    }
+    return true;
+}
+
 bool GpuTransformer::generate(const char* prompt, const std::function<bool(const char*, int, int, bool)>& cb,
                               int max_new_tokens, float temperature, float topp) {
     const std::vector<int> input = encode(prompt);

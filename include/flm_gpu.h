@@ -371,6 +371,54 @@ int  flm_generate_n(flm_ctx* ctx, const int32_t* prompt, int n_prompt, int pos, 
                     int32_t stop_token /* -1: none */, flm_fan_cb cb /* may be NULL */, void* user,
                     int32_t* out_tokens /* [n][max_tokens] */, int* n_out /* [n] */);
 int  flm_fan_keep(flm_ctx* ctx, int seq);
+/* Cache slots: up to FLM_BATCH_MAX INDEPENDENT sequences -- each its own prompt, length, sampler parameters and state -- served per pass over the weights, at step
+ * granularity, so that a sequence can join while others are in flight (continuous batching).  One context, one cache; no reference counterpart.
+ * Contract, for every request, in any slot, whatever else shares the pass, joins or finishes around it: the ids delivered from flm_batch_join through the flm_batch_steps,
+ * their count and the final sampler state are exactly what
+ *     flm_generate(ctx, prompt, n_prompt, 0, max_tokens, temperature, topp, &rng_state, stop_token, ...)
+ * delivers on a fresh context, the ids element for element, the state as a 64-bit integer; and the slot's rows [base, base + n_prompt + n_out - 1) of every layer's K and V
+ * are that context's rows [0, ...), bit for bit.  The stop token is delivered, counted and not fed.  temperature == 0 is the greedy run: the state passes through.  Like plain
+ * flm_generate these calls IGNORE installed sampling controls, stop rules, the constraint, armed log-probabilities and flm_entropy_set (per-slot forms of them are follow-ups).
+ *   layout    no cache memory of its own: the context's rows [0, max_seq_len) are divided into n_slots regions, slot s owning the physical rows [base[s], base[s] + rows[s]),
+ *             base the prefix sum of rows.  A sequence in slot s keeps LOGICAL position p -- for RoPE and for the attention's order -- in physical row base[s] + p.
+ *             flm_batch_layout_for computes and checks this without a device (pure host arithmetic, like flm_fan_layout_for) and is the one place the capacity condition
+ *             sum(rows) <= max_seq_len is written: FLM_ERR_INVALID for n_slots outside 1 .. FLM_BATCH_MAX, a rows[s] < 1, or a layout that does not fit.
+ *   open      records the layout (it must be what flm_batch_layout_for gives for this context's max_seq_len) and empties all slots.  Launches nothing, allocates nothing.  Any
+ *             other entry point that writes the cache ends the batch: join, step, state and close(keep) then answer FLM_ERR_STATE.
+ *   join      needs an empty slot (a slot whose sequence finished is empty again; its flm_batch_state stays readable until the next join into it), n_prompt >= 1,
+ *             max_tokens >= 1, n_prompt + max_tokens - 1 <= rows[slot], and flm_generate_n's checks on ids, temperature, top-p, stop token and the sampler's vocabulary bound.
+ *             The prompt enters at logical positions [0, n_prompt) of the slot as ONE batch through the batched kernels with the last layer completed (a verify pass's route:
+ *             every row's logits are flm_forward's bits; no token launch, the decode state and the captured graphs untouched); token 0 is drawn from its last row with the
+ *             request's first coin and returned in *first_token.  *live = 0 if token 0 was the stop token or max_tokens == 1.  Other slots' rows and state are untouched.
+ *   step      ONE pass over the weights for all live slots: each feeds its last id at its own position (k_rope_kv_slots, k_attn_slots -- csrc/flm_batch.h: workgroup
+ *             (head, row) narrows the cache to the row's slot and runs the one-query attention), one id is drawn per slot with its own state, temperature and top-p.  A
+ *             finished or empty slot is not in the batch and costs nothing.  A slot leaves the live set when it draws its stop token or has delivered max_tokens ids.  ONE
+ *             host synchronisation (the result block); a step's inputs are launch arguments, so a step that retries enqueues the same work.  No live slot: FLM_OK, live = 0,
+ *             nothing launched.
+ *   state     the sampler state behind exactly the delivered ids, their count, and FLM_STOP_TOKEN / FLM_STOP_LENGTH (0 while the slot runs).
+ *   close     ends the batch.  keep_slot >= 0: that slot's rows move to [0, len), len = n_prompt + n_out - 1, and any entry point continues the conversation from pos = len, as
+ *             after flm_fan_keep (where source and destination overlap, base < len, the move runs as successive copies of at most base rows, ascending).
+ *   flm_generate_batch  the loop on top: rows[j] = n_prompt[j] + max_tokens[j] - 1, open, join every request in order, step until nobody is live, close(-1).  Request j's
+ *             ids go to out_tokens[j * stride ..) (stride >= every max_tokens), n_out[j], rng_out[j].  cb(user, seq, index, token, last) runs on the calling thread in
+ *             (step, slot) order; a non-zero return ends the call behind that step ("stop_reason": cancel; else length where any sequence ran to max_tokens; else token).
+ * Errors, with nothing launched and the cache untouched: FLM_ERR_INVALID for the checks above, a slot outside the layout, a join into a live slot; FLM_ERR_STATE without an open
+ * batch; FLM_ERR_UNSUPPORTED for world > 1, for head sizes whose one-query attention does not fit the LDS, and for temperature > 0 where flm_decode_sample refuses.
+ * Nothing is allocated in any of these calls: the result block exists since flm_ctx_create. */
+#define FLM_BATCH_MAX 16
+typedef struct flm_batch_layout { int32_t n_slots; int32_t base[FLM_BATCH_MAX], rows[FLM_BATCH_MAX]; } flm_batch_layout;
+typedef struct flm_batch_req { const int32_t* prompt; int32_t n_prompt, max_tokens; float temperature, topp;
+                               uint64_t rng_state; int32_t stop_token /* -1: none */; } flm_batch_req;
+typedef struct flm_batch_out { int32_t ids[FLM_BATCH_MAX];      /* -1: the slot delivered nothing in this step */
+                               uint32_t live;                   /* slots still running behind this step */
+                               uint32_t finished; } flm_batch_out; /* slots whose LAST id is in this step */
+int  flm_batch_layout_for(int n_slots, const int32_t* rows, int max_seq_len, flm_batch_layout* out);
+int  flm_batch_open(flm_ctx* ctx, const flm_batch_layout* layout);
+int  flm_batch_join(flm_ctx* ctx, int slot, const flm_batch_req* req, int32_t* first_token, int* live);
+int  flm_batch_step(flm_ctx* ctx, flm_batch_out* out);
+int  flm_batch_state(flm_ctx* ctx, int slot, uint64_t* rng_state, int* n_out, int* stop_reason);
+int  flm_batch_close(flm_ctx* ctx, int keep_slot /* -1: none */);
+int  flm_generate_batch(flm_ctx* ctx, const flm_batch_req* reqs, int n, flm_fan_cb cb /* may be NULL */, void* user,
+                        int32_t* out_tokens /* [n][stride] */, int stride, int* n_out /* [n] */, uint64_t* rng_out /* [n], may be NULL */);
 /* Constrained decoding: a token-level deterministic automaton masks the logits in front of the controls -- what "one of these strings", a JSON shape or a regular expression
  * reduce to.  No reference counterpart.  The automaton is CSR: the edges of state q are [row_ptr[q], row_ptr[q + 1]).
  *   delta(q, t)  the edge_next of t's edge in state q, or q ITSELF when t has no edge there.  The no-edge case is reachable only through the multinomial branch's last-index
@@ -692,6 +740,11 @@ int  flm_op_attention(float* out, float* kc, float* vc, const float* q, const fl
  * 2 <= n <= FLM_FAN_MAX, hs <= 128, S >= 1, S + t + 1 <= max_seq and every base[j] + t < max_seq (FLM_ERR_INVALID otherwise). */
 int  flm_op_attention_fan(float* out, float* kc, float* vc, const float* q, const float* k, const float* v,
                           int n_heads, int hs, int max_seq, int n, int S, int t, const int32_t* base);
+/* the same task for the n rows of one flm_batch_step (k_rope_kv_slots + k_attn_slots, csrc/flm_batch.h): q, k, v are [n][n_heads*hs]; row r is at ITS logical position pos[r]
+ * of the slot that starts at cache row base[r] (and reaches to max_seq): its k / v go to cache row base[r] + pos[r], its query attends rows base[r] .. base[r] + pos[r].
+ * kc, vc as above (updated); out [n][n_heads*hs].  1 <= n <= FLM_BATCH_MAX, pos[r] >= 0, base[r] >= 0, base[r] + pos[r] < max_seq (FLM_ERR_INVALID otherwise). */
+int  flm_op_attention_slots(float* out, float* kc, float* vc, const float* q, const float* k, const float* v,
+                            int n_heads, int hs, int max_seq, int n, const int32_t* base, const int32_t* pos);
 /* libm expf as the device evaluates it (the reference calls glibc expf in softmax_sisd and swiglu);
  * in place over n floats.  Lets the tests pin the device routine against glibc bit for bit. */
 int  flm_op_expf(float* x, size_t n);
