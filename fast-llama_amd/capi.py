@@ -37,6 +37,7 @@ SYMBOLS = (
     "flm_entropy_validate", "flm_entropy_set", "flm_entropy_mu", "flm_op_logf", "flm_op_entropy_rows",
     "flm_fan_layout_for", "flm_generate_n", "flm_fan_keep", "flm_op_attention_fan",
     "flm_batch_layout_for", "flm_batch_open", "flm_batch_join", "flm_batch_step", "flm_batch_state", "flm_batch_close", "flm_generate_batch", "flm_op_attention_slots",
+    "flm_batch_plan_for", "flm_batch_admit", "flm_batch_pass", "flm_op_attention_segs",
 )
 
 # flm_score (include/flm_gpu.h): one row of flm_score_tokens / flm_op_score_rows
@@ -75,6 +76,25 @@ class BatchReqStruct(C.Structure):
 class BatchOutStruct(C.Structure):
     """flm_batch_out (include/flm_gpu.h)"""
     _fields_ = [("ids", C.c_int32 * BATCH_MAX), ("live", C.c_uint32), ("finished", C.c_uint32)]
+
+
+class BatchSegStruct(C.Structure):
+    """flm_batch_seg (include/flm_gpu.h)"""
+    _fields_ = [("slot", C.c_int32), ("row0", C.c_int32), ("n", C.c_int32), ("pos0", C.c_int32), ("draws", C.c_int32)]
+
+
+class BatchPlan(C.Structure):
+    """flm_batch_plan (include/flm_gpu.h): the segments of one flm_batch_pass -- the running slots' step rows first, then the filling slots' prompt chunks"""
+    _fields_ = [("n_segs", C.c_int32), ("n_rows", C.c_int32), ("n_step", C.c_int32), ("n_draws", C.c_int32), ("seg", BatchSegStruct * BATCH_MAX)]
+
+    def segments(self):
+        """-> [(slot, row0, n, pos0, draws)] of the plan's n_segs segments"""
+        return [(g.slot, g.row0, g.n, g.pos0, g.draws) for g in self.seg[:self.n_segs]]
+
+
+class BatchPassOutStruct(C.Structure):
+    """flm_batch_pass_out (include/flm_gpu.h)"""
+    _fields_ = [("ids", C.c_int32 * BATCH_MAX), ("live", C.c_uint32), ("finished", C.c_uint32), ("filling", C.c_uint32)]
 
 
 @dataclasses.dataclass
@@ -713,6 +733,26 @@ class Ctx:
         _check(lib().flm_batch_step(self._h, C.byref(out)), self._h)
         return np.array(out.ids[:], dtype=np.int32), int(out.live), int(out.finished)
 
+    def batch_admit(self, slot, req):
+        """flm_batch_admit: the request is recorded in the empty slot `slot`, which is filling from now on; launches nothing.  The library reads the prompt's ids until
+        the slot has delivered its token 0: this object keeps them alive until then (or until the next batch_open / close)"""
+        st, keep = req.struct()
+        _check(lib().flm_batch_admit(self._h, int(slot), C.byref(st)), self._h)
+        if not hasattr(self, "_admitted"):
+            self._admitted = {}
+        self._admitted[int(slot)] = keep
+
+    def batch_pass(self, prompt_rows_max=0):
+        """flm_batch_pass: one pass over the weights -- every running slot's step row and up to prompt_rows_max rows (0: no bound) of the filling slots' prompts ->
+        (ids[BATCH_MAX] by slot: a running slot's next id, token 0 of a slot whose prompt completed, -1 otherwise; the running mask behind the pass; the mask of the slots
+        whose last id is in it; the mask of the slots still filling)"""
+        out = BatchPassOutStruct()
+        _check(lib().flm_batch_pass(self._h, int(prompt_rows_max), C.byref(out)), self._h)
+        held = getattr(self, "_admitted", {})
+        for s in [s for s in held if not (out.filling >> s) & 1]:
+            del held[s]
+        return np.array(out.ids[:], dtype=np.int32), int(out.live), int(out.finished), int(out.filling)
+
     def batch_state(self, slot):
         """flm_batch_state -> (the sampler state behind the slot's delivered ids, their count, FLM_STOP_TOKEN (1) / FLM_STOP_LENGTH (0); 0 while the slot runs)"""
         st = C.c_uint64(0); n = C.c_int(0); why = C.c_int(0)
@@ -1188,6 +1228,38 @@ def batch_layout(rows, max_seq_len) -> BatchLayout:
     r = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
     out = BatchLayout()
     _check(lib().flm_batch_layout_for(int(r.size), _p(r), int(max_seq_len), C.byref(out)))
+    return out
+
+
+def batch_plan(fed, pending, running, prompt_rows_max=0) -> BatchPlan:
+    """flm_batch_plan_for (pure host arithmetic): the segments flm_batch_pass runs for slots with fed[s] rows in the cache and pending[s] prompt rows to go, `running` the
+    mask of running slots and a budget of prompt_rows_max prompt rows (0: no bound), or FlmError where the call would refuse"""
+    f = np.ascontiguousarray(fed, dtype=np.int32).reshape(-1); p = np.ascontiguousarray(pending, dtype=np.int32).reshape(-1)
+    if f.size != p.size:
+        raise ValueError("batch_plan: fed and pending have one entry per slot")
+    if not 0 <= int(running) < 1 << 32:
+        raise ValueError("batch_plan: running is a 32-bit mask")
+    out = BatchPlan()
+    _check(lib().flm_batch_plan_for(int(f.size), _p(f), _p(p), C.c_uint32(int(running)), int(prompt_rows_max), C.byref(out)))
+    return out
+
+
+def op_attention_segs(kc, vc, q, k, v, n_heads, hs, max_seq, base, rows, n, pos0, n_step=0, one_query=False):
+    """one flm_batch_pass's attention: q, k, v [B, n_heads*hs], B = sum(n); segment s (n[s] consecutive rows) lies in the slot [base[s], base[s] + rows[s]) and enters at
+    logical position pos0[s]; the first n_step segments are step rows.  one_query: the one-query form although the multi-query one would fit.  kc, vc
+    [n_heads, max_seq, hs] are updated in place; returns out [B, n_heads*hs]."""
+    for a in (kc, vc):
+        assert a.dtype == np.float32 and a.flags.c_contiguous
+    b = np.ascontiguousarray(base, dtype=np.int32); rw = np.ascontiguousarray(rows, dtype=np.int32)
+    ns = np.ascontiguousarray(n, dtype=np.int32); ps = np.ascontiguousarray(pos0, dtype=np.int32)
+    if not len(b) == len(rw) == len(ns) == len(ps):
+        raise ValueError("op_attention_segs: base, rows, n and pos0 have one entry per segment")
+    q = np.ascontiguousarray(q, dtype=np.float32); k = np.ascontiguousarray(k, dtype=np.float32); v = np.ascontiguousarray(v, dtype=np.float32)
+    if not (q.ndim == 2 and q.shape == k.shape == v.shape and q.shape[1] == n_heads * hs):
+        raise ValueError("op_attention_segs: q, k, v are [B, n_heads*hs]")
+    out = np.empty_like(q)
+    _check(lib().flm_op_attention_segs(_p(out), _p(kc), _p(vc), _p(q), _p(k), _p(v), n_heads, hs, max_seq, int(q.shape[0]), len(b), int(n_step), _p(b), _p(rw), _p(ns), _p(ps),
+                                       1 if one_query else 0))
     return out
 
 

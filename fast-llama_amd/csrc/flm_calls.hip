@@ -1020,6 +1020,7 @@ int flm_batch_open(flm_ctx* c, const flm_batch_layout* layout) {
     c->batch_lay = lay;
     for (auto& s : c->batch_slot) s = flm_ctx::BatchSlot{};
     c->batch_open = true;
+    c->batch_passes = 0;
     return FLM_OK;
 }
 // the result block's trip back behind the accept step (the error word rides along: xwg_check looks at it next)
@@ -1041,7 +1042,7 @@ int flm_batch_join(flm_ctx* c, int slot, const flm_batch_req* q, int32_t* first_
     const flm_batch_layout& lay = c->batch_lay;
     if (slot < 0 || slot >= lay.n_slots) return fail(c, FLM_ERR_INVALID, "batch_join: slot outside the layout");
     flm_ctx::BatchSlot& b = c->batch_slot[slot];
-    if (b.live) return fail(c, FLM_ERR_INVALID, "batch_join: the slot's sequence is still running");
+    if (b.live || b.filling) return fail(c, FLM_ERR_INVALID, "batch_join: the slot's sequence is still running, or still taking in its prompt");
     if (!q->prompt || q->n_prompt < 1 || q->max_tokens < 1 || (long long)q->n_prompt + q->max_tokens - 1 > lay.rows[slot] || q->n_prompt > c->pf_cap || q->n_prompt > c->prompt_cap)
         return fail(c, FLM_ERR_INVALID, "batch_join: n_prompt >= 1, max_tokens >= 1, n_prompt + max_tokens - 1 <= the slot's rows");
     if (!(q->temperature >= 0.0f) || q->topp != q->topp || q->stop_token >= c->d.vocab_size)
@@ -1067,6 +1068,7 @@ int flm_batch_join(flm_ctx* c, int slot, const flm_batch_req* q, int32_t* first_
         b.used = true; b.live = true; b.pos = n; b.max_tokens = q->max_tokens; b.stop = stop; b.temp = q->temperature; b.topp = q->topp;
         batch_take(c, slot, so);
         *first_token = b.last; *live = b.live ? 1 : 0;
+        c->batch_passes += 1;
     });
 }
 int flm_batch_step(flm_ctx* c, flm_batch_out* out) {
@@ -1102,6 +1104,137 @@ int flm_batch_step(flm_ctx* c, flm_batch_out* out) {
         for (int i = 0; i < B; ++i) { c->batch_slot[f.slot[i]].pos += 1; batch_take(c, f.slot[i], so); }     // (the fed id's row is in the cache; the drawn one is the next to feed)
         for (int s = 0; s < FLM_BATCH_MAX; ++s) out->ids[s] = so.ids[s];
         out->live = so.live; out->finished = so.finished;
+        c->batch_passes += 1;
+    });
+}
+// Ragged passes (include/flm_gpu.h; kernels: flm_segs.h; the batch pass: flm_prompt.hip prefill_batched with a SegDesc).  The scheduling rule is pure host arithmetic
+// and written here alone: every running slot's one step row first, in slot order; then the filling slots in ascending slot order, each min(pending, what is left of
+// the budget) rows of its prompt; a slot that gets no rows has no segment
+int flm_batch_plan_for(int n_slots, const int32_t* fed, const int32_t* pending, uint32_t running, int prompt_rows_max, flm_batch_plan* out) {
+    if (!out || !fed || !pending) return FLM_ERR_INVALID;
+    const char* why = nullptr;
+    if (n_slots < 1 || n_slots > FLM_BATCH_MAX) why = "batch_plan: n_slots outside 1 .. FLM_BATCH_MAX";
+    else if (prompt_rows_max < 0) why = "batch_plan: a negative budget of prompt rows";
+    else if (n_slots < 32 && (running >> n_slots) != 0) why = "batch_plan: a running slot outside the layout";
+    for (int s = 0; !why && s < n_slots; ++s) {
+        if (fed[s] < 0 || pending[s] < 0 || (long long)fed[s] + pending[s] > 0x7fffffffLL) why = "batch_plan: fed and pending are row counts";
+        else if (((running >> s) & 1u) && pending[s] > 0) why = "batch_plan: a slot cannot run and take in its prompt at once";
+    }
+    if (why) { g_last_error = why; return FLM_ERR_INVALID; }
+    flm_batch_plan p{};
+    for (int s = 0; s < n_slots; ++s) {
+        if (!((running >> s) & 1u)) continue;
+        flm_batch_seg& g = p.seg[p.n_segs++];
+        g.slot = s; g.row0 = p.n_rows; g.n = 1; g.pos0 = fed[s]; g.draws = 1;
+        p.n_rows += 1; p.n_step += 1; p.n_draws += 1;
+    }
+    long long budget = prompt_rows_max > 0 ? prompt_rows_max : 0x7fffffffLL;
+    for (int s = 0; s < n_slots && budget > 0; ++s) {
+        if (pending[s] < 1) continue;
+        const int n = pending[s] < budget ? pending[s] : (int)budget;
+        if ((long long)p.n_rows + n > 0x7fffffffLL) { g_last_error = "batch_plan: more rows than an int holds"; return FLM_ERR_INVALID; }
+        flm_batch_seg& g = p.seg[p.n_segs++];
+        g.slot = s; g.row0 = p.n_rows; g.n = n; g.pos0 = fed[s]; g.draws = n == pending[s] ? 1 : 0;
+        p.n_rows += n; p.n_draws += g.draws; budget -= n;
+    }
+    *out = p;
+    return FLM_OK;
+}
+int flm_batch_admit(flm_ctx* c, int slot, const flm_batch_req* q) {
+    if (!c || !q) return FLM_ERR_INVALID;
+    int r = batch_ready(c, "batch_admit"); if (r) return r;
+    const flm_batch_layout& lay = c->batch_lay;
+    if (slot < 0 || slot >= lay.n_slots) return fail(c, FLM_ERR_INVALID, "batch_admit: slot outside the layout");
+    flm_ctx::BatchSlot& b = c->batch_slot[slot];
+    if (b.live || b.filling) return fail(c, FLM_ERR_INVALID, "batch_admit: the slot's sequence is still running, or still taking in its prompt");
+    if (!q->prompt || q->n_prompt < 1 || q->max_tokens < 1 || (long long)q->n_prompt + q->max_tokens - 1 > lay.rows[slot] || q->n_prompt > c->pf_cap || q->n_prompt > c->prompt_cap)
+        return fail(c, FLM_ERR_INVALID, "batch_admit: n_prompt >= 1, max_tokens >= 1, n_prompt + max_tokens - 1 <= the slot's rows");
+    if (!(q->temperature >= 0.0f) || q->topp != q->topp || q->stop_token >= c->d.vocab_size)
+        return fail(c, FLM_ERR_INVALID, "batch_admit: temperature >= 0, top-p a number, stop_token < vocab_size (or -1)");
+    if (!ids_in_vocab(c, q->prompt, q->n_prompt)) return fail(c, FLM_ERR_INVALID, "token id out of range");
+    if (q->temperature != 0.0f && !sample_supported(c)) return fail(c, FLM_ERR_UNSUPPORTED, "device sampler: vocabulary too large for one workgroup's LDS (sample on the host)");
+    b = flm_ctx::BatchSlot{};
+    b.filling = true; b.prompt = q->prompt; b.n_prompt = q->n_prompt; b.fed = 0;
+    b.max_tokens = q->max_tokens; b.stop = q->stop_token < 0 ? -1 : q->stop_token; b.temp = q->temperature; b.topp = q->topp; b.rng = (unsigned long long)q->rng_state;
+    return FLM_OK;
+}
+int flm_batch_pass(flm_ctx* c, int prompt_rows_max, flm_batch_pass_out* out) {
+    if (!c || !out) return FLM_ERR_INVALID;
+    int r = batch_ready(c, "batch_pass"); if (r) return r;
+    if (prompt_rows_max < 0) return fail(c, FLM_ERR_INVALID, "batch_pass: a negative budget of prompt rows");
+    const flm_batch_layout& lay = c->batch_lay;
+    int32_t fed[FLM_BATCH_MAX] = {0}, pending[FLM_BATCH_MAX] = {0};
+    uint32_t running = 0, filling = 0;
+    for (int s = 0; s < lay.n_slots; ++s) {
+        const flm_ctx::BatchSlot& b = c->batch_slot[s];
+        if (b.live) { running |= 1u << s; fed[s] = b.pos; }
+        else if (b.filling) { filling |= 1u << s; fed[s] = b.fed; pending[s] = b.n_prompt - b.fed; }
+    }
+    for (int s = 0; s < FLM_BATCH_MAX; ++s) out->ids[s] = -1;
+    out->live = 0; out->finished = 0; out->filling = 0;
+    if (!running && !filling) return FLM_OK;
+    flm_batch_plan plan{};
+    if (flm_batch_plan_for(lay.n_slots, fed, pending, running, prompt_rows_max, &plan)) { c->err = g_last_error; return FLM_ERR_INVALID; }
+    const int B = plan.n_rows, L = plan.n_step;
+    if (B > c->pf_cap || B > c->prompt_cap) return fail(c, FLM_ERR_INVALID, "batch_pass: more rows than max_seq_len");
+    // the pass's geometry, the step rows' SlotDesc, and the draw rows: the step rows, then the last row of every segment that completes its prompt (gathered behind them)
+    SegDesc sg{}; SlotDesc fs{}; SlotDesc fd{}; SlotIn in_step{}; SlotIn in{}; GatherDesc ga{};
+    sg.n_segs = plan.n_segs; sg.n_step = L; ga.dst0 = L;
+    in.live = running;
+    for (int i = 0; i < plan.n_segs; ++i) {
+        const flm_batch_seg& g = plan.seg[i];
+        const flm_ctx::BatchSlot& b = c->batch_slot[g.slot];
+        sg.slot[i] = g.slot; sg.row0[i] = g.row0; sg.n[i] = g.n; sg.base[i] = lay.base[g.slot]; sg.pos0[i] = g.pos0; sg.rows[i] = lay.rows[g.slot];
+        if (i < L) {
+            fs.slot[i] = g.slot; fs.base[i] = lay.base[g.slot]; fs.pos[i] = b.pos; fs.rows[i] = lay.rows[g.slot]; fs.n = i + 1;
+            in_step.ids[i] = b.last;
+        } else {
+            memcpy(c->pass_ids.data() + (g.row0 - L), b.prompt + g.pos0, sizeof(int32_t) * (size_t)g.n);
+        }
+        if (!g.draws) continue;
+        const int j = fd.n++;                                        // the draw's row: a SlotIn / SlotDesc of the draw rows
+        fd.slot[j] = g.slot; fd.base[j] = lay.base[g.slot]; fd.pos[j] = g.pos0 + g.n - 1; fd.rows[j] = lay.rows[g.slot];
+        in.ids[j] = i < L ? b.last : b.prompt[b.n_prompt - 1]; in.rng[j] = b.rng; in.temp[j] = b.temp; in.topp[j] = b.topp; in.stop[j] = b.stop;
+        in.left[j] = b.max_tokens - b.n_out;
+        in.live |= 1u << g.slot;
+        if (i >= L) ga.src[ga.n++] = g.row0 + g.n - 1;
+    }
+    const int D = fd.n;                                              // (= plan.n_draws; 0: a pass of unfinished chunks -- the cache rows only, nothing is classified)
+    const bool skinny = c->spec_gemm != 0 && B <= kSkinnyTokens;
+    int chunk = 1; float* const stage = score_stage(c, &chunk);
+    SlotOut so{};
+    return with_retry(c, B, [&]() -> int {
+        int r = FLM_OK;
+        if (B > L) { r = h2d(c, c->prompt_dev + L, c->pass_ids.data(), sizeof(int) * (size_t)(B - L)); if (r) return r; }
+        if (L > 0) {
+            hipLaunchKernelGGL(k_slots_load, dim3(1), dim3(64), 0, c->stream, in_step, L, c->prompt_dev);
+            HIPC(c, hipGetLastError());
+        }
+        r = prefill_batched_qt(c, B, 0, D > 0, skinny, nullptr, 0, L > 0 ? &fs : nullptr, &sg); if (r) return r;
+        if (ga.n > 0) {
+            hipLaunchKernelGGL(k_gather_rows, dim3(1), dim3(256), 0, c->stream, c->pf_x, c->d.dim, ga);
+            HIPC(c, hipGetLastError());
+        }
+        for (int r0 = 0; r0 < D; r0 += chunk) {
+            const int m = D - r0 < chunk ? D - r0 : chunk;
+            r = batch_classify(c, r0, r0, m, stage, skinny, in); if (r) return r;
+        }
+        return batch_accept(c, in, fd, &so);       // (D == 0: every slot delivers -1, live = the running slots; the one trip back carries the error word)
+    }, [&] {
+        for (int i = 0; i < plan.n_segs; ++i) {
+            const flm_batch_seg& g = plan.seg[i];
+            flm_ctx::BatchSlot& b = c->batch_slot[g.slot];
+            if (i < L) { b.pos += 1; batch_take(c, g.slot, so); continue; }     // (the fed id's row is in the cache; the drawn one is the next to feed)
+            b.fed += g.n;
+            if (!g.draws) continue;
+            b.filling = false; b.prompt = nullptr; b.used = true; b.live = true; b.pos = b.n_prompt;     // the prompt is in: the slot runs from the next pass on ...
+            batch_take(c, g.slot, so);                                                                   // ... unless token 0 ended it
+        }
+        uint32_t still = 0;
+        for (int s = 0; s < lay.n_slots; ++s) if (c->batch_slot[s].filling) still |= 1u << s;
+        for (int s = 0; s < FLM_BATCH_MAX; ++s) out->ids[s] = so.ids[s];
+        out->live = so.live; out->finished = so.finished; out->filling = still;
+        c->batch_passes += 1;
     });
 }
 int flm_batch_state(flm_ctx* c, int slot, uint64_t* rng_state, int* n_out, int* stop_reason) {
@@ -1118,7 +1251,8 @@ int flm_batch_close(flm_ctx* c, int keep_slot) {
     if (!c) return FLM_ERR_INVALID;
     if (keep_slot < 0) { c->batch_open = false; return FLM_OK; }
     int r = batch_ready(c, "batch_close"); if (r) return r;
-    if (keep_slot >= c->batch_lay.n_slots || !c->batch_slot[keep_slot].used) return fail(c, FLM_ERR_INVALID, "batch_close: keep_slot outside the layout, or a slot that never held a sequence");
+    if (keep_slot >= c->batch_lay.n_slots || !c->batch_slot[keep_slot].used || c->batch_slot[keep_slot].filling)
+        return fail(c, FLM_ERR_INVALID, "batch_close: keep_slot outside the layout, a slot that never held a sequence, or one that is still taking in its prompt");
     const int base = c->batch_lay.base[keep_slot], len = c->batch_slot[keep_slot].pos;      // (pos: the rows the sequence has in the cache = n_prompt + n_out - 1)
     c->batch_open = false;
     // rows [base, base + len) -> [0, len).  base < len: source and destination overlap -- chunks of at most `base` rows, ascending, each launch's ranges disjoint (a chunk's
@@ -1147,6 +1281,22 @@ int flm_generate_batch(flm_ctx* c, const flm_batch_req* reqs, int n, flm_fan_cb 
     bool cancelled = false;
     unsigned live_mask = 0;
     for (int j = 0; j < n; ++j) n_out[j] = 0;
+    if (c->batch_rows >= 0) {      // option "batch_rows": every request admitted, then ragged passes until nobody runs or fills; callbacks in (pass, slot) order
+        for (int j = 0; j < n; ++j) { r = flm_batch_admit(c, j, &reqs[j]); if (r) { c->batch_open = false; return r; } }
+        unsigned busy = 1;
+        while (busy && !cancelled) {
+            flm_batch_pass_out po{};
+            r = flm_batch_pass(c, c->batch_rows, &po); if (r) { c->batch_open = false; return r; }
+            for (int j = 0; j < n; ++j) {
+                if (po.ids[j] < 0) continue;
+                const int index = n_out[j];
+                out_tokens[(size_t)j * stride + index] = po.ids[j]; n_out[j] = index + 1;
+                if (cb && !cancelled && cb(user, j, index, po.ids[j], (po.finished >> j) & 1u ? 1 : 0) != 0) cancelled = true;
+            }
+            busy = po.live | po.filling;
+        }
+    }
+    else
     for (int j = 0; j < n && !cancelled; ++j) {
         int32_t id = -1; int live = 0;
         r = flm_batch_join(c, j, &reqs[j], &id, &live); if (r) { c->batch_open = false; return r; }

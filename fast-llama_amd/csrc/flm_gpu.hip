@@ -343,6 +343,8 @@ int alloc_run_bufs(flm_ctx* c) {
     HIPC(c, dev_alloc(c, &c->fan_res, sizeof(FanOut), true));
     HIPC(c, dev_alloc(c, &c->batch_res, sizeof(SlotOut), true));                            // flm_batch_join / flm_batch_step: the result block
     HIPC(c, dev_alloc(c, &c->batch_views, sizeof(AttnArgs) * kBatchMax, true));            // ... and k_attn_slots' views
+    HIPC(c, dev_alloc(c, &c->seg_views, sizeof(AttnArgs) * kBatchMax, true));              // flm_batch_pass: the prompt segments' views (flm_segs.h)
+    c->pass_ids.assign((size_t)d.max_seq_len, 0);                                          // ... and the host's gather of a pass's prompt ids
     c->bounce_bytes = (size_t)d.vocab_size * 4; if (c->bounce_bytes < sizeof(ScoreRow) * (size_t)d.max_seq_len) c->bounce_bytes = sizeof(ScoreRow) * (size_t)d.max_seq_len;   // (a row of logits | max_seq_len ids | max_seq_len flm_score: each one trip)
     HIPC(c, hipHostMalloc((void**)&c->bounce, c->bounce_bytes + 64, hipHostMallocDefault));          // (+ a line for the error word that rides along: d2h)
     HIPC(c, hipHostMalloc((void**)&c->shape_stage, sizeof(ShapeParams), hipHostMallocDefault));   // (the shaper's parameter block on its way to the device: set_shape)
@@ -797,6 +799,7 @@ int flm_set_option(flm_ctx* c, const char* key, int value) {
         c->p2p = value ? 1 : 0;
     }
     else if (k == "spec_gemm") { c->spec_gemm = value ? 1 : 0; return FLM_OK; }      // (read per call by the new entry points only: no captured graph depends on it)
+    else if (k == "batch_rows") { c->batch_rows = value < 0 ? -1 : value; return FLM_OK; }      // (read per flm_generate_batch call: no captured graph depends on it)
     else if (kAblate && k == "ablate") c->ablate = value;              // FLM_ABLATE builds only: a product library cannot skip work
     else if (kAblate && k == "trace") {   // value = kernel class to trace (KC_*), -1 off
         c->trace_class = value;
@@ -866,6 +869,7 @@ int flm_query(flm_ctx* c, const char* key, int* value) {
         {"spec_steps", c->spec_steps},
         {"spec_accepted", c->spec_accepted},
         {"draft_tokens", c->draft_tokens},
+        {"batch_passes", c->batch_passes},
         // which hand-offs of the token's launch (short contexts) are consumed in arrival order; -1: that launch was not planned (yet)
         {"ao_active", c->la_ok[0] ? (c->la_p[0].ao_o ? 1 : 0) | (c->la_p[0].ao_2 ? 2 : 0) : -1},
         {"token_path", (c->world == 1 ? path : 0) | (c->attn_split ? 64 : 0)},

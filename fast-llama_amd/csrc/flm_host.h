@@ -222,9 +222,16 @@ struct flm_ctx {
     // cache slots (include/flm_gpu.h flm_batch_*; flm_calls.hip; kernels: flm_batch.h): the open batch's layout, what the host holds of every slot between two steps, and
     // the step's result block in device memory since create (the drawn ids and the states behind the draws share the fan's two arrays).  batch_open: until flm_batch_close
     // or the next call of another entry point that writes the cache
-    struct BatchSlot { bool used = false, live = false; int pos = 0, last = 0, n_out = 0, max_tokens = 0, stop = -1, reason = 0; float temp = 0.0f, topp = 0.0f; unsigned long long rng = 0; };
+    // A FILLING slot (flm_batch_admit): admitted, its prompt not yet wholly in the cache -- prompt (the CALLER's ids: valid until the slot has delivered its token 0),
+    // n_prompt, and fed = the rows flm_batch_pass has verified so far; it turns into a running slot behind the pass that feeds its last row
+    struct BatchSlot { bool used = false, live = false; int pos = 0, last = 0, n_out = 0, max_tokens = 0, stop = -1, reason = 0; float temp = 0.0f, topp = 0.0f; unsigned long long rng = 0;
+                       bool filling = false; const int32_t* prompt = nullptr; int n_prompt = 0, fed = 0; };
     flm_batch_layout batch_lay{}; BatchSlot batch_slot[FLM_BATCH_MAX]; bool batch_open = false; flm::SlotOut* batch_res = nullptr;
     flm::AttnArgs* batch_views = nullptr;              // ... and the rows' views of the cache for k_attn_slots [FLM_BATCH_MAX], rewritten in front of every layer's attention
+    flm::AttnArgs* seg_views = nullptr;                // ... the prompt segments' views for k_attn_segs_mq / k_attn_segs [FLM_BATCH_MAX] (flm_segs.h), device memory since create
+    std::vector<int32_t> pass_ids;                     // flm_batch_pass: the pass's prompt rows gathered from the callers' prompts on their way to the device [max_seq_len], sized at create
+    int batch_rows = -1;                               // option "batch_rows": flm_generate_batch admits every request and runs flm_batch_pass(batch_rows) (-1: serial joins, then steps)
+    int batch_passes = 0;                              // flm_query "batch_passes": weight passes (joins, steps, passes) since the last flm_batch_open
     int score_rows = 0;                                // option "score_rows": rows per classifier chunk of flm_score_tokens (0: as many as the staging holds; < 0: one row at a time through c->logits)
     std::map<GraphKey, hipGraphExec_t> graphs;        // the token graphs captured so far (flm_gpu.hip token_graph)
     std::vector<TimedLaunch>* timing = nullptr;
@@ -459,7 +466,7 @@ int feed(flm_ctx* c, const int32_t* tokens, int n, int pos, TokenForm last);
 int d2h(flm_ctx* c, void* dst, const void* src_dev, size_t bytes);
 float* score_stage(const flm_ctx* c, int* chunk);
 constexpr int kPrefillMin = 4;
-int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers = false, bool skinny = false, const flm::FanDesc* fan = nullptr, int row0 = 0, const flm::SlotDesc* slots = nullptr);      // (flm_prompt.hip; by the model's quant type.  all_layers: the last layer is completed too -- flm_score_tokens needs every row's final residual; skinny: int8 and B <= 16: every GEMM through k_gemm_q8_skinny -- the verify pass under "spec_gemm" 1; fan: the rows are a fan step's -- flm_generate_n; row0: the batch is a prompt entering the cache slot that starts at physical row row0 -- flm_batch_join; slots: the rows are a batch step's -- flm_batch_step)
+int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers = false, bool skinny = false, const flm::FanDesc* fan = nullptr, int row0 = 0, const flm::SlotDesc* slots = nullptr, const flm::SegDesc* segs = nullptr);      // (flm_prompt.hip; by the model's quant type.  all_layers: the last layer is completed too -- flm_score_tokens needs every row's final residual; skinny: int8 and B <= 16: every GEMM through k_gemm_q8_skinny -- the verify pass under "spec_gemm" 1; fan: the rows are a fan step's -- flm_generate_n; row0: the batch is a prompt entering the cache slot that starts at physical row row0 -- flm_batch_join; slots: the rows are a batch step's -- flm_batch_step; segs: a ragged pass -- flm_batch_pass: rows [0, n_step) are a step's (slots, where n_step > 0), the rest prompt segments)
 // a fan step's pieces (flm_prompt.hip; kernels: flm_fan.h).  fan_classify: rows [row0, row0 + m) through score_classify's prologue and GEMM into `stage`, then k_sample_fan
 // into fan_drawn / fan_after, row j with in.rng[j].  The launchers take c == null from the op-level mirror (flm_op_attention_fan)
 int fan_classify(flm_ctx* c, int row0, int m, float* stage, bool skinny, float temperature, float topp, const flm::FanIn& in);
@@ -470,6 +477,12 @@ int launch_sample_fan(flm_ctx* c, hipStream_t st, const float* logits, int ld, i
 int batch_classify(flm_ctx* c, int src_row0, int row0, int m, float* stage, bool skinny, const flm::SlotIn& in);
 int launch_attn_slots(flm_ctx* c, hipStream_t st, const flm::AttnArgs& aa, const flm::SlotDesc& f, int heads, int row_stride, flm::AttnArgs* views);
 int launch_rope_kv_slots(flm_ctx* c, hipStream_t st, const float* qkv, float* qout, float* kcache, float* vcache, const float* rope_cos, const float* rope_sin, int dim, int hs, int kv_rows, const flm::SlotDesc& f);
+// a ragged pass's pieces (flm_prompt.hip; kernels: flm_segs.h) for the prompt segments [n_step, n_segs) of f; q / out / qkv are the WHOLE batch's (the views move them);
+// one_query: k_attn_segs although the multi-query form would fit; views: device memory for 16 AttnArgs.  seg_check: null, or what is wrong with f as a pass of B rows
+// over a cache of max_seq rows.  c may be null (flm_op_attention_segs)
+const char* seg_check(const flm::SegDesc& f, int B, int max_seq);
+int launch_attn_segs(flm_ctx* c, hipStream_t st, const flm::AttnArgs& aa, const flm::SegDesc& f, int heads, int row_stride, flm::AttnArgs* views, bool one_query);
+int launch_rope_kv_segs(flm_ctx* c, hipStream_t st, const float* qkv, float* qout, float* kcache, float* vcache, const float* rope_cos, const float* rope_sin, int dim, int hs, int kv_rows, const flm::SegDesc& f, int B);
 int launch_attn_fan(flm_ctx* c, hipStream_t st, const flm::AttnArgs& aa, const flm::FanDesc& f, int heads, int row_stride);
 int launch_rope_kv_fan(flm_ctx* c, hipStream_t st, const float* qkv, float* qout, float* kcache, float* vcache, const float* rope_cos, const float* rope_sin, int dim, int hs, int kv_rows, const flm::FanDesc& f);
 // flm_score_tokens' classifier stage (flm_prompt.hip): rows [row0, row0 + m) of the batch's final residual (pf_x) -> output norm, quantize, the classifier GEMM tiles into

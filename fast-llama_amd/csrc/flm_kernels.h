@@ -57,11 +57,13 @@
 //                         pass -- every row attends the shared prompt rows followed by its own tail, and is drawn with its own sampler state
 //   k_rope_kv_slots, k_attn_slots, k_sample_slots, k_batch_accept  (flm_batch.h) cache slots (flm_batch_*): up to 16 independent sequences as ONE batch per weight pass --
 //                         every row at its own position in its own region of the one cache, drawn with its own sampler parameters and state
+//   k_rope_kv_segs, k_seg_views, k_attn_segs_mq, k_attn_segs, k_gather_rows  (flm_segs.h) ragged passes over the slots (flm_batch_admit / flm_batch_pass): prompt chunks of
+//                         several slots, each at its own position, in the same batch as the running slots' step rows
 // plus small op-level kernels that expose the same __device__ functions to the parity tests.
 // (Round 3's weight-streaming engine -- loader / consumer waves around an LDS ring -- was measured slower than these launches and left the library in round 4:
 //  tools/experiments/engine/, numbers in profiles/r03_engine_timelines.txt.)
 //
-// The code lives in: flm_math.h (exact scalar / wave building blocks), flm_wait.h (every cross-workgroup wait: flag polls, granule pieces, the give-up policy), flm_gemv.h, flm_attn.h, flm_layer.h, flm_prefill.h, flm_misc.h, flm_sample.h, flm_score.h, flm_logprob.h, flm_spec.h, flm_stop.h, flm_fan.h, flm_batch.h, flm_entropy.h (with flm_logf.h, the logarithm the host compiles too).
+// The code lives in: flm_math.h (exact scalar / wave building blocks), flm_wait.h (every cross-workgroup wait: flag polls, granule pieces, the give-up policy), flm_gemv.h, flm_attn.h, flm_layer.h, flm_prefill.h, flm_misc.h, flm_sample.h, flm_score.h, flm_logprob.h, flm_spec.h, flm_stop.h, flm_fan.h, flm_batch.h, flm_segs.h, flm_entropy.h (with flm_logf.h, the logarithm the host compiles too).
 #pragma once
 #include "flm_math.h"
 #include "flm_wait.h"
@@ -79,3 +81,4 @@
 #include "flm_spec.h"
 #include "flm_fan.h"
 #include "flm_batch.h"
+#include "flm_segs.h"

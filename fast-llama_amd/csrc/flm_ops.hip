@@ -500,6 +500,49 @@ int flm_op_attention_slots(float* out, float* kc, float* vc, const float* q, con
     return FLM_OK;
 }
 
+// one flm_batch_pass's RoPE / cache rows / attention on caller-supplied caches: the launches prefill_batched makes with a SegDesc (flm_prompt.hip)
+int flm_op_attention_segs(float* out, float* kc, float* vc, const float* q, const float* k, const float* v,
+                          int n_heads, int hs, int max_seq, int B, int n_segs, int n_step, const int32_t* base, const int32_t* rows, const int32_t* n, const int32_t* pos0,
+                          int one_query) {
+    if (!out || !kc || !vc || !q || !k || !v || !base || !rows || !n || !pos0 || n_heads < 1 || hs < 32 || hs > 256 || hs % 8 || max_seq < 1 || B < 1 ||
+        n_segs < 1 || n_segs > FLM_BATCH_MAX || n_step < 0 || n_step > n_segs) return FLM_ERR_INVALID;
+    SegDesc f{}; f.n_segs = n_segs; f.n_step = n_step;
+    SlotDesc fs{}; fs.n = n_step;
+    int top = 0;
+    for (int s = 0, at = 0; s < n_segs; ++s) {
+        f.slot[s] = s; f.row0[s] = at; f.n[s] = n[s]; f.base[s] = base[s]; f.pos0[s] = pos0[s]; f.rows[s] = rows[s];
+        if (n[s] < 1 || (long long)at + n[s] > B) return FLM_ERR_INVALID;
+        at += n[s];
+        if (s < n_step) { fs.slot[s] = s; fs.base[s] = base[s]; fs.pos[s] = pos0[s]; fs.rows[s] = rows[s]; }
+        if (pos0[s] >= 0 && (long long)pos0[s] + n[s] <= max_seq) top = pos0[s] + n[s] > top ? pos0[s] + n[s] : top;
+    }
+    if (seg_check(f, B, max_seq)) return FLM_ERR_INVALID;
+    const int dim = n_heads * hs;
+    const size_t nd = (size_t)B * dim, nc = (size_t)n_heads * max_seq * hs, h2 = hs / 2;
+    std::vector<float> cs, sn; build_rope_table(hs, top, cs, sn);
+    std::vector<float> qkv(3 * nd);
+    for (int j = 0; j < B; ++j) {
+        memcpy(&qkv[(size_t)j * 3 * dim], q + (size_t)j * dim, (size_t)dim * 4); memcpy(&qkv[(size_t)j * 3 * dim + dim], k + (size_t)j * dim, (size_t)dim * 4);
+        memcpy(&qkv[(size_t)j * 3 * dim + 2 * dim], v + (size_t)j * dim, (size_t)dim * 4);
+    }
+    DevBuf dqkv, dq, dkc, dvc, dout, dc, dsn, dviews, dsviews;
+    if (dqkv.alloc(3 * nd * 4) || dq.alloc(nd * 4) || dkc.alloc(nc * 4) || dvc.alloc(nc * 4) || dout.alloc(nd * 4) || dc.alloc(top * h2 * 4) || dsn.alloc(top * h2 * 4) ||
+        dviews.alloc(sizeof(AttnArgs) * kBatchMax) || dsviews.alloc(sizeof(AttnArgs) * kBatchMax)) return FLM_ERR_OOM;
+    OPC(hipMemcpy(dqkv.p, qkv.data(), 3 * nd * 4, hipMemcpyHostToDevice));
+    OPC(hipMemcpy(dkc.p, kc, nc * 4, hipMemcpyHostToDevice)); OPC(hipMemcpy(dvc.p, vc, nc * 4, hipMemcpyHostToDevice));
+    OPC(hipMemcpy(dc.p, cs.data(), top * h2 * 4, hipMemcpyHostToDevice)); OPC(hipMemcpy(dsn.p, sn.data(), top * h2 * 4, hipMemcpyHostToDevice));
+    AttnArgs a{}; a.q = dq.as<float>(); a.kcache = dkc.as<float>(); a.vcache = dvc.as<float>(); a.out = dout.as<float>(); a.hs = hs; a.max_seq = max_seq;
+    int r = FLM_OK;
+    if (n_step > 0) { r = launch_rope_kv_slots(nullptr, 0, dqkv.as<float>(), dq.as<float>(), dkc.as<float>(), dvc.as<float>(), dc.as<float>(), dsn.as<float>(), dim, hs, max_seq, fs); if (r) return r; }
+    if (n_step < n_segs) { r = launch_rope_kv_segs(nullptr, 0, dqkv.as<float>(), dq.as<float>(), dkc.as<float>(), dvc.as<float>(), dc.as<float>(), dsn.as<float>(), dim, hs, max_seq, f, B); if (r) return r; }
+    if (n_step > 0) { r = launch_attn_slots(nullptr, 0, a, fs, n_heads, dim, dviews.as<AttnArgs>()); if (r) return r; }
+    if (n_step < n_segs) { r = launch_attn_segs(nullptr, 0, a, f, n_heads, dim, dsviews.as<AttnArgs>(), one_query != 0); if (r) return r; }
+    OPC(hipDeviceSynchronize());
+    OPC(hipMemcpy(out, dout.p, nd * 4, hipMemcpyDeviceToHost));
+    OPC(hipMemcpy(kc, dkc.p, nc * 4, hipMemcpyDeviceToHost)); OPC(hipMemcpy(vc, dvc.p, nc * 4, hipMemcpyDeviceToHost));
+    return FLM_OK;
+}
+
 /* elementary functions exactly as the kernels evaluate them (tests pin them against the host's IEEE results) */
 int flm_op_math(int fn, float* x, const float* y, size_t n) {
     if (!x || n == 0 || fn < 0 || fn > 5 || (fn >= 2 && !y)) return FLM_ERR_INVALID;

@@ -141,14 +141,67 @@ int launch_rope_kv_slots(flm_ctx* c, hipStream_t st, const float* qkv, float* qo
     return FLM_OK;
 }
 
+// A ragged pass's geometry (flm_segs.h), checked in front of the first launch (k_rope_kv_segs writes cache rows): the step rows first, one each; the prompt segments
+// behind them in batch order, each inside its slot, the slots inside the cache, the rows adding up to B
+const char* seg_check(const SegDesc& f, int B, int max_seq) {
+    if (f.n_segs < 1 || f.n_segs > kBatchMax || f.n_step < 0 || f.n_step > f.n_segs) return "segs: 1 .. 16 segments, the step rows first";
+    int at = 0;
+    for (int s = 0; s < f.n_segs; ++s) {
+        if (f.row0[s] != at || f.n[s] < 1 || (s < f.n_step && f.n[s] != 1)) return "segs: the segments' rows follow one another, a step segment has one row";
+        if (f.base[s] < 0 || f.rows[s] < 1 || (long long)f.base[s] + f.rows[s] > max_seq) return "segs: a slot outside the cache";
+        if (f.pos0[s] < 0 || (long long)f.pos0[s] + f.n[s] > f.rows[s]) return "segs: a segment outside its slot";
+        if ((long long)at + f.n[s] > B) return "segs: the segments' rows do not add up to the batch";
+        at += f.n[s];
+    }
+    return at == B ? nullptr : "segs: the segments' rows do not add up to the batch";
+}
+// k_seg_views + k_attn_segs_mq / k_attn_segs on the prompt segments of a ragged pass (flm_segs.h); the LDS of the largest slot among them
+int launch_attn_segs(flm_ctx* c, hipStream_t st, const AttnArgs& aa, const SegDesc& f, int heads, int row_stride, AttnArgs* views, bool one_query) {
+    {   // a long slot's score rows can take more than the default limit: raise the kernels' dynamic-LDS limit, once per device
+        static std::mutex mu; static bool done[64] = {false};
+        int dev = 0; HIPC(c, hipGetDevice(&dev));
+        std::lock_guard<std::mutex> lk(mu);
+        if (dev >= 0 && dev < 64 && !done[dev]) {
+            HIPC(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_segs_mq), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
+            HIPC(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_segs), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
+            done[dev] = true;
+        }
+    }
+    if (aa.hs > 256 || aa.hs % 8 || aa.n_peer || !views || f.n_step >= f.n_segs) return fail(c, FLM_ERR_INVALID, "attn_segs: head size <= 256, one GPU, at least one prompt segment");
+    int largest = 0, groups = 0, P = 0;
+    for (int s = f.n_step; s < f.n_segs; ++s) {
+        largest = f.rows[s] > largest ? f.rows[s] : largest;
+        groups += (f.n[s] + kMqQueries - 1) / kMqQueries; P += f.n[s];
+    }
+    hipLaunchKernelGGL(k_seg_views, dim3(1), dim3(64), 0, st, aa, f, row_stride, views);
+    HIPC(c, hipGetLastError());
+    if (!one_query && aa.hs <= 128 && attn_mq_lds_bytes(largest, aa.hs) <= kLdsMax)      // kMqQueries queries of one sequence per workgroup share every K / V tile
+        hipLaunchKernelGGL(k_attn_segs_mq, dim3(heads, groups), dim3(kAttnBlock), attn_mq_lds_bytes(largest, aa.hs), st, (const AttnArgs*)views, f, row_stride);
+    else {
+        if (attn_lds_bytes(largest, aa.hs) > kLdsMax) return fail(c, FLM_ERR_UNSUPPORTED, "attn_segs: one query's scores do not fit the LDS");
+        hipLaunchKernelGGL(k_attn_segs, dim3(heads, P), dim3(kAttnBlock), attn_lds_bytes(largest, aa.hs), st, (const AttnArgs*)views, f, row_stride);
+    }
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
+int launch_rope_kv_segs(flm_ctx* c, hipStream_t st, const float* qkv, float* qout, float* kcache, float* vcache, const float* rope_cos, const float* rope_sin, int dim, int hs, int kv_rows, const SegDesc& f, int B) {
+    const int P = B - (f.n_step < f.n_segs ? f.row0[f.n_step] : B);
+    if (P < 1) return fail(c, FLM_ERR_INVALID, "rope_kv_segs: no prompt rows");
+    hipLaunchKernelGGL(k_rope_kv_segs, dim3(P), dim3(256), 0, st, qkv, qout, kcache, vcache, rope_cos, rope_sin, dim, hs, kv_rows, f);
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
+
 // all_layers (flm_score_tokens): the last layer runs to its end as well -- pf_x then holds every row's final residual, the classifier's input
 // fan (flm_generate_n; null: every launch is the one made without it): the B rows are the sequences of a fan step (flm_fan.h) -- `pos` is their one LOGICAL position, the
 // QKV GEMM takes the plain-store route with k_rope_kv_fan behind it, the attention is k_attn_fan; everything else is a row's own and stays what it is
 // row0 (flm_batch_join; 0: every launch is the one made without it): the batch is a prompt entering the cache slot whose region starts at physical row row0 -- the layer's
 // cache pointers move by row0 rows for every kernel that writes or reads them, the attention's bound shrinks to what lies behind row0; `pos` stays the LOGICAL position
 // slots (a flm_batch_step; null: as above): the B rows are the live slots' last ids, each at its own position in its own region -- the fan's route with k_rope_kv_slots and k_attn_slots
+// segs (a flm_batch_pass; null: every launch is the one made without it): a ragged pass (flm_segs.h) -- rows [0, n_step) are a step's rows (`slots` describes them, null
+// where n_step is 0) and keep the step's launches, the rest are prompt segments: k_rope_kv_segs and k_attn_segs_mq / k_attn_segs on the same q / out buffers
 template <int QT>
-int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req = false, const FanDesc* fan = nullptr, int row0 = 0, const SlotDesc* slots = nullptr) {
+int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req = false, const FanDesc* fan = nullptr, int row0 = 0, const SlotDesc* slots = nullptr, const SegDesc* segs = nullptr) {
     const bool skinny = skinny_req && QT == QT_INT8 && B <= kSkinnyTokens && c->world == 1;      // (the verify pass; int16: the tiles)
     const auto& d = c->d;
     const int L = d.n_layers, dim = d.dim, hid = d.hidden_dim, hs = c->hs;
@@ -185,6 +238,11 @@ int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req
             r = launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, skinny); if (r) return r;
             r = launch_rope_kv_fan(c, st, c->pf_qkv, c->pf_q, kc, vc, c->rope_cos, c->rope_sin, dimL, hs, c->kv_rows, *fan); if (r) return r;
         }
+        else if (segs) {
+            r = launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, skinny); if (r) return r;
+            if (segs->n_step > 0) { r = launch_rope_kv_slots(c, st, c->pf_qkv, c->pf_q, kc, vc, c->rope_cos, c->rope_sin, dimL, hs, c->kv_rows, *slots); if (r) return r; }
+            if (segs->n_step < B) { r = launch_rope_kv_segs(c, st, c->pf_qkv, c->pf_q, kc, vc, c->rope_cos, c->rope_sin, dimL, hs, c->kv_rows, *segs, B); if (r) return r; }
+        }
         else if (slots) {
             r = launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, skinny); if (r) return r;
             r = launch_rope_kv_slots(c, st, c->pf_qkv, c->pf_q, kc, vc, c->rope_cos, c->rope_sin, dimL, hs, c->kv_rows, *slots); if (r) return r;
@@ -210,6 +268,10 @@ int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req
         const bool mq_fits = attn_mq_lds_bytes(d.max_seq_len, hs) <= kLdsMax;
         const bool pv_mfma = c->use_pv_mfma && (hs & 1) == 0;
         if (fan) { r = launch_attn_fan(c, st, aa, *fan, c->heads_local, dim); if (r) return r; }
+        else if (segs) {
+            if (segs->n_step > 0) { r = launch_attn_slots(c, st, aa, *slots, c->heads_local, dim, c->batch_views); if (r) return r; }
+            if (segs->n_step < B) { r = launch_attn_segs(c, st, aa, *segs, c->heads_local, dim, c->seg_views, !c->use_prefill_mq); if (r) return r; }
+        }
         else if (slots) { r = launch_attn_slots(c, st, aa, *slots, c->heads_local, dim, c->batch_views); if (r) return r; }
         else if (hs <= 128 && c->use_prefill_mq && c->use_qk_mfma && c->pf_scores && (pv_mfma || mq_fits)) {
             // scores on the matrix cores (fp32 MFMA = the reference's chains, bit for bit), then softmax + weighted sum per tile of queries
@@ -271,7 +333,15 @@ int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req
 int launch_gemm_store(flm_ctx* c, hipStream_t st, int qt, const GemmArgs& g, int use_mfma) {
     return qt == FLM_QT_INT8 ? launch_gemm<QT_INT8, EPI_STORE>(c, st, g, use_mfma) : launch_gemm<QT_INT16, EPI_STORE>(c, st, g, use_mfma);
 }
-int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers, bool skinny, const FanDesc* fan, int row0, const SlotDesc* slots) {
+int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers, bool skinny, const FanDesc* fan, int row0, const SlotDesc* slots, const SegDesc* segs) {
+    if (segs) {   // (in front of the first launch: k_rope_kv_segs writes the rows' cache rows)
+        if (c->world != 1 || fan || row0 || pos || B > c->pf_cap || (segs->n_step > 0) != (slots != nullptr) || (slots && slots->n != segs->n_step))
+            return fail(c, FLM_ERR_INVALID, "prefill: a ragged pass is one GPU's, not a fan step, at row origin 0, within the batch buffers, its step rows described by a SlotDesc");
+        if (const char* why = seg_check(*segs, B, c->d.max_seq_len)) return fail(c, FLM_ERR_INVALID, why);
+        for (int r = 0; slots && r < slots->n; ++r)
+            if (slots->base[r] != segs->base[r] || slots->rows[r] != segs->rows[r] || slots->pos[r] != segs->pos0[r]) return fail(c, FLM_ERR_INVALID, "prefill: a ragged pass's step rows and its SlotDesc disagree");
+        return c->d.quant_type == FLM_QT_INT8 ? prefill_batched<QT_INT8>(c, B, 0, all_layers, skinny, nullptr, 0, slots, segs) : prefill_batched<QT_INT16>(c, B, 0, all_layers, skinny, nullptr, 0, slots, segs);
+    }
     if (fan && (c->world != 1 || fan->n != B || pos != fan->S + fan->t)) return fail(c, FLM_ERR_INVALID, "prefill: a fan step is one GPU's batch of fan.n rows at S + t");
     if ((row0 || slots) && (c->world != 1 || fan || row0 < 0 || (slots && (row0 || slots->n != B)) || row0 + pos + (slots ? 0 : B) > c->d.max_seq_len))
         return fail(c, FLM_ERR_INVALID, "prefill: a slot's batch is one GPU's, inside the cache, and not a fan step");

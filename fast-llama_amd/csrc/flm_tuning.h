@@ -49,6 +49,7 @@ constexpr OptionRow kOptions[] = {
     {"use_prefill", &flm_ctx::use_prefill, 0},
     {"score_rows", &flm_ctx::score_rows, 0},
     {"spec_gemm", &flm_ctx::spec_gemm, 0},
+    {"batch_rows", &flm_ctx::batch_rows, 0},
     {"use_mfma", &flm_ctx::use_mfma, kOptDial | kOptFrozen},
     {"use_pv_mfma", &flm_ctx::use_pv_mfma, kOptFrozen},
     {"use_qk_mfma", &flm_ctx::use_qk_mfma, kOptFrozen},

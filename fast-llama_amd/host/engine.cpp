@@ -225,7 +225,7 @@ bool GpuTransformer::generate_samples(const char* prompt, int n, uint64_t seed, 
     return true;
 }
 
-bool GpuTransformer::generate_prompts(const std::vector<std::string>& prompts, uint64_t seed, int max_new_tokens, float temperature, float topp, std::vector<std::string>& texts) {
+bool GpuTransformer::generate_prompts(const std::vector<std::string>& prompts, uint64_t seed, int max_new_tokens, float temperature, float topp, std::vector<std::string>& texts, int batch_rows) {
     texts.clear();
     const int n = (int)prompts.size();
     if (_ctxs.size() != 1) { _err = "--prompts: one device only"; return false; }
@@ -250,6 +250,7 @@ bool GpuTransformer::generate_prompts(const std::vector<std::string>& prompts, u
     }
     std::vector<int32_t> ids((size_t)n * want);
     std::vector<int> n_out(n, 0);
+    if (flm_set_option(_ctxs[0], "batch_rows", batch_rows < 0 ? -1 : batch_rows) != FLM_OK) { _err = std::string("--batch-rows: ") + flm_last_error(_ctxs[0]); return false; }
     const int rc = flm_generate_batch(_ctxs[0], reqs.data(), n, nullptr, nullptr, ids.data(), want, n_out.data(), nullptr);
     if (rc != FLM_OK) { _err = std::string("--prompts: ") + flm_last_error(_ctxs[0]); return false; }
     texts.resize(n);

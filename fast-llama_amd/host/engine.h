@@ -37,7 +37,8 @@ public:
     // --prompts FILE (this build only; one device, none of the other extras): 1 .. 16 INDEPENDENT prompts served together, one batch per pass over the weights
     // (flm_generate_batch).  Prompt j's sampler state is seed + j, every completion stops on token 0 by itself, and max_new_tokens is cut to an equal share of the cache.
     // texts[j]: what generate_samples(prompts[j], 1, seed + j, ...) gives
-    bool generate_prompts(const std::vector<std::string>& prompts, uint64_t seed, int max_new_tokens, float temperature, float topp, std::vector<std::string>& texts);
+    // batch_rows >= 0 (--batch-rows): option "batch_rows" -- the prompts are admitted and enter inside the steps' passes (flm_batch_pass); the same texts
+    bool generate_prompts(const std::vector<std::string>& prompts, uint64_t seed, int max_new_tokens, float temperature, float topp, std::vector<std::string>& texts, int batch_rows = -1);
     // --mode score (this build only): the prompt's tokens through flm_score_tokens in one call; one line per position (index, token id, argmax id, the probability of the
     // next token), then a summary line (token count, mean natural-log loss, perplexity, ms)
     bool score(const char* prompt);

@@ -41,6 +41,7 @@ struct Args {
     const char* bad_devices = nullptr;      // a --devices argument that did not parse
     int samples = 0; const char* bad_samples = nullptr;      // --samples N: 1..16 completions of the prompt (0 = off)
     const char* prompts_file = nullptr; std::vector<std::string> prompts;      // --prompts FILE: one prompt per line, 1..16 lines
+    int batch_rows = -1; const char* bad_batch_rows = nullptr;      // --batch-rows N (with --prompts): the prompts enter inside the steps' passes, at most N prompt rows per pass (0: no bound; -1 = off)
     int lookup_k = 0, lookup_g = 3;         // --lookup K[,G]: draft length (4..15; 0 = off) and longest n-gram (1..8) of the prompt-lookup drafter
     const char* bad_lookup = nullptr;
     int draft_k = 0, draft_g = 3;           // --draft K[,G]: the same drafter and ranges at whatever temperature the run has (-t 0: flm_generate_lookup, else flm_generate_lookup_sample)
@@ -79,6 +80,7 @@ void usage(const char* bin) {
     fprintf(stderr, "   --draft           <K[,G]>     on one device, at any temperature: draft K (4..15) tokens per step by prompt lookup (n-grams up to G, 1..8, default 3) and verify them in one pass, sampled rows drawn with the sampler's own coins; the same text (this build only)\n");
     fprintf(stderr, "   --draft-model     <file>      on one device, at any temperature: a second, small model of the same vocabulary (quantisation: the file's own or -q) drafts the K tokens of --draft (default 7) instead of the prompt lookup; the same text (this build only)\n");
     fprintf(stderr, "   --prompts         <FILE>      on one device: the file's lines (1..16, one prompt per line) as independent prompts served together, one batch per pass over the weights, the completions printed in the file's order, each behind a line `--- prompt j ---`; prompt j's sampler state is --seed + j; not with --samples or the other extras of this build (this build only)\n");
+    fprintf(stderr, "   --batch-rows      <N>         with --prompts: the prompts enter inside the steps' passes over the weights, at most N prompt rows per pass (0: no bound), instead of one pass per prompt; the same completions (this build only)\n");
     fprintf(stderr, "   --samples         <N>         on one device: N (1..16) completions of the prompt, all N drawn per pass over the weights, printed one after another, each behind a line `--- sample j ---`; sample j's sampler state is --seed + j (here --seed counts); not with the other extras of this build (this build only)\n");
     fprintf(stderr, "   --top-k           <integer>   keep the K most likely tokens, 0 = off (this build only)\n");
     fprintf(stderr, "   --min-p           <float>     drop tokens whose probability is below this fraction of the most likely one's, [0, 1), 0 = off (this build only)\n");
@@ -189,6 +191,7 @@ const Flag kFlags[] = {
         if (ok && *e == 0) { a.lookup_k = (int)k; a.lookup_g = (int)g; } else a.bad_lookup = v; }},
     {nullptr, "--draft",       true,  [](Args& a, const char* v) { if (!parse_draft(v, a.draft_k, a.draft_g)) a.bad_draft = v; }},                 // (this build only)
     {nullptr, "--prompts",     true,  [](Args& a, const char* v) { a.prompts_file = v; }},   // (this build only)
+    {nullptr, "--batch-rows",  true,  [](Args& a, const char* v) { char* e; const long k = strtol(v, &e, 10); if (e == v || *e || k < 0 || k > 1000000) a.bad_batch_rows = v; else a.batch_rows = (int)k; }},   // (this build only)
     {nullptr, "--samples",     true,  [](Args& a, const char* v) { char* e; const long k = strtol(v, &e, 10); if (e == v || *e || k < 1 || k > FLM_FAN_MAX) a.bad_samples = v; else a.samples = (int)k; }},   // (this build only)
     {nullptr, "--draft-model", true,  [](Args& a, const char* v) { a.draft_model = v; }},                                                                                          // (this build only)
     {nullptr, "--top-k",             true, [](Args& a, const char* v) { char* e; const long k = strtol(v, &e, 10); a.shape_set = true; if (e == v || *e || k < 0 || k > 0x7fffffff) a.bad_sampling = v; else a.shape.top_k = (int)k; }},   // (this build only)
@@ -241,6 +244,7 @@ void parse(Args& a, int argc, const char** argv) {
             fprintf(stderr, "Invalid --prompts file:\x1b[31m%s\x1b[0m (expected a readable file of 1 to 16 non-empty lines, one prompt per line)\n", a.prompts_file); usage(argv[0]); exit(-1);
         }
     }
+    if (a.bad_batch_rows) { fprintf(stderr, "Invalid --batch-rows:\x1b[31m%s\x1b[0m (expected a number of prompt rows per pass, 0 for no bound)\n", a.bad_batch_rows); usage(argv[0]); exit(-1); }
     if (a.bad_samples) { fprintf(stderr, "Invalid --samples:\x1b[31m%s\x1b[0m (expected a number of completions, 1 to 16)\n", a.bad_samples); usage(argv[0]); exit(-1); }
     if (a.bad_draft) { fprintf(stderr, "Invalid --draft:\x1b[31m%s\x1b[0m (expected K or K,G with 4 <= K <= 15 and 1 <= G <= 8)\n", a.bad_draft); usage(argv[0]); exit(-1); }
     if (!a.bad_sampling && a.mirostat == 2 && a.typical > 0.0f && a.typical < 1.0f) a.bad_sampling = "--typical together with --mirostat 2";
@@ -338,6 +342,10 @@ int main(int argc, const char** argv) {
         fprintf(stderr, "--prompts applies to --mode gen on one device, without --samples, --lookup / --draft / --draft-model, the sampling controls, --typical / --mirostat, --logprobs, the stop rules and --constraint\n");
         return -1;
     }
+    if (args.batch_rows >= 0 && !args.prompts_file) {          // (refused, not ignored: only flm_generate_batch reads the budget)
+        fprintf(stderr, "--batch-rows applies to --prompts only\n");
+        return -1;
+    }
     if (stop_set && args.devices.size() > 1) {                  // (refused, not ignored: where the output ends is what the caller asked for)
         fprintf(stderr, "--stop-ids / --stop-seq / --stop apply to one device only: they cannot be combined with --devices of more than one\n");
         return -1;
@@ -379,7 +387,7 @@ int main(int argc, const char** argv) {
 
     if (args.prompts_file) {      // (its own lines: the completions in the file's order; no summary line -- tools/batch_bench.py times this path's library calls)
         std::vector<std::string> texts;
-        if (!tf.generate_prompts(args.prompts, (uint64_t)(int64_t)args.seed, args.max_tokens, args.temp, args.topp, texts)) { fprintf(stderr, "%s\n", tf.error().c_str()); return 1; }
+        if (!tf.generate_prompts(args.prompts, (uint64_t)(int64_t)args.seed, args.max_tokens, args.temp, args.topp, texts, args.batch_rows)) { fprintf(stderr, "%s\n", tf.error().c_str()); return 1; }
         for (size_t j = 0; j < texts.size(); ++j) printf("--- prompt %zu ---\n%s\n", j, texts[j].c_str());
         return 0;
     }

@@ -403,7 +403,30 @@ int  flm_fan_keep(flm_ctx* ctx, int seq);
  *             (step, slot) order; a non-zero return ends the call behind that step ("stop_reason": cancel; else length where any sequence ran to max_tokens; else token).
  * Errors, with nothing launched and the cache untouched: FLM_ERR_INVALID for the checks above, a slot outside the layout, a join into a live slot; FLM_ERR_STATE without an open
  * batch; FLM_ERR_UNSUPPORTED for world > 1, for head sizes whose one-query attention does not fit the LDS, and for temperature > 0 where flm_decode_sample refuses.
- * Nothing is allocated in any of these calls: the result block exists since flm_ctx_create. */
+ * Nothing is allocated in any of these calls: the result block exists since flm_ctx_create.
+ *
+ * Ragged passes: requests enter INSIDE the steps' pass.  Between empty and running a slot can be FILLING: admitted, its prompt not yet wholly in the cache.
+ *   admit     join's checks (an empty slot -- neither running nor filling --, the lengths against the slot's rows, ids in the vocabulary, the sampler's bounds), then the
+ *             request is recorded and the slot is filling.  No launch, no allocation, nothing is copied: req->prompt MUST STAY VALID until the slot has delivered its
+ *             token 0 (req itself may go).
+ *   pass      ONE pass over the weights for a plan of at most 16 segments {slot, row0, n, pos0, draws}, at most one per slot: first every running slot's one step row
+ *             (a step's rows and kernels), then, in ascending slot order, a chunk of every filling slot's prompt -- min(pending, what is left of prompt_rows_max) rows
+ *             each, entering at the slot's logical position pos0 = the rows fed so far (csrc/flm_segs.h: k_rope_kv_segs, and k_attn_segs_mq, where eight consecutive
+ *             queries of ONE sequence share every K / V tile of that sequence's slot; head sizes above 128 and "use_prefill_mq" 0: one query per workgroup).
+ *             prompt_rows_max 0: no bound -- every filling slot's whole remainder.  A slot whose prompt completes draws its token 0 from the chunk's last row in the same
+ *             pass, runs from the next pass on, and is finished at once if token 0 is its stop token or max_tokens == 1.  ids[s]: the next id of a running slot, token 0
+ *             of a slot whose prompt completed in this pass, -1 otherwise; live: the running slots behind the pass; filling: the slots still filling; finished as in a
+ *             step.  Nobody running or filling: FLM_OK, nothing launched.  ONE host synchronisation; what the pass reads is launch arguments and ids uploaded inside the
+ *             retried region; the host's copy of a slot moves only behind a verified pass.  "spec_gemm" 1 and at most 16 rows in the pass: the skinny GEMM, as in a step.
+ *   flm_batch_plan_for  the scheduling rule above, pure host arithmetic and the one place it is written (flm_batch_pass calls it): fed[s] = the rows slot s has in the
+ *             cache (a running slot's position, a filling slot's rows fed so far), pending[s] = the prompt rows a filling slot still lacks (0: not filling), running =
+ *             the mask of running slots.  FLM_ERR_INVALID for n_slots outside 1 .. FLM_BATCH_MAX, a negative budget, negative counts, a slot both running and pending.
+ *   The contract is the one above, unchanged, whatever the budget is, however a prompt was cut into chunks, and whatever else ran, joined, filled or finished in the same
+ *   passes.  The calls mix: step leaves filling slots alone; join or admit into a filling or running slot, and close(keep) of a filling slot, answer FLM_ERR_INVALID;
+ *   flm_batch_state of a filling slot answers n_out 0, reason 0; a negative budget answers FLM_ERR_INVALID; FLM_ERR_STATE / FLM_ERR_UNSUPPORTED as for step.
+ *   flm_generate_batch under option "batch_rows" b >= 0: every request is admitted, then flm_batch_pass(b) until nobody runs or fills.  The results are the default's;
+ *   the callbacks come in (pass, slot) order -- with a bounded budget a slot can deliver its token 1 before a later slot delivers its token 0.
+ *   flm_query "batch_passes": the weight passes (joins, steps, passes) since the last flm_batch_open. */
 #define FLM_BATCH_MAX 16
 typedef struct flm_batch_layout { int32_t n_slots; int32_t base[FLM_BATCH_MAX], rows[FLM_BATCH_MAX]; } flm_batch_layout;
 typedef struct flm_batch_req { const int32_t* prompt; int32_t n_prompt, max_tokens; float temperature, topp;
@@ -417,6 +440,12 @@ int  flm_batch_join(flm_ctx* ctx, int slot, const flm_batch_req* req, int32_t* f
 int  flm_batch_step(flm_ctx* ctx, flm_batch_out* out);
 int  flm_batch_state(flm_ctx* ctx, int slot, uint64_t* rng_state, int* n_out, int* stop_reason);
 int  flm_batch_close(flm_ctx* ctx, int keep_slot /* -1: none */);
+typedef struct flm_batch_seg  { int32_t slot, row0 /* first batch row */, n /* rows */, pos0 /* logical position of its first row */, draws /* 1: its last row is drawn from */; } flm_batch_seg;
+typedef struct flm_batch_plan { int32_t n_segs, n_rows, n_step, n_draws; flm_batch_seg seg[FLM_BATCH_MAX]; } flm_batch_plan;
+typedef struct flm_batch_pass_out { int32_t ids[FLM_BATCH_MAX]; uint32_t live, finished, filling; } flm_batch_pass_out;
+int  flm_batch_plan_for(int n_slots, const int32_t* fed, const int32_t* pending, uint32_t running, int prompt_rows_max /* 0: no bound */, flm_batch_plan* out);
+int  flm_batch_admit(flm_ctx* ctx, int slot, const flm_batch_req* req);
+int  flm_batch_pass(flm_ctx* ctx, int prompt_rows_max /* 0: no bound */, flm_batch_pass_out* out);
 int  flm_generate_batch(flm_ctx* ctx, const flm_batch_req* reqs, int n, flm_fan_cb cb /* may be NULL */, void* user,
                         int32_t* out_tokens /* [n][stride] */, int stride, int* n_out /* [n] */, uint64_t* rng_out /* [n], may be NULL */);
 /* Constrained decoding: a token-level deterministic automaton masks the logits in front of the controls -- what "one of these strings", a JSON shape or a regular expression
@@ -622,6 +651,8 @@ int  flm_debug_read(flm_ctx* ctx, int what, int layer, float* out, size_t n);
  *   "score_rows"     n = flm_score_tokens runs its classifier on chunks of at most n rows (default 0: as many rows as the staging holds; < 0: one row at a time through the logits vector, the staging of a context without prefill scores)
  *   "spec_gemm"      1 = flm_verify_greedy / flm_generate_lookup and their sampled forms run the verify batch's int8 GEMMs on the skinny kernel for <= 16 rows (default 0: the prompt path's 64 x 64
  *                    tiles, until both forms have been timed on the device: DESIGN.md section 5e); the same bits; no other entry point looks at it
+ *   "batch_rows"     b >= 0 = flm_generate_batch admits every request and runs ragged passes with a budget of b prompt rows each (0: no bound); default -1: serial joins, then
+ *                    steps; the same results; read per call
  *   "use_prefill_mq" 0 = batched attention with one query per workgroup (default 1: eight)
  *   "use_qk_mfma" / "use_pv_mfma"  0 = prefill scores / softmax x V on VALU chains (default 1: v_mfma_f32_16x16x4_f32, the same bits)
  * Tensor parallel (set on every rank alike, before flm_p2p_export where noted):
@@ -745,6 +776,14 @@ int  flm_op_attention_fan(float* out, float* kc, float* vc, const float* q, cons
  * kc, vc as above (updated); out [n][n_heads*hs].  1 <= n <= FLM_BATCH_MAX, pos[r] >= 0, base[r] >= 0, base[r] + pos[r] < max_seq (FLM_ERR_INVALID otherwise). */
 int  flm_op_attention_slots(float* out, float* kc, float* vc, const float* q, const float* k, const float* v,
                             int n_heads, int hs, int max_seq, int n, const int32_t* base, const int32_t* pos);
+/* the same task for the B rows of one flm_batch_pass (csrc/flm_segs.h): n_segs <= FLM_BATCH_MAX segments whose rows follow one another in q, k, v [B][n_heads*hs], B = the
+ * sum of n[s].  Segment s lies in the slot [base[s], base[s] + rows[s]) and enters at logical position pos0[s]: row i of it is rotated at pos0[s] + i, its k / v go to cache
+ * row base[s] + pos0[s] + i, its query attends the slot's rows 0 .. pos0[s] + i.  The first n_step segments are step rows (n[s] = 1: k_rope_kv_slots + k_attn_slots), the
+ * rest prompt segments (k_rope_kv_segs + k_seg_views + k_attn_segs_mq; one_query != 0, head sizes above 128 or a multi-query LDS that does not fit: k_attn_segs).
+ * FLM_ERR_INVALID, with nothing launched, for more than FLM_BATCH_MAX segments, a segment outside its slot, a slot outside the cache, or a sum of n[s] other than B. */
+int  flm_op_attention_segs(float* out, float* kc, float* vc, const float* q, const float* k, const float* v,
+                           int n_heads, int hs, int max_seq, int B, int n_segs, int n_step, const int32_t* base, const int32_t* rows, const int32_t* n, const int32_t* pos0,
+                           int one_query);
 /* libm expf as the device evaluates it (the reference calls glibc expf in softmax_sisd and swiglu);
  * in place over n floats.  Lets the tests pin the device routine against glibc bit for bit. */
 int  flm_op_expf(float* x, size_t n);
