@@ -38,6 +38,7 @@ SYMBOLS = (
     "flm_fan_layout_for", "flm_generate_n", "flm_fan_keep", "flm_op_attention_fan",
     "flm_batch_layout_for", "flm_batch_open", "flm_batch_join", "flm_batch_step", "flm_batch_state", "flm_batch_close", "flm_generate_batch", "flm_op_attention_slots",
     "flm_batch_plan_for", "flm_batch_admit", "flm_batch_pass", "flm_op_attention_segs",
+    "flm_batch_layout_prefix_for", "flm_batch_open_prefix", "flm_generate_batch_prefix", "flm_op_attention_slots_prefix", "flm_op_attention_segs_prefix",
 )
 
 # flm_score (include/flm_gpu.h): one row of flm_score_tokens / flm_op_score_rows
@@ -714,9 +715,13 @@ class Ctx:
         """flm_fan_keep: move sequence `seq`'s tail of the last generate_n behind the shared rows; any entry point continues from pos + n_prompt + n_out[seq] - 1"""
         _check(lib().flm_fan_keep(self._h, int(seq)), self._h)
 
-    def batch_open(self, layout):
-        """flm_batch_open: divide the cache into the layout's slots (batch_layout) and empty them all; launches nothing"""
-        _check(lib().flm_batch_open(self._h, C.byref(layout)), self._h)
+    def batch_open(self, layout, prefix_rows=0):
+        """flm_batch_open: divide the cache into the layout's slots (batch_layout) and empty them all; launches nothing.  prefix_rows S > 0 (flm_batch_open_prefix): the
+        slots continue the conversation in the cache rows [0, S), which stay untouched; the layout is batch_layout(..., prefix_rows=S)"""
+        if int(prefix_rows) != 0:
+            _check(lib().flm_batch_open_prefix(self._h, C.byref(layout), int(prefix_rows)), self._h)
+        else:
+            _check(lib().flm_batch_open(self._h, C.byref(layout)), self._h)
 
     def batch_join(self, slot, req):
         """flm_batch_join: the request's prompt enters the empty slot `slot` -> (token 0, whether the slot is live behind it)"""
@@ -763,9 +768,10 @@ class Ctx:
         """flm_batch_close: end the batch; keep_slot >= 0: that slot's rows move to [0, len) and any entry point continues its conversation from pos = len"""
         _check(lib().flm_batch_close(self._h, int(keep_slot)), self._h)
 
-    def generate_batch(self, reqs, on_token=None):
+    def generate_batch(self, reqs, on_token=None, prefix_rows=0):
         """flm_generate_batch: the requests (BatchReq, 1 .. BATCH_MAX of them) served together, one batch per pass over the weights -> (a list of id arrays, the sampler
-        states after each request's draws).  on_token(seq, index, token, last) is called per delivered id; a truthy return ends the call behind that step."""
+        states after each request's draws).  on_token(seq, index, token, last) is called per delivered id; a truthy return ends the call behind that step.
+        prefix_rows S > 0 (flm_generate_batch_prefix): every request continues the conversation in the cache rows [0, S); its prompt is its own part"""
         reqs = list(reqs)
         n = len(reqs)
         if not 1 <= n <= BATCH_MAX:
@@ -783,7 +789,10 @@ class Ctx:
                 raised.append(e)
                 return 1
         cb = FAN_CB(tramp) if on_token is not None else C.cast(None, FAN_CB)
-        rc = lib().flm_generate_batch(self._h, arr, n, cb, None, _p(out), stride, _p(n_out), _p(st))
+        if int(prefix_rows) != 0:
+            rc = lib().flm_generate_batch_prefix(self._h, int(prefix_rows), arr, n, cb, None, _p(out), stride, _p(n_out), _p(st))
+        else:
+            rc = lib().flm_generate_batch(self._h, arr, n, cb, None, _p(out), stride, _p(n_out), _p(st))
         del cb, pairs
         if raised:
             raise raised[0]
@@ -1223,11 +1232,15 @@ def fan_layout(pos, n_prompt, max_tokens, n, max_seq_len) -> FanLayout:
     return out
 
 
-def batch_layout(rows, max_seq_len) -> BatchLayout:
-    """flm_batch_layout_for (pure host arithmetic): slot s owns the cache rows [base[s], base[s] + rows[s]), or FlmError where the layout is refused"""
+def batch_layout(rows, max_seq_len, prefix_rows=0) -> BatchLayout:
+    """flm_batch_layout_for (pure host arithmetic): slot s owns the cache rows [base[s], base[s] + rows[s]), or FlmError where the layout is refused.  prefix_rows S != 0
+    (flm_batch_layout_prefix_for): the slots lie behind S shared rows, base[0] = S"""
     r = np.ascontiguousarray(rows, dtype=np.int32).reshape(-1)
     out = BatchLayout()
-    _check(lib().flm_batch_layout_for(int(r.size), _p(r), int(max_seq_len), C.byref(out)))
+    if int(prefix_rows) != 0:
+        _check(lib().flm_batch_layout_prefix_for(int(prefix_rows), int(r.size), _p(r), int(max_seq_len), C.byref(out)))
+    else:
+        _check(lib().flm_batch_layout_for(int(r.size), _p(r), int(max_seq_len), C.byref(out)))
     return out
 
 
@@ -1260,6 +1273,39 @@ def op_attention_segs(kc, vc, q, k, v, n_heads, hs, max_seq, base, rows, n, pos0
     out = np.empty_like(q)
     _check(lib().flm_op_attention_segs(_p(out), _p(kc), _p(vc), _p(q), _p(k), _p(v), n_heads, hs, max_seq, int(q.shape[0]), len(b), int(n_step), _p(b), _p(rw), _p(ns), _p(ps),
                                        1 if one_query else 0))
+    return out
+
+
+def op_attention_segs_prefix(kc, vc, q, k, v, n_heads, hs, max_seq, prefix_rows, base, rows, n, pos0, n_step=0):
+    """op_attention_segs behind prefix_rows shared rows (flm_op_attention_segs_prefix): pos0 are logical positions and count them, base the slots' physical origins"""
+    for a in (kc, vc):
+        assert a.dtype == np.float32 and a.flags.c_contiguous
+    b = np.ascontiguousarray(base, dtype=np.int32); rw = np.ascontiguousarray(rows, dtype=np.int32)
+    ns = np.ascontiguousarray(n, dtype=np.int32); ps = np.ascontiguousarray(pos0, dtype=np.int32)
+    if not len(b) == len(rw) == len(ns) == len(ps):
+        raise ValueError("op_attention_segs_prefix: base, rows, n and pos0 have one entry per segment")
+    q = np.ascontiguousarray(q, dtype=np.float32); k = np.ascontiguousarray(k, dtype=np.float32); v = np.ascontiguousarray(v, dtype=np.float32)
+    if not (q.ndim == 2 and q.shape == k.shape == v.shape and q.shape[1] == n_heads * hs):
+        raise ValueError("op_attention_segs_prefix: q, k, v are [B, n_heads*hs]")
+    out = np.empty_like(q)
+    _check(lib().flm_op_attention_segs_prefix(_p(out), _p(kc), _p(vc), _p(q), _p(k), _p(v), n_heads, hs, max_seq, int(prefix_rows), int(q.shape[0]), len(b), int(n_step),
+                                              _p(b), _p(rw), _p(ns), _p(ps)))
+    return out
+
+
+def op_attention_slots_prefix(kc, vc, q, k, v, n_heads, hs, max_seq, prefix_rows, base, rows, pos):
+    """op_attention_slots behind prefix_rows shared rows (flm_op_attention_slots_prefix): row r at LOGICAL position pos[r] >= prefix_rows of the slot
+    [base[r], base[r] + rows[r]); its k / v go to cache row base[r] + pos[r] - prefix_rows"""
+    for a in (kc, vc):
+        assert a.dtype == np.float32 and a.flags.c_contiguous
+    b = np.ascontiguousarray(base, dtype=np.int32); rw = np.ascontiguousarray(rows, dtype=np.int32); ps = np.ascontiguousarray(pos, dtype=np.int32); n = len(b)
+    if not len(rw) == len(ps) == n:
+        raise ValueError("op_attention_slots_prefix: base, rows and pos have one entry per row")
+    q = np.ascontiguousarray(q, dtype=np.float32); k = np.ascontiguousarray(k, dtype=np.float32); v = np.ascontiguousarray(v, dtype=np.float32)
+    if not q.shape == k.shape == v.shape == (n, n_heads * hs):
+        raise ValueError("op_attention_slots_prefix: q, k, v are [n, n_heads*hs]")
+    out = np.empty((n, n_heads * hs), dtype=np.float32)
+    _check(lib().flm_op_attention_slots_prefix(_p(out), _p(kc), _p(vc), _p(q), _p(k), _p(v), n_heads, hs, max_seq, int(prefix_rows), n, _p(b), _p(rw), _p(ps)))
     return out
 
 

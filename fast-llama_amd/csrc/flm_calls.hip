@@ -982,19 +982,22 @@ int flm_fan_keep(flm_ctx* c, int seq) {
 
 // Cache slots (include/flm_gpu.h; kernels: flm_batch.h; the batch pass: flm_prompt.hip prefill_batched with a row origin / a SlotDesc).  The layout is pure host arithmetic
 // and the one place the capacity condition is written
-int flm_batch_layout_for(int n_slots, const int32_t* rows, int max_seq_len, flm_batch_layout* out) {
+int flm_batch_layout_for(int n_slots, const int32_t* rows, int max_seq_len, flm_batch_layout* out) { return flm_batch_layout_prefix_for(0, n_slots, rows, max_seq_len, out); }
+// ... behind prefix_rows shared rows (flm_batch_open_prefix): base[0] = prefix_rows, and the condition is prefix_rows + sum(rows) <= max_seq_len
+int flm_batch_layout_prefix_for(int prefix_rows, int n_slots, const int32_t* rows, int max_seq_len, flm_batch_layout* out) {
     if (!out || !rows) return FLM_ERR_INVALID;
     const char* why = nullptr;
-    long long sum = 0;
-    if (n_slots < 1 || n_slots > FLM_BATCH_MAX) why = "batch: n_slots outside 1 .. FLM_BATCH_MAX";
+    long long sum = prefix_rows;
+    if (prefix_rows < 0) why = "batch: a negative number of prefix rows";
+    else if (n_slots < 1 || n_slots > FLM_BATCH_MAX) why = "batch: n_slots outside 1 .. FLM_BATCH_MAX";
     else {
         for (int s = 0; s < n_slots && !why; ++s) { if (rows[s] < 1) why = "batch: a slot of fewer than 1 row"; sum += rows[s]; }
-        if (!why && sum > max_seq_len) why = "batch: the slots' rows exceed max_seq_len";
+        if (!why && sum > max_seq_len) why = prefix_rows ? "batch: the prefix and the slots' rows exceed max_seq_len" : "batch: the slots' rows exceed max_seq_len";
     }
     if (why) { g_last_error = why; return FLM_ERR_INVALID; }
     flm_batch_layout l{};
     l.n_slots = n_slots;
-    for (int s = 0, b = 0; s < n_slots; ++s) { l.base[s] = b; l.rows[s] = rows[s]; b += rows[s]; }
+    for (int s = 0, b = prefix_rows; s < n_slots; ++s) { l.base[s] = b; l.rows[s] = rows[s]; b += rows[s]; }
     *out = l;
     return FLM_OK;
 }
@@ -1007,17 +1010,23 @@ static int batch_ready(flm_ctx* c, const char* who) {
     HIPC(c, hipSetDevice(c->device));
     return FLM_OK;
 }
-int flm_batch_open(flm_ctx* c, const flm_batch_layout* layout) {
+int flm_batch_open(flm_ctx* c, const flm_batch_layout* layout) { return flm_batch_open_prefix(c, layout, 0); }
+// S > 0: the cache rows [0, S) stay what they are -- the caller vouches for them, as for `pos` in flm_generate -- and every slot continues them (kernels: flm_prefix.h)
+int flm_batch_open_prefix(flm_ctx* c, const flm_batch_layout* layout, int S) {
     if (!c || !layout) return FLM_ERR_INVALID;
     if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "batch: one GPU only");
     if (!model_complete(c)) return fail(c, FLM_ERR_STATE, "batch_open before all tensors were uploaded");
+    if (S < 0) return fail(c, FLM_ERR_INVALID, "batch: a negative number of prefix rows");
     if (attn_lds_bytes(c->d.max_seq_len, c->hs) > kLdsMax) return fail(c, FLM_ERR_UNSUPPORTED, "batch: the one-query attention's LDS does not fit at this head size and max_seq_len");
+    if (S > 0 && c->hs > 128) return fail(c, FLM_ERR_UNSUPPORTED, "batch: a shared prefix needs a head size of at most 128 (the multi-query attention's bound)");
     flm_batch_layout lay{};
     if (layout->n_slots < 1 || layout->n_slots > FLM_BATCH_MAX) return fail(c, FLM_ERR_INVALID, "batch: n_slots outside 1 .. FLM_BATCH_MAX");
-    if (flm_batch_layout_for(layout->n_slots, layout->rows, c->d.max_seq_len, &lay)) { c->err = g_last_error; return FLM_ERR_INVALID; }
-    for (int s = 0; s < lay.n_slots; ++s) if (layout->base[s] != lay.base[s]) return fail(c, FLM_ERR_INVALID, "batch: the layout is not flm_batch_layout_for's (base is the prefix sum of rows)");
+    if (flm_batch_layout_prefix_for(S, layout->n_slots, layout->rows, c->d.max_seq_len, &lay)) { c->err = g_last_error; return FLM_ERR_INVALID; }
+    for (int s = 0; s < lay.n_slots; ++s) if (layout->base[s] != lay.base[s]) return fail(c, FLM_ERR_INVALID, "batch: the layout is not flm_batch_layout_prefix_for's for these prefix rows (base is the prefix rows plus the prefix sum of rows)");
+    if (S > 0 && prefix_lds_bytes(1, c->d.max_seq_len, c->hs) > kLdsMax) return fail(c, FLM_ERR_UNSUPPORTED, "batch: one query's scores behind the prefix do not fit the LDS");
     c->fan_valid = false;
     c->batch_lay = lay;
+    c->batch_prefix = S;
     for (auto& s : c->batch_slot) s = flm_ctx::BatchSlot{};
     c->batch_open = true;
     c->batch_passes = 0;
@@ -1055,12 +1064,16 @@ int flm_batch_join(flm_ctx* c, int slot, const flm_batch_req* q, int32_t* first_
     for (int s = 0; s < lay.n_slots; ++s) if (c->batch_slot[s].live) in.live |= 1u << s;
     in.live |= 1u << slot;
     SlotDesc f{}; f.n = 1; f.slot[0] = slot; f.base[0] = lay.base[slot]; f.pos[0] = n - 1; f.rows[0] = lay.rows[slot];
+    // behind a shared prefix the prompt is a pass of ONE segment and no step row: the serial prompt kernels know one contiguous range, the segment kernels walk two
+    const PrefixDesc px{c->batch_prefix, 0, 0};
+    SegDesc sg{}; sg.n_segs = 1; sg.n_step = 0; sg.slot[0] = slot; sg.row0[0] = 0; sg.n[0] = n; sg.base[0] = lay.base[slot]; sg.pos0[0] = px.S; sg.rows[0] = lay.rows[slot];
     const bool skinny = c->spec_gemm != 0 && n <= kSkinnyTokens;
     int chunk = 1; float* const stage = score_stage(c, &chunk);
     SlotOut so{};
     return with_retry(c, n, [&]() -> int {
         int r = h2d(c, c->prompt_dev, q->prompt, sizeof(int) * (size_t)n); if (r) return r;
-        r = prefill_batched_qt(c, n, 0, true, skinny, nullptr, lay.base[slot], nullptr); if (r) return r;
+        r = px.S > 0 ? prefill_batched_qt(c, n, 0, true, skinny, nullptr, 0, nullptr, &sg, &px) : prefill_batched_qt(c, n, 0, true, skinny, nullptr, lay.base[slot], nullptr);
+        if (r) return r;
         r = batch_classify(c, n - 1, 0, 1, stage, skinny, in); if (r) return r;          // (only the prompt's last row goes through the classifier and the draw)
         return batch_accept(c, in, f, &so);
     }, [&] {
@@ -1076,11 +1089,12 @@ int flm_batch_step(flm_ctx* c, flm_batch_out* out) {
     int r = batch_ready(c, "batch_step"); if (r) return r;
     const flm_batch_layout& lay = c->batch_lay;
     SlotIn in{}; SlotDesc f{};
+    const PrefixDesc px{c->batch_prefix, 0, 0};                  // (S > 0: a row's logical position counts the shared rows; the host's copy of a slot counts its own)
     for (int s = 0; s < lay.n_slots; ++s) {
         const flm_ctx::BatchSlot& b = c->batch_slot[s];
         if (!b.live) continue;
         const int i = f.n++;
-        f.slot[i] = s; f.base[i] = lay.base[s]; f.pos[i] = b.pos; f.rows[i] = lay.rows[s];
+        f.slot[i] = s; f.base[i] = lay.base[s]; f.pos[i] = px.S + b.pos; f.rows[i] = lay.rows[s];
         in.ids[i] = b.last; in.rng[i] = b.rng; in.temp[i] = b.temp; in.topp[i] = b.topp; in.stop[i] = b.stop; in.left[i] = b.max_tokens - b.n_out;
         in.live |= 1u << s;
     }
@@ -1094,7 +1108,7 @@ int flm_batch_step(flm_ctx* c, flm_batch_out* out) {
     return with_retry(c, B, [&]() -> int {
         hipLaunchKernelGGL(k_slots_load, dim3(1), dim3(64), 0, c->stream, in, B, c->prompt_dev);
         HIPC(c, hipGetLastError());
-        int r = prefill_batched_qt(c, B, 0, true, skinny, nullptr, 0, &f); if (r) return r;
+        int r = prefill_batched_qt(c, B, 0, true, skinny, nullptr, 0, &f, nullptr, &px); if (r) return r;
         for (int r0 = 0; r0 < B; r0 += chunk) {
             const int m = B - r0 < chunk ? B - r0 : chunk;
             r = batch_classify(c, r0, r0, m, stage, skinny, in); if (r) return r;
@@ -1179,14 +1193,15 @@ int flm_batch_pass(flm_ctx* c, int prompt_rows_max, flm_batch_pass_out* out) {
     if (B > c->pf_cap || B > c->prompt_cap) return fail(c, FLM_ERR_INVALID, "batch_pass: more rows than max_seq_len");
     // the pass's geometry, the step rows' SlotDesc, and the draw rows: the step rows, then the last row of every segment that completes its prompt (gathered behind them)
     SegDesc sg{}; SlotDesc fs{}; SlotDesc fd{}; SlotIn in_step{}; SlotIn in{}; GatherDesc ga{};
+    const PrefixDesc px{c->batch_prefix, 0, 0};                  // (S > 0: the plan counts a slot's own rows, the pass's geometry the logical positions behind the shared rows)
     sg.n_segs = plan.n_segs; sg.n_step = L; ga.dst0 = L;
     in.live = running;
     for (int i = 0; i < plan.n_segs; ++i) {
         const flm_batch_seg& g = plan.seg[i];
         const flm_ctx::BatchSlot& b = c->batch_slot[g.slot];
-        sg.slot[i] = g.slot; sg.row0[i] = g.row0; sg.n[i] = g.n; sg.base[i] = lay.base[g.slot]; sg.pos0[i] = g.pos0; sg.rows[i] = lay.rows[g.slot];
+        sg.slot[i] = g.slot; sg.row0[i] = g.row0; sg.n[i] = g.n; sg.base[i] = lay.base[g.slot]; sg.pos0[i] = px.S + g.pos0; sg.rows[i] = lay.rows[g.slot];
         if (i < L) {
-            fs.slot[i] = g.slot; fs.base[i] = lay.base[g.slot]; fs.pos[i] = b.pos; fs.rows[i] = lay.rows[g.slot]; fs.n = i + 1;
+            fs.slot[i] = g.slot; fs.base[i] = lay.base[g.slot]; fs.pos[i] = px.S + b.pos; fs.rows[i] = lay.rows[g.slot]; fs.n = i + 1;
             in_step.ids[i] = b.last;
         } else {
             memcpy(c->pass_ids.data() + (g.row0 - L), b.prompt + g.pos0, sizeof(int32_t) * (size_t)g.n);
@@ -1210,7 +1225,7 @@ int flm_batch_pass(flm_ctx* c, int prompt_rows_max, flm_batch_pass_out* out) {
             hipLaunchKernelGGL(k_slots_load, dim3(1), dim3(64), 0, c->stream, in_step, L, c->prompt_dev);
             HIPC(c, hipGetLastError());
         }
-        r = prefill_batched_qt(c, B, 0, D > 0, skinny, nullptr, 0, L > 0 ? &fs : nullptr, &sg); if (r) return r;
+        r = prefill_batched_qt(c, B, 0, D > 0, skinny, nullptr, 0, L > 0 ? &fs : nullptr, &sg, &px); if (r) return r;
         if (ga.n > 0) {
             hipLaunchKernelGGL(k_gather_rows, dim3(1), dim3(256), 0, c->stream, c->pf_x, c->d.dim, ga);
             HIPC(c, hipGetLastError());
@@ -1253,31 +1268,36 @@ int flm_batch_close(flm_ctx* c, int keep_slot) {
     int r = batch_ready(c, "batch_close"); if (r) return r;
     if (keep_slot >= c->batch_lay.n_slots || !c->batch_slot[keep_slot].used || c->batch_slot[keep_slot].filling)
         return fail(c, FLM_ERR_INVALID, "batch_close: keep_slot outside the layout, a slot that never held a sequence, or one that is still taking in its prompt");
-    const int base = c->batch_lay.base[keep_slot], len = c->batch_slot[keep_slot].pos;      // (pos: the rows the sequence has in the cache = n_prompt + n_out - 1)
+    const int S = c->batch_prefix, base = c->batch_lay.base[keep_slot] - S, len = c->batch_slot[keep_slot].pos;      // (pos: the rows the sequence has in the cache = n_prompt + n_out - 1; base: how far they move)
     c->batch_open = false;
-    // rows [base, base + len) -> [0, len).  base < len: source and destination overlap -- chunks of at most `base` rows, ascending, each launch's ranges disjoint (a chunk's
-    // destination was the source of the chunks in front of it, which the stream has finished)
+    // rows [S + base, S + base + len) -> [S, S + len) (S: the shared prefix rows, 0 without one).  base < len: source and destination overlap -- chunks of at most `base` rows,
+    // ascending, each launch's ranges disjoint (a chunk's destination was the source of the chunks in front of it, which the stream has finished)
     for (int off = 0; base > 0 && off < len; off += base) {
         const int count = len - off < base ? len - off : base;
-        hipLaunchKernelGGL(k_fan_keep, dim3(c->d.n_layers * c->heads_local), dim3(256), 0, c->stream, c->kcache, c->vcache, c->kv_rows, c->hs, base + off, off, count);
+        hipLaunchKernelGGL(k_fan_keep, dim3(c->d.n_layers * c->heads_local), dim3(256), 0, c->stream, c->kcache, c->vcache, c->kv_rows, c->hs, S + base + off, S + off, count);
         HIPC(c, hipGetLastError());
     }
     HIPC(c, hipStreamSynchronize(c->stream));
     return FLM_OK;
 }
 int flm_generate_batch(flm_ctx* c, const flm_batch_req* reqs, int n, flm_fan_cb cb, void* user, int32_t* out_tokens, int stride, int* n_out, uint64_t* rng_out) {
+    return flm_generate_batch_prefix(c, 0, reqs, n, cb, user, out_tokens, stride, n_out, rng_out);
+}
+// the same loop behind prefix_rows shared rows: every request's prompt is ITS OWN part and enters at logical position prefix_rows
+int flm_generate_batch_prefix(flm_ctx* c, int prefix_rows, const flm_batch_req* reqs, int n, flm_fan_cb cb, void* user, int32_t* out_tokens, int stride, int* n_out, uint64_t* rng_out) {
     if (!c || !reqs || !out_tokens || !n_out) return FLM_ERR_INVALID;
+    if (prefix_rows < 0) return fail(c, FLM_ERR_INVALID, "generate_batch: a negative number of prefix rows");
     if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "generate_batch: one GPU only");
     if (n < 1 || n > FLM_BATCH_MAX) return fail(c, FLM_ERR_INVALID, "generate_batch: n outside 1 .. FLM_BATCH_MAX");
     int32_t rows[FLM_BATCH_MAX];
     for (int j = 0; j < n; ++j) {
-        if (reqs[j].n_prompt < 1 || reqs[j].max_tokens < 1 || reqs[j].max_tokens > stride || (long long)reqs[j].n_prompt + reqs[j].max_tokens - 1 > c->d.max_seq_len)
+        if (reqs[j].n_prompt < 1 || reqs[j].max_tokens < 1 || reqs[j].max_tokens > stride || (long long)prefix_rows + reqs[j].n_prompt + reqs[j].max_tokens - 1 > c->d.max_seq_len)
             return fail(c, FLM_ERR_INVALID, "generate_batch: n_prompt >= 1, 1 <= max_tokens <= stride, n_prompt + max_tokens - 1 <= max_seq_len");
         rows[j] = reqs[j].n_prompt + reqs[j].max_tokens - 1;
     }
     flm_batch_layout lay{};
-    if (flm_batch_layout_for(n, rows, c->d.max_seq_len, &lay)) { c->err = g_last_error; return FLM_ERR_INVALID; }
-    int r = flm_batch_open(c, &lay); if (r) return r;
+    if (flm_batch_layout_prefix_for(prefix_rows, n, rows, c->d.max_seq_len, &lay)) { c->err = g_last_error; return FLM_ERR_INVALID; }
+    int r = flm_batch_open_prefix(c, &lay, prefix_rows); if (r) return r;
     bool cancelled = false;
     unsigned live_mask = 0;
     for (int j = 0; j < n; ++j) n_out[j] = 0;

@@ -870,6 +870,7 @@ int flm_query(flm_ctx* c, const char* key, int* value) {
         {"spec_accepted", c->spec_accepted},
         {"draft_tokens", c->draft_tokens},
         {"batch_passes", c->batch_passes},
+        {"batch_prefix", c->batch_open ? c->batch_prefix : 0},
         // which hand-offs of the token's launch (short contexts) are consumed in arrival order; -1: that launch was not planned (yet)
         {"ao_active", c->la_ok[0] ? (c->la_p[0].ao_o ? 1 : 0) | (c->la_p[0].ao_2 ? 2 : 0) : -1},
         {"token_path", (c->world == 1 ? path : 0) | (c->attn_split ? 64 : 0)},

@@ -10,6 +10,7 @@
 //   flm_layers.hip       all layers of a token / the whole greedy token in one launch (k_layers); flm_layers_tp.hip: its rank-spanning form
 //   flm_launch.h         from a run-time choice to one instantiation of a kernel template: the variant lists' dispatch() / for_each_variant()
 //   flm_prompt.hip       the batched prompt path (GEMM tiles on the matrix cores, prompt attention; with a FanDesc: one step of flm_generate_n)
+//   flm_prefix.hip       the launchers of the attention behind a shared prefix (flm_prefix.h: cache slots opened by flm_batch_open_prefix)
 //   flm_ops.hip          the op-level exports of the parity tests (flm_op_*)
 //   flm_wait.h           (device side, part of flm_kernels.h) every cross-workgroup / cross-rank wait of the fused launches: flag polls, granule pieces, when a wait gives up
 //   flm_tuning.h         the option table: one row per flm_set_option / flm_query key (flm_gpu.hip walks it)
@@ -231,6 +232,7 @@ struct flm_ctx {
     flm::AttnArgs* seg_views = nullptr;                // ... the prompt segments' views for k_attn_segs_mq / k_attn_segs [FLM_BATCH_MAX] (flm_segs.h), device memory since create
     std::vector<int32_t> pass_ids;                     // flm_batch_pass: the pass's prompt rows gathered from the callers' prompts on their way to the device [max_seq_len], sized at create
     int batch_rows = -1;                               // option "batch_rows": flm_generate_batch admits every request and runs flm_batch_pass(batch_rows) (-1: serial joins, then steps)
+    int batch_prefix = 0;                              // flm_batch_open_prefix: the shared rows [0, S) in front of the slots (flm_prefix.h); 0: none -- every launch is the plain batch's.  A slot's pos / fed count ITS OWN rows
     int batch_passes = 0;                              // flm_query "batch_passes": weight passes (joins, steps, passes) since the last flm_batch_open
     int score_rows = 0;                                // option "score_rows": rows per classifier chunk of flm_score_tokens (0: as many as the staging holds; < 0: one row at a time through c->logits)
     std::map<GraphKey, hipGraphExec_t> graphs;        // the token graphs captured so far (flm_gpu.hip token_graph)
@@ -466,7 +468,7 @@ int feed(flm_ctx* c, const int32_t* tokens, int n, int pos, TokenForm last);
 int d2h(flm_ctx* c, void* dst, const void* src_dev, size_t bytes);
 float* score_stage(const flm_ctx* c, int* chunk);
 constexpr int kPrefillMin = 4;
-int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers = false, bool skinny = false, const flm::FanDesc* fan = nullptr, int row0 = 0, const flm::SlotDesc* slots = nullptr, const flm::SegDesc* segs = nullptr);      // (flm_prompt.hip; by the model's quant type.  all_layers: the last layer is completed too -- flm_score_tokens needs every row's final residual; skinny: int8 and B <= 16: every GEMM through k_gemm_q8_skinny -- the verify pass under "spec_gemm" 1; fan: the rows are a fan step's -- flm_generate_n; row0: the batch is a prompt entering the cache slot that starts at physical row row0 -- flm_batch_join; slots: the rows are a batch step's -- flm_batch_step; segs: a ragged pass -- flm_batch_pass: rows [0, n_step) are a step's (slots, where n_step > 0), the rest prompt segments)
+int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers = false, bool skinny = false, const flm::FanDesc* fan = nullptr, int row0 = 0, const flm::SlotDesc* slots = nullptr, const flm::SegDesc* segs = nullptr, const flm::PrefixDesc* pfx = nullptr);      // (flm_prompt.hip; by the model's quant type.  all_layers: the last layer is completed too -- flm_score_tokens needs every row's final residual; skinny: int8 and B <= 16: every GEMM through k_gemm_q8_skinny -- the verify pass under "spec_gemm" 1; fan: the rows are a fan step's -- flm_generate_n; row0: the batch is a prompt entering the cache slot that starts at physical row row0 -- flm_batch_join; slots: the rows are a batch step's -- flm_batch_step; segs: a ragged pass -- flm_batch_pass: rows [0, n_step) are a step's (slots, where n_step > 0), the rest prompt segments; pfx, S > 0: the slots lie behind S shared rows -- flm_batch_open_prefix: pos / pos0 count them, base stays physical, and the attention is flm_prefix.h's; null or S == 0: every launch is the one made without it)
 // a fan step's pieces (flm_prompt.hip; kernels: flm_fan.h).  fan_classify: rows [row0, row0 + m) through score_classify's prologue and GEMM into `stage`, then k_sample_fan
 // into fan_drawn / fan_after, row j with in.rng[j].  The launchers take c == null from the op-level mirror (flm_op_attention_fan)
 int fan_classify(flm_ctx* c, int row0, int m, float* stage, bool skinny, float temperature, float topp, const flm::FanIn& in);
@@ -483,6 +485,9 @@ int launch_rope_kv_slots(flm_ctx* c, hipStream_t st, const float* qkv, float* qo
 const char* seg_check(const flm::SegDesc& f, int B, int max_seq);
 int launch_attn_segs(flm_ctx* c, hipStream_t st, const flm::AttnArgs& aa, const flm::SegDesc& f, int heads, int row_stride, flm::AttnArgs* views, bool one_query);
 int launch_rope_kv_segs(flm_ctx* c, hipStream_t st, const float* qkv, float* qout, float* kcache, float* vcache, const float* rope_cos, const float* rope_sin, int dim, int hs, int kv_rows, const flm::SegDesc& f, int B);
+// the attention behind S shared rows (flm_prefix.hip; kernels: flm_prefix.h): base physical (>= S), pos / pos0 logical (>= S); c may be null (the op-level mirrors)
+int launch_attn_slots_prefix(flm_ctx* c, hipStream_t st, const flm::AttnArgs& aa, const flm::SlotDesc& f, int S, int heads, int row_stride);
+int launch_attn_segs_prefix(flm_ctx* c, hipStream_t st, const flm::AttnArgs& aa, const flm::SegDesc& f, int S, int heads, int row_stride);
 int launch_attn_fan(flm_ctx* c, hipStream_t st, const flm::AttnArgs& aa, const flm::FanDesc& f, int heads, int row_stride);
 int launch_rope_kv_fan(flm_ctx* c, hipStream_t st, const float* qkv, float* qout, float* kcache, float* vcache, const float* rope_cos, const float* rope_sin, int dim, int hs, int kv_rows, const flm::FanDesc& f);
 // flm_score_tokens' classifier stage (flm_prompt.hip): rows [row0, row0 + m) of the batch's final residual (pf_x) -> output norm, quantize, the classifier GEMM tiles into

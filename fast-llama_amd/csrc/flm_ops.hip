@@ -543,6 +543,63 @@ int flm_op_attention_segs(float* out, float* kc, float* vc, const float* q, cons
     return FLM_OK;
 }
 
+// The two ops behind S shared rows (flm_prefix.h): the launches prefill_batched makes with a PrefixDesc -- RoPE and the cache rows by the plain kernels with base - S, the
+// attention by k_attn_slots_prefix / k_attn_segs_prefix_mq.  One body: the step rows are the segments [0, n_step), as in flm_op_attention_segs
+static int op_attention_prefix(float* out, float* kc, float* vc, const float* q, const float* k, const float* v, int n_heads, int hs, int max_seq, int S, int B, int n_segs, int n_step,
+                               const int32_t* base, const int32_t* rows, const int32_t* n, const int32_t* pos0) {
+    if (!out || !kc || !vc || !q || !k || !v || !base || !rows || !pos0 || n_heads < 1 || hs < 32 || hs % 8 || hs > 256 || max_seq < 1 || B < 1 || S < 1 || S >= max_seq ||
+        n_segs < 1 || n_segs > FLM_BATCH_MAX || n_step < 0 || n_step > n_segs) return FLM_ERR_INVALID;
+    if (hs > 128) return FLM_ERR_UNSUPPORTED;
+    SegDesc f{}, own{}; f.n_segs = n_segs; f.n_step = n_step;
+    SlotDesc fs{}; fs.n = n_step;
+    int top = 0;
+    for (int s = 0, at = 0; s < n_segs; ++s) {
+        const int ns = n ? n[s] : 1;
+        if (ns < 1 || (long long)at + ns > B || base[s] < S || pos0[s] < S) return FLM_ERR_INVALID;
+        f.slot[s] = s; f.row0[s] = at; f.n[s] = ns; f.base[s] = base[s]; f.pos0[s] = pos0[s]; f.rows[s] = rows[s];
+        at += ns;
+        if (s < n_step) { fs.slot[s] = s; fs.base[s] = base[s]; fs.pos[s] = pos0[s]; fs.rows[s] = rows[s]; }
+        if ((long long)pos0[s] + ns <= max_seq) top = pos0[s] + ns > top ? pos0[s] + ns : top;
+    }
+    own = f; for (int s = 0; s < n_segs; ++s) own.pos0[s] -= S;
+    if (seg_check(own, B, max_seq)) return FLM_ERR_INVALID;
+    SegDesc rf = f; SlotDesc rfs = fs;                                             // RoPE's copies: a row's cache row is (base - S) + pos
+    for (int s = 0; s < n_segs; ++s) { rf.base[s] -= S; rfs.base[s] -= S; }
+    const int dim = n_heads * hs;
+    const size_t nd = (size_t)B * dim, nc = (size_t)n_heads * max_seq * hs, h2 = hs / 2;
+    std::vector<float> cs, sn; build_rope_table(hs, top, cs, sn);
+    std::vector<float> qkv(3 * nd);
+    for (int j = 0; j < B; ++j) {
+        memcpy(&qkv[(size_t)j * 3 * dim], q + (size_t)j * dim, (size_t)dim * 4); memcpy(&qkv[(size_t)j * 3 * dim + dim], k + (size_t)j * dim, (size_t)dim * 4);
+        memcpy(&qkv[(size_t)j * 3 * dim + 2 * dim], v + (size_t)j * dim, (size_t)dim * 4);
+    }
+    DevBuf dqkv, dq, dkc, dvc, dout, dc, dsn;
+    if (dqkv.alloc(3 * nd * 4) || dq.alloc(nd * 4) || dkc.alloc(nc * 4) || dvc.alloc(nc * 4) || dout.alloc(nd * 4) || dc.alloc(top * h2 * 4) || dsn.alloc(top * h2 * 4)) return FLM_ERR_OOM;
+    OPC(hipMemcpy(dqkv.p, qkv.data(), 3 * nd * 4, hipMemcpyHostToDevice));
+    OPC(hipMemcpy(dkc.p, kc, nc * 4, hipMemcpyHostToDevice)); OPC(hipMemcpy(dvc.p, vc, nc * 4, hipMemcpyHostToDevice));
+    OPC(hipMemcpy(dc.p, cs.data(), top * h2 * 4, hipMemcpyHostToDevice)); OPC(hipMemcpy(dsn.p, sn.data(), top * h2 * 4, hipMemcpyHostToDevice));
+    AttnArgs a{}; a.q = dq.as<float>(); a.kcache = dkc.as<float>(); a.vcache = dvc.as<float>(); a.out = dout.as<float>(); a.hs = hs; a.max_seq = max_seq;
+    int r = FLM_OK;
+    if (n_step > 0) { r = launch_rope_kv_slots(nullptr, 0, dqkv.as<float>(), dq.as<float>(), dkc.as<float>(), dvc.as<float>(), dc.as<float>(), dsn.as<float>(), dim, hs, max_seq, rfs); if (r) return r; }
+    if (n_step < n_segs) { r = launch_rope_kv_segs(nullptr, 0, dqkv.as<float>(), dq.as<float>(), dkc.as<float>(), dvc.as<float>(), dc.as<float>(), dsn.as<float>(), dim, hs, max_seq, rf, B); if (r) return r; }
+    if (n_step > 0) { r = launch_attn_slots_prefix(nullptr, 0, a, fs, S, n_heads, dim); if (r) return r; }
+    if (n_step < n_segs) { r = launch_attn_segs_prefix(nullptr, 0, a, f, S, n_heads, dim); if (r) return r; }
+    OPC(hipDeviceSynchronize());
+    OPC(hipMemcpy(out, dout.p, nd * 4, hipMemcpyDeviceToHost));
+    OPC(hipMemcpy(kc, dkc.p, nc * 4, hipMemcpyDeviceToHost)); OPC(hipMemcpy(vc, dvc.p, nc * 4, hipMemcpyDeviceToHost));
+    return FLM_OK;
+}
+int flm_op_attention_slots_prefix(float* out, float* kc, float* vc, const float* q, const float* k, const float* v,
+                                  int n_heads, int hs, int max_seq, int prefix_rows, int n, const int32_t* base, const int32_t* rows, const int32_t* pos) {
+    if (n < 1 || n > FLM_BATCH_MAX) return FLM_ERR_INVALID;
+    return op_attention_prefix(out, kc, vc, q, k, v, n_heads, hs, max_seq, prefix_rows, n, n, n, base, rows, nullptr, pos);
+}
+int flm_op_attention_segs_prefix(float* out, float* kc, float* vc, const float* q, const float* k, const float* v,
+                                 int n_heads, int hs, int max_seq, int prefix_rows, int B, int n_segs, int n_step, const int32_t* base, const int32_t* rows, const int32_t* n, const int32_t* pos0) {
+    if (!n) return FLM_ERR_INVALID;
+    return op_attention_prefix(out, kc, vc, q, k, v, n_heads, hs, max_seq, prefix_rows, B, n_segs, n_step, base, rows, n, pos0);
+}
+
 /* elementary functions exactly as the kernels evaluate them (tests pin them against the host's IEEE results) */
 int flm_op_math(int fn, float* x, const float* y, size_t n) {
     if (!x || n == 0 || fn < 0 || fn > 5 || (fn >= 2 && !y)) return FLM_ERR_INVALID;

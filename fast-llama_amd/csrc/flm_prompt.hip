@@ -200,8 +200,16 @@ int launch_rope_kv_segs(flm_ctx* c, hipStream_t st, const float* qkv, float* qou
 // slots (a flm_batch_step; null: as above): the B rows are the live slots' last ids, each at its own position in its own region -- the fan's route with k_rope_kv_slots and k_attn_slots
 // segs (a flm_batch_pass; null: every launch is the one made without it): a ragged pass (flm_segs.h) -- rows [0, n_step) are a step's rows (`slots` describes them, null
 // where n_step is 0) and keep the step's launches, the rest are prompt segments: k_rope_kv_segs and k_attn_segs_mq / k_attn_segs on the same q / out buffers
+// pfx (flm_batch_open_prefix; null or S == 0: every launch is the one made without it): the slots of `slots` / `segs` lie behind S shared rows -- pos / pos0 are LOGICAL and
+// count them, base is PHYSICAL.  RoPE and the cache rows keep their kernels, which place a row at base + pos: they get copies with base - S.  The attention is flm_prefix.h's
 template <int QT>
-int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req = false, const FanDesc* fan = nullptr, int row0 = 0, const SlotDesc* slots = nullptr, const SegDesc* segs = nullptr) {
+int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req = false, const FanDesc* fan = nullptr, int row0 = 0, const SlotDesc* slots = nullptr, const SegDesc* segs = nullptr, const PrefixDesc* pfx = nullptr) {
+    const int S = pfx ? pfx->S : 0;
+    SlotDesc rope_slots{}; SegDesc rope_segs{};
+    if (S > 0 && slots) { rope_slots = *slots; for (int i = 0; i < kBatchMax; ++i) rope_slots.base[i] -= S; }
+    if (S > 0 && segs) { rope_segs = *segs; for (int i = 0; i < kBatchMax; ++i) rope_segs.base[i] -= S; }
+    const SlotDesc* const rslots = S > 0 && slots ? &rope_slots : slots;
+    const SegDesc* const rsegs = S > 0 && segs ? &rope_segs : segs;
     const bool skinny = skinny_req && QT == QT_INT8 && B <= kSkinnyTokens && c->world == 1;      // (the verify pass; int16: the tiles)
     const auto& d = c->d;
     const int L = d.n_layers, dim = d.dim, hid = d.hidden_dim, hs = c->hs;
@@ -240,12 +248,12 @@ int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req
         }
         else if (segs) {
             r = launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, skinny); if (r) return r;
-            if (segs->n_step > 0) { r = launch_rope_kv_slots(c, st, c->pf_qkv, c->pf_q, kc, vc, c->rope_cos, c->rope_sin, dimL, hs, c->kv_rows, *slots); if (r) return r; }
-            if (segs->n_step < B) { r = launch_rope_kv_segs(c, st, c->pf_qkv, c->pf_q, kc, vc, c->rope_cos, c->rope_sin, dimL, hs, c->kv_rows, *segs, B); if (r) return r; }
+            if (segs->n_step > 0) { r = launch_rope_kv_slots(c, st, c->pf_qkv, c->pf_q, kc, vc, c->rope_cos, c->rope_sin, dimL, hs, c->kv_rows, *rslots); if (r) return r; }
+            if (segs->n_step < B) { r = launch_rope_kv_segs(c, st, c->pf_qkv, c->pf_q, kc, vc, c->rope_cos, c->rope_sin, dimL, hs, c->kv_rows, *rsegs, B); if (r) return r; }
         }
         else if (slots) {
             r = launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, skinny); if (r) return r;
-            r = launch_rope_kv_slots(c, st, c->pf_qkv, c->pf_q, kc, vc, c->rope_cos, c->rope_sin, dimL, hs, c->kv_rows, *slots); if (r) return r;
+            r = launch_rope_kv_slots(c, st, c->pf_qkv, c->pf_q, kc, vc, c->rope_cos, c->rope_sin, dimL, hs, c->kv_rows, *rslots); if (r) return r;
         }
         else if ((QT == QT_INT16 || c->use_mfma || skinny) && dimL % 32 == 0 && hs % 2 == 0) {      // (int16: always the matrix-core tiles -- round 5: with the same epilogues as the int8 tiles)
             // RoPE and the cache rows as the epilogue of the matrix-core tiles: no [tokens][3 dim] round trip, no k_rope_kv_rows
@@ -268,6 +276,10 @@ int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req
         const bool mq_fits = attn_mq_lds_bytes(d.max_seq_len, hs) <= kLdsMax;
         const bool pv_mfma = c->use_pv_mfma && (hs & 1) == 0;
         if (fan) { r = launch_attn_fan(c, st, aa, *fan, c->heads_local, dim); if (r) return r; }
+        else if (S > 0) {      // behind a shared prefix: a group of rows walks the prefix tiles once, then the rows' own
+            if (slots) { r = launch_attn_slots_prefix(c, st, aa, *slots, S, c->heads_local, dim); if (r) return r; }
+            if (segs && segs->n_step < B) { r = launch_attn_segs_prefix(c, st, aa, *segs, S, c->heads_local, dim); if (r) return r; }
+        }
         else if (segs) {
             if (segs->n_step > 0) { r = launch_attn_slots(c, st, aa, *slots, c->heads_local, dim, c->batch_views); if (r) return r; }
             if (segs->n_step < B) { r = launch_attn_segs(c, st, aa, *segs, c->heads_local, dim, c->seg_views, !c->use_prefill_mq); if (r) return r; }
@@ -333,14 +345,27 @@ int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req
 int launch_gemm_store(flm_ctx* c, hipStream_t st, int qt, const GemmArgs& g, int use_mfma) {
     return qt == FLM_QT_INT8 ? launch_gemm<QT_INT8, EPI_STORE>(c, st, g, use_mfma) : launch_gemm<QT_INT16, EPI_STORE>(c, st, g, use_mfma);
 }
-int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers, bool skinny, const FanDesc* fan, int row0, const SlotDesc* slots, const SegDesc* segs) {
+int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers, bool skinny, const FanDesc* fan, int row0, const SlotDesc* slots_in, const SegDesc* segs_in, const PrefixDesc* pfx_in) {
+    // behind a shared prefix the checks below see every row's OWN position (pos - S) in its slot; in front of them: S <= base[s], no slot begins inside the prefix
+    const PrefixDesc* const pfx = pfx_in && pfx_in->S != 0 ? pfx_in : nullptr;
+    SlotDesc own_slots{}; SegDesc own_segs{};
+    if (pfx) {
+        const int S = pfx->S;
+        if (S < 0 || fan || row0 || (!slots_in && !segs_in) || c->hs > 128) return fail(c, FLM_ERR_INVALID, "prefill: a shared prefix serves a batch step or a ragged pass, at head sizes <= 128");
+        if (slots_in) { own_slots = *slots_in; for (int r = 0; r < kBatchMax; ++r) own_slots.pos[r] -= S; }
+        if (segs_in) { own_segs = *segs_in; for (int r = 0; r < kBatchMax; ++r) own_segs.pos0[r] -= S; }
+        for (int r = 0; slots_in && r < slots_in->n && r < kBatchMax; ++r) if (slots_in->base[r] < S) return fail(c, FLM_ERR_INVALID, "prefill: a slot begins inside the shared prefix");
+        for (int r = 0; segs_in && r < segs_in->n_segs && r < kBatchMax; ++r) if (segs_in->base[r] < S) return fail(c, FLM_ERR_INVALID, "prefill: a slot begins inside the shared prefix");
+    }
+    const SlotDesc* const slots = pfx && slots_in ? &own_slots : slots_in;
+    const SegDesc* const segs = pfx && segs_in ? &own_segs : segs_in;
     if (segs) {   // (in front of the first launch: k_rope_kv_segs writes the rows' cache rows)
         if (c->world != 1 || fan || row0 || pos || B > c->pf_cap || (segs->n_step > 0) != (slots != nullptr) || (slots && slots->n != segs->n_step))
             return fail(c, FLM_ERR_INVALID, "prefill: a ragged pass is one GPU's, not a fan step, at row origin 0, within the batch buffers, its step rows described by a SlotDesc");
         if (const char* why = seg_check(*segs, B, c->d.max_seq_len)) return fail(c, FLM_ERR_INVALID, why);
         for (int r = 0; slots && r < slots->n; ++r)
             if (slots->base[r] != segs->base[r] || slots->rows[r] != segs->rows[r] || slots->pos[r] != segs->pos0[r]) return fail(c, FLM_ERR_INVALID, "prefill: a ragged pass's step rows and its SlotDesc disagree");
-        return c->d.quant_type == FLM_QT_INT8 ? prefill_batched<QT_INT8>(c, B, 0, all_layers, skinny, nullptr, 0, slots, segs) : prefill_batched<QT_INT16>(c, B, 0, all_layers, skinny, nullptr, 0, slots, segs);
+        return c->d.quant_type == FLM_QT_INT8 ? prefill_batched<QT_INT8>(c, B, 0, all_layers, skinny, nullptr, 0, slots_in, segs_in, pfx) : prefill_batched<QT_INT16>(c, B, 0, all_layers, skinny, nullptr, 0, slots_in, segs_in, pfx);
     }
     if (fan && (c->world != 1 || fan->n != B || pos != fan->S + fan->t)) return fail(c, FLM_ERR_INVALID, "prefill: a fan step is one GPU's batch of fan.n rows at S + t");
     if ((row0 || slots) && (c->world != 1 || fan || row0 < 0 || (slots && (row0 || slots->n != B)) || row0 + pos + (slots ? 0 : B) > c->d.max_seq_len))
@@ -348,7 +373,7 @@ int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers, bool skinny,
     for (int r = 0; slots && r < slots->n; ++r)      // (in front of the first launch: k_rope_kv_slots writes the rows' cache rows)
         if (slots->n > kBatchMax || slots->base[r] < 0 || slots->rows[r] < 1 || slots->pos[r] < 0 || slots->pos[r] >= slots->rows[r] || (long long)slots->base[r] + slots->rows[r] > c->d.max_seq_len)
             return fail(c, FLM_ERR_INVALID, "prefill: a batch row outside its slot, or a slot outside the cache");
-    return c->d.quant_type == FLM_QT_INT8 ? prefill_batched<QT_INT8>(c, B, pos, all_layers, skinny, fan, row0, slots) : prefill_batched<QT_INT16>(c, B, pos, all_layers, skinny, fan, row0, slots);
+    return c->d.quant_type == FLM_QT_INT8 ? prefill_batched<QT_INT8>(c, B, pos, all_layers, skinny, fan, row0, slots_in, nullptr, pfx) : prefill_batched<QT_INT16>(c, B, pos, all_layers, skinny, fan, row0, slots_in, nullptr, pfx);
 }
 int launch_gemm_skinny_store(flm_ctx* c, hipStream_t st, const GemmArgs& g, int force_nb) { return launch_gemm_skinny<EPI_STORE>(c, st, g, force_nb); }
 

@@ -225,18 +225,26 @@ bool GpuTransformer::generate_samples(const char* prompt, int n, uint64_t seed, 
     return true;
 }
 
-bool GpuTransformer::generate_prompts(const std::vector<std::string>& prompts, uint64_t seed, int max_new_tokens, float temperature, float topp, std::vector<std::string>& texts, int batch_rows) {
+bool GpuTransformer::generate_prompts(const std::vector<std::string>& prompts, uint64_t seed, int max_new_tokens, float temperature, float topp, std::vector<std::string>& texts, int batch_rows, const char* system) {
     texts.clear();
     const int n = (int)prompts.size();
     if (_ctxs.size() != 1) { _err = "--prompts: one device only"; return false; }
     if (n < 1 || n > FLM_BATCH_MAX) { _err = "--prompts: 1 to 16 prompts"; return false; }
     if (max_new_tokens < 0) max_new_tokens = 0;
-    const int share = _cfg.max_seq_len / n;                  // (every prompt gets an equal share of the cache's rows: flm_batch_layout_for)
+    // --system: the shared text's tokens are the cache rows [0, S), fed once; every prompt's own tokens are what its full text has behind them
+    const std::vector<int> shared = system ? encode(system) : std::vector<int>();
+    const int S = (int)shared.size();
+    if (system && (S < 1 || S >= _cfg.max_seq_len)) { _err = "--system: an empty text, or one that fills the cache"; return false; }
+    const int share = (_cfg.max_seq_len - S) / n;            // (every prompt gets an equal share of the rows behind the shared ones: flm_batch_layout_prefix_for)
     std::vector<std::vector<int>> inputs(n);
     std::vector<flm_batch_req> reqs(n);
     int want = 1;
     for (int j = 0; j < n; ++j) {
-        inputs[j] = encode(prompts[j].c_str());
+        inputs[j] = encode(system ? (std::string(system) + prompts[j]).c_str() : prompts[j].c_str());
+        if (system) {
+            if ((int)inputs[j].size() <= S || !std::equal(shared.begin(), shared.end(), inputs[j].begin())) { _err = "--system: a prompt's tokens do not continue the system text's (the tokenizer merged across the seam)"; return false; }
+            inputs[j].erase(inputs[j].begin(), inputs[j].begin() + S);
+        }
         if (inputs[j].empty()) { fprintf(stderr, "Empty input for generate()\n"); return false; }
         printf("Input prompt:%s\n", prompts[j].c_str());
         print_vector("Input tokens:", inputs[j]);
@@ -251,7 +259,9 @@ bool GpuTransformer::generate_prompts(const std::vector<std::string>& prompts, u
     std::vector<int32_t> ids((size_t)n * want);
     std::vector<int> n_out(n, 0);
     if (flm_set_option(_ctxs[0], "batch_rows", batch_rows < 0 ? -1 : batch_rows) != FLM_OK) { _err = std::string("--batch-rows: ") + flm_last_error(_ctxs[0]); return false; }
-    const int rc = flm_generate_batch(_ctxs[0], reqs.data(), n, nullptr, nullptr, ids.data(), want, n_out.data(), nullptr);
+    std::vector<float> unused(S > 0 ? (size_t)_cfg.vocab_size : 0);      // (the shared text's last logits: nobody draws from them)
+    if (S > 0 && flm_forward(_ctxs[0], shared.data(), S, 0, unused.data()) != FLM_OK) { _err = std::string("--system: ") + flm_last_error(_ctxs[0]); return false; }
+    const int rc = flm_generate_batch_prefix(_ctxs[0], S, reqs.data(), n, nullptr, nullptr, ids.data(), want, n_out.data(), nullptr);
     if (rc != FLM_OK) { _err = std::string("--prompts: ") + flm_last_error(_ctxs[0]); return false; }
     texts.resize(n);
     for (int j = 0; j < n; ++j) {

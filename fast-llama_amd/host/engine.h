@@ -38,7 +38,11 @@ public:
     // (flm_generate_batch).  Prompt j's sampler state is seed + j, every completion stops on token 0 by itself, and max_new_tokens is cut to an equal share of the cache.
     // texts[j]: what generate_samples(prompts[j], 1, seed + j, ...) gives
     // batch_rows >= 0 (--batch-rows): option "batch_rows" -- the prompts are admitted and enter inside the steps' passes (flm_batch_pass); the same texts
-    bool generate_prompts(const std::vector<std::string>& prompts, uint64_t seed, int max_new_tokens, float temperature, float topp, std::vector<std::string>& texts, int batch_rows = -1);
+    // system (--system TEXT; null: none): every prompt CONTINUES this text.  Its tokens enter the cache once, through the ordinary prompt path (flm_forward), and the
+    // prompts are served behind them (flm_generate_batch_prefix).  Prompt j's own part is what encode(system + prompts[j]) has behind encode(system) -- which must be its
+    // beginning --, so texts[j] is what generate_samples(system + prompts[j], 1, seed + j, ...) gives
+    bool generate_prompts(const std::vector<std::string>& prompts, uint64_t seed, int max_new_tokens, float temperature, float topp, std::vector<std::string>& texts, int batch_rows = -1,
+                          const char* system = nullptr);
     // --mode score (this build only): the prompt's tokens through flm_score_tokens in one call; one line per position (index, token id, argmax id, the probability of the
     // next token), then a summary line (token count, mean natural-log loss, perplexity, ms)
     bool score(const char* prompt);

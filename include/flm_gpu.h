@@ -448,6 +448,29 @@ int  flm_batch_admit(flm_ctx* ctx, int slot, const flm_batch_req* req);
 int  flm_batch_pass(flm_ctx* ctx, int prompt_rows_max /* 0: no bound */, flm_batch_pass_out* out);
 int  flm_generate_batch(flm_ctx* ctx, const flm_batch_req* reqs, int n, flm_fan_cb cb /* may be NULL */, void* user,
                         int32_t* out_tokens /* [n][stride] */, int stride, int* n_out /* [n] */, uint64_t* rng_out /* [n], may be NULL */);
+/* A shared prefix: the slots continue ONE conversation that is in the cache once -- a system prompt, a few-shot block, a document -- instead of prefilling, storing and
+ * reading it once per request.  The cache rows [0, S) hold it when the batch is opened, written by any entry point or left by flm_batch_close(keep); the caller vouches for
+ * S, as for `pos` in flm_generate.  They are never written while the batch is open.
+ *   layout    flm_batch_layout_prefix_for: base[0] = S, base = S + the prefix sum of rows; the capacity condition is S + sum(rows) <= max_seq_len (flm_batch_layout_for is
+ *             this function at S = 0).  A sequence in slot s keeps logical position p in physical row p for p < S and in row base[s] + (p - S) for p >= S.
+ *   open      flm_batch_open_prefix(ctx, layout, S): the layout must be flm_batch_layout_prefix_for's for S.  flm_query "batch_prefix" answers S while the batch is open.
+ *   requests  a request's prompt is ITS OWN part (n_prompt >= 1); it enters at logical position S and needs n_prompt + max_tokens - 1 <= rows[slot].
+ *   contract  for every request, in any slot, on every route (join + step, admit + pass at any budget, the loop): the ids, their count and the final sampler state are what
+ *                 flm_generate(ctx2, prompt, n_prompt, S, max_tokens, temperature, topp, &rng_state, stop_token, ...)
+ *             delivers on a context whose cache holds the same S rows, and the slot's rows [base, base + n_prompt + n_out - 1) of every layer's K and V are that context's
+ *             rows [S, ...), bit for bit.
+ *   kernels   csrc/flm_prefix.h: a workgroup takes a group of the pass's step rows (k_attn_slots_prefix) or of one prompt segment's queries (k_attn_segs_prefix_mq), walks
+ *             the prefix tiles ONCE for the group and then the rows' own tiles, in the logical order, per query the one-query attention's arithmetic.  RoPE and the cache
+ *             rows keep their kernels.  A join is one single-segment pass (it counts in "batch_passes" as before).
+ *   close     keep_slot >= 0: the slot's rows move to [S, S + len); any entry point continues from pos = S + len (the overlap rule above with base - S in place of base).
+ *   flm_generate_batch_prefix  flm_generate_batch behind prefix_rows shared rows, honouring "batch_rows" the same way.
+ * With S = 0 every call launches exactly what the plain calls launch.  Refusals, with nothing launched and the cache untouched: FLM_ERR_INVALID for S < 0, a layout that does
+ * not fit behind S or whose base[0] != S; FLM_ERR_UNSUPPORTED for S > 0 with head sizes above 128 (the multi-query form's bound, as in flm_generate_n) and for world > 1;
+ * everything else as above.  Nothing is allocated in any of these calls. */
+int  flm_batch_layout_prefix_for(int prefix_rows, int n_slots, const int32_t* rows, int max_seq_len, flm_batch_layout* out);
+int  flm_batch_open_prefix(flm_ctx* ctx, const flm_batch_layout* layout, int prefix_rows);
+int  flm_generate_batch_prefix(flm_ctx* ctx, int prefix_rows, const flm_batch_req* reqs, int n, flm_fan_cb cb /* may be NULL */, void* user,
+                               int32_t* out_tokens /* [n][stride] */, int stride, int* n_out /* [n] */, uint64_t* rng_out /* [n], may be NULL */);
 /* Constrained decoding: a token-level deterministic automaton masks the logits in front of the controls -- what "one of these strings", a JSON shape or a regular expression
  * reduce to.  No reference counterpart.  The automaton is CSR: the edges of state q are [row_ptr[q], row_ptr[q + 1]).
  *   delta(q, t)  the edge_next of t's edge in state q, or q ITSELF when t has no edge there.  The no-edge case is reachable only through the multinomial branch's last-index
@@ -784,6 +807,16 @@ int  flm_op_attention_slots(float* out, float* kc, float* vc, const float* q, co
 int  flm_op_attention_segs(float* out, float* kc, float* vc, const float* q, const float* k, const float* v,
                            int n_heads, int hs, int max_seq, int B, int n_segs, int n_step, const int32_t* base, const int32_t* rows, const int32_t* n, const int32_t* pos0,
                            int one_query);
+/* the two tasks above behind prefix_rows = S shared rows (flm_batch_open_prefix; csrc/flm_prefix.h): the cache rows [0, S) are every row's first S logical rows.  pos[r] /
+ * pos0[s] are LOGICAL positions and count them (>= S); base[r] / base[s] are the slots' PHYSICAL origins (>= S), rows[] their sizes.  A row at logical position p is rotated at
+ * p, its k / v go to cache row base + (p - S), its query attends rows 0 .. S - 1 followed by base .. base + (p - S).  slots: k_rope_kv_slots + k_attn_slots_prefix on n step
+ * rows; segs: the first n_step segments are step rows, the rest prompt segments (k_rope_kv_segs + k_attn_segs_prefix_mq).  FLM_ERR_INVALID, with nothing launched, for S < 1,
+ * a slot that begins inside the prefix, a position in front of S, and what the plain ops refuse; FLM_ERR_UNSUPPORTED for head sizes above 128. */
+int  flm_op_attention_slots_prefix(float* out, float* kc, float* vc, const float* q, const float* k, const float* v,
+                                   int n_heads, int hs, int max_seq, int prefix_rows, int n, const int32_t* base, const int32_t* rows, const int32_t* pos);
+int  flm_op_attention_segs_prefix(float* out, float* kc, float* vc, const float* q, const float* k, const float* v,
+                                  int n_heads, int hs, int max_seq, int prefix_rows, int B, int n_segs, int n_step, const int32_t* base, const int32_t* rows, const int32_t* n,
+                                  const int32_t* pos0);
 /* libm expf as the device evaluates it (the reference calls glibc expf in softmax_sisd and swiglu);
  * in place over n floats.  Lets the tests pin the device routine against glibc bit for bit. */
 int  flm_op_expf(float* x, size_t n);

@@ -7,7 +7,11 @@ Exits non-zero unless every sequence's ids and final state equal flm_generate's.
 --admit: the ragged passes instead (flm_batch_admit / flm_batch_pass, option "batch_rows") against the serial joins timed in the same run, per cell: the time until every
 request has its token 0 -- n flm_batch_joins | one flm_batch_pass(0) | flm_batch_pass(256) until nobody fills -- and flm_generate_batch's whole-call tokens/s under
 "batch_rows" -1, 0 and 256; ids and final states must be equal in every form (exit non-zero otherwise).
-python tools/batch_bench.py [--admit] [--new M] [--temperature T] [--topp P] [--max-seq S] [--gemm 0|1] [--only PROMPT,N] [reps] [layers]"""
+--prefix P: the slots behind a shared prefix of P tokens (flm_batch_open_prefix; kernels: csrc/flm_prefix.h), n requests with an own prompt of --own tokens each, against
+the yardstick timed in the same run: the plain batch on the full `prefix + own` prompts, on the same context, whose max_seq_len is raised to where those fit.  Per cell:
+ms per step, ms until every request has its token 0 (the prefix form: with and without the one prefill of the prefix), the cache rows each form needs; ids and final states
+must be equal (exit non-zero otherwise).
+python tools/batch_bench.py [--admit | --prefix P [--own K]] [--new M] [--temperature T] [--topp P] [--max-seq S] [--gemm 0|1] [--only PROMPT,N] [reps] [layers]"""
 import argparse
 import json
 import os
@@ -27,6 +31,8 @@ ap.add_argument("--target", default="7B")
 ap.add_argument("--max-seq", type=int, default=2048)
 ap.add_argument("--gemm", type=int, default=0, help='"spec_gemm" for the batch and the fan: 0 the 64 x 64 tiles (default), 1 the skinny kernel')
 ap.add_argument("--admit", action="store_true", help="time the ragged passes (admit / pass, \"batch_rows\") against the serial joins")
+ap.add_argument("--prefix", type=int, default=0, help="time the slots behind a shared prefix of this many tokens against the plain batch on the full prompts")
+ap.add_argument("--own", type=int, default=16, help="with --prefix: tokens of every request's own prompt")
 ap.add_argument("--only", default=None, help="PROMPT,N: that one cell alone (a profiler's run)")
 ap.add_argument("reps", nargs="?", type=int, default=3)
 ap.add_argument("layers", nargs="?", type=int, default=None)
@@ -35,6 +41,8 @@ M, T, P, reps, max_seq = opt.new, opt.temperature, opt.topp, opt.reps, opt.max_s
 NS, PROMPTS = (4, 8, 16), (16, 512)
 if opt.only:
     PROMPTS, NS = ((int(opt.only.split(",")[0]),), (int(opt.only.split(",")[1]),))
+if opt.prefix:                                             # (the yardstick's slots hold the prefix once per request: a cache where they fit)
+    max_seq = max(max_seq, max(NS) * (opt.prefix + opt.own + M - 1))
 cfg = synth.make_config(opt.target, ff.QT_INT8)
 if opt.layers is not None:
     cfg.n_layers = opt.layers
@@ -53,12 +61,12 @@ def sequential(prompts, states):
     return time.perf_counter() - t0, ids, after
 
 
-def batch(prompts, states):
-    """flm_generate_batch's loop through the step API, so that the joins and the steps are timed apart -> (whole, the steps alone, ids, states)"""
+def batch(prompts, states, S=0):
+    """flm_generate_batch's loop through the step API, so that the joins and the steps are timed apart -> (whole, the steps alone, ids, states); S: behind S shared rows"""
     reqs = [capi.BatchReq(p, M, T, P, rng_state=s) for p, s in zip(prompts, states)]
-    lay = capi.batch_layout([len(p) + M - 1 for p in prompts], max_seq)
+    lay = capi.batch_layout([len(p) + M - 1 for p in prompts], max_seq, prefix_rows=S)
     t0 = time.perf_counter()
-    ctx.batch_open(lay)
+    ctx.batch_open(lay, prefix_rows=S)
     ids = [[ctx.batch_join(j, q)[0]] for j, q in enumerate(reqs)]
     t1 = time.perf_counter()
     live = 1
@@ -114,6 +122,42 @@ def whole_call(prompts, states, rows):
     ctx.set_option("batch_rows", -1)
     return dt, ids, after, ctx.query("batch_passes")
 
+
+if opt.prefix:
+    S, K = opt.prefix, opt.own
+    ctx.set_option("spec_gemm", opt.gemm)
+    shared = np.concatenate([[1], np.random.default_rng(99).integers(0, cfg.vocab_size, S - 1)]).astype(np.int32)
+    for n in NS:
+        own = [np.random.default_rng(1000 * K + j).integers(0, cfg.vocab_size, K).astype(np.int32) for j in range(n)]
+        full = [np.concatenate([shared, o]) for o in own]
+        states = [1234 + j for j in range(n)]
+        ts = {k: [] for k in ("full_joins", "full_steps", "prefill", "joins", "steps")}
+        for r in range(reps + 1):                          # (round 0 warms both forms; the forms alternate)
+            dt, dsteps, want, want_after = batch(full, states)
+            t0 = time.perf_counter()
+            ctx.forward(shared, 0)                         # the prefix's one prefill, through the ordinary prompt path
+            dfeed = time.perf_counter() - t0
+            dt2, dsteps2, got, after = batch(own, states, S)
+            ok = ok and all(np.array_equal(a, b) for a, b in zip(got, want)) and after == want_after
+            if r:
+                ts["full_joins"].append(dt - dsteps); ts["full_steps"].append(dsteps); ts["prefill"].append(dfeed); ts["joins"].append(dt2 - dsteps2); ts["steps"].append(dsteps2)
+        med = {k: float(np.median(v)) * 1e3 for k, v in ts.items()}
+        spread = {k: float(max(v) - min(v)) * 1e3 for k, v in ts.items()}
+        row = {"prefix": S, "own": K, "n": n, "rows_prefix": S + n * (K + M - 1), "rows_full": n * (S + K + M - 1),
+               "step_ms": round(med["steps"] / (M - 1), 3), "step_spread_ms": round(spread["steps"] / (M - 1), 3),
+               "full_step_ms": round(med["full_steps"] / (M - 1), 3), "full_step_spread_ms": round(spread["full_steps"] / (M - 1), 3),
+               "token0_ms": round(med["prefill"] + med["joins"], 2), "token0_cached_ms": round(med["joins"], 2), "token0_spread_ms": round(spread["prefill"] + spread["joins"], 2),
+               "full_token0_ms": round(med["full_joins"], 2), "full_token0_spread_ms": round(spread["full_joins"], 2)}
+        res["rows"].append(row)
+        print(f"prefix {S:4d}  own {K:3d}  n {n:2d}  ms per step: prefix form {row['step_ms']:7.3f} (spread {row['step_spread_ms']})  full prompts {row['full_step_ms']:7.3f} (spread {row['full_step_spread_ms']})   "
+              f"token 0 for all: prefix form {row['token0_ms']:9.2f} ms ({row['token0_cached_ms']} with the prefix already in the cache; spread {row['token0_spread_ms']})  "
+              f"full prompts {row['full_token0_ms']:9.2f} ms (spread {row['full_token0_spread_ms']})   cache rows: {row['rows_prefix']} against {row['rows_full']}", flush=True)
+    res["prefix"] = S; res["max_seq_len"] = max_seq
+    res["ids_and_states_agree"] = bool(ok)
+    res["fallback"] = ctx.query("fallback")
+    print(json.dumps(res), flush=True)
+    ctx.close()
+    sys.exit(0 if ok else 1)
 
 if opt.admit:
     FORMS = (("joins", None), ("pass0", 0), ("pass256", 256))
