@@ -39,6 +39,7 @@ SYMBOLS = (
     "flm_batch_layout_for", "flm_batch_open", "flm_batch_join", "flm_batch_step", "flm_batch_state", "flm_batch_close", "flm_generate_batch", "flm_op_attention_slots",
     "flm_batch_plan_for", "flm_batch_admit", "flm_batch_pass", "flm_op_attention_segs",
     "flm_batch_layout_prefix_for", "flm_batch_open_prefix", "flm_generate_batch_prefix", "flm_op_attention_slots_prefix", "flm_op_attention_segs_prefix",
+    "flm_tree_validate", "flm_tree_walk", "flm_verify_tree_greedy", "flm_op_attention_tree",
 )
 
 # flm_score (include/flm_gpu.h): one row of flm_score_tokens / flm_op_score_rows
@@ -831,6 +832,16 @@ class Ctx:
         _check(lib().flm_last_tokens(self._h, int(n), _p(out)), self._h)
         return out
 
+    def verify_tree(self, pos, tokens, parent):
+        """flm_verify_tree_greedy -> (ids, path): tokens[0] fed at pos, node i > 0 a draft behind node parent[i] < i (parent[0] = -1, 2 <= n <= 16).  path = the accepted
+        nodes from the root (0) down, ids = the rows' greedy ids along it -- what the decode loop started with tokens[0] at pos produces in len(path) steps"""
+        t = np.ascontiguousarray(tokens, dtype=np.int32); par = np.ascontiguousarray(parent, dtype=np.int32)
+        if len(t) != len(par):
+            raise ValueError("verify_tree: tokens and parent differ in length")
+        ids = np.empty(max(len(t), 1), dtype=np.int32); path = np.empty_like(ids); cnt = C.c_int(0)
+        _check(lib().flm_verify_tree_greedy(self._h, int(pos), len(t), _p(t), _p(par), _p(ids), C.byref(cnt), _p(path)), self._h)
+        return ids[:cnt.value].copy(), path[:cnt.value].copy()
+
     def reset_kv(self):
         _check(lib().flm_reset_kv(self._h), self._h)
 
@@ -1320,6 +1331,34 @@ def op_attention_slots(kc, vc, q, k, v, n_heads, hs, max_seq, base, pos):
     assert q.shape == k.shape == v.shape == (n, n_heads * hs)
     out = np.empty((n, n_heads * hs), dtype=np.float32)
     _check(lib().flm_op_attention_slots(_p(out), _p(kc), _p(vc), _p(q), _p(k), _p(v), n_heads, hs, max_seq, n, _p(b), _p(ps)))
+    return out
+
+
+def tree_validate(parent):
+    """flm_tree_validate: raises FlmError naming the rule that is broken"""
+    par = np.ascontiguousarray(parent, dtype=np.int32)
+    _check(lib().flm_tree_validate(len(par), _p(par)))
+
+
+def tree_walk(tokens, parent, row_ids):
+    """flm_tree_walk: the accept walk's host restatement -> the accepted node indices, the root first"""
+    t = np.ascontiguousarray(tokens, dtype=np.int32); par = np.ascontiguousarray(parent, dtype=np.int32); a = np.ascontiguousarray(row_ids, dtype=np.int32)
+    assert len(t) == len(par) == len(a)
+    path = np.empty(max(len(t), 1), dtype=np.int32); cnt = C.c_int(0)
+    _check(lib().flm_tree_walk(len(t), _p(t), _p(par), _p(a), _p(path), C.byref(cnt)))
+    return path[:cnt.value].copy()
+
+
+def op_attention_tree(kc, vc, q, k, v, n_heads, hs, max_seq, pos, parent):
+    """one tree verify pass's attention: q, k, v [n, n_heads*hs]; row i at logical position pos + depth(i), its k / v go to cache row pos + i, its query attends rows
+    [0, pos) and its ancestors.  kc, vc [n_heads, max_seq, hs] are updated in place; returns out [n, n_heads*hs]."""
+    for a in (kc, vc):
+        assert a.dtype == np.float32 and a.flags.c_contiguous
+    par = np.ascontiguousarray(parent, dtype=np.int32); n = len(par)
+    q = np.ascontiguousarray(q, dtype=np.float32); k = np.ascontiguousarray(k, dtype=np.float32); v = np.ascontiguousarray(v, dtype=np.float32)
+    assert q.shape == k.shape == v.shape == (n, n_heads * hs)
+    out = np.empty((n, n_heads * hs), dtype=np.float32)
+    _check(lib().flm_op_attention_tree(_p(out), _p(kc), _p(vc), _p(q), _p(k), _p(v), n_heads, hs, max_seq, int(pos), n, _p(par)))
     return out
 
 

@@ -398,6 +398,29 @@ static int spec_step(flm_ctx* c, int pos, int k, int ngram_max, int n_hist, int 
     return FLM_OK;
 }
 
+// spec_step for the plain greedy lookup loop under "spec_branches" B > 1: k_spec_draft_tree drafts a tree of k + 1 nodes from the history (tokens into the batch, parents /
+// depths / masks into tree_dev: nothing of it goes through the host, which knows pos and n), the tree pass verifies it, k_tree_accept leaves the run in the loop's result
+// block -- cut at room and the stop token, appended to the history -- and k_tree_keep moves the accepted rows into place.  Enqueues only
+static int spec_step_tree(flm_ctx* c, int pos, int k, int ngram_max, int n_hist, int stop, int room, int branches) {
+    const int B = k + 1;
+    hipLaunchKernelGGL(k_spec_draft_tree, dim3(1), dim3(kSampleBlock), 0, c->stream, (const int*)c->spec_hist, n_hist, k, ngram_max, branches, c->prompt_dev, c->tree_dev);
+    HIPC(c, hipGetLastError());
+    TreeDesc f{}; f.pos = pos; f.n = B;
+    const bool skinny = c->spec_gemm != 0;
+    int r = prefill_batched_qt(c, B, pos, true, skinny, nullptr, 0, nullptr, nullptr, nullptr, &f, c->tree_dev); if (r) return r;
+    int chunk = 1; float* const stage = score_stage(c, &chunk);
+    const SpecDraw draw{0.0f, 0.0f, 0ull};
+    for (int r0 = 0; r0 < B; r0 += chunk) {
+        const int m = B - r0 < chunk ? B - r0 : chunk;
+        r = spec_classify(c, r0, m, stage, skinny, c->spec_arg, draw); if (r) return r;
+    }
+    hipLaunchKernelGGL(k_tree_accept, dim3(1), dim3(kWave), 0, c->stream, c->tree_res, (const int*)c->spec_arg, (const int*)c->prompt_dev, f, (const TreeDesc*)c->tree_dev, c->spec_res, c->spec_hist, n_hist, stop, room, 0ull);
+    HIPC(c, hipGetLastError());
+    hipLaunchKernelGGL(k_tree_keep, dim3(c->d.n_layers * c->heads_local), dim3(64), 0, c->stream, c->kcache, c->vcache, c->kv_rows, c->hs, pos, (const TreeOut*)c->tree_res);
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
+
 } // namespace fh
 
 extern "C" {
@@ -709,6 +732,52 @@ int flm_verify_sample_ex(flm_ctx* c, int32_t first_token, const int32_t* drafts,
     return verify_impl(c, first_token, drafts, k, pos, dr, out_tokens, n_out);
 }
 
+// Tree draft-and-verify, greedy (include/flm_gpu.h; kernels: flm_tree.h).  The verify pass of flm_verify_greedy with the batch's rows a TREE: the n tokens go to the device as
+// the batch, the parent array as a launch descriptor (depths and ancestor masks, built here) -- RoPE per row at pos + depth, the attention over the cache and the row's
+// ancestors; every other launch of the pass is the chain's.  Behind the classifier and the rows' first maxima k_tree_accept walks the path and k_tree_keep moves its K/V rows
+// to [pos, pos + count) -- both on the stream, so the count, the ids and the path come back in ONE trip.  A re-run attempt rewrites all n rows of a layer before that layer's
+// attention reads them, and the accept block is a function of the rows: it enqueues the same work.
+int flm_tree_validate(int n, const int32_t* parent) {
+    if (const char* why = tree_check(n, parent)) { g_last_error = why; return FLM_ERR_INVALID; }
+    return FLM_OK;
+}
+int flm_tree_walk(int n, const int32_t* tokens, const int32_t* parent, const int32_t* row_ids, int32_t* out_path, int* out_count) {
+    if (!tokens || !row_ids || !out_path || !out_count) { g_last_error = "tree: null argument"; return FLM_ERR_INVALID; }
+    if (int r = flm_tree_validate(n, parent)) return r;
+    *out_count = tree_walk(n, tokens, parent, row_ids, out_path);
+    return FLM_OK;
+}
+int flm_verify_tree_greedy(flm_ctx* c, int pos, int n, const int32_t* tokens, const int32_t* parent, int32_t* out_ids, int* out_count, int32_t* out_path) {
+    if (!c || !tokens || !parent || !out_ids || !out_count) return fail(c, FLM_ERR_INVALID, "verify_tree: null argument");
+    if (const char* why = tree_check(n, parent)) return fail(c, FLM_ERR_INVALID, why);
+    if (sharded(c)) return fail(c, FLM_ERR_UNSUPPORTED, "verify_tree: one GPU only");
+    if (c->hs > 128) return fail(c, FLM_ERR_UNSUPPORTED, "verify_tree: head sizes above 128 are not built (k_attn_tree)");
+    int r = check_ready(c, n, pos); if (r) return r;
+    if (!ids_in_vocab(c, tokens, n)) return fail(c, FLM_ERR_INVALID, "verify_tree: token outside [0, vocab)");
+    const TreeDesc f = tree_fill(pos, n, parent);
+    const SpecDraw draw{0.0f, 0.0f, 0ull};                                                // (the rows' first maxima: no coin, no shape, no record)
+    TreeOut to{};
+    return with_retry(c, n, [&]() -> int {
+        int r = h2d(c, c->prompt_dev, tokens, sizeof(int) * (size_t)n); if (r) return r;
+        const bool skinny = c->spec_gemm != 0;
+        r = prefill_batched_qt(c, n, pos, true, skinny, nullptr, 0, nullptr, nullptr, nullptr, &f); if (r) return r;
+        int chunk = 1; float* const stage = score_stage(c, &chunk);
+        for (int r0 = 0; r0 < n; r0 += chunk) {
+            const int m = n - r0 < chunk ? n - r0 : chunk;
+            r = spec_classify(c, r0, m, stage, skinny, c->spec_arg, draw); if (r) return r;
+        }
+        hipLaunchKernelGGL(k_tree_accept, dim3(1), dim3(kWave), 0, c->stream, c->tree_res, (const int*)c->spec_arg, (const int*)c->prompt_dev, f, (const TreeDesc*)nullptr, (SpecOut*)nullptr, (int*)nullptr, 0, -1, 0, 0ull);
+        HIPC(c, hipGetLastError());
+        hipLaunchKernelGGL(k_tree_keep, dim3(c->d.n_layers * c->heads_local), dim3(64), 0, c->stream, c->kcache, c->vcache, c->kv_rows, c->hs, pos, (const TreeOut*)c->tree_res);
+        HIPC(c, hipGetLastError());
+        return d2h(c, &to, c->tree_res, sizeof to);                                   // (the count, the ids and the path in one trip; the error word rides along)
+    }, [&] {
+        memcpy(out_ids, to.ids, sizeof(int32_t) * (size_t)to.count);
+        if (out_path) memcpy(out_path, to.path, sizeof(int32_t) * (size_t)to.count);
+        *out_count = to.count;
+    });
+}
+
 // flm_generate with several ids per pass over the weights: the prompt enters as in flm_forward_argmax / flm_forward_sample (token 0 is drawn from its last logits, with the
 // first coin); then every step drafts draft_len tokens ON THE DEVICE from the call's history (k_spec_draft), verifies them in one batch of draft_len + 1 rows and accepts the
 // longest prefix the model would have produced itself (k_spec_accept_sample: cut at the stop token and at max_tokens, appended to the history).  The batched kernels take the
@@ -750,6 +819,8 @@ static int generate_lookup_impl(flm_ctx* c, const int32_t* prompt, int n_prompt,
     const TokenForm d_form = dr.temperature != 0.0f ? TokenForm::Sampled : TokenForm::Greedy;      // the draft's plain form
     int d_rows = pos, d_tokens = 0;                                  // draft: the cache rows it holds of this sequence / tokens it computed in this call
     const int stop = stop_token < 0 ? -1 : stop_token;
+    // "spec_branches" B > 1: the PLAIN greedy form with the prompt-lookup drafter drafts and verifies a tree (spec_step_tree); every other form keeps the chain
+    const bool tree = c->spec_branches > 1 && !d && dr.form == TokenForm::Greedy && !dr.rules && c->hs <= 128;
     int total = 0, steps = 0, accepted = 0; bool done = false, cancelled = false;
     int32_t last_tok = 0;
     // the running copies the host holds for re-runnable steps, handed to the plan's commit at the end: the sampler's state and the constraint's state behind the ids
@@ -800,7 +871,8 @@ static int generate_lookup_impl(flm_ctx* c, const int32_t* prompt, int n_prompt,
                 r = draft_rc(c, d, run_tokens(d, at, draft_len, d_form)); if (r) return r;
                 r = draft_close(c, d); if (r) return r;
             }
-            if (batch) {       // (the block: as token 0's attempt left it; the rows' windows: the history; records land behind the ids delivered so far)
+            if (batch && tree) r = spec_step_tree(c, at, draft_len, ngram_max, n_hist, stop, room, c->spec_branches);
+            else if (batch) {       // (the block: as token 0's attempt left it; the rows' windows: the history; records land behind the ids delivered so far)
                 r = spec_step(c, at, draft_len, ngram_max, n_hist, stop, room, true, dr.batch(c, state, c->spec_hist, n_hist, cst, total), rules, n_prompt, d);
             }
             else {      // one token through the token graph and the accept kernel with K = 0: the id from the decode state's first output slot, cut / appended / counted like a verified run of one

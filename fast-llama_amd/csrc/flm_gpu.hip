@@ -341,6 +341,8 @@ int alloc_run_bufs(flm_ctx* c) {
     HIPC(c, dev_alloc(c, &c->fan_drawn, sizeof(int) * kFanMax, true));                      // flm_generate_n: a step's drawn ids, the states behind the draws, its result block
     HIPC(c, dev_alloc(c, &c->fan_after, sizeof(unsigned long long) * kFanMax, true));
     HIPC(c, dev_alloc(c, &c->fan_res, sizeof(FanOut), true));
+    HIPC(c, dev_alloc(c, &c->tree_res, sizeof(TreeOut), true));                             // flm_verify_tree_greedy: the result block
+    HIPC(c, dev_alloc(c, &c->tree_dev, sizeof(TreeDesc), true));                            // ... and the tree k_spec_draft_tree drafts ("spec_branches")
     HIPC(c, dev_alloc(c, &c->batch_res, sizeof(SlotOut), true));                            // flm_batch_join / flm_batch_step: the result block
     HIPC(c, dev_alloc(c, &c->batch_views, sizeof(AttnArgs) * kBatchMax, true));            // ... and k_attn_slots' views
     HIPC(c, dev_alloc(c, &c->seg_views, sizeof(AttnArgs) * kBatchMax, true));              // flm_batch_pass: the prompt segments' views (flm_segs.h)
@@ -798,6 +800,7 @@ int flm_set_option(flm_ctx* c, const char* key, int value) {
         else if (c->world > 1 && !c->comm) return fail(c, FLM_ERR_STATE, "use_p2p 0: no RCCL communicator (comm_id was NULL at create)");
         c->p2p = value ? 1 : 0;
     }
+    else if (k == "spec_branches") { if (value < 1 || value > 4) return fail(c, FLM_ERR_INVALID, "spec_branches: 1 .. 4"); c->spec_branches = value; return FLM_OK; }
     else if (k == "spec_gemm") { c->spec_gemm = value ? 1 : 0; return FLM_OK; }      // (read per call by the new entry points only: no captured graph depends on it)
     else if (k == "batch_rows") { c->batch_rows = value < 0 ? -1 : value; return FLM_OK; }      // (read per flm_generate_batch call: no captured graph depends on it)
     else if (kAblate && k == "ablate") c->ablate = value;              // FLM_ABLATE builds only: a product library cannot skip work
@@ -866,7 +869,7 @@ int flm_query(flm_ctx* c, const char* key, int* value) {
         {"stop_rule", c->stop_rule},
         {"gen_tokens", c->gen_tokens},
         {"gen_streamed", c->gen_streamed},
-        {"spec_steps", c->spec_steps},
+        {"spec_steps", c->spec_steps}, {"spec_branches", c->spec_branches},
         {"spec_accepted", c->spec_accepted},
         {"draft_tokens", c->draft_tokens},
         {"batch_passes", c->batch_passes},

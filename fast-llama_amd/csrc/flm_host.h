@@ -195,6 +195,7 @@ struct flm_ctx {
     int* spec_hist = nullptr; int* spec_arg = nullptr; flm::SpecOut* spec_res = nullptr;
     int spec_gemm = 0;                                 // option "spec_gemm": 1 = the verify pass's int8 GEMMs through k_gemm_q8_skinny (B <= 16), 0 (default until both forms have been timed: DESIGN.md section 5e) = the 64 x 64 tiles; the new entry points only
     int spec_steps = 0, spec_accepted = 0;
+    int spec_branches = 1;                             // option "spec_branches": B > 1 = the plain greedy lookup loop drafts a TREE from the B most recent distinct history matches (flm_tree.h); 1: the chain, today's launches
     // the model-based drafter (include/flm_gpu.h flm_draft_set / flm_generate_draft; flm_calls.hip generate_lookup_impl): the paired draft context (not owned; null: none),
     // the two events that order its stream and this one -- [0] recorded here, waited for there, in front of everything the draft enqueues; [1] recorded there, waited for
     // here, behind it -- created by flm_draft_set, and how many tokens the draft computed in the last call ("draft_tokens").  The draft's error word travels to the second
@@ -218,7 +219,7 @@ struct flm_ctx {
     // parallel sampling (include/flm_gpu.h flm_generate_n / flm_fan_keep; flm_calls.hip; kernels: flm_fan.h): a step's drawn ids [16] and the states behind the draws [16],
     // its result block (one trip per step) -- device memory since create --, and what flm_fan_keep needs of the last call: its layout and every sequence's count
     // (fan_valid: until the next call that writes the cache)
-    int* fan_drawn = nullptr; unsigned long long* fan_after = nullptr; flm::FanOut* fan_res = nullptr;
+    int* fan_drawn = nullptr; unsigned long long* fan_after = nullptr; flm::FanOut* fan_res = nullptr; flm::TreeOut* tree_res = nullptr; flm::TreeDesc* tree_dev = nullptr;
     flm_fan_layout fan_lay{}; int fan_count[FLM_FAN_MAX] = {0}; bool fan_valid = false;
     // cache slots (include/flm_gpu.h flm_batch_*; flm_calls.hip; kernels: flm_batch.h): the open batch's layout, what the host holds of every slot between two steps, and
     // the step's result block in device memory since create (the drawn ids and the states behind the draws share the fan's two arrays).  batch_open: until flm_batch_close
@@ -468,7 +469,7 @@ int feed(flm_ctx* c, const int32_t* tokens, int n, int pos, TokenForm last);
 int d2h(flm_ctx* c, void* dst, const void* src_dev, size_t bytes);
 float* score_stage(const flm_ctx* c, int* chunk);
 constexpr int kPrefillMin = 4;
-int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers = false, bool skinny = false, const flm::FanDesc* fan = nullptr, int row0 = 0, const flm::SlotDesc* slots = nullptr, const flm::SegDesc* segs = nullptr, const flm::PrefixDesc* pfx = nullptr);      // (flm_prompt.hip; by the model's quant type.  all_layers: the last layer is completed too -- flm_score_tokens needs every row's final residual; skinny: int8 and B <= 16: every GEMM through k_gemm_q8_skinny -- the verify pass under "spec_gemm" 1; fan: the rows are a fan step's -- flm_generate_n; row0: the batch is a prompt entering the cache slot that starts at physical row row0 -- flm_batch_join; slots: the rows are a batch step's -- flm_batch_step; segs: a ragged pass -- flm_batch_pass: rows [0, n_step) are a step's (slots, where n_step > 0), the rest prompt segments; pfx, S > 0: the slots lie behind S shared rows -- flm_batch_open_prefix: pos / pos0 count them, base stays physical, and the attention is flm_prefix.h's; null or S == 0: every launch is the one made without it)
+int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers = false, bool skinny = false, const flm::FanDesc* fan = nullptr, int row0 = 0, const flm::SlotDesc* slots = nullptr, const flm::SegDesc* segs = nullptr, const flm::PrefixDesc* pfx = nullptr, const flm::TreeDesc* tree = nullptr, const flm::TreeDesc* tree_dev = nullptr);      // (flm_prompt.hip; by the model's quant type.  tree: the rows are a tree of candidates -- flm_verify_tree_greedy, flm_tree.h;  all_layers: the last layer is completed too -- flm_score_tokens needs every row's final residual; skinny: int8 and B <= 16: every GEMM through k_gemm_q8_skinny -- the verify pass under "spec_gemm" 1; fan: the rows are a fan step's -- flm_generate_n; row0: the batch is a prompt entering the cache slot that starts at physical row row0 -- flm_batch_join; slots: the rows are a batch step's -- flm_batch_step; segs: a ragged pass -- flm_batch_pass: rows [0, n_step) are a step's (slots, where n_step > 0), the rest prompt segments; pfx, S > 0: the slots lie behind S shared rows -- flm_batch_open_prefix: pos / pos0 count them, base stays physical, and the attention is flm_prefix.h's; null or S == 0: every launch is the one made without it)
 // a fan step's pieces (flm_prompt.hip; kernels: flm_fan.h).  fan_classify: rows [row0, row0 + m) through score_classify's prologue and GEMM into `stage`, then k_sample_fan
 // into fan_drawn / fan_after, row j with in.rng[j].  The launchers take c == null from the op-level mirror (flm_op_attention_fan)
 int fan_classify(flm_ctx* c, int row0, int m, float* stage, bool skinny, float temperature, float topp, const flm::FanIn& in);
@@ -490,6 +491,9 @@ int launch_attn_slots_prefix(flm_ctx* c, hipStream_t st, const flm::AttnArgs& aa
 int launch_attn_segs_prefix(flm_ctx* c, hipStream_t st, const flm::AttnArgs& aa, const flm::SegDesc& f, int S, int heads, int row_stride);
 int launch_attn_fan(flm_ctx* c, hipStream_t st, const flm::AttnArgs& aa, const flm::FanDesc& f, int heads, int row_stride);
 int launch_rope_kv_fan(flm_ctx* c, hipStream_t st, const float* qkv, float* qout, float* kcache, float* vcache, const float* rope_cos, const float* rope_sin, int dim, int hs, int kv_rows, const flm::FanDesc& f);
+// a tree verify pass's pieces (flm_prompt.hip; kernels: flm_tree.h); c may be null (flm_op_attention_tree)
+int launch_attn_tree(flm_ctx* c, hipStream_t st, const flm::AttnArgs& aa, const flm::TreeDesc& f, int heads, int row_stride, const flm::TreeDesc* dev = nullptr);
+int launch_rope_kv_tree(flm_ctx* c, hipStream_t st, const float* qkv, float* qout, float* kcache, float* vcache, const float* rope_cos, const float* rope_sin, int dim, int hs, int kv_rows, const flm::TreeDesc& f, const flm::TreeDesc* dev = nullptr);
 // flm_score_tokens' classifier stage (flm_prompt.hip): rows [row0, row0 + m) of the batch's final residual (pf_x) -> output norm, quantize, the classifier GEMM tiles into
 // `stage` [m][vocab], k_score_rows into score_dev[row0 ..]
 int score_classify(flm_ctx* c, int row0, int m, float* stage);

@@ -61,11 +61,13 @@
 //                         several slots, each at its own position, in the same batch as the running slots' step rows
 //   k_attn_slots_prefix, k_attn_segs_prefix_mq  (flm_prefix.h) cache slots behind a shared prefix (flm_batch_open_prefix): the prefix rows are in the cache once, and a
 //                         group of queries walks "prefix, then own rows" in the logical order with every prefix tile brought to LDS once per group
+//   k_rope_kv_tree, k_attn_tree, k_tree_accept, k_tree_keep, k_spec_draft_tree  (flm_tree.h) tree draft-and-verify (flm_verify_tree_greedy): a verify batch whose rows are a tree of candidates --
+//                         every row attends the cache followed by its ancestors inside the batch (a 16-bit ancestor mask per row), the accepted path is kept
 // plus small op-level kernels that expose the same __device__ functions to the parity tests.
 // (Round 3's weight-streaming engine -- loader / consumer waves around an LDS ring -- was measured slower than these launches and left the library in round 4:
 //  tools/experiments/engine/, numbers in profiles/r03_engine_timelines.txt.)
 //
-// The code lives in: flm_math.h (exact scalar / wave building blocks), flm_wait.h (every cross-workgroup wait: flag polls, granule pieces, the give-up policy), flm_gemv.h, flm_attn.h, flm_layer.h, flm_prefill.h, flm_misc.h, flm_sample.h, flm_score.h, flm_logprob.h, flm_spec.h, flm_stop.h, flm_fan.h, flm_batch.h, flm_segs.h, flm_prefix.h, flm_entropy.h (with flm_logf.h, the logarithm the host compiles too).
+// The code lives in: flm_math.h (exact scalar / wave building blocks), flm_wait.h (every cross-workgroup wait: flag polls, granule pieces, the give-up policy), flm_gemv.h, flm_attn.h, flm_layer.h, flm_prefill.h, flm_misc.h, flm_sample.h, flm_score.h, flm_logprob.h, flm_spec.h, flm_stop.h, flm_fan.h, flm_tree.h, flm_batch.h, flm_segs.h, flm_prefix.h, flm_entropy.h (with flm_logf.h, the logarithm the host compiles too).
 #pragma once
 #include "flm_math.h"
 #include "flm_wait.h"
@@ -82,6 +84,7 @@
 #include "flm_logprob.h"
 #include "flm_spec.h"
 #include "flm_fan.h"
+#include "flm_tree.h"
 #include "flm_batch.h"
 #include "flm_segs.h"
 #include "flm_prefix.h"

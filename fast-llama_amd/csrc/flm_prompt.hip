@@ -110,6 +110,33 @@ int launch_rope_kv_fan(flm_ctx* c, hipStream_t st, const float* qkv, float* qout
     return FLM_OK;
 }
 
+// k_attn_tree on the n rows of a tree verify pass (flm_tree.h): queries per workgroup by what the LDS allows, as the fan; c may be null (flm_op_attention_tree)
+int launch_attn_tree(flm_ctx* c, hipStream_t st, const AttnArgs& aa, const TreeDesc& f, int heads, int row_stride, const TreeDesc* dev) {
+    {   // a group's score rows and tiles can take most of the LDS: raise the kernel's dynamic-LDS limit, once per device
+        static std::mutex mu; static bool done[64] = {false};
+        int dev = 0; HIPC(c, hipGetDevice(&dev));
+        std::lock_guard<std::mutex> lk(mu);
+        if (dev >= 0 && dev < 64 && !done[dev]) {
+            HIPC(c, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attn_tree), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
+            done[dev] = true;
+        }
+    }
+    if (aa.hs % 8 || aa.n_peer || f.n < 1 || f.n > kTreeMax || f.pos < 0 || f.pos + f.n > aa.max_seq) return fail(c, FLM_ERR_INVALID, "attn_tree: 1 .. 16 rows, pos + n <= max_seq_len, one GPU");
+    if (aa.hs > 128) return fail(c, FLM_ERR_UNSUPPORTED, "attn_tree: head sizes above 128 are not built");
+    for (int i = 0; i < f.n && !dev; ++i)      // (dev: the drafter kernel built them.  The kernel trusts the masks: bit i set, nothing at or above bit n, the depth = the ancestors in front)
+        if (!((f.mask[i] >> i) & 1u) || (f.mask[i] >> (i + 1)) || __builtin_popcount(f.mask[i]) != f.depth[i] + 1) return fail(c, FLM_ERR_INVALID, "attn_tree: a row's ancestor mask and depth disagree");
+    const int G = fan_group(aa.max_seq, aa.hs, kLdsMax);
+    if (fan_lds_bytes(G, aa.max_seq, aa.hs) > kLdsMax) return fail(c, FLM_ERR_UNSUPPORTED, "attn_tree: one query's scores do not fit the LDS");
+    hipLaunchKernelGGL(k_attn_tree, dim3(heads, (f.n + G - 1) / G), dim3(kAttnBlock), fan_lds_bytes(G, aa.max_seq, aa.hs), st, aa, f, dev, row_stride, G);
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
+int launch_rope_kv_tree(flm_ctx* c, hipStream_t st, const float* qkv, float* qout, float* kcache, float* vcache, const float* rope_cos, const float* rope_sin, int dim, int hs, int kv_rows, const TreeDesc& f, const TreeDesc* dev) {
+    hipLaunchKernelGGL(k_rope_kv_tree, dim3(f.n), dim3(256), 0, st, qkv, qout, kcache, vcache, rope_cos, rope_sin, dim, hs, kv_rows, f, dev);
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
+
 // k_slot_views + k_attn_slots on the n live rows of a batch step (flm_batch.h): one workgroup per (head, row), the LDS of the largest slot; views: device memory for 16
 // AttnArgs; c may be null (flm_op_attention_slots)
 int launch_attn_slots(flm_ctx* c, hipStream_t st, const AttnArgs& aa, const SlotDesc& f, int heads, int row_stride, AttnArgs* views) {
@@ -202,8 +229,11 @@ int launch_rope_kv_segs(flm_ctx* c, hipStream_t st, const float* qkv, float* qou
 // where n_step is 0) and keep the step's launches, the rest are prompt segments: k_rope_kv_segs and k_attn_segs_mq / k_attn_segs on the same q / out buffers
 // pfx (flm_batch_open_prefix; null or S == 0: every launch is the one made without it): the slots of `slots` / `segs` lie behind S shared rows -- pos / pos0 are LOGICAL and
 // count them, base is PHYSICAL.  RoPE and the cache rows keep their kernels, which place a row at base + pos: they get copies with base - S.  The attention is flm_prefix.h's
+// tree (flm_verify_tree_greedy; null: every launch is the one made without it): the B rows are a tree of candidates at `pos` (flm_tree.h) -- the fan's route with
+// k_rope_kv_tree and k_attn_tree; tree_dev (the lookup loop under "spec_branches"): the rows' parents, depths and masks are the ones k_spec_draft_tree left in device
+// memory, `tree` carries pos and n only
 template <int QT>
-int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req = false, const FanDesc* fan = nullptr, int row0 = 0, const SlotDesc* slots = nullptr, const SegDesc* segs = nullptr, const PrefixDesc* pfx = nullptr) {
+int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req = false, const FanDesc* fan = nullptr, int row0 = 0, const SlotDesc* slots = nullptr, const SegDesc* segs = nullptr, const PrefixDesc* pfx = nullptr, const TreeDesc* tree = nullptr, const TreeDesc* tree_dev = nullptr) {
     const int S = pfx ? pfx->S : 0;
     SlotDesc rope_slots{}; SegDesc rope_segs{};
     if (S > 0 && slots) { rope_slots = *slots; for (int i = 0; i < kBatchMax; ++i) rope_slots.base[i] -= S; }
@@ -242,7 +272,11 @@ int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req
         RowsArgs ra{c->pf_x, w.att_norm, c->pf_xq, c->pf_xs, dim, c->pf_xst};
         r = launch_rows<QT, PRO_RMSNORM_QUANT>(c, st, ra, B, tp); if (r) return r;
         GemmArgs g{w.qkv.q, w.qkv.s, c->pf_xq, c->pf_xs, c->pf_qkv, 3 * dimL, dim, 3 * dimL, B, c->pf_xst, w.qkv.st};
-        if (fan) {
+        if (tree) {
+            r = launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, skinny); if (r) return r;
+            r = launch_rope_kv_tree(c, st, c->pf_qkv, c->pf_q, kc, vc, c->rope_cos, c->rope_sin, dimL, hs, c->kv_rows, *tree, tree_dev); if (r) return r;
+        }
+        else if (fan) {
             r = launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, skinny); if (r) return r;
             r = launch_rope_kv_fan(c, st, c->pf_qkv, c->pf_q, kc, vc, c->rope_cos, c->rope_sin, dimL, hs, c->kv_rows, *fan); if (r) return r;
         }
@@ -275,7 +309,8 @@ int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req
         // one query per workgroup needs 4 bytes per position and always fits (flm_ctx_create checked max_seq_len against it)
         const bool mq_fits = attn_mq_lds_bytes(d.max_seq_len, hs) <= kLdsMax;
         const bool pv_mfma = c->use_pv_mfma && (hs & 1) == 0;
-        if (fan) { r = launch_attn_fan(c, st, aa, *fan, c->heads_local, dim); if (r) return r; }
+        if (tree) { r = launch_attn_tree(c, st, aa, *tree, c->heads_local, dim, tree_dev); if (r) return r; }
+        else if (fan) { r = launch_attn_fan(c, st, aa, *fan, c->heads_local, dim); if (r) return r; }
         else if (S > 0) {      // behind a shared prefix: a group of rows walks the prefix tiles once, then the rows' own
             if (slots) { r = launch_attn_slots_prefix(c, st, aa, *slots, S, c->heads_local, dim); if (r) return r; }
             if (segs && segs->n_step < B) { r = launch_attn_segs_prefix(c, st, aa, *segs, S, c->heads_local, dim); if (r) return r; }
@@ -345,7 +380,12 @@ int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req
 int launch_gemm_store(flm_ctx* c, hipStream_t st, int qt, const GemmArgs& g, int use_mfma) {
     return qt == FLM_QT_INT8 ? launch_gemm<QT_INT8, EPI_STORE>(c, st, g, use_mfma) : launch_gemm<QT_INT16, EPI_STORE>(c, st, g, use_mfma);
 }
-int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers, bool skinny, const FanDesc* fan, int row0, const SlotDesc* slots_in, const SegDesc* segs_in, const PrefixDesc* pfx_in) {
+int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers, bool skinny, const FanDesc* fan, int row0, const SlotDesc* slots_in, const SegDesc* segs_in, const PrefixDesc* pfx_in, const TreeDesc* tree, const TreeDesc* tree_dev) {
+    if (tree) {   // (in front of the first launch: k_rope_kv_tree writes the rows' cache rows)
+        if (c->world != 1 || fan || row0 || slots_in || segs_in || pfx_in || tree->n != B || tree->pos != pos || pos < 0 || pos + B > c->d.max_seq_len || c->hs > 128)
+            return fail(c, FLM_ERR_INVALID, "prefill: a tree pass is one GPU's batch of tree.n rows at tree.pos, inside the cache, at head sizes <= 128");
+        return c->d.quant_type == FLM_QT_INT8 ? prefill_batched<QT_INT8>(c, B, pos, all_layers, skinny, nullptr, 0, nullptr, nullptr, nullptr, tree, tree_dev) : prefill_batched<QT_INT16>(c, B, pos, all_layers, skinny, nullptr, 0, nullptr, nullptr, nullptr, tree, tree_dev);
+    }
     // behind a shared prefix the checks below see every row's OWN position (pos - S) in its slot; in front of them: S <= base[s], no slot begins inside the prefix
     const PrefixDesc* const pfx = pfx_in && pfx_in->S != 0 ? pfx_in : nullptr;
     SlotDesc own_slots{}; SegDesc own_segs{};

@@ -380,6 +380,7 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
             }
             else if (_draft_k > 0 || (greedy && _lookup_k > 0)) {
                 const bool draft = _draft_k > 0;
+                flm_set_option(_ctxs[0], "spec_branches", draft ? 1 : _lookup_b);
                 rc = flm_generate_lookup_ex(_ctxs[0], input.data(), n_in, 0, want, &sp, &st, 0, draft ? _draft_k : _lookup_k, draft ? _draft_g : _lookup_g, on_token, &sink, nullptr, &n_out);
                 count();
             }
@@ -403,6 +404,7 @@ bool GpuTransformer::generate(const char* prompt, const std::function<bool(const
             // --draft: the same loop through draft-and-verify steps at the run's temperature; refused (nothing was launched): the run without the flag.
             // --lookup: the same at temperature 0 only (the same ids and callbacks)
             const bool draft = _draft_k > 0;
+            flm_set_option(_ctxs[0], "spec_branches", draft ? 1 : _lookup_b);
             rc = flm_generate_lookup_sample(_ctxs[0], input.data(), n_in, 0, want, temperature, topp, &st, 0, draft ? _draft_k : _lookup_k, draft ? _draft_g : _lookup_g, on_token, &sink, nullptr, &n_out);
             count();
             whole = draft && rc == FLM_ERR_UNSUPPORTED;

@@ -43,7 +43,7 @@ struct Args {
     const char* prompts_file = nullptr; std::vector<std::string> prompts;      // --prompts FILE: one prompt per line, 1..16 lines
     const char* system_text = nullptr;                              // --system TEXT (with --prompts): every line of the file continues this text, which enters the cache once
     int batch_rows = -1; const char* bad_batch_rows = nullptr;      // --batch-rows N (with --prompts): the prompts enter inside the steps' passes, at most N prompt rows per pass (0: no bound; -1 = off)
-    int lookup_k = 0, lookup_g = 3;         // --lookup K[,G]: draft length (4..15; 0 = off) and longest n-gram (1..8) of the prompt-lookup drafter
+    int lookup_k = 0, lookup_g = 3, lookup_b = 1;   // --lookup K[,G[,B]]: draft length (4..15; 0 = off), longest n-gram (1..8) of the prompt-lookup drafter, branches of its tree (1..4; 1: a chain)
     const char* bad_lookup = nullptr;
     int draft_k = 0, draft_g = 3;           // --draft K[,G]: the same drafter and ranges at whatever temperature the run has (-t 0: flm_generate_lookup, else flm_generate_lookup_sample)
     const char* bad_draft = nullptr;
@@ -77,7 +77,7 @@ void usage(const char* bin) {
     fprintf(stderr, "   --threads,-j      <number>    accepted for compatibility (the GPU build has no worker threads)\n");
     fprintf(stderr, "   --device          <number>    HIP device ordinal (this build only)\n");
     fprintf(stderr, "   --devices         <a,b,...>   shard ONE sequence over these HIP devices, 1 to 8 of them (this build only)\n");
-    fprintf(stderr, "   --lookup          <K[,G]>     with -t 0 on one device: draft K (4..15) tokens per step by prompt lookup (n-grams up to G, 1..8, default 3) and verify them in one pass; the same text (this build only)\n");
+    fprintf(stderr, "   --lookup          <K[,G[,B]]> with -t 0 on one device: draft K (4..15) tokens per step by prompt lookup (n-grams up to G, 1..8, default 3; B, 1..4, default 1: a tree of K + 1 nodes from the B most recent distinct matches) and verify them in one pass; the same text (this build only)\n");
     fprintf(stderr, "   --draft           <K[,G]>     on one device, at any temperature: draft K (4..15) tokens per step by prompt lookup (n-grams up to G, 1..8, default 3) and verify them in one pass, sampled rows drawn with the sampler's own coins; the same text (this build only)\n");
     fprintf(stderr, "   --draft-model     <file>      on one device, at any temperature: a second, small model of the same vocabulary (quantisation: the file's own or -q) drafts the K tokens of --draft (default 7) instead of the prompt lookup; the same text (this build only)\n");
     fprintf(stderr, "   --prompts         <FILE>      on one device: the file's lines (1..16, one prompt per line) as independent prompts served together, one batch per pass over the weights, the completions printed in the file's order, each behind a line `--- prompt j ---`; prompt j's sampler state is --seed + j; not with --samples or the other extras of this build (this build only)\n");
@@ -189,8 +189,10 @@ const Flag kFlags[] = {
     {nullptr, "--lookup",      true,  [](Args& a, const char* v) {                                                            // (this build only)
         char* e; const long k = strtol(v, &e, 10); long g = 3;
         bool ok = e != v && k >= 4 && k <= 15;
+        long b = 1;
         if (ok && *e == ',') { const char* s = e + 1; g = strtol(s, &e, 10); ok = e != s && g >= 1 && g <= 8; }
-        if (ok && *e == 0) { a.lookup_k = (int)k; a.lookup_g = (int)g; } else a.bad_lookup = v; }},
+        if (ok && *e == ',') { const char* s = e + 1; b = strtol(s, &e, 10); ok = e != s && b >= 1 && b <= 4; }
+        if (ok && *e == 0) { a.lookup_k = (int)k; a.lookup_g = (int)g; a.lookup_b = (int)b; } else a.bad_lookup = v; }},
     {nullptr, "--draft",       true,  [](Args& a, const char* v) { if (!parse_draft(v, a.draft_k, a.draft_g)) a.bad_draft = v; }},                 // (this build only)
     {nullptr, "--prompts",     true,  [](Args& a, const char* v) { a.prompts_file = v; }},   // (this build only)
     {nullptr, "--system",      true,  [](Args& a, const char* v) { a.system_text = v; }},    // (this build only)
@@ -231,7 +233,7 @@ void parse(Args& a, int argc, const char** argv) {
         hit->apply(a, v);
         if (a.bad_devices) { fprintf(stderr, "Invalid --devices list:\x1b[31m%s\x1b[0m (expected 1 to 8 HIP device ordinals, e.g. 0,1,2,3)\n", a.bad_devices); usage(argv[0]); exit(-1); }
     }
-    if (a.bad_lookup) { fprintf(stderr, "Invalid --lookup:\x1b[31m%s\x1b[0m (expected K or K,G with 4 <= K <= 15 and 1 <= G <= 8)\n", a.bad_lookup); usage(argv[0]); exit(-1); }
+    if (a.bad_lookup) { fprintf(stderr, "Invalid --lookup:\x1b[31m%s\x1b[0m (expected K, K,G or K,G,B with 4 <= K <= 15, 1 <= G <= 8 and 1 <= B <= 4)\n", a.bad_lookup); usage(argv[0]); exit(-1); }
     if (a.prompts_file) {      // a file that cannot be read, or whose line count is out of range, is a usage error, before any model is loaded
         FILE* f = fopen(a.prompts_file, "rb");
         std::string line; int ch; bool any = false;
@@ -249,7 +251,7 @@ void parse(Args& a, int argc, const char** argv) {
     }
     if (a.bad_batch_rows) { fprintf(stderr, "Invalid --batch-rows:\x1b[31m%s\x1b[0m (expected a number of prompt rows per pass, 0 for no bound)\n", a.bad_batch_rows); usage(argv[0]); exit(-1); }
     if (a.bad_samples) { fprintf(stderr, "Invalid --samples:\x1b[31m%s\x1b[0m (expected a number of completions, 1 to 16)\n", a.bad_samples); usage(argv[0]); exit(-1); }
-    if (a.bad_draft) { fprintf(stderr, "Invalid --draft:\x1b[31m%s\x1b[0m (expected K or K,G with 4 <= K <= 15 and 1 <= G <= 8)\n", a.bad_draft); usage(argv[0]); exit(-1); }
+    if (a.bad_draft) { fprintf(stderr, "Invalid --draft:\x1b[31m%s\x1b[0m (expected K, K,G or K,G,B with 4 <= K <= 15, 1 <= G <= 8 and 1 <= B <= 4)\n", a.bad_draft); usage(argv[0]); exit(-1); }
     if (!a.bad_sampling && a.mirostat == 2 && a.typical > 0.0f && a.typical < 1.0f) a.bad_sampling = "--typical together with --mirostat 2";
     if (a.bad_sampling) { fprintf(stderr, "Invalid sampling control:\x1b[31m%s\x1b[0m (--top-k >= 0, --min-p in [0, 1), --repeat-penalty > 0, --repeat-last-n 0..1024, --logit-bias id=val[,id=val...] with at most 256 pairs, --typical a number, --mirostat 0 or 2 with finite --mirostat-ent / --mirostat-lr, never --typical in (0, 1) together with --mirostat 2)\n", a.bad_sampling); usage(argv[0]); exit(-1); }
     if (a.bad_logprobs) { fprintf(stderr, "Invalid --logprobs:\x1b[31m%s\x1b[0m (expected N or N,shaped with 0 <= N <= 20)\n", a.bad_logprobs); usage(argv[0]); exit(-1); }
@@ -372,7 +374,7 @@ int main(int argc, const char** argv) {
     if (args.ent_set) tf.set_entropy(flm_entropy{args.typical, args.mirostat, args.miro_tau, args.miro_eta, 2.0f * args.miro_tau});
     if (args.logprobs_n >= 0) tf.set_logprobs(args.logprobs_n, args.logprobs_shaped);
     if (stop_set) tf.set_stop(args.stop_ids, args.stop_seqs, args.stop_strs);
-    if (args.lookup_k) tf.set_lookup(args.lookup_k, args.lookup_g);
+    if (args.lookup_k) tf.set_lookup(args.lookup_k, args.lookup_g, args.lookup_b);
     if (args.draft_k) tf.set_draft(args.draft_k, args.draft_g);
     if (!tf.load(args.ckpt, args.tknr, args.ft, args.qtype, args.devices)) { fprintf(stderr, "Failed to load model\n%s\n", tf.error().c_str()); return 1; }
     if (!args.draft_model.empty() && !tf.load_draft(args.draft_model, args.tknr, args.ft, args.qtype, args.devices[0])) { fprintf(stderr, "Failed to load the draft model\n%s\n", tf.error().c_str()); return 1; }

@@ -194,6 +194,23 @@ int  flm_score_tokens(flm_ctx* ctx, const int32_t* tokens, int n, int pos,
  * tiles of the prompt path.  int16 models always run the hi / lo-plane tiles here: correct, not fast. */
 int  flm_verify_greedy(flm_ctx* ctx, int32_t first_token, const int32_t* drafts, int k, int pos,
                        int32_t* out_tokens /* [k + 1] */, int* n_out);
+/* Tree draft-and-verify, greedy: flm_verify_greedy with the batch's rows a TREE of candidates, for callers whose drafter has several continuations to offer.  tokens[0] is the
+ * token fed at pos (parent[0] = -1); node i > 0 is a draft behind node parent[i], 0 <= parent[i] < i; 2 <= n <= FLM_TREE_MAX; pos + n <= max_seq_len.  Node i is at LOGICAL
+ * position pos + depth(i) and attends the cache rows [0, pos) followed by its ancestors root .. i, so its row of logits is flm_forward's behind the path root .. i, bit for
+ * bit; a[i] = that row's first maximum.  The accepted path starts at the root and steps to the child of the current node whose token is a[current] -- among children with
+ * equal tokens the lowest index -- until there is none.  *out_count = the nodes on the path; out_ids[0 .. count) = a[] along it: exactly what the greedy decode loop started
+ * with tokens[0] at pos returns for count steps; out_path[0 .. count) (may be NULL) = the path's node indices, out_path[0] = 0.  Afterwards the K/V rows pos .. pos + count - 1
+ * hold the path's nodes in depth order and are the token path's bits (during the pass node i lives in row pos + i; the accepted ones are moved on the device); the rows
+ * behind them are stale; the caller continues at pos + count with token out_ids[count - 1], through any entry point.  One pass over the weights, the ids and the path in one
+ * trip, nothing allocated; "spec_gemm" as in flm_verify_greedy.  Errors, with nothing launched and the cache untouched: FLM_ERR_INVALID as flm_tree_validate reports it, for
+ * pos + n > max_seq_len and ids outside [0, vocab); FLM_ERR_UNSUPPORTED for world > 1 and head sizes above 128; FLM_ERR_STATE before the model is complete.
+ * flm_tree_validate (pure host arithmetic, like flm_dfa_validate): FLM_OK, or FLM_ERR_INVALID with flm_last_error(NULL) naming the rule.  flm_tree_walk: the accept walk's
+ * host restatement over given row ids a[] (what the device computes; for callers' tests and tools). */
+#define FLM_TREE_MAX 16
+int  flm_tree_validate(int n, const int32_t* parent /* [n] */);
+int  flm_tree_walk(int n, const int32_t* tokens, const int32_t* parent, const int32_t* row_ids /* [n] */, int32_t* out_path /* [n] */, int* out_count);
+int  flm_verify_tree_greedy(flm_ctx* ctx, int pos, int n, const int32_t* tokens /* [n] */, const int32_t* parent /* [n] */,
+                            int32_t* out_ids /* [n] */, int* out_count, int32_t* out_path /* [n], may be NULL */);
 /* The loop on top of it, with a built-in prompt-lookup drafter: flm_generate's contract at temperature 0 for *n_out, out_tokens and cb (the stop token is delivered and counted
  * with last = 1 and not fed; the loop ends after max_tokens or behind a callback's non-zero return; cb runs on the calling thread in index order, for all accepted ids of a step).
  * The prompt enters exactly as in flm_forward_argmax.  A step = draft -> a batch of draft_len + 1 rows -> row argmax -> accept, all on the device:
@@ -672,6 +689,10 @@ int  flm_debug_read(flm_ctx* ctx, int what, int layer, float* out, size_t n);
  *   "attn_split"     0 = one workgroup per head at every context length (default 1: hs / 32 workgroups per head from 128 positions on; n >= 2: always n)
  *   "use_prefill"    0 = prompts token by token (default 1: batched; under tensor parallelism once the peers are mapped with flm_p2p_import)
  *   "score_rows"     n = flm_score_tokens runs its classifier on chunks of at most n rows (default 0: as many rows as the staging holds; < 0: one row at a time through the logits vector, the staging of a context without prefill scores)
+ *   "spec_branches"  B in 1 .. 4 (default 1: every launch is today's).  B > 1: flm_generate_lookup* in its PLAIN form at temperature 0 (no control, constraint, stop rule,
+ *                    log-probability or entropy setting in force; head sizes <= 128) drafts a TREE per step -- k_spec_draft_tree keeps the B most recent longest-matching places
+ *                    of the history whose continuations differ and merges them by common prefix, breadth first, into draft_len + 1 nodes on the device -- and verifies it
+ *                    with flm_verify_tree_greedy's pass.  Ids, count, stop behaviour and final cache stay flm_generate's.  Every other form ignores the option.
  *   "spec_gemm"      1 = flm_verify_greedy / flm_generate_lookup and their sampled forms run the verify batch's int8 GEMMs on the skinny kernel for <= 16 rows (default 0: the prompt path's 64 x 64
  *                    tiles, until both forms have been timed on the device: DESIGN.md section 5e); the same bits; no other entry point looks at it
  *   "batch_rows"     b >= 0 = flm_generate_batch admits every request and runs ragged passes with a budget of b prompt rows each (0: no bound); default -1: serial joins, then
@@ -794,6 +815,11 @@ int  flm_op_attention(float* out, float* kc, float* vc, const float* q, const fl
  * 2 <= n <= FLM_FAN_MAX, hs <= 128, S >= 1, S + t + 1 <= max_seq and every base[j] + t < max_seq (FLM_ERR_INVALID otherwise). */
 int  flm_op_attention_fan(float* out, float* kc, float* vc, const float* q, const float* k, const float* v,
                           int n_heads, int hs, int max_seq, int n, int S, int t, const int32_t* base);
+/* the same task for the n rows of one flm_verify_tree_greedy pass (k_rope_kv_tree + k_attn_tree, csrc/flm_tree.h): q, k, v are [n][n_heads*hs]; row i is at logical position
+ * pos + depth(i), its k / v go to cache row pos + i, and its query attends rows 0 .. pos - 1 followed by the rows of its ancestors root .. i.  kc, vc as above (updated); out
+ * [n][n_heads*hs].  parent as flm_tree_validate takes it, pos + n <= max_seq (FLM_ERR_INVALID otherwise); hs <= 128 (FLM_ERR_UNSUPPORTED above). */
+int  flm_op_attention_tree(float* out, float* kc, float* vc, const float* q, const float* k, const float* v,
+                           int n_heads, int hs, int max_seq, int pos, int n, const int32_t* parent);
 /* the same task for the n rows of one flm_batch_step (k_rope_kv_slots + k_attn_slots, csrc/flm_batch.h): q, k, v are [n][n_heads*hs]; row r is at ITS logical position pos[r]
  * of the slot that starts at cache row base[r] (and reaches to max_seq): its k / v go to cache row base[r] + pos[r], its query attends rows base[r] .. base[r] + pos[r].
  * kc, vc as above (updated); out [n][n_heads*hs].  1 <= n <= FLM_BATCH_MAX, pos[r] >= 0, base[r] >= 0, base[r] + pos[r] < max_seq (FLM_ERR_INVALID otherwise). */

@@ -21,9 +21,11 @@ With --draft-model SHAPE (behind (a), nothing else; SHAPE a synthetic shape of t
 context: every draft accepted, the upper bound; --target SHAPE picks the target, default 7B): draft-and-verify with a draft MODEL as the drafter (flm_generate_draft), in
 one run on one box: t_1 of the target, the draft's time per token, the target's verify pass t_B for B = 5, 8, 16, and the loop's tokens/s with accepted / steps beside
 flm_generate_ex on the target alone in the same process -- at temperature 0 and, with --temperature T, sampled at state 1234; under "draft_model".
+With --branches (behind (c), nothing after it): flm_generate_lookup on (c)'s prompt with option "spec_branches" 1, 2 and 4 at draft_len 7 and 15 -- tokens/s, passes, ids
+per pass --, and one 16-row pass three ways, alternating: the chain (flm_verify_greedy), the same chain as a tree and a ragged tree (flm_verify_tree_greedy); under "branches".
 Exits non-zero unless the ids of (a), (b) and (c) agree -- and, sampled, unless ids and final states agree with flm_generate; shaped, with flm_generate_ex.  Prints one
 JSON line.
-python tools/spec_bench.py [--temperature T] [--topp P] [--shape] [--stop] [--target SHAPE] [--draft-model SHAPE|self] [N] [reps] [layers]"""
+python tools/spec_bench.py [--temperature T] [--topp P] [--shape] [--stop] [--branches] [--target SHAPE] [--draft-model SHAPE|self] [N] [reps] [layers]"""
 import argparse
 import json
 import os
@@ -41,6 +43,7 @@ ap.add_argument("--topp", "-p", type=float, default=0.9)
 ap.add_argument("--shape", action="store_true")
 ap.add_argument("--stop", action="store_true")
 ap.add_argument("--target", default="7B")
+ap.add_argument("--branches", action="store_true", help='the tree drafter: option "spec_branches" 1 against 2 and 4 on the loop\'s prompt, and a 16-row tree pass against a 16-row chain pass')
 ap.add_argument("--draft-model", dest="draft_model", default=None)
 ap.add_argument("N", nargs="?", type=int, default=128)
 ap.add_argument("reps", nargs="?", type=int, default=9)
@@ -167,6 +170,41 @@ t0 = time.perf_counter(); got = ctx.generate_lookup(prompt, 0, N, draft_len=7, n
 ok = ok and np.array_equal(got, ref)
 res.update({"lookup_tok_s": round(N / dt_c, 1), "lookup_steps": ctx.query("spec_steps"), "lookup_accepted": ctx.query("spec_accepted"),
             "lookup_gemm": ctx.query("spec_gemm"), "ids_agree": bool(ok), "fallback": ctx.query("fallback")})
+
+# --branches: the tree drafter (option "spec_branches") beside the chain on the loop's prompt, and one 16-row tree pass beside one 16-row chain pass
+if opt.branches:
+    tr = {"gemm": ctx.query("spec_gemm")}
+    for K in (7, 15):
+        for b in (1, 2, 4):
+            ctx.set_option("spec_branches", b)
+            ts = []
+            for _ in range(reps + 1):
+                ctx.reset_kv()
+                t0 = time.perf_counter(); got = ctx.generate_lookup(prompt, 0, N, draft_len=K, ngram_max=3); ts.append(time.perf_counter() - t0)
+                ok = ok and np.array_equal(got, ref)
+            st = ctx.query("spec_steps")
+            tr[f"K{K}_B{b}"] = {"tok_s": round(N / float(np.median(ts[1:])), 1), "passes": st, "accepted": ctx.query("spec_accepted"), "ids_per_pass": round((N - 1) / max(st, 1), 2)}
+    ctx.set_option("spec_branches", 1)
+    # the same 16 rows -- the first token and the 15 true drafts -- as a chain (flm_verify_greedy) and as a tree whose parent array is that chain (flm_verify_tree_greedy),
+    # alternating so that both see the same machine; then a ragged tree of 16 (the true chain of 8 drafts with a wrong sibling beside each but the last)
+    chain_par = [-1] + list(range(15))
+    rag_par, rag_tok = [-1], [first]
+    for dpt in range(8):
+        p = 0 if dpt == 0 else 2 * dpt - 1
+        rag_par += [p, p]; rag_tok += [int(ids[dpt]), (int(ids[dpt]) + 1) % cfg.vocab_size]
+    rag_par, rag_tok = rag_par[:16], rag_tok[:16]
+    tc, tt, tg = [], [], []
+    for _ in range(4 * reps + 1):
+        t0 = time.perf_counter(); a = ctx.verify_greedy(first, ids[:15], len(seed)); tc.append((time.perf_counter() - t0) * 1e3)
+        t0 = time.perf_counter(); b_, _ = ctx.verify_tree(len(seed), np.concatenate([[first], ids[:15]]), chain_par); tt.append((time.perf_counter() - t0) * 1e3)
+        t0 = time.perf_counter(); c_, _ = ctx.verify_tree(len(seed), rag_tok, rag_par); tg.append((time.perf_counter() - t0) * 1e3)
+        ok = ok and np.array_equal(a, ids[:16]) and np.array_equal(b_, ids[:16]) and np.array_equal(c_, ids[:len(c_)]) and len(c_) == 9
+    q = lambda v: [round(float(np.percentile(v[1:], x)), 3) for x in (25, 50, 75)]
+    tr["pass16_ms_q25_q50_q75"] = {"chain": q(tc), "tree_as_chain": q(tt), "tree_ragged": q(tg)}
+    res["branches"] = tr; res["ids_agree"] = bool(ok)
+    print(json.dumps(res), flush=True)
+    ctx.close()
+    sys.exit(0 if ok else 1)
 
 # the sampled path
 if opt.temperature > 0:
