@@ -16,6 +16,32 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FLM_GPU_LIB") or os.path.join(_HERE, "lib", "libflm_gpu.so")   # FLM_GPU_LIB: tools/variants.sh builds
 
 QT_NONE, QT_INT16, QT_INT8 = 0, 1, 2
+QT_INT4 = 3          # W4A8: 4-bit weights (the reference's Bit4Pair bytes, uint8 [rows, cols / 2]) against int8 activations (include/flm_gpu.h FLM_QT_INT4)
+
+
+def pack_int4(q):
+    """int8 values in [-8, 7], [..., cols] -> uint8 [..., cols / 2]: element 2i in the low nibble, element 2i + 1 in the high nibble, two's complement"""
+    v = np.ascontiguousarray(q, dtype=np.int8).view("<u2")                  # a pair of elements: 2i in the low byte
+    return ((v & 0xF) | ((v >> 4) & 0xF0)).astype(np.uint8)
+
+
+def unpack_int4(p):
+    """uint8 [..., cols / 2] -> int8 [..., cols], sign extended"""
+    v = np.ascontiguousarray(p, dtype=np.uint8).astype("<u2")
+    v = (v & 0xF) | ((v & 0xF0) << 4)                                       # the nibbles, one to the byte
+    return ((((v ^ 0x0808) | 0x8080) - 0x0808) ^ 0x8080).view(np.int8)      # per byte (u ^ 8) - 8: u >= 8 -> u - 16 (bit 7 set first: no borrow crosses a byte)
+
+
+def quantize_int4_host(x, gs=64):
+    """the device's weight quantizer of an INT4 context, restated: per group r = max|x| / 7 in fp32, q = trunc(x / r) in fp32, an all-zero group r = 0, q = 0
+    -> (packed uint8 [..., cols / 2], fp32 scales [..., cols / gs])"""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    g = x.reshape(-1, gs)
+    r = (np.abs(g).max(axis=1) / np.float32(7.0)).astype(np.float32)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = (g / r[:, None]).astype(np.float32)
+    q = np.where(r[:, None] != 0, np.trunc(t), 0.0).astype(np.int8).reshape(x.shape)
+    return pack_int4(q), r.reshape(x.shape[:-1] + (x.shape[-1] // gs,))
 KCLASSES = ("embed", "qkv", "attn", "attn_o", "ffn13", "ffn2", "cls", "argmax", "allreduce", "attn_wo", "ffn", "qkv_attn_wo", "layer", "back", "layers", "token")   # from "attn_wo" on: the fused launches of the single-GPU token path ("layer": k_attn_ffn, the whole decoder layer in one launch; "back": the same without the QKV GEMV; "layers": k_layers, all layers of the token in one launch; "token": k_layers<.., TAIL>, the whole greedy token in one launch)
 
 # every symbol include/flm_gpu.h declares (tests check the library exports all of them)
@@ -452,8 +478,9 @@ class Ctx:
         if isinstance(value, tuple):
             q, s = value
             q = np.ascontiguousarray(q); s = np.ascontiguousarray(s, dtype=np.float32)
-            qt = QT_INT8 if q.dtype == np.int8 else QT_INT16
-            _check(lib().flm_upload_tensor(self._h, kind, layer, qt, _p(q), _p(s), q.shape[0], q.shape[1]), self._h)
+            qt = QT_INT8 if q.dtype == np.int8 else QT_INT4 if q.dtype == np.uint8 else QT_INT16
+            cols = 2 * q.shape[1] if qt == QT_INT4 else q.shape[1]          # (packed nibbles: two weights to the byte)
+            _check(lib().flm_upload_tensor(self._h, kind, layer, qt, _p(q), _p(s), q.shape[0], cols), self._h)
         else:
             v = np.ascontiguousarray(value, dtype=np.float32)
             rows, cols = v.shape if v.ndim == 2 else (1, v.shape[0])
@@ -906,7 +933,7 @@ class Ctx:
 # ---- op level ---------------------------------------------------------------------------------
 def op_quantize(x, qt, gs=64):
     x = np.ascontiguousarray(x, dtype=np.float32)
-    q = np.empty(x.size, dtype=np.int8 if qt == QT_INT8 else np.int16)
+    q = np.empty(x.size // 2, dtype=np.uint8) if qt == QT_INT4 else np.empty(x.size, dtype=np.int8 if qt == QT_INT8 else np.int16)
     s = np.empty(x.size // gs, dtype=np.float32)
     _check(lib().flm_op_quantize(qt, _p(q), _p(s), _p(x), C.c_size_t(x.size), gs))
     return q, s
@@ -916,6 +943,8 @@ def op_matmul_q(qt, W, sW, X, sX, gs=64):
     W = np.ascontiguousarray(W); X = np.ascontiguousarray(X)
     sW = np.ascontiguousarray(sW, dtype=np.float32); sX = np.ascontiguousarray(sX, dtype=np.float32)
     m, n = W.shape; w = X.shape[0]
+    if qt == QT_INT4:                                   # W: packed nibbles uint8 [m, n / 2]; X: int8
+        n *= 2
     out = np.empty((w, m), dtype=np.float32)
     _check(lib().flm_op_matmul_q(qt, _p(out), _p(W), _p(sW), _p(X), _p(sX), m, n, w, gs))
     return out

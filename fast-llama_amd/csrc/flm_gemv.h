@@ -3,6 +3,7 @@
 #pragma once
 #include "flm_math.h"
 #include "flm_wait.h"
+#include <type_traits>
 // (bit-exactness hygiene: see flm_math.h -- no implicit FMA contraction in any of these headers)
 #pragma clang fp contract(off)
 
@@ -70,17 +71,19 @@ __host__ __device__ inline int chain_strip_floats(int n) { return 64 * ((1 << ch
 // scratch = max( rmsnorm staging: 4 chain strips of [64 lanes][B + 4] floats (sq_chain_spec) ,
 //                2 buffers x (Rm + RB) strips; strip r = { float(group dot), sW*sX } pairs of row r, groups ascending
 //                (SWIGLU: entries { d(W1), d(W3), s(W1), s(W3) }: the two chains are the halves of one packed FMA) )
+// W4A8 (w4): [xsum : n/64 ints, padded to 16 B] between xs and red -- the activation's per-group sums, the offset-nibble correction (GemvCtx::reduce_step)
 struct GemvLds {
-    int off_xs, off_red, off_ctr, off_scr;     // byte offsets (off_ctr: the two step counters of GemvCtx)
+    int off_xs, off_xsum, off_red, off_ctr, off_scr;     // byte offsets (off_ctr: the two step counters of GemvCtx)
     int gstride;                      // BYTES per strip: 16 x odd, so that 16 lanes reading 16 B each from 16 strips hit all banks
     int buf_bytes;                    // one strip buffer
     int total;                        // bytes
 };
-__host__ __device__ inline GemvLds gemv_lds_layout(int n, int esz, bool norm, int Rm, int RB, bool two, int nbuf = 2) {
+__host__ __device__ inline GemvLds gemv_lds_layout(int n, int esz, bool norm, int Rm, int RB, bool two, int nbuf = 2, bool w4 = false) {
     GemvLds L;
     const int sn = n / kGroup, ng = two ? 2 * sn : sn;
-    L.off_xs = n * esz;
-    L.off_red = L.off_xs + ((sn * 4 + 15) & ~15);
+    L.off_xs = n * esz;                                                        // (esz: bytes per ACTIVATION element)
+    L.off_xsum = L.off_xs + ((sn * 4 + 15) & ~15);
+    L.off_red = L.off_xsum + (w4 ? (sn * 4 + 15) & ~15 : 0);
     L.off_ctr = L.off_red + 64;
     L.off_scr = L.off_ctr + 16;
     int g16 = (ng * 8 + 15) / 16; if ((g16 & 1) == 0) ++g16;
@@ -349,8 +352,9 @@ __device__ __forceinline__ void st_result_granule(const GemvArgs& a, unsigned ro
 #ifndef FLM_QUANT_SHARED_RCP
 #define FLM_QUANT_SHARED_RCP 1          // the four divisions of a quantizer round share the refined reciprocal of the group's scale (flm_math.h: quant_elems4); 0: four IEEE divisions
 #endif
+// xsum (W4A8 only, else null): the group's exact int32 sum of its quantized values goes to xsum[e / 64] -- every lane of a row is either live or quantizes zeros to zeros
 template <int QT>
-__device__ __forceinline__ void quant_round4(char* xq, float* xs, int e, bool act, const float4& v) {
+__device__ __forceinline__ void quant_round4(char* xq, float* xs, int e, bool act, const float4& v, int* xsum = nullptr) {
     using T = QTraits<QT>;
     // group max over the 16 lanes that share this 64-element group (order-free, exact)
     const float mx = row16_max(fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
@@ -361,6 +365,10 @@ __device__ __forceinline__ void quant_round4(char* xq, float* xs, int e, bool ac
 #else
     qq[0] = quant_elem(v.x, sc); qq[1] = quant_elem(v.y, sc); qq[2] = quant_elem(v.z, sc); qq[3] = quant_elem(v.w, sc);
 #endif
+    if (xsum) {                                       // (uniform: a launch has the array or has not)
+        const int gsum = row16_sum(qq[0] + qq[1] + qq[2] + qq[3]);
+        if (act && (threadIdx.x & 15) == 0) xsum[e / kGroup] = gsum;
+    }
     if (act) {
         const int q0 = qq[0], q1 = qq[1], q2 = qq[2], q3 = qq[3];
         if constexpr (QT == QT_INT8) {
@@ -389,12 +397,16 @@ __device__ __forceinline__ void quant_round4(char* xq, float* xs, int e, bool ac
 // accepted ~4.5 us after the first, long after the chain is done.  Only worth it where the run has something to start on while those sets are in flight (k_attn_ffn's stash).
 template <int QT, int PRO, int XR, bool COH = false, bool LATE = false, class AfterStage>
 __device__ __forceinline__ void gemv_prologue(const GemvArgs& a, char* lds, float4 (&xv)[XR > 0 ? XR : 1], float4 (&wv)[XR > 0 ? XR : 1], AfterStage&& after_stage) {
-    using T = QTraits<QT>;
+    // W4A8: the activation is QT_INT8's (same quantizer, same bytes in LDS) plus its per-group sums, computed here once per GEMV
+    constexpr bool W4 = QT == QT_INT4;
+    constexpr int AQ = W4 ? (int)QT_INT8 : QT;
+    using T = QTraits<AQ>;
     const int n = a.n;
     const int tid = threadIdx.x;
-    const GemvLds L = gemv_lds_layout(n, T::kEsz, PRO == PRO_RMSNORM_QUANT, a.rows_per_pass, 64 >> a.cb_shift, false);   // only the fixed offsets are used here
+    const GemvLds L = gemv_lds_layout(n, T::kEsz, PRO == PRO_RMSNORM_QUANT, a.rows_per_pass, 64 >> a.cb_shift, false, 2, W4);   // only the fixed offsets are used here
     char*  xq = lds;
     float* xs = reinterpret_cast<float*>(lds + L.off_xs);
+    int* const xsum = W4 ? reinterpret_cast<int*>(lds + L.off_xsum) : nullptr;
     float* red = reinterpret_cast<float*>(lds + L.off_red);
     float* scratch = reinterpret_cast<float*>(lds + L.off_scr);
 
@@ -412,6 +424,15 @@ __device__ __forceinline__ void gemv_prologue(const GemvArgs& a, char* lds, floa
             for (int g = tid; g < n / kGroup; g += kGemvBlock) xs[g] = a.xs[g];
         }
         __syncthreads();
+        if constexpr (W4) {   // a short pass over the staged bytes: the group sums (16 dwords each against four ones)
+            for (int g = tid; g < n / kGroup; g += kGemvBlock) {
+                int t = 0;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) t = dot16_i8(reinterpret_cast<const v4i*>(xq + g * kGroup)[k], v4i{0x01010101, 0x01010101, 0x01010101, 0x01010101}, t);
+                xsum[g] = t;
+            }
+            __syncthreads();
+        }
         return;
     } else {
         const int rounds = (n + kGemvBlock * 4 - 1) / (kGemvBlock * 4);
@@ -512,7 +533,7 @@ __device__ __forceinline__ void gemv_prologue(const GemvArgs& a, char* lds, floa
                 v.z = __fmul_rn(__fmul_rn(v.z, w.z), r); v.w = __fmul_rn(__fmul_rn(v.w, w.w), r);
             }
             if (act && a.dbg_xn && blockIdx.x == 0) *reinterpret_cast<float4*>(a.dbg_xn + e) = v;
-            quant_round4<QT>(xq, xs, e, act, v);
+            quant_round4<AQ>(xq, xs, e, act, v, xsum);
         };
 #pragma unroll
         for (int i = 0; i < XR; ++i) { if (i < rounds) round(i, xv[i], wv[i]); }
@@ -574,7 +595,10 @@ typedef unsigned v4u __attribute__((ext_vector_type(4)));
 template <int QT, int EPI, bool STASH = false>
 struct GemvCtx {
     using T = QTraits<QT>;
-    static constexpr u32 LPGS = (T::kEPC == 16) ? 2 : 3;                      // log2(lanes per quant group): 4 | 8 lanes
+    static constexpr bool W4 = QT == QT_INT4;                                  // W4A8: nibble weights in the device layout (flm_gemv4.h), int8 activations
+    static_assert(!(W4 && STASH), "the LDS stash holds one scale dword per lane and step: not built for W4A8");
+    static constexpr u32 LPGS = W4 ? 1 : (T::kEPC == 16) ? 2 : 3;              // log2(lanes per quant group): 2 (int4) | 4 | 8 lanes
+    static constexpr u32 XCH = W4 ? 32 : 16;                                   // activation bytes a lane holds per column block: the 32 (16 | 8) elements of its weight chunk
     static constexpr u32 LPG = 1u << LPGS;
     static constexpr bool TWO = EPI == EPI_SWIGLU;
     static constexpr int H = kStepBlk;
@@ -591,7 +615,13 @@ struct GemvCtx {
     // 3 us after the first ones, on a 12 us main loop; the wave that runs a pass's chain falls behind as well.
     // Numbered steps cost two scalar multiply-high's to decode, and the activation chunk is re-read from LDS when the
     // column block changes (one ds_read_b128 per step at most).
-    struct Set { v4i w[H]; float sw; u32 itl, st, xo, nlive; };               // itl: workgroup-local pass index (np_wg: no work left)
+    // W4A8: a block holds 32 groups, so the wave's lanes cover the scales of TWO blocks: lane (j, g), j = 0 | 1, fetches block j's in sw and block j + 2's in sw2 --
+    // two scale loads per step (an 8-byte load per lane would need a block's and the next-but-one's scales adjacent; they are RB rows apart)
+    // What only W4A8 needs is two small structs that are EMPTY for the other types, whose instantiations are then the code they were.
+    struct NoStep {}; struct NoLane {};
+    struct W4Step { float sw2; };                                              // the scale of block j + 2
+    struct W4Lane { v4i xb; int xoff8; u32 off_xsum, lane_sxoff; };            // the chunk's second 16 bytes; 8 x (the activation's sum over the lane's quant group); where the sums live; the lane's group among the column block's (x 4)
+    struct Set { v4i w[H]; float sw; [[no_unique_address]] std::conditional_t<W4, W4Step, NoStep> q4; u32 itl, st, xo, nlive; };   // itl: workgroup-local pass index (np_wg: no work left)
 
     // geometry (wave-uniform unless noted)
     u32 n, lane, wave, rowbytes, sn, cbs, RB, nbc, NBCV, TRm, Rm, RBP, SP, NS, np_wg, npass, gstride, buf_bytes, off_xs, off_scr, ctr_off;
@@ -627,7 +657,7 @@ struct GemvCtx {
         n = a.n; wg = wg_; nwg = nwg_; st_base = st_base_; st_n = st_n_;
         lane = threadIdx.x & 63;
         wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        rowbytes = n * T::kEsz; sn = n / kGroup;
+        rowbytes = W4 ? n / 2 : n * T::kEsz; sn = n / kGroup;                   // bytes of a WEIGHT row
         const u32 nchunks = rowbytes / 16;
         cbs = a.cb_shift; RB = 64u >> cbs;
         const u32 CB = 1u << cbs;
@@ -642,15 +672,16 @@ struct GemvCtx {
         NS = np_wg * SP;
         inv_SP = inv_of(SP); inv_NBCV = inv_of(NBCV);
         nbuf = a.nbuf > 0 ? a.nbuf : 2;
-        const GemvLds L = gemv_lds_layout(n, T::kEsz, true, Rm, RB, TWO, nbuf);
-        gstride = L.gstride; buf_bytes = L.buf_bytes; off_xs = L.off_xs; off_scr = L.off_scr; ctr_off = a.ctr_off ? (u32)a.ctr_off : (u32)L.off_ctr + 4 * (ctr_slot & 1);
+        const GemvLds L = gemv_lds_layout(n, T::kEsz, true, Rm, RB, TWO, nbuf, W4);
+        gstride = L.gstride; buf_bytes = L.buf_bytes; off_xs = L.off_xs; if constexpr (W4) q4.off_xsum = L.off_xsum; off_scr = L.off_scr; ctr_off = a.ctr_off ? (u32)a.ctr_off : (u32)L.off_ctr + 4 * (ctr_slot & 1);
         dW = RB * rowbytes; dS = RB * sn * 4; dT = RB * gstride;               // row block to row block
         dummy_st = Rm * gstride;
         // lane-constant parts of every address (the per-step parts are wave-uniform scalars)
         const u32 rb = lane >> cbs, cb = lane & (CB - 1);
         lane_woff = rb * rowbytes + cb * 16;                                   // weights, bytes from the block base
-        lane_xoff = cb * 16;                                                   // activation chunk in LDS
+        lane_xoff = cb * XCH;                                                  // activation chunk in LDS
         lane_goff = rb * gstride + (cb >> LPGS) * ES;                          // strip entry of this lane's group
+        if constexpr (W4) q4.lane_sxoff = (cb >> LPGS) * 4;
         leader = (cb & (LPG - 1)) == 0;
         // scale role: lane -> (block j of the step, quant group g of the block); g's leader lane is g * LPG
         constexpr u32 GPB = 64u / LPG;
@@ -677,6 +708,23 @@ struct GemvCtx {
 
     // step number -> the set's bookkeeping and the scalar offsets of its first block
     __device__ __forceinline__ void decode(u32 s, Set& S, u32& wo, u32& so) const {
+        if constexpr (W4) {
+            // The same values, every field of S stored ONCE: with two places that store them the compiler merges stores of DIFFERENT fields into one store at a
+            // selected offset (seen in this instantiation), a variable index into the context -- which then cannot be promoted to registers and lives in scratch
+            // memory, its accesses queued behind the weight stream (the build refuses a k_gemv with scratch: __graft_entry__.py).
+            const bool live = s < NS;
+            const u32 itl = udiv(s, SP, inv_SP), rem = s - itl * SP;
+            const u32 q = udiv(rem, NBCV, inv_NBCV), cv = rem - q * NBCV;
+            const bool second = TWO && cv >= nbc;
+            const u32 cc = second ? cv - nbc : cv, g0 = (cc << cbs) >> LPGS, rb0 = q * H;
+            const u32 row0 = (second ? TRm : 0u) + (wg + itl * nwg) * Rm + rb0 * RB;
+            wo = live ? row0 * rowbytes + ((cc << cbs) * 16) : kOOB;
+            so = live ? (row0 * sn + g0) * 4 : kOOB;
+            S.itl = live ? itl : np_wg; S.xo = live ? cc : 0u;
+            S.nlive = !live ? 0u : RBP - rb0 < (u32)H ? RBP - rb0 : (u32)H;
+            S.st = live ? rb0 * RB * gstride + g0 * ES + (second ? 4u : 0u) : 0u;
+            return;
+        }
         if (s >= NS) { S.itl = np_wg; S.st = 0; S.xo = 0; S.nlive = 0; wo = kOOB; so = kOOB; return; }
         const u32 itl = udiv(s, SP, inv_SP), rem = s - itl * SP;
         const u32 q = udiv(rem, NBCV, inv_NBCV), cv = rem - q * NBCV;
@@ -710,6 +758,10 @@ struct GemvCtx {
         }
         const u32 svo = lane_j < nl ? lane_s2off + so : kOOB;
         S.sw = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rS, (int)svo, 0, 2));
+        if constexpr (W4) {
+            const u32 svo2 = lane_j + 2 < nl ? lane_s2off + 2 * dS + so : kOOB;
+            S.q4.sw2 = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rS, (int)svo2, 0, 2));
+        }
     }
     // the first two steps of weight loads: independent of the activation
     // (part 1 / 2: only the first / second set; a set that was never requested is drawn at the start of run())
@@ -746,18 +798,32 @@ struct GemvCtx {
 
     // reduce one step: the group dots of its H blocks (registers), then the leaders park them; the scale-role lanes park s = sW * sX
     v4i xa; float sx2; u32 cur_xo;                                             // activation chunk (dot role) / activation scale (scale role) of the current column block
+    [[no_unique_address]] std::conditional_t<W4, W4Lane, NoLane> q4;
     __device__ __forceinline__ void reduce_step(const Set& S, char* lds, char* strips, int ablate) {
         const char* xq = lds; const char* xs = lds + off_xs;
         if (S.xo != cur_xo) {                                                  // wave-uniform: a new column block
             cur_xo = S.xo;
-            xa = *reinterpret_cast<const v4i*>(xq + ((cur_xo << cbs) * 16) + lane_xoff);
+            xa = *reinterpret_cast<const v4i*>(xq + ((cur_xo << cbs) * XCH) + lane_xoff);
+            if constexpr (W4) {
+                q4.xb = *reinterpret_cast<const v4i*>(xq + ((cur_xo << cbs) * XCH) + lane_xoff + 16);
+                q4.xoff8 = 8 * *reinterpret_cast<const int*>(lds + q4.off_xsum + (((cur_xo << cbs) >> LPGS) * 4) + q4.lane_sxoff);
+            }
             sx2 = *reinterpret_cast<const float*>(xs + (((cur_xo << cbs) >> LPGS) * 4) + lane_sx2off);
         }
         float d[H];
 #pragma unroll
         for (int j = 0; j < H; ++j) {
-            int t = (kAblate && (ablate & 8)) ? 0 : quad_sum(dot_chunk<QT>(S.w[j], xa));
-            if constexpr (LPG == 8) t += __builtin_amdgcn_update_dpp(0, t, 0x104 /* row_shl:4 */, 0xF, 0xF, true);
+            int t;
+            if constexpr (W4) {
+                // sum (u - 8) x = sum u x - 8 sum x over the group's two lanes, every term an exact int32 (|sum u x| <= 64 * 15 * 127): in the leader, the int8 kernel's
+                // group dot of the sign-extended nibbles.  (A block past the step's live ones read zeros = weights of -8: its value goes to the dummy strips like int8's zero)
+                t = (kAblate && (ablate & 8)) ? 0 : dot32_u4i8(S.w[j], xa, q4.xb);
+                t += __builtin_amdgcn_update_dpp(0, t, 0xB1 /* quad_perm [1,0,3,2] */, 0xF, 0xF, true);
+                t -= q4.xoff8;
+            } else {
+                t = (kAblate && (ablate & 8)) ? 0 : quad_sum(dot_chunk<QT>(S.w[j], xa));
+                if constexpr (LPG == 8) t += __builtin_amdgcn_update_dpp(0, t, 0x104 /* row_shl:4 */, 0xF, 0xF, true);
+            }
             d[j] = (float)t;                                                   // exact int32 -> fp32, as "s * dot" does
         }
         if (leader) {
@@ -768,6 +834,7 @@ struct GemvCtx {
             }
         }
         if (lane_j < S.nlive) *reinterpret_cast<float*>(strips + S.st + lane_poff) = __fmul_rn(S.sw, sx2);   // s = sW * sX (quant_operators.cpp:274)
+        if constexpr (W4) { if (lane_j + 2 < S.nlive) *reinterpret_cast<float*>(strips + S.st + 2 * dT + lane_poff) = __fmul_rn(S.q4.sw2, sx2); }
     }
 
     // the end of a pass: one barrier, then ONE wave runs the fp32 chains of all Rm rows and the epilogue

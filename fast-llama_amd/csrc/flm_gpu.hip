@@ -38,7 +38,10 @@ struct SavedError {
     explicit SavedError(flm_ctx* c_) : c(c_), err(c_->err), gerr(g_last_error) {}
     void restore() const { c->err = err; g_last_error = gerr; (void)hipGetLastError(); }
 };
-int esz_of(int qt) { return qt == FLM_QT_INT8 ? 1 : qt == FLM_QT_INT16 ? 2 : 4; }
+// bytes per ACTIVATION element of a context of type qt (INT4 is W4A8: int8 activations) -- and per element of an int8 / int16 / fp32 tensor as uploaded
+int esz_of(int qt) { return qt == FLM_QT_INT8 || qt == FLM_QT_INT4 ? 1 : qt == FLM_QT_INT16 ? 2 : 4; }
+// bytes of a row of `cols` WEIGHTS of type qt (INT4: two to the byte)
+size_t wrow_bytes(int qt, size_t cols) { return qt == FLM_QT_INT4 ? cols / 2 : cols * (size_t)esz_of(qt); }
 
 // balanced contiguous split (split_rows, transformer.cpp:264-287)
 void split_even(int total, int parts, int idx, int* begin, int* count) {
@@ -59,10 +62,13 @@ __global__ void k_quantize_flat(void* q, float* s, const float* x, size_t n) {
         const bool act = e < n;
         float4 v = act ? *reinterpret_cast<const float4*>(x + e) : make_float4(0.f, 0.f, 0.f, 0.f);
         const float mx = row16_max(fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
-        const float sc = __fdiv_rn(mx, T::kF);
+        float F = T::kF; if constexpr (QT == QT_INT4) F = T::kFW;              // (weights: QUANT4_FACTOR)
+        const float sc = __fdiv_rn(mx, F);
         if (act) {
             const int q0 = quant_elem(v.x, sc), q1 = quant_elem(v.y, sc), q2 = quant_elem(v.z, sc), q3 = quant_elem(v.w, sc);
-            if constexpr (QT == QT_INT8) {
+            if constexpr (QT == QT_INT4) {
+                quantize4_store(q, e, q0, q1, q2, q3);                          // nibbles, interchange order (flm_gemv4.h)
+            } else if constexpr (QT == QT_INT8) {
                 reinterpret_cast<uint32_t*>(q)[e / 4] = (uint32_t)(q0 & 0xff) | ((uint32_t)(q1 & 0xff) << 8) | ((uint32_t)(q2 & 0xff) << 16) | ((uint32_t)(q3 & 0xff) << 24);
             } else {
                 uint2 pk; pk.x = (uint32_t)(q0 & 0xffff) | ((uint32_t)(q1 & 0xffff) << 16); pk.y = (uint32_t)(q2 & 0xffff) | ((uint32_t)(q3 & 0xffff) << 16);
@@ -77,7 +83,21 @@ int quantize_flat(flm_ctx* c, hipStream_t st, int qt, void* q, float* s, const f
     size_t blocks = (n / 4 + kBlock - 1) / kBlock; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
     if (qt == FLM_QT_INT8) hipLaunchKernelGGL(k_quantize_flat<QT_INT8>, dim3((unsigned)blocks), dim3(kBlock), 0, st, q, s, x, n);
     else if (qt == FLM_QT_INT16) hipLaunchKernelGGL(k_quantize_flat<QT_INT16>, dim3((unsigned)blocks), dim3(kBlock), 0, st, q, s, x, n);
+    else if (qt == FLM_QT_INT4) hipLaunchKernelGGL(k_quantize_flat<QT_INT4>, dim3((unsigned)blocks), dim3(kBlock), 0, st, q, s, x, n);
     else return fail(c, FLM_ERR_UNSUPPORTED, "quantize: type");
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
+// W4A8: `nbytes` of packed weights, interchange order -> device layout, in place / device layout -> int8 [rows][cols] (flm_gemv4.h)
+int repack_w4(flm_ctx* c, hipStream_t st, void* w, size_t nbytes) {
+    const size_t nw = nbytes / 4; size_t blocks = (nw + kBlock - 1) / kBlock; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(k_repack_w4, dim3((unsigned)blocks), dim3(kBlock), 0, st, (uint32_t*)w, nw);
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
+int unpack_w4(flm_ctx* c, hipStream_t st, void* out, const void* w, size_t nbytes) {
+    const size_t nw = nbytes / 4; size_t blocks = (nw + kBlock - 1) / kBlock; if (blocks > 8192) blocks = 8192; if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(k_unpack_w4, dim3((unsigned)blocks), dim3(kBlock), 0, st, (uint2*)out, (const uint32_t*)w, nw);
     HIPC(c, hipGetLastError());
     return FLM_OK;
 }
@@ -100,7 +120,7 @@ void build_rope_table(int hs, int max_seq, std::vector<float>& cs, std::vector<f
 
 int alloc_qmat(flm_ctx* c, QMat& m, int rows, int cols, int qt, bool with_st = false) {
     m.rows = rows; m.cols = cols;
-    HIPC(c, dev_alloc(c, &m.q, (size_t)rows * cols * esz_of(qt)));
+    HIPC(c, dev_alloc(c, &m.q, (size_t)rows * wrow_bytes(qt, cols)));
     HIPC(c, dev_alloc(c, &m.s, (size_t)rows * (cols / kGroup) * sizeof(float)));
     if (with_st) HIPC(c, dev_alloc(c, &m.st, (size_t)rows * (cols / kGroup) * sizeof(float)));
     return FLM_OK;
@@ -118,16 +138,19 @@ int upload_window(flm_ctx* c, QMat& m, int dst_row0, int src_qt, const void* val
         float* stage = (float*)stage_mem.p;
         HIPC(c, hipMemcpy2DAsync(stage, (size_t)ncols * 4, (const float*)values + (size_t)row0 * src_cols + col0, (size_t)src_cols * 4,
                                  (size_t)ncols * 4, nrows, hipMemcpyHostToDevice, c->stream));
-        int r = quantize_flat(c, c->stream, qt, (char*)m.q + (size_t)dst_row0 * ncols * c->esz, m.s + (size_t)dst_row0 * (ncols / gs), stage, (size_t)nrows * ncols);
+        int r = quantize_flat(c, c->stream, qt, (char*)m.q + (size_t)dst_row0 * wrow_bytes(qt, ncols), m.s + (size_t)dst_row0 * (ncols / gs), stage, (size_t)nrows * ncols);
         if (r) return r;
+        if (qt == FLM_QT_INT4) { r = repack_w4(c, c->stream, (char*)m.q + (size_t)dst_row0 * wrow_bytes(qt, ncols), (size_t)nrows * wrow_bytes(qt, ncols)); if (r) return r; }
         HIPC(c, hipStreamSynchronize(c->stream));
         return FLM_OK;
     }
     if (src_qt != qt) return fail(c, FLM_ERR_INVALID, "upload: tensor quant type differs from the model's");
-    const int e = c->esz;
-    HIPC(c, hipMemcpy2DAsync((char*)m.q + (size_t)dst_row0 * ncols * e, (size_t)ncols * e,
-                             (const char*)values + ((size_t)row0 * src_cols + col0) * e, (size_t)src_cols * e,
-                             (size_t)ncols * e, nrows, hipMemcpyHostToDevice, c->stream));
+    // (bytes of a weight row; INT4: two weights to the byte -- contexts of that type are unsharded, every window starts at column 0)
+    const size_t wb = wrow_bytes(qt, ncols), swb = wrow_bytes(qt, src_cols), c0b = wrow_bytes(qt, col0);
+    HIPC(c, hipMemcpy2DAsync((char*)m.q + (size_t)dst_row0 * wb, wb,
+                             (const char*)values + (size_t)row0 * swb + c0b, swb,
+                             wb, nrows, hipMemcpyHostToDevice, c->stream));
+    if (qt == FLM_QT_INT4) { int r = repack_w4(c, c->stream, (char*)m.q + (size_t)dst_row0 * wb, (size_t)nrows * wb); if (r) return r; }
     HIPC(c, hipMemcpy2DAsync(m.s + (size_t)dst_row0 * (ncols / gs), (size_t)(ncols / gs) * 4,
                              scales + (size_t)row0 * (src_cols / gs) + col0 / gs, (size_t)(src_cols / gs) * 4,
                              (size_t)(ncols / gs) * 4, nrows, hipMemcpyHostToDevice, c->stream));
@@ -427,7 +450,8 @@ int flm_ctx_create(const flm_model_desc* desc, int device_id, int rank, int worl
     if (d.dim < 64 || d.hidden_dim < 64 || d.n_layers < 1 || d.n_heads < 1 || d.vocab_size < 1 || d.max_seq_len < 1)
         return fail(nullptr, FLM_ERR_INVALID, "invalid model dimensions");
     if (d.quant_group_size != kGroup) return fail(nullptr, FLM_ERR_UNSUPPORTED, "quant_group_size must be 64");
-    if (d.quant_type != FLM_QT_INT8 && d.quant_type != FLM_QT_INT16) return fail(nullptr, FLM_ERR_UNSUPPORTED, "quant_type must be INT8 or INT16");
+    if (d.quant_type != FLM_QT_INT8 && d.quant_type != FLM_QT_INT16 && d.quant_type != FLM_QT_INT4) return fail(nullptr, FLM_ERR_UNSUPPORTED, "quant_type must be INT8, INT16 or INT4");
+    if (d.quant_type == FLM_QT_INT4 && world > 1) return fail(nullptr, FLM_ERR_UNSUPPORTED, "quant_type INT4 (W4A8) runs on one GPU: tensor parallelism is not built for it");
     if (d.n_kv_heads != d.n_heads) return fail(nullptr, FLM_ERR_UNSUPPORTED, "n_kv_heads != n_heads: the reference's grouped-query path is broken (transformer.cpp:449); not reproduced");
     if (d.dim % d.n_heads || d.dim % kGroup || d.hidden_dim % kGroup) return fail(nullptr, FLM_ERR_INVALID, "dim/hidden_dim must be multiples of 64 and dim of n_heads");
     const int hs = d.dim / d.n_heads;
@@ -467,6 +491,10 @@ int flm_ctx_create(const flm_model_desc* desc, int device_id, int rank, int worl
     }
     if (alloc_qmat(c, c->cls, c->plan.vocab_count > 0 ? c->plan.vocab_count : 1, d.dim, qt, true)) return bail(FLM_ERR_OOM);   // (cls.st: flm_score_tokens' classifier runs on the GEMM tiles)
     c->cls.rows = c->plan.vocab_count;
+    if (qt == FLM_QT_INT4) {   // the batched path's int8 copy: the larger of one layer's matrices and the classifier (here, so that no call allocates)
+        const size_t layer = ((size_t)3 * c->dim_local + c->drow_count + (size_t)2 * c->hidden_local) * d.dim + (size_t)c->drow_count * d.hidden_dim, cls = (size_t)c->plan.vocab_count * d.dim;
+        HIPB(dev_alloc(c, &c->w4_scratch, layer > cls ? layer : cls));
+    }
     HIPB(dev_alloc(c, &c->out_norm, d.dim * 4));
 #ifndef FLM_KV_PAD
 #define FLM_KV_PAD 8
@@ -900,6 +928,7 @@ static int upload_tensor_impl(flm_ctx* c, int kind, int layer, int src_qt, const
     switch (kind) {
     case FLM_T_TOKEN_EMBD: {
         if (rows != d.vocab_size || cols != d.dim) return fail(c, FLM_ERR_INVALID, "embedding shape");
+        if (src_qt == FLM_QT_INT4) return fail(c, FLM_ERR_INVALID, "embedding table: fp32, INT8 or INT16 (INT4 is a type of the streamed matrices only)");
         const size_t n = (size_t)rows * cols;
         if (c->emb) { hipFree(c->emb); c->emb = nullptr; } if (c->emb_s) { hipFree(c->emb_s); c->emb_s = nullptr; }
         HIPC(c, hipMalloc(&c->emb, n * esz_of(src_qt)));

@@ -74,7 +74,7 @@ struct flm_ctx {
     flm_model_desc d{};
     int device = 0, rank = 0, world = 1;
     flm_shard_plan plan{};
-    int hs = 0, esz = 1, cu_count = 256, cu_total = 256, n_xcd = 8;   // cu_count: CUs this context's launches are sized for (cu_total / cu_parts)
+    int hs = 0, esz = 1 /* bytes per ACTIVATION element (a weight row: wrow_bytes) */, cu_count = 256, cu_total = 256, n_xcd = 8;   // cu_count: CUs this context's launches are sized for (cu_total / cu_parts)
     int dim_local = 0, hidden_local = 0, heads_local = 0, vocab_slot = 0;    // dim_local = heads_local*hs: q/k/v rows and attention outputs owned
     int drow_begin = 0, drow_count = 0;                                       // rows of Wo / W2 (= slice of the residual stream) owned
     hipStream_t stream = nullptr;
@@ -236,6 +236,9 @@ struct flm_ctx {
     int batch_prefix = 0;                              // flm_batch_open_prefix: the shared rows [0, S) in front of the slots (flm_prefix.h); 0: none -- every launch is the plain batch's.  A slot's pos / fed count ITS OWN rows
     int batch_passes = 0;                              // flm_query "batch_passes": weight passes (joins, steps, passes) since the last flm_batch_open
     int score_rows = 0;                                // option "score_rows": rows per classifier chunk of flm_score_tokens (0: as many as the staging holds; < 0: one row at a time through c->logits)
+    // W4A8 (quant_type INT4): the batched path's int8 copy of ONE layer's matrices [qkv | o | w13 | w2] or of the classifier, refilled by k_unpack_w4 in front of the GEMMs
+    // that read it (flm_prompt.hip pass_weights / pass_classifier); allocated at create
+    char* w4_scratch = nullptr;
     std::map<GraphKey, hipGraphExec_t> graphs;        // the token graphs captured so far (flm_gpu.hip token_graph)
     std::vector<TimedLaunch>* timing = nullptr;
     std::vector<void*> owned;                          // every device allocation that lives as long as the context (flm_gpu.hip dev_alloc); flm_ctx_destroy frees these
@@ -254,23 +257,27 @@ namespace fh {
 
 int fail(flm_ctx* c, int code, const char* msg);
 int esz_of(int qt);
+size_t wrow_bytes(int qt, size_t cols);
+int repack_w4(flm_ctx* c, hipStream_t st, void* w, size_t nbytes);
+int unpack_w4(flm_ctx* c, hipStream_t st, void* out, const void* w, size_t nbytes);
 void split_even(int total, int parts, int idx, int* begin, int* count);
 
 // Pass geometry of k_gemv for one launch (flm_token.hip)
 struct GemvPlan { int Rm, cb_shift, grid, nbuf; size_t lds; };
-GemvPlan gemv_plan(int n, int esz, int rows, bool two, bool pairs, bool norm, int wgs);
+// esz: bytes per activation element; w4 (W4A8): a weight row is n / 2 bytes whatever esz says, and the LDS holds the activation's group sums too
+GemvPlan gemv_plan(int n, int esz, int rows, bool two, bool pairs, bool norm, int wgs, bool w4 = false);
 // fill the pass geometry of one GEMV into its argument block; returns the LDS bytes and grid it needs
-inline int plan_gemv(flm_ctx* c, GemvArgs& a, int esz, int pro, int epi, int wgs, GemvPlan& P) {
+inline int plan_gemv(flm_ctx* c, GemvArgs& a, int esz, int pro, int epi, int wgs, GemvPlan& P, bool w4 = false) {
     const bool TWO = epi == EPI_SWIGLU, PAIRS = epi == EPI_ROPE_KV;
     const int rows = a.items * (PAIRS ? 2 : 1);
-    if ((double)rows * a.n * esz * (TWO ? 2 : 1) >= 2147483648.0) return fail(c, FLM_ERR_UNSUPPORTED, "gemv: matrix of 2 GiB or more");
-    P = gemv_plan(a.n, esz, rows, TWO, PAIRS, pro == PRO_RMSNORM_QUANT, wgs);     // (the chain staging area only where an rmsnorm prologue runs)
+    if ((double)rows * a.n * (w4 ? 0.5 : (double)esz) * (TWO ? 2 : 1) >= 2147483648.0) return fail(c, FLM_ERR_UNSUPPORTED, "gemv: matrix of 2 GiB or more");
+    P = gemv_plan(a.n, esz, rows, TWO, PAIRS, pro == PRO_RMSNORM_QUANT, wgs, w4);     // (the chain staging area only where an rmsnorm prologue runs)
     if (P.lds > kLdsMax) return fail(c, FLM_ERR_UNSUPPORTED, "gemv: activation vector does not fit LDS");
     a.rows_per_pass = P.Rm; a.cb_shift = P.cb_shift; a.nbuf = P.nbuf;
     return FLM_OK;
 }
 template <int QT, int PRO, int EPI>
-int plan_gemv(flm_ctx* c, GemvArgs& a, int wgs, GemvPlan& P) { return plan_gemv(c, a, QTraits<QT>::kEsz, PRO, EPI, wgs, P); }
+int plan_gemv(flm_ctx* c, GemvArgs& a, int wgs, GemvPlan& P) { return plan_gemv(c, a, QTraits<QT>::kEsz, PRO, EPI, wgs, P, QT == QT_INT4); }
 // rounds of the activation sweep: every thread of a workgroup takes four elements of the n per round
 inline int gemv_rounds(int n) { return (n + kGemvBlock * 4 - 1) / (kGemvBlock * 4); }
 // the kernels' rounds template argument (XR / XR2) for a sweep of 1 .. 3 rounds: 1 | 3
@@ -291,7 +298,11 @@ int launch_gemv_xr(flm_ctx* c, hipStream_t st, GemvArgs a, int wgs) {
 template <int PRO, int EPI>
 int launch_gemv(flm_ctx* c, hipStream_t st, int qt, const GemvArgs& a, int wgs, bool coh = false) {
     if (a.n % kGroup != 0 || a.n <= 0) return fail(c, FLM_ERR_INVALID, "gemv: n must be a positive multiple of 64");
-    if (qt != FLM_QT_INT8 && qt != FLM_QT_INT16) return fail(c, FLM_ERR_UNSUPPORTED, "gemv: quant type must be INT8 or INT16");
+    if (qt != FLM_QT_INT8 && qt != FLM_QT_INT16 && qt != FLM_QT_INT4) return fail(c, FLM_ERR_UNSUPPORTED, "gemv: quant type must be INT8, INT16 or INT4");
+    if (qt == FLM_QT_INT4) {   // W4A8 (flm_gemv4.h): one GPU, so never the coherent form
+        if (coh) return fail(c, FLM_ERR_UNSUPPORTED, "gemv: INT4 weights run on one GPU");
+        return launch_gemv_xr<QT_INT4, PRO, EPI, false>(c, st, a, wgs);
+    }
     if constexpr (PRO != PRO_NONE) {
         if (coh) return qt == FLM_QT_INT8 ? launch_gemv_xr<QT_INT8, PRO, EPI, true>(c, st, a, wgs) : launch_gemv_xr<QT_INT16, PRO, EPI, true>(c, st, a, wgs);
     }
@@ -394,6 +405,8 @@ inline TokenPlan token_plan(const flm_ctx* c, int G) {   // G: workgroups per he
     P.fold = P.tp && c->p2p && c->world > 1 && c->grp_fold;          // (agreed by the group at flm_p2p_import)
     P.span = P.fold && c->grp_span;                                   // (they wait across workgroups of one launch too: only where the census found one workgroup per CU resident)
     P.tpfa = P.span ? c->grp_tpfa : 0; P.tpff = P.span ? c->grp_tpff : 0;
+    // W4A8: no fused form is instantiated for the type -- the token is one launch per phase, the "fuse_*" options stay accepted and decide nothing
+    if (c->d.quant_type == FLM_QT_INT4) { for (int f = 0; f < kLaunchForms; ++f) o[f] = false; P.qkv = 0; }
     for (int f = 0; f < kLaunchForms; ++f) P.use[f] = !P.tp && o[f];
     P.use[LF_LAYERS_TP] = P.span && c->grp_tpl && o[LF_LAYERS_TP];
     P.use[LF_QKV_ATTN_O] |= P.tpfa >= 2; P.use[LF_ATTN_O] |= P.tpfa != 0; P.use[LF_FFN] |= P.tpff != 0;

@@ -133,6 +133,7 @@ int plan_layer(flm_ctx* c, int l, bool with_qkv, int G, LayerArgs& A, BackArgs& 
     return FLM_OK;
 }
 int plan_layer_qt(flm_ctx* c, int qt, int l, bool with_qkv, int G, LayerArgs& A, BackArgs& p, int& grid, int& r2, TailArgs* tail) {
+    if (qt == FLM_QT_INT4) return FLM_ERR_UNSUPPORTED;                     // W4A8: k_attn_ffn / k_layers are not instantiated for the type (the token runs one launch per phase)
     return qt == FLM_QT_INT8 ? plan_layer<QT_INT8>(c, l, with_qkv, G, A, p, grid, r2, tail) : plan_layer<QT_INT16>(c, l, with_qkv, G, A, p, grid, r2, tail);
 }
 

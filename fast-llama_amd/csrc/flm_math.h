@@ -95,14 +95,16 @@ __device__ __forceinline__ bool gen_last_act(DecodeState* st, const int step, co
     return halt;
 }
 
-enum { QT_INT16 = 1, QT_INT8 = 2 };
+enum { QT_INT16 = 1, QT_INT8 = 2, QT_INT4 = 3 };   // QT_INT4 (W4A8): 4-bit weights against int8 activations -- everything but the weight stream is QT_INT8's
 enum Prologue { PRO_NONE = 0, PRO_QUANT = 1, PRO_RMSNORM_QUANT = 2 };
 enum Epilogue { EPI_STORE = 0, EPI_RESIDUAL = 1, EPI_SWIGLU = 2, EPI_ROPE_KV = 3 };
 
 template <int QT> struct QTraits;
 template <> struct QTraits<QT_INT8>  { using elem = int8_t;  static constexpr int kEsz = 1; static constexpr int kEPC = 16; static constexpr float kF = 127.0f; };
 template <> struct QTraits<QT_INT16> { using elem = int16_t; static constexpr int kEsz = 2; static constexpr int kEPC = 8;  static constexpr float kF = 5792.0f; };
-// kEPC = elements per 16-byte chunk; lanes per quant group = 64 / kEPC (4 for int8, 8 for int16)
+// QT_INT4: kEsz / kF are the ACTIVATION's (int8, F = 127); a weight is a nibble (32 per 16-byte chunk), quantized with kFW = QUANT4_FACTOR
+template <> struct QTraits<QT_INT4>  { using elem = int8_t;  static constexpr int kEsz = 1; static constexpr int kEPC = 32; static constexpr float kF = 127.0f; static constexpr float kFW = 7.0f; };
+// kEPC = elements per 16-byte chunk; lanes per quant group = 64 / kEPC (4 for int8, 8 for int16, 2 for int4)
 
 // ------------------------------------------------------------------------------------------
 // block reductions for ORDER-FREE quantities only (max)
@@ -141,6 +143,14 @@ __device__ __forceinline__ float row16_max(float v) {
 __device__ __forceinline__ int quad_sum(int p) {
     p += __builtin_amdgcn_update_dpp(0, p, 0xB1 /* quad_perm [1,0,3,2] */, 0xF, 0xF, true);
     p += __builtin_amdgcn_update_dpp(0, p, 0x4E /* quad_perm [2,3,0,1] */, 0xF, 0xF, true);
+    return p;
+}
+
+// exact integer sum over each aligned group of 16 lanes (one DPP row), result in all 16 lanes
+__device__ __forceinline__ int row16_sum(int p) {
+    p = quad_sum(p);
+    p += __builtin_amdgcn_update_dpp(0, p, 0x141 /* row_half_mirror */, 0xF, 0xF, true);
+    p += __builtin_amdgcn_update_dpp(0, p, 0x140 /* row_mirror */, 0xF, 0xF, true);
     return p;
 }
 
@@ -264,6 +274,17 @@ __device__ __forceinline__ int dot8_i16(const v4i& w, const v4i& a, int acc) {
     acc = __builtin_amdgcn_sdot2(as_short2(w1), as_short2(a1), acc, false);
     acc = __builtin_amdgcn_sdot2(as_short2(w2), as_short2(a2), acc, false);
     acc = __builtin_amdgcn_sdot2(as_short2(w3), as_short2(a3), acc, false);
+    return acc;
+}
+// W4A8: a 16-byte chunk of 32 offset nibbles (device layout, flm_gemv4.h: byte j of a word holds u_j in its low and u_{j+4} in its high nibble, u = q + 8) against the 32
+// int8 activations a0 | a1 of the same columns.  The masked bytes 0 .. 15 are valid signed operands of v_dot4_i32_i8: sum u x, exact; the caller takes 8 sum x off
+__device__ __forceinline__ int dot32_u4i8(const v4i& w, const v4i& a0, const v4i& a1) {
+    constexpr int M = 0x0F0F0F0F;
+    int acc = 0;
+    acc = __builtin_amdgcn_sdot4(w.x & M, a0.x, acc, false); acc = __builtin_amdgcn_sdot4((int)((unsigned)w.x >> 4) & M, a0.y, acc, false);
+    acc = __builtin_amdgcn_sdot4(w.y & M, a0.z, acc, false); acc = __builtin_amdgcn_sdot4((int)((unsigned)w.y >> 4) & M, a0.w, acc, false);
+    acc = __builtin_amdgcn_sdot4(w.z & M, a1.x, acc, false); acc = __builtin_amdgcn_sdot4((int)((unsigned)w.z >> 4) & M, a1.y, acc, false);
+    acc = __builtin_amdgcn_sdot4(w.w & M, a1.z, acc, false); acc = __builtin_amdgcn_sdot4((int)((unsigned)w.w >> 4) & M, a1.w, acc, false);
     return acc;
 }
 template <int QT> __device__ __forceinline__ int dot_chunk(const v4i& w, const v4i& a) {

@@ -20,12 +20,12 @@ extern "C" {
 
 int flm_op_quantize(int qt, void* qx, float* qs, const float* x, size_t n, int gs) {
     if (!qx || !qs || !x || gs != kGroup || n % kGroup) return FLM_ERR_INVALID;
-    if (qt != FLM_QT_INT8 && qt != FLM_QT_INT16) return FLM_ERR_UNSUPPORTED;
-    const int e = esz_of(qt);
+    if (qt != FLM_QT_INT8 && qt != FLM_QT_INT16 && qt != FLM_QT_INT4) return FLM_ERR_UNSUPPORTED;
+    const size_t qbytes = wrow_bytes(qt, n);                    // (INT4: the WEIGHT quantizer, F = 7, nibbles in the interchange order -- an INT4 context's activations are int8)
     DevBuf dx, dq, ds;
-    if (dx.alloc(n * 4) || dq.alloc(n * e) || ds.alloc(n / kGroup * 4)) return FLM_ERR_OOM;
+    if (dx.alloc(n * 4) || dq.alloc(qbytes) || ds.alloc(n / kGroup * 4)) return FLM_ERR_OOM;
     OPC(hipMemcpy(dx.p, x, n * 4, hipMemcpyHostToDevice));
-    if (n <= 16384) {
+    if (n <= 16384 && qt != FLM_QT_INT4) {
         // through the fused path's prologue (PRO_QUANT), tapped
         GemvArgs a{}; a.n = (int)n; a.items = 0; a.x = dx.as<float>(); a.dbg_xq = dq.p; a.dbg_xs = ds.as<float>();
         int r = launch_gemv<PRO_QUANT, EPI_STORE>(nullptr, 0, qt, a, 1); if (r) return r;
@@ -33,7 +33,7 @@ int flm_op_quantize(int qt, void* qx, float* qs, const float* x, size_t n, int g
         int r = quantize_flat(nullptr, 0, qt, dq.p, ds.as<float>(), dx.as<float>(), n); if (r) return r;
     }
     OPC(hipDeviceSynchronize());
-    OPC(hipMemcpy(qx, dq.p, n * e, hipMemcpyDeviceToHost));
+    OPC(hipMemcpy(qx, dq.p, qbytes, hipMemcpyDeviceToHost));
     OPC(hipMemcpy(qs, ds.p, n / kGroup * 4, hipMemcpyDeviceToHost));
     return FLM_OK;
 }
@@ -84,10 +84,12 @@ int flm_op_rmsnorm(float* o, const float* x, const float* w, size_t n) {
 
 int flm_op_matmul_q(int qt, float* out, const void* W, const float* sW, const void* X, const float* sX, int m, int n, int w, int gs) {
     if (!out || !W || !sW || !X || !sX || m < 1 || n < 1 || w < 1 || gs != kGroup || n % kGroup) return FLM_ERR_INVALID;
-    if (qt != FLM_QT_INT8 && qt != FLM_QT_INT16) return FLM_ERR_UNSUPPORTED;
-    const size_t e = esz_of(qt), sn = n / kGroup;
-    DevBuf dW, dsW, dX, dsX, dsXT, dsWT, dO;
-    if (dW.alloc((size_t)m * n * e) || dsW.alloc((size_t)m * sn * 4) || dX.alloc((size_t)w * n * e) || dsX.alloc((size_t)w * sn * 4) || dsXT.alloc((size_t)w * sn * 4 + 64) || dsWT.alloc((size_t)m * sn * 4) || dO.alloc((size_t)w * m * 4)) return FLM_ERR_OOM;
+    if (qt != FLM_QT_INT8 && qt != FLM_QT_INT16 && qt != FLM_QT_INT4) return FLM_ERR_UNSUPPORTED;
+    // INT4 (W4A8): W is [m][n / 2] nibbles in the interchange order, X is int8.  w < 16: the nibble GEMV per row; w >= 16: unpacked to int8, the int8 tiles -- a context's two routes
+    const bool w4 = qt == FLM_QT_INT4;
+    const size_t e = esz_of(qt), sn = n / kGroup, wbytes = (size_t)m * wrow_bytes(qt, n);
+    DevBuf dW, dsW, dX, dsX, dsXT, dsWT, dO, dW8;
+    if (dW.alloc(wbytes) || dsW.alloc((size_t)m * sn * 4) || dX.alloc((size_t)w * n * e) || dsX.alloc((size_t)w * sn * 4) || dsXT.alloc((size_t)w * sn * 4 + 64) || dsWT.alloc((size_t)m * sn * 4) || dO.alloc((size_t)w * m * 4)) return FLM_ERR_OOM;
     {   // the activation scales once more, group-major (k_rows_prologue writes both layouts on the prompt path)
         std::vector<float> t((size_t)w * sn);
         for (int b = 0; b < w; ++b) for (size_t g = 0; g < sn; ++g) t[g * w + b] = sX[(size_t)b * sn + g];
@@ -96,15 +98,17 @@ int flm_op_matmul_q(int qt, float* out, const void* W, const float* sW, const vo
         for (int r = 0; r < m; ++r) for (size_t g = 0; g < sn; ++g) tw[g * m + r] = sW[(size_t)r * sn + g];
         OPC(hipMemcpy(dsWT.p, tw.data(), tw.size() * 4, hipMemcpyHostToDevice));
     }
-    OPC(hipMemcpy(dW.p, W, (size_t)m * n * e, hipMemcpyHostToDevice)); OPC(hipMemcpy(dsW.p, sW, (size_t)m * sn * 4, hipMemcpyHostToDevice));
+    OPC(hipMemcpy(dW.p, W, wbytes, hipMemcpyHostToDevice)); OPC(hipMemcpy(dsW.p, sW, (size_t)m * sn * 4, hipMemcpyHostToDevice));
     OPC(hipMemcpy(dX.p, X, (size_t)w * n * e, hipMemcpyHostToDevice)); OPC(hipMemcpy(dsX.p, sX, (size_t)w * sn * 4, hipMemcpyHostToDevice));
+    if (w4) { int r = repack_w4(nullptr, 0, dW.p, wbytes); if (r) return r; }     // (as an upload does)
     int dev = 0, cus = 256; hipGetDevice(&dev); hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     const char* gv = getenv("FLM_OP_GEMM");                     // tests: 0 .. 3 = launch_gemm's use_mfma, "gemv" = a GEMV per batch row
     if (w >= 16 && !(gv && !strcmp(gv, "gemv"))) {
         // the batched path the prompt takes (quant::matmul with w > 1, quant_operators.cpp:252-284): one tile kernel
-        GemmArgs g{dW.p, dsW.as<float>(), dX.p, dsX.as<float>(), dO.as<float>(), m, n, m, w, dsXT.as<float>(), dsWT.as<float>()};
+        if (w4) { if (dW8.alloc((size_t)m * n)) return FLM_ERR_OOM; int r = unpack_w4(nullptr, 0, dW8.p, dW.p, wbytes); if (r) return r; }
+        GemmArgs g{w4 ? dW8.p : dW.p, dsW.as<float>(), dX.p, dsX.as<float>(), dO.as<float>(), m, n, m, w, dsXT.as<float>(), dsWT.as<float>()};
         const int um = gv ? atoi(gv) : 1;
-        int r = launch_gemm_store(nullptr, 0, qt, g, um);
+        int r = launch_gemm_store(nullptr, 0, w4 ? FLM_QT_INT8 : qt, g, um);
         if (r) return r;
     } else {
         for (int b = 0; b < w; ++b) {

@@ -232,6 +232,30 @@ int launch_rope_kv_segs(flm_ctx* c, hipStream_t st, const float* qkv, float* qou
 // tree (flm_verify_tree_greedy; null: every launch is the one made without it): the B rows are a tree of candidates at `pos` (flm_tree.h) -- the fan's route with
 // k_rope_kv_tree and k_attn_tree; tree_dev (the lookup loop under "spec_branches"): the rows' parents, depths and masks are the ones k_spec_draft_tree left in device
 // memory, `tree` carries pos and n only
+// W4A8 (quant_type INT4): the batched kernels run as QT_INT8 on an int8 copy of the weights they are about to read -- k_unpack_w4 on the pass's stream (inside the capture
+// where the pass is captured) in front of a layer's GEMMs / the classifier's, into the context's scratch; the scales and their group-major copies are the packed matrix's
+// own.  Bit-identical by construction (the int8 kernels on the sign-extended nibbles); it costs one more read of the packed weights and a write + read of their int8 copy
+// per layer and pass, and for the classifier per CHUNK of rows its stage runs -- a nibble-fragment loader for the tiles is the follow-up.
+static inline bool tiles_int8(const flm_ctx* c) { return c->d.quant_type != FLM_QT_INT16; }
+// the ONE place a pass picks layer l's weight pointers
+static int pass_weights(flm_ctx* c, hipStream_t st, int l, LayerW& w) {
+    w = c->layers[l];
+    if (c->d.quant_type != FLM_QT_INT4) return FLM_OK;
+    char* p = c->w4_scratch;
+    for (QMat* m : {&w.qkv, &w.o, &w.w13, &w.w2}) {
+        const size_t n = (size_t)m->rows * m->cols;
+        const int r = unpack_w4(c, st, p, m->q, n / 2); if (r) return r;
+        m->q = p; p += n;
+    }
+    return FLM_OK;
+}
+// ... and the classifier's
+static int pass_classifier(flm_ctx* c, hipStream_t st, const void** q) {
+    *q = c->cls.q;
+    if (c->d.quant_type != FLM_QT_INT4) return FLM_OK;
+    *q = c->w4_scratch;
+    return unpack_w4(c, st, c->w4_scratch, c->cls.q, (size_t)c->cls.rows * c->cls.cols / 2);
+}
 template <int QT>
 int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req = false, const FanDesc* fan = nullptr, int row0 = 0, const SlotDesc* slots = nullptr, const SegDesc* segs = nullptr, const PrefixDesc* pfx = nullptr, const TreeDesc* tree = nullptr, const TreeDesc* tree_dev = nullptr) {
     const int S = pfx ? pfx->S : 0;
@@ -265,7 +289,7 @@ int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req
     hipLaunchKernelGGL(k_embed_rows, dim3(B), dim3(256), 0, st, c->pf_x, (const void*)c->emb, (const float*)c->emb_s, c->emb_qt, dim, (const int*)c->prompt_dev);
     HIPC(c, hipGetLastError());
     for (int l = 0; l < L; ++l) {
-        LayerW& w = c->layers[l];
+        LayerW w; r = pass_weights(c, st, l, w); if (r) return r;
         float* const kc = c->kcache + (size_t)l * kv_layer + (size_t)row0 * hs;    // (row0: the slot's origin; the stride between two heads' rows stays kv_rows)
         float* const vc = c->vcache + (size_t)l * kv_layer + (size_t)row0 * hs;
         // x2 = rmsnorm(x1); qx = quantize(x2); q,k,v = W x; RoPE; cache rows   (transformer.cpp:132-135, 386-395, 431-439)
@@ -384,7 +408,7 @@ int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers, bool skinny,
     if (tree) {   // (in front of the first launch: k_rope_kv_tree writes the rows' cache rows)
         if (c->world != 1 || fan || row0 || slots_in || segs_in || pfx_in || tree->n != B || tree->pos != pos || pos < 0 || pos + B > c->d.max_seq_len || c->hs > 128)
             return fail(c, FLM_ERR_INVALID, "prefill: a tree pass is one GPU's batch of tree.n rows at tree.pos, inside the cache, at head sizes <= 128");
-        return c->d.quant_type == FLM_QT_INT8 ? prefill_batched<QT_INT8>(c, B, pos, all_layers, skinny, nullptr, 0, nullptr, nullptr, nullptr, tree, tree_dev) : prefill_batched<QT_INT16>(c, B, pos, all_layers, skinny, nullptr, 0, nullptr, nullptr, nullptr, tree, tree_dev);
+        return tiles_int8(c) ? prefill_batched<QT_INT8>(c, B, pos, all_layers, skinny, nullptr, 0, nullptr, nullptr, nullptr, tree, tree_dev) : prefill_batched<QT_INT16>(c, B, pos, all_layers, skinny, nullptr, 0, nullptr, nullptr, nullptr, tree, tree_dev);
     }
     // behind a shared prefix the checks below see every row's OWN position (pos - S) in its slot; in front of them: S <= base[s], no slot begins inside the prefix
     const PrefixDesc* const pfx = pfx_in && pfx_in->S != 0 ? pfx_in : nullptr;
@@ -405,7 +429,7 @@ int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers, bool skinny,
         if (const char* why = seg_check(*segs, B, c->d.max_seq_len)) return fail(c, FLM_ERR_INVALID, why);
         for (int r = 0; slots && r < slots->n; ++r)
             if (slots->base[r] != segs->base[r] || slots->rows[r] != segs->rows[r] || slots->pos[r] != segs->pos0[r]) return fail(c, FLM_ERR_INVALID, "prefill: a ragged pass's step rows and its SlotDesc disagree");
-        return c->d.quant_type == FLM_QT_INT8 ? prefill_batched<QT_INT8>(c, B, 0, all_layers, skinny, nullptr, 0, slots_in, segs_in, pfx) : prefill_batched<QT_INT16>(c, B, 0, all_layers, skinny, nullptr, 0, slots_in, segs_in, pfx);
+        return tiles_int8(c) ? prefill_batched<QT_INT8>(c, B, 0, all_layers, skinny, nullptr, 0, slots_in, segs_in, pfx) : prefill_batched<QT_INT16>(c, B, 0, all_layers, skinny, nullptr, 0, slots_in, segs_in, pfx);
     }
     if (fan && (c->world != 1 || fan->n != B || pos != fan->S + fan->t)) return fail(c, FLM_ERR_INVALID, "prefill: a fan step is one GPU's batch of fan.n rows at S + t");
     if ((row0 || slots) && (c->world != 1 || fan || row0 < 0 || (slots && (row0 || slots->n != B)) || row0 + pos + (slots ? 0 : B) > c->d.max_seq_len))
@@ -413,7 +437,7 @@ int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers, bool skinny,
     for (int r = 0; slots && r < slots->n; ++r)      // (in front of the first launch: k_rope_kv_slots writes the rows' cache rows)
         if (slots->n > kBatchMax || slots->base[r] < 0 || slots->rows[r] < 1 || slots->pos[r] < 0 || slots->pos[r] >= slots->rows[r] || (long long)slots->base[r] + slots->rows[r] > c->d.max_seq_len)
             return fail(c, FLM_ERR_INVALID, "prefill: a batch row outside its slot, or a slot outside the cache");
-    return c->d.quant_type == FLM_QT_INT8 ? prefill_batched<QT_INT8>(c, B, pos, all_layers, skinny, fan, row0, slots_in, nullptr, pfx) : prefill_batched<QT_INT16>(c, B, pos, all_layers, skinny, fan, row0, slots_in, nullptr, pfx);
+    return tiles_int8(c) ? prefill_batched<QT_INT8>(c, B, pos, all_layers, skinny, fan, row0, slots_in, nullptr, pfx) : prefill_batched<QT_INT16>(c, B, pos, all_layers, skinny, fan, row0, slots_in, nullptr, pfx);
 }
 int launch_gemm_skinny_store(flm_ctx* c, hipStream_t st, const GemmArgs& g, int force_nb) { return launch_gemm_skinny<EPI_STORE>(c, st, g, force_nb); }
 
@@ -509,7 +533,8 @@ static int classify_rows_t(flm_ctx* c, int row0, int m, float* stage, bool skinn
     // logits = Wcls quantize(rmsnorm(x1))   (transformer.cpp:154-160)
     RowsArgs ra{c->pf_x + (size_t)row0 * dim, c->out_norm, c->pf_xq, c->pf_xs, dim, c->pf_xst};
     int r = launch_rows<QT, PRO_RMSNORM_QUANT>(c, st, ra, m); if (r) return r;
-    GemmArgs g{c->cls.q, c->cls.s, c->pf_xq, c->pf_xs, stage, V, dim, V, m, c->pf_xst, c->cls.st};
+    const void* wq = nullptr; r = pass_classifier(c, st, &wq); if (r) return r;
+    GemmArgs g{wq, c->cls.s, c->pf_xq, c->pf_xs, stage, V, dim, V, m, c->pf_xst, c->cls.st};
     return launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, skinny && m <= kSkinnyTokens);
 }
 template <int QT>
@@ -543,7 +568,7 @@ static int score_classify_t(flm_ctx* c, int row0, int m, float* stage, bool skin
     return launch_score_rows(c, st, stage, V, V, c->score_tgt + row0, c->score_dev + row0, m);
 }
 int score_classify(flm_ctx* c, int row0, int m, float* stage) {
-    return c->d.quant_type == FLM_QT_INT8 ? score_classify_t<QT_INT8>(c, row0, m, stage, false, nullptr) : score_classify_t<QT_INT16>(c, row0, m, stage, false, nullptr);
+    return tiles_int8(c) ? score_classify_t<QT_INT8>(c, row0, m, stage, false, nullptr) : score_classify_t<QT_INT16>(c, row0, m, stage, false, nullptr);
 }
 // k_sample_fan on `rows` rows of n logits, ld floats apart (0: all from one row), batch rows row0 ..; sort_buf [16][2][n] (c may be null)
 int launch_sample_fan(flm_ctx* c, hipStream_t st, const float* logits, int ld, int n, int row0, int rows, float temperature, float topp, const FanIn& in,
@@ -566,7 +591,7 @@ int launch_sample_fan(flm_ctx* c, hipStream_t st, const float* logits, int ld, i
 // a fan step's classifier stage: the chunk through score_classify's prologue and GEMM, then k_sample_fan -- every row with its own state
 int fan_classify(flm_ctx* c, int row0, int m, float* stage, bool skinny, float temperature, float topp, const FanIn& in) {
     const int V = c->d.vocab_size;
-    int r = c->d.quant_type == FLM_QT_INT8 ? classify_rows_t<QT_INT8>(c, row0, m, stage, skinny) : classify_rows_t<QT_INT16>(c, row0, m, stage, false); if (r) return r;
+    int r = tiles_int8(c) ? classify_rows_t<QT_INT8>(c, row0, m, stage, skinny) : classify_rows_t<QT_INT16>(c, row0, m, stage, false); if (r) return r;
     return launch_sample_fan(c, c->stream, stage, V, V, row0, m, temperature, topp, in, c->sort_buf, c->fan_drawn, c->fan_after);
 }
 // k_sample_slots on `rows` rows of n logits, ld floats apart, batch rows row0 ..; sort_buf [16][2][n] (needed where a row of the chunk is sampled)
@@ -592,13 +617,13 @@ int launch_sample_slots(flm_ctx* c, hipStream_t st, const float* logits, int ld,
 // score_classify's prologue and GEMM, then k_sample_slots -- every row with its own parameters and state
 int batch_classify(flm_ctx* c, int src_row0, int row0, int m, float* stage, bool skinny, const SlotIn& in) {
     const int V = c->d.vocab_size;
-    int r = c->d.quant_type == FLM_QT_INT8 ? classify_rows_t<QT_INT8>(c, src_row0, m, stage, skinny) : classify_rows_t<QT_INT16>(c, src_row0, m, stage, false); if (r) return r;
+    int r = tiles_int8(c) ? classify_rows_t<QT_INT8>(c, src_row0, m, stage, skinny) : classify_rows_t<QT_INT16>(c, src_row0, m, stage, false); if (r) return r;
     return launch_sample_slots(c, c->stream, stage, V, V, row0, m, in, c->sort_buf, c->fan_drawn, c->fan_after);
 }
 // the verify pass's classifier stage: the same chunk through the same prologue and GEMM (skinny: k_gemm_q8_skinny, int8), then k_argmax_rows into argmax_out[row0 ..]
 // (draw given and its temperature > 0: k_sample_rows in place of k_argmax_rows)
 int spec_classify(flm_ctx* c, int row0, int m, float* stage, bool skinny, int* argmax_out, const SpecDraw& draw) {
-    return c->d.quant_type == FLM_QT_INT8 ? score_classify_t<QT_INT8>(c, row0, m, stage, skinny, argmax_out, &draw) : score_classify_t<QT_INT16>(c, row0, m, stage, false, argmax_out, &draw);
+    return tiles_int8(c) ? score_classify_t<QT_INT8>(c, row0, m, stage, skinny, argmax_out, &draw) : score_classify_t<QT_INT16>(c, row0, m, stage, false, argmax_out, &draw);
 }
 
 } // namespace fh

@@ -12,15 +12,15 @@ namespace fh {
 //   Rm       : rows (per matrix) per workgroup pass; bounded by LDS (two strip buffers) and by 64 chain
 //              lanes; chosen so that the passes divide evenly over `wgs` workgroups (CU-level balance is
 //              what matters for an HBM-bound kernel; inside a workgroup the waves draw steps from a counter)
-GemvPlan gemv_plan(int n, int esz, int rows, bool two, bool pairs, bool norm, int wgs) {
+GemvPlan gemv_plan(int n, int esz, int rows, bool two, bool pairs, bool norm, int wgs, bool w4) {
     GemvPlan P{};
-    const int nchunks = n * esz / 16;
-    int cbs = 0; while (cbs < 6 && (nchunks % (2 << cbs)) == 0) ++cbs;       // nchunks % 4 == 0 always
+    const int nchunks = w4 ? n / 32 : n * esz / 16;                          // 16-byte chunks of a WEIGHT row
+    int cbs = 0; while (cbs < 6 && (nchunks % (2 << cbs)) == 0) ++cbs;       // nchunks % 4 == 0 always (W4A8: % 2 -- CB >= 2 = the lanes of a quant group)
     const int RB = 64 >> cbs;
     const int mult = (pairs && RB < 2) ? 2 : RB;                             // ROPE_KV: row pairs stay in one pass
     const int lds_budget = 150 * 1024;                                       // one 1024-thread workgroup per CU out of 160 KiB
     int rmax = 64;                                                           // one chain lane per row
-    while (rmax > mult && gemv_lds_layout(n, esz, norm, rmax, RB, two).total > lds_budget) rmax -= mult;
+    while (rmax > mult && gemv_lds_layout(n, esz, norm, rmax, RB, two, 2, w4).total > lds_budget) rmax -= mult;
     rmax = rmax / mult * mult; if (rmax < mult) rmax = mult;
     if (rows < 1) rows = 1;
     int ppw = (rows + wgs * rmax - 1) / (wgs * rmax);                        // passes per workgroup
@@ -30,7 +30,7 @@ GemvPlan gemv_plan(int n, int esz, int rows, bool two, bool pairs, bool norm, in
     const int npass = (rows + Rm - 1) / Rm;
     P.Rm = Rm; P.cb_shift = cbs; P.grid = npass < wgs ? npass : wgs; if (P.grid < 1) P.grid = 1;
     P.nbuf = 2;
-    P.lds = (size_t)gemv_lds_layout(n, esz, norm, Rm, RB, two, P.nbuf).total;
+    P.lds = (size_t)gemv_lds_layout(n, esz, norm, Rm, RB, two, P.nbuf, w4).total;
     return P;
 }
 
@@ -128,6 +128,7 @@ using VFfn = cross_t<VQuant, cross_t<VRounds, Variants<Variant<0>, Variant<1>>>>
 // attention + Wo GEMV of layer l in one launch (k_attn_o), with_qkv: with the QKV GEMV in front (k_qkv_attn_o); returns FLM_ERR_UNSUPPORTED when the shape does not allow it
 static int launch_attn_o(flm_ctx* c, hipStream_t st, int qt, int l, int G, bool with_qkv) {
     const auto& d = c->d;
+    if (qt == FLM_QT_INT4) return FLM_ERR_UNSUPPORTED;                     // (W4A8: the per-phase launches only)
     const int qv = quant_variant(qt), parts = c->heads_local * G, all = with_qkv && c->cu_count > 256 ? 256 : c->cu_count, wgs = all - parts;
     if (wgs < 1 || parts > 256) return FLM_ERR_UNSUPPORTED;
     GemvArgs aq = with_qkv ? args_qkv(c, l) : GemvArgs{}, a = args_o(c, l);          // (without the QKV phase: aq unused, Pq stays zero -- neutral in the LDS and grid maxima below)
@@ -173,6 +174,7 @@ static int launch_attn_o(flm_ctx* c, hipStream_t st, int qt, int l, int G, bool 
 
 // FFN13 + FFN2 of layer l in one launch (k_ffn); returns FLM_ERR_UNSUPPORTED when the shape does not allow it
 static int launch_ffn(flm_ctx* c, hipStream_t st, int qt, int l) {
+    if (qt == FLM_QT_INT4) return FLM_ERR_UNSUPPORTED;                     // (W4A8: the per-phase launches only)
     GemvArgs a13 = args_ffn13(c, l), a2 = args_ffn2(c, l);
     const int qv = quant_variant(qt), wgs = c->cu_count < 256 ? c->cu_count : 256;       // every workgroup resident, one flag line each
     GemvPlan P13, P2;
@@ -473,7 +475,7 @@ int flm_kernel_times(flm_ctx* c, int pos, int iters, float* avg_us, int32_t* cou
 
 int flm_kernel_bytes(flm_ctx* c, int kclass, int pos, double* bytes) {
     if (!c || !bytes) return FLM_ERR_INVALID;
-    const auto& d = c->d; const double e = c->esz, sb = 4.0 / kGroup;
+    const auto& d = c->d; const double e = d.quant_type == FLM_QT_INT4 ? 0.5 : (double)c->esz /* bytes per WEIGHT */, sb = 4.0 / kGroup;
     auto mat = [&](double rows, double cols) { return rows * cols * (e + sb); };
     // the five phases of a layer (every term an integer multiple of 1/16 far below 2^53: the sums are exact in any grouping)
     const double qkv = mat(3.0 * c->dim_local, d.dim) + d.dim * 4.0;               // + rmsnorm weight

@@ -44,6 +44,7 @@ KIND_NAMES = {
 }
 
 QT_NONE, QT_INT16, QT_INT8 = 0, 1, 2
+QT_INT4 = 3          # a CONTEXT's type (W4A8, include/flm_gpu.h); .flm files that carry int4 tensors are neither read nor written
 QFACTOR = {QT_INT8: 127.0, QT_INT16: 5792.0}
 QDTYPE = {QT_INT8: np.int8, QT_INT16: np.int16}
 

@@ -53,6 +53,8 @@ bool GpuTransformer::load(const std::string& ckpt, const std::string& tknr, File
     _cfg = mf.cfg;
     _cfg.max_seq_len = 1024;                                   // transformer.cpp:32
     if (_cfg.quant_type == 0) _cfg.quant_type = qtype;         // the file's quant type wins over -q (transformer.cpp:36-38)
+    else if (qtype == 3 && _cfg.quant_type != 3)                 // (-q int4 needs fp32 master weights: a quantized file, and a llama2.c file -- quantized to INT8 at load --, keep their type)
+        fprintf(stderr, "warning: -q int4 ignored: the model's weights are %s (an unquantized .flm or gguf file is needed)\n", _cfg.quant_type == 2 ? "int8" : "int16");
     _tok.set_vocab(std::move(mf.vocab));
     _sampler.build(_cfg.vocab_size, seed);
     flm_model_desc d{};

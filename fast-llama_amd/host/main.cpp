@@ -73,7 +73,7 @@ void usage(const char* bin) {
     fprintf(stderr, "   --max-tokens,-n   <integer>   the maximum number of generated tokens\n");
     fprintf(stderr, "   --temperature,-t  <float>     the value for temperature sampling, [0, 1]\n");
     fprintf(stderr, "   --topp,-p         <float>     the value for top-p sampling, [0, 1]\n");
-    fprintf(stderr, "   --quant,-q        <string>    quantization type, can be INT8, INT16\n");
+    fprintf(stderr, "   --quant,-q        <string>    quantization type, can be INT8, INT16, INT4 (4-bit weights, 8-bit activations; an unquantized .flm / gguf file, one device)\n");
     fprintf(stderr, "   --threads,-j      <number>    accepted for compatibility (the GPU build has no worker threads)\n");
     fprintf(stderr, "   --device          <number>    HIP device ordinal (this build only)\n");
     fprintf(stderr, "   --devices         <a,b,...>   shard ONE sequence over these HIP devices, 1 to 8 of them (this build only)\n");

@@ -35,8 +35,9 @@ def make_config(shape="tiny", qt=ff.QT_INT8, **over) -> ff.FlmConfig:
 
 
 def _qweights(rng, rows, cols, qt, gs):
-    lim = 127 if qt == ff.QT_INT8 else 5792
-    dt = np.int8 if qt == ff.QT_INT8 else np.int16
+    """(QT_INT4: int8 values in [-7, 7] -- make_tensors packs them, int8_statement gives them back)"""
+    lim = 127 if qt == ff.QT_INT8 else 7 if qt == ff.QT_INT4 else 5792
+    dt = np.int16 if qt == ff.QT_INT16 else np.int8
     q = rng.integers(-lim, lim + 1, size=(rows, cols), dtype=dt)
     # W ~ U(-1,1) * sqrt(3)/sqrt(cols) * (0.5 + u): unit-gain rows, O(1) activations through the stack
     base = np.float32(np.sqrt(3.0) / (lim * np.sqrt(cols)))
@@ -76,15 +77,28 @@ def make_tensors(c: ff.FlmConfig, seed=1234, fp32_master=False, layers=None, sha
             if fp32_master:
                 t[(kind, l)] = (q.astype(np.float32).reshape(r, k // gs, gs) * s[:, :, None]).reshape(r, k).astype(np.float32)
             else:
-                t[(kind, l)] = (q, s)
+                t[(kind, l)] = (_pack(q, qt), s)
     fr = np.random.default_rng([seed, 999])
     t[(ff.T_OUTPUT_NORM, 0)] = (0.8 + 0.4 * fr.random(c.dim, dtype=np.float32)).astype(np.float32)
     q, s = _qweights(fr, c.vocab_size, c.dim, qt, gs)
     if fp32_master:
         t[(ff.T_CLASSIFIER, 0)] = (q.astype(np.float32).reshape(c.vocab_size, c.dim // gs, gs) * s[:, :, None]).reshape(c.vocab_size, c.dim).astype(np.float32)
     else:
-        t[(ff.T_CLASSIFIER, 0)] = (q, s)
+        t[(ff.T_CLASSIFIER, 0)] = (_pack(q, qt), s)
     return t
+
+
+def _pack(q, qt):
+    if qt != ff.QT_INT4:
+        return q
+    from . import capi
+    return capi.pack_int4(q)
+
+
+def int8_statement(tensors):
+    """the tensors of an INT4 model as the INT8 model that computes the same bits: packed nibbles (uint8) -> their sign-extended int8 values, same scales"""
+    from . import capi
+    return {k: (capi.unpack_int4(v[0]), v[1]) if isinstance(v, tuple) and v[0].dtype == np.uint8 else v for k, v in tensors.items()}
 
 
 def make_tokenizer(vocab_size: int, seed=7) -> ff.FlmTokenizer:

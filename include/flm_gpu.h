@@ -43,6 +43,18 @@ extern "C" {
 #define FLM_QT_NONE  0
 #define FLM_QT_INT16 1
 #define FLM_QT_INT8  2
+/* FLM_QT_INT4 (the reference's number for its int4): here W4A8 -- 4-bit WEIGHTS against 8-bit activations.  The matrices a decode token streams (Wq, Wk, Wv, Wo, W1, W3, W2,
+ * classifier) are nibbles in [-8, 7] with fp32 scales per 64 elements; activations are quantized to int8 exactly as in an INT8 context, and the K / V cache, attention, norms
+ * and samplers are the INT8 context's.  Hence the rule every test of the type rests on: an INT4 context computes, bit for bit, what an INT8 context computes whose weight
+ * bytes are the sign-extended nibbles with the same scales.  (The reference's own int4 arithmetic -- both operands of every product in 4 bits -- is NOT reproduced.)
+ *   format     the reference's Bit4Pair: a row of `cols` weights is cols / 2 bytes, element 2i in the low and element 2i + 1 in the high nibble of byte i, two's complement;
+ *              scales fp32 [rows][cols / 64].  flm_upload_tensor(src_qtype 3) takes it with the LOGICAL cols, flm_op_matmul_q(3, ..) takes W in it, flm_op_quantize(3, ..) writes it
+ *   quantizer  an fp32 linear tensor uploaded into an INT4 context, and flm_op_quantize(3, ..): r = max|x| / 7 (IEEE fp32 division), q = trunc(x / r); an all-zero group r = 0, q = 0
+ *   launches   one kernel per phase under the token graph: no fused form exists for the type, the "fuse_*" options are accepted and change nothing (flm_query "token_path"
+ *              reports none).  Prompts and every batched entry point run the INT8 kernels on an int8 copy of one layer's weights, unpacked in front of its GEMMs
+ *   refused    world > 1 at flm_ctx_create (FLM_ERR_UNSUPPORTED); an upload whose src_qtype differs from the context's, either way, and src_qtype 3 for the embedding table
+ *              (FLM_ERR_INVALID); flm_op_matmul_skinny (INT8 only) */
+#define FLM_QT_INT4  3
 
 /* tensor kinds == .flm TensorType (src/model_loaders/flm_loader.cpp:50-67) */
 #define FLM_T_TOKEN_EMBD  1
@@ -72,7 +84,7 @@ typedef struct flm_model_desc {
     int32_t vocab_size;
     int32_t max_seq_len;      /* reference clamps to 1024 (transformer.cpp:32); here any length whose scores (4 bytes per position) fit the
                                * LDS beside a head's K/V tiles: ~22 000 positions at head size 128 (FLM_ERR_UNSUPPORTED beyond) */
-    int32_t quant_type;       /* FLM_QT_INT8 | FLM_QT_INT16: type of the linear layers and activations */
+    int32_t quant_type;       /* FLM_QT_INT8 | FLM_QT_INT16: type of the linear layers and activations; FLM_QT_INT4: 4-bit linear layers, int8 activations (above) */
     int32_t quant_group_size; /* 64 */
 } flm_model_desc;
 
