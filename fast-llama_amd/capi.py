@@ -950,13 +950,16 @@ def op_matmul_q(qt, W, sW, X, sX, gs=64):
     return out
 
 
-def op_matmul_skinny(W, sW, X, sX, gs=64):
-    """flm_op_matmul_skinny: the verify pass's int8 GEMM (k_gemm_q8_skinny), 1 <= X.shape[0] <= 16 -> out[w][m]"""
-    W = np.ascontiguousarray(W, dtype=np.int8); X = np.ascontiguousarray(X, dtype=np.int8)
+def op_matmul_skinny(W, sW, X, sX, gs=64, qt=QT_INT8):
+    """flm_op_matmul_skinny: the verify pass's GEMM, 1 <= X.shape[0] <= 16 -> out[w][m].  qt = QT_INT8: W int8 [m, n] (k_gemm_q8_skinny); QT_INT4: W the packed
+    nibbles, uint8 [m, n / 2] (pack_int4), against the int8 X (k_gemm_q4_skinny)"""
+    W = np.ascontiguousarray(W, dtype=np.uint8 if qt == QT_INT4 else np.int8); X = np.ascontiguousarray(X, dtype=np.int8)
     sW = np.ascontiguousarray(sW, dtype=np.float32); sX = np.ascontiguousarray(sX, dtype=np.float32)
     m, n = W.shape; w = X.shape[0]
+    if qt == QT_INT4:
+        n *= 2
     out = np.empty((w, m), dtype=np.float32)
-    _check(lib().flm_op_matmul_skinny(QT_INT8, _p(out), _p(W), _p(sW), _p(X), _p(sX), m, n, w, gs))
+    _check(lib().flm_op_matmul_skinny(qt, _p(out), _p(W), _p(sW), _p(X), _p(sX), m, n, w, gs))
     return out
 
 

@@ -122,24 +122,27 @@ int flm_op_matmul_q(int qt, float* out, const void* W, const float* sW, const vo
     return FLM_OK;
 }
 
-/* quant::matmul for 1 <= w <= 16 batch rows through k_gemm_q8_skinny, the verify pass's int8 GEMM (plain store epilogue): out[w][m] */
+/* quant::matmul for 1 <= w <= 16 batch rows through k_gemm_q8_skinny, the verify pass's int8 GEMM (plain store epilogue): out[w][m].  INT4 (W4A8): W is [m][n / 2]
+   nibbles in the interchange order, repacked as an upload does, X is int8: k_gemm_q4_skinny on the packed matrix */
 int flm_op_matmul_skinny(int qt, float* out, const void* W, const float* sW, const void* X, const float* sX, int m, int n, int w, int gs) {
     if (!out || !W || !sW || !X || !sX || m < 1 || n < 1 || w < 1 || w > kSkinnyTokens || gs != kGroup || n % kGroup) return FLM_ERR_INVALID;
-    if (qt != FLM_QT_INT8) return FLM_ERR_UNSUPPORTED;
-    const size_t sn = n / kGroup;
+    if (qt != FLM_QT_INT8 && qt != FLM_QT_INT4) return FLM_ERR_UNSUPPORTED;
+    const bool w4 = qt == FLM_QT_INT4;
+    const size_t sn = n / kGroup, wbytes = (size_t)m * wrow_bytes(qt, n);
     DevBuf dW, dsW, dX, dsX, dsWT, dO;
-    if (dW.alloc((size_t)m * n) || dsW.alloc((size_t)m * sn * 4) || dX.alloc((size_t)w * n) || dsX.alloc((size_t)w * sn * 4) || dsWT.alloc((size_t)m * sn * 4) || dO.alloc((size_t)w * m * 4)) return FLM_ERR_OOM;
+    if (dW.alloc(wbytes) || dsW.alloc((size_t)m * sn * 4) || dX.alloc((size_t)w * n) || dsX.alloc((size_t)w * sn * 4) || dsWT.alloc((size_t)m * sn * 4) || dO.alloc((size_t)w * m * 4)) return FLM_ERR_OOM;
     {   // the weight scales once more, group-major (k_transpose_scales on the model path)
         std::vector<float> tw((size_t)m * sn);
         for (int r = 0; r < m; ++r) for (size_t g = 0; g < sn; ++g) tw[g * m + r] = sW[(size_t)r * sn + g];
         OPC(hipMemcpy(dsWT.p, tw.data(), tw.size() * 4, hipMemcpyHostToDevice));
     }
-    OPC(hipMemcpy(dW.p, W, (size_t)m * n, hipMemcpyHostToDevice)); OPC(hipMemcpy(dsW.p, sW, (size_t)m * sn * 4, hipMemcpyHostToDevice));
+    OPC(hipMemcpy(dW.p, W, wbytes, hipMemcpyHostToDevice)); OPC(hipMemcpy(dsW.p, sW, (size_t)m * sn * 4, hipMemcpyHostToDevice));
     OPC(hipMemcpy(dX.p, X, (size_t)w * n, hipMemcpyHostToDevice)); OPC(hipMemcpy(dsX.p, sX, (size_t)w * sn * 4, hipMemcpyHostToDevice));
     OPC(hipMemset(dO.p, 0xff, (size_t)w * m * 4));                                      // (an output nobody stored reads as NaN)
+    if (w4) { int r = repack_w4(nullptr, 0, dW.p, wbytes); if (r) return r; }
     GemmArgs g{dW.p, dsW.as<float>(), dX.p, dsX.as<float>(), dO.as<float>(), m, n, m, w, nullptr, dsWT.as<float>()};
-    const char* nb = getenv("FLM_OP_SKINNY_NB");                  // tests: 1 / 2 = fragments per wave (by size otherwise: two only from 8192 rows on)
-    int r = launch_gemm_skinny_store(nullptr, 0, g, nb ? atoi(nb) : 0); if (r) return r;
+    const char* nb = getenv("FLM_OP_SKINNY_NB");                  // tests: 1 / 2 = fragments per wave (by size otherwise: two only from 8192 rows on, w4: beyond 16384)
+    int r = launch_gemm_skinny_store(nullptr, 0, g, nb ? atoi(nb) : 0, w4); if (r) return r;
     OPC(hipDeviceSynchronize());
     OPC(hipMemcpy(out, dO.p, (size_t)w * m * 4, hipMemcpyDeviceToHost));
     return FLM_OK;

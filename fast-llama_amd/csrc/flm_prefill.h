@@ -582,6 +582,115 @@ __global__ void __launch_bounds__(64) k_gemm_q8_skinny(const GemmArgs a) {
     skinny_epilogue<EPI, NB>(a, acc, r0 + l15, lane);
 }
 
+// ------------------------------------------------------------------------------------------
+// The skinny W4A8 GEMM: k_gemm_q8_skinny's contract (tokens = A, weight rows = B of v_mfma_i32_16x16x64_i8, C/D col = lane & 15 = the weight row, row = 4 (lane >> 4)
+// + reg = the token, one wave per workgroup, activation scales [groups][16] in LDS, the chain step and skinny_epilogue unchanged) on a matrix in the DEVICE nibble layout
+// (flm_gemv4.h) -- a.W is [rows][n / 2] packed bytes, nothing is unpacked to memory.
+//   * operand: lane (l15, q) owns weights 16 q .. 16 q + 15 of group g of its row = the 8 bytes at row * n / 2 + 32 g + 8 q, ONE 8-byte buffer load.  Its two words are
+//     the B operand {w0 & M, (w0 >> 4) & M, w1 & M, (w1 >> 4) & M}, M = 0x0F0F0F0F: the 16 offset nibbles u = q + 8 in column order, byte for byte next to the 16
+//     activation bytes the lane loads at 64 g + 16 q.  Six VALU per fragment and group, no per-byte shift, no sign extension.
+//   * the offset leaves once per group, exactly: sum (u - 8) x = sum u x - 8 sum x.  One more MFMA per group with B = 0x01010101 gives sum x of every token in the C
+//     layout (every column alike); shifted left by 3 and negated (4 VALU, shared by the NB fragments) it is the accumulator INPUT of the fragment MFMAs, whose result is
+//     then the exact int32 dot of the sign-extended nibbles (|sum u x| <= 64 * 15 * 127, |8 sum x| <= 8 * 64 * 127).  The float chain behind it is the int8 kernel's.
+//   * ring: a fragment's slot is 8 bytes, half of int8's, so the ring holds D = 16 (NB = 1) or 12 (NB = 2) groups.  The activation ring has the SAME depth although
+//     its bytes come from L2: a wave's loads return in issue order, so a wait for the activation of group g + 1 from a shallower ring would also wait for every weight
+//     load issued before it, and the weight ring's depth would shrink to the activation ring's.  One wave per workgroup and at most a few workgroups per CU: the 112 /
+//     120 ring registers limit nothing.
+//   * zeros: a zero WORD now means sixteen weights of -8, not 0.  Rows past the matrix: their weight loads are out of range (words 0, dot = -8 sum x) and so are their
+//     scale loads -- sw = 0, fma(0 * sx, d, acc) = acc -- and skinny_epilogue masks them at the store.  Groups past the end (the ring's last round) and token columns
+//     >= B read zero ACTIVATIONS: sum x = 0 and every product is 0, so d = 0 whatever the weight words are; their sx (LDS) and sw are 0 as well.
+//   num_records of the weight descriptor is in BYTES of the packed matrix (SWIGLU: of both halves).
+// ------------------------------------------------------------------------------------------
+typedef unsigned v2u __attribute__((ext_vector_type(2)));
+template <bool T> struct SkinnyTail { static constexpr bool value = T; };
+__host__ __device__ constexpr int skinny4_depth(int nb) { return nb == 1 ? 16 : 12; }                    // groups in flight per wave
+__host__ __device__ inline int skinny4_groups_padded(int sn, int nb) { const int d = skinny4_depth(nb); return (sn + d - 1) / d * d + d; }
+__host__ __device__ inline size_t skinny4_lds_bytes(int n, int nb) { return (size_t)skinny4_groups_padded(n / kGroup, nb) * kSkinnyTokens * 4; }
+// grid: ceil(rows / (16 NB)) workgroups of 64 threads (SWIGLU: ceil(rows / 16), NB = 2); skinny4_lds_bytes(n, NB) of dynamic LDS; B <= 16; single GPU (no peers)
+// waves_per_eu(2): with at most 256 registers to a wave the compiler keeps the MFMA results in VGPRs; given 512 it puts them into AGPRs and pays 12 v_accvgpr copies per group
+template <int EPI, int NB>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) k_gemm_q4_skinny(const GemmArgs a) {
+    constexpr bool TWO = EPI == EPI_SWIGLU;
+    static_assert(!TWO || NB == 2, "gate and up are the two B fragments of the wave");
+    constexpr int D = skinny4_depth(NB);
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    float* const sxl = reinterpret_cast<float*>(lds);                       // [groups, padded][16 tokens]
+    const int lane = threadIdx.x, l15 = lane & 15, q = lane >> 4;
+    const int sn = a.n / kGroup, snp = skinny4_groups_padded(sn, NB);
+    const int r0 = blockIdx.x * (TWO ? 16 : 16 * NB);
+    for (int i = lane; i < snp * kSkinnyTokens; i += 64) { const int g = i >> 4, b = i & 15; sxl[i] = (g < sn && b < a.B) ? a.Xs[(size_t)b * sn + g] : 0.0f; }
+    __syncthreads();
+    const unsigned xbytes = (unsigned)a.n, wbytes = (unsigned)a.n / 2;      // a row of activations, a row of packed weights
+    constexpr unsigned kOOB = 0x80000000u, kWGroup = kGroup / 2, kNib = 0x0F0F0F0Fu;
+    const unsigned s_rows = (TWO ? 2u : 1u) * (unsigned)a.rows;
+    const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.W), 0, (int)(s_rows * wbytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rX = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.Xq), 0, (int)((unsigned)a.B * xbytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rS = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.sWT), 0, (int)(s_rows * (unsigned)sn * 4), 0x00020000);
+    // fragment j: rows r0 + 16 j .. (SWIGLU: rows r0 .. of W1 (j = 0) and of W3 (j = 1)).  A dead lane (a row past the matrix, a token column >= B) carries bit 31 in its
+    // offsets, a dead group ORs it in: an offset of 2^31 or more is out of range of every descriptor here (the launcher bounds them), and no sum below wraps
+    unsigned woff[NB], soff[NB];
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+        const int row = r0 + (TWO ? 0 : 16 * j) + l15;
+        const unsigned wrow = (unsigned)(TWO ? j * a.rows + row : row);
+        woff[j] = row < a.rows ? wrow * wbytes + (unsigned)q * 8 : kOOB;
+        soff[j] = row < a.rows ? wrow * 4 : kOOB;
+    }
+    const unsigned xoff = l15 < a.B ? (unsigned)l15 * xbytes + (unsigned)q * 16 : kOOB;
+    const unsigned sstep = s_rows * 4;
+    v2u wr[D][NB]; v4u xr[D]; unsigned sr[D][NB];
+    // groups gb + k -> ring slot k.  A round's addresses are one VALU add per stream (the step's share is the instruction's immediate offset) plus one per scale load;
+    // TAIL: the round may run past the last group -- those loads go out of range and are never issued to memory.  The full rounds carry no test at all
+    auto fetch = [&](auto tail, const int k, const int gb, const unsigned (&wb)[NB], const unsigned xb) {
+        constexpr bool TAIL = decltype(tail)::value;
+        const unsigned dead = TAIL && gb + k >= sn ? kOOB : 0u;           // (uniform: a scalar select)
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            wr[k][j] = __builtin_bit_cast(v2u, __builtin_amdgcn_raw_buffer_load_b64(rW, (int)((wb[j] + (unsigned)k * kWGroup) | dead), 0, 0));
+            sr[k][j] = __builtin_amdgcn_raw_buffer_load_b32(rS, (int)((soff[j] + (unsigned)(gb + k) * sstep) | dead), 0, 0);
+        }
+        xr[k] = __builtin_amdgcn_raw_buffer_load_b128(rX, (int)((xb + (unsigned)k * kGroup) | dead), 0, 0);
+    };
+    float acc[NB][4];
+#pragma unroll
+    for (int j = 0; j < NB; ++j)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[j][i] = 0.f;
+#pragma unroll
+    for (int k = 0; k < D; ++k) fetch(SkinnyTail<true>{}, k, 0, woff, xoff);
+    const v4i ones = {0x01010101, 0x01010101, 0x01010101, 0x01010101}, z = {0, 0, 0, 0};
+    auto round = [&](auto tail, const int g0) {                          // consumes groups g0 .. g0 + D - 1, requests g0 + D .. g0 + 2 D - 1 into their slots
+        unsigned wb[NB];
+#pragma unroll
+        for (int j = 0; j < NB; ++j) wb[j] = woff[j] + (unsigned)(g0 + D) * kWGroup;
+        const unsigned xb = xoff + (unsigned)(g0 + D) * kGroup;
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            const int g = g0 + k;                                           // (g >= sn in the last round: zero activations, zero scales)
+            const float4 sx = *reinterpret_cast<const float4*>(sxl + g * kSkinnyTokens + 4 * q);
+            const v4i x = __builtin_bit_cast(v4i, xr[k]);
+            const v4i sum = __builtin_amdgcn_mfma_i32_16x16x64_i8(x, ones, z, 0, 0, 0);      // sum x of tokens 4 q .. 4 q + 3, in every column
+            const v4i off = {__mul24(sum[0], -8), __mul24(sum[1], -8), __mul24(sum[2], -8), __mul24(sum[3], -8)};      // (|sum x| <= 64 * 127: 14 bits)
+#pragma unroll
+            for (int j = 0; j < NB; ++j) {
+                const v2u w = wr[k][j];
+                const v4u u = {w[0] & kNib, (w[0] >> 4) & kNib, w[1] & kNib, (w[1] >> 4) & kNib};
+                const v4i d = __builtin_amdgcn_mfma_i32_16x16x64_i8(x, __builtin_bit_cast(v4i, u), off, 0, 0, 0);
+                const float sw = __uint_as_float(sr[k][j]);
+                acc[j][0] = __fmaf_rn(__fmul_rn(sw, sx.x), (float)d[0], acc[j][0]);   // quant_operators.cpp:274
+                acc[j][1] = __fmaf_rn(__fmul_rn(sw, sx.y), (float)d[1], acc[j][1]);
+                acc[j][2] = __fmaf_rn(__fmul_rn(sw, sx.z), (float)d[2], acc[j][2]);
+                acc[j][3] = __fmaf_rn(__fmul_rn(sw, sx.w), (float)d[3], acc[j][3]);
+            }
+            fetch(tail, k, g0 + D, wb, xb);
+        }
+    };
+    int g0 = 0;
+    for (; g0 + 2 * D <= sn; g0 += D) round(SkinnyTail<false>{}, g0);
+    for (; g0 < sn; g0 += D) round(SkinnyTail<true>{}, g0);
+    skinny_epilogue<EPI, NB>(a, acc, r0 + l15, lane);
+}
+
 // qkv[b] = [q ; k ; v] (dim each) of token b at position pos0 + b: RoPE on q and k (rope_v2 pairs), q -> qout[b], k / v -> cache rows
 inline __global__ void k_rope_kv_rows(const float* qkv, float* qout, float* kcache, float* vcache, const float* rope_cos, const float* rope_sin,
                                int dim, int hs, int max_seq, int pos0) {

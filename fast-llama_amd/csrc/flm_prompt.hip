@@ -78,10 +78,31 @@ int launch_gemm_skinny(flm_ctx* c, hipStream_t st, const GemmArgs& g, int force_
     HIPC(c, hipGetLastError());
     return FLM_OK;
 }
-// one GEMM of the batched path: the tiles, or -- int8, `skinny` (the verify pass under "spec_gemm" 1) -- the skinny kernel
+// The skinny W4A8 GEMM (flm_prefill.h k_gemm_q4_skinny): the same refusals and the same split as above, on a PACKED matrix in the device nibble layout -- g.W is
+// [rows][n / 2] bytes and the 2 GiB bound of the buffer descriptor is on those.  Fragments per wave, measured at the 7B shape with the choice forced either way (DESIGN.md
+// section 5o): one while the one-wave workgroups are no more than the SIMDs (Wo, W2: 256; QKV: 768 -- 17.6 us against 20.8 with two), two beyond (the classifier: 29.7 us
+// against 35.3 with one); the int8 kernel's rule (two once every CU has a workgroup) would give QKV two.
+template <int EPI>
+int launch_gemm_skinny_w4(flm_ctx* c, hipStream_t st, const GemmArgs& g, int force_nb = 0) {
+    if (g.B < 1 || g.B > kSkinnyTokens || g.n_peer) return fail(c, FLM_ERR_INVALID, "skinny gemm: 1 .. 16 tokens, one GPU");
+    if ((double)g.rows * (g.n / 2) * (EPI == EPI_SWIGLU ? 2 : 1) >= 2147483648.0 || skinny4_lds_bytes(g.n, 1) > 64 * 1024 || skinny4_lds_bytes(g.n, 2) > 64 * 1024)
+        return fail(c, FLM_ERR_UNSUPPORTED, "skinny gemm: packed matrix of 2 GiB or more, or rows longer than 65536");
+    const int cus = c ? c->cu_count : 256;
+    if constexpr (EPI == EPI_SWIGLU) hipLaunchKernelGGL((k_gemm_q4_skinny<EPI_SWIGLU, 2>), dim3((g.rows + 15) / 16), dim3(64), skinny4_lds_bytes(g.n, 2), st, g);
+    else if (force_nb == 2 || (force_nb == 0 && (g.rows + 15) / 16 > 4 * cus)) hipLaunchKernelGGL((k_gemm_q4_skinny<EPI, 2>), dim3((g.rows + 31) / 32), dim3(64), skinny4_lds_bytes(g.n, 2), st, g);
+    else hipLaunchKernelGGL((k_gemm_q4_skinny<EPI, 1>), dim3((g.rows + 15) / 16), dim3(64), skinny4_lds_bytes(g.n, 1), st, g);
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
+// which GEMM family a pass's weight pointers belong to: pass_weights / pass_classifier decide it together with the pointers
+enum GemmKind { GEMM_TILES = 0, GEMM_SKINNY8, GEMM_SKINNY4 };
+// one GEMM of the batched path: the tiles, or -- the verify pass under "spec_gemm" 1 -- the skinny kernel of the weights' type (int8 bytes | packed nibbles)
 template <int QT, int EPI>
-int launch_gemm_any(flm_ctx* c, hipStream_t st, const GemmArgs& g, int use_mfma, bool skinny) {
-    if constexpr (QT == QT_INT8) { if (skinny) return launch_gemm_skinny<EPI>(c, st, g); }
+int launch_gemm_any(flm_ctx* c, hipStream_t st, const GemmArgs& g, int use_mfma, GemmKind kind) {
+    if constexpr (QT == QT_INT8) {
+        if (kind == GEMM_SKINNY4) return launch_gemm_skinny_w4<EPI>(c, st, g);
+        if (kind == GEMM_SKINNY8) return launch_gemm_skinny<EPI>(c, st, g);
+    }
     return launch_gemm<QT, EPI>(c, st, g, use_mfma);
 }
 
@@ -232,15 +253,18 @@ int launch_rope_kv_segs(flm_ctx* c, hipStream_t st, const float* qkv, float* qou
 // tree (flm_verify_tree_greedy; null: every launch is the one made without it): the B rows are a tree of candidates at `pos` (flm_tree.h) -- the fan's route with
 // k_rope_kv_tree and k_attn_tree; tree_dev (the lookup loop under "spec_branches"): the rows' parents, depths and masks are the ones k_spec_draft_tree left in device
 // memory, `tree` carries pos and n only
-// W4A8 (quant_type INT4): the batched kernels run as QT_INT8 on an int8 copy of the weights they are about to read -- k_unpack_w4 on the pass's stream (inside the capture
-// where the pass is captured) in front of a layer's GEMMs / the classifier's, into the context's scratch; the scales and their group-major copies are the packed matrix's
-// own.  Bit-identical by construction (the int8 kernels on the sign-extended nibbles); it costs one more read of the packed weights and a write + read of their int8 copy
-// per layer and pass, and for the classifier per CHUNK of rows its stage runs -- a nibble-fragment loader for the tiles is the follow-up.
+// W4A8 (quant_type INT4): the batched kernels run as QT_INT8.  A `skinny` pass (<= 16 rows under "spec_gemm" 1, one GPU) reads the PACKED matrices where they lie, through
+// k_gemm_q4_skinny: nothing is unpacked, 0.5 bytes per weight and pass.  Every other pass runs the tiles on an int8 copy of the weights it is about to read -- k_unpack_w4
+// on the pass's stream (inside the capture where the pass is captured) in front of a layer's GEMMs / the classifier's, into the context's scratch: one more read of the
+// packed weights and a write + read of their int8 copy per layer and pass, and for the classifier per CHUNK of rows its stage runs -- a nibble-fragment loader for the
+// 64 x 64 / 128 x 128 tiles is the follow-up.  The scales and their group-major copies are the packed matrix's own on both routes; both are bit-identical by construction
+// (the int8 arithmetic on the sign-extended nibbles).
 static inline bool tiles_int8(const flm_ctx* c) { return c->d.quant_type != FLM_QT_INT16; }
-// the ONE place a pass picks layer l's weight pointers
-static int pass_weights(flm_ctx* c, hipStream_t st, int l, LayerW& w) {
+// the ONE place a pass picks layer l's weight pointers and the GEMM family that reads them
+static int pass_weights(flm_ctx* c, hipStream_t st, int l, bool skinny, LayerW& w, GemmKind& kind) {
     w = c->layers[l];
-    if (c->d.quant_type != FLM_QT_INT4) return FLM_OK;
+    kind = !skinny ? GEMM_TILES : c->d.quant_type == FLM_QT_INT4 ? GEMM_SKINNY4 : GEMM_SKINNY8;
+    if (c->d.quant_type != FLM_QT_INT4 || kind == GEMM_SKINNY4) return FLM_OK;
     char* p = c->w4_scratch;
     for (QMat* m : {&w.qkv, &w.o, &w.w13, &w.w2}) {
         const size_t n = (size_t)m->rows * m->cols;
@@ -250,9 +274,10 @@ static int pass_weights(flm_ctx* c, hipStream_t st, int l, LayerW& w) {
     return FLM_OK;
 }
 // ... and the classifier's
-static int pass_classifier(flm_ctx* c, hipStream_t st, const void** q) {
+static int pass_classifier(flm_ctx* c, hipStream_t st, bool skinny, const void** q, GemmKind& kind) {
     *q = c->cls.q;
-    if (c->d.quant_type != FLM_QT_INT4) return FLM_OK;
+    kind = !skinny ? GEMM_TILES : c->d.quant_type == FLM_QT_INT4 ? GEMM_SKINNY4 : GEMM_SKINNY8;
+    if (c->d.quant_type != FLM_QT_INT4 || kind == GEMM_SKINNY4) return FLM_OK;
     *q = c->w4_scratch;
     return unpack_w4(c, st, c->w4_scratch, c->cls.q, (size_t)c->cls.rows * c->cls.cols / 2);
 }
@@ -289,7 +314,7 @@ int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req
     hipLaunchKernelGGL(k_embed_rows, dim3(B), dim3(256), 0, st, c->pf_x, (const void*)c->emb, (const float*)c->emb_s, c->emb_qt, dim, (const int*)c->prompt_dev);
     HIPC(c, hipGetLastError());
     for (int l = 0; l < L; ++l) {
-        LayerW w; r = pass_weights(c, st, l, w); if (r) return r;
+        LayerW w; GemmKind kind; r = pass_weights(c, st, l, skinny, w, kind); if (r) return r;
         float* const kc = c->kcache + (size_t)l * kv_layer + (size_t)row0 * hs;    // (row0: the slot's origin; the stride between two heads' rows stays kv_rows)
         float* const vc = c->vcache + (size_t)l * kv_layer + (size_t)row0 * hs;
         // x2 = rmsnorm(x1); qx = quantize(x2); q,k,v = W x; RoPE; cache rows   (transformer.cpp:132-135, 386-395, 431-439)
@@ -297,29 +322,29 @@ int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req
         r = launch_rows<QT, PRO_RMSNORM_QUANT>(c, st, ra, B, tp); if (r) return r;
         GemmArgs g{w.qkv.q, w.qkv.s, c->pf_xq, c->pf_xs, c->pf_qkv, 3 * dimL, dim, 3 * dimL, B, c->pf_xst, w.qkv.st};
         if (tree) {
-            r = launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, skinny); if (r) return r;
+            r = launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, kind); if (r) return r;
             r = launch_rope_kv_tree(c, st, c->pf_qkv, c->pf_q, kc, vc, c->rope_cos, c->rope_sin, dimL, hs, c->kv_rows, *tree, tree_dev); if (r) return r;
         }
         else if (fan) {
-            r = launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, skinny); if (r) return r;
+            r = launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, kind); if (r) return r;
             r = launch_rope_kv_fan(c, st, c->pf_qkv, c->pf_q, kc, vc, c->rope_cos, c->rope_sin, dimL, hs, c->kv_rows, *fan); if (r) return r;
         }
         else if (segs) {
-            r = launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, skinny); if (r) return r;
+            r = launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, kind); if (r) return r;
             if (segs->n_step > 0) { r = launch_rope_kv_slots(c, st, c->pf_qkv, c->pf_q, kc, vc, c->rope_cos, c->rope_sin, dimL, hs, c->kv_rows, *rslots); if (r) return r; }
             if (segs->n_step < B) { r = launch_rope_kv_segs(c, st, c->pf_qkv, c->pf_q, kc, vc, c->rope_cos, c->rope_sin, dimL, hs, c->kv_rows, *rsegs, B); if (r) return r; }
         }
         else if (slots) {
-            r = launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, skinny); if (r) return r;
+            r = launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, kind); if (r) return r;
             r = launch_rope_kv_slots(c, st, c->pf_qkv, c->pf_q, kc, vc, c->rope_cos, c->rope_sin, dimL, hs, c->kv_rows, *rslots); if (r) return r;
         }
         else if ((QT == QT_INT16 || c->use_mfma || skinny) && dimL % 32 == 0 && hs % 2 == 0) {      // (int16: always the matrix-core tiles -- round 5: with the same epilogues as the int8 tiles)
             // RoPE and the cache rows as the epilogue of the matrix-core tiles: no [tokens][3 dim] round trip, no k_rope_kv_rows
             g.qout = c->pf_q; g.kcache = kc; g.vcache = vc;
             g.rope_cos = c->rope_cos; g.rope_sin = c->rope_sin; g.dim = dimL; g.hs = hs; g.max_seq = c->kv_rows /* (the stride between two heads' cache rows) */; g.pos0 = pos;
-            r = launch_gemm_any<QT, EPI_ROPE_KV>(c, st, g, c->use_mfma, skinny); if (r) return r;
+            r = launch_gemm_any<QT, EPI_ROPE_KV>(c, st, g, c->use_mfma, kind); if (r) return r;
         } else {
-            r = launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, skinny); if (r) return r;
+            r = launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, kind); if (r) return r;
             hipLaunchKernelGGL(k_rope_kv_rows, dim3(B), dim3(256), 0, st, (const float*)c->pf_qkv, c->pf_q, kc, vc,
                                (const float*)c->rope_cos, (const float*)c->rope_sin, dimL, hs, c->kv_rows, pos);
             HIPC(c, hipGetLastError());
@@ -372,7 +397,7 @@ int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req
         r = launch_rows<QT, PRO_QUANT>(c, st, rq, B, tp); if (r) return r;
         GemmArgs go{w.o.q, w.o.s, c->pf_xq, c->pf_xs, c->pf_x + col_o, dim, dim, rows_o, B, c->pf_xst, w.o.st};
         peers(go, go.out);
-        r = launch_gemm_any<QT, EPI_RESIDUAL>(c, st, go, c->use_mfma, skinny); if (r) return r;
+        r = launch_gemm_any<QT, EPI_RESIDUAL>(c, st, go, c->use_mfma, kind); if (r) return r;
         if (tp) { r = exchange(c, st, XK_X1, nullptr, nullptr, 0); if (r) return r; }
         // hd = swiglu(W1 qx, W3 qx) with qx = quantize(rmsnorm(x1))   (transformer.cpp:144-147, 468-483): this rank's slice of hd
         RowsArgs rf{c->pf_x, w.ffn_norm, c->pf_xq, c->pf_xs, dim, c->pf_xst};
@@ -381,7 +406,7 @@ int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req
             // 128 x 128 tiles of 64 gate + 64 up rows: the GEMM's epilogue is the SwiGLU
             GemmArgs g13{w.w13.q, w.w13.s, c->pf_xq, c->pf_xs, c->pf_hd + col_h, hid, dim, hidL, B, c->pf_xst, w.w13.st};
             peers(g13, g13.out);
-            r = launch_gemm_any<QT, EPI_SWIGLU>(c, st, g13, c->use_mfma, skinny); if (r) return r;
+            r = launch_gemm_any<QT, EPI_SWIGLU>(c, st, g13, c->use_mfma, kind); if (r) return r;
         } else {
             GemmArgs g13{w.w13.q, w.w13.s, c->pf_xq, c->pf_xs, c->pf_gu, 2 * hidL, dim, 2 * hidL, B, c->pf_xst, w.w13.st};
             r = launch_gemm<QT, EPI_STORE>(c, st, g13, c->use_mfma); if (r) return r;
@@ -395,7 +420,7 @@ int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req
         r = launch_rows<QT, PRO_QUANT>(c, st, rh, B, tp); if (r) return r;
         GemmArgs g2{w.w2.q, w.w2.s, c->pf_xq, c->pf_xs, c->pf_x + col_o, dim, hid, rows_o, B, c->pf_xst, w.w2.st};
         peers(g2, g2.out);
-        r = launch_gemm_any<QT, EPI_RESIDUAL>(c, st, g2, c->use_mfma, skinny); if (r) return r;
+        r = launch_gemm_any<QT, EPI_RESIDUAL>(c, st, g2, c->use_mfma, kind); if (r) return r;
         if (tp) { r = exchange(c, st, XK_X1, nullptr, nullptr, 0); if (r) return r; }
     }
     return FLM_OK;
@@ -439,7 +464,7 @@ int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers, bool skinny,
             return fail(c, FLM_ERR_INVALID, "prefill: a batch row outside its slot, or a slot outside the cache");
     return tiles_int8(c) ? prefill_batched<QT_INT8>(c, B, pos, all_layers, skinny, fan, row0, slots_in, nullptr, pfx) : prefill_batched<QT_INT16>(c, B, pos, all_layers, skinny, fan, row0, slots_in, nullptr, pfx);
 }
-int launch_gemm_skinny_store(flm_ctx* c, hipStream_t st, const GemmArgs& g, int force_nb) { return launch_gemm_skinny<EPI_STORE>(c, st, g, force_nb); }
+int launch_gemm_skinny_store(flm_ctx* c, hipStream_t st, const GemmArgs& g, int force_nb, bool w4) { return w4 ? launch_gemm_skinny_w4<EPI_STORE>(c, st, g, force_nb) : launch_gemm_skinny<EPI_STORE>(c, st, g, force_nb); }
 
 // ---------------------------------------------------------------------------------------------
 // flm_score_tokens: the classifier for a chunk of the batch's rows.  The row prologue is the decode classifier's (rmsnorm with the output norm's weight, quantize), the tiles
@@ -533,9 +558,9 @@ static int classify_rows_t(flm_ctx* c, int row0, int m, float* stage, bool skinn
     // logits = Wcls quantize(rmsnorm(x1))   (transformer.cpp:154-160)
     RowsArgs ra{c->pf_x + (size_t)row0 * dim, c->out_norm, c->pf_xq, c->pf_xs, dim, c->pf_xst};
     int r = launch_rows<QT, PRO_RMSNORM_QUANT>(c, st, ra, m); if (r) return r;
-    const void* wq = nullptr; r = pass_classifier(c, st, &wq); if (r) return r;
+    const void* wq = nullptr; GemmKind kind; r = pass_classifier(c, st, skinny && QT == QT_INT8 && m <= kSkinnyTokens, &wq, kind); if (r) return r;
     GemmArgs g{wq, c->cls.s, c->pf_xq, c->pf_xs, stage, V, dim, V, m, c->pf_xst, c->cls.st};
-    return launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, skinny && m <= kSkinnyTokens);
+    return launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, kind);
 }
 template <int QT>
 static int score_classify_t(flm_ctx* c, int row0, int m, float* stage, bool skinny, int* argmax_out, const SpecDraw* draw = nullptr) {

@@ -51,9 +51,10 @@ extern "C" {
  *              scales fp32 [rows][cols / 64].  flm_upload_tensor(src_qtype 3) takes it with the LOGICAL cols, flm_op_matmul_q(3, ..) takes W in it, flm_op_quantize(3, ..) writes it
  *   quantizer  an fp32 linear tensor uploaded into an INT4 context, and flm_op_quantize(3, ..): r = max|x| / 7 (IEEE fp32 division), q = trunc(x / r); an all-zero group r = 0, q = 0
  *   launches   one kernel per phase under the token graph: no fused form exists for the type, the "fuse_*" options are accepted and change nothing (flm_query "token_path"
- *              reports none).  Prompts and every batched entry point run the INT8 kernels on an int8 copy of one layer's weights, unpacked in front of its GEMMs
+ *              reports none).  Prompts and every batched entry point run the INT8 kernels on an int8 copy of one layer's weights, unpacked in front of its GEMMs --
+ *              but a pass of <= 16 rows under option "spec_gemm" 1, which reads the nibbles where they lie (the skinny W4A8 GEMM; flm_op_matmul_skinny(3, ..))
  *   refused    world > 1 at flm_ctx_create (FLM_ERR_UNSUPPORTED); an upload whose src_qtype differs from the context's, either way, and src_qtype 3 for the embedding table
- *              (FLM_ERR_INVALID); flm_op_matmul_skinny (INT8 only) */
+ *              (FLM_ERR_INVALID) */
 #define FLM_QT_INT4  3
 
 /* tensor kinds == .flm TensorType (src/model_loaders/flm_loader.cpp:50-67) */
@@ -201,9 +202,10 @@ int  flm_score_tokens(flm_ctx* ctx, const int32_t* tokens, int n, int pos,
  * continues at pos + m + 1 with token out_tokens[m], through any entry point.  4 <= k <= 15 (batches of 5 .. 16 rows).  Errors, with nothing launched: FLM_ERR_INVALID for k
  * outside 4 .. 15, pos + k + 1 > max_seq_len, ids outside [0, vocab); FLM_ERR_UNSUPPORTED for world > 1; FLM_ERR_STATE before the model is complete.  No vocabulary bound (an
  * argmax needs no LDS strip).  Nothing is allocated in the call; the m + 1 ids come back in one trip.
- * The weight pass: option "spec_gemm" 1 = int8 models run every GEMM of the batch through the skinny kernel (v_mfma_i32_16x16x64_i8, 16 tokens x 16 rows x one quant group per
+ * The weight pass: option "spec_gemm" 1 = int8 and int4 models run every GEMM of the batch through the skinny kernel (v_mfma_i32_16x16x64_i8, 16 tokens x 16 rows x one quant group per
  * instruction, weights from global memory straight into the operand registers, one wave per 16 or 32 rows so that every matrix of the 7B shape fills 256 CUs); 0 = the 64 x 64
- * tiles of the prompt path.  int16 models always run the hi / lo-plane tiles here: correct, not fast. */
+ * tiles of the prompt path (int4: on the unpacked int8 copy; the skinny kernel reads the packed nibbles, an 8-byte load per lane and group).  int16 models always run the
+ * hi / lo-plane tiles here: correct, not fast. */
 int  flm_verify_greedy(flm_ctx* ctx, int32_t first_token, const int32_t* drafts, int k, int pos,
                        int32_t* out_tokens /* [k + 1] */, int* n_out);
 /* Tree draft-and-verify, greedy: flm_verify_greedy with the batch's rows a TREE of candidates, for callers whose drafter has several continuations to offer.  tokens[0] is the
@@ -705,7 +707,7 @@ int  flm_debug_read(flm_ctx* ctx, int what, int layer, float* out, size_t n);
  *                    log-probability or entropy setting in force; head sizes <= 128) drafts a TREE per step -- k_spec_draft_tree keeps the B most recent longest-matching places
  *                    of the history whose continuations differ and merges them by common prefix, breadth first, into draft_len + 1 nodes on the device -- and verifies it
  *                    with flm_verify_tree_greedy's pass.  Ids, count, stop behaviour and final cache stay flm_generate's.  Every other form ignores the option.
- *   "spec_gemm"      1 = flm_verify_greedy / flm_generate_lookup and their sampled forms run the verify batch's int8 GEMMs on the skinny kernel for <= 16 rows (default 0: the prompt path's 64 x 64
+ *   "spec_gemm"      1 = flm_verify_greedy / flm_generate_lookup and their sampled forms run the verify batch's int8 / int4 GEMMs on the skinny kernel for <= 16 rows (default 0: the prompt path's 64 x 64
  *                    tiles, until both forms have been timed on the device: DESIGN.md section 5e); the same bits; no other entry point looks at it
  *   "batch_rows"     b >= 0 = flm_generate_batch admits every request and runs ragged passes with a budget of b prompt rows each (0: no bound); default -1: serial joins, then
  *                    steps; the same results; read per call
@@ -768,7 +770,8 @@ int  flm_op_quantize(int qt, void* qx, float* qs, const float* x, size_t n, int 
  * kernel); w >= 16: the tile kernels of the batched prompt path (int8 and int16 on the int8 matrix cores; FLM_OP_GEMM=1|2|3: the tile shape) */
 int  flm_op_matmul_q(int qt, float* out, const void* mat1, const float* scales1,
                      const void* mat2, const float* scales2, int m, int n, int w, int gs);
-/* the same product for 1 <= w <= 16 batch rows through the skinny int8 kernel of the verify pass (k_gemm_q8_skinny); FLM_QT_INT8 only
+/* the same product for 1 <= w <= 16 batch rows through the skinny kernels of the verify pass: FLM_QT_INT8 (k_gemm_q8_skinny) and FLM_QT_INT4
+ * (k_gemm_q4_skinny: mat1 = [m][n / 2] nibbles in the interchange order, repacked as an upload does; mat2 int8); FLM_QT_INT16: FLM_ERR_UNSUPPORTED
  * (FLM_OP_SKINNY_NB=1|2: 16-row fragments per wave; by size otherwise) */
 int  flm_op_matmul_skinny(int qt, float* out, const void* mat1, const float* scales1,
                           const void* mat2, const float* scales2, int m, int n, int w, int gs);

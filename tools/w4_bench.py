@@ -1,7 +1,11 @@
 """W4A8 against int8 on the 32-layer 7B-shaped synthetic model, one GPU: per-phase GEMV times of an INT4 context and of an INT8 context with every "fuse_*" option 0 (the
 same launch form), from flm_kernel_times at position 20, each with its bytes (flm_kernel_bytes), achieved bytes/s and share of the 8 TB/s peak; then tokens/s of
 decode_greedy over 128 steps for INT4, INT8 per phase and INT8 default (one launch per token), the three alternating, medians of `reps`.
-python tools/w4_bench.py [reps] [layers]   -- prints the tables and one JSON line"""
+python tools/w4_bench.py [reps] [layers]   -- prints the tables and one JSON line
+
+python tools/w4_bench.py --verify [reps] [layers]   -- the passes of up to 16 rows instead: the time of one flm_verify_greedy pass at B = 5, 8 and 16 rows (position 20) and
+the time per step of flm_generate_batch with 16 slots, for an INT4 context under "spec_gemm" 1 and 0 and an INT8 context under "spec_gemm" 1, the three alternating,
+medians of `reps` with min .. max.  FLM_GPU_LIB picks the library (capi.py): under the build of the commit before k_gemm_q4_skinny the first row is unpack + int8 skinny."""
 import json
 import os
 import statistics
@@ -13,8 +17,10 @@ import numpy as np
 import __graft_entry__ as g; g.load_package()
 from fast_llama_amd import capi, synth, flmfile as ff
 
-reps = int(sys.argv[1]) if len(sys.argv) > 1 else 5
-layers = int(sys.argv[2]) if len(sys.argv) > 2 else None
+verify = "--verify" in sys.argv
+args = [a for a in sys.argv[1:] if a != "--verify"]
+reps = int(args[0]) if len(args) > 0 else 5
+layers = int(args[1]) if len(args) > 1 else None
 PEAK, POS, STEPS = 8e12, 20, 128
 FUSE = ("fuse_tail", "fuse_token", "fuse_layer", "fuse_back", "fuse_qkv", "fuse_attn_o", "fuse_ffn")
 PHASES = ("qkv", "attn_o", "ffn13", "ffn2", "cls")
@@ -32,6 +38,46 @@ def context(qt, per_phase):
     return ctx
 
 
+def verify_bench():
+    """every timed window ends behind a device synchronise: verify_greedy and generate_batch return ids that are on the host"""
+    CALLS, SLOTS, SHORT, LONG = 20, 16, 9, 41
+    runs = {}
+    for name, qt, gemm in (("int4 spec_gemm 1", capi.QT_INT4, 1), ("int4 spec_gemm 0", capi.QT_INT4, 0), ("int8 spec_gemm 1", ff.QT_INT8, 1)):
+        runs[name] = context(qt, False); runs[name].set_option("spec_gemm", gemm)
+    prompt = (np.arange(POS, dtype=np.int32) * 7 + 1) % 1000
+    reqs = lambda n: [capi.BatchReq((np.arange(4, dtype=np.int32) + 11 * s) % 1000 + 1, n) for s in range(SLOTS)]   # noqa: E731
+    cases = [f"verify B={b}" for b in (5, 8, 16)] + ["batch step, 16 slots"]
+    times = {(n, c): [] for n in runs for c in cases}
+    for r in range(reps + 1):                               # the first round warms every form
+        for name, ctx in runs.items():
+            for b in (5, 8, 16):
+                ctx.reset_kv()
+                first = ctx.forward_argmax(prompt, 0)
+                drafts = (np.arange(b - 1, dtype=np.int32) * 13 + 5) % 1000
+                t0 = time.perf_counter()
+                for _ in range(CALLS):
+                    ctx.verify_greedy(first, drafts, POS)
+                times[name, f"verify B={b}"].append((time.perf_counter() - t0) / CALLS)
+            t = []
+            for n in (SHORT, LONG):                         # the steps between the two lengths: joins and the calls' fixed parts cancel
+                ctx.reset_kv()
+                t0 = time.perf_counter()
+                ctx.generate_batch(reqs(n))
+                t.append(time.perf_counter() - t0)
+            times[name, cases[-1]].append((t[1] - t[0]) / (LONG - SHORT))
+    out = {"reps": reps, "layers": next(iter(runs.values())).desc.n_layers, "lib": os.environ.get("FLM_GPU_LIB", "default"), "us": {}}
+    print(f"{'case':22s} {'context':18s} {'median us':>10s} {'min':>9s} {'max':>9s}")
+    for c in cases:
+        for n in runs:
+            t = [x * 1e6 for x in times[n, c][1:]]
+            out["us"][f"{c} / {n}"] = [round(statistics.median(t), 1), round(min(t), 1), round(max(t), 1)]
+            print(f"{c:22s} {n:18s} {statistics.median(t):10.1f} {min(t):9.1f} {max(t):9.1f}")
+    print(json.dumps(out))
+
+
+if verify:
+    verify_bench()
+    sys.exit(0)
 runs = {"int4": context(capi.QT_INT4, False), "int8 per phase": context(ff.QT_INT8, True), "int8 default": context(ff.QT_INT8, False)}
 res = {"reps": reps, "layers": runs["int4"].desc.n_layers, "kernels": {}, "tokens_per_s": {}}
 print(f"{'phase':8s} {'type':16s} {'us':>9s} {'MB':>9s} {'GB/s':>9s} {'of peak':>8s}")
