@@ -26,23 +26,11 @@ __device__ __forceinline__ uint32_t w4_word_to_device(uint32_t v) {
     for (int j = 0; j < 4; ++j) o |= (((v >> (4 * j)) & 0xFu) | (((v >> (4 * j + 16)) & 0xFu) << 4)) << (8 * j);
     return o;
 }
-// device word -> its 8 weights as int8: out.x = e0 .. e3, out.y = e4 .. e7 (one byte each, sign extended)
-__device__ __forceinline__ uint2 w4_word_to_int8(uint32_t w) {
-    const uint32_t lo = w & 0x0F0F0F0Fu, hi = (w >> 4) & 0x0F0F0F0Fu;
-    // per byte: q = u - 8; u in 0 .. 15, so (u | 0x80) - 8 never borrows across bytes, and flipping bit 7 back (-8 .. -1 -> 0xF8 .. 0xFF, 0 .. 7 -> 0x00 .. 0x07) sign-extends
-    auto sx = [](uint32_t u) { return ((u | 0x80808080u) - 0x08080808u) ^ 0x80808080u; };
-    return make_uint2(sx(lo), sx(hi));
-}
 
 // in place over the words of a packed matrix (rows x cols / 8 of them)
 inline __global__ void k_repack_w4(uint32_t* w, size_t nwords) {
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nwords; i += stride) w[i] = w4_word_to_device(w[i]);
-}
-// a packed device matrix -> plain int8 [rows][cols] (the batched path's scratch copy: its GEMM tiles then run as QT_INT8 on the same scales)
-inline __global__ void k_unpack_w4(uint2* out, const uint32_t* w, size_t nwords) {
-    const size_t stride = (size_t)gridDim.x * blockDim.x;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nwords; i += stride) out[i] = w4_word_to_int8(__builtin_nontemporal_load(w + i));
 }
 
 // The project's quantizer with F = 7 over a flat fp32 array (the third case of k_quantize_flat, flm_gpu.hip): r = max|x| / 7, q = trunc(x / r), an all-zero group r = 0, q = 0;

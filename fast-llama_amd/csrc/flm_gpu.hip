@@ -88,16 +88,10 @@ int quantize_flat(flm_ctx* c, hipStream_t st, int qt, void* q, float* s, const f
     HIPC(c, hipGetLastError());
     return FLM_OK;
 }
-// W4A8: `nbytes` of packed weights, interchange order -> device layout, in place / device layout -> int8 [rows][cols] (flm_gemv4.h)
+// W4A8: `nbytes` of packed weights, interchange order -> device layout, in place (flm_gemv4.h)
 int repack_w4(flm_ctx* c, hipStream_t st, void* w, size_t nbytes) {
     const size_t nw = nbytes / 4; size_t blocks = (nw + kBlock - 1) / kBlock; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(k_repack_w4, dim3((unsigned)blocks), dim3(kBlock), 0, st, (uint32_t*)w, nw);
-    HIPC(c, hipGetLastError());
-    return FLM_OK;
-}
-int unpack_w4(flm_ctx* c, hipStream_t st, void* out, const void* w, size_t nbytes) {
-    const size_t nw = nbytes / 4; size_t blocks = (nw + kBlock - 1) / kBlock; if (blocks > 8192) blocks = 8192; if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(k_unpack_w4, dim3((unsigned)blocks), dim3(kBlock), 0, st, (uint2*)out, (const uint32_t*)w, nw);
     HIPC(c, hipGetLastError());
     return FLM_OK;
 }
@@ -491,10 +485,6 @@ int flm_ctx_create(const flm_model_desc* desc, int device_id, int rank, int worl
     }
     if (alloc_qmat(c, c->cls, c->plan.vocab_count > 0 ? c->plan.vocab_count : 1, d.dim, qt, true)) return bail(FLM_ERR_OOM);   // (cls.st: flm_score_tokens' classifier runs on the GEMM tiles)
     c->cls.rows = c->plan.vocab_count;
-    if (qt == FLM_QT_INT4) {   // the batched path's int8 copy: the larger of one layer's matrices and the classifier (here, so that no call allocates)
-        const size_t layer = ((size_t)3 * c->dim_local + c->drow_count + (size_t)2 * c->hidden_local) * d.dim + (size_t)c->drow_count * d.hidden_dim, cls = (size_t)c->plan.vocab_count * d.dim;
-        HIPB(dev_alloc(c, &c->w4_scratch, layer > cls ? layer : cls));
-    }
     HIPB(dev_alloc(c, &c->out_norm, d.dim * 4));
 #ifndef FLM_KV_PAD
 #define FLM_KV_PAD 8
@@ -901,6 +891,7 @@ int flm_query(flm_ctx* c, const char* key, int* value) {
         {"spec_accepted", c->spec_accepted},
         {"draft_tokens", c->draft_tokens},
         {"batch_passes", c->batch_passes},
+        {"pass_gemm", c->pass_gemm},
         {"batch_prefix", c->batch_open ? c->batch_prefix : 0},
         // which hand-offs of the token's launch (short contexts) are consumed in arrival order; -1: that launch was not planned (yet)
         {"ao_active", c->la_ok[0] ? (c->la_p[0].ao_o ? 1 : 0) | (c->la_p[0].ao_2 ? 2 : 0) : -1},

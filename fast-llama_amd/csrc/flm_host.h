@@ -236,9 +236,7 @@ struct flm_ctx {
     int batch_prefix = 0;                              // flm_batch_open_prefix: the shared rows [0, S) in front of the slots (flm_prefix.h); 0: none -- every launch is the plain batch's.  A slot's pos / fed count ITS OWN rows
     int batch_passes = 0;                              // flm_query "batch_passes": weight passes (joins, steps, passes) since the last flm_batch_open
     int score_rows = 0;                                // option "score_rows": rows per classifier chunk of flm_score_tokens (0: as many as the staging holds; < 0: one row at a time through c->logits)
-    // W4A8 (quant_type INT4): the batched path's int8 copy of ONE layer's matrices [qkv | o | w13 | w2] or of the classifier, refilled by k_unpack_w4 in front of the GEMMs
-    // that read it (flm_prompt.hip pass_weights / pass_classifier); allocated at create.  A pass of <= 16 rows under "spec_gemm" 1 does not touch it (k_gemm_q4_skinny reads the nibbles)
-    char* w4_scratch = nullptr;
+    int pass_gemm = -1;                                // flm_query "pass_gemm": the GemmKind (flm_prompt.hip pass_weights) of the layer GEMMs of the most recent batched pass; -1: none yet
     std::map<GraphKey, hipGraphExec_t> graphs;        // the token graphs captured so far (flm_gpu.hip token_graph)
     std::vector<TimedLaunch>* timing = nullptr;
     std::vector<void*> owned;                          // every device allocation that lives as long as the context (flm_gpu.hip dev_alloc); flm_ctx_destroy frees these
@@ -259,7 +257,6 @@ int fail(flm_ctx* c, int code, const char* msg);
 int esz_of(int qt);
 size_t wrow_bytes(int qt, size_t cols);
 int repack_w4(flm_ctx* c, hipStream_t st, void* w, size_t nbytes);
-int unpack_w4(flm_ctx* c, hipStream_t st, void* out, const void* w, size_t nbytes);
 void split_even(int total, int parts, int idx, int* begin, int* count);
 
 // Pass geometry of k_gemv for one launch (flm_token.hip)
@@ -538,7 +535,7 @@ int launch_sample_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, 
 int launch_gemm_skinny_store(flm_ctx* c, hipStream_t st, const GemmArgs& g, int force_nb = 0, bool w4 = false);   // (flm_prompt.hip: k_gemm_q8_skinny | w4: k_gemm_q4_skinny on a packed matrix in the device layout; plain store epilogue: flm_op_matmul_skinny; c may be null; force_nb 1 / 2: that many 16-row fragments per wave, 0: by size)
 // k_score_rows on `rows` rows of n logits, ld floats apart (c may be null: flm_op_score_rows)
 int launch_score_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, int n, const int* targets, flm::ScoreRow* out, int rows);
-int launch_gemm_store(flm_ctx* c, hipStream_t st, int qt, const GemmArgs& g, int use_mfma);   // (flm_prompt.hip: one GEMM tile launch, plain store epilogue: flm_op_matmul_q)
+int launch_gemm_store(flm_ctx* c, hipStream_t st, int qt, const GemmArgs& g, int use_mfma);   // (flm_prompt.hip: one GEMM tile launch, plain store epilogue: flm_op_matmul_q; qt INT4: k_gemm_q4_mfma on a packed matrix in the device layout)
 void build_rope_table(int hs, int max_seq, std::vector<float>& cs, std::vector<float>& sn);  // (flm_gpu.hip)
 
 } // namespace fh

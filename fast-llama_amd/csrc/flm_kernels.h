@@ -31,8 +31,8 @@
 //   k_attn_ffn<QT,XR2,QKV,SPLIT> the same layer_body as one launch per layer ("fuse_token" 0; "fuse_layer" 0: without the QKV GEMV; "fuse_back" 0: off)
 //   k_gemv<QT,PRO,EPI,XR> group-quantized GEMV, HBM-bound; fused prologue (rmsnorm+quantize | quantize) and epilogue (store | residual add | SwiGLU | RoPE + KV-cache
 //                         append): the classifier of every token; every phase of a tensor-parallel rank's token; the per-phase fallback behind a timed-out hand-off
-//   k_gemv<QT_INT4,..>    the same GEMV over 4-bit weights against int8 activations (W4A8; flm_gemv4.h: the layout, k_repack_w4 at upload, k_unpack_w4 in front of the batched
-//                         path's int8 tiles): a quant group is two lanes, the nibbles' offset leaves once per group; an INT4 context's token is one launch per phase
+//   k_gemv<QT_INT4,..>    the same GEMV over 4-bit weights against int8 activations (W4A8; flm_gemv4.h: the layout, k_repack_w4 at upload; the batched path reads the same layout through
+//                         k_gemm_q4_skinny / k_gemm_q4_mfma, flm_prefill.h): a quant group is two lanes, the nibbles' offset leaves once per group; an INT4 context's token is one launch per phase
 //   k_attn_decode         fp32 single-query attention over the fp32 KV cache (heads split over workgroups at long contexts): the stand-alone launch
 //                         of the tensor-parallel token path and of "fuse_attn_o" 0
 //   k_attn_o<QT,XR,PREQ>  attention heads and the Wo GEMV in one launch ("fuse_back" 0; head sizes that are not multiples of 64; across tensor-parallel ranks)

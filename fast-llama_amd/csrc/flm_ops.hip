@@ -85,10 +85,10 @@ int flm_op_rmsnorm(float* o, const float* x, const float* w, size_t n) {
 int flm_op_matmul_q(int qt, float* out, const void* W, const float* sW, const void* X, const float* sX, int m, int n, int w, int gs) {
     if (!out || !W || !sW || !X || !sX || m < 1 || n < 1 || w < 1 || gs != kGroup || n % kGroup) return FLM_ERR_INVALID;
     if (qt != FLM_QT_INT8 && qt != FLM_QT_INT16 && qt != FLM_QT_INT4) return FLM_ERR_UNSUPPORTED;
-    // INT4 (W4A8): W is [m][n / 2] nibbles in the interchange order, X is int8.  w < 16: the nibble GEMV per row; w >= 16: unpacked to int8, the int8 tiles -- a context's two routes
+    // INT4 (W4A8): W is [m][n / 2] nibbles in the interchange order, X is int8.  w < 16: the nibble GEMV per row; w >= 16: the nibble-fed tiles (k_gemm_q4_mfma) on the repacked matrix -- a context's routes
     const bool w4 = qt == FLM_QT_INT4;
     const size_t e = esz_of(qt), sn = n / kGroup, wbytes = (size_t)m * wrow_bytes(qt, n);
-    DevBuf dW, dsW, dX, dsX, dsXT, dsWT, dO, dW8;
+    DevBuf dW, dsW, dX, dsX, dsXT, dsWT, dO;
     if (dW.alloc(wbytes) || dsW.alloc((size_t)m * sn * 4) || dX.alloc((size_t)w * n * e) || dsX.alloc((size_t)w * sn * 4) || dsXT.alloc((size_t)w * sn * 4 + 64) || dsWT.alloc((size_t)m * sn * 4) || dO.alloc((size_t)w * m * 4)) return FLM_ERR_OOM;
     {   // the activation scales once more, group-major (k_rows_prologue writes both layouts on the prompt path)
         std::vector<float> t((size_t)w * sn);
@@ -105,10 +105,9 @@ int flm_op_matmul_q(int qt, float* out, const void* W, const float* sW, const vo
     const char* gv = getenv("FLM_OP_GEMM");                     // tests: 0 .. 3 = launch_gemm's use_mfma, "gemv" = a GEMV per batch row
     if (w >= 16 && !(gv && !strcmp(gv, "gemv"))) {
         // the batched path the prompt takes (quant::matmul with w > 1, quant_operators.cpp:252-284): one tile kernel
-        if (w4) { if (dW8.alloc((size_t)m * n)) return FLM_ERR_OOM; int r = unpack_w4(nullptr, 0, dW8.p, dW.p, wbytes); if (r) return r; }
-        GemmArgs g{w4 ? dW8.p : dW.p, dsW.as<float>(), dX.p, dsX.as<float>(), dO.as<float>(), m, n, m, w, dsXT.as<float>(), dsWT.as<float>()};
+        GemmArgs g{dW.p, dsW.as<float>(), dX.p, dsX.as<float>(), dO.as<float>(), m, n, m, w, dsXT.as<float>(), dsWT.as<float>()};
         const int um = gv ? atoi(gv) : 1;
-        int r = launch_gemm_store(nullptr, 0, w4 ? FLM_QT_INT8 : qt, g, um);
+        int r = launch_gemm_store(nullptr, 0, qt, g, um);
         if (r) return r;
     } else {
         for (int b = 0; b < w; ++b) {

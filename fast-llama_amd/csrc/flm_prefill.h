@@ -691,6 +691,153 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) k_
     skinny_epilogue<EPI, NB>(a, acc, r0 + l15, lane);
 }
 
+// ------------------------------------------------------------------------------------------
+// The W4A8 GEMM tiles: k_gemm_q8_mfma's contract (GemmArgs, the tile shapes <2, 2, 1> and <4, 2, 2>, tokens = A of v_mfma_i32_32x32x32_i8 so that a lane owns ONE weight
+// row, tiles dealt to the XCDs in contiguous runs, both sides' scales from the group-major copies, the step acc = fma(sw * sx, float(d), acc) with groups ascending,
+// gemm_epilogue as it is) on a matrix in the DEVICE nibble layout (flm_gemv4.h) -- a.W is [rows][n / 2] packed bytes (SWIGLU: W3 behind W1); nothing is unpacked to
+// memory and nothing is expanded on the way into LDS.  The stored value is, bit for bit, what k_gemm_q8_mfma stores for the sign-extended nibbles.
+//   * staging: a stage is still kGPS = 2 groups = 64 PACKED bytes of a weight row: four 16-byte pieces per row, parked as they come -- half the global bytes, half the
+//     LDS stores and half the LDS bytes per weight row of the int8 kernel, whose bound is the LDS.  X is staged as there (128 bytes per token and stage).
+//     LDS row stride of the packed strip: 80 bytes = 20 banks; the eight lanes one cycle of a 16-byte read serves are eight consecutive rows, starting at banks 20 r mod
+//     32 = {0, 20, 8, 28, 16, 4, 24, 12}: four banks each, all 32 once (GemmTile::LS = 144 does the same for 128-byte rows).  The STORES need the loader's row order
+//     below.  SQ_LDS_BANK_CONFLICT is 0 with both.
+//   * operand: lane (l31, h) reads ONE 16-byte piece per fragment and group: packed bytes 16 h .. 16 h + 15 of group g of its row = weights 32 h .. 32 h + 31.  Its words
+//     w0 .. w3 expand as in k_gemm_q4_skinny, M = 0x0F0F0F0F: {w0 & M, (w0 >> 4) & M, w1 & M, (w1 >> 4) & M} = weights 32 h .. 32 h + 15 in column order is the B operand
+//     of the group's first MFMA, the same of w2, w3 (weights 32 h + 16 .. 32 h + 31) of the second: 12 VALU per fragment and group, one ds_read_b128 where the int8
+//     kernel issues two.  The A side follows (integer group sums are order-free as long as A and B agree): lane half h takes activation bytes 32 h .. 32 h + 15 for the
+//     first MFMA and 32 h + 16 .. 32 h + 31 for the second (int8: 16 h .. and 32 + 16 h ..).
+//   * the offset leaves once per group, exactly: sum (u - 8) x = sum u x - 8 sum x.  Two MFMAs per group and wave with B = 0x01010101 give sum x of every token in the C
+//     layout (every column alike); times -8 (16 VALU, shared by the NB fragments) it is the accumulator INPUT of the fragment MFMAs, whose result is the exact int32 dot
+//     of the sign-extended nibbles (|sum u x| <= 64 * 15 * 127).  No table of sum x, nothing folded into the scales (sw * sx stays the int8 kernel's product).
+//   * zeros: a zero WORD is now eight weights of -8, not 0.  (1) Rows past the matrix: weight loads out of range (d = -8 sum x) and scale loads too -- sw = 0,
+//     fma(0 * sx, float(d), acc) = acc -- and gemm_epilogue masks them at the store.  (2) Token columns >= B: zero ACTIVATIONS, so sum x = 0 and every product is 0:
+//     d = 0 whatever the weight words are.  (3) The half stage behind an odd group count (and the stages past the end): whatever bytes lie there, the scale load is
+//     refused (sw = 0), as in the int8 kernel.
+//   num_records of the weight descriptor is in BYTES of the packed matrix (SWIGLU: of both halves); n_peer is 0 (INT4 is one GPU's).
+// ------------------------------------------------------------------------------------------
+template <int WT, int WR, int NB>
+struct GemmTile4 {
+    static constexpr int TT = 32 * WT, TR = 32 * NB * WR, NT = 64 * WT * WR;
+    static constexpr int SBX = kGPS * kGroup, SBW = SBX / 2;      // bytes of a stage in one token's row | in one packed weight row
+    static constexpr int LSX = SBX + 16, LSW = SBW + 16;          // LDS row strides (conflict-free 16-byte reads of 16 consecutive rows, see above)
+    static constexpr int kOffX = TR * LSW, kOffS = kOffX + TT * LSX, kBuf = kOffS + kGPS * (TR + TT) * 4;   // packed W rows | X rows | scales [W g0][W g1][X g0][X g1]
+    static constexpr int NPW = TR * 4 / NT, NPX = TT * 8 / NT;    // 16-byte pieces per thread and stage
+    static constexpr int kLds = 2 * kBuf;
+    static_assert(kGPS == 2 && NT == kGPS * (TR + TT) && TR % 64 == 0 && TT % 64 == 0, "one scale per thread and stage, wave-uniform (matrix, group)");
+    static_assert(TR * 4 % NT == 0 && TT * 8 % NT == 0, "whole pieces per thread");
+    static_assert(kLds <= 64 * 1024, "both shapes fit the default dynamic-LDS limit (128 x 128: 60 KiB, two workgroups per CU; 64 x 64: 30 KiB, four)");
+};
+template <int EPI, int WT, int WR, int NB>
+__global__ void __launch_bounds__(64 * WT * WR, 4) k_gemm_q4_mfma(const GemmArgs a) {
+    using G = GemmTile4<WT, WR, NB>;
+    constexpr bool TWO = EPI == EPI_SWIGLU;
+    static_assert(!TWO || NB == 2, "gate and up are the two B fragments of a wave");
+    constexpr int TRH = TWO ? G::TR / 2 : G::TR;              // rows of a.rows one tile advances
+    constexpr int SBX = G::SBX, SBW = G::SBW, LSX = G::LSX, LSW = G::LSW, TT = G::TT, TR = G::TR, NT = G::NT, kOffX = G::kOffX, kOffS = G::kOffS, kBuf = G::kBuf, NPW = G::NPW, NPX = G::NPX;
+    constexpr int kWGroup = kGroup / 2;                       // packed bytes of a quant group
+    extern __shared__ __attribute__((aligned(16))) char lds[]; char* const sm = lds;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int ntt = (a.B + TT - 1) / TT;
+    const int nb = gridDim.x, per = nb >> 3, rem = nb & 7, xcd = blockIdx.x & 7;              // tiles dealt to the XCDs in contiguous runs, token tile fastest (k_gemm_q8_mfma)
+    const int tile = xcd * per + (xcd < rem ? xcd : rem) + (blockIdx.x >> 3);
+    const int r0 = (tile / ntt) * TRH, b0 = (tile % ntt) * TT;
+    const int sn = a.n / kGroup, nst = (sn + kGPS - 1) / kGPS;
+    const unsigned xbytes = (unsigned)a.n, wbytes = (unsigned)a.n / 2;      // a row of activations, a row of packed weights
+    constexpr unsigned kOOB = 0x80000000u, kNib = 0x0F0F0F0Fu;
+    const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.W), 0, (int)((TWO ? 2u : 1u) * (unsigned)a.rows * wbytes), 0x00020000);
+    // tile row -> row of W (or -1): SWIGLU tiles hold TRH rows of W1, then the same TRH rows of W3
+    auto wrow = [&](int tr) -> int { const int within = TWO ? tr % TRH : tr, r = r0 + within; return r < a.rows ? (TWO ? (tr / TRH) * a.rows + r : r) : -1; };
+    const __amdgpu_buffer_rsrc_t rX = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.Xq), 0, (int)((unsigned)a.B * xbytes), 0x00020000);
+    // loaders: weight piece k of a thread = 16 packed bytes at (row pwrow + (NT / 4) k, chunk tid & 3); activation piece k = 16 bytes at (token (tid >> 3) + (NT / 8) k,
+    // chunk tid & 7); rows outside a matrix read as zero
+    // The eight lanes one cycle of a 16-byte LDS store serves write two weight rows' four pieces: 2 x 64 bytes must be all 32 banks once, and rows r, r + 1 at stride 80
+    // share four (measured: SQ_LDS_BANK_CONFLICT at 9 % of the active cycles, every one from this store).  Rows r and r + 4 lie 320 = 64 mod 128 bytes apart: inside every
+    // eight rows, lane pairs take the rows in the order 0 4 1 5 2 6 3 7.
+    const int pwq = tid >> 2, pwrow = (pwq & ~7) | ((pwq & 1) << 2) | ((pwq >> 1) & 3), pwch = tid & 3, pxrow = tid >> 3, pxch = tid & 7;
+    unsigned woff[NPW], xoff[NPX];
+#pragma unroll
+    for (int k = 0; k < NPW; ++k) { const int r = wrow(pwrow + (NT / 4) * k); woff[k] = r >= 0 ? (unsigned)r * wbytes + pwch * 16 : kOOB; }
+#pragma unroll
+    for (int k = 0; k < NPX; ++k) xoff[k] = (b0 + pxrow + (NT / 8) * k < a.B) ? (unsigned)(b0 + pxrow + (NT / 8) * k) * xbytes + pxch * 16 : kOOB;
+    const unsigned pwoff = (unsigned)(pwrow * LSW + pwch * 16), pxoff = (unsigned)(kOffX + pxrow * LSX + pxch * 16);
+    // scales: one per thread and stage from the group-major copies, LDS slots [W g0 (TR)][W g1 (TR)][X g0 (TT)][X g1 (TT)], a group past the end gets scale zero (k_gemm_q8_mfma)
+    const int s_slot = wave * 64;
+    const bool s_x = s_slot >= kGPS * TR;
+    const int s_gi = s_x ? (s_slot - kGPS * TR) / TT : s_slot / TR;
+    const int s_row = s_x ? (b0 + (s_slot - kGPS * TR) % TT + lane < a.B ? b0 + (s_slot - kGPS * TR) % TT + lane : -1) : wrow(s_slot % TR + lane);
+    const unsigned s_rows = s_x ? (unsigned)a.B : (TWO ? 2u : 1u) * (unsigned)a.rows;
+    const __amdgpu_buffer_rsrc_t rS = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(s_x ? a.XsT : a.sWT), 0, (int)(s_rows * sn * 4), 0x00020000);
+    unsigned soff = s_row >= 0 ? ((unsigned)s_gi * s_rows + s_row) * 4 : kOOB;
+    const unsigned sstep = kGPS * s_rows * 4;
+    const unsigned spoff = (unsigned)(kOffS + tid * 4);
+    v4u wr[NPW], xr[NPX]; unsigned sr;
+    auto fetch = [&](int st) {                    // stage st -> the register slot (stages past the end: the offsets have run past the rows; never consumed with a non-zero scale)
+#pragma unroll
+        for (int k = 0; k < NPW; ++k) { wr[k] = __builtin_amdgcn_raw_buffer_load_b128(rW, (int)woff[k], 0, 0); woff[k] += SBW; }
+#pragma unroll
+        for (int k = 0; k < NPX; ++k) { xr[k] = __builtin_amdgcn_raw_buffer_load_b128(rX, (int)xoff[k], 0, 0); xoff[k] += SBX; }
+        sr = __builtin_amdgcn_raw_buffer_load_b32(rS, (int)(st * kGPS + s_gi < sn ? soff : kOOB), 0, 0); soff += sstep;
+    };
+    auto park = [&](int buf) {
+        char* base = sm + buf * kBuf;
+#pragma unroll
+        for (int k = 0; k < NPW; ++k) *reinterpret_cast<v4u*>(base + pwoff + k * (NT / 4) * LSW) = wr[k];
+#pragma unroll
+        for (int k = 0; k < NPX; ++k) *reinterpret_cast<v4u*>(base + pxoff + k * (NT / 8) * LSX) = xr[k];
+        *reinterpret_cast<unsigned*>(base + spoff) = sr;
+    };
+    // this wave's 32 tokens x (NB x 32) weight rows (SWIGLU: fragment j = rows wr0 .. wr0 + 31 of half j; otherwise fragment j = tile rows wr0 + 32 j ..)
+    const int wt0 = (wave % WT) * 32, wr0 = (wave / WT) * 32 * (TWO ? 1 : NB), l31 = lane & 31, h = lane >> 5;
+    constexpr int FS = TWO ? TRH : 32;                            // tile rows between a wave's fragments
+    const unsigned offA = (unsigned)(kOffX + (wt0 + l31) * LSX + h * 32), offB = (unsigned)((wr0 + l31) * LSW + h * 16);
+    const unsigned offsw = (unsigned)(kOffS + (wr0 + l31) * 4), offsx = (unsigned)(kOffS + (kGPS * TR + wt0 + 4 * h) * 4);
+    float acc[NB][16];
+#pragma unroll
+    for (int j = 0; j < NB; ++j)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[j][i] = 0.f;
+    const v4i ones = {0x01010101, 0x01010101, 0x01010101, 0x01010101};
+    fetch(0); park(0); fetch(1);
+    __syncthreads();
+    for (int st = 0; st < nst; ++st) {
+        const char* base = sm + (st & 1) * kBuf;
+#pragma unroll
+        for (int gi = 0; gi < kGPS; ++gi) {
+            const v4i a0 = *reinterpret_cast<const v4i*>(base + offA + gi * kGroup), a1 = *reinterpret_cast<const v4i*>(base + offA + gi * kGroup + 16);
+            const v16i z = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+            v16i off = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, ones, z, 0, 0, 0);      // sum x of the wave's tokens in the C layout, in every column
+            off = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, ones, off, 0, 0, 0);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) off[i] = __mul24(off[i], -8);                  // (|sum x| <= 64 * 127: 14 bits)
+            v16i d[NB];
+#pragma unroll
+            for (int j = 0; j < NB; ++j) {
+                const v4u w = *reinterpret_cast<const v4u*>(base + offB + j * FS * LSW + gi * kWGroup);
+                const v4u u0 = {w[0] & kNib, (w[0] >> 4) & kNib, w[1] & kNib, (w[1] >> 4) & kNib}, u1 = {w[2] & kNib, (w[2] >> 4) & kNib, w[3] & kNib, (w[3] >> 4) & kNib};
+                d[j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a0, __builtin_bit_cast(v4i, u0), off, 0, 0, 0);
+                d[j] = __builtin_amdgcn_mfma_i32_32x32x32_i8(a1, __builtin_bit_cast(v4i, u1), d[j], 0, 0, 0);
+            }
+            float4 sx[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) sx[q] = *reinterpret_cast<const float4*>(base + offsx + gi * TT * 4 + q * 32);
+#pragma unroll
+            for (int j = 0; j < NB; ++j) {
+                const float sw = *reinterpret_cast<const float*>(base + offsw + (gi * TR + j * FS) * 4);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    acc[j][4 * q + 0] = __fmaf_rn(__fmul_rn(sw, sx[q].x), (float)d[j][4 * q + 0], acc[j][4 * q + 0]);   // quant_operators.cpp:274
+                    acc[j][4 * q + 1] = __fmaf_rn(__fmul_rn(sw, sx[q].y), (float)d[j][4 * q + 1], acc[j][4 * q + 1]);
+                    acc[j][4 * q + 2] = __fmaf_rn(__fmul_rn(sw, sx[q].z), (float)d[j][4 * q + 2], acc[j][4 * q + 2]);
+                    acc[j][4 * q + 3] = __fmaf_rn(__fmul_rn(sw, sx[q].w), (float)d[j][4 * q + 3], acc[j][4 * q + 3]);
+                }
+            }
+        }
+        park((st & 1) ^ 1); fetch(st + 2);        // unconditional: a stage past the end is parked and never read with a non-zero scale
+        __syncthreads();
+    }
+    gemm_epilogue<EPI, NB>(a, acc, r0 + wr0 + l31, b0 + wt0, lane);
+}
+
 // qkv[b] = [q ; k ; v] (dim each) of token b at position pos0 + b: RoPE on q and k (rope_v2 pairs), q -> qout[b], k / v -> cache rows
 inline __global__ void k_rope_kv_rows(const float* qkv, float* qout, float* kcache, float* vcache, const float* rope_cos, const float* rope_sin,
                                int dim, int hs, int max_seq, int pos0) {

@@ -94,12 +94,33 @@ int launch_gemm_skinny_w4(flm_ctx* c, hipStream_t st, const GemmArgs& g, int for
     HIPC(c, hipGetLastError());
     return FLM_OK;
 }
-// which GEMM family a pass's weight pointers belong to: pass_weights / pass_classifier decide it together with the pointers
-enum GemmKind { GEMM_TILES = 0, GEMM_SKINNY8, GEMM_SKINNY4 };
-// one GEMM of the batched path: the tiles, or -- the verify pass under "spec_gemm" 1 -- the skinny kernel of the weights' type (int8 bytes | packed nibbles)
+// The W4A8 GEMM tiles (flm_prefill.h k_gemm_q4_mfma): launch_gemm's tile-shape rule and use_mfma (1 by size, 2 / 0 always 64 x 64, 3 always 128 x 128; SwiGLU always 128 x
+// 128 on [W1; W3]) on a PACKED matrix in the device nibble layout -- g.W is [rows][n / 2] bytes and the 2 GiB bound of the buffer descriptor is on those.  Both shapes stage
+// less than the default dynamic-LDS limit (GemmTile4::kLds, asserted there), so no kernel attribute is raised.  One GPU: INT4 is refused across ranks at create.
+template <int EPI>
+int launch_gemm_w4(flm_ctx* c, hipStream_t st, const GemmArgs& g, int use_mfma) {
+    using Big = GemmTile4<4, 2, 2>; using Small = GemmTile4<2, 2, 1>;
+    if (g.B < 1 || g.rows < 1 || g.n < kGroup || g.n % kGroup || g.n_peer) return fail(c, FLM_ERR_INVALID, "w4 gemm: whole quant groups, one GPU");
+    if ((double)g.rows * (g.n / 2) * (EPI == EPI_SWIGLU ? 2 : 1) >= 2147483648.0 || (double)g.B * g.n >= 2147483648.0) return fail(c, FLM_ERR_UNSUPPORTED, "w4 gemm: packed matrix or activations of 2 GiB or more");
+    if (use_mfma == 0) use_mfma = 2;
+    if constexpr (EPI == EPI_SWIGLU) {   // g.rows = hidden: a tile = 64 rows of W1 and of W3
+        const int tiles = ((g.rows + Big::TR / 2 - 1) / (Big::TR / 2)) * ((g.B + Big::TT - 1) / Big::TT);
+        hipLaunchKernelGGL((k_gemm_q4_mfma<EPI_SWIGLU, 4, 2, 2>), dim3(tiles), dim3(Big::NT), Big::kLds, st, g);
+    } else {
+        const int tiles = ((g.rows + Small::TR - 1) / Small::TR) * ((g.B + Small::TT - 1) / Small::TT), tiles128 = ((g.rows + Big::TR - 1) / Big::TR) * ((g.B + Big::TT - 1) / Big::TT);
+        if (use_mfma == 3 || (use_mfma == 1 && tiles128 >= 256)) hipLaunchKernelGGL((k_gemm_q4_mfma<EPI, 4, 2, 2>), dim3(tiles128), dim3(Big::NT), Big::kLds, st, g);
+        else hipLaunchKernelGGL((k_gemm_q4_mfma<EPI, 2, 2, 1>), dim3(tiles), dim3(Small::NT), Small::kLds, st, g);
+    }
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
+// which GEMM family a pass's weight pointers belong to: pass_weights / pass_classifier decide it together with the pointers (flm_query "pass_gemm" reports the values)
+enum GemmKind { GEMM_TILES = 0, GEMM_SKINNY8, GEMM_SKINNY4, GEMM_TILES4 };
+// one GEMM of the batched path: the tiles, or -- the verify pass under "spec_gemm" 1 -- the skinny kernel, each of the weights' type (int8 / int16 bytes | packed nibbles)
 template <int QT, int EPI>
 int launch_gemm_any(flm_ctx* c, hipStream_t st, const GemmArgs& g, int use_mfma, GemmKind kind) {
     if constexpr (QT == QT_INT8) {
+        if (kind == GEMM_TILES4) return launch_gemm_w4<EPI>(c, st, g, use_mfma);
         if (kind == GEMM_SKINNY4) return launch_gemm_skinny_w4<EPI>(c, st, g);
         if (kind == GEMM_SKINNY8) return launch_gemm_skinny<EPI>(c, st, g);
     }
@@ -253,33 +274,27 @@ int launch_rope_kv_segs(flm_ctx* c, hipStream_t st, const float* qkv, float* qou
 // tree (flm_verify_tree_greedy; null: every launch is the one made without it): the B rows are a tree of candidates at `pos` (flm_tree.h) -- the fan's route with
 // k_rope_kv_tree and k_attn_tree; tree_dev (the lookup loop under "spec_branches"): the rows' parents, depths and masks are the ones k_spec_draft_tree left in device
 // memory, `tree` carries pos and n only
-// W4A8 (quant_type INT4): the batched kernels run as QT_INT8.  A `skinny` pass (<= 16 rows under "spec_gemm" 1, one GPU) reads the PACKED matrices where they lie, through
-// k_gemm_q4_skinny: nothing is unpacked, 0.5 bytes per weight and pass.  Every other pass runs the tiles on an int8 copy of the weights it is about to read -- k_unpack_w4
-// on the pass's stream (inside the capture where the pass is captured) in front of a layer's GEMMs / the classifier's, into the context's scratch: one more read of the
-// packed weights and a write + read of their int8 copy per layer and pass, and for the classifier per CHUNK of rows its stage runs -- a nibble-fragment loader for the
-// 64 x 64 / 128 x 128 tiles is the follow-up.  The scales and their group-major copies are the packed matrix's own on both routes; both are bit-identical by construction
-// (the int8 arithmetic on the sign-extended nibbles).
+// W4A8 (quant_type INT4): the batched kernels run as QT_INT8 and read the PACKED matrices where they lie -- nothing is unpacked, 0.5 bytes per weight and pass.  A `skinny`
+// pass (<= 16 rows under "spec_gemm" 1) goes through k_gemm_q4_skinny, every other pass through the nibble-fed tiles k_gemm_q4_mfma.  The scales and their group-major
+// copies are the packed matrix's own; both families are bit-identical to the int8 arithmetic on the sign-extended nibbles.  (The int8 scratch copy that k_unpack_w4 used to
+// refill in front of every layer's GEMMs and every classifier chunk is gone: DESIGN.md section 5o has the measurement that retired it.)
 static inline bool tiles_int8(const flm_ctx* c) { return c->d.quant_type != FLM_QT_INT16; }
+static inline GemmKind pass_kind(const flm_ctx* c, bool skinny) {
+    const bool w4 = c->d.quant_type == FLM_QT_INT4;
+    return skinny ? (w4 ? GEMM_SKINNY4 : GEMM_SKINNY8) : (w4 ? GEMM_TILES4 : GEMM_TILES);
+}
 // the ONE place a pass picks layer l's weight pointers and the GEMM family that reads them
-static int pass_weights(flm_ctx* c, hipStream_t st, int l, bool skinny, LayerW& w, GemmKind& kind) {
+static int pass_weights(flm_ctx* c, int l, bool skinny, LayerW& w, GemmKind& kind) {
     w = c->layers[l];
-    kind = !skinny ? GEMM_TILES : c->d.quant_type == FLM_QT_INT4 ? GEMM_SKINNY4 : GEMM_SKINNY8;
-    if (c->d.quant_type != FLM_QT_INT4 || kind == GEMM_SKINNY4) return FLM_OK;
-    char* p = c->w4_scratch;
-    for (QMat* m : {&w.qkv, &w.o, &w.w13, &w.w2}) {
-        const size_t n = (size_t)m->rows * m->cols;
-        const int r = unpack_w4(c, st, p, m->q, n / 2); if (r) return r;
-        m->q = p; p += n;
-    }
+    kind = pass_kind(c, skinny);
+    c->pass_gemm = kind;
     return FLM_OK;
 }
 // ... and the classifier's
-static int pass_classifier(flm_ctx* c, hipStream_t st, bool skinny, const void** q, GemmKind& kind) {
+static int pass_classifier(flm_ctx* c, bool skinny, const void** q, GemmKind& kind) {
     *q = c->cls.q;
-    kind = !skinny ? GEMM_TILES : c->d.quant_type == FLM_QT_INT4 ? GEMM_SKINNY4 : GEMM_SKINNY8;
-    if (c->d.quant_type != FLM_QT_INT4 || kind == GEMM_SKINNY4) return FLM_OK;
-    *q = c->w4_scratch;
-    return unpack_w4(c, st, c->w4_scratch, c->cls.q, (size_t)c->cls.rows * c->cls.cols / 2);
+    kind = pass_kind(c, skinny);
+    return FLM_OK;
 }
 template <int QT>
 int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req = false, const FanDesc* fan = nullptr, int row0 = 0, const SlotDesc* slots = nullptr, const SegDesc* segs = nullptr, const PrefixDesc* pfx = nullptr, const TreeDesc* tree = nullptr, const TreeDesc* tree_dev = nullptr) {
@@ -314,7 +329,7 @@ int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req
     hipLaunchKernelGGL(k_embed_rows, dim3(B), dim3(256), 0, st, c->pf_x, (const void*)c->emb, (const float*)c->emb_s, c->emb_qt, dim, (const int*)c->prompt_dev);
     HIPC(c, hipGetLastError());
     for (int l = 0; l < L; ++l) {
-        LayerW w; GemmKind kind; r = pass_weights(c, st, l, skinny, w, kind); if (r) return r;
+        LayerW w; GemmKind kind; r = pass_weights(c, l, skinny, w, kind); if (r) return r;
         float* const kc = c->kcache + (size_t)l * kv_layer + (size_t)row0 * hs;    // (row0: the slot's origin; the stride between two heads' rows stays kv_rows)
         float* const vc = c->vcache + (size_t)l * kv_layer + (size_t)row0 * hs;
         // x2 = rmsnorm(x1); qx = quantize(x2); q,k,v = W x; RoPE; cache rows   (transformer.cpp:132-135, 386-395, 431-439)
@@ -409,7 +424,7 @@ int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req
             r = launch_gemm_any<QT, EPI_SWIGLU>(c, st, g13, c->use_mfma, kind); if (r) return r;
         } else {
             GemmArgs g13{w.w13.q, w.w13.s, c->pf_xq, c->pf_xs, c->pf_gu, 2 * hidL, dim, 2 * hidL, B, c->pf_xst, w.w13.st};
-            r = launch_gemm<QT, EPI_STORE>(c, st, g13, c->use_mfma); if (r) return r;
+            r = launch_gemm_any<QT, EPI_STORE>(c, st, g13, c->use_mfma, kind); if (r) return r;
             SwigluPeers sp{}; { GemmArgs t{}; peers(t, c->pf_hd + col_h); sp.n = t.n_peer; for (int i = 0; i < t.n_peer; ++i) sp.p[i] = t.out_peer[i]; }
             hipLaunchKernelGGL(k_swiglu_rows, dim3(B), dim3(256), 0, st, c->pf_hd + col_h, (const float*)c->pf_gu, hidL, hid, sp);
             HIPC(c, hipGetLastError());
@@ -427,6 +442,7 @@ int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req
 }
 
 int launch_gemm_store(flm_ctx* c, hipStream_t st, int qt, const GemmArgs& g, int use_mfma) {
+    if (qt == FLM_QT_INT4) return launch_gemm_w4<EPI_STORE>(c, st, g, use_mfma);
     return qt == FLM_QT_INT8 ? launch_gemm<QT_INT8, EPI_STORE>(c, st, g, use_mfma) : launch_gemm<QT_INT16, EPI_STORE>(c, st, g, use_mfma);
 }
 int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers, bool skinny, const FanDesc* fan, int row0, const SlotDesc* slots_in, const SegDesc* segs_in, const PrefixDesc* pfx_in, const TreeDesc* tree, const TreeDesc* tree_dev) {
@@ -558,7 +574,7 @@ static int classify_rows_t(flm_ctx* c, int row0, int m, float* stage, bool skinn
     // logits = Wcls quantize(rmsnorm(x1))   (transformer.cpp:154-160)
     RowsArgs ra{c->pf_x + (size_t)row0 * dim, c->out_norm, c->pf_xq, c->pf_xs, dim, c->pf_xst};
     int r = launch_rows<QT, PRO_RMSNORM_QUANT>(c, st, ra, m); if (r) return r;
-    const void* wq = nullptr; GemmKind kind; r = pass_classifier(c, st, skinny && QT == QT_INT8 && m <= kSkinnyTokens, &wq, kind); if (r) return r;
+    const void* wq = nullptr; GemmKind kind; r = pass_classifier(c, skinny && QT == QT_INT8 && m <= kSkinnyTokens, &wq, kind); if (r) return r;
     GemmArgs g{wq, c->cls.s, c->pf_xq, c->pf_xs, stage, V, dim, V, m, c->pf_xst, c->cls.st};
     return launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, kind);
 }

@@ -51,8 +51,9 @@ extern "C" {
  *              scales fp32 [rows][cols / 64].  flm_upload_tensor(src_qtype 3) takes it with the LOGICAL cols, flm_op_matmul_q(3, ..) takes W in it, flm_op_quantize(3, ..) writes it
  *   quantizer  an fp32 linear tensor uploaded into an INT4 context, and flm_op_quantize(3, ..): r = max|x| / 7 (IEEE fp32 division), q = trunc(x / r); an all-zero group r = 0, q = 0
  *   launches   one kernel per phase under the token graph: no fused form exists for the type, the "fuse_*" options are accepted and change nothing (flm_query "token_path"
- *              reports none).  Prompts and every batched entry point run the INT8 kernels on an int8 copy of one layer's weights, unpacked in front of its GEMMs --
- *              but a pass of <= 16 rows under option "spec_gemm" 1, which reads the nibbles where they lie (the skinny W4A8 GEMM; flm_op_matmul_skinny(3, ..))
+ *              reports none).  Prompts and every batched entry point read the nibbles where they lie, nothing is unpacked: a pass of <= 16 rows under option "spec_gemm" 1
+ *              through the skinny W4A8 GEMM (flm_op_matmul_skinny(3, ..)), every other pass through the W4A8 64 x 64 / 128 x 128 tiles (flm_op_matmul_q(3, ..) with
+ *              w >= 16); flm_query "pass_gemm" names the family the last batched pass ran
  *   refused    world > 1 at flm_ctx_create (FLM_ERR_UNSUPPORTED); an upload whose src_qtype differs from the context's, either way, and src_qtype 3 for the embedding table
  *              (FLM_ERR_INVALID) */
 #define FLM_QT_INT4  3
@@ -204,7 +205,7 @@ int  flm_score_tokens(flm_ctx* ctx, const int32_t* tokens, int n, int pos,
  * argmax needs no LDS strip).  Nothing is allocated in the call; the m + 1 ids come back in one trip.
  * The weight pass: option "spec_gemm" 1 = int8 and int4 models run every GEMM of the batch through the skinny kernel (v_mfma_i32_16x16x64_i8, 16 tokens x 16 rows x one quant group per
  * instruction, weights from global memory straight into the operand registers, one wave per 16 or 32 rows so that every matrix of the 7B shape fills 256 CUs); 0 = the 64 x 64
- * tiles of the prompt path (int4: on the unpacked int8 copy; the skinny kernel reads the packed nibbles, an 8-byte load per lane and group).  int16 models always run the
+ * tiles of the prompt path (int4: both kernels read the packed nibbles -- the tiles a 16-byte LDS read per lane and group, the skinny kernel an 8-byte load).  int16 models always run the
  * hi / lo-plane tiles here: correct, not fast. */
 int  flm_verify_greedy(flm_ctx* ctx, int32_t first_token, const int32_t* drafts, int k, int pos,
                        int32_t* out_tokens /* [k + 1] */, int* n_out);
@@ -457,7 +458,9 @@ int  flm_fan_keep(flm_ctx* ctx, int seq);
  *   flm_batch_state of a filling slot answers n_out 0, reason 0; a negative budget answers FLM_ERR_INVALID; FLM_ERR_STATE / FLM_ERR_UNSUPPORTED as for step.
  *   flm_generate_batch under option "batch_rows" b >= 0: every request is admitted, then flm_batch_pass(b) until nobody runs or fills.  The results are the default's;
  *   the callbacks come in (pass, slot) order -- with a bounded budget a slot can deliver its token 1 before a later slot delivers its token 0.
- *   flm_query "batch_passes": the weight passes (joins, steps, passes) since the last flm_batch_open. */
+ *   flm_query "batch_passes": the weight passes (joins, steps, passes) since the last flm_batch_open.
+ *   flm_query "pass_gemm" (read-only): the kernel family of the layer GEMMs of the context's most recent batched pass of any entry point (prompt, score, verify, tree, fan,
+ *   join, step, pass; flm_prepare's self-check is one) -- 0 tiles on int8 / int16 bytes, 1 skinny int8, 2 skinny nibbles, 3 nibble tiles; -1 before the first. */
 #define FLM_BATCH_MAX 16
 typedef struct flm_batch_layout { int32_t n_slots; int32_t base[FLM_BATCH_MAX], rows[FLM_BATCH_MAX]; } flm_batch_layout;
 typedef struct flm_batch_req { const int32_t* prompt; int32_t n_prompt, max_tokens; float temperature, topp;
@@ -767,7 +770,8 @@ int  flm_query(flm_ctx* ctx, const char* key, int* value);
 /* quant::quantize (quant_operators.cpp:78-97) */
 int  flm_op_quantize(int qt, void* qx, float* qs, const float* x, size_t n, int gs);
 /* quant::matmul (quant_operators.cpp:571-591), same argument order: out[w][m].  w < 16: one GEMV per batch row (the decode
- * kernel); w >= 16: the tile kernels of the batched prompt path (int8 and int16 on the int8 matrix cores; FLM_OP_GEMM=1|2|3: the tile shape) */
+ * kernel); w >= 16: the tile kernels of the batched prompt path (int8 and int16 on the int8 matrix cores, int4 the nibble-fed tiles on the repacked matrix;
+ * FLM_OP_GEMM=1|2|3: the tile shape) */
 int  flm_op_matmul_q(int qt, float* out, const void* mat1, const float* scales1,
                      const void* mat2, const float* scales2, int m, int n, int w, int gs);
 /* the same product for 1 <= w <= 16 batch rows through the skinny kernels of the verify pass: FLM_QT_INT8 (k_gemm_q8_skinny) and FLM_QT_INT4

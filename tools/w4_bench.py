@@ -5,7 +5,12 @@ python tools/w4_bench.py [reps] [layers]   -- prints the tables and one JSON lin
 
 python tools/w4_bench.py --verify [reps] [layers]   -- the passes of up to 16 rows instead: the time of one flm_verify_greedy pass at B = 5, 8 and 16 rows (position 20) and
 the time per step of flm_generate_batch with 16 slots, for an INT4 context under "spec_gemm" 1 and 0 and an INT8 context under "spec_gemm" 1, the three alternating,
-medians of `reps` with min .. max.  FLM_GPU_LIB picks the library (capi.py): under the build of the commit before k_gemm_q4_skinny the first row is unpack + int8 skinny."""
+medians of `reps` with min .. max.  FLM_GPU_LIB picks the library (capi.py): under the build of the commit before k_gemm_q4_skinny the first row is unpack + int8 skinny.
+
+python tools/w4_bench.py --prefill [reps] [layers]   -- the passes of more than 16 rows (and the tile route of a 16-row one): flm_forward of a 17-, 64-, 130- and 512-token
+prompt, flm_score_tokens of 512 tokens with "score_rows" 128 (the classifier in 4 chunks) and a verify pass at B = 16 under "spec_gemm" 0 on an INT4 context, and the
+512-token prompt on an INT8 context; medians of `reps` runs with min .. max, a run = the mean over 20 calls.  Under the build of the commit before k_gemm_q4_mfma the INT4
+rows are unpack + int8 tiles."""
 import json
 import os
 import statistics
@@ -17,8 +22,8 @@ import numpy as np
 import __graft_entry__ as g; g.load_package()
 from fast_llama_amd import capi, synth, flmfile as ff
 
-verify = "--verify" in sys.argv
-args = [a for a in sys.argv[1:] if a != "--verify"]
+verify, prefill = "--verify" in sys.argv, "--prefill" in sys.argv
+args = [a for a in sys.argv[1:] if not a.startswith("--")]
 reps = int(args[0]) if len(args) > 0 else 5
 layers = int(args[1]) if len(args) > 1 else None
 PEAK, POS, STEPS = 8e12, 20, 128
@@ -75,8 +80,38 @@ def verify_bench():
     print(json.dumps(out))
 
 
-if verify:
-    verify_bench()
+def prefill_bench():
+    """every timed window ends behind a device synchronise: forward, score and verify_greedy return values that are on the host"""
+    CALLS = 20
+    int4, int8 = context(capi.QT_INT4, False), context(ff.QT_INT8, False)
+    int4.set_option("spec_gemm", 0); int4.set_option("score_rows", 128)
+    toks = (np.arange(512, dtype=np.int32) * 7 + 1) % 1000
+    drafts = (np.arange(15, dtype=np.int32) * 13 + 5) % 1000
+
+    def verify16():
+        int4.verify_greedy(int(toks[POS]), drafts, POS)
+    cases = [(f"forward {n} / int4", (lambda n=n: int4.forward(toks[:n], 0))) for n in (17, 64, 130, 512)]
+    cases += [("score 512, 4 chunks / int4", lambda: int4.score(toks, 0)), ("verify B=16 spec_gemm 0 / int4", verify16), ("forward 512 / int8", lambda: int8.forward(toks, 0))]
+    times = {c: [] for c, _ in cases}
+    for r in range(reps + 1):                               # the first round warms every case
+        for c, call in cases:
+            if c.startswith("verify"):
+                int4.reset_kv(); int4.forward(toks[:POS], 0)
+            t0 = time.perf_counter()
+            for _ in range(CALLS):
+                call()
+            times[c].append((time.perf_counter() - t0) / CALLS)
+    out = {"reps": reps, "layers": int4.desc.n_layers, "lib": os.environ.get("FLM_GPU_LIB", "default"), "us": {}}
+    print(f"{'case':32s} {'median us':>10s} {'min':>9s} {'max':>9s}")
+    for c, _ in cases:
+        t = [x * 1e6 for x in times[c][1:]]
+        out["us"][c] = [round(statistics.median(t), 1), round(min(t), 1), round(max(t), 1)]
+        print(f"{c:32s} {statistics.median(t):10.1f} {min(t):9.1f} {max(t):9.1f}")
+    print(json.dumps(out))
+
+
+if verify or prefill:
+    verify_bench() if verify else prefill_bench()
     sys.exit(0)
 runs = {"int4": context(capi.QT_INT4, False), "int8 per phase": context(ff.QT_INT8, True), "int8 default": context(ff.QT_INT8, False)}
 res = {"reps": reps, "layers": runs["int4"].desc.n_layers, "kernels": {}, "tokens_per_s": {}}
