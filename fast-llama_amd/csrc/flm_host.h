@@ -193,7 +193,7 @@ struct flm_ctx {
     // ids [16] (first maxima or draws) and the step's result block (the accepted ids and the sampler's state behind them, one trip), device memory since create; which GEMM
     // the verify pass runs; the last call's figures ("spec_steps" / "spec_accepted")
     int* spec_hist = nullptr; int* spec_arg = nullptr; flm::SpecOut* spec_res = nullptr;
-    int spec_gemm = 0;                                 // option "spec_gemm": 1 = the verify pass's GEMMs through k_gemm_q8_skinny (INT4 contexts: k_gemm_q4_skinny on the packed weights) (B <= 16), 0 (default until both forms have been timed: DESIGN.md section 5e) = the 64 x 64 tiles; the new entry points only
+    int spec_gemm = 0;                                 // option "spec_gemm": 1 = the verify pass's GEMMs through k_gemm_q8_skinny (INT4 contexts: k_gemm_q4_skinny on the packed weights; INT16 contexts: k_gemm_q16_skinny) (B <= 16), 0 (default until both forms have been timed: DESIGN.md section 5e) = the 64 x 64 tiles; the new entry points only
     int spec_steps = 0, spec_accepted = 0;
     int spec_branches = 1;                             // option "spec_branches": B > 1 = the plain greedy lookup loop drafts a TREE from the B most recent distinct history matches (flm_tree.h); 1: the chain, today's launches
     // the model-based drafter (include/flm_gpu.h flm_draft_set / flm_generate_draft; flm_calls.hip generate_lookup_impl): the paired draft context (not owned; null: none),
@@ -479,7 +479,7 @@ int feed(flm_ctx* c, const int32_t* tokens, int n, int pos, TokenForm last);
 int d2h(flm_ctx* c, void* dst, const void* src_dev, size_t bytes);
 float* score_stage(const flm_ctx* c, int* chunk);
 constexpr int kPrefillMin = 4;
-int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers = false, bool skinny = false, const flm::FanDesc* fan = nullptr, int row0 = 0, const flm::SlotDesc* slots = nullptr, const flm::SegDesc* segs = nullptr, const flm::PrefixDesc* pfx = nullptr, const flm::TreeDesc* tree = nullptr, const flm::TreeDesc* tree_dev = nullptr);      // (flm_prompt.hip; by the model's quant type.  tree: the rows are a tree of candidates -- flm_verify_tree_greedy, flm_tree.h;  all_layers: the last layer is completed too -- flm_score_tokens needs every row's final residual; skinny: int8 and B <= 16: every GEMM through k_gemm_q8_skinny -- the verify pass under "spec_gemm" 1; fan: the rows are a fan step's -- flm_generate_n; row0: the batch is a prompt entering the cache slot that starts at physical row row0 -- flm_batch_join; slots: the rows are a batch step's -- flm_batch_step; segs: a ragged pass -- flm_batch_pass: rows [0, n_step) are a step's (slots, where n_step > 0), the rest prompt segments; pfx, S > 0: the slots lie behind S shared rows -- flm_batch_open_prefix: pos / pos0 count them, base stays physical, and the attention is flm_prefix.h's; null or S == 0: every launch is the one made without it)
+int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers = false, bool skinny = false, const flm::FanDesc* fan = nullptr, int row0 = 0, const flm::SlotDesc* slots = nullptr, const flm::SegDesc* segs = nullptr, const flm::PrefixDesc* pfx = nullptr, const flm::TreeDesc* tree = nullptr, const flm::TreeDesc* tree_dev = nullptr);      // (flm_prompt.hip; by the model's quant type.  tree: the rows are a tree of candidates -- flm_verify_tree_greedy, flm_tree.h;  all_layers: the last layer is completed too -- flm_score_tokens needs every row's final residual; skinny: B <= 16, one GPU: every GEMM through the weight type's skinny kernel (k_gemm_q8_skinny / k_gemm_q4_skinny / k_gemm_q16_skinny) -- the verify pass under "spec_gemm" 1; fan: the rows are a fan step's -- flm_generate_n; row0: the batch is a prompt entering the cache slot that starts at physical row row0 -- flm_batch_join; slots: the rows are a batch step's -- flm_batch_step; segs: a ragged pass -- flm_batch_pass: rows [0, n_step) are a step's (slots, where n_step > 0), the rest prompt segments; pfx, S > 0: the slots lie behind S shared rows -- flm_batch_open_prefix: pos / pos0 count them, base stays physical, and the attention is flm_prefix.h's; null or S == 0: every launch is the one made without it)
 // a fan step's pieces (flm_prompt.hip; kernels: flm_fan.h).  fan_classify: rows [row0, row0 + m) through score_classify's prologue and GEMM into `stage`, then k_sample_fan
 // into fan_drawn / fan_after, row j with in.rng[j].  The launchers take c == null from the op-level mirror (flm_op_attention_fan)
 int fan_classify(flm_ctx* c, int row0, int m, float* stage, bool skinny, float temperature, float topp, const flm::FanIn& in);
@@ -532,7 +532,7 @@ int launch_entropy_rows(flm_ctx* c, hipStream_t st, const flm::EntropyRowsArgs& 
 // k_sample_rows on `rows` <= 16 rows of n logits, ld floats apart, batch rows row0 ..; sort_buf [rows][2][n] (flm_prompt.hip; c may be null: flm_op_sample_rows)
 int launch_sample_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, int n, int row0, int rows, float temperature, float topp, unsigned long long base,
                        unsigned long long* sort_buf, int* out);
-int launch_gemm_skinny_store(flm_ctx* c, hipStream_t st, const GemmArgs& g, int force_nb = 0, bool w4 = false);   // (flm_prompt.hip: k_gemm_q8_skinny | w4: k_gemm_q4_skinny on a packed matrix in the device layout; plain store epilogue: flm_op_matmul_skinny; c may be null; force_nb 1 / 2: that many 16-row fragments per wave, 0: by size)
+int launch_gemm_skinny_store(flm_ctx* c, hipStream_t st, int qt, const GemmArgs& g, int force_nb = 0);   // (flm_prompt.hip: the skinny GEMM of weight type qt -- k_gemm_q8_skinny | INT4: k_gemm_q4_skinny on a packed matrix in the device layout | INT16: k_gemm_q16_skinny; plain store epilogue: flm_op_matmul_skinny, flm_op_matmul_q under FLM_OP_GEMM=skinny; c may be null; force_nb 1 / 2: that many 16-row fragments per wave, 0: by size)
 // k_score_rows on `rows` rows of n logits, ld floats apart (c may be null: flm_op_score_rows)
 int launch_score_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, int n, const int* targets, flm::ScoreRow* out, int rows);
 int launch_gemm_store(flm_ctx* c, hipStream_t st, int qt, const GemmArgs& g, int use_mfma);   // (flm_prompt.hip: one GEMM tile launch, plain store epilogue: flm_op_matmul_q; qt INT4: k_gemm_q4_mfma on a packed matrix in the device layout)

@@ -49,6 +49,8 @@
 //   k_gemm_q8_skinny      (flm_prefill.h) the int8 GEMM for <= 16 tokens on v_mfma_i32_16x16x64_i8, weights straight from global memory: the verify pass of draft-and-verify
 //   k_gemm_q4_skinny      (flm_prefill.h) its W4A8 sibling: the packed nibbles straight from global memory into the B operand (8 bytes per lane and group), the offset taken out
 //                         by one all-ones MFMA per group; an INT4 context's passes of <= 16 rows under "spec_gemm" 1
+//   k_gemm_q16_skinny     (flm_prefill.h) its int16 sibling: a lane's 32 bytes per group straight from global memory, split in registers into low / high byte planes (split16),
+//                         four MFMAs per group on one accumulator (k_gemm_q16_mfma's arithmetic); an INT16 context's passes of <= 16 rows under "spec_gemm" 1
 //   k_spec_draft, k_argmax_rows, k_spec_begin, k_spec_accept_sample  (flm_spec.h) draft-and-verify, greedy and sampled: the prompt-lookup drafter, the per-row first-maximum argmax
 //                         (temperature 0), the history's start and the accept step, which leaves the accepted ids and the sampler's state after their draws in one block
 //   k_score_rows          (flm_score.h) per row of a block of logits: first-maximum argmax, the clipped softmax's max / exact sequential sum, the target's logit and probability

@@ -102,8 +102,14 @@ int flm_op_matmul_q(int qt, float* out, const void* W, const float* sW, const vo
     OPC(hipMemcpy(dX.p, X, (size_t)w * n * e, hipMemcpyHostToDevice)); OPC(hipMemcpy(dsX.p, sX, (size_t)w * sn * 4, hipMemcpyHostToDevice));
     if (w4) { int r = repack_w4(nullptr, 0, dW.p, wbytes); if (r) return r; }     // (as an upload does)
     int dev = 0, cus = 256; hipGetDevice(&dev); hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    const char* gv = getenv("FLM_OP_GEMM");                     // tests: 0 .. 3 = launch_gemm's use_mfma, "gemv" = a GEMV per batch row
-    if (w >= 16 && !(gv && !strcmp(gv, "gemv"))) {
+    const char* gv = getenv("FLM_OP_GEMM");                     // tests: 0 .. 3 = launch_gemm's use_mfma, "gemv" = a GEMV per batch row, "skinny" = the type's skinny GEMM (w <= 16)
+    if (gv && !strcmp(gv, "skinny")) {
+        if (w > kSkinnyTokens) return FLM_ERR_INVALID;
+        OPC(hipMemset(dO.p, 0xff, (size_t)w * m * 4));                                  // (an output nobody stored reads as NaN)
+        GemmArgs g{dW.p, dsW.as<float>(), dX.p, dsX.as<float>(), dO.as<float>(), m, n, m, w, nullptr, dsWT.as<float>()};
+        const char* nb = getenv("FLM_OP_SKINNY_NB");              // tests: 1 / 2 = fragments per wave, as in flm_op_matmul_skinny
+        int r = launch_gemm_skinny_store(nullptr, 0, qt, g, nb ? atoi(nb) : 0); if (r) return r;
+    } else if (w >= 16 && !(gv && !strcmp(gv, "gemv"))) {
         // the batched path the prompt takes (quant::matmul with w > 1, quant_operators.cpp:252-284): one tile kernel
         GemmArgs g{dW.p, dsW.as<float>(), dX.p, dsX.as<float>(), dO.as<float>(), m, n, m, w, dsXT.as<float>(), dsWT.as<float>()};
         const int um = gv ? atoi(gv) : 1;
@@ -141,7 +147,7 @@ int flm_op_matmul_skinny(int qt, float* out, const void* W, const float* sW, con
     if (w4) { int r = repack_w4(nullptr, 0, dW.p, wbytes); if (r) return r; }
     GemmArgs g{dW.p, dsW.as<float>(), dX.p, dsX.as<float>(), dO.as<float>(), m, n, m, w, nullptr, dsWT.as<float>()};
     const char* nb = getenv("FLM_OP_SKINNY_NB");                  // tests: 1 / 2 = fragments per wave (by size otherwise: two only from 8192 rows on, w4: beyond 16384)
-    int r = launch_gemm_skinny_store(nullptr, 0, g, nb ? atoi(nb) : 0, w4); if (r) return r;
+    int r = launch_gemm_skinny_store(nullptr, 0, qt, g, nb ? atoi(nb) : 0); if (r) return r;
     OPC(hipDeviceSynchronize());
     OPC(hipMemcpy(out, dO.p, (size_t)w * m * 4, hipMemcpyDeviceToHost));
     return FLM_OK;

@@ -460,7 +460,7 @@ __global__ void __launch_bounds__(256, 3) k_gemm_q16_mfma(const GemmArgs a) {
 //     workgroup: QKV, the classifier; the two fragments share the activation operand) -- SwiGLU: the same 16 rows of W1 and W3, gate and up meet in one lane.
 //   * the <= 16 quantized activation rows are read through L2 (buffer loads; token columns >= B read as zero and are never stored); their scales sit in LDS,
 //     [groups][16], zero for idle columns and for the ring's groups past the end: fma(0 * 0, float(0), acc) = acc (acc is never -0).
-// int16 models keep the hi / lo-plane tiles (k_gemm_q16_mfma) in the verify pass: correct, not fast.
+// INT4 and int16 models have siblings below: k_gemm_q4_skinny on the packed nibbles, k_gemm_q16_skinny on byte planes split in registers.
 // ------------------------------------------------------------------------------------------
 template <int EPI, int NB>
 __device__ __forceinline__ void skinny_epilogue(const GemmArgs& a, const float (&acc)[NB][4], const int rbase, const int lane) {
@@ -676,6 +676,119 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) k_
                 const v2u w = wr[k][j];
                 const v4u u = {w[0] & kNib, (w[0] >> 4) & kNib, w[1] & kNib, (w[1] >> 4) & kNib};
                 const v4i d = __builtin_amdgcn_mfma_i32_16x16x64_i8(x, __builtin_bit_cast(v4i, u), off, 0, 0, 0);
+                const float sw = __uint_as_float(sr[k][j]);
+                acc[j][0] = __fmaf_rn(__fmul_rn(sw, sx.x), (float)d[0], acc[j][0]);   // quant_operators.cpp:274
+                acc[j][1] = __fmaf_rn(__fmul_rn(sw, sx.y), (float)d[1], acc[j][1]);
+                acc[j][2] = __fmaf_rn(__fmul_rn(sw, sx.z), (float)d[2], acc[j][2]);
+                acc[j][3] = __fmaf_rn(__fmul_rn(sw, sx.w), (float)d[3], acc[j][3]);
+            }
+            fetch(tail, k, g0 + D, wb, xb);
+        }
+    };
+    int g0 = 0;
+    for (; g0 + 2 * D <= sn; g0 += D) round(SkinnyTail<false>{}, g0);
+    for (; g0 < sn; g0 += D) round(SkinnyTail<true>{}, g0);
+    skinny_epilogue<EPI, NB>(a, acc, r0 + l15, lane);
+}
+
+// ------------------------------------------------------------------------------------------
+// The skinny int16 GEMM: k_gemm_q8_skinny's contract once more (tokens = A, weight rows = B of v_mfma_i32_16x16x64_i8, C/D col = lane & 15 = the weight row, row = 4 (lane
+// >> 4) + reg = the token, one wave per workgroup, activation scales [groups][16] in LDS, the chain step and skinny_epilogue unchanged) with k_gemm_q16_mfma's arithmetic:
+// gfx950 has no int16 MFMA, a value is two signed bytes (split16: w = 256 wh + wl) and a group's dot four int8 products on ONE accumulator.
+//   * operand: lane (l15, q) owns elements 16 q .. 16 q + 15 of group g of its row = the 32 bytes at row * 2 n + 128 g + 32 q, two 16-byte buffer loads.  split16 turns each
+//     piece, in registers, into 8 low and 8 high bytes; the lane ends with two v4i operands wl and wh whose byte k is element 16 q + k.  The activation side is the same
+//     (token l15's 32 bytes -> xl, xh; the split is shared by the NB fragments).  A and B use the same byte -> k assignment, and integer sums are order-free.
+//   * four MFMAs per fragment and group: d = S(xh, wh); d <<= 8; d += S(xh, wl) + S(xl, wh); d <<= 8; d += S(xl, wl) -- the accumulator INPUT carries the shifted sum,
+//     everything mod 2^32, landing on the true int32 group dot (64 * 5792^2 < 2^31: the reference's own int32).  The shifts are 4 VALU each.
+//   * ring: a slot is 8 NB + 8 registers of operands plus NB scales; D groups of all three streams are in flight (equal depths: a wave's loads return in issue order, see
+//     k_gemm_q4_skinny).  Nothing but the activation scales is staged in LDS.  The full rounds carry no bounds test.
+//   * zeros: a zero word is eight zero weights in both planes.  Rows past the matrix read zero weights and zero scales and are masked at the store; groups past the end
+//     (the ring's last round) and token columns >= B read zero activations and zero scales: fma(0 * 0, float(0), acc) = acc.
+//   num_records of the weight descriptor is in BYTES: rows * 2 n (SWIGLU: of both halves).
+// ------------------------------------------------------------------------------------------
+__host__ __device__ constexpr int skinny16_depth(int nb) { return nb == 1 ? 10 : 6; }                    // groups in flight per wave
+__host__ __device__ inline int skinny16_groups_padded(int sn, int nb) { const int d = skinny16_depth(nb); return (sn + d - 1) / d * d + d; }
+__host__ __device__ inline size_t skinny16_lds_bytes(int n, int nb) { return (size_t)skinny16_groups_padded(n / kGroup, nb) * kSkinnyTokens * 4; }
+// grid: ceil(rows / (16 NB)) workgroups of 64 threads (SWIGLU: ceil(rows / 16), NB = 2); skinny16_lds_bytes(n, NB) of dynamic LDS; B <= 16; single GPU (no peers)
+// waves_per_eu(2): at most 256 registers to a wave, so that the MFMA results stay in VGPRs (see k_gemm_q4_skinny)
+template <int EPI, int NB>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) k_gemm_q16_skinny(const GemmArgs a) {
+    constexpr bool TWO = EPI == EPI_SWIGLU;
+    static_assert(!TWO || NB == 2, "gate and up are the two B fragments of the wave");
+    constexpr int D = skinny16_depth(NB);
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    float* const sxl = reinterpret_cast<float*>(lds);                       // [groups, padded][16 tokens]
+    const int lane = threadIdx.x, l15 = lane & 15, q = lane >> 4;
+    const int sn = a.n / kGroup, snp = skinny16_groups_padded(sn, NB);
+    const int r0 = blockIdx.x * (TWO ? 16 : 16 * NB);
+    for (int i = lane; i < snp * kSkinnyTokens; i += 64) { const int g = i >> 4, b = i & 15; sxl[i] = (g < sn && b < a.B) ? a.Xs[(size_t)b * sn + g] : 0.0f; }
+    __syncthreads();
+    const unsigned rowbytes = (unsigned)a.n * 2;                            // a row of either side
+    constexpr unsigned kOOB = 0x80000000u, kGB = kGroup * 2;
+    const unsigned s_rows = (TWO ? 2u : 1u) * (unsigned)a.rows;
+    const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.W), 0, (int)(s_rows * rowbytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rX = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.Xq), 0, (int)((unsigned)a.B * rowbytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rS = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.sWT), 0, (int)(s_rows * (unsigned)sn * 4), 0x00020000);
+    // fragment j: rows r0 + 16 j .. (SWIGLU: rows r0 .. of W1 (j = 0) and of W3 (j = 1)).  A dead lane (a row past the matrix, a token column >= B) carries bit 31 in its
+    // offsets, a dead group ORs it in: an offset of 2^31 or more is out of range of every descriptor here (the launcher bounds them), and no sum below wraps
+    unsigned woff[NB], soff[NB];
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+        const int row = r0 + (TWO ? 0 : 16 * j) + l15;
+        const unsigned wrow = (unsigned)(TWO ? j * a.rows + row : row);
+        woff[j] = row < a.rows ? wrow * rowbytes + (unsigned)q * 32 : kOOB;
+        soff[j] = row < a.rows ? wrow * 4 : kOOB;
+    }
+    const unsigned xoff = l15 < a.B ? (unsigned)l15 * rowbytes + (unsigned)q * 32 : kOOB;
+    const unsigned sstep = s_rows * 4;
+    v4u wr[D][NB][2], xr[D][2]; unsigned sr[D][NB];
+    // groups gb + k -> ring slot k; TAIL: the round may run past the last group -- those loads go out of range and are never issued to memory
+    auto fetch = [&](auto tail, const int k, const int gb, const unsigned (&wb)[NB], const unsigned xb) {
+        constexpr bool TAIL = decltype(tail)::value;
+        const unsigned dead = TAIL && gb + k >= sn ? kOOB : 0u;           // (uniform: a scalar select)
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            wr[k][j][0] = __builtin_amdgcn_raw_buffer_load_b128(rW, (int)((wb[j] + (unsigned)k * kGB) | dead), 0, 0);
+            wr[k][j][1] = __builtin_amdgcn_raw_buffer_load_b128(rW, (int)((wb[j] + (unsigned)k * kGB + 16u) | dead), 0, 0);
+            sr[k][j] = __builtin_amdgcn_raw_buffer_load_b32(rS, (int)((soff[j] + (unsigned)(gb + k) * sstep) | dead), 0, 0);
+        }
+        xr[k][0] = __builtin_amdgcn_raw_buffer_load_b128(rX, (int)((xb + (unsigned)k * kGB) | dead), 0, 0);
+        xr[k][1] = __builtin_amdgcn_raw_buffer_load_b128(rX, (int)((xb + (unsigned)k * kGB + 16u) | dead), 0, 0);
+    };
+    auto planes = [](const v4u (&p)[2], v4i& lo, v4i& hi) {                // 32 bytes = 16 int16 -> their low and their (carry-corrected) high bytes, element order
+        unsigned l0[2], h0[2], l1[2], h1[2];
+        split16(__builtin_bit_cast(v4i, p[0]), l0, h0); split16(__builtin_bit_cast(v4i, p[1]), l1, h1);
+        lo = v4i{(int)l0[0], (int)l0[1], (int)l1[0], (int)l1[1]}; hi = v4i{(int)h0[0], (int)h0[1], (int)h1[0], (int)h1[1]};
+    };
+    float acc[NB][4];
+#pragma unroll
+    for (int j = 0; j < NB; ++j)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[j][i] = 0.f;
+#pragma unroll
+    for (int k = 0; k < D; ++k) fetch(SkinnyTail<true>{}, k, 0, woff, xoff);
+    auto round = [&](auto tail, const int g0) {                          // consumes groups g0 .. g0 + D - 1, requests g0 + D .. g0 + 2 D - 1 into their slots
+        unsigned wb[NB];
+#pragma unroll
+        for (int j = 0; j < NB; ++j) wb[j] = woff[j] + (unsigned)(g0 + D) * kGB;
+        const unsigned xb = xoff + (unsigned)(g0 + D) * kGB;
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            const int g = g0 + k;                                           // (g >= sn in the last round: zero activations, zero scales)
+            const float4 sx = *reinterpret_cast<const float4*>(sxl + g * kSkinnyTokens + 4 * q);
+            v4i xl, xh; planes(xr[k], xl, xh);
+#pragma unroll
+            for (int j = 0; j < NB; ++j) {
+                v4i wl, wh; planes(wr[k][j], wl, wh);
+                const v4i z = {0, 0, 0, 0};
+                v4i d = __builtin_amdgcn_mfma_i32_16x16x64_i8(xh, wh, z, 0, 0, 0);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) d[i] = (int)((unsigned)d[i] << 8);
+                d = __builtin_amdgcn_mfma_i32_16x16x64_i8(xh, wl, d, 0, 0, 0);
+                d = __builtin_amdgcn_mfma_i32_16x16x64_i8(xl, wh, d, 0, 0, 0);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) d[i] = (int)((unsigned)d[i] << 8);
+                d = __builtin_amdgcn_mfma_i32_16x16x64_i8(xl, wl, d, 0, 0, 0);                  // wraps mod 2^32 onto the exact int32 dot
                 const float sw = __uint_as_float(sr[k][j]);
                 acc[j][0] = __fmaf_rn(__fmul_rn(sw, sx.x), (float)d[0], acc[j][0]);   // quant_operators.cpp:274
                 acc[j][1] = __fmaf_rn(__fmul_rn(sw, sx.y), (float)d[1], acc[j][1]);

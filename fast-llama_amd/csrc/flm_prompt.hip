@@ -94,6 +94,20 @@ int launch_gemm_skinny_w4(flm_ctx* c, hipStream_t st, const GemmArgs& g, int for
     HIPC(c, hipGetLastError());
     return FLM_OK;
 }
+// The skinny int16 GEMM (flm_prefill.h k_gemm_q16_skinny): the same refusals, on int16 bytes -- the 2 GiB bound of the buffer descriptor is on rows * n * 2.  Fragments
+// per wave: the int8 kernel's rule (two once that still gives every CU a workgroup; SwiGLU always two).
+template <int EPI>
+int launch_gemm_skinny_w16(flm_ctx* c, hipStream_t st, const GemmArgs& g, int force_nb = 0) {
+    if (g.B < 1 || g.B > kSkinnyTokens || g.n_peer) return fail(c, FLM_ERR_INVALID, "skinny gemm: 1 .. 16 tokens, one GPU");
+    if ((double)g.rows * g.n * 2 * (EPI == EPI_SWIGLU ? 2 : 1) >= 2147483648.0 || skinny16_lds_bytes(g.n, 1) > 64 * 1024 || skinny16_lds_bytes(g.n, 2) > 64 * 1024)
+        return fail(c, FLM_ERR_UNSUPPORTED, "skinny gemm: int16 matrix of 2 GiB or more, or rows longer than 65536");
+    const int cus = c ? c->cu_count : 256;
+    if constexpr (EPI == EPI_SWIGLU) hipLaunchKernelGGL((k_gemm_q16_skinny<EPI_SWIGLU, 2>), dim3((g.rows + 15) / 16), dim3(64), skinny16_lds_bytes(g.n, 2), st, g);
+    else if (force_nb == 2 || (force_nb == 0 && (g.rows + 31) / 32 >= cus)) hipLaunchKernelGGL((k_gemm_q16_skinny<EPI, 2>), dim3((g.rows + 31) / 32), dim3(64), skinny16_lds_bytes(g.n, 2), st, g);
+    else hipLaunchKernelGGL((k_gemm_q16_skinny<EPI, 1>), dim3((g.rows + 15) / 16), dim3(64), skinny16_lds_bytes(g.n, 1), st, g);
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
 // The W4A8 GEMM tiles (flm_prefill.h k_gemm_q4_mfma): launch_gemm's tile-shape rule and use_mfma (1 by size, 2 / 0 always 64 x 64, 3 always 128 x 128; SwiGLU always 128 x
 // 128 on [W1; W3]) on a PACKED matrix in the device nibble layout -- g.W is [rows][n / 2] bytes and the 2 GiB bound of the buffer descriptor is on those.  Both shapes stage
 // less than the default dynamic-LDS limit (GemmTile4::kLds, asserted there), so no kernel attribute is raised.  One GPU: INT4 is refused across ranks at create.
@@ -115,7 +129,7 @@ int launch_gemm_w4(flm_ctx* c, hipStream_t st, const GemmArgs& g, int use_mfma) 
     return FLM_OK;
 }
 // which GEMM family a pass's weight pointers belong to: pass_weights / pass_classifier decide it together with the pointers (flm_query "pass_gemm" reports the values)
-enum GemmKind { GEMM_TILES = 0, GEMM_SKINNY8, GEMM_SKINNY4, GEMM_TILES4 };
+enum GemmKind { GEMM_TILES = 0, GEMM_SKINNY8, GEMM_SKINNY4, GEMM_TILES4, GEMM_SKINNY16 };
 // one GEMM of the batched path: the tiles, or -- the verify pass under "spec_gemm" 1 -- the skinny kernel, each of the weights' type (int8 / int16 bytes | packed nibbles)
 template <int QT, int EPI>
 int launch_gemm_any(flm_ctx* c, hipStream_t st, const GemmArgs& g, int use_mfma, GemmKind kind) {
@@ -123,7 +137,7 @@ int launch_gemm_any(flm_ctx* c, hipStream_t st, const GemmArgs& g, int use_mfma,
         if (kind == GEMM_TILES4) return launch_gemm_w4<EPI>(c, st, g, use_mfma);
         if (kind == GEMM_SKINNY4) return launch_gemm_skinny_w4<EPI>(c, st, g);
         if (kind == GEMM_SKINNY8) return launch_gemm_skinny<EPI>(c, st, g);
-    }
+    } else if (kind == GEMM_SKINNY16) return launch_gemm_skinny_w16<EPI>(c, st, g);
     return launch_gemm<QT, EPI>(c, st, g, use_mfma);
 }
 
@@ -280,8 +294,8 @@ int launch_rope_kv_segs(flm_ctx* c, hipStream_t st, const float* qkv, float* qou
 // refill in front of every layer's GEMMs and every classifier chunk is gone: DESIGN.md section 5o has the measurement that retired it.)
 static inline bool tiles_int8(const flm_ctx* c) { return c->d.quant_type != FLM_QT_INT16; }
 static inline GemmKind pass_kind(const flm_ctx* c, bool skinny) {
-    const bool w4 = c->d.quant_type == FLM_QT_INT4;
-    return skinny ? (w4 ? GEMM_SKINNY4 : GEMM_SKINNY8) : (w4 ? GEMM_TILES4 : GEMM_TILES);
+    const bool w4 = c->d.quant_type == FLM_QT_INT4, w16 = c->d.quant_type == FLM_QT_INT16;
+    return skinny ? (w4 ? GEMM_SKINNY4 : w16 ? GEMM_SKINNY16 : GEMM_SKINNY8) : (w4 ? GEMM_TILES4 : GEMM_TILES);
 }
 // the ONE place a pass picks layer l's weight pointers and the GEMM family that reads them
 static int pass_weights(flm_ctx* c, int l, bool skinny, LayerW& w, GemmKind& kind) {
@@ -304,7 +318,7 @@ int prefill_batched(flm_ctx* c, int B, int pos, bool all_layers, bool skinny_req
     if (S > 0 && segs) { rope_segs = *segs; for (int i = 0; i < kBatchMax; ++i) rope_segs.base[i] -= S; }
     const SlotDesc* const rslots = S > 0 && slots ? &rope_slots : slots;
     const SegDesc* const rsegs = S > 0 && segs ? &rope_segs : segs;
-    const bool skinny = skinny_req && QT == QT_INT8 && B <= kSkinnyTokens && c->world == 1;      // (the verify pass; int16: the tiles)
+    const bool skinny = skinny_req && B <= kSkinnyTokens && c->world == 1;      // (the verify pass; either type: pass_kind picks the kernel)
     const auto& d = c->d;
     const int L = d.n_layers, dim = d.dim, hid = d.hidden_dim, hs = c->hs;
     hipStream_t st = c->stream;
@@ -480,7 +494,10 @@ int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers, bool skinny,
             return fail(c, FLM_ERR_INVALID, "prefill: a batch row outside its slot, or a slot outside the cache");
     return tiles_int8(c) ? prefill_batched<QT_INT8>(c, B, pos, all_layers, skinny, fan, row0, slots_in, nullptr, pfx) : prefill_batched<QT_INT16>(c, B, pos, all_layers, skinny, fan, row0, slots_in, nullptr, pfx);
 }
-int launch_gemm_skinny_store(flm_ctx* c, hipStream_t st, const GemmArgs& g, int force_nb, bool w4) { return w4 ? launch_gemm_skinny_w4<EPI_STORE>(c, st, g, force_nb) : launch_gemm_skinny<EPI_STORE>(c, st, g, force_nb); }
+int launch_gemm_skinny_store(flm_ctx* c, hipStream_t st, int qt, const GemmArgs& g, int force_nb) {
+    if (qt == FLM_QT_INT4) return launch_gemm_skinny_w4<EPI_STORE>(c, st, g, force_nb);
+    return qt == FLM_QT_INT16 ? launch_gemm_skinny_w16<EPI_STORE>(c, st, g, force_nb) : launch_gemm_skinny<EPI_STORE>(c, st, g, force_nb);
+}
 
 // ---------------------------------------------------------------------------------------------
 // flm_score_tokens: the classifier for a chunk of the batch's rows.  The row prologue is the decode classifier's (rmsnorm with the output norm's weight, quantize), the tiles
@@ -574,7 +591,7 @@ static int classify_rows_t(flm_ctx* c, int row0, int m, float* stage, bool skinn
     // logits = Wcls quantize(rmsnorm(x1))   (transformer.cpp:154-160)
     RowsArgs ra{c->pf_x + (size_t)row0 * dim, c->out_norm, c->pf_xq, c->pf_xs, dim, c->pf_xst};
     int r = launch_rows<QT, PRO_RMSNORM_QUANT>(c, st, ra, m); if (r) return r;
-    const void* wq = nullptr; GemmKind kind; r = pass_classifier(c, skinny && QT == QT_INT8 && m <= kSkinnyTokens, &wq, kind); if (r) return r;
+    const void* wq = nullptr; GemmKind kind; r = pass_classifier(c, skinny && m <= kSkinnyTokens, &wq, kind); if (r) return r;
     GemmArgs g{wq, c->cls.s, c->pf_xq, c->pf_xs, stage, V, dim, V, m, c->pf_xst, c->cls.st};
     return launch_gemm_any<QT, EPI_STORE>(c, st, g, c->use_mfma, kind);
 }
@@ -632,7 +649,7 @@ int launch_sample_fan(flm_ctx* c, hipStream_t st, const float* logits, int ld, i
 // a fan step's classifier stage: the chunk through score_classify's prologue and GEMM, then k_sample_fan -- every row with its own state
 int fan_classify(flm_ctx* c, int row0, int m, float* stage, bool skinny, float temperature, float topp, const FanIn& in) {
     const int V = c->d.vocab_size;
-    int r = tiles_int8(c) ? classify_rows_t<QT_INT8>(c, row0, m, stage, skinny) : classify_rows_t<QT_INT16>(c, row0, m, stage, false); if (r) return r;
+    int r = tiles_int8(c) ? classify_rows_t<QT_INT8>(c, row0, m, stage, skinny) : classify_rows_t<QT_INT16>(c, row0, m, stage, skinny); if (r) return r;
     return launch_sample_fan(c, c->stream, stage, V, V, row0, m, temperature, topp, in, c->sort_buf, c->fan_drawn, c->fan_after);
 }
 // k_sample_slots on `rows` rows of n logits, ld floats apart, batch rows row0 ..; sort_buf [16][2][n] (needed where a row of the chunk is sampled)
@@ -658,13 +675,13 @@ int launch_sample_slots(flm_ctx* c, hipStream_t st, const float* logits, int ld,
 // score_classify's prologue and GEMM, then k_sample_slots -- every row with its own parameters and state
 int batch_classify(flm_ctx* c, int src_row0, int row0, int m, float* stage, bool skinny, const SlotIn& in) {
     const int V = c->d.vocab_size;
-    int r = tiles_int8(c) ? classify_rows_t<QT_INT8>(c, src_row0, m, stage, skinny) : classify_rows_t<QT_INT16>(c, src_row0, m, stage, false); if (r) return r;
+    int r = tiles_int8(c) ? classify_rows_t<QT_INT8>(c, src_row0, m, stage, skinny) : classify_rows_t<QT_INT16>(c, src_row0, m, stage, skinny); if (r) return r;
     return launch_sample_slots(c, c->stream, stage, V, V, row0, m, in, c->sort_buf, c->fan_drawn, c->fan_after);
 }
-// the verify pass's classifier stage: the same chunk through the same prologue and GEMM (skinny: k_gemm_q8_skinny, int8), then k_argmax_rows into argmax_out[row0 ..]
+// the verify pass's classifier stage: the same chunk through the same prologue and GEMM (skinny: k_gemm_q8_skinny or its INT4 / int16 sibling), then k_argmax_rows into argmax_out[row0 ..]
 // (draw given and its temperature > 0: k_sample_rows in place of k_argmax_rows)
 int spec_classify(flm_ctx* c, int row0, int m, float* stage, bool skinny, int* argmax_out, const SpecDraw& draw) {
-    return tiles_int8(c) ? score_classify_t<QT_INT8>(c, row0, m, stage, skinny, argmax_out, &draw) : score_classify_t<QT_INT16>(c, row0, m, stage, false, argmax_out, &draw);
+    return tiles_int8(c) ? score_classify_t<QT_INT8>(c, row0, m, stage, skinny, argmax_out, &draw) : score_classify_t<QT_INT16>(c, row0, m, stage, skinny, argmax_out, &draw);
 }
 
 } // namespace fh

@@ -6,6 +6,8 @@ python tools/w4_bench.py [reps] [layers]   -- prints the tables and one JSON lin
 python tools/w4_bench.py --verify [reps] [layers]   -- the passes of up to 16 rows instead: the time of one flm_verify_greedy pass at B = 5, 8 and 16 rows (position 20) and
 the time per step of flm_generate_batch with 16 slots, for an INT4 context under "spec_gemm" 1 and 0 and an INT8 context under "spec_gemm" 1, the three alternating,
 medians of `reps` with min .. max.  FLM_GPU_LIB picks the library (capi.py): under the build of the commit before k_gemm_q4_skinny the first row is unpack + int8 skinny.
+--type int16 (with --verify): the same table for an INT16 context in place of the INT4 one -- k_gemm_q16_skinny under "spec_gemm" 1, the hi / lo-plane tiles under 0; under
+the build of the commit before k_gemm_q16_skinny both rows are the tiles.
 
 python tools/w4_bench.py --prefill [reps] [layers]   -- the passes of more than 16 rows (and the tile route of a 16-row one): flm_forward of a 17-, 64-, 130- and 512-token
 prompt, flm_score_tokens of 512 tokens with "score_rows" 128 (the classifier in 4 chunks) and a verify pass at B = 16 under "spec_gemm" 0 on an INT4 context, and the
@@ -23,7 +25,8 @@ import __graft_entry__ as g; g.load_package()
 from fast_llama_amd import capi, synth, flmfile as ff
 
 verify, prefill = "--verify" in sys.argv, "--prefill" in sys.argv
-args = [a for a in sys.argv[1:] if not a.startswith("--")]
+wtype = sys.argv[sys.argv.index("--type") + 1] if "--type" in sys.argv else "int4"
+args = [a for i, a in enumerate(sys.argv[1:], 1) if not a.startswith("--") and sys.argv[i - 1] != "--type"]
 reps = int(args[0]) if len(args) > 0 else 5
 layers = int(args[1]) if len(args) > 1 else None
 PEAK, POS, STEPS = 8e12, 20, 128
@@ -47,7 +50,8 @@ def verify_bench():
     """every timed window ends behind a device synchronise: verify_greedy and generate_batch return ids that are on the host"""
     CALLS, SLOTS, SHORT, LONG = 20, 16, 9, 41
     runs = {}
-    for name, qt, gemm in (("int4 spec_gemm 1", capi.QT_INT4, 1), ("int4 spec_gemm 0", capi.QT_INT4, 0), ("int8 spec_gemm 1", ff.QT_INT8, 1)):
+    wqt = {"int4": capi.QT_INT4, "int16": ff.QT_INT16}[wtype]
+    for name, qt, gemm in ((f"{wtype} spec_gemm 1", wqt, 1), (f"{wtype} spec_gemm 0", wqt, 0), ("int8 spec_gemm 1", ff.QT_INT8, 1)):
         runs[name] = context(qt, False); runs[name].set_option("spec_gemm", gemm)
     prompt = (np.arange(POS, dtype=np.int32) * 7 + 1) % 1000
     reqs = lambda n: [capi.BatchReq((np.arange(4, dtype=np.int32) + 11 * s) % 1000 + 1, n) for s in range(SLOTS)]   # noqa: E731
