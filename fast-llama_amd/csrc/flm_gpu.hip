@@ -819,7 +819,7 @@ int flm_set_option(flm_ctx* c, const char* key, int value) {
         c->p2p = value ? 1 : 0;
     }
     else if (k == "spec_branches") { if (value < 1 || value > 4) return fail(c, FLM_ERR_INVALID, "spec_branches: 1 .. 4"); c->spec_branches = value; return FLM_OK; }
-    else if (k == "spec_gemm") { c->spec_gemm = value ? 1 : 0; return FLM_OK; }      // (read per call by the new entry points only: no captured graph depends on it)
+    else if (k == "spec_gemm") { if (value < 0 || value > 2) return fail(c, FLM_ERR_INVALID, "spec_gemm: 0, 1 or 2"); c->spec_gemm = value; return FLM_OK; }      // (read per call by the new entry points only: no captured graph depends on it)
     else if (k == "batch_rows") { c->batch_rows = value < 0 ? -1 : value; return FLM_OK; }      // (read per flm_generate_batch call: no captured graph depends on it)
     else if (kAblate && k == "ablate") c->ablate = value;              // FLM_ABLATE builds only: a product library cannot skip work
     else if (kAblate && k == "trace") {   // value = kernel class to trace (KC_*), -1 off

@@ -193,7 +193,7 @@ struct flm_ctx {
     // ids [16] (first maxima or draws) and the step's result block (the accepted ids and the sampler's state behind them, one trip), device memory since create; which GEMM
     // the verify pass runs; the last call's figures ("spec_steps" / "spec_accepted")
     int* spec_hist = nullptr; int* spec_arg = nullptr; flm::SpecOut* spec_res = nullptr;
-    int spec_gemm = 0;                                 // option "spec_gemm": 1 = the verify pass's GEMMs through k_gemm_q8_skinny (INT4 contexts: k_gemm_q4_skinny on the packed weights; INT16 contexts: k_gemm_q16_skinny) (B <= 16), 0 (default until both forms have been timed: DESIGN.md section 5e) = the 64 x 64 tiles; the new entry points only
+    int spec_gemm = 0;                                 // option "spec_gemm": 1 = the verify pass's GEMMs through k_gemm_q8_skinny (INT4 contexts: k_gemm_q4_skinny on the packed weights; INT16 contexts: k_gemm_q16_skinny) (B <= 16), 2 = the same with int8 weights on the split-K k_gemm_q8_skinny_sk (INT4 / INT16 contexts: as 1), 0 (default until both forms have been timed: DESIGN.md section 5e) = the 64 x 64 tiles; the new entry points only
     int spec_steps = 0, spec_accepted = 0;
     int spec_branches = 1;                             // option "spec_branches": B > 1 = the plain greedy lookup loop drafts a TREE from the B most recent distinct history matches (flm_tree.h); 1: the chain, today's launches
     // the model-based drafter (include/flm_gpu.h flm_draft_set / flm_generate_draft; flm_calls.hip generate_lookup_impl): the paired draft context (not owned; null: none),
@@ -532,7 +532,7 @@ int launch_entropy_rows(flm_ctx* c, hipStream_t st, const flm::EntropyRowsArgs& 
 // k_sample_rows on `rows` <= 16 rows of n logits, ld floats apart, batch rows row0 ..; sort_buf [rows][2][n] (flm_prompt.hip; c may be null: flm_op_sample_rows)
 int launch_sample_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, int n, int row0, int rows, float temperature, float topp, unsigned long long base,
                        unsigned long long* sort_buf, int* out);
-int launch_gemm_skinny_store(flm_ctx* c, hipStream_t st, int qt, const GemmArgs& g, int force_nb = 0);   // (flm_prompt.hip: the skinny GEMM of weight type qt -- k_gemm_q8_skinny | INT4: k_gemm_q4_skinny on a packed matrix in the device layout | INT16: k_gemm_q16_skinny; plain store epilogue: flm_op_matmul_skinny, flm_op_matmul_q under FLM_OP_GEMM=skinny; c may be null; force_nb 1 / 2: that many 16-row fragments per wave, 0: by size)
+int launch_gemm_skinny_store(flm_ctx* c, hipStream_t st, int qt, const GemmArgs& g, int force_nb = 0, bool splitk = false);   // (flm_prompt.hip: the skinny GEMM of weight type qt -- k_gemm_q8_skinny, splitk: k_gemm_q8_skinny_sk | INT4: k_gemm_q4_skinny on a packed matrix in the device layout | INT16: k_gemm_q16_skinny; plain store epilogue: flm_op_matmul_skinny, flm_op_matmul_q under FLM_OP_GEMM=skinny; c may be null; force_nb 1 / 2: that many 16-row fragments per wave, 0: by size)
 // k_score_rows on `rows` rows of n logits, ld floats apart (c may be null: flm_op_score_rows)
 int launch_score_rows(flm_ctx* c, hipStream_t st, const float* logits, int ld, int n, const int* targets, flm::ScoreRow* out, int rows);
 int launch_gemm_store(flm_ctx* c, hipStream_t st, int qt, const GemmArgs& g, int use_mfma);   // (flm_prompt.hip: one GEMM tile launch, plain store epilogue: flm_op_matmul_q; qt INT4: k_gemm_q4_mfma on a packed matrix in the device layout)

@@ -47,6 +47,9 @@
 //   k_sample_rows         (flm_sample.h) the same draw (sample_draw, one __device__ function for both) over the rows of a verify batch, row i with the (i + 1)-th coin of the step's
 //                         state: flm_verify_sample / flm_generate_lookup_sample
 //   k_gemm_q8_skinny      (flm_prefill.h) the int8 GEMM for <= 16 tokens on v_mfma_i32_16x16x64_i8, weights straight from global memory: the verify pass of draft-and-verify
+//   k_gemm_q8_skinny_sk   (flm_prefill.h) its split-K form: four waves per workgroup on the same 16 / 32 rows, wave w on the quant groups g = w (mod 4) with a register ring of
+//                         its own; the exact group dots meet in a double-buffered LDS ring, one barrier per round of four groups, and every wave carries the ordered fp32
+//                         chains of four tokens; the same bits; an INT8 context's passes of <= 16 rows under "spec_gemm" 2
 //   k_gemm_q4_skinny      (flm_prefill.h) its W4A8 sibling: the packed nibbles straight from global memory into the B operand (8 bytes per lane and group), the offset taken out
 //                         by one all-ones MFMA per group; an INT4 context's passes of <= 16 rows under "spec_gemm" 1
 //   k_gemm_q16_skinny     (flm_prefill.h) its int16 sibling: a lane's 32 bytes per group straight from global memory, split in registers into low / high byte planes (split16),

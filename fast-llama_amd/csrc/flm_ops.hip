@@ -128,7 +128,7 @@ int flm_op_matmul_q(int qt, float* out, const void* W, const float* sW, const vo
 }
 
 /* quant::matmul for 1 <= w <= 16 batch rows through k_gemm_q8_skinny, the verify pass's int8 GEMM (plain store epilogue): out[w][m].  INT4 (W4A8): W is [m][n / 2]
-   nibbles in the interchange order, repacked as an upload does, X is int8: k_gemm_q4_skinny on the packed matrix */
+   nibbles in the interchange order, repacked as an upload does, X is int8: k_gemm_q4_skinny on the packed matrix.  FLM_OP_SKINNY_SPLITK=1: int8 through k_gemm_q8_skinny_sk */
 int flm_op_matmul_skinny(int qt, float* out, const void* W, const float* sW, const void* X, const float* sX, int m, int n, int w, int gs) {
     if (!out || !W || !sW || !X || !sX || m < 1 || n < 1 || w < 1 || w > kSkinnyTokens || gs != kGroup || n % kGroup) return FLM_ERR_INVALID;
     if (qt != FLM_QT_INT8 && qt != FLM_QT_INT4) return FLM_ERR_UNSUPPORTED;
@@ -147,7 +147,8 @@ int flm_op_matmul_skinny(int qt, float* out, const void* W, const float* sW, con
     if (w4) { int r = repack_w4(nullptr, 0, dW.p, wbytes); if (r) return r; }
     GemmArgs g{dW.p, dsW.as<float>(), dX.p, dsX.as<float>(), dO.as<float>(), m, n, m, w, nullptr, dsWT.as<float>()};
     const char* nb = getenv("FLM_OP_SKINNY_NB");                  // tests: 1 / 2 = fragments per wave (by size otherwise: two only from 8192 rows on, w4: beyond 16384)
-    int r = launch_gemm_skinny_store(nullptr, 0, qt, g, nb ? atoi(nb) : 0); if (r) return r;
+    const char* sk = getenv("FLM_OP_SKINNY_SPLITK");              // tests: 1 = int8 through the split-K kernel k_gemm_q8_skinny_sk (other types ignore it)
+    int r = launch_gemm_skinny_store(nullptr, 0, qt, g, nb ? atoi(nb) : 0, sk && !strcmp(sk, "1")); if (r) return r;
     OPC(hipDeviceSynchronize());
     OPC(hipMemcpy(out, dO.p, (size_t)w * m * 4, hipMemcpyDeviceToHost));
     return FLM_OK;

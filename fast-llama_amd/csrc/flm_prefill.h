@@ -583,6 +583,129 @@ __global__ void __launch_bounds__(64) k_gemm_q8_skinny(const GemmArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------
+// The split-K skinny int8 GEMM ("spec_gemm" 2): k_gemm_q8_skinny's GemmArgs, epilogues, grid rule and bits, with W = 4 waves (one per SIMD) on a workgroup's 16 NB rows.
+// One wave per 16 rows keeps D KiB per fragment in flight and three SIMDs of a CU idle where the grid is the CU count (Wo, W2); four waves on the same rows keep the grid
+// and carry four rings.
+//   * split: wave w owns the quant groups g = w (mod W); a round is W consecutive groups, one per wave, 256 contiguous bytes of a weight row.  Every wave has its own
+//     register ring of D groups (weights by b128 buffer loads straight into the B operand, its groups' activation bytes, its groups' weight scales); addresses, descriptors
+//     and zero rules are k_gemm_q8_skinny's (rows past the matrix, groups past the end and idle token columns read as zero).
+//   * integer part: per group and fragment one v_mfma_i32_16x16x64_i8, tokens = A, weight rows = B.  The 256 int32 dots are exact: which wave made them changes no bit.
+//   * ordered chain: acc = fma(sw * sx, float(d), acc) must see the groups ascending, so the dots leave the wave that made them.  A wave parks its group's dots in an LDS
+//     slot [W groups][NB][16 tokens][16 rows] int32 (1 KiB per group and fragment) and its 16 weight scales beside them; the activation scales are the [groups][16]
+//     table of k_gemm_q8_skinny (sw * sx is formed by the consumer from the parked sw and the table's sx -- not parked as a product, which would double the ring).  The
+//     slots are double-buffered, so a round costs ONE barrier: round r + 2 overwrites slot r & 1 only behind barrier r + 1, which every wave reaches after its reads of
+//     round r.  After the barrier wave w carries the chains of tokens 4 w .. 4 w + 3: lane (l15, q) = (row, token 4 w + q), ONE output per fragment, W chain steps per
+//     round in group order.  A lane carries NB chains where k_gemm_q8_skinny's carries 4 NB, and the chain work of a workgroup runs on four SIMDs.
+//   * banks: a producer lane (l15, q) holds tokens 4 q + i; token t lies in row t ^ (t >> 2) of its 16 x 16 block, so that the four lane quarters of one ds_write hit
+//     four different 16-bank groups.  A consumer wave's four tokens are a permutation of four neighbouring rows: its reads are 64 consecutive words.
+//   * uniform: every wave runs all ceil(groups / W) rounds (a wave without a live group in the last one parks zeros and a zero scale); the barriers sit under
+//     conditions on n alone.  No wait on another workgroup.
+//   * epilogue: the 16 x 16 NB accumulators meet in LDS and wave 0 reads them in k_gemm_q8_skinny's C layout (lane = row, registers = tokens 4 q + i) and runs
+//     skinny_epilogue unchanged -- the RoPE pair in neighbouring lanes, the SwiGLU pairing, the residual add.
+// LDS: the sx table (64 bytes per group) + 2 slots x W NB x (1 KiB + 64 B) + NB KiB: 20.5 KiB at n = 11008, NB = 1; the launcher refuses rows whose table does not fit.
+// ------------------------------------------------------------------------------------------
+constexpr int kSkinnySkWaves = 4;
+__host__ __device__ constexpr int skinny_sk_depth(int nb) { return nb == 1 ? 8 : 4; }                    // groups in flight per wave: 32 KiB per workgroup either way (even: a round's slot is its ring index & 1; six groups of two fragments do not fit 128 registers)
+__host__ __device__ inline int skinny_sk_rounds(int sn) { return (sn + kSkinnySkWaves - 1) / kSkinnySkWaves; }
+__host__ __device__ constexpr int skinny_sk_slot_words(int nb) { return kSkinnySkWaves * nb * (256 + 16); }   // a round's dots and weight scales
+__host__ __device__ inline size_t skinny_sk_lds_bytes(int n, int nb) {
+    return ((size_t)skinny_sk_rounds(n / kGroup) * kSkinnySkWaves * kSkinnyTokens + 2 * skinny_sk_slot_words(nb) + nb * 256) * 4;
+}
+// grid: ceil(rows / (16 NB)) workgroups of 256 threads (SWIGLU: ceil(rows / 16), NB = 2); skinny_sk_lds_bytes(n, NB) of dynamic LDS; B <= 16; single GPU (no peers)
+// waves_per_eu(4): at most 128 registers to a wave -- two workgroups to a CU where the grid exceeds the CUs -- and the MFMA results in VGPRs (see k_gemm_q4_skinny)
+template <int EPI, int NB>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_gemm_q8_skinny_sk(const GemmArgs a) {
+    constexpr bool TWO = EPI == EPI_SWIGLU;
+    static_assert(!TWO || NB == 2, "gate and up are the two B fragments of the wave");
+    constexpr int W = kSkinnySkWaves, D = skinny_sk_depth(NB), SLOT = skinny_sk_slot_words(NB);
+    static_assert(D % 2 == 0, "slot of round r0 + k = k & 1");
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = threadIdx.x & 63, l15 = lane & 15, q = lane >> 4;
+    const int sn = a.n / kGroup, rounds = skinny_sk_rounds(sn);
+    float* const sxl = reinterpret_cast<float*>(lds);                       // [rounds W groups][16 tokens]
+    int* const ring = reinterpret_cast<int*>(sxl + rounds * W * kSkinnyTokens);   // [2 slots]{[W][NB][16][16] dots, [W][NB][16] weight scales}
+    float* const fin = reinterpret_cast<float*>(ring + 2 * SLOT);            // [NB][16 tokens][16 rows]
+    const int r0 = blockIdx.x * (TWO ? 16 : 16 * NB);
+    for (int i = threadIdx.x; i < rounds * W * kSkinnyTokens; i += 256) { const int g = i >> 4, b = i & 15; sxl[i] = (g < sn && b < a.B) ? a.Xs[(size_t)b * sn + g] : 0.0f; }
+    // (no barrier here: the table is first read behind the barrier of round 0)
+    const unsigned rowbytes = (unsigned)a.n;
+    constexpr unsigned kOOB = 0x80000000u;
+    const unsigned s_rows = (TWO ? 2u : 1u) * (unsigned)a.rows;
+    const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.W), 0, (int)(s_rows * rowbytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rX = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.Xq), 0, (int)((unsigned)a.B * rowbytes), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rS = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.sWT), 0, (int)(s_rows * (unsigned)sn * 4), 0x00020000);
+    unsigned woff[NB], soff[NB];
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+        const int row = r0 + (TWO ? 0 : 16 * j) + l15;
+        const unsigned wrow = (unsigned)(TWO ? j * a.rows + row : row);
+        woff[j] = row < a.rows ? wrow * rowbytes + (unsigned)q * 16 : kOOB;
+        soff[j] = row < a.rows ? wrow * 4 : kOOB;
+    }
+    const unsigned xoff = l15 < a.B ? (unsigned)l15 * rowbytes + (unsigned)q * 16 : kOOB;
+    const unsigned sstep = s_rows * 4;
+    v4u wr[D][NB], xr[D]; unsigned sr[D][NB];
+    auto fetch = [&](const int slot, const int g) {                       // group g -> ring slot `slot`
+        const bool in = g < sn;
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            wr[slot][j] = __builtin_amdgcn_raw_buffer_load_b128(rW, (int)(in && woff[j] != kOOB ? woff[j] + (unsigned)g * kGroup : kOOB), 0, 0);
+            sr[slot][j] = __builtin_amdgcn_raw_buffer_load_b32(rS, (int)(in && soff[j] != kOOB ? soff[j] + (unsigned)g * sstep : kOOB), 0, 0);
+        }
+        xr[slot] = __builtin_amdgcn_raw_buffer_load_b128(rX, (int)(in && xoff != kOOB ? xoff + (unsigned)g * kGroup : kOOB), 0, 0);
+    };
+    // producer: token 4 q + i of this wave's group -> word pofs[i] of the group's block; consumer: (token 4 wave + q, row l15) -> word cofs
+    int pofs[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) pofs[i] = (4 * q + (i ^ q)) * 16 + l15;
+    const int cofs = (4 * wave + (q ^ wave)) * 16 + l15, ctok = 4 * wave + q;
+    float acc[NB];
+#pragma unroll
+    for (int j = 0; j < NB; ++j) acc[j] = 0.f;
+#pragma unroll
+    for (int k = 0; k < D; ++k) fetch(k, k * W + wave);
+    for (int rb = 0; rb < rounds; rb += D) {
+#pragma unroll
+        for (int k = 0; k < D; ++k) {
+            const int r = rb + k;
+            if (r >= rounds) break;                                         // (a condition on n alone: every wave of every workgroup takes it alike)
+            int* const dots = ring + (k & 1) * SLOT;
+            float* const sws = reinterpret_cast<float*>(dots + W * NB * 256);
+#pragma unroll
+            for (int j = 0; j < NB; ++j) {                                  // group r W + wave (past the end in the last round: zero operands, a zero scale)
+                const v4i z = {0, 0, 0, 0};
+                const v4i d = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(v4i, xr[k]), __builtin_bit_cast(v4i, wr[k][j]), z, 0, 0, 0);
+                int* const blk = dots + (wave * NB + j) * 256;
+                blk[pofs[0]] = d[0]; blk[pofs[1]] = d[1]; blk[pofs[2]] = d[2]; blk[pofs[3]] = d[3];
+                if (q == 0) sws[(wave * NB + j) * 16 + l15] = __uint_as_float(sr[k][j]);
+            }
+            fetch(k, (r + D) * W + wave);
+            __syncthreads();
+#pragma unroll
+            for (int u = 0; u < W; ++u) {                                   // the round's W groups, ascending
+                const float sx = sxl[(r * W + u) * kSkinnyTokens + ctok];
+#pragma unroll
+                for (int j = 0; j < NB; ++j) {
+                    const int d = dots[(u * NB + j) * 256 + cofs];
+                    const float sw = sws[(u * NB + j) * 16 + l15];
+                    acc[j] = __fmaf_rn(__fmul_rn(sw, sx), (float)d, acc[j]);   // quant_operators.cpp:274
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NB; ++j) fin[j * 256 + ctok * 16 + l15] = acc[j];
+    __syncthreads();
+    if (wave != 0) return;
+    float out[NB][4];
+#pragma unroll
+    for (int j = 0; j < NB; ++j)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) out[j][i] = fin[j * 256 + (4 * q + i) * 16 + l15];
+    skinny_epilogue<EPI, NB>(a, out, r0 + l15, lane);
+}
+
+// ------------------------------------------------------------------------------------------
 // The skinny W4A8 GEMM: k_gemm_q8_skinny's contract (tokens = A, weight rows = B of v_mfma_i32_16x16x64_i8, C/D col = lane & 15 = the weight row, row = 4 (lane >> 4)
 // + reg = the token, one wave per workgroup, activation scales [groups][16] in LDS, the chain step and skinny_epilogue unchanged) on a matrix in the DEVICE nibble layout
 // (flm_gemv4.h) -- a.W is [rows][n / 2] packed bytes, nothing is unpacked to memory.

@@ -78,6 +78,20 @@ int launch_gemm_skinny(flm_ctx* c, hipStream_t st, const GemmArgs& g, int force_
     HIPC(c, hipGetLastError());
     return FLM_OK;
 }
+// The split-K skinny int8 GEMM ("spec_gemm" 2, flm_prefill.h k_gemm_q8_skinny_sk): the same refusals, the same grid and the same fragments-per-workgroup rule as above, four
+// waves per workgroup.  Its LDS holds the activation-scale table AND the waves' product ring, so the row-length bound is on both together (46080 elements: 19 KiB of ring at NB = 2).
+template <int EPI>
+int launch_gemm_skinny_sk(flm_ctx* c, hipStream_t st, const GemmArgs& g, int force_nb = 0) {
+    if (g.B < 1 || g.B > kSkinnyTokens || g.n_peer) return fail(c, FLM_ERR_INVALID, "skinny gemm: 1 .. 16 tokens, one GPU");
+    if ((double)g.rows * g.n * (EPI == EPI_SWIGLU ? 2 : 1) >= 2147483648.0 || g.n > 65536 || skinny_sk_lds_bytes(g.n, 2) > 64 * 1024)
+        return fail(c, FLM_ERR_UNSUPPORTED, "split-K skinny gemm: matrix of 2 GiB or more, or rows too long for the scale table and the product ring in 64 KiB of LDS");
+    const int cus = c ? c->cu_count : 256;
+    if constexpr (EPI == EPI_SWIGLU) hipLaunchKernelGGL((k_gemm_q8_skinny_sk<EPI_SWIGLU, 2>), dim3((g.rows + 15) / 16), dim3(256), skinny_sk_lds_bytes(g.n, 2), st, g);
+    else if (force_nb == 2 || (force_nb == 0 && (g.rows + 31) / 32 >= cus)) hipLaunchKernelGGL((k_gemm_q8_skinny_sk<EPI, 2>), dim3((g.rows + 31) / 32), dim3(256), skinny_sk_lds_bytes(g.n, 2), st, g);
+    else hipLaunchKernelGGL((k_gemm_q8_skinny_sk<EPI, 1>), dim3((g.rows + 15) / 16), dim3(256), skinny_sk_lds_bytes(g.n, 1), st, g);
+    HIPC(c, hipGetLastError());
+    return FLM_OK;
+}
 // The skinny W4A8 GEMM (flm_prefill.h k_gemm_q4_skinny): the same refusals and the same split as above, on a PACKED matrix in the device nibble layout -- g.W is
 // [rows][n / 2] bytes and the 2 GiB bound of the buffer descriptor is on those.  Fragments per wave, measured at the 7B shape with the choice forced either way (DESIGN.md
 // section 5o): one while the one-wave workgroups are no more than the SIMDs (Wo, W2: 256; QKV: 768 -- 17.6 us against 20.8 with two), two beyond (the classifier: 29.7 us
@@ -129,14 +143,16 @@ int launch_gemm_w4(flm_ctx* c, hipStream_t st, const GemmArgs& g, int use_mfma) 
     return FLM_OK;
 }
 // which GEMM family a pass's weight pointers belong to: pass_weights / pass_classifier decide it together with the pointers (flm_query "pass_gemm" reports the values)
-enum GemmKind { GEMM_TILES = 0, GEMM_SKINNY8, GEMM_SKINNY4, GEMM_TILES4, GEMM_SKINNY16 };
-// one GEMM of the batched path: the tiles, or -- the verify pass under "spec_gemm" 1 -- the skinny kernel, each of the weights' type (int8 / int16 bytes | packed nibbles)
+enum GemmKind { GEMM_TILES = 0, GEMM_SKINNY8, GEMM_SKINNY4, GEMM_TILES4, GEMM_SKINNY16, GEMM_SKINNY8_SK };
+// one GEMM of the batched path: the tiles, or -- the verify pass under "spec_gemm" 1 -- the skinny kernel, each of the weights' type (int8 / int16 bytes | packed nibbles),
+// or -- int8 weights under "spec_gemm" 2 -- the split-K skinny kernel
 template <int QT, int EPI>
 int launch_gemm_any(flm_ctx* c, hipStream_t st, const GemmArgs& g, int use_mfma, GemmKind kind) {
     if constexpr (QT == QT_INT8) {
         if (kind == GEMM_TILES4) return launch_gemm_w4<EPI>(c, st, g, use_mfma);
         if (kind == GEMM_SKINNY4) return launch_gemm_skinny_w4<EPI>(c, st, g);
         if (kind == GEMM_SKINNY8) return launch_gemm_skinny<EPI>(c, st, g);
+        if (kind == GEMM_SKINNY8_SK) return launch_gemm_skinny_sk<EPI>(c, st, g);
     } else if (kind == GEMM_SKINNY16) return launch_gemm_skinny_w16<EPI>(c, st, g);
     return launch_gemm<QT, EPI>(c, st, g, use_mfma);
 }
@@ -295,7 +311,7 @@ int launch_rope_kv_segs(flm_ctx* c, hipStream_t st, const float* qkv, float* qou
 static inline bool tiles_int8(const flm_ctx* c) { return c->d.quant_type != FLM_QT_INT16; }
 static inline GemmKind pass_kind(const flm_ctx* c, bool skinny) {
     const bool w4 = c->d.quant_type == FLM_QT_INT4, w16 = c->d.quant_type == FLM_QT_INT16;
-    return skinny ? (w4 ? GEMM_SKINNY4 : w16 ? GEMM_SKINNY16 : GEMM_SKINNY8) : (w4 ? GEMM_TILES4 : GEMM_TILES);
+    return skinny ? (w4 ? GEMM_SKINNY4 : w16 ? GEMM_SKINNY16 : c->spec_gemm == 2 ? GEMM_SKINNY8_SK : GEMM_SKINNY8) : (w4 ? GEMM_TILES4 : GEMM_TILES);   // ("spec_gemm" 2: split-K, int8 weights only)
 }
 // the ONE place a pass picks layer l's weight pointers and the GEMM family that reads them
 static int pass_weights(flm_ctx* c, int l, bool skinny, LayerW& w, GemmKind& kind) {
@@ -494,8 +510,9 @@ int prefill_batched_qt(flm_ctx* c, int B, int pos, bool all_layers, bool skinny,
             return fail(c, FLM_ERR_INVALID, "prefill: a batch row outside its slot, or a slot outside the cache");
     return tiles_int8(c) ? prefill_batched<QT_INT8>(c, B, pos, all_layers, skinny, fan, row0, slots_in, nullptr, pfx) : prefill_batched<QT_INT16>(c, B, pos, all_layers, skinny, fan, row0, slots_in, nullptr, pfx);
 }
-int launch_gemm_skinny_store(flm_ctx* c, hipStream_t st, int qt, const GemmArgs& g, int force_nb) {
+int launch_gemm_skinny_store(flm_ctx* c, hipStream_t st, int qt, const GemmArgs& g, int force_nb, bool splitk) {
     if (qt == FLM_QT_INT4) return launch_gemm_skinny_w4<EPI_STORE>(c, st, g, force_nb);
+    if (splitk && qt == FLM_QT_INT8) return launch_gemm_skinny_sk<EPI_STORE>(c, st, g, force_nb);
     return qt == FLM_QT_INT16 ? launch_gemm_skinny_w16<EPI_STORE>(c, st, g, force_nb) : launch_gemm_skinny<EPI_STORE>(c, st, g, force_nb);
 }
 

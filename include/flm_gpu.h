@@ -206,7 +206,9 @@ int  flm_score_tokens(flm_ctx* ctx, const int32_t* tokens, int n, int pos,
  * The weight pass: option "spec_gemm" 1 = int8, int4 and int16 models run every GEMM of the batch through the skinny kernel (v_mfma_i32_16x16x64_i8, 16 tokens x 16 rows x one quant group per
  * instruction, weights from global memory straight into the operand registers, one wave per 16 or 32 rows so that every matrix of the 7B shape fills 256 CUs); 0 = the 64 x 64
  * tiles of the prompt path (int4: both kernels read the packed nibbles -- the tiles a 16-byte LDS read per lane and group, the skinny kernel an 8-byte load; int16: the skinny kernel
- * splits a lane's 32 bytes into low and high byte planes in registers, four MFMAs per group as in the hi / lo-plane tiles). */
+ * splits a lane's 32 bytes into low and high byte planes in registers, four MFMAs per group as in the hi / lo-plane tiles); 2 = as 1, and int8 models run the split-K form
+ * of the skinny kernel: four waves per workgroup on the same rows, each on every fourth quant group, the exact group dots handed through LDS to the ordered chains -- the
+ * same bits (int4 and int16 models: exactly what 1 runs).  Other values: FLM_ERR_INVALID. */
 int  flm_verify_greedy(flm_ctx* ctx, int32_t first_token, const int32_t* drafts, int k, int pos,
                        int32_t* out_tokens /* [k + 1] */, int* n_out);
 /* Tree draft-and-verify, greedy: flm_verify_greedy with the batch's rows a TREE of candidates, for callers whose drafter has several continuations to offer.  tokens[0] is the
@@ -460,7 +462,8 @@ int  flm_fan_keep(flm_ctx* ctx, int seq);
  *   the callbacks come in (pass, slot) order -- with a bounded budget a slot can deliver its token 1 before a later slot delivers its token 0.
  *   flm_query "batch_passes": the weight passes (joins, steps, passes) since the last flm_batch_open.
  *   flm_query "pass_gemm" (read-only): the kernel family of the layer GEMMs of the context's most recent batched pass of any entry point (prompt, score, verify, tree, fan,
- *   join, step, pass; flm_prepare's self-check is one) -- 0 tiles on int8 / int16 bytes, 1 skinny int8, 2 skinny nibbles, 3 nibble tiles, 4 skinny int16; -1 before the first. */
+ *   join, step, pass; flm_prepare's self-check is one) -- 0 tiles on int8 / int16 bytes, 1 skinny int8, 2 skinny nibbles, 3 nibble tiles, 4 skinny int16,
+ *   5 split-K skinny int8 ("spec_gemm" 2); -1 before the first. */
 #define FLM_BATCH_MAX 16
 typedef struct flm_batch_layout { int32_t n_slots; int32_t base[FLM_BATCH_MAX], rows[FLM_BATCH_MAX]; } flm_batch_layout;
 typedef struct flm_batch_req { const int32_t* prompt; int32_t n_prompt, max_tokens; float temperature, topp;
@@ -711,7 +714,8 @@ int  flm_debug_read(flm_ctx* ctx, int what, int layer, float* out, size_t n);
  *                    of the history whose continuations differ and merges them by common prefix, breadth first, into draft_len + 1 nodes on the device -- and verifies it
  *                    with flm_verify_tree_greedy's pass.  Ids, count, stop behaviour and final cache stay flm_generate's.  Every other form ignores the option.
  *   "spec_gemm"      1 = flm_verify_greedy / flm_generate_lookup and their sampled forms run the verify batch's int8 / int4 / int16 GEMMs on the skinny kernel for <= 16 rows (default 0: the prompt path's 64 x 64
- *                    tiles, until both forms have been timed on the device: DESIGN.md section 5e); the same bits; no other entry point looks at it
+ *                    tiles, until both forms have been timed on the device: DESIGN.md section 5e); 2 = the same, int8 weights on the split-K skinny kernel (four waves per
+ *                    workgroup; int4 / int16: as 1); the same bits; other values FLM_ERR_INVALID; no other entry point looks at it
  *   "batch_rows"     b >= 0 = flm_generate_batch admits every request and runs ragged passes with a budget of b prompt rows each (0: no bound); default -1: serial joins, then
  *                    steps; the same results; read per call
  *   "use_prefill_mq" 0 = batched attention with one query per workgroup (default 1: eight)
@@ -776,7 +780,7 @@ int  flm_op_matmul_q(int qt, float* out, const void* mat1, const float* scales1,
                      const void* mat2, const float* scales2, int m, int n, int w, int gs);
 /* the same product for 1 <= w <= 16 batch rows through the skinny kernels of the verify pass: FLM_QT_INT8 (k_gemm_q8_skinny) and FLM_QT_INT4
  * (k_gemm_q4_skinny: mat1 = [m][n / 2] nibbles in the interchange order, repacked as an upload does; mat2 int8); FLM_QT_INT16: FLM_ERR_UNSUPPORTED
- * (FLM_OP_SKINNY_NB=1|2: 16-row fragments per wave; by size otherwise) */
+ * (FLM_OP_SKINNY_NB=1|2: 16-row fragments per wave; by size otherwise.  FLM_OP_SKINNY_SPLITK=1: FLM_QT_INT8 through the split-K kernel k_gemm_q8_skinny_sk) */
 int  flm_op_matmul_skinny(int qt, float* out, const void* mat1, const float* scales1,
                           const void* mat2, const float* scales2, int m, int n, int w, int gs);
 /* the prompt-lookup drafter of flm_generate_lookup (k_spec_draft) on a caller-supplied history h[n]: d[k], 1 <= k <= 15, 1 <= ngram_max <= 8 */

@@ -4,8 +4,9 @@ decode_greedy over 128 steps for INT4, INT8 per phase and INT8 default (one laun
 python tools/w4_bench.py [reps] [layers]   -- prints the tables and one JSON line
 
 python tools/w4_bench.py --verify [reps] [layers]   -- the passes of up to 16 rows instead: the time of one flm_verify_greedy pass at B = 5, 8 and 16 rows (position 20) and
-the time per step of flm_generate_batch with 16 slots, for an INT4 context under "spec_gemm" 1 and 0 and an INT8 context under "spec_gemm" 1, the three alternating,
-medians of `reps` with min .. max.  FLM_GPU_LIB picks the library (capi.py): under the build of the commit before k_gemm_q4_skinny the first row is unpack + int8 skinny.
+the time per step of flm_generate_batch with 16 slots, for an INT4 context under "spec_gemm" 1 and 0 and an INT8 context under "spec_gemm" 1 and 2 (the split-K skinny
+kernel), the four alternating, medians of `reps` with min .. max.  FLM_GPU_LIB picks the library (capi.py): under the build of the commit before k_gemm_q4_skinny the first
+row is unpack + int8 skinny, under the build of the commit before k_gemm_q8_skinny_sk the last row is "spec_gemm" 1 once more.
 --type int16 (with --verify): the same table for an INT16 context in place of the INT4 one -- k_gemm_q16_skinny under "spec_gemm" 1, the hi / lo-plane tiles under 0; under
 the build of the commit before k_gemm_q16_skinny both rows are the tiles.
 
@@ -51,7 +52,7 @@ def verify_bench():
     CALLS, SLOTS, SHORT, LONG = 20, 16, 9, 41
     runs = {}
     wqt = {"int4": capi.QT_INT4, "int16": ff.QT_INT16}[wtype]
-    for name, qt, gemm in ((f"{wtype} spec_gemm 1", wqt, 1), (f"{wtype} spec_gemm 0", wqt, 0), ("int8 spec_gemm 1", ff.QT_INT8, 1)):
+    for name, qt, gemm in ((f"{wtype} spec_gemm 1", wqt, 1), (f"{wtype} spec_gemm 0", wqt, 0), ("int8 spec_gemm 1", ff.QT_INT8, 1), ("int8 spec_gemm 2", ff.QT_INT8, 2)):
         runs[name] = context(qt, False); runs[name].set_option("spec_gemm", gemm)
     prompt = (np.arange(POS, dtype=np.int32) * 7 + 1) % 1000
     reqs = lambda n: [capi.BatchReq((np.arange(4, dtype=np.int32) + 11 * s) % 1000 + 1, n) for s in range(SLOTS)]   # noqa: E731
